@@ -9,6 +9,7 @@ the rate with the frames left sharded in the ranks' HBM is printed beside it (`s
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode primary|primary_shadow|full]
                     [--map dragon|monu9|nature|terrain|terrain_full|room] [--width 1920 --height 1080] [--variant V]
+                    [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no torchrun environment starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, before this process touches the
@@ -30,6 +31,11 @@ full extent and as the window the texel format holds, nature 4K + shadow rays), 
 and the reference's translucent room, each timed the same way (pre-roll, W warm-up, K timed frames, hipEvent pairs on the
 kernel) and checked against the oracle's golden hashes, and config 1's CPU ray cast (the host library's octree_ray_cast,
 256 x 256). `--no-configs` leaves them out (profiling runs of the headline kernel).
+
+`--dump-outputs DIR` writes the frame the headline region's last timed step delivered (rank 0) as DIR/rgba.npy (float32,
+[H, W, 4] colour bytes) and DIR/id_dist.npy ([H, W, 2] voxelID, dist; float32 where every value is exact in it, else
+float64), so that two builds can be compared output for output; above DUMP_BUDGET bytes the same fixed, seeded sample of
+pixels is written instead, flattened, with its row-major pixel indices in DIR/pixel_index.npy.
 """
 import argparse
 import json
@@ -66,6 +72,7 @@ CONFIGS = [
     ("room_inside_1080p_full_path_tracer", "room", 1920, 1080, "full"),
 ]
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BUDGET = 64_000_000   # bytes of array data --dump-outputs may write
 KERNEL_SAMPLES = 16    # launches of the timed region that carry a hipEvent pair (every max(2, steps // 16)-th: >= 10 of 20)
 
 
@@ -118,6 +125,8 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the measured path); gloo only rehearses the N>1 code path on a "
                          "box whose ranks share one GPU (collective staged through host memory)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the headline region's last timed step to DIR/*.npy (see the module docstring)")
     ap.add_argument("--dry-plan", action="store_true",
                     help="no GPU work: start/join the ranks exactly as a real run does, build each rank's shard plan, check "
                          "it across ranks (with --backend gloo through a real process group) and print the plan as JSON")
@@ -223,6 +232,27 @@ def cpu_baseline(args, tex, dim, cam, budget_s=10.0):
     out["row_parallel"] = {"value": round(sum(done) / dt_mt / 1e6, 3), "unit": "Mrays/s", "cores": T,
                            "sample": f"{sum(done)} rays in {dt_mt:.1f} s on {T} threads (every core open to the process)"}
     return out
+
+
+def dump_outputs(out_dir, rgba_host, id_host, seed=0):
+    """rgba_host [H, W, 4] uint8, id_host [H, W, 2] int32 -> out_dir/rgba.npy (float32) and out_dir/id_dist.npy (float32 when
+    every value is exact in it, float64 otherwise): whole frames while they fit DUMP_BUDGET, else a seeded sample of pixels
+    (a function of the frame size only) with its row-major indices in out_dir/pixel_index.npy"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rgba = rgba_host.astype(np.float32)
+    exact32 = id_host.size == 0 or int(np.abs(id_host.astype(np.int64)).max()) <= 1 << 24
+    idd = id_host.astype(np.float32 if exact32 else np.float64)
+    n_pix = rgba.shape[0] * rgba.shape[1]
+    per_pixel = rgba.itemsize * 4 + idd.itemsize * 2
+    budget = DUMP_BUDGET - 3 * 4096   # room for the .npy headers
+    if n_pix * per_pixel > budget:
+        n = budget // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(seed).permutation(n_pix)[:n])
+        rgba, idd = rgba.reshape(n_pix, 4)[idx], idd.reshape(n_pix, 2)[idx]
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "rgba.npy"), rgba)
+    np.save(os.path.join(out_dir, "id_dist.npy"), idd)
 
 
 def load_world(V, name):
@@ -582,6 +612,9 @@ def main():
                 "what": "the same W warm-up + K timed frames as the process's first GPU work, no untimed frames before them"}
         del pipe_c
     elapsed, pipe, kernel_ms = timed_region(gather, not args.no_kernel_events, PREROLL)
+    if args.dump_outputs and rank == 0:   # the frame of the last timed step, before any later region runs
+        d_rgba, d_id = pipe.frame_views()
+        dump_outputs(args.dump_outputs, d_rgba.cpu().numpy().view("uint8").reshape(H, W, 4), d_id.cpu().numpy())
 
     # several GPUs: SURVEY 8(e) asks for the rate with AND without the per-frame gather: the other mode, same K frames
     other = None

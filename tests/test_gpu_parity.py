@@ -585,7 +585,9 @@ def test_full_path_tracer_without_a_stack_for_opaque_scenes(V, O, golden, produc
             for s_ in range(n_shards):
                 rows = V.shard_rows(H, 5, s_, n_shards)
                 bufs.append((torch.zeros(rows * W, dtype=torch.int32, device="cuda"), torch.zeros(rows * W * 2, dtype=torch.int32, device="cuda")))
-                c.dispatch_shard(W, H, 5, s_, n_shards, 2, bufs[-1][0].data_ptr(), bufs[-1][1].data_ptr(), streams[s_ & 1].cuda_stream)
+            torch.cuda.synchronize()   # the zero fills run on the default stream: done before the side streams write
+            for s_ in range(n_shards):
+                c.dispatch_shard(W, H, 5, s_, n_shards, 2, bufs[s_][0].data_ptr(), bufs[s_][1].data_ptr(), streams[s_ & 1].cuda_stream)
             torch.cuda.synchronize()
             for s_ in range(n_shards):
                 rows = V.shard_row_indices(H, 5, s_, n_shards)
