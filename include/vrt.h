@@ -125,6 +125,50 @@ int vrt_compact(vrt_ctx *ctx);
  * tex_dim must still be ceil(cbrt(_octree_texel_size(tree))): it feeds the voxelID output. */
 int vrt_upload_records(vrt_ctx *ctx, const uint32_t *records, size_t n_records, uint32_t tex_dim);
 
+/* EXTENSION: the world questions of the reference's frame loop, answered on the device from the uploaded tree (after
+ * patches and compaction, whatever the scene form) instead of a host copy kept in step with it.
+ *   vrt_cast_rays     octree_ray_cast (src/octree.cpp:364-485) as src/main.cpp:822-829 picks the voxel under the
+ *                     crosshair, plus get_placement_coord (src/main.cpp:315-360), the cell a build click fills (:864)
+ *   vrt_find_voxels   octree_find (src/octree.cpp:102-130) as isVoxelSolid / checkCollision ask it (src/main.cpp:100-125)
+ * The answers are the reference's functions, bit for bit, on the pointer tree the device tree was made from with ONE
+ * difference the device tree cannot express: a leaf whose record words are 0/0 (colour 0, zero material) is empty space
+ * there. Such leaves are the phantom voxels of SURVEY F3 (coord.y = MIN_HEIGHT: never hit anyway) and the "ghost" volumes
+ * the F1 split makes of them -- a phantom whose lbb has x = z = 0 is split as a volume, its children get coord = their
+ * lbb, and the reference's ray cast and octree_find DO hit those (invisible: alpha 0; 38 leaves in dragon.vox, 682 in
+ * nature.vox) -- plus any voxel inserted with colour 0 and zero material. The queries answer as the reference does on
+ * the tree with those leaves' has_voxel cleared (csrc/vrt_query.hip.h). World bounds of vrt_params must be the tree's
+ * root cube (the reference: [-1023, 1024)^3 both, src/main.cpp:478-480). coord is the hit node's minimum corner, which
+ * voxel.coord is for every other leaf octree_insert / octree_remove make. Leaf words are the records
+ * vrth_world_records() emits, refraction byte 0 under alpha 0 (the layouts keep no other). VRT_E_STATE before any upload and while a patch batch is open; NULL buffers with
+ * n > 0 are VRT_E_INVALID; n == 0 does nothing. At most 2^31 rays / points per call. */
+typedef struct vrt_ray_hit {
+    int32_t hit;        /* 1: octree_ray_cast returned a node, 0: NULL                                              */
+    int32_t coord[3];   /* node->voxel.coord of the returned node (src/main.cpp:831); -1,-1,-1 on a miss            */
+    int32_t place[3];   /* get_placement_coord(origin, dir, coord) (src/main.cpp:315-360); -1,-1,-1 on a miss       */
+    uint32_t leaf[2];   /* the hit leaf's device record words: RGBA, refr | illum << 8 | k << 16; 0 on a miss       */
+    int32_t steps;      /* loop iterations begun (<= 512): for tests and tuning                                     */
+} vrt_ray_hit;          /* 40 bytes */
+/* n rays: origins n x 3 floats (origin_stride 3), or ONE origin shared by all rays (origin_stride 0: config 1, picking);
+ * dirs n x 3, used as given (the reference does not normalise them); box_min / box_max = octree_ray_cast's worldMin /
+ * worldMax (the reference passes 0..1024), truncated to int as the reference does. The same origin feeds the placement
+ * (the reference passes camera.Position there and Position * voxelScale to the cast: equal at its voxelScale 1).
+ * HOST buffers, synchronous (copied through device buffers the context keeps). As for frames, page-locked host buffers
+ * (vrt_host_alloc) make the copies faster: from pageable memory the runtime stages them, and at 1 M rays the copies
+ * are most of the call. */
+int vrt_cast_rays(vrt_ctx *ctx, size_t n, const float *origins, int origin_stride, const float *dirs, const float box_min[3],
+                  const float box_max[3], vrt_ray_hit *out);
+/* The same on DEVICE buffers (d_out: n vrt_ray_hit), enqueued on `stream` (NULL: the context's) -- ordered after the
+ * patches and frames enqueued before it on that stream; returns after enqueueing. */
+int vrt_cast_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int origin_stride, const void *d_dirs,
+                         const float box_min[3], const float box_max[3], void *d_out, void *stream);
+/* octree_find for n integer points (n x 3 int32): out n x 3 uint32 = {present, leaf word 0, leaf word 1}. present is
+ * isVoxelSolid's v.coord.y > MIN_HEIGHT, with octree_find's own equality (vmm's ivec3_equal_vec: x and z equal, both y
+ * non-zero -- SURVEY F1): inside a merged volume only the column of its corner, and no point with y == 0, is found; and
+ * with octree_find's own child choice at (lbb + rtf) / 2, which differs from the tree's split lo + (hi - lo) / 2 where
+ * lo + hi is odd and negative: a voxel on the planes -512, -768, -896, ... of the reference's world is not found.
+ * The words are 0 when present is 0. HOST buffers, synchronous. */
+int vrt_find_voxels(vrt_ctx *ctx, size_t n, const int32_t *coords, uint32_t *out);
+
 /* Column-major mat4 x2 + vec4, exactly the std140 Camera block (comp:17-21). */
 int vrt_set_camera(vrt_ctx *ctx, const float inv_projection[16], const float inv_view[16],
                    const float camera_pos[4]);

@@ -57,6 +57,62 @@ class SceneInfo(C.Structure):
                 ("lds_records", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RayHit(C.Structure):
+    """vrt_ray_hit: one answer of vrt_cast_rays (40 bytes)"""
+    _fields_ = [("hit", C.c_int32), ("coord", C.c_int32 * 3), ("place", C.c_int32 * 3), ("leaf", C.c_uint32 * 2),
+                ("steps", C.c_int32)]
+
+
+# the same record as a numpy dtype, for arrays of answers
+RAY_HIT_DTYPE = np.dtype([("hit", np.int32), ("coord", np.int32, 3), ("place", np.int32, 3), ("leaf", np.uint32, 2),
+                          ("steps", np.int32)])
+WORLD_BOX = ((0.0, 0.0, 0.0), (1024.0, 1024.0, 1024.0))   # the box src/main.cpp:827 passes to octree_ray_cast
+
+
+def _real_array(a, what):
+    a = np.asarray(a)
+    if a.dtype.kind not in "fiu":
+        raise TypeError(f"{what}: expected real numbers, got dtype {a.dtype}")
+    return a
+
+
+def query_ray_args(origins, dirs, box=WORLD_BOX):
+    """Checks and converts the arguments of Context.cast_rays (no device involved) -> (origins float32[k, 3] with k = 1
+    (shared origin) or n, origin_stride 0 or 3, dirs float32[n, 3], box_min float32[3], box_max float32[3])."""
+    o = _real_array(origins, "origins")
+    d = _real_array(dirs, "dirs")
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError(f"dirs: expected shape (n, 3), got {d.shape}")
+    if o.shape == (3,):
+        stride = 0
+        o = o.reshape(1, 3)
+    elif o.ndim == 2 and o.shape[1] == 3 and o.shape[0] == d.shape[0]:
+        stride = 3
+    else:
+        raise ValueError(f"origins: expected shape (3,) or ({d.shape[0]}, 3), got {o.shape}")
+    if d.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2^31 rays per call")
+    b = _real_array(box, "box")
+    if b.shape != (2, 3):
+        raise ValueError(f"box: expected ((x, y, z), (x, y, z)), got shape {b.shape}")
+    return (np.ascontiguousarray(o, np.float32), stride, np.ascontiguousarray(d, np.float32),
+            np.ascontiguousarray(b[0], np.float32), np.ascontiguousarray(b[1], np.float32))
+
+
+def query_point_args(coords):
+    """Checks and converts the argument of Context.find_voxels (no device involved) -> int32[n, 3]."""
+    c = np.asarray(coords)
+    if c.dtype.kind not in "iu":
+        raise TypeError(f"coords: expected integers, got dtype {c.dtype}")
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError(f"coords: expected shape (n, 3), got {c.shape}")
+    if c.size and (c.min() < -2 ** 31 or c.max() >= 2 ** 31):
+        raise ValueError("coords: values outside int32")
+    if c.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2^31 points per call")
+    return np.ascontiguousarray(c, np.int32)
+
+
 _host = None
 _hip = None
 
@@ -188,6 +244,10 @@ def hip_lib():
         L.vrt_multi_stream.restype = C.c_void_p
         L.vrt_multi_stream.argtypes = [C.c_void_p]
         L.vrt_version.restype = C.c_char_p
+        L.vrt_cast_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_cast_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         if hasattr(L, "vrt_ab_set_full_split"):   # `make AB=1` builds only
             L.vrt_ab_set_full_split.argtypes = [C.c_void_p, C.c_int]
             L.vrt_ab_set_bounce.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -652,6 +712,42 @@ class Context:
         if n < 0:
             self._chk(n)
         return np.array(ms[:n], np.float32)
+
+    def cast_rays(self, origins, dirs, box=WORLD_BOX):
+        """octree_ray_cast + get_placement_coord on the device tree (vrt_cast_rays). origins: (n, 3), or (3,) shared by
+        all rays; dirs: (n, 3); box: the worldMin / worldMax pair. -> (hit bool[n], coord int32[n, 3], place int32[n, 3],
+        leaf uint32[n, 2], steps int32[n]); coord and place are -1 where nothing is hit."""
+        o, stride, d, bmin, bmax = query_ray_args(origins, dirs, box)
+        n = d.shape[0]
+        out = np.zeros(n, RAY_HIT_DTYPE)
+        L = self._L
+        self._chk(L.vrt_cast_rays(self._h, n, o.ctypes.data if n else None, stride, d.ctypes.data if n else None,
+                                  bmin.ctypes.data, bmax.ctypes.data, out.ctypes.data if n else None))
+        return out["hit"] != 0, out["coord"].copy(), out["place"].copy(), out["leaf"].copy(), out["steps"].copy()
+
+    def cast_rays_device(self, n, d_origins, origin_stride, d_dirs, d_out, box=WORLD_BOX, stream=None):
+        """vrt_cast_rays_device: DEVICE buffers (d_out receives n vrt_ray_hit, RAY_HIT_DTYPE), enqueued on `stream`"""
+        b = _real_array(box, "box")
+        if b.shape != (2, 3):
+            raise ValueError(f"box: expected ((x, y, z), (x, y, z)), got shape {b.shape}")
+        b = np.ascontiguousarray(b, np.float32)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 31:
+            raise ValueError(f"n: expected an integer in [0, 2^31), got {n!r}")
+        if origin_stride not in (0, 3):
+            raise ValueError(f"origin_stride: expected 0 (one shared origin) or 3, got {origin_stride!r}")
+        L = self._L
+        self._chk(L.vrt_cast_rays_device(self._h, n, d_origins, origin_stride, d_dirs, b[0].ctypes.data, b[1].ctypes.data,
+                                         d_out, stream))
+
+    def find_voxels(self, coords):
+        """octree_find as isVoxelSolid reads it, on the device tree (vrt_find_voxels). coords: int (n, 3)
+        -> (present bool[n], leaf uint32[n, 2])."""
+        c = query_point_args(coords)
+        n = c.shape[0]
+        out = np.zeros((n, 3), np.uint32)
+        L = self._L
+        self._chk(L.vrt_find_voxels(self._h, n, c.ctypes.data if n else None, out.ctypes.data if n else None))
+        return out[:, 0] != 0, out[:, 1:].copy()
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -5,6 +5,7 @@
 //   vrt_dispatch.cpp   enqueue(): kernel arguments, variant choice, feedback scheduling, ray tables; the vrt_dispatch* entry points
 //   vrt_display.cpp    the display pass and the fused frame call
 //   vrt_patch.cpp      edits without re-upload: patch plan / apply / batches / compaction
+//   vrt_query.cpp      world queries on the device tree: ray casts (picking), voxel lookups
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts)
@@ -106,6 +107,9 @@ struct vrt_ctx {
     void *d_id = nullptr;
     void *d_shown = nullptr;
     size_t scratch_pixels = 0;
+    // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
+    void *d_query = nullptr;
+    size_t query_bytes = 0;
     // edits collected between vrt_patch_begin and vrt_patch_end: applied to the host structures at once, sent to the
     // device together
     struct PatchBatch {

@@ -2,6 +2,7 @@
 // kernel headers; everything else launches through these functions.
 #pragma once
 #include "vrt_internal.h"
+#include "vrt_query.h"
 
 namespace vrt {
 namespace launch {
@@ -45,6 +46,10 @@ struct Denoise {
 };
 void denoise_tiling(int width, int height, int &tiles_x, int &n_tiles);
 hipError_t denoise(const Denoise &d, int variant, bool whole_groups, hipStream_t s);
+
+// vrt_launch_query.hip: the world queries (vrt_query.hip.h), one lane per ray / point; a carries the scene part of KArgs only
+hipError_t cast_rays(const KArgs &a, const query::RayArgs &q, hipStream_t s);
+hipError_t find_voxels(const KArgs &a, const query::PointArgs &q, hipStream_t s);
 
 #if VRT_AB
 // vrt_launch_ab.hip -- the full path tracer as two kernels with cross-wave repacking (ab/vrt_bounce.hip.h): an experiment that lost

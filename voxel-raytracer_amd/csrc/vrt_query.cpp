@@ -1,0 +1,157 @@
+// vrt_query.cpp -- the world queries of include/vrt.h (vrt_cast_rays, vrt_cast_rays_device, vrt_find_voxels): call-order
+// checks, the scene part of the kernel arguments, and the device buffers the host-buffer forms stage through.
+#include "vrt_internal.h"
+#include "vrt_launch.h"
+
+#include <cstring>
+
+using namespace vrt_internal;
+
+namespace {
+
+int query_state(vrt_ctx *c, const char *what) {
+    if (!c) return VRT_E_INVALID;
+    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no octree uploaded (call vrt_upload_octree first)");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
+    return VRT_OK;
+}
+
+// what the query kernels read of KArgs: the world bounds and the tree in both layouts, wide root 0 as uploaded (no
+// tighter root, no root0_only: those are answers the shader may take and octree_ray_cast may not)
+int scene_args(vrt_ctx *c, vrt::KArgs &a) {
+    const int ra = ensure_analysis(c);
+    if (ra) return ra;
+    std::memset(&a, 0, sizeof a);
+    a.n_views = 1;
+    a.voxel_scale = c->params.voxel_scale;
+    for (int k = 0; k < 3; ++k) {
+        a.wmin[k] = c->params.world_min[k];
+        a.wmax[k] = c->params.world_max[k];
+    }
+    a.tex_dim = (int)c->info.tex_dim;
+    a.nodes = c->d_nodes;
+    a.n_records = c->info.n_records;
+    a.cells = c->d_cells;
+    a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
+    a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
+    for (int k = 0; k < 3; ++k) a.root0_min[k] = a.n_roots ? c->wide.roots[0].origin[k] : 0;
+    a.root_table = c->d_roots;
+    a.root0_node = a.n_roots ? c->wide.roots[0].node : 0u;
+    a.root0_shift = a.n_roots ? c->wide.roots[0].shift : 0;
+    a.root0_only = 0;
+    return VRT_OK;
+}
+
+// ivec3_vec3 (truncation) as the reference's x86-64 build executes it: INT_MIN for NaN and out-of-range values
+float box_plane(float v) {
+    const int i = (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : (int)0x80000000u;
+    return (float)i;
+}
+
+int check_rays(vrt_ctx *c, size_t n, const void *origins, int origin_stride, const void *dirs, const float *box_min,
+               const float *box_max, const void *out, const char *what) {
+    const int r = query_state(c, what);
+    if (r) return r;
+    if (origin_stride != 0 && origin_stride != 3) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": origin_stride must be 0 or 3");
+    if (n > (size_t)0x7fffffff) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": at most 2^31 rays per call");
+    if (n > 0 && (!origins || !dirs || !out)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null buffer");
+    if (n > 0 && (!box_min || !box_max)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null box");
+    return VRT_OK;
+}
+
+int cast(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const float *d_dirs, const float *box_min,
+         const float *box_max, vrt::query::RayHit *d_out, hipStream_t s) {
+    vrt::KArgs a;
+    const int r = scene_args(c, a);
+    if (r) return r;
+    vrt::query::RayArgs q;
+    q.origins = d_origins;
+    q.origin_stride = origin_stride;
+    q.dirs = d_dirs;
+    for (int k = 0; k < 3; ++k) {
+        q.box_lo[k] = box_plane(box_min[k]);
+        q.box_hi[k] = box_plane(box_max[k]);
+    }
+    q.out = d_out;
+    q.n = (uint32_t)n;
+    VRT_HIP(c, vrt::launch::cast_rays(a, q, s));
+    return VRT_OK;
+}
+
+// device buffers behind the host-buffer forms, kept by the context and grown, never shrunk
+int ensure_query_scratch(vrt_ctx *c, size_t bytes) {
+    if (bytes <= c->query_bytes) return VRT_OK;
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_query) VRT_HIP(c, hipFree(c->d_query));
+    c->d_query = nullptr;
+    c->query_bytes = 0;
+    const size_t grown = bytes + bytes / 2;
+    VRT_HIP(c, hipMalloc(&c->d_query, grown));
+    c->query_bytes = grown;
+    return VRT_OK;
+}
+
+inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+}  // namespace
+
+extern "C" {
+
+int vrt_cast_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride, const float *dirs, const float box_min[3],
+                  const float box_max[3], vrt_ray_hit *out) {
+    int r = check_rays(c, n, origins, origin_stride, dirs, box_min, box_max, out, "vrt_cast_rays");
+    if (r || n == 0) return r;
+    static_assert(sizeof(vrt_ray_hit) == sizeof(vrt::query::RayHit), "vrt_ray_hit and the kernel's record differ");
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
+    const size_t out_bytes = n * sizeof(vrt_ray_hit);
+    r = ensure_query_scratch(c, align256(o_bytes) + align256(d_bytes) + out_bytes);
+    if (r) return r;
+    char *base = static_cast<char *>(c->d_query);
+    float *d_o = reinterpret_cast<float *>(base);
+    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
+    auto *d_out = reinterpret_cast<vrt::query::RayHit *>(base + align256(o_bytes) + align256(d_bytes));
+    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
+    r = cast(c, n, d_o, origin_stride, d_d, box_min, box_max, d_out, c->stream);
+    if (r) return r;
+    VRT_HIP(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_cast_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs,
+                         const float box_min[3], const float box_max[3], void *d_out, void *stream) {
+    const int r = check_rays(c, n, d_origins, origin_stride, d_dirs, box_min, box_max, d_out, "vrt_cast_rays_device");
+    if (r || n == 0) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    return cast(c, n, static_cast<const float *>(d_origins), origin_stride, static_cast<const float *>(d_dirs), box_min, box_max,
+                static_cast<vrt::query::RayHit *>(d_out), stream ? (hipStream_t)stream : c->stream);
+}
+
+int vrt_find_voxels(vrt_ctx *c, size_t n, const int32_t *coords, uint32_t *out) {
+    int r = query_state(c, "vrt_find_voxels");
+    if (r) return r;
+    if (n > (size_t)0x7fffffff) return vrt_fail(c, VRT_E_INVALID, "vrt_find_voxels: at most 2^31 points per call");
+    if (n > 0 && (!coords || !out)) return vrt_fail(c, VRT_E_INVALID, "vrt_find_voxels: null buffer");
+    if (n == 0) return VRT_OK;
+    VRT_HIP(c, hipSetDevice(c->device));
+    vrt::KArgs a;
+    r = scene_args(c, a);
+    if (r) return r;
+    const size_t bytes = n * 3 * sizeof(uint32_t);
+    r = ensure_query_scratch(c, 2 * align256(bytes));
+    if (r) return r;
+    char *base = static_cast<char *>(c->d_query);
+    vrt::query::PointArgs q;
+    q.coords = reinterpret_cast<const int32_t *>(base);
+    q.out = reinterpret_cast<uint32_t *>(base + align256(bytes));
+    q.n = (uint32_t)n;
+    VRT_HIP(c, hipMemcpyAsync(base, coords, bytes, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, vrt::launch::find_voxels(a, q, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(out, q.out, bytes, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+}  // extern "C"

@@ -197,6 +197,7 @@ void vrt_destroy(vrt_ctx *c) {
     if (c->d_rgba) (void)hipFree(c->d_rgba);
     if (c->d_id) (void)hipFree(c->d_id);
     if (c->d_shown) (void)hipFree(c->d_shown);
+    if (c->d_query) (void)hipFree(c->d_query);
     for (auto &d : c->defer) {
         (void)hipFree(d.rec);
         (void)hipFree(d.count);
