@@ -169,6 +169,30 @@ int vrt_cast_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int orig
  * The words are 0 when present is 0. HOST buffers, synchronous. */
 int vrt_find_voxels(vrt_ctx *ctx, size_t n, const int32_t *coords, uint32_t *out);
 
+/* Progressive multi-sample accumulation of VRT_MODE_FULL (one per context). Sample k is the VRT_MODE_FULL frame rendered with
+ * initRNG(pixel, k) (shaders/raytracing.comp:380-387; the shader itself passes 0): camera, uniforms, tree and every other
+ * convention unchanged. The accumulation holds the samples first, first + 1, ..., first + n - 1 (sample indices modulo 2^32) as
+ * one integer sum per pixel and channel of the unorm8 bytes each sample would store -- exact, whatever chunks they were added
+ * in -- and resolves to (sum + n / 2) / n per channel, alpha 255: at n = 1 the sample itself. Averaging clamped bytes is what a
+ * display of the successive frames shows. The resolved (voxel ID, dist) image is the frame's: no sample changes it.
+ *
+ * vrt_accum_begin     (re)starts with zero samples; allocates (grows) the accumulation's device buffers.
+ * vrt_accum_add       enqueues n_samples more on the context's stream and stores the new count in *total_out (may be NULL).
+ *                     Restart rule: when the camera block's bytes, the vrt_params bytes (highlighted voxel and bounds
+ *                     included) or the tree (upload, patch apply / batch end, compaction) differ from what the first sample
+ *                     in the sums saw, the sums start again at `first` -- *total_out then shows n_samples. Setting the same
+ *                     values again changes nothing, so "add one sample per frame" converges exactly while nothing moves.
+ *                     VRT_E_INVALID: n_samples == 0, or more than 2^24 samples in all. VRT_E_STATE: no begin, no scene or
+ *                     camera, or a patch batch is open.
+ * vrt_accum_resolve   the resolved rgba8 [H][W][4], id_dist [H][W][2] and the display pass of vrt_denoise on them, into host
+ *                     buffers (any may be NULL); synchronous. VRT_E_STATE: no begin, or no sample yet.
+ * vrt_accum_resolve_device  the same into device buffers, enqueued on `stream` (NULL: the context's), ordered after the adds
+ *                     before it and before the adds after it; d_shown_rgba8 needs d_rgba8. */
+int vrt_accum_begin(vrt_ctx *ctx, int width, int height, uint32_t first_sample);
+int vrt_accum_add(vrt_ctx *ctx, uint32_t n_samples, uint32_t *total_out);
+int vrt_accum_resolve(vrt_ctx *ctx, uint8_t *out_rgba8, int32_t *out_id_dist, uint8_t *out_shown_rgba8);
+int vrt_accum_resolve_device(vrt_ctx *ctx, void *d_rgba8, void *d_id_dist, void *d_shown_rgba8, void *stream);
+
 /* Column-major mat4 x2 + vec4, exactly the std140 Camera block (comp:17-21). */
 int vrt_set_camera(vrt_ctx *ctx, const float inv_projection[16], const float inv_view[16],
                    const float camera_pos[4]);

@@ -1,0 +1,82 @@
+"""Progressive-accumulation rate on one MI355X: wall time of one vrt_accum_add of n samples (n = 1, 4, 16, 64; the adds after
+the first, i.e. without pass 1 on the opaque path) on the 1080p dragon and nature frames and the 1080p room from inside, beside
+n times the frame time of vrt_dispatch(VRT_MODE_FULL) (vrt_dispatch_timed: events around each launch). Prints one JSON object per
+line; --out writes them to a file too.
+
+    python3 tools/accum_rate.py --out profiles/accum_rate.jsonl
+    rocprofv3 --kernel-trace --stats -d <dir> -o a -- python3 tools/accum_rate.py --reps 3   (kernel times)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import vrt_import  # noqa: E402
+
+SAMPLES = (1, 4, 16, 64)
+SCENES = {   # name -> (map, pose): the golden 1080p / 4K frames' poses
+    "dragon_1080p": ("dragon", (63.5, 60.5, 140.5), -90.0, -10.0),
+    "nature_1080p": ("nature", (60.5, 80.5, 200.5), -90.0, -20.0),
+    "room_inside_1080p": ("room", (14.5, 30.5, 16.5), 32.0, -10.0),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    V = vrt_import.vrt()
+    from conftest import MAPS, room_world
+    W, H = 1920, 1080
+    ctx = V.Context(0)
+    d_rgba, d_id = ctx.device_alloc(W * H * 4), ctx.device_alloc(W * H * 8)
+    rows = []
+    for name, (m, pos, yaw, pitch) in SCENES.items():
+        if m == "room":
+            w = room_world(V)
+        else:
+            w = V.World()
+            assert w.load_vox(os.path.join(MAPS, m + ".vox"))
+        tex, dim = w.flatten()
+        w.close()
+        ctx.upload_octree(tex, dim)
+        ip, iv, cp, _ = V.camera_block(pos, yaw, pitch, W, H)
+        ctx.set_camera(ip, iv, cp)
+        ctx.set_params(ctx.default_params())
+        ctx.dispatch_timed(W, H, 0, H, V.MODE_FULL, d_rgba, d_id, 5)
+        frame_ms = float(np.median(ctx.dispatch_timed(W, H, 0, H, V.MODE_FULL, d_rgba, d_id, max(args.reps, 5))))
+        opaque = V.tree_is_opaque(tex)
+        for n in SAMPLES:
+            ctx.accum_begin(W, H, 0)
+            ctx.accum_add(n)          # the first add: pass 1 on the opaque path, code object load
+            ctx.synchronize()
+            ts = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                ctx.accum_add(n)
+                ctx.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ms = float(np.median(ts))
+            row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "n": n,
+                   "add_ms": round(ms, 4), "n_frames_ms": round(n * frame_ms, 4), "frame_ms": round(frame_ms, 4),
+                   "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    ctx.device_free(d_rgba)
+    ctx.device_free(d_id)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()

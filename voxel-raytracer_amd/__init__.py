@@ -248,6 +248,10 @@ def hip_lib():
         L.vrt_cast_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
         L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
+        L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "vrt_ab_set_full_split"):   # `make AB=1` builds only
             L.vrt_ab_set_full_split.argtypes = [C.c_void_p, C.c_int]
             L.vrt_ab_set_bounce.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -748,6 +752,42 @@ class Context:
         L = self._L
         self._chk(L.vrt_find_voxels(self._h, n, c.ctypes.data if n else None, out.ctypes.data if n else None))
         return out[:, 0] != 0, out[:, 1:].copy()
+
+    def accum_begin(self, width, height, first_sample=0):
+        """(Re)start the progressive accumulation of VRT_MODE_FULL at initRNG sample index `first_sample` (vrt_accum_begin)."""
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 1 << 30:
+                raise ValueError(f"{name}: expected a positive integer, got {v!r}")
+        if width * height > 1 << 30:
+            raise ValueError(f"width * height: at most 2^30 pixels, got {width * height}")
+        if isinstance(first_sample, bool) or not isinstance(first_sample, (int, np.integer)) or not 0 <= first_sample < 1 << 32:
+            raise ValueError(f"first_sample: expected an integer in [0, 2^32), got {first_sample!r}")
+        self._chk(self._L.vrt_accum_begin(self._h, int(width), int(height), int(first_sample)))
+        self._accum_shape = (int(height), int(width))
+
+    def accum_add(self, n_samples=1):
+        """Enqueue n_samples more samples (vrt_accum_add) -> the samples now in the accumulation (n_samples after a restart)."""
+        if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or not 1 <= n_samples <= 1 << 24:
+            raise ValueError(f"n_samples: expected an integer in [1, 2^24], got {n_samples!r}")
+        total = C.c_uint32(0)
+        self._chk(self._L.vrt_accum_add(self._h, int(n_samples), C.byref(total)))
+        return int(total.value)
+
+    def accum_resolve(self):
+        """The resolved accumulation (vrt_accum_resolve) -> (rgba8[H,W,4], id_dist[H,W,2], shown rgba8[H,W,4])."""
+        shape = getattr(self, "_accum_shape", None)
+        if shape is None:
+            raise VrtError("accum_resolve: no accumulation (call accum_begin first)")
+        h, w = shape
+        rgba = np.zeros((h, w, 4), np.uint8)
+        idd = np.zeros((h, w, 2), np.int32)
+        shown = np.zeros((h, w, 4), np.uint8)
+        self._chk(self._L.vrt_accum_resolve(self._h, rgba.ctypes.data, idd.ctypes.data, shown.ctypes.data))
+        return rgba, idd, shown
+
+    def accum_resolve_device(self, d_rgba, d_id, d_shown, stream=None):
+        """vrt_accum_resolve_device: DEVICE buffers (any may be None; d_shown needs d_rgba), enqueued on `stream`"""
+        self._chk(self._L.vrt_accum_resolve_device(self._h, d_rgba, d_id, d_shown, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

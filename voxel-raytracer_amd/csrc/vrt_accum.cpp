@@ -1,0 +1,160 @@
+// vrt_accum.cpp -- progressive multi-sample accumulation of VRT_MODE_FULL (include/vrt.h vrt_accum_*): call-order checks, the
+// restart rule, the context's buffers, the resolve and the display pass on it. The samples themselves are enqueued by the
+// dispatcher (vrt_dispatch.cpp enqueue() with an AccumStep), which chooses between the sample-looped bounce and the general
+// kernel (vrt_accum.hip.h) as it chooses between the two forms of a frame.
+#include "vrt_internal.h"
+#include "vrt_launch.h"
+
+#include <cstring>
+
+using namespace vrt_internal;
+
+namespace {
+
+using Accum = vrt_ctx::Accum;
+
+// does the next sample still belong to the samples in the sums? (camera block, uniforms and tree as at the first of them)
+bool same_inputs(const vrt_ctx *c, const Accum &ac) {
+    return std::memcmp(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj) == 0 && std::memcmp(ac.inv_view, c->inv_view, sizeof ac.inv_view) == 0 &&
+           std::memcmp(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos) == 0 && std::memcmp(&ac.params, &c->params, sizeof ac.params) == 0 &&
+           ac.tree_gen == c->tree_gen;
+}
+
+void take_inputs(const vrt_ctx *c, Accum &ac) {
+    std::memcpy(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj);
+    std::memcpy(ac.inv_view, c->inv_view, sizeof ac.inv_view);
+    std::memcpy(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos);
+    ac.params = c->params;
+    ac.tree_gen = c->tree_gen;
+}
+
+template <class T>
+int grow(vrt_ctx *c, T *&p, size_t bytes) {
+    if (p) VRT_HIP(c, hipFree(p));
+    p = nullptr;
+    VRT_HIP(c, hipMalloc((void **)&p, bytes));
+    return VRT_OK;
+}
+
+int resolve_state(vrt_ctx *c, const char *what) {
+    if (!c) return VRT_E_INVALID;
+    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
+    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
+    return VRT_OK;
+}
+
+// sums -> rgba8 into d_rgba, the frame's id_dist into d_id (either may be null), the display pass into d_shown (needs d_rgba)
+int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_t s) {
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if (d_rgba) {
+        vrt::accum::Resolve q{ac.d_sums, static_cast<uint32_t *>(d_rgba), ac.total, (uint32_t)px};
+        VRT_HIP(c, vrt::launch::accum_resolve(q, s));
+    }
+    if (d_id) VRT_HIP(c, hipMemcpyAsync(d_id, ac.d_id, px * 8, hipMemcpyDeviceToDevice, s));
+    if (d_shown) return vrt_denoise(c, ac.width, ac.height, d_rgba, ac.d_id, d_shown, s);
+    return VRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrt_accum_begin(vrt_ctx *c, int width, int height, uint32_t first_sample) {
+    int r = check_frame(c, width, height);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    Accum &ac = c->accum;
+    const size_t px = (size_t)width * (size_t)height;
+    const size_t tiles = (size_t)((width + 7) / 8) * (size_t)((height + 7) / 8);
+    if (px > ac.pixels || tiles > ac.seed_tiles) {
+        VRT_HIP(c, hipStreamSynchronize(c->stream));   // samples in flight still write the old buffers
+        ac.begun = false;
+        ac.pixels = ac.seed_tiles = 0;
+        if ((r = grow(c, ac.d_sums, px * 16)) || (r = grow(c, ac.d_pass1, px * 4)) || (r = grow(c, ac.d_id, px * 8)) ||
+            (r = grow(c, ac.d_seed, tiles * 64 * vrt::kSeedPlanesHost * 4)))
+            return r;
+        ac.pixels = px;
+        ac.seed_tiles = tiles;
+    }
+    if (!ac.added) VRT_HIP(c, hipEventCreateWithFlags(&ac.added, hipEventDisableTiming));
+    if (!ac.read) VRT_HIP(c, hipEventCreateWithFlags(&ac.read, hipEventDisableTiming));
+    ac.begun = true;
+    ac.width = width;
+    ac.height = height;
+    ac.first = first_sample;
+    ac.total = 0;
+    ac.pass1 = false;
+    return VRT_OK;
+}
+
+int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
+    if (!c) return VRT_E_INVALID;
+    Accum &ac = c->accum;
+    if (!ac.begun) return vrt_fail(c, VRT_E_STATE, "vrt_accum_add: no accumulation (call vrt_accum_begin first)");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, "vrt_accum_add: a patch batch is open (call vrt_patch_end first)");
+    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, "vrt_accum_add: no octree uploaded (call vrt_upload_octree first)");
+    if (!c->have_camera) return vrt_fail(c, VRT_E_STATE, "vrt_accum_add: no camera set (call vrt_set_camera first)");
+    if (n_samples == 0) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_add: n_samples must be at least 1");
+    // the restart rule: anything a sample depends on changed since the first sample in the sums -> the sums start again at `first`
+    const bool restart = ac.total == 0 || !same_inputs(c, ac);
+    const uint32_t base = restart ? 0u : ac.total;
+    if (n_samples > vrt::accum::kMaxSamples - base)
+        return vrt_fail(c, VRT_E_INVALID, "vrt_accum_add: at most 2^24 samples per accumulation");
+    VRT_HIP(c, hipSetDevice(c->device));
+    if (restart) {
+        VRT_HIP(c, hipMemsetAsync(ac.d_sums, 0, (size_t)ac.width * (size_t)ac.height * 16, c->stream));
+        take_inputs(c, ac);
+        ac.total = 0;
+        ac.pass1 = false;
+    }
+    const AccumStep step{ac.first + base, n_samples};
+    const int r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, VRT_MODE_FULL, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
+    if (r) {   // what this add left in the sums is unknown: the next add starts again
+        ac.total = 0;
+        return r;
+    }
+    ac.total = base + n_samples;
+    if (total_out) *total_out = ac.total;
+    return VRT_OK;
+}
+
+int vrt_accum_resolve(vrt_ctx *c, uint8_t *out_rgba8, int32_t *out_id_dist, uint8_t *out_shown_rgba8) {
+    int r = resolve_state(c, "vrt_accum_resolve");
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    r = ensure_scratch(c, px);
+    if (r) return r;
+    const bool want_rgba = out_rgba8 || out_shown_rgba8;
+    r = resolve_into(c, want_rgba ? c->d_rgba : nullptr, nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
+    if (r) return r;
+    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_id_dist) VRT_HIP(c, hipMemcpyAsync(out_id_dist, ac.d_id, px * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_shown_rgba8) VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_accum_resolve_device(vrt_ctx *c, void *d_rgba8, void *d_id_dist, void *d_shown_rgba8, void *stream) {
+    int r = resolve_state(c, "vrt_accum_resolve_device");
+    if (r) return r;
+    if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_device: the display pass needs d_rgba8");
+    VRT_HIP(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    Accum &ac = c->accum;
+    if (s != c->stream) {   // the samples were added on the context's stream; later adds must not overtake this read
+        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
+        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
+    }
+    r = resolve_into(c, d_rgba8, d_id_dist, d_shown_rgba8, s);
+    if (r) return r;
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.read, s));
+        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
+    }
+    return VRT_OK;
+}
+
+}  // extern "C"

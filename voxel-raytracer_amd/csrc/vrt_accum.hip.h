@@ -1,0 +1,122 @@
+// vrt_accum.hip.h -- progressive multi-sample accumulation of VRT_MODE_FULL (include/vrt.h vrt_accum_*). Sample k of a pixel is
+// the frame the shader renders with initRNG(pixel, k) (comp:380-387; comp:629 itself passes 0): the same camera, uniforms and
+// tree, only the random numbers differ. An accumulation keeps, per pixel and channel, the integer sum of the unorm8 bytes each
+// sample would store -- exact and independent of the order of the adds -- and resolves it to (sum + n / 2) / n.
+//
+// Two kernels add samples, as VRT_MODE_FULL has two forms (vrt_dispatch.cpp enqueue()):
+//   bounce_accum_kernel   scenes the dispatcher proves opaque, seen from empty space. Pass 1 (trace_kernel MODE 4) does not
+//                         depend on the sample and runs once per accumulation; this kernel then runs the diffuse bounce of
+//                         full::bounce_pixel (the only part that reads the RNG, its first two numbers) for n samples in a loop
+//                         over the seed each lane loaded once: the 8 x 8 tiles and the tile ballot of MODE 5, the three sums
+//                         in LDS, one read-add-write of the pixel's sums at the end (one lane per pixel: no atomics).
+//   full_accum_kernel     everything else: full::trace_pixel_full with the sample index, its bytes added to the sums. One
+//                         sample per launch; the traversal is the one trace_kernel<2> would take.
+// and one resolves: accum_resolve_kernel.
+#pragma once
+#include "vrt_accum.h"
+#include "vrt_full.hip.h"
+
+namespace vrt {
+namespace accum {
+
+VRT_DEV void add_bytes(uint32_t rgba, uint32_t &r, uint32_t &g, uint32_t &b) {
+    r += rgba & 0xffu;
+    g += (rgba >> 8) & 0xffu;
+    b += (rgba >> 16) & 0xffu;
+}
+
+VRT_DEV void store_sums(uint32_t *sums, size_t o, uint32_t r, uint32_t g, uint32_t b) {
+    uint4 *p = reinterpret_cast<uint4 *>(sums) + o;
+    uint4 s = *p;
+    s.x += r; s.y += g; s.z += b;
+    *p = s;
+}
+
+// One wave per 8 x 8 tile of a whole frame (KArgs: row0 = 0, n_rows = height, compact = 0); a.defer_rec holds pass 1's seeds in
+// the tile-major planes of MODE 4 / 5 (vrt_common.hip.h kSeedPlanes). Built as MODE 5 is: 64 lanes, seven waves per SIMD, whose
+// 72 registers MODE 5's bounce fills. The loop's own state -- the seed, which MODE 5 lets die at the march, and the three sums --
+// waits in LDS (2 KiB per wave; 28 waves per CU hold 56 of its 160 KiB) instead of in spilled registers: the lane loads its seed
+// from memory once, and each sample reads it back from LDS and adds its bytes there.
+template <class TRAV>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const Args q) {
+    __shared__ uint32_t s_seed[kSeedPlanes][64];
+    __shared__ uint32_t s_sum[3][64];
+    typename TRAV::Ctx tc_;
+    TRAV::template block_init<64>(a, nullptr, tc_);
+    const int lane = threadIdx.x & 63;
+    const int tiles_x = (a.width + 7) / 8;
+    const int tile = blockIdx.x;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+    if (px >= a.width || py >= a.height) return;
+    const uint32_t *sp = reinterpret_cast<const uint32_t *>(a.defer_rec) + ((size_t)tile * kSeedPlanes) * 64 + lane;
+    const uint32_t word = sp[3 * 64];
+    uint32_t r = 0u, g = 0u, b = 0u;
+    if (word & kSeedValid) {
+#pragma unroll
+        for (uint32_t p = 0; p < kSeedPlanes; ++p) s_seed[p][lane] = sp[p * 64];
+        s_sum[0][lane] = 0u; s_sum[1][lane] = 0u; s_sum[2][lane] = 0u;
+        // volatile: the seed is read back for every sample, not hoisted into registers across the loop
+        volatile uint32_t *vs_seed = &s_seed[0][0];
+        volatile uint32_t *vs_sum = &s_sum[0][0];
+        // every sample is bounce_pixel's own arithmetic on the same seed: direct term, then the bounce's term, then unorm8
+        for (uint32_t k = 0; k < q.n; ++k) {
+            Seed seed;
+            seed.hp = F3{__uint_as_float(vs_seed[0 * 64 + lane]), __uint_as_float(vs_seed[1 * 64 + lane]), __uint_as_float(vs_seed[2 * 64 + lane])};
+            seed.word = vs_seed[3 * 64 + lane];
+            seed.iof = __uint_as_float(vs_seed[4 * 64 + lane]);
+            // the kernel's arguments re-read from the kernarg segment for every sample (late_args()): held in scalar registers
+            // across the loop's back edge they spilled into vector lanes (20 SGPRs, then 18 VGPRs to scratch)
+#ifdef __HIP_DEVICE_COMPILE__
+            const KArgs ak = *late_args();
+#else
+            const KArgs &ak = a;
+#endif
+            uint32_t rgba = 0u;
+            full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, rgba, q.first + k);
+            vs_sum[0 * 64 + lane] = vs_sum[0 * 64 + lane] + (rgba & 0xffu);
+            vs_sum[1 * 64 + lane] = vs_sum[1 * 64 + lane] + ((rgba >> 8) & 0xffu);
+            vs_sum[2 * 64 + lane] = vs_sum[2 * 64 + lane] + ((rgba >> 16) & 0xffu);
+        }
+        r = vs_sum[0 * 64 + lane]; g = vs_sum[1 * 64 + lane]; b = vs_sum[2 * 64 + lane];
+    } else {   // sky, emissive surfaces: pass 1's bytes are every sample's
+        add_bytes(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], r, g, b);
+        r *= q.n; g *= q.n; b *= q.n;
+    }
+    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+}
+
+// The general full path tracer with initRNG's sampleIndex = q.first (q.n == 1): trace_kernel<2>'s tiles, one pixel per lane.
+template <class TRAV, int BLOCK, int WPE>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const Args q) {
+    extern __shared__ __attribute__((aligned(16))) uint2 lds_dyn[];
+    typename TRAV::Ctx tc_;
+    TRAV::template block_init<BLOCK>(a, lds_dyn, tc_);
+    if constexpr (TRAV::kStagesLds) __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int tiles_x = (a.width + 7) / 8;
+    const int tile = (int)blockIdx.x * (BLOCK / 64) + (int)(threadIdx.x >> 6);
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+    if (px >= a.width || py >= a.height) return;
+    uint32_t rgba;
+    int2 idd;
+    LateOut lo;
+    full::trace_pixel_full<TRAV, false>(a, vs.v[0], tc_, px, py, rgba, idd, lo, 0u, 0u, q.first);
+    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+    uint32_t r = 0u, g = 0u, b = 0u;
+    add_bytes(rgba, r, g, b);
+    store_sums(q.sums, o, r, g, b);
+    q.out_id[o] = idd;
+}
+
+__global__ __launch_bounds__(256) void accum_resolve_kernel(const Resolve q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.pixels) return;
+    const uint4 s = reinterpret_cast<const uint4 *>(q.sums)[i];
+    const uint32_t h = q.n >> 1;
+    q.out_rgba[i] = ((s.x + h) / q.n) | (((s.y + h) / q.n) << 8) | (((s.z + h) / q.n) << 16) | (255u << 24);
+}
+
+}  // namespace accum
+}  // namespace vrt

@@ -390,10 +390,10 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
 namespace full {  // MODE 2 and 3 (3: the last diffuse bounce of a pixel goes to a queue for bounce_kernel), defined in vrt_full.hip.h
 template <class TRAV, bool DEFER>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t queue, uint32_t out_offset);
+                                 uint32_t queue, uint32_t out_offset, uint32_t sample = 0u);
 // pass 2 of the two-pass form: the diffuse bounce of a seeded pixel; false when the pixel has none (rgba untouched)
 template <class TRAV>
-__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, Seed seed, uint32_t &rgba);
+__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, Seed seed, uint32_t &rgba, uint32_t sample = 0u);
 }
 
 // One lane per pixel; a wave covers a TW x TH pixel tile (TW*TH == 64) so the 64 rays of a wave stay spatially

@@ -129,7 +129,7 @@ vrt_ctx::RayTable *ray_table(vrt_ctx *c, const float *inv_proj, int W, int H) {
 
 // views == nullptr: one view, the context's camera (vrt_set_camera) rendering into d_rgba / d_id.
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact,
-            int mode, void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views, int n_views) {
+            int mode, void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views, int n_views, const AccumStep *acc) {
     if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: no octree uploaded (call vrt_upload_octree first)");
     if (c->batch.open) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: a patch batch is open (call vrt_patch_end first)");
     if (!views && !c->have_camera) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: no camera set (call vrt_set_camera first)");
@@ -278,7 +278,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     // feedback scheduling: wide-traversal kernels, one view, launches large enough to have a tail worth shaping
     SchedState *st = nullptr;
     bool measure = false;
-    const bool sched_kernel = v.trav >= 3 && !v.use_lds && v.tw == 8 && v.blocks_per_cu == 0 && n_views == 1 &&
+    const bool sched_kernel = !acc && v.trav >= 3 && !v.use_lds && v.tw == 8 && v.blocks_per_cu == 0 && n_views == 1 &&
                               (v.trav == 4 || (v.block == 64 && (v.wpe == 5 || v.wpe == 6 || v.wpe == 7)) ||
                                (v.block == 256 && (v.wpe == 5 || v.wpe == 6)));
     const long groups = (tiles + vrt::kGroupTiles - 1) / vrt::kGroupTiles;
@@ -300,12 +300,12 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         }
     }
     if (a.group_order) grid = groups * (vrt::kGroupTiles / waves);  // whole groups: the last one may hold tiles past the end
-    const bool prof = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
+    const bool prof = !acc && c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
     const hipEvent_t ev0 = prof ? c->prof_events[2 * c->prof_count] : nullptr;
     const hipEvent_t ev1 = prof ? c->prof_events[2 * c->prof_count + 1] : nullptr;
     hipError_t e;
     // The full path tracer as two kernels (vrt_bounce.hip.h): the default traversal, one view, a scene with a wide form.
-    const bool split = VRT_AB && mode == VRT_MODE_FULL && c->full_split && c->wide_ok && v.trav == 3 && v.block == 64 && n_views == 1 && c->variant == 0;
+    const bool split = !acc && VRT_AB && mode == VRT_MODE_FULL && c->full_split && c->wide_ok && v.trav == 3 && v.block == 64 && n_views == 1 && c->variant == 0;
     // the full path tracer as two tile-coherent passes, where the scene and the view allow it
     bool two_pass = false;
     if (mode == VRT_MODE_FULL && c->two_pass_on && v.trav == 4 && n_views == 1 && c->variant == 0 && !split && vs.v[0].out_rgba) {
@@ -351,7 +351,32 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         a.defer_count = dq->count;
         a.defer_cap = (uint32_t)dq->cap;
     }
-    if (two_pass && c->two_pass_form >= 5) {
+    if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
+        vrt_ctx::Accum &ac = c->accum;
+        vrt::accum::Args q{};
+        q.sums = ac.d_sums;
+        q.pass1_rgba = ac.d_pass1;
+        q.out_id = ac.d_id;
+        e = hipSuccess;
+        if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
+            a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
+            if (!ac.pass1) {
+                vs.v[0].out_rgba = ac.d_pass1;
+                vs.v[0].out_id = ac.d_id;
+                e = vrt::launch::trace_full_pass1(a, vs, (int)grid, s);
+                if (e == hipSuccess) ac.pass1 = true;
+            }
+            q.first = acc->first;
+            q.n = acc->n;
+            if (e == hipSuccess) e = vrt::launch::accum_bounce(a, vs, q, (int)grid, s);
+        } else {          // the general path tracer, one launch per sample
+            for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
+                q.first = acc->first + k;
+                q.n = 1u;
+                e = vrt::launch::accum_full(v, a, vs, q, (int)grid, s);
+            }
+        }
+    } else if (two_pass && c->two_pass_form >= 5) {
         e = vrt::launch::trace_full_opaque(a, vs, (int)grid, c->two_pass_form, s, ev0, ev1);
     } else if (two_pass) {
         vrt_ctx::SeedBuffer *sb = nullptr;

@@ -101,9 +101,9 @@ VRT_DEV void det_sincos(float xin, float &s_out, float &c_out) {  // Cephes sinf
     c_out = sign_c < 0 ? -cv : cv;
 }
 
-// comp:381-399
-VRT_DEV uint32_t rng_init(int px, int py, int sample) {
-    uint32_t seed = (uint32_t)px + (uint32_t)py * 1920u + 123456u + (uint32_t)sample * 78901u;
+// comp:381-399; `sample` is initRNG's sampleIndex (uint(sampleIndex): the same bits for every int)
+VRT_DEV uint32_t rng_init(int px, int py, uint32_t sample) {
+    uint32_t seed = (uint32_t)px + (uint32_t)py * 1920u + 123456u + sample * 78901u;
     uint32_t st = seed * 747796405u + 2891336453u;
     uint32_t w = ((st >> ((st >> 28u) + 4u)) ^ st) * 277803737u;
     return (w >> 22u) ^ w;
@@ -187,13 +187,14 @@ VRT_DEV void defer_bounce(const KArgs &a, uint32_t queue, uint32_t out_offset, F
 // pixel -- nothing is accumulated after it -- so it goes to a queue instead, together with the colour summed so far;
 // bounce_kernel (vrt_bounce.hip.h) marches it among full waves of such rays and writes the pixel. A bounce ray (depth 1)
 // spawns nothing (comp:590-594), so the queue is one level deep. The accumulation order per pixel is unchanged.
+// sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...)
 template <class TRAV, bool DEFER>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t queue, uint32_t out_offset) {
+                                 uint32_t queue, uint32_t out_offset, uint32_t sample) {
     const float kPI = 3.14159265359f;
     const float sky[3] = {0.5f, 0.7f, 1.0f};
     const float kSun = 3.0f;
-    uint32_t rng = rng_init(px, py, 0);
+    uint32_t rng = rng_init(px, py, sample);
     const F3 ray_dir = primary_ray_dir(a, vw, px, py);
     const F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
 
@@ -434,8 +435,9 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
 // this function) marches the bounce rays of the seeded pixels in the same 8 x 8 tiles (the coherence the one-kernel form has),
 // again without a stack, and writes the pixel's final colour. The accumulation order per pixel is pathTrace's: direct term, then
 // the bounce's term. Everything pass 2 recomputes is computed from the same inputs by the same operations as pass 1 did.
+// Only the bounce depends on initRNG's sampleIndex (`sample`): the sample loop of vrt_accum.hip.h runs this once per sample on one seed.
 template <class TRAV>
-__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, const Seed seed, uint32_t &rgba) {
+__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, const Seed seed, uint32_t &rgba, uint32_t sample) {
     const uint32_t word = seed.word;
     const bool valid = (word & kSeedValid) != 0u;
     if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return false;   // a tile without bounces (sky, emissive surfaces)
@@ -465,7 +467,7 @@ __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int 
         tint[k] = gl[k] * sc[k];
     }
     // comp:596-616: the first two random numbers of the pixel
-    uint32_t rng = rng_init(px, py, 0);
+    uint32_t rng = rng_init(px, py, sample);
     const float rx = rng_next(rng), ry = rng_next(rng);
     const F3 bd = cosine_hemisphere(normal, rx, ry);
     const F3 ro = add3(hp, scale3(normal, 1e-1f));

@@ -6,6 +6,7 @@
 //   vrt_display.cpp    the display pass and the fused frame call
 //   vrt_patch.cpp      edits without re-upload: patch plan / apply / batches / compaction
 //   vrt_query.cpp      world queries on the device tree: ray casts (picking), voxel lookups
+//   vrt_accum.cpp      progressive multi-sample accumulation of VRT_MODE_FULL: begin / add / resolve, the restart rule
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts)
@@ -191,6 +192,28 @@ struct vrt_ctx {
     bool tight_root_on = true;                   // VRT_OPT_EMPTY_OCTANTS 2 = on without the tighter root
     bool root0_only_on = true;                   // VRT_OPT_EMPTY_OCTANTS 0: never tell the kernels that the world is empty outside wide root 0
     bool ray_tables_on = true;                   // VRT_OPT_RAY_TABLES 0: always the shader's own prologue (A/B, tests)
+    // every change of the tree (upload, patch, batch end, compaction) counts one: the accumulation's restart rule compares it
+    uint64_t tree_gen = 0;
+    // the progressive accumulation of VRT_MODE_FULL (vrt_accum.cpp): one per context
+    struct Accum {
+        bool begun = false;
+        int width = 0, height = 0;
+        uint32_t first = 0;                      // initRNG sampleIndex of the first sample in the sums
+        uint32_t total = 0;                      // samples in the sums
+        bool pass1 = false;                      // d_seed and d_pass1 hold pass 1 of the current samples (opaque path)
+        // what every sample depends on, as it was at the first sample in the sums
+        float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
+        vrt_params params{};
+        uint64_t tree_gen = 0;
+        uint32_t *d_sums = nullptr;              // 4 words per pixel
+        uint32_t *d_pass1 = nullptr;             // pass 1's rgba8 (opaque path)
+        int2 *d_id = nullptr;                    // the frame's (voxel ID, dist)
+        uint32_t *d_seed = nullptr;              // pass 1's seeds, tile-major (kSeedPlanesHost words per pixel)
+        size_t pixels = 0, seed_tiles = 0;       // capacities
+        uint32_t *d_resolved = nullptr;          // vrt_accum_resolve_device without d_rgba8 but with d_shown_rgba8
+        hipEvent_t added = nullptr, read = nullptr;   // ordering against a caller's stream in vrt_accum_resolve_device
+    };
+    Accum accum;
     const uint32_t *dbg_group_order = nullptr;  // vrt_set_tile_order: caller-owned buffers instead of the scheduler's
     uint32_t *dbg_tile_cost = nullptr;
     bool dbg_sched = false;
@@ -221,8 +244,11 @@ int check_frame(vrt_ctx *c, int width, int height);
 int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-buffer entry points
 
 // vrt_dispatch.cpp
+// AccumStep: instead of rendering a frame, add samples first .. first + n - 1 of VRT_MODE_FULL to the context's accumulation
+// (vrt_accum.cpp; whole frame, the context's camera, d_rgba / d_id unused)
+struct AccumStep { uint32_t first, n; };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
-            void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1);
+            void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
 SchedState *sched_state(vrt_ctx *c, hipStream_t s, int width, int n_rows, int row0, int row_stride, int tile_rows, int mode,
                         uint32_t n_tiles, uint32_t n_groups);
 bool measuring_launch(uint64_t launches, int period);

@@ -3,6 +3,7 @@
 #pragma once
 #include "vrt_internal.h"
 #include "vrt_query.h"
+#include "vrt_accum.h"
 
 namespace vrt {
 namespace launch {
@@ -19,6 +20,8 @@ hipError_t trace_full(const Variant &v, const KArgs &a, const ViewSet &vs, int g
 // ... and the same two stages in ONE kernel, the seed in registers (no stack, no seed traffic, no second launch); wpe 5, 6 or 7
 hipError_t trace_full_opaque(const KArgs &a, const ViewSet &vs, int grid, int wpe, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 hipError_t trace_full_two_pass(const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// pass 1 of the two-pass form alone (the progressive accumulation runs it once and the bounce once per sample)
+hipError_t trace_full_pass1(const KArgs &a, const ViewSet &vs, int grid, hipStream_t s);
 inline hipError_t trace(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, int grid, size_t lds, hipStream_t s, hipEvent_t ev0,
                         hipEvent_t ev1) {
     return mode == VRT_MODE_FULL ? trace_full(v, a, vs, grid, s, ev0, ev1)
@@ -50,6 +53,13 @@ hipError_t denoise(const Denoise &d, int variant, bool whole_groups, hipStream_t
 // vrt_launch_query.hip: the world queries (vrt_query.hip.h), one lane per ray / point; a carries the scene part of KArgs only
 hipError_t cast_rays(const KArgs &a, const query::RayArgs &q, hipStream_t s);
 hipError_t find_voxels(const KArgs &a, const query::PointArgs &q, hipStream_t s);
+
+// vrt_launch_accum.hip: progressive accumulation of VRT_MODE_FULL (vrt_accum.hip.h), whole frames, one tile per wave.
+// accum_bounce: q.n samples of the diffuse bounce over pass 1's seeds in a.defer_rec (grid = tiles). accum_full: one sample
+// (q.first) of the general path tracer in the traversal and workgroup shape of `v` (grid = tiles / waves per workgroup).
+hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
+hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
+hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s);
 
 #if VRT_AB
 // vrt_launch_ab.hip -- the full path tracer as two kernels with cross-wave repacking (ab/vrt_bounce.hip.h): an experiment that lost

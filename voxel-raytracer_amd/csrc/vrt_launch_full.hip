@@ -32,5 +32,9 @@ hipError_t trace_full_two_pass(const KArgs &a, const ViewSet &vs, int grid, hipS
     return launch_sched<5, v4::TravAny, 8, 64, 7>(b, vs, grid, 0, s, nullptr, ev1);
 }
 
+hipError_t trace_full_pass1(const KArgs &a, const ViewSet &vs, int grid, hipStream_t s) {
+    return launch_one<4, v4::Trav, 8, 64, 7>(a, vs, grid, 0, s);
+}
+
 }  // namespace launch
 }  // namespace vrt

@@ -41,6 +41,7 @@ int patch_host(vrt_ctx *c, const vrt_patch &patch, const uint32_t *subtree_recor
         return vrt_fail(c, VRT_E_MALFORMED, "vrt_patch_apply: " + why);   // apply_patch modifies nothing when it refuses
     bt.dirty = true;
     c->scene_opaque_valid = false;   // the tree changed: what the two-pass path tracer may assume about it is re-derived
+    ++c->tree_gen;
     bt.rewritten_records.push_back(site.record);
     bt.texel_delta += rg.texel_delta;
     if (wide_now) {
@@ -164,6 +165,7 @@ int vrt_patch_end(vrt_ctx *c) {
     if (!c) return VRT_E_INVALID;
     if (!c->batch.open) return vrt_fail(c, VRT_E_STATE, "vrt_patch_end: no batch open");
     VRT_HIP(c, hipSetDevice(c->device));
+    ++c->tree_gen;
     return patch_device(c);
 }
 
@@ -196,6 +198,7 @@ int vrt_compact(vrt_ctx *c) {
     VRT_HIP(c, hipDeviceSynchronize());   // dispatches in flight read the old arrays
     vrt::compact_records(c->host_records);
     c->scene_opaque_valid = false;
+    ++c->tree_gen;
     struct Guard { vrt_ctx *c; bool armed = true; ~Guard() { if (armed) { c->have_scene = false; c->analysis_valid = false; } } } guard{c};
     const size_t bytes = c->host_records.size() * sizeof(vrt::Record);
     if (bytes > c->nodes_capacity) {   // cannot grow, but a context whose array was never sized stays correct

@@ -198,6 +198,12 @@ void vrt_destroy(vrt_ctx *c) {
     if (c->d_id) (void)hipFree(c->d_id);
     if (c->d_shown) (void)hipFree(c->d_shown);
     if (c->d_query) (void)hipFree(c->d_query);
+    (void)hipFree(c->accum.d_sums);
+    (void)hipFree(c->accum.d_pass1);
+    (void)hipFree(c->accum.d_id);
+    (void)hipFree(c->accum.d_seed);
+    if (c->accum.added) (void)hipEventDestroy(c->accum.added);
+    if (c->accum.read) (void)hipEventDestroy(c->accum.read);
     for (auto &d : c->defer) {
         (void)hipFree(d.rec);
         (void)hipFree(d.count);
@@ -276,6 +282,7 @@ int vrt_upload_octree(vrt_ctx *c, const uint8_t *texels, size_t used_bytes, uint
     c->dim_from_texels = tex_dim == dim_of_texels(c->stream_texels);
     c->analysis_valid = false;
     c->scene_opaque_valid = false;
+    ++c->tree_gen;
     c->have_scene = true;
     return VRT_OK;
 }
@@ -341,6 +348,7 @@ int vrt_upload_records(vrt_ctx *c, const uint32_t *records, size_t n_records, ui
     c->dim_from_texels = tex_dim == dim_of_texels(c->stream_texels);
     c->analysis_valid = false;
     c->scene_opaque_valid = false;
+    ++c->tree_gen;
     c->have_scene = true;
     return VRT_OK;
 }
