@@ -169,9 +169,10 @@ int vrt_cast_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int orig
  * The words are 0 when present is 0. HOST buffers, synchronous. */
 int vrt_find_voxels(vrt_ctx *ctx, size_t n, const int32_t *coords, uint32_t *out);
 
-/* Progressive multi-sample accumulation of VRT_MODE_FULL (one per context). Sample k is the VRT_MODE_FULL frame rendered with
- * initRNG(pixel, k) (shaders/raytracing.comp:380-387; the shader itself passes 0): camera, uniforms, tree and every other
- * convention unchanged. The accumulation holds the samples first, first + 1, ..., first + n - 1 (sample indices modulo 2^32) as
+/* Progressive multi-sample accumulation (one per context; vrt_accum_begin_ex below: the other modes, sub-pixel jitter).
+ * Sample k is the VRT_MODE_FULL frame rendered with initRNG(pixel, k) (shaders/raytracing.comp:380-387; the shader itself
+ * passes 0): camera, uniforms, tree and every other convention unchanged. The accumulation holds the samples first, first + 1,
+ * ..., first + n - 1 (sample indices modulo 2^32) as
  * one integer sum per pixel and channel of the unorm8 bytes each sample would store -- exact, whatever chunks they were added
  * in -- and resolves to (sum + n / 2) / n per channel, alpha 255: at n = 1 the sample itself. Averaging clamped bytes is what a
  * display of the successive frames shows. The resolved (voxel ID, dist) image is the frame's: no sample changes it.
@@ -189,6 +190,31 @@ int vrt_find_voxels(vrt_ctx *ctx, size_t n, const int32_t *coords, uint32_t *out
  * vrt_accum_resolve_device  the same into device buffers, enqueued on `stream` (NULL: the context's), ordered after the adds
  *                     before it and before the adds after it; d_shown_rgba8 needs d_rgba8. */
 int vrt_accum_begin(vrt_ctx *ctx, int width, int height, uint32_t first_sample);
+
+/* Anti-aliased progressive frames, and accumulations of the other two modes. vrt_accum_begin_ex (re)starts an accumulation of
+ * `mode` (VRT_MODE_PRIMARY, _PRIMARY_SHADOW or _FULL); vrt_accum_begin(ctx, w, h, first) is exactly
+ * vrt_accum_begin_ex(ctx, w, h, VRT_MODE_FULL, first, 0). The mode and flags belong to the accumulation: add, resolve,
+ * resolve_device, the 2^24 cap and the restart rule are the ones above. VRT_E_INVALID: an unknown mode or flag.
+ *
+ * Without VRT_ACCUM_JITTER sample k is the frame of `mode` (VRT_MODE_FULL: with initRNG(pixel, k), as above; the other two modes
+ * draw no random number, so every sample is their frame and the resolve is that frame byte for byte).
+ *
+ * VRT_ACCUM_JITTER: sample k also moves the pixel's ray inside the pixel. The shader's ray generation
+ * u = (float(px) / float(W)) * 2 - 1 (comp:631-638, and v with py and H) measures from the pixel's corner; jittered sample k uses
+ * float(px) + jx(k) and float(py) + jy(k) instead of float(px) and float(py) -- one float32 addition each, rounded to nearest,
+ * not contracted into the divide or multiply-add that follows. Everything after that -- the projection, the normalisations, the
+ * traversal, the shading, the unorm8 store -- is unchanged, and in VRT_MODE_FULL the sample also seeds initRNG(pixel, k).
+ * The offsets are a 2-D (0,2)-sequence, every value exact in float32:
+ *     jx(k) = (float)(bitreverse32(k) >> 8) * 0x1p-24f                      van der Corput, base 2
+ *     jy(k) = (float)(sobol2(k) >> 8) * 0x1p-24f                            Sobol's second dimension:
+ *             sobol2(k): y = 0; v = 1u << 31; for (i = k; i; i >>= 1, v ^= v >> 1) if (i & 1) y ^= v;
+ * so jx, jy lie in [0, 1), (jx, jy)(0) = (0, 0) -- sample 0 is the frame -- and the first 2^m samples of any aligned block of
+ * 2^m fall one into each elementary interval. The first eight: (0, 0), (1/2, 1/2), (1/4, 3/4), (3/4, 1/4), (1/8, 5/8),
+ * (5/8, 1/8), (3/8, 3/8), (7/8, 7/8).
+ * The resolved id_dist is the unjittered frame's: what vrt_dispatch stores in that mode. The display pass runs on the resolved
+ * mean with that image. */
+#define VRT_ACCUM_JITTER 1u
+int vrt_accum_begin_ex(vrt_ctx *ctx, int width, int height, int mode, uint32_t first_sample, uint32_t flags);
 int vrt_accum_add(vrt_ctx *ctx, uint32_t n_samples, uint32_t *total_out);
 int vrt_accum_resolve(vrt_ctx *ctx, uint8_t *out_rgba8, int32_t *out_id_dist, uint8_t *out_shown_rgba8);
 int vrt_accum_resolve_device(vrt_ctx *ctx, void *d_rgba8, void *d_id_dist, void *d_shown_rgba8, void *stream);

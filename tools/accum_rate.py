@@ -1,9 +1,11 @@
 """Progressive-accumulation rate on one MI355X: wall time of one vrt_accum_add of n samples (n = 1, 4, 16, 64; the adds after
 the first, i.e. without pass 1 on the opaque path) on the 1080p dragon and nature frames and the 1080p room from inside, beside
-n times the frame time of vrt_dispatch(VRT_MODE_FULL) (vrt_dispatch_timed: events around each launch). Prints one JSON object per
-line; --out writes them to a file too.
+n times the frame time of vrt_dispatch in the same mode (vrt_dispatch_timed: events around each launch). --mode picks the modes
+(default: full), --jitter accumulates jittered samples (VRT_ACCUM_JITTER). Prints one JSON object per line; --out writes them to
+a file too.
 
     python3 tools/accum_rate.py --out profiles/accum_rate.jsonl
+    python3 tools/accum_rate.py --mode primary primary_shadow full --jitter --out profiles/accum_jitter_rate.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -o a -- python3 tools/accum_rate.py --reps 3   (kernel times)
 """
 import argparse
@@ -31,6 +33,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out")
+    ap.add_argument("--mode", nargs="+", default=["full"], choices=["primary", "primary_shadow", "full"])
+    ap.add_argument("--jitter", action="store_true", help="jittered samples (anti-aliasing)")
     args = ap.parse_args()
     V = vrt_import.vrt()
     from conftest import MAPS, room_world
@@ -50,25 +54,29 @@ def main():
         ip, iv, cp, _ = V.camera_block(pos, yaw, pitch, W, H)
         ctx.set_camera(ip, iv, cp)
         ctx.set_params(ctx.default_params())
-        ctx.dispatch_timed(W, H, 0, H, V.MODE_FULL, d_rgba, d_id, 5)
-        frame_ms = float(np.median(ctx.dispatch_timed(W, H, 0, H, V.MODE_FULL, d_rgba, d_id, max(args.reps, 5))))
         opaque = V.tree_is_opaque(tex)
-        for n in SAMPLES:
-            ctx.accum_begin(W, H, 0)
-            ctx.accum_add(n)          # the first add: pass 1 on the opaque path, code object load
-            ctx.synchronize()
-            ts = []
-            for _ in range(args.reps):
-                t0 = time.perf_counter()
-                ctx.accum_add(n)
+        for mname in args.mode:
+            mode = V.MODES[mname]
+            ctx.dispatch_timed(W, H, 0, H, mode, d_rgba, d_id, 5)
+            frame_ms = float(np.median(ctx.dispatch_timed(W, H, 0, H, mode, d_rgba, d_id, max(args.reps, 5))))
+            for n in SAMPLES:
+                ctx.accum_begin(W, H, 0, mode=mode, jitter=args.jitter)
+                ctx.accum_add(n)          # the first add: pass 1 or the frame once per accumulation, code object load
                 ctx.synchronize()
-                ts.append((time.perf_counter() - t0) * 1e3)
-            ms = float(np.median(ts))
-            row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "n": n,
-                   "add_ms": round(ms, 4), "n_frames_ms": round(n * frame_ms, 4), "frame_ms": round(frame_ms, 4),
-                   "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
-            print(json.dumps(row), flush=True)
-            rows.append(row)
+                ts = []
+                for _ in range(args.reps):
+                    t0 = time.perf_counter()
+                    ctx.accum_add(n)
+                    ctx.synchronize()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                ms = float(np.median(ts))
+                row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "n": n,
+                       "add_ms": round(ms, 4), "n_frames_ms": round(n * frame_ms, 4), "frame_ms": round(frame_ms, 4),
+                       "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
+                if args.mode != ["full"] or args.jitter:
+                    row.update(mode=mname, jitter=bool(args.jitter))
+                print(json.dumps(row), flush=True)
+                rows.append(row)
     ctx.device_free(d_rgba)
     ctx.device_free(d_id)
     ctx.close()

@@ -24,6 +24,7 @@ OPT_RAY_TABLES, OPT_EMPTY_OCTANTS, OPT_DISPLAY_KERNEL, OPT_FULL_OPAQUE, OPT_HEAV
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL = 0, 1, 2
 MODES = {"primary": MODE_PRIMARY, "primary_shadow": MODE_PRIMARY_SHADOW, "full": MODE_FULL}
+ACCUM_JITTER = 1   # vrt_accum_begin_ex flags (include/vrt.h VRT_ACCUM_JITTER)
 
 
 class VrtError(RuntimeError):
@@ -249,6 +250,7 @@ def hip_lib():
                                            C.c_void_p, C.c_void_p]
         L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
+        L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
         L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -753,8 +755,13 @@ class Context:
         self._chk(L.vrt_find_voxels(self._h, n, c.ctypes.data if n else None, out.ctypes.data if n else None))
         return out[:, 0] != 0, out[:, 1:].copy()
 
-    def accum_begin(self, width, height, first_sample=0):
-        """(Re)start the progressive accumulation of VRT_MODE_FULL at initRNG sample index `first_sample` (vrt_accum_begin)."""
+    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False):
+        """(Re)start the progressive accumulation of `mode` at sample index `first_sample` (vrt_accum_begin_ex); jitter=True
+        moves each sample's ray inside the pixel (VRT_ACCUM_JITTER: anti-aliased frames)."""
+        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or mode not in (MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL):
+            raise ValueError(f"mode: expected MODE_PRIMARY, MODE_PRIMARY_SHADOW or MODE_FULL, got {mode!r}")
+        if not isinstance(jitter, (bool, np.bool_)) and not (isinstance(jitter, (int, np.integer)) and jitter in (0, 1)):
+            raise ValueError(f"jitter: expected a bool, got {jitter!r}")
         for name, v in (("width", width), ("height", height)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 1 << 30:
                 raise ValueError(f"{name}: expected a positive integer, got {v!r}")
@@ -762,7 +769,8 @@ class Context:
             raise ValueError(f"width * height: at most 2^30 pixels, got {width * height}")
         if isinstance(first_sample, bool) or not isinstance(first_sample, (int, np.integer)) or not 0 <= first_sample < 1 << 32:
             raise ValueError(f"first_sample: expected an integer in [0, 2^32), got {first_sample!r}")
-        self._chk(self._L.vrt_accum_begin(self._h, int(width), int(height), int(first_sample)))
+        self._chk(self._L.vrt_accum_begin_ex(self._h, int(width), int(height), int(mode), int(first_sample),
+                                             ACCUM_JITTER if jitter else 0))
         self._accum_shape = (int(height), int(width))
 
     def accum_add(self, n_samples=1):

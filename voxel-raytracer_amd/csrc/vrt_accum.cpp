@@ -1,7 +1,9 @@
-// vrt_accum.cpp -- progressive multi-sample accumulation of VRT_MODE_FULL (include/vrt.h vrt_accum_*): call-order checks, the
-// restart rule, the context's buffers, the resolve and the display pass on it. The samples themselves are enqueued by the
-// dispatcher (vrt_dispatch.cpp enqueue() with an AccumStep), which chooses between the sample-looped bounce and the general
-// kernel (vrt_accum.hip.h) as it chooses between the two forms of a frame.
+// vrt_accum.cpp -- progressive multi-sample accumulation (include/vrt.h vrt_accum_*): call-order checks, the restart rule, the
+// context's buffers, the resolve and the display pass on it. The samples themselves are enqueued by the dispatcher
+// (vrt_dispatch.cpp enqueue() with an AccumStep), which chooses between the sample-looped bounce and the general kernel
+// (vrt_accum.hip.h) -- or, for jittered samples, their jittered forms and the sample-looped primary kernels (vrt_jitter.hip.h) --
+// as it chooses between the forms of a frame. A jittered accumulation, or one of VRT_MODE_PRIMARY / _SHADOW, first renders the
+// mode's ordinary frame once: its id_dist is the resolve's, and without jitter its bytes are every sample's.
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
@@ -61,8 +63,15 @@ int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_
 extern "C" {
 
 int vrt_accum_begin(vrt_ctx *c, int width, int height, uint32_t first_sample) {
+    return vrt_accum_begin_ex(c, width, height, VRT_MODE_FULL, first_sample, 0u);
+}
+
+int vrt_accum_begin_ex(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, uint32_t flags) {
     int r = check_frame(c, width, height);
     if (r) return r;
+    if (mode != VRT_MODE_PRIMARY && mode != VRT_MODE_PRIMARY_SHADOW && mode != VRT_MODE_FULL)
+        return vrt_fail(c, VRT_E_INVALID, "vrt_accum_begin_ex: unknown mode");
+    if (flags & ~(uint32_t)VRT_ACCUM_JITTER) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_begin_ex: unknown flags");
     VRT_HIP(c, hipSetDevice(c->device));
     Accum &ac = c->accum;
     const size_t px = (size_t)width * (size_t)height;
@@ -83,8 +92,11 @@ int vrt_accum_begin(vrt_ctx *c, int width, int height, uint32_t first_sample) {
     ac.width = width;
     ac.height = height;
     ac.first = first_sample;
+    ac.mode = mode;
+    ac.flags = flags;
     ac.total = 0;
     ac.pass1 = false;
+    ac.frame = false;
     return VRT_OK;
 }
 
@@ -107,9 +119,22 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         take_inputs(c, ac);
         ac.total = 0;
         ac.pass1 = false;
+        ac.frame = false;
     }
-    const AccumStep step{ac.first + base, n_samples};
-    const int r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, VRT_MODE_FULL, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
+    const bool jitter = (ac.flags & VRT_ACCUM_JITTER) != 0u;
+    int r = VRT_OK;
+    if ((jitter || ac.mode != VRT_MODE_FULL) && !ac.frame) {   // the mode's unjittered frame, once per accumulation
+        r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream);
+        ac.frame = r == VRT_OK;
+    }
+    if (r == VRT_OK && !jitter && ac.mode != VRT_MODE_FULL) {   // every sample is that frame
+        const vrt::accum::Repeat q{ac.d_pass1, ac.d_sums, n_samples, (uint32_t)((size_t)ac.width * (size_t)ac.height)};
+        const hipError_t e = vrt::launch::accum_repeat(q, c->stream);
+        if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    } else if (r == VRT_OK) {
+        const AccumStep step{ac.first + base, n_samples, jitter};
+        r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
+    }
     if (r) {   // what this add left in the sums is unknown: the next add starts again
         ac.total = 0;
         return r;

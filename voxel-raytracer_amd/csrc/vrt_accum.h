@@ -1,4 +1,4 @@
-// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h), shared by the host side (vrt_accum.cpp,
+// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h, vrt_jitter.hip.h), shared by the host side (vrt_accum.cpp,
 // vrt_dispatch.cpp) and the launch file (vrt_launch_accum.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,14 @@ struct Resolve {
     const uint32_t *sums;
     uint32_t *out_rgba;
     uint32_t n;                  // samples in the sums (>= 1)
+    uint32_t pixels;
+};
+
+// A mode without jitter (vrt_jitter.hip.h repeat_kernel): n more samples that are all the frame in frame_rgba.
+struct Repeat {
+    const uint32_t *frame_rgba;
+    uint32_t *sums;
+    uint32_t n;
     uint32_t pixels;
 };
 

@@ -208,6 +208,34 @@ VRT_DEV F3 primary_ray_dir(const KArgs &a, const View &vw, int px, int py) {
     return scale3(d, 1.0f / __builtin_sqrtf(dot3(d, d)));
 }
 
+// Sub-pixel jitter of the progressive accumulation (include/vrt.h vrt_accum_begin_ex, VRT_ACCUM_JITTER): sample k moves the
+// pixel's ray from its corner by (jitter_x(k), jitter_y(k)) in [0, 1)^2, a (0,2)-sequence of multiples of 2^-24 (exact in
+// float32): van der Corput in base 2 for x, the second Sobol' dimension for y. Sample 0 is (0, 0), the frame's own ray.
+VRT_DEV float jitter_x(uint32_t k) { return (float)(__builtin_bitreverse32(k) >> 8) * 0x1p-24f; }
+VRT_DEV float jitter_y(uint32_t k) {
+    uint32_t y = 0u, v = 1u << 31;
+    for (uint32_t i = k; i; i >>= 1, v ^= v >> 1)
+        if (i & 1u) y ^= v;
+    return (float)(y >> 8) * 0x1p-24f;
+}
+
+// The shader's ray generation with float(px) + jitter_x(sample) and float(py) + jitter_y(sample) (one rounded addition
+// each) in place of float(px) and float(py); everything after them is primary_ray_dir()'s own form, one operation at a time
+// (the per-projection tables hold the pixel corner's values only).
+VRT_DEV F3 jittered_ray_dir(const KArgs &a, const View &vw, int px, int py, uint32_t sample) {
+    const float fx = (float)px + jitter_x(sample), fy = (float)py + jitter_y(sample);
+    float u = (fx / (float)a.width) * 2.0f - 1.0f;
+    float v = (fy / (float)a.height) * 2.0f - 1.0f;
+    float view[4];
+    mat_vec(vw.inv_proj, u, v, -1.0f, 1.0f, view);
+    if (__builtin_fabsf(view[3]) > 1e-6f) { float w = view[3]; view[0] = view[0] / w; view[1] = view[1] / w; view[2] = view[2] / w; view[3] = view[3] / w; }
+    F3 vd = normalize3(F3{view[0], view[1], view[2]});
+    float wd4[4];
+    mat_vec(vw.inv_view, vd.x, vd.y, vd.z, 0.0f, wd4);
+    const F3 d = normalize3(F3{wd4[0], wd4[1], wd4[2]});
+    return scale3(d, 1.0f / __builtin_sqrtf(dot3(d, d)));
+}
+
 // traversals whose shadow() takes the dispatcher's LightSetup declare `static constexpr bool kHostLight = true`
 template <class T, class = void> struct host_light { static constexpr bool value = false; };
 template <class T> struct host_light<T, decltype((void)T::kHostLight)> { static constexpr bool value = T::kHostLight; };
@@ -223,11 +251,14 @@ struct Seed { F3 hp; uint32_t word; float iof; };   // the same in registers (MO
 
 // One pixel: ray generation (comp:624-641), primary-ray pathTrace, packing of the two outputs.
 // TRAV supplies the traversal: march(), shadow(). MODE: 0 primary, 1 primary + shadow ray. seed (MODE 1 only): see above.
-template <int MODE, class TRAV>
+// JIT: the ray of jittered sample `sample` (jittered_ray_dir(); the progressive accumulation, vrt_jitter.hip.h).
+template <int MODE, class TRAV, bool JIT = false>
 VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                         uint32_t *seed = nullptr, Seed *seed_regs = nullptr) {
+                         uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u) {
     const float kPI = 3.14159265359f;
-    const F3 ray_dir = primary_ray_dir(a, vw, px, py);
+    F3 ray_dir;
+    if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
+    else ray_dir = primary_ray_dir(a, vw, px, py);
     F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
 
     int voxel_id = 0;
@@ -388,7 +419,7 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
 }
 
 namespace full {  // MODE 2 and 3 (3: the last diffuse bounce of a pixel goes to a queue for bounce_kernel), defined in vrt_full.hip.h
-template <class TRAV, bool DEFER>
+template <class TRAV, bool DEFER, bool JIT = false>   // JIT: the ray of jittered sample `sample` (jittered_ray_dir())
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
                                  uint32_t queue, uint32_t out_offset, uint32_t sample = 0u);
 // pass 2 of the two-pass form: the diffuse bounce of a seeded pixel; false when the pixel has none (rgba untouched)

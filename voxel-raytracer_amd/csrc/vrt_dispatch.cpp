@@ -160,6 +160,12 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         if (v.trav == 4 && VRT_AB && c->full_split) v.trav = 3;
         if (v.trav >= 3) { v.block = (v.block == 64 || !VRT_AB) ? 64 : 256; v.wpe = 5; }
         else { v.block = 256; v.wpe = 1; }
+    } else if (acc) {
+        // the accumulation's primary kernels (vrt_launch_accum.hip) exist in one shape per traversal: the frame kernels' default
+        // one for the wide traversals, the record-array fallbacks' for the others
+        v.use_lds = false; v.tw = 8; v.lds_cap = 0; v.blocks_per_cu = 0;
+        if (v.trav >= 3) { v.block = 64; v.wpe = v.trav == 4 ? 7 : 6; }
+        else { v.block = 256; v.wpe = 1; }
     } else if (mode == VRT_MODE_PRIMARY_SHADOW && c->variant == 20 && v.trav == 3) {
         v.wpe = 7;  // round 1's default: the shadow march was 1.5 % faster seven waves deep, the primary one six deep
     }
@@ -358,7 +364,24 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         q.pass1_rgba = ac.d_pass1;
         q.out_id = ac.d_id;
         e = hipSuccess;
-        if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
+        if (acc->jitter) {   // every sample has a ray of its own: jittered_ray_dir(), no per-projection tables
+            vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
+            vs.v[0].gen_z = 0.0f;
+            vs.v[0].gen_fast = 0u;
+            q.first = acc->first;
+            q.n = acc->n;
+            if (mode != VRT_MODE_FULL) {   // one launch, the samples looped in the lanes
+                e = vrt::launch::jitter_primary(mode, v, a, vs, q, (int)grid, s);
+            } else if (two_pass) {         // MODE 6's chain per sample, looped in the lanes
+                e = vrt::launch::jitter_opaque(a, vs, q, (int)grid, s);
+            } else {                       // the general path tracer, one launch per sample
+                for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
+                    q.first = acc->first + k;
+                    q.n = 1u;
+                    e = vrt::launch::jitter_full(v, a, vs, q, (int)grid, s);
+                }
+            }
+        } else if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
             a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
             if (!ac.pass1) {
                 vs.v[0].out_rgba = ac.d_pass1;

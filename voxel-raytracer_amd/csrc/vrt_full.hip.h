@@ -187,15 +187,18 @@ VRT_DEV void defer_bounce(const KArgs &a, uint32_t queue, uint32_t out_offset, F
 // pixel -- nothing is accumulated after it -- so it goes to a queue instead, together with the colour summed so far;
 // bounce_kernel (vrt_bounce.hip.h) marches it among full waves of such rays and writes the pixel. A bounce ray (depth 1)
 // spawns nothing (comp:590-594), so the queue is one level deep. The accumulation order per pixel is unchanged.
-// sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...)
-template <class TRAV, bool DEFER>
+// sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
+// with JIT also the jittered sample whose ray is traced (jittered_ray_dir(), vrt_jitter.hip.h)
+template <class TRAV, bool DEFER, bool JIT>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
                                  uint32_t queue, uint32_t out_offset, uint32_t sample) {
     const float kPI = 3.14159265359f;
     const float sky[3] = {0.5f, 0.7f, 1.0f};
     const float kSun = 3.0f;
     uint32_t rng = rng_init(px, py, sample);
-    const F3 ray_dir = primary_ray_dir(a, vw, px, py);
+    F3 ray_dir;
+    if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
+    else ray_dir = primary_ray_dir(a, vw, px, py);
     const F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
 
     int voxel_id = 0;

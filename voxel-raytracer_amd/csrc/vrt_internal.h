@@ -6,7 +6,7 @@
 //   vrt_display.cpp    the display pass and the fused frame call
 //   vrt_patch.cpp      edits without re-upload: patch plan / apply / batches / compaction
 //   vrt_query.cpp      world queries on the device tree: ray casts (picking), voxel lookups
-//   vrt_accum.cpp      progressive multi-sample accumulation of VRT_MODE_FULL: begin / add / resolve, the restart rule
+//   vrt_accum.cpp      progressive multi-sample accumulation (any mode, sub-pixel jitter): begin / add / resolve, the restart rule
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts)
@@ -201,12 +201,15 @@ struct vrt_ctx {
         uint32_t first = 0;                      // initRNG sampleIndex of the first sample in the sums
         uint32_t total = 0;                      // samples in the sums
         bool pass1 = false;                      // d_seed and d_pass1 hold pass 1 of the current samples (opaque path)
+        int mode = VRT_MODE_FULL;                // vrt_accum_begin_ex: the mode and VRT_ACCUM_* flags of the samples
+        uint32_t flags = 0;
+        bool frame = false;                      // d_pass1 and d_id hold the mode's unjittered frame (jitter, or modes 0 / 1)
         // what every sample depends on, as it was at the first sample in the sums
         float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
         vrt_params params{};
         uint64_t tree_gen = 0;
         uint32_t *d_sums = nullptr;              // 4 words per pixel
-        uint32_t *d_pass1 = nullptr;             // pass 1's rgba8 (opaque path)
+        uint32_t *d_pass1 = nullptr;             // pass 1's rgba8 (opaque path), or the unjittered frame's (`frame`)
         int2 *d_id = nullptr;                    // the frame's (voxel ID, dist)
         uint32_t *d_seed = nullptr;              // pass 1's seeds, tile-major (kSeedPlanesHost words per pixel)
         size_t pixels = 0, seed_tiles = 0;       // capacities
@@ -246,7 +249,8 @@ int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-bu
 // vrt_dispatch.cpp
 // AccumStep: instead of rendering a frame, add samples first .. first + n - 1 of VRT_MODE_FULL to the context's accumulation
 // (vrt_accum.cpp; whole frame, the context's camera, d_rgba / d_id unused)
-struct AccumStep { uint32_t first, n; };
+// (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_jitter.hip.h)
+struct AccumStep { uint32_t first, n; bool jitter; };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
 SchedState *sched_state(vrt_ctx *c, hipStream_t s, int width, int n_rows, int row0, int row_stride, int tile_rows, int mode,

@@ -60,6 +60,14 @@ hipError_t find_voxels(const KArgs &a, const query::PointArgs &q, hipStream_t s)
 hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
 hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
 hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s);
+// The jittered samples and the primary modes (vrt_jitter.hip.h), whole frames, one 8 x 8 tile per wave, grid =
+// tiles / waves per workgroup of `v`. jitter_primary: q.n samples of `mode` (0 or 1), `v` as the dispatcher normalises it for an
+// accumulation (v4 64/7, v3 64/6, v2 or v1 256/1). jitter_opaque: q.n samples of the opaque full path tracer (v4, 64 lanes).
+// jitter_full: one sample (q.first) of the general full path tracer in the shapes of accum_full. accum_repeat: n frames' bytes.
+hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
+hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
+hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
+hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s);
 
 #if VRT_AB
 // vrt_launch_ab.hip -- the full path tracer as two kernels with cross-wave repacking (ab/vrt_bounce.hip.h): an experiment that lost

@@ -1,5 +1,8 @@
 // vrt_launch_accum.hip -- progressive accumulation of VRT_MODE_FULL (vrt_accum.hip.h): the sample-looped bounce kernel of opaque
-// scenes, the general kernel with a sample index in the shapes trace_full() launches trace_kernel<2> in, and the resolve.
+// scenes, the general kernel with a sample index in the shapes trace_full() launches trace_kernel<2> in, and the resolve. Then the
+// jittered samples and the primary modes (vrt_jitter.hip.h): the sample-looped primary / primary + shadow kernel in the
+// traversals a frame of those modes takes, the looped opaque full path tracer, the general full path tracer with a jittered ray
+// in the shapes of accum_full, and the repeat of a frame.
 #include <hip/hip_runtime.h>
 
 #include "vrt_launch.h"
@@ -8,6 +11,7 @@
 #include "vrt_kernels_wide.hip.h"
 #include "vrt_kernels_v4.hip.h"
 #include "vrt_accum.hip.h"
+#include "vrt_jitter.hip.h"
 
 namespace vrt {
 namespace launch {
@@ -29,6 +33,44 @@ hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const
 hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s) {
     if (q.pixels == 0u) return hipSuccess;
     hipLaunchKernelGGL(accum::accum_resolve_kernel, dim3((q.pixels + 255u) / 256u), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
+namespace {
+template <int MODE>
+hipError_t primary(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
+    if (v.trav == 4 && v.block == 64) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v4::Trav, 64, 7>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 3 && v.block == 64) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v3::Trav, 64, 6>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 2 && v.block == 256) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v2::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 1 && v.block == 256) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v1::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
+    if (mode == VRT_MODE_PRIMARY) return primary<0>(v, a, vs, q, grid, s);
+    if (mode == VRT_MODE_PRIMARY_SHADOW) return primary<1>(v, a, vs, q, grid, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
+    hipLaunchKernelGGL((accum::opaque_jitter_kernel<v4::Trav, 6>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    return hipGetLastError();
+}
+
+hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
+    if (v.trav == 4) hipLaunchKernelGGL((accum::full_jitter_kernel<v4::TravAny, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 3 && v.block == 64) hipLaunchKernelGGL((accum::full_jitter_kernel<v3::Trav, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 2 && v.block == 256) hipLaunchKernelGGL((accum::full_jitter_kernel<v2::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 1 && v.block == 256) hipLaunchKernelGGL((accum::full_jitter_kernel<v1::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s) {
+    if (q.pixels == 0u) return hipSuccess;
+    hipLaunchKernelGGL(accum::repeat_kernel, dim3((q.pixels + 255u) / 256u), dim3(256), 0, s, q);
     return hipGetLastError();
 }
 
