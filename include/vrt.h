@@ -60,7 +60,7 @@ typedef struct vrt_scene_info {
     uint32_t n_internal;        /* internal nodes */
     uint32_t n_leaves;          /* leaf nodes */
     uint32_t max_depth;         /* deepest node below the root */
-    uint32_t lds_records;       /* records of the level-order prefix staged in LDS */
+    uint32_t lds_records;       /* always 0 (no kernel stages records in LDS) */
     uint32_t reserved;
 } vrt_scene_info;
 
@@ -375,9 +375,8 @@ int vrt_synchronize(vrt_ctx *ctx);
 void *vrt_stream(vrt_ctx *ctx);
 int vrt_device(const vrt_ctx *ctx);
 
-/* kernel variant selection (0 = default). The shipped library holds the default and the fallbacks its dispatcher may
- * take (variants 0, 1, 4, 20, 22); the A/B variants exist only in a `make AB=1` build: vrt_variant_available() says
- * which, vrt_set_variant() returns VRT_E_INVALID for the others. */
+/* kernel variant selection (0 = default). The library holds the default and the fallbacks its dispatcher may take
+ * (variants 0, 1, 4, 20, 22): vrt_variant_available() says which, vrt_set_variant() returns VRT_E_INVALID for the others. */
 int vrt_set_variant(vrt_ctx *ctx, int variant);
 int vrt_variant_available(int variant);
 
@@ -401,8 +400,8 @@ int vrt_set_tile_scheduling(vrt_ctx *ctx, int period);
  *   VRT_OPT_DISPLAY_KERNEL 0 (default): the display pass sums two pixels per lane and every wave takes the cheaper of two walks over its
  *                          staged window: the rows and column segments any of its 64 lanes needs, the same for all lanes (faces that fill
  *                          the window: close-ups), or every pixel the box its own voxel face occupies (faces small against the window:
- *                          1080p dragon frame 0.186 -> 0.123 ms with the staging changes that came with it); 2 / 3: always the first / the second walk (A/B, tests); 1: one pixel per
- *                          lane (round 1's kernel; exists in `make AB=1` builds only, VRT_E_INVALID otherwise).
+ *                          1080p dragon frame 0.186 -> 0.123 ms with the staging changes that came with it); 2 / 3: always the first / the second walk (A/B, tests);
+ *                          any other value: VRT_E_INVALID.
  *   VRT_OPT_FULL_OPAQUE    VRT_MODE_FULL where pathTrace cannot branch: in a scene without translucent voxels seen from empty space it is
  *                          the primary ray, a shadow ray and ONE diffuse bounce ray that spawns nothing (comp:573-616), so the 8-deep ray
  *                          stack is never used. 6 (default): such launches run a kernel that holds no stack -- primary + shadow stage, then

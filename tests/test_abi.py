@@ -21,11 +21,13 @@ def test_hip_library_exports_vrt_h(V):
     for n in names:
         assert hasattr(lib, n), f"libvrt_hip.so does not export {n}"
     assert b"gfx950" in V.hip_lib().vrt_version()
-    # ... and nothing else: no test hooks, no internals (csrc/vrt_exports.map); a `make AB=1` build adds its two vrt_ab_ switches
+    # ... and nothing else: no test hooks, no internals (csrc/vrt_exports.map)
     exported = sorted(l.split()[-1] for l in os.popen(f"nm -D --defined-only {V.HIP_LIB}").read().splitlines() if " T " in l)
-    extra = [n for n in exported if n not in names and not n.startswith("vrt_ab_")]
+    extra = [n for n in exported if n not in names]
     assert not extra, f"libvrt_hip.so exports symbols include/vrt.h does not declare: {extra}"
     assert not any("debug" in n for n in exported)
+    # the kernel variants vrt_set_variant() accepts (vrt_variant_available() needs no device)
+    assert V.available_variants() == [0, 1, 4, 20, 22]
 
 
 def test_test_support_library_is_separate(V):

@@ -34,10 +34,9 @@ def main():
     d_rgba = torch.from_numpy(rgba.view(np.int32).reshape(H, W)).cuda()
     d_id = torch.from_numpy(idd).cuda()
     outs = []
-    # (VRT_OPT_DISPLAY_KERNEL, scheduling period): 1 = one pixel per lane (A/B builds only); 2 / 3 = every wave walks the wave's common
-    # rows / every pixel its own box; 0 = each wave the cheaper of the two (shipped)
+    # (VRT_OPT_DISPLAY_KERNEL, scheduling period): 2 / 3 = every wave walks the wave's common rows / every pixel its own box;
+    # 0 = each wave the cheaper of the two (shipped)
     kinds = ((2, 0), (3, 0), (0, 0), (2, 16), (3, 16), (0, 16))
-    if len(V.available_variants()) > 5: kinds = ((1, 0),) + kinds
     # DENOISE_CHECK: the displayed frame against the oracle's committed hash, where tests/golden/frames.json holds this frame (the oracle
     # itself is run by tests/ only: tests/test_gpu_parity.py compares the display pass with its quad.frag restatement on rendered and synthetic fields)
     want = None
@@ -47,7 +46,7 @@ def main():
             if g.get("map") == name and g.get("width") == W and g.get("height") == H and g.get("mode") == 2 and "shown_fnv1a64" in g and \
                     "%016x" % V.fnv1a64(rgba) == g["rgba_fnv1a64"]:
                 want = g["shown_fnv1a64"]
-    for variant, period in kinds:   # one pixel per lane; two; two with feedback tile scheduling
+    for variant, period in kinds:   # without, then with feedback tile scheduling
         ctx.set_denoise_variant(variant)
         ctx.set_tile_scheduling(period)
         d_out = torch.zeros_like(d_rgba)

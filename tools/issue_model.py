@@ -96,8 +96,8 @@ def half_share(mode):
     """static share of half/quarter-rate kinds among the vector instructions inside the loops of the kernel a workload of `mode` ran
     (mode "full_opaque": the stack-free full path tracer, trace_kernel<6, ...>)"""
     src = {"primary": "vrt_launch_primary.hip", "primary_shadow": "vrt_launch_shadow.hip", "full": "vrt_launch_full.hip", "full_opaque": "vrt_launch_full.hip"}[mode]
-    sym = {"primary": "trace_kernelILi0ENS_2v45TravTILb1EEELi8ELi64ELi7ELb0ELi1EEE", "primary_shadow": "trace_kernelILi1ENS_2v45TravTILb1EEELi8ELi64ELi7ELb0ELi1EEE",
-           "full": "trace_kernelILi2ENS_2v45TravTILb0EEELi8ELi64ELi5ELb0ELi1EEE", "full_opaque": "trace_kernelILi6ENS_2v45TravTILb1EEELi8ELi64ELi6ELb0ELi1EEE"}[mode]
+    sym = {"primary": "trace_kernelILi0ENS_2v45TravTILb1EEELi64ELi7ELi1EEE", "primary_shadow": "trace_kernelILi1ENS_2v45TravTILb1EEELi64ELi7ELi1EEE",
+           "full": "trace_kernelILi2ENS_2v45TravTILb0EEELi64ELi5ELi1EEE", "full_opaque": "trace_kernelILi6ENS_2v45TravTILb1EEELi64ELi6ELi1EEE"}[mode]
     csrc = os.path.join(ROOT, "voxel-raytracer_amd", "csrc")
     asm = f"/tmp/issue_model_{mode}.s"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
@@ -128,13 +128,13 @@ def build(summary_path):
     for wl, kernels in S.items():
         m = re.match(r"(.+)_(primary_shadow|primary|full)_(\d+)x(\d+)$", wl)
         mp, mode, W, H = m.group(1), m.group(2), int(m.group(3)), int(m.group(4))
-        # the ordered flavour (SCHED = 1: "Lb0ELi1EEE") is what a frame loop runs; fall back to the plain one
+        # the ordered flavour (SCHED = 1, the last template argument: "ELi1EEEv") is what a frame loop runs; fall back to the plain one
         pick = None
         for k in kernels:
-            if "trace_kernel" in k and (", 1>" in k or "Lb0ELi1E" in k):
+            if "trace_kernel" in k and (", 1>" in k or "ELi1EEEv" in k):
                 pick = k
         if pick is None:
-            pick = next((k for k in kernels if "trace_kernel" in k and (", 0>" in k or "Lb0ELi0E" in k)), None)
+            pick = next((k for k in kernels if "trace_kernel" in k and (", 0>" in k or "ELi0EEEv" in k)), None)
         if pick is None:
             continue
         c = kernels[pick]["counters"]

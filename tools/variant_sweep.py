@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--iters", type=int, default=30)
-    ap.add_argument("--variants", default="0,1,2,3,4,5,6,7,8,9")
+    ap.add_argument("--variants", default="0,1,4,20,22")
     ap.add_argument("--modes", default="0,1")
     args = ap.parse_args()
     V = vrt_import.vrt()
@@ -46,7 +46,7 @@ def main():
             ref.setdefault(mode, h)
             print(json.dumps({"map": args.map, "mode": mode, "variant": v, "median_ms": round(float(np.median(ms)), 4),
                               "min_ms": round(float(ms.min()), 4), "Mrays/s": round(W * H / float(np.median(ms)) / 1e3, 1),
-                              "same_pixels": h == ref[mode], "lds_records": ctx.scene_info()["lds_records"]}), flush=True)
+                              "same_pixels": h == ref[mode]}), flush=True)
 
 
 if __name__ == "__main__":

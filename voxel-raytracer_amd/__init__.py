@@ -254,9 +254,6 @@ def hip_lib():
         L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "vrt_ab_set_full_split"):   # `make AB=1` builds only
-            L.vrt_ab_set_full_split.argtypes = [C.c_void_p, C.c_int]
-            L.vrt_ab_set_bounce.argtypes = [C.c_void_p, C.c_int, C.c_int]
         _hip = L
     return _hip
 
@@ -293,7 +290,7 @@ def test_lib():
 
 
 def available_variants(upto=64):
-    """kernel variants compiled into libvrt_hip.so (the shipped ones; all of them in a `make AB=1` build)"""
+    """the kernel variants vrt_set_variant() accepts (0, 1, 4, 20, 22)"""
     L = hip_lib()
     return [v for v in range(upto) if L.vrt_variant_available(v)]
 
@@ -914,19 +911,8 @@ class Context:
         """caller-owned device buffers for the default kernel's group order / per-tile ticks (vrt_set_tile_order)"""
         self._chk(self._L.vrt_set_tile_order(self._h, 1 if enable else 0, d_group_order, d_tile_cost))
 
-    def set_full_split(self, on):
-        """`make AB=1` builds: the full path tracer as two kernels with cross-wave repacking (off by default)"""
-        if not hasattr(self._L, "vrt_ab_set_full_split"):
-            if on:
-                raise VrtError("the two-kernel full path tracer exists in A/B builds only (make AB=1)")
-            return
-        self._chk(self._L.vrt_ab_set_full_split(self._h, 1 if on else 0))
-
-    def set_bounce(self, refill_below, waves_per_simd):
-        self._chk(self._L.vrt_ab_set_bounce(self._h, refill_below, waves_per_simd))
-
     def set_denoise_variant(self, v):
-        """VRT_OPT_DISPLAY_KERNEL: 0 = two pixels per lane, each wave the cheaper walk (default); 2 / 3 = one walk forced; 1 = one pixel per lane (A/B builds only)."""
+        """VRT_OPT_DISPLAY_KERNEL: 0 = each wave the cheaper of its two walks (default); 2 / 3 = one walk forced."""
         self.set_option(OPT_DISPLAY_KERNEL, v)
 
     def synchronize(self):

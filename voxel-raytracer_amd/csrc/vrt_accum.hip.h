@@ -42,7 +42,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
     __shared__ uint32_t s_seed[kSeedPlanes][64];
     __shared__ uint32_t s_sum[3][64];
     typename TRAV::Ctx tc_;
-    TRAV::template block_init<64>(a, nullptr, tc_);
+    TRAV::block_init(a, tc_);
     const int lane = threadIdx.x & 63;
     const int tiles_x = (a.width + 7) / 8;
     const int tile = blockIdx.x;
@@ -89,10 +89,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
 // The general full path tracer with initRNG's sampleIndex = q.first (q.n == 1): trace_kernel<2>'s tiles, one pixel per lane.
 template <class TRAV, int BLOCK, int WPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const Args q) {
-    extern __shared__ __attribute__((aligned(16))) uint2 lds_dyn[];
     typename TRAV::Ctx tc_;
-    TRAV::template block_init<BLOCK>(a, lds_dyn, tc_);
-    if constexpr (TRAV::kStagesLds) __syncthreads();
+    TRAV::block_init(a, tc_);
     const int lane = threadIdx.x & 63;
     const int tiles_x = (a.width + 7) / 8;
     const int tile = (int)blockIdx.x * (BLOCK / 64) + (int)(threadIdx.x >> 6);
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     uint32_t rgba;
     int2 idd;
     LateOut lo;
-    full::trace_pixel_full<TRAV, false>(a, vs.v[0], tc_, px, py, rgba, idd, lo, 0u, 0u, q.first);
+    full::trace_pixel_full<TRAV>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
     const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
     uint32_t r = 0u, g = 0u, b = 0u;
     add_bytes(rgba, r, g, b);

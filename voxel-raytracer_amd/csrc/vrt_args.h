@@ -70,7 +70,7 @@ struct KArgs {
     int row_mode;             // 1: one row tile (y = row0 + j); 2: tile_rows == 8 == tile height (y = row0 + ty * row_stride + ly); 0: divide
     const uint2 *nodes;       // level-ordered records (vrt_layout.h), root = record 0
     uint32_t n_records;
-    uint32_t lds_records;     // prefix of `nodes` staged in LDS by each workgroup
+    uint32_t lds_records;     // always 0 and read by no kernel: the word keeps the kernarg offsets (late_args(), kernarg_probe)
     // wide layout (vrt_layout.h): 64 cells per node; roots = octree records where a wide tree starts
     const uint2 *cells;
     const uint2 *cells4;      // the same cells in the form of the v4 kernels (vrt_layout.h to_cell4)
@@ -93,18 +93,13 @@ struct KArgs {
     // kSplitMaxGroups; 0 when the heaviest tile does not outlast its even share of the frame -- no tail to shorten). The grid then holds
     // kSplitMaxGroups * kGroupTiles * (kSplitParts - 1) workgroups more than tiles; the ones no group needs leave at once. null: none.
     const uint32_t *split_count;
-    // Deferred diffuse bounces of the full path tracer (MODE 3 of trace_kernel, vrt_bounce.hip.h): kDeferQueues queues of
-    // defer_cap ray records each, structure of arrays (plane p of queue q starts at defer_rec + (p * kDeferQueues + q) * defer_cap),
-    // defer_count[q * kDeferStride] = records in queue q, defer_count[(kDeferQueues + q) * kDeferStride] = records already
-    // handed out by bounce_kernel: every counter in a cache line of its own (atomics on one line are served one at a time).
+    // MODE 4 / 5 of trace_kernel and the accumulation of opaque scenes: the two-pass full path tracer's seeds (kSeedPlanesHost
+    // words per pixel, tile-major). defer_count and defer_cap are read by no kernel; they keep the kernarg layout.
     float *defer_rec;
     uint32_t *defer_count;
     uint32_t defer_cap;
 };
 constexpr uint32_t kSeedPlanesHost = 5;  // words per pixel of the two-pass full path tracer's seed (vrt_common.hip.h kSeedPlanes)
-constexpr uint32_t kDeferQueues = 64;   // a wave appends to queue (tile % 64): sixty-four counters share the atomic traffic
-constexpr uint32_t kDeferStride = 64;   // words between two counters: 256 bytes
-constexpr uint32_t kDeferPlanes = 19;   // o[3] d[3] tint[3] fc[3] iof weight mc[3] md out_offset
 
 namespace v3 { constexpr int kAnchorShift = 6; }  // restart point of the wide traversals: the wide node of side 64 the ray is in
 

@@ -179,9 +179,8 @@ struct LateOut {
     uint32_t *out_rgba;
     int2 *out_id;
     int width, compact;
-    bool skip_rgba;   // MODE 3: the pixel's colour is finished by bounce_kernel
 };
-VRT_DEV LateOut late_out(LateArgs la, LateView lv) { return LateOut{lv->out_rgba, lv->out_id, la->width, la->compact, false}; }
+VRT_DEV LateOut late_out(LateArgs la, LateView lv) { return LateOut{lv->out_rgba, lv->out_id, la->width, la->compact}; }
 
 // Ray generation (comp:624-641) and pathTrace's own normalisation of the direction (comp:441). Two forms, chosen per view
 // by the dispatcher (wave-uniform): the shader's operations one by one, or -- View::gen_fast -- the same operations with
@@ -418,41 +417,35 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
     }
 }
 
-namespace full {  // MODE 2 and 3 (3: the last diffuse bounce of a pixel goes to a queue for bounce_kernel), defined in vrt_full.hip.h
-template <class TRAV, bool DEFER, bool JIT = false>   // JIT: the ray of jittered sample `sample` (jittered_ray_dir())
+namespace full {  // MODE 2, defined in vrt_full.hip.h
+template <class TRAV, bool JIT = false>   // JIT: the ray of jittered sample `sample` (jittered_ray_dir())
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t queue, uint32_t out_offset, uint32_t sample = 0u);
+                                 uint32_t sample = 0u);
 // pass 2 of the two-pass form: the diffuse bounce of a seeded pixel; false when the pixel has none (rgba untouched)
 template <class TRAV>
 __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, Seed seed, uint32_t &rgba, uint32_t sample = 0u);
 }
 
-// One lane per pixel; a wave covers a TW x TH pixel tile (TW*TH == 64) so the 64 rays of a wave stay spatially
-// coherent. One tile per wave (PERSIST: a fixed grid walks the tiles with a grid-stride loop instead).
+// One lane per pixel; a wave covers an 8 x 8 pixel tile so the 64 rays of a wave stay spatially coherent. One tile per wave.
 // WPE: waves per SIMD the register allocator must leave room for (1 = no constraint beyond BLOCK). It also bounds
 // the SCALAR registers: a SIMD admits floor(800 / (ceil(sgprs / 16) * 16 + 16)) waves (MI355X_MICROARCH.md,
 // "Residency") -- 6 with the 106 this kernel takes when unconstrained, whatever its 67 vector registers would
 // allow -- and amdgpu_waves_per_eu(7) makes the compiler stay within the 96 that admit 7.
 // SCHED: feedback scheduling flavours (KArgs::group_order / tile_cost).
-template <int MODE, class TRAV, int TW, int BLOCK, int WPE = 1, bool PERSIST = false, int SCHED = 0>
+template <int MODE, class TRAV, int BLOCK, int WPE = 1, int SCHED = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void trace_kernel(const KArgs a, const ViewSet vs) {
-    extern __shared__ __attribute__((aligned(16))) uint2 lds_dyn[];
-    constexpr int TH = 64 / TW;
+    constexpr int TW = 8, TH = 8;
     constexpr int WAVES = BLOCK / 64;
     typename TRAV::Ctx tc_;
-    TRAV::template block_init<BLOCK>(a, lds_dyn, tc_);
-    // only the traversals that stage records in LDS have anything to wait for: the others start tracing as soon
-    // as the wave is launched, without meeting the other waves of the workgroup
-    if constexpr (TRAV::kStagesLds) __syncthreads();
+    TRAV::block_init(a, tc_);
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int tiles_x = (a.width + TW - 1) / TW;
     const int tiles_y = (a.n_rows + TH - 1) / TH;
     const int n_tiles = tiles_x * tiles_y;
     int lx = lane % TW, ly = lane / TW;
-    // One tile per wave and no loop unless PERSIST: without the back edge the kernel arguments need not stay live
-    // after ray generation, which is worth ~19 VGPRs (88 -> 69) and two thirds of the SGPR spills on gfx950.
-    static_assert(!(PERSIST && SCHED), "the scheduled flavours trace one tile per wave");
+    // One tile per wave and no loop: without the back edge the kernel arguments need not stay live after ray generation, which
+    // is worth ~19 VGPRs (88 -> 69) and two thirds of the SGPR spills on gfx950 (measured against a grid-stride loop).
     int first = blockIdx.x * WAVES;  // first tile of this workgroup
     bool part_wave = false;          // KArgs::split_count: this wave traces one row of its tile
     if constexpr (SCHED & 1) {
@@ -462,7 +455,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         // long as its longest wave -- 79 rays one after the other behind the glass ball of the reference's room, every round as long
         // as the longest of the wave's 64 marches (profiles/r03_room_critical_path.txt) -- so the few heaviest groups are traced as
         // kSplitParts waves per tile, one row of 8 pixels each: the longest of 8 marches instead of 64 per round, 23 % off that wave.
-        constexpr bool kSplit = MODE == 2 && WAVES == 1 && TW == 8;   // SCHED 1 and 3: a measuring launch under an order splits like the others
+        constexpr bool kSplit = MODE == 2 && WAVES == 1;   // SCHED 1 and 3: a measuring launch under an order splits like the others
         uint32_t wg = blockIdx.x;
         if constexpr (kSplit) {
             const uint32_t n_split = a.split_count ? *a.split_count : 0u;
@@ -483,7 +476,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     }
     unsigned long long t_begin = 0;
     if constexpr (SCHED & 2) t_begin = __builtin_readcyclecounter();
-    for (int tile = first + wave; tile < n_tiles; tile += gridDim.x * WAVES) {
+    const int tile = first + wave;
+    if (tile < n_tiles) {
         int tx, ty;
         if (a.tiles_x_magic) {
             ty = (int)__umulhi((uint32_t)tile, a.tiles_x_magic);
@@ -497,13 +491,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         if (px < a.width && j < a.n_rows) {
             int py;
             if (a.row_mode == 1) py = a.row0 + j;
-            else if (a.row_mode == 2 && TH == 8) py = a.row0 + ty * a.row_stride + ly;
+            else if (a.row_mode == 2) py = a.row0 + ty * a.row_stride + ly;
             else py = a.row0 + (j / a.tile_rows) * a.row_stride + (j % a.tile_rows);
             uint32_t rgba;
             int2 idd;
             const View &vw = vs.v[blockIdx.y];
-            LateOut lo;  // MODE 1, 2, 3: the output side of the arguments, re-read after the trace rather than kept in registers across it
-            lo.skip_rgba = false;
+            LateOut lo;  // MODE 1, 2: the output side of the arguments, re-read after the trace rather than kept in registers across it
             if constexpr (MODE == 5) {   // pass 2 of the two-pass full path tracer: only the colour of seeded pixels is (re)written
                 const uint32_t *sp = reinterpret_cast<const uint32_t *>(a.defer_rec) + ((size_t)tile * kSeedPlanes) * 64 + lane;
                 Seed seed;
@@ -520,9 +513,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                     lv_->out_rgba[(size_t)(la->compact ? j : py) * (size_t)la->width + (size_t)px] = rgba;
                 }
             } else {
-            if constexpr (MODE == 2 || MODE == 3)
-                full::trace_pixel_full<TRAV, MODE == 3>(a, vw, tc_, px, py, rgba, idd, lo, (uint32_t)tile % kDeferQueues,
-                                                        (uint32_t)((a.compact ? j : py) * a.width + px));
+            if constexpr (MODE == 2)
+                full::trace_pixel_full<TRAV>(a, vw, tc_, px, py, rgba, idd, lo);
             else if constexpr (MODE == 4)   // pass 1: the primary + shadow kernel, leaving a seed per pixel
                 trace_pixel<1, TRAV>(a, vw, tc_, px, py, rgba, idd, lo, reinterpret_cast<uint32_t *>(a.defer_rec) + ((size_t)tile * kSeedPlanes) * 64 + lane);
             else if constexpr (MODE == 6) {   // both passes in this wave: the seed stays in registers
@@ -533,9 +525,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 if (full::bounce_pixel<TRAV>(a, tc_, px, py, seed, both)) rgba = both;
             }
             else trace_pixel<MODE, TRAV>(a, vw, tc_, px, py, rgba, idd, lo);
-            if constexpr (MODE == 0) lo = LateOut{vw.out_rgba, vw.out_id, a.width, a.compact, false};
+            if constexpr (MODE == 0) lo = LateOut{vw.out_rgba, vw.out_id, a.width, a.compact};
             size_t o = (size_t)(lo.compact ? j : py) * (size_t)lo.width + (size_t)px;
-            if (lo.out_rgba && !lo.skip_rgba) lo.out_rgba[o] = rgba;
+            if (lo.out_rgba) lo.out_rgba[o] = rgba;
             if (lo.out_id) lo.out_id[o] = idd;
             }
         }
@@ -548,7 +540,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             else if (lane == 0) a.tile_cost[tile] = (uint32_t)(__builtin_readcyclecounter() - t_begin);
 #endif
         }
-        if constexpr (!PERSIST) break;
     }
 }
 

@@ -3,23 +3,17 @@
 // pixel of the (2R+1)^2 window around it that carries the SAME voxelID contributes its colour;
 // R = clamp(int(200 / sqrt(max(1, dist))), 1, 20), so up to 41 x 41 = 1681 taps per pixel.
 //
-// gfx950 form: a 16x16-pixel workgroup stages its tile plus a 20-pixel halo (56 x 56 pixels) in LDS
-// once -- voxel IDs as int32 and the colours already converted to the floats the shader's sampler
-// returns (byte / 255.0f, one correctly rounded division per staged pixel instead of one per tap) --
-// 50 KB per workgroup, three workgroups per CU. Every lane then walks its own window in the
-// shader's order (y outer, x inner) so the fp32 sums round exactly as the reference's do; window
-// rows/columns that fall outside the image are skipped by clamping the loop bounds, which visits
-// the surviving taps in the same order. One ds_read for the ID and, on a match, one 12-byte read
-// for the colour per tap; global memory is touched only by the staging loads and the final store.
+// gfx950 form (denoise_px_kernel below): a workgroup stages its tile plus a 20-pixel halo in LDS once -- voxel IDs and the
+// colours already converted to the floats the shader's sampler returns (byte / 255.0f, one correctly rounded division per
+// staged pixel instead of one per tap) -- and every lane walks its pixels' windows in the shader's order (y outer, x inner), so
+// the fp32 sums round exactly as the reference's do. Global memory is touched only by the staging loads and the final store.
 #pragma once
 #include "vrt_common.hip.h"
 
 namespace vrt {
 namespace denoise {
 
-constexpr int kTile = 16;
 constexpr int kMaxR = 20;
-constexpr int kSpan = kTile + 2 * kMaxR;  // 56
 
 struct Args {
     const uint32_t *rgba;  // packed rgba8, W*H
@@ -34,64 +28,10 @@ struct Args {
     int rows_path;         // 0: per wave, the cheaper of the two walks below; 2: always the wave's common rows (rows_static); 3: always own boxes (rows_own_box)
 };
 
-__global__ __launch_bounds__(kTile *kTile) void denoise_kernel(const Args a) {
-    __shared__ int s_id[kSpan * kSpan];
-    __shared__ float s_col[kSpan * kSpan * 3];
-    const int tx0 = blockIdx.x * kTile - kMaxR, ty0 = blockIdx.y * kTile - kMaxR;
-    const int tid = threadIdx.y * kTile + threadIdx.x;
-    for (int i = tid; i < kSpan * kSpan; i += kTile * kTile) {
-        const int lx = i % kSpan, ly = i / kSpan;
-        const int gx = tx0 + lx, gy = ty0 + ly;
-        int vid = 0;
-        uint32_t c = 0u;
-        if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {
-            const size_t g = (size_t)gy * (size_t)a.width + (size_t)gx;
-            vid = a.id[g].x;
-            c = a.rgba[g];
-        }
-        s_id[i] = vid;
-        s_col[3 * i + 0] = (float)(c & 0xffu) / 255.0f;
-        s_col[3 * i + 1] = (float)((c >> 8) & 0xffu) / 255.0f;
-        s_col[3 * i + 2] = (float)((c >> 16) & 0xffu) / 255.0f;
-    }
-    __syncthreads();
-    const int px = blockIdx.x * kTile + threadIdx.x, py = blockIdx.y * kTile + threadIdx.y;
-    if (px >= a.width || py >= a.height) return;
-    const size_t p = (size_t)py * (size_t)a.width + (size_t)px;
-    const int2 center = a.id[p];
-    if (center.x == 0) {  // quad.frag:36-39: sky / no first-hit id: pass the colour through
-        a.out[p] = a.rgba[p];
-        return;
-    }
-    const float radius_f = 200.0f / __builtin_sqrtf((float)(center.y > 1 ? center.y : 1));  // :45
-    int R = (int)radius_f;
-    R = R < 1 ? 1 : (R > kMaxR ? kMaxR : R);  // :48
-    // window clipped to the image (:60-63); same visiting order for the taps that remain
-    const int y_lo = -R < -py ? -py : -R, y_hi = R > a.height - 1 - py ? a.height - 1 - py : R;
-    const int x_lo = -R < -px ? -px : -R, x_hi = R > a.width - 1 - px ? a.width - 1 - px : R;
-    const int cx = threadIdx.x + kMaxR, cy = threadIdx.y + kMaxR;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    int count = 0;
-    for (int y = y_lo; y <= y_hi; ++y) {
-        const int row = (cy + y) * kSpan + cx;
-        for (int x = x_lo; x <= x_hi; ++x) {
-            const int i = row + x;
-            if (s_id[i] == center.x) {  // :67-73
-                s0 = s0 + s_col[3 * i + 0];
-                s1 = s1 + s_col[3 * i + 1];
-                s2 = s2 + s_col[3 * i + 2];
-                ++count;
-            }
-        }
-    }
-    const float d = fmax_c((float)count, 1.0f);  // count <= 1681: the float the shader accumulates, exactly
-    a.out[p] = unorm8(s0 / d) | (unorm8(s1 / d) << 8) | (unorm8(s2 / d) << 16) | (255u << 24);
-}
-
-
 // ---------------------------------------------------------------------------------------------------
-// PX pixels per lane. The one-pixel kernel above reads 16 LDS bytes per tap per pixel and is bound by
-// LDS bandwidth and by waiting on it. Here a lane owns PX horizontally adjacent pixels and walks the
+// PX pixels per lane. Round 1's one-pixel-per-lane kernel (a 16 x 16 tile and its halo in 50 KB of LDS, removed after
+// commit adab131: `git show adab131:voxel-raytracer_amd/csrc/vrt_denoise.hip.h`) read 16 LDS bytes per tap per pixel and
+// was bound by LDS bandwidth and by waiting on it. Here a lane owns PX horizontally adjacent pixels and walks the
 // UNION of their windows, x = -R .. R+PX-1 relative to its first pixel: one ds_read_b128 ({r, g, b, id})
 // serves up to PX windows, and every pixel still receives its own taps in the shader's order (y outer,
 // x inner), so each fp32 sum rounds as before.
@@ -147,63 +87,23 @@ __device__ __forceinline__ int slot(const int col) {
     return (col % PX) * (kSpanX / PX) + col / PX;
 }
 
-#ifndef VRT_DENOISE_TAP
-#define VRT_DENOISE_TAP 0
-#endif
-#ifndef VRT_DENOISE_MASKED_TAP   // a 0/1 mask multiplied in: compare, select, then the four sums
-// How the four sums are issued (same values in every form: an fma with a 0/1 multiplier IS the conditional add, and count + m is
-// fma(m, 1, count)). A gfx950 SIMD issues one vector instruction per ~2.3 cycles whatever its kind and runs the half-rate kinds
-// (v_cmp, v_cndmask, every v_pk_*_f32) on a second pipe that needs ~4.3 cycles for each (profiles/r03_valu_rate.txt), so a tap
-// costs max(2.3 x instructions, 4.3 x half-rate instructions):
-//   0  v_cmp, v_cndmask, 2 x v_pk_fma_f32                      (round 1-2)   4 instructions, 4 half-rate: 17.2
-//   1  v_cmp, v_cndmask, v_pk_fma_f32 (r, g), v_fma_f32 (b), v_add_f32 (count)  5 instructions, 3 half-rate: 12.9
-//   2  v_cmp, v_cndmask, 3 x v_fma_f32, v_add_f32                           6 instructions, 2 half-rate: 13.8
+// The four sums of a tap: an fma with a 0/1 multiplier IS the conditional add, and count + m is fma(m, 1, count) -- compare,
+// select, then two v_pk_fma_f32. Tried in round 2 and measured SLOWER: the conditional add as what it is -- the comparison's
+// lane mask becomes exec for two packed adds (inline asm), which saves the v_cndmask (as dear as a packed add,
+// profiles/r02_valu_rate.txt) and turns the fmas into adds: 13.2 instead of 17.6 ticks of vector issue per tap and pixel. Same
+// pixels, but 1080p dragon 0.463 ms against 0.342 (0.449 / 0.285 with feedback scheduling), monu9 720p 0.222 / 0.190, nature
+// 4K 0.230 / 0.178 (profiles/r02_f_denoise_masked_tap.txt): every tap then hangs on a scalar -> vector hand-over of exec, and
+// this kernel runs two waves per SIMD (70 KB of LDS per workgroup) -- too few to hide it. The mask-multiply form is a pure
+// stream of independent vector instructions, which is what so few waves need. (That form, and two that trade packed fmas for
+// scalar ones, were removed after commit adab131: `git show adab131:voxel-raytracer_amd/csrc/vrt_denoise.hip.h`.)
 __device__ __forceinline__ void tap(const f4 rec, const int cid, f2 &rg, f2 &bc, const bool in_range = true) {
     const float m = (__float_as_int(rec.w) == cid && in_range) ? 1.0f : 0.0f;
-#if VRT_DENOISE_TAP == 0
     const f2 mm = {m, m};
     const f2 c01 = {rec.x, rec.y};
     const f2 c2 = {rec.z, 1.0f};
     rg = __builtin_elementwise_fma(mm, c01, rg);
     bc = __builtin_elementwise_fma(mm, c2, bc);
-#elif VRT_DENOISE_TAP == 1
-    const f2 mm = {m, m};
-    const f2 c01 = {rec.x, rec.y};
-    rg = __builtin_elementwise_fma(mm, c01, rg);
-    bc.x = __builtin_fmaf(m, rec.z, bc.x);
-    bc.y = bc.y + m;
-#else
-    rg.x = __builtin_fmaf(m, rec.x, rg.x);
-    rg.y = __builtin_fmaf(m, rec.y, rg.y);
-    bc.x = __builtin_fmaf(m, rec.z, bc.x);
-    bc.y = bc.y + m;
-#endif
 }
-#else
-// Tried in round 2 and measured SLOWER (kept for the record, -DVRT_DENOISE_MASKED_TAP): the conditional add as what it
-// is -- the comparison's lane mask becomes exec for two packed adds, which saves the v_cndmask (as dear as a packed add,
-// profiles/r02_valu_rate.txt) and turns the fmas into adds: 13.2 instead of 17.6 ticks of vector issue per tap and
-// pixel. Same pixels, but 1080p dragon 0.463 ms against 0.342 (0.449 / 0.285 with feedback scheduling), monu9 720p
-// 0.222 / 0.190, nature 4K 0.230 / 0.178 (profiles/r02_f_denoise_masked_tap.txt): every tap now hangs on a scalar ->
-// vector hand-over of exec, and this kernel runs two waves per SIMD (70 KB of LDS per workgroup) -- too few to hide it.
-// The mask-multiply form is a pure stream of independent vector instructions, which is what so few waves need.
-__device__ __forceinline__ void tap(const f4 rec, const int cid, f2 &rg, f2 &bc, const bool in_range = true) {
-    // two ballots and a scalar AND: the ballot of `a && b` is lowered through a select and a second compare
-    const uint64_t m = __builtin_amdgcn_ballot_w64(__float_as_int(rec.w) == cid) & __builtin_amdgcn_ballot_w64(in_range);
-    const f2 c01 = {rec.x, rec.y};
-    const f2 c2 = {rec.z, 1.0f};
-    uint64_t saved;
-    // not volatile: exec is back to what it was when the statement ends, and a volatile statement keeps the row's LDS reads
-    // from being hoisted over it
-    asm("s_and_saveexec_b64 %[saved], %[m]\n\t"
-                 "v_pk_add_f32 %[rg], %[rg], %[c01]\n\t"
-                 "v_pk_add_f32 %[bc], %[bc], %[c2]\n\t"
-                 "s_mov_b64 exec, %[saved]"
-                 : [rg] "+v"(rg), [bc] "+v"(bc), [saved] "=&s"(saved)
-                 : [m] "s"(m), [c01] "v"(c01), [c2] "v"(c2)
-                 : "scc");
-}
-#endif
 
 // RM is the largest radius among the wave's summed pixels, DELTA (wave-uniform) at least RM - the smallest.
 // Tap u of a row (x = u - RM relative to pixel 0) can only matter to pixel k when k <= u <= k + 2RM, and it

@@ -141,33 +141,18 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         const int ra = ensure_analysis(c);
         if (ra) return ra;
     }
-    Variant v = kVariants[c->variant];
-    if (v.trav >= 3 && !c->wide_ok) {  // wide layout not expressible for this scene: record-array kernels
-        v.trav = 2; v.use_lds = false; v.tw = 8; v.block = 256; v.wpe = 1; v.lds_cap = 0;
-    }
-    if (v.trav == 2 && c->unit_internal) {  // precondition of vrt_kernels.hip.h not met: explicit-AABB kernels
-        v.trav = 1; v.tw = 8; v.block = 256; v.wpe = 1;
-        if (v.lds_cap > 2048) v.lds_cap = 2048;
-    }
+    Variant v = *find_variant(c->variant);
+    if (v.trav >= 3 && !c->wide_ok) { v.trav = 2; v.wpe = 1; }      // wide layout not expressible for this scene: record-array kernels
+    if (v.trav == 2 && c->unit_internal) v.trav = 1;                 // precondition of vrt_kernels.hip.h not met: explicit-AABB kernels
     if (mode == VRT_MODE_FULL) {
-        // the full path tracer exists for the wide traversal (64- or 256-lane workgroups, five waves per SIMD: 96 VGPRs
-        // and no extra spills measured 8-10 % faster than the unconstrained 105-VGPR build) and, as baselines, for
-        // the other two in one shape each
-        v.use_lds = false; v.tw = 8; v.lds_cap = 0; v.blocks_per_cu = 0;
-        // the default takes the v4 traversal here too (one march loop, for rays that start in any medium: 96 registers
-        // without spills; 9 % faster than v3, profiles/r02_f_full_shader_v4_ab.jsonl); variant 20 is v3, and so is the
-        // two-kernel experiment of an A/B build
-        if (v.trav == 4 && VRT_AB && c->full_split) v.trav = 3;
-        if (v.trav >= 3) { v.block = (v.block == 64 || !VRT_AB) ? 64 : 256; v.wpe = 5; }
-        else { v.block = 256; v.wpe = 1; }
-    } else if (acc) {
-        // the accumulation's primary kernels (vrt_launch_accum.hip) exist in one shape per traversal: the frame kernels' default
-        // one for the wide traversals, the record-array fallbacks' for the others
-        v.use_lds = false; v.tw = 8; v.lds_cap = 0; v.blocks_per_cu = 0;
-        if (v.trav >= 3) { v.block = 64; v.wpe = v.trav == 4 ? 7 : 6; }
-        else { v.block = 256; v.wpe = 1; }
-    } else if (mode == VRT_MODE_PRIMARY_SHADOW && c->variant == 20 && v.trav == 3) {
-        v.wpe = 7;  // round 1's default: the shadow march was 1.5 % faster seven waves deep, the primary one six deep
+        // the full path tracer takes the wide traversals at five waves per SIMD (96 VGPRs and no extra spills measured 8-10 %
+        // faster than the unconstrained 105-VGPR build); the default takes v4 here too (one march loop, for rays that start in
+        // any medium: 96 registers without spills; 9 % faster than v3, profiles/r02_f_full_shader_v4_ab.jsonl), variant 20 v3
+        if (v.trav >= 3) v.wpe = 5;
+    } else if (!acc && mode == VRT_MODE_PRIMARY_SHADOW && c->variant == 20 && v.trav == 3) {
+        // round 1's default: the shadow march was 1.5 % faster seven waves deep, the primary one six deep (the accumulation's
+        // primary kernels, vrt_launch_accum.hip, exist in the table's shapes only)
+        v.wpe = 7;
     }
     vrt::KArgs a;
     vrt::ViewSet vs;
@@ -242,7 +227,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     a.compact = compact;
     a.nodes = c->d_nodes;
     a.n_records = c->info.n_records;
-    a.lds_records = v.use_lds ? (c->info.n_records < v.lds_cap ? c->info.n_records : v.lds_cap) : 0u;
+    a.lds_records = 0u;
     a.cells = c->d_cells;
     a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
     a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
@@ -265,28 +250,20 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     a.defer_count = nullptr;
     a.defer_cap = 0;
 
-    const int th = 64 / v.tw;
-    const long tiles = (long)((width + v.tw - 1) / v.tw) * (long)((n_rows + th - 1) / th);
+    const long tiles = (long)((width + 7) / 8) * (long)((n_rows + 7) / 8);   // 8 x 8 pixel tiles, one per wave
     {   // index arithmetic of the prologue without integer divisions where the shapes allow it
-        const unsigned long tiles_x = (unsigned long)((width + v.tw - 1) / v.tw);
+        const unsigned long tiles_x = (unsigned long)((width + 7) / 8);
         // q = (n * M) >> 32 with M = floor(2^32 / d) + 1 equals n / d while n * d < 2^32 (the error term n * (M * d - 2^32) stays below 2^32)
         a.tiles_x_magic = (tiles_x > 1 && (unsigned long)(tiles + 4) * tiles_x < (1ul << 32)) ? (uint32_t)((1ul << 32) / tiles_x + 1) : 0u;
-        a.row_mode = tile_rows >= n_rows ? 1 : ((tile_rows == 8 && th == 8) ? 2 : 0);
+        a.row_mode = tile_rows >= n_rows ? 1 : (tile_rows == 8 ? 2 : 0);
     }
-    const int waves = v.block / 64;
+    const int waves = v.block() / 64;
     long grid = (tiles + waves - 1) / waves;
-    if (v.blocks_per_cu > 0) {
-        long cap = (long)c->n_cus * v.blocks_per_cu;
-        if (grid > cap) grid = cap;
-    }
     if (grid < 1) grid = 1;
-    const size_t lds_bytes = (size_t)a.lds_records * sizeof(uint2);
     // feedback scheduling: wide-traversal kernels, one view, launches large enough to have a tail worth shaping
     SchedState *st = nullptr;
     bool measure = false;
-    const bool sched_kernel = !acc && v.trav >= 3 && !v.use_lds && v.tw == 8 && v.blocks_per_cu == 0 && n_views == 1 &&
-                              (v.trav == 4 || (v.block == 64 && (v.wpe == 5 || v.wpe == 6 || v.wpe == 7)) ||
-                               (v.block == 256 && (v.wpe == 5 || v.wpe == 6)));
+    const bool sched_kernel = !acc && v.trav >= 3 && n_views == 1;
     const long groups = (tiles + vrt::kGroupTiles - 1) / vrt::kGroupTiles;
     if (sched_kernel && c->dbg_sched) {
         a.group_order = c->dbg_group_order;
@@ -310,52 +287,19 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     const hipEvent_t ev0 = prof ? c->prof_events[2 * c->prof_count] : nullptr;
     const hipEvent_t ev1 = prof ? c->prof_events[2 * c->prof_count + 1] : nullptr;
     hipError_t e;
-    // The full path tracer as two kernels (vrt_bounce.hip.h): the default traversal, one view, a scene with a wide form.
-    const bool split = !acc && VRT_AB && mode == VRT_MODE_FULL && c->full_split && c->wide_ok && v.trav == 3 && v.block == 64 && n_views == 1 && c->variant == 0;
     // the full path tracer as two tile-coherent passes, where the scene and the view allow it
     bool two_pass = false;
-    if (mode == VRT_MODE_FULL && c->two_pass_on && v.trav == 4 && n_views == 1 && c->variant == 0 && !split && vs.v[0].out_rgba) {
+    if (mode == VRT_MODE_FULL && c->two_pass_on && v.trav == 4 && n_views == 1 && c->variant == 0 && vs.v[0].out_rgba) {
         if (!c->scene_opaque_valid) { c->scene_opaque = vrt::tree_is_opaque(c->host_records); c->scene_opaque_valid = true; }
         const uint32_t eye_alpha = vs.v[0].eye0 >> 24, eye_b = vs.v[0].eye1 & 0xffu;
         two_pass = c->scene_opaque && eye_alpha == 0u && (eye_b == 0u || eye_b == 85u || eye_b == 255u);
     }
     // the general full path tracer starts the heaviest groups of an ordered, non-measuring launch as part-tile waves (KArgs::split_count)
-    if (mode == VRT_MODE_FULL && !two_pass && !split && st && a.group_order && v.block == 64 && c->heavy_split_on) {
+    if (mode == VRT_MODE_FULL && !two_pass && st && a.group_order && c->heavy_split_on) {
         a.split_count = st->d_order + st->n_groups;
         grid += (long)vrt::kSplitMaxGroups * vrt::kGroupTiles * (vrt::kSplitParts - 1);
         // a measuring launch: the part-tile waves of a tile meet in its ticks with atomicMax
         if (a.tile_cost) VRT_HIP(c, hipMemsetAsync(st->d_cost, 0, (size_t)st->n_groups * vrt::kGroupTiles * sizeof(uint32_t), s));
-    }
-    if (split) {
-        const size_t cap = (size_t)((tiles + vrt::kDeferQueues - 1) / vrt::kDeferQueues) * 64;   // every pixel of a queue's tiles may defer
-        vrt_ctx::DeferQueues *dq = nullptr;
-        for (auto &d : c->defer)
-            if (d.stream == s) dq = &d;
-        if (!dq) {
-            if (c->defer.size() < 8) {
-                c->defer.emplace_back();
-                dq = &c->defer.back();
-            } else {   // recycle the least recently used set: its launches may still be in flight on its stream
-                for (auto &d : c->defer)
-                    if (!dq || d.last_use < dq->last_use) dq = &d;
-                VRT_HIP(c, hipStreamSynchronize(dq->stream));
-            }
-            dq->stream = s;
-        }
-        if (cap > dq->cap) {
-            VRT_HIP(c, hipStreamSynchronize(s));   // launches in flight on this stream still use the old queues
-            float *fresh = nullptr;
-            VRT_HIP(c, hipMalloc((void **)&fresh, cap * vrt::kDeferQueues * vrt::kDeferPlanes * sizeof(float)));
-            if (dq->rec) (void)hipFree(dq->rec);
-            dq->rec = fresh;
-            dq->cap = cap;
-        }
-        if (!dq->count) VRT_HIP(c, hipMalloc((void **)&dq->count, 2 * vrt::kDeferQueues * vrt::kDeferStride * sizeof(uint32_t)));
-        dq->last_use = ++c->defer_tick;
-        VRT_HIP(c, hipMemsetAsync(dq->count, 0, 2 * vrt::kDeferQueues * vrt::kDeferStride * sizeof(uint32_t), s));
-        a.defer_rec = dq->rec;
-        a.defer_count = dq->count;
-        a.defer_cap = (uint32_t)dq->cap;
     }
     if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
         vrt_ctx::Accum &ac = c->accum;
@@ -428,12 +372,9 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         sb->last_use = ++c->seed_tick;
         a.defer_rec = reinterpret_cast<float *>(sb->d);
         e = vrt::launch::trace_full_two_pass(a, vs, (int)grid, s, ev0, ev1);
-    } else
-#if VRT_AB
-    if (split) e = vrt::launch::trace_split(a, vs, (int)grid, c->n_cus * 4 * c->bounce_waves_per_simd, c->bounce_refill_below, s, ev0, ev1);
-    else
-#endif
-    e = vrt::launch::trace(mode, v, a, vs, (int)grid, lds_bytes, s, ev0, ev1);
+    } else {
+        e = vrt::launch::trace(mode, v, a, vs, (int)grid, s, ev0, ev1);
+    }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     if (st) {
         ++st->launches;
@@ -443,7 +384,6 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         }
     }
     if (prof) ++c->prof_count;
-    c->info.lds_records = a.lds_records;
     return VRT_OK;
 }
 
@@ -671,8 +611,9 @@ int vrt_set_option(vrt_ctx *c, int option, int value) {
             c->heavy_split_on = value != 0;
             return VRT_OK;
         case VRT_OPT_DISPLAY_KERNEL:
-            if (value == 0 || value == 2 || value == 3 || (value == 1 && VRT_AB)) { c->denoise_variant = value; return VRT_OK; }
-            return vrt_fail(c, VRT_E_INVALID, "vrt_set_option: the one-pixel-per-lane display kernel exists in A/B builds only (make AB=1)");
+            if (value != 0 && value != 2 && value != 3) break;
+            c->denoise_variant = value;
+            return VRT_OK;
         default:
             return vrt_fail(c, VRT_E_INVALID, "vrt_set_option: unknown option");
     }
@@ -699,20 +640,5 @@ long vrt_get_tile_order(vrt_ctx *c, void *stream, uint32_t *out, size_t cap) {
     if (out && n) VRT_HIP(c, hipMemcpy(out, best->d_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return (long)best->n_groups;
 }
-
-#if VRT_AB
-// A/B builds only (tools/full_split_ab.py): the full path tracer as two kernels with cross-wave repacking (ab/vrt_bounce.hip.h)
-int vrt_ab_set_full_split(vrt_ctx *c, int on) {
-    if (!c) return VRT_E_INVALID;
-    c->full_split = on != 0;
-    return VRT_OK;
-}
-int vrt_ab_set_bounce(vrt_ctx *c, int refill_below, int waves_per_simd) {
-    if (!c || refill_below < 1 || refill_below > 65 || waves_per_simd < 1 || waves_per_simd > 8) return VRT_E_INVALID;
-    c->bounce_refill_below = refill_below;
-    c->bounce_waves_per_simd = waves_per_simd;
-    return VRT_OK;
-}
-#endif
 
 }  // extern "C"

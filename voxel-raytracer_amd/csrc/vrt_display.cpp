@@ -17,12 +17,8 @@ int vrt_denoise(vrt_ctx *c, int width, int height, const void *d_rgba8, const vo
     if (!d_rgba8 || !d_id_dist || !d_out_rgba8 || d_rgba8 == d_out_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_denoise: null or aliased buffers");
     VRT_HIP(c, hipSetDevice(c->device));
     vrt::launch::Denoise d{d_rgba8, d_id_dist, d_out_rgba8, width, height, nullptr, nullptr};
-    d.rows_path = c->denoise_variant >= 2 ? c->denoise_variant : 0;
+    d.rows_path = c->denoise_variant;
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->denoise_variant == 1) {
-        VRT_HIP(c, vrt::launch::denoise(d, 1, false, s));
-        return VRT_OK;
-    }
     // the trace kernel's feedback scheduling, keyed as mode kSchedDenoise: one tile = one workgroup here
     int tiles_x = 0, n_tiles = 0;
     vrt::launch::denoise_tiling(width, height, tiles_x, n_tiles);
@@ -31,7 +27,7 @@ int vrt_denoise(vrt_ctx *c, int width, int height, const void *d_rgba8, const vo
     if (c->sched_period > 0 && groups >= kSchedMinDenoiseGroups && groups <= kSchedMaxDenoiseGroups)
         st = sched_state(c, s, width, height, 0, 0, 0, kSchedDenoise, (uint32_t)n_tiles, (uint32_t)groups);
     if (!st) {
-        VRT_HIP(c, vrt::launch::denoise(d, 0, false, s));
+        VRT_HIP(c, vrt::launch::denoise(d, false, s));
         return VRT_OK;
     }
     const bool measure = measuring_launch(st->launches, c->sched_period);
@@ -40,7 +36,7 @@ int vrt_denoise(vrt_ctx *c, int width, int height, const void *d_rgba8, const vo
         d.tile_cost = st->d_cost;
         VRT_HIP(c, hipMemsetAsync(st->d_cost, 0, (size_t)groups * vrt::kGroupTiles * sizeof(uint32_t), s));
     }
-    VRT_HIP(c, vrt::launch::denoise(d, 0, true, s));
+    VRT_HIP(c, vrt::launch::denoise(d, true, s));
     ++st->launches;
     if (measure) {
         const int rr = launch_order_kernel(c, st, s);

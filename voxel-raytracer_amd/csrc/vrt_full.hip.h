@@ -162,36 +162,11 @@ VRT_DEV RayS make_ray(F3 o, F3 d, float iof, float w, const float tint[3], float
     return r;
 }
 
-// One record of the deferred-bounce queues (KArgs::defer_rec): the lanes that are here together take consecutive slots
-// of queue `queue` with one atomic between them (ballot + popcount: the wave's aggregate), then each writes its planes.
-VRT_DEV void defer_bounce(const KArgs &a, uint32_t queue, uint32_t out_offset, F3 o, F3 d, const float tint[3], const float fc[3], float iof,
-                          float weight, const float mc[3], float md) {
-    const uint64_t here = __builtin_amdgcn_ballot_w64(true);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(here >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)here, 0u));
-    uint32_t base = 0u;
-    if (rank == 0u) base = atomicAdd(&a.defer_count[queue * kDeferStride], (uint32_t)__builtin_popcountll(here));
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);   // the first active lane is the one of rank 0
-    const size_t plane = (size_t)kDeferQueues * a.defer_cap;
-    float *r = a.defer_rec + (size_t)queue * a.defer_cap + base + rank;
-    r[0 * plane] = o.x; r[1 * plane] = o.y; r[2 * plane] = o.z;
-    r[3 * plane] = d.x; r[4 * plane] = d.y; r[5 * plane] = d.z;
-    r[6 * plane] = tint[0]; r[7 * plane] = tint[1]; r[8 * plane] = tint[2];
-    r[9 * plane] = fc[0]; r[10 * plane] = fc[1]; r[11 * plane] = fc[2];
-    r[12 * plane] = iof; r[13 * plane] = weight;
-    r[14 * plane] = mc[0]; r[15 * plane] = mc[1]; r[16 * plane] = mc[2];
-    r[17 * plane] = md;
-    r[18 * plane] = __uint_as_float(out_offset);
-}
-
-// DEFER: when the ray stack is empty at the moment a diffuse bounce would be pushed, that bounce is the last ray of the
-// pixel -- nothing is accumulated after it -- so it goes to a queue instead, together with the colour summed so far;
-// bounce_kernel (vrt_bounce.hip.h) marches it among full waves of such rays and writes the pixel. A bounce ray (depth 1)
-// spawns nothing (comp:590-594), so the queue is one level deep. The accumulation order per pixel is unchanged.
 // sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
 // with JIT also the jittered sample whose ray is traced (jittered_ray_dir(), vrt_jitter.hip.h)
-template <class TRAV, bool DEFER, bool JIT>
+template <class TRAV, bool JIT>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t queue, uint32_t out_offset, uint32_t sample) {
+                                 uint32_t sample) {
     const float kPI = 3.14159265359f;
     const float sky[3] = {0.5f, 0.7f, 1.0f};
     const float kSun = 3.0f;
@@ -238,7 +213,6 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
         r.md = unorm_of((float)(e.medium >> 24)) * 5.0f;
         r.depth = 0;
     };
-    bool deferred = false;
     float fc[3] = {0.0f, 0.0f, 0.0f};
     const float *gl = a.global_light;
     const F3 light{a.light_dir[0], a.light_dir[1], a.light_dir[2]};
@@ -402,16 +376,11 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 const float nw = r.weight / (float)kIndirectSamples;
                 const float tint[3] = {tc[0] * sc[0], tc[1] * sc[1], tc[2] * sc[2]};
                 static_assert(kIndirectSamples == 1, "the bounce ray takes the finished ray's registers: one per hit");
-                if (DEFER && sp == 0) {
-                    defer_bounce(a, queue, out_offset, add3(hp, scale3(normal, 1e-1f)), bd, tint, fc, n1, nw, last.c, last.c[3] * 5.0f);
-                    deferred = true;
-                } else {
-                    // Pushed last, it is the ray popped next -- whatever else waits on the stack (the reflections of the glass
-                    // the primary ray came through): it takes r's registers instead of a round trip through scratch, 17 words each
-                    // way per lane with the march waiting on the reload. (Round 2 did this for an empty stack only.)
-                    r = make_ray(add3(hp, scale3(normal, 1e-1f)), bd, n1, nw, tint, 0.0f, last.c, last.c[3] * 5.0f, r.depth + 1);
-                    in_regs = true;
-                }
+                // Pushed last, it is the ray popped next -- whatever else waits on the stack (the reflections of the glass
+                // the primary ray came through): it takes r's registers instead of a round trip through scratch, 17 words each
+                // way per lane with the march waiting on the reload. (Round 2 did this for an empty stack only.)
+                r = make_ray(add3(hp, scale3(normal, 1e-1f)), bd, n1, nw, tint, 0.0f, last.c, last.c[3] * 5.0f, r.depth + 1);
+                in_regs = true;
             }
             VRT_ST_MARK(9);
         }
@@ -428,7 +397,6 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     rgba = unorm8(fc[0]) | (unorm8(fc[1]) << 8) | (unorm8(fc[2]) << 16) | (255u << 24);
     idd = make_int2(voxel_id, pixel_dist);
     lo = late_out(late_args(), late_view());
-    lo.skip_rgba = deferred;
 }
 
 // ---- the two-pass form for opaque scenes ------------------------------------------------------------------------------------

@@ -24,55 +24,30 @@
 
 // Variant 0 is what the library ships: the v4 traversal, seven waves per SIMD (five for the full path tracer, which runs
 // v4's general march loop); the dispatcher takes v3 when a primary / primary + shadow launch has its eye inside a medium,
-// v2 when the scene has no wide form, v1 when it has a unit-size internal node. Variants 1, 4 and 20 select those fallbacks explicitly (tests). Everything else is A/B material and is only
-// compiled into the library with `make AB=1` (-DVRT_AB_VARIANTS); vrt_set_variant() refuses what is not there.
-#ifdef VRT_AB_VARIANTS
-#define VRT_AB 1
-#else
-#define VRT_AB 0
-#endif
-
+// v2 when the scene has no wide form, v1 when it has a unit-size internal node. Variants 1, 4 and 20 select those fallbacks
+// explicitly, and 22 is variant 0 without the full path tracer's opaque and two-pass forms (tests). vrt_set_variant() refuses
+// every other number. A wave traces an 8 x 8 pixel tile; a workgroup is one wave for the wide traversals (v3, v4) and four
+// for the record-array ones (v1, v2).
 struct Variant {
-    int trav;          // 2: bit-indexed descent with restart anchors (vrt_kernels.hip.h); 1: baseline (vrt_kernels_v1.hip.h)
-    bool use_lds;      // stage the level-order record prefix in LDS
-    int tw;            // tile width in pixels (tile = tw x 64/tw)
-    int block;         // threads per workgroup
-    uint32_t lds_cap;  // max records staged in LDS
-    int blocks_per_cu; // > 0: persistent grid of CUs*blocks_per_cu workgroups; 0: one pass over all tiles
-    int wpe;           // waves per SIMD the register allocator is held to (1 = unconstrained)
+    int id;     // the public number (vrt_set_variant)
+    int trav;   // 4, 3: wide layout (vrt_kernels_v4.hip.h, vrt_kernels_wide.hip.h); 2: bit-indexed descent with restart
+                // anchors (vrt_kernels.hip.h); 1: baseline (vrt_kernels_v1.hip.h)
+    int wpe;    // waves per SIMD the register allocator is held to (1 = unconstrained)
+    int block() const { return trav >= 3 ? 64 : 256; }   // threads per workgroup
 };
 
 inline constexpr Variant kVariants[] = {
-    /*0*/ {4, false, 8, 64, 0, 0, 7},
-    /*1*/ {1, false, 8, 256, 0, 0, 1},
-    /*2*/ {2, true, 8, 256, 2048, 0, 1},
-    /*3*/ {2, false, 16, 256, 0, 0, 1},
-    /*4*/ {2, false, 8, 256, 0, 0, 1},
-    /*5*/ {2, true, 8, 1024, 8192, 0, 1},
-    /*6*/ {2, false, 8, 256, 0, 8, 1},
-    /*7*/ {1, true, 8, 256, 2048, 0, 1},
-    /*8*/ {2, false, 8, 64, 0, 0, 1},
-    /*9*/ {2, false, 8, 128, 0, 0, 1},
-    /*10*/ {2, false, 8, 256, 0, 0, 5},
-    /*11*/ {2, false, 8, 256, 0, 0, 6},
-    /*12*/ {2, false, 8, 256, 0, 0, 8},
-    /*13*/ {3, false, 8, 256, 0, 0, 1},
-    /*14*/ {3, false, 8, 256, 0, 0, 6},
-    /*15*/ {3, false, 8, 256, 0, 0, 8},
-    /*16*/ {3, false, 8, 64, 0, 0, 1},
-    /*17*/ {3, false, 8, 64, 0, 0, 8},
-    /*18*/ {3, false, 16, 256, 0, 0, 1},
-    /*19*/ {3, false, 8, 64, 0, 0, 7},
-    /*20*/ {3, false, 8, 64, 0, 0, 6},  // v3 as round 1 shipped it (six waves per SIMD; seven with the shadow march)
-    /*21*/ {4, false, 8, 64, 0, 0, 6},
-    /*22*/ {4, false, 8, 64, 0, 0, 7},  // == variant 0
-    /*23*/ {4, false, 8, 64, 0, 0, 8},
-    /*24*/ {4, false, 8, 64, 0, 0, 1},
+    {0, 4, 7},
+    {1, 1, 1},
+    {4, 2, 1},
+    {20, 3, 6},   // v3 as round 1 shipped it (six waves per SIMD; seven with the shadow march)
+    {22, 4, 7},   // == variant 0 but for the dispatcher's choice of the full path tracer's form
 };
-inline constexpr bool kVariantShipped[] = {true, true, false, false, true, false, false, false, false, false, false, false, false,
-                                    false, false, false, false, false, false, false, true, false, true, false, false};
-inline constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
-static_assert(sizeof(kVariantShipped) / sizeof(kVariantShipped[0]) == (size_t)kNumVariants, "one flag per variant");
+inline const Variant *find_variant(int id) {
+    for (const Variant &v : kVariants)
+        if (v.id == id) return &v;
+    return nullptr;
+}
 
 // Feedback scheduling state of one launch shape on one stream. Launches that repeat a shape on a stream (the frames of
 // a camera path) share it: every sched_period-th of them also records what each tile cost, tile_order_kernel turns that
@@ -102,7 +77,7 @@ struct vrt_ctx {
     vrt_params params{};
     float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
     int variant = 0;
-    int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL: 0 two pixels per lane, each wave the cheaper walk; 1 one pixel per lane (A/B builds); 2, 3: one walk forced
+    int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL = denoise::Args::rows_path: 0 each wave the cheaper walk; 2, 3: one walk forced
     // scratch outputs for the host-buffer dispatch
     void *d_rgba = nullptr;
     void *d_id = nullptr;
@@ -151,18 +126,6 @@ struct vrt_ctx {
     uint2 *d_cells = nullptr;     // cells_capacity cells in the layout of vrt_layout.h, then as many in the v4 form (cells4)
     uint32_t *d_roots = nullptr;  // 16 words: record and wide node of each wide root (vrt_common.hip.h KArgs::root_table)
     size_t cells_capacity = 0;
-    // the full path tracer as two kernels (vrt_bounce.hip.h): deferred-bounce queues, sized for the largest launch so far
-    bool full_split = false;
-    int bounce_refill_below = 40, bounce_waves_per_simd = 6;   // vrt_ab_set_bounce (A/B builds; tools sweep them)
-    struct DeferQueues {                  // one set per stream: launches on different streams may overlap
-        hipStream_t stream = nullptr;
-        float *rec = nullptr;
-        uint32_t *count = nullptr;        // 2 * kDeferQueues counters, kDeferStride words apart: records written, records handed out
-        size_t cap = 0;                   // records per queue
-        uint64_t last_use = 0;
-    };
-    std::vector<DeferQueues> defer;
-    uint64_t defer_tick = 0;
     // feedback scheduling of the default kernel (see SchedState)
     int sched_period = 16;                   // every n-th launch of a shape measures its tiles; 0 = off
     std::vector<SchedState> sched;

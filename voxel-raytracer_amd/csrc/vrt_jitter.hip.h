@@ -33,10 +33,8 @@ VRT_DEV bool jitter_pixel(const KArgs &a, int &px, int &py) {
 // q.n samples q.first, q.first + 1, ... of MODE 0 or 1; whole frame (KArgs: row0 = 0, n_rows = height, compact = 0)
 template <int MODE, class TRAV, int BLOCK, int WPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_jitter_kernel(const KArgs a, const ViewSet vs, const Args q) {
-    extern __shared__ __attribute__((aligned(16))) uint2 lds_dyn[];
     typename TRAV::Ctx tc_;
-    TRAV::template block_init<BLOCK>(a, lds_dyn, tc_);
-    if constexpr (TRAV::kStagesLds) __syncthreads();
+    TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<BLOCK>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
@@ -63,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 template <class TRAV, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_jitter_kernel(const KArgs a, const ViewSet vs, const Args q) {
     typename TRAV::Ctx tc_;
-    TRAV::template block_init<64>(a, nullptr, tc_);
+    TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<64>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
@@ -91,16 +89,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 // the general full path tracer, jittered sample q.first (q.n == 1): trace_kernel<2>'s tiles, one pixel per lane
 template <class TRAV, int BLOCK, int WPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_jitter_kernel(const KArgs a, const ViewSet vs, const Args q) {
-    extern __shared__ __attribute__((aligned(16))) uint2 lds_dyn[];
     typename TRAV::Ctx tc_;
-    TRAV::template block_init<BLOCK>(a, lds_dyn, tc_);
-    if constexpr (TRAV::kStagesLds) __syncthreads();
+    TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<BLOCK>(a, px, py)) return;
     uint32_t rgba;
     int2 idd;
     LateOut lo;
-    full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, 0u, 0u, q.first);
+    full::trace_pixel_full<TRAV, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
     uint32_t r = 0u, g = 0u, b = 0u;
     add_bytes(rgba, r, g, b);
     store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);

@@ -26,8 +26,6 @@
 //  * The medium-change test of hitMarching (comp:318-321) is evaluated on the
 //    refraction BYTES instead of on floats; see medium_byte() for the proof of
 //    equivalence. No division and no table per DDA step.
-//  * Optionally the level-order prefix of the record array (the hot top of the
-//    tree) is staged in LDS (USE_LDS).
 //
 // Precondition checked by the host before choosing this variant: no internal
 // node is an aligned cube of side 1 (octree_texture never writes one); scenes
@@ -60,30 +58,15 @@ VRT_DEV uint32_t medium_byte(uint32_t w0, uint32_t w1) { return (w0 >> 24) != 0u
 // b in 1..254 or 1.0 (comp:448-449). Hence the float test is true exactly when the two bytes
 // differ, once "no medium" is replaced by 85 (new side) or by the byte of rayIOF (old side).
 
-template <bool USE_LDS>
 struct Trav {
-    static constexpr bool kStagesLds = USE_LDS;
     struct Ctx {
-        const uint2 *lds;      // staged record prefix (USE_LDS)
         uint2 root;
     };
 
-    template <int BLOCK>
-    static VRT_DEV void block_init(const KArgs &a, uint2 *lds_dyn, Ctx &c) {
-        if (USE_LDS) {
-            for (uint32_t i = threadIdx.x; i < a.lds_records; i += BLOCK) lds_dyn[i] = a.nodes[i];
-            __syncthreads();
-        }
-        c.lds = lds_dyn;
-        c.root = a.nodes[0];
-    }
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { c.root = a.nodes[0]; }
 
-    static VRT_DEV uint2 load_record(const KArgs &a, const Ctx &c, uint32_t idx) {
-        if (USE_LDS) {
-            if (idx < a.lds_records) return c.lds[idx];
-        }
-        return a.nodes[idx];
-    }
+    // a call rather than a.nodes[...] at the two sites: written out there, the compiler orders two scalar moves differently
+    static VRT_DEV uint2 load_record(const KArgs &a, uint32_t idx) { return a.nodes[idx]; }
 
     static VRT_DEV void reset(Walk &w) { w.ps = -1; w.as = -1; w.pm = w.pb = w.am = w.ab = 0u; w.last = I3{0, 0, 0}; }
 
@@ -109,7 +92,7 @@ struct Trav {
             const uint32_t bit = 1u << ci;
             f.mn = mn; f.mx = mx;
             if (!(m & bit)) return true;
-            const uint2 rec = load_record(a, c, b + (uint32_t)__builtin_popcount(m & (bit - 1u)));
+            const uint2 rec = load_record(a, b + (uint32_t)__builtin_popcount(m & (bit - 1u)));
             if (m & (bit << 8)) { f.w0 = rec.x; f.w1 = rec.y; return true; }
             m = rec.x; b = rec.y;
         }
@@ -141,7 +124,7 @@ struct Trav {
             const uint32_t ci = ((((uint32_t)p.x >> s1) & 1u) << 2) | ((((uint32_t)p.y >> s1) & 1u) << 1) | (((uint32_t)p.z >> s1) & 1u);
             sh = m >> ci;  // bit 0: child present, bit 8: child is a leaf
             rec = make_uint2(0u, 0u);
-            if (sh & 1u) rec = load_record(a, c, b + (uint32_t)__builtin_popcount(m & ((1u << ci) - 1u)));
+            if (sh & 1u) rec = load_record(a, b + (uint32_t)__builtin_popcount(m & ((1u << ci) - 1u)));
             go = (sh & 0x101u) == 1u;
             m = go ? rec.x : m;
             b = go ? rec.y : b;

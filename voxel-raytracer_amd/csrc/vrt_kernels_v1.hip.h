@@ -18,30 +18,12 @@ struct Found {             // deepest node containing the query point
     I3 mn, mx;             // that node's AABB (half-open)
 };
 
-template <bool USE_LDS>
 struct Trav {
-    static constexpr bool kStagesLds = USE_LDS;
     struct Ctx {
-        const uint2 *lds;
         uint2 root;
     };
 
-    template <int BLOCK>
-    static VRT_DEV void block_init(const KArgs &a, uint2 *lds_dyn, Ctx &c) {
-        if (USE_LDS) {
-            for (uint32_t i = threadIdx.x; i < a.lds_records; i += BLOCK) lds_dyn[i] = a.nodes[i];
-            __syncthreads();
-        }
-        c.lds = lds_dyn;
-        c.root = a.nodes[0];
-    }
-
-    static VRT_DEV uint2 load_record(const KArgs &a, const Ctx &c, uint32_t idx) {
-        if (USE_LDS) {
-            if (idx < a.lds_records) return c.lds[idx];
-        }
-        return a.nodes[idx];
-    }
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { c.root = a.nodes[0]; }
 
     static VRT_DEV Parent root_parent(const KArgs &a, const Ctx &c) {
         Parent p;
@@ -74,7 +56,7 @@ struct Trav {
             uint32_t bit = 1u << ci;
             if (!(par.masks & bit)) { f.mn = cmn; f.mx = cmx; return f; }  // absent child: empty space
             uint32_t idx = par.base + (uint32_t)__builtin_popcount(par.masks & 0xffu & (bit - 1u));
-            uint2 rec = load_record(a, c, idx);
+            uint2 rec = a.nodes[idx];
             if (par.masks & (bit << 8)) { f.w0 = rec.x; f.w1 = rec.y; f.mn = cmn; f.mx = cmx; return f; }
             par.masks = rec.x; par.base = rec.y; par.mn = cmn; par.mx = cmx;
         }

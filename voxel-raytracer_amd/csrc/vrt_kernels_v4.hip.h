@@ -70,13 +70,11 @@ VRT_DEV uint32_t cell4_y(uint32_t w0, uint32_t w1, uint32_t tp1) {
 // its registers; otherwise march() runs the loop that takes a ray's own starting medium (the full path tracer).
 template <bool EYE85>
 struct TravT {
-    static constexpr bool kStagesLds = false;
     using Ctx = v3::Trav::Ctx;
     using Eye85 = TravT<true>;   // the same traversal with the one march loop of rays that start in empty space
     using General = TravT<false>;   // ... and with the loop that takes a ray's own starting medium
 
-    template <int BLOCK>
-    static VRT_DEV void block_init(const KArgs &a, uint2 *, Ctx &c) { c.root = a.nodes[0]; }
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { c.root = a.nodes[0]; }
 
     // No current node: cell shift 0 makes both tests "d < 4", and no floor() of a float can come that close to this
     // point (in the world every coordinate is sign-extended from bit 11; beyond 2^24 floor() is a multiple of 128).

@@ -57,13 +57,11 @@ VRT_DEV bool in_world_u(const KArgs &a, I3 p) {  // comp:224-226, as three unsig
 }
 
 struct Trav {
-    static constexpr bool kStagesLds = false;
     struct Ctx {
         uint2 root;
     };
 
-    template <int BLOCK>
-    static VRT_DEV void block_init(const KArgs &a, uint2 *, Ctx &c) { c.root = a.nodes[0]; }
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { c.root = a.nodes[0]; }
 
     static VRT_DEV void reset(Walk &w) { w.s = -1; w.as = -1; w.node = w.anode = 0u; w.last = I3{0, 0, 0}; }
 

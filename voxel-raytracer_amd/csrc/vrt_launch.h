@@ -10,9 +10,9 @@ namespace launch {
 
 // trace_kernel<MODE, ...> for the variant the dispatcher settled on (vrt_launch_primary / _shadow / _full .hip). ev0 / ev1 (both
 // or neither): events attached to THIS dispatch packet, so their elapsed time is the kernel's own begin-to-end time.
-// hipErrorInvalidValue: the combination is not in this build.
-hipError_t trace_primary(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-hipError_t trace_shadow(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// hipErrorInvalidValue: no kernel of that shape.
+hipError_t trace_primary(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+hipError_t trace_shadow(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 hipError_t trace_full(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 // The full path tracer as two tile-coherent passes (vrt_full.hip.h bounce_pixel) for scenes the dispatcher has checked: pass 1 = the
 // primary + shadow kernel leaving a seed per pixel in a.defer_rec, pass 2 = the diffuse bounce of the seeded pixels. ev0 rides on
@@ -22,10 +22,9 @@ hipError_t trace_full_opaque(const KArgs &a, const ViewSet &vs, int grid, int wp
 hipError_t trace_full_two_pass(const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 // pass 1 of the two-pass form alone (the progressive accumulation runs it once and the bounce once per sample)
 hipError_t trace_full_pass1(const KArgs &a, const ViewSet &vs, int grid, hipStream_t s);
-inline hipError_t trace(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, int grid, size_t lds, hipStream_t s, hipEvent_t ev0,
-                        hipEvent_t ev1) {
+inline hipError_t trace(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     return mode == VRT_MODE_FULL ? trace_full(v, a, vs, grid, s, ev0, ev1)
-                                 : (mode == VRT_MODE_PRIMARY ? trace_primary(v, a, vs, grid, lds, s, ev0, ev1) : trace_shadow(v, a, vs, grid, lds, s, ev0, ev1));
+                                 : (mode == VRT_MODE_PRIMARY ? trace_primary(v, a, vs, grid, s, ev0, ev1) : trace_shadow(v, a, vs, grid, s, ev0, ev1));
 }
 
 // vrt_launch_misc.hip
@@ -36,9 +35,8 @@ hipError_t tile_order(const uint32_t *d_cost, uint32_t n_groups, uint32_t *d_ord
 // checks on the device that the kernarg segment is laid out as late_args() / late_view() assume; *d_bad += mismatches
 hipError_t kernarg_probe(const KArgs &a, const ViewSet &vs, uint32_t *d_bad, hipStream_t s);
 
-// the display pass (vrt_denoise.hip.h). variant 0: 32 x 16-pixel tiles, two pixels per lane (tiles_x / n_tiles: its tiling;
-// whole_groups: a 1-D grid of whole scheduling groups that reads group_order / writes tile_cost when given); variant 1 (A/B builds):
-// the one-pixel-per-lane kernel of round 1.
+// the display pass (vrt_denoise.hip.h): 32 x 16-pixel tiles, two pixels per lane (tiles_x / n_tiles: its tiling; whole_groups: a
+// 1-D grid of whole scheduling groups that reads group_order / writes tile_cost when given).
 struct Denoise {
     const void *rgba, *id;
     void *out;
@@ -48,7 +46,7 @@ struct Denoise {
     int rows_path = 0;   // denoise::Args::rows_path
 };
 void denoise_tiling(int width, int height, int &tiles_x, int &n_tiles);
-hipError_t denoise(const Denoise &d, int variant, bool whole_groups, hipStream_t s);
+hipError_t denoise(const Denoise &d, bool whole_groups, hipStream_t s);
 
 // vrt_launch_query.hip: the world queries (vrt_query.hip.h), one lane per ray / point; a carries the scene part of KArgs only
 hipError_t cast_rays(const KArgs &a, const query::RayArgs &q, hipStream_t s);
@@ -68,12 +66,6 @@ hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const View
 hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
 hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
 hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s);
-
-#if VRT_AB
-// vrt_launch_ab.hip -- the full path tracer as two kernels with cross-wave repacking (ab/vrt_bounce.hip.h): an experiment that lost
-// (profiles/r02_b_*), A/B builds only
-hipError_t trace_split(const KArgs &a, const ViewSet &vs, int grid, int bounce_waves, int refill_below, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-#endif
 
 }  // namespace launch
 }  // namespace vrt

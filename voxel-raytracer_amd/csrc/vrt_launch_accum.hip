@@ -23,9 +23,9 @@ hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::Args &q,
 
 hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
     if (v.trav == 4) hipLaunchKernelGGL((accum::full_accum_kernel<v4::TravAny, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
-    else if (v.trav == 3 && v.block == 64) hipLaunchKernelGGL((accum::full_accum_kernel<v3::Trav, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
-    else if (v.trav == 2 && v.block == 256) hipLaunchKernelGGL((accum::full_accum_kernel<v2::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
-    else if (v.trav == 1 && v.block == 256) hipLaunchKernelGGL((accum::full_accum_kernel<v1::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 3) hipLaunchKernelGGL((accum::full_accum_kernel<v3::Trav, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 2) hipLaunchKernelGGL((accum::full_accum_kernel<v2::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 1) hipLaunchKernelGGL((accum::full_accum_kernel<v1::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -39,10 +39,10 @@ hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s) {
 namespace {
 template <int MODE>
 hipError_t primary(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
-    if (v.trav == 4 && v.block == 64) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v4::Trav, 64, 7>), dim3(grid), dim3(64), 0, s, a, vs, q);
-    else if (v.trav == 3 && v.block == 64) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v3::Trav, 64, 6>), dim3(grid), dim3(64), 0, s, a, vs, q);
-    else if (v.trav == 2 && v.block == 256) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v2::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
-    else if (v.trav == 1 && v.block == 256) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v1::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    if (v.trav == 4) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v4::Trav, 64, 7>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 3) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v3::Trav, 64, 6>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 2) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v2::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 1) hipLaunchKernelGGL((accum::primary_jitter_kernel<MODE, v1::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -61,9 +61,9 @@ hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q
 
 hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s) {
     if (v.trav == 4) hipLaunchKernelGGL((accum::full_jitter_kernel<v4::TravAny, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
-    else if (v.trav == 3 && v.block == 64) hipLaunchKernelGGL((accum::full_jitter_kernel<v3::Trav, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
-    else if (v.trav == 2 && v.block == 256) hipLaunchKernelGGL((accum::full_jitter_kernel<v2::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
-    else if (v.trav == 1 && v.block == 256) hipLaunchKernelGGL((accum::full_jitter_kernel<v1::Trav<false>, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 3) hipLaunchKernelGGL((accum::full_jitter_kernel<v3::Trav, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q);
+    else if (v.trav == 2) hipLaunchKernelGGL((accum::full_jitter_kernel<v2::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
+    else if (v.trav == 1) hipLaunchKernelGGL((accum::full_jitter_kernel<v1::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

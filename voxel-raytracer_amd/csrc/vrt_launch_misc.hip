@@ -29,7 +29,7 @@ void denoise_tiling(int width, int height, int &tiles_x, int &n_tiles) {
     n_tiles = tiles_x * ((height + 15) / 16);
 }
 
-hipError_t denoise(const Denoise &d, int variant, bool whole_groups, hipStream_t s) {
+hipError_t denoise(const Denoise &d, bool whole_groups, hipStream_t s) {
     using namespace vrt::denoise;
     Args a;
     a.rgba = (const uint32_t *)d.rgba;
@@ -41,15 +41,6 @@ hipError_t denoise(const Denoise &d, int variant, bool whole_groups, hipStream_t
     a.group_order = d.group_order;
     a.tile_cost = d.tile_cost;
     a.rows_path = d.rows_path;
-    if (variant == 1) {
-#if VRT_AB
-        const dim3 grid((unsigned)((d.width + kTile - 1) / kTile), (unsigned)((d.height + kTile - 1) / kTile));
-        hipLaunchKernelGGL(denoise_kernel, grid, dim3(kTile, kTile), 0, s, a);
-        return hipGetLastError();
-#else
-        return hipErrorInvalidValue;
-#endif
-    }
     if (!whole_groups) {
         const dim3 grid((unsigned)a.tiles_x, (unsigned)(a.n_tiles / a.tiles_x));
         hipLaunchKernelGGL((denoise_px_kernel<2, 16>), grid, dim3(kTW / 2, 16), 0, s, a);

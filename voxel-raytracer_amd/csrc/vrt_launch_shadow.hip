@@ -3,8 +3,8 @@
 
 namespace vrt {
 namespace launch {
-hipError_t trace_shadow(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, size_t lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    return launch_mode<1>(v, a, vs, grid, lds, s, ev0, ev1);
+hipError_t trace_shadow(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    return launch_mode<1>(v, a, vs, grid, s, ev0, ev1);
 }
 }  // namespace launch
 }  // namespace vrt

@@ -204,10 +204,6 @@ void vrt_destroy(vrt_ctx *c) {
     (void)hipFree(c->accum.d_seed);
     if (c->accum.added) (void)hipEventDestroy(c->accum.added);
     if (c->accum.read) (void)hipEventDestroy(c->accum.read);
-    for (auto &d : c->defer) {
-        (void)hipFree(d.rec);
-        (void)hipFree(d.count);
-    }
     if (!c->seeds.empty()) (void)hipDeviceSynchronize();   // their launches may be on the caller's streams
     for (auto &b : c->seeds) (void)hipFree(b.d);
     if (!c->sched.empty()) (void)hipDeviceSynchronize();  // their launches may be on the caller's streams
@@ -370,14 +366,12 @@ int vrt_set_camera(vrt_ctx *c, const float inv_projection[16], const float inv_v
 }
 
 int vrt_variant_available(int variant) {
-    return variant >= 0 && variant < kNumVariants && (VRT_AB || kVariantShipped[variant]) ? 1 : 0;
+    return find_variant(variant) ? 1 : 0;
 }
 
 int vrt_set_variant(vrt_ctx *c, int variant) {
     if (!c) return VRT_E_INVALID;
-    if (variant < 0 || variant >= kNumVariants) return vrt_fail(c, VRT_E_INVALID, "vrt_set_variant: unknown variant");
-    if (!VRT_AB && !kVariantShipped[variant])
-        return vrt_fail(c, VRT_E_INVALID, "vrt_set_variant: an A/B variant; this library was built without them (make AB=1)");
+    if (!find_variant(variant)) return vrt_fail(c, VRT_E_INVALID, "vrt_set_variant: unknown variant");
     c->variant = variant;
     return VRT_OK;
 }
