@@ -219,6 +219,36 @@ int vrt_accum_add(vrt_ctx *ctx, uint32_t n_samples, uint32_t *total_out);
 int vrt_accum_resolve(vrt_ctx *ctx, uint8_t *out_rgba8, int32_t *out_id_dist, uint8_t *out_shown_rgba8);
 int vrt_accum_resolve_device(vrt_ctx *ctx, void *d_rgba8, void *d_id_dist, void *d_shown_rgba8, void *stream);
 
+/* Thin lens for the progressive accumulation. aperture: lens radius; focus_distance: distance of the plane of focus
+ * along the view axis. Both are in world units, the units of camera_pos (before u_voxelScale). Default (0, 1): a pinhole.
+ * VRT_E_INVALID unless aperture is finite and >= 0 and focus_distance is finite and > 0. The lens is context state, like the
+ * camera, and applies to every accumulation mode, with or without VRT_ACCUM_JITTER; its bytes join the restart rule (a change
+ * restarts the sums at `first`, the same values set again change nothing). Frames, views, shards and vrt_multi stay pinhole.
+ *
+ * Sample k with a lens, all arithmetic float32, every operation rounded on its own (no contraction):
+ *  1. d: the pixel's ray direction as the shader's prologue hands it to pathTrace (comp:640-641), with the jittered pixel
+ *     position under VRT_ACCUM_JITTER and the corner without; e = camera_pos.xyz.
+ *  2. Lens point (lu, lv) in [0,1)^2: two digital sequences over x^3+x+1 (m = 1,1,5) and x^3+x^2+1 (m = 1,3,1), 24 bits,
+ *     top bit flipped (a digital shift by 1/2, so that sample 0 is the lens centre):
+ *        direction numbers v[i] = m[i] << (31 - i) for i < 3, then v[i] = v[i-3] ^ (v[i-3] >> 3) ^ (x^2 term: v[i-1]) ^
+ *        (x term: v[i-2]); g(D, k) = XOR of D[i] over the set bits i of k;
+ *        lu(k) = (float)((g(U, k) >> 8) ^ 0x800000) * 0x1p-24f, lv(k) likewise with V.
+ *     The first eight: (1/2,1/2), (0,0), (3/4,1/4), (1/4,3/4), (1/8,5/8), (5/8,1/8), (3/8,3/8), (7/8,7/8).
+ *  3. Concentric map to the unit disc (Shirley-Chiu): a = 2*lu - 1, b = 2*lv - 1; a == b == 0: (lx, ly) = (0, 0); else if
+ *     |a| > |b|: r = a, phi = 0.785398163f * (b / a); else r = b, phi = 1.57079633f - 0.785398163f * (a / b);
+ *     lx = r * cos(phi), ly = r * sin(phi) with the conventions' Cephes sin/cos (det_sincos).
+ *  4. R = inv_view[0..2], U = inv_view[4..6], Z = inv_view[8..10] (column-major, as given);
+ *     cosd = -((d.x*Z.x + d.y*Z.y) + d.z*Z.z).
+ *  5. aperture == 0, or lx == ly == 0, or !(cosd > 0): the pinhole ray (e, d) bit for bit. Otherwise sx = aperture*lx,
+ *     sy = aperture*ly, o_i = (e_i + sx*R_i) + sy*U_i, t = focus_distance / cosd, p_i = e_i + t*d_i, dir = normalize(p - o),
+ *     and the sample is pathTrace from o along dir, which normalises dir again on entry as it does any ray (comp:441;
+ *     VRT_MODE_FULL: with initRNG(pixel, k)). Everything the shader derives
+ *     from the ray origin comes from o: gro = o * u_voxelScale, the medium looked up at floor(gro), the distance in the medium
+ *     and the eye vector of the shading.
+ *  6. The resolved id_dist stays the unjittered pinhole frame's.
+ * Sample 0 is therefore the frame, and aperture 0 reproduces the lens-free accumulations byte for byte. */
+int vrt_set_lens(vrt_ctx *ctx, float aperture, float focus_distance);
+
 /* Column-major mat4 x2 + vec4, exactly the std140 Camera block (comp:17-21). */
 int vrt_set_camera(vrt_ctx *ctx, const float inv_projection[16], const float inv_view[16],
                    const float camera_pos[4]);

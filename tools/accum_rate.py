@@ -1,11 +1,14 @@
 """Progressive-accumulation rate on one MI355X: wall time of one vrt_accum_add of n samples (n = 1, 4, 16, 64; the adds after
 the first, i.e. without pass 1 on the opaque path) on the 1080p dragon and nature frames and the 1080p room from inside, beside
 n times the frame time of vrt_dispatch in the same mode (vrt_dispatch_timed: events around each launch). --mode picks the modes
-(default: full), --jitter accumulates jittered samples (VRT_ACCUM_JITTER). Prints one JSON object per line; --out writes them to
-a file too.
+(default: full), --jitter accumulates jittered samples (VRT_ACCUM_JITTER). --lens APERTURE FOCUS (repeatable) adds the same
+accumulation with that thin lens (vrt_set_lens) beside it, with the side of the dispatcher's one-eye proofs the lens takes
+(shared: one eye lookup and one first lookup for every origin; per_lane: either made per lane) and its cost over the lens-free one. Prints one JSON object per line; --out
+writes them to a file too.
 
     python3 tools/accum_rate.py --out profiles/accum_rate.jsonl
     python3 tools/accum_rate.py --mode primary primary_shadow full --jitter --out profiles/accum_jitter_rate.jsonl
+    python3 tools/accum_rate.py --mode primary primary_shadow full --jitter --lens 0.1 40 --lens 10 40 --out profiles/accum_lens_rate.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -o a -- python3 tools/accum_rate.py --reps 3   (kernel times)
 """
 import argparse
@@ -35,6 +38,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--mode", nargs="+", default=["full"], choices=["primary", "primary_shadow", "full"])
     ap.add_argument("--jitter", action="store_true", help="jittered samples (anti-aliasing)")
+    ap.add_argument("--lens", nargs=2, type=float, action="append", default=[], metavar=("APERTURE", "FOCUS"),
+                    help="also with this thin lens (repeatable)")
     args = ap.parse_args()
     V = vrt_import.vrt()
     from conftest import MAPS, room_world
@@ -60,23 +65,33 @@ def main():
             ctx.dispatch_timed(W, H, 0, H, mode, d_rgba, d_id, 5)
             frame_ms = float(np.median(ctx.dispatch_timed(W, H, 0, H, mode, d_rgba, d_id, max(args.reps, 5))))
             for n in SAMPLES:
-                ctx.accum_begin(W, H, 0, mode=mode, jitter=args.jitter)
-                ctx.accum_add(n)          # the first add: pass 1 or the frame once per accumulation, code object load
-                ctx.synchronize()
-                ts = []
-                for _ in range(args.reps):
-                    t0 = time.perf_counter()
-                    ctx.accum_add(n)
+                base_ms = None
+                for lens in [None] + args.lens:
+                    ctx.set_lens(*(lens or (0.0, 1.0)))
+                    ctx.accum_begin(W, H, 0, mode=mode, jitter=args.jitter)
+                    ctx.accum_add(n)          # the first add: pass 1 or the frame once per accumulation, code object load
                     ctx.synchronize()
-                    ts.append((time.perf_counter() - t0) * 1e3)
-                ms = float(np.median(ts))
-                row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "n": n,
-                       "add_ms": round(ms, 4), "n_frames_ms": round(n * frame_ms, 4), "frame_ms": round(frame_ms, 4),
-                       "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
-                if args.mode != ["full"] or args.jitter:
-                    row.update(mode=mname, jitter=bool(args.jitter))
-                print(json.dumps(row), flush=True)
-                rows.append(row)
+                    ts = []
+                    for _ in range(args.reps):
+                        t0 = time.perf_counter()
+                        ctx.accum_add(n)
+                        ctx.synchronize()
+                        ts.append((time.perf_counter() - t0) * 1e3)
+                    ms = float(np.median(ts))
+                    row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "n": n,
+                           "add_ms": round(ms, 4), "n_frames_ms": round(n * frame_ms, 4), "frame_ms": round(frame_ms, 4),
+                           "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
+                    if args.mode != ["full"] or args.jitter or args.lens:
+                        row.update(mode=mname, jitter=bool(args.jitter))
+                    if lens is None:
+                        base_ms = ms
+                    else:
+                        sel = V.lens_choice(tex, cp, iv, lens[0])
+                        row.update(aperture=lens[0], focus=lens[1], side="shared" if sel["eye_shared"] and sel["first_shared"] else "per_lane",
+                                   eye_shared=sel["eye_shared"], first_shared=sel["first_shared"], vs_lens_free=round(ms / base_ms, 3))
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+            ctx.set_lens(0.0, 1.0)
     ctx.device_free(d_rgba)
     ctx.device_free(d_id)
     ctx.close()

@@ -251,6 +251,7 @@ def hip_lib():
         L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
         L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+        L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
         L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -514,6 +515,25 @@ def root0_choice(texels, eye, world_min=(-1023, -1023, -1023), world_max=(1024, 
         raise VrtError(f"vrt_test_root0 failed ({r})")
     return bool(out[0]), int(out[1]), (int(out[2]), int(out[3]), int(out[4])), int(out[5])
 
+def lens_choice(texels, cam_pos, inv_view, aperture, voxel_scale=1.0, world_min=(-1023, -1023, -1023),
+                world_max=(1024, 1024, 1024)):
+    """Host-only (vrt_test_lens_select): which side of each one-eye shortcut an accumulation with a thin lens of this aperture
+    takes -> dict(box_valid, eye_shared, first_shared, no_medium, empty, lo, hi, root_shift); root_shift -1: no wide form."""
+    L = test_lib()
+    L.vrt_test_lens_select.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int32)]
+    t = np.ascontiguousarray(texels, np.uint8)
+    cp = np.ascontiguousarray(cam_pos, np.float32)
+    iv = np.ascontiguousarray(inv_view, np.float32)
+    out = (C.c_int32 * 12)()
+    r = L.vrt_test_lens_select(t.ctypes.data if t.size else None, t.size, (C.c_int32 * 3)(*world_min), (C.c_int32 * 3)(*world_max),
+                               float(voxel_scale), _fptr(cp), _fptr(iv), float(aperture), out)
+    if r != 0:
+        raise VrtError(f"vrt_test_lens_select failed ({r})")
+    return dict(box_valid=bool(out[0]), eye_shared=bool(out[1]), first_shared=bool(out[2]), no_medium=bool(out[3]),
+                empty=bool(out[4]), lo=tuple(out[5:8]), hi=tuple(out[8:11]), root_shift=int(out[11]))
+
+
 def test_tile_order(tile_ticks, wave_slots, device=0):
     """Device probe (vrt_test_tile_order): the feedback scheduler's order kernel on synthetic per-tile ticks (4 per group) ->
     (order of the groups, how many groups at its head the general full path tracer would trace as part-tile waves)."""
@@ -769,6 +789,21 @@ class Context:
         self._chk(self._L.vrt_accum_begin_ex(self._h, int(width), int(height), int(mode), int(first_sample),
                                              ACCUM_JITTER if jitter else 0))
         self._accum_shape = (int(height), int(width))
+
+    def set_lens(self, aperture, focus_distance):
+        """Thin lens for the progressive accumulation (vrt_set_lens): lens radius `aperture` (0: a pinhole) and the distance of
+        the plane of focus along the view axis, both in world units. Frames stay pinhole."""
+        vals = []
+        for name, v, ok, want in (("aperture", aperture, lambda x: x >= 0.0, "finite and >= 0"),
+                                  ("focus_distance", focus_distance, lambda x: x > 0.0, "finite and > 0")):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{name}: expected a number, got {v!r}")
+            x = float(v)
+            f = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
+            if not (np.isfinite(f) and ok(f)):
+                raise ValueError(f"{name}: expected a float32 value {want}, got {v!r}")
+            vals.append(float(f))
+        self._chk(self._L.vrt_set_lens(self._h, vals[0], vals[1]))
 
     def accum_add(self, n_samples=1):
         """Enqueue n_samples more samples (vrt_accum_add) -> the samples now in the accumulation (n_samples after a restart)."""

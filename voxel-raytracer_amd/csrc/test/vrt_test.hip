@@ -140,6 +140,37 @@ int vrt_test_root0(const uint8_t *texels, size_t used_bytes, const int32_t wmin[
     return VRT_OK;
 }
 
+// Host-only (tests): which side of each one-eye shortcut an accumulation with this thin lens takes (vrt_layout.h lens_select(),
+// what enqueue() in vrt_dispatch.cpp consults). out: [0] the box of origins is finite, [1] one eye lookup for every origin,
+// [2] one first lookup of the wide kernels, [3] no origin in a medium (the v4 primary kernels), [4] every origin in empty
+// space (the opaque chain, given an opaque tree), [5..7] / [8..10] the box's lowest / highest cell, [11] log2 of the side of
+// the wide root 0 the launch uses (tightened to the box where root0_only holds; -1: no wide layout).
+// Returns 0 or VRT_E_MALFORMED.
+int vrt_test_lens_select(const uint8_t *texels, size_t used_bytes, const int32_t wmin[3], const int32_t wmax[3], float voxel_scale,
+                         const float cam_pos[4], const float inv_view[16], float aperture, int32_t out[12]) {
+    if (!wmin || !wmax || !cam_pos || !inv_view || !out) return VRT_E_INVALID;
+    vrt::Layout lay;
+    std::string err;
+    if (!vrt::build_layout(texels, used_bytes, lay, err)) return VRT_E_MALFORMED;
+    vrt::WideTree wt;
+    const bool wide_ok = !vrt::has_unit_internal_node(lay.records, wmin, wmax) && vrt::build_wide(lay.records, wmin, wmax, wt, err) &&
+                         !wt.roots.empty();
+    vrt::LensSel ls;
+    vrt::lens_select(lay.records, wide_ok ? &wt : nullptr, wmin, wmax, voxel_scale, cam_pos, inv_view, aperture, ls);
+    out[0] = ls.box_valid; out[1] = ls.eye_shared; out[2] = ls.first_shared; out[3] = ls.no_medium; out[4] = ls.empty;
+    for (int k = 0; k < 3; ++k) { out[5 + k] = ls.lo[k]; out[8 + k] = ls.hi[k]; }
+    out[11] = -1;
+    if (wide_ok) {
+        uint32_t node = wt.roots[0].node;
+        int shift = wt.roots[0].shift, mn[3] = {wt.roots[0].origin[0], wt.roots[0].origin[1], wt.roots[0].origin[2]};
+        const int corners[2][3] = {{ls.lo[0], ls.lo[1], ls.lo[2]}, {ls.hi[0], ls.hi[1], ls.hi[2]}};
+        if (wt.roots.size() == 1 && ls.box_valid && vrt::content_only_in_root0(lay.records, wt))
+            vrt::tighten_root0(wt, corners, 2, vrt::v3::kAnchorShift, node, shift, mn);
+        out[11] = shift;
+    }
+    return VRT_OK;
+}
+
 // Host-only check of the wide layout (tests without a GPU): builds it for the texel stream and world
 // bounds and answers n point queries through it. out: n * 8 words = w0, w1, mn[3], mx[3].
 // stats (optional): wide nodes, roots. Returns 0, VRT_E_MALFORMED, or VRT_E_STATE when the scene has no wide form.

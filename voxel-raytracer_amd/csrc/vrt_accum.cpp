@@ -3,7 +3,8 @@
 // (vrt_dispatch.cpp enqueue() with an AccumStep), which chooses between the sample-looped bounce and the general kernel
 // (vrt_accum.hip.h) -- or, for jittered samples, their jittered forms and the sample-looped primary kernels (vrt_jitter.hip.h) --
 // as it chooses between the forms of a frame. A jittered accumulation, or one of VRT_MODE_PRIMARY / _SHADOW, first renders the
-// mode's ordinary frame once: its id_dist is the resolve's, and without jitter its bytes are every sample's.
+// mode's ordinary frame once: its id_dist is the resolve's, and without jitter its bytes are every sample's. So does one with a
+// thin lens (vrt_set_lens, aperture > 0), whose samples the dispatcher enqueues as the lens kernels (vrt_lens.hip.h).
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
@@ -19,13 +20,14 @@ using Accum = vrt_ctx::Accum;
 bool same_inputs(const vrt_ctx *c, const Accum &ac) {
     return std::memcmp(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj) == 0 && std::memcmp(ac.inv_view, c->inv_view, sizeof ac.inv_view) == 0 &&
            std::memcmp(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos) == 0 && std::memcmp(&ac.params, &c->params, sizeof ac.params) == 0 &&
-           ac.tree_gen == c->tree_gen;
+           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && ac.tree_gen == c->tree_gen;
 }
 
 void take_inputs(const vrt_ctx *c, Accum &ac) {
     std::memcpy(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj);
     std::memcpy(ac.inv_view, c->inv_view, sizeof ac.inv_view);
     std::memcpy(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos);
+    std::memcpy(ac.lens, c->lens, sizeof ac.lens);
     ac.params = c->params;
     ac.tree_gen = c->tree_gen;
 }
@@ -122,17 +124,18 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         ac.frame = false;
     }
     const bool jitter = (ac.flags & VRT_ACCUM_JITTER) != 0u;
+    const bool lens = ac.lens[0] != 0.0f;   // a thin lens (vrt_set_lens): every sample has an origin of its own
     int r = VRT_OK;
-    if ((jitter || ac.mode != VRT_MODE_FULL) && !ac.frame) {   // the mode's unjittered frame, once per accumulation
+    if ((jitter || lens || ac.mode != VRT_MODE_FULL) && !ac.frame) {   // the mode's unjittered frame, once per accumulation
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream);
         ac.frame = r == VRT_OK;
     }
-    if (r == VRT_OK && !jitter && ac.mode != VRT_MODE_FULL) {   // every sample is that frame
+    if (r == VRT_OK && !jitter && !lens && ac.mode != VRT_MODE_FULL) {   // every sample is that frame
         const vrt::accum::Repeat q{ac.d_pass1, ac.d_sums, n_samples, (uint32_t)((size_t)ac.width * (size_t)ac.height)};
         const hipError_t e = vrt::launch::accum_repeat(q, c->stream);
         if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     } else if (r == VRT_OK) {
-        const AccumStep step{ac.first + base, n_samples, jitter};
+        const AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1]};
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again

@@ -1,4 +1,4 @@
-// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h, vrt_jitter.hip.h), shared by the host side (vrt_accum.cpp,
+// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h, vrt_jitter.hip.h, vrt_lens.hip.h), shared by the host side (vrt_accum.cpp,
 // vrt_dispatch.cpp) and the launch file (vrt_launch_accum.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +34,13 @@ struct Repeat {
     uint32_t *sums;
     uint32_t n;
     uint32_t pixels;
+};
+
+// A thin lens (vrt_lens.hip.h, include/vrt.h vrt_set_lens), the fourth argument of the lens kernels.
+struct Lens {
+    float aperture, focus;       // aperture > 0
+    uint32_t jitter;             // 1: the accumulation's VRT_ACCUM_JITTER
+    uint32_t lane_eye;           // 1: look the medium up at each sample's own origin; 0: View::eye0 / eye1 hold it for every origin
 };
 
 }  // namespace accum

@@ -235,6 +235,69 @@ VRT_DEV F3 jittered_ray_dir(const KArgs &a, const View &vw, int px, int py, uint
     return scale3(d, 1.0f / __builtin_sqrtf(dot3(d, d)));
 }
 
+// Thin lens of the progressive accumulation (include/vrt.h vrt_set_lens): sample k's ray from the lens point (lx, ly) on the unit
+// disc (vrt_lens.hip.h lens_point(): the same for every lane of a sample). d is the direction the prologue hands pathTrace without
+// a lens -- the jittered one (jx, jy = jitter_x(k), jitter_y(k)) or, with jx = jy = 0, the corner ray: float(px) + 0 is float(px)
+// -- and the ray returned is normalised as pathTrace normalises its argument, so that the pinhole ray is jittered_ray_dir() /
+// primary_ray_dir() bit for bit. The origin moves in the camera's right / up plane, the direction goes through
+// the point where the pinhole ray meets the plane of focus; the pinhole ray itself at the lens centre, aperture 0, or a ray
+// that does not point forward. eye0 / eye1: the raw leaf words at floor(o * u_voxelScale), filled in by the caller.
+struct LensRay { F3 o, dir; uint32_t eye0, eye1; };
+VRT_DEV LensRay lens_ray(const KArgs &a, const View &vw, int px, int py, float jx, float jy, float aperture, float focus, float lx, float ly) {
+    const float fx = (float)px + jx, fy = (float)py + jy;
+    float u = (fx / (float)a.width) * 2.0f - 1.0f;
+    float v = (fy / (float)a.height) * 2.0f - 1.0f;
+    float view[4];
+    mat_vec(vw.inv_proj, u, v, -1.0f, 1.0f, view);
+    if (__builtin_fabsf(view[3]) > 1e-6f) { float w = view[3]; view[0] = view[0] / w; view[1] = view[1] / w; view[2] = view[2] / w; view[3] = view[3] / w; }
+    F3 vd = normalize3(F3{view[0], view[1], view[2]});
+    float wd4[4];
+    mat_vec(vw.inv_view, vd.x, vd.y, vd.z, 0.0f, wd4);
+    const F3 d = normalize3(F3{wd4[0], wd4[1], wd4[2]});   // what main() hands pathTrace (comp:640-641)
+    const F3 e{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
+    LensRay r;
+    r.o = e; r.dir = d; r.eye0 = r.eye1 = 0u;
+    const F3 R{vw.inv_view[0], vw.inv_view[1], vw.inv_view[2]}, U{vw.inv_view[4], vw.inv_view[5], vw.inv_view[6]},
+             Z{vw.inv_view[8], vw.inv_view[9], vw.inv_view[10]};
+    const float cosd = -dot3(d, Z);
+    if (!(aperture == 0.0f || (lx == 0.0f && ly == 0.0f) || !(cosd > 0.0f))) {
+        const float sx = aperture * lx, sy = aperture * ly;
+        r.o = add3(add3(e, scale3(R, sx)), scale3(U, sy));
+        const float t = focus / cosd;
+        const F3 p = add3(e, scale3(d, t));
+        r.dir = normalize3(sub3(p, r.o));
+    }
+    r.dir = scale3(r.dir, 1.0f / __builtin_sqrtf(dot3(r.dir, r.dir)));   // pathTrace's own normalisation (comp:441)
+    return r;
+}
+
+// The node that holds p (octreeFind, comp:137-220, on the record array; the dispatcher's eye_lookup() in vrt_layout.cpp on the
+// device): its raw leaf words, 0 / 0 for empty space and outside the world. The medium at a lens sample's own origin when the
+// dispatcher cannot prove one node for every origin of the lens.
+VRT_DEV void record_find(const KArgs &a, I3 p, uint32_t &w0, uint32_t &w1) {
+    w0 = w1 = 0u;
+    if (!in_world(a, p)) return;
+    int mn[3] = {a.wmin[0], a.wmin[1], a.wmin[2]}, mx[3] = {a.wmax[0], a.wmax[1], a.wmax[2]};
+    const int q[3] = {p.x, p.y, p.z};
+    uint32_t rec = 0u;
+    for (int i = 0; i < 16; ++i) {
+        uint32_t ci = 0u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int mid = mn[k] + ((mx[k] - mn[k]) >> 1);
+            const bool hi = q[k] >= mid;
+            if (hi) { ci |= 1u << (2 - k); mn[k] = mid; } else mx[k] = mid;
+        }
+        const uint2 r = a.nodes[rec];
+        const uint32_t bit = 1u << ci;
+        if (!(r.x & bit)) return;
+        const uint32_t idx = r.y + (uint32_t)__builtin_popcount(r.x & 0xffu & (bit - 1u));
+        if (idx >= a.n_records) return;
+        if (r.x & (bit << 8)) { const uint2 l = a.nodes[idx]; w0 = l.x; w1 = l.y; return; }
+        rec = idx;
+    }
+}
+
 // traversals whose shadow() takes the dispatcher's LightSetup declare `static constexpr bool kHostLight = true`
 template <class T, class = void> struct host_light { static constexpr bool value = false; };
 template <class T> struct host_light<T, decltype((void)T::kHostLight)> { static constexpr bool value = T::kHostLight; };
@@ -251,21 +314,25 @@ struct Seed { F3 hp; uint32_t word; float iof; };   // the same in registers (MO
 // One pixel: ray generation (comp:624-641), primary-ray pathTrace, packing of the two outputs.
 // TRAV supplies the traversal: march(), shadow(). MODE: 0 primary, 1 primary + shadow ray. seed (MODE 1 only): see above.
 // JIT: the ray of jittered sample `sample` (jittered_ray_dir(); the progressive accumulation, vrt_jitter.hip.h).
-template <int MODE, class TRAV, bool JIT = false>
+// LENS: the ray `lens` of a thin-lens sample (lens_ray(), vrt_lens.hip.h): its origin, direction and the medium at its origin.
+template <int MODE, class TRAV, bool JIT = false, bool LENS = false>
 VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                         uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u) {
+                         uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u, const LensRay *lens = nullptr) {
     const float kPI = 3.14159265359f;
     F3 ray_dir;
-    if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
+    if constexpr (LENS) ray_dir = lens->dir;
+    else if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
     else ray_dir = primary_ray_dir(a, vw, px, py);
     F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
+    uint32_t eye0 = vw.eye0, eye1 = vw.eye1;
+    if constexpr (LENS) { ray_origin = lens->o; eye0 = lens->eye0; eye1 = lens->eye1; }
 
     int voxel_id = 0;
     int pixel_dist = a.wmax[0] - a.wmin[0];
     F3 gro = scale3(ray_origin, a.voxel_scale);
     // medium at the eye (comp:445-449)
     // medium at the eye (comp:445-449): the same node for every ray of the view, found once by the dispatcher
-    Decoded tvd = decode_leaf(vw.eye0, vw.eye1);
+    Decoded tvd = decode_leaf(eye0, eye1);
     float start_iof = (tvd.p[0] > 0.0f && tvd.p[0] < 3.0f) ? tvd.p[0] : 1.0f;
     float medium_density = tvd.c[3] * 5.0f;
     float mc[3] = {1.0f, 1.0f, 1.0f};
@@ -277,7 +344,7 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
     uint32_t seed_word = 0u;
     float seed_iof = 1.0f;
     // byte form of start_iof for traversals that test media on bytes: r(b) in (0, 3) <=> 1 <= b <= 254, else 1.0 == r(85)
-    const uint32_t eye_b = vw.eye1 & 0xffu;
+    const uint32_t eye_b = eye1 & 0xffu;
     const uint32_t iof_byte = (eye_b >= 1u && eye_b <= 254u) ? eye_b : 85u;
     bool hit = TRAV::march(a, tc_, gro, ray_dir, start_iof, iof_byte, h, &vw);
     // The uniforms of the shading stage. With a shadow march still to come they are re-read from the kernarg segment
@@ -304,7 +371,7 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
             l_ls.dposf = F3{la->light_dposf[0], la->light_dposf[1], la->light_dposf[2]};
             l_ls.dpos = I3{la->light_dpos[0], la->light_dpos[1], la->light_dpos[2]};
         }
-        l_eye = F3{lv_->cam_pos[0], lv_->cam_pos[1], lv_->cam_pos[2]};
+        if constexpr (!LENS) l_eye = F3{lv_->cam_pos[0], lv_->cam_pos[1], lv_->cam_pos[2]};   // a lens sample keeps its origin
         lo = late_out(la, lv_);
     }
     // late copies where they were loaded, the arguments themselves (read where they are used) otherwise
@@ -314,7 +381,7 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
     const auto scale_ = [&]() { if constexpr (kLate) return l_scale; else return a.voxel_scale; };
     const auto dim_ = [&]() { if constexpr (kLate) return l_dim; else return a.tex_dim; };
     const bool shade_fast = (kLate ? l_shade_fast : a.shade_fast) != 0;
-    const auto eye_ = [&]() { if constexpr (kLate) return l_eye; else return ray_origin; };  // ray_origin; gro = ray_origin * u_voxelScale
+    const auto eye_ = [&]() { if constexpr (kLate && !LENS) return l_eye; else return ray_origin; };  // ray_origin; gro = ray_origin * u_voxelScale
     const auto light_ = [&]() { if constexpr (kLate) return l_light; else return F3{a.light_dir[0], a.light_dir[1], a.light_dir[2]}; };
     float tc[3] = {gl[0], gl[1], gl[2]};
     if (!hit) {
@@ -418,9 +485,9 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
 }
 
 namespace full {  // MODE 2, defined in vrt_full.hip.h
-template <class TRAV, bool JIT = false>   // JIT: the ray of jittered sample `sample` (jittered_ray_dir())
+template <class TRAV, bool JIT = false, bool LENS = false>   // JIT: the ray of jittered sample `sample` (jittered_ray_dir()); LENS: `lens`
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t sample = 0u);
+                                 uint32_t sample = 0u, const LensRay *lens = nullptr);
 // pass 2 of the two-pass form: the diffuse bounce of a seeded pixel; false when the pixel has none (rgba untouched)
 template <class TRAV>
 __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, Seed seed, uint32_t &rgba, uint32_t sample = 0u);

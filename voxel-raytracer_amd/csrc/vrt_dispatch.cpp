@@ -188,6 +188,16 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
             }
         }
     }
+    // A thin lens (vrt_set_lens; accumulations only): every sample has an origin of its own, anywhere in a box of cells around
+    // the eye. What the loop above made at the eye is kept only where it holds at every origin of that box (vrt_layout.h
+    // lens_select()): otherwise the lens kernels look the medium up per lane and the wide kernels make their own first lookup.
+    const bool lens = acc && acc->aperture > 0.0f;
+    vrt::LensSel lsel;
+    if (lens) {
+        vrt::lens_select(c->host_records, c->wide_ok ? &c->wide : nullptr, c->params.world_min, c->params.world_max,
+                         c->params.voxel_scale, vs.v[0].cam_pos, vs.v[0].inv_view, acc->aperture, lsel);
+        if (!lsel.first_shared) vs.v[0].first_valid = 0;
+    }
     if (v.trav == 4 && mode != VRT_MODE_FULL) {
         // the v4 primary kernels hold the march loop for rays that start in refraction byte 85 (1.0) only: an eye inside a
         // medium (comp:445-449: refraction byte 1..254 of the voxel that holds it) takes the v3 kernels
@@ -196,6 +206,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
             const uint32_t b = vs.v[i].eye1 & 0xffu;
             eye_in_medium = eye_in_medium || (b >= 1u && b <= 254u && b != 85u);
         }
+        if (lens) eye_in_medium = !lsel.no_medium;   // ... any origin of the lens inside one
         if (eye_in_medium) { v.trav = 3; v.wpe = 6; }
     }
     a.voxel_scale = c->params.voxel_scale;
@@ -241,8 +252,12 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     // dragon.vox: [0, 1024)^3 holds everything in its cell [0, 256)^3, whose 64-unit cells the model spreads over: root 0
     // becomes [0, 256)^3 for eyes inside it. Not below the anchor level (a node of side 2^kAnchorShift).
     a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
-    if (a.root0_only && c->tight_root_on)
+    if (a.root0_only && c->tight_root_on && !lens)
         vrt::tighten_root0(c->wide, eyes, n_views, vrt::v3::kAnchorShift, a.root0_node, a.root0_shift, a.root0_min);
+    if (a.root0_only && c->tight_root_on && lens && lsel.box_valid) {   // a lens: every origin is an eye
+        const int corners[2][3] = {{lsel.lo[0], lsel.lo[1], lsel.lo[2]}, {lsel.hi[0], lsel.hi[1], lsel.hi[2]}};
+        vrt::tighten_root0(c->wide, corners, 2, vrt::v3::kAnchorShift, a.root0_node, a.root0_shift, a.root0_min);
+    }
     a.group_order = nullptr;
     a.tile_cost = nullptr;
     a.split_count = nullptr;
@@ -293,6 +308,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         if (!c->scene_opaque_valid) { c->scene_opaque = vrt::tree_is_opaque(c->host_records); c->scene_opaque_valid = true; }
         const uint32_t eye_alpha = vs.v[0].eye0 >> 24, eye_b = vs.v[0].eye1 & 0xffu;
         two_pass = c->scene_opaque && eye_alpha == 0u && (eye_b == 0u || eye_b == 85u || eye_b == 255u);
+        if (lens) two_pass = c->scene_opaque && lsel.empty;   // every origin of the lens in empty space
     }
     // the general full path tracer starts the heaviest groups of an ordered, non-measuring launch as part-tile waves (KArgs::split_count)
     if (mode == VRT_MODE_FULL && !two_pass && st && a.group_order && c->heavy_split_on) {
@@ -308,7 +324,25 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         q.pass1_rgba = ac.d_pass1;
         q.out_id = ac.d_id;
         e = hipSuccess;
-        if (acc->jitter) {   // every sample has a ray of its own: jittered_ray_dir(), no per-projection tables
+        if (lens) {   // the thin-lens kernels (vrt_lens.hip.h), the same three forms as the jittered ones below
+            vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
+            vs.v[0].gen_z = 0.0f;
+            vs.v[0].gen_fast = 0u;
+            const vrt::accum::Lens l{acc->aperture, acc->focus, acc->jitter ? 1u : 0u, lsel.eye_shared ? 0u : 1u};
+            q.first = acc->first;
+            q.n = acc->n;
+            if (mode != VRT_MODE_FULL) {
+                e = vrt::launch::lens_primary(mode, v, a, vs, q, l, (int)grid, s);
+            } else if (two_pass) {
+                e = vrt::launch::lens_opaque(a, vs, q, l, (int)grid, s);
+            } else {
+                for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
+                    q.first = acc->first + k;
+                    q.n = 1u;
+                    e = vrt::launch::lens_full(v, a, vs, q, l, (int)grid, s);
+                }
+            }
+        } else if (acc->jitter) {   // every sample has a ray of its own: jittered_ray_dir(), no per-projection tables
             vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
             vs.v[0].gen_z = 0.0f;
             vs.v[0].gen_fast = 0u;

@@ -163,23 +163,27 @@ VRT_DEV RayS make_ray(F3 o, F3 d, float iof, float w, const float tint[3], float
 }
 
 // sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
-// with JIT also the jittered sample whose ray is traced (jittered_ray_dir(), vrt_jitter.hip.h)
-template <class TRAV, bool JIT>
+// with JIT also the jittered sample whose ray is traced (jittered_ray_dir(), vrt_jitter.hip.h); LENS: the ray `lens` instead
+// (lens_ray(), vrt_lens.hip.h), origin and medium included
+template <class TRAV, bool JIT, bool LENS>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t sample) {
+                                 uint32_t sample, const LensRay *lens) {
     const float kPI = 3.14159265359f;
     const float sky[3] = {0.5f, 0.7f, 1.0f};
     const float kSun = 3.0f;
     uint32_t rng = rng_init(px, py, sample);
     F3 ray_dir;
-    if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
+    if constexpr (LENS) ray_dir = lens->dir;
+    else if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
     else ray_dir = primary_ray_dir(a, vw, px, py);
-    const F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
+    F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
+    uint32_t eye0 = vw.eye0, eye1 = vw.eye1;
+    if constexpr (LENS) { ray_origin = lens->o; eye0 = lens->eye0; eye1 = lens->eye1; }   // the lens sample's origin and its medium
 
     int voxel_id = 0;
     int pixel_dist = a.wmax[0] - a.wmin[0];
     F3 gro = scale3(ray_origin, a.voxel_scale);
-    Decoded tv = decode_leaf(vw.eye0, vw.eye1);  // medium at the eye: looked up once by the dispatcher
+    Decoded tv = decode_leaf(eye0, eye1);  // medium at the eye: looked up once by the dispatcher (LENS: by the caller)
     float start_iof = (tv.p[0] > 0.0f && tv.p[0] < 3.0f) ? tv.p[0] : 1.0f;
 
     // The ray stack (comp:451) lives in private memory: 8 x 68 bytes per lane. (Holding the entry pushed last in registers

@@ -76,6 +76,7 @@ struct vrt_ctx {
     vrt_scene_info info{};
     vrt_params params{};
     float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
+    float lens[2] = {0.0f, 1.0f};   // vrt_set_lens: aperture, focus distance (the progressive accumulation only)
     int variant = 0;
     int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL = denoise::Args::rows_path: 0 each wave the cheaper walk; 2, 3: one walk forced
     // scratch outputs for the host-buffer dispatch
@@ -169,6 +170,7 @@ struct vrt_ctx {
         bool frame = false;                      // d_pass1 and d_id hold the mode's unjittered frame (jitter, or modes 0 / 1)
         // what every sample depends on, as it was at the first sample in the sums
         float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
+        float lens[2] = {0.0f, 1.0f};
         vrt_params params{};
         uint64_t tree_gen = 0;
         uint32_t *d_sums = nullptr;              // 4 words per pixel
@@ -213,7 +215,8 @@ int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-bu
 // AccumStep: instead of rendering a frame, add samples first .. first + n - 1 of VRT_MODE_FULL to the context's accumulation
 // (vrt_accum.cpp; whole frame, the context's camera, d_rgba / d_id unused)
 // (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_jitter.hip.h)
-struct AccumStep { uint32_t first, n; bool jitter; };
+// (aperture > 0: the samples of a thin lens, vrt_set_lens; vrt_lens.hip.h)
+struct AccumStep { uint32_t first, n; bool jitter; float aperture = 0.0f, focus = 1.0f; };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
 SchedState *sched_state(vrt_ctx *c, hipStream_t s, int width, int n_rows, int row0, int row_stride, int tile_rows, int mode,

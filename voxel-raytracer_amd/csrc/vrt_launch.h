@@ -66,6 +66,11 @@ hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const View
 hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
 hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
 hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s);
+// The thin-lens samples (vrt_lens.hip.h, vrt_launch_accum.hip) in the shapes of the three above: lens_primary (modes 0 / 1, q.n
+// samples), lens_opaque (the opaque chain, q.n samples), lens_full (one sample of the general full path tracer).
+hipError_t lens_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t lens_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t lens_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt

@@ -2,7 +2,8 @@
 // scenes, the general kernel with a sample index in the shapes trace_full() launches trace_kernel<2> in, and the resolve. Then the
 // jittered samples and the primary modes (vrt_jitter.hip.h): the sample-looped primary / primary + shadow kernel in the
 // traversals a frame of those modes takes, the looped opaque full path tracer, the general full path tracer with a jittered ray
-// in the shapes of accum_full, and the repeat of a frame.
+// in the shapes of accum_full, and the repeat of a frame. Last, the thin-lens samples (vrt_lens.hip.h) in the shapes of their
+// jittered forms.
 #include <hip/hip_runtime.h>
 
 #include "vrt_launch.h"
@@ -12,6 +13,7 @@
 #include "vrt_kernels_v4.hip.h"
 #include "vrt_accum.hip.h"
 #include "vrt_jitter.hip.h"
+#include "vrt_lens.hip.h"
 
 namespace vrt {
 namespace launch {
@@ -71,6 +73,39 @@ hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, cons
 hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s) {
     if (q.pixels == 0u) return hipSuccess;
     hipLaunchKernelGGL(accum::repeat_kernel, dim3((q.pixels + 255u) / 256u), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
+// ---- thin lens (vrt_lens.hip.h) ----
+namespace {
+template <int MODE>
+hipError_t lens_primary_mode(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s) {
+    if (v.trav == 4) hipLaunchKernelGGL((accum::primary_lens_kernel<MODE, v4::Trav, 64, 7>), dim3(grid), dim3(64), 0, s, a, vs, q, l);
+    else if (v.trav == 3) hipLaunchKernelGGL((accum::primary_lens_kernel<MODE, v3::Trav, 64, 6>), dim3(grid), dim3(64), 0, s, a, vs, q, l);
+    else if (v.trav == 2) hipLaunchKernelGGL((accum::primary_lens_kernel<MODE, v2::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q, l);
+    else if (v.trav == 1) hipLaunchKernelGGL((accum::primary_lens_kernel<MODE, v1::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q, l);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t lens_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s) {
+    if (mode == VRT_MODE_PRIMARY) return lens_primary_mode<0>(v, a, vs, q, l, grid, s);
+    if (mode == VRT_MODE_PRIMARY_SHADOW) return lens_primary_mode<1>(v, a, vs, q, l, grid, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t lens_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s) {
+    hipLaunchKernelGGL((accum::opaque_lens_kernel<v4::Trav, 6>), dim3(grid), dim3(64), 0, s, a, vs, q, l);
+    return hipGetLastError();
+}
+
+hipError_t lens_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s) {
+    if (v.trav == 4) hipLaunchKernelGGL((accum::full_lens_kernel<v4::TravAny, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q, l);
+    else if (v.trav == 3) hipLaunchKernelGGL((accum::full_lens_kernel<v3::Trav, 64, 5>), dim3(grid), dim3(64), 0, s, a, vs, q, l);
+    else if (v.trav == 2) hipLaunchKernelGGL((accum::full_lens_kernel<v2::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q, l);
+    else if (v.trav == 1) hipLaunchKernelGGL((accum::full_lens_kernel<v1::Trav, 256, 1>), dim3(grid), dim3(256), 0, s, a, vs, q, l);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 #include "vrt_layout.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include <deque>
@@ -696,5 +697,128 @@ bool tree_is_opaque(const std::vector<Record> &rec) {
     return true;
 }
 
+
+
+namespace {
+
+// the leaves (and absent children) of the record array that a box of cells [lo, hi] touches: whether any is a medium for the
+// primary kernels' start (the dispatcher's eye_in_medium), whether all are empty space for the opaque chain (its eye test)
+struct BoxWalk {
+    const std::vector<Record> &recs;
+    const int *lo, *hi;
+    long budget;
+    bool medium = false, nonempty = false, gave_up = false;
+    void leaf(uint32_t w0, uint32_t w1) {
+        const uint32_t b = w1 & 0xffu, alpha = w0 >> 24;
+        if (b >= 1u && b <= 254u && b != 85u) medium = true;
+        if (!(alpha == 0u && (b == 0u || b == 85u || b == 255u))) nonempty = true;
+    }
+    void visit(uint32_t rec, const Box &b, int depth) {
+        if (gave_up || --budget < 0 || depth >= 16) { gave_up = true; return; }
+        for (uint32_t ci = 0; ci < 8; ++ci) {
+            const Box cb = child_box(b, ci);
+            bool touches = true;
+            for (int k = 0; k < 3; ++k)
+                if (cb.mx[k] <= lo[k] || cb.mn[k] > hi[k]) touches = false;
+            if (!touches) continue;
+            uint32_t idx = 0;
+            const int kind = child_of(recs, rec, ci, idx);
+            if (kind == kAbsent) leaf(0u, 0u);
+            else if (kind == kLeaf) leaf(recs[idx].w0, recs[idx].w1);
+            else visit(idx, cb, depth + 1);
+            if (gave_up) return;
+        }
+    }
+};
+
+// floor(v) as the device converts it to int (saturating) -- false when the value is not finite or does not fit
+bool cell_of(double v, int &out) {
+    if (!std::isfinite(v)) return false;
+    const double f = std::floor(v);
+    if (f < -2147483648.0 || f > 2147483647.0) return false;
+    out = (int)f;
+    return true;
+}
+
+}  // namespace
+
+void lens_select(const std::vector<Record> &records, const WideTree *wide, const int wmin[3], const int wmax[3], float voxel_scale,
+                 const float cam_pos[4], const float inv_view[16], float aperture, LensSel &out) {
+    out = LensSel{};
+    // |o_i - e_i| <= aperture * (|R_i| + |U_i|) in exact arithmetic (|lx|, |ly| <= 1 up to the rounding of sin / cos); the
+    // float32 evaluation adds a few roundings of at most 2^-24 relative to |e_i| + that extent, and so do the scale and floor
+    for (int k = 0; k < 3; ++k) {
+        const double e = cam_pos[k], ext = (double)aperture * (std::fabs((double)inv_view[k]) + std::fabs((double)inv_view[4 + k]));
+        const double bound = ext * (1.0 + 0x1p-20) + (std::fabs(e) + ext) * 0x1p-20;
+        const double g0 = (e - bound) * (double)voxel_scale, g1 = (e + bound) * (double)voxel_scale;
+        double glo = g0 < g1 ? g0 : g1, ghi = g0 < g1 ? g1 : g0;
+        glo -= std::fabs(glo) * 0x1p-20;
+        ghi += std::fabs(ghi) * 0x1p-20;
+        if (!cell_of(glo, out.lo[k]) || !cell_of(ghi, out.hi[k])) return;
+    }
+    out.box_valid = true;
+    const int *lo = out.lo, *hi = out.hi;
+    if (records.empty()) { out.eye_shared = out.no_medium = out.empty = true; return; }
+    bool all_out = false, all_in = true;
+    for (int k = 0; k < 3; ++k) {
+        if (hi[k] < wmin[k] || lo[k] >= wmax[k]) all_out = true;
+        if (lo[k] < wmin[k] || hi[k] >= wmax[k]) all_in = false;
+    }
+    // eye_lookup(): 0 / 0 outside the world; inside, the node that holds the whole box, if one does
+    if (all_out) {
+        out.eye_shared = true;
+    } else if (all_in) {
+        Box b;
+        for (int k = 0; k < 3; ++k) { b.mn[k] = wmin[k]; b.mx[k] = wmax[k]; }
+        uint32_t rec = 0;
+        for (int i = 0; i < 16; ++i) {
+            uint32_t ci = 0;
+            bool straddles = false;
+            for (int k = 0; k < 3; ++k) {
+                const int mid = b.mn[k] + ((b.mx[k] - b.mn[k]) >> 1);
+                if ((lo[k] >= mid) != (hi[k] >= mid)) straddles = true;
+                if (lo[k] >= mid) ci |= 1u << (2 - k);
+            }
+            if (straddles) break;
+            b = child_box(b, ci);
+            uint32_t idx = 0;
+            const int kind = child_of(records, rec, ci, idx);
+            if (kind != kInternal) { out.eye_shared = true; break; }
+            rec = idx;
+        }
+    }
+    // first_find(): the wide cell that holds the whole box, if one does (a box partly outside the world or root 0's cube
+    // gets no first lookup: the kernels make their own)
+    if (wide && !wide->roots.empty() && all_in) {
+        const WideRoot &r = wide->roots[0];
+        bool in_root = true;
+        for (int k = 0; k < 3; ++k)
+            if (((uint32_t)(lo[k] ^ r.origin[k]) >> (r.shift & 31)) || ((uint32_t)(hi[k] ^ r.origin[k]) >> (r.shift & 31))) in_root = false;
+        uint32_t node = r.node;
+        int s = r.shift;
+        while (in_root) {
+            const int cs = s - 2;
+            bool same = true;
+            for (int k = 0; k < 3; ++k)
+                if ((((uint32_t)lo[k] >> cs) & 3u) != (((uint32_t)hi[k] >> cs) & 3u)) same = false;
+            if (!same) break;
+            const uint32_t ci = ((((uint32_t)lo[0] >> cs) & 3u) << 4) | ((((uint32_t)lo[1] >> cs) & 3u) << 2) | (((uint32_t)lo[2] >> cs) & 3u);
+            const WideCell c = wide->cells[(size_t)node * 64 + ci];
+            if (!(c.w1 & kWideInternal)) { out.first_shared = true; break; }
+            node = c.w0;
+            s = cs;
+            if (cs < 2 || (size_t)node * 64 + 63 >= wide->cells.size()) break;
+        }
+    }
+    // the leaves the box touches (outside the world: 0 / 0, empty space)
+    BoxWalk w{records, lo, hi, 1l << 16};
+    if (!all_out) {
+        Box b;
+        for (int k = 0; k < 3; ++k) { b.mn[k] = wmin[k]; b.mx[k] = wmax[k]; }
+        w.visit(0u, b, 0);
+    }
+    out.no_medium = !w.gave_up && !w.medium;
+    out.empty = !w.gave_up && !w.nonempty;
+}
 
 }  // namespace vrt

@@ -128,6 +128,25 @@ void eye_lookup(const std::vector<Record> &records, const int wmin[3], const int
 struct FirstFind { uint32_t w0, w1, node, anode; int s, as; };
 bool first_find(const WideTree &wide, const int wmin[3], const int wmax[3], const int p[3], int anchor_shift, FirstFind &out);
 
+// A thin lens (include/vrt.h vrt_set_lens) moves the ray origin of every sample inside the camera's right / up plane. What the
+// dispatcher makes once at the eye holds for a lens only where it holds at every origin the lens can produce: lens_select()
+// bounds floor(o * voxel_scale) over all samples by a box of cells (box_valid false: no finite box, nothing is shared) and
+// proves each one-eye shortcut on that box.
+//   eye_shared    one node holds the whole box (eye_lookup() is the same everywhere): View::eye0 / eye1 (else per lane)
+//   first_shared  one wide cell holds the whole box (first_find() is the same everywhere): View::first_* (else the kernels' own)
+//   no_medium     no leaf the box touches is a medium (refraction byte 1..254 other than 85): the v4 primary kernels
+//   empty         every leaf the box touches is empty space in the sense of the opaque chain (alpha 0, refraction byte 0, 85
+//                 or 255): MODE 6's chain, given an opaque tree
+// tighten_root0() takes the box's two corners as its eyes. The walks give up (answering "not proven") beyond a fixed number
+// of nodes.
+struct LensSel {
+    bool box_valid = false;
+    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // cells, inclusive
+    bool eye_shared = false, first_shared = false, no_medium = false, empty = false;
+};
+void lens_select(const std::vector<Record> &records, const WideTree *wide, const int wmin[3], const int wmax[3], float voxel_scale,
+                 const float cam_pos[4], const float inv_view[16], float aperture, LensSel &out);
+
 // ---------------------------------------------------------------------------------------------
 // Edits without a rebuild. A voxel edit changes the octree below some ancestor A of the voxel and
 // nothing else. When A is an INTERNAL node before and after the edit, the device structures can be

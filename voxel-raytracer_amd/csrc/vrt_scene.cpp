@@ -365,6 +365,17 @@ int vrt_set_camera(vrt_ctx *c, const float inv_projection[16], const float inv_v
     return VRT_OK;
 }
 
+int vrt_set_lens(vrt_ctx *c, float aperture, float focus_distance) {
+    if (!c) return VRT_E_INVALID;
+    if (!(std::isfinite(aperture) && aperture >= 0.0f))
+        return vrt_fail(c, VRT_E_INVALID, "vrt_set_lens: the aperture must be finite and >= 0");
+    if (!(std::isfinite(focus_distance) && focus_distance > 0.0f))
+        return vrt_fail(c, VRT_E_INVALID, "vrt_set_lens: the focus distance must be finite and > 0");
+    c->lens[0] = aperture;
+    c->lens[1] = focus_distance;
+    return VRT_OK;
+}
+
 int vrt_variant_available(int variant) {
     return find_variant(variant) ? 1 : 0;
 }
