@@ -16,6 +16,7 @@
 #include "../../../include/vrt.h"
 #include "../vrt_common.hip.h"
 #include "../vrt_full.hip.h"
+#include "../vrt_kernels_v4.hip.h"
 #include "../vrt_layout.h"
 #include "../vrt_sched.hip.h"
 
@@ -63,6 +64,50 @@ __global__ void math_probe_full_kernel(int op, const float *x, const float *y, f
 }
 
 }  // namespace full
+
+// The march step of v4 (dda_step + axis_of, the node planes of find()) against the arithmetic it replaced, written out in
+// plain C: the position after the step, its floor as integers, the exit axis and the planes of a node of side 2^t there.
+// in: 16 words per case = rp[3], plane[3], dir[3], inv[3], push[3] (floats), t (uint); dpos[3] (ints) separately.
+// out: 20 words per case = the step's rp[3], mp[3], axis, planes[3]; then the same from the old arithmetic.
+__global__ void march_step_probe_kernel(const float *in, const int *dpos, uint32_t *out, int n) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *q = in + 16 * i;
+    const F3 plane{q[3], q[4], q[5]}, dir{q[6], q[7], q[8]}, inv{q[9], q[10], q[11]}, push{q[12], q[13], q[14]};
+    const uint32_t t = __float_as_uint(q[15]);
+    const I3 dp{dpos[3 * i], dpos[3 * i + 1], dpos[3 * i + 2]};
+    uint32_t *o = out + 20 * i;
+    {   // the kernel's step
+        F3 rp{q[0], q[1], q[2]};
+        I3 mp;
+        const v4::Trav::Step st = v4::Trav::dda_step(rp, mp, dir, inv, push, plane);
+        const F3 pl = v4::Trav::planes(mp, dp, t);
+        o[0] = __float_as_uint(rp.x); o[1] = __float_as_uint(rp.y); o[2] = __float_as_uint(rp.z);
+        o[3] = (uint32_t)mp.x; o[4] = (uint32_t)mp.y; o[5] = (uint32_t)mp.z;
+        o[6] = (uint32_t)v4::Trav::axis_of(st);
+        o[7] = __float_as_uint(pl.x); o[8] = __float_as_uint(pl.y); o[9] = __float_as_uint(pl.z);
+    }
+    {   // the arithmetic it replaced: selects, two floors, float planes
+        F3 rp{q[0], q[1], q[2]};
+        const float tx = (plane.x - rp.x) * inv.x, ty = (plane.y - rp.y) * inv.y, tz = (plane.z - rp.z) * inv.z;
+        const bool ax = tx < (ty < tz ? ty : tz), ayz = ty < tz;
+        const float ts = ax ? tx : (ayz ? ty : tz);
+        rp.x = rp.x + dir.x * ts; rp.y = rp.y + dir.y * ts; rp.z = rp.z + dir.z * ts;
+        const int axis = ax ? 0 : (ayz ? 1 : 2);
+        if (axis == 0) rp.x = push.x + rp.x;
+        if (axis == 1) rp.y = push.y + rp.y;
+        if (axis == 2) rp.z = push.z + rp.z;
+        const F3 pf{__builtin_floorf(rp.x), __builtin_floorf(rp.y), __builtin_floorf(rp.z)};
+        const float side = __uint_as_float((127u + t) << 23), inv_side = __uint_as_float((127u - t) << 23);
+        const F3 dposf{dp.x ? 1.0f : 0.0f, dp.y ? 1.0f : 0.0f, dp.z ? 1.0f : 0.0f};
+        o[10] = __float_as_uint(rp.x); o[11] = __float_as_uint(rp.y); o[12] = __float_as_uint(rp.z);
+        o[13] = (uint32_t)(int)pf.x; o[14] = (uint32_t)(int)pf.y; o[15] = (uint32_t)(int)pf.z;
+        o[16] = (uint32_t)axis;
+        o[17] = __float_as_uint((__builtin_floorf(pf.x * inv_side) + dposf.x) * side);
+        o[18] = __float_as_uint((__builtin_floorf(pf.y * inv_side) + dposf.y) * side);
+        o[19] = __float_as_uint((__builtin_floorf(pf.z * inv_side) + dposf.z) * side);
+    }
+}
 }  // namespace vrt
 
 namespace vrt_internal {
@@ -100,6 +145,26 @@ int vrt_test_math(int device, int op, const float *x, const float *y, float *out
     VRT_HIP(c, hipGetLastError());
     VRT_HIP(c, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, stream));
     VRT_HIP(c, hipStreamSynchronize(stream));
+    return VRT_OK;
+}
+
+// Device probe of the v4 march step (march_step_probe_kernel): n cases, host arrays, synchronous.
+int vrt_test_march_step(int device, const float *in, const int32_t *dpos, uint32_t *out, int n) {
+    if (!in || !dpos || !out || n < 1) return VRT_E_INVALID;
+    VRT_HIP(c, hipSetDevice(device));
+    float *din = nullptr;
+    int *ddp = nullptr;
+    uint32_t *dout = nullptr;
+    struct Free { float *&a; int *&b; uint32_t *&o; ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(o); } } free_on_exit{din, ddp, dout};
+    VRT_HIP(c, hipMalloc((void **)&din, (size_t)n * 16 * sizeof(float)));
+    VRT_HIP(c, hipMalloc((void **)&ddp, (size_t)n * 3 * sizeof(int)));
+    VRT_HIP(c, hipMalloc((void **)&dout, (size_t)n * 20 * sizeof(uint32_t)));
+    VRT_HIP(c, hipMemcpy(din, in, (size_t)n * 16 * sizeof(float), hipMemcpyHostToDevice));
+    VRT_HIP(c, hipMemcpy(ddp, dpos, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(vrt::march_step_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, din, ddp, dout, n);
+    VRT_HIP(c, hipGetLastError());
+    VRT_HIP(c, hipMemcpy(out, dout, (size_t)n * 20 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VRT_HIP(c, hipDeviceSynchronize());
     return VRT_OK;
 }
 

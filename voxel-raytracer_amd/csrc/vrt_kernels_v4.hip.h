@@ -24,10 +24,9 @@
 //   * "no current node" is a walk state whose tests cannot pass (cell shift 0 and a `last` point no representable
 //     floor() can come within 4 of), not an extra flag;
 //   * planes, min-axis selection and the push in plain f32 / integer ops from the first row of the table above: the cells are read
-//     in a second form (vrt_layout.h to_cell4) that carries 2^t as a float exponent, so a node's planes are
-//     (floor(floor(p) * 2^-t) + dpos) * 2^t in four f32 operations per axis -- every step exact, hence the same floats
-//     the integer arithmetic gives -- the child node as a byte offset, and the medium byte with 85 for empty space, so
-//     that "the medium changed" is one comparison;
+//     in a second form (vrt_layout.h to_cell4) that carries t + 1 in a float's exponent field, so a node's planes are
+//     ((p >> t) + dpos) << t in two integer operations and one exact conversion per axis (planes()) -- the child node
+//     as a byte offset, and the medium byte with 85 for empty space, so that "the medium changed" is one comparison;
 //   * the first cell load of a lookup is straight-line code, only a further descent loops; the walk's reference point
 //     moves only when the node changes.
 #pragma once
@@ -88,14 +87,25 @@ struct TravT {
                        bz = __builtin_amdgcn_ubfe((uint32_t)p.z, cs, 2u);
         // node + (((bx << 2 | by) << 2 | bz) << 3) as three v_lshl_add_u32 (the compiler spreads it over four instructions)
         uint32_t off;
-        asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(off) : "v"(bx), "v"(by));
-        asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(off) : "v"(off), "v"(bz));
-        asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(off) : "v"(off), "v"(node));
+        asm("v_lshl_add_u32 %0, %1, 2, %2\n\t"
+            "v_lshl_add_u32 %0, %0, 2, %3\n\t"
+            "v_lshl_add_u32 %0, %0, 3, %4"
+            : "=&v"(off) : "v"(bx), "v"(by), "v"(bz), "v"(node));
         return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(a.cells4) + off);
     }
 
-    // octreeFind (comp:137-220): the deepest octree node containing p (= floor of a ray position, pf the same as
-    // floats), through the wide layout.
+    // The planes of the node of side 2^t that holds the cell p: per axis the face a ray with signs dpos leaves through,
+    // ((p >> t) + dpos) << t, as a float. p lies in the world here (|p| < 2^24 by far), so the arithmetic shift is the
+    // floor of p / 2^t, nothing overflows and the conversion is exact: the same floats as the float form
+    // (floor(floor(x) * 2^-t) + dposf) * 2^t of the first lookup of v4, +0 included (tests/test_march_step_identities.py).
+    // Two integer operations and one conversion per axis, and no second floor of the ray position.
+    static VRT_DEV F3 planes(I3 p, I3 dpos, uint32_t t) {
+        return F3{(float)(int)((uint32_t)((p.x >> t) + dpos.x) << t), (float)(int)((uint32_t)((p.y >> t) + dpos.y) << t),
+                  (float)(int)((uint32_t)((p.z >> t) + dpos.z) << t)};
+    }
+
+    // octreeFind (comp:137-220): the deepest octree node containing p (= floor of a ray position), through the wide
+    // layout.
     // kGo: the answer came from a cell (f set). kDone: from the record walk above the wide roots (f set).
     // kOutside: p is outside the world (comp:143-145): f untouched -- and w then refers to p as if it were a point of wide
     // root 0: a caller that goes on after kOutside (only the first lookups of march() and shadow() do) must reset(w).
@@ -104,7 +114,7 @@ struct TravT {
     // test, then wide root 0 when the point lies in its cube -- where the descent from the octree root would arrive
     // anyway -- else the record walk of v3 (the other seven octants of the reference's world: a nested, rarely
     // entered block). Inside the block everything is a select, so its lanes meet again after a handful of instructions.
-    static VRT_DEV int find(const KArgs &a, const Ctx &c, I3 p, F3 pf, I3 dpos, F3 dposf, Walk &w, Found &f, bool forward, uint32_t leaving_m = 85u) {
+    static VRT_DEV int find(const KArgs &a, const Ctx &c, I3 p, I3 dpos, Walk &w, Found &f, bool forward, uint32_t leaving_m = 85u) {
         const uint32_t d = (uint32_t)((p.x ^ w.last.x) | (p.y ^ w.last.y) | (p.z ^ w.last.z));
         const bool in_node = (d >> w.cs) < 4u;
         const bool in_anchor = (d >> w.acs) < 4u;     // the anchor contains the node: in_node implies in_anchor
@@ -154,8 +164,8 @@ struct TravT {
         }
         if (status == kGo) {
             uint2 cell = load_cell(a, node, cs, p);
-            uint32_t e = cell.y & kExpMask;
-            if (e == 0u) {            // subdivided further: cell.x = the child wide node
+            uint32_t tp1 = __builtin_amdgcn_ubfe(cell.y, 23u, 5u);   // kExpMask's field: t + 1, 0 in a subdivided cell
+            if (tp1 == 0u) {          // subdivided further: cell.x = the child wide node
                 do {
                     node = cell.x;
                     const bool up = cs == (uint32_t)kAnchorShift;    // the child has side 2^kAnchorShift: the new anchor
@@ -163,16 +173,12 @@ struct TravT {
                     anode = up ? node : anode;
                     acs = up ? cs : acs;
                     cell = load_cell(a, node, cs, p);
-                    e = cell.y & kExpMask;
-                } while (e == 0u);
+                    tp1 = __builtin_amdgcn_ubfe(cell.y, 23u, 5u);
+                } while (tp1 == 0u);
                 last = p;
             }
             f.x = cell.x; f.y = cell.y;
-            // the node found has side 2^t, t + 1 in the exponent field: its planes are ((p >> t) + dpos) << t
-            const float side = __uint_as_float(e + 0x3f000000u), inv_side = __uint_as_float(0x40000000u - e);
-            f.plane.x = (__builtin_floorf(pf.x * inv_side) + dposf.x) * side;
-            f.plane.y = (__builtin_floorf(pf.y * inv_side) + dposf.y) * side;
-            f.plane.z = (__builtin_floorf(pf.z * inv_side) + dposf.z) * side;
+            f.plane = planes(p, dpos, tp1 - 1u);
         }
         w.node = node; w.cs = cs; w.anode = anode; w.acs = acs; w.last = last;
         return status;
@@ -195,74 +201,100 @@ struct TravT {
     // its negation with a v_cmp of its own (four per step, 4.4 ticks each) and branches around every masked add. Here:
     // two v_cmp into scalar mask pairs, two v_cndmask on them, three adds under exec = the axis' lanes (an add with no
     // lane enabled costs its issue slot and nothing else). gfx950 needs two wait states between a VALU instruction that
-    // writes a scalar register and a VALU instruction that reads it as a mask (s_nop 1); scalar instructions interlock.
-    struct Axis { bool x, yz; };   // exit axis: x ? 0 : (yz ? 1 : 2)
-    static VRT_DEV Axis dda_step(F3 &rp, F3 dir, F3 inv, F3 push, F3 plane) {
-        const float tx = (plane.x - rp.x) * inv.x;
+    // writes a scalar register and a VALU instruction that reads it as a mask: tx's subtraction and product fill the first
+    // gap, an s_nop 1 the second; scalar instructions interlock. The exec juggling takes five scalar instructions and no
+    // register for the saved mask: y's and z's lanes are exec & ~mx split by myz, and mx | (exec & ~mx) restores exec.
+    //
+    // The exit axis is not returned as lane masks: carried out of a loop whose lanes leave at different steps, a lane
+    // mask costs the loop six scalar instructions per step to merge. The step returns the three floats the selections
+    // were made from, which a lane's registers keep after it leaves, and axis_of() reads the axis off them once.
+    struct Step { float t, m, tz; };   // t = tStep, m = min(ty, tz) as selected, tz
+    static VRT_DEV Step dda_step(F3 &rp, I3 &mp, F3 dir, F3 inv, F3 push, F3 plane) {
         const float ty = (plane.y - rp.y) * inv.y;
         const float tz = (plane.z - rp.z) * inv.z;
         uint64_t mx, myz;
-        float t;
+        float tx, m, t;
         asm("v_cmp_lt_f32_e64 %[myz], %[ty], %[tz]\n\t"
+            "v_sub_f32_e32 %[tx], %[plx], %[rpx]\n\t"           // tx = (plane.x - rp.x) * inv.x
+            "v_mul_f32_e32 %[tx], %[ivx], %[tx]\n\t"
+            "v_cndmask_b32_e64 %[m], %[tz], %[ty], %[myz]\n\t"   // m = ty < tz ? ty : tz
+            "v_cmp_lt_f32_e64 %[mx], %[tx], %[m]\n\t"
             "s_nop 1\n\t"
-            "v_cndmask_b32_e64 %[t], %[tz], %[ty], %[myz]\n\t"     // m = ty < tz ? ty : tz
-            "v_cmp_lt_f32_e64 %[mx], %[tx], %[t]\n\t"
-            "s_nop 1\n\t"
-            "v_cndmask_b32_e64 %[t], %[t], %[tx], %[mx]"             // t = tx < m ? tx : m
-            : [t] "=&v"(t), [mx] "=&s"(mx), [myz] "=&s"(myz)
-            : [tx] "v"(tx), [ty] "v"(ty), [tz] "v"(tz));
+            "v_cndmask_b32_e64 %[t], %[m], %[tx], %[mx]"           // t = tx < m ? tx : m
+            : [t] "=&v"(t), [m] "=&v"(m), [tx] "=&v"(tx), [mx] "=&s"(mx), [myz] "=&s"(myz)
+            : [ty] "v"(ty), [tz] "v"(tz), [plx] "v"(plane.x), [rpx] "v"(rp.x), [ivx] "v"(inv.x));
         float rx = rp.x + dir.x * t, ry = rp.y + dir.y * t, rz = rp.z + dir.z * t;
-        uint64_t save, rest;
-        asm volatile("s_mov_b64 %[save], exec\n\t"
-                     "s_mov_b64 exec, %[mx]\n\t"                    // a v_cmp result holds no lane that is not enabled
+        uint64_t rest;
+        int fx, fy, fz;
+        asm volatile("s_andn2_b64 %[rest], exec, %[mx]\n\t"        // a v_cmp result holds no lane that is not enabled
+                     "s_mov_b64 exec, %[mx]\n\t"
                      "v_add_f32_e32 %[rx], %[px], %[rx]\n\t"
-                     "s_andn2_b64 %[rest], %[save], %[mx]\n\t"
                      "s_and_b64 exec, %[rest], %[myz]\n\t"
                      "v_add_f32_e32 %[ry], %[py], %[ry]\n\t"
                      "s_andn2_b64 exec, %[rest], %[myz]\n\t"
                      "v_add_f32_e32 %[rz], %[pz], %[rz]\n\t"
-                     "s_mov_b64 exec, %[save]"
-                     : [rx] "+v"(rx), [ry] "+v"(ry), [rz] "+v"(rz), [save] "=&s"(save), [rest] "=&s"(rest)
+                     "s_or_b64 exec, %[rest], %[mx]\n\t"
+                     "v_cvt_flr_i32_f32 %[fx], %[rx]\n\t"              // floor_i() of the new position, in the same
+                     "v_cvt_flr_i32_f32 %[fy], %[ry]\n\t"              // statement: one boundary fewer
+                     "v_cvt_flr_i32_f32 %[fz], %[rz]"
+                     : [rx] "+v"(rx), [ry] "+v"(ry), [rz] "+v"(rz), [rest] "=&s"(rest), [fx] "=&v"(fx), [fy] "=&v"(fy),
+                       [fz] "=&v"(fz)
                      : [mx] "s"(mx), [myz] "s"(myz), [px] "v"(push.x), [py] "v"(push.y), [pz] "v"(push.z)
                      : "scc");
         rp.x = rx; rp.y = ry; rp.z = rz;
-        // the masks as per-lane conditions again: no instruction, the compiler keeps such conditions as lane masks
-        return Axis{__builtin_amdgcn_inverse_ballot_w64(mx), __builtin_amdgcn_inverse_ballot_w64(myz)};
+        mp = I3{fx, fy, fz};
+        return Step{t, m, tz};
+    }
+    // The exit axis of a step (comp:292): x when tx < m, else y when ty < tz, else z. A v_cndmask copies the bits of the
+    // operand it selects, and a strict "<" between two floats that holds makes them differ in value, hence in bits; so
+    // tx < m exactly when t and m differ in bits, and ty < tz exactly when m and tz do (NaN included: "<" fails, the
+    // bits are equal).
+    static VRT_DEV int axis_of(Step s) {
+        return __float_as_uint(s.t) != __float_as_uint(s.m) ? 0 : (__float_as_uint(s.m) != __float_as_uint(s.tz) ? 1 : 2);
     }
 
-    static VRT_DEV void floor_both(F3 rp, F3 &pf, I3 &p) {
-        pf = F3{__builtin_floorf(rp.x), __builtin_floorf(rp.y), __builtin_floorf(rp.z)};
-        p = I3{(int)pf.x, (int)pf.y, (int)pf.z};   // v_cvt_i32_f32 of an integer-valued float: saturates, NaN -> 0, like v_cvt_flr_i32_f32
+    // floor() of a ray position as integers in one v_cvt_flr_i32_f32 per axis: floor, then a saturating conversion -- the
+    // same integers as v_floor_f32 + v_cvt_i32_f32 for every input but NaN (which that pair turns into 0; measured,
+    // tests/test_gpu_march_step.py). A position is never NaN: origins are finite, directions finite with a length near 1
+    // (or the light's, used as given), t is finite (|plane - rp| is bounded in the world and a reciprocal by 1e20), and a
+    // position that leaves the world ends the ray at that lookup.
+    static VRT_DEV I3 floor_i(F3 rp) {
+        int x, y, z;
+        asm("v_cvt_flr_i32_f32 %0, %3\n\t"
+            "v_cvt_flr_i32_f32 %1, %4\n\t"
+            "v_cvt_flr_i32_f32 %2, %5"
+            : "=&v"(x), "=&v"(y), "=v"(z) : "v"(rp.x), "v"(rp.y), "v"(rp.z));
+        return I3{x, y, z};
     }
 
     // The march loop. IOF85: every lane's starting medium is refraction byte 85 (1.0: the eye in empty space), so the
     // medium a step leaves is the mapped byte of the cell before (see to_cell4()); otherwise empty space counts as
     // the ray's own starting medium on the leaving side (comp:318-326).
     template <bool IOF85>
-    static VRT_DEV bool march_loop(const KArgs &a, const Ctx &c, F3 &rp, F3 dir, F3 inv, F3 push, I3 dpos, F3 dposf, Walk &w, Found &cur,
+    static VRT_DEV bool march_loop(const KArgs &a, const Ctx &c, F3 &rp, F3 dir, F3 inv, F3 push, I3 dpos, Walk &w, Found &cur,
                                    uint32_t iof_byte, int &axis, uint32_t &px, uint32_t &py, I3 &mp, bool forward, int *iters = nullptr) {
-        Axis ax{false, false};
-        F3 pf;
+        Step st;
         int i = 0, status = kGo;
         uint32_t prev_m = 0u;
         bool go;
         do {
-            ax = dda_step(rp, dir, inv, push, cur.plane);
-            floor_both(rp, pf, mp);
+            st = dda_step(rp, mp, dir, inv, push, cur.plane);
             const uint32_t cur_m = cur.y & 0xffu;
             if constexpr (IOF85) prev_m = cur_m;
             else prev_m = ((cur.x >> 24) == 0u || (cur.y & (1u << 29)) != 0u) ? iof_byte : cur_m;
             // a ray that leaves the world misses (comp:307-310) and find() leaves `cur` alone then: nothing reads its voxel
             // words afterwards, so the previous voxel is updated unconditionally rather than through selects
             px = cur.x; py = cur.y;
-            status = find(a, c, mp, pf, dpos, dposf, w, cur, forward, prev_m);
+            status = find(a, c, mp, dpos, w, cur, forward, prev_m);
             asm volatile("" : "+v"(status));
             bool hit = (cur.y & 0xffu) != prev_m;
             if constexpr (!IOF85) hit = hit && status != kOutside;
             ++i;
             go = status != kOutside && !hit && i < 1024;
         } while (go);
-        axis = ax.x ? 0 : (ax.yz ? 1 : 2);   // two lane masks merged per iteration by scalar instructions: off the vector port
+        // the last step's floats as the lane left them: vector registers, so nothing is merged per step
+        asm volatile("" : "+v"(st.t), "+v"(st.m), "+v"(st.tz));
+        axis = axis_of(st);
         if (iters) *iters = i;
         // the hit flag from the registers the lane left the loop with (IOF85: outside the world `cur` is unchanged, so the
         // bytes are equal)
@@ -293,13 +325,10 @@ struct TravT {
             inv.z = (__builtin_fabsf(dir.z) < 1e-8f) ? 1e20f : 1.0f / dir.z;
         }
         const I3 dpos{dir.x > 0.0f ? 1 : 0, dir.y > 0.0f ? 1 : 0, dir.z > 0.0f ? 1 : 0};
-        const F3 dposf{dir.x > 0.0f ? 1.0f : 0.0f, dir.y > 0.0f ? 1.0f : 0.0f, dir.z > 0.0f ? 1.0f : 0.0f};
         const F3 sd{sign_c(dir.x), sign_c(dir.y), sign_c(dir.z)};
         const F3 push{sd.x * 0.0001f, sd.y * 0.0001f, sd.z * 0.0001f};  // comp:300-304
         Walk w;
-        F3 pf;
-        I3 mp;
-        floor_both(rp, pf, mp);
+        I3 mp = floor_i(rp);
         Found cur;
         cur.x = 0u; cur.y = 85u | (1u << 23); cur.plane = F3{0.0f, 0.0f, 0.0f};   // empty space
         if (eye && eye->first_valid) {  // wave-uniform: the first lookup was made by the host
@@ -308,14 +337,12 @@ struct TravT {
             const uint32_t t = eye->first_w1 >> 24;
             cur.x = eye->first_w0;
             cur.y = cell4_y(eye->first_w0, eye->first_w1 & 0x00ffffffu, t + 1u);
-            const float side = __uint_as_float((127u + t) << 23), inv_side = __uint_as_float((127u - t) << 23);
-            cur.plane = F3{(__builtin_floorf(pf.x * inv_side) + dposf.x) * side, (__builtin_floorf(pf.y * inv_side) + dposf.y) * side,
-                           (__builtin_floorf(pf.z * inv_side) + dposf.z) * side};
+            cur.plane = planes(mp, dpos, t);
         } else {
             reset(w);
             // an eye outside the world: find() has noted that point as the walk's reference, and the next point -- still
             // outside, a few units on -- would pass for a point of wide root 0: no current node again
-            if (find(a, c, mp, pf, dpos, dposf, w, cur, false) == kOutside) { cur.plane = world_planes(a, dpos); reset(w); }
+            if (find(a, c, mp, dpos, w, cur, false) == kOutside) { cur.plane = world_planes(a, dpos); reset(w); }
         }
         int axis = 2;
         uint32_t px = 0u, py = 85u | (1u << 23);
@@ -324,11 +351,11 @@ struct TravT {
         // path tracer hold both and spill 16 registers at its five waves per SIMD
         const bool forward = forward_only(dir);
 #ifdef VRT_EXP_STATS
-        if constexpr (EYE85) hit = march_loop<true>(a, c, rp, dir, inv, push, dpos, dposf, w, cur, iof_byte, axis, px, py, mp, forward, &h.iters);
-        else hit = march_loop<false>(a, c, rp, dir, inv, push, dpos, dposf, w, cur, iof_byte, axis, px, py, mp, forward, &h.iters);
+        if constexpr (EYE85) hit = march_loop<true>(a, c, rp, dir, inv, push, dpos, w, cur, iof_byte, axis, px, py, mp, forward, &h.iters);
+        else hit = march_loop<false>(a, c, rp, dir, inv, push, dpos, w, cur, iof_byte, axis, px, py, mp, forward, &h.iters);
 #else
-        if constexpr (EYE85) hit = march_loop<true>(a, c, rp, dir, inv, push, dpos, dposf, w, cur, iof_byte, axis, px, py, mp, forward);
-        else hit = march_loop<false>(a, c, rp, dir, inv, push, dpos, dposf, w, cur, iof_byte, axis, px, py, mp, forward);
+        if constexpr (EYE85) hit = march_loop<true>(a, c, rp, dir, inv, push, dpos, w, cur, iof_byte, axis, px, py, mp, forward);
+        else hit = march_loop<false>(a, c, rp, dir, inv, push, dpos, w, cur, iof_byte, axis, px, py, mp, forward);
 #endif
         const float n = -comp(sd, axis);
         h.axis = axis; h.n = n;
@@ -343,11 +370,9 @@ struct TravT {
     static constexpr bool kHostLight = true;
     static VRT_DEV int shadow(const KArgs &a, const Ctx &c, F3 origin, const LightSetup &ls, const Hit &h) {
         F3 rp = origin;
-        const F3 ld = ls.dir, inv = ls.inv, push = ls.push, dposf = ls.dposf;
+        const F3 ld = ls.dir, inv = ls.inv, push = ls.push;
         const I3 dpos = ls.dpos;
-        F3 pf;
-        I3 mp;
-        floor_both(rp, pf, mp);
+        I3 mp = floor_i(rp);
         Walk w;  // resume where the primary ray stopped: the origin is 2e-3 off its hit point
         w.node = h.r_node; w.cs = (uint32_t)h.r_s; w.anode = h.r_anode; w.acs = (uint32_t)h.r_as; w.last = h.r_last;
         Found v;
@@ -355,18 +380,17 @@ struct TravT {
         const bool forward = forward_only(ld);
         // the first lookup never takes the root0_only shortcut: the walk it resumes is the primary ray's, and "has been inside
         // wide root 0" must be this ray's own history (an origin 2e-3 outside the cube's face starts outside)
-        if (find(a, c, mp, pf, dpos, dposf, w, v, false) == kOutside) { v.plane = world_planes(a, dpos); reset(w); }   // as in march()
+        if (find(a, c, mp, dpos, w, v, false) == kOutside) { v.plane = world_planes(a, dpos); reset(w); }   // as in march()
         int lit = 1, i = 0;
         bool go;
         do {
             // occluder: alpha > 0.1 <=> alpha byte >= 26; illumination byte == 0 (comp:355)
             const bool occluder = (v.x >> 24) >= 26u && (v.y & 0xff00u) == 0u;
             lit = occluder ? 0 : lit;
-            (void)dda_step(rp, ld, inv, push, v.plane);
-            floor_both(rp, pf, mp);
+            (void)dda_step(rp, mp, ld, inv, push, v.plane);
             ++i;
             go = !occluder && i < 64;
-            if (go) go = find(a, c, mp, pf, dpos, dposf, w, v, forward) != kOutside;
+            if (go) go = find(a, c, mp, dpos, w, v, forward) != kOutside;
         } while (go);
         return lit;
     }

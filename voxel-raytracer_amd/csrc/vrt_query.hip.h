@@ -57,9 +57,7 @@ VRT_DEV void leaf_words(const v4::Found &f, uint32_t &w0, uint32_t &w1) {
 // up = 1 -- and the words of what it holds
 VRT_DEV I3 node_corner(const KArgs &a, const T::Ctx &c, I3 p, v4::Walk &w, int up, uint32_t &w0, uint32_t &w1) {
     v4::Found f;
-    const F3 pf{(float)p.x, (float)p.y, (float)p.z};
-    const float u = up ? 1.0f : 0.0f;
-    (void)T::find(a, c, p, pf, I3{up, up, up}, F3{u, u, u}, w, f, false);
+    (void)T::find(a, c, p, I3{up, up, up}, w, f, false);
     leaf_words(f, w0, w1);
     return I3{(int)f.plane.x, (int)f.plane.y, (int)f.plane.z};
 }
@@ -100,7 +98,6 @@ __global__ void __launch_bounds__(64) cast_rays_kernel(KArgs a, RayArgs q) {
     inv.y = (__builtin_fabsf(rd.y) < 1e-8f) ? 1e20f : 1.0f / rd.y;
     inv.z = (__builtin_fabsf(rd.z) < 1e-8f) ? 1e20f : 1.0f / rd.z;
     const I3 dpos{rd.x > 0.0f ? 1 : 0, rd.y > 0.0f ? 1 : 0, rd.z > 0.0f ? 1 : 0};
-    const F3 dposf{rd.x > 0.0f ? 1.0f : 0.0f, rd.y > 0.0f ? 1.0f : 0.0f, rd.z > 0.0f ? 1.0f : 0.0f};
     T::Ctx c;
     c.root = a.nodes[0];
     v4::Walk w;
@@ -119,8 +116,7 @@ __global__ void __launch_bounds__(64) cast_rays_kernel(KArgs a, RayArgs q) {
             // _octree_find_leaf returns NULL without writing the bounds: the caller's worldMin / worldMax stand
             plane = F3{dpos.x ? q.box_hi[0] : q.box_lo[0], dpos.y ? q.box_hi[1] : q.box_lo[1], dpos.z ? q.box_hi[2] : q.box_lo[2]};
         } else {
-            const F3 pf{(float)mp.x, (float)mp.y, (float)mp.z};
-            if (T::find(a, c, mp, pf, dpos, dposf, w, f, false) == v4::kOutside) T::reset(w);   // not reached: mp is in the world
+            if (T::find(a, c, mp, dpos, w, f, false) == v4::kOutside) T::reset(w);   // not reached: mp is in the world
             leaf_words(f, w0, w1);
             if ((w0 | w1) != 0u) {   // a leaf: the hit test is has_voxel && coord.y > MIN_HEIGHT (:434)
                 uint32_t u0, u1;
