@@ -249,6 +249,32 @@ int vrt_accum_resolve_device(vrt_ctx *ctx, void *d_rgba8, void *d_id_dist, void 
  * Sample 0 is therefore the frame, and aperture 0 reproduces the lens-free accumulations byte for byte. */
 int vrt_set_lens(vrt_ctx *ctx, float aperture, float focus_distance);
 
+/* Adaptive accumulation: stop sampling pixels whose mean has converged. vrt_accum_begin_adaptive is vrt_accum_begin_ex (same
+ * modes, VRT_ACCUM_JITTER, the lens as context state) plus a stopping rule, which belongs to the accumulation. VRT_E_INVALID
+ * unless 2 <= min_samples <= max_samples <= 2^24 and tolerance <= 65535, or for what vrt_accum_begin_ex refuses.
+ *
+ * The rule. Pixel p holds n samples; for each, L_i = R_i + G_i + B_i (its three unorm8 bytes); S = sum L_i, Q = sum L_i^2.
+ * The pixel is active -- it takes the next round's sample -- iff
+ *     n < min_samples  ||  (n < max_samples  &&  256 * (n*Q - S^2) > tolerance^2 * n^2 * (n - 1))
+ * in exact integer arithmetic: sampling goes on while the standard error of the mean of L exceeds tolerance / 16 units of L.
+ * tolerance 0 stops a pixel once all its samples are identical, after at least min_samples.
+ *
+ * Rounds. vrt_accum_add(ctx, n, &total) runs n rounds: in round r (counted from the first round in the sums) every pixel
+ * active at the start of the round adds sample first + r, exactly the sample a plain accumulation of the same mode, flags and
+ * lens would add at that index. A stopped pixel never takes another sample, so pixels only drop out, and each pixel's fate
+ * depends on its own samples alone: 3 + 5 rounds equal 8 rounds equal 8 x 1 round, and min_samples == max_samples == N is the
+ * plain accumulation of N samples byte for byte. `total` and the 2^24 cap count rounds. The restart rule is unchanged; a
+ * restart makes every pixel active again with zero samples.
+ *
+ * vrt_accum_resolve / _resolve_device give each pixel (sum + n_p / 2) / n_p with its own count n_p; the id_dist image and the
+ * display pass are as above.
+ * vrt_accum_counts: synchronous; writes the per-pixel counts [H][W] to out_counts (may be NULL) and returns the number of active
+ * pixels (>= 0), or VRT_E_STATE before any begin or on a non-adaptive accumulation. Before the first round every pixel is active
+ * with zero samples; a restart that the next add will make is not yet seen. */
+int vrt_accum_begin_adaptive(vrt_ctx *ctx, int width, int height, int mode, uint32_t first_sample, uint32_t flags,
+                             uint32_t min_samples, uint32_t max_samples, uint32_t tolerance);
+int vrt_accum_counts(vrt_ctx *ctx, uint32_t *out_counts);
+
 /* Column-major mat4 x2 + vec4, exactly the std140 Camera block (comp:17-21). */
 int vrt_set_camera(vrt_ctx *ctx, const float inv_projection[16], const float inv_view[16],
                    const float camera_pos[4]);

@@ -10,6 +10,13 @@ writes them to a file too.
     python3 tools/accum_rate.py --mode primary primary_shadow full --jitter --out profiles/accum_jitter_rate.jsonl
     python3 tools/accum_rate.py --mode primary primary_shadow full --jitter --lens 0.1 40 --lens 10 40 --out profiles/accum_lens_rate.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -o a -- python3 tools/accum_rate.py --reps 3   (kernel times)
+
+--adaptive MIN MAX TOL measures adaptive accumulations (vrt_accum_begin_adaptive) instead: on each scene, primary + jitter, full,
+and full + jitter + a thin lens (--adaptive-lens, default 0.1 40), `--rounds` adds of one round each, and for every add its wall
+time, the fraction of pixels still active after it (vrt_accum_counts) and its ratio to the add of the same round of the plain
+accumulation (the median of --reps runs of each).
+
+    python3 tools/accum_rate.py --adaptive 4 64 24 --out profiles/accum_adaptive_rate.jsonl
 """
 import argparse
 import json
@@ -40,8 +47,13 @@ def main():
     ap.add_argument("--jitter", action="store_true", help="jittered samples (anti-aliasing)")
     ap.add_argument("--lens", nargs=2, type=float, action="append", default=[], metavar=("APERTURE", "FOCUS"),
                     help="also with this thin lens (repeatable)")
+    ap.add_argument("--adaptive", nargs=3, type=int, metavar=("MIN", "MAX", "TOL"), help="adaptive accumulations (see above)")
+    ap.add_argument("--adaptive-lens", nargs=2, type=float, default=(0.1, 40.0), metavar=("APERTURE", "FOCUS"))
+    ap.add_argument("--rounds", type=int, default=32)
     args = ap.parse_args()
     V = vrt_import.vrt()
+    if args.adaptive:
+        return adaptive_main(V, args)
     from conftest import MAPS, room_world
     W, H = 1920, 1080
     ctx = V.Context(0)
@@ -94,6 +106,70 @@ def main():
             ctx.set_lens(0.0, 1.0)
     ctx.device_free(d_rgba)
     ctx.device_free(d_id)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+def _scenes(V, ctx, W, H):
+    from conftest import MAPS, room_world
+    for name, (m, pos, yaw, pitch) in SCENES.items():
+        if m == "room":
+            w = room_world(V)
+        else:
+            w = V.World()
+            assert w.load_vox(os.path.join(MAPS, m + ".vox"))
+        tex, dim = w.flatten()
+        w.close()
+        ctx.upload_octree(tex, dim)
+        ip, iv, cp, _ = V.camera_block(pos, yaw, pitch, W, H)
+        ctx.set_camera(ip, iv, cp)
+        ctx.set_params(ctx.default_params())
+        yield name, tex
+
+
+def _round_times(ctx, W, H, mode, jitter, adaptive, rounds):
+    """one accumulation, one round per add: [(ms, active fraction or None)] per add"""
+    ctx.accum_begin(W, H, 0, mode=mode, jitter=jitter, adaptive=adaptive)
+    ctx.synchronize()
+    out = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        ctx.accum_add(1)
+        ctx.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        out.append((ms, ctx.accum_counts()[1] / (W * H) if adaptive else None))
+    return out
+
+
+def adaptive_main(V, args):
+    W, H = 1920, 1080
+    rule = tuple(args.adaptive)
+    ctx = V.Context(0)
+    configs = (("primary", True, None), ("full", False, None), ("full", True, tuple(args.adaptive_lens)))
+    rows = []
+    for name, tex in _scenes(V, ctx, W, H):
+        opaque = V.tree_is_opaque(tex)
+        for mname, jitter, lens in configs:
+            mode = V.MODES[mname]
+            ctx.set_lens(*(lens or (0.0, 1.0)))
+            _round_times(ctx, W, H, mode, jitter, rule, 2)          # code objects, buffers
+            _round_times(ctx, W, H, mode, jitter, None, 2)
+            reps = max(1, args.reps)
+            plain = np.median([[t for t, _ in _round_times(ctx, W, H, mode, jitter, None, args.rounds)] for _ in range(reps)], axis=0)
+            runs = [_round_times(ctx, W, H, mode, jitter, rule, args.rounds) for _ in range(reps)]
+            adapt = np.median([[t for t, _ in r] for r in runs], axis=0)
+            for r in range(args.rounds):
+                row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "mode": mname,
+                       "jitter": jitter, "aperture": lens[0] if lens else 0.0, "focus": lens[1] if lens else 1.0,
+                       "min": rule[0], "max": rule[1], "tol": rule[2], "round": r + 1, "add_ms": round(float(adapt[r]), 4),
+                       "active_after": round(runs[0][r][1], 5), "plain_add_ms": round(float(plain[r]), 4),
+                       "ratio": round(float(adapt[r] / plain[r]), 3), "reps": reps}
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+            ctx.set_lens(0.0, 1.0)
     ctx.close()
     if args.out:
         with open(args.out, "w") as f:

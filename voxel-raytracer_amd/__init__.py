@@ -252,6 +252,9 @@ def hip_lib():
         L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
         L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
         L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, C.c_uint32]
+        L.vrt_accum_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -515,6 +518,31 @@ def root0_choice(texels, eye, world_min=(-1023, -1023, -1023), world_max=(1024, 
         raise VrtError(f"vrt_test_root0 failed ({r})")
     return bool(out[0]), int(out[1]), (int(out[2]), int(out[3]), int(out[4])), int(out[5])
 
+def adaptive_rule(n, s, q, min_samples, max_samples, tolerance):
+    """Host probe (vrt_test_adaptive_rule): is a pixel with n samples, S = s and Q = q active under the adaptive accumulation's
+    stopping rule (include/vrt.h vrt_accum_begin_adaptive)? The function the kernels evaluate, compiled for the host."""
+    L = test_lib()
+    L.vrt_test_adaptive_rule.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+    return L.vrt_test_adaptive_rule(int(n), int(s), int(q), int(min_samples), int(max_samples), int(tolerance)) == 1
+
+
+def adaptive_rule_device(n, s, q, min_samples, max_samples, tolerance, device=0):
+    """Device probe (vrt_test_adaptive_rule_device): the same rule on the GPU for arrays of states -> bool array"""
+    L = test_lib()
+    L.vrt_test_adaptive_rule_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_int]
+    n = np.ascontiguousarray(n, np.uint32)
+    s = np.ascontiguousarray(s, np.uint64)
+    q = np.ascontiguousarray(q, np.uint64)
+    assert n.shape == s.shape == q.shape and n.ndim == 1
+    out = np.zeros(n.shape, np.uint32)
+    r = L.vrt_test_adaptive_rule_device(device, n.ctypes.data, s.ctypes.data, q.ctypes.data, int(min_samples), int(max_samples),
+                                        int(tolerance), out.ctypes.data, n.size)
+    if r != 0:
+        raise VrtError(f"vrt_test_adaptive_rule_device failed ({r})")
+    return out != 0
+
+
 def lens_choice(texels, cam_pos, inv_view, aperture, voxel_scale=1.0, world_min=(-1023, -1023, -1023),
                 world_max=(1024, 1024, 1024)):
     """Host-only (vrt_test_lens_select): which side of each one-eye shortcut an accumulation with a thin lens of this aperture
@@ -772,9 +800,11 @@ class Context:
         self._chk(L.vrt_find_voxels(self._h, n, c.ctypes.data if n else None, out.ctypes.data if n else None))
         return out[:, 0] != 0, out[:, 1:].copy()
 
-    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False):
+    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False, adaptive=None):
         """(Re)start the progressive accumulation of `mode` at sample index `first_sample` (vrt_accum_begin_ex); jitter=True
-        moves each sample's ray inside the pixel (VRT_ACCUM_JITTER: anti-aliased frames)."""
+        moves each sample's ray inside the pixel (VRT_ACCUM_JITTER: anti-aliased frames). adaptive=(min_samples, max_samples,
+        tolerance) makes it adaptive (vrt_accum_begin_adaptive): accum_add then adds rounds, in which only the pixels the
+        stopping rule keeps active take a sample; accum_counts() reports them."""
         if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or mode not in (MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL):
             raise ValueError(f"mode: expected MODE_PRIMARY, MODE_PRIMARY_SHADOW or MODE_FULL, got {mode!r}")
         if not isinstance(jitter, (bool, np.bool_)) and not (isinstance(jitter, (int, np.integer)) and jitter in (0, 1)):
@@ -786,9 +816,34 @@ class Context:
             raise ValueError(f"width * height: at most 2^30 pixels, got {width * height}")
         if isinstance(first_sample, bool) or not isinstance(first_sample, (int, np.integer)) or not 0 <= first_sample < 1 << 32:
             raise ValueError(f"first_sample: expected an integer in [0, 2^32), got {first_sample!r}")
-        self._chk(self._L.vrt_accum_begin_ex(self._h, int(width), int(height), int(mode), int(first_sample),
-                                             ACCUM_JITTER if jitter else 0))
+        if adaptive is not None:
+            if not isinstance(adaptive, (tuple, list)) or len(adaptive) != 3:
+                raise ValueError(f"adaptive: expected None or (min_samples, max_samples, tolerance), got {adaptive!r}")
+            for name, v in zip(("min_samples", "max_samples", "tolerance"), adaptive):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                    raise ValueError(f"adaptive {name}: expected an integer, got {v!r}")
+            lo, hi, tol = (int(v) for v in adaptive)
+            if not 2 <= lo <= hi <= 1 << 24:
+                raise ValueError(f"adaptive: need 2 <= min_samples <= max_samples <= 2^24, got {adaptive!r}")
+            if not 0 <= tol <= 65535:
+                raise ValueError(f"adaptive tolerance: expected an integer in [0, 65535], got {tol!r}")
+            self._chk(self._L.vrt_accum_begin_adaptive(self._h, int(width), int(height), int(mode), int(first_sample),
+                                                       ACCUM_JITTER if jitter else 0, lo, hi, tol))
+        else:
+            self._chk(self._L.vrt_accum_begin_ex(self._h, int(width), int(height), int(mode), int(first_sample),
+                                                 ACCUM_JITTER if jitter else 0))
         self._accum_shape = (int(height), int(width))
+
+    def accum_counts(self):
+        """An adaptive accumulation's per-pixel sample counts and how many pixels are still active (vrt_accum_counts)
+        -> (counts uint32[H, W], active int)."""
+        shape = getattr(self, "_accum_shape", None)
+        if shape is None:
+            raise VrtError("accum_counts: no accumulation (call accum_begin first)")
+        counts = np.zeros(shape, np.uint32)
+        r = self._L.vrt_accum_counts(self._h, counts.ctypes.data)
+        self._chk(min(r, 0))
+        return counts, int(r)
 
     def set_lens(self, aperture, focus_distance):
         """Thin lens for the progressive accumulation (vrt_set_lens): lens radius `aperture` (0: a pinhole) and the distance of

@@ -6,6 +6,7 @@
 //   * host-only views of the layouts the uploader builds (record array, wide cells), of the edit patches, of the per-projection
 //     ray tables and of the dispatcher's "world is empty outside wide root 0" analysis: the same sources (vrt_layout.cpp,
 //     vrt_raygen.cpp) linked a second time.
+//   * the adaptive accumulation's stopping rule (vrt_accum.h adaptive_active), on the host and on the device.
 // libvrt_hip.so exports none of this (tests/test_abi.py checks that).
 #include <hip/hip_runtime.h>
 
@@ -15,12 +16,21 @@
 
 #include "../../../include/vrt.h"
 #include "../vrt_common.hip.h"
+#include "../vrt_accum.h"
 #include "../vrt_full.hip.h"
 #include "../vrt_kernels_v4.hip.h"
 #include "../vrt_layout.h"
 #include "../vrt_sched.hip.h"
 
 namespace vrt {
+// the adaptive stopping rule on the device: out[i] = adaptive_active(n[i], s[i], q[i], min, max, tol)
+__global__ void adaptive_probe_kernel(const uint32_t *n, const uint64_t *s, const uint64_t *q, uint32_t min, uint32_t max,
+                                      uint32_t tol, uint32_t *out, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    out[i] = accum::adaptive_active(n[i], s[i], q[i], min, max, tol) ? 1u : 0u;
+}
+
 // exactness probe for the arithmetic contract: out[i] = op(x[i], y[i])
 __global__ void math_probe_kernel(int op, const float *x, const float *y, float *out, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -365,6 +375,37 @@ int vrt_test_tile_order(int device, const uint32_t *tile_ticks, uint32_t n_group
     VRT_HIP(c, hipMemcpy(split_out, d_order + n_groups, sizeof(uint32_t), hipMemcpyDeviceToHost));
     (void)hipFree(d_cost);
     (void)hipFree(d_order);
+    return VRT_OK;
+}
+
+// The adaptive accumulation's stopping rule (include/vrt.h vrt_accum_begin_adaptive) as the kernels evaluate it: 1 active, 0 not
+int vrt_test_adaptive_rule(uint32_t n, uint64_t s, uint64_t q, uint32_t min, uint32_t max, uint32_t tol) {
+    return vrt::accum::adaptive_active(n, s, q, min, max, tol) ? 1 : 0;
+}
+
+// The same on the device, for `count` states: host arrays, synchronous
+int vrt_test_adaptive_rule_device(int device, const uint32_t *n, const uint64_t *s, const uint64_t *q, uint32_t min, uint32_t max,
+                                  uint32_t tol, uint32_t *out, int count) {
+    if (!n || !s || !q || !out || count < 1 || count > (1 << 20)) return VRT_E_INVALID;
+    void *c = nullptr; (void)c;
+    VRT_HIP(c, hipSetDevice(device));
+    uint32_t *d_n = nullptr, *d_out = nullptr;
+    uint64_t *d_s = nullptr, *d_q = nullptr;
+    VRT_HIP(c, hipMalloc((void **)&d_n, (size_t)count * 4));
+    VRT_HIP(c, hipMalloc((void **)&d_out, (size_t)count * 4));
+    VRT_HIP(c, hipMalloc((void **)&d_s, (size_t)count * 8));
+    VRT_HIP(c, hipMalloc((void **)&d_q, (size_t)count * 8));
+    VRT_HIP(c, hipMemcpy(d_n, n, (size_t)count * 4, hipMemcpyHostToDevice));
+    VRT_HIP(c, hipMemcpy(d_s, s, (size_t)count * 8, hipMemcpyHostToDevice));
+    VRT_HIP(c, hipMemcpy(d_q, q, (size_t)count * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(vrt::adaptive_probe_kernel, dim3((count + 255) / 256), dim3(256), 0, 0, d_n, d_s, d_q, min, max, tol, d_out, count);
+    VRT_HIP(c, hipGetLastError());
+    VRT_HIP(c, hipDeviceSynchronize());
+    VRT_HIP(c, hipMemcpy(out, d_out, (size_t)count * 4, hipMemcpyDeviceToHost));
+    (void)hipFree(d_n);
+    (void)hipFree(d_out);
+    (void)hipFree(d_s);
+    (void)hipFree(d_q);
     return VRT_OK;
 }
 

@@ -5,6 +5,8 @@
 // as it chooses between the forms of a frame. A jittered accumulation, or one of VRT_MODE_PRIMARY / _SHADOW, first renders the
 // mode's ordinary frame once: its id_dist is the resolve's, and without jitter its bytes are every sample's. So does one with a
 // thin lens (vrt_set_lens, aperture > 0), whose samples the dispatcher enqueues as the lens kernels (vrt_lens.hip.h).
+// An adaptive accumulation (vrt_accum_begin_adaptive) adds rounds instead of samples: the same paths with the kernels' adaptive
+// forms, its per-pixel counts and Q beside the sums, the resolve by each pixel's count, and vrt_accum_counts.
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
@@ -53,27 +55,20 @@ int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_
     const size_t px = (size_t)ac.width * (size_t)ac.height;
     if (d_rgba) {
         vrt::accum::Resolve q{ac.d_sums, static_cast<uint32_t *>(d_rgba), ac.total, (uint32_t)px};
-        VRT_HIP(c, vrt::launch::accum_resolve(q, s));
+        VRT_HIP(c, ac.adaptive ? vrt::launch::adaptive_resolve(q, s) : vrt::launch::accum_resolve(q, s));
     }
     if (d_id) VRT_HIP(c, hipMemcpyAsync(d_id, ac.d_id, px * 8, hipMemcpyDeviceToDevice, s));
     if (d_shown) return vrt_denoise(c, ac.width, ac.height, d_rgba, ac.d_id, d_shown, s);
     return VRT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vrt_accum_begin(vrt_ctx *c, int width, int height, uint32_t first_sample) {
-    return vrt_accum_begin_ex(c, width, height, VRT_MODE_FULL, first_sample, 0u);
-}
-
-int vrt_accum_begin_ex(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, uint32_t flags) {
+// vrt_accum_begin_ex, and with rule = {min, max, tolerance} vrt_accum_begin_adaptive
+int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, uint32_t flags, const uint32_t *rule) {
     int r = check_frame(c, width, height);
     if (r) return r;
     if (mode != VRT_MODE_PRIMARY && mode != VRT_MODE_PRIMARY_SHADOW && mode != VRT_MODE_FULL)
-        return vrt_fail(c, VRT_E_INVALID, "vrt_accum_begin_ex: unknown mode");
-    if (flags & ~(uint32_t)VRT_ACCUM_JITTER) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_begin_ex: unknown flags");
+        return vrt_fail(c, VRT_E_INVALID, rule ? "vrt_accum_begin_adaptive: unknown mode" : "vrt_accum_begin_ex: unknown mode");
+    if (flags & ~(uint32_t)VRT_ACCUM_JITTER) return vrt_fail(c, VRT_E_INVALID, rule ? "vrt_accum_begin_adaptive: unknown flags" : "vrt_accum_begin_ex: unknown flags");
     VRT_HIP(c, hipSetDevice(c->device));
     Accum &ac = c->accum;
     const size_t px = (size_t)width * (size_t)height;
@@ -88,6 +83,14 @@ int vrt_accum_begin_ex(vrt_ctx *c, int width, int height, int mode, uint32_t fir
         ac.pixels = px;
         ac.seed_tiles = tiles;
     }
+    if (rule && (px > ac.sq_pixels || tiles > ac.tile_cap)) {   // the adaptive state: Q per pixel, the round's tile list
+        VRT_HIP(c, hipStreamSynchronize(c->stream));
+        ac.begun = false;
+        ac.sq_pixels = ac.tile_cap = 0;
+        if ((r = grow(c, ac.d_sq, px * 8)) || (r = grow(c, ac.d_tiles, (tiles + 2) * 4))) return r;
+        ac.sq_pixels = px;
+        ac.tile_cap = tiles;
+    }
     if (!ac.added) VRT_HIP(c, hipEventCreateWithFlags(&ac.added, hipEventDisableTiming));
     if (!ac.read) VRT_HIP(c, hipEventCreateWithFlags(&ac.read, hipEventDisableTiming));
     ac.begun = true;
@@ -99,7 +102,33 @@ int vrt_accum_begin_ex(vrt_ctx *c, int width, int height, int mode, uint32_t fir
     ac.total = 0;
     ac.pass1 = false;
     ac.frame = false;
+    ac.adaptive = rule != nullptr;
+    ac.min_samples = rule ? rule[0] : 0u;
+    ac.max_samples = rule ? rule[1] : 0u;
+    ac.tolerance = rule ? rule[2] : 0u;
     return VRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrt_accum_begin(vrt_ctx *c, int width, int height, uint32_t first_sample) {
+    return vrt_accum_begin_ex(c, width, height, VRT_MODE_FULL, first_sample, 0u);
+}
+
+int vrt_accum_begin_ex(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, uint32_t flags) {
+    return begin(c, width, height, mode, first_sample, flags, nullptr);
+}
+
+int vrt_accum_begin_adaptive(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, uint32_t flags,
+                             uint32_t min_samples, uint32_t max_samples, uint32_t tolerance) {
+    if (!c) return VRT_E_INVALID;
+    if (min_samples < 2u || min_samples > max_samples || max_samples > vrt::accum::kMaxSamples)
+        return vrt_fail(c, VRT_E_INVALID, "vrt_accum_begin_adaptive: need 2 <= min_samples <= max_samples <= 2^24");
+    if (tolerance > 65535u) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_begin_adaptive: tolerance must be at most 65535");
+    const uint32_t rule[3] = {min_samples, max_samples, tolerance};
+    return begin(c, width, height, mode, first_sample, flags, rule);
 }
 
 int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
@@ -113,11 +142,12 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
     // the restart rule: anything a sample depends on changed since the first sample in the sums -> the sums start again at `first`
     const bool restart = ac.total == 0 || !same_inputs(c, ac);
     const uint32_t base = restart ? 0u : ac.total;
-    if (n_samples > vrt::accum::kMaxSamples - base)
+    if (n_samples > vrt::accum::kMaxSamples - base)   // an adaptive accumulation: rounds
         return vrt_fail(c, VRT_E_INVALID, "vrt_accum_add: at most 2^24 samples per accumulation");
     VRT_HIP(c, hipSetDevice(c->device));
     if (restart) {
         VRT_HIP(c, hipMemsetAsync(ac.d_sums, 0, (size_t)ac.width * (size_t)ac.height * 16, c->stream));
+        if (ac.adaptive) VRT_HIP(c, hipMemsetAsync(ac.d_sq, 0, (size_t)ac.width * (size_t)ac.height * 8, c->stream));
         take_inputs(c, ac);
         ac.total = 0;
         ac.pass1 = false;
@@ -132,10 +162,19 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
     }
     if (r == VRT_OK && !jitter && !lens && ac.mode != VRT_MODE_FULL) {   // every sample is that frame
         const vrt::accum::Repeat q{ac.d_pass1, ac.d_sums, n_samples, (uint32_t)((size_t)ac.width * (size_t)ac.height)};
-        const hipError_t e = vrt::launch::accum_repeat(q, c->stream);
+        hipError_t e;
+        if (ac.adaptive) {   // each pixel's count goes to min(rounds, min_samples): no trace
+            vrt::accum::RepeatAdapt qa{};
+            static_cast<vrt::accum::Repeat &>(qa) = q;
+            qa.sq = ac.d_sq;
+            qa.min = ac.min_samples;
+            e = vrt::launch::accum_repeat(qa, c->stream);
+        } else {
+            e = vrt::launch::accum_repeat(q, c->stream);
+        }
         if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     } else if (r == VRT_OK) {
-        const AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1]};
+        const AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive};
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again
@@ -183,6 +222,30 @@ int vrt_accum_resolve_device(vrt_ctx *c, void *d_rgba8, void *d_id_dist, void *d
         VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
     }
     return VRT_OK;
+}
+
+int vrt_accum_counts(vrt_ctx *c, uint32_t *out_counts) {
+    if (!c) return VRT_E_INVALID;
+    Accum &ac = c->accum;
+    if (!ac.begun) return vrt_fail(c, VRT_E_STATE, "vrt_accum_counts: no accumulation (call vrt_accum_begin_adaptive first)");
+    if (!ac.adaptive) return vrt_fail(c, VRT_E_STATE, "vrt_accum_counts: the accumulation is not adaptive");
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if (ac.total == 0) {   // no round yet: every pixel active with zero samples
+        if (out_counts) std::memset(out_counts, 0, px * 4);
+        return (int)px;
+    }
+    VRT_HIP(c, hipSetDevice(c->device));
+    int r = ensure_scratch(c, px);
+    if (r) return r;
+    uint32_t *d_active = ac.d_tiles + ac.tile_cap + 1;
+    const vrt::accum::Counts q{ac.d_sums, ac.d_sq, static_cast<uint32_t *>(c->d_rgba), d_active, (uint32_t)px, ac.min_samples,
+                               ac.max_samples, ac.tolerance};
+    VRT_HIP(c, vrt::launch::adaptive_counts(q, c->stream));
+    uint32_t active = 0;
+    if (out_counts) VRT_HIP(c, hipMemcpyAsync(out_counts, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(&active, d_active, 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return (int)active;
 }
 
 }  // extern "C"

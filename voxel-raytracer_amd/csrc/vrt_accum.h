@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace vrt {
 namespace accum {
 
@@ -34,6 +36,65 @@ struct Repeat {
     uint32_t *sums;
     uint32_t n;
     uint32_t pixels;
+};
+
+// ---- adaptive accumulation (include/vrt.h vrt_accum_begin_adaptive) ----
+// Pixel state: the three sums, the pixel's own sample count n in the fourth word of the sums, and Q = sum of L^2 over its samples
+// (L = R + G + B of one sample's bytes; Q < 765^2 * 2^24 < 2^44) in a 64-bit word of its own.
+
+// The stopping rule, exact: a pixel with n samples, S = sum of L and Q = sum of L^2 takes the next round's sample iff
+//     n < min  ||  (n < max  &&  256 * (n * Q - S^2) > tol^2 * n^2 * (n - 1))
+// n * Q - S^2 >= 0 (Cauchy-Schwarz); every term is below 2^105, so 128-bit unsigned arithmetic is exact. Device and host (the
+// test library's probe) evaluate this one function.
+__host__ __device__ inline bool adaptive_active(uint32_t n, uint64_t s, uint64_t q, uint32_t min, uint32_t max, uint32_t tol) {
+    if (n < min) return true;
+    if (n >= max) return false;
+    typedef unsigned __int128 u128;
+    const u128 spread = (u128)n * q - (u128)s * s;
+    const u128 bound = (u128)((uint64_t)tol * tol) * ((u128)((uint64_t)n * n) * (n - 1u));
+    return (spread << 8) > bound;
+}
+
+// Samples a pixel holds after `rounds` more rounds whose every sample equals its earlier ones (its spread stays 0, so the rule
+// stops it at min, and at once where it already has min): the repeat path, and sky pixels of the opaque bounce.
+__host__ __device__ inline uint32_t adaptive_constant_count(uint32_t n, uint32_t rounds, uint32_t min) {
+    return n < min ? (rounds < min - n ? n + rounds : min) : n;
+}
+
+// Args of an adaptive launch: the kernels' template parameter ADAPT picks this type (ArgsOf), so the plain kernels keep Args.
+struct AdaptArgs : Args {
+    uint64_t *sq;                // Q per pixel, row-major
+    const uint32_t *tiles;       // one-sample kernels: the tiles compact_tiles_kernel listed for this round ...
+    const uint32_t *n_tiles;     // ... and how many
+    uint32_t min, max, tol;      // the rule
+};
+template <bool ADAPT>
+using ArgsOf = typename std::conditional<ADAPT, AdaptArgs, Args>::type;
+
+// Before each round of a one-sample kernel: the 8 x 8 tiles of the frame that hold an active pixel -> tiles[0 .. *n_tiles)
+struct Tiles {
+    const uint32_t *sums;
+    const uint64_t *sq;
+    uint32_t *tiles;
+    uint32_t *n_tiles;           // zeroed before the launch
+    int width, height;
+    uint32_t min, max, tol;
+};
+
+// vrt_accum_counts: the per-pixel counts -> out, the number of active pixels added to *n_active (zeroed before the launch)
+struct Counts {
+    const uint32_t *sums;
+    const uint64_t *sq;
+    uint32_t *out;
+    uint32_t *n_active;
+    uint32_t pixels;
+    uint32_t min, max, tol;
+};
+
+// The repeat path of an adaptive accumulation: each pixel's count goes to adaptive_constant_count(n, n_rounds, min)
+struct RepeatAdapt : Repeat {
+    uint64_t *sq;
+    uint32_t min;
 };
 
 // A thin lens (vrt_lens.hip.h, include/vrt.h vrt_set_lens), the fourth argument of the lens kernels.

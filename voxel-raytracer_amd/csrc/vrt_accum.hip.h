@@ -12,6 +12,11 @@
 //   full_accum_kernel     everything else: full::trace_pixel_full with the sample index, its bytes added to the sums. One
 //                         sample per launch; the traversal is the one trace_kernel<2> would take.
 // and one resolves: accum_resolve_kernel.
+//
+// Adaptive accumulations (include/vrt.h vrt_accum_begin_adaptive) take the same kernels with the template parameter ADAPT = true:
+// each lane reads its pixel's state (sums, its count n in the fourth word, Q) once, takes a round's sample only while
+// adaptive_active() holds, and writes the state back once. The sample-looped kernels leave the loop at the pixel's stop; the
+// one-sample kernels trace the tiles compact_tiles_kernel listed for the round and leave inactive lanes idle.
 #pragma once
 #include "vrt_accum.h"
 #include "vrt_full.hip.h"
@@ -32,13 +37,61 @@ VRT_DEV void store_sums(uint32_t *sums, size_t o, uint32_t r, uint32_t g, uint32
     *p = s;
 }
 
+// ---- adaptive state (ADAPT = true) ----
+struct PixelState { uint32_t r, g, b, n; uint64_t q; };
+
+VRT_DEV PixelState load_state(const AdaptArgs &q, size_t o) {
+    const uint4 s = reinterpret_cast<const uint4 *>(q.sums)[o];
+    return PixelState{s.x, s.y, s.z, s.w, q.sq[o]};
+}
+
+VRT_DEV void store_state(const AdaptArgs &q, size_t o, const PixelState &p) {
+    reinterpret_cast<uint4 *>(q.sums)[o] = make_uint4(p.r, p.g, p.b, p.n);
+    q.sq[o] = p.q;
+}
+
+VRT_DEV bool state_active(uint32_t min, uint32_t max, uint32_t tol, const PixelState &p) {
+    return adaptive_active(p.n, (uint64_t)p.r + p.g + p.b, p.q, min, max, tol);
+}
+
+VRT_DEV void add_sample(uint32_t rgba, PixelState &p) {
+    const uint32_t r = rgba & 0xffu, g = (rgba >> 8) & 0xffu, b = (rgba >> 16) & 0xffu, l = r + g + b;
+    p.r += r; p.g += g; p.b += b;
+    p.n += 1u;
+    p.q += (uint64_t)(l * l);
+}
+
+// adds `k` more samples equal to rgba (l * l * k < 2^44)
+VRT_DEV void add_repeat(uint32_t rgba, uint32_t k, PixelState &p) {
+    const uint32_t r = rgba & 0xffu, g = (rgba >> 8) & 0xffu, b = (rgba >> 16) & 0xffu, l = r + g + b;
+    p.r += r * k; p.g += g * k; p.b += b * k;
+    p.n += k;
+    p.q += (uint64_t)(l * l) * k;
+}
+
+// An adaptive one-sample launch: wave w of the grid (sized for every tile) takes tile q.tiles[w] while w < *q.n_tiles
+template <int BLOCK>
+VRT_DEV bool listed_pixel(const KArgs &a, const AdaptArgs &q, int &px, int &py) {
+    const uint32_t slot = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    if (slot >= *q.n_tiles) return false;
+    const int lane = threadIdx.x & 63;
+    const int tiles_x = (a.width + 7) / 8;
+    const int tile = (int)q.tiles[slot];
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    px = tx * 8 + (lane & 7);
+    py = ty * 8 + (lane >> 3);
+    return px < a.width && py < a.height;
+}
+
 // One wave per 8 x 8 tile of a whole frame (KArgs: row0 = 0, n_rows = height, compact = 0); a.defer_rec holds pass 1's seeds in
 // the tile-major planes of MODE 4 / 5 (vrt_common.hip.h kSeedPlanes). Built as MODE 5 is: 64 lanes, seven waves per SIMD, whose
 // 72 registers MODE 5's bounce fills. The loop's own state -- the seed, which MODE 5 lets die at the march, and the three sums --
 // waits in LDS (2 KiB per wave; 28 waves per CU hold 56 of its 160 KiB) instead of in spilled registers: the lane loads its seed
 // from memory once, and each sample reads it back from LDS and adds its bytes there.
-template <class TRAV>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const Args q) {
+// ADAPT: the loop stops at the pixel's stop (n and Q in registers); sky and emissive pixels, whose every sample is the same,
+// take adaptive_constant_count() at once.
+template <class TRAV, bool ADAPT = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
     __shared__ uint32_t s_seed[kSeedPlanes][64];
     __shared__ uint32_t s_sum[3][64];
     typename TRAV::Ctx tc_;
@@ -52,15 +105,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
     const uint32_t *sp = reinterpret_cast<const uint32_t *>(a.defer_rec) + ((size_t)tile * kSeedPlanes) * 64 + lane;
     const uint32_t word = sp[3 * 64];
     uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
     if (word & kSeedValid) {
 #pragma unroll
         for (uint32_t p = 0; p < kSeedPlanes; ++p) s_seed[p][lane] = sp[p * 64];
-        s_sum[0][lane] = 0u; s_sum[1][lane] = 0u; s_sum[2][lane] = 0u;
+        if constexpr (ADAPT) {
+            s_sum[0][lane] = st.r; s_sum[1][lane] = st.g; s_sum[2][lane] = st.b;
+        } else {
+            s_sum[0][lane] = 0u; s_sum[1][lane] = 0u; s_sum[2][lane] = 0u;
+        }
         // volatile: the seed is read back for every sample, not hoisted into registers across the loop
         volatile uint32_t *vs_seed = &s_seed[0][0];
         volatile uint32_t *vs_sum = &s_sum[0][0];
         // every sample is bounce_pixel's own arithmetic on the same seed: direct term, then the bounce's term, then unorm8
         for (uint32_t k = 0; k < q.n; ++k) {
+            if constexpr (ADAPT) {
+                st.r = vs_sum[0 * 64 + lane]; st.g = vs_sum[1 * 64 + lane]; st.b = vs_sum[2 * 64 + lane];
+                if (!state_active(q.min, q.max, q.tol, st)) break;
+            }
             Seed seed;
             seed.hp = F3{__uint_as_float(vs_seed[0 * 64 + lane]), __uint_as_float(vs_seed[1 * 64 + lane]), __uint_as_float(vs_seed[2 * 64 + lane])};
             seed.word = vs_seed[3 * 64 + lane];
@@ -77,35 +140,64 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
             vs_sum[0 * 64 + lane] = vs_sum[0 * 64 + lane] + (rgba & 0xffu);
             vs_sum[1 * 64 + lane] = vs_sum[1 * 64 + lane] + ((rgba >> 8) & 0xffu);
             vs_sum[2 * 64 + lane] = vs_sum[2 * 64 + lane] + ((rgba >> 16) & 0xffu);
+            if constexpr (ADAPT) {
+                const uint32_t l = (rgba & 0xffu) + ((rgba >> 8) & 0xffu) + ((rgba >> 16) & 0xffu);
+                st.n += 1u;
+                st.q += (uint64_t)(l * l);
+            }
         }
         r = vs_sum[0 * 64 + lane]; g = vs_sum[1 * 64 + lane]; b = vs_sum[2 * 64 + lane];
+    } else if constexpr (ADAPT) {
+        add_repeat(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], adaptive_constant_count(st.n, q.n, q.min) - st.n, st);
+        r = st.r; g = st.g; b = st.b;
     } else {   // sky, emissive surfaces: pass 1's bytes are every sample's
         add_bytes(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], r, g, b);
         r *= q.n; g *= q.n; b *= q.n;
     }
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) {
+        st.r = r; st.g = g; st.b = b;
+        store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    } else {
+        store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    }
 }
 
 // The general full path tracer with initRNG's sampleIndex = q.first (q.n == 1): trace_kernel<2>'s tiles, one pixel per lane.
-template <class TRAV, int BLOCK, int WPE>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const Args q) {
+// ADAPT: the waves take the round's listed tiles (listed_pixel()), and only active lanes trace.
+template <class TRAV, int BLOCK, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
-    const int lane = threadIdx.x & 63;
-    const int tiles_x = (a.width + 7) / 8;
-    const int tile = (int)blockIdx.x * (BLOCK / 64) + (int)(threadIdx.x >> 6);
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
-    if (px >= a.width || py >= a.height) return;
-    uint32_t rgba;
-    int2 idd;
-    LateOut lo;
-    full::trace_pixel_full<TRAV>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
-    const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
-    uint32_t r = 0u, g = 0u, b = 0u;
-    add_bytes(rgba, r, g, b);
-    store_sums(q.sums, o, r, g, b);
-    q.out_id[o] = idd;
+    if constexpr (ADAPT) {
+        int px, py;
+        if (!listed_pixel<BLOCK>(a, q, px, py)) return;
+        const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+        PixelState st = load_state(q, o);
+        if (!state_active(q.min, q.max, q.tol, st)) return;
+        uint32_t rgba;
+        int2 idd;
+        LateOut lo;
+        full::trace_pixel_full<TRAV>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
+        add_sample(rgba, st);
+        store_state(q, o, st);
+        q.out_id[o] = idd;
+    } else {
+        const int lane = threadIdx.x & 63;
+        const int tiles_x = (a.width + 7) / 8;
+        const int tile = (int)blockIdx.x * (BLOCK / 64) + (int)(threadIdx.x >> 6);
+        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+        if (px >= a.width || py >= a.height) return;
+        uint32_t rgba;
+        int2 idd;
+        LateOut lo;
+        full::trace_pixel_full<TRAV>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
+        const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
+        uint32_t r = 0u, g = 0u, b = 0u;
+        add_bytes(rgba, r, g, b);
+        store_sums(q.sums, o, r, g, b);
+        q.out_id[o] = idd;
+    }
 }
 
 __global__ __launch_bounds__(256) void accum_resolve_kernel(const Resolve q) {
@@ -114,6 +206,58 @@ __global__ __launch_bounds__(256) void accum_resolve_kernel(const Resolve q) {
     const uint4 s = reinterpret_cast<const uint4 *>(q.sums)[i];
     const uint32_t h = q.n >> 1;
     q.out_rgba[i] = ((s.x + h) / q.n) | (((s.y + h) / q.n) << 8) | (((s.z + h) / q.n) << 16) | (255u << 24);
+}
+
+// An adaptive accumulation's resolve: each pixel by its own count (the fourth word; >= 1 after the first round, as min >= 2)
+__global__ __launch_bounds__(256) void adaptive_resolve_kernel(const Resolve q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.pixels) return;
+    const uint4 s = reinterpret_cast<const uint4 *>(q.sums)[i];
+    const uint32_t n = s.w > 0u ? s.w : 1u, h = n >> 1;
+    q.out_rgba[i] = ((s.x + h) / n) | (((s.y + h) / n) << 8) | (((s.z + h) / n) << 16) | (255u << 24);
+}
+
+// One lane per tile: does it hold an active pixel? Active tiles of a wave are appended with one atomic (ballot, mbcnt offsets);
+// the list's order does not matter, as every pixel's samples depend on that pixel alone.
+__global__ __launch_bounds__(256) void compact_tiles_kernel(const Tiles t) {
+    const int tiles_x = (t.width + 7) / 8, n_tiles = tiles_x * ((t.height + 7) / 8);
+    const int tile = (int)(blockIdx.x * 256u + threadIdx.x);
+    bool any = false;
+    if (tile < n_tiles) {
+        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        const int x1 = min(tx * 8 + 8, t.width), y1 = min(ty * 8 + 8, t.height);
+        for (int y = ty * 8; y < y1 && !any; ++y)
+            for (int x = tx * 8; x < x1 && !any; ++x) {
+                const size_t o = (size_t)y * (size_t)t.width + (size_t)x;
+                const uint4 s = reinterpret_cast<const uint4 *>(t.sums)[o];
+                any = adaptive_active(s.w, (uint64_t)s.x + s.y + s.z, t.sq[o], t.min, t.max, t.tol);
+            }
+    }
+    const uint64_t mask = __ballot(any);
+    if (mask == 0u) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t base = 0u;
+    if (lane == (uint32_t)(__ffsll((unsigned long long)mask) - 1)) base = atomicAdd(t.n_tiles, (uint32_t)__popcll(mask));
+    base = __shfl(base, __ffsll((unsigned long long)mask) - 1);
+    if (any) t.tiles[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)tile;
+}
+
+// vrt_accum_counts: a grid-stride loop, one pixel per lane per step; each wave counts its active pixels with ballots and adds
+// them with one atomic at the end (one atomic per pixel wave serialised on the one word: 0.25 ms at 1080p)
+__global__ __launch_bounds__(256) void adaptive_counts_kernel(const Counts c) {
+    const uint32_t stride = gridDim.x * 256u;
+    uint32_t wave_active = 0u;
+    for (uint32_t base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < c.pixels; base += stride) {   // uniform per wave
+        const uint32_t i = base + (threadIdx.x & 63u);
+        bool act = false;
+        if (i < c.pixels) {
+            const uint4 s = reinterpret_cast<const uint4 *>(c.sums)[i];
+            c.out[i] = s.w;
+            act = adaptive_active(s.w, (uint64_t)s.x + s.y + s.z, c.sq[i], c.min, c.max, c.tol);
+        }
+        wave_active += (uint32_t)__popcll(__ballot(act));
+    }
+    if ((threadIdx.x & 63u) == 0u && wave_active != 0u) atomicAdd(c.n_active, wave_active);
 }
 
 }  // namespace accum

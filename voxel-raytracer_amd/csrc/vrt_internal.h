@@ -180,6 +180,12 @@ struct vrt_ctx {
         size_t pixels = 0, seed_tiles = 0;       // capacities
         uint32_t *d_resolved = nullptr;          // vrt_accum_resolve_device without d_rgba8 but with d_shown_rgba8
         hipEvent_t added = nullptr, read = nullptr;   // ordering against a caller's stream in vrt_accum_resolve_device
+        // vrt_accum_begin_adaptive: the stopping rule; per pixel, the count in the fourth word of d_sums and Q in d_sq
+        bool adaptive = false;
+        uint32_t min_samples = 0, max_samples = 0, tolerance = 0;
+        uint64_t *d_sq = nullptr;
+        uint32_t *d_tiles = nullptr;             // the round's tile list [tile_cap], then its count and vrt_accum_counts' count
+        size_t sq_pixels = 0, tile_cap = 0;      // capacities
     };
     Accum accum;
     const uint32_t *dbg_group_order = nullptr;  // vrt_set_tile_order: caller-owned buffers instead of the scheduler's
@@ -216,7 +222,8 @@ int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-bu
 // (vrt_accum.cpp; whole frame, the context's camera, d_rgba / d_id unused)
 // (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_jitter.hip.h)
 // (aperture > 0: the samples of a thin lens, vrt_set_lens; vrt_lens.hip.h)
-struct AccumStep { uint32_t first, n; bool jitter; float aperture = 0.0f, focus = 1.0f; };
+// (adaptive: n rounds of the context's adaptive accumulation, vrt_accum_begin_adaptive; the kernels' adaptive forms)
+struct AccumStep { uint32_t first, n; bool jitter; float aperture = 0.0f, focus = 1.0f; bool adaptive = false; };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
 SchedState *sched_state(vrt_ctx *c, hipStream_t s, int width, int n_rows, int row0, int row_stride, int tile_rows, int mode,

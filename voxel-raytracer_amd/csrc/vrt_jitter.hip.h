@@ -13,6 +13,8 @@
 //                          bounce_accum_kernel shares it.
 //   full_jitter_kernel     VRT_MODE_FULL, everything else: trace_pixel_full with the jittered ray, one sample per launch.
 //   repeat_kernel          a mode without jitter: every sample is the frame, so n samples add n times its bytes.
+// Every kernel but repeat_kernel has an adaptive form (template parameter ADAPT, vrt_accum.hip.h); repeat_adaptive_kernel is
+// the repeat's.
 #pragma once
 #include "vrt_accum.hip.h"
 
@@ -31,14 +33,18 @@ VRT_DEV bool jitter_pixel(const KArgs &a, int &px, int &py) {
 }
 
 // q.n samples q.first, q.first + 1, ... of MODE 0 or 1; whole frame (KArgs: row0 = 0, n_rows = height, compact = 0)
-template <int MODE, class TRAV, int BLOCK, int WPE>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_jitter_kernel(const KArgs a, const ViewSet vs, const Args q) {
+template <int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_jitter_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<BLOCK>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
     for (uint32_t k = 0; k < q.n; ++k) {
+        if constexpr (ADAPT)
+            if (!state_active(q.min, q.max, q.tol, st)) break;
         uint32_t rgba;
         int2 idd;
         LateOut lo;
@@ -52,20 +58,26 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         const View &vk = vs.v[0];
 #endif
         trace_pixel<MODE, TRAV, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k);
-        add_bytes(rgba, r, g, b);
+        if constexpr (ADAPT) add_sample(rgba, st);
+        else add_bytes(rgba, r, g, b);
     }
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    else store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
 }
 
 // MODE 6's two stages per sample, the seed in registers; 64 lanes, one 8 x 8 tile per wave
-template <class TRAV, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_jitter_kernel(const KArgs a, const ViewSet vs, const Args q) {
+template <class TRAV, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_jitter_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<64>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
     for (uint32_t k = 0; k < q.n; ++k) {
+        if constexpr (ADAPT)
+            if (!state_active(q.min, q.max, q.tol, st)) break;
         const uint32_t sample = q.first + k;
         uint32_t rgba, both;
         int2 idd;
@@ -81,25 +93,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 #endif
         trace_pixel<1, TRAV, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample);
         if (full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, both, sample)) rgba = both;
-        add_bytes(rgba, r, g, b);
+        if constexpr (ADAPT) add_sample(rgba, st);
+        else add_bytes(rgba, r, g, b);
     }
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    else store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
 }
 
 // the general full path tracer, jittered sample q.first (q.n == 1): trace_kernel<2>'s tiles, one pixel per lane
-template <class TRAV, int BLOCK, int WPE>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_jitter_kernel(const KArgs a, const ViewSet vs, const Args q) {
+// (ADAPT: the round's listed tiles, active lanes only)
+template <class TRAV, int BLOCK, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_jitter_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     int px, py;
-    if (!jitter_pixel<BLOCK>(a, px, py)) return;
+    if constexpr (ADAPT) {
+        if (!listed_pixel<BLOCK>(a, q, px, py)) return;
+    } else {
+        if (!jitter_pixel<BLOCK>(a, px, py)) return;
+    }
+    PixelState st{};
+    if constexpr (ADAPT) {
+        st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
+        if (!state_active(q.min, q.max, q.tol, st)) return;
+    }
     uint32_t rgba;
     int2 idd;
     LateOut lo;
     full::trace_pixel_full<TRAV, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
-    uint32_t r = 0u, g = 0u, b = 0u;
-    add_bytes(rgba, r, g, b);
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) {
+        add_sample(rgba, st);
+        store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    } else {
+        uint32_t r = 0u, g = 0u, b = 0u;
+        add_bytes(rgba, r, g, b);
+        store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    }
 }
 
 __global__ __launch_bounds__(256) void repeat_kernel(const Repeat q) {
@@ -108,6 +137,19 @@ __global__ __launch_bounds__(256) void repeat_kernel(const Repeat q) {
     uint32_t r = 0u, g = 0u, b = 0u;
     add_bytes(q.frame_rgba[i], r, g, b);
     store_sums(q.sums, i, r * q.n, g * q.n, b * q.n);
+}
+
+// the same for an adaptive accumulation: q.n rounds of a sample that never changes take each pixel to
+// adaptive_constant_count(), with no trace at all
+__global__ __launch_bounds__(256) void repeat_adaptive_kernel(const RepeatAdapt q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.pixels) return;
+    AdaptArgs s{};
+    s.sums = q.sums;
+    s.sq = q.sq;
+    PixelState st = load_state(s, i);
+    add_repeat(q.frame_rgba[i], adaptive_constant_count(st.n, q.n, q.min) - st.n, st);
+    store_state(s, i, st);
 }
 
 }  // namespace accum

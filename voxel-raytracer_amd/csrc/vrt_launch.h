@@ -71,6 +71,21 @@ hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s);
 hipError_t lens_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
 hipError_t lens_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
 hipError_t lens_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
+// Adaptive accumulations (include/vrt.h vrt_accum_begin_adaptive): the same launches with AdaptArgs take the kernels' adaptive
+// forms; the one-sample ones (accum_full, jitter_full, lens_full) trace the tiles adaptive_tiles listed before them.
+// adaptive_resolve: by each pixel's own count. adaptive_counts: vrt_accum_counts.
+hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
+hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
+hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
+hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
+hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
+hipError_t accum_repeat(const accum::RepeatAdapt &q, hipStream_t s);
+hipError_t lens_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t lens_opaque(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t lens_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t adaptive_resolve(const accum::Resolve &q, hipStream_t s);
+hipError_t adaptive_tiles(const accum::Tiles &t, hipStream_t s);
+hipError_t adaptive_counts(const accum::Counts &c, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt

@@ -14,6 +14,7 @@
 //   primary_lens_kernel  VRT_MODE_PRIMARY / _SHADOW: the samples of a launch looped in the lanes
 //   opaque_lens_kernel   VRT_MODE_FULL, opaque scenes whose every lens origin is in empty space: MODE 6's chain per sample
 //   full_lens_kernel     VRT_MODE_FULL, everything else: trace_pixel_full from the lens ray, one sample per launch
+// Each has an adaptive form (template parameter ADAPT, vrt_accum.hip.h).
 #pragma once
 #include "vrt_jitter.hip.h"
 
@@ -70,14 +71,18 @@ VRT_DEV LensRay lens_sample(const KArgs &a, const View &vw, const Lens &L, int p
 }
 
 // q.n lens samples q.first, q.first + 1, ... of MODE 0 or 1; whole frame
-template <int MODE, class TRAV, int BLOCK, int WPE>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_lens_kernel(const KArgs a, const ViewSet vs, const Args q, const Lens L) {
+template <int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_lens_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const Lens L) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<BLOCK>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
     for (uint32_t k = 0; k < q.n; ++k) {
+        if constexpr (ADAPT)
+            if (!state_active(q.min, q.max, q.tol, st)) break;
         uint32_t rgba;
         int2 idd;
         LateOut lo;
@@ -90,20 +95,26 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 #endif
         const LensRay lr = lens_sample(ak, vk, L, px, py, q.first + k);
         trace_pixel<MODE, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, &lr);
-        add_bytes(rgba, r, g, b);
+        if constexpr (ADAPT) add_sample(rgba, st);
+        else add_bytes(rgba, r, g, b);
     }
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    else store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
 }
 
 // MODE 6's two stages per lens sample, the seed in registers; 64 lanes, one 8 x 8 tile per wave
-template <class TRAV, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_lens_kernel(const KArgs a, const ViewSet vs, const Args q, const Lens L) {
+template <class TRAV, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_lens_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const Lens L) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     int px, py;
     if (!jitter_pixel<64>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
     for (uint32_t k = 0; k < q.n; ++k) {
+        if constexpr (ADAPT)
+            if (!state_active(q.min, q.max, q.tol, st)) break;
         const uint32_t sample = q.first + k;
         uint32_t rgba, both;
         int2 idd;
@@ -120,26 +131,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         const LensRay lr = lens_sample(ak, vk, L, px, py, sample);
         trace_pixel<1, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, &lr);
         if (full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, both, sample)) rgba = both;
-        add_bytes(rgba, r, g, b);
+        if constexpr (ADAPT) add_sample(rgba, st);
+        else add_bytes(rgba, r, g, b);
     }
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    else store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
 }
 
 // the general full path tracer, lens sample q.first (q.n == 1)
-template <class TRAV, int BLOCK, int WPE>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_lens_kernel(const KArgs a, const ViewSet vs, const Args q, const Lens L) {
+// (ADAPT: the round's listed tiles, active lanes only)
+template <class TRAV, int BLOCK, int WPE, bool ADAPT = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_lens_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const Lens L) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     int px, py;
-    if (!jitter_pixel<BLOCK>(a, px, py)) return;
+    if constexpr (ADAPT) {
+        if (!listed_pixel<BLOCK>(a, q, px, py)) return;
+    } else {
+        if (!jitter_pixel<BLOCK>(a, px, py)) return;
+    }
+    PixelState st{};
+    if constexpr (ADAPT) {
+        st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
+        if (!state_active(q.min, q.max, q.tol, st)) return;
+    }
     uint32_t rgba;
     int2 idd;
     LateOut lo;
     const LensRay lr = lens_sample(a, vs.v[0], L, px, py, q.first);
     full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    uint32_t r = 0u, g = 0u, b = 0u;
-    add_bytes(rgba, r, g, b);
-    store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    if constexpr (ADAPT) {
+        add_sample(rgba, st);
+        store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
+    } else {
+        uint32_t r = 0u, g = 0u, b = 0u;
+        add_bytes(rgba, r, g, b);
+        store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
+    }
 }
 
 }  // namespace accum

@@ -202,6 +202,8 @@ void vrt_destroy(vrt_ctx *c) {
     (void)hipFree(c->accum.d_pass1);
     (void)hipFree(c->accum.d_id);
     (void)hipFree(c->accum.d_seed);
+    (void)hipFree(c->accum.d_sq);
+    (void)hipFree(c->accum.d_tiles);
     if (c->accum.added) (void)hipEventDestroy(c->accum.added);
     if (c->accum.read) (void)hipEventDestroy(c->accum.read);
     if (!c->seeds.empty()) (void)hipDeviceSynchronize();   // their launches may be on the caller's streams
