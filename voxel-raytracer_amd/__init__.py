@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 HIP_LIB = os.environ.get("VRT_HIP_LIB") or os.path.join(HERE, "libvrt_hip.so")   # VRT_HIP_LIB: an A/B build of the same library (tools)
 HOST_LIB = os.path.join(HERE, "libvrt_host.so")
 TEST_LIB = os.path.join(HERE, "libvrt_hip_test.so")   # test support, not product (csrc/test/vrt_test.hip)
-OPT_RAY_TABLES, OPT_EMPTY_OCTANTS, OPT_DISPLAY_KERNEL, OPT_FULL_OPAQUE, OPT_HEAVY_TILES = 1, 2, 3, 4, 5
+OPT_RAY_TABLES, OPT_EMPTY_OCTANTS, OPT_DISPLAY_KERNEL, OPT_FULL_OPAQUE, OPT_HEAVY_TILES, OPT_MISS_TILES = 1, 2, 3, 4, 5, 6
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL = 0, 1, 2
 MODES = {"primary": MODE_PRIMARY, "primary_shadow": MODE_PRIMARY_SHADOW, "full": MODE_FULL}
@@ -560,6 +560,31 @@ def lens_choice(texels, cam_pos, inv_view, aperture, voxel_scale=1.0, world_min=
         raise VrtError(f"vrt_test_lens_select failed ({r})")
     return dict(box_valid=bool(out[0]), eye_shared=bool(out[1]), first_shared=bool(out[2]), no_medium=bool(out[3]),
                 empty=bool(out[4]), lo=tuple(out[5:8]), hi=tuple(out[8:11]), root_shift=int(out[11]))
+
+
+def miss_mask(texels, inv_proj, inv_view, cam_pos, width, height, voxel_scale=1.0, world_min=(-1023, -1023, -1023),
+              world_max=(1024, 1024, 1024)):
+    """Host-only (vrt_test_miss_mask): the miss-tile mask the dispatcher gives this view (VRT_OPT_MISS_TILES) -> (mask, boxes,
+    whole_view) with mask a ((height + 7) // 8, (width + 7) // 8) uint8 array, 1 = traced, 0 = forward-pointing rays miss; or None
+    when the view gets no mask."""
+    L = test_lib()
+    L.vrt_test_miss_mask.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float,
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_int32)]
+    t = np.ascontiguousarray(texels, np.uint8)
+    ip = np.ascontiguousarray(inv_proj, np.float32).reshape(-1)
+    iv = np.ascontiguousarray(inv_view, np.float32).reshape(-1)
+    cp = np.zeros(4, np.float32)
+    cp[:len(cam_pos)] = np.asarray(cam_pos, np.float32).reshape(-1)[:4]
+    mask = np.zeros(((height + 7) // 8, (width + 7) // 8), np.uint8)
+    stats = (C.c_int32 * 2)()
+    r = L.vrt_test_miss_mask(t.ctypes.data if t.size else None, t.size, (C.c_int32 * 3)(*world_min), (C.c_int32 * 3)(*world_max),
+                             float(voxel_scale), _fptr(ip), _fptr(iv), _fptr(cp), int(width), int(height), mask.ctypes.data, stats)
+    if r < 0:
+        raise VrtError(f"vrt_test_miss_mask failed ({r})")
+    if r == 0:
+        return None
+    return mask, int(stats[0]), bool(stats[1])
 
 
 def test_tile_order(tile_ticks, wave_slots, device=0):

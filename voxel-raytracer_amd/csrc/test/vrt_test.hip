@@ -20,6 +20,7 @@
 #include "../vrt_full.hip.h"
 #include "../vrt_kernels_v4.hip.h"
 #include "../vrt_layout.h"
+#include "../vrt_miss.h"
 #include "../vrt_sched.hip.h"
 
 namespace vrt {
@@ -123,6 +124,8 @@ __global__ void march_step_probe_kernel(const float *in, const int *dpos, uint32
 namespace vrt_internal {
 bool build_ray_table(const float *m, int W, int H, std::vector<float> &tab, float &z_out);
 bool view_matrix_in_range(const float *m);
+bool miss_table_fit(const float *tab, float z, int W, int H, vrt::miss::TableFit &f);
+bool miss_view_params(const float *inv_view, const float gro[3], const vrt::miss::TableFit &f, vrt::miss::ViewParams &v);
 }
 using vrt_internal::build_ray_table;
 using vrt_internal::view_matrix_in_range;
@@ -244,6 +247,43 @@ int vrt_test_lens_select(const uint8_t *texels, size_t used_bytes, const int32_t
         out[11] = shift;
     }
     return VRT_OK;
+}
+
+// Host-only (tests without a GPU): the miss mask the dispatcher would give this view of this tree (VRT_OPT_MISS_TILES) -- the same
+// occupancy boxes (vrt_layout.cpp), view parameters (vrt_raygen.cpp) and per-box marking (vrt_miss.h mark_box, the function
+// miss_mask_kernel runs per box). mask_out: ((W + 7) / 8) * ((H + 7) / 8) bytes, 1 = traced, 0 = every forward-pointing ray of the
+// tile misses. stats (optional): [0] boxes, [1] 1 when some box needed the whole view. Returns 1 with a mask, 0 when the view gets
+// none (no ray tables, view matrix out of range, view parameters refused, too many boxes), VRT_E_MALFORMED / VRT_E_INVALID.
+int vrt_test_miss_mask(const uint8_t *texels, size_t used_bytes, const int32_t wmin[3], const int32_t wmax[3], float voxel_scale,
+                       const float inv_proj[16], const float inv_view[16], const float cam_pos[4], int width, int height,
+                       uint8_t *mask_out, int32_t stats[2]) {
+    if (!wmin || !wmax || !inv_proj || !inv_view || !cam_pos || !mask_out || width < 1 || height < 1) return VRT_E_INVALID;
+    vrt::Layout lay;
+    std::string err;
+    if (!vrt::build_layout(texels, used_bytes, lay, err)) return VRT_E_MALFORMED;
+    for (int k = 0; k < 3; ++k)
+        if (wmin[k] < -vrt::miss::kMaxWorld || wmax[k] > vrt::miss::kMaxWorld) return 0;
+    if (!view_matrix_in_range(inv_view)) return 0;
+    std::vector<float> tab;
+    float z = 0.0f;
+    if (!build_ray_table(inv_proj, width, height, tab, z)) return 0;
+    const float gro[3] = {cam_pos[0] * voxel_scale, cam_pos[1] * voxel_scale, cam_pos[2] * voxel_scale};
+    if (!vrt::miss::eye_in_world(gro, wmin, wmax)) return 0;
+    vrt::miss::ViewParams vp;
+    vrt::miss::TableFit fit;
+    if (!vrt_internal::miss_table_fit(tab.data(), z, width, height, fit) || !vrt_internal::miss_view_params(inv_view, gro, fit, vp)) return 0;
+    std::vector<int> boxes;
+    if (!vrt::occupancy_boxes(lay.records, wmin, wmax, (size_t)vrt::miss::kMaxBoxes, boxes)) return 0;
+    const size_t tiles = (size_t)vp.tiles_x * (size_t)vp.tiles_y;
+    std::memset(mask_out, 0, tiles);
+    bool all = false;
+    for (size_t i = 0; i + 6 <= boxes.size(); i += 6) {
+        const vrt::miss::Box b{{boxes[i], boxes[i + 1], boxes[i + 2]}, {boxes[i + 3], boxes[i + 4], boxes[i + 5]}};
+        all = vrt::miss::mark_box(vp, b, mask_out, 1u) || all;
+    }
+    if (all) std::memset(mask_out, 1, tiles);
+    if (stats) { stats[0] = (int32_t)(boxes.size() / 6); stats[1] = all ? 1 : 0; }
+    return 1;
 }
 
 // Host-only check of the wide layout (tests without a GPU): builds it for the texel stream and world

@@ -36,6 +36,12 @@ struct View {
     const float *gen_x, *gen_y;
     float gen_z;
     uint32_t gen_fast;
+    // Miss tiles (include/vrt.h VRT_OPT_MISS_TILES, vrt_miss.h): a header word equal to miss_stamp when every tile is traced, a
+    // spare word, then one byte per 8 x 8 tile of the FRAME, row-major, (width + 7) / 8 per row; a byte other than miss_stamp: the
+    // rays of that tile that point forward on every axis provably hit nothing. Null: no mask (every pixel traced). Set by the
+    // dispatcher only for the EYE85 primary kernels and views with gen_fast.
+    const uint8_t *miss;
+    uint32_t miss_stamp;
 };
 
 // Kernel arguments: passed by value (kernarg segment -> scalar loads, wave-uniform).

@@ -301,6 +301,15 @@ VRT_DEV void record_find(const KArgs &a, I3 p, uint32_t &w0, uint32_t &w1) {
 // traversals whose shadow() takes the dispatcher's LightSetup declare `static constexpr bool kHostLight = true`
 template <class T, class = void> struct host_light { static constexpr bool value = false; };
 template <class T> struct host_light<T, decltype((void)T::kHostLight)> { static constexpr bool value = T::kHostLight; };
+// ... and the ones whose primary rays may skip the march on miss tiles (View::miss) `static constexpr bool kMissTiles = true`
+template <class T, class = void> struct miss_tiles { static constexpr bool value = false; };
+template <class T> struct miss_tiles<T, decltype((void)T::kMissTiles)> { static constexpr bool value = T::kMissTiles; };
+
+// A primary ray the miss-tile proof covers ("Miss tiles"): no component of its direction within 2e-8 of (-1e-8, 0], so that after
+// march()'s renormalisation (a factor within a few ulps of 1) none lies in (-1e-8, 0] and every step of the DDA has t >= 0.
+VRT_DEV bool miss_forward(F3 d) {
+    return (d.x > 0.0f || d.x < -2e-8f) && (d.y > 0.0f || d.y < -2e-8f) && (d.z > 0.0f || d.z < -2e-8f);
+}
 
 // The seed pass 1 of the two-pass full path tracer (trace_kernel MODE 4) leaves per pixel for pass 2 (MODE 5, vrt_full.hip.h
 // bounce_pixel): five words, tile-major planes of 64 lanes -- seed[(tile * 5 + plane) * 64 + lane] -- so a wave's store of a plane is
@@ -315,9 +324,13 @@ struct Seed { F3 hp; uint32_t word; float iof; };   // the same in registers (MO
 // TRAV supplies the traversal: march(), shadow(). MODE: 0 primary, 1 primary + shadow ray. seed (MODE 1 only): see above.
 // JIT: the ray of jittered sample `sample` (jittered_ray_dir(); the progressive accumulation, vrt_jitter.hip.h).
 // LENS: the ray `lens` of a thin-lens sample (lens_ray(), vrt_lens.hip.h): its origin, direction and the medium at its origin.
-template <int MODE, class TRAV, bool JIT = false, bool LENS = false>
+// MISS (modes 0 and 1 of the traversals with kMissTiles): miss_byte is this pixel's byte of the view's miss mask (View::miss), or
+// View::miss_stamp when there is none: any other value clears the tile, and a ray that points forward on every axis (miss_forward())
+// then hits nothing ("Miss tiles") and takes the miss outputs without marching.
+template <int MODE, class TRAV, bool JIT = false, bool LENS = false, bool MISS = false>
 VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                         uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u, const LensRay *lens = nullptr) {
+                         uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u, const LensRay *lens = nullptr,
+                         uint32_t miss_byte = 0u) {
     const float kPI = 3.14159265359f;
     F3 ray_dir;
     if constexpr (LENS) ray_dir = lens->dir;
@@ -346,7 +359,16 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
     // byte form of start_iof for traversals that test media on bytes: r(b) in (0, 3) <=> 1 <= b <= 254, else 1.0 == r(85)
     const uint32_t eye_b = eye1 & 0xffu;
     const uint32_t iof_byte = (eye_b >= 1u && eye_b <= 254u) ? eye_b : 85u;
-    bool hit = TRAV::march(a, tc_, gro, ray_dir, start_iof, iof_byte, h, &vw);
+    bool hit = false;
+    bool miss_tile = false;
+    if constexpr (MISS) {
+        static_assert((MODE == 0 || MODE == 1) && !JIT && !LENS && miss_tiles<TRAV>::value, "miss tiles: EYE85 primary rays only");
+        // the byte as a value in a vector register, read only once the direction is made: the compare is not hoisted to the load
+        // (whose latency would then stall the wave before its ray generation)
+        asm volatile("" : "+v"(miss_byte) : "v"(ray_dir.x), "v"(ray_dir.y), "v"(ray_dir.z));
+        miss_tile = miss_byte != vw.miss_stamp;
+    }
+    if (!(miss_tile && miss_forward(ray_dir))) hit = TRAV::march(a, tc_, gro, ray_dir, start_iof, iof_byte, h, &vw);
     // The uniforms of the shading stage. With a shadow march still to come they are re-read from the kernarg segment
     // here, in one scalar-load round trip, so that they do not occupy registers across the traversal (-2 % per
     // frame); the primary-only kernel is short enough that the round trip costs more than the two spills it saves.
@@ -590,6 +612,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 trace_pixel<1, TRAV>(a, vw, tc_, px, py, rgba, idd, lo, nullptr, &seed);
                 uint32_t both;
                 if (full::bounce_pixel<TRAV>(a, tc_, px, py, seed, both)) rgba = both;
+            }
+            else if constexpr ((MODE == 0 || MODE == 1) && miss_tiles<TRAV>::value) {
+                // one byte per lane from the view's mask (the FRAME's 8 x 8 tiles: a row-range launch's tile may straddle two), compared
+                // with the stamp only after ray generation, so that the load's latency hides behind it
+                uint32_t miss_byte = vw.miss_stamp;
+                if (vw.miss) {
+                    miss_byte = vw.miss[8u + (uint32_t)(py >> 3) * (uint32_t)((a.width + 7) >> 3) + (uint32_t)(px >> 3)];
+                    if (*reinterpret_cast<const uint32_t *>(vw.miss) == vw.miss_stamp) miss_byte = vw.miss_stamp;   // every tile traced
+                }
+                trace_pixel<MODE, TRAV, false, false, true>(a, vw, tc_, px, py, rgba, idd, lo, nullptr, nullptr, 0u, nullptr, miss_byte);
             }
             else trace_pixel<MODE, TRAV>(a, vw, tc_, px, py, rgba, idd, lo);
             if constexpr (MODE == 0) lo = LateOut{vw.out_rgba, vw.out_id, a.width, a.compact};

@@ -3,6 +3,7 @@
 // vrt_dispatch* entry points of include/vrt.h. Host code; the kernels are behind vrt_launch.h.
 #include "vrt_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <new>
@@ -123,8 +124,143 @@ vrt_ctx::RayTable *ray_table(vrt_ctx *c, const float *inv_proj, int W, int H) {
         t->capacity = tab.size();
     }
     if (hipMemcpy(t->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    t->fit_ok = miss_table_fit(tab.data(), z, W, H, t->fit);
     t->ok = true;
     return t;
+}
+
+// The occupancy boxes of the current tree and world bounds on the device (vrt_layout.h occupancy_boxes), made when a mask is about
+// to be built (miss_mask(), second sight) and the list on the device is not for the current tree_gen (uploads, patches, batches and
+// compaction all advance it) and bounds. Never on a dispatch that builds no mask: an application that edits before every frame
+// never pays for it (a key that holds tree_gen is new after every edit). Host time: the walk of the record array, 0.9 ms for
+// dragon.vox, 33 ms for the config-4 terrain (2.7 M records, 408 K boxes), plus the copy. False: no list (too many boxes, a world
+// beyond the proof's bounds, a malformed tree, no device memory).
+bool occupancy(vrt_ctx *c) {
+    vrt_ctx::Occupancy &o = c->occ;
+    const bool same = o.built && o.tree_gen == c->tree_gen && std::memcmp(o.wmin, c->params.world_min, sizeof o.wmin) == 0 &&
+                      std::memcmp(o.wmax, c->params.world_max, sizeof o.wmax) == 0;
+    if (same) return o.ok;
+    o.built = true; o.ok = false;
+    o.tree_gen = c->tree_gen;
+    std::memcpy(o.wmin, c->params.world_min, sizeof o.wmin);
+    std::memcpy(o.wmax, c->params.world_max, sizeof o.wmax);
+    for (int k = 0; k < 3; ++k)   // the proof's bound on a march position (DESIGN §3 "Miss tiles"): a world inside [-2^11, 2^11]^3
+        if (o.wmin[k] < -vrt::miss::kMaxWorld || o.wmax[k] > vrt::miss::kMaxWorld) return false;
+    std::vector<int> boxes;
+    if (!vrt::occupancy_boxes(c->host_records, o.wmin, o.wmax, (size_t)vrt::miss::kMaxBoxes, boxes)) return false;
+    const size_t bytes = boxes.size() * sizeof(int);
+    // launches in flight may read the old list (through the masks built from it: they read the masks only)
+    if (hipDeviceSynchronize() != hipSuccess) return false;
+    if (bytes > o.capacity) {
+        (void)hipFree(o.d_boxes);
+        o.d_boxes = nullptr; o.capacity = 0;
+        if (hipMalloc((void **)&o.d_boxes, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        o.capacity = bytes;
+    }
+    if (bytes && hipMemcpy(o.d_boxes, boxes.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return false; }
+    o.n_boxes = boxes.size() / 6;
+    o.ok = true;
+    return true;
+}
+
+// The miss mask of one view (vrt_miss.h), from the cache or built now on stream s by miss_mask_kernel over the occupancy boxes.
+// The key is what the mask depends on: the projection and the frame shape (the ray tables), the view matrix, the eye in voxels,
+// the tree generation and the world bounds. A mask is built the SECOND time its key is seen: a camera that moves every frame would pay a build per frame (5.2 us
+// at 1080p on the dragon) for less than that back (profiles/miss_tiles_moving.txt: the frame right after a build gains little), a
+// camera that holds still pays one build and gains every frame after (8.5 us). A build writes a
+// new stamp into the tiles it marks (View::miss_stamp), so it needs no clearing pass. Eight keys are kept; the least recently used
+// one is replaced -- its buffer rebuilt at once when only its own stream read it (stream order keeps the launches that did before
+// the rebuild), after a device synchronize otherwise. Every build records an event on its stream right after the kernel; a launch on
+// another stream waits for it (the build's stream, which may be a caller's, is never touched again). nullptr: no mask for this view
+// (yet).
+const uint8_t *miss_mask(vrt_ctx *c, const vrt::View &w, const vrt_ctx::RayTable &t, float voxel_scale, hipStream_t s, uint32_t &stamp) {
+    // The box list costs a walk of the whole record array (~12 ns per record: 0.9 ms for dragon.vox, 33 ms for the config-4 terrain)
+    // and a frame gains ~10 us: masks are made only once the tree and the bounds have stood unchanged for max(kStableMin, records /
+    // kStablePerRecords) of these requests -- an application that edits every few frames never pays for a list it could not
+    // amortise (tools/miss_tiles_edit.py), and the walk costs at most ~6 us per frame of the stable stretch before it.
+    vrt_ctx::Occupancy &o = c->occ;
+    if (o.seen_gen != c->tree_gen || std::memcmp(o.seen_wmin, c->params.world_min, sizeof o.seen_wmin) != 0 ||
+        std::memcmp(o.seen_wmax, c->params.world_max, sizeof o.seen_wmax) != 0) {
+        o.seen_gen = c->tree_gen;
+        std::memcpy(o.seen_wmin, c->params.world_min, sizeof o.seen_wmin);
+        std::memcpy(o.seen_wmax, c->params.world_max, sizeof o.seen_wmax);
+        o.stable = 0;
+    }
+    const uint64_t need = std::max<uint64_t>(vrt::miss::kStableMin, c->host_records.size() / vrt::miss::kStablePerRecords);
+    if (o.stable < need) { ++o.stable; return nullptr; }
+    const float gro[3] = {w.cam_pos[0] * voxel_scale, w.cam_pos[1] * voxel_scale, w.cam_pos[2] * voxel_scale};   // the kernel's gro
+    // an eye outside the world: the march's first step goes to the world face in the direction of travel, which lies BEHIND a ray
+    // that leaves that face's half-space (t < 0), and rounding can land it inside -- the proof's t >= 0 does not hold: no mask
+    if (!vrt::miss::eye_in_world(gro, c->params.world_min, c->params.world_max)) return nullptr;
+    const int W = t.width, H = t.height;
+    vrt_ctx::MissMask *hit = nullptr, *lru = nullptr;
+    for (auto &m : c->miss_masks) {
+        if (m.width == W && m.height == H && m.tree_gen == c->tree_gen && std::memcmp(m.wmin, c->params.world_min, sizeof m.wmin) == 0 &&
+            std::memcmp(m.wmax, c->params.world_max, sizeof m.wmax) == 0 && std::memcmp(m.inv_proj, w.inv_proj, sizeof m.inv_proj) == 0 &&
+            std::memcmp(m.inv_view, w.inv_view, sizeof m.inv_view) == 0 && std::memcmp(m.gro, gro, sizeof m.gro) == 0)
+            hit = &m;
+        if (!lru || m.last_use < lru->last_use) lru = &m;
+    }
+    if (hit && !hit->pending) {
+        hit->last_use = ++c->miss_tick;
+        if (!hit->ok) return nullptr;
+        if (hit->stream != s) {
+            if (hipStreamWaitEvent(s, hit->built, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            hit->shared = true;
+        }
+        stamp = hit->stamp;
+        return reinterpret_cast<const uint8_t *>(hit->d_mask);
+    }
+    if (!hit) {   // first sight: note the key, build nothing (the slot's buffer, which launches in flight may read, stays as it is)
+        vrt_ctx::MissMask *m;
+        if (c->miss_masks.size() < 8) {
+            c->miss_masks.emplace_back();
+            m = &c->miss_masks.back();
+        } else {
+            m = lru;
+        }
+        std::memcpy(m->inv_proj, w.inv_proj, sizeof m->inv_proj);
+        std::memcpy(m->inv_view, w.inv_view, sizeof m->inv_view);
+        std::memcpy(m->gro, gro, sizeof m->gro);
+        m->width = W; m->height = H; m->tree_gen = c->tree_gen;
+        std::memcpy(m->wmin, c->params.world_min, sizeof m->wmin);
+        std::memcpy(m->wmax, c->params.world_max, sizeof m->wmax);
+        m->ok = false;
+        m->pending = true;
+        m->last_use = ++c->miss_tick;
+        return nullptr;
+    }
+    vrt_ctx::MissMask *m = hit;   // second sight: build
+    m->pending = false;
+    m->last_use = ++c->miss_tick;
+    vrt::miss::ViewParams vp;
+    if (!t.fit_ok || !miss_view_params(w.inv_view, gro, t.fit, vp)) return nullptr;
+    if (!m->built && hipEventCreateWithFlags(&m->built, hipEventDisableTiming) != hipSuccess) { m->built = nullptr; (void)hipGetLastError(); return nullptr; }
+    if (!occupancy(c)) return nullptr;
+    if (m->d_mask && (m->shared || m->stream != s) && hipDeviceSynchronize() != hipSuccess) return nullptr;
+    const size_t bytes = 8 + (size_t)vp.tiles_x * (size_t)vp.tiles_y;
+    if (bytes > m->capacity) {
+        if (m->d_mask && hipDeviceSynchronize() != hipSuccess) return nullptr;   // any stream may still read the old buffer
+        uint32_t *fresh = nullptr;
+        if (hipMalloc((void **)&fresh, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        (void)hipFree(m->d_mask);
+        m->d_mask = fresh;
+        m->capacity = bytes;
+        m->stamp = 0;   // cleared below
+    }
+    if (m->stamp == 255u) m->stamp = 0u;   // wrapped: bytes of every stamp may be left, cleared below
+    m->stamp = (uint8_t)(m->stamp + 1u);
+    if (m->stamp == 1u && hipMemsetAsync(m->d_mask, 0, m->capacity, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // new or wrapped
+    if (vrt::launch::miss_mask(vp, c->occ.d_boxes, (uint32_t)c->occ.n_boxes, m->d_mask, m->stamp, s) != hipSuccess ||
+        hipEventRecord(m->built, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    m->stream = s;
+    m->shared = false;
+    m->ok = true;
+    stamp = m->stamp;
+    return reinterpret_cast<const uint8_t *>(m->d_mask);
 }
 
 // views == nullptr: one view, the context's camera (vrt_set_camera) rendering into d_rgba / d_id.
@@ -159,6 +295,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     std::memset(&vs, 0, sizeof vs);
     a.n_views = n_views;
     int eyes[vrt::kMaxViews][3];
+    const vrt_ctx::RayTable *tables[vrt::kMaxViews] = {};
     for (int i = 0; i < n_views; ++i) {
         vrt::View &w = vs.v[i];
         std::memcpy(w.inv_proj, views ? views[i].inv_projection : c->inv_proj, sizeof w.inv_proj);
@@ -182,9 +319,13 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
             w.first_s = ff.s; w.first_as = ff.as;
         }
         w.gen_x = w.gen_y = nullptr; w.gen_z = 0.0f; w.gen_fast = 0u;
+        w.miss = nullptr;
+        w.miss_stamp = 0u;
+        tables[i] = nullptr;
         if (view_matrix_in_range(w.inv_view)) {
             if (const vrt_ctx::RayTable *t = ray_table(c, w.inv_proj, width, height)) {
                 w.gen_x = t->d_tab; w.gen_y = t->d_tab + width; w.gen_z = t->z; w.gen_fast = 1u;
+                tables[i] = t;
             }
         }
     }
@@ -209,6 +350,10 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         if (lens) eye_in_medium = !lsel.no_medium;   // ... any origin of the lens inside one
         if (eye_in_medium) { v.trav = 3; v.wpe = 6; }
     }
+    // miss tiles: the EYE85 primary kernels (v4, seven waves per SIMD) read a mask for every view with ray tables
+    if (c->miss_tiles_on && !acc && v.trav == 4 && v.wpe == 7 && mode != VRT_MODE_FULL)
+        for (int i = 0; i < n_views; ++i)
+            if (tables[i]) vs.v[i].miss = miss_mask(c, vs.v[i], *tables[i], c->params.voxel_scale, s, vs.v[i].miss_stamp);
     a.voxel_scale = c->params.voxel_scale;
     for (int i = 0; i < 3; ++i) {
         a.wmin[i] = c->params.world_min[i];
@@ -666,6 +811,10 @@ int vrt_set_option(vrt_ctx *c, int option, int value) {
         case VRT_OPT_HEAVY_TILES:
             if (value != 0 && value != 1) break;
             c->heavy_split_on = value != 0;
+            return VRT_OK;
+        case VRT_OPT_MISS_TILES:
+            if (value != 0 && value != 1) break;
+            c->miss_tiles_on = value != 0;
             return VRT_OK;
         case VRT_OPT_DISPLAY_KERNEL:
             if (value != 0 && value != 2 && value != 3) break;

@@ -21,6 +21,7 @@
 
 #include "vrt_args.h"
 #include "vrt_layout.h"
+#include "vrt_miss.h"
 
 // Variant 0 is what the library ships: the v4 traversal, seven waves per SIMD (five for the full path tracer, which runs
 // v4's general march loop); the dispatcher takes v3 when a primary / primary + shadow launch has its eye inside a medium,
@@ -139,11 +140,44 @@ struct vrt_ctx {
         bool ok = false;            // the projection has the separable shape and the tables are on the device
         float z = 0.0f;
         float *d_tab = nullptr;     // width floats (x per column) then height floats (y per row)
+        bool fit_ok = false;        // `fit` holds the miss-tile build's part of the tables (vrt_raygen.cpp miss_table_fit)
+        vrt::miss::TableFit fit{};
         size_t capacity = 0;        // floats
         uint64_t last_use = 0;
     };
     std::vector<RayTable> ray_tables;
     uint64_t ray_tick = 0;
+    // miss tiles (VRT_OPT_MISS_TILES, vrt_miss.h): the occupancy boxes (vrt_layout.h occupancy_boxes) of the tree and world bounds
+    // the last mask was built for; and one mask per (view, frame shape, tree_gen, bounds) seen lately
+    bool miss_tiles_on = true;
+    struct Occupancy {
+        bool built = false, ok = false;
+        uint64_t tree_gen = 0;
+        int wmin[3] = {0, 0, 0}, wmax[3] = {0, 0, 0};
+        uint64_t seen_gen = ~0ull;         // the tree generation and bounds mask requests have seen, and for how many requests
+        int seen_wmin[3] = {0, 0, 0}, seen_wmax[3] = {0, 0, 0};
+        uint64_t stable = 0;
+        int *d_boxes = nullptr;            // n_boxes vrt::miss::Box
+        size_t capacity = 0, n_boxes = 0;
+    };
+    Occupancy occ;
+    struct MissMask {
+        float inv_proj[16]{}, inv_view[16]{}, gro[3]{};
+        int width = 0, height = 0;
+        uint64_t tree_gen = 0;             // ... the tree and world bounds it was made for
+        int wmin[3] = {0, 0, 0}, wmax[3] = {0, 0, 0};
+        bool pending = false;              // the key has been seen once: the next sight builds the mask
+        bool ok = false;                   // d_mask holds this view's mask (or is being built on `stream`)
+        uint32_t *d_mask = nullptr;        // View::miss: the header word, a spare word, then the tile bytes
+        size_t capacity = 0;               // bytes
+        uint8_t stamp = 0;                 // of the last build: View::miss_stamp
+        bool shared = false;               // a launch on another stream than `stream` has read it since the build
+        hipStream_t stream = nullptr;
+        hipEvent_t built = nullptr;        // recorded on `stream` right after the build
+        uint64_t last_use = 0;
+    };
+    std::vector<MissMask> miss_masks;
+    uint64_t miss_tick = 0;
     // VRT_MODE_FULL as two passes (vrt_launch.h trace_full_two_pass): the option, what the uploaded tree allows, the seed buffers
     bool two_pass_on = true;                     // vrt_set_option(VRT_OPT_FULL_OPAQUE)
     bool heavy_split_on = true;                  // KArgs::split_count (VRT_OPT_HEAVY_TILES)
@@ -240,5 +274,7 @@ constexpr long kSchedMaxDenoiseGroups = 2048;   // beyond ~8,000 tiles (16 round
 // vrt_raygen.cpp
 bool build_ray_table(const float *m, int W, int H, std::vector<float> &tab, float &z_out);
 bool view_matrix_in_range(const float *m);
+bool miss_table_fit(const float *tab, float z, int W, int H, vrt::miss::TableFit &f);
+bool miss_view_params(const float *inv_view, const float gro[3], const vrt::miss::TableFit &f, vrt::miss::ViewParams &v);
 
 }  // namespace vrt_internal

@@ -72,6 +72,9 @@ struct TravT {
     using Ctx = v3::Trav::Ctx;
     using Eye85 = TravT<true>;   // the same traversal with the one march loop of rays that start in empty space
     using General = TravT<false>;   // ... and with the loop that takes a ray's own starting medium
+    // primary rays of an EYE85 launch may skip the march on the view's miss tiles (View::miss, DESIGN §3 "Miss tiles"): the proof needs
+    // the one march loop of rays that start in empty space
+    static constexpr bool kMissTiles = EYE85;
 
     static VRT_DEV void block_init(const KArgs &a, Ctx &c) { c.root = a.nodes[0]; }
 

@@ -32,6 +32,10 @@ inline hipError_t trace(int mode, const Variant &v, const KArgs &a, const ViewSe
 // ceiling first (once per device; needed above 48 KiB).
 // wave_slots: waves the chip holds of the kernel the order is for (KArgs::split_count is 0 unless the heaviest tile outlasts its even share); 0: no split count
 hipError_t tile_order(const uint32_t *d_cost, uint32_t n_groups, uint32_t *d_order, uint32_t wave_slots, bool raise_lds, size_t lds_ceiling, hipStream_t s);
+// miss tiles (vrt_miss.h): d_mask = a header word, a spare word, then v.tiles_x * v.tiles_y bytes, none of which (header included)
+// holds `stamp` before the build; writes `stamp` to the tiles the n boxes may be seen through, and to the header word when one of
+// them reaches the eye's plane (every tile traced)
+hipError_t miss_mask(const miss::ViewParams &v, const int *d_boxes, uint32_t n, uint32_t *d_mask, uint8_t stamp, hipStream_t s);
 // checks on the device that the kernarg segment is laid out as late_args() / late_view() assume; *d_bad += mismatches
 hipError_t kernarg_probe(const KArgs &a, const ViewSet &vs, uint32_t *d_bad, hipStream_t s);
 

@@ -822,3 +822,49 @@ void lens_select(const std::vector<Record> &records, const WideTree *wide, const
 }
 
 }  // namespace vrt
+
+namespace vrt {
+
+bool occupancy_boxes(const std::vector<Record> &records, const int wmin[3], const int wmax[3], size_t max_boxes, std::vector<int> &out) {
+    out.clear();
+    if (records.empty()) return true;
+    struct Item { uint32_t rec; Box box; int depth; };
+    std::vector<Item> todo;
+    Box world;
+    for (int k = 0; k < 3; ++k) { world.mn[k] = wmin[k]; world.mx[k] = wmax[k]; }
+    todo.push_back(Item{0u, world, 0});
+    while (!todo.empty()) {
+        const Item it = todo.back();
+        todo.pop_back();
+        const uint32_t mask = records[it.rec].w0 & 0xffu, leaf_mask = (records[it.rec].w0 >> 8) & 0xffu;
+        uint32_t child = records[it.rec].w1;
+        int mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+        bool any = false;
+        for (uint32_t ci = 0; ci < 8; ++ci) {
+            if (!((mask >> ci) & 1u)) continue;
+            const uint32_t idx = child++;
+            if ((size_t)idx >= records.size()) { out.clear(); return false; }
+            const Box b = child_box(it.box, ci);
+            if (!((leaf_mask >> ci) & 1u)) {
+                if (it.depth + 1 >= 32) { out.clear(); return false; }   // deeper than any layout build_layout() makes
+                todo.push_back(Item{idx, b, it.depth + 1});
+                continue;
+            }
+            const uint32_t refr = records[idx].w1 & 0xffu;
+            if (refr == 0u || refr == 85u) continue;
+            if (b.mx[0] <= b.mn[0] || b.mx[1] <= b.mn[1] || b.mx[2] <= b.mn[2]) continue;   // holds no cell
+            for (int k = 0; k < 3; ++k) {
+                mn[k] = any && mn[k] < b.mn[k] ? mn[k] : b.mn[k];
+                mx[k] = any && mx[k] > b.mx[k] ? mx[k] : b.mx[k];
+            }
+            any = true;
+        }
+        if (any) {
+            out.insert(out.end(), {mn[0], mn[1], mn[2], mx[0], mx[1], mx[2]});
+            if (out.size() / 6 > max_boxes) { out.clear(); return false; }
+        }
+    }
+    return true;
+}
+
+}  // namespace vrt

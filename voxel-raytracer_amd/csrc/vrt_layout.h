@@ -106,6 +106,16 @@ void tighten_root0(const WideTree &wt, const int (*eyes)[3], int n, int min_shif
 // runs VRT_MODE_FULL without a ray stack (vrt_full.hip.h bounce_pixel).
 bool tree_is_opaque(const std::vector<Record> &records);
 
+// Miss tiles (vrt_miss.h, DESIGN §3 "Miss tiles"): boxes that together cover every cell an EYE85 primary ray can stop in -- every leaf whose
+// refraction byte is neither 0 nor 85 (the cells whose medium byte in to_cell4() form is not 85, whichever alpha the leaf has:
+// a superset of the wide layout's stopping cells, and of the record walk's outside the wide roots). One box per internal node: the
+// bounds of its stopping leaf children, the boxes as the shader splits the world (for the usual unit leaves a box of at most
+// 2 x 2 x 2 voxels). One pass over the records, no sort: 0.9 ms for dragon.vox (9,811 boxes), 33 ms for the config-4 terrain.
+// Not rounded out to cells of side 4: at the bench pose a voxel spans two 8-pixel tiles, and that rounding alone costs a fifth of
+// the tiles a mask clears. Boxes are [mn, mx) in voxel cells, 6 ints each. False when the tree is malformed or the list would
+// exceed max_boxes (out is then empty).
+bool occupancy_boxes(const std::vector<Record> &records, const int wmin[3], const int wmax[3], size_t max_boxes, std::vector<int> &out);
+
 // Returns false when the scene cannot be expressed (an internal node of unit size inside an aligned
 // cube, or more than kMaxWideRoots roots): the dispatcher then uses the record-array kernels.
 bool build_wide(const std::vector<Record> &records, const int wmin[3], const int wmax[3], WideTree &out, std::string &why);

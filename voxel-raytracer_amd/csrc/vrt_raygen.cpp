@@ -4,6 +4,8 @@
 #include <cstring>
 #include <vector>
 
+#include "vrt_miss.h"
+
 namespace vrt_internal {
 
 // ---- ray generation, the part that does not depend on the pixel as a whole ---------------------------------------------
@@ -66,6 +68,64 @@ bool view_matrix_in_range(const float *m) {
     const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
                        a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
     return det * det >= 2.3842e-7 * f2 * f2 * f2;                   // sigma_min >= 2^-10 sqrt(F2)  <=  det^2 >= 2^-22 F2^3
+}
+
+// The miss-tile build's view (vrt_miss.h ViewParams) in two parts. miss_table_fit(), once per ray table (tab = gen_x[0..W) then
+// gen_y[0..H), z = gen_z): the affine fit gen_x[px] = gx0 + px * gdx (and y), the tables' largest distance from it in pixels, the
+// largest |g|^2. miss_view_params(), per view: inv_view as View::inv_view, gro = cam_pos * voxel_scale as the kernel computes it.
+// The margin covers, in pixels,
+//   * the tables' distance from the fit;
+//   * the rays' own float error: a direction within a relative 1e-5 * cond(invView3x3) of inv_view3x3 * (gen_x, gen_y, gen_z)
+//     (the prologue's normalisations and product and the march's renormalisation take a few ulps, 2^-24 each) moves the
+//     table point by that much times |g|^2 / |gz|;
+//   * 1.5 pixels on top.
+// False when the view gives no usable mask (degenerate tables, a singular or non-finite matrix, an eye beyond miss::kMaxEye, a
+// margin above 16 pixels).
+bool miss_table_fit(const float *tab, float z, int W, int H, vrt::miss::TableFit &f) {
+    if (W < 1 || H < 1) return false;
+    const float *tx = tab, *ty = tab + W;
+    f.gx0 = tx[0]; f.gdx = W > 1 ? ((double)tx[W - 1] - (double)tx[0]) / (double)(W - 1) : 1.0;
+    f.gy0 = ty[0]; f.gdy = H > 1 ? ((double)ty[H - 1] - (double)ty[0]) / (double)(H - 1) : 1.0;
+    f.gz = z;
+    if (!(std::fabs(f.gdx) > 0.0) || !(std::fabs(f.gdy) > 0.0) || !(std::fabs(f.gz) > 0.0)) return false;
+    double dev = 0.0;   // largest distance from the fit, in pixels
+    for (int px = 0; px < W; ++px) dev = std::fmax(dev, std::fabs(((double)tx[px] - (f.gx0 + px * f.gdx)) / f.gdx));
+    for (int py = 0; py < H; ++py) dev = std::fmax(dev, std::fabs(((double)ty[py] - (f.gy0 + py * f.gdy)) / f.gdy));
+    const double xm = std::fmax(std::fabs((double)tx[0]), std::fabs((double)tx[W - 1]));
+    const double ym = std::fmax(std::fabs((double)ty[0]), std::fabs((double)ty[H - 1]));
+    f.dev_px = dev;
+    f.gmax2 = xm * xm + ym * ym + f.gz * f.gz;
+    f.width = W; f.height = H;
+    return dev == dev && f.gmax2 == f.gmax2;
+}
+
+bool miss_view_params(const float *inv_view, const float gro[3], const vrt::miss::TableFit &f, vrt::miss::ViewParams &v) {
+    double a[3][3], f2 = 0.0;
+    for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) { a[r][c] = (double)inv_view[c * 4 + r]; f2 += a[r][c] * a[r][c]; }
+    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                       a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+    if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
+    double g2 = 0.0;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {   // adjugate / det: inverse[r][c] = cofactor(c, r) / det
+            const int r0 = (c + 1) % 3, r1 = (c + 2) % 3, c0 = (r + 1) % 3, c1 = (r + 2) % 3;
+            v.m[r * 3 + c] = (a[r0][c0] * a[r1][c1] - a[r0][c1] * a[r1][c0]) / det;
+            g2 += v.m[r * 3 + c] * v.m[r * 3 + c];
+        }
+    for (int k = 0; k < 3; ++k) {
+        if (!(std::fabs((double)gro[k]) <= vrt::miss::kMaxEye)) return false;
+        v.eye[k] = (double)gro[k];
+    }
+    v.gx0 = f.gx0; v.gdx = f.gdx; v.gy0 = f.gy0; v.gdy = f.gdy; v.gz = f.gz;
+    const double eps = 1e-5 * std::sqrt(f2 * g2);   // cond_F(invView3x3) >= 3 for any matrix, 3 for a rotation
+    const double err = eps * f.gmax2 / std::fabs(f.gz) / std::fmin(std::fabs(f.gdx), std::fabs(f.gdy));
+    v.margin_px = 1.5 + f.dev_px + err;
+    if (!(v.margin_px <= 16.0)) return false;
+    v.width = f.width; v.height = f.height;
+    v.tiles_x = (f.width + vrt::miss::kTile - 1) / vrt::miss::kTile;
+    v.tiles_y = (f.height + vrt::miss::kTile - 1) / vrt::miss::kTile;
+    return true;
 }
 
 }  // namespace vrt_internal

@@ -220,8 +220,13 @@ void vrt_destroy(vrt_ctx *c) {
         if (ln.done) (void)hipEventDestroy(ln.done);
     }
     for (auto &e : c->prof_events) (void)hipEventDestroy(e);
-    if (!c->ray_tables.empty()) (void)hipDeviceSynchronize();
+    if (!c->ray_tables.empty() || !c->miss_masks.empty() || c->occ.d_boxes) (void)hipDeviceSynchronize();
     for (auto &t : c->ray_tables) (void)hipFree(t.d_tab);
+    for (auto &m : c->miss_masks) {
+        (void)hipFree(m.d_mask);
+        if (m.built) (void)hipEventDestroy(m.built);
+    }
+    (void)hipFree(c->occ.d_boxes);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
