@@ -1,0 +1,638 @@
+"""A float64 restatement of pathTrace (shaders/raytracing.comp:435-622) in VRT_MODE_FULL, the whole ray tree (test helper,
+not a test).
+
+It reuses tests/shader_ref64.py's decoded grid, node-to-node step, floor rule and notInShadow, and follows the same
+independence rules: numpy and shader_ref64 only, nothing under oracle/ and nothing of the product's tracing
+(tests/test_shader_reference64.py enforces that for both modules).
+
+What is restated, from the GLSL:
+  * The ray stack (comp:451-470): a real LIFO of MAX_RAYS = 8 entries per pixel. Every pass pops the top ray of every
+    pixel whose stack is not empty and marches those rays together; pushes go on top, reflected ray before refracted.
+  * The initial ray (comp:443-462): the grid origin cameraPos * voxelScale, startIOF (the eye voxel's refraction when it is
+    in (0, 3), else 1), the eye voxel's colour and density a*5 as the medium (colour 1 when a == 0), colorTint =
+    globalLight, weight 1, depth 0.
+  * hitMarching (comp:248-330) from any origin with the ray's own rayIOF as the "air" refraction of the start.
+  * A miss (comp:480-495): at depth <= 0 the in-medium absorption exp(-density * distanceInMedium * (1 - mediumColor))
+    when distanceInMedium > 1e-6 and density > 0, then sky * globalLight; at depth > 0 sky * sunIntensity (3) / PI.
+  * A hit (comp:497-544): distanceInMedium += length(hitPoint / voxelScale - origin) / voxelScale (a world-space point
+    minus a grid-space origin, divided once more), the property overrides for a <= 0 (comp:503-504), surfaceColor,
+    n1 / n2, the absorption, the highlight inversion (alpha 1), the exit-side flip and swap when cosi > 0, GLSL refract
+    and reflect, Fresnel with a true pow, TIR as |refractDir| < 0.001, ndotl; the voxel ID and dist of the first
+    depth-0 hit with surfaceColor.a >= 1 while primaryVoxelID is still 0 (an ID-0 hit -- the origin voxel's +X face --
+    leaves it re-enterable), dist = int(length(hitPointWorld - cameraPos)).
+  * Glass (comp:546-572): the directly lit fall-back when the stack is full or an intensity is <= 0.001; otherwise the
+    reflected ray (hitPoint + N*1e-4, n1, weight*R if > 1e-4, the parent's distanceInMedium, the last voxel as medium)
+    and the refracted one (hitPoint - N*1e-4, n2, weight*(1-R), distance 0, the hit voxel as medium).
+  * Opaque (comp:573-618), also glass at depth > 0: emission * 10 at depth 0 and / PI deeper; at depth 0 the direct
+    term through notInShadow(hitPoint + N*2e-3); at depth > 0 ambient max(1 - exp(-distanceInMedium / 512), 0.01) / PI;
+    the bounce from hitPoint + N*0.1 with rayIOF n1, tint colorTint * surfaceColor, the last voxel as medium.
+  * initRNG / rand (comp:381-395) in exact uint32 arithmetic, seed x + y*1920 + 123456 + sampleIndex*78901 (mod 2^32);
+    rand() keeps its float32 conversion float(state) / 2^32 (it is part of the shader's definition, and may give 1.0).
+    cosineSampleHemisphere (comp:402-417) after it -- phi, sqrt, sin / cos, cross, normalize -- is float64.
+
+Two facts of the GLSL that the restatement shows rather than assumes: hitMarching's normal is -sign(d) on the axis
+crossed, so cosi = dot(d, normal) = -|d[axis]| < 0 at every hit and the exit-side flip and n1 / n2 swap (comp:522-526)
+never run -- n1 is the medium left and n2 the medium entered on both sides of glass already. And the swap test
+stackSize == MAX_RAYS (comp:548) follows a pop, so it is never true either; a full stack shows as a refracted ray that is
+not pushed (comp:565) after the reflected one took the last slot.
+
+Error model (the undecided rule of shader_ref64 carried into every ray of the tree; a pixel is undecided when any ray of
+its tree is, and decided pixels must match exactly: rgb bytes, ID and dist):
+  * Position. Each ray carries a per-axis bound on the float32 error of its position. A march adds shader_ref64's step
+    error plus dir_err * t. The coordinate a step crosses is computed, not carried: the float32 landing is
+    pos + d * ((P - pos) * (1 / d)), within 4u * (|P - pos| + err) of the node plane P before two roundings, whatever
+    pos's own error was, so the crossed coordinate's bound drops to that when no other coordinate is near a plane (the
+    axis is the same in float32); when 8u * (|P - pos| + err) is below half the float32 spacing at P the landing is P
+    itself and the pushed coordinate is exactly float32(P + s*1e-4), error 0. The bounds never drop below the ray's line
+    error lo3: its origin's bound, which the line keeps however often a coordinate lands on a plane.
+    A ray spawned at a hit starts at hitPoint + N * offset with the hit's error plus the rounding of the offset (u times
+    the coordinate). The reflected ray's origin along N is P + s*1e-4 - s*1e-4: within float32 rounding of the plane.
+    It is evaluated in float32 for every float32 landing within the error bound of P. When they all floor alike the
+    start voxel is decided and the spread of those origins is the error along N. When they do not, the start is either
+    the last voxel (A) or the hit voxel (B); B's first step goes back across P and is pushed 1e-4 into the last voxel,
+    and if that is no change of medium (comp:318-321 with rayIOF n1: a reflection inside glass off its face to air)
+    B is A's ray moved 1e-4 along N, so the ray is traced as A with 1e-4 more error along N; otherwise the ray is
+    undecided (a reflection seen from air after an approach step too long for the landing to be decided). A start
+    on the near side of P is locked there: the coordinate moves away from P monotonically, so that plane is not tested
+    again. The error along N shows in the other coordinates where the line crosses planes of N's axis, scaled by
+    |d_k / d_N|; the reflected ray's line error holds that.
+  * Direction. dir_err bounds the absolute error of each unit direction component beyond the primary ray's ~6u (which
+    shader_ref64's step error already holds): reflect is exact for an axis normal (the error stays the parent's);
+    refract adds 8u + 4u(1 + eta^2) / sqrt(k) and scales the parent's by eta + eta^2 |cos| / sqrt(k); a bounce has
+    E_SINCOS + 2*pi*u (phi's rounding) + 6u (sqrt, products, normalize). Components within max(DIR_MARGIN, 2 * dir_err)
+    of 0 are undecided.
+  * Colour. Each ray carries a relative error bound of weight * colorTint. A contribution adds the factors it multiplies
+    (<= 6u), E_EXP and the exponent's error (|arg| * 5u + density * (1 - mediumColor) * dist_err) where it absorbs, the
+    ambient's error (E_EXP * e + e * dist_err / 512 + 2u over its value), and a spawned ray adds Fresnel's absolute error
+    e_F (R0 * (8u + 4u(n1 + n2)/|n1 - n2|), E_POW * pow, 5 (1 - cos)^4 (dir_err + 8u)) over the intensity it takes.
+    The byte is undecided within EPS_COLOR + 255 * (sum of |contribution| * rel + (contributions + 1) * u * colour) of a
+    .5 tie. dist_err grows by the two endpoints' position errors and 4u of the coordinates per hit (over voxelScale).
+  * Thresholds a float32 run could land on the other side of: reflect / refract intensity within e_F of 0.001, the
+    reflected weight within its error of 1e-4, k within 6u(1 + eta^2) + 2 eta^2 |cos| dir_err of 0 (TIR: refract then
+    returns 0 and the < 0.001 length test follows it), |cosi| within dir_err + DIR_MARGIN of 0, distanceInMedium within
+    its error of 1e-6 where a medium absorbs, the primary cap (shader_ref64's 1000 of 1024 steps) for every ray and the
+    shadow cap (64) as in shader_ref64. The ambient's 0.01 kink is continuous (max is 1-Lipschitz), so it takes the same
+    value bound as the rest of the ambient.
+  * The det_* routines that stand in for exp, pow, sin and cos are held to these measured bounds on the shader's domains
+    (tests/test_path_reference64.py measures them on the oracle, tests/test_gpu_path_reference64.py on the device):
+    det_expf on [-87, 0]: relative 7.85e-8 (E_EXP = 1.2e-7; below -87 it returns 0, off by < 1.7e-38);
+    det_powf(x, 5) on [0, 1]: relative 8.66e-6 where x^5 >= 1.7e-38 (E_POW = 1.2e-5; absolute < 1.7e-38 below);
+    det_sinf / det_cosf on [0, 2 pi): absolute 6.82e-8 / 7.61e-8 (E_SINCOS = 1.2e-7).
+
+Not restated: the display pass of a mode-2 frame (shader_ref64.display covers quad.frag), jitter, the thin lens and the
+adaptive rule of the accumulation (each tied to its own restatement), INDIRECT_SAMPLES / BOUNCES other than 1.
+
+flaws= plants one plausible misreading at a time, so the tests can show that the comparison catches it."""
+import numpy as np
+
+import shader_ref64 as R
+
+U = R.U
+MAX_RAYS = 8
+E_EXP = 1.2e-7             # relative, det_expf on [-87, 0]
+E_POW = 1.2e-5             # relative, det_powf(x, 5) on [0, 1] where x^5 >= 1.7e-38
+E_POW_ABS = 1.7e-38
+E_SINCOS = 1.2e-7          # absolute, det_sinf / det_cosf on [0, 2 pi)
+BOUNCE_DIR_ERR = E_SINCOS + 2.0 * np.pi * U + 6.0 * U
+SUN = 3.0
+_M32 = (1 << 32) - 1
+_F1E4 = np.float32(1e-4)
+
+FLAWS = ("fifo", "exit_swap", "dim_no_scale", "bounce_offset", "no_pi_deep", "rng_row", "no_miss_absorption",
+         "id_reflect_first", "id_zero_locks")
+
+
+def _pcg(st):
+    """one step of initRNG / rand's hash (comp:385-387, 391-393) on uint32 values held in int64"""
+    st = (st * 747796405 + 2891336453) & _M32
+    word = (((st >> ((st >> 28) + 4)) ^ st) * 277803737) & _M32
+    return (word >> 22) ^ word
+
+
+def init_rng(xs, ys, sample, row=1920):
+    """initRNG (comp:381-388) -> rngState per pixel"""
+    seed = (np.asarray(xs, np.int64) + np.asarray(ys, np.int64) * row + 123456 + (int(sample) & _M32) * 78901) & _M32
+    return _pcg(seed)
+
+
+def rand(state):
+    """rand() (comp:390-395) -> (new state, the float32 value float(state) / 2^32 as float64)"""
+    state = _pcg(state)
+    return state, (state.astype(np.float64).astype(np.float32) / np.float32(4294967296.0)).astype(np.float64)
+
+
+def cosine_hemisphere(n, rx, ry):
+    """cosineSampleHemisphere (comp:402-417) in float64"""
+    phi = 2.0 * R.PI * ry
+    ct, st = np.sqrt(rx), np.sqrt(1.0 - rx)
+    x, z = st * np.cos(phi), st * np.sin(phi)
+    up = np.where((np.abs(n[:, 2]) < 0.999)[:, None], [0.0, 0.0, 1.0], [1.0, 0.0, 0.0])
+    t = np.cross(up, n)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(n, t)
+    r = t * x[:, None] + b * z[:, None] + n * ct[:, None]
+    return r / np.linalg.norm(r, axis=1, keepdims=True)
+
+
+def _spacing_below(P):
+    """the float32 spacing just below |P| (0 at P == 0)"""
+    a = np.abs(P).astype(np.float32)
+    return np.where(a > 0, a - np.nextafter(a, np.float32(0)), 0.0).astype(np.float64)
+
+
+def _reflect_origin(P, s, err, K=8):
+    """float32 hitPoint[axis] + normal[axis]*1e-4 of a reflected ray (comp:559): the landing L on the plane P, pushed by
+    s*1e-4 (comp:304), then moved back by the normal -s. Every float32 L within err of P is tried
+    -> (origin coordinate of L == P, alike: all of them floor alike, spread: bound on |origin - that coordinate|)"""
+    P32 = P.astype(np.float32)
+    s32 = s.astype(np.float32)
+
+    def origin(L):
+        L1 = (L + s32 * _F1E4).astype(np.float32)
+        return (L1 + (-s32) * _F1E4).astype(np.float32)
+
+    o0 = origin(P32)
+    f0 = np.floor(o0)
+    alike = np.ones(P.size, bool)
+    spread = np.zeros(P.size)
+    for direction in (np.float32(np.inf), np.float32(-np.inf)):
+        L = P32.copy()
+        for _ in range(K):
+            L = np.nextafter(L, direction)
+            inside = np.abs(L.astype(np.float64) - P) <= err
+            o = origin(L)
+            alike &= ~inside | (np.floor(o) == f0)
+            spread = np.where(inside, np.maximum(spread, np.abs(o.astype(np.float64) - o0)), spread)
+        more = np.abs(L.astype(np.float64) - P) <= err                        # more than K float32 values within err
+        alike &= ~more
+        spread = np.where(more, err + 4 * np.spacing(np.abs(P32)).astype(np.float64), spread)
+    return o0.astype(np.float64), alike, spread
+
+
+class _March:
+    pass
+
+
+def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
+    """hitMarching (comp:248-330) for rays from grid-space origins org[n, 3] (per-axis error err3) with rayIOF iof.
+    oax: an axis whose start floor is already decided (-1: none); lock_ax / lock_p: a coordinate that moves away from
+    the plane lock_p and cannot cross it again (-1: none); lo3: per-axis error the ray's line keeps however often a
+    coordinate lands on a plane (default: the origin's error). -> _March (hit, mp, pt, ax, hv, lv, err3, snap, P, amb)"""
+    n = org.shape[0]
+    m = _March()
+    m.amb = np.zeros(n, bool)
+    m.hit = np.zeros(n, bool)
+    m.mp = np.zeros((n, 3), np.int64)
+    m.pt = np.zeros((n, 3))
+    m.ax = np.zeros(n, np.int64)
+    m.hv = np.zeros(n, np.int64)
+    m.lv = np.zeros(n, np.int64)
+    m.err3 = err3.copy()
+    lo3 = err3 if lo3 is None else lo3
+    m.snap = np.zeros(n, bool)
+    m.P = np.zeros(n)
+    if not n:
+        return m
+    m.amb |= np.any((d != 0) & (np.abs(d) < np.maximum(R.DIR_MARGIN, 2.0 * dir_err)[:, None]), 1)
+    start = np.floor(org).astype(np.int64)
+    inw = w.in_world(start)
+    m.amb |= ~inw                                       # octreeFind's early return leaves the node box undefined (comp:143)
+    node = np.full(n, -1, np.int64)
+    node[inw] = w.find(start[inw])
+    margin = np.where(np.arange(3)[None] == oax[:, None], -1.0, R.DELTA_FLOOR + R.DELTA_SAFETY * err3)
+    near = (org != np.rint(org)) & (np.abs(org - np.rint(org)) < margin)
+    m.amb |= R._floor_undecided(w, org, start, node, near)
+    pos = org.copy()
+    inv = R._inv_dir(d)
+    steps = np.zeros(n, np.int64)
+    act = np.nonzero(~m.amb)[0]
+    for it in range(R.PRIMARY_CAP):
+        if not act.size:
+            break
+        cur = node[act]
+        new, ax, stuck, fr, t = R._step(w, pos[act], d[act], inv[act], cur, 1e-4)
+        r = np.arange(act.size)
+        dax = d[act][r, ax]
+        P = np.where(dax > 0, w.mx[cur][r, ax], w.mn[cur][r, ax]).astype(np.float64)
+        span = np.abs(P - pos[act][r, ax])
+        with np.errstate(invalid="ignore", over="ignore"):
+            e = m.err3[act] + (R._step_error(new, t) + dir_err[act] * np.abs(t))[:, None]
+        lk = lock_ax[act]
+        has = np.nonzero(lk >= 0)[0]
+        if has.size:
+            onp = np.rint(new[has, lk[has]]) == lock_p[act][has]
+            fr[has[onp], lk[has[onp]]] = np.inf
+        with np.errstate(invalid="ignore"):
+            mp = np.floor(np.clip(new, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
+        ax_in = (mp[r, ax] >= w.wmin[ax]) & (mp[r, ax] < w.wmax[ax])
+        go = w.in_world(mp) & ~stuck
+        nxt = np.full(act.size, -1, np.int64)
+        nxt[go] = w.find(mp[go])
+        near = (ax_in & ~stuck)[:, None] & (fr < R.DELTA_FLOOR + R.DELTA_SAFETY * e)
+        m.amb[act] |= R._floor_undecided(w, new, mp, nxt, near)
+        sn = (8.0 * U * (span + e[r, ax]) < _spacing_below(P) / 2) & ~near.any(1)
+        s32 = np.sign(dax).astype(np.float32)
+        new[sn, ax[sn]] = (P[sn].astype(np.float32) + s32[sn] * _F1E4).astype(np.float32)
+        # the crossed coordinate is the plane, computed: off by 4u |P - pos| and two roundings whatever pos's error was
+        e = np.maximum(e, lo3[act])
+        land = 4.0 * U * (span + e[r, ax]) + 2.0 * np.spacing(np.abs(P).astype(np.float32)).astype(np.float64)
+        dec_ax = ~near.any(1)
+        e[r[dec_ax], ax[dec_ax]] = np.minimum(e[r[dec_ax], ax[dec_ax]], land[dec_ax])
+        e[sn, ax[sn]] = 0.0
+        steps[act] = it + 1
+        pos[act], m.err3[act] = new, e
+        prev = cur
+        pr = np.where(w.refractive[prev], w.refr[prev], iof[act])              # comp:318
+        cr = np.where(w.refractive[np.maximum(nxt, 0)], w.refr[np.maximum(nxt, 0)], 1.0)   # comp:319
+        hit = go & (np.abs(cr - pr) > 1e-4)                                    # comp:321
+        h = act[hit]
+        m.hit[h] = True
+        m.mp[h], m.pt[h], m.ax[h] = mp[hit], new[hit], ax[hit]
+        m.hv[h], m.lv[h], m.snap[h], m.P[h] = nxt[hit], prev[hit], sn[hit], P[hit]
+        node[act] = nxt
+        act = act[go & ~hit]
+    m.amb[act] = True                                                          # capped while still moving
+    m.amb |= steps > R.PRIMARY_DECIDED_STEPS
+    return m
+
+
+_FIELDS = {"org": 3, "err3": 3, "lo3": 3, "d": 3, "dir_err": 0, "iof": 0, "w": 0, "tint": 3, "dim": 0, "edim": 0, "mc": 3, "md": 0,
+           "depth": 0, "rel": 0, "oax": 0, "lock_ax": 0, "lock_p": 0}
+_INT = ("depth", "oax", "lock_ax")
+STATS = ("rays", "peak_stack", "dropped_refract", "tir", "exit_glass", "deep_emission", "deep_sky", "miss_absorbed",
+         "hit_absorbed", "glass_hits", "deep_ambient", "id_zero_hit", "id_reentry")
+
+
+class PathTrace:
+    """pathTrace in VRT_MODE_FULL for every requested pixel at initRNG sample `sample`; frame() assembles the outputs."""
+
+    def __init__(self, world, inv_proj, inv_view, cam_pos, width, height, xs=None, ys=None, sample=0, voxel_scale=1.0,
+                 global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1), flaws=()):
+        assert light_dir is not None, "lightDir is a uniform: pass the host's float32 value"
+        unknown = set(flaws) - set(FLAWS) - set(R.FLAWS)
+        assert not unknown, unknown
+        self.w, self.flaws = world, frozenset(flaws)
+        self.W, self.H = int(width), int(height)
+        if xs is None:
+            ys, xs = np.mgrid[0:self.H, 0:self.W]
+        self.xs, self.ys = np.asarray(xs, np.int64).ravel(), np.asarray(ys, np.int64).ravel()
+        self.scale = float(np.float32(voxel_scale))
+        self.gl = np.array(global_light, np.float32).astype(np.float64)
+        self.L = np.array(light_dir, np.float32).astype(np.float64)
+        self.hl = np.array(highlighted, np.int64)
+        self.cam = np.array(cam_pos, np.float32).astype(np.float64)[:3]
+        P = np.array(inv_proj, np.float32).astype(np.float64).reshape(4, 4).T
+        Vw = np.array(inv_view, np.float32).astype(np.float64).reshape(4, 4).T
+        d = R.ray_dirs(P, Vw, self.xs, self.ys, self.W, self.H, "pixel_center" in self.flaws)
+        self.rng = init_rng(self.xs, self.ys, sample, self.W if "rng_row" in self.flaws else 1920)
+        self._run(d)
+
+    def _run(self, d):
+        w, n = self.w, d.shape[0]
+        self.amb = np.zeros(n, bool)
+        eye = self.cam * self.scale
+        emp = np.floor(eye).astype(np.int64)
+        if not w.in_world(emp):
+            raise ValueError("eye outside the world: octreeFind's early return leaves the node box undefined (comp:143)")
+        e = int(w.find(emp[None])[0])
+        p0 = w.p[e, 0] / 255.0 * 3.0
+        self.eye_node = e
+        S = {k: np.zeros((n, MAX_RAYS, c) if c else (n, MAX_RAYS), np.int64 if k in _INT else np.float64)
+             for k, c in _FIELDS.items()}
+        self.sp = np.ones(n, np.int64)
+        S["org"][:, 0] = eye
+        S["err3"][:, 0] = S["lo3"][:, 0] = U * np.abs(eye).max()
+        S["d"][:, 0] = d
+        S["iof"][:, 0] = p0 if 0.0 < p0 < 3.0 else 1.0                          # comp:448-449
+        S["w"][:, 0] = 1.0
+        S["tint"][:, 0] = self.gl[:3]
+        S["mc"][:, 0] = w.rgb[e] / 255.0 if w.a[e] > 0 else 1.0                  # comp:460
+        S["md"][:, 0] = w.a[e] / 255.0 * 5.0                                    # comp:461
+        S["oax"][:, 0] = S["lock_ax"][:, 0] = -1
+        self.S = S
+        self.fc = np.zeros((n, 3))
+        self.cerr = np.zeros((n, 3))
+        self.ncon = np.zeros(n, np.int64)
+        self.id = np.zeros(n, np.int64)
+        self.dist = np.full(n, int(w.wmax[0] - w.wmin[0]), np.int64)            # comp:441
+        self.und_dist = np.zeros(n, bool)
+        self.first_hit = np.zeros(n, bool)
+        self.stats = {k: np.zeros(n, np.int64) for k in STATS}
+        self.id_written = np.zeros(n, bool)
+        for _ in range(1024):
+            act = np.nonzero((self.sp > 0) & ~self.amb)[0]
+            if not act.size:
+                break
+            self._pass(act)
+        else:
+            raise AssertionError("a ray tree of more than 1024 rays")
+
+    # ---- one pass: the top ray of every pixel in act ----------------------------------------------------------------
+    def _pop(self, act):
+        S = self.S
+        if "fifo" in self.flaws:
+            ray = {k: v[act, 0].copy() for k, v in S.items()}
+            for v in S.values():
+                v[act, :-1] = v[act, 1:]
+            self.sp[act] -= 1
+        else:
+            self.sp[act] -= 1
+            ray = {k: v[act, self.sp[act]].copy() for k, v in S.items()}
+        return ray
+
+    def _push(self, idx, **f):
+        sl = self.sp[idx]
+        assert np.all(sl < MAX_RAYS)
+        for k, v in f.items():
+            self.S[k][idx, sl] = v
+        self.sp[idx] += 1
+        self.stats["peak_stack"][idx] = np.maximum(self.stats["peak_stack"][idx], self.sp[idx])
+
+    def _add(self, idx, c, rel):
+        self.fc[idx] += c
+        self.cerr[idx] += c * rel[:, None]
+        self.ncon[idx] += 1
+
+    def _pass(self, act):
+        w, fl = self.w, self.flaws
+        r = self._pop(act)
+        self.stats["rays"][act] += 1
+        m = march(w, r["org"], r["err3"], r["d"], r["dir_err"], r["iof"], r["oax"], r["lock_ax"], r["lock_p"], r["lo3"])
+        self.amb[act] |= m.amb
+        one = self.stats["rays"][act] == 1                                          # the primary ray
+        self.first_hit[act[one]] = m.hit[one]
+        ok = ~m.amb
+        tint, wt, depth = r["tint"], r["w"], r["depth"]
+        deep_pi = 1.0 if "no_pi_deep" in fl else R.PI
+
+        # ---- misses (comp:480-495) ----
+        mi = np.nonzero(ok & ~m.hit)[0]
+        if mi.size:
+            tc = tint[mi].copy()
+            rel = r["rel"][mi] + 6 * U
+            shallow = depth[mi] <= 0
+            ab = shallow & (r["dim"][mi] > 1e-6) & (r["md"][mi] > 0.0) & ("no_miss_absorption" not in fl)
+            self.amb[act[mi]] |= shallow & (r["md"][mi] > 0) & (np.abs(r["dim"][mi] - 1e-6) <= r["edim"][mi])
+            if ab.any():
+                f, e = self._absorb(r["md"][mi[ab]], r["dim"][mi[ab]], r["edim"][mi[ab]], r["mc"][mi[ab]])
+                tc[ab] *= f
+                rel[ab] += e
+                self.stats["miss_absorbed"][act[mi[ab]]] += 1
+            c = np.where(shallow[:, None], self.gl[:3] * R.SKY * tc * wt[mi, None], tc * R.SKY * SUN * wt[mi, None] / deep_pi)
+            # sky seen by an exact ray (rel 0): the float32 products of comp:489 may be exact too (a white globalLight)
+            f32 = ((self.gl[:3].astype(np.float32) * R.SKY.astype(np.float32)) * tc.astype(np.float32)) * wt[mi, None].astype(np.float32)
+            exact = shallow & ~ab & (r["rel"][mi] == 0) & np.all(f32.astype(np.float64) == c, 1)
+            rel[exact] = 0.0
+            self._add(act[mi], c, rel)
+            self.stats["deep_sky"][act[mi[~shallow]]] += 1
+
+        # ---- hits ----
+        hi = np.nonzero(ok & m.hit)[0]
+        if not hi.size:
+            return
+        idx = act[hi]
+        k = hi.size
+        kr = np.arange(k)
+        org, d, dep = r["org"][hi], r["d"][hi], depth[hi]
+        derr = r["dir_err"][hi] + 8 * U
+        hv, lv, ax, pt, mp = m.hv[hi], m.lv[hi], m.ax[hi], m.pt[hi], m.mp[hi]
+        perr = m.err3[hi]
+        s = -np.sign(d[kr, ax])                                                  # comp:294
+        normal = np.zeros((k, 3))
+        normal[kr, ax] = s
+        hpw = pt / self.scale                                                    # comp:498
+        ln = np.linalg.norm(hpw - org, axis=1)
+        dim = r["dim"][hi] + (ln if "dim_no_scale" in fl else ln / self.scale)  # comp:501
+        edim = r["edim"][hi] + (perr.max(1) + r["err3"][hi].max(1) + 4 * U * (np.abs(hpw).max(1) + np.abs(org).max(1) + ln)) / self.scale
+        hva, lva = w.a[hv] > 0, w.a[lv] > 0
+        n2 = np.where(w.refractive[hv], w.refr[hv], 1.0)                         # comp:503, 507
+        n1 = np.where(w.refractive[lv], w.refr[lv], 1.0)                         # comp:504, 508
+        sc = np.where(hva[:, None], w.rgb[hv], w.rgb[lv]) / 255.0               # comp:506
+        sa = np.where(hva, w.a[hv], w.a[lv]) / 255.0
+        lv_rgb, lv_md = w.rgb[lv] / 255.0, w.a[lv] / 255.0 * 5.0
+        hv_rgb, hv_md = w.rgb[hv] / 255.0, w.a[hv] / 255.0 * 5.0
+        tc = tint[hi].copy()
+        rel = r["rel"][hi].copy()
+        md, mc = r["md"][hi], r["mc"][hi]
+        self.amb[idx] |= (md > 0) & (np.abs(dim - 1e-6) <= edim)
+        ab = (dim > 1e-6) & (md > 0.0)                                           # comp:512-516
+        if ab.any():
+            f, e = self._absorb(md[ab], dim[ab], edim[ab], mc[ab])
+            tc[ab] *= f
+            rel[ab] += e
+            self.stats["hit_absorbed"][idx[ab]] += 1
+        hl = np.all(mp == self.hl, 1)                                            # comp:518-520
+        sc[hl] = 1.0 - sc[hl]
+        sa[hl] = 1.0
+        cosi = np.einsum("ij,ij->i", d, normal)                                  # comp:522-526
+        self.amb[idx] |= np.abs(cosi) < r["dir_err"][hi] + R.DIR_MARGIN
+        flip = cosi > 0
+        normal[flip] = -normal[flip]
+        swap = flip | (("exit_swap" in fl) & (n1 > n2))
+        n1, n2 = np.where(swap, n2, n1), np.where(swap, n1, n2)
+        eta = n1 / n2                                                            # GLSL refract
+        dd = np.einsum("ij,ij->i", normal, d)
+        kk = 1.0 - eta * eta * (1.0 - dd * dd)
+        tir = kk < 0.0                                                           # refract returns 0: |0| < 0.001
+        sq = np.sqrt(np.maximum(kk, 0.0))
+        refr = eta[:, None] * d - (eta * dd + sq)[:, None] * normal
+        refr[tir] = 0.0
+        R0 = (n1 - n2) / (n1 + n2) * (n1 - n2) / (n1 + n2)                       # comp:529-531
+        cos_t = np.maximum(0.0, -dd)
+        pw = (1.0 - cos_t) ** 5
+        fres = np.clip(R0 + (1.0 - R0) * pw, 0.0, 1.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            e_f = (R0 * (8 * U + 4 * U * (n1 + n2) / np.where(n1 != n2, np.abs(n1 - n2), 1.0)) + E_POW * pw + E_POW_ABS
+                   + 5.0 * (1.0 - cos_t) ** 4 * derr + 3 * U)
+        refl_i = fres
+        refr_i = np.where(tir, 0.0, 1.0 - fres)
+        ndotl = np.maximum(normal @ self.L, 0.0)                                 # comp:537
+
+        # ---- voxel ID and dist (comp:539-544) ----
+        open_id = ~self.id_written[idx] if "id_zero_locks" in fl else self.id[idx] == 0
+        idset = (dep == 0) & open_id & (sa >= 1.0)
+        if idset.any():
+            j = idx[idset]
+            self.stats["id_reentry"][j] += self.stats["id_zero_hit"][j] > 0       # an earlier ID-0 hit left it open
+            self.id_written[j] = True
+            lin = mp[idset, 0] + w.tex_dim * (mp[idset, 1] + w.tex_dim * mp[idset, 2])
+            face = ax[idset] * 2 + np.where(s[idset] > 0, 0, 1)
+            if "face_order" in fl:
+                face ^= 1
+            self.id[j] = ((lin * 6 + face + (1 << 31)) % (1 << 32)) - (1 << 31)
+            lc = np.linalg.norm(hpw[idset] - self.cam, axis=1)
+            self.dist[j] = np.trunc(lc)
+            margin = (R.DELTA_FLOOR + R.DELTA_SAFETY * perr[idset].max(1)) / self.scale + 4 * U * lc
+            self.und_dist[j] = np.abs(lc - np.rint(lc)) < margin
+            self.stats["id_zero_hit"][j] += self.id[j] == 0
+
+        # ---- glass at depth <= 0 (comp:547-572) ----
+        glass = (dep <= 0) & (sa < 1.0)
+        g = np.nonzero(glass)[0]
+        if g.size:
+            gi = idx[g]
+            self.stats["glass_hits"][gi] += 1
+            self.stats["tir"][gi] += tir[g]
+            self.stats["exit_glass"][gi] += n1[g] > n2[g]
+            sp = self.sp[gi]
+            wg = r["w"][hi][g]
+            rw = wg * refl_i[g]
+            und = (np.abs(refl_i[g] - 0.001) <= e_f[g]) | (~tir[g] & (np.abs(refr_i[g] - 0.001) <= e_f[g]))
+            und |= np.abs(kk[g]) <= 6 * U * (1 + eta[g] ** 2) + 2 * eta[g] ** 2 * np.abs(dd[g]) * derr[g]
+            und |= np.abs(rw - 1e-4) <= wg * e_f[g] + rw * (rel[g] + 2 * U)
+            self.amb[gi] |= und
+            fall = (sp == MAX_RAYS) | (refl_i[g] <= 0.001) | (refr_i[g] <= 0.001)
+            fb = g[fall]
+            if fb.size:
+                c = tc[fb] * (sc[fb] * (self.gl[:3] * ndotl[fb, None])) * r["w"][hi][fb, None]
+                self._add(idx[fb], c, rel[fb] + 5 * U)
+            sp_g = g[~fall]
+            if sp_g.size:
+                self._spawn_glass(idx[sp_g], d=d[sp_g], normal=normal[sp_g], pt=pt[sp_g], perr=perr[sp_g], ax=ax[sp_g],
+                                  P=m.P[hi[sp_g]], hv=hv[sp_g], lv=lv[sp_g], iof=r["iof"][hi[sp_g]], w=r["w"][hi[sp_g]],
+                                  rel=rel[sp_g], tc=tc[sp_g], fres=fres[sp_g], e_f=e_f[sp_g], n1=n1[sp_g], n2=n2[sp_g],
+                                  dep=dep[sp_g], tir=tir[sp_g], refr=refr[sp_g], eta=eta[sp_g], dd=dd[sp_g], kk=kk[sp_g],
+                                  dir_err=r["dir_err"][hi[sp_g]], dim=dim[sp_g], edim=edim[sp_g], lv_rgb=lv_rgb[sp_g],
+                                  lv_md=lv_md[sp_g], hv_rgb=hv_rgb[sp_g], hv_md=hv_md[sp_g])
+        # ---- opaque, and glass deeper (comp:573-618) ----
+        o = np.nonzero(~glass)[0]
+        if not o.size:
+            return
+        em = np.where(hva[o], w.p[hv[o], 1] / 255.0, 0.0) * 10.0                 # comp:575
+        wo = r["w"][hi][o]
+        base = sc[o] * tc[o] * wo[:, None]
+        e0 = (em > 0) & (dep[o] == 0)
+        e1 = (em > 0) & (dep[o] != 0)
+        if e0.any():
+            self._add(idx[o[e0]], base[e0] * em[e0, None], rel[o[e0]] + 5 * U)
+        if e1.any():
+            self._add(idx[o[e1]], base[e1] * em[e1, None] / deep_pi, rel[o[e1]] + 6 * U)
+            self.stats["deep_emission"][idx[o[e1]]] += 1
+        deep = (em <= 0) & (dep[o] != 0)
+        if deep.any():
+            q = o[deep]
+            ex = np.exp(-dim[q] / 512.0)
+            amb_c = np.maximum(1.0 - ex, 0.01)
+            e_amb = E_EXP * ex + ex * (edim[q] + 2 * U * dim[q]) / 512.0 + 2 * U
+            self._add(idx[q], base[deep] * amb_c[:, None] / deep_pi, rel[q] + e_amb / amb_c + 6 * U)
+            self.stats["deep_ambient"][idx[q]] += 1
+        top = (em <= 0) & (dep[o] == 0)
+        if top.any():
+            q = o[top]
+            lit, samb = R.not_in_shadow(w, pt[q], normal[q], perr[q].max(1), self.L, self.flaws)
+            self.amb[idx[q]] |= samb
+            c = (self.gl[:3] * (lit * ndotl[q])[:, None]) * sc[q] * tc[q] * r["w"][hi][q, None] / R.PI
+            self._add(idx[q], c, rel[q] + 6 * U)
+            b = q[(self.sp[idx[q]] < MAX_RAYS) & (dep[q] <= 1)]                 # comp:597
+            if b.size:
+                bi = idx[b]
+                st = self.rng[bi]
+                st, rx = rand(st)
+                st, ry = rand(st)
+                self.rng[bi] = st
+                bd = cosine_hemisphere(normal[b], rx, ry)
+                off = 1e-4 if "bounce_offset" in fl else 1e-1
+                o_ = pt[b] + normal[b] * off
+                self._push(bi, org=o_, err3=perr[b] + U * np.abs(o_), lo3=perr[b] + U * np.abs(o_), d=bd, dir_err=np.full(b.size, BOUNCE_DIR_ERR),
+                           iof=n1[b], w=r["w"][hi][b], tint=tc[b] * sc[b], dim=0.0, edim=0.0, mc=lv_rgb[b], md=lv_md[b],
+                           depth=dep[b] + 1, rel=rel[b] + 2 * U, oax=-1, lock_ax=-1, lock_p=0.0)
+
+    def _spawn_glass(self, gi, d, normal, pt, perr, ax, P, hv, lv, iof, w, rel, tc, fres, e_f, n1, n2, dep, tir, refr, eta,
+                     dd, kk, dir_err, dim, edim, lv_rgb, lv_md, hv_rgb, hv_md):
+        """push the reflected and the refracted ray of the glass hits of pixels gi (comp:555-571); every array has one
+        row per pixel: the hit (point, normal after the flip, error, axis, plane P, hit and last voxel), the popped ray
+        (rayIOF, weight, direction error, distanceInMedium) and what comp:497-537 made of them"""
+        kr = np.arange(gi.size)
+        s = np.sign(d[kr, ax])
+        Wd = self.w
+
+        def reflect(sel):
+            if not sel.any():
+                return
+            q = np.nonzero(sel)[0]
+            rw = w[q] * fres[q]
+            q, rw = q[rw > 1e-4], rw[rw > 1e-4]                                   # comp:557
+            if not q.size:
+                return
+            qr, aq = np.arange(q.size), ax[q]
+            o = pt[q] + normal[q] * 1e-4
+            oc, alike, spread = _reflect_origin(P[q], s[q], perr[q, aq])
+            # The start voxel is the last voxel (A: the near side of P) or the hit voxel (B). When the float32 landings
+            # disagree, B is still A's tree if B's first step -- back across P, pushed 1e-4 into the last voxel -- is no
+            # change of medium (comp:318-321 with rayIOF n1): then B is A's ray moved 1e-4 along the axis.
+            prev_b = np.where(Wd.refractive[hv[q]], Wd.refr[hv[q]], n1[q])
+            cur_b = np.where(Wd.refractive[lv[q]], Wd.refr[lv[q]], 1.0)
+            same = np.abs(cur_b - prev_b) <= 1e-4
+            near_side = np.nextafter(P[q].astype(np.float32), (P[q] - s[q]).astype(np.float32)).astype(np.float64)
+            use_a = ~alike & same
+            oc = np.where(use_a, near_side, oc)
+            spread = np.where(use_a, spread + 1e-4 + 2 * np.abs(near_side - P[q]), spread)
+            o[qr, aq] = oc
+            self.amb[gi[q]] |= ~alike & ~same
+            away = np.floor(oc) != np.floor(pt[q, aq])                           # started on the near side of P
+            rd = d[q] - 2.0 * dd[q, None] * normal[q]
+            e3 = perr[q] + U * np.abs(o)
+            e3[qr, aq] = spread
+            # the line's offset along the axis shows in the other coordinates where it crosses planes of that axis
+            with np.errstate(divide="ignore", invalid="ignore"):
+                e3 += spread[:, None] * np.abs(rd / rd[qr, aq][:, None])
+            e3[qr, aq] = spread
+            self._push(gi[q], org=o, err3=e3, lo3=e3, d=rd, dir_err=dir_err[q], iof=n1[q], w=rw, tint=tc[q], dim=dim[q],
+                       edim=edim[q], mc=lv_rgb[q], md=lv_md[q], depth=dep[q],
+                       rel=rel[q] + e_f[q] / np.maximum(fres[q], 1e-30) + 2 * U, oax=aq,
+                       lock_ax=np.where(away, aq, -1), lock_p=P[q])
+
+        def refract(sel):
+            q = np.nonzero(sel & (self.sp[gi] < MAX_RAYS) & ~tir)[0]
+            self.stats["dropped_refract"][gi[sel & (self.sp[gi] >= MAX_RAYS) & ~tir]] += 1
+            if not q.size:
+                return
+            o = pt[q] - normal[q] * 1e-4
+            sq = np.sqrt(kk[q])
+            de = dir_err[q] * (eta[q] + eta[q] ** 2 * np.abs(dd[q]) / sq) + 8 * U + 4 * U * (1 + eta[q] ** 2) / sq
+            self._push(gi[q], org=o, err3=perr[q] + U * np.abs(o), lo3=perr[q] + U * np.abs(o), d=refr[q] / np.linalg.norm(refr[q], axis=1, keepdims=True),
+                       dir_err=de, iof=n2[q], w=w[q] * (1.0 - fres[q]), tint=tc[q], dim=0.0, edim=0.0, mc=hv_rgb[q],
+                       md=hv_md[q], depth=dep[q], rel=rel[q] + e_f[q] / np.maximum(1.0 - fres[q], 1e-30) + 2 * U, oax=-1,
+                       lock_ax=-1, lock_p=0.0)
+
+        first = np.ones(gi.size, bool)
+        if "id_reflect_first" in self.flaws:
+            refract(first)
+            reflect(self.sp[gi] < MAX_RAYS)
+        else:
+            reflect(self.sp[gi] < MAX_RAYS)                                      # comp:555
+            refract(first)                                                       # comp:565
+
+    def _absorb(self, md, dim, edim, mc):
+        """exp(-density * distanceInMedium * (1 - mediumColor)) -> (factor[k, 3], relative error bound[k])"""
+        arg = -md[:, None] * dim[:, None] * (1.0 - mc)
+        e = np.abs(arg) * 5 * U + md[:, None] * (1.0 - mc) * edim[:, None] + E_EXP
+        return np.exp(arg), e.max(1)
+
+    def frame(self):
+        """-> shader_ref64.Frame of mode 2 with every field decided or not"""
+        n = self.xs.size
+        f = PathFrame(self.xs, self.ys, 2)
+        f.id, f.dist = self.id.copy(), self.dist.copy()
+        x = np.clip(self.fc, 0.0, 1.0) * 255.0
+        f.rgba = np.concatenate([np.rint(x), np.full((n, 1), 255.0)], 1).astype(np.int64)
+        eps = R.EPS_COLOR + 255.0 * (self.cerr + (self.ncon + 1)[:, None] * U * self.fc)
+        eps[(self.ncon == 1) & (self.cerr == 0).all(1)] = 0.0                      # one exact term: rint's ties-to-even
+        tie = np.abs(x - np.floor(x) - 0.5) < eps
+        f.hit = self.first_hit.copy()
+        f.kind = np.where(self.first_hit, R.KIND_OPAQUE, R.KIND_SKY)
+        f.dec_id = ~self.amb
+        f.dec_dist = f.dec_id & ~self.und_dist
+        f.dec_rgb = (~self.amb)[:, None] & ~tie
+        f.stats = {k: v.copy() for k, v in self.stats.items()}
+        return f
+
+
+class PathFrame(R.Frame):
+    def hit_undecided_share(self):
+        """of the pixels whose primary ray hits: not every field decided"""
+        full = self.dec_id & self.dec_dist & self.dec_rgb.all(1)
+        return float((~full[self.hit]).mean()) if self.hit.any() else 0.0
+
+    def undecided_share(self):
+        return float((~(self.dec_id & self.dec_dist & self.dec_rgb.all(1))).mean())

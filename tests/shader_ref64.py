@@ -19,7 +19,8 @@ What is restated, from the GLSL:
     forcing alpha to 1, voxelID = toLinear(mapPos)*6 + getFaceIndex(hitNormal) only when surfaceColor.a >= 1,
     dist = int(length(hitPoint/voxelScale - cameraPos)); colour of the primary ray for VRT_MODE_PRIMARY (0) and
     VRT_MODE_PRIMARY_SHADOW (1); in VRT_MODE_FULL (2) only what the first hit decides (id/dist of an opaque first hit,
-    sky and emissive colour). Not restated: the bounce colour, in-medium absorption (exp) and the glass stack.
+    sky and emissive colour). The whole mode-2 ray tree -- bounce colour, in-medium absorption (exp), the glass
+    stack -- is restated by tests/path_ref64.py on top of this module.
   * quad.frag: the ID-aware box blur at chosen pixels.
 
 Undecided pixels. A pixel is left out of a comparison when float32 rounding in the shader could change the answer:
@@ -259,6 +260,67 @@ def _floor_undecided(world, new, mp, node, near):
     return und
 
 
+def ray_dirs(P, Vw, xs, ys, W, H, pixel_center=False):
+    """comp:631-638: the float64 world direction of pixels (xs, ys) from the float32 camera block (P, Vw: row-major 4x4)"""
+    off = 0.5 if pixel_center else 0.0
+    u = (xs + off) / W * 2.0 - 1.0
+    v = (ys + off) / H * 2.0 - 1.0
+    clip = np.stack([u, v, -np.ones_like(u), np.ones_like(u)], 1)
+    view = clip @ P.T
+    w = view[:, 3:4]
+    view = np.where(np.abs(w) > 1e-6, view / np.where(w == 0, 1.0, w), view)
+    vd = view[:, :3] / np.linalg.norm(view[:, :3], axis=1, keepdims=True)
+    wd = np.concatenate([vd, np.zeros_like(u)[:, None]], 1) @ Vw.T
+    return wd[:, :3] / np.linalg.norm(wd[:, :3], axis=1, keepdims=True)
+
+
+def not_in_shadow(w, pt, normal, err, L, flaws=()):
+    """notInShadow (comp:333-377) from hit points pt[n, 3] with axis normals normal[n, 3] (origin pt + normal*2e-3) and
+    float32 position error bounds err[n] -> (lit bool[n], undecided bool[n])"""
+    n = pt.shape[0]
+    lit = np.ones(n, bool)
+    amb = np.zeros(n, bool)
+    if not n:
+        return lit, amb
+    pos = pt + normal * 2e-3
+    err = np.asarray(err, np.float64).copy()
+    d = np.broadcast_to(L, pos.shape).copy()
+    inv = _inv_dir(d)
+    mp = np.floor(pos).astype(np.int64)
+    assert np.all(w.in_world(mp))
+    near = np.abs(pos - np.rint(pos))[np.abs(normal) > 0] < 2.5e-4            # the offset origin, along the normal
+    amb[near] = True
+    occluder = (w.a > 25) if "emissive_shadows" in flaws else ((w.a > 25) & (w.p[:, 1] == 0))   # comp:355
+    cap = 1 << 16 if "no_shadow_cap" in flaws else SHADOW_CAP
+    act = np.arange(n)
+    node = w.find(mp)
+    for k in range(1, cap + SHADOW_CAP_MARGIN + 1):                             # k: the octreeFind just made
+        if not act.size:
+            break
+        occ = occluder[node]
+        o = act[occ]
+        lit[o] = k > cap
+        amb[o] |= abs(k - (cap + 0.5)) < SHADOW_CAP_MARGIN
+        act, node = act[~occ], node[~occ]
+        new, ax, stuck, fr, t = _step(w, pos[act], d[act], inv[act], node, 1e-3)
+        err[act] += _step_error(new, t)
+        margin = DELTA_FLOOR + DELTA_SAFETY * err[act]
+        with np.errstate(invalid="ignore"):
+            m = np.floor(np.clip(new, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
+        r = np.arange(act.size)
+        ax_in = (m[r, ax] >= w.wmin[ax]) & (m[r, ax] < w.wmax[ax])
+        go = w.in_world(m)                                                     # comp:374
+        nn = np.full(act.size, -1, np.int64)
+        nn[go] = w.find(m[go])
+        if k <= cap:
+            near = (ax_in & ~stuck)[:, None] & (fr < margin[:, None])
+            amb[act] |= _floor_undecided(w, new, m, nn, near)
+        pos[act], mp[act] = new, m
+        act, node = act[go], nn[go]
+    # rays still inside after cap + margin finds are lit by the cap (lit stays True)
+    return lit, amb
+
+
 class Trace:
     """The first hit of every requested pixel (and its shadow ray), from which frame(mode) assembles the outputs."""
 
@@ -283,19 +345,8 @@ class Trace:
         self._shadow()
 
     def _rays(self, P, Vw):
-        """comp:631-638"""
-        off = 0.5 if "pixel_center" in self.flaws else 0.0
-        u = (self.xs + off) / self.W * 2.0 - 1.0
-        v = (self.ys + off) / self.H * 2.0 - 1.0
-        clip = np.stack([u, v, -np.ones_like(u), np.ones_like(u)], 1)
-        view = clip @ P.T
-        w = view[:, 3:4]
-        view = np.where(np.abs(w) > 1e-6, view / np.where(w == 0, 1.0, w), view)
-        vd = view[:, :3] / np.linalg.norm(view[:, :3], axis=1, keepdims=True)
-        wd = np.concatenate([vd, np.zeros_like(u)[:, None]], 1) @ Vw.T
-        d = wd[:, :3] / np.linalg.norm(wd[:, :3], axis=1, keepdims=True)
-        self.d = d
-        self.amb = np.any((d != 0) & (np.abs(d) < DIR_MARGIN), 1)
+        self.d = ray_dirs(P, Vw, self.xs, self.ys, self.W, self.H, "pixel_center" in self.flaws)
+        self.amb = np.any((self.d != 0) & (np.abs(self.d) < DIR_MARGIN), 1)
 
     def _primary(self):
         """pathTrace's first hitMarching (comp:443-478) for every ray"""
@@ -379,51 +430,13 @@ class Trace:
 
     def _shadow(self):
         """notInShadow (comp:333-377) from every opaque, non-emissive first hit"""
-        w = self.w
         n = self.d.shape[0]
         self.lit = np.ones(n, bool)
         self.shadow_amb = np.zeros(n, bool)
         i, rgb, a, emission, normal, ndotl, _, _ = self._surface()
         need = (a >= 1.0) & (emission <= 0.0)
         i, normal = i[need], normal[need]
-        if not i.size:
-            return
-        pos = self.pt[i] + normal * 2e-3
-        err = self.err[i].copy()
-        d = np.broadcast_to(self.L, pos.shape).copy()
-        inv = _inv_dir(d)
-        mp = np.floor(pos).astype(np.int64)
-        assert np.all(w.in_world(mp))
-        near = np.abs(pos - np.rint(pos))[np.abs(normal) > 0] < 2.5e-4        # the offset origin, along the normal
-        self.shadow_amb[i[near]] = True
-        occluder = (w.a > 25) if "emissive_shadows" in self.flaws else ((w.a > 25) & (w.p[:, 1] == 0))   # comp:355
-        cap = 1 << 16 if "no_shadow_cap" in self.flaws else SHADOW_CAP
-        act = np.arange(i.size)
-        node = w.find(mp)
-        for k in range(1, cap + SHADOW_CAP_MARGIN + 1):                         # k: the octreeFind just made
-            if not act.size:
-                break
-            occ = occluder[node]
-            o = act[occ]
-            self.lit[i[o]] = k > cap
-            self.shadow_amb[i[o]] |= abs(k - (cap + 0.5)) < SHADOW_CAP_MARGIN
-            act, node = act[~occ], node[~occ]
-            new, ax, stuck, fr, t = _step(w, pos[act], d[act], inv[act], node, 1e-3)
-            err[act] += _step_error(new, t)
-            margin = DELTA_FLOOR + DELTA_SAFETY * err[act]
-            with np.errstate(invalid="ignore"):
-                m = np.floor(np.clip(new, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
-            r = np.arange(act.size)
-            ax_in = (m[r, ax] >= w.wmin[ax]) & (m[r, ax] < w.wmax[ax])
-            go = w.in_world(m)                                                 # comp:374
-            nn = np.full(act.size, -1, np.int64)
-            nn[go] = w.find(m[go])
-            if k <= cap:
-                near = (ax_in & ~stuck)[:, None] & (fr < margin[:, None])
-                self.shadow_amb[i[act]] |= _floor_undecided(w, new, m, nn, near)
-            pos[act], mp[act] = new, m
-            act, node = act[go], nn[go]
-        # rays still inside after cap + margin finds are lit by the cap (self.lit stays True)
+        self.lit[i], self.shadow_amb[i] = not_in_shadow(self.w, self.pt[i], normal, self.err[i], self.L, self.flaws)
 
     def frame(self, mode):
         """-> Frame for VRT_MODE_PRIMARY (0), VRT_MODE_PRIMARY_SHADOW (1) or VRT_MODE_FULL (2)"""
