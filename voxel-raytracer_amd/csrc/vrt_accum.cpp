@@ -1,10 +1,9 @@
 // vrt_accum.cpp -- progressive multi-sample accumulation (include/vrt.h vrt_accum_*): call-order checks, the restart rule, the
 // context's buffers, the resolve and the display pass on it. The samples themselves are enqueued by the dispatcher
-// (vrt_dispatch.cpp enqueue() with an AccumStep), which chooses between the sample-looped bounce and the general kernel
-// (vrt_accum.hip.h) -- or, for jittered samples, their jittered forms and the sample-looped primary kernels (vrt_jitter.hip.h) --
-// as it chooses between the forms of a frame. A jittered accumulation, or one of VRT_MODE_PRIMARY / _SHADOW, first renders the
-// mode's ordinary frame once: its id_dist is the resolve's, and without jitter its bytes are every sample's. So does one with a
-// thin lens (vrt_set_lens, aperture > 0), whose samples the dispatcher enqueues as the lens kernels (vrt_lens.hip.h).
+// (vrt_dispatch.cpp enqueue() with an AccumStep), which picks the kernel of vrt_accum.hip.h -- by the sample's ray source
+// (corner, jitter or thin lens) and the shape the mode and scene allow -- as it chooses between the forms of a frame. A jittered
+// accumulation, or one of VRT_MODE_PRIMARY / _SHADOW, first renders the mode's ordinary frame once: its id_dist is the resolve's,
+// and without jitter its bytes are every sample's. So does one with a thin lens (vrt_set_lens, aperture > 0).
 // An adaptive accumulation (vrt_accum_begin_adaptive) adds rounds instead of samples: the same paths with the kernels' adaptive
 // forms, its per-pixel counts and Q beside the sums, the resolve by each pixel's count, and vrt_accum_counts.
 #include "vrt_internal.h"

@@ -1,4 +1,4 @@
-// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h, vrt_jitter.hip.h, vrt_lens.hip.h), shared by the host side (vrt_accum.cpp,
+// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h), shared by the host side (vrt_accum.cpp,
 // vrt_dispatch.cpp) and the launch file (vrt_launch_accum.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,7 +30,7 @@ struct Resolve {
     uint32_t pixels;
 };
 
-// A mode without jitter (vrt_jitter.hip.h repeat_kernel): n more samples that are all the frame in frame_rgba.
+// A mode without jitter or lens (vrt_accum.hip.h repeat_kernel): n more samples that are all the frame in frame_rgba.
 struct Repeat {
     const uint32_t *frame_rgba;
     uint32_t *sums;
@@ -96,6 +96,10 @@ struct RepeatAdapt : Repeat {
     uint64_t *sq;
     uint32_t min;
 };
+
+// Where a sample's ray comes from (vrt_accum.hip.h CornerSource, JitterSource, LensSource): the pixel's corner, the jittered ray
+// of VRT_ACCUM_JITTER, or a thin lens (Lens).
+enum class Source { kCorner, kJitter, kLens };
 
 // A thin lens (vrt_lens.hip.h, include/vrt.h vrt_set_lens), the fourth argument of the lens kernels.
 struct Lens {

@@ -1,25 +1,35 @@
-// vrt_accum.hip.h -- progressive multi-sample accumulation of VRT_MODE_FULL (include/vrt.h vrt_accum_*). Sample k of a pixel is
-// the frame the shader renders with initRNG(pixel, k) (comp:380-387; comp:629 itself passes 0): the same camera, uniforms and
-// tree, only the random numbers differ. An accumulation keeps, per pixel and channel, the integer sum of the unorm8 bytes each
-// sample would store -- exact and independent of the order of the adds -- and resolves it to (sum + n / 2) / n.
+// vrt_accum.hip.h -- the progressive accumulation's kernels (include/vrt.h vrt_accum_*). Sample k of a pixel is the frame of the
+// accumulation's mode rendered with initRNG(pixel, k) (comp:380-387; comp:629 itself passes 0) from the sample's ray: the same
+// camera, uniforms and tree, only the random numbers and the ray differ. An accumulation keeps, per pixel and channel, the integer
+// sum of the unorm8 bytes each sample would store -- exact and independent of the order of the adds -- and resolves it to
+// (sum + n / 2) / n. Every kernel adds a launch's samples to the sums with one read-add-write of a pixel's sums, one lane per
+// pixel: no atomics.
 //
-// Two kernels add samples, as VRT_MODE_FULL has two forms (vrt_dispatch.cpp enqueue()):
-//   bounce_accum_kernel   scenes the dispatcher proves opaque, seen from empty space. Pass 1 (trace_kernel MODE 4) does not
-//                         depend on the sample and runs once per accumulation; this kernel then runs the diffuse bounce of
-//                         full::bounce_pixel (the only part that reads the RNG, its first two numbers) for n samples in a loop
-//                         over the seed each lane loaded once: the 8 x 8 tiles and the tile ballot of MODE 5, the three sums
-//                         in LDS, one read-add-write of the pixel's sums at the end (one lane per pixel: no atomics).
-//   full_accum_kernel     everything else: full::trace_pixel_full with the sample index, its bytes added to the sums. One
-//                         sample per launch; the traversal is the one trace_kernel<2> would take.
-// and one resolves: accum_resolve_kernel.
+// A sample's ray comes from one of three sources (the template parameter SRC of the kernels below):
+//   CornerSource  the pixel's corner, the frame's own ray: only the full path tracer's random numbers differ between samples
+//   JitterSource  the ray moved from the corner by (jitter_x(k), jitter_y(k)) (VRT_ACCUM_JITTER, vrt_common.hip.h jittered_ray_dir())
+//   LensSource    a thin lens (vrt_set_lens): the ray of lens_sample() (vrt_lens.hip.h), jittered or not per the accumulation's flags
+// Sample 0 of every source is the frame itself. The jittered and lens accumulations, and those of VRT_MODE_PRIMARY / _SHADOW,
+// take the frame's (voxel ID, dist) image from an ordinary frame rendered once per accumulation (vrt_accum.cpp); the corner
+// source's one-sample kernel writes it.
+//
+// The kernels by shape and source (vrt_dispatch.cpp enqueue() picks one as it picks the form of a frame):
+//   shape                                           corner                 jitter / lens
+//   samples looped in the lanes, modes 0 / 1        repeat_kernel          primary_accum_kernel<JitterSource / LensSource, ...>
+//   MODE 6's chain looped in the lanes (opaque)     bounce_accum_kernel    opaque_accum_kernel<JitterSource / LensSource, ...>
+//   one sample per launch, the general full tracer  full_accum_kernel<CornerSource / JitterSource / LensSource, ...>
+// The corner source has kernels of its own where a sample does not depend on its ray: a primary mode's every sample is the frame
+// (repeat_kernel), and an opaque scene's pass 1 runs once per accumulation (bounce_accum_kernel). Then the resolve:
+// accum_resolve_kernel.
 //
 // Adaptive accumulations (include/vrt.h vrt_accum_begin_adaptive) take the same kernels with the template parameter ADAPT = true:
 // each lane reads its pixel's state (sums, its count n in the fourth word, Q) once, takes a round's sample only while
-// adaptive_active() holds, and writes the state back once. The sample-looped kernels leave the loop at the pixel's stop; the
-// one-sample kernels trace the tiles compact_tiles_kernel listed for the round and leave inactive lanes idle.
+// adaptive_active() holds, and writes the state back once. The sample-looped kernels leave the loop at the pixel's stop;
+// the one-sample kernels trace the tiles compact_tiles_kernel listed for the round and leave inactive lanes idle.
 #pragma once
 #include "vrt_accum.h"
 #include "vrt_full.hip.h"
+#include "vrt_lens.hip.h"
 
 namespace vrt {
 namespace accum {
@@ -69,18 +79,171 @@ VRT_DEV void add_repeat(uint32_t rgba, uint32_t k, PixelState &p) {
     p.q += (uint64_t)(l * l) * k;
 }
 
+VRT_DEV size_t pixel_offset(const KArgs &a, int px, int py) { return (size_t)py * (size_t)a.width + (size_t)px; }
+
+// This lane's pixel of 8 x 8 tile `tile` of a whole frame (KArgs: row0 = 0, n_rows = height, compact = 0)
+VRT_DEV void tile_pixel(const KArgs &a, int tile, int &px, int &py) {
+    const int lane = threadIdx.x & 63;
+    const int tiles_x = (a.width + 7) / 8;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    px = tx * 8 + (lane & 7);
+    py = ty * 8 + (lane >> 3);
+}
+
+// One 8 x 8 tile per wave, trace_kernel's tiles in order; false past the frame's edge. Written out rather than through
+// tile_pixel(): with the tile computed ahead of the lane, the kernels' tile arithmetic compiles differently.
+template <int BLOCK>
+VRT_DEV bool frame_pixel(const KArgs &a, int &px, int &py) {
+    const int lane = threadIdx.x & 63;
+    const int tiles_x = (a.width + 7) / 8;
+    const int tile = (int)blockIdx.x * (BLOCK / 64) + (int)(threadIdx.x >> 6);
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    px = tx * 8 + (lane & 7);
+    py = ty * 8 + (lane >> 3);
+    return px < a.width && py < a.height;
+}
+
 // An adaptive one-sample launch: wave w of the grid (sized for every tile) takes tile q.tiles[w] while w < *q.n_tiles
 template <int BLOCK>
 VRT_DEV bool listed_pixel(const KArgs &a, const AdaptArgs &q, int &px, int &py) {
     const uint32_t slot = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
     if (slot >= *q.n_tiles) return false;
-    const int lane = threadIdx.x & 63;
-    const int tiles_x = (a.width + 7) / 8;
-    const int tile = (int)q.tiles[slot];
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    px = tx * 8 + (lane & 7);
-    py = ty * 8 + (lane >> 3);
+    tile_pixel(a, (int)q.tiles[slot], px, py);
     return px < a.width && py < a.height;
+}
+
+// The arguments of a sample loop, re-read from the kernarg segment for every sample (late_args(), late_view()): held in scalar
+// registers across the loop's back edge they spill, into vector lanes and from there to scratch (20 SGPRs, then 18 VGPRs in the
+// bounce kernel)
+VRT_DEV KArgs loop_args(const KArgs &a) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return *late_args();
+#else
+    return a;
+#endif
+}
+VRT_DEV View loop_view(const ViewSet &vs) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return *late_view();
+#else
+    return vs.v[0];
+#endif
+}
+
+// ---- ray sources (JIT and LENS of trace_pixel and trace_pixel_full) ----
+struct CornerSource { static constexpr bool kJitter = false, kLens = false; };
+struct JitterSource { static constexpr bool kJitter = true, kLens = false; };
+struct LensSource {
+    static constexpr bool kJitter = false, kLens = true;
+    const Lens &L;   // the kernel's Lens argument, read where it is used
+};
+
+// ---- the kernels of the three shapes ----
+// L...: the lens kernels' fourth argument, the Lens. Each body is its kernel's own and writes out its trace call per source and its
+// ADAPT pairs: a shared __device__ body under thin wrappers, the call as a member of the source, or an accumulator type over ADAPT
+// each compile to different code (profiles/accum_kernel_fold_codegen.txt).
+
+// q.n samples q.first, q.first + 1, ... of MODE 0 or 1, looped in the lanes: the traversal the frame kernel would take
+// (trace_kernel's 8 x 8 tiles, its eye lookup and empty-octant proofs: the eye does not move), the shadow ray in MODE 1
+template <class SRC, int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT, class... L>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const L... lens) {
+    const SRC src{lens...};
+    typename TRAV::Ctx tc_;
+    TRAV::block_init(a, tc_);
+    int px, py;
+    if (!frame_pixel<BLOCK>(a, px, py)) return;
+    uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, pixel_offset(a, px, py));
+    for (uint32_t k = 0; k < q.n; ++k) {
+        if constexpr (ADAPT)
+            if (!state_active(q.min, q.max, q.tol, st)) break;
+        uint32_t rgba;
+        int2 idd;
+        LateOut lo;
+        const KArgs ak = loop_args(a);
+        const View vk = loop_view(vs);
+        if constexpr (SRC::kLens) {
+            const LensRay lr = lens_sample(ak, vk, src.L, px, py, q.first + k);
+            trace_pixel<MODE, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, &lr);
+        } else trace_pixel<MODE, TRAV, SRC::kJitter>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k);
+        if constexpr (ADAPT) add_sample(rgba, st);
+        else add_bytes(rgba, r, g, b);
+    }
+    if constexpr (ADAPT) store_state(q, pixel_offset(a, px, py), st);
+    else store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
+}
+
+// q.n samples of MODE 6's two stages, looped in the lanes: pass 1 from the sample's ray, its seed in registers, then bounce_pixel
+// with initRNG's sample index; 64 lanes, one 8 x 8 tile per wave. Pass 1 depends on the sample, so it cannot be shared as
+// bounce_accum_kernel shares it.
+template <class SRC, class TRAV, int WPE, bool ADAPT, class... L>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const L... lens) {
+    const SRC src{lens...};
+    typename TRAV::Ctx tc_;
+    TRAV::block_init(a, tc_);
+    int px, py;
+    if (!frame_pixel<64>(a, px, py)) return;
+    uint32_t r = 0u, g = 0u, b = 0u;
+    PixelState st{};
+    if constexpr (ADAPT) st = load_state(q, pixel_offset(a, px, py));
+    for (uint32_t k = 0; k < q.n; ++k) {
+        if constexpr (ADAPT)
+            if (!state_active(q.min, q.max, q.tol, st)) break;
+        const uint32_t sample = q.first + k;
+        uint32_t rgba, both;
+        int2 idd;
+        LateOut lo;
+        Seed seed;
+        seed.word = 0u;
+        const KArgs ak = loop_args(a);
+        const View vk = loop_view(vs);
+        if constexpr (SRC::kLens) {
+            const LensRay lr = lens_sample(ak, vk, src.L, px, py, sample);
+            trace_pixel<1, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, &lr);
+        } else trace_pixel<1, TRAV, SRC::kJitter>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample);
+        if (full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, both, sample)) rgba = both;
+        if constexpr (ADAPT) add_sample(rgba, st);
+        else add_bytes(rgba, r, g, b);
+    }
+    if constexpr (ADAPT) store_state(q, pixel_offset(a, px, py), st);
+    else store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
+}
+
+// Sample q.first (q.n == 1) of the general full path tracer: trace_kernel<2>'s tiles, one pixel per lane.
+// ADAPT: the waves take the round's listed tiles (listed_pixel()), and only active lanes trace.
+template <class SRC, class TRAV, int BLOCK, int WPE, bool ADAPT, class... L>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const L... lens) {
+    const SRC src{lens...};
+    typename TRAV::Ctx tc_;
+    TRAV::block_init(a, tc_);
+    int px, py;
+    if constexpr (ADAPT) {
+        if (!listed_pixel<BLOCK>(a, q, px, py)) return;
+    } else {
+        if (!frame_pixel<BLOCK>(a, px, py)) return;
+    }
+    PixelState st{};
+    if constexpr (ADAPT) {
+        st = load_state(q, pixel_offset(a, px, py));
+        if (!state_active(q.min, q.max, q.tol, st)) return;
+    }
+    uint32_t rgba;
+    int2 idd;
+    LateOut lo;
+    if constexpr (SRC::kLens) {
+        const LensRay lr = lens_sample(a, vs.v[0], src.L, px, py, q.first);
+        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
+    } else full::trace_pixel_full<TRAV, SRC::kJitter>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
+    if constexpr (ADAPT) {
+        add_sample(rgba, st);
+        store_state(q, pixel_offset(a, px, py), st);
+    } else {
+        uint32_t r = 0u, g = 0u, b = 0u;
+        add_bytes(rgba, r, g, b);
+        store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
+    }
+    if constexpr (!SRC::kJitter && !SRC::kLens) q.out_id[pixel_offset(a, px, py)] = idd;   // no frame of its own: the id_dist is the samples'
 }
 
 // One wave per 8 x 8 tile of a whole frame (KArgs: row0 = 0, n_rows = height, compact = 0); a.defer_rec holds pass 1's seeds in
@@ -97,10 +260,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     const int lane = threadIdx.x & 63;
-    const int tiles_x = (a.width + 7) / 8;
     const int tile = blockIdx.x;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
+    int px, py;
+    tile_pixel(a, tile, px, py);
     if (px >= a.width || py >= a.height) return;
     const uint32_t *sp = reinterpret_cast<const uint32_t *>(a.defer_rec) + ((size_t)tile * kSeedPlanes) * 64 + lane;
     const uint32_t word = sp[3 * 64];
@@ -128,13 +290,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
             seed.hp = F3{__uint_as_float(vs_seed[0 * 64 + lane]), __uint_as_float(vs_seed[1 * 64 + lane]), __uint_as_float(vs_seed[2 * 64 + lane])};
             seed.word = vs_seed[3 * 64 + lane];
             seed.iof = __uint_as_float(vs_seed[4 * 64 + lane]);
-            // the kernel's arguments re-read from the kernarg segment for every sample (late_args()): held in scalar registers
-            // across the loop's back edge they spilled into vector lanes (20 SGPRs, then 18 VGPRs to scratch)
-#ifdef __HIP_DEVICE_COMPILE__
-            const KArgs ak = *late_args();
-#else
-            const KArgs &ak = a;
-#endif
+            const KArgs ak = loop_args(a);
             uint32_t rgba = 0u;
             full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, rgba, q.first + k);
             vs_sum[0 * 64 + lane] = vs_sum[0 * 64 + lane] + (rgba & 0xffu);
@@ -159,44 +315,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
         store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
     } else {
         store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
-    }
-}
-
-// The general full path tracer with initRNG's sampleIndex = q.first (q.n == 1): trace_kernel<2>'s tiles, one pixel per lane.
-// ADAPT: the waves take the round's listed tiles (listed_pixel()), and only active lanes trace.
-template <class TRAV, int BLOCK, int WPE, bool ADAPT = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    if constexpr (ADAPT) {
-        int px, py;
-        if (!listed_pixel<BLOCK>(a, q, px, py)) return;
-        const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
-        PixelState st = load_state(q, o);
-        if (!state_active(q.min, q.max, q.tol, st)) return;
-        uint32_t rgba;
-        int2 idd;
-        LateOut lo;
-        full::trace_pixel_full<TRAV>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
-        add_sample(rgba, st);
-        store_state(q, o, st);
-        q.out_id[o] = idd;
-    } else {
-        const int lane = threadIdx.x & 63;
-        const int tiles_x = (a.width + 7) / 8;
-        const int tile = (int)blockIdx.x * (BLOCK / 64) + (int)(threadIdx.x >> 6);
-        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-        const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
-        if (px >= a.width || py >= a.height) return;
-        uint32_t rgba;
-        int2 idd;
-        LateOut lo;
-        full::trace_pixel_full<TRAV>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
-        const size_t o = (size_t)py * (size_t)a.width + (size_t)px;
-        uint32_t r = 0u, g = 0u, b = 0u;
-        add_bytes(rgba, r, g, b);
-        store_sums(q.sums, o, r, g, b);
-        q.out_id[o] = idd;
     }
 }
 
@@ -258,6 +376,28 @@ __global__ __launch_bounds__(256) void adaptive_counts_kernel(const Counts c) {
         wave_active += (uint32_t)__popcll(__ballot(act));
     }
     if ((threadIdx.x & 63u) == 0u && wave_active != 0u) atomicAdd(c.n_active, wave_active);
+}
+
+// A primary mode from the corner: every sample is the frame in q.frame_rgba, so n samples add n times its bytes
+__global__ __launch_bounds__(256) void repeat_kernel(const Repeat q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.pixels) return;
+    uint32_t r = 0u, g = 0u, b = 0u;
+    add_bytes(q.frame_rgba[i], r, g, b);
+    store_sums(q.sums, i, r * q.n, g * q.n, b * q.n);
+}
+
+// the same for an adaptive accumulation: q.n rounds of a sample that never changes take each pixel to
+// adaptive_constant_count(), with no trace at all
+__global__ __launch_bounds__(256) void repeat_adaptive_kernel(const RepeatAdapt q) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.pixels) return;
+    AdaptArgs s{};
+    s.sums = q.sums;
+    s.sq = q.sq;
+    PixelState st = load_state(s, i);
+    add_repeat(q.frame_rgba[i], adaptive_constant_count(st.n, q.n, q.min) - st.n, st);
+    store_state(s, i, st);
 }
 
 }  // namespace accum

@@ -182,8 +182,22 @@ struct LateOut {
 };
 VRT_DEV LateOut late_out(LateArgs la, LateView lv) { return LateOut{lv->out_rgba, lv->out_id, la->width, la->compact}; }
 
+// The shader's ray generation (comp:624-641) from the pixel's position (fx, fy), one operation at a time: u, v, inv_proj, the
+// perspective divide, normalise, inv_view, normalise -- the direction main() hands pathTrace
+VRT_DEV F3 shader_ray_dir(const KArgs &a, const View &vw, float fx, float fy) {
+    float u = (fx / (float)a.width) * 2.0f - 1.0f;
+    float v = (fy / (float)a.height) * 2.0f - 1.0f;
+    float view[4];
+    mat_vec(vw.inv_proj, u, v, -1.0f, 1.0f, view);
+    if (__builtin_fabsf(view[3]) > 1e-6f) { float w = view[3]; view[0] = view[0] / w; view[1] = view[1] / w; view[2] = view[2] / w; view[3] = view[3] / w; }
+    F3 vd = normalize3(F3{view[0], view[1], view[2]});
+    float wd4[4];
+    mat_vec(vw.inv_view, vd.x, vd.y, vd.z, 0.0f, wd4);
+    return normalize3(F3{wd4[0], wd4[1], wd4[2]});
+}
+
 // Ray generation (comp:624-641) and pathTrace's own normalisation of the direction (comp:441). Two forms, chosen per view
-// by the dispatcher (wave-uniform): the shader's operations one by one, or -- View::gen_fast -- the same operations with
+// by the dispatcher (wave-uniform): the shader's operations one by one (shader_ray_dir()), or -- View::gen_fast -- the same operations with
 // everything that depends on the column or the row alone read from the view's tables (the two index divisions, the
 // first matrix product and the perspective divide: 8 of the prologue's 15 divisions) and the remaining 1/x and sqrt in
 // their in-range forms. Same bits either way (tests: frames of both forms against the oracle).
@@ -195,15 +209,7 @@ VRT_DEV F3 primary_ray_dir(const KArgs &a, const View &vw, int px, int py) {
         const F3 d = normalize3_inrange(F3{wd4[0], wd4[1], wd4[2]});
         return scale3(d, rcp_inrange(sqrt_inrange(dot3(d, d))));
     }
-    float u = ((float)px / (float)a.width) * 2.0f - 1.0f;
-    float v = ((float)py / (float)a.height) * 2.0f - 1.0f;
-    float view[4];
-    mat_vec(vw.inv_proj, u, v, -1.0f, 1.0f, view);
-    if (__builtin_fabsf(view[3]) > 1e-6f) { float w = view[3]; view[0] = view[0] / w; view[1] = view[1] / w; view[2] = view[2] / w; view[3] = view[3] / w; }
-    F3 vd = normalize3(F3{view[0], view[1], view[2]});
-    float wd4[4];
-    mat_vec(vw.inv_view, vd.x, vd.y, vd.z, 0.0f, wd4);
-    const F3 d = normalize3(F3{wd4[0], wd4[1], wd4[2]});
+    const F3 d = shader_ray_dir(a, vw, (float)px, (float)py);
     return scale3(d, 1.0f / __builtin_sqrtf(dot3(d, d)));
 }
 
@@ -219,19 +225,11 @@ VRT_DEV float jitter_y(uint32_t k) {
 }
 
 // The shader's ray generation with float(px) + jitter_x(sample) and float(py) + jitter_y(sample) (one rounded addition
-// each) in place of float(px) and float(py); everything after them is primary_ray_dir()'s own form, one operation at a time
-// (the per-projection tables hold the pixel corner's values only).
+// each) in place of float(px) and float(py); everything after them is primary_ray_dir()'s own form, shader_ray_dir() (the
+// per-projection tables hold the pixel corner's values only).
 VRT_DEV F3 jittered_ray_dir(const KArgs &a, const View &vw, int px, int py, uint32_t sample) {
     const float fx = (float)px + jitter_x(sample), fy = (float)py + jitter_y(sample);
-    float u = (fx / (float)a.width) * 2.0f - 1.0f;
-    float v = (fy / (float)a.height) * 2.0f - 1.0f;
-    float view[4];
-    mat_vec(vw.inv_proj, u, v, -1.0f, 1.0f, view);
-    if (__builtin_fabsf(view[3]) > 1e-6f) { float w = view[3]; view[0] = view[0] / w; view[1] = view[1] / w; view[2] = view[2] / w; view[3] = view[3] / w; }
-    F3 vd = normalize3(F3{view[0], view[1], view[2]});
-    float wd4[4];
-    mat_vec(vw.inv_view, vd.x, vd.y, vd.z, 0.0f, wd4);
-    const F3 d = normalize3(F3{wd4[0], wd4[1], wd4[2]});
+    const F3 d = shader_ray_dir(a, vw, fx, fy);
     return scale3(d, 1.0f / __builtin_sqrtf(dot3(d, d)));
 }
 
@@ -245,15 +243,7 @@ VRT_DEV F3 jittered_ray_dir(const KArgs &a, const View &vw, int px, int py, uint
 struct LensRay { F3 o, dir; uint32_t eye0, eye1; };
 VRT_DEV LensRay lens_ray(const KArgs &a, const View &vw, int px, int py, float jx, float jy, float aperture, float focus, float lx, float ly) {
     const float fx = (float)px + jx, fy = (float)py + jy;
-    float u = (fx / (float)a.width) * 2.0f - 1.0f;
-    float v = (fy / (float)a.height) * 2.0f - 1.0f;
-    float view[4];
-    mat_vec(vw.inv_proj, u, v, -1.0f, 1.0f, view);
-    if (__builtin_fabsf(view[3]) > 1e-6f) { float w = view[3]; view[0] = view[0] / w; view[1] = view[1] / w; view[2] = view[2] / w; view[3] = view[3] / w; }
-    F3 vd = normalize3(F3{view[0], view[1], view[2]});
-    float wd4[4];
-    mat_vec(vw.inv_view, vd.x, vd.y, vd.z, 0.0f, wd4);
-    const F3 d = normalize3(F3{wd4[0], wd4[1], wd4[2]});   // what main() hands pathTrace (comp:640-641)
+    const F3 d = shader_ray_dir(a, vw, fx, fy);
     const F3 e{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
     LensRay r;
     r.o = e; r.dir = d; r.eye0 = r.eye1 = 0u;
@@ -268,6 +258,21 @@ VRT_DEV LensRay lens_ray(const KArgs &a, const View &vw, int px, int py, float j
         r.dir = normalize3(sub3(p, r.o));
     }
     r.dir = scale3(r.dir, 1.0f / __builtin_sqrtf(dot3(r.dir, r.dir)));   // pathTrace's own normalisation (comp:441)
+    return r;
+}
+
+// The ray trace_pixel() and full::trace_pixel_full() start from: the pixel's corner ray from the eye, whose medium the
+// dispatcher looked up (View::eye0 / eye1); JIT: the ray of jittered sample `sample` (jittered_ray_dir()); LENS: the ray `lens`
+// of a thin-lens sample, origin and medium at it included
+template <bool JIT, bool LENS>
+VRT_DEV LensRay pixel_ray(const KArgs &a, const View &vw, int px, int py, uint32_t sample, const LensRay *lens) {
+    if constexpr (LENS) return *lens;
+    LensRay r;
+    if constexpr (JIT) r.dir = jittered_ray_dir(a, vw, px, py, sample);
+    else r.dir = primary_ray_dir(a, vw, px, py);
+    r.o = F3{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
+    r.eye0 = vw.eye0;
+    r.eye1 = vw.eye1;
     return r;
 }
 
@@ -322,8 +327,8 @@ struct Seed { F3 hp; uint32_t word; float iof; };   // the same in registers (MO
 
 // One pixel: ray generation (comp:624-641), primary-ray pathTrace, packing of the two outputs.
 // TRAV supplies the traversal: march(), shadow(). MODE: 0 primary, 1 primary + shadow ray. seed (MODE 1 only): see above.
-// JIT: the ray of jittered sample `sample` (jittered_ray_dir(); the progressive accumulation, vrt_jitter.hip.h).
-// LENS: the ray `lens` of a thin-lens sample (lens_ray(), vrt_lens.hip.h): its origin, direction and the medium at its origin.
+// JIT, LENS: the ray of jittered sample `sample` or the thin-lens ray `lens` (pixel_ray(); the progressive accumulation,
+// vrt_accum.hip.h).
 // MISS (modes 0 and 1 of the traversals with kMissTiles): miss_byte is this pixel's byte of the view's miss mask (View::miss), or
 // View::miss_stamp when there is none: any other value clears the tile, and a ray that points forward on every axis (miss_forward())
 // then hits nothing ("Miss tiles") and takes the miss outputs without marching.
@@ -332,13 +337,9 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
                          uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u, const LensRay *lens = nullptr,
                          uint32_t miss_byte = 0u) {
     const float kPI = 3.14159265359f;
-    F3 ray_dir;
-    if constexpr (LENS) ray_dir = lens->dir;
-    else if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
-    else ray_dir = primary_ray_dir(a, vw, px, py);
-    F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
-    uint32_t eye0 = vw.eye0, eye1 = vw.eye1;
-    if constexpr (LENS) { ray_origin = lens->o; eye0 = lens->eye0; eye1 = lens->eye1; }
+    const LensRay pr = pixel_ray<JIT, LENS>(a, vw, px, py, sample, lens);
+    F3 ray_dir = pr.dir, ray_origin = pr.o;
+    uint32_t eye0 = pr.eye0, eye1 = pr.eye1;
 
     int voxel_id = 0;
     int pixel_dist = a.wmax[0] - a.wmin[0];

@@ -464,69 +464,34 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     }
     if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
         vrt_ctx::Accum &ac = c->accum;
-        // an adaptive accumulation (acc->adaptive) passes the same arguments with its rule and state to the kernels' adaptive forms
-        vrt::accum::AdaptArgs qa{};
-        vrt::accum::Args &q = qa;
+        // an adaptive accumulation (acc->adaptive) passes its rule and state too, to the kernels' adaptive forms
+        vrt::accum::AdaptArgs q{};
         q.sums = ac.d_sums;
         q.pass1_rgba = ac.d_pass1;
         q.out_id = ac.d_id;
+        q.first = acc->first;
+        q.n = acc->n;
         if (acc->adaptive) {
-            qa.sq = ac.d_sq;
-            qa.tiles = ac.d_tiles;
-            qa.n_tiles = ac.d_tiles + ac.tile_cap;
-            qa.min = ac.min_samples;
-            qa.max = ac.max_samples;
-            qa.tol = ac.tolerance;
+            q.sq = ac.d_sq;
+            q.tiles = ac.d_tiles;
+            q.n_tiles = ac.d_tiles + ac.tile_cap;
+            q.min = ac.min_samples;
+            q.max = ac.max_samples;
+            q.tol = ac.tolerance;
         }
-        const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, width, height, ac.min_samples,
-                                   ac.max_samples, ac.tolerance};
-        // launch(q) or launch(qa); before a one-sample launch of an adaptive round, the round's list of tiles with an active pixel
-        auto run = [&](auto &&launch) {
-            return acc->adaptive ? launch(static_cast<const vrt::accum::AdaptArgs &>(qa)) : launch(static_cast<const vrt::accum::Args &>(q));
-        };
-        auto run_round = [&](auto &&launch) {
-            if (acc->adaptive) {
-                const hipError_t et = vrt::launch::adaptive_tiles(tl, s);
-                if (et != hipSuccess) return et;
-            }
-            return run(launch);
-        };
+        using vrt::accum::Source;
+        const Source src = lens ? Source::kLens : (acc->jitter ? Source::kJitter : Source::kCorner);
+        const vrt::accum::Lens l{acc->aperture, acc->focus, acc->jitter ? 1u : 0u, lsel.eye_shared ? 0u : 1u};
+        if (src != Source::kCorner) {   // every sample has a ray of its own: no per-projection tables
+            vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
+            vs.v[0].gen_z = 0.0f;
+            vs.v[0].gen_fast = 0u;
+        }
         e = hipSuccess;
-        if (lens) {   // the thin-lens kernels (vrt_lens.hip.h), the same three forms as the jittered ones below
-            vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
-            vs.v[0].gen_z = 0.0f;
-            vs.v[0].gen_fast = 0u;
-            const vrt::accum::Lens l{acc->aperture, acc->focus, acc->jitter ? 1u : 0u, lsel.eye_shared ? 0u : 1u};
-            q.first = acc->first;
-            q.n = acc->n;
-            if (mode != VRT_MODE_FULL) {
-                e = run([&](const auto &qq) { return vrt::launch::lens_primary(mode, v, a, vs, qq, l, (int)grid, s); });
-            } else if (two_pass) {
-                e = run([&](const auto &qq) { return vrt::launch::lens_opaque(a, vs, qq, l, (int)grid, s); });
-            } else {
-                for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
-                    q.first = acc->first + k;
-                    q.n = 1u;
-                    e = run_round([&](const auto &qq) { return vrt::launch::lens_full(v, a, vs, qq, l, (int)grid, s); });
-                }
-            }
-        } else if (acc->jitter) {   // every sample has a ray of its own: jittered_ray_dir(), no per-projection tables
-            vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
-            vs.v[0].gen_z = 0.0f;
-            vs.v[0].gen_fast = 0u;
-            q.first = acc->first;
-            q.n = acc->n;
-            if (mode != VRT_MODE_FULL) {   // one launch, the samples looped in the lanes
-                e = run([&](const auto &qq) { return vrt::launch::jitter_primary(mode, v, a, vs, qq, (int)grid, s); });
-            } else if (two_pass) {         // MODE 6's chain per sample, looped in the lanes
-                e = run([&](const auto &qq) { return vrt::launch::jitter_opaque(a, vs, qq, (int)grid, s); });
-            } else {                       // the general path tracer, one launch per sample
-                for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
-                    q.first = acc->first + k;
-                    q.n = 1u;
-                    e = run_round([&](const auto &qq) { return vrt::launch::jitter_full(v, a, vs, qq, (int)grid, s); });
-                }
-            }
+        if (mode != VRT_MODE_FULL) {   // one launch, the samples looped in the lanes
+            e = vrt::launch::accum_primary(mode, src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
+        } else if (two_pass && src != Source::kCorner) {   // MODE 6's chain per sample, looped in the lanes
+            e = vrt::launch::accum_opaque(src, a, vs, q, acc->adaptive, l, (int)grid, s);
         } else if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
             a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
             if (!ac.pass1) {
@@ -535,14 +500,15 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
                 e = vrt::launch::trace_full_pass1(a, vs, (int)grid, s);
                 if (e == hipSuccess) ac.pass1 = true;
             }
-            q.first = acc->first;
-            q.n = acc->n;
-            if (e == hipSuccess) e = run([&](const auto &qq) { return vrt::launch::accum_bounce(a, vs, qq, (int)grid, s); });
-        } else {          // the general path tracer, one launch per sample
+            if (e == hipSuccess) e = vrt::launch::accum_bounce(a, vs, q, acc->adaptive, (int)grid, s);
+        } else {   // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
+            const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, width, height, ac.min_samples,
+                                       ac.max_samples, ac.tolerance};
             for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
                 q.first = acc->first + k;
                 q.n = 1u;
-                e = run_round([&](const auto &qq) { return vrt::launch::accum_full(v, a, vs, qq, (int)grid, s); });
+                if (acc->adaptive) e = vrt::launch::adaptive_tiles(tl, s);
+                if (e == hipSuccess) e = vrt::launch::accum_full(src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
             }
         }
     } else if (two_pass && c->two_pass_form >= 5) {

@@ -163,8 +163,7 @@ VRT_DEV RayS make_ray(F3 o, F3 d, float iof, float w, const float tint[3], float
 }
 
 // sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
-// with JIT also the jittered sample whose ray is traced (jittered_ray_dir(), vrt_jitter.hip.h); LENS: the ray `lens` instead
-// (lens_ray(), vrt_lens.hip.h), origin and medium included
+// with JIT also the jittered sample whose ray is traced; LENS: the ray `lens` instead, origin and medium included (pixel_ray())
 template <class TRAV, bool JIT, bool LENS>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
                                  uint32_t sample, const LensRay *lens) {
@@ -172,13 +171,9 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     const float sky[3] = {0.5f, 0.7f, 1.0f};
     const float kSun = 3.0f;
     uint32_t rng = rng_init(px, py, sample);
-    F3 ray_dir;
-    if constexpr (LENS) ray_dir = lens->dir;
-    else if constexpr (JIT) ray_dir = jittered_ray_dir(a, vw, px, py, sample);
-    else ray_dir = primary_ray_dir(a, vw, px, py);
-    F3 ray_origin{vw.cam_pos[0], vw.cam_pos[1], vw.cam_pos[2]};
-    uint32_t eye0 = vw.eye0, eye1 = vw.eye1;
-    if constexpr (LENS) { ray_origin = lens->o; eye0 = lens->eye0; eye1 = lens->eye1; }   // the lens sample's origin and its medium
+    const LensRay pr = pixel_ray<JIT, LENS>(a, vw, px, py, sample, lens);
+    F3 ray_dir = pr.dir, ray_origin = pr.o;
+    uint32_t eye0 = pr.eye0, eye1 = pr.eye1;
 
     int voxel_id = 0;
     int pixel_dist = a.wmax[0] - a.wmin[0];

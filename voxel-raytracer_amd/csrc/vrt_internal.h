@@ -254,8 +254,8 @@ int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-bu
 // vrt_dispatch.cpp
 // AccumStep: instead of rendering a frame, add samples first .. first + n - 1 of VRT_MODE_FULL to the context's accumulation
 // (vrt_accum.cpp; whole frame, the context's camera, d_rgba / d_id unused)
-// (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_jitter.hip.h)
-// (aperture > 0: the samples of a thin lens, vrt_set_lens; vrt_lens.hip.h)
+// (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_accum.hip.h JitterSource)
+// (aperture > 0: the samples of a thin lens, vrt_set_lens; vrt_accum.hip.h LensSource, vrt_lens.hip.h)
 // (adaptive: n rounds of the context's adaptive accumulation, vrt_accum_begin_adaptive; the kernels' adaptive forms)
 struct AccumStep { uint32_t first, n; bool jitter; float aperture = 0.0f, focus = 1.0f; bool adaptive = false; };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,

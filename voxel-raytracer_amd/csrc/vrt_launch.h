@@ -56,37 +56,25 @@ hipError_t denoise(const Denoise &d, bool whole_groups, hipStream_t s);
 hipError_t cast_rays(const KArgs &a, const query::RayArgs &q, hipStream_t s);
 hipError_t find_voxels(const KArgs &a, const query::PointArgs &q, hipStream_t s);
 
-// vrt_launch_accum.hip: progressive accumulation of VRT_MODE_FULL (vrt_accum.hip.h), whole frames, one tile per wave.
-// accum_bounce: q.n samples of the diffuse bounce over pass 1's seeds in a.defer_rec (grid = tiles). accum_full: one sample
-// (q.first) of the general path tracer in the traversal and workgroup shape of `v` (grid = tiles / waves per workgroup).
-hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
-hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
-hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s);
-// The jittered samples and the primary modes (vrt_jitter.hip.h), whole frames, one 8 x 8 tile per wave, grid =
-// tiles / waves per workgroup of `v`. jitter_primary: q.n samples of `mode` (0 or 1), `v` as the dispatcher normalises it for an
-// accumulation (v4 64/7, v3 64/6, v2 or v1 256/1). jitter_opaque: q.n samples of the opaque full path tracer (v4, 64 lanes).
-// jitter_full: one sample (q.first) of the general full path tracer in the shapes of accum_full. accum_repeat: n frames' bytes.
-hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
-hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
-hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, int grid, hipStream_t s);
+// vrt_launch_accum.hip: the progressive accumulation (vrt_accum.hip.h), whole frames, one 8 x 8 tile per wave. One launch per
+// shape, for the ray source `src` (l: the lens of Source::kLens, read for that source only) and, with `adaptive`, the kernels'
+// adaptive forms, which read all of q; the others read its Args part. hipErrorInvalidValue: no kernel of that shape.
+// accum_primary: q.n samples of `mode` (0 or 1) from the jitter or lens source, `v` as the dispatcher normalises it for an
+// accumulation (v4 64/7, v3 64/6, v2 or v1 256/1). accum_opaque: q.n samples of the opaque full path tracer from the jitter or
+// lens source (v4, 64 lanes). accum_full: one sample (q.first) of the general full path tracer in the traversal and workgroup
+// shape of `v` (grid = tiles / waves per workgroup); adaptive, it traces the tiles adaptive_tiles listed before it.
+// accum_bounce: q.n samples of the diffuse bounce over pass 1's seeds in a.defer_rec (grid = tiles). accum_repeat: n frames'
+// bytes. adaptive_resolve: by each pixel's own count. adaptive_counts: vrt_accum_counts.
+hipError_t accum_primary(int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q,
+                         bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
+                        int grid, hipStream_t s);
+hipError_t accum_full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
+                      const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, int grid, hipStream_t s);
 hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s);
-// The thin-lens samples (vrt_lens.hip.h, vrt_launch_accum.hip) in the shapes of the three above: lens_primary (modes 0 / 1, q.n
-// samples), lens_opaque (the opaque chain, q.n samples), lens_full (one sample of the general full path tracer).
-hipError_t lens_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t lens_opaque(const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t lens_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::Args &q, const accum::Lens &l, int grid, hipStream_t s);
-// Adaptive accumulations (include/vrt.h vrt_accum_begin_adaptive): the same launches with AdaptArgs take the kernels' adaptive
-// forms; the one-sample ones (accum_full, jitter_full, lens_full) trace the tiles adaptive_tiles listed before them.
-// adaptive_resolve: by each pixel's own count. adaptive_counts: vrt_accum_counts.
-hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
-hipError_t accum_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
-hipError_t jitter_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
-hipError_t jitter_opaque(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
-hipError_t jitter_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, int grid, hipStream_t s);
 hipError_t accum_repeat(const accum::RepeatAdapt &q, hipStream_t s);
-hipError_t lens_primary(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t lens_opaque(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t lens_full(const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s);
 hipError_t adaptive_resolve(const accum::Resolve &q, hipStream_t s);
 hipError_t adaptive_tiles(const accum::Tiles &t, hipStream_t s);
 hipError_t adaptive_counts(const accum::Counts &c, hipStream_t s);

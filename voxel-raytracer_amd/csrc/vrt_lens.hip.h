@@ -1,22 +1,17 @@
-// vrt_lens.hip.h -- the progressive accumulation's thin-lens samples (include/vrt.h vrt_set_lens). Lens sample k of a pixel is
-// the sample of vrt_jitter.hip.h (jittered or not, per the accumulation's flags) traced from a point of the lens towards the
-// point where the pinhole ray meets the plane of focus (vrt_common.hip.h lens_ray()); sample 0, the lens centre, is the frame.
-// The lens point depends on k alone, so it is wave-uniform: its 24-bit sequence and the concentric disc map are made once
-// per sample by every lane alike, on scalar loads of the direction numbers. The origin differs per lane only where a ray does
+// vrt_lens.hip.h -- the thin lens of the progressive accumulation (include/vrt.h vrt_set_lens), its LensSource in vrt_accum.hip.h.
+// Lens sample k of a pixel is the sample of the accumulation (jittered or not, per its flags) traced from a point of the lens
+// towards the point where the pinhole ray meets the plane of focus (vrt_common.hip.h lens_ray()); sample 0, the lens centre, is
+// the frame. The lens point depends on k alone, so it is wave-uniform: its 24-bit sequence and the concentric disc map are made
+// once per sample by every lane alike, on scalar loads of the direction numbers. The origin differs per lane only where a ray does
 // not point forward (it keeps the eye), but nothing below relies on that.
 //
 // What the frame kernels take from the one eye of a view is taken from the view only where the dispatcher proved it for
 // every origin the lens can produce (vrt_dispatch.cpp, vrt_layout.h lens_select()): the eye lookup (View::eye0 / eye1, or
 // Lens::lane_eye and record_find() at the lane's own floor(o * u_voxelScale)), the first lookup of the wide traversals
-// (View::first_valid, else their own find()), root 0's tightening, the v4 primary loop and the opaque chain. Like
-// vrt_jitter.hip.h, every kernel adds each sample's unorm8 bytes to the per-pixel sums, one read-add-write per launch,
-// one lane per pixel; the resolve's id_dist is the pinhole frame's, rendered by an ordinary frame (vrt_accum.cpp).
-//   primary_lens_kernel  VRT_MODE_PRIMARY / _SHADOW: the samples of a launch looped in the lanes
-//   opaque_lens_kernel   VRT_MODE_FULL, opaque scenes whose every lens origin is in empty space: MODE 6's chain per sample
-//   full_lens_kernel     VRT_MODE_FULL, everything else: trace_pixel_full from the lens ray, one sample per launch
-// Each has an adaptive form (template parameter ADAPT, vrt_accum.hip.h).
+// (View::first_valid, else their own find()), root 0's tightening, the v4 primary loop and the opaque chain.
 #pragma once
-#include "vrt_jitter.hip.h"
+#include "vrt_accum.h"
+#include "vrt_full.hip.h"
 
 namespace vrt {
 namespace accum {
@@ -68,106 +63,6 @@ VRT_DEV LensRay lens_sample(const KArgs &a, const View &vw, const Lens &L, int p
     if (L.lane_eye) record_find(a, floor_i3(scale3(lr.o, a.voxel_scale)), lr.eye0, lr.eye1);
     else { lr.eye0 = vw.eye0; lr.eye1 = vw.eye1; }
     return lr;
-}
-
-// q.n lens samples q.first, q.first + 1, ... of MODE 0 or 1; whole frame
-template <int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_lens_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const Lens L) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    int px, py;
-    if (!jitter_pixel<BLOCK>(a, px, py)) return;
-    uint32_t r = 0u, g = 0u, b = 0u;
-    PixelState st{};
-    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
-    for (uint32_t k = 0; k < q.n; ++k) {
-        if constexpr (ADAPT)
-            if (!state_active(q.min, q.max, q.tol, st)) break;
-        uint32_t rgba;
-        int2 idd;
-        LateOut lo;
-#ifdef __HIP_DEVICE_COMPILE__   // re-read for every sample, as in primary_jitter_kernel
-        const KArgs ak = *late_args();
-        const View vk = *late_view();
-#else
-        const KArgs &ak = a;
-        const View &vk = vs.v[0];
-#endif
-        const LensRay lr = lens_sample(ak, vk, L, px, py, q.first + k);
-        trace_pixel<MODE, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, &lr);
-        if constexpr (ADAPT) add_sample(rgba, st);
-        else add_bytes(rgba, r, g, b);
-    }
-    if constexpr (ADAPT) store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
-    else store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
-}
-
-// MODE 6's two stages per lens sample, the seed in registers; 64 lanes, one 8 x 8 tile per wave
-template <class TRAV, int WPE, bool ADAPT = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_lens_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const Lens L) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    int px, py;
-    if (!jitter_pixel<64>(a, px, py)) return;
-    uint32_t r = 0u, g = 0u, b = 0u;
-    PixelState st{};
-    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
-    for (uint32_t k = 0; k < q.n; ++k) {
-        if constexpr (ADAPT)
-            if (!state_active(q.min, q.max, q.tol, st)) break;
-        const uint32_t sample = q.first + k;
-        uint32_t rgba, both;
-        int2 idd;
-        LateOut lo;
-        Seed seed;
-        seed.word = 0u;
-#ifdef __HIP_DEVICE_COMPILE__
-        const KArgs ak = *late_args();
-        const View vk = *late_view();
-#else
-        const KArgs &ak = a;
-        const View &vk = vs.v[0];
-#endif
-        const LensRay lr = lens_sample(ak, vk, L, px, py, sample);
-        trace_pixel<1, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, &lr);
-        if (full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, both, sample)) rgba = both;
-        if constexpr (ADAPT) add_sample(rgba, st);
-        else add_bytes(rgba, r, g, b);
-    }
-    if constexpr (ADAPT) store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
-    else store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
-}
-
-// the general full path tracer, lens sample q.first (q.n == 1)
-// (ADAPT: the round's listed tiles, active lanes only)
-template <class TRAV, int BLOCK, int WPE, bool ADAPT = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_lens_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const Lens L) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    int px, py;
-    if constexpr (ADAPT) {
-        if (!listed_pixel<BLOCK>(a, q, px, py)) return;
-    } else {
-        if (!jitter_pixel<BLOCK>(a, px, py)) return;
-    }
-    PixelState st{};
-    if constexpr (ADAPT) {
-        st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
-        if (!state_active(q.min, q.max, q.tol, st)) return;
-    }
-    uint32_t rgba;
-    int2 idd;
-    LateOut lo;
-    const LensRay lr = lens_sample(a, vs.v[0], L, px, py, q.first);
-    full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    if constexpr (ADAPT) {
-        add_sample(rgba, st);
-        store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
-    } else {
-        uint32_t r = 0u, g = 0u, b = 0u;
-        add_bytes(rgba, r, g, b);
-        store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
-    }
 }
 
 }  // namespace accum
