@@ -169,6 +169,42 @@ int vrt_cast_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int orig
  * The words are 0 when present is 0. HOST buffers, synchronous. */
 int vrt_find_voxels(vrt_ctx *ctx, size_t n, const int32_t *coords, uint32_t *out);
 
+/* EXTENSION: the SHADED answer for rays of the caller's own -- panoramic and fisheye cameras, cube-map faces, light probes, a
+ * mirror pass, sparse re-rendering: pathTrace (comp:435-622) for n rays, in `mode` (VRT_MODE_PRIMARY, _PRIMARY_SHADOW, _FULL).
+ *   Rays      ray i is pathTrace(origin_i, dir_i) exactly as the shader's main() calls it (comp:641). origin_i is in world units,
+ *             the units of camera_pos, before u_voxelScale: gro = origin_i * u_voxelScale, the medium the ray starts in is looked
+ *             up at floor(gro) (comp:445-449), and the distance in the medium and the eye vector of the shading come from
+ *             origin_i. origin_stride 3: n x 3 floats; 0: ONE origin shared by all rays, as in vrt_cast_rays.
+ *   Direction dir_i (n x 3 floats) is used as given; pathTrace normalises it on entry (comp:441) as d * (1 / sqrt(dot(d, d))),
+ *             float32, every operation rounded on its own, / and sqrt correctly rounded: any length from 1e-3 to 1e3 and far
+ *             beyond gives the ray of the unit vector those operations make of it. A zero, infinite or NaN direction or origin
+ *             gives an unspecified result for THAT ray; the call still terminates and no other ray of the batch changes.
+ *   State     the uploaded tree (after patches and compaction, either upload form) and vrt_params (bounds, u_texDim for the
+ *             voxel ID, the lights, the highlighted voxel). No camera is read (vrt_set_camera is not needed), and no
+ *             accumulation, lens, ray table, miss mask or tile order is read or written: frames and accumulations before and
+ *             after the call are what they would be without it. Pixels do not depend on vrt_set_variant / vrt_set_option.
+ *   width     >= 1: the batch is read as an image of that width FOR THE RANDOM NUMBERS ONLY: ray i of sample k seeds
+ *             initRNG(ivec2(i % width, i / width), k) (comp:380-387). A batch that is a frame's rays in row-major order, with the
+ *             frame's width, therefore draws the frame's random numbers and gives the frame, byte for byte. A plain list passes
+ *             any width. (Batches at least 8 wide and two rows high are also traced in 8 x 8 tiles of that image, the frame
+ *             kernels' shape; that is a matter of speed, never of results.)
+ *   Samples   the result is the mean of samples first_sample ... first_sample + n_samples - 1 (indices modulo 2^32) by the
+ *             accumulation's rule: per channel the integer sum of the unorm8 bytes each sample would store, resolved as
+ *             (sum + n_samples / 2) / n_samples, alpha 255; n_samples == 1 is the sample itself. VRT_MODE_PRIMARY and
+ *             _PRIMARY_SHADOW draw no random number, so every sample is the same and one is traced. 1 <= n_samples <= 2^24.
+ *   Outputs   out_rgba8: n x 4 bytes; out_id_dist: n x 2 int32 = (voxelID, dist) of ray i's primary hit as vrt_dispatch stores
+ *             them (0 and the world's x extent on a miss). Either may be NULL, not both.
+ *   Errors    VRT_E_STATE before any upload and while a patch batch is open. VRT_E_INVALID: origin_stride not 0 or 3, an unknown
+ *             mode, width < 1, n_samples outside [1, 2^24], n > 2^30, both outputs NULL, NULL origins or dirs with n > 0.
+ *             n == 0 (with valid arguments otherwise) does nothing and returns VRT_OK.
+ * vrt_shade_rays: HOST buffers, synchronous, copied through device buffers the context keeps and grows. */
+int vrt_shade_rays(vrt_ctx *ctx, size_t n, const float *origins, int origin_stride, const float *dirs, int width, int mode,
+                   uint32_t first_sample, uint32_t n_samples, uint8_t *out_rgba8, int32_t *out_id_dist);
+/* The same on DEVICE buffers, enqueued on `stream` (NULL: the context's) -- ordered after the patches and frames enqueued before
+ * it on that stream; returns after enqueueing. */
+int vrt_shade_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width,
+                          int mode, uint32_t first_sample, uint32_t n_samples, void *d_rgba8, void *d_id_dist, void *stream);
+
 /* Progressive multi-sample accumulation (one per context; vrt_accum_begin_ex below: the other modes, sub-pixel jitter).
  * Sample k is the VRT_MODE_FULL frame rendered with initRNG(pixel, k) (shaders/raytracing.comp:380-387; the shader itself
  * passes 0): camera, uniforms, tree and every other convention unchanged. The accumulation holds the samples first, first + 1,

@@ -1,0 +1,148 @@
+"""Rate of vrt_shade_rays_device on one MI355X, kernel time from the events attached to each launch (vrt_set_profiling):
+  (a) the 1080p dragon frame's rays as a batch (width 1920), each mode, alternated launch by launch with the frame kernel of the
+      same frame and mode -- the same work with every per-view shortcut available (ray tables, the shared eye lookup, the
+      tightened root, the empty-space march loop, miss tiles, tile scheduling). The frame kernels are the parent commit's,
+      unchanged. The batch's rays are made here in numpy, so they are the frame's rays up to rounding, not bit for bit.
+  (b) 2 M random incoherent rays through the dragon, each mode.
+  (c) 2 M probe rays: origins in the cells in front of surfaces, cosine-distributed directions about the face normal, mode 2,
+      n_samples 1 and 16.
+Prints one JSON object per line; --out writes them to a file too.
+
+    python3 tools/shade_rays_rate.py --out profiles/shade_rays_rate.jsonl
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import vrt_import  # noqa: E402
+
+POSE = ((63.5, 60.5, 140.5), -90.0, -10.0)   # the golden 1080p dragon frame
+
+
+def frame_rays(V, W, H):
+    """comp:624-641 in float64, rounded to float32 at the end"""
+    ip, iv, cp, _ = V.camera_block(POSE[0], POSE[1], POSE[2], W, H)
+    ipm = np.asarray(ip, np.float64).reshape(4, 4).T
+    ivm = np.asarray(iv, np.float64).reshape(4, 4).T
+    u = np.arange(W) / W * 2 - 1
+    v = np.arange(H) / H * 2 - 1
+    uu, vv = np.meshgrid(u, v)
+    view = ipm @ np.stack([uu.ravel(), vv.ravel(), -np.ones(W * H), np.ones(W * H)])
+    view = view[:3] / view[3]
+    view /= np.linalg.norm(view, axis=0, keepdims=True)
+    d = (ivm[:3, :3] @ view).T
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return (ip, iv, cp), np.asarray(cp[:3], np.float32), np.ascontiguousarray(d, np.float32)
+
+
+def cosine_dirs(rng, normals):
+    n = len(normals)
+    r1, r2 = rng.random(n), rng.random(n)
+    phi = 2 * np.pi * r2
+    x, z, y = np.sqrt(1 - r1) * np.cos(phi), np.sqrt(1 - r1) * np.sin(phi), np.sqrt(r1)
+    up = np.where(np.abs(normals[:, 2:3]) < 0.999, np.array([[0.0, 0.0, 1.0]]), np.array([[1.0, 0.0, 0.0]]))
+    t = np.cross(up, normals)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(normals, t)
+    return np.ascontiguousarray(t * x[:, None] + b * z[:, None] + normals * y[:, None], np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rays", type=int, default=1 << 21)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    V = vrt_import.vrt()
+    w = V.World()
+    assert w.load_vox(os.path.join(ROOT, "tests", "golden", "maps", "dragon.vox"))
+    ctx = V.Context(0)
+    ctx.upload_octree(*w.flatten())
+    rows = []
+
+    def emit(r):
+        print(json.dumps(r), flush=True)
+        rows.append(r)
+
+    def upload(o, d):
+        d_o, d_d = ctx.device_alloc(o.nbytes), ctx.device_alloc(d.nbytes)
+        ctx.device_write(d_o, o)
+        ctx.device_write(d_d, d)
+        return d_o, d_d
+
+    def timed(launches, reps):
+        """launches: callables, run in turn `reps` times with per-launch events -> one array of kernel ms per callable"""
+        for f in launches:   # warm-up: code objects, scratch
+            f()
+        ctx.synchronize()
+        ctx.set_profiling(len(launches) * reps)
+        for _ in range(reps):
+            for f in launches:
+                f()
+        ms = ctx.profile_read(len(launches) * reps)
+        ctx.set_profiling(0)
+        assert len(ms) == len(launches) * reps, "a launch was not timed"
+        return [ms[i::len(launches)] for i in range(len(launches))]
+
+    # (a) the frame's rays against the frame kernel
+    W, H = 1920, 1080
+    cam, origin, dirs = frame_rays(V, W, H)
+    ctx.set_camera(*cam)
+    n = W * H
+    d_o, d_d = upload(origin.reshape(1, 3), dirs)
+    d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
+    for mode in (0, 1, 2):
+        for _ in range(40):   # let the frame kernel's scheduler and miss mask settle, as in a frame loop
+            ctx.dispatch_rows(W, H, 0, H, mode, d_rgba, d_id)
+        frame, batch = timed([lambda: ctx.dispatch_rows(W, H, 0, H, mode, d_rgba, d_id),
+                              lambda: ctx.shade_rays_device(n, d_o, 0, d_d, d_rgba, d_id, mode=mode, width=W)], args.reps)
+        fm, bm = float(np.median(frame)), float(np.median(batch))
+        emit({"case": "a_frame_rays_1080p_dragon", "mode": mode, "rays": n, "frame_kernel_ms": round(fm, 4), "batch_kernel_ms": round(bm, 4),
+              "batch_over_frame": round(bm / fm, 3), "batch_rays_per_s": round(n / (bm * 1e-3)), "reps": args.reps})
+    for p in (d_o, d_d, d_rgba, d_id):
+        ctx.device_free(p)
+
+    # (b) random incoherent rays
+    rng = np.random.default_rng(1)
+    n = args.rays
+    o = rng.uniform((-64, -64, -64), (192, 160, 128), (n, 3)).astype(np.float32)
+    d = rng.normal(0, 1, (n, 3)).astype(np.float32)
+    d_o, d_d = upload(o, d)
+    d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
+    for mode in (0, 1, 2):
+        (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, 3, d_d, d_rgba, d_id, mode=mode, width=n)], max(3, args.reps // 2))
+        m = float(np.median(ms))
+        emit({"case": "b_random_rays_dragon", "mode": mode, "rays": n, "batch_kernel_ms": round(m, 4), "batch_rays_per_s": round(n / (m * 1e-3))})
+
+    # (c) probes: from the cell in front of a hit surface, cosine-distributed about its normal
+    hit, coord, place, _, _ = ctx.cast_rays(o, d)
+    face = (place - coord)[hit].astype(np.float64)
+    ok = np.abs(face).sum(1) == 1   # unit voxels: the placement cell is a face neighbour
+    cells, normals = place[hit][ok], face[ok]
+    pick = rng.integers(0, len(cells), n)
+    po = (cells[pick] + rng.random((n, 3))).astype(np.float32)
+    pd = cosine_dirs(rng, normals[pick])
+    ctx.device_write(d_o, po)
+    ctx.device_write(d_d, pd)
+    for n_samples in (1, 16):
+        (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, 3, d_d, d_rgba, d_id, mode=2, width=n, n_samples=n_samples)], max(3, args.reps // 4))
+        m = float(np.median(ms))
+        emit({"case": "c_probe_rays_dragon", "mode": 2, "rays": n, "n_samples": n_samples, "surfaces": int(len(cells)),
+              "batch_kernel_ms": round(m, 4), "paths_per_s": round(n * n_samples / (m * 1e-3))})
+    for p in (d_o, d_d, d_rgba, d_id):
+        ctx.device_free(p)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -100,6 +100,15 @@ def query_ray_args(origins, dirs, box=WORLD_BOX):
             np.ascontiguousarray(b[0], np.float32), np.ascontiguousarray(b[1], np.float32))
 
 
+def shade_ray_args(origins, dirs):
+    """Checks and converts the ray arguments of Context.shade_rays (no device involved) -> (origins float32[k, 3] with k = 1
+    (shared origin) or n, origin_stride 0 or 3, dirs float32[n, 3])."""
+    o, stride, d, _, _ = query_ray_args(origins, dirs)
+    if d.shape[0] > 2 ** 30:
+        raise ValueError("at most 2^30 rays per call")
+    return o, stride, d
+
+
 def query_point_args(coords):
     """Checks and converts the argument of Context.find_voxels (no device involved) -> int32[n, 3]."""
     c = np.asarray(coords)
@@ -249,6 +258,10 @@ def hip_lib():
         L.vrt_cast_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
         L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.vrt_shade_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_void_p]
+        L.vrt_shade_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
         L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
         L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
@@ -824,6 +837,30 @@ class Context:
         L = self._L
         self._chk(L.vrt_find_voxels(self._h, n, c.ctypes.data if n else None, out.ctypes.data if n else None))
         return out[:, 0] != 0, out[:, 1:].copy()
+
+    def shade_rays(self, origins, dirs, mode=MODE_FULL, width=None, first_sample=0, n_samples=1):
+        """pathTrace for the caller's own rays (vrt_shade_rays). origins: (n, 3), or (3,) shared by all rays; dirs: (n, 3),
+        used as given; width: the batch as an image of that width for the random numbers (None: n); the mean of samples
+        first_sample .. first_sample + n_samples - 1 -> (rgba8 uint8[n, 4], id_dist int32[n, 2])."""
+        o, stride, d = shade_ray_args(origins, dirs)
+        n = d.shape[0]
+        rgba = np.zeros((n, 4), np.uint8)
+        idd = np.zeros((n, 2), np.int32)
+        w = max(n, 1) if width is None else int(width)
+        self._chk(self._L.vrt_shade_rays(self._h, n, o.ctypes.data if n else None, stride, d.ctypes.data if n else None, w,
+                                         int(mode), int(first_sample) & 0xFFFFFFFF, int(n_samples), rgba.ctypes.data,
+                                         idd.ctypes.data))
+        return rgba, idd
+
+    def shade_rays_device(self, n, d_origins, origin_stride, d_dirs, d_rgba, d_id, mode=MODE_FULL, width=None, first_sample=0,
+                          n_samples=1, stream=None):
+        """vrt_shade_rays_device: DEVICE buffers (d_rgba: n x 4 bytes, d_id: n x 2 int32, either may be None), enqueued on
+        `stream`"""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 30:
+            raise ValueError(f"n: expected an integer in [0, 2^30], got {n!r}")
+        w = max(int(n), 1) if width is None else int(width)
+        self._chk(self._L.vrt_shade_rays_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, int(mode),
+                                                int(first_sample) & 0xFFFFFFFF, int(n_samples), d_rgba, d_id, stream))
 
     def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False, adaptive=None):
         """(Re)start the progressive accumulation of `mode` at sample index `first_sample` (vrt_accum_begin_ex); jitter=True

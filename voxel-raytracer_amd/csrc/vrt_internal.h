@@ -6,6 +6,7 @@
 //   vrt_display.cpp    the display pass and the fused frame call
 //   vrt_patch.cpp      edits without re-upload: patch plan / apply / batches / compaction
 //   vrt_query.cpp      world queries on the device tree: ray casts (picking), voxel lookups
+//   vrt_rays.cpp       pathTrace for ray batches of the caller's (vrt_shade_rays): arguments without a camera, the staging buffers
 //   vrt_accum.cpp      progressive multi-sample accumulation (any mode, sub-pixel jitter): begin / add / resolve, the restart rule
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
@@ -88,6 +89,9 @@ struct vrt_ctx {
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     void *d_query = nullptr;
     size_t query_bytes = 0;
+    // device buffers behind vrt_shade_rays (vrt_rays.cpp)
+    void *d_rays = nullptr;
+    size_t rays_bytes = 0;
     // edits collected between vrt_patch_begin and vrt_patch_end: applied to the host structures at once, sent to the
     // device together
     struct PatchBatch {

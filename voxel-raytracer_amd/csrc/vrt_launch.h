@@ -4,6 +4,7 @@
 #include "vrt_internal.h"
 #include "vrt_query.h"
 #include "vrt_accum.h"
+#include "vrt_rays.h"
 
 namespace vrt {
 namespace launch {
@@ -78,6 +79,12 @@ hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s);
 hipError_t adaptive_resolve(const accum::Resolve &q, hipStream_t s);
 hipError_t adaptive_tiles(const accum::Tiles &t, hipStream_t s);
 hipError_t adaptive_counts(const accum::Counts &c, hipStream_t s);
+
+// vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
+// rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
+// starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
+hipError_t shade_rays(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s,
+                      hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

@@ -1,0 +1,151 @@
+// vrt_rays.cpp -- vrt_shade_rays / vrt_shade_rays_device (include/vrt.h): pathTrace for ray batches of the caller's. Call-order and
+// argument checks, the kernel arguments -- the scene and the uniforms as a frame launch carries them, and nothing of a camera: no
+// eye lookup, first lookup, ray table, miss mask, tightened root or tile order -- and the device buffers the host form stages
+// through. Reads no camera, lens or accumulation state and writes none.
+#include "vrt_internal.h"
+#include "vrt_launch.h"
+
+#include <cmath>
+#include <cstring>
+
+using namespace vrt_internal;
+
+namespace {
+
+int check(vrt_ctx *c, size_t n, const void *origins, int origin_stride, const void *dirs, int width, int mode, uint32_t n_samples,
+          const void *out_rgba, const void *out_id, const char *what) {
+    if (!c) return VRT_E_INVALID;
+    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no octree uploaded (call vrt_upload_octree first)");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
+    if (origin_stride != 0 && origin_stride != 3) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": origin_stride must be 0 or 3");
+    if (mode != VRT_MODE_PRIMARY && mode != VRT_MODE_PRIMARY_SHADOW && mode != VRT_MODE_FULL)
+        return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown mode");
+    if (width < 1) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": width must be at least 1");
+    if (n_samples < 1u || n_samples > (1u << 24)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": 1 to 2^24 samples per call");
+    if (n > ((size_t)1 << 30)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": at most 2^30 rays per call");
+    if (!out_rgba && !out_id) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": both outputs are null");
+    if (n > 0 && (!origins || !dirs)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null buffer");
+    return VRT_OK;
+}
+
+// The launch: KArgs as enqueue() (vrt_dispatch.cpp) fills them for a frame, without anything derived from an eye
+int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const float *d_dirs, int width, int mode, uint32_t first_sample,
+          uint32_t n_samples, uint32_t *d_rgba, int2 *d_id, hipStream_t s) {
+    const int ra = ensure_analysis(c);
+    if (ra) return ra;
+    Variant v = *find_variant(c->variant);
+    if (v.trav >= 3 && !c->wide_ok) v.trav = 2;          // wide layout not expressible for this scene: record-array kernels
+    if (v.trav == 2 && c->unit_internal) v.trav = 1;     // precondition of vrt_kernels.hip.h not met: explicit-AABB kernels
+    vrt::KArgs a;
+    vrt::ViewSet vs;
+    std::memset(&a, 0, sizeof a);
+    std::memset(&vs, 0, sizeof vs);   // no first lookup (first_valid 0), no ray tables (gen_fast 0), no miss mask
+    a.n_views = 1;
+    a.voxel_scale = c->params.voxel_scale;
+    for (int i = 0; i < 3; ++i) {
+        a.wmin[i] = c->params.world_min[i];
+        a.wmax[i] = c->params.world_max[i];
+        a.light_dir[i] = c->params.light_dir[i];
+        a.highlighted[i] = c->params.highlighted[i];
+        const float d = a.light_dir[i];   // comp:335-345 on the launch's one light direction
+        a.light_inv[i] = (fabsf(d) < 1e-8f) ? 1e20f : 1.0f / d;
+        a.light_push[i] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * 0.001f;
+        a.light_dpos[i] = d > 0.0f ? 1 : 0;
+        a.light_dposf[i] = d > 0.0f ? 1.0f : 0.0f;
+    }
+    for (int i = 0; i < 4; ++i) a.global_light[i] = c->params.global_light[i];
+    a.shade_fast = 1;   // div_pi_inrange(): the lights' range, as enqueue() checks it
+    for (int i = 0; i < 3; ++i)
+        if (!(fabsf(a.global_light[i]) <= 1073741824.0f) || !(fabsf(a.light_dir[i]) <= 1073741824.0f)) a.shade_fast = 0;
+    a.tex_dim = (int)c->info.tex_dim;
+    a.width = width;
+    a.height = (int)((n + (size_t)width - 1) / (size_t)width);
+    a.n_rows = a.height;
+    a.tile_rows = a.height;
+    a.row_mode = 1;
+    a.nodes = c->d_nodes;
+    a.n_records = c->info.n_records;
+    a.cells = c->d_cells;
+    a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
+    a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
+    for (int k = 0; k < 3; ++k) a.root0_min[k] = a.n_roots ? c->wide.roots[0].origin[k] : 0;
+    a.root_table = c->d_roots;
+    a.root0_node = a.n_roots ? c->wide.roots[0].node : 0u;
+    a.root0_shift = a.n_roots ? c->wide.roots[0].shift : 0;
+    // the world is empty outside wide root 0: a property of the tree, applied by find() per ray (never to a first lookup); the
+    // tighter root is a property of a view's eye and is not taken
+    a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
+
+    vrt::rays::Args q;
+    q.origins = d_origins;
+    q.dirs = d_dirs;
+    q.out_rgba = d_rgba;
+    q.out_id = d_id;
+    q.n = (uint32_t)n;
+    q.origin_stride = origin_stride;
+    q.width = (uint32_t)width;
+    q.first = first_sample;
+    q.n_samples = mode == VRT_MODE_FULL ? n_samples : 1u;   // the other modes draw no random number: every sample is the same
+    const uint32_t grid = vrt::rays::plan(q.n, q.width, q.tiles_x);
+    const bool prof = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
+    const hipEvent_t ev0 = prof ? c->prof_events[2 * c->prof_count] : nullptr;
+    const hipEvent_t ev1 = prof ? c->prof_events[2 * c->prof_count + 1] : nullptr;
+    const hipError_t e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, ev0, ev1);
+    if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (prof) ++c->prof_count;
+    return VRT_OK;
+}
+
+// device buffers behind the host form, kept by the context and grown, never shrunk
+int ensure_rays_scratch(vrt_ctx *c, size_t bytes) {
+    if (bytes <= c->rays_bytes) return VRT_OK;
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_rays) VRT_HIP(c, hipFree(c->d_rays));
+    c->d_rays = nullptr;
+    c->rays_bytes = 0;
+    const size_t grown = bytes + bytes / 2;
+    VRT_HIP(c, hipMalloc(&c->d_rays, grown));
+    c->rays_bytes = grown;
+    return VRT_OK;
+}
+
+inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+}  // namespace
+
+extern "C" {
+
+int vrt_shade_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride, const float *dirs, int width, int mode,
+                   uint32_t first_sample, uint32_t n_samples, uint8_t *out_rgba8, int32_t *out_id_dist) {
+    int r = check(c, n, origins, origin_stride, dirs, width, mode, n_samples, out_rgba8, out_id_dist, "vrt_shade_rays");
+    if (r || n == 0) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
+    const size_t rgba_bytes = out_rgba8 ? n * 4 : 0, id_bytes = out_id_dist ? n * 8 : 0;
+    r = ensure_rays_scratch(c, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + id_bytes);
+    if (r) return r;
+    char *base = static_cast<char *>(c->d_rays);
+    float *d_o = reinterpret_cast<float *>(base);
+    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
+    uint32_t *d_rgba = out_rgba8 ? reinterpret_cast<uint32_t *>(base + align256(o_bytes) + align256(d_bytes)) : nullptr;
+    int2 *d_id = out_id_dist ? reinterpret_cast<int2 *>(base + align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes)) : nullptr;
+    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
+    r = shade(c, n, d_o, origin_stride, d_d, width, mode, first_sample, n_samples, d_rgba, d_id, c->stream);
+    if (r) return r;
+    if (d_rgba) VRT_HIP(c, hipMemcpyAsync(out_rgba8, d_rgba, rgba_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d_id) VRT_HIP(c, hipMemcpyAsync(out_id_dist, d_id, id_bytes, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_shade_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, int mode,
+                          uint32_t first_sample, uint32_t n_samples, void *d_rgba8, void *d_id_dist, void *stream) {
+    const int r = check(c, n, d_origins, origin_stride, d_dirs, width, mode, n_samples, d_rgba8, d_id_dist, "vrt_shade_rays_device");
+    if (r || n == 0) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    return shade(c, n, static_cast<const float *>(d_origins), origin_stride, static_cast<const float *>(d_dirs), width, mode, first_sample,
+                 n_samples, static_cast<uint32_t *>(d_rgba8), static_cast<int2 *>(d_id_dist), stream ? (hipStream_t)stream : c->stream);
+}
+
+}  // extern "C"

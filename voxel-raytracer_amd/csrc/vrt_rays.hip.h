@@ -1,0 +1,144 @@
+// vrt_rays.hip.h -- pathTrace (comp:435-622) for rays the caller brings (include/vrt.h vrt_shade_rays): the fourth source of a
+// sample's ray, after the accumulation's corner, jitter and lens sources (vrt_accum.hip.h). RaySource reads ray i's origin and
+// direction from the caller's arrays, normalises the direction as pathTrace does on entry (comp:441: correctly rounded / and
+// sqrt -- a caller's direction is in no proven range, so none of the in-range forms), looks the medium up at the lane's own
+// floor(origin * u_voxelScale) (record_find()) and hands the LensRay to the shared trace_pixel<MODE, TRAV, false, true> /
+// full::trace_pixel_full<TRAV, false, true>: the march, the shading and the path tracer are the frame's, not copies.
+//
+// One ray per lane, 64-lane workgroups, no LDS, no barrier. Nothing here is "at the eye": the kernels get a View with no first
+// lookup, no ray tables and no miss mask, wide root 0 as uploaded (never tightened), and a traversal that is right for a start in
+// any medium (v4::TravAny, v3, or the record-array traversals). KArgs::root0_only stays: find() applies it only to a ray whose own
+// walk has been inside wide root 0, that moves forward on every axis and is in empty space -- conditions on the ray, not on where
+// it started -- and never to a ray's first lookup ("Ray batches").
+//
+// Lane-to-ray mapping (ray_of_lane()): a batch that is an image -- rays::plan(): width >= 8 and at least two rows -- is cut into
+// the frame kernels' 8 x 8 tiles, one per wave, because neighbouring pixels walk the same nodes; any other batch is a list, 64
+// consecutive rays per wave. Either way ray i's random numbers are those of pixel (i % width, i / width).
+#pragma once
+#include "vrt_full.hip.h"
+#include "vrt_rays.h"
+
+namespace vrt {
+namespace rays {
+
+// The kernel's third argument, re-read from the kernarg segment where it is used (as late_args() re-reads the first): it follows
+// KArgs and ViewSet at its natural alignment
+typedef const Args __attribute__((address_space(4))) *LateRays;
+VRT_DEV LateRays late_rays() {
+    constexpr size_t kViews = (sizeof(KArgs) + alignof(ViewSet) - 1) / alignof(ViewSet) * alignof(ViewSet);
+    constexpr size_t kOffset = (kViews + sizeof(ViewSet) + alignof(Args) - 1) / alignof(Args) * alignof(Args);
+    const char __attribute__((address_space(4))) *p = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + kOffset;
+    asm volatile("" : "+s"(p));
+    return (LateRays)p;
+}
+
+// This lane's ray i and its RNG pixel; false past the end of the batch
+VRT_DEV bool ray_of_lane(const Args &q, uint32_t &i, int &px, int &py) {
+    const uint32_t lane = threadIdx.x & 63u;
+    if (q.tiles_x) {   // wave-uniform
+        const uint32_t ty = blockIdx.x / q.tiles_x, tx = blockIdx.x - ty * q.tiles_x;
+        const uint32_t x = tx * 8u + (lane & 7u), y = ty * 8u + (lane >> 3);
+        const uint64_t at = (uint64_t)y * q.width + x;   // the last tile row may reach 8 * width past n: beyond 32 bits
+        i = (uint32_t)at;
+        px = (int)x; py = (int)y;
+        return x < q.width && at < (uint64_t)q.n;
+    }
+    i = blockIdx.x * 64u + lane;
+    const uint32_t y = i / q.width;
+    px = (int)(i - y * q.width); py = (int)y;
+    return i < q.n;
+}
+
+struct RaySource {
+    // ray i as pathTrace takes it: eye0 / eye1 = the raw leaf words of the node that holds floor(origin * u_voxelScale)
+    static VRT_DEV LensRay load(const KArgs &a, const Args &q, uint32_t i) {
+        LensRay r;
+        if (q.origin_stride == 0) {   // one origin for the batch: scalar loads
+            r.o = F3{q.origins[0], q.origins[1], q.origins[2]};
+        } else {
+            const float *o = q.origins + (size_t)i * 3u;
+            r.o = F3{o[0], o[1], o[2]};
+        }
+        const float *d = q.dirs + (size_t)i * 3u;
+        const F3 dir{d[0], d[1], d[2]};
+        r.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));   // comp:441
+        record_find(a, floor_i3(scale3(r.o, a.voxel_scale)), r.eye0, r.eye1);
+        return r;
+    }
+};
+
+VRT_DEV void store(uint32_t i, uint32_t rgba, int2 idd) {
+    const LateRays lq = late_rays();
+    uint32_t *out_rgba = lq->out_rgba;
+    int2 *out_id = lq->out_id;
+    if (out_rgba) out_rgba[i] = rgba;
+    if (out_id) out_id[i] = idd;
+}
+
+// VRT_MODE_PRIMARY / _PRIMARY_SHADOW: no random number is drawn, so every sample is the same and one trace serves any n_samples
+template <int MODE, class TRAV, int WPE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_kernel(const KArgs a, const ViewSet vs, const Args q) {
+    typename TRAV::Ctx tc_;
+    TRAV::block_init(a, tc_);
+    uint32_t i;
+    int px, py;
+    if (!ray_of_lane(q, i, px, py)) return;
+    const LensRay lr = RaySource::load(a, q, i);
+    uint32_t rgba;
+    int2 idd;
+    LateOut lo;
+    trace_pixel<MODE, TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, nullptr, nullptr, 0u, &lr);
+    store(i, rgba, idd);
+}
+
+// VRT_MODE_FULL, the general stack kernel (right for any scene and any origin). LOOP: samples first .. first + n_samples - 1 looped
+// in the lane, the arguments and the ray re-read for every sample (held across the back edge they spill, vrt_accum.hip.h
+// loop_args()); the medium's two words stay in registers. The mean is accum_resolve_kernel's: (sum + n / 2) / n per channel of the
+// bytes each sample would store, alpha 255; the (voxel ID, dist) pair is the same for every sample.
+template <class TRAV, int WPE, bool LOOP>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_kernel(const KArgs a, const ViewSet vs, const Args q) {
+    typename TRAV::Ctx tc_;
+    TRAV::block_init(a, tc_);
+    uint32_t i;
+    int px, py;
+    if (!ray_of_lane(q, i, px, py)) return;
+    LensRay lr = RaySource::load(a, q, i);
+    uint32_t rgba;
+    int2 idd;
+    LateOut lo;
+    if constexpr (!LOOP) {
+        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
+    } else {
+        const uint32_t eye0 = lr.eye0, eye1 = lr.eye1;
+        uint32_t r = 0u, g = 0u, b = 0u;
+        const uint32_t n = q.n_samples;
+        for (uint32_t k = 0; k < n; ++k) {
+#ifdef __HIP_DEVICE_COMPILE__
+            const KArgs ak = *late_args();
+            const View vk = *late_view();
+            const Args qk = *late_rays();
+#else
+            const KArgs ak = a;
+            const View vk = vs.v[0];
+            const Args qk = q;
+#endif
+            const float *o = qk.origins + (qk.origin_stride ? (size_t)i * 3u : (size_t)0);
+            const float *d = qk.dirs + (size_t)i * 3u;
+            const F3 dir{d[0], d[1], d[2]};
+            LensRay lk;
+            lk.o = F3{o[0], o[1], o[2]};
+            lk.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));
+            lk.eye0 = eye0; lk.eye1 = eye1;
+            full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
+            r += rgba & 0xffu;
+            g += (rgba >> 8) & 0xffu;
+            b += (rgba >> 16) & 0xffu;
+        }
+        const uint32_t h = n >> 1;
+        rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
+    }
+    store(i, rgba, idd);
+}
+
+}  // namespace rays
+}  // namespace vrt

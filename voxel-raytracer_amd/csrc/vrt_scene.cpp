@@ -198,6 +198,7 @@ void vrt_destroy(vrt_ctx *c) {
     if (c->d_id) (void)hipFree(c->d_id);
     if (c->d_shown) (void)hipFree(c->d_shown);
     if (c->d_query) (void)hipFree(c->d_query);
+    if (c->d_rays) (void)hipFree(c->d_rays);
     (void)hipFree(c->accum.d_sums);
     (void)hipFree(c->accum.d_pass1);
     (void)hipFree(c->accum.d_id);
