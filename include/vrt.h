@@ -211,7 +211,7 @@ int vrt_shade_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int ori
  * ..., first + n - 1 (sample indices modulo 2^32) as
  * one integer sum per pixel and channel of the unorm8 bytes each sample would store -- exact, whatever chunks they were added
  * in -- and resolves to (sum + n / 2) / n per channel, alpha 255: at n = 1 the sample itself. Averaging clamped bytes is what a
- * display of the successive frames shows. The resolved (voxel ID, dist) image is the frame's: no sample changes it.
+ * display of the successive frames shows (the mean of the unclamped colours: vrt_accum_keep_hdr below). The resolved (voxel ID, dist) image is the frame's: no sample changes it.
  *
  * vrt_accum_begin     (re)starts with zero samples; allocates (grows) the accumulation's device buffers.
  * vrt_accum_add       enqueues n_samples more on the context's stream and stores the new count in *total_out (may be NULL).
@@ -310,6 +310,49 @@ int vrt_set_lens(vrt_ctx *ctx, float aperture, float focus_distance);
 int vrt_accum_begin_adaptive(vrt_ctx *ctx, int width, int height, int mode, uint32_t first_sample, uint32_t flags,
                              uint32_t min_samples, uint32_t max_samples, uint32_t tolerance);
 int vrt_accum_counts(vrt_ctx *ctx, uint32_t *out_counts);
+
+/* HDR accumulation: float64 sums of the samples' unclamped colours, a float resolve and a tone map. The accumulations above
+ * average the unorm8 bytes, so every sample brighter than 1 -- an emitter (comp:575-581: colour * light * 10), the sky behind a
+ * bounce (comp:493: sky * 3 / PI) -- is clamped before it enters the mean: mean(min(c, 1)), where a still wants min(mean(c), 1).
+ *
+ * vrt_accum_keep_hdr(ctx, 1) makes the accumulations begun after it keep HDR sums too. It is context state, like the lens, read
+ * by the next vrt_accum_begin / _begin_ex / _begin_adaptive; it is not part of the restart rule, and changing it leaves a running
+ * accumulation as it was begun. Default 0. VRT_E_INVALID unless enable is 0 or 1.
+ *
+ * All arithmetic below: every operation rounded on its own, no contraction.
+ *  1. The HDR sample. Sample k's HDR value is the three floats c the sample's unorm8 store receives (the shader's finalColor.rgb,
+ *     comp:645), each mapped by h(c) = min(max(0, c), 65504.0f) with min(a, b) = b < a ? b : a and max(a, b) = a < b ? b : a --
+ *     the conventions of the unorm8 store, the zero first, so that NaN goes to +0 (0 < NaN is false). unorm8(h(c)) == unorm8(c)
+ *     for every float c (a NaN stores byte 0). The same in all three modes and for the corner, jittered and thin-lens samples.
+ *  2. The sums. An accumulation begun with HDR on keeps everything it keeps otherwise -- the integer sums, and when adaptive the
+ *     counts and Q; the adaptive rule stays on the bytes -- and three float64 sums per pixel, which start at +0.0 and take
+ *     sum = sum + (double)h(c) once per sample the pixel takes, in sample-index order. They continue across vrt_accum_add calls
+ *     (3 + 5 samples equal 8 bit for bit); a restart zeroes them. float64: a float32 sum stalls long before the 2^24-sample cap,
+ *     and m * c is exact in a double for a float c and m <= 2^24, so a pixel whose every sample is the same float adds
+ *     (double)c * k for k samples at once and gets the k sequential adds' result.
+ *  3. The resolve. mean = (float)(sum / (double)n_p) per channel, n_p the pixel's own count (the accumulation's when not adaptive).
+ *  4. The tone map, per channel on the float mean x with exposure e:
+ *        VRT_TONEMAP_CLAMP     y = e * x
+ *        VRT_TONEMAP_REINHARD  x' = e * x;  y = x' / (1.0f + x')
+ *     and the bytes are unorm8(y), alpha 255. tm == NULL: VRT_TONEMAP_CLAMP with exposure 1.
+ *
+ * vrt_accum_resolve_hdr   the float means [H][W][3], the tone-mapped rgba8 [H][W][4] and the display pass of vrt_denoise on those
+ *                         bytes with the accumulation's id_dist image (as vrt_accum_resolve runs it), into host buffers (any may
+ *                         be NULL); synchronous.
+ * vrt_accum_resolve_hdr_device  the same into device buffers, enqueued on `stream` (NULL: the context's), ordered against the adds
+ *                         as vrt_accum_resolve_device is; d_shown_rgba8 needs d_rgba8.
+ * VRT_E_STATE: no begin, no sample yet, or the accumulation was begun without HDR. VRT_E_INVALID: an unknown op, an exposure that
+ * is not finite or not > 0, d_shown_rgba8 without d_rgba8.
+ * With HDR off nothing changes: behaviour, buffers and kernels are those of the accumulations above. With HDR on,
+ * vrt_accum_resolve, _resolve_device and vrt_accum_counts return exactly what the same accumulation without HDR returns; the
+ * accumulation takes 36 bytes per pixel more (the sums, and the frame's float colour for the pixels whose samples all equal it).
+ * Frames, views, shards, vrt_multi and vrt_shade_rays have no float output. */
+int vrt_accum_keep_hdr(vrt_ctx *ctx, int enable);
+#define VRT_TONEMAP_CLAMP 0
+#define VRT_TONEMAP_REINHARD 1
+typedef struct vrt_tonemap { int32_t op; float exposure; } vrt_tonemap;
+int vrt_accum_resolve_hdr(vrt_ctx *ctx, float *out_rgb, const vrt_tonemap *tm, uint8_t *out_rgba8, uint8_t *out_shown_rgba8);
+int vrt_accum_resolve_hdr_device(vrt_ctx *ctx, void *d_rgb, const vrt_tonemap *tm, void *d_rgba8, void *d_shown_rgba8, void *stream);
 
 /* Column-major mat4 x2 + vec4, exactly the std140 Camera block (comp:17-21). */
 int vrt_set_camera(vrt_ctx *ctx, const float inv_projection[16], const float inv_view[16],

@@ -17,6 +17,13 @@ time, the fraction of pixels still active after it (vrt_accum_counts) and its ra
 accumulation (the median of --reps runs of each).
 
     python3 tools/accum_rate.py --adaptive 4 64 24 --out profiles/accum_adaptive_rate.jsonl
+
+--hdr measures every accumulation a second time as an HDR accumulation (vrt_accum_keep_hdr: float64 sums of the samples' float
+colours beside the integer sums) and records its add time and ratio beside the plain one (hdr_add_ms, hdr_vs_plain), and the
+time of one vrt_accum_resolve_hdr_device beside vrt_accum_resolve_device (resolve_ms, hdr_resolve_ms).
+
+    python3 tools/accum_rate.py --hdr --out profiles/accum_hdr_rate.jsonl
+    python3 tools/accum_rate.py --hdr --mode primary primary_shadow full --jitter --out profiles/accum_hdr_jitter_rate.jsonl
 """
 import argparse
 import json
@@ -50,6 +57,7 @@ def main():
     ap.add_argument("--adaptive", nargs=3, type=int, metavar=("MIN", "MAX", "TOL"), help="adaptive accumulations (see above)")
     ap.add_argument("--adaptive-lens", nargs=2, type=float, default=(0.1, 40.0), metavar=("APERTURE", "FOCUS"))
     ap.add_argument("--rounds", type=int, default=32)
+    ap.add_argument("--hdr", action="store_true", help="each accumulation again with HDR sums, beside the plain one")
     args = ap.parse_args()
     V = vrt_import.vrt()
     if args.adaptive:
@@ -58,6 +66,7 @@ def main():
     W, H = 1920, 1080
     ctx = V.Context(0)
     d_rgba, d_id = ctx.device_alloc(W * H * 4), ctx.device_alloc(W * H * 8)
+    d_rgb = ctx.device_alloc(W * H * 12) if args.hdr else None
     rows = []
     for name, (m, pos, yaw, pitch) in SCENES.items():
         if m == "room":
@@ -80,16 +89,33 @@ def main():
                 base_ms = None
                 for lens in [None] + args.lens:
                     ctx.set_lens(*(lens or (0.0, 1.0)))
-                    ctx.accum_begin(W, H, 0, mode=mode, jitter=args.jitter)
-                    ctx.accum_add(n)          # the first add: pass 1 or the frame once per accumulation, code object load
-                    ctx.synchronize()
-                    ts = []
-                    for _ in range(args.reps):
-                        t0 = time.perf_counter()
-                        ctx.accum_add(n)
+
+                    def add_ms(hdr):
+                        ctx.accum_begin(W, H, 0, mode=mode, jitter=args.jitter, **({"hdr": True} if hdr else {}))
+                        ctx.accum_add(n)          # the first add: pass 1 or the frame once per accumulation, code object load
                         ctx.synchronize()
-                        ts.append((time.perf_counter() - t0) * 1e3)
-                    ms = float(np.median(ts))
+                        ts = []
+                        for _ in range(args.reps):
+                            t0 = time.perf_counter()
+                            ctx.accum_add(n)
+                            ctx.synchronize()
+                            ts.append((time.perf_counter() - t0) * 1e3)
+                        return float(np.median(ts))
+
+                    def resolve_ms(hdr):
+                        ts = []
+                        for _ in range(args.reps + 1):
+                            t0 = time.perf_counter()
+                            if hdr:
+                                ctx.accum_resolve_hdr_device(d_rgb, d_rgba, None, "reinhard", 1.0)
+                            else:
+                                ctx.accum_resolve_device(d_rgba, None, None)
+                            ctx.synchronize()
+                            ts.append((time.perf_counter() - t0) * 1e3)
+                        return float(np.median(ts[1:]))
+
+                    ms = add_ms(False)
+                    plain_resolve = resolve_ms(False) if args.hdr else None
                     row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "n": n,
                            "add_ms": round(ms, 4), "n_frames_ms": round(n * frame_ms, 4), "frame_ms": round(frame_ms, 4),
                            "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
@@ -101,11 +127,17 @@ def main():
                         sel = V.lens_choice(tex, cp, iv, lens[0])
                         row.update(aperture=lens[0], focus=lens[1], side="shared" if sel["eye_shared"] and sel["first_shared"] else "per_lane",
                                    eye_shared=sel["eye_shared"], first_shared=sel["first_shared"], vs_lens_free=round(ms / base_ms, 3))
+                    if args.hdr:
+                        hms = add_ms(True)
+                        row.update(hdr_add_ms=round(hms, 4), hdr_vs_plain=round(hms / ms, 3), resolve_ms=round(plain_resolve, 4),
+                                   hdr_resolve_ms=round(resolve_ms(True), 4))
                     print(json.dumps(row), flush=True)
                     rows.append(row)
             ctx.set_lens(0.0, 1.0)
     ctx.device_free(d_rgba)
     ctx.device_free(d_id)
+    if d_rgb:
+        ctx.device_free(d_rgb)
     ctx.close()
     if args.out:
         with open(args.out, "w") as f:

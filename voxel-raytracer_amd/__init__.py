@@ -25,6 +25,13 @@ OPT_RAY_TABLES, OPT_EMPTY_OCTANTS, OPT_DISPLAY_KERNEL, OPT_FULL_OPAQUE, OPT_HEAV
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL = 0, 1, 2
 MODES = {"primary": MODE_PRIMARY, "primary_shadow": MODE_PRIMARY_SHADOW, "full": MODE_FULL}
 ACCUM_JITTER = 1   # vrt_accum_begin_ex flags (include/vrt.h VRT_ACCUM_JITTER)
+TONEMAP_CLAMP, TONEMAP_REINHARD = 0, 1   # include/vrt.h VRT_TONEMAP_*
+TONEMAPS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD}
+
+
+class Tonemap(C.Structure):
+    """include/vrt.h vrt_tonemap"""
+    _fields_ = [("op", C.c_int32), ("exposure", C.c_float)]
 
 
 class VrtError(RuntimeError):
@@ -271,6 +278,9 @@ def hip_lib():
         L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_accum_keep_hdr.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_accum_resolve_hdr.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_hdr_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
         _hip = L
     return _hip
 
@@ -862,11 +872,14 @@ class Context:
         self._chk(self._L.vrt_shade_rays_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, int(mode),
                                                 int(first_sample) & 0xFFFFFFFF, int(n_samples), d_rgba, d_id, stream))
 
-    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False, adaptive=None):
+    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False, adaptive=None, hdr=False):
         """(Re)start the progressive accumulation of `mode` at sample index `first_sample` (vrt_accum_begin_ex); jitter=True
         moves each sample's ray inside the pixel (VRT_ACCUM_JITTER: anti-aliased frames). adaptive=(min_samples, max_samples,
         tolerance) makes it adaptive (vrt_accum_begin_adaptive): accum_add then adds rounds, in which only the pixels the
-        stopping rule keeps active take a sample; accum_counts() reports them."""
+        stopping rule keeps active take a sample; accum_counts() reports them. hdr=True keeps float64 sums of the samples'
+        unclamped colours too (vrt_accum_keep_hdr, set for this begin): accum_resolve_hdr() resolves them."""
+        if not isinstance(hdr, (bool, np.bool_)) and not (isinstance(hdr, (int, np.integer)) and hdr in (0, 1)):
+            raise ValueError(f"hdr: expected a bool, got {hdr!r}")
         if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or mode not in (MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL):
             raise ValueError(f"mode: expected MODE_PRIMARY, MODE_PRIMARY_SHADOW or MODE_FULL, got {mode!r}")
         if not isinstance(jitter, (bool, np.bool_)) and not (isinstance(jitter, (int, np.integer)) and jitter in (0, 1)):
@@ -889,9 +902,11 @@ class Context:
                 raise ValueError(f"adaptive: need 2 <= min_samples <= max_samples <= 2^24, got {adaptive!r}")
             if not 0 <= tol <= 65535:
                 raise ValueError(f"adaptive tolerance: expected an integer in [0, 65535], got {tol!r}")
+            self._chk(self._L.vrt_accum_keep_hdr(self._h, 1 if hdr else 0))
             self._chk(self._L.vrt_accum_begin_adaptive(self._h, int(width), int(height), int(mode), int(first_sample),
                                                        ACCUM_JITTER if jitter else 0, lo, hi, tol))
         else:
+            self._chk(self._L.vrt_accum_keep_hdr(self._h, 1 if hdr else 0))
             self._chk(self._L.vrt_accum_begin_ex(self._h, int(width), int(height), int(mode), int(first_sample),
                                                  ACCUM_JITTER if jitter else 0))
         self._accum_shape = (int(height), int(width))
@@ -945,6 +960,38 @@ class Context:
     def accum_resolve_device(self, d_rgba, d_id, d_shown, stream=None):
         """vrt_accum_resolve_device: DEVICE buffers (any may be None; d_shown needs d_rgba), enqueued on `stream`"""
         self._chk(self._L.vrt_accum_resolve_device(self._h, d_rgba, d_id, d_shown, stream))
+
+    @staticmethod
+    def _tonemap(tonemap, exposure):
+        if tonemap not in TONEMAPS:
+            raise ValueError(f"tonemap: expected 'clamp' or 'reinhard', got {tonemap!r}")
+        if isinstance(exposure, bool) or not isinstance(exposure, (int, float, np.integer, np.floating)):
+            raise ValueError(f"exposure: expected a number, got {exposure!r}")
+        x = float(exposure)
+        e = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
+        if not (np.isfinite(e) and e > 0.0):
+            raise ValueError(f"exposure: expected a float32 value finite and > 0, got {exposure!r}")
+        return Tonemap(TONEMAPS[tonemap], float(e))
+
+    def accum_resolve_hdr(self, tonemap="clamp", exposure=1.0):
+        """An HDR accumulation's float resolve (vrt_accum_resolve_hdr) -> (rgb float32[H,W,3]: the mean of the samples' unclamped
+        colours; rgba8[H,W,4]: its tone-mapped bytes, 'clamp' (exposure * x) or 'reinhard' (x' / (1 + x'), x' = exposure * x);
+        shown rgba8[H,W,4]: the display pass on those bytes)."""
+        tm = self._tonemap(tonemap, exposure)
+        shape = getattr(self, "_accum_shape", None)
+        if shape is None:
+            raise VrtError("accum_resolve_hdr: no accumulation (call accum_begin first)")
+        h, w = shape
+        rgb = np.zeros((h, w, 3), np.float32)
+        rgba = np.zeros((h, w, 4), np.uint8)
+        shown = np.zeros((h, w, 4), np.uint8)
+        self._chk(self._L.vrt_accum_resolve_hdr(self._h, rgb.ctypes.data, C.byref(tm), rgba.ctypes.data, shown.ctypes.data))
+        return rgb, rgba, shown
+
+    def accum_resolve_hdr_device(self, d_rgb, d_rgba, d_shown, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_device: DEVICE buffers (any may be None; d_shown needs d_rgba), enqueued on `stream`"""
+        tm = self._tonemap(tonemap, exposure)
+        self._chk(self._L.vrt_accum_resolve_hdr_device(self._h, d_rgb, C.byref(tm), d_rgba, d_shown, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

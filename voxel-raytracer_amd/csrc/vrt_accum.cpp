@@ -6,6 +6,9 @@
 // and without jitter its bytes are every sample's. So does one with a thin lens (vrt_set_lens, aperture > 0).
 // An adaptive accumulation (vrt_accum_begin_adaptive) adds rounds instead of samples: the same paths with the kernels' adaptive
 // forms, its per-pixel counts and Q beside the sums, the resolve by each pixel's count, and vrt_accum_counts.
+// An HDR accumulation (vrt_accum_keep_hdr before the begin) keeps three float64 sums per pixel of the samples' float colours too:
+// the kernels' HDR forms, 24 + 12 bytes per pixel allocated only then, and vrt_accum_resolve_hdr's mean and tone map. Where the
+// samples are all one frame, that frame comes from the HDR frame kernel, which hands out its float colour.
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
@@ -61,6 +64,32 @@ int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_
     return VRT_OK;
 }
 
+// vrt_accum_resolve_hdr*: the call-order checks of a resolve, an HDR accumulation, a tone map the header defines
+int resolve_hdr_state(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
+    int r = resolve_state(c, what);
+    if (r) return r;
+    if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
+    if (tm) {
+        if (tm->op != VRT_TONEMAP_CLAMP && tm->op != VRT_TONEMAP_REINHARD) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown tone-map operator");
+        if (!(tm->exposure > 0.0f) || !(tm->exposure <= 3.402823466e38f))
+            return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": exposure must be finite and > 0");
+    }
+    return VRT_OK;
+}
+
+// float64 sums -> float mean into d_rgb, its tone-mapped rgba8 into d_rgba (either may be null), the display pass into d_shown
+int resolve_hdr_into(vrt_ctx *c, float *d_rgb, const vrt_tonemap *tm, void *d_rgba, void *d_shown, hipStream_t s) {
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if (d_rgb || d_rgba) {
+        const vrt::accum::HdrResolve q{ac.d_hsum, ac.d_sums, d_rgb, static_cast<uint32_t *>(d_rgba), ac.total, ac.adaptive ? 1u : 0u,
+                                       (uint32_t)px, tm ? tm->op : VRT_TONEMAP_CLAMP, tm ? tm->exposure : 1.0f};
+        VRT_HIP(c, vrt::launch::accum_resolve_hdr(q, s));
+    }
+    if (d_shown) return vrt_denoise(c, ac.width, ac.height, d_rgba, ac.d_id, d_shown, s);
+    return VRT_OK;
+}
+
 // vrt_accum_begin_ex, and with rule = {min, max, tolerance} vrt_accum_begin_adaptive
 int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, uint32_t flags, const uint32_t *rule) {
     int r = check_frame(c, width, height);
@@ -90,6 +119,13 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
         ac.sq_pixels = px;
         ac.tile_cap = tiles;
     }
+    if (c->accum_keep_hdr && px > ac.hdr_pixels) {   // the HDR state: the float64 sums, the corner frame's float colour
+        VRT_HIP(c, hipStreamSynchronize(c->stream));
+        ac.begun = false;
+        ac.hdr_pixels = 0;
+        if ((r = grow(c, ac.d_hsum, px * 24)) || (r = grow(c, ac.d_hframe, px * 12))) return r;
+        ac.hdr_pixels = px;
+    }
     if (!ac.added) VRT_HIP(c, hipEventCreateWithFlags(&ac.added, hipEventDisableTiming));
     if (!ac.read) VRT_HIP(c, hipEventCreateWithFlags(&ac.read, hipEventDisableTiming));
     ac.begun = true;
@@ -105,6 +141,7 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
     ac.min_samples = rule ? rule[0] : 0u;
     ac.max_samples = rule ? rule[1] : 0u;
     ac.tolerance = rule ? rule[2] : 0u;
+    ac.hdr = c->accum_keep_hdr;
     return VRT_OK;
 }
 
@@ -147,6 +184,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
     if (restart) {
         VRT_HIP(c, hipMemsetAsync(ac.d_sums, 0, (size_t)ac.width * (size_t)ac.height * 16, c->stream));
         if (ac.adaptive) VRT_HIP(c, hipMemsetAsync(ac.d_sq, 0, (size_t)ac.width * (size_t)ac.height * 8, c->stream));
+        if (ac.hdr) VRT_HIP(c, hipMemsetAsync(ac.d_hsum, 0, (size_t)ac.width * (size_t)ac.height * 24, c->stream));   // +0.0
         take_inputs(c, ac);
         ac.total = 0;
         ac.pass1 = false;
@@ -156,24 +194,38 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
     const bool lens = ac.lens[0] != 0.0f;   // a thin lens (vrt_set_lens): every sample has an origin of its own
     int r = VRT_OK;
     if ((jitter || lens || ac.mode != VRT_MODE_FULL) && !ac.frame) {   // the mode's unjittered frame, once per accumulation
-        r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream);
+        if (ac.hdr && !jitter && !lens) {   // every sample is that frame: its float colour too, from the HDR frame kernel
+            AccumStep fr{ac.first, 0u, false};
+            fr.hdr = fr.frame_only = true;
+            r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &fr);
+        } else {
+            r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream);
+        }
         ac.frame = r == VRT_OK;
     }
     if (r == VRT_OK && !jitter && !lens && ac.mode != VRT_MODE_FULL) {   // every sample is that frame
         const vrt::accum::Repeat q{ac.d_pass1, ac.d_sums, n_samples, (uint32_t)((size_t)ac.width * (size_t)ac.height)};
         hipError_t e;
         if (ac.adaptive) {   // each pixel's count goes to min(rounds, min_samples): no trace
-            vrt::accum::RepeatAdapt qa{};
+            vrt::accum::RepeatHdrOf<vrt::accum::RepeatAdapt> qa{};
             static_cast<vrt::accum::Repeat &>(qa) = q;
             qa.sq = ac.d_sq;
             qa.min = ac.min_samples;
-            e = vrt::launch::accum_repeat(qa, c->stream);
+            qa.hsum = ac.d_hsum;
+            qa.hframe = ac.d_hframe;
+            e = ac.hdr ? vrt::launch::accum_repeat_hdr(qa, c->stream) : vrt::launch::accum_repeat(qa, c->stream);
+        } else if (ac.hdr) {
+            vrt::accum::RepeatHdrOf<vrt::accum::Repeat> qh{};
+            static_cast<vrt::accum::Repeat &>(qh) = q;
+            qh.hsum = ac.d_hsum;
+            qh.hframe = ac.d_hframe;
+            e = vrt::launch::accum_repeat_hdr(qh, c->stream);
         } else {
             e = vrt::launch::accum_repeat(q, c->stream);
         }
         if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     } else if (r == VRT_OK) {
-        const AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive};
+        const AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again
@@ -215,6 +267,57 @@ int vrt_accum_resolve_device(vrt_ctx *c, void *d_rgba8, void *d_id_dist, void *d
         VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
     }
     r = resolve_into(c, d_rgba8, d_id_dist, d_shown_rgba8, s);
+    if (r) return r;
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.read, s));
+        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
+    }
+    return VRT_OK;
+}
+
+int vrt_accum_keep_hdr(vrt_ctx *c, int enable) {
+    if (!c) return VRT_E_INVALID;
+    if (enable != 0 && enable != 1) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_keep_hdr: enable must be 0 or 1");
+    c->accum_keep_hdr = enable == 1;
+    return VRT_OK;
+}
+
+int vrt_accum_resolve_hdr(vrt_ctx *c, float *out_rgb, const vrt_tonemap *tm, uint8_t *out_rgba8, uint8_t *out_shown_rgba8) {
+    int r = resolve_hdr_state(c, "vrt_accum_resolve_hdr", tm);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    r = ensure_scratch(c, px);
+    if (r) return r;
+    if (out_rgb && px > ac.hrgb_pixels) {   // the float image's way to the host, made at the first call that asks for it
+        VRT_HIP(c, hipStreamSynchronize(c->stream));
+        ac.hrgb_pixels = 0;
+        if ((r = grow(c, ac.d_hrgb, px * 12))) return r;
+        ac.hrgb_pixels = px;
+    }
+    const bool want_rgba = out_rgba8 || out_shown_rgba8;
+    r = resolve_hdr_into(c, out_rgb ? ac.d_hrgb : nullptr, tm, want_rgba ? c->d_rgba : nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
+    if (r) return r;
+    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, ac.d_hrgb, px * 12, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_shown_rgba8) VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_accum_resolve_hdr_device(vrt_ctx *c, void *d_rgb, const vrt_tonemap *tm, void *d_rgba8, void *d_shown_rgba8, void *stream) {
+    int r = resolve_hdr_state(c, "vrt_accum_resolve_hdr_device", tm);
+    if (r) return r;
+    if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_hdr_device: the display pass needs d_rgba8");
+    VRT_HIP(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    Accum &ac = c->accum;
+    if (s != c->stream) {   // as vrt_accum_resolve_device orders itself against the adds
+        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
+        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
+    }
+    r = resolve_hdr_into(c, static_cast<float *>(d_rgb), tm, d_rgba8, d_shown_rgba8, s);
     if (r) return r;
     if (s != c->stream) {
         VRT_HIP(c, hipEventRecord(ac.read, s));

@@ -68,8 +68,41 @@ struct AdaptArgs : Args {
     const uint32_t *n_tiles;     // ... and how many
     uint32_t min, max, tol;      // the rule
 };
-template <bool ADAPT>
-using ArgsOf = typename std::conditional<ADAPT, AdaptArgs, Args>::type;
+
+// ---- HDR accumulation (include/vrt.h vrt_accum_keep_hdr) ----
+// Beside everything above, three float64 sums per pixel of the samples' unclamped float colours, h(c) = min(max(c, 0), kHdrMax)
+// each, added in sample order. The kernels' template parameter HDR picks the argument type that carries them, so the other
+// kernels keep their arguments (and their code).
+constexpr float kHdrMax = 65504.0f;
+template <class BASE>
+struct HdrOf : BASE {
+    double *hsum;                // 3 doubles per pixel, row-major: the R, G, B sums of h(c)
+    const float *hframe;         // 3 floats per pixel: the corner frame's float colour (bounce kernel: pass 1's), where one was made
+};
+template <bool ADAPT, bool HDR = false>
+using ArgsOf = typename std::conditional<HDR, HdrOf<typename std::conditional<ADAPT, AdaptArgs, Args>::type>,
+                                         typename std::conditional<ADAPT, AdaptArgs, Args>::type>::type;
+using HdrArgs = HdrOf<AdaptArgs>;   // what the dispatcher fills; the launch functions pass the kernel its own slice
+
+// hdr_frame_kernel: where the corner frame's bytes, id_dist and float colour go
+struct HdrFrame {
+    uint32_t *out_rgba;
+    int2 *out_id;
+    float *hframe;
+};
+
+// The HDR resolve: mean = (float)(sum / (double)n_p), then the tone map and the byte pack, in one pass.
+struct HdrResolve {
+    const double *hsum;
+    const uint32_t *sums;        // adaptive: the pixel's own count is its fourth word
+    float *out_rgb;              // 3 floats per pixel, or null
+    uint32_t *out_rgba;          // or null
+    uint32_t n;                  // samples in the sums (not adaptive)
+    uint32_t adaptive;
+    uint32_t pixels;
+    int32_t op;                  // VRT_TONEMAP_*
+    float exposure;
+};
 
 // Before each round of a one-sample kernel: the 8 x 8 tiles of the frame that hold an active pixel -> tiles[0 .. *n_tiles)
 struct Tiles {
@@ -95,6 +128,12 @@ struct Counts {
 struct RepeatAdapt : Repeat {
     uint64_t *sq;
     uint32_t min;
+};
+// ... and of HDR accumulations: the frame's float colour beside its bytes
+template <class BASE>
+struct RepeatHdrOf : BASE {
+    double *hsum;
+    const float *hframe;
 };
 
 // Where a sample's ray comes from (vrt_accum.hip.h CornerSource, JitterSource, LensSource): the pixel's corner, the jittered ray

@@ -20,12 +20,19 @@
 //   one sample per launch, the general full tracer  full_accum_kernel<CornerSource / JitterSource / LensSource, ...>
 // The corner source has kernels of its own where a sample does not depend on its ray: a primary mode's every sample is the frame
 // (repeat_kernel), and an opaque scene's pass 1 runs once per accumulation (bounce_accum_kernel). Then the resolve:
-// accum_resolve_kernel.
+// accum_resolve_kernel (vrt_accum_state.hip.h, with the other kernels that only read or list the state).
 //
 // Adaptive accumulations (include/vrt.h vrt_accum_begin_adaptive) take the same kernels with the template parameter ADAPT = true:
 // each lane reads its pixel's state (sums, its count n in the fourth word, Q) once, takes a round's sample only while
 // adaptive_active() holds, and writes the state back once. The sample-looped kernels leave the loop at the pixel's stop;
 // the one-sample kernels trace the tiles compact_tiles_kernel listed for the round and leave inactive lanes idle.
+//
+// HDR accumulations (include/vrt.h vrt_accum_keep_hdr) take the same kernels with the template parameter HDR = true: beside the
+// bytes, the float colour each sample's unorm8() receives goes, clamped by hdr_value(), into three float64 sums per pixel, one
+// add per sample in sample order -- so a lane reads its pixel's sums before its first sample and writes them after its last.
+// Where every sample of a pixel is the same float c (repeat_kernel, the bounce kernel's sky and emissive pixels), k samples add
+// (double)c * k: m * c is exact in a double for m <= 2^24, so the product equals the k adds. Those routes read the float from
+// hdr_frame_kernel's image, which replaces the frame (or pass 1) they otherwise take the bytes from. Both, and hdr_resolve_kernel: vrt_accum_hdr.hip.h.
 #pragma once
 #include "vrt_accum.h"
 #include "vrt_full.hip.h"
@@ -77,6 +84,42 @@ VRT_DEV void add_repeat(uint32_t rgba, uint32_t k, PixelState &p) {
     p.r += r * k; p.g += g * k; p.b += b * k;
     p.n += k;
     p.q += (uint64_t)(l * l) * k;
+}
+
+// ---- HDR sums (HDR = true) ----
+struct HdrSum { double r, g, b; };
+
+// h(c) of include/vrt.h: [0, kHdrMax], NaN -> +0 (0 < NaN is false); unorm8(hdr_value(c)) == unorm8(c) for every float
+VRT_DEV float hdr_value(float c) { return fmin_c(fmax_c(0.0f, c), kHdrMax); }
+
+VRT_DEV HdrSum load_hdr(const double *hsum, size_t o) {
+    const double *p = hsum + o * 3;
+    return HdrSum{p[0], p[1], p[2]};
+}
+VRT_DEV void store_hdr(double *hsum, size_t o, const HdrSum &h) {
+    double *p = hsum + o * 3;
+    p[0] = h.r; p[1] = h.g; p[2] = h.b;
+}
+VRT_DEV void add_hdr(const float *fc, HdrSum &h) {
+    h.r = h.r + (double)hdr_value(fc[0]);
+    h.g = h.g + (double)hdr_value(fc[1]);
+    h.b = h.b + (double)hdr_value(fc[2]);
+}
+// k more samples equal to fc, for a pixel whose every sample is fc (see above)
+VRT_DEV void add_hdr_repeat(const float *fc, uint32_t k, HdrSum &h) {
+    h.r = h.r + (double)hdr_value(fc[0]) * (double)k;
+    h.g = h.g + (double)hdr_value(fc[1]) * (double)k;
+    h.b = h.b + (double)hdr_value(fc[2]) * (double)k;
+}
+
+// The sample-looped kernels keep a lane's three float64 sums in LDS across the loop (24 bytes per lane), as the bounce kernel keeps
+// its state, rather than six more live registers at budgets of 72 and 80 (what the HDR forms still spill: profiles/accum_resource_usage.txt)
+VRT_DEV void lds_put_hdr(volatile double *p, int n, const HdrSum &h) { p[0] = h.r; p[n] = h.g; p[2 * n] = h.b; }
+VRT_DEV HdrSum lds_get_hdr(volatile double *p, int n) { return HdrSum{p[0], p[n], p[2 * n]}; }
+VRT_DEV void lds_add_hdr(volatile double *p, int n, const float *fc) {
+    p[0] = p[0] + (double)hdr_value(fc[0]);
+    p[n] = p[n] + (double)hdr_value(fc[1]);
+    p[2 * n] = p[2 * n] + (double)hdr_value(fc[2]);
 }
 
 VRT_DEV size_t pixel_offset(const KArgs &a, int px, int py) { return (size_t)py * (size_t)a.width + (size_t)px; }
@@ -145,8 +188,8 @@ struct LensSource {
 
 // q.n samples q.first, q.first + 1, ... of MODE 0 or 1, looped in the lanes: the traversal the frame kernel would take
 // (trace_kernel's 8 x 8 tiles, its eye lookup and empty-octant proofs: the eye does not move), the shadow ray in MODE 1
-template <class SRC, int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT, class... L>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const L... lens) {
+template <class SRC, int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT, bool HDR, class... L>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const L... lens) {
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
@@ -154,31 +197,39 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     if (!frame_pixel<BLOCK>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
     PixelState st{};
+    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? BLOCK : 1];   // (HDR = false: never touched, and dropped)
+    volatile double *vs_hsum = &s_hsum[0][HDR ? threadIdx.x : 0];
     if constexpr (ADAPT) st = load_state(q, pixel_offset(a, px, py));
+    if constexpr (HDR) lds_put_hdr(vs_hsum, BLOCK, load_hdr(q.hsum, pixel_offset(a, px, py)));
     for (uint32_t k = 0; k < q.n; ++k) {
         if constexpr (ADAPT)
             if (!state_active(q.min, q.max, q.tol, st)) break;
         uint32_t rgba;
         int2 idd;
         LateOut lo;
+        float fc[3];
         const KArgs ak = loop_args(a);
         const View vk = loop_view(vs);
         if constexpr (SRC::kLens) {
             const LensRay lr = lens_sample(ak, vk, src.L, px, py, q.first + k);
-            trace_pixel<MODE, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, &lr);
-        } else trace_pixel<MODE, TRAV, SRC::kJitter>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k);
+            if constexpr (HDR) trace_pixel<MODE, TRAV, false, true, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, &lr, 0u, fc);
+            else trace_pixel<MODE, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, &lr);
+        } else if constexpr (HDR) trace_pixel<MODE, TRAV, SRC::kJitter, false, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k, nullptr, 0u, fc);
+        else trace_pixel<MODE, TRAV, SRC::kJitter>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, nullptr, q.first + k);
         if constexpr (ADAPT) add_sample(rgba, st);
         else add_bytes(rgba, r, g, b);
+        if constexpr (HDR) lds_add_hdr(vs_hsum, BLOCK, fc);
     }
     if constexpr (ADAPT) store_state(q, pixel_offset(a, px, py), st);
     else store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
+    if constexpr (HDR) store_hdr(q.hsum, pixel_offset(a, px, py), lds_get_hdr(vs_hsum, BLOCK));
 }
 
 // q.n samples of MODE 6's two stages, looped in the lanes: pass 1 from the sample's ray, its seed in registers, then bounce_pixel
 // with initRNG's sample index; 64 lanes, one 8 x 8 tile per wave. Pass 1 depends on the sample, so it cannot be shared as
 // bounce_accum_kernel shares it.
-template <class SRC, class TRAV, int WPE, bool ADAPT, class... L>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const L... lens) {
+template <class SRC, class TRAV, int WPE, bool ADAPT, bool HDR, class... L>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const L... lens) {
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
@@ -186,7 +237,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     if (!frame_pixel<64>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
     PixelState st{};
+    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];
+    volatile double *vs_hsum = &s_hsum[0][HDR ? threadIdx.x : 0];
     if constexpr (ADAPT) st = load_state(q, pixel_offset(a, px, py));
+    if constexpr (HDR) lds_put_hdr(vs_hsum, 64, load_hdr(q.hsum, pixel_offset(a, px, py)));
     for (uint32_t k = 0; k < q.n; ++k) {
         if constexpr (ADAPT)
             if (!state_active(q.min, q.max, q.tol, st)) break;
@@ -196,24 +250,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         LateOut lo;
         Seed seed;
         seed.word = 0u;
+        float fc[3];   // HDR: pass 1's colour, then the bounce's where the pixel has one -- as the bytes go
         const KArgs ak = loop_args(a);
         const View vk = loop_view(vs);
         if constexpr (SRC::kLens) {
             const LensRay lr = lens_sample(ak, vk, src.L, px, py, sample);
-            trace_pixel<1, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, &lr);
-        } else trace_pixel<1, TRAV, SRC::kJitter>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample);
-        if (full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, both, sample)) rgba = both;
+            if constexpr (HDR) trace_pixel<1, TRAV, false, true, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, &lr, 0u, fc);
+            else trace_pixel<1, TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, &lr);
+        } else if constexpr (HDR) trace_pixel<1, TRAV, SRC::kJitter, false, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample, nullptr, 0u, fc);
+        else trace_pixel<1, TRAV, SRC::kJitter>(ak, vk, tc_, px, py, rgba, idd, lo, nullptr, &seed, sample);
+        if constexpr (HDR) {
+            if (full::bounce_pixel<TRAV, true>(ak, tc_, px, py, seed, both, sample, fc)) rgba = both;
+        } else {
+            if (full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, both, sample)) rgba = both;
+        }
         if constexpr (ADAPT) add_sample(rgba, st);
         else add_bytes(rgba, r, g, b);
+        if constexpr (HDR) lds_add_hdr(vs_hsum, 64, fc);
     }
     if constexpr (ADAPT) store_state(q, pixel_offset(a, px, py), st);
     else store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
+    if constexpr (HDR) store_hdr(q.hsum, pixel_offset(a, px, py), lds_get_hdr(vs_hsum, 64));
 }
 
 // Sample q.first (q.n == 1) of the general full path tracer: trace_kernel<2>'s tiles, one pixel per lane.
 // ADAPT: the waves take the round's listed tiles (listed_pixel()), and only active lanes trace.
-template <class SRC, class TRAV, int BLOCK, int WPE, bool ADAPT, class... L>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q, const L... lens) {
+template <class SRC, class TRAV, int BLOCK, int WPE, bool ADAPT, bool HDR, class... L>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const L... lens) {
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
@@ -231,10 +294,18 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     uint32_t rgba;
     int2 idd;
     LateOut lo;
+    float fc[3];
     if constexpr (SRC::kLens) {
         const LensRay lr = lens_sample(a, vs.v[0], src.L, px, py, q.first);
-        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    } else full::trace_pixel_full<TRAV, SRC::kJitter>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
+        if constexpr (HDR) full::trace_pixel_full<TRAV, false, true, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr, fc);
+        else full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
+    } else if constexpr (HDR) full::trace_pixel_full<TRAV, SRC::kJitter, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, nullptr, fc);
+    else full::trace_pixel_full<TRAV, SRC::kJitter>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first);
+    if constexpr (HDR) {   // one sample: the pixel's sums read, added to and written here
+        HdrSum hs = load_hdr(q.hsum, pixel_offset(a, px, py));
+        add_hdr(fc, hs);
+        store_hdr(q.hsum, pixel_offset(a, px, py), hs);
+    }
     if constexpr (ADAPT) {
         add_sample(rgba, st);
         store_state(q, pixel_offset(a, px, py), st);
@@ -253,10 +324,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 // from memory once, and each sample reads it back from LDS and adds its bytes there.
 // ADAPT: the loop stops at the pixel's stop (n and Q in registers); sky and emissive pixels, whose every sample is the same,
 // take adaptive_constant_count() at once.
-template <class TRAV, bool ADAPT = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT> q) {
+// HDR: the three float64 sums wait in LDS too (1.5 KiB more per wave: 98 of the CU's 160 KiB at 28 waves); sky and emissive pixels
+// take their float colour from q.hframe, which hdr_frame_kernel wrote as it ran pass 1.
+template <class TRAV, bool ADAPT = false, bool HDR = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q) {
     __shared__ uint32_t s_seed[kSeedPlanes][64];
     __shared__ uint32_t s_sum[3][64];
+    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];   // (HDR = false: never touched, and dropped)
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     const int lane = threadIdx.x & 63;
@@ -268,7 +342,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
     const uint32_t word = sp[3 * 64];
     uint32_t r = 0u, g = 0u, b = 0u;
     PixelState st{};
+    HdrSum hs{};
     if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
+    if constexpr (HDR) hs = load_hdr(q.hsum, (size_t)py * (size_t)a.width + (size_t)px);
     if (word & kSeedValid) {
 #pragma unroll
         for (uint32_t p = 0; p < kSeedPlanes; ++p) s_seed[p][lane] = sp[p * 64];
@@ -280,6 +356,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
         // volatile: the seed is read back for every sample, not hoisted into registers across the loop
         volatile uint32_t *vs_seed = &s_seed[0][0];
         volatile uint32_t *vs_sum = &s_sum[0][0];
+        volatile double *vs_hsum = &s_hsum[0][0];
+        if constexpr (HDR) { vs_hsum[0 * 64 + lane] = hs.r; vs_hsum[1 * 64 + lane] = hs.g; vs_hsum[2 * 64 + lane] = hs.b; }
         // every sample is bounce_pixel's own arithmetic on the same seed: direct term, then the bounce's term, then unorm8
         for (uint32_t k = 0; k < q.n; ++k) {
             if constexpr (ADAPT) {
@@ -292,7 +370,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
             seed.iof = __uint_as_float(vs_seed[4 * 64 + lane]);
             const KArgs ak = loop_args(a);
             uint32_t rgba = 0u;
-            full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, rgba, q.first + k);
+            if constexpr (HDR) {
+                float fc[3] = {0.0f, 0.0f, 0.0f};
+                full::bounce_pixel<TRAV, true>(ak, tc_, px, py, seed, rgba, q.first + k, fc);
+                vs_hsum[0 * 64 + lane] = vs_hsum[0 * 64 + lane] + (double)hdr_value(fc[0]);
+                vs_hsum[1 * 64 + lane] = vs_hsum[1 * 64 + lane] + (double)hdr_value(fc[1]);
+                vs_hsum[2 * 64 + lane] = vs_hsum[2 * 64 + lane] + (double)hdr_value(fc[2]);
+            } else full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, rgba, q.first + k);
             vs_sum[0 * 64 + lane] = vs_sum[0 * 64 + lane] + (rgba & 0xffu);
             vs_sum[1 * 64 + lane] = vs_sum[1 * 64 + lane] + ((rgba >> 8) & 0xffu);
             vs_sum[2 * 64 + lane] = vs_sum[2 * 64 + lane] + ((rgba >> 16) & 0xffu);
@@ -303,13 +387,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
             }
         }
         r = vs_sum[0 * 64 + lane]; g = vs_sum[1 * 64 + lane]; b = vs_sum[2 * 64 + lane];
+        if constexpr (HDR) { hs.r = vs_hsum[0 * 64 + lane]; hs.g = vs_hsum[1 * 64 + lane]; hs.b = vs_hsum[2 * 64 + lane]; }
     } else if constexpr (ADAPT) {
-        add_repeat(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], adaptive_constant_count(st.n, q.n, q.min) - st.n, st);
+        const uint32_t more = adaptive_constant_count(st.n, q.n, q.min) - st.n;
+        add_repeat(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], more, st);
         r = st.r; g = st.g; b = st.b;
+        if constexpr (HDR) add_hdr_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, more, hs);
     } else {   // sky, emissive surfaces: pass 1's bytes are every sample's
         add_bytes(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], r, g, b);
         r *= q.n; g *= q.n; b *= q.n;
+        if constexpr (HDR) add_hdr_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, q.n, hs);
     }
+    if constexpr (HDR) store_hdr(q.hsum, (size_t)py * (size_t)a.width + (size_t)px, hs);
     if constexpr (ADAPT) {
         st.r = r; st.g = g; st.b = b;
         store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
@@ -318,86 +407,40 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bo
     }
 }
 
-__global__ __launch_bounds__(256) void accum_resolve_kernel(const Resolve q) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= q.pixels) return;
-    const uint4 s = reinterpret_cast<const uint4 *>(q.sums)[i];
-    const uint32_t h = q.n >> 1;
-    q.out_rgba[i] = ((s.x + h) / q.n) | (((s.y + h) / q.n) << 8) | (((s.z + h) / q.n) << 16) | (255u << 24);
-}
-
-// An adaptive accumulation's resolve: each pixel by its own count (the fourth word; >= 1 after the first round, as min >= 2)
-__global__ __launch_bounds__(256) void adaptive_resolve_kernel(const Resolve q) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= q.pixels) return;
-    const uint4 s = reinterpret_cast<const uint4 *>(q.sums)[i];
-    const uint32_t n = s.w > 0u ? s.w : 1u, h = n >> 1;
-    q.out_rgba[i] = ((s.x + h) / n) | (((s.y + h) / n) << 8) | (((s.z + h) / n) << 16) | (255u << 24);
-}
-
-// One lane per tile: does it hold an active pixel? Active tiles of a wave are appended with one atomic (ballot, mbcnt offsets);
-// the list's order does not matter, as every pixel's samples depend on that pixel alone.
-__global__ __launch_bounds__(256) void compact_tiles_kernel(const Tiles t) {
-    const int tiles_x = (t.width + 7) / 8, n_tiles = tiles_x * ((t.height + 7) / 8);
-    const int tile = (int)(blockIdx.x * 256u + threadIdx.x);
-    bool any = false;
-    if (tile < n_tiles) {
-        const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-        const int x1 = min(tx * 8 + 8, t.width), y1 = min(ty * 8 + 8, t.height);
-        for (int y = ty * 8; y < y1 && !any; ++y)
-            for (int x = tx * 8; x < x1 && !any; ++x) {
-                const size_t o = (size_t)y * (size_t)t.width + (size_t)x;
-                const uint4 s = reinterpret_cast<const uint4 *>(t.sums)[o];
-                any = adaptive_active(s.w, (uint64_t)s.x + s.y + s.z, t.sq[o], t.min, t.max, t.tol);
-            }
-    }
-    const uint64_t mask = __ballot(any);
-    if (mask == 0u) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t base = 0u;
-    if (lane == (uint32_t)(__ffsll((unsigned long long)mask) - 1)) base = atomicAdd(t.n_tiles, (uint32_t)__popcll(mask));
-    base = __shfl(base, __ffsll((unsigned long long)mask) - 1);
-    if (any) t.tiles[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)tile;
-}
-
-// vrt_accum_counts: a grid-stride loop, one pixel per lane per step; each wave counts its active pixels with ballots and adds
-// them with one atomic at the end (one atomic per pixel wave serialised on the one word: 0.25 ms at 1080p)
-__global__ __launch_bounds__(256) void adaptive_counts_kernel(const Counts c) {
-    const uint32_t stride = gridDim.x * 256u;
-    uint32_t wave_active = 0u;
-    for (uint32_t base = blockIdx.x * 256u + (threadIdx.x & ~63u); base < c.pixels; base += stride) {   // uniform per wave
-        const uint32_t i = base + (threadIdx.x & 63u);
-        bool act = false;
-        if (i < c.pixels) {
-            const uint4 s = reinterpret_cast<const uint4 *>(c.sums)[i];
-            c.out[i] = s.w;
-            act = adaptive_active(s.w, (uint64_t)s.x + s.y + s.z, c.sq[i], c.min, c.max, c.tol);
-        }
-        wave_active += (uint32_t)__popcll(__ballot(act));
-    }
-    if ((threadIdx.x & 63u) == 0u && wave_active != 0u) atomicAdd(c.n_active, wave_active);
-}
-
 // A primary mode from the corner: every sample is the frame in q.frame_rgba, so n samples add n times its bytes
-__global__ __launch_bounds__(256) void repeat_kernel(const Repeat q) {
+// (HDR: and n times its float colour in q.hframe)
+template <bool HDR>
+__global__ __launch_bounds__(256) void repeat_kernel(const typename std::conditional<HDR, RepeatHdrOf<Repeat>, Repeat>::type q) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= q.pixels) return;
     uint32_t r = 0u, g = 0u, b = 0u;
     add_bytes(q.frame_rgba[i], r, g, b);
     store_sums(q.sums, i, r * q.n, g * q.n, b * q.n);
+    if constexpr (HDR) {
+        HdrSum hs = load_hdr(q.hsum, i);
+        add_hdr_repeat(q.hframe + (size_t)i * 3, q.n, hs);
+        store_hdr(q.hsum, i, hs);
+    }
 }
 
 // the same for an adaptive accumulation: q.n rounds of a sample that never changes take each pixel to
 // adaptive_constant_count(), with no trace at all
-__global__ __launch_bounds__(256) void repeat_adaptive_kernel(const RepeatAdapt q) {
+template <bool HDR>
+__global__ __launch_bounds__(256) void repeat_adaptive_kernel(const typename std::conditional<HDR, RepeatHdrOf<RepeatAdapt>, RepeatAdapt>::type q) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= q.pixels) return;
     AdaptArgs s{};
     s.sums = q.sums;
     s.sq = q.sq;
     PixelState st = load_state(s, i);
-    add_repeat(q.frame_rgba[i], adaptive_constant_count(st.n, q.n, q.min) - st.n, st);
+    const uint32_t more = adaptive_constant_count(st.n, q.n, q.min) - st.n;
+    add_repeat(q.frame_rgba[i], more, st);
     store_state(s, i, st);
+    if constexpr (HDR) {
+        HdrSum hs = load_hdr(q.hsum, i);
+        add_hdr_repeat(q.hframe + (size_t)i * 3, more, hs);
+        store_hdr(q.hsum, i, hs);
+    }
 }
 
 }  // namespace accum

@@ -332,10 +332,11 @@ struct Seed { F3 hp; uint32_t word; float iof; };   // the same in registers (MO
 // MISS (modes 0 and 1 of the traversals with kMissTiles): miss_byte is this pixel's byte of the view's miss mask (View::miss), or
 // View::miss_stamp when there is none: any other value clears the tile, and a ray that points forward on every axis (miss_forward())
 // then hits nothing ("Miss tiles") and takes the miss outputs without marching.
-template <int MODE, class TRAV, bool JIT = false, bool LENS = false, bool MISS = false>
+// HDR (the HDR accumulation, vrt_accum.hip.h): fc_out[3] takes the float colour itself, as unorm8() receives it.
+template <int MODE, class TRAV, bool JIT = false, bool LENS = false, bool MISS = false, bool HDR = false>
 VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
                          uint32_t *seed = nullptr, Seed *seed_regs = nullptr, uint32_t sample = 0u, const LensRay *lens = nullptr,
-                         uint32_t miss_byte = 0u) {
+                         uint32_t miss_byte = 0u, float *fc_out = nullptr) {
     const float kPI = 3.14159265359f;
     const LensRay pr = pixel_ray<JIT, LENS>(a, vw, px, py, sample, lens);
     F3 ray_dir = pr.dir, ray_origin = pr.o;
@@ -494,6 +495,7 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
         }
     }
     rgba = unorm8(fc[0]) | (unorm8(fc[1]) << 8) | (unorm8(fc[2]) << 16) | (255u << 24);
+    if constexpr (HDR) { fc_out[0] = fc[0]; fc_out[1] = fc[1]; fc_out[2] = fc[2]; }
     idd = make_int2(voxel_id, pixel_dist);
     if constexpr (MODE == 1) {
         if (seed_regs) { seed_regs->hp = h.point; seed_regs->word = seed_word; seed_regs->iof = seed_iof; }
@@ -508,12 +510,14 @@ VRT_DEV void trace_pixel(const KArgs &a, const View &vw, const typename TRAV::Ct
 }
 
 namespace full {  // MODE 2, defined in vrt_full.hip.h
-template <class TRAV, bool JIT = false, bool LENS = false>   // JIT: the ray of jittered sample `sample` (jittered_ray_dir()); LENS: `lens`
+// JIT: the ray of jittered sample `sample` (jittered_ray_dir()); LENS: `lens`; HDR: fc_out[3] takes the float colour (trace_pixel)
+template <class TRAV, bool JIT = false, bool LENS = false, bool HDR = false>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t sample = 0u, const LensRay *lens = nullptr);
+                                 uint32_t sample = 0u, const LensRay *lens = nullptr, float *fc_out = nullptr);
 // pass 2 of the two-pass form: the diffuse bounce of a seeded pixel; false when the pixel has none (rgba untouched)
-template <class TRAV>
-__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, Seed seed, uint32_t &rgba, uint32_t sample = 0u);
+template <class TRAV, bool HDR = false>
+__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, Seed seed, uint32_t &rgba, uint32_t sample = 0u,
+                             float *fc_out = nullptr);
 }
 
 // One lane per pixel; a wave covers an 8 x 8 pixel tile so the 64 rays of a wave stay spatially coherent. One tile per wave.

@@ -465,7 +465,11 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
         vrt_ctx::Accum &ac = c->accum;
         // an adaptive accumulation (acc->adaptive) passes its rule and state too, to the kernels' adaptive forms
-        vrt::accum::AdaptArgs q{};
+        vrt::accum::HdrArgs q{};   // (the plain launch functions take its AdaptArgs)
+        q.hsum = ac.d_hsum;
+        q.hframe = ac.d_hframe;
+        const bool hdr = acc->hdr;
+        const vrt::accum::HdrFrame hf{ac.d_pass1, ac.d_id, ac.d_hframe};
         q.sums = ac.d_sums;
         q.pass1_rgba = ac.d_pass1;
         q.out_id = ac.d_id;
@@ -488,19 +492,27 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
             vs.v[0].gen_fast = 0u;
         }
         e = hipSuccess;
-        if (mode != VRT_MODE_FULL) {   // one launch, the samples looped in the lanes
-            e = vrt::launch::accum_primary(mode, src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
+        if (acc->frame_only) {   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
+            e = (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? vrt::launch::accum_frame_hdr(mode, v, a, vs, hf, (int)grid, s)
+                                                                         : hipErrorInvalidValue;
+        } else if (mode != VRT_MODE_FULL) {   // one launch, the samples looped in the lanes
+            e = hdr ? vrt::launch::accum_primary_hdr(mode, src, v, a, vs, q, acc->adaptive, l, (int)grid, s)
+                    : vrt::launch::accum_primary(mode, src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
         } else if (two_pass && src != Source::kCorner) {   // MODE 6's chain per sample, looped in the lanes
-            e = vrt::launch::accum_opaque(src, a, vs, q, acc->adaptive, l, (int)grid, s);
+            e = hdr ? vrt::launch::accum_opaque_hdr(src, a, vs, q, acc->adaptive, l, (int)grid, s)
+                    : vrt::launch::accum_opaque(src, a, vs, q, acc->adaptive, l, (int)grid, s);
         } else if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
             a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
             if (!ac.pass1) {
                 vs.v[0].out_rgba = ac.d_pass1;
                 vs.v[0].out_id = ac.d_id;
-                e = vrt::launch::trace_full_pass1(a, vs, (int)grid, s);
+                // (HDR: the same pass with its float colour, for the pixels without a bounce)
+                e = hdr ? vrt::launch::accum_pass1_hdr(a, vs, hf, (int)grid, s) : vrt::launch::trace_full_pass1(a, vs, (int)grid, s);
                 if (e == hipSuccess) ac.pass1 = true;
             }
-            if (e == hipSuccess) e = vrt::launch::accum_bounce(a, vs, q, acc->adaptive, (int)grid, s);
+            if (e == hipSuccess)
+                e = hdr ? vrt::launch::accum_bounce_hdr(a, vs, q, acc->adaptive, (int)grid, s)
+                        : vrt::launch::accum_bounce(a, vs, q, acc->adaptive, (int)grid, s);
         } else {   // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
             const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, width, height, ac.min_samples,
                                        ac.max_samples, ac.tolerance};
@@ -508,7 +520,9 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
                 q.first = acc->first + k;
                 q.n = 1u;
                 if (acc->adaptive) e = vrt::launch::adaptive_tiles(tl, s);
-                if (e == hipSuccess) e = vrt::launch::accum_full(src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
+                if (e == hipSuccess)
+                    e = hdr ? vrt::launch::accum_full_hdr(src, v, a, vs, q, acc->adaptive, l, (int)grid, s)
+                            : vrt::launch::accum_full(src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
             }
         }
     } else if (two_pass && c->two_pass_form >= 5) {

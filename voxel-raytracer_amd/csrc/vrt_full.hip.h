@@ -164,9 +164,10 @@ VRT_DEV RayS make_ray(F3 o, F3 d, float iof, float w, const float tint[3], float
 
 // sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
 // with JIT also the jittered sample whose ray is traced; LENS: the ray `lens` instead, origin and medium included (pixel_ray())
-template <class TRAV, bool JIT, bool LENS>
+// HDR: fc_out[3] takes the float colour unorm8() receives
+template <class TRAV, bool JIT, bool LENS, bool HDR>
 __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename TRAV::Ctx &tc_, int px, int py, uint32_t &rgba, int2 &idd, LateOut &lo,
-                                 uint32_t sample, const LensRay *lens) {
+                                 uint32_t sample, const LensRay *lens, float *fc_out) {
     const float kPI = 3.14159265359f;
     const float sky[3] = {0.5f, 0.7f, 1.0f};
     const float kSun = 3.0f;
@@ -394,6 +395,7 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     }
 #endif
     rgba = unorm8(fc[0]) | (unorm8(fc[1]) << 8) | (unorm8(fc[2]) << 16) | (255u << 24);
+    if constexpr (HDR) { fc_out[0] = fc[0]; fc_out[1] = fc[1]; fc_out[2] = fc[2]; }
     idd = make_int2(voxel_id, pixel_dist);
     lo = late_out(late_args(), late_view());
 }
@@ -406,8 +408,9 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
 // again without a stack, and writes the pixel's final colour. The accumulation order per pixel is pathTrace's: direct term, then
 // the bounce's term. Everything pass 2 recomputes is computed from the same inputs by the same operations as pass 1 did.
 // Only the bounce depends on initRNG's sampleIndex (`sample`): the sample loop of vrt_accum.hip.h runs this once per sample on one seed.
-template <class TRAV>
-__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, const Seed seed, uint32_t &rgba, uint32_t sample) {
+template <class TRAV, bool HDR>
+__device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, const Seed seed, uint32_t &rgba, uint32_t sample,
+                             float *fc_out) {
     const uint32_t word = seed.word;
     const bool valid = (word & kSeedValid) != 0u;
     if (__builtin_amdgcn_ballot_w64(valid) == 0ull) return false;   // a tile without bounces (sky, emissive surfaces)
@@ -480,6 +483,7 @@ __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int 
         }
     }
     rgba = unorm8(fc[0]) | (unorm8(fc[1]) << 8) | (unorm8(fc[2]) << 16) | (255u << 24);
+    if constexpr (HDR) { fc_out[0] = fc[0]; fc_out[1] = fc[1]; fc_out[2] = fc[2]; }
     return true;
 }
 

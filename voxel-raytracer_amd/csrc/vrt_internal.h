@@ -224,8 +224,15 @@ struct vrt_ctx {
         uint64_t *d_sq = nullptr;
         uint32_t *d_tiles = nullptr;             // the round's tile list [tile_cap], then its count and vrt_accum_counts' count
         size_t sq_pixels = 0, tile_cap = 0;      // capacities
+        // vrt_accum_keep_hdr as it stood at the begin: the float64 sums of the samples' float colours beside everything above
+        bool hdr = false;
+        double *d_hsum = nullptr;                // 3 doubles per pixel
+        float *d_hframe = nullptr;               // 3 floats per pixel: the corner frame's (or pass 1's) float colour
+        float *d_hrgb = nullptr;                 // vrt_accum_resolve_hdr's float image on its way to the host
+        size_t hdr_pixels = 0, hrgb_pixels = 0;  // capacities
     };
     Accum accum;
+    bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
     const uint32_t *dbg_group_order = nullptr;  // vrt_set_tile_order: caller-owned buffers instead of the scheduler's
     uint32_t *dbg_tile_cost = nullptr;
     bool dbg_sched = false;
@@ -261,7 +268,14 @@ int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-bu
 // (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_accum.hip.h JitterSource)
 // (aperture > 0: the samples of a thin lens, vrt_set_lens; vrt_accum.hip.h LensSource, vrt_lens.hip.h)
 // (adaptive: n rounds of the context's adaptive accumulation, vrt_accum_begin_adaptive; the kernels' adaptive forms)
-struct AccumStep { uint32_t first, n; bool jitter; float aperture = 0.0f, focus = 1.0f; bool adaptive = false; };
+// (hdr: an HDR accumulation, vrt_accum_keep_hdr; the kernels' HDR forms. frame_only, with hdr, modes 0 / 1 from the corner: no
+// sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
+struct AccumStep {
+    uint32_t first, n;
+    bool jitter;
+    float aperture = 0.0f, focus = 1.0f;
+    bool adaptive = false, hdr = false, frame_only = false;
+};
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
 SchedState *sched_state(vrt_ctx *c, hipStream_t s, int width, int n_rows, int row0, int row_stride, int tile_rows, int mode,

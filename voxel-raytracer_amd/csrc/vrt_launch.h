@@ -80,6 +80,23 @@ hipError_t adaptive_resolve(const accum::Resolve &q, hipStream_t s);
 hipError_t adaptive_tiles(const accum::Tiles &t, hipStream_t s);
 hipError_t adaptive_counts(const accum::Counts &c, hipStream_t s);
 
+// vrt_launch_accum_hdr.hip: the same for HDR accumulations (include/vrt.h vrt_accum_keep_hdr), `q` with the float64 sums and the
+// corner frame's float image. accum_frame_hdr: the frame of `mode` (0 or 1) from the corner with its float colour, in accum_primary's
+// shapes; accum_pass1_hdr: pass 1 of the opaque path likewise (trace_full_pass1's outputs and the floats). accum_resolve_hdr: the
+// float mean and its tone-mapped bytes.
+hipError_t accum_primary_hdr(int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                             bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_opaque_hdr(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
+                            int grid, hipStream_t s);
+hipError_t accum_full_hdr(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                          const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_bounce_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s);
+hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::Repeat> &q, hipStream_t s);
+hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::RepeatAdapt> &q, hipStream_t s);
+hipError_t accum_frame_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
+hipError_t accum_pass1_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
+hipError_t accum_resolve_hdr(const accum::HdrResolve &q, hipStream_t s);
+
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.

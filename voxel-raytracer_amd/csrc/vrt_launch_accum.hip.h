@@ -1,0 +1,124 @@
+// vrt_launch_accum.hip.h -- the launch functions of the progressive accumulation's sample kernels (vrt_accum.hip.h), templated on
+// HDR: vrt_launch_accum.hip instantiates the plain forms, vrt_launch_accum_hdr.hip those of HDR accumulations (two objects, so
+// that `make -j` compiles them side by side). One function per shape -- the primary modes and the opaque chain looped in the
+// lanes, one sample of the general full path tracer, the bounce over pass 1's seeds, the repeat of a frame -- each for the ray
+// source and the adaptive form asked for.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "vrt_launch.h"
+#include "vrt_kernels.hip.h"
+#include "vrt_kernels_v1.hip.h"
+#include "vrt_kernels_wide.hip.h"
+#include "vrt_kernels_v4.hip.h"
+#include "vrt_accum.hip.h"
+
+namespace vrt {
+namespace launch {
+namespace accum_impl {
+
+template <class K, class... P>
+hipError_t go(K kernel, int grid, int block, hipStream_t s, const P &...p) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, p...);
+    return hipGetLastError();
+}
+
+// A kernel's traversal, workgroup, waves per SIMD and form: f(Shape<...>{}) for the variant's traversal and `adaptive`
+template <class TRAV, int BLOCK, int WPE, bool ADAPT>
+struct Shape {
+    using Trav = TRAV;
+    static constexpr int kBlock = BLOCK, kWpe = WPE;
+    static constexpr bool kAdapt = ADAPT;
+};
+template <class TRAV, int BLOCK, int WPE, class F>
+hipError_t shape(bool adaptive, F &&f) {
+    return adaptive ? f(Shape<TRAV, BLOCK, WPE, true>{}) : f(Shape<TRAV, BLOCK, WPE, false>{});
+}
+// the general full path tracer: the shapes trace_full() launches trace_kernel<2> in
+template <class F>
+hipError_t full_shapes(const Variant &v, bool adaptive, F &&f) {
+    if (v.trav == 4) return shape<v4::TravAny, 64, 5>(adaptive, f);
+    if (v.trav == 3) return shape<v3::Trav, 64, 5>(adaptive, f);
+    if (v.trav == 2) return shape<v2::Trav, 256, 1>(adaptive, f);
+    if (v.trav == 1) return shape<v1::Trav, 256, 1>(adaptive, f);
+    return hipErrorInvalidValue;
+}
+// the primary modes: the variants the dispatcher normalises an accumulation to
+template <class F>
+hipError_t primary_shapes(const Variant &v, bool adaptive, F &&f) {
+    if (v.trav == 4) return shape<v4::Trav, 64, 7>(adaptive, f);
+    if (v.trav == 3) return shape<v3::Trav, 64, 6>(adaptive, f);
+    if (v.trav == 2) return shape<v2::Trav, 256, 1>(adaptive, f);
+    if (v.trav == 1) return shape<v1::Trav, 256, 1>(adaptive, f);
+    return hipErrorInvalidValue;
+}
+
+// what the dispatcher fills (every field a form may need), and the kernel's own slice of it
+template <bool HDR>
+using Filled = typename std::conditional<HDR, accum::HdrArgs, accum::AdaptArgs>::type;
+template <bool ADAPT, bool HDR>
+accum::ArgsOf<ADAPT, HDR> slice(const Filled<HDR> &q) {
+    if constexpr (HDR && !ADAPT) {
+        accum::ArgsOf<false, true> r{};
+        static_cast<accum::Args &>(r) = q;
+        r.hsum = q.hsum;
+        r.hframe = q.hframe;
+        return r;
+    } else {
+        return q;
+    }
+}
+
+template <bool HDR>
+hipError_t primary(int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
+                   const accum::Lens &l, int grid, hipStream_t s) {
+    if (mode != VRT_MODE_PRIMARY && mode != VRT_MODE_PRIMARY_SHADOW) return hipErrorInvalidValue;
+    const bool shadow = mode == VRT_MODE_PRIMARY_SHADOW;
+    return primary_shapes(v, adaptive, [&](auto sh) {
+        using S = decltype(sh);
+        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
+        if (src == accum::Source::kJitter)
+            return shadow ? go(accum::primary_accum_kernel<accum::JitterSource, 1, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR>, grid, S::kBlock, s, a, vs, qs)
+                          : go(accum::primary_accum_kernel<accum::JitterSource, 0, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR>, grid, S::kBlock, s, a, vs, qs);
+        if (src == accum::Source::kLens)
+            return shadow ? go(accum::primary_accum_kernel<accum::LensSource, 1, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens>, grid, S::kBlock, s, a, vs, qs, l)
+                          : go(accum::primary_accum_kernel<accum::LensSource, 0, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens>, grid, S::kBlock, s, a, vs, qs, l);
+        return hipErrorInvalidValue;   // the corner's samples of these modes are the frame: accum_repeat
+    });
+}
+
+template <bool HDR>
+hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, const accum::Lens &l, int grid,
+                  hipStream_t s) {
+    return shape<v4::Trav, 64, 6>(adaptive, [&](auto sh) {
+        using S = decltype(sh);
+        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
+        if (src == accum::Source::kJitter) return go(accum::opaque_accum_kernel<accum::JitterSource, typename S::Trav, S::kWpe, S::kAdapt, HDR>, grid, 64, s, a, vs, qs);
+        if (src == accum::Source::kLens) return go(accum::opaque_accum_kernel<accum::LensSource, typename S::Trav, S::kWpe, S::kAdapt, HDR, accum::Lens>, grid, 64, s, a, vs, qs, l);
+        return hipErrorInvalidValue;   // the corner's: pass 1 once, then accum_bounce
+    });
+}
+
+template <bool HDR>
+hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
+                const accum::Lens &l, int grid, hipStream_t s) {
+    return full_shapes(v, adaptive, [&](auto sh) {
+        using S = decltype(sh);
+        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
+        if (src == accum::Source::kCorner)
+            return go(accum::full_accum_kernel<accum::CornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR>, grid, S::kBlock, s, a, vs, qs);
+        if (src == accum::Source::kJitter)
+            return go(accum::full_accum_kernel<accum::JitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR>, grid, S::kBlock, s, a, vs, qs);
+        return go(accum::full_accum_kernel<accum::LensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens>, grid, S::kBlock, s, a, vs, qs, l);
+    });
+}
+
+template <bool HDR>
+hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s) {
+    if (adaptive) return go(accum::bounce_accum_kernel<v4::TravAny, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q));
+    return go(accum::bounce_accum_kernel<v4::TravAny, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q));
+}
+
+}  // namespace accum_impl
+}  // namespace launch
+}  // namespace vrt

@@ -205,6 +205,9 @@ void vrt_destroy(vrt_ctx *c) {
     (void)hipFree(c->accum.d_seed);
     (void)hipFree(c->accum.d_sq);
     (void)hipFree(c->accum.d_tiles);
+    (void)hipFree(c->accum.d_hsum);
+    (void)hipFree(c->accum.d_hframe);
+    (void)hipFree(c->accum.d_hrgb);
     if (c->accum.added) (void)hipEventDestroy(c->accum.added);
     if (c->accum.read) (void)hipEventDestroy(c->accum.read);
     if (!c->seeds.empty()) (void)hipDeviceSynchronize();   // their launches may be on the caller's streams
