@@ -346,13 +346,49 @@ int vrt_accum_counts(vrt_ctx *ctx, uint32_t *out_counts);
  * With HDR off nothing changes: behaviour, buffers and kernels are those of the accumulations above. With HDR on,
  * vrt_accum_resolve, _resolve_device and vrt_accum_counts return exactly what the same accumulation without HDR returns; the
  * accumulation takes 36 bytes per pixel more (the sums, and the frame's float colour for the pixels whose samples all equal it).
- * Frames, views, shards, vrt_multi and vrt_shade_rays have no float output. */
+ * Frames, views, shards and vrt_multi have no float output; a ray batch's float mean comes from vrt_shade_rays_hdr / _hdr_device (below). */
 int vrt_accum_keep_hdr(vrt_ctx *ctx, int enable);
 #define VRT_TONEMAP_CLAMP 0
 #define VRT_TONEMAP_REINHARD 1
 typedef struct vrt_tonemap { int32_t op; float exposure; } vrt_tonemap;
 int vrt_accum_resolve_hdr(vrt_ctx *ctx, float *out_rgb, const vrt_tonemap *tm, uint8_t *out_rgba8, uint8_t *out_shown_rgba8);
 int vrt_accum_resolve_hdr_device(vrt_ctx *ctx, void *d_rgb, const vrt_tonemap *tm, void *d_rgba8, void *d_shown_rgba8, void *stream);
+
+/* Ray batches in HDR: vrt_shade_rays with the mean of the samples' unclamped colours -- what a light probe, an environment map or
+ * a mirror pass of an emitter wants, where vrt_shade_rays averages clamped bytes. Rays, Direction, width (for the random numbers
+ * only), State -- no camera, accumulation, lens, ray table, miss mask or tile order is read or written -- and the stream ordering
+ * are those of vrt_shade_rays / vrt_shade_rays_device. vrt_accum_keep_hdr has no bearing on these calls.
+ *
+ * All arithmetic below: every operation rounded on its own, no contraction.
+ *  1. The HDR sample. Sample k of ray i is the three floats c its unorm8 store receives, each through
+ *     h(c) = min(max(0, c), 65504.0f): point 1 of vrt_accum_keep_hdr above, unchanged (NaN goes to +0).
+ *  2. The sums. Three float64 sums per ray. They start at +0.0, or -- device form, d_sums not NULL -- at the three doubles of ray i
+ *     in d_sums (n x 3 float64, the caller's, read and written). VRT_MODE_FULL: sum = sum + (double)h(c) once per sample, in the
+ *     order first_sample, first_sample + 1, ... (indices modulo 2^32). VRT_MODE_PRIMARY and _PRIMARY_SHADOW draw no random number,
+ *     so one sample is traced and sum = sum + (double)h(c) * (double)n_samples, one multiply and one add: m * h(c) is exact in a
+ *     double for m <= 2^24, so from a sum that holds m * h(c) with m + n_samples <= 2^24 this is the n_samples sequential adds'
+ *     result exactly. The sums are written back to d_sums when it is given.
+ *  3. The mean. out_rgb[i] = (float)(sum / (double)(n_prior + n_samples)) per channel, n x 3 floats. n_prior is the number of
+ *     samples the caller says d_sums already holds; the host form has no sums, so its n_prior is 0.
+ *  4. The tone map. out_rgba8 (n x 4 bytes) is the mean through the tone map of vrt_accum_resolve_hdr: the same vrt_tonemap, the
+ *     same two operators, unorm8 of the result, alpha 255; tm == NULL: VRT_TONEMAP_CLAMP with exposure 1. With n_samples == 1,
+ *     n_prior == 0 and tm == NULL these are vrt_shade_rays's bytes.
+ *  5. out_id_dist: exactly what vrt_shade_rays stores.
+ * Progressive use: the library keeps no state between calls. Call k + 1 passes first_sample + (samples so far) and
+ * n_prior = (samples so far) with the same d_sums, zeroed before the first call: 3 + 5 samples equal 8 in one call bit for bit,
+ * in the sums and in the mean.
+ * Errors: everything vrt_shade_rays refuses (for "both outputs NULL": all of out_rgb, out_rgba8 and out_id_dist NULL in the host
+ * form; all of d_rgb, d_rgba8, d_id_dist and d_sums NULL in the device form -- d_sums alone is an output), and VRT_E_INVALID for
+ * n_prior != 0 with d_sums == NULL, n_prior + n_samples > 2^24, an unknown tm->op, an exposure that is not finite or not > 0.
+ * n == 0 (with valid arguments otherwise) does nothing and returns VRT_OK.
+ * vrt_shade_rays_hdr: HOST buffers, synchronous, staged through the device buffers vrt_shade_rays keeps (n x 12 bytes more for
+ * out_rgb; they grow by the same rule and never shrink). vrt_shade_rays_hdr_device: DEVICE buffers, enqueued on `stream`. */
+int vrt_shade_rays_hdr(vrt_ctx *ctx, size_t n, const float *origins, int origin_stride, const float *dirs, int width, int mode,
+                       uint32_t first_sample, uint32_t n_samples, const vrt_tonemap *tm,
+                       float *out_rgb, uint8_t *out_rgba8, int32_t *out_id_dist);
+int vrt_shade_rays_hdr_device(vrt_ctx *ctx, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, int mode,
+                              uint32_t first_sample, uint32_t n_samples, uint32_t n_prior, void *d_sums, const vrt_tonemap *tm,
+                              void *d_rgb, void *d_rgba8, void *d_id_dist, void *stream);
 
 /* Column-major mat4 x2 + vec4, exactly the std140 Camera block (comp:17-21). */
 int vrt_set_camera(vrt_ctx *ctx, const float inv_projection[16], const float inv_view[16],

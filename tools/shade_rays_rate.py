@@ -6,9 +6,13 @@
   (b) 2 M random incoherent rays through the dragon, each mode.
   (c) 2 M probe rays: origins in the cells in front of surfaces, cosine-distributed directions about the face normal, mode 2,
       n_samples 1 and 16.
+--hdr measures vrt_shade_rays_hdr_device instead (float mean, tone-mapped bytes and id_dist written, no d_sums), alternated launch
+by launch with the plain vrt_shade_rays_device call of the same build on the same rays: each mode, 1 and 16 samples, on the 1080p
+dragon frame's rays and on a list of 1 M random rays.
 Prints one JSON object per line; --out writes them to a file too.
 
     python3 tools/shade_rays_rate.py --out profiles/shade_rays_rate.jsonl
+    python3 tools/shade_rays_rate.py --hdr --out profiles/shade_rays_hdr_rate.jsonl
 """
 import argparse
 import json
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rays", type=int, default=1 << 21)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--hdr", action="store_true", help="the HDR calls beside the plain ones (see above)")
     args = ap.parse_args()
     V = vrt_import.vrt()
     w = V.World()
@@ -89,6 +94,43 @@ def main():
         ctx.set_profiling(0)
         assert len(ms) == len(launches) * reps, "a launch was not timed"
         return [ms[i::len(launches)] for i in range(len(launches))]
+
+    def finish():
+        ctx.close()
+        if args.out:
+            with open(args.out, "w") as f:
+                for r in rows:
+                    f.write(json.dumps(r) + "\n")
+
+    if args.hdr:
+        W, H = 1920, 1080
+        _, origin, dirs = frame_rays(V, W, H)
+        rng = np.random.default_rng(1)
+        n_list = 1 << 20
+        lo = rng.uniform((-64, -64, -64), (192, 160, 128), (n_list, 3)).astype(np.float32)
+        ld = rng.normal(0, 1, (n_list, 3)).astype(np.float32)
+        for case, o, d, stride, width in (("frame_rays_1080p_dragon", origin.reshape(1, 3), dirs, 0, W),
+                                          ("random_rays_1m_dragon", lo, ld, 3, n_list)):
+            n = len(d)
+            d_o, d_d = upload(o, d)
+            d_rgb, d_rgba, d_id = ctx.device_alloc(n * 12), ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
+            for mode in (0, 1, 2):
+                for n_samples in (1, 16):
+                    reps = args.reps if n_samples == 1 or mode != 2 else max(3, args.reps // 4)
+                    plain, hdr = timed([lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=mode, width=width,
+                                                                      n_samples=n_samples),
+                                        lambda: ctx.shade_rays_hdr_device(n, d_o, stride, d_d, d_rgb, d_rgba, d_id, mode=mode, width=width,
+                                                                          n_samples=n_samples, tonemap="reinhard")], reps)
+                    pm, hm = float(np.median(plain)), float(np.median(hdr))
+                    emit({"case": case, "mode": mode, "rays": n, "n_samples": n_samples, "plain_kernel_ms": round(pm, 4),
+                          "hdr_kernel_ms": round(hm, 4), "hdr_over_plain": round(hm / pm, 3),
+                          "plain_ms_min_max": [round(float(plain.min()), 4), round(float(plain.max()), 4)],
+                          "hdr_ms_min_max": [round(float(hdr.min()), 4), round(float(hdr.max()), 4)],
+                          "hdr_rays_per_s": round(n / (hm * 1e-3)), "reps": reps})
+            for p in (d_o, d_d, d_rgb, d_rgba, d_id):
+                ctx.device_free(p)
+        finish()
+        return
 
     # (a) the frame's rays against the frame kernel
     W, H = 1920, 1080
@@ -137,11 +179,7 @@ def main():
               "batch_kernel_ms": round(m, 4), "paths_per_s": round(n * n_samples / (m * 1e-3))})
     for p in (d_o, d_d, d_rgba, d_id):
         ctx.device_free(p)
-    ctx.close()
-    if args.out:
-        with open(args.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
+    finish()
 
 
 if __name__ == "__main__":

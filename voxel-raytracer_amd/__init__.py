@@ -269,6 +269,11 @@ def hip_lib():
                                      C.c_uint32, C.c_void_p, C.c_void_p]
         L.vrt_shade_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_shade_rays_hdr.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32,
+                                         C.c_uint32, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_shade_rays_hdr_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Tonemap), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
         L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
         L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
@@ -972,6 +977,47 @@ class Context:
         if not (np.isfinite(e) and e > 0.0):
             raise ValueError(f"exposure: expected a float32 value finite and > 0, got {exposure!r}")
         return Tonemap(TONEMAPS[tonemap], float(e))
+
+    @staticmethod
+    def _hdr_samples(n_samples, n_prior):
+        for name, v, lo in (("n_samples", n_samples, 1), ("n_prior", n_prior, 0)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= 1 << 24:
+                raise ValueError(f"{name}: expected an integer in [{lo}, 2^24], got {v!r}")
+        if int(n_prior) + int(n_samples) > 1 << 24:
+            raise ValueError(f"n_prior + n_samples: at most 2^24 samples in all, got {int(n_prior) + int(n_samples)}")
+
+    def shade_rays_hdr(self, origins, dirs, mode=MODE_FULL, width=None, first_sample=0, n_samples=1, tonemap="clamp",
+                       exposure=1.0):
+        """Context.shade_rays with the mean of the samples' unclamped colours (vrt_shade_rays_hdr) -> (rgb float32[n, 3];
+        rgba8 uint8[n, 4]: its tone-mapped bytes, as accum_resolve_hdr maps them; id_dist int32[n, 2])."""
+        tm = self._tonemap(tonemap, exposure)
+        self._hdr_samples(n_samples, 0)
+        o, stride, d = shade_ray_args(origins, dirs)
+        n = d.shape[0]
+        rgb = np.zeros((n, 3), np.float32)
+        rgba = np.zeros((n, 4), np.uint8)
+        idd = np.zeros((n, 2), np.int32)
+        w = max(n, 1) if width is None else int(width)
+        self._chk(self._L.vrt_shade_rays_hdr(self._h, n, o.ctypes.data if n else None, stride, d.ctypes.data if n else None, w,
+                                             int(mode), int(first_sample) & 0xFFFFFFFF, int(n_samples), C.byref(tm),
+                                             rgb.ctypes.data, rgba.ctypes.data, idd.ctypes.data))
+        return rgb, rgba, idd
+
+    def shade_rays_hdr_device(self, n, d_origins, origin_stride, d_dirs, d_rgb, d_rgba, d_id, d_sums=None, n_prior=0,
+                              mode=MODE_FULL, width=None, first_sample=0, n_samples=1, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_shade_rays_hdr_device: DEVICE buffers (d_rgb: n x 3 floats, d_rgba: n x 4 bytes, d_id: n x 2 int32, d_sums: n x 3
+        float64 holding n_prior samples, read and written; any may be None, not all), enqueued on `stream`. Refining a batch:
+        zero d_sums, then call with first_sample and n_prior advanced by the samples so far."""
+        tm = self._tonemap(tonemap, exposure)
+        self._hdr_samples(n_samples, n_prior)
+        if n_prior != 0 and d_sums is None:
+            raise ValueError("n_prior: needs d_sums")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 30:
+            raise ValueError(f"n: expected an integer in [0, 2^30], got {n!r}")
+        w = max(int(n), 1) if width is None else int(width)
+        self._chk(self._L.vrt_shade_rays_hdr_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, int(mode),
+                                                    int(first_sample) & 0xFFFFFFFF, int(n_samples), int(n_prior), d_sums,
+                                                    C.byref(tm), d_rgb, d_rgba, d_id, stream))
 
     def accum_resolve_hdr(self, tonemap="clamp", exposure=1.0):
         """An HDR accumulation's float resolve (vrt_accum_resolve_hdr) -> (rgb float32[H,W,3]: the mean of the samples' unclamped

@@ -112,6 +112,12 @@ VRT_DEV void add_hdr_repeat(const float *fc, uint32_t k, HdrSum &h) {
     h.b = h.b + (double)hdr_value(fc[2]) * (double)k;
 }
 
+// The tone map of include/vrt.h vrt_tonemap on one channel of the mean: every operation rounded on its own
+VRT_DEV float tone_map(float x, int op, float e) {
+    const float xe = e * x;
+    return op == 1 ? xe / (1.0f + xe) : xe;   // VRT_TONEMAP_REINHARD : _CLAMP (unorm8 clamps)
+}
+
 // The sample-looped kernels keep a lane's three float64 sums in LDS across the loop (24 bytes per lane), as the bounce kernel keeps
 // its state, rather than six more live registers at budgets of 72 and 80 (what the HDR forms still spill: profiles/accum_resource_usage.txt)
 VRT_DEV void lds_put_hdr(volatile double *p, int n, const HdrSum &h) { p[0] = h.r; p[n] = h.g; p[2 * n] = h.b; }

@@ -31,12 +31,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     q.hframe[o * 3 + 0] = fc[0]; q.hframe[o * 3 + 1] = fc[1]; q.hframe[o * 3 + 2] = fc[2];
 }
 
-// The tone map of include/vrt.h vrt_tonemap on one channel of the mean: every operation rounded on its own
-VRT_DEV float tone_map(float x, int op, float e) {
-    const float xe = e * x;
-    return op == 1 ? xe / (1.0f + xe) : xe;   // VRT_TONEMAP_REINHARD : _CLAMP (unorm8 clamps)
-}
-
 // The HDR resolve: the mean by the pixel's own count, its tone-mapped bytes
 __global__ __launch_bounds__(256) void hdr_resolve_kernel(const HdrResolve q) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;

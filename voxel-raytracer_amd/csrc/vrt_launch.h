@@ -102,6 +102,10 @@ hipError_t accum_resolve_hdr(const accum::HdrResolve &q, hipStream_t s);
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
 hipError_t shade_rays(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s,
                       hipEvent_t ev0, hipEvent_t ev1);
+// vrt_launch_rays_hdr.hip: the same kernels' HDR forms (include/vrt.h vrt_shade_rays_hdr): q.n_samples is the call's own in every
+// mode, q.out_rgba takes the tone-mapped bytes of the mean
+hipError_t shade_rays_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, uint32_t grid, hipStream_t s,
+                          hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

@@ -1,4 +1,4 @@
-// vrt_rays.cpp -- vrt_shade_rays / vrt_shade_rays_device (include/vrt.h): pathTrace for ray batches of the caller's. Call-order and
+// vrt_rays.cpp -- vrt_shade_rays / vrt_shade_rays_device and their HDR forms (include/vrt.h): pathTrace for ray batches of the caller's. Call-order and
 // argument checks, the kernel arguments -- the scene and the uniforms as a frame launch carries them, and nothing of a camera: no
 // eye lookup, first lookup, ray table, miss mask, tightened root or tile order -- and the device buffers the host form stages
 // through. Reads no camera, lens or accumulation state and writes none.
@@ -13,7 +13,7 @@ using namespace vrt_internal;
 namespace {
 
 int check(vrt_ctx *c, size_t n, const void *origins, int origin_stride, const void *dirs, int width, int mode, uint32_t n_samples,
-          const void *out_rgba, const void *out_id, const char *what) {
+          bool any_out, const char *what) {
     if (!c) return VRT_E_INVALID;
     if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no octree uploaded (call vrt_upload_octree first)");
     if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
@@ -23,14 +23,37 @@ int check(vrt_ctx *c, size_t n, const void *origins, int origin_stride, const vo
     if (width < 1) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": width must be at least 1");
     if (n_samples < 1u || n_samples > (1u << 24)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": 1 to 2^24 samples per call");
     if (n > ((size_t)1 << 30)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": at most 2^30 rays per call");
-    if (!out_rgba && !out_id) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": both outputs are null");
+    if (!any_out) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": every output is null");
     if (n > 0 && (!origins || !dirs)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null buffer");
+    return VRT_OK;
+}
+
+// What the HDR forms add to a launch: the caller's sums and the count they hold, the float output, the tone map
+struct Hdr {
+    double *d_sums;
+    float *d_rgb;
+    uint32_t n_prior;
+    const vrt_tonemap *tm;
+};
+
+// ... and to the checks (any_out: one of the form's outputs, the sums included, is given)
+int check_hdr(vrt_ctx *c, size_t n, const void *origins, int origin_stride, const void *dirs, int width, int mode, uint32_t n_samples,
+              bool any_out, const void *sums, uint32_t n_prior, const vrt_tonemap *tm, const char *what) {
+    const int r = check(c, n, origins, origin_stride, dirs, width, mode, n_samples, any_out, what);
+    if (r) return r;
+    if (n_prior != 0u && !sums) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": n_prior without sums");
+    if ((uint64_t)n_prior + n_samples > ((uint64_t)1 << 24)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": more than 2^24 samples in all");
+    if (tm) {
+        if (tm->op != VRT_TONEMAP_CLAMP && tm->op != VRT_TONEMAP_REINHARD) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown tone-map operator");
+        if (!(tm->exposure > 0.0f) || !(tm->exposure <= 3.402823466e38f))
+            return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": exposure must be finite and > 0");
+    }
     return VRT_OK;
 }
 
 // The launch: KArgs as enqueue() (vrt_dispatch.cpp) fills them for a frame, without anything derived from an eye
 int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const float *d_dirs, int width, int mode, uint32_t first_sample,
-          uint32_t n_samples, uint32_t *d_rgba, int2 *d_id, hipStream_t s) {
+          uint32_t n_samples, uint32_t *d_rgba, int2 *d_id, hipStream_t s, const Hdr *hdr = nullptr) {
     const int ra = ensure_analysis(c);
     if (ra) return ra;
     Variant v = *find_variant(c->variant);
@@ -57,6 +80,9 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     a.shade_fast = 1;   // div_pi_inrange(): the lights' range, as enqueue() checks it
     for (int i = 0; i < 3; ++i)
         if (!(fabsf(a.global_light[i]) <= 1073741824.0f) || !(fabsf(a.light_dir[i]) <= 1073741824.0f)) a.shade_fast = 0;
+    // the HDR forms hand the float itself out: below 2^-103 div_pi_inrange() may differ from x / PI in the last bit -- a colour term
+    // that stores byte 0 either way, but a different float
+    if (hdr) a.shade_fast = 0;
     a.tex_dim = (int)c->info.tex_dim;
     a.width = width;
     a.height = (int)((n + (size_t)width - 1) / (size_t)width);
@@ -90,7 +116,22 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     const bool prof = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
     const hipEvent_t ev0 = prof ? c->prof_events[2 * c->prof_count] : nullptr;
     const hipEvent_t ev1 = prof ? c->prof_events[2 * c->prof_count + 1] : nullptr;
-    const hipError_t e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, ev0, ev1);
+    hipError_t e;
+    if (hdr) {
+        vrt::rays::HdrArgs hq;
+        // HdrArgs derives from Args: the plain arguments are its base, first in the layout -- what late_rays() (vrt_rays.hip.h) relies
+        // on when it reads the kernel's third argument at Args' place in either form
+        static_cast<vrt::rays::Args &>(hq) = q;
+        hq.n_samples = n_samples;   // every mode: the primary modes add their one sample n_samples times over
+        hq.sums = hdr->d_sums;
+        hq.out_rgb = hdr->d_rgb;
+        hq.n_total = hdr->n_prior + n_samples;
+        hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
+        hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
+        e = vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, ev0, ev1);
+    } else {
+        e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, ev0, ev1);
+    }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     if (prof) ++c->prof_count;
     return VRT_OK;
@@ -117,7 +158,7 @@ extern "C" {
 
 int vrt_shade_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride, const float *dirs, int width, int mode,
                    uint32_t first_sample, uint32_t n_samples, uint8_t *out_rgba8, int32_t *out_id_dist) {
-    int r = check(c, n, origins, origin_stride, dirs, width, mode, n_samples, out_rgba8, out_id_dist, "vrt_shade_rays");
+    int r = check(c, n, origins, origin_stride, dirs, width, mode, n_samples, out_rgba8 || out_id_dist, "vrt_shade_rays");
     if (r || n == 0) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
@@ -141,11 +182,53 @@ int vrt_shade_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride
 
 int vrt_shade_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, int mode,
                           uint32_t first_sample, uint32_t n_samples, void *d_rgba8, void *d_id_dist, void *stream) {
-    const int r = check(c, n, d_origins, origin_stride, d_dirs, width, mode, n_samples, d_rgba8, d_id_dist, "vrt_shade_rays_device");
+    const int r = check(c, n, d_origins, origin_stride, d_dirs, width, mode, n_samples, d_rgba8 || d_id_dist, "vrt_shade_rays_device");
     if (r || n == 0) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     return shade(c, n, static_cast<const float *>(d_origins), origin_stride, static_cast<const float *>(d_dirs), width, mode, first_sample,
                  n_samples, static_cast<uint32_t *>(d_rgba8), static_cast<int2 *>(d_id_dist), stream ? (hipStream_t)stream : c->stream);
+}
+
+int vrt_shade_rays_hdr(vrt_ctx *c, size_t n, const float *origins, int origin_stride, const float *dirs, int width, int mode,
+                       uint32_t first_sample, uint32_t n_samples, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8,
+                       int32_t *out_id_dist) {
+    int r = check_hdr(c, n, origins, origin_stride, dirs, width, mode, n_samples, out_rgb || out_rgba8 || out_id_dist, nullptr, 0u, tm,
+                      "vrt_shade_rays_hdr");
+    if (r || n == 0) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
+    const size_t rgba_bytes = out_rgba8 ? n * 4 : 0, id_bytes = out_id_dist ? n * 8 : 0, rgb_bytes = out_rgb ? n * 12 : 0;
+    r = ensure_rays_scratch(c, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + align256(id_bytes) + rgb_bytes);
+    if (r) return r;
+    char *base = static_cast<char *>(c->d_rays);
+    float *d_o = reinterpret_cast<float *>(base);
+    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
+    char *out = base + align256(o_bytes) + align256(d_bytes);
+    uint32_t *d_rgba = out_rgba8 ? reinterpret_cast<uint32_t *>(out) : nullptr;
+    int2 *d_id = out_id_dist ? reinterpret_cast<int2 *>(out + align256(rgba_bytes)) : nullptr;
+    float *d_rgb = out_rgb ? reinterpret_cast<float *>(out + align256(rgba_bytes) + align256(id_bytes)) : nullptr;
+    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
+    const Hdr hdr{nullptr, d_rgb, 0u, tm};
+    r = shade(c, n, d_o, origin_stride, d_d, width, mode, first_sample, n_samples, d_rgba, d_id, c->stream, &hdr);
+    if (r) return r;
+    if (d_rgba) VRT_HIP(c, hipMemcpyAsync(out_rgba8, d_rgba, rgba_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d_id) VRT_HIP(c, hipMemcpyAsync(out_id_dist, d_id, id_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (d_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_shade_rays_hdr_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, int mode,
+                              uint32_t first_sample, uint32_t n_samples, uint32_t n_prior, void *d_sums, const vrt_tonemap *tm,
+                              void *d_rgb, void *d_rgba8, void *d_id_dist, void *stream) {
+    const int r = check_hdr(c, n, d_origins, origin_stride, d_dirs, width, mode, n_samples, d_rgb || d_rgba8 || d_id_dist || d_sums, d_sums,
+                            n_prior, tm, "vrt_shade_rays_hdr_device");
+    if (r || n == 0) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const Hdr hdr{static_cast<double *>(d_sums), static_cast<float *>(d_rgb), n_prior, tm};
+    return shade(c, n, static_cast<const float *>(d_origins), origin_stride, static_cast<const float *>(d_dirs), width, mode, first_sample,
+                 n_samples, static_cast<uint32_t *>(d_rgba8), static_cast<int2 *>(d_id_dist), stream ? (hipStream_t)stream : c->stream, &hdr);
 }
 
 }  // extern "C"

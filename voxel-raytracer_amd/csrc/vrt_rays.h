@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace vrt {
 namespace rays {
@@ -20,6 +21,19 @@ struct Args {
     uint32_t tiles_x;         // != 0: a wave takes the 8 x 8 tile blockIdx.x of that image, tiles_x tiles per row; 0: 64 consecutive rays
     uint32_t first, n_samples;
 };
+
+// The HDR forms (include/vrt.h vrt_shade_rays_hdr): the kernels' template parameter HDR picks this type (ArgsOf), so the plain
+// kernels keep Args and their code. Args::out_rgba takes the tone-mapped bytes of the mean; Args::n_samples is the call's own
+// in every mode (the primary modes trace one sample and add it n_samples times over).
+struct HdrArgs : Args {
+    double *sums;             // n x 3 float64, read before the first sample and written after the last, or null (start at +0.0)
+    float *out_rgb;           // n x 3 floats: the mean, or null
+    uint32_t n_total;         // n_prior + n_samples: what the mean divides by
+    int32_t op;               // VRT_TONEMAP_*
+    float exposure;
+};
+template <bool HDR>
+using ArgsOf = typename std::conditional<HDR, HdrArgs, Args>::type;
 
 // Which mapping a batch takes (vrt_rays.hip.h ray_of_lane()): images -- at least 8 wide and two rows high -- keep the frame kernels'
 // 8 x 8 tiles, everything else is a list. Returns the grid (waves) and sets tiles_x.

@@ -14,8 +14,14 @@
 // Lane-to-ray mapping (ray_of_lane()): a batch that is an image -- rays::plan(): width >= 8 and at least two rows -- is cut into
 // the frame kernels' 8 x 8 tiles, one per wave, because neighbouring pixels walk the same nodes; any other batch is a list, 64
 // consecutive rays per wave. Either way ray i's random numbers are those of pixel (i % width, i / width).
+//
+// HDR forms (include/vrt.h vrt_shade_rays_hdr; template parameter HDR = true, arguments HdrArgs): the same kernels hand the float
+// colour out of trace_pixel / trace_pixel_full, add h(c) of it to three float64 sums the lane keeps in registers -- read from
+// HdrArgs::sums before the first sample and written back after the last, where the caller brings them -- and finish in the
+// lane: mean, float store, tone map, bytes (finish_hdr()). No LDS: unlike the accumulation's 72- and 80-register sample kernels
+// (vrt_accum.hip.h lds_put_hdr()) these run at 96 registers and more. Instantiated by vrt_launch_rays_hdr.hip alone.
 #pragma once
-#include "vrt_full.hip.h"
+#include "vrt_accum.hip.h"
 #include "vrt_rays.h"
 
 namespace vrt {
@@ -75,9 +81,38 @@ VRT_DEV void store(uint32_t i, uint32_t rgba, int2 idd) {
     if (out_id) out_id[i] = idd;
 }
 
+// HDR: the sums a lane starts from
+VRT_DEV accum::HdrSum first_hdr(const double *sums, uint32_t i) {
+    return sums ? accum::load_hdr(sums, i) : accum::HdrSum{0.0, 0.0, 0.0};
+}
+
+// HDR: the lane's sums after its last sample -> HdrArgs::sums, the mean over n_total, its tone-mapped bytes; the arguments re-read
+// from the kernarg segment (HdrArgs begins with Args, at late_rays()'s place)
+VRT_DEV void finish_hdr(uint32_t i, const accum::HdrSum &hs, int2 idd) {
+    const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
+    double *sums = lq->sums;
+    float *out_rgb = lq->out_rgb;
+    uint32_t *out_rgba = lq->out_rgba;
+    int2 *out_id = lq->out_id;
+    if (sums) accum::store_hdr(sums, i, hs);
+    if (out_rgb || out_rgba) {
+        const double n = (double)lq->n_total;
+        const float m[3] = {(float)(hs.r / n), (float)(hs.g / n), (float)(hs.b / n)};
+        if (out_rgb) { out_rgb[(size_t)i * 3 + 0] = m[0]; out_rgb[(size_t)i * 3 + 1] = m[1]; out_rgb[(size_t)i * 3 + 2] = m[2]; }
+        if (out_rgba) {
+            const int op = lq->op;
+            const float e = lq->exposure;
+            out_rgba[i] = unorm8(accum::tone_map(m[0], op, e)) | (unorm8(accum::tone_map(m[1], op, e)) << 8) |
+                          (unorm8(accum::tone_map(m[2], op, e)) << 16) | (255u << 24);
+        }
+    }
+    if (out_id) out_id[i] = idd;
+}
+
 // VRT_MODE_PRIMARY / _PRIMARY_SHADOW: no random number is drawn, so every sample is the same and one trace serves any n_samples
-template <int MODE, class TRAV, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_kernel(const KArgs a, const ViewSet vs, const Args q) {
+// (HDR: added as (double)h(c) * n_samples, accum::add_hdr_repeat())
+template <int MODE, class TRAV, int WPE, bool HDR = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     uint32_t i;
@@ -87,16 +122,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     uint32_t rgba;
     int2 idd;
     LateOut lo;
-    trace_pixel<MODE, TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, nullptr, nullptr, 0u, &lr);
-    store(i, rgba, idd);
+    if constexpr (HDR) {
+        float fc[3];
+        trace_pixel<MODE, TRAV, false, true, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, nullptr, nullptr, 0u, &lr, 0u, fc);
+        const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
+        accum::HdrSum hs = first_hdr(lq->sums, i);
+        accum::add_hdr_repeat(fc, lq->n_samples, hs);
+        finish_hdr(i, hs, idd);
+    } else {
+        trace_pixel<MODE, TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, nullptr, nullptr, 0u, &lr);
+        store(i, rgba, idd);
+    }
 }
 
 // VRT_MODE_FULL, the general stack kernel (right for any scene and any origin). LOOP: samples first .. first + n_samples - 1 looped
 // in the lane, the arguments and the ray re-read for every sample (held across the back edge they spill, vrt_accum.hip.h
 // loop_args()); the medium's two words stay in registers. The mean is accum_resolve_kernel's: (sum + n / 2) / n per channel of the
 // bytes each sample would store, alpha 255; the (voxel ID, dist) pair is the same for every sample.
-template <class TRAV, int WPE, bool LOOP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_kernel(const KArgs a, const ViewSet vs, const Args q) {
+// HDR: one add_hdr() per sample in sample order; LOOP carries the three float64 sums (six registers) across the back edge.
+template <class TRAV, int WPE, bool LOOP, bool HDR = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     uint32_t i;
@@ -106,11 +151,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     uint32_t rgba;
     int2 idd;
     LateOut lo;
-    if constexpr (!LOOP) {
+    if constexpr (!LOOP && HDR) {
+        float fc[3];
+        full::trace_pixel_full<TRAV, false, true, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr, fc);
+        const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
+        accum::HdrSum hs = first_hdr(lq->sums, i);
+        accum::add_hdr(fc, hs);
+        finish_hdr(i, hs, idd);
+    } else if constexpr (!LOOP) {
         full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
     } else {
         const uint32_t eye0 = lr.eye0, eye1 = lr.eye1;
         uint32_t r = 0u, g = 0u, b = 0u;
+        accum::HdrSum hs{};
+        if constexpr (HDR) hs = first_hdr(q.sums, i);
         const uint32_t n = q.n_samples;
         for (uint32_t k = 0; k < n; ++k) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -129,15 +183,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
             lk.o = F3{o[0], o[1], o[2]};
             lk.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));
             lk.eye0 = eye0; lk.eye1 = eye1;
-            full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
-            r += rgba & 0xffu;
-            g += (rgba >> 8) & 0xffu;
-            b += (rgba >> 16) & 0xffu;
+            if constexpr (HDR) {
+                float fc[3];
+                full::trace_pixel_full<TRAV, false, true, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk, fc);
+                accum::add_hdr(fc, hs);
+            } else {
+                full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
+                r += rgba & 0xffu;
+                g += (rgba >> 8) & 0xffu;
+                b += (rgba >> 16) & 0xffu;
+            }
         }
-        const uint32_t h = n >> 1;
-        rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
+        if constexpr (HDR) {
+            finish_hdr(i, hs, idd);
+        } else {
+            const uint32_t h = n >> 1;
+            rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
+        }
     }
-    store(i, rgba, idd);
+    if constexpr (!HDR) store(i, rgba, idd);
 }
 
 }  // namespace rays
