@@ -79,7 +79,24 @@ its tree is, and decided pixels must match exactly: rgb bytes, ID and dist):
     det_powf(x, 5) on [0, 1]: relative 8.66e-6 where x^5 >= 1.7e-38 (E_POW = 1.2e-5; absolute < 1.7e-38 below);
     det_sinf / det_cosf on [0, 2 pi): absolute 6.82e-8 / 7.61e-8 (E_SINCOS = 1.2e-7).
 
-Not restated: the display pass of a mode-2 frame (shader_ref64.display covers quad.frag), jitter, the thin lens and the
+Ray batches (PathTrace.rays; the camera constructor is a thin caller of the same entry). shader_ref64's docstring has the
+per-ray rules; here they enter as: the primary ray's origin gro = float32(origin * voxelScale) with the per-axis rounding
+of that product as err3 and lo3 (zero when exact); startIOF, medium colour and density from the voxel at floor(gro);
+dist from the ray's own world-space origin; dir_err = 4.5u (R.GIVEN_DIR_ERR, the float32 normalisation, derived there)
+for a given direction, whose components below DIR_MARGIN are decided by the shader's own rule because their error is
+relative; initRNG((i % width, i // width), sample); origins outside the world in `outside`, never traced or compared.
+  * Radiance. bound() = cerr + (ncon + 1) * u * |fc| + EPS_COLOR / 255 is the one colour bound: frame()'s tie test is
+    255 * bound() and radiance() returns (h(fc), bound(), decided).
+  * What the float comparison found missing: a hit point's error ACROSS the ray. The crossed coordinate is computed
+    (above), but the float32 run follows its own line o + (d + delta) s, and where that line meets the plane of axis b
+    after a path s, coordinate a differs by s (delta_a - delta_b d_a / d_b) <= s (dir_err + 6u) (1 + |d_a / d_b|),
+    whatever planes were crossed on the way. The per-axis bounds reset at every crossing and lost this; on a ray from
+    480 voxels away into glass the entry point moved by 3e-5 and the distance in the medium by 6.5e-5, 1.06 times the
+    bound then stated. march() now returns it (m.line) and it enters distanceInMedium's error (edim) at the hit and at
+    the origin of every ray spawned there. The floor margins keep the per-axis bounds: every decided ray of every
+    frame and batch agrees exactly with them, and they are doubled by DELTA_SAFETY.
+
+Not restated: origins outside the world, the display pass of a mode-2 frame (shader_ref64.display covers quad.frag), jitter, the thin lens and the
 adaptive rule of the accumulation (each tied to its own restatement), INDIRECT_SAMPLES / BOUNCES other than 1.
 
 flaws= plants one plausible misreading at a time, so the tests can show that the comparison catches it."""
@@ -89,7 +106,7 @@ import shader_ref64 as R
 
 U = R.U
 MAX_RAYS = 8
-E_EXP = 1.2e-7             # relative, det_expf on [-87, 0]
+E_EXP = R.E_EXP             # relative, det_expf on [-87, 0]
 E_POW = 1.2e-5             # relative, det_powf(x, 5) on [0, 1] where x^5 >= 1.7e-38
 E_POW_ABS = 1.7e-38
 E_SINCOS = 1.2e-7          # absolute, det_sinf / det_cosf on [0, 2 pi)
@@ -173,7 +190,7 @@ class _March:
     pass
 
 
-def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
+def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=None):
     """hitMarching (comp:248-330) for rays from grid-space origins org[n, 3] (per-axis error err3) with rayIOF iof.
     oax: an axis whose start floor is already decided (-1: none); lock_ax / lock_p: a coordinate that moves away from
     the plane lock_p and cannot cross it again (-1: none); lo3: per-axis error the ray's line keeps however often a
@@ -191,9 +208,13 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
     lo3 = err3 if lo3 is None else lo3
     m.snap = np.zeros(n, bool)
     m.P = np.zeros(n)
+    m.line = np.zeros(n)
     if not n:
         return m
-    m.amb |= np.any((d != 0) & (np.abs(d) < np.maximum(R.DIR_MARGIN, 2.0 * dir_err)[:, None]), 1)
+    small = np.any((d != 0) & (np.abs(d) < np.maximum(R.DIR_MARGIN, 2.0 * dir_err)[:, None]), 1)
+    if given is not None:                               # a caller's direction: its error is relative (R.dir_undecided)
+        small &= given == 0
+    m.amb |= small
     start = np.floor(org).astype(np.int64)
     inw = w.in_world(start)
     m.amb |= ~inw                                       # octreeFind's early return leaves the node box undefined (comp:143)
@@ -205,6 +226,7 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
     pos = org.copy()
     inv = R._inv_dir(d)
     steps = np.zeros(n, np.int64)
+    trav = np.zeros(n)
     act = np.nonzero(~m.amb)[0]
     for it in range(R.PRIMARY_CAP):
         if not act.size:
@@ -240,6 +262,13 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
         e[r[dec_ax], ax[dec_ax]] = np.minimum(e[r[dec_ax], ax[dec_ax]], land[dec_ax])
         e[sn, ax[sn]] = 0.0
         steps[act] = it + 1
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            trav[act] += np.abs(t)
+            # the float32 run follows its own line, o + (d + delta) s: where it meets the plane of axis b after a path s,
+            # coordinate a is off by s (delta_a - delta_b d_a / d_b), whatever the planes crossed on the way reset
+            line = (trav[act] * (dir_err[act] + 6.0 * U))[:, None] * (1.0 + np.abs(d[act] / dax[:, None]))
+        line[r, ax] = 0.0
+        line = np.where(np.isfinite(line), line, np.inf)
         pos[act], m.err3[act] = new, e
         prev = cur
         pr = np.where(w.refractive[prev], w.refr[prev], iof[act])              # comp:318
@@ -249,6 +278,7 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
         m.hit[h] = True
         m.mp[h], m.pt[h], m.ax[h] = mp[hit], new[hit], ax[hit]
         m.hv[h], m.lv[h], m.snap[h], m.P[h] = nxt[hit], prev[hit], sn[hit], P[hit]
+        m.line[h] = line[hit].max(1)
         node[act] = nxt
         act = act[go & ~hit]
     m.amb[act] = True                                                          # capped while still moving
@@ -257,8 +287,8 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None):
 
 
 _FIELDS = {"org": 3, "err3": 3, "lo3": 3, "d": 3, "dir_err": 0, "iof": 0, "w": 0, "tint": 3, "dim": 0, "edim": 0, "mc": 3, "md": 0,
-           "depth": 0, "rel": 0, "oax": 0, "lock_ax": 0, "lock_p": 0}
-_INT = ("depth", "oax", "lock_ax")
+           "depth": 0, "rel": 0, "oax": 0, "lock_ax": 0, "lock_p": 0, "given": 0}
+_INT = ("depth", "oax", "lock_ax", "given")
 STATS = ("rays", "peak_stack", "dropped_refract", "tir", "exit_glass", "deep_emission", "deep_sky", "miss_absorbed",
          "hit_absorbed", "glass_hits", "deep_ambient", "id_zero_hit", "id_reentry")
 
@@ -268,47 +298,70 @@ class PathTrace:
 
     def __init__(self, world, inv_proj, inv_view, cam_pos, width, height, xs=None, ys=None, sample=0, voxel_scale=1.0,
                  global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1), flaws=()):
-        assert light_dir is not None, "lightDir is a uniform: pass the host's float32 value"
-        unknown = set(flaws) - set(FLAWS) - set(R.FLAWS)
-        assert not unknown, unknown
-        self.w, self.flaws = world, frozenset(flaws)
+        """a frame: one origin (cameraPos), ray_dirs' directions, the frame's width"""
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
         self.W, self.H = int(width), int(height)
         if xs is None:
             ys, xs = np.mgrid[0:self.H, 0:self.W]
         self.xs, self.ys = np.asarray(xs, np.int64).ravel(), np.asarray(ys, np.int64).ravel()
-        self.scale = float(np.float32(voxel_scale))
-        self.gl = np.array(global_light, np.float32).astype(np.float64)
-        self.L = np.array(light_dir, np.float32).astype(np.float64)
-        self.hl = np.array(highlighted, np.int64)
         self.cam = np.array(cam_pos, np.float32).astype(np.float64)[:3]
         P = np.array(inv_proj, np.float32).astype(np.float64).reshape(4, 4).T
         Vw = np.array(inv_view, np.float32).astype(np.float64).reshape(4, 4).T
         d = R.ray_dirs(P, Vw, self.xs, self.ys, self.W, self.H, "pixel_center" in self.flaws)
         self.rng = init_rng(self.xs, self.ys, sample, self.W if "rng_row" in self.flaws else 1920)
-        self._run(d)
-
-    def _run(self, d):
-        w, n = self.w, d.shape[0]
-        self.amb = np.zeros(n, bool)
-        eye = self.cam * self.scale
-        emp = np.floor(eye).astype(np.int64)
-        if not w.in_world(emp):
+        self._run(self.cam, d, np.ones(d.shape[0]), given=False)
+        if self.outside.any():
             raise ValueError("eye outside the world: octreeFind's early return leaves the node box undefined (comp:143)")
-        e = int(w.find(emp[None])[0])
-        p0 = w.p[e, 0] / 255.0 * 3.0
-        self.eye_node = e
+
+    @classmethod
+    def rays(cls, world, origins, dirs, width, sample=0, voxel_scale=1.0, global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None,
+             highlighted=(-1, -1, -1), flaws=()):
+        """a ray batch (include/vrt.h, "Rays", "Direction", "width"): origins float32 (n, 3) or (3,) shared, in world units;
+        dirs float32 (n, 3) as given, any length; ray i of sample `sample` seeds initRNG((i % width, i // width), sample)"""
+        self = cls.__new__(cls)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        d, length = R.given_dirs(dirs)
+        self.W = int(width)
+        self.xs, self.ys = R.batch_pixels(d.shape[0], self.W, self.flaws)
+        self.H = int(self.ys.max()) + 1 if d.shape[0] else 0
+        self.rng = init_rng(self.xs, self.ys, sample, self.W if "rng_row" in self.flaws else 1920)
+        self._run(np.array(origins, np.float32).astype(np.float64), d, length, given=True)
+        return self
+
+    def _uniforms(self, world, voxel_scale, global_light, light_dir, highlighted, flaws):
+        assert light_dir is not None, "lightDir is a uniform: pass the host's float32 value"
+        unknown = set(flaws) - set(FLAWS) - set(R.FLAWS) - set(R.RAY_FLAWS)
+        assert not unknown, unknown
+        self.w, self.flaws = world, frozenset(flaws)
+        self.scale = float(np.float32(voxel_scale))
+        self.gl = np.array(global_light, np.float32).astype(np.float64)
+        self.L = np.array(light_dir, np.float32).astype(np.float64)
+        self.hl = np.array(highlighted, np.int64)
+
+    def _run(self, origins, d, length, given):
+        """the entry both constructors share: world-space origins (3,) or (n, 3), unit directions d[n, 3] in float64,
+        length[n]: |dir| as given (1 for a frame); given: the directions are a caller's (R.given_dirs)"""
+        w, n = self.w, d.shape[0]
+        self.org = np.broadcast_to(origins.reshape(-1, 3), (n, 3)).copy()
+        self.tlen = length if "rays_dir_length" in self.flaws else np.ones(n)
+        st = R.ray_start(w, self.org, self.scale, self.flaws)
+        self.outside = st.outside
+        self.amb = st.amb | (R.dir_undecided(d, given) & ~st.outside)
+        self.eye_node = st.node
         S = {k: np.zeros((n, MAX_RAYS, c) if c else (n, MAX_RAYS), np.int64 if k in _INT else np.float64)
              for k, c in _FIELDS.items()}
-        self.sp = np.ones(n, np.int64)
-        S["org"][:, 0] = eye
-        S["err3"][:, 0] = S["lo3"][:, 0] = U * np.abs(eye).max()
-        S["d"][:, 0] = d
-        S["iof"][:, 0] = p0 if 0.0 < p0 < 3.0 else 1.0                          # comp:448-449
+        self.sp = np.where(st.outside, 0, 1).astype(np.int64)
+        S["org"][:, 0] = np.where(st.outside[:, None], 0.0, st.gro)
+        S["err3"][:, 0] = S["lo3"][:, 0] = st.err
+        S["d"][:, 0] = np.where(st.outside[:, None], 1.0, d)
+        S["dir_err"][:, 0] = R.GIVEN_DIR_ERR if given else 0.0
+        S["iof"][:, 0] = st.iof                                                 # comp:448-449
         S["w"][:, 0] = 1.0
         S["tint"][:, 0] = self.gl[:3]
-        S["mc"][:, 0] = w.rgb[e] / 255.0 if w.a[e] > 0 else 1.0                  # comp:460
-        S["md"][:, 0] = w.a[e] / 255.0 * 5.0                                    # comp:461
+        S["mc"][:, 0] = st.mc                                                   # comp:460
+        S["md"][:, 0] = st.md                                                   # comp:461
         S["oax"][:, 0] = S["lock_ax"][:, 0] = -1
+        S["given"][:, 0] = 1 if given else 0
         self.S = S
         self.fc = np.zeros((n, 3))
         self.cerr = np.zeros((n, 3))
@@ -357,7 +410,7 @@ class PathTrace:
         w, fl = self.w, self.flaws
         r = self._pop(act)
         self.stats["rays"][act] += 1
-        m = march(w, r["org"], r["err3"], r["d"], r["dir_err"], r["iof"], r["oax"], r["lock_ax"], r["lock_p"], r["lo3"])
+        m = march(w, r["org"], r["err3"], r["d"], r["dir_err"], r["iof"], r["oax"], r["lock_ax"], r["lock_p"], r["lo3"], r["given"])
         self.amb[act] |= m.amb
         one = self.stats["rays"][act] == 1                                          # the primary ray
         self.first_hit[act[one]] = m.hit[one]
@@ -378,7 +431,8 @@ class PathTrace:
                 tc[ab] *= f
                 rel[ab] += e
                 self.stats["miss_absorbed"][act[mi[ab]]] += 1
-            c = np.where(shallow[:, None], self.gl[:3] * R.SKY * tc * wt[mi, None], tc * R.SKY * SUN * wt[mi, None] / deep_pi)
+            sun = 1.0 if "hdr_deep_sky_no_sun" in fl else SUN
+            c = np.where(shallow[:, None], self.gl[:3] * R.SKY * tc * wt[mi, None], tc * R.SKY * sun * wt[mi, None] / deep_pi)
             # sky seen by an exact ray (rel 0): the float32 products of comp:489 may be exact too (a white globalLight)
             f32 = ((self.gl[:3].astype(np.float32) * R.SKY.astype(np.float32)) * tc.astype(np.float32)) * wt[mi, None].astype(np.float32)
             exact = shallow & ~ab & (r["rel"][mi] == 0) & np.all(f32.astype(np.float64) == c, 1)
@@ -401,9 +455,10 @@ class PathTrace:
         normal = np.zeros((k, 3))
         normal[kr, ax] = s
         hpw = pt / self.scale                                                    # comp:498
-        ln = np.linalg.norm(hpw - org, axis=1)
+        ln = np.linalg.norm(hpw - org, axis=1) * np.where(r["given"][hi] == 1, self.tlen[idx], 1.0)
         dim = r["dim"][hi] + (ln if "dim_no_scale" in fl else ln / self.scale)  # comp:501
-        edim = r["edim"][hi] + (perr.max(1) + r["err3"][hi].max(1) + 4 * U * (np.abs(hpw).max(1) + np.abs(org).max(1) + ln)) / self.scale
+        lerr = m.line[hi] / self.scale                                           # the hit point's deviation across the ray
+        edim = r["edim"][hi] + lerr + (perr.max(1) + r["err3"][hi].max(1) + 4 * U * (np.abs(hpw).max(1) + np.abs(org).max(1) + ln)) / self.scale
         hva, lva = w.a[hv] > 0, w.a[lv] > 0
         n2 = np.where(w.refractive[hv], w.refr[hv], 1.0)                         # comp:503, 507
         n1 = np.where(w.refractive[lv], w.refr[lv], 1.0)                         # comp:504, 508
@@ -460,7 +515,8 @@ class PathTrace:
             if "face_order" in fl:
                 face ^= 1
             self.id[j] = ((lin * 6 + face + (1 << 31)) % (1 << 32)) - (1 << 31)
-            lc = np.linalg.norm(hpw[idset] - self.cam, axis=1)
+            eye = self.org[0] if "rays_dist_from_first_origin" in fl else self.org[j]
+            lc = np.linalg.norm(hpw[idset] - eye, axis=1) * self.tlen[j]
             self.dist[j] = np.trunc(lc)
             margin = (R.DELTA_FLOOR + R.DELTA_SAFETY * perr[idset].max(1)) / self.scale + 4 * U * lc
             self.und_dist[j] = np.abs(lc - np.rint(lc)) < margin
@@ -492,19 +548,20 @@ class PathTrace:
                                   P=m.P[hi[sp_g]], hv=hv[sp_g], lv=lv[sp_g], iof=r["iof"][hi[sp_g]], w=r["w"][hi[sp_g]],
                                   rel=rel[sp_g], tc=tc[sp_g], fres=fres[sp_g], e_f=e_f[sp_g], n1=n1[sp_g], n2=n2[sp_g],
                                   dep=dep[sp_g], tir=tir[sp_g], refr=refr[sp_g], eta=eta[sp_g], dd=dd[sp_g], kk=kk[sp_g],
-                                  dir_err=r["dir_err"][hi[sp_g]], dim=dim[sp_g], edim=edim[sp_g], lv_rgb=lv_rgb[sp_g],
+                                  dir_err=r["dir_err"][hi[sp_g]], dim=dim[sp_g], edim=edim[sp_g], lerr=lerr[sp_g], lv_rgb=lv_rgb[sp_g],
                                   lv_md=lv_md[sp_g], hv_rgb=hv_rgb[sp_g], hv_md=hv_md[sp_g])
         # ---- opaque, and glass deeper (comp:573-618) ----
         o = np.nonzero(~glass)[0]
         if not o.size:
             return
         em = np.where(hva[o], w.p[hv[o], 1] / 255.0, 0.0) * 10.0                 # comp:575
+        em0 = em / 10.0 if "hdr_emission_x1" in fl else em
         wo = r["w"][hi][o]
         base = sc[o] * tc[o] * wo[:, None]
         e0 = (em > 0) & (dep[o] == 0)
         e1 = (em > 0) & (dep[o] != 0)
         if e0.any():
-            self._add(idx[o[e0]], base[e0] * em[e0, None], rel[o[e0]] + 5 * U)
+            self._add(idx[o[e0]], base[e0] * em0[e0, None], rel[o[e0]] + 5 * U)
         if e1.any():
             self._add(idx[o[e1]], base[e1] * em[e1, None] / deep_pi, rel[o[e1]] + 6 * U)
             self.stats["deep_emission"][idx[o[e1]]] += 1
@@ -534,11 +591,11 @@ class PathTrace:
                 off = 1e-4 if "bounce_offset" in fl else 1e-1
                 o_ = pt[b] + normal[b] * off
                 self._push(bi, org=o_, err3=perr[b] + U * np.abs(o_), lo3=perr[b] + U * np.abs(o_), d=bd, dir_err=np.full(b.size, BOUNCE_DIR_ERR),
-                           iof=n1[b], w=r["w"][hi][b], tint=tc[b] * sc[b], dim=0.0, edim=0.0, mc=lv_rgb[b], md=lv_md[b],
-                           depth=dep[b] + 1, rel=rel[b] + 2 * U, oax=-1, lock_ax=-1, lock_p=0.0)
+                           iof=n1[b], w=r["w"][hi][b], tint=tc[b] * sc[b], dim=0.0, edim=lerr[b], mc=lv_rgb[b], md=lv_md[b],
+                           depth=dep[b] + 1, rel=rel[b] + 2 * U, oax=-1, lock_ax=-1, lock_p=0.0, given=0)
 
     def _spawn_glass(self, gi, d, normal, pt, perr, ax, P, hv, lv, iof, w, rel, tc, fres, e_f, n1, n2, dep, tir, refr, eta,
-                     dd, kk, dir_err, dim, edim, lv_rgb, lv_md, hv_rgb, hv_md):
+                     dd, kk, dir_err, dim, edim, lerr, lv_rgb, lv_md, hv_rgb, hv_md):
         """push the reflected and the refracted ray of the glass hits of pixels gi (comp:555-571); every array has one
         row per pixel: the hit (point, normal after the flip, error, axis, plane P, hit and last voxel), the popped ray
         (rayIOF, weight, direction error, distanceInMedium) and what comp:497-537 made of them"""
@@ -578,9 +635,9 @@ class PathTrace:
                 e3 += spread[:, None] * np.abs(rd / rd[qr, aq][:, None])
             e3[qr, aq] = spread
             self._push(gi[q], org=o, err3=e3, lo3=e3, d=rd, dir_err=dir_err[q], iof=n1[q], w=rw, tint=tc[q], dim=dim[q],
-                       edim=edim[q], mc=lv_rgb[q], md=lv_md[q], depth=dep[q],
+                       edim=edim[q] + lerr[q], mc=lv_rgb[q], md=lv_md[q], depth=dep[q],
                        rel=rel[q] + e_f[q] / np.maximum(fres[q], 1e-30) + 2 * U, oax=aq,
-                       lock_ax=np.where(away, aq, -1), lock_p=P[q])
+                       lock_ax=np.where(away, aq, -1), lock_p=P[q], given=0)
 
         def refract(sel):
             q = np.nonzero(sel & (self.sp[gi] < MAX_RAYS) & ~tir)[0]
@@ -591,9 +648,9 @@ class PathTrace:
             sq = np.sqrt(kk[q])
             de = dir_err[q] * (eta[q] + eta[q] ** 2 * np.abs(dd[q]) / sq) + 8 * U + 4 * U * (1 + eta[q] ** 2) / sq
             self._push(gi[q], org=o, err3=perr[q] + U * np.abs(o), lo3=perr[q] + U * np.abs(o), d=refr[q] / np.linalg.norm(refr[q], axis=1, keepdims=True),
-                       dir_err=de, iof=n2[q], w=w[q] * (1.0 - fres[q]), tint=tc[q], dim=0.0, edim=0.0, mc=hv_rgb[q],
+                       dir_err=de, iof=n2[q], w=w[q] * (1.0 - fres[q]), tint=tc[q], dim=0.0, edim=lerr[q], mc=hv_rgb[q],
                        md=hv_md[q], depth=dep[q], rel=rel[q] + e_f[q] / np.maximum(1.0 - fres[q], 1e-30) + 2 * U, oax=-1,
-                       lock_ax=-1, lock_p=0.0)
+                       lock_ax=-1, lock_p=0.0, given=0)
 
         first = np.ones(gi.size, bool)
         if "id_reflect_first" in self.flaws:
@@ -605,9 +662,19 @@ class PathTrace:
 
     def _absorb(self, md, dim, edim, mc):
         """exp(-density * distanceInMedium * (1 - mediumColor)) -> (factor[k, 3], relative error bound[k])"""
-        arg = -md[:, None] * dim[:, None] * (1.0 - mc)
-        e = np.abs(arg) * 5 * U + md[:, None] * (1.0 - mc) * edim[:, None] + E_EXP
-        return np.exp(arg), e.max(1)
+        return R.absorb(md, dim, edim, mc)
+
+    def bound(self):
+        """what a float32 run's colour may differ from fc by: cerr + (ncon + 1) * u * |fc| + EPS_COLOR / 255 (the margin the
+        byte test keeps around a .5 tie, in colour units); 0 for one exact term. frame()'s tie test and radiance() both
+        use it, so bytes and floats are held to the same bound."""
+        b = self.cerr + (self.ncon + 1)[:, None] * U * np.abs(self.fc) + R.EPS_COLOR / 255.0
+        b[(self.ncon == 1) & (self.cerr == 0).all(1)] = 0.0                      # one exact term: rint's ties-to-even
+        return b
+
+    def radiance(self):
+        """-> (h(fc) float64[n, 3], bound[n, 3], decided[n]): the unclamped colour through vrt.h's h (R.hdr_value)"""
+        return R.hdr_value(self.fc), self.bound(), ~self.amb & ~self.outside
 
     def frame(self):
         """-> shader_ref64.Frame of mode 2 with every field decided or not"""
@@ -616,14 +683,13 @@ class PathTrace:
         f.id, f.dist = self.id.copy(), self.dist.copy()
         x = np.clip(self.fc, 0.0, 1.0) * 255.0
         f.rgba = np.concatenate([np.rint(x), np.full((n, 1), 255.0)], 1).astype(np.int64)
-        eps = R.EPS_COLOR + 255.0 * (self.cerr + (self.ncon + 1)[:, None] * U * self.fc)
-        eps[(self.ncon == 1) & (self.cerr == 0).all(1)] = 0.0                      # one exact term: rint's ties-to-even
-        tie = np.abs(x - np.floor(x) - 0.5) < eps
+        tie = np.abs(x - np.floor(x) - 0.5) < 255.0 * self.bound()
         f.hit = self.first_hit.copy()
         f.kind = np.where(self.first_hit, R.KIND_OPAQUE, R.KIND_SKY)
-        f.dec_id = ~self.amb
+        f.outside = self.outside.copy()
+        f.dec_id = ~self.amb & ~self.outside
         f.dec_dist = f.dec_id & ~self.und_dist
-        f.dec_rgb = (~self.amb)[:, None] & ~tie
+        f.dec_rgb = f.dec_id[:, None] & ~tie
         f.stats = {k: v.copy() for k, v in self.stats.items()}
         return f
 

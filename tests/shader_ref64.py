@@ -44,7 +44,34 @@ Undecided pixels. A pixel is left out of a comparison when float32 rounding in t
     [0, 1] is off by at most (count+1)*u relative; 255*u ~ 1.52e-5), or a radius 200/sqrt(d) within 1e-5 of an integer
     without being one exactly.
 
-flaws= plants one plausible misreading at a time, so the tests can show that the comparison catches it."""
+Ray batches (Trace.rays; include/vrt.h "Rays", "Direction", "width"). The camera constructor is a thin caller of the same
+entry: one origin, ray_dirs' directions, the frame's width. Per ray:
+  * gro = float32(origin * voxelScale) is the march's start, exactly as the shader has it; the position bound is the
+    rounding |gro - origin * voxelScale| (zero when the product is exact, e.g. voxelScale 1, 0.5 or 2). An origin whose
+    floor is not decided within DELTA_FLOOR + DELTA_SAFETY * that bound is undecided (exact integers are decided).
+  * The start medium (startIOF, colour, density a * 5) is the voxel at floor(gro) (comp:445-461); distanceInMedium is
+    length(hitPoint / voxelScale - gro) / voxelScale as the GLSL has it and dist is int(length(hitPoint / voxelScale -
+    origin)), both from the ray's own origin. In modes 0 and 1 the start medium's absorption of the first hit
+    (comp:512-516) is restated: its relative error is |arg| * 5u (three products and the float32 distance) +
+    density * (1 - mediumColor) * (the distance's error) + E_EXP; distanceInMedium within its error of 1e-6 is undecided.
+  * Direction: d * (1 / sqrt(dot(d, d))) in float32, every operation rounded once. dot is three products and two sums
+    of non-negative terms (relative error <= 3u), sqrt halves that and rounds (<= 2.5u), the reciprocal rounds (<= 3.5u)
+    and the product rounds (<= 4.5u): every component has RELATIVE error <= GIVEN_DIR_ERR = 4.5u, below the ~6u
+    _step_error already carries for a frame's ray. So an exactly-zero component stays exactly zero with its sign, no
+    component changes sign, and the 1e-8 branch is the float32 run's unless |d| lies within BRANCH_MARGIN (1e-5 relative)
+    of 1e-8: given components below DIR_MARGIN are decided by restating the shader's rule for them (the 1e20 branch
+    sends such a ray backwards out of the world), as the zero_direction edge case does for exact zeros.
+  * The RNG pixel of ray i is (i % width, i // width) (mode 2: tests/path_ref64.py; modes 0 and 1 draw nothing).
+  * Origins outside the world are not restated: octreeFind's early return leaves the node box undefined (comp:143).
+    They are reported in `outside`, never compared, and counted neither as decided nor as undecided.
+
+Radiance. colour_bound is the one bound on a colour: rel * |c| + EPS_COLOR / 255, rel = 7u for the products (+ the
+absorption's terms), 0 for a sky whose float32 products are exact. frame()'s tie test and radiance() both call it.
+radiance() returns (h(c), bound, decided) with h of vrt_accum_keep_hdr point 1 (clamp to [0, 65504]; 1-Lipschitz, so the
+bound holds after clamping both sides). hdr_mean and tonemap restate vrt.h points 2-4 in float64 with the bound carried.
+
+flaws= plants one plausible misreading at a time, so the tests can show that the comparison catches it (FLAWS: the
+frame's; RAY_FLAWS: the ray-batch entry's and the HDR arithmetic's, kept apart because the frame tests pin FLAWS)."""
 import numpy as np
 
 U = 2.0 ** -24             # float32 unit roundoff
@@ -59,6 +86,14 @@ PRIMARY_DECIDED_STEPS = 1000
 
 FLAWS = ("face_order", "pixel_center", "dist_round", "alpha_hit", "no_shadow_cap", "emissive_shadows", "highlight_alpha",
          "display_across_ids")
+# misreadings of the ray-batch entry and of the HDR arithmetic (both references take them; tests/test_rays_reference64.py)
+RAY_FLAWS = ("rays_shared_medium", "rays_dist_from_first_origin", "rays_rng_linear", "rays_dir_length", "hdr_clamp_before_mean",
+             "hdr_emission_x1", "hdr_deep_sky_no_sun")
+E_EXP = 1.2e-7             # relative, det_expf on [-87, 0] (measured by tests/test_path_reference64.py)
+GIVEN_DIR_ERR = 4.5 * U    # relative error of each component of a caller's direction after the float32 normalisation
+BRANCH_MARGIN = 1e-5       # relative distance of a given component from the 1e-8 branch below which it is undecided
+COLOUR_REL = 7.0 * U       # a product of at most six float32-rounded factors
+HDR_MAX = 65504.0
 
 
 def _f32(x):
@@ -321,52 +356,191 @@ def not_in_shadow(w, pt, normal, err, L, flaws=()):
     return lit, amb
 
 
+def given_dirs(dirs):
+    """pathTrace's normalisation of a caller's direction (comp:441 as include/vrt.h states it: d * (1 / sqrt(dot(d, d))),
+    float32, every operation rounded once) -> (unit direction in float64 of the float32 input, |dir| as given).
+    Exactly-zero components stay exactly zero (0 * x == 0) and keep their sign; every other component keeps its sign and
+    has relative error <= GIVEN_DIR_ERR (see the module docstring)"""
+    g = np.array(dirs, np.float32).astype(np.float64).reshape(-1, 3)
+    length = np.sqrt((g * g).sum(1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return g / length[:, None], length
+
+
+def batch_pixels(n, width, flaws=()):
+    """the RNG pixel of ray i of a batch read as an image `width` wide: (i % width, i // width)"""
+    i = np.arange(n, dtype=np.int64)
+    if "rays_rng_linear" in flaws:
+        return i, np.zeros(n, np.int64)
+    return i % int(width), i // int(width)
+
+
+def dir_undecided(d, given):
+    """a component float32 may put on the other side of a rule of hitMarching: for a frame's ray 0 < |d| < DIR_MARGIN (its
+    error is absolute, ~6u); for a given direction the error is relative, so zero-ness, sign and the 1e-8 branch are the
+    float32 run's unless |d| is within BRANCH_MARGIN (relative) of 1e-8"""
+    a = np.abs(d)
+    if given:
+        return np.any(np.abs(a - 1e-8) <= BRANCH_MARGIN * 1e-8, 1) | ~np.isfinite(d).all(1)
+    return np.any((d != 0) & (a < DIR_MARGIN), 1)
+
+
+class _Start:
+    pass
+
+
+def ray_start(w, org, scale, flaws=()):
+    """comp:443-462 per ray from world-space origins org[n, 3] (float32 values): gro = float32(origin * voxelScale), its
+    rounding as the position bound (zero when the product is exact), the voxel at floor(gro) as the start medium
+    (startIOF, colour, density a * 5). Origins outside the world are reported in .outside and nothing else is said
+    about them (octreeFind's early return leaves the node box undefined there, comp:143)
+    -> .gro .err[n, 3] .outside .amb .start (node, -1 outside) .node (the medium's node) .iof .mc[n, 3] .md"""
+    st = _Start()
+    n = org.shape[0]
+    exact = org * scale
+    with np.errstate(invalid="ignore", over="ignore"):
+        st.gro = exact.astype(np.float32).astype(np.float64)
+        st.err = np.abs(st.gro - exact)
+        mp = np.floor(np.clip(st.gro, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
+    st.outside = ~w.in_world(mp) | ~np.isfinite(st.gro).all(1)
+    ins = np.nonzero(~st.outside)[0]
+    st.start = np.full(n, -1, np.int64)
+    st.start[ins] = w.find(mp[ins])
+    st.amb = np.zeros(n, bool)
+    g = st.gro[ins]
+    near = (g != np.rint(g)) & (np.abs(g - np.rint(g)) < DELTA_FLOOR + DELTA_SAFETY * st.err[ins].max(1)[:, None])
+    st.amb[ins] = _floor_undecided(w, g, mp[ins], st.start[ins], near)
+    e = np.maximum(st.start, 0)
+    if "rays_shared_medium" in flaws:
+        e = np.full(n, e[0])
+    st.node = e
+    p0 = w.p[e, 0] / 255.0 * 3.0
+    st.iof = np.where((p0 > 0.0) & (p0 < 3.0), p0, 1.0)                       # comp:448-449
+    st.mc = np.where((w.a[e] > 0)[:, None], w.rgb[e] / 255.0, 1.0)             # comp:460
+    st.md = w.a[e] / 255.0 * 5.0                                              # comp:461
+    return st
+
+
+def absorb(md, dim, edim, mc):
+    """exp(-density * distanceInMedium * (1 - mediumColor)) (comp:512-516) -> (factor[k, 3], relative error bound[k]):
+    the exponent's three products and the float32 distance (|arg| * 5u), the distance's own error, det_expf"""
+    arg = -md[:, None] * dim[:, None] * (1.0 - mc)
+    e = np.abs(arg) * 5 * U + md[:, None] * (1.0 - mc) * edim[:, None] + E_EXP
+    return np.exp(arg), e.max(1)
+
+
+def colour_bound(c, rel, extra=0.0):
+    """what a float32 run may differ from the float64 colour c by: rel * |c| + extra, plus EPS_COLOR / 255 (the margin the
+    byte test has always kept around a .5 tie, in colour units); rel < 0 marks a colour that is exact in float32 (bound 0:
+    the byte is rint's ties-to-even). frame()'s tie test and radiance() both use it."""
+    rel = np.asarray(rel)
+    return np.where((rel < 0)[:, None], 0.0, rel[:, None] * np.abs(c) + extra + EPS_COLOR / 255.0)
+
+
+def hdr_value(c):
+    """h(c) of vrt_accum_keep_hdr point 1 (include/vrt.h): clamp to [0, 65504]. 1-Lipschitz: |h(a) - h(b)| <= |a - b|, so a
+    value within its bound of either end is compared after clamping both sides with the same bound."""
+    return np.clip(c, 0.0, HDR_MAX)
+
+
+def hdr_mean(values, bounds, decided, flaws=()):
+    """vrt.h points 2-3 over samples: values / bounds float64[k][n, 3], decided bool[k][n] -> (mean, bound, decided).
+    The mean of h(c_k); its bound is the mean of the samples' bounds plus u * |mean| for the final cast to float (the
+    float64 sums' own error, <= k * 2^-53 relative, is far below that and is not carried). A ray's mean is decided only
+    when every one of its samples is."""
+    v = [np.minimum(x, 1.0) for x in values] if "hdr_clamp_before_mean" in flaws else values
+    k = len(v)
+    mean = sum(hdr_value(x) for x in v) / k
+    return mean, sum(bounds) / k + U * np.abs(mean), np.all(decided, axis=0)
+
+
+def tonemap(mean, bound, op, exposure):
+    """vrt.h point 4 on a float64 mean with its bound -> (bytes int64[n, 3], byte decided[n, 3], y, y's bound).
+    clamp: y = e * x, bound e * b (exact in float32 for a power-of-two exposure; u * |y| more for any other).
+    reinhard: x' = e * x, y = x' / (1 + x'): 1-Lipschitz in x' for x' >= 0, plus 3u of its value (the product, the sum and
+    the quotient round once each). A byte is decided when unorm8's x = clamp(y, 0, 1) * 255 is further than 255 * bound
+    from a .5 tie (the bound already holds EPS_COLOR / 255)."""
+    e = float(np.float32(exposure))
+    x = e * mean
+    b = e * bound
+    if np.frexp(e)[0] != 0.5:
+        b = b + U * np.abs(x)
+    if op == "reinhard":
+        y = x / (1.0 + x)
+        b = b + 3 * U * np.abs(y)
+    else:
+        assert op == "clamp", op
+        y = x
+    t = np.clip(y, 0.0, 1.0) * 255.0
+    return np.rint(t).astype(np.int64), np.abs(t - np.floor(t) - 0.5) >= 255.0 * b, y, b
+
+
 class Trace:
     """The first hit of every requested pixel (and its shadow ray), from which frame(mode) assembles the outputs."""
 
     def __init__(self, world, inv_proj, inv_view, cam_pos, width, height, xs=None, ys=None, voxel_scale=1.0,
                  global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1), flaws=()):
-        assert light_dir is not None, "lightDir is a uniform: pass the host's float32 value"
-        unknown = set(flaws) - set(FLAWS)
-        assert not unknown, unknown
-        self.w, self.flaws = world, frozenset(flaws)
+        """a frame: one origin (cameraPos), ray_dirs' directions, the frame's width"""
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
         self.W, self.H = int(width), int(height)
         if xs is None:
             ys, xs = np.mgrid[0:self.H, 0:self.W]
         self.xs, self.ys = np.asarray(xs, np.int64).ravel(), np.asarray(ys, np.int64).ravel()
+        self.cam = np.array(cam_pos, np.float32).astype(np.float64)[:3]
+        d = ray_dirs(np.array(inv_proj, np.float32).astype(np.float64).reshape(4, 4).T,
+                     np.array(inv_view, np.float32).astype(np.float64).reshape(4, 4).T,
+                     self.xs, self.ys, self.W, self.H, "pixel_center" in self.flaws)
+        self._trace(self.cam, d, np.ones(d.shape[0]), given=False)
+        if self.outside.any():
+            raise ValueError("eye outside the world: octreeFind's early return leaves the node box undefined (comp:143)")
+
+    @classmethod
+    def rays(cls, world, origins, dirs, width, sample=0, voxel_scale=1.0, global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None,
+             highlighted=(-1, -1, -1), flaws=()):
+        """a ray batch (include/vrt.h, "Rays", "Direction", "width"): origins float32 (n, 3) or (3,) shared, in world units;
+        dirs float32 (n, 3) as given, any length; ray i is pixel (i % width, i // width) of an image of that width for the
+        random numbers (modes 0 and 1 draw none, so `sample` changes nothing here)"""
+        self = cls.__new__(cls)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        d, length = given_dirs(dirs)
+        self.W = int(width)
+        self.xs, self.ys = batch_pixels(d.shape[0], self.W, self.flaws)
+        self.H = int(self.ys.max()) + 1 if d.shape[0] else 0
+        self._trace(np.array(origins, np.float32).astype(np.float64), d, length, given=True)
+        return self
+
+    def _uniforms(self, world, voxel_scale, global_light, light_dir, highlighted, flaws):
+        assert light_dir is not None, "lightDir is a uniform: pass the host's float32 value"
+        unknown = set(flaws) - set(FLAWS) - set(RAY_FLAWS)
+        assert not unknown, unknown
+        self.w, self.flaws = world, frozenset(flaws)
         self.scale = float(np.float32(voxel_scale))
         self.gl = np.array(global_light, np.float32).astype(np.float64)
         self.L = np.array(light_dir, np.float32).astype(np.float64)
         self.hl = np.array(highlighted, np.int64)
-        self.cam = np.array(cam_pos, np.float32).astype(np.float64)[:3]
-        self._rays(np.array(inv_proj, np.float32).astype(np.float64).reshape(4, 4).T,
-                   np.array(inv_view, np.float32).astype(np.float64).reshape(4, 4).T)
+
+    def _trace(self, origins, d, length, given):
+        """the entry both constructors share: world-space origins (3,) or (n, 3), unit directions d[n, 3] in float64,
+        length[n]: |dir| as given (1 for a frame); given: the directions are a caller's (see given_dirs)"""
+        n = d.shape[0]
+        self.d = d
+        self.org = np.broadcast_to(origins.reshape(-1, 3), (n, 3)).copy()
+        self.tlen = length if "rays_dir_length" in self.flaws else np.ones(n)
+        self.amb = dir_undecided(d, given)
         self._primary()
         self._shadow()
-
-    def _rays(self, P, Vw):
-        self.d = ray_dirs(P, Vw, self.xs, self.ys, self.W, self.H, "pixel_center" in self.flaws)
-        self.amb = np.any((self.d != 0) & (np.abs(self.d) < DIR_MARGIN), 1)
 
     def _primary(self):
         """pathTrace's first hitMarching (comp:443-478) for every ray"""
         w, n = self.w, self.d.shape[0]
-        eye = self.cam * self.scale
-        emp = np.floor(eye).astype(np.int64)
-        if not w.in_world(emp):
-            raise ValueError("eye outside the world: octreeFind's early return leaves the node box undefined (comp:143)")
-        e = int(w.find(emp[None])[0])
-        self.err = np.full(n, U * np.abs(eye).max())                          # float32 error bound of rayPos so far
-        near = (eye != np.rint(eye)) & (np.abs(eye - np.rint(eye)) < DELTA_FLOOR + DELTA_SAFETY * self.err[0])
-        if _floor_undecided(w, eye[None], emp[None], np.array([e]), near[None])[0]:
-            self.amb[:] = True
-        self.eye_node = e
-        p0 = w.p[e, 0] / 255.0 * 3.0
-        self.iof = p0 if 0.0 < p0 < 3.0 else 1.0                              # comp:448-449
-        self.in_medium = w.a[e] > 0                                            # comp:460-461: mediumDensity = a*5
-        pos = np.tile(eye, (n, 1))
+        st = ray_start(w, self.org, self.scale, self.flaws)
+        self.outside, self.gro, self.err0 = st.outside, st.gro, st.err.max(1)
+        self.err = self.err0.copy()                                            # float32 error bound of rayPos so far
+        self.amb |= st.amb
+        self.eye_node, self.iof, self.in_medium, self.mc, self.md = st.node, st.iof, st.md > 0, st.mc, st.md
+        pos = self.gro.copy()
         inv = _inv_dir(self.d)
-        cur = np.full(n, e, np.int64)
+        cur = np.maximum(st.start, 0)
         self.hit = np.zeros(n, bool)
         self.mp = np.zeros((n, 3), np.int64)
         self.pt = np.zeros((n, 3))
@@ -374,7 +548,7 @@ class Trace:
         self.hv = np.zeros(n, np.int64)
         self.lv = np.zeros(n, np.int64)
         self.steps = np.zeros(n, np.int64)
-        act = np.arange(n)
+        act = np.nonzero(~self.outside)[0]
         for it in range(PRIMARY_CAP):
             if not act.size:
                 break
@@ -395,7 +569,7 @@ class Trace:
             if "alpha_hit" in self.flaws:
                 hit = (w.a[nxt] > 0) & (w.a[prev] == 0)
             else:
-                pr = np.where(w.refractive[prev], w.refr[prev], self.iof)      # comp:318-321
+                pr = np.where(w.refractive[prev], w.refr[prev], self.iof[act])  # comp:318-321
                 cr = np.where(w.refractive[nxt], w.refr[nxt], 1.0)
                 hit = np.abs(cr - pr) > 1e-4
             h = act[hit]
@@ -417,7 +591,7 @@ class Trace:
         rgb[hl] = 1.0 - rgb[hl]
         if "highlight_alpha" not in self.flaws:
             a[hl] = 1.0
-        emission = np.where(hva, w.p[hv, 1] / 255.0, 0.0) * 10.0               # comp:503, 575
+        emission = np.where(hva, w.p[hv, 1] / 255.0, 0.0) * (1.0 if "hdr_emission_x1" in self.flaws else 10.0)   # comp:503, 575
         s = -np.sign(self.d[i, self.ax[i]])                                    # comp:293-294
         normal = np.zeros((i.size, 3))
         normal[np.arange(i.size), self.ax[i]] = s
@@ -438,55 +612,90 @@ class Trace:
         i, normal = i[need], normal[need]
         self.lit[i], self.shadow_amb[i] = not_in_shadow(self.w, self.pt[i], normal, self.err[i], self.L, self.flaws)
 
+    def _colour(self, mode):
+        """-> (c float64[n, 3], rel[n] relative error bound, open[n]: colour not restated, hits i, surface tuple)"""
+        n = self.d.shape[0]
+        c = np.zeros((n, 3))
+        rel = np.full(n, COLOUR_REL)
+        colour_open = np.zeros(n, bool)
+        tc = self.gl[:3]
+        c[~self.hit] = self.gl[:3] * SKY * tc                                 # comp:489
+        # the float32 products of comp:489 may be exact (a white globalLight): then the sky is the float32 run's, bound 0
+        f32 = (self.gl[:3].astype(np.float32) * SKY.astype(np.float32)) * tc.astype(np.float32)
+        if np.all(f32.astype(np.float64) == self.gl[:3] * SKY * tc):
+            rel[~self.hit] = -1.0
+        sf = self._surface()
+        i, rgb, a, emission, normal, ndotl, ax, s = sf
+        opaque = a >= 1.0
+        em = opaque & (emission > 0)
+        tr = ~opaque
+        op = opaque & ~em
+        # the start medium's absorption (comp:501, 512-516): length(hitPoint / voxelScale - origin) / voxelScale with the
+        # grid-space origin, as the GLSL has it
+        tci = np.tile(tc, (i.size, 1))
+        hpw = self.pt[i] / self.scale
+        ln = np.linalg.norm(hpw - self.gro[i], axis=1) * self.tlen[i]
+        dim = ln / self.scale
+        edim = (self.err[i] + self.err0[i] + 4 * U * (np.abs(hpw).max(1) + np.abs(self.gro[i]).max(1) + ln)) / self.scale
+        md = self.md[i]
+        colour_open[i] |= (md > 0) & (np.abs(dim - 1e-6) <= edim)
+        ab = (dim > 1e-6) & (md > 0.0)
+        if ab.any():
+            f, e = absorb(md[ab], dim[ab], edim[ab], self.mc[i[ab]])
+            tci[ab] *= f
+            rel[i[ab]] += e + U
+        cc = np.zeros((i.size, 3))
+        cc[tr] = tci[tr] * rgb[tr] * (self.gl[:3] * ndotl[tr, None])           # comp:548-552
+        cc[em] = tci[em] * rgb[em] * emission[em, None]                        # comp:576-577
+        lit = self.lit[i] if mode == 1 else np.ones(i.size, bool)
+        cc[op] = self.gl[:3] * (lit[op] * ndotl[op])[:, None] * rgb[op] * tci[op] / PI   # comp:587-588
+        c[i] = cc
+        if mode == 1:
+            colour_open[i[op]] |= self.shadow_amb[i[op]]
+        if mode == 2:                                                          # bounce and glass stack: not restated
+            colour_open[i[op | tr]] = True
+        return c, rel, colour_open, sf, (em, tr, op)
+
     def frame(self, mode):
         """-> Frame for VRT_MODE_PRIMARY (0), VRT_MODE_PRIMARY_SHADOW (1) or VRT_MODE_FULL (2)"""
         w, n = self.w, self.d.shape[0]
         f = Frame(self.xs, self.ys, mode)
         f.id = np.zeros(n, np.int64)
         f.dist = np.full(n, int(w.wmax[0] - w.wmin[0]), np.int64)            # comp:441
-        c = np.zeros((n, 3))
         f.kind = np.full(n, KIND_SKY, np.int64)
         f.hit = self.hit.copy()
-        tc = self.gl[:3]
-        c[~self.hit] = self.gl[:3] * SKY * tc                                 # comp:489
+        f.outside = self.outside.copy()
         und_dist = np.zeros(n, bool)
-        colour_open = np.zeros(n, bool)
-        i, rgb, a, emission, normal, ndotl, ax, s = self._surface()
+        c, rel, colour_open, (i, rgb, a, emission, normal, ndotl, ax, s), (em, tr, op) = self._colour(mode)
         opaque = a >= 1.0
         idset = opaque                                                         # comp:539
         j = i[idset]
         lin = self.mp[j, 0] + w.tex_dim * (self.mp[j, 1] + w.tex_dim * self.mp[j, 2])
         face = self._face(ax[idset], s[idset])
         f.id[j] = ((lin * 6 + face + (1 << 31)) % (1 << 32)) - (1 << 31)     # int arithmetic wraps in GLSL
-        ln = np.linalg.norm(self.pt[j] / self.scale - self.cam, axis=1)        # comp:498, 543
+        eye = self.org[0] if "rays_dist_from_first_origin" in self.flaws else self.org[j]
+        ln = np.linalg.norm(self.pt[j] / self.scale - eye, axis=1) * self.tlen[j]   # comp:498, 543
         f.dist[j] = np.rint(ln) if "dist_round" in self.flaws else np.trunc(ln)
         margin = (DELTA_FLOOR + DELTA_SAFETY * self.err[j]) / self.scale + 4 * U * ln
         und_dist[j] = np.abs(ln - np.rint(ln)) < margin
-        em = opaque & (emission > 0)
-        tr = ~opaque
-        op = opaque & ~em
         f.kind[i[em]], f.kind[i[tr]], f.kind[i[op]] = KIND_EMISSIVE, KIND_TRANSLUCENT, KIND_OPAQUE
-        cc = np.zeros((i.size, 3))
-        cc[tr] = tc * rgb[tr] * (self.gl[:3] * ndotl[tr, None])                # comp:548-552
-        cc[em] = tc * rgb[em] * emission[em, None]                             # comp:576-577
-        lit = self.lit[i] if mode == 1 else np.ones(i.size, bool)
-        cc[op] = self.gl[:3] * (lit[op] * ndotl[op])[:, None] * rgb[op] * tc / PI   # comp:587-588
-        c[i] = cc
-        if self.in_medium:                                                     # absorption (comp:512-516) is not restated
-            colour_open[i] = True
-        if mode == 1:
-            colour_open[i[op]] |= self.shadow_amb[i[op]]
-        if mode == 2:                                                          # bounce and glass stack: not restated
-            colour_open[i[op | tr]] = True
-        x = np.clip(c, 0.0, 1.0) * 255.0
+        cl = np.clip(c, 0.0, 1.0)
+        x = cl * 255.0
         f.rgba = np.concatenate([np.rint(x), np.full((n, 1), 255.0)], 1).astype(np.int64)
-        tie = np.abs(x - np.floor(x) - 0.5) < EPS_COLOR
-        f.dec_id = ~self.amb.copy()
+        tie = np.abs(x - np.floor(x) - 0.5) < 255.0 * colour_bound(cl, rel)
+        f.dec_id = ~self.amb & ~self.outside
         if mode == 2:                                                          # a glass first hit leaves the id to the stack
             f.dec_id[i[tr]] = False
         f.dec_dist = f.dec_id & ~und_dist
-        f.dec_rgb = (~self.amb & ~colour_open)[:, None] & ~tie
+        f.dec_rgb = (~self.amb & ~self.outside & ~colour_open)[:, None] & ~tie
         return f
+
+    def radiance(self, mode):
+        """the unclamped colour of mode 0 or 1 -> (h(c) float64[n, 3], bound[n, 3], decided[n]): a float32 run's h(c) lies
+        within bound of it wherever decided (frame()'s tie test uses the same bound on the clamped colour)"""
+        assert mode in (0, 1)
+        c, rel, colour_open, _, _ = self._colour(mode)
+        return hdr_value(c), colour_bound(c, rel), ~self.amb & ~self.outside & ~colour_open
 
     def _face(self, ax, s):
         """getFaceIndex (comp:419-433) of an axis normal with sign s (ax -1: the zero normal)"""
@@ -512,12 +721,23 @@ class Frame:
             scope &= self.kind != KIND_TRANSLUCENT
         return float((~full[scope]).mean()) if scope.any() else 0.0
 
+    def all_decided(self):
+        return self.dec_id & self.dec_dist & self.dec_rgb.all(1)
+
+    def in_world_undecided_share(self):
+        """of a batch's rays whose origin is inside the world: not every field decided (outside origins are neither)"""
+        inw = ~self.outside
+        return float((~self.all_decided()[inw]).mean()) if inw.any() else 0.0
+
 
 def compare(ref, rgba, idd):
     """ref (Frame) against images rgba8[H, W, 4] / id_dist[H, W, 2] at ref's pixels, on decided fields only.
     -> dict: checked / mismatch counts per field, decided hit pixels, undecided share of hit pixels, first mismatch"""
-    got_rgba = np.asarray(rgba)[ref.ys, ref.xs].astype(np.int64)
-    got = np.asarray(idd)[ref.ys, ref.xs].astype(np.int64)
+    rgba, idd = np.asarray(rgba), np.asarray(idd)
+    if rgba.ndim == 2:                                                         # a ray batch: one row per ray
+        got_rgba, got = rgba.astype(np.int64), idd.astype(np.int64)
+    else:
+        got_rgba, got = rgba[ref.ys, ref.xs].astype(np.int64), idd[ref.ys, ref.xs].astype(np.int64)
     bad_id = ref.dec_id & (got[:, 0] != ref.id)
     bad_dist = ref.dec_dist & (got[:, 1] != ref.dist)
     bad_rgb = ref.dec_rgb & (got_rgba[:, :3] != ref.rgba[:, :3])
