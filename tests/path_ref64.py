@@ -96,8 +96,12 @@ relative; initRNG((i % width, i // width), sample); origins outside the world in
     the origin of every ray spawned there. The floor margins keep the per-axis bounds: every decided ray of every
     frame and batch agrees exactly with them, and they are doubled by DELTA_SAFETY.
 
-Not restated: origins outside the world, the display pass of a mode-2 frame (shader_ref64.display covers quad.frag), jitter, the thin lens and the
-adaptive rule of the accumulation (each tied to its own restatement), INDIRECT_SAMPLES / BOUNCES other than 1.
+Jittered and thin-lens samples of the accumulation enter through PathTrace.lens: tests/lens_ref64.py restates their rays
+in float64 with a per-ray origin bound (err3 / lo3) and direction bound (dir_err), and _run carries both as it does a
+batch's.
+
+Not restated: origins outside the world, the display pass of a mode-2 frame (shader_ref64.display covers quad.frag), the
+adaptive rule of the accumulation (tied to its own restatement), INDIRECT_SAMPLES / BOUNCES other than 1.
 
 flaws= plants one plausible misreading at a time, so the tests can show that the comparison catches it."""
 import numpy as np
@@ -338,15 +342,41 @@ class PathTrace:
         self.L = np.array(light_dir, np.float32).astype(np.float64)
         self.hl = np.array(highlighted, np.int64)
 
-    def _run(self, origins, d, length, given):
-        """the entry both constructors share: world-space origins (3,) or (n, 3), unit directions d[n, 3] in float64,
-        length[n]: |dir| as given (1 for a frame); given: the directions are a caller's (R.given_dirs)"""
+    @classmethod
+    def lens(cls, world, rays, voxel_scale=1.0, global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1),
+             flaws=()):
+        """a jittered and / or thin-lens sample of the accumulation (include/vrt.h VRT_ACCUM_JITTER, vrt_set_lens): `rays` is
+        tests/lens_ref64.py's lens_rays(camera block, W, H, xs, ys, sample, jitter, aperture, focus) -- per-ray float64
+        origins and unit directions with the bounds of their float32 counterparts; initRNG(pixel, sample)"""
+        self = cls.__new__(cls)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        self.W, self.H, self.xs, self.ys = rays.W, rays.H, rays.xs, rays.ys
+        self.rng = init_rng(self.xs, self.ys, rays.rng_sample, 1920)
+        self._run(rays.o, rays.d, np.ones(rays.d.shape[0]), given=False, err3=rays.err_o * abs(self.scale) + U * np.abs(rays.o * self.scale),
+                  dir_err=rays.dir_err, medium_org=rays.medium_org, measure_org=rays.measure_org, amb=rays.amb)
+        return self
+
+    def _run(self, origins, d, length, given, err3=None, dir_err=None, medium_org=None, measure_org=None, amb=None):
+        """the entry the constructors share: world-space origins (3,) or (n, 3), unit directions d[n, 3] in float64,
+        length[n]: |dir| as given (1 for a frame); given: the directions are a caller's (R.given_dirs). Optional, for
+        computed rays (R.Trace._trace has the same): err3[n, 3] the origin's bound in grid units on top of ray_start's
+        rounding, dir_err[n] the primary ray's direction bound, amb[n] rays undecided before they start, medium_org /
+        measure_org (planted misreadings only)"""
         w, n = self.w, d.shape[0]
         self.org = np.broadcast_to(origins.reshape(-1, 3), (n, 3)).copy()
         self.tlen = length if "rays_dir_length" in self.flaws else np.ones(n)
-        st = R.ray_start(w, self.org, self.scale, self.flaws)
+        st = R.ray_start(w, self.org, self.scale, self.flaws, err3)
+        if medium_org is not None:
+            m = R.ray_start(w, np.broadcast_to(medium_org, self.org.shape), self.scale)
+            st.node, st.iof, st.mc, st.md = m.node, m.iof, m.mc, m.md
+        self.dim_org = None
+        if measure_org is not None:
+            self.org = np.broadcast_to(measure_org, self.org.shape).copy()
+            self.dim_org = self.org * self.scale
         self.outside = st.outside
         self.amb = st.amb | (R.dir_undecided(d, given) & ~st.outside)
+        if amb is not None:
+            self.amb |= amb
         self.eye_node = st.node
         S = {k: np.zeros((n, MAX_RAYS, c) if c else (n, MAX_RAYS), np.int64 if k in _INT else np.float64)
              for k, c in _FIELDS.items()}
@@ -354,7 +384,7 @@ class PathTrace:
         S["org"][:, 0] = np.where(st.outside[:, None], 0.0, st.gro)
         S["err3"][:, 0] = S["lo3"][:, 0] = st.err
         S["d"][:, 0] = np.where(st.outside[:, None], 1.0, d)
-        S["dir_err"][:, 0] = R.GIVEN_DIR_ERR if given else 0.0
+        S["dir_err"][:, 0] = R.GIVEN_DIR_ERR if given else (0.0 if dir_err is None else dir_err)
         S["iof"][:, 0] = st.iof                                                 # comp:448-449
         S["w"][:, 0] = 1.0
         S["tint"][:, 0] = self.gl[:3]
@@ -448,6 +478,8 @@ class PathTrace:
         k = hi.size
         kr = np.arange(k)
         org, d, dep = r["org"][hi], r["d"][hi], depth[hi]
+        if self.dim_org is not None:
+            org = np.where(one[hi][:, None], self.dim_org[idx], org)
         derr = r["dir_err"][hi] + 8 * U
         hv, lv, ax, pt, mp = m.hv[hi], m.lv[hi], m.ax[hi], m.pt[hi], m.mp[hi]
         perr = m.err3[hi]

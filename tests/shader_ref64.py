@@ -65,6 +65,12 @@ entry: one origin, ray_dirs' directions, the frame's width. Per ray:
   * Origins outside the world are not restated: octreeFind's early return leaves the node box undefined (comp:143).
     They are reported in `outside`, never compared, and counted neither as decided nor as undecided.
 
+Jittered and thin-lens samples (Trace.lens; include/vrt.h VRT_ACCUM_JITTER, vrt_set_lens). tests/lens_ref64.py restates
+the sample's rays in float64 with a per-axis origin bound and a per-ray direction bound; _trace takes them as optional
+inputs: the origin bound joins ray_start's rounding (the floor of the origin, the position error, the distances), the
+direction bound adds dir_err * t to every step's position error and makes a component within 2 * dir_err of 0 undecided.
+Still not restated: origins outside the world, the adaptive rule, INDIRECT_SAMPLES / BOUNCES other than 1.
+
 Radiance. colour_bound is the one bound on a colour: rel * |c| + EPS_COLOR / 255, rel = 7u for the products (+ the
 absorption's terms), 0 for a sky whose float32 products are exact. frame()'s tie test and radiance() both call it.
 radiance() returns (h(c), bound, decided) with h of vrt_accum_keep_hdr point 1 (clamp to [0, 65504]; 1-Lipschitz, so the
@@ -389,11 +395,12 @@ class _Start:
     pass
 
 
-def ray_start(w, org, scale, flaws=()):
+def ray_start(w, org, scale, flaws=(), err3=None):
     """comp:443-462 per ray from world-space origins org[n, 3] (float32 values): gro = float32(origin * voxelScale), its
     rounding as the position bound (zero when the product is exact), the voxel at floor(gro) as the start medium
     (startIOF, colour, density a * 5). Origins outside the world are reported in .outside and nothing else is said
-    about them (octreeFind's early return leaves the node box undefined there, comp:143)
+    about them (octreeFind's early return leaves the node box undefined there, comp:143). err3[n, 3]: what the float32
+    run's gro may differ by on top of that rounding, in grid units (a computed origin: tests/lens_ref64.py)
     -> .gro .err[n, 3] .outside .amb .start (node, -1 outside) .node (the medium's node) .iof .mc[n, 3] .md"""
     st = _Start()
     n = org.shape[0]
@@ -401,6 +408,8 @@ def ray_start(w, org, scale, flaws=()):
     with np.errstate(invalid="ignore", over="ignore"):
         st.gro = exact.astype(np.float32).astype(np.float64)
         st.err = np.abs(st.gro - exact)
+        if err3 is not None:
+            st.err = st.err + err3
         mp = np.floor(np.clip(st.gro, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
     st.outside = ~w.in_world(mp) | ~np.isfinite(st.gro).all(1)
     ins = np.nonzero(~st.outside)[0]
@@ -519,22 +528,50 @@ class Trace:
         self.L = np.array(light_dir, np.float32).astype(np.float64)
         self.hl = np.array(highlighted, np.int64)
 
-    def _trace(self, origins, d, length, given):
-        """the entry both constructors share: world-space origins (3,) or (n, 3), unit directions d[n, 3] in float64,
-        length[n]: |dir| as given (1 for a frame); given: the directions are a caller's (see given_dirs)"""
+    @classmethod
+    def lens(cls, world, rays, voxel_scale=1.0, global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1),
+             flaws=()):
+        """a jittered and / or thin-lens sample of the accumulation (include/vrt.h VRT_ACCUM_JITTER, vrt_set_lens): `rays` is
+        tests/lens_ref64.py's lens_rays(camera block, W, H, xs, ys, sample, jitter, aperture, focus) -- per-ray float64
+        origins and unit directions with the bounds of their float32 counterparts (modes 0 and 1 draw no random number)"""
+        self = cls.__new__(cls)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        self.W, self.H, self.xs, self.ys = rays.W, rays.H, rays.xs, rays.ys
+        self._trace(rays.o, rays.d, np.ones(rays.d.shape[0]), given=False, err3=rays.err_o * abs(self.scale) + U * np.abs(rays.o * self.scale),
+                    dir_err=rays.dir_err, medium_org=rays.medium_org, measure_org=rays.measure_org)
+        self.amb |= rays.amb
+        return self
+
+    def _trace(self, origins, d, length, given, err3=None, dir_err=None, medium_org=None, measure_org=None):
+        """the entry the constructors share: world-space origins (3,) or (n, 3), unit directions d[n, 3] in float64,
+        length[n]: |dir| as given (1 for a frame); given: the directions are a caller's (see given_dirs). Optional, for
+        computed rays: err3[n, 3] the origin's bound in grid units on top of ray_start's rounding, dir_err[n] the absolute
+        bound of each direction component (it replaces nothing: the step error's own ~6u stays), medium_org / measure_org
+        world-space origins the start medium is looked up at / dist and distanceInMedium are measured from instead of the
+        ray's own (planted misreadings only)"""
         n = d.shape[0]
         self.d = d
         self.org = np.broadcast_to(origins.reshape(-1, 3), (n, 3)).copy()
         self.tlen = length if "rays_dir_length" in self.flaws else np.ones(n)
         self.amb = dir_undecided(d, given)
+        self._err3, self._dir_err, self._medium_org, self._measure_org = err3, dir_err, medium_org, measure_org
+        if dir_err is not None:
+            self.amb |= np.any((d != 0) & (np.abs(d) < 2.0 * np.asarray(dir_err)[:, None]), 1)
         self._primary()
         self._shadow()
 
     def _primary(self):
         """pathTrace's first hitMarching (comp:443-478) for every ray"""
         w, n = self.w, self.d.shape[0]
-        st = ray_start(w, self.org, self.scale, self.flaws)
+        st = ray_start(w, self.org, self.scale, self.flaws, self._err3)
+        if self._medium_org is not None:
+            m = ray_start(w, np.broadcast_to(self._medium_org, self.org.shape), self.scale)
+            st.node, st.iof, st.mc, st.md = m.node, m.iof, m.mc, m.md
         self.outside, self.gro, self.err0 = st.outside, st.gro, st.err.max(1)
+        self.dim_gro = self.gro
+        if self._measure_org is not None:
+            self.org = np.broadcast_to(self._measure_org, self.org.shape).copy()
+            self.dim_gro = self.org * self.scale
         self.err = self.err0.copy()                                            # float32 error bound of rayPos so far
         self.amb |= st.amb
         self.eye_node, self.iof, self.in_medium, self.mc, self.md = st.node, st.iof, st.md > 0, st.mc, st.md
@@ -554,6 +591,9 @@ class Trace:
                 break
             new, ax, stuck, fr, t = _step(w, pos[act], self.d[act], inv[act], cur[act], 1e-4)
             self.err[act] += _step_error(new, t)
+            if self._dir_err is not None:
+                with np.errstate(invalid="ignore", over="ignore"):
+                    self.err[act] += self._dir_err[act] * np.abs(t)
             with np.errstate(invalid="ignore"):
                 mp = np.floor(np.clip(new, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
             r = np.arange(act.size)
@@ -634,7 +674,7 @@ class Trace:
         # grid-space origin, as the GLSL has it
         tci = np.tile(tc, (i.size, 1))
         hpw = self.pt[i] / self.scale
-        ln = np.linalg.norm(hpw - self.gro[i], axis=1) * self.tlen[i]
+        ln = np.linalg.norm(hpw - self.dim_gro[i], axis=1) * self.tlen[i]
         dim = ln / self.scale
         edim = (self.err[i] + self.err0[i] + 4 * U * (np.abs(hpw).max(1) + np.abs(self.gro[i]).max(1) + ln)) / self.scale
         md = self.md[i]

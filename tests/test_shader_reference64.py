@@ -85,9 +85,11 @@ def check(frame, rgba, idd, min_decided_hits, what, cap=UNDECIDED_CAP):
 
 
 def test_reference_never_touches_the_oracle_or_the_product():
-    """shader_ref64.py and path_ref64.py read texels, a camera block and uniforms: they import numpy (and path_ref64 the
-    other reference) and nothing else, and name no file, library or entry point of oracle/ or of the product's tracing."""
-    for module, allowed in (("shader_ref64.py", {"numpy"}), ("path_ref64.py", {"numpy", "shader_ref64"})):
+    """shader_ref64.py, path_ref64.py and lens_ref64.py read texels, a camera block and uniforms: they import numpy (and
+    path_ref64 and lens_ref64 the first reference) and nothing else, and name no file, library or entry point of oracle/,
+    of the checkers or of the product's tracing."""
+    for module, allowed in (("shader_ref64.py", {"numpy"}), ("path_ref64.py", {"numpy", "shader_ref64"}),
+                            ("lens_ref64.py", {"numpy", "shader_ref64"})):
         _independent(module, allowed)
 
 
@@ -98,7 +100,7 @@ def _independent(module, allowed):
     assert imported == allowed, imported
     names = {n.id for n in ast.walk(tree) if isinstance(n, ast.Name)} | {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute)}
     for banned in ("open", "exec", "eval", "__import__", "ctypes", "CDLL", "subprocess", "importlib", "load", "fromfile",
-                   "vrt", "dispatch", "render", "oracle_py", "oracle_samples"):
+                   "vrt", "dispatch", "render", "oracle_py", "oracle_samples", "oracle_jitter", "oracle_lens"):
         assert banned not in names, banned
     docs = {id(n.body[0].value) for n in ast.walk(tree) if isinstance(n, (ast.Module, ast.ClassDef, ast.FunctionDef))
             and n.body and isinstance(n.body[0], ast.Expr) and isinstance(n.body[0].value, ast.Constant)}
