@@ -1,7 +1,8 @@
 // vrt_accum.cpp -- progressive multi-sample accumulation (include/vrt.h vrt_accum_*): call-order checks, the restart rule, the
 // context's buffers, the resolve and the display pass on it. The samples themselves are enqueued by the dispatcher
-// (vrt_dispatch.cpp enqueue() with an AccumStep), which picks the kernel of vrt_accum.hip.h -- by the sample's ray source
-// (corner, jitter or thin lens) and the shape the mode and scene allow -- as it chooses between the forms of a frame. A jittered
+// (vrt_dispatch.cpp enqueue() with an AccumStep), which settles the variant and the shape the mode and scene allow as it does
+// for a frame; launch_accum_step() below then picks the kernel of vrt_accum.hip.h by the sample's ray source (corner, jitter
+// or thin lens) and fills its arguments from the context's buffers. A jittered
 // accumulation, or one of VRT_MODE_PRIMARY / _SHADOW, first renders the mode's ordinary frame once: its id_dist is the resolve's,
 // and without jitter its bytes are every sample's. So does one with a thin lens (vrt_set_lens, aperture > 0).
 // An adaptive accumulation (vrt_accum_begin_adaptive) adds rounds instead of samples: the same paths with the kernels' adaptive
@@ -146,6 +147,64 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
 }
 
 }  // namespace
+
+// the step's samples go into the context's sums; an adaptive accumulation (acc.adaptive) passes its rule and state too, to the
+// kernels' adaptive forms, an HDR one (acc.hdr) its float64 sums, to the HDR object's
+hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSet &vs, const Variant &v, int mode, int grid, bool two_pass,
+                                           const vrt::LensSel &lsel, const AccumStep &acc, hipStream_t s) {
+    namespace launch = vrt::launch;
+    vrt::accum::HdrArgs q{};
+    q.hsum = ac.d_hsum;
+    q.hframe = ac.d_hframe;
+    const bool hdr = acc.hdr, adaptive = acc.adaptive;
+    const vrt::accum::HdrFrame hf{ac.d_pass1, ac.d_id, ac.d_hframe};
+    q.sums = ac.d_sums;
+    q.pass1_rgba = ac.d_pass1;
+    q.out_id = ac.d_id;
+    q.first = acc.first;
+    q.n = acc.n;
+    if (adaptive) {
+        q.sq = ac.d_sq; q.tiles = ac.d_tiles; q.n_tiles = ac.d_tiles + ac.tile_cap;
+        q.min = ac.min_samples; q.max = ac.max_samples; q.tol = ac.tolerance;
+    }
+    using vrt::accum::Source;
+    const Source src = acc.aperture > 0.0f ? Source::kLens : (acc.jitter ? Source::kJitter : Source::kCorner);
+    const vrt::accum::Lens l{acc.aperture, acc.focus, acc.jitter ? 1u : 0u, lsel.eye_shared ? 0u : 1u};
+    if (src != Source::kCorner) {   // every sample has a ray of its own: no per-projection tables
+        vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
+        vs.v[0].gen_z = 0.0f;
+        vs.v[0].gen_fast = 0u;
+    }
+    if (acc.frame_only)   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
+        return (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? launch::accum_frame_hdr(mode, v, a, vs, hf, grid, s) : hipErrorInvalidValue;
+    if (mode != VRT_MODE_FULL)   // one launch, the samples looped in the lanes
+        return launch::accum_primary(hdr, mode, src, v, a, vs, q, adaptive, l, grid, s);
+    if (two_pass && src != Source::kCorner)   // MODE 6's chain per sample, looped in the lanes
+        return launch::accum_opaque(hdr, src, a, vs, q, adaptive, l, grid, s);
+    hipError_t e = hipSuccess;
+    if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
+        a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
+        if (!ac.pass1) {
+            vs.v[0].out_rgba = ac.d_pass1;
+            vs.v[0].out_id = ac.d_id;
+            // (HDR: the same pass with its float colour, for the pixels without a bounce)
+            e = hdr ? launch::accum_pass1_hdr(a, vs, hf, grid, s) : launch::trace_full_pass1(a, vs, grid, s);
+            if (e != hipSuccess) return e;
+            ac.pass1 = true;
+        }
+        return launch::accum_bounce(hdr, a, vs, q, adaptive, grid, s);
+    }
+    // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
+    const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, a.width, a.height, ac.min_samples, ac.max_samples,
+                               ac.tolerance};
+    for (uint32_t k = 0; k < acc.n && e == hipSuccess; ++k) {
+        q.first = acc.first + k;
+        q.n = 1u;
+        if (adaptive) e = launch::adaptive_tiles(tl, s);
+        if (e == hipSuccess) e = launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
+    }
+    return e;
+}
 
 extern "C" {
 

@@ -1,5 +1,5 @@
-// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h), shared by the host side (vrt_accum.cpp,
-// vrt_dispatch.cpp) and the launch file (vrt_launch_accum.hip).
+// vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h), shared by the host side (vrt_accum.cpp)
+// and the launch files (vrt_launch_accum.hip, vrt_launch_accum_hdr.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,6 +1,7 @@
-// vrt_dispatch.cpp -- the dispatch boundary (src/main.cpp:941-946): builds the kernel arguments of one launch, chooses the kernel
-// variant the scene and the view allow, runs the feedback tile scheduler and the per-projection ray tables, and carries the
-// vrt_dispatch* entry points of include/vrt.h. Host code; the kernels are behind vrt_launch.h.
+// vrt_dispatch.cpp -- the dispatch boundary (src/main.cpp:941-946): enqueue() makes one frame launch as a sequence of steps -- the
+// views, the kernel variant the scene and the views allow, the frame block of the kernel arguments (the scene and light blocks are
+// vrt_scene.cpp's), the feedback tile scheduler, the form of the full path tracer -- over the caches above it (scheduling states, ray
+// tables, miss masks), and carries the vrt_dispatch* entry points of include/vrt.h. Host code; the kernels are behind vrt_launch.h.
 #include "vrt_internal.h"
 
 #include <algorithm>
@@ -263,39 +264,15 @@ const uint8_t *miss_mask(vrt_ctx *c, const vrt::View &w, const vrt_ctx::RayTable
     return reinterpret_cast<const uint8_t *>(m->d_mask);
 }
 
-// views == nullptr: one view, the context's camera (vrt_set_camera) rendering into d_rgba / d_id.
-int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact,
-            int mode, void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views, int n_views, const AccumStep *acc) {
-    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: no octree uploaded (call vrt_upload_octree first)");
-    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: a patch batch is open (call vrt_patch_end first)");
-    if (!views && !c->have_camera) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: no camera set (call vrt_set_camera first)");
-    if (n_views < 1 || n_views > vrt::kMaxViews) return vrt_fail(c, VRT_E_INVALID, "vrt_dispatch_views: 1 to 4 views per launch");
-    if (mode != VRT_MODE_PRIMARY && mode != VRT_MODE_PRIMARY_SHADOW && mode != VRT_MODE_FULL)
-        return vrt_fail(c, VRT_E_INVALID, "unknown mode");
-    if (n_rows <= 0) return VRT_OK;
-    {
-        const int ra = ensure_analysis(c);
-        if (ra) return ra;
-    }
-    Variant v = *find_variant(c->variant);
-    if (v.trav >= 3 && !c->wide_ok) { v.trav = 2; v.wpe = 1; }      // wide layout not expressible for this scene: record-array kernels
-    if (v.trav == 2 && c->unit_internal) v.trav = 1;                 // precondition of vrt_kernels.hip.h not met: explicit-AABB kernels
-    if (mode == VRT_MODE_FULL) {
-        // the full path tracer takes the wide traversals at five waves per SIMD (96 VGPRs and no extra spills measured 8-10 %
-        // faster than the unconstrained 105-VGPR build); the default takes v4 here too (one march loop, for rays that start in
-        // any medium: 96 registers without spills; 9 % faster than v3, profiles/r02_f_full_shader_v4_ab.jsonl), variant 20 v3
-        if (v.trav >= 3) v.wpe = 5;
-    } else if (!acc && mode == VRT_MODE_PRIMARY_SHADOW && c->variant == 20 && v.trav == 3) {
-        // round 1's default: the shadow march was 1.5 % faster seven waves deep, the primary one six deep (the accumulation's
-        // primary kernels, vrt_launch_accum.hip, exist in the table's shapes only)
-        v.wpe = 7;
-    }
-    vrt::KArgs a;
-    vrt::ViewSet vs;
+namespace {
+
+// ---- enqueue(), step by step: each function below is one decision of a frame launch, called in this order -------------------------
+
+// Views: per view the camera block and the images, the eye's cell (-> eyes[i]), what the host looks up there for the kernels (the
+// leaf that holds the eye, the wide kernels' first lookup) and the ray table of its projection (-> tables[i], nullptr: none).
+void fill_views(vrt_ctx *c, const vrt_view *views, int n_views, void *d_rgba, void *d_id, int width, int height, vrt::ViewSet &vs,
+                int eyes[][3], const vrt_ctx::RayTable *tables[]) {
     std::memset(&vs, 0, sizeof vs);
-    a.n_views = n_views;
-    int eyes[vrt::kMaxViews][3];
-    const vrt_ctx::RayTable *tables[vrt::kMaxViews] = {};
     for (int i = 0; i < n_views; ++i) {
         vrt::View &w = vs.v[i];
         std::memcpy(w.inv_proj, views ? views[i].inv_projection : c->inv_proj, sizeof w.inv_proj);
@@ -304,13 +281,12 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         w.out_rgba = (uint32_t *)(views ? views[i].d_rgba8 : d_rgba);
         w.out_id = (int2 *)(views ? views[i].d_id_dist : d_id);
         // the shader's lookup at the eye (comp:445-449), same arithmetic: floor(cameraPos * u_voxelScale)
-        int eye[3];
+        int *eye = eyes[i];
         for (int k = 0; k < 3; ++k) {
             const float g = floorf(w.cam_pos[k] * c->params.voxel_scale);
             // float -> int as the device converts: NaN -> 0, out of range saturates (and is outside any world)
             eye[k] = g != g ? 0 : (g >= 2147483648.0f ? 2147483647 : (g < -2147483648.0f ? (-2147483647 - 1) : (int)g));
         }
-        for (int k = 0; k < 3; ++k) eyes[i][k] = eye[k];
         vrt::eye_lookup(c->host_records, c->params.world_min, c->params.world_max, eye, w.eye0, w.eye1);
         vrt::FirstFind ff;
         w.first_valid = (c->wide_ok && vrt::first_find(c->wide, c->params.world_min, c->params.world_max, eye, vrt::v3::kAnchorShift, ff)) ? 1 : 0;
@@ -329,15 +305,31 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
             }
         }
     }
-    // A thin lens (vrt_set_lens; accumulations only): every sample has an origin of its own, anywhere in a box of cells around
-    // the eye. What the loop above made at the eye is kept only where it holds at every origin of that box (vrt_layout.h
-    // lens_select()): otherwise the lens kernels look the medium up per lane and the wide kernels make their own first lookup.
-    const bool lens = acc && acc->aperture > 0.0f;
-    vrt::LensSel lsel;
-    if (lens) {
-        vrt::lens_select(c->host_records, c->wide_ok ? &c->wide : nullptr, c->params.world_min, c->params.world_max,
-                         c->params.voxel_scale, vs.v[0].cam_pos, vs.v[0].inv_view, acc->aperture, lsel);
-        if (!lsel.first_shared) vs.v[0].first_valid = 0;
+}
+
+// A thin lens (vrt_set_lens; accumulations only): every sample has an origin of its own, anywhere in a box of cells around the
+// eye. What fill_views() made at the eye is kept only where it holds at every origin of that box (vrt_layout.h lens_select()):
+// otherwise the lens kernels look the medium up per lane and the wide kernels make their own first lookup. False: no lens.
+bool select_lens(const vrt_ctx *c, const AccumStep *acc, vrt::ViewSet &vs, vrt::LensSel &lsel) {
+    if (!acc || !(acc->aperture > 0.0f)) return false;
+    vrt::lens_select(c->host_records, c->wide_ok ? &c->wide : nullptr, c->params.world_min, c->params.world_max, c->params.voxel_scale,
+                     vs.v[0].cam_pos, vs.v[0].inv_view, acc->aperture, lsel);
+    if (!lsel.first_shared) vs.v[0].first_valid = 0;
+    return true;
+}
+
+// The variant of this launch: the scene's (base_variant()) in the shape the mode asks for, v3 for eyes the v4 kernels do not take
+Variant launch_variant(const vrt_ctx *c, int mode, bool accumulating, const vrt::ViewSet &vs, int n_views, bool lens, const vrt::LensSel &lsel) {
+    Variant v = base_variant(c);
+    if (mode == VRT_MODE_FULL) {
+        // the full path tracer takes the wide traversals at five waves per SIMD (96 VGPRs and no extra spills measured 8-10 %
+        // faster than the unconstrained 105-VGPR build); the default takes v4 here too (one march loop, for rays that start in
+        // any medium: 96 registers without spills; 9 % faster than v3, profiles/r02_f_full_shader_v4_ab.jsonl), variant 20 v3
+        if (v.trav >= 3) v.wpe = 5;
+    } else if (!accumulating && mode == VRT_MODE_PRIMARY_SHADOW && c->variant == 20 && v.trav == 3) {
+        // round 1's default: the shadow march was 1.5 % faster seven waves deep, the primary one six deep (the accumulation's
+        // primary kernels, vrt_launch_accum.hip, exist in the table's shapes only)
+        v.wpe = 7;
     }
     if (v.trav == 4 && mode != VRT_MODE_FULL) {
         // the v4 primary kernels hold the march loop for rays that start in refraction byte 85 (1.0) only: an eye inside a
@@ -350,47 +342,20 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         if (lens) eye_in_medium = !lsel.no_medium;   // ... any origin of the lens inside one
         if (eye_in_medium) { v.trav = 3; v.wpe = 6; }
     }
-    // miss tiles: the EYE85 primary kernels (v4, seven waves per SIMD) read a mask for every view with ray tables
-    if (c->miss_tiles_on && !acc && v.trav == 4 && v.wpe == 7 && mode != VRT_MODE_FULL)
-        for (int i = 0; i < n_views; ++i)
-            if (tables[i]) vs.v[i].miss = miss_mask(c, vs.v[i], *tables[i], c->params.voxel_scale, s, vs.v[i].miss_stamp);
-    a.voxel_scale = c->params.voxel_scale;
-    for (int i = 0; i < 3; ++i) {
-        a.wmin[i] = c->params.world_min[i];
-        a.wmax[i] = c->params.world_max[i];
-        a.light_dir[i] = c->params.light_dir[i];
-        a.highlighted[i] = c->params.highlighted[i];
-        // comp:335-345 on the launch's one light direction
-        const float d = a.light_dir[i];
-        a.light_inv[i] = (fabsf(d) < 1e-8f) ? 1e20f : 1.0f / d;
-        a.light_push[i] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * 0.001f;
-        a.light_dpos[i] = d > 0.0f ? 1 : 0;
-        a.light_dposf[i] = d > 0.0f ? 1.0f : 0.0f;
-    }
-    for (int i = 0; i < 4; ++i) a.global_light[i] = c->params.global_light[i];
-    // |globalLight|, |lightDir| <= 2^30: direct (light * n.l) * colour * throughput (starts as the light) stays below 2^90 < 2^97,
-    // where x / PI needs no range scaling
-    a.shade_fast = 1;
-    for (int i = 0; i < 3; ++i)
-        if (!(fabsf(a.global_light[i]) <= 1073741824.0f) || !(fabsf(a.light_dir[i]) <= 1073741824.0f)) a.shade_fast = 0;
-    a.tex_dim = (int)c->info.tex_dim;
-    a.width = width;
-    a.height = height;
-    a.row0 = row0;
-    a.n_rows = n_rows;
-    a.tile_rows = tile_rows;
-    a.row_stride = row_stride;
-    a.compact = compact;
-    a.nodes = c->d_nodes;
-    a.n_records = c->info.n_records;
-    a.lds_records = 0u;
-    a.cells = c->d_cells;
-    a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
-    a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
-    for (int k = 0; k < 3; ++k) a.root0_min[k] = a.n_roots ? c->wide.roots[0].origin[k] : 0;
-    a.root_table = c->d_roots;
-    a.root0_node = a.n_roots ? c->wide.roots[0].node : 0u;
-    a.root0_shift = a.n_roots ? c->wide.roots[0].shift : 0;
+    return v;
+}
+
+// The frame block of KArgs: the rows of this launch, the prologue's index arithmetic for its `tiles` tiles, and what a frame from
+// these eyes may assume of the world outside wide root 0 (after fill_scene_args(): it may replace root 0 by a deeper node).
+void fill_frame_args(const vrt_ctx *c, vrt::KArgs &a, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact,
+                     long tiles, const int eyes[][3], int n_views, bool lens, const vrt::LensSel &lsel) {
+    a.n_views = n_views; a.width = width; a.height = height;
+    a.row0 = row0; a.n_rows = n_rows; a.tile_rows = tile_rows; a.row_stride = row_stride; a.compact = compact;
+    // index arithmetic of the prologue without integer divisions where the shapes allow it
+    const unsigned long tiles_x = (unsigned long)((width + 7) / 8);
+    // q = (n * M) >> 32 with M = floor(2^32 / d) + 1 equals n / d while n * d < 2^32 (the error term n * (M * d - 2^32) stays below 2^32)
+    a.tiles_x_magic = (tiles_x > 1 && (unsigned long)(tiles + 4) * tiles_x < (1ul << 32)) ? (uint32_t)((1ul << 32) / tiles_x + 1) : 0u;
+    a.row_mode = tile_rows >= n_rows ? 1 : (tile_rows == 8 ? 2 : 0);
     // nothing outside wide root 0? (the shipped maps: the octree root's only child is the octant [0, 1024)^3) -- then rays
     // that leave it are done (find() in vrt_kernels_v4.hip.h), and the same argument one level down, as often as it holds,
     // lets a deeper node stand in for it: a shorter descent whenever a lookup restarts there, leaving rays done sooner.
@@ -403,33 +368,25 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         const int corners[2][3] = {{lsel.lo[0], lsel.lo[1], lsel.lo[2]}, {lsel.hi[0], lsel.hi[1], lsel.hi[2]}};
         vrt::tighten_root0(c->wide, corners, 2, vrt::v3::kAnchorShift, a.root0_node, a.root0_shift, a.root0_min);
     }
-    a.group_order = nullptr;
-    a.tile_cost = nullptr;
-    a.split_count = nullptr;
-    a.defer_rec = nullptr;
-    a.defer_count = nullptr;
-    a.defer_cap = 0;
+    a.group_order = nullptr; a.tile_cost = nullptr; a.split_count = nullptr;   // schedule() and the launch's form set these
+    a.defer_rec = nullptr; a.defer_count = nullptr; a.defer_cap = 0;
+}
 
-    const long tiles = (long)((width + 7) / 8) * (long)((n_rows + 7) / 8);   // 8 x 8 pixel tiles, one per wave
-    {   // index arithmetic of the prologue without integer divisions where the shapes allow it
-        const unsigned long tiles_x = (unsigned long)((width + 7) / 8);
-        // q = (n * M) >> 32 with M = floor(2^32 / d) + 1 equals n / d while n * d < 2^32 (the error term n * (M * d - 2^32) stays below 2^32)
-        a.tiles_x_magic = (tiles_x > 1 && (unsigned long)(tiles + 4) * tiles_x < (1ul << 32)) ? (uint32_t)((1ul << 32) / tiles_x + 1) : 0u;
-        a.row_mode = tile_rows >= n_rows ? 1 : (tile_rows == 8 ? 2 : 0);
-    }
+// Feedback scheduling: wide-traversal kernels, one view, launches large enough to have a tail worth shaping. Sets a.group_order /
+// a.tile_cost (the caller's buffers under vrt_set_tile_order) and returns the grid: the tiles' workgroups, or whole groups under an order.
+// st: the state of this launch shape, when the scheduler runs it; measure: this launch records its tile times.
+long schedule(vrt_ctx *c, hipStream_t s, const Variant &v, bool accumulating, int mode, long tiles, const vrt::ViewSet &vs, vrt::KArgs &a,
+              SchedState *&st, bool &measure) {
     const int waves = v.block() / 64;
     long grid = (tiles + waves - 1) / waves;
     if (grid < 1) grid = 1;
-    // feedback scheduling: wide-traversal kernels, one view, launches large enough to have a tail worth shaping
-    SchedState *st = nullptr;
-    bool measure = false;
-    const bool sched_kernel = !acc && v.trav >= 3 && n_views == 1;
+    const bool sched_kernel = !accumulating && v.trav >= 3 && a.n_views == 1;
     const long groups = (tiles + vrt::kGroupTiles - 1) / vrt::kGroupTiles;
     if (sched_kernel && c->dbg_sched) {
         a.group_order = c->dbg_group_order;
         a.tile_cost = c->dbg_tile_cost;
     } else if (sched_kernel && c->sched_period > 0 && groups >= kSchedMinGroups && groups <= kSchedMaxGroups) {
-        st = sched_state(c, s, width, n_rows, row0, row_stride, tile_rows, mode, (uint32_t)tiles, (uint32_t)groups);
+        st = sched_state(c, s, a.width, a.n_rows, a.row0, a.row_stride, a.tile_rows, mode, (uint32_t)tiles, (uint32_t)groups);
         if (st) {
             // eye = invView's translation column, viewing direction = minus its third column (column-major)
             const float *iv = vs.v[0].inv_view;
@@ -443,119 +400,101 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
         }
     }
     if (a.group_order) grid = groups * (vrt::kGroupTiles / waves);  // whole groups: the last one may hold tiles past the end
-    const bool prof = !acc && c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
-    const hipEvent_t ev0 = prof ? c->prof_events[2 * c->prof_count] : nullptr;
-    const hipEvent_t ev1 = prof ? c->prof_events[2 * c->prof_count + 1] : nullptr;
-    hipError_t e;
-    // the full path tracer as two tile-coherent passes, where the scene and the view allow it
-    bool two_pass = false;
-    if (mode == VRT_MODE_FULL && c->two_pass_on && v.trav == 4 && n_views == 1 && c->variant == 0 && vs.v[0].out_rgba) {
-        if (!c->scene_opaque_valid) { c->scene_opaque = vrt::tree_is_opaque(c->host_records); c->scene_opaque_valid = true; }
-        const uint32_t eye_alpha = vs.v[0].eye0 >> 24, eye_b = vs.v[0].eye1 & 0xffu;
-        two_pass = c->scene_opaque && eye_alpha == 0u && (eye_b == 0u || eye_b == 85u || eye_b == 255u);
-        if (lens) two_pass = c->scene_opaque && lsel.empty;   // every origin of the lens in empty space
+    return grid;
+}
+
+// The full path tracer as two tile-coherent passes, where the scene and the view allow it
+bool opaque_two_pass(vrt_ctx *c, int mode, const Variant &v, const vrt::ViewSet &vs, int n_views, bool lens, const vrt::LensSel &lsel) {
+    if (!(mode == VRT_MODE_FULL && c->two_pass_on && v.trav == 4 && n_views == 1 && c->variant == 0 && vs.v[0].out_rgba)) return false;
+    if (!c->scene_opaque_valid) { c->scene_opaque = vrt::tree_is_opaque(c->host_records); c->scene_opaque_valid = true; }
+    if (lens) return c->scene_opaque && lsel.empty;   // every origin of the lens in empty space
+    const uint32_t eye_alpha = vs.v[0].eye0 >> 24, eye_b = vs.v[0].eye1 & 0xffu;
+    return c->scene_opaque && eye_alpha == 0u && (eye_b == 0u || eye_b == 85u || eye_b == 255u);
+}
+
+// The seed buffer of stream s (one per stream: launches on different streams may overlap; eight are kept, the least recently
+// used one changes streams once its own has drained), grown to `need` tiles -> a.defer_rec
+int stream_seeds(vrt_ctx *c, hipStream_t s, size_t need, vrt::KArgs &a) {
+    vrt_ctx::SeedBuffer *sb = nullptr;
+    for (auto &b : c->seeds)
+        if (b.stream == s) sb = &b;
+    if (!sb) {
+        if (c->seeds.size() < 8) {
+            c->seeds.emplace_back();
+            sb = &c->seeds.back();
+        } else {
+            for (auto &b : c->seeds)
+                if (!sb || b.last_use < sb->last_use) sb = &b;
+            VRT_HIP(c, hipStreamSynchronize(sb->stream));   // its launches may still be in flight there
+        }
+        sb->stream = s;
     }
-    // the general full path tracer starts the heaviest groups of an ordered, non-measuring launch as part-tile waves (KArgs::split_count)
+    if (need > sb->tiles) {
+        VRT_HIP(c, hipStreamSynchronize(s));
+        uint32_t *fresh = nullptr;
+        VRT_HIP(c, hipMalloc((void **)&fresh, need * vrt::kSeedPlanesHost * 64 * sizeof(uint32_t)));
+        if (sb->d) (void)hipFree(sb->d);
+        sb->d = fresh;
+        sb->tiles = need;
+    }
+    sb->last_use = ++c->seed_tick;
+    a.defer_rec = reinterpret_cast<float *>(sb->d);
+    return VRT_OK;
+}
+
+}  // namespace
+
+// views == nullptr: one view, the context's camera (vrt_set_camera) rendering into d_rgba / d_id.
+int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact,
+            int mode, void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views, int n_views, const AccumStep *acc) {
+    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: no octree uploaded (call vrt_upload_octree first)");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: a patch batch is open (call vrt_patch_end first)");
+    if (!views && !c->have_camera) return vrt_fail(c, VRT_E_STATE, "vrt_dispatch: no camera set (call vrt_set_camera first)");
+    if (n_views < 1 || n_views > vrt::kMaxViews) return vrt_fail(c, VRT_E_INVALID, "vrt_dispatch_views: 1 to 4 views per launch");
+    if (mode != VRT_MODE_PRIMARY && mode != VRT_MODE_PRIMARY_SHADOW && mode != VRT_MODE_FULL)
+        return vrt_fail(c, VRT_E_INVALID, "unknown mode");
+    if (n_rows <= 0) return VRT_OK;
+    const int ra = ensure_analysis(c);
+    if (ra) return ra;
+    vrt::KArgs a;
+    vrt::ViewSet vs;
+    int eyes[vrt::kMaxViews][3];
+    const vrt_ctx::RayTable *tables[vrt::kMaxViews] = {};
+    fill_views(c, views, n_views, d_rgba, d_id, width, height, vs, eyes, tables);
+    vrt::LensSel lsel;
+    const bool lens = select_lens(c, acc, vs, lsel);
+    const Variant v = launch_variant(c, mode, acc != nullptr, vs, n_views, lens, lsel);
+    // miss tiles: the EYE85 primary kernels (v4, seven waves per SIMD) read a mask for every view with ray tables
+    if (c->miss_tiles_on && !acc && v.trav == 4 && v.wpe == 7 && mode != VRT_MODE_FULL)
+        for (int i = 0; i < n_views; ++i)
+            if (tables[i]) vs.v[i].miss = miss_mask(c, vs.v[i], *tables[i], c->params.voxel_scale, s, vs.v[i].miss_stamp);
+    const long tiles = (long)((width + 7) / 8) * (long)((n_rows + 7) / 8);   // 8 x 8 pixel tiles, one per wave
+    fill_scene_args(c, a);
+    fill_light_args(c, a);
+    fill_frame_args(c, a, width, height, row0, n_rows, tile_rows, row_stride, compact, tiles, eyes, n_views, lens, lsel);
+    SchedState *st = nullptr;
+    bool measure = false;
+    long grid = schedule(c, s, v, acc != nullptr, mode, tiles, vs, a, st, measure);
+    const ProfSlot prof = acc ? ProfSlot{} : ProfSlot::take(c);
+    const bool two_pass = opaque_two_pass(c, mode, v, vs, n_views, lens, lsel);
+    // the general full path tracer starts the heaviest groups of an ordered launch, measuring or not, as part-tile waves (KArgs::split_count)
     if (mode == VRT_MODE_FULL && !two_pass && st && a.group_order && c->heavy_split_on) {
         a.split_count = st->d_order + st->n_groups;
         grid += (long)vrt::kSplitMaxGroups * vrt::kGroupTiles * (vrt::kSplitParts - 1);
         // a measuring launch: the part-tile waves of a tile meet in its ticks with atomicMax
         if (a.tile_cost) VRT_HIP(c, hipMemsetAsync(st->d_cost, 0, (size_t)st->n_groups * vrt::kGroupTiles * sizeof(uint32_t), s));
     }
+    hipError_t e;
     if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
-        vrt_ctx::Accum &ac = c->accum;
-        // an adaptive accumulation (acc->adaptive) passes its rule and state too, to the kernels' adaptive forms
-        vrt::accum::HdrArgs q{};   // (the plain launch functions take its AdaptArgs)
-        q.hsum = ac.d_hsum;
-        q.hframe = ac.d_hframe;
-        const bool hdr = acc->hdr;
-        const vrt::accum::HdrFrame hf{ac.d_pass1, ac.d_id, ac.d_hframe};
-        q.sums = ac.d_sums;
-        q.pass1_rgba = ac.d_pass1;
-        q.out_id = ac.d_id;
-        q.first = acc->first;
-        q.n = acc->n;
-        if (acc->adaptive) {
-            q.sq = ac.d_sq;
-            q.tiles = ac.d_tiles;
-            q.n_tiles = ac.d_tiles + ac.tile_cap;
-            q.min = ac.min_samples;
-            q.max = ac.max_samples;
-            q.tol = ac.tolerance;
-        }
-        using vrt::accum::Source;
-        const Source src = lens ? Source::kLens : (acc->jitter ? Source::kJitter : Source::kCorner);
-        const vrt::accum::Lens l{acc->aperture, acc->focus, acc->jitter ? 1u : 0u, lsel.eye_shared ? 0u : 1u};
-        if (src != Source::kCorner) {   // every sample has a ray of its own: no per-projection tables
-            vs.v[0].gen_x = vs.v[0].gen_y = nullptr;
-            vs.v[0].gen_z = 0.0f;
-            vs.v[0].gen_fast = 0u;
-        }
-        e = hipSuccess;
-        if (acc->frame_only) {   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
-            e = (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? vrt::launch::accum_frame_hdr(mode, v, a, vs, hf, (int)grid, s)
-                                                                         : hipErrorInvalidValue;
-        } else if (mode != VRT_MODE_FULL) {   // one launch, the samples looped in the lanes
-            e = hdr ? vrt::launch::accum_primary_hdr(mode, src, v, a, vs, q, acc->adaptive, l, (int)grid, s)
-                    : vrt::launch::accum_primary(mode, src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
-        } else if (two_pass && src != Source::kCorner) {   // MODE 6's chain per sample, looped in the lanes
-            e = hdr ? vrt::launch::accum_opaque_hdr(src, a, vs, q, acc->adaptive, l, (int)grid, s)
-                    : vrt::launch::accum_opaque(src, a, vs, q, acc->adaptive, l, (int)grid, s);
-        } else if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
-            a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
-            if (!ac.pass1) {
-                vs.v[0].out_rgba = ac.d_pass1;
-                vs.v[0].out_id = ac.d_id;
-                // (HDR: the same pass with its float colour, for the pixels without a bounce)
-                e = hdr ? vrt::launch::accum_pass1_hdr(a, vs, hf, (int)grid, s) : vrt::launch::trace_full_pass1(a, vs, (int)grid, s);
-                if (e == hipSuccess) ac.pass1 = true;
-            }
-            if (e == hipSuccess)
-                e = hdr ? vrt::launch::accum_bounce_hdr(a, vs, q, acc->adaptive, (int)grid, s)
-                        : vrt::launch::accum_bounce(a, vs, q, acc->adaptive, (int)grid, s);
-        } else {   // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
-            const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, width, height, ac.min_samples,
-                                       ac.max_samples, ac.tolerance};
-            for (uint32_t k = 0; k < acc->n && e == hipSuccess; ++k) {
-                q.first = acc->first + k;
-                q.n = 1u;
-                if (acc->adaptive) e = vrt::launch::adaptive_tiles(tl, s);
-                if (e == hipSuccess)
-                    e = hdr ? vrt::launch::accum_full_hdr(src, v, a, vs, q, acc->adaptive, l, (int)grid, s)
-                            : vrt::launch::accum_full(src, v, a, vs, q, acc->adaptive, l, (int)grid, s);
-            }
-        }
+        e = launch_accum_step(c->accum, a, vs, v, mode, (int)grid, two_pass, lsel, *acc, s);
     } else if (two_pass && c->two_pass_form >= 5) {
-        e = vrt::launch::trace_full_opaque(a, vs, (int)grid, c->two_pass_form, s, ev0, ev1);
+        e = vrt::launch::trace_full_opaque(a, vs, (int)grid, c->two_pass_form, s, prof.ev0, prof.ev1);
     } else if (two_pass) {
-        vrt_ctx::SeedBuffer *sb = nullptr;
-        for (auto &b : c->seeds)
-            if (b.stream == s) sb = &b;
-        if (!sb) {
-            if (c->seeds.size() < 8) {
-                c->seeds.emplace_back();
-                sb = &c->seeds.back();
-            } else {
-                for (auto &b : c->seeds)
-                    if (!sb || b.last_use < sb->last_use) sb = &b;
-                VRT_HIP(c, hipStreamSynchronize(sb->stream));   // its launches may still be in flight there
-            }
-            sb->stream = s;
-        }
-        const size_t need = (size_t)(a.group_order ? groups * vrt::kGroupTiles : tiles);
-        if (need > sb->tiles) {
-            VRT_HIP(c, hipStreamSynchronize(s));
-            uint32_t *fresh = nullptr;
-            VRT_HIP(c, hipMalloc((void **)&fresh, need * vrt::kSeedPlanesHost * 64 * sizeof(uint32_t)));
-            if (sb->d) (void)hipFree(sb->d);
-            sb->d = fresh;
-            sb->tiles = need;
-        }
-        sb->last_use = ++c->seed_tick;
-        a.defer_rec = reinterpret_cast<float *>(sb->d);
-        e = vrt::launch::trace_full_two_pass(a, vs, (int)grid, s, ev0, ev1);
+        const int rs = stream_seeds(c, s, (size_t)(a.group_order ? (tiles + vrt::kGroupTiles - 1) / vrt::kGroupTiles * vrt::kGroupTiles : tiles), a);   // whole groups
+        if (rs) return rs;
+        e = vrt::launch::trace_full_two_pass(a, vs, (int)grid, s, prof.ev0, prof.ev1);
     } else {
-        e = vrt::launch::trace(mode, v, a, vs, (int)grid, s, ev0, ev1);
+        e = vrt::launch::trace(mode, v, a, vs, (int)grid, s, prof.ev0, prof.ev1);
     }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     if (st) {
@@ -565,7 +504,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
             if (rr) return rr;
         }
     }
-    if (prof) ++c->prof_count;
+    prof.commit(c);
     return VRT_OK;
 }
 

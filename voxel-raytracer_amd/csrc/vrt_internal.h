@@ -1,13 +1,16 @@
 // vrt_internal.h -- what the translation units of libvrt_hip.so share: the context behind `vrt_ctx`, the kernel variant
 // table, error plumbing and the few helpers that cross files. Host code only; nothing here is exported.
 //
-//   vrt_scene.cpp      create / destroy, uniforms, camera, uploads, the layouts on the device (ensure_analysis)
-//   vrt_dispatch.cpp   enqueue(): kernel arguments, variant choice, feedback scheduling, ray tables; the vrt_dispatch* entry points
+//   vrt_scene.cpp      create / destroy, uniforms, camera, uploads, the layouts on the device (ensure_analysis); what every launch
+//                      takes from them: the scene and light blocks of KArgs, the base variant, the profiling slot
+//   vrt_dispatch.cpp   enqueue(), a frame launch in steps: views, variant, frame block of KArgs, feedback scheduling, the form of the
+//                      full path tracer; the caches behind them (ray tables, miss masks, seed buffers); the vrt_dispatch* entry points
 //   vrt_display.cpp    the display pass and the fused frame call
 //   vrt_patch.cpp      edits without re-upload: patch plan / apply / batches / compaction
 //   vrt_query.cpp      world queries on the device tree: ray casts (picking), voxel lookups
 //   vrt_rays.cpp       pathTrace for ray batches of the caller's (vrt_shade_rays): arguments without a camera, the staging buffers
-//   vrt_accum.cpp      progressive multi-sample accumulation (any mode, sub-pixel jitter): begin / add / resolve, the restart rule
+//   vrt_accum.cpp      progressive multi-sample accumulation (any mode, sub-pixel jitter): begin / add / resolve, the restart rule,
+//                      and the launches of one step of it (launch_accum_step, called by enqueue())
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts)
@@ -261,6 +264,27 @@ int upload_roots(vrt_ctx *c);
 uint32_t dim_of_texels(size_t texels);   // src/main.cpp:266-268
 int check_frame(vrt_ctx *c, int width, int height);
 int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-buffer entry points
+// What frames, ray batches and queries put into KArgs the same way (after ensure_analysis). The scene block: everything a kernel
+// reads of the tree and the world, wide root 0 as build_wide() found it -- and not root0_only, which each caller decides for
+// itself. The light block: the uniforms of the shading and the shadow ray's set-up.
+void fill_scene_args(const vrt_ctx *c, vrt::KArgs &a);
+void fill_light_args(const vrt_ctx *c, vrt::KArgs &a);
+// The context's variant (vrt_set_variant) as this scene allows it: the record-array kernels without a wide layout, the
+// explicit-AABB ones where a unit-size node is internal. Frames and ray batches start from it.
+Variant base_variant(const vrt_ctx *c);
+// The event pair of the next bracketed launch (vrt_set_profiling), or nothing: taken before a launch that could carry events
+// (every prof_stride-th of them while slots are left), committed once that launch has succeeded.
+struct ProfSlot {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool taken = false;
+    static ProfSlot take(vrt_ctx *c) {
+        ProfSlot p;
+        p.taken = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
+        if (p.taken) { p.ev0 = c->prof_events[2 * c->prof_count]; p.ev1 = c->prof_events[2 * c->prof_count + 1]; }
+        return p;
+    }
+    void commit(vrt_ctx *c) const { if (taken) ++c->prof_count; }
+};
 
 // vrt_dispatch.cpp
 // AccumStep: instead of rendering a frame, add samples first .. first + n - 1 of VRT_MODE_FULL to the context's accumulation
@@ -288,6 +312,12 @@ constexpr size_t kSchedMaxStates = 16;
 constexpr int kSchedDenoise = 100;              // SchedState::mode of the display pass
 constexpr long kSchedMinDenoiseGroups = 256;    // two workgroups fit a CU: 1,024 tiles are two rounds
 constexpr long kSchedMaxDenoiseGroups = 2048;   // beyond ~8,000 tiles (16 rounds) the tail is small and heaviest-first starts cost the halo reads their L2 locality: 4K nature 0.147 ms row-major, 0.157 ordered
+
+// vrt_accum.cpp
+// The launches of one AccumStep, for enqueue(): `a`, `vs`, `v`, `grid` and `two_pass` as it made them for a frame of `mode`, `lsel`
+// the lens selection (as constructed when there is no lens). Points a.defer_rec, and pass 1's outputs, at the accumulation's buffers.
+hipError_t launch_accum_step(vrt_ctx::Accum &ac, vrt::KArgs &a, vrt::ViewSet &vs, const Variant &v, int mode, int grid, bool two_pass,
+                             const vrt::LensSel &lsel, const AccumStep &acc, hipStream_t s);
 
 // vrt_raygen.cpp
 bool build_ray_table(const float *m, int W, int H, std::vector<float> &tab, float &z_out);

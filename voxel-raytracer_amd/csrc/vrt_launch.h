@@ -96,6 +96,22 @@ hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::RepeatAdapt> &q, hip
 hipError_t accum_frame_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
 hipError_t accum_pass1_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
 hipError_t accum_resolve_hdr(const accum::HdrResolve &q, hipStream_t s);
+// One call per shape of a sample launch: `q` filled for either object, `hdr` picks it (the plain functions take q's AdaptArgs part)
+inline hipError_t accum_primary(bool hdr, int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
+                                const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+    return hdr ? accum_primary_hdr(mode, src, v, a, vs, q, adaptive, l, grid, s) : accum_primary(mode, src, v, a, vs, q, adaptive, l, grid, s);
+}
+inline hipError_t accum_opaque(bool hdr, accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                               const accum::Lens &l, int grid, hipStream_t s) {
+    return hdr ? accum_opaque_hdr(src, a, vs, q, adaptive, l, grid, s) : accum_opaque(src, a, vs, q, adaptive, l, grid, s);
+}
+inline hipError_t accum_full(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                             bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+    return hdr ? accum_full_hdr(src, v, a, vs, q, adaptive, l, grid, s) : accum_full(src, v, a, vs, q, adaptive, l, grid, s);
+}
+inline hipError_t accum_bounce(bool hdr, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s) {
+    return hdr ? accum_bounce_hdr(a, vs, q, adaptive, grid, s) : accum_bounce(a, vs, q, adaptive, grid, s);
+}
 
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here

@@ -1,5 +1,5 @@
 // vrt_query.cpp -- the world queries of include/vrt.h (vrt_cast_rays, vrt_cast_rays_device, vrt_find_voxels): call-order
-// checks, the scene part of the kernel arguments, and the device buffers the host-buffer forms stage through.
+// checks, the scene block of the kernel arguments (fill_scene_args), and the device buffers the host-buffer forms stage through.
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
@@ -23,22 +23,8 @@ int scene_args(vrt_ctx *c, vrt::KArgs &a) {
     if (ra) return ra;
     std::memset(&a, 0, sizeof a);
     a.n_views = 1;
-    a.voxel_scale = c->params.voxel_scale;
-    for (int k = 0; k < 3; ++k) {
-        a.wmin[k] = c->params.world_min[k];
-        a.wmax[k] = c->params.world_max[k];
-    }
-    a.tex_dim = (int)c->info.tex_dim;
-    a.nodes = c->d_nodes;
-    a.n_records = c->info.n_records;
-    a.cells = c->d_cells;
-    a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
-    a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
-    for (int k = 0; k < 3; ++k) a.root0_min[k] = a.n_roots ? c->wide.roots[0].origin[k] : 0;
-    a.root_table = c->d_roots;
-    a.root0_node = a.n_roots ? c->wide.roots[0].node : 0u;
-    a.root0_shift = a.n_roots ? c->wide.roots[0].shift : 0;
-    a.root0_only = 0;
+    fill_scene_args(c, a);
+    a.root0_only = 0;   // never for a query (above)
     return VRT_OK;
 }
 

@@ -5,7 +5,6 @@
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
-#include <cmath>
 #include <cstring>
 
 using namespace vrt_internal;
@@ -51,53 +50,27 @@ int check_hdr(vrt_ctx *c, size_t n, const void *origins, int origin_stride, cons
     return VRT_OK;
 }
 
-// The launch: KArgs as enqueue() (vrt_dispatch.cpp) fills them for a frame, without anything derived from an eye
+// The launch: the scene and light blocks of KArgs as a frame carries them (vrt_scene.cpp), and nothing derived from an eye
 int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const float *d_dirs, int width, int mode, uint32_t first_sample,
           uint32_t n_samples, uint32_t *d_rgba, int2 *d_id, hipStream_t s, const Hdr *hdr = nullptr) {
     const int ra = ensure_analysis(c);
     if (ra) return ra;
-    Variant v = *find_variant(c->variant);
-    if (v.trav >= 3 && !c->wide_ok) v.trav = 2;          // wide layout not expressible for this scene: record-array kernels
-    if (v.trav == 2 && c->unit_internal) v.trav = 1;     // precondition of vrt_kernels.hip.h not met: explicit-AABB kernels
+    const Variant v = base_variant(c);   // the launch reads its traversal only
     vrt::KArgs a;
     vrt::ViewSet vs;
     std::memset(&a, 0, sizeof a);
     std::memset(&vs, 0, sizeof vs);   // no first lookup (first_valid 0), no ray tables (gen_fast 0), no miss mask
     a.n_views = 1;
-    a.voxel_scale = c->params.voxel_scale;
-    for (int i = 0; i < 3; ++i) {
-        a.wmin[i] = c->params.world_min[i];
-        a.wmax[i] = c->params.world_max[i];
-        a.light_dir[i] = c->params.light_dir[i];
-        a.highlighted[i] = c->params.highlighted[i];
-        const float d = a.light_dir[i];   // comp:335-345 on the launch's one light direction
-        a.light_inv[i] = (fabsf(d) < 1e-8f) ? 1e20f : 1.0f / d;
-        a.light_push[i] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * 0.001f;
-        a.light_dpos[i] = d > 0.0f ? 1 : 0;
-        a.light_dposf[i] = d > 0.0f ? 1.0f : 0.0f;
-    }
-    for (int i = 0; i < 4; ++i) a.global_light[i] = c->params.global_light[i];
-    a.shade_fast = 1;   // div_pi_inrange(): the lights' range, as enqueue() checks it
-    for (int i = 0; i < 3; ++i)
-        if (!(fabsf(a.global_light[i]) <= 1073741824.0f) || !(fabsf(a.light_dir[i]) <= 1073741824.0f)) a.shade_fast = 0;
+    fill_scene_args(c, a);
+    fill_light_args(c, a);
     // the HDR forms hand the float itself out: below 2^-103 div_pi_inrange() may differ from x / PI in the last bit -- a colour term
     // that stores byte 0 either way, but a different float
     if (hdr) a.shade_fast = 0;
-    a.tex_dim = (int)c->info.tex_dim;
     a.width = width;
     a.height = (int)((n + (size_t)width - 1) / (size_t)width);
     a.n_rows = a.height;
     a.tile_rows = a.height;
     a.row_mode = 1;
-    a.nodes = c->d_nodes;
-    a.n_records = c->info.n_records;
-    a.cells = c->d_cells;
-    a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
-    a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
-    for (int k = 0; k < 3; ++k) a.root0_min[k] = a.n_roots ? c->wide.roots[0].origin[k] : 0;
-    a.root_table = c->d_roots;
-    a.root0_node = a.n_roots ? c->wide.roots[0].node : 0u;
-    a.root0_shift = a.n_roots ? c->wide.roots[0].shift : 0;
     // the world is empty outside wide root 0: a property of the tree, applied by find() per ray (never to a first lookup); the
     // tighter root is a property of a view's eye and is not taken
     a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
@@ -113,9 +86,7 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     q.first = first_sample;
     q.n_samples = mode == VRT_MODE_FULL ? n_samples : 1u;   // the other modes draw no random number: every sample is the same
     const uint32_t grid = vrt::rays::plan(q.n, q.width, q.tiles_x);
-    const bool prof = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
-    const hipEvent_t ev0 = prof ? c->prof_events[2 * c->prof_count] : nullptr;
-    const hipEvent_t ev1 = prof ? c->prof_events[2 * c->prof_count + 1] : nullptr;
+    const ProfSlot prof = ProfSlot::take(c);
     hipError_t e;
     if (hdr) {
         vrt::rays::HdrArgs hq;
@@ -128,12 +99,12 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
         hq.n_total = hdr->n_prior + n_samples;
         hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
         hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, ev0, ev1);
+        e = vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
     } else {
-        e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, ev0, ev1);
+        e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
     }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    if (prof) ++c->prof_count;
+    prof.commit(c);
     return VRT_OK;
 }
 

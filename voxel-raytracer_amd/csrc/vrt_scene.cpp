@@ -93,6 +93,51 @@ int ensure_analysis(vrt_ctx *c) {
     return VRT_OK;
 }
 
+void fill_scene_args(const vrt_ctx *c, vrt::KArgs &a) {
+    a.voxel_scale = c->params.voxel_scale;
+    for (int k = 0; k < 3; ++k) {
+        a.wmin[k] = c->params.world_min[k];
+        a.wmax[k] = c->params.world_max[k];
+    }
+    a.tex_dim = (int)c->info.tex_dim;
+    a.nodes = c->d_nodes;
+    a.n_records = c->info.n_records;
+    a.lds_records = 0u;
+    a.cells = c->d_cells;
+    a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
+    a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
+    a.root_table = c->d_roots;
+    a.root0_node = a.n_roots ? c->wide.roots[0].node : 0u;
+    a.root0_shift = a.n_roots ? c->wide.roots[0].shift : 0;
+    for (int k = 0; k < 3; ++k) a.root0_min[k] = a.n_roots ? c->wide.roots[0].origin[k] : 0;
+}
+
+void fill_light_args(const vrt_ctx *c, vrt::KArgs &a) {
+    for (int i = 0; i < 3; ++i) {
+        a.light_dir[i] = c->params.light_dir[i];
+        a.highlighted[i] = c->params.highlighted[i];
+        // comp:335-345 on the launch's one light direction
+        const float d = a.light_dir[i];
+        a.light_inv[i] = (fabsf(d) < 1e-8f) ? 1e20f : 1.0f / d;
+        a.light_push[i] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * 0.001f;
+        a.light_dpos[i] = d > 0.0f ? 1 : 0;
+        a.light_dposf[i] = d > 0.0f ? 1.0f : 0.0f;
+    }
+    for (int i = 0; i < 4; ++i) a.global_light[i] = c->params.global_light[i];
+    // |globalLight|, |lightDir| <= 2^30: direct (light * n.l) * colour * throughput (starts as the light) stays below 2^90 < 2^97,
+    // where x / PI needs no range scaling (div_pi_inrange())
+    a.shade_fast = 1;
+    for (int i = 0; i < 3; ++i)
+        if (!(fabsf(a.global_light[i]) <= 1073741824.0f) || !(fabsf(a.light_dir[i]) <= 1073741824.0f)) a.shade_fast = 0;
+}
+
+Variant base_variant(const vrt_ctx *c) {
+    Variant v = *find_variant(c->variant);
+    if (v.trav >= 3 && !c->wide_ok) { v.trav = 2; v.wpe = 1; }      // wide layout not expressible for this scene: record-array kernels
+    if (v.trav == 2 && c->unit_internal) v.trav = 1;                 // precondition of vrt_kernels.hip.h not met: explicit-AABB kernels
+    return v;
+}
+
 // device images behind the host-buffer entry points: rgba8, (id, dist) and the displayed rgba8
 int ensure_scratch(vrt_ctx *c, size_t px) {
     if (px <= c->scratch_pixels) return VRT_OK;
