@@ -22,7 +22,13 @@ namespace vrt {
 namespace miss {
 
 constexpr int kTile = 8;               // the trace kernel's tile: 8 x 8 pixels, tiles indexed by FRAME row and column
-constexpr double kDilate = 1.0;        // voxels added to every side of a box (>= delta of the proof)
+// delta of the proof, per axis, in voxels: the march's 1,024 steps each add two roundings of a coordinate of at most 2^11 (the sum
+// rp + dir * t and the push; half an ulp, 2^-14, each) and the push itself, 1e-4, and the roundings of the products dir * t add up to
+// 2^-24 of the distance travelled, below 0.001: 0.001 + 1024 * (2 * 2^-14 + 1e-4) = 0.2284 (DESIGN §3 "Miss tiles", "The bound")
+constexpr double kDelta = 0.24;
+constexpr double kDilate = 0.25;       // voxels added to every side of a box: delta rounded up
+static_assert(kDilate >= kDelta, "the mask must dilate the occupancy boxes by at least the proof's bound");
+static_assert(kDelta >= 0.001 + 1024.0 * (2.0 / 16384.0 + 1e-4), "delta must cover the three terms of the proof");
 constexpr double kMinDepth = 0.25;     // a dilated box whose corners are not all this far in front of the eye marks the view
 constexpr int kMaxBoxes = 1 << 21;     // more boxes than this: no mask (the per-view build would cost more than it saves)
 constexpr double kMaxEye = 65536.0;    // |gro| per axis above this: no mask (the proof's bound on the first step's rounding)
