@@ -524,6 +524,52 @@ int vrt_denoise(vrt_ctx *ctx, int width, int height, const void *d_rgba8, const 
 /* the same through HOST buffers, synchronous */
 int vrt_denoise_host(vrt_ctx *ctx, int width, int height, const uint8_t *rgba8, const int32_t *id_dist,
                      uint8_t *out_rgba8);
+
+/* The display pass in HDR: the same ID-aware blur on a FLOAT image, then the tone map. vrt_denoise reads rgba8, so the shown image
+ * of an HDR accumulation (vrt_accum_resolve_hdr's out_shown_rgba8) is tone map, quantise, then blur: an emitter sample of 10.0 is
+ * clamped to 1.0 before its face's neighbours average it, and blur(tonemap(x)) != tonemap(blur(x)). These calls filter the floats
+ * and map the filtered estimate; they also hand out the filtered floats themselves, to save or to grade.
+ *
+ * All arithmetic below is float32: every operation rounded on its own, no contraction.
+ *  1. The input value. Every float read from the input image [H][W][3] goes through h(c) = min(max(0, c), 65504.0f), with the min /
+ *     max conventions of vrt_accum_keep_hdr point 1: NaN -> +0, a negative value (and -0) -> +0, +Inf -> 65504; subnormals are
+ *     kept. The centre pixel, every tap, and the pixels that pass through alike.
+ *  2. The filter, quad.frag:22-83 with screenTexture that float image. A pixel whose voxel ID is 0 yields h(c) per channel.
+ *     Otherwise R = clamp(int(200.0f / sqrtf((float)max(1, dist))), 1, 20); sum_ch = 0 and count = 0; then, over the taps of the
+ *     (2R+1)^2 window that lie inside the image and whose voxel ID equals the centre's, y outer, x inner:
+ *     sum_ch = sum_ch + h(c_ch), count = count + 1.0f; and f_ch = sum_ch / max(count, 1.0f).
+ *  3. The outputs; either may be NULL, not both. out_rgb [H][W][3] receives f. out_rgba8 [H][W][4] receives unorm8(tonemap(f)),
+ *     alpha 255, with the vrt_tonemap of vrt_accum_resolve_hdr: the same two operators, the same validation, tm == NULL means
+ *     VRT_TONEMAP_CLAMP with exposure 1.
+ *  4. Identity with the byte pass. Where every input float is byte / 255.0f of an rgba8 image whose alpha is 255 (what every image
+ *     this library writes) and tm == NULL, out_rgba8 equals vrt_denoise's output on that image byte for byte: the staged floats
+ *     are the same, 1.0f * x is exact, and unorm8(byte / 255.0f) is the byte. (vrt_denoise copies a pass-through pixel's alpha;
+ *     this pass always writes 255.)
+ * The sums cannot overflow: at most 1681 taps of at most 65504. Options, tile scheduling and VRT_OPT_DISPLAY_KERNEL act on this
+ * pass as on vrt_denoise, from scheduling state of its own: neither pass changes the other's measurements or tile order. (The
+ * states of all launch shapes share one pool of 16 per context; once a context has used more shapes than that, a new shape of
+ * either pass recycles the least recently used state of any, which only costs that shape its measured order.)
+ *
+ * vrt_denoise_hdr       DEVICE pointers, full frames (W*H x 3 floats / W*H int2 / W*H x 3 floats / W*H packed rgba8), stream-ordered.
+ *                       VRT_E_INVALID: d_rgb or d_id_dist NULL, both outputs NULL, d_out_rgb == d_rgb, an unknown tm->op, an exposure
+ *                       that is not finite or not > 0, a frame size vrt_denoise refuses.
+ * vrt_denoise_hdr_host  the same through HOST buffers, synchronous; staged through device buffers the context keeps (24 bytes per
+ *                       pixel for the two float images; like the other host forms' they grow and never shrink).
+ * vrt_accum_resolve_hdr_shown  the filter on an HDR accumulation: the input is its float mean -- exactly what vrt_accum_resolve_hdr
+ *                       writes to out_rgb -- with the accumulation's id_dist image. HOST buffers (either may be NULL, not both),
+ *                       synchronous. Errors: those of vrt_accum_resolve_hdr (VRT_E_STATE: no begin, no sample yet, begun without
+ *                       HDR; VRT_E_INVALID: the tone map), VRT_E_INVALID for both outputs NULL.
+ * vrt_accum_resolve_hdr_shown_device  the same into DEVICE buffers, enqueued on `stream` (NULL: the context's), ordered against the
+ *                       adds as vrt_accum_resolve_hdr_device is.
+ * The mean passes through 12 bytes per pixel of device memory that belong to the accumulation and are allocated by the first of
+ * these two calls: an HDR accumulation that never makes one takes what it took. vrt_accum_resolve_hdr's three outputs are not
+ * changed by them. Frames, views and vrt_multi have no float output, so vrt_dispatch_frame's display pass stays the byte pass. */
+int vrt_denoise_hdr(vrt_ctx *ctx, int width, int height, const void *d_rgb, const void *d_id_dist, const vrt_tonemap *tm,
+                    void *d_out_rgb, void *d_out_rgba8, void *stream);
+int vrt_denoise_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, const int32_t *id_dist, const vrt_tonemap *tm,
+                         float *out_rgb, uint8_t *out_rgba8);
+int vrt_accum_resolve_hdr_shown(vrt_ctx *ctx, const vrt_tonemap *tm, float *out_shown_rgb, uint8_t *out_shown_rgba8);
+int vrt_accum_resolve_hdr_shown_device(vrt_ctx *ctx, const vrt_tonemap *tm, void *d_shown_rgb, void *d_shown_rgba8, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

@@ -286,6 +286,11 @@ def hip_lib():
         L.vrt_accum_keep_hdr.argtypes = [C.c_void_p, C.c_int]
         L.vrt_accum_resolve_hdr.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_denoise_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+        L.vrt_denoise_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_hdr_shown.argtypes = [C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_hdr_shown_device.argtypes = [C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
         _hip = L
     return _hip
 
@@ -1038,6 +1043,46 @@ class Context:
         """vrt_accum_resolve_hdr_device: DEVICE buffers (any may be None; d_shown needs d_rgba), enqueued on `stream`"""
         tm = self._tonemap(tonemap, exposure)
         self._chk(self._L.vrt_accum_resolve_hdr_device(self._h, d_rgb, C.byref(tm), d_rgba, d_shown, stream))
+
+    def accum_resolve_hdr_shown(self, tonemap="clamp", exposure=1.0):
+        """The HDR display pass on an HDR accumulation (vrt_accum_resolve_hdr_shown): the ID-aware blur on the float mean, then the
+        tone map -> (shown_rgb float32[H,W,3]: the filtered mean; shown_rgba8[H,W,4]: its tone-mapped bytes)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        shape = getattr(self, "_accum_shape", None)
+        if shape is None:
+            raise VrtError("accum_resolve_hdr_shown: no accumulation (call accum_begin first)")
+        h, w = shape
+        rgb = np.zeros((h, w, 3), np.float32)
+        rgba = np.zeros((h, w, 4), np.uint8)
+        self._chk(self._L.vrt_accum_resolve_hdr_shown(self._h, C.byref(tm) if tm else None, rgb.ctypes.data, rgba.ctypes.data))
+        return rgb, rgba
+
+    def accum_resolve_hdr_shown_device(self, d_shown_rgb, d_shown_rgba, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_shown_device: DEVICE buffers (either may be None, not both), enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        self._chk(self._L.vrt_accum_resolve_hdr_shown_device(self._h, C.byref(tm) if tm else None, d_shown_rgb, d_shown_rgba, stream))
+
+    def denoise_hdr(self, rgb, id_dist, tonemap="clamp", exposure=1.0):
+        """The display pass in HDR through host arrays (vrt_denoise_hdr_host): quad.frag's ID-aware blur on a float image
+        rgb[H,W,3], each float through h(c) = min(max(0, c), 65504), then the tone map of accum_resolve_hdr
+        -> (rgb float32[H,W,3]: the filtered floats; rgba8 uint8[H,W,4]: their tone-mapped bytes)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        idd = np.ascontiguousarray(id_dist, np.int32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3 or idd.shape != rgb.shape[:2] + (2,):
+            raise ValueError(f"expected rgb[H,W,3] and id_dist[H,W,2], got {rgb.shape} and {idd.shape}")
+        h, w = rgb.shape[:2]
+        out = np.zeros_like(rgb)
+        out8 = np.zeros((h, w, 4), np.uint8)
+        self._chk(self._L.vrt_denoise_hdr_host(self._h, w, h, rgb.ctypes.data, idd.ctypes.data, C.byref(tm) if tm else None, out.ctypes.data,
+                                               out8.ctypes.data))
+        return out, out8
+
+    def denoise_hdr_device(self, width, height, d_rgb, d_id, d_out_rgb, d_out_rgba, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_denoise_hdr: DEVICE buffers (d_rgb: W*H x 3 floats; d_out_rgb, d_out_rgba: either may be None, not both), enqueued
+        on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        self._chk(self._L.vrt_denoise_hdr(self._h, width, height, d_rgb, d_id, C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -70,12 +70,7 @@ int resolve_hdr_state(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
     int r = resolve_state(c, what);
     if (r) return r;
     if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
-    if (tm) {
-        if (tm->op != VRT_TONEMAP_CLAMP && tm->op != VRT_TONEMAP_REINHARD) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown tone-map operator");
-        if (!(tm->exposure > 0.0f) || !(tm->exposure <= 3.402823466e38f))
-            return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": exposure must be finite and > 0");
-    }
-    return VRT_OK;
+    return check_tonemap(c, what, tm);
 }
 
 // float64 sums -> float mean into d_rgb, its tone-mapped rgba8 into d_rgba (either may be null), the display pass into d_shown
@@ -89,6 +84,31 @@ int resolve_hdr_into(vrt_ctx *c, float *d_rgb, const vrt_tonemap *tm, void *d_rg
     }
     if (d_shown) return vrt_denoise(c, ac.width, ac.height, d_rgba, ac.d_id, d_shown, s);
     return VRT_OK;
+}
+
+// vrt_accum_resolve_hdr_shown*: the float mean's scratch (12 bytes per pixel), the accumulation's own, made at the first such call --
+// an HDR accumulation that never asks for the filtered mean keeps its footprint. Every use of it is ordered on the context's stream:
+// a caller's stream is joined back through Accum::read.
+int ensure_hmean(vrt_ctx *c, size_t px) {
+    Accum &ac = c->accum;
+    if (px <= ac.hmean_pixels) return VRT_OK;
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    ac.hmean_pixels = 0;
+    const int r = grow(c, ac.d_hmean, px * 12);
+    if (r) return r;
+    ac.hmean_pixels = px;
+    return VRT_OK;
+}
+
+// The HDR display pass on the accumulation: the existing resolve launch writes the float mean (exactly vrt_accum_resolve_hdr's
+// out_rgb) into the scratch, vrt_denoise_hdr filters it with the accumulation's id_dist image. Two launches on purpose: the display
+// pass stages every pixel about eight times across its tiles' halos, and 28 bytes of sums and count per staged tap against 12 of
+// mean -- with a float64 divide each -- loses to one more pass over the frame.
+int resolve_hdr_shown_into(vrt_ctx *c, const vrt_tonemap *tm, void *d_shown_rgb, void *d_shown_rgba, hipStream_t s) {
+    Accum &ac = c->accum;
+    const int r = resolve_hdr_into(c, ac.d_hmean, tm, nullptr, nullptr, s);
+    if (r) return r;
+    return vrt_denoise_hdr(c, ac.width, ac.height, ac.d_hmean, ac.d_id, tm, d_shown_rgb, d_shown_rgba, s);
 }
 
 // vrt_accum_begin_ex, and with rule = {min, max, tolerance} vrt_accum_begin_adaptive
@@ -377,6 +397,49 @@ int vrt_accum_resolve_hdr_device(vrt_ctx *c, void *d_rgb, const vrt_tonemap *tm,
         VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
     }
     r = resolve_hdr_into(c, static_cast<float *>(d_rgb), tm, d_rgba8, d_shown_rgba8, s);
+    if (r) return r;
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.read, s));
+        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
+    }
+    return VRT_OK;
+}
+
+int vrt_accum_resolve_hdr_shown(vrt_ctx *c, const vrt_tonemap *tm, float *out_shown_rgb, uint8_t *out_shown_rgba8) {
+    int r = resolve_hdr_state(c, "vrt_accum_resolve_hdr_shown", tm);
+    if (r) return r;
+    if (!out_shown_rgb && !out_shown_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_hdr_shown: both outputs null");
+    VRT_HIP(c, hipSetDevice(c->device));
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if ((r = ensure_scratch(c, px)) || (r = ensure_hmean(c, px))) return r;
+    if (out_shown_rgb && px > ac.hrgb_pixels) {   // as vrt_accum_resolve_hdr makes it
+        VRT_HIP(c, hipStreamSynchronize(c->stream));
+        ac.hrgb_pixels = 0;
+        if ((r = grow(c, ac.d_hrgb, px * 12))) return r;
+        ac.hrgb_pixels = px;
+    }
+    r = resolve_hdr_shown_into(c, tm, out_shown_rgb ? ac.d_hrgb : nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
+    if (r) return r;
+    if (out_shown_rgb) VRT_HIP(c, hipMemcpyAsync(out_shown_rgb, ac.d_hrgb, px * 12, hipMemcpyDeviceToHost, c->stream));
+    if (out_shown_rgba8) VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_accum_resolve_hdr_shown_device(vrt_ctx *c, const vrt_tonemap *tm, void *d_shown_rgb, void *d_shown_rgba8, void *stream) {
+    int r = resolve_hdr_state(c, "vrt_accum_resolve_hdr_shown_device", tm);
+    if (r) return r;
+    if (!d_shown_rgb && !d_shown_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_hdr_shown_device: both outputs null");
+    VRT_HIP(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    Accum &ac = c->accum;
+    if ((r = ensure_hmean(c, (size_t)ac.width * (size_t)ac.height))) return r;
+    if (s != c->stream) {   // as vrt_accum_resolve_device orders itself against the adds (and, through `read`, against the last call's use of the mean)
+        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
+        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
+    }
+    r = resolve_hdr_shown_into(c, tm, d_shown_rgb, d_shown_rgba8, s);
     if (r) return r;
     if (s != c->stream) {
         VRT_HIP(c, hipEventRecord(ac.read, s));

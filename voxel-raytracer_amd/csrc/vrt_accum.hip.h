@@ -35,6 +35,7 @@
 // hdr_frame_kernel's image, which replaces the frame (or pass 1) they otherwise take the bytes from. Both, and hdr_resolve_kernel: vrt_accum_hdr.hip.h.
 #pragma once
 #include "vrt_accum.h"
+#include "vrt_hdr.hip.h"
 #include "vrt_full.hip.h"
 #include "vrt_lens.hip.h"
 
@@ -89,8 +90,7 @@ VRT_DEV void add_repeat(uint32_t rgba, uint32_t k, PixelState &p) {
 // ---- HDR sums (HDR = true) ----
 struct HdrSum { double r, g, b; };
 
-// h(c) of include/vrt.h: [0, kHdrMax], NaN -> +0 (0 < NaN is false); unorm8(hdr_value(c)) == unorm8(c) for every float
-VRT_DEV float hdr_value(float c) { return fmin_c(fmax_c(0.0f, c), kHdrMax); }
+// hdr_value(): h(c) of include/vrt.h, and tone_map(): vrt_hdr.hip.h
 
 VRT_DEV HdrSum load_hdr(const double *hsum, size_t o) {
     const double *p = hsum + o * 3;
@@ -110,12 +110,6 @@ VRT_DEV void add_hdr_repeat(const float *fc, uint32_t k, HdrSum &h) {
     h.r = h.r + (double)hdr_value(fc[0]) * (double)k;
     h.g = h.g + (double)hdr_value(fc[1]) * (double)k;
     h.b = h.b + (double)hdr_value(fc[2]) * (double)k;
-}
-
-// The tone map of include/vrt.h vrt_tonemap on one channel of the mean: every operation rounded on its own
-VRT_DEV float tone_map(float x, int op, float e) {
-    const float xe = e * x;
-    return op == 1 ? xe / (1.0f + xe) : xe;   // VRT_TONEMAP_REINHARD : _CLAMP (unorm8 clamps)
 }
 
 // The sample-looped kernels keep a lane's three float64 sums in LDS across the loop (24 bytes per lane), as the bounce kernel keeps

@@ -7,8 +7,11 @@
 // colours already converted to the floats the shader's sampler returns (byte / 255.0f, one correctly rounded division per
 // staged pixel instead of one per tap) -- and every lane walks its pixels' windows in the shader's order (y outer, x inner), so
 // the fp32 sums round exactly as the reference's do. Global memory is touched only by the staging loads and the final store.
+// The HDR instances (include/vrt.h vrt_denoise_hdr) are the same pass on a float image: what differs is how a tap's colour reaches
+// LDS (float loads through h(c) instead of byte unpacking) and how a pixel leaves (floats and / or tone-mapped bytes); see tile().
 #pragma once
 #include "vrt_common.hip.h"
+#include "vrt_hdr.hip.h"
 
 namespace vrt {
 namespace denoise {
@@ -26,6 +29,12 @@ struct Args {
     const uint32_t *group_order;
     uint32_t *tile_cost;   // atomicMax of the waves' clock ticks; zeroed by the host before a measuring launch
     int rows_path;         // 0: per wave, the cheaper of the two walks below; 2: always the wave's common rows (rows_static); 3: always own boxes (rows_own_box)
+    // the HDR instances (HDR = true, include/vrt.h vrt_denoise_hdr) read `rgb` in place of `rgba`; `out` (their tone-mapped bytes) and
+    // `out_rgb` may each be null, not both
+    const float *rgb;      // 3 floats per pixel, W*H
+    float *out_rgb;        // 3 floats per pixel, W*H
+    int op;                // VRT_TONEMAP_*
+    float exposure;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -292,7 +301,32 @@ struct IdRows {
 
 __device__ __forceinline__ uint32_t id_slot(const int id) { return ((uint32_t)id * 2654435761u) >> 25; }   // 7 bits
 
-template <int PX, int TH>
+// HDR: the colours are floats (Args::rgb), each through h(c) = accum::hdr_value on its way into LDS, and the result leaves as floats
+// and / or tone-mapped bytes. h(c) is what makes the float image fit the walks, which are shared and know nothing of it: every
+// staged colour is finite (rows_own_box multiplies what it over-reads by a zero mask) and no sum is negative (a masked
+// fma(0, c, s) must leave s as it is).
+template <bool HDR>
+__device__ __forceinline__ void put_pixel(const Args &a, const size_t p, const float r, const float g, const float b) {
+    static_assert(HDR, "the byte pass packs its own bytes");
+    if (a.out_rgb) { a.out_rgb[p * 3 + 0] = r; a.out_rgb[p * 3 + 1] = g; a.out_rgb[p * 3 + 2] = b; }
+    if (a.out)
+        a.out[p] = unorm8(accum::tone_map(r, a.op, a.exposure)) | (unorm8(accum::tone_map(g, a.op, a.exposure)) << 8) |
+                   (unorm8(accum::tone_map(b, a.op, a.exposure)) << 16) | (255u << 24);
+}
+// a pixel that passes through (quad.frag:36-39): h(c) of its own colour
+template <bool HDR>
+__device__ __forceinline__ void pass_pixel(const Args &a, const size_t p) {
+    if constexpr (HDR) {
+        const float *c = a.rgb + p * 3;
+        put_pixel<true>(a, p, accum::hdr_value(c[0]), accum::hdr_value(c[1]), accum::hdr_value(c[2]));
+    } else {
+        a.out[p] = a.rgba[p];
+    }
+}
+
+struct Rgb { float r, g, b; };   // a float image's pixel on its way into LDS
+
+template <int PX, int TH, bool HDR = false>
 __device__ __forceinline__ void tile(const Args &a, const int bx, const int by, f4 *s_rec, IdRows *s_ids) {
     constexpr int kTH = TH, kSpanY = TH + 2 * kMaxR;
     constexpr int kLanesX = kTW / PX, kThreads = kLanesX * kTH, kTaps = kSpanX * kSpanY;
@@ -339,7 +373,7 @@ __device__ __forceinline__ void tile(const Args &a, const int bx, const int by, 
             for (int k = 0; k < PX; ++k)
                 if (px0 + k < a.width) {
                     const size_t p = (size_t)py * (size_t)a.width + (size_t)(px0 + k);
-                    a.out[p] = a.rgba[p];
+                    pass_pixel<HDR>(a, p);
                 }
         }
         return;
@@ -389,11 +423,18 @@ __device__ __forceinline__ void tile(const Args &a, const int bx, const int by, 
             atomicMin(&s_ids->xlo[run_slot], run_xlo); atomicMax(&s_ids->xhi[run_slot], run_xhi);
         }
     };
-    const auto stage_tap = [&](const int vidj, const uint32_t colj, const int lx, const int ly) {
+    // colj: the tap's colour as the image holds it -- packed rgba8, or (HDR) three floats, which pass through h(c) here
+    const auto stage_tap = [&](const int vidj, const auto colj, const int lx, const int ly) {
         f4 rec;
-        rec.x = unorm_of((float)(colj & 0xffu));          // byte / 255.0f, bit for bit (vrt_common.hip.h), without a table in LDS
-        rec.y = unorm_of((float)((colj >> 8) & 0xffu));
-        rec.z = unorm_of((float)((colj >> 16) & 0xffu));
+        if constexpr (HDR) {
+            rec.x = accum::hdr_value(colj.r);
+            rec.y = accum::hdr_value(colj.g);
+            rec.z = accum::hdr_value(colj.b);
+        } else {
+            rec.x = unorm_of((float)(colj & 0xffu));          // byte / 255.0f, bit for bit (vrt_common.hip.h), without a table in LDS
+            rec.y = unorm_of((float)((colj >> 8) & 0xffu));
+            rec.z = unorm_of((float)((colj >> 16) & 0xffu));
+        }
         rec.w = __int_as_float(vidj);
         s_rec[ly * kStride<PX> + slot<PX>(lx)] = rec;
         if (vidj != 0) {   // fold this tap's row and column into its id's ranges, if one of the tile's own pixels carries that id
@@ -425,7 +466,63 @@ __device__ __forceinline__ void tile(const Args &a, const int bx, const int by, 
     // reads -- same time: what the staging phase waits for is LDS itself, busy with the other work-group's walk.)
     constexpr int kQuads = kTaps / 4, kQuadIters = (kQuads + kThreads - 1) / kThreads;
     static_assert(kSpanX % 4 == 0 && kTW % 4 == 0 && kMaxR % 4 == 0, "quads never straddle a row or the image's edge");
-    const bool quads = (a.width & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.rgba) | reinterpret_cast<uintptr_t>(a.id)) & 15u) == 0u;   // uniform
+    // HDR: the four colours are twelve floats, three 16-byte loads (a quad starts at a pixel index g that is a multiple of four, so
+    // its 12 * g bytes are 16-byte aligned when the image is); tap by tap, three 4-byte loads per colour
+    const bool quads = (a.width & 3) == 0 && ((reinterpret_cast<uintptr_t>(HDR ? (const void *)a.rgb : (const void *)a.rgba) | reinterpret_cast<uintptr_t>(a.id)) & 15u) == 0u;   // uniform
+    if constexpr (HDR) {
+        if (quads) {
+            f4 c0[kQuadIters], c1[kQuadIters], c2[kQuadIters];
+            uint4 iq0[kQuadIters], iq1[kQuadIters];
+#pragma unroll
+            for (int q = 0; q < kQuadIters; ++q) {
+                const int i4 = tid + q * kThreads;
+                const int lx = (i4 % (kSpanX / 4)) * 4, ly = i4 / (kSpanX / 4);
+                const int gx = tx0 + lx, gy = ty0 + ly;
+                c0[q] = c1[q] = c2[q] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+                iq0[q] = iq1[q] = make_uint4(0u, 0u, 0u, 0u);
+                if (i4 < kQuads && gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {
+                    const size_t g = (size_t)gy * (size_t)a.width + (size_t)gx;
+                    const f4 *c = reinterpret_cast<const f4 *>(a.rgb + g * 3);
+                    c0[q] = c[0]; c1[q] = c[1]; c2[q] = c[2];
+                    iq0[q] = *reinterpret_cast<const uint4 *>(a.id + g);
+                    iq1[q] = *reinterpret_cast<const uint4 *>(a.id + g + 2);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < kQuadIters; ++q) {
+                const int i4 = tid + q * kThreads;
+                if (i4 < kQuads) {
+                    const int lx = (i4 % (kSpanX / 4)) * 4, ly = i4 / (kSpanX / 4);
+                    stage_tap((int)iq0[q].x, Rgb{c0[q].x, c0[q].y, c0[q].z}, lx, ly);
+                    stage_tap((int)iq0[q].z, Rgb{c0[q].w, c1[q].x, c1[q].y}, lx + 1, ly);
+                    stage_tap((int)iq1[q].x, Rgb{c1[q].z, c1[q].w, c2[q].x}, lx + 2, ly);
+                    stage_tap((int)iq1[q].z, Rgb{c2[q].y, c2[q].z, c2[q].w}, lx + 3, ly);
+                }
+            }
+        } else
+        for (int b = 0; b < kStageIters; b += kBatch) {
+            int vid[kBatch];
+            float col[kBatch][3];
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const int i = tid + (b + j) * kThreads;
+                const int lx = i % kSpanX, ly = i / kSpanX;
+                const int gx = tx0 + lx, gy = ty0 + ly;
+                vid[j] = 0;
+                col[j][0] = col[j][1] = col[j][2] = 0.0f;
+                if (i < kTaps && gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {
+                    const size_t g = (size_t)gy * (size_t)a.width + (size_t)gx;
+                    vid[j] = a.id[g].x;
+                    col[j][0] = a.rgb[g * 3 + 0]; col[j][1] = a.rgb[g * 3 + 1]; col[j][2] = a.rgb[g * 3 + 2];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kBatch; ++j) {
+                const int i = tid + (b + j) * kThreads;
+                if (i < kTaps) stage_tap(vid[j], Rgb{col[j][0], col[j][1], col[j][2]}, i % kSpanX, i / kSpanX);
+            }
+        }
+    } else
     if (quads) {
         uint4 cq[kQuadIters], iq0[kQuadIters], iq1[kQuadIters];
 #pragma unroll
@@ -598,15 +695,17 @@ __device__ __forceinline__ void tile(const Args &a, const int bx, const int by, 
         if (px >= a.width) break;
         const size_t p = (size_t)py * (size_t)a.width + (size_t)px;
         if (cid[k] == 0) {  // quad.frag:36-39
-            a.out[p] = a.rgba[p];
+            pass_pixel<HDR>(a, p);
             continue;
         }
         const float d = fmax_c(acc.bc[k].y, 1.0f);
+        if constexpr (HDR) put_pixel<true>(a, p, acc.rg[k].x / d, acc.rg[k].y / d, acc.bc[k].x / d);
+        else
         a.out[p] = unorm8(acc.rg[k].x / d) | (unorm8(acc.rg[k].y / d) << 8) | (unorm8(acc.bc[k].x / d) << 16) | (255u << 24);
     }
 #ifdef VRT_DENOISE_PHASE
     VRT_PH(9);   // divisions and stores
-    if (tid == 0) a.out[(size_t)py * (size_t)a.width + (size_t)px0] = ph_ticks;
+    if (tid == 0 && a.out) a.out[(size_t)py * (size_t)a.width + (size_t)px0] = ph_ticks;
 #endif
 }
 
@@ -614,19 +713,19 @@ __device__ __forceinline__ void tile(const Args &a, const int bx, const int by, 
 // One workgroup per tile. waves_per_eu(2, 2) keeps an instance within 256 registers: the default kernel (PX = 2,
 // TH = 16: four waves per workgroup, two workgroups per CU by LDS) needs two waves to share a SIMD. Without it the
 // compiler, seeing occupancy already limited by LDS, spreads into AGPRs and the second workgroup no longer fits.
-template <int PX, int TH, bool SCHED = false>
+template <int PX, int TH, bool SCHED = false, bool HDR = false>
 __global__ __launch_bounds__(kTW / PX *TH) __attribute__((amdgpu_waves_per_eu(2, 2))) void denoise_px_kernel(const Args a) {
     __shared__ f4 s_rec[kStride<PX> * (TH + 2 * kMaxR + 1)];   // + one row of zeros behind the window (rows_own_box reads past its boxes)
     __shared__ IdRows s_ids;
     if constexpr (!SCHED) {
-        tile<PX, TH>(a, blockIdx.x, blockIdx.y, s_rec, &s_ids);
+        tile<PX, TH, HDR>(a, blockIdx.x, blockIdx.y, s_rec, &s_ids);
     } else {  // 1-D grid of whole groups; the tiles of a frame differ by two orders of magnitude (sky: a copy; radius 20: 1,681 taps)
         int t = (int)blockIdx.x;
         if (a.group_order) t = (int)a.group_order[blockIdx.x / kGroupTiles] * kGroupTiles + (int)(blockIdx.x % kGroupTiles);
         if (t >= a.n_tiles) return;
         const unsigned long long t_begin = a.tile_cost ? __builtin_readcyclecounter() : 0ull;
         const int by = t / a.tiles_x;
-        tile<PX, TH>(a, t - by * a.tiles_x, by, s_rec, &s_ids);
+        tile<PX, TH, HDR>(a, t - by * a.tiles_x, by, s_rec, &s_ids);
         if (a.tile_cost && ((threadIdx.y * (kTW / PX) + threadIdx.x) & 63) == 0)
             atomicMax(&a.tile_cost[t], (uint32_t)(__builtin_readcyclecounter() - t_begin));
     }

@@ -89,6 +89,9 @@ struct vrt_ctx {
     void *d_id = nullptr;
     void *d_shown = nullptr;
     size_t scratch_pixels = 0;
+    // ... and the two float images of vrt_denoise_hdr_host (vrt_display.cpp)
+    void *d_hdr_in = nullptr, *d_hdr_out = nullptr;
+    size_t hdr_scratch_pixels = 0;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     void *d_query = nullptr;
     size_t query_bytes = 0;
@@ -232,7 +235,8 @@ struct vrt_ctx {
         double *d_hsum = nullptr;                // 3 doubles per pixel
         float *d_hframe = nullptr;               // 3 floats per pixel: the corner frame's (or pass 1's) float colour
         float *d_hrgb = nullptr;                 // vrt_accum_resolve_hdr's float image on its way to the host
-        size_t hdr_pixels = 0, hrgb_pixels = 0;  // capacities
+        float *d_hmean = nullptr;                // vrt_accum_resolve_hdr_shown*: the float mean the display pass reads, made at the first such call
+        size_t hdr_pixels = 0, hrgb_pixels = 0, hmean_pixels = 0;  // capacities
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
@@ -264,6 +268,8 @@ int upload_roots(vrt_ctx *c);
 uint32_t dim_of_texels(size_t texels);   // src/main.cpp:266-268
 int check_frame(vrt_ctx *c, int width, int height);
 int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-buffer entry points
+// a vrt_tonemap the header defines (NULL: VRT_TONEMAP_CLAMP, exposure 1), else VRT_E_INVALID in the name of `what`
+int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm);
 // What frames, ray batches and queries put into KArgs the same way (after ensure_analysis). The scene block: everything a kernel
 // reads of the tree and the world, wide root 0 as build_wide() found it -- and not root0_only, which each caller decides for
 // itself. The light block: the uniforms of the shading and the shadow ray's set-up.
@@ -310,6 +316,7 @@ constexpr long kSchedMinGroups = 768;    // an eighth of a 1080p frame (1,013 gr
 constexpr long kSchedMaxGroups = 36864;  // tile_order_kernel keeps one word per group in LDS (144 KiB of 160)
 constexpr size_t kSchedMaxStates = 16;
 constexpr int kSchedDenoise = 100;              // SchedState::mode of the display pass
+constexpr int kSchedDenoiseHdr = kSchedDenoise + 1;   // ... and of its HDR form (vrt_denoise_hdr): states, counters and orders of its own
 constexpr long kSchedMinDenoiseGroups = 256;    // two workgroups fit a CU: 1,024 tiles are two rounds
 constexpr long kSchedMaxDenoiseGroups = 2048;   // beyond ~8,000 tiles (16 rounds) the tail is small and heaviest-first starts cost the halo reads their L2 locality: 4K nature 0.147 ms row-major, 0.157 ordered
 

@@ -52,6 +52,19 @@ struct Denoise {
 };
 void denoise_tiling(int width, int height, int &tiles_x, int &n_tiles);
 hipError_t denoise(const Denoise &d, bool whole_groups, hipStream_t s);
+// vrt_launch_denoise_hdr.hip: the same pass on a float image (include/vrt.h vrt_denoise_hdr): rgb in, the filtered floats and / or
+// their tone-mapped bytes out (either may be null), the tiling and the scheduling arguments as above
+struct DenoiseHdr {
+    const void *rgb, *id;
+    void *out_rgb, *out_rgba;
+    int width, height;
+    const uint32_t *group_order;
+    uint32_t *tile_cost;
+    int rows_path = 0;
+    int op = 0;              // VRT_TONEMAP_*
+    float exposure = 1.0f;
+};
+hipError_t denoise_hdr(const DenoiseHdr &d, bool whole_groups, hipStream_t s);
 
 // vrt_launch_query.hip: the world queries (vrt_query.hip.h), one lane per ray / point; a carries the scene part of KArgs only
 hipError_t cast_rays(const KArgs &a, const query::RayArgs &q, hipStream_t s);

@@ -76,6 +76,10 @@ hipError_t denoise(const Denoise &d, bool whole_groups, hipStream_t s) {
     a.group_order = d.group_order;
     a.tile_cost = d.tile_cost;
     a.rows_path = d.rows_path;
+    a.rgb = nullptr;   // the HDR instances' (vrt_launch_denoise_hdr.hip)
+    a.out_rgb = nullptr;
+    a.op = 0;
+    a.exposure = 1.0f;
     if (!whole_groups) {
         const dim3 grid((unsigned)a.tiles_x, (unsigned)(a.n_tiles / a.tiles_x));
         hipLaunchKernelGGL((denoise_px_kernel<2, 16>), grid, dim3(kTW / 2, 16), 0, s, a);

@@ -154,6 +154,14 @@ int ensure_scratch(vrt_ctx *c, size_t px) {
     return VRT_OK;
 }
 
+int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
+    if (!tm) return VRT_OK;
+    if (tm->op != VRT_TONEMAP_CLAMP && tm->op != VRT_TONEMAP_REINHARD) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown tone-map operator");
+    if (!(tm->exposure > 0.0f) || !(tm->exposure <= 3.402823466e38f))
+        return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": exposure must be finite and > 0");
+    return VRT_OK;
+}
+
 }  // namespace vrt_internal
 
 extern "C" {
@@ -242,6 +250,8 @@ void vrt_destroy(vrt_ctx *c) {
     if (c->d_rgba) (void)hipFree(c->d_rgba);
     if (c->d_id) (void)hipFree(c->d_id);
     if (c->d_shown) (void)hipFree(c->d_shown);
+    if (c->d_hdr_in) (void)hipFree(c->d_hdr_in);
+    if (c->d_hdr_out) (void)hipFree(c->d_hdr_out);
     if (c->d_query) (void)hipFree(c->d_query);
     if (c->d_rays) (void)hipFree(c->d_rays);
     (void)hipFree(c->accum.d_sums);
@@ -253,6 +263,7 @@ void vrt_destroy(vrt_ctx *c) {
     (void)hipFree(c->accum.d_hsum);
     (void)hipFree(c->accum.d_hframe);
     (void)hipFree(c->accum.d_hrgb);
+    (void)hipFree(c->accum.d_hmean);
     if (c->accum.added) (void)hipEventDestroy(c->accum.added);
     if (c->accum.read) (void)hipEventDestroy(c->accum.read);
     if (!c->seeds.empty()) (void)hipDeviceSynchronize();   // their launches may be on the caller's streams
