@@ -581,10 +581,27 @@ int vrt_dispatch_frame(vrt_ctx *ctx, int width, int height, int mode, uint8_t *o
  * to the kernel's dispatch packet (hipExtLaunchKernel), so it reads the kernel's
  * own begin-to-end time on the stream it runs on, for up to max_launches
  * launches (0 switches it off). vrt_profile_read waits for the recorded
- * launches, writes their durations (ms) and returns how many. */
+ * launches, writes their durations (ms) and returns how many.
+ *
+ * What takes a slot: one per accepted call of vrt_dispatch, vrt_dispatch_rows, vrt_dispatch_shard, vrt_dispatch_tiles,
+ * vrt_dispatch_views (its up to four views are one launch and one slot), vrt_dispatch_async, vrt_dispatch_frame (the frame; its
+ * display pass takes none), vrt_shade_rays, vrt_shade_rays_device, vrt_shade_rays_hdr, vrt_shade_rays_hdr_device (the host forms
+ * shade a batch in one launch), and one per iteration of vrt_dispatch_timed -- in every mode, on every variant and traversal the
+ * dispatcher may take. What takes none, and does not count towards the stride either: vrt_accum_add (the frame it may launch for
+ * itself included), the resolves, vrt_denoise, vrt_denoise_hdr and their host forms, vrt_cast_rays, vrt_find_voxels, and every
+ * call that is refused (bad argument, open patch batch, no camera, no scene).
+ * The span of a slot is the trace kernel's dispatch packet. VRT_MODE_FULL as two kernels (VRT_OPT_FULL_OPAQUE 1) is ONE slot from
+ * the first kernel's begin to the second one's end. The kernels and memsets a launch may put around its trace kernel lie outside
+ * the span and take no slot: the miss-mask build of VRT_OPT_MISS_TILES (a memset and a kernel before it), the feedback
+ * scheduler's order kernel after a measuring launch, the memset of the tile times before a measuring launch with part-tile waves.
+ * Every vrt_set_profiling call starts a new record of at most max_launches slots and restarts the stride's count; the stride
+ * itself persists. tests/test_gpu_profiling.py pins all of this against event pairs of the caller's own. */
 int vrt_set_profiling(vrt_ctx *ctx, int max_launches);
-/* time only every `every`-th launch (default 1): timing every launch costs a few percent of the frame rate */
+/* time only every `every`-th launch (launches 0, every, 2 * every, ... since vrt_set_profiling; default 1): timing every launch
+ * costs a few percent of the frame rate. every < 1: VRT_E_INVALID. */
 int vrt_set_profiling_stride(vrt_ctx *ctx, int every);
+/* Returns the number of entries written: min(recorded launches, cap), oldest first. The read EMPTIES the record: recorded launches
+ * beyond cap are dropped, and a second read returns 0 until more launches are recorded. ms_out == NULL or cap < 0: VRT_E_INVALID. */
 int vrt_profile_read(vrt_ctx *ctx, float *ms_out, int cap);
 
 int vrt_synchronize(vrt_ctx *ctx);

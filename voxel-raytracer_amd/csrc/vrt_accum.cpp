@@ -278,7 +278,12 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
             fr.hdr = fr.frame_only = true;
             r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &fr);
         } else {
+            // a frame launch of the accumulation's own: like every other launch of vrt_accum_add it takes no profiling slot and
+            // does not count towards the stride (include/vrt.h vrt_set_profiling)
+            const bool profiling = c->profiling;
+            c->profiling = false;
             r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream);
+            c->profiling = profiling;
         }
         ac.frame = r == VRT_OK;
     }

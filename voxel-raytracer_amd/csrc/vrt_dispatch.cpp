@@ -675,11 +675,13 @@ int vrt_set_profiling(vrt_ctx *c, int max_launches) {
     c->prof_count = 0;
     c->prof_seen = 0;
     c->profiling = max_launches > 0;
+    c->prof_cap = 0;
     while (c->profiling && c->prof_events.size() < (size_t)max_launches * 2) {
         hipEvent_t e;
         VRT_HIP(c, hipEventCreate(&e));
         c->prof_events.push_back(e);
     }
+    if (c->profiling) c->prof_cap = (size_t)max_launches;   // not events.size() / 2: an earlier call may have asked for more
     return VRT_OK;
 }
 

@@ -122,7 +122,7 @@ struct vrt_ctx {
     // optional per-launch hipEvent pairs (vrt_set_profiling)
     bool profiling = false;
     std::vector<hipEvent_t> prof_events;  // 2 per slot
-    size_t prof_count = 0;
+    size_t prof_count = 0, prof_cap = 0;  // slots recorded / slots of the current vrt_set_profiling (the events of a larger earlier one are kept)
     size_t prof_seen = 0, prof_stride = 1;  // every prof_stride-th launch is bracketed
     // host copy of the records: lets the dispatcher check the bit-indexed traversal's precondition
     // against the CURRENT world bounds (they arrive separately, through vrt_set_params)
@@ -285,7 +285,7 @@ struct ProfSlot {
     bool taken = false;
     static ProfSlot take(vrt_ctx *c) {
         ProfSlot p;
-        p.taken = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && (c->prof_count + 1) * 2 <= c->prof_events.size();
+        p.taken = c->profiling && (c->prof_seen++ % c->prof_stride) == 0 && c->prof_count < c->prof_cap;
         if (p.taken) { p.ev0 = c->prof_events[2 * c->prof_count]; p.ev1 = c->prof_events[2 * c->prof_count + 1]; }
         return p;
     }

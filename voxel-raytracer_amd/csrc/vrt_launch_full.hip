@@ -8,8 +8,8 @@ namespace launch {
 hipError_t trace_full(const Variant &v, const KArgs &a, const ViewSet &vs, int grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (v.trav == 4) return launch_sched<2, v4::TravAny, 64, 5>(a, vs, grid, s, ev0, ev1);
     if (v.trav == 3) return launch_sched<2, v3::Trav, 64, 5>(a, vs, grid, s, ev0, ev1);
-    if (v.trav == 2) return launch_one<2, v2::Trav, 256, 1>(a, vs, grid, s);
-    return launch_one<2, v1::Trav, 256, 1>(a, vs, grid, s);
+    if (v.trav == 2) return launch_one<2, v2::Trav, 256, 1>(a, vs, grid, s, ev0, ev1);
+    return launch_one<2, v1::Trav, 256, 1>(a, vs, grid, s, ev0, ev1);
 }
 
 hipError_t trace_full_opaque(const KArgs &a, const ViewSet &vs, int grid, int wpe, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
