@@ -37,14 +37,6 @@ void take_inputs(const vrt_ctx *c, Accum &ac) {
     ac.tree_gen = c->tree_gen;
 }
 
-template <class T>
-int grow(vrt_ctx *c, T *&p, size_t bytes) {
-    if (p) VRT_HIP(c, hipFree(p));
-    p = nullptr;
-    VRT_HIP(c, hipMalloc((void **)&p, bytes));
-    return VRT_OK;
-}
-
 int resolve_state(vrt_ctx *c, const char *what) {
     if (!c) return VRT_E_INVALID;
     if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
@@ -89,14 +81,26 @@ int resolve_hdr_into(vrt_ctx *c, float *d_rgb, const vrt_tonemap *tm, void *d_rg
 // vrt_accum_resolve_hdr_shown*: the float mean's scratch (12 bytes per pixel), the accumulation's own, made at the first such call --
 // an HDR accumulation that never asks for the filtered mean keeps its footprint. Every use of it is ordered on the context's stream:
 // a caller's stream is joined back through Accum::read.
-int ensure_hmean(vrt_ctx *c, size_t px) {
+// So is d_hrgb, the float image's way to the host (vrt_accum_resolve_hdr, _hdr_shown): made at the first call that asks for it.
+int ensure_float_image(vrt_ctx *c, DevBuf<float> &buf, size_t px) {
+    return px * 12 <= buf.bytes() ? VRT_OK : reserve_synced(c, {{&buf, px * 12}});
+}
+
+// A resolve on stream s, ordered against the context's: the samples were added on the context's stream, and later adds must not
+// overtake this read (nor, through `read`, the last call's use of the float mean). Nothing to do when s is the context's stream.
+template <class BODY>
+int joined(vrt_ctx *c, hipStream_t s, const BODY &body) {
     Accum &ac = c->accum;
-    if (px <= ac.hmean_pixels) return VRT_OK;
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    ac.hmean_pixels = 0;
-    const int r = grow(c, ac.d_hmean, px * 12);
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
+        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
+    }
+    const int r = body();
     if (r) return r;
-    ac.hmean_pixels = px;
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.read, s));
+        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
+    }
     return VRT_OK;
 }
 
@@ -122,29 +126,25 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
     Accum &ac = c->accum;
     const size_t px = (size_t)width * (size_t)height;
     const size_t tiles = (size_t)((width + 7) / 8) * (size_t)((height + 7) / 8);
+    // each group grows together, after the samples in flight that still write the old buffers (reserve_synced waits for them); a
+    // begin that cannot have its buffers ends the accumulation
     if (px > ac.pixels || tiles > ac.seed_tiles) {
-        VRT_HIP(c, hipStreamSynchronize(c->stream));   // samples in flight still write the old buffers
         ac.begun = false;
-        ac.pixels = ac.seed_tiles = 0;
-        if ((r = grow(c, ac.d_sums, px * 16)) || (r = grow(c, ac.d_pass1, px * 4)) || (r = grow(c, ac.d_id, px * 8)) ||
-            (r = grow(c, ac.d_seed, tiles * 64 * vrt::kSeedPlanesHost * 4)))
+        if ((r = reserve_synced(c, {{&ac.d_sums, px * 16}, {&ac.d_pass1, px * 4}, {&ac.d_id, px * 8},
+                                    {&ac.d_seed, tiles * 64 * vrt::kSeedPlanesHost * 4}})))
             return r;
         ac.pixels = px;
         ac.seed_tiles = tiles;
     }
     if (rule && (px > ac.sq_pixels || tiles > ac.tile_cap)) {   // the adaptive state: Q per pixel, the round's tile list
-        VRT_HIP(c, hipStreamSynchronize(c->stream));
         ac.begun = false;
-        ac.sq_pixels = ac.tile_cap = 0;
-        if ((r = grow(c, ac.d_sq, px * 8)) || (r = grow(c, ac.d_tiles, (tiles + 2) * 4))) return r;
+        if ((r = reserve_synced(c, {{&ac.d_sq, px * 8}, {&ac.d_tiles, (tiles + 2) * 4}}))) return r;
         ac.sq_pixels = px;
         ac.tile_cap = tiles;
     }
     if (c->accum_keep_hdr && px > ac.hdr_pixels) {   // the HDR state: the float64 sums, the corner frame's float colour
-        VRT_HIP(c, hipStreamSynchronize(c->stream));
         ac.begun = false;
-        ac.hdr_pixels = 0;
-        if ((r = grow(c, ac.d_hsum, px * 24)) || (r = grow(c, ac.d_hframe, px * 12))) return r;
+        if ((r = reserve_synced(c, {{&ac.d_hsum, px * 24}, {&ac.d_hframe, px * 12}}))) return r;
         ac.hdr_pixels = px;
     }
     if (!ac.added) VRT_HIP(c, hipEventCreateWithFlags(&ac.added, hipEventDisableTiming));
@@ -203,7 +203,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         return launch::accum_opaque(hdr, src, a, vs, q, adaptive, l, grid, s);
     hipError_t e = hipSuccess;
     if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
-        a.defer_rec = reinterpret_cast<float *>(ac.d_seed);
+        a.defer_rec = reinterpret_cast<float *>(ac.d_seed.get());
         if (!ac.pass1) {
             vs.v[0].out_rgba = ac.d_pass1;
             vs.v[0].out_id = ac.d_id;
@@ -345,18 +345,7 @@ int vrt_accum_resolve_device(vrt_ctx *c, void *d_rgba8, void *d_id_dist, void *d
     if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_device: the display pass needs d_rgba8");
     VRT_HIP(c, hipSetDevice(c->device));
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    Accum &ac = c->accum;
-    if (s != c->stream) {   // the samples were added on the context's stream; later adds must not overtake this read
-        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
-        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
-    }
-    r = resolve_into(c, d_rgba8, d_id_dist, d_shown_rgba8, s);
-    if (r) return r;
-    if (s != c->stream) {
-        VRT_HIP(c, hipEventRecord(ac.read, s));
-        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
-    }
-    return VRT_OK;
+    return joined(c, s, [&] { return resolve_into(c, d_rgba8, d_id_dist, d_shown_rgba8, s); });
 }
 
 int vrt_accum_keep_hdr(vrt_ctx *c, int enable) {
@@ -374,12 +363,7 @@ int vrt_accum_resolve_hdr(vrt_ctx *c, float *out_rgb, const vrt_tonemap *tm, uin
     const size_t px = (size_t)ac.width * (size_t)ac.height;
     r = ensure_scratch(c, px);
     if (r) return r;
-    if (out_rgb && px > ac.hrgb_pixels) {   // the float image's way to the host, made at the first call that asks for it
-        VRT_HIP(c, hipStreamSynchronize(c->stream));
-        ac.hrgb_pixels = 0;
-        if ((r = grow(c, ac.d_hrgb, px * 12))) return r;
-        ac.hrgb_pixels = px;
-    }
+    if (out_rgb && (r = ensure_float_image(c, ac.d_hrgb, px))) return r;
     const bool want_rgba = out_rgba8 || out_shown_rgba8;
     r = resolve_hdr_into(c, out_rgb ? ac.d_hrgb : nullptr, tm, want_rgba ? c->d_rgba : nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
     if (r) return r;
@@ -396,18 +380,7 @@ int vrt_accum_resolve_hdr_device(vrt_ctx *c, void *d_rgb, const vrt_tonemap *tm,
     if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_hdr_device: the display pass needs d_rgba8");
     VRT_HIP(c, hipSetDevice(c->device));
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    Accum &ac = c->accum;
-    if (s != c->stream) {   // as vrt_accum_resolve_device orders itself against the adds
-        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
-        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
-    }
-    r = resolve_hdr_into(c, static_cast<float *>(d_rgb), tm, d_rgba8, d_shown_rgba8, s);
-    if (r) return r;
-    if (s != c->stream) {
-        VRT_HIP(c, hipEventRecord(ac.read, s));
-        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
-    }
-    return VRT_OK;
+    return joined(c, s, [&] { return resolve_hdr_into(c, static_cast<float *>(d_rgb), tm, d_rgba8, d_shown_rgba8, s); });
 }
 
 int vrt_accum_resolve_hdr_shown(vrt_ctx *c, const vrt_tonemap *tm, float *out_shown_rgb, uint8_t *out_shown_rgba8) {
@@ -417,13 +390,8 @@ int vrt_accum_resolve_hdr_shown(vrt_ctx *c, const vrt_tonemap *tm, float *out_sh
     VRT_HIP(c, hipSetDevice(c->device));
     Accum &ac = c->accum;
     const size_t px = (size_t)ac.width * (size_t)ac.height;
-    if ((r = ensure_scratch(c, px)) || (r = ensure_hmean(c, px))) return r;
-    if (out_shown_rgb && px > ac.hrgb_pixels) {   // as vrt_accum_resolve_hdr makes it
-        VRT_HIP(c, hipStreamSynchronize(c->stream));
-        ac.hrgb_pixels = 0;
-        if ((r = grow(c, ac.d_hrgb, px * 12))) return r;
-        ac.hrgb_pixels = px;
-    }
+    if ((r = ensure_scratch(c, px)) || (r = ensure_float_image(c, ac.d_hmean, px))) return r;
+    if (out_shown_rgb && (r = ensure_float_image(c, ac.d_hrgb, px))) return r;
     r = resolve_hdr_shown_into(c, tm, out_shown_rgb ? ac.d_hrgb : nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
     if (r) return r;
     if (out_shown_rgb) VRT_HIP(c, hipMemcpyAsync(out_shown_rgb, ac.d_hrgb, px * 12, hipMemcpyDeviceToHost, c->stream));
@@ -439,18 +407,8 @@ int vrt_accum_resolve_hdr_shown_device(vrt_ctx *c, const vrt_tonemap *tm, void *
     VRT_HIP(c, hipSetDevice(c->device));
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     Accum &ac = c->accum;
-    if ((r = ensure_hmean(c, (size_t)ac.width * (size_t)ac.height))) return r;
-    if (s != c->stream) {   // as vrt_accum_resolve_device orders itself against the adds (and, through `read`, against the last call's use of the mean)
-        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
-        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
-    }
-    r = resolve_hdr_shown_into(c, tm, d_shown_rgb, d_shown_rgba8, s);
-    if (r) return r;
-    if (s != c->stream) {
-        VRT_HIP(c, hipEventRecord(ac.read, s));
-        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
-    }
-    return VRT_OK;
+    if ((r = ensure_float_image(c, ac.d_hmean, (size_t)ac.width * (size_t)ac.height))) return r;
+    return joined(c, s, [&] { return resolve_hdr_shown_into(c, tm, d_shown_rgb, d_shown_rgba8, s); });
 }
 
 int vrt_accum_counts(vrt_ctx *c, uint32_t *out_counts) {
@@ -467,7 +425,7 @@ int vrt_accum_counts(vrt_ctx *c, uint32_t *out_counts) {
     int r = ensure_scratch(c, px);
     if (r) return r;
     uint32_t *d_active = ac.d_tiles + ac.tile_cap + 1;
-    const vrt::accum::Counts q{ac.d_sums, ac.d_sq, static_cast<uint32_t *>(c->d_rgba), d_active, (uint32_t)px, ac.min_samples,
+    const vrt::accum::Counts q{ac.d_sums, ac.d_sq, static_cast<uint32_t *>(c->d_rgba.get()), d_active, (uint32_t)px, ac.min_samples,
                                ac.max_samples, ac.tolerance};
     VRT_HIP(c, vrt::launch::adaptive_counts(q, c->stream));
     uint32_t active = 0;

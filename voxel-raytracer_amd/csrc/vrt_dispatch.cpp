@@ -35,17 +35,13 @@ SchedState *sched_state(vrt_ctx *c, hipStream_t s, int width, int n_rows, int ro
             if (!slot || st.last_use < slot->last_use) slot = &st;
         // the recycled buffers may still be read by launches in flight on the old stream
         if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-        (void)hipFree(slot->d_cost);
-        (void)hipFree(slot->d_order);
-        *slot = SchedState{};
+        *slot = SchedState{};   // frees them
     }
     // whole groups of ticks; the words past the last tile are never written and must read as zero
     const size_t cost_bytes = (size_t)n_groups * vrt::kGroupTiles * sizeof(uint32_t);
-    if (hipMalloc((void **)&slot->d_cost, cost_bytes) != hipSuccess ||
-        hipMalloc((void **)&slot->d_order, ((size_t)n_groups + 1) * sizeof(uint32_t)) != hipSuccess ||   // + KArgs::split_count
+    if (slot->d_cost.reserve(cost_bytes) != hipSuccess ||
+        slot->d_order.reserve(((size_t)n_groups + 1) * sizeof(uint32_t)) != hipSuccess ||   // + KArgs::split_count
         hipMemsetAsync(slot->d_cost, 0, cost_bytes, s) != hipSuccess) {
-        (void)hipFree(slot->d_cost);
-        (void)hipFree(slot->d_order);
         *slot = SchedState{};  // an empty state matches no launch and is the first to be recycled
         (void)hipGetLastError();
         return nullptr;
@@ -117,13 +113,7 @@ vrt_ctx::RayTable *ray_table(vrt_ctx *c, const float *inv_proj, int W, int H) {
     t->width = W; t->height = H; t->z = z; t->ok = false;
     t->last_use = ++c->ray_tick;
     if (!ok) return nullptr;
-    if (tab.size() > t->capacity) {
-        float *fresh = nullptr;
-        if (hipMalloc((void **)&fresh, tab.size() * sizeof(float)) != hipSuccess) return nullptr;
-        if (t->d_tab) (void)hipFree(t->d_tab);
-        t->d_tab = fresh;
-        t->capacity = tab.size();
-    }
+    if (t->d_tab.reserve(tab.size() * sizeof(float)) != hipSuccess) return nullptr;
     if (hipMemcpy(t->d_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     t->fit_ok = miss_table_fit(tab.data(), z, W, H, t->fit);
     t->ok = true;
@@ -152,12 +142,7 @@ bool occupancy(vrt_ctx *c) {
     const size_t bytes = boxes.size() * sizeof(int);
     // launches in flight may read the old list (through the masks built from it: they read the masks only)
     if (hipDeviceSynchronize() != hipSuccess) return false;
-    if (bytes > o.capacity) {
-        (void)hipFree(o.d_boxes);
-        o.d_boxes = nullptr; o.capacity = 0;
-        if (hipMalloc((void **)&o.d_boxes, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-        o.capacity = bytes;
-    }
+    if (o.d_boxes.reserve(bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (bytes && hipMemcpy(o.d_boxes, boxes.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return false; }
     o.n_boxes = boxes.size() / 6;
     o.ok = true;
@@ -210,7 +195,7 @@ const uint8_t *miss_mask(vrt_ctx *c, const vrt::View &w, const vrt_ctx::RayTable
             hit->shared = true;
         }
         stamp = hit->stamp;
-        return reinterpret_cast<const uint8_t *>(hit->d_mask);
+        return reinterpret_cast<const uint8_t *>(hit->d_mask.get());
     }
     if (!hit) {   // first sight: note the key, build nothing (the slot's buffer, which launches in flight may read, stays as it is)
         vrt_ctx::MissMask *m;
@@ -240,18 +225,14 @@ const uint8_t *miss_mask(vrt_ctx *c, const vrt::View &w, const vrt_ctx::RayTable
     if (!occupancy(c)) return nullptr;
     if (m->d_mask && (m->shared || m->stream != s) && hipDeviceSynchronize() != hipSuccess) return nullptr;
     const size_t bytes = 8 + (size_t)vp.tiles_x * (size_t)vp.tiles_y;
-    if (bytes > m->capacity) {
+    if (bytes > m->d_mask.bytes()) {
         if (m->d_mask && hipDeviceSynchronize() != hipSuccess) return nullptr;   // any stream may still read the old buffer
-        uint32_t *fresh = nullptr;
-        if (hipMalloc((void **)&fresh, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        (void)hipFree(m->d_mask);
-        m->d_mask = fresh;
-        m->capacity = bytes;
-        m->stamp = 0;   // cleared below
+        if (m->d_mask.reserve(bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        m->stamp = 0;   // a new block: cleared below
     }
     if (m->stamp == 255u) m->stamp = 0u;   // wrapped: bytes of every stamp may be left, cleared below
     m->stamp = (uint8_t)(m->stamp + 1u);
-    if (m->stamp == 1u && hipMemsetAsync(m->d_mask, 0, m->capacity, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // new or wrapped
+    if (m->stamp == 1u && hipMemsetAsync(m->d_mask, 0, m->d_mask.bytes(), s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // new or wrapped
     if (vrt::launch::miss_mask(vp, c->occ.d_boxes, (uint32_t)c->occ.n_boxes, m->d_mask, m->stamp, s) != hipSuccess ||
         hipEventRecord(m->built, s) != hipSuccess) {
         (void)hipGetLastError();
@@ -261,7 +242,7 @@ const uint8_t *miss_mask(vrt_ctx *c, const vrt::View &w, const vrt_ctx::RayTable
     m->shared = false;
     m->ok = true;
     stamp = m->stamp;
-    return reinterpret_cast<const uint8_t *>(m->d_mask);
+    return reinterpret_cast<const uint8_t *>(m->d_mask.get());
 }
 
 namespace {
@@ -431,14 +412,11 @@ int stream_seeds(vrt_ctx *c, hipStream_t s, size_t need, vrt::KArgs &a) {
     }
     if (need > sb->tiles) {
         VRT_HIP(c, hipStreamSynchronize(s));
-        uint32_t *fresh = nullptr;
-        VRT_HIP(c, hipMalloc((void **)&fresh, need * vrt::kSeedPlanesHost * 64 * sizeof(uint32_t)));
-        if (sb->d) (void)hipFree(sb->d);
-        sb->d = fresh;
+        VRT_HIP(c, sb->d.reserve(need * vrt::kSeedPlanesHost * 64 * sizeof(uint32_t)));
         sb->tiles = need;
     }
     sb->last_use = ++c->seed_tick;
-    a.defer_rec = reinterpret_cast<float *>(sb->d);
+    a.defer_rec = reinterpret_cast<float *>(sb->d.get());
     return VRT_OK;
 }
 
@@ -609,13 +587,10 @@ int vrt_dispatch_async(vrt_ctx *c, int width, int height, int mode, uint8_t *out
         VRT_HIP(c, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
         VRT_HIP(c, hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
     }
-    if (px > ln.pixels) {
-        void *a = nullptr, *b = nullptr;
-        VRT_HIP(c, hipMalloc(&a, px * 4));
-        if (hipMalloc(&b, px * 8) != hipSuccess) { (void)hipFree(a); return vrt_fail(c, VRT_E_HIP, "vrt_dispatch_async: hipMalloc"); }
-        (void)hipFree(ln.d_rgba);
-        (void)hipFree(ln.d_id);
-        ln.d_rgba = a; ln.d_id = b; ln.pixels = px;
+    if (px > ln.pixels) {   // nothing to wait for: vrt_dispatch_wait above has seen the lane's last copies land
+        VRT_HIP(c, ln.d_rgba.reserve(px * 4));
+        VRT_HIP(c, ln.d_id.reserve(px * 8));
+        ln.pixels = px;
     }
     r = enqueue(c, width, height, 0, height, height, 0, 0, mode, out_rgba8 ? ln.d_rgba : nullptr, out_id_dist ? ln.d_id : nullptr, ln.stream);
     if (r) return r;

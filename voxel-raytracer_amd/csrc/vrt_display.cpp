@@ -40,15 +40,9 @@ int scheduled_display(vrt_ctx *c, int width, int height, int key, hipStream_t s,
 // vrt_denoise_hdr_host's float images on the device: in and out, 12 bytes per pixel each; grow by ensure_scratch's rule, never shrink
 int ensure_hdr_scratch(vrt_ctx *c, size_t px) {
     if (px <= c->hdr_scratch_pixels) return VRT_OK;
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_hdr_in) VRT_HIP(c, hipFree(c->d_hdr_in));
-    if (c->d_hdr_out) VRT_HIP(c, hipFree(c->d_hdr_out));
-    c->d_hdr_in = c->d_hdr_out = nullptr;
-    c->hdr_scratch_pixels = 0;
-    VRT_HIP(c, hipMalloc(&c->d_hdr_in, px * 12));
-    VRT_HIP(c, hipMalloc(&c->d_hdr_out, px * 12));
-    c->hdr_scratch_pixels = px;
-    return VRT_OK;
+    const int r = reserve_synced(c, {{&c->d_hdr_in, px * 12}, {&c->d_hdr_out, px * 12}});
+    if (!r) c->hdr_scratch_pixels = px;
+    return r;
 }
 
 }  // namespace

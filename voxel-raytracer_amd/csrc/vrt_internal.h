@@ -1,8 +1,13 @@
-// vrt_internal.h -- what the translation units of libvrt_hip.so share: the context behind `vrt_ctx`, the kernel variant
-// table, error plumbing and the few helpers that cross files. Host code only; nothing here is exported.
+// vrt_internal.h -- what the translation units of libvrt_hip.so share: the context behind `vrt_ctx` (every device buffer it keeps
+// is a DevBuf member of it or of its nested structs: `delete c` frees them all), the kernel variant table, error plumbing and the
+// few helpers that cross files. Host code only; nothing here is exported.
 //
+//   vrt_devbuf.h       DevBuf<T>, the owner of every device buffer below: reserve() is the one way to grow, the destructor the one
+//                      free. A new buffer is a DevBuf member, its owner waits for what may still use the old block in front of
+//                      reserve(), and vrt_destroy gets no line for it
 //   vrt_scene.cpp      create / destroy, uniforms, camera, uploads, the layouts on the device (ensure_analysis); what every launch
-//                      takes from them: the scene and light blocks of KArgs, the base variant, the profiling slot
+//                      takes from them: the scene and light blocks of KArgs, the base variant, the profiling slot; growth of the
+//                      buffers the context's stream orders (reserve_synced: scratch images, staging, the accumulation's groups)
 //   vrt_dispatch.cpp   enqueue(), a frame launch in steps: views, variant, frame block of KArgs, feedback scheduling, the form of the
 //                      full path tracer; the caches behind them (ray tables, miss masks, seed buffers); the vrt_dispatch* entry points
 //   vrt_display.cpp    the display pass and the fused frame call
@@ -13,17 +18,20 @@
 //                      and the launches of one step of it (launch_accum_step, called by enqueue())
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
-//   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts)
+//   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts; its shard and band
+//                      images are DevBufs too)
 #pragma once
 #include "../../include/vrt.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "vrt_args.h"
+#include "vrt_devbuf.h"
 #include "vrt_layout.h"
 #include "vrt_miss.h"
 
@@ -63,7 +71,7 @@ struct SchedState {
     hipStream_t stream = nullptr;
     int width = 0, n_rows = 0, row0 = 0, row_stride = 0, tile_rows = 0, mode = 0;
     uint32_t n_tiles = 0, n_groups = 0;
-    uint32_t *d_cost = nullptr, *d_order = nullptr;
+    DevBuf<uint32_t> d_cost, d_order;
     bool valid = false;        // d_order holds an order
     float cam[6] = {0, 0, 0, 0, 0, 0};  // eye and viewing direction of the launch the order was measured on (trace states)
     uint64_t launches = 0;
@@ -74,8 +82,7 @@ struct vrt_ctx {
     int device = 0;
     int n_cus = 256;
     hipStream_t stream = nullptr;
-    uint2 *d_nodes = nullptr;
-    size_t nodes_capacity = 0;
+    DevBuf<uint2> d_nodes;    // the record array: bytes() is its capacity, info.n_records what it holds
     bool have_scene = false;
     bool have_camera = false;
     vrt_scene_info info{};
@@ -85,19 +92,15 @@ struct vrt_ctx {
     int variant = 0;
     int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL = denoise::Args::rows_path: 0 each wave the cheaper walk; 2, 3: one walk forced
     // scratch outputs for the host-buffer dispatch
-    void *d_rgba = nullptr;
-    void *d_id = nullptr;
-    void *d_shown = nullptr;
+    DevBuf<void> d_rgba, d_id, d_shown;
     size_t scratch_pixels = 0;
     // ... and the two float images of vrt_denoise_hdr_host (vrt_display.cpp)
-    void *d_hdr_in = nullptr, *d_hdr_out = nullptr;
+    DevBuf<void> d_hdr_in, d_hdr_out;
     size_t hdr_scratch_pixels = 0;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
-    void *d_query = nullptr;
-    size_t query_bytes = 0;
+    DevBuf<void> d_query;
     // device buffers behind vrt_shade_rays (vrt_rays.cpp)
-    void *d_rays = nullptr;
-    size_t rays_bytes = 0;
+    DevBuf<void> d_rays;
     // edits collected between vrt_patch_begin and vrt_patch_end: applied to the host structures at once, sent to the
     // device together
     struct PatchBatch {
@@ -112,7 +115,7 @@ struct vrt_ctx {
     // vrt_dispatch_async: two lanes, each a stream + device images + "the copies have landed" event
     struct AsyncLane {
         hipStream_t stream = nullptr;
-        void *d_rgba = nullptr, *d_id = nullptr;
+        DevBuf<void> d_rgba, d_id;
         size_t pixels = 0;
         hipEvent_t done = nullptr;
         bool busy = false;
@@ -135,8 +138,8 @@ struct vrt_ctx {
     // wide layout (vrt_layout.h), rebuilt whenever the tree or the world bounds change
     bool wide_ok = false;
     vrt::WideTree wide;
-    uint2 *d_cells = nullptr;     // cells_capacity cells in the layout of vrt_layout.h, then as many in the v4 form (cells4)
-    uint32_t *d_roots = nullptr;  // 16 words: record and wide node of each wide root (vrt_common.hip.h KArgs::root_table)
+    DevBuf<uint2> d_cells;        // cells_capacity cells in the layout of vrt_layout.h, then as many in the v4 form (cells4)
+    DevBuf<uint32_t> d_roots;     // 16 words: record and wide node of each wide root (vrt_common.hip.h KArgs::root_table)
     size_t cells_capacity = 0;
     // feedback scheduling of the default kernel (see SchedState)
     int sched_period = 16;                   // every n-th launch of a shape measures its tiles; 0 = off
@@ -149,10 +152,9 @@ struct vrt_ctx {
         int width = 0, height = 0;
         bool ok = false;            // the projection has the separable shape and the tables are on the device
         float z = 0.0f;
-        float *d_tab = nullptr;     // width floats (x per column) then height floats (y per row)
+        DevBuf<float> d_tab;        // width floats (x per column) then height floats (y per row)
         bool fit_ok = false;        // `fit` holds the miss-tile build's part of the tables (vrt_raygen.cpp miss_table_fit)
         vrt::miss::TableFit fit{};
-        size_t capacity = 0;        // floats
         uint64_t last_use = 0;
     };
     std::vector<RayTable> ray_tables;
@@ -167,8 +169,8 @@ struct vrt_ctx {
         uint64_t seen_gen = ~0ull;         // the tree generation and bounds mask requests have seen, and for how many requests
         int seen_wmin[3] = {0, 0, 0}, seen_wmax[3] = {0, 0, 0};
         uint64_t stable = 0;
-        int *d_boxes = nullptr;            // n_boxes vrt::miss::Box
-        size_t capacity = 0, n_boxes = 0;
+        DevBuf<int> d_boxes;               // n_boxes vrt::miss::Box
+        size_t n_boxes = 0;
     };
     Occupancy occ;
     struct MissMask {
@@ -178,8 +180,7 @@ struct vrt_ctx {
         int wmin[3] = {0, 0, 0}, wmax[3] = {0, 0, 0};
         bool pending = false;              // the key has been seen once: the next sight builds the mask
         bool ok = false;                   // d_mask holds this view's mask (or is being built on `stream`)
-        uint32_t *d_mask = nullptr;        // View::miss: the header word, a spare word, then the tile bytes
-        size_t capacity = 0;               // bytes
+        DevBuf<uint32_t> d_mask;           // View::miss: the header word, a spare word, then the tile bytes
         uint8_t stamp = 0;                 // of the last build: View::miss_stamp
         bool shared = false;               // a launch on another stream than `stream` has read it since the build
         hipStream_t stream = nullptr;
@@ -194,7 +195,7 @@ struct vrt_ctx {
     int two_pass_form = 6;                       // 6 (default): both stages in one kernel built for six waves per SIMD; 5, 7: for five, seven; 1: two kernels
     bool scene_opaque = false;                   // every leaf has alpha 0, or alpha 255 and a refraction byte that is a surface (not 0 / 85)
     bool scene_opaque_valid = false;
-    struct SeedBuffer { hipStream_t stream = nullptr; uint32_t *d = nullptr; size_t tiles = 0; uint64_t last_use = 0; };
+    struct SeedBuffer { hipStream_t stream = nullptr; DevBuf<uint32_t> d; size_t tiles = 0; uint64_t last_use = 0; };
     std::vector<SeedBuffer> seeds;               // one per stream: launches on different streams may overlap
     uint64_t seed_tick = 0;
     bool tight_root_on = true;                   // VRT_OPT_EMPTY_OCTANTS 2 = on without the tighter root
@@ -217,26 +218,25 @@ struct vrt_ctx {
         float lens[2] = {0.0f, 1.0f};
         vrt_params params{};
         uint64_t tree_gen = 0;
-        uint32_t *d_sums = nullptr;              // 4 words per pixel
-        uint32_t *d_pass1 = nullptr;             // pass 1's rgba8 (opaque path), or the unjittered frame's (`frame`)
-        int2 *d_id = nullptr;                    // the frame's (voxel ID, dist)
-        uint32_t *d_seed = nullptr;              // pass 1's seeds, tile-major (kSeedPlanesHost words per pixel)
-        size_t pixels = 0, seed_tiles = 0;       // capacities
-        uint32_t *d_resolved = nullptr;          // vrt_accum_resolve_device without d_rgba8 but with d_shown_rgba8
+        DevBuf<uint32_t> d_sums;                 // 4 words per pixel
+        DevBuf<uint32_t> d_pass1;                // pass 1's rgba8 (opaque path), or the unjittered frame's (`frame`)
+        DevBuf<int2> d_id;                       // the frame's (voxel ID, dist)
+        DevBuf<uint32_t> d_seed;                 // pass 1's seeds, tile-major (kSeedPlanesHost words per pixel)
+        size_t pixels = 0, seed_tiles = 0;       // what the four above were last sized for
         hipEvent_t added = nullptr, read = nullptr;   // ordering against a caller's stream in vrt_accum_resolve_device
         // vrt_accum_begin_adaptive: the stopping rule; per pixel, the count in the fourth word of d_sums and Q in d_sq
         bool adaptive = false;
         uint32_t min_samples = 0, max_samples = 0, tolerance = 0;
-        uint64_t *d_sq = nullptr;
-        uint32_t *d_tiles = nullptr;             // the round's tile list [tile_cap], then its count and vrt_accum_counts' count
-        size_t sq_pixels = 0, tile_cap = 0;      // capacities
+        DevBuf<uint64_t> d_sq;
+        DevBuf<uint32_t> d_tiles;                // the round's tile list [tile_cap], then its count and vrt_accum_counts' count
+        size_t sq_pixels = 0, tile_cap = 0;      // what the two above were last sized for
         // vrt_accum_keep_hdr as it stood at the begin: the float64 sums of the samples' float colours beside everything above
         bool hdr = false;
-        double *d_hsum = nullptr;                // 3 doubles per pixel
-        float *d_hframe = nullptr;               // 3 floats per pixel: the corner frame's (or pass 1's) float colour
-        float *d_hrgb = nullptr;                 // vrt_accum_resolve_hdr's float image on its way to the host
-        float *d_hmean = nullptr;                // vrt_accum_resolve_hdr_shown*: the float mean the display pass reads, made at the first such call
-        size_t hdr_pixels = 0, hrgb_pixels = 0, hmean_pixels = 0;  // capacities
+        DevBuf<double> d_hsum;                   // 3 doubles per pixel
+        DevBuf<float> d_hframe;                  // 3 floats per pixel: the corner frame's (or pass 1's) float colour
+        size_t hdr_pixels = 0;                   // what the two above were last sized for
+        DevBuf<float> d_hrgb;                    // vrt_accum_resolve_hdr's float image on its way to the host
+        DevBuf<float> d_hmean;                   // vrt_accum_resolve_hdr_shown*: the float mean the display pass reads, made at the first such call
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
@@ -267,6 +267,11 @@ int upload_cells(vrt_ctx *c, size_t from, size_t n);
 int upload_roots(vrt_ctx *c);
 uint32_t dim_of_texels(size_t texels);   // src/main.cpp:266-268
 int check_frame(vrt_ctx *c, int width, int height);
+// Growth of buffers that only work ordered by the context's stream touches: waits for that stream, then reserves every
+// {buffer, bytes} of `wants`. The caller has found one of them too small, and sets the count they share once this has succeeded.
+struct Want { DevMem *buf; size_t bytes; };
+int reserve_synced(vrt_ctx *c, std::initializer_list<Want> wants);
+int reserve_staging(vrt_ctx *c, DevMem &buf, size_t bytes);   // ... one staging buffer (queries, ray batches), grown to 1.5 x bytes
 int ensure_scratch(vrt_ctx *c, size_t px);   // device images behind the host-buffer entry points
 // a vrt_tonemap the header defines (NULL: VRT_TONEMAP_CLAMP, exposure 1), else VRT_E_INVALID in the name of `what`
 int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm);

@@ -6,6 +6,7 @@
 // through xGMI peer mappings (VRT_DELIVER_PEER_STORE) or one pull kernel per image on the assembling device
 // (VRT_DELIVER_GATHER). The one-process-per-GPU form with RCCL lives in voxel-raytracer_amd/sharding.py (bench.py).
 #include "../../include/vrt.h"
+#include "vrt_devbuf.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,10 +38,12 @@ struct vrt_multi {
     std::vector<int> devices;
     std::vector<vrt_ctx *> ctx;
     std::vector<hipEvent_t> traced;     // per device: its share of the current frame has been enqueued / finished
-    std::vector<void *> shard_rgba, shard_id;   // VRT_DELIVER_GATHER: per-device compact buffers
-    std::vector<size_t> shard_pixels;
-    std::vector<void *> band_rgba, band_id, band_shown;   // vrt_multi_dispatch_frame: per-device band + halo (traced, ids, displayed)
-    std::vector<size_t> band_pixels;
+    struct Images {                     // one device's images of `pixels` pixels, grown together (reserve_images)
+        DevBuf<char> rgba, id, shown;
+        size_t pixels = 0;
+    };
+    std::vector<Images> shard;          // VRT_DELIVER_GATHER: per-device compact buffers (rgba, id)
+    std::vector<Images> band;           // vrt_multi_dispatch_frame: per-device band + halo (traced, ids, displayed)
     hipEvent_t frame_free = nullptr;    // device 0: the consumers of the previous frame have been enqueued before this point
     std::string err;
 };
@@ -64,6 +67,18 @@ int mfail(vrt_multi *m, int code, const std::string &msg) {
         hipError_t e_ = (call);                         \
         if (e_ != hipSuccess) return VRT_E_HIP;         \
     } while (0)
+
+// im's images for px pixels (the displayed one only for a band), once the device's stream s has drained: launches in flight there
+// still write the old ones
+hipError_t reserve_images(vrt_multi::Images &im, size_t px, bool shown, hipStream_t s) {
+    if (px <= im.pixels) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = im.rgba.reserve(px * 4);
+    if (e == hipSuccess) e = im.id.reserve(px * 8);
+    if (e == hipSuccess && shown) e = im.shown.reserve(px * 4);
+    if (e == hipSuccess) im.pixels = px;
+    return e;
+}
 
 }  // namespace
 
@@ -178,13 +193,11 @@ void vrt_destroy_multi(vrt_multi *m) {
         if (!m->ctx[i]) continue;
         (void)hipSetDevice(m->devices[i]);
         (void)hipStreamSynchronize((hipStream_t)vrt_stream(m->ctx[i]));
-        if (i < m->shard_rgba.size()) { (void)hipFree(m->shard_rgba[i]); (void)hipFree(m->shard_id[i]); }
-        if (i < m->band_rgba.size()) { (void)hipFree(m->band_rgba[i]); (void)hipFree(m->band_id[i]); (void)hipFree(m->band_shown[i]); }
         if (i < m->traced.size() && m->traced[i]) (void)hipEventDestroy(m->traced[i]);
     }
     if (m->frame_free) { (void)hipSetDevice(m->devices[0]); (void)hipEventDestroy(m->frame_free); }
     for (vrt_ctx *c : m->ctx) vrt_destroy(c);
-    delete m;
+    delete m;   // the shard and band images go here: every stream that touched them has drained above
 }
 
 int vrt_create_multi(int n_devices, const int *device_ids, vrt_multi **out) {
@@ -199,9 +212,7 @@ int vrt_create_multi(int n_devices, const int *device_ids, vrt_multi **out) {
     m->devices.assign(device_ids, device_ids + n_devices);
     m->ctx.assign((size_t)n_devices, nullptr);
     m->traced.assign((size_t)n_devices, nullptr);
-    m->shard_rgba.assign((size_t)n_devices, nullptr);
-    m->shard_id.assign((size_t)n_devices, nullptr);
-    m->shard_pixels.assign((size_t)n_devices, 0);
+    m->shard.resize((size_t)n_devices);
     for (int i = 0; i < n_devices; ++i) {
         const int r = vrt_create(device_ids[i], &m->ctx[(size_t)i]);
         if (r != VRT_OK) {
@@ -316,18 +327,10 @@ int vrt_multi_dispatch(vrt_multi *m, int width, int height, int tile_rows, int m
         } else {
             const int rows = vrt_shard_rows(height, tile_rows, i, n);
             const size_t px = (size_t)(rows > 0 ? rows : 0) * (size_t)width;
-            if (px > m->shard_pixels[(size_t)i]) {
-                VRTM_HIP(m, hipStreamSynchronize(s));
-                (void)hipFree(m->shard_rgba[(size_t)i]);
-                (void)hipFree(m->shard_id[(size_t)i]);
-                m->shard_rgba[(size_t)i] = m->shard_id[(size_t)i] = nullptr;
-                m->shard_pixels[(size_t)i] = 0;
-                VRTM_HIP(m, hipMalloc(&m->shard_rgba[(size_t)i], px * 4));
-                VRTM_HIP(m, hipMalloc(&m->shard_id[(size_t)i], px * 8));
-                m->shard_pixels[(size_t)i] = px;
-            }
-            r = rows > 0 ? vrt_dispatch_shard(c, width, height, tile_rows, i, n, mode, d_rgba8 ? m->shard_rgba[(size_t)i] : nullptr,
-                                              d_id_dist ? m->shard_id[(size_t)i] : nullptr, nullptr)
+            vrt_multi::Images &sh = m->shard[(size_t)i];
+            VRTM_HIP(m, reserve_images(sh, px, false, s));
+            r = rows > 0 ? vrt_dispatch_shard(c, width, height, tile_rows, i, n, mode, d_rgba8 ? sh.rgba.get() : nullptr,
+                                              d_id_dist ? sh.id.get() : nullptr, nullptr)
                          : VRT_OK;
         }
         if (r) return mfail(m, r, std::string("device ") + std::to_string(m->devices[(size_t)i]) + ": " + vrt_last_error(c));
@@ -343,10 +346,10 @@ int vrt_multi_dispatch(vrt_multi *m, int width, int height, int tile_rows, int m
             const size_t px = (size_t)rows * (size_t)width;
             const unsigned blocks = (unsigned)((px + 255) / 256 < 4096 ? (px + 255) / 256 : 4096);
             if (d_rgba8)
-                hipLaunchKernelGGL(unshard_kernel, dim3(blocks), dim3(256), 0, s0, (const uint32_t *)m->shard_rgba[(size_t)i], (uint32_t *)d_rgba8,
+                hipLaunchKernelGGL(unshard_kernel, dim3(blocks), dim3(256), 0, s0, (const uint32_t *)m->shard[(size_t)i].rgba.get(), (uint32_t *)d_rgba8,
                                    width, rows, tile_rows, i * tile_rows, tile_rows * n, 1);
             if (d_id_dist)
-                hipLaunchKernelGGL(unshard_kernel, dim3(blocks), dim3(256), 0, s0, (const uint32_t *)m->shard_id[(size_t)i], (uint32_t *)d_id_dist,
+                hipLaunchKernelGGL(unshard_kernel, dim3(blocks), dim3(256), 0, s0, (const uint32_t *)m->shard[(size_t)i].id.get(), (uint32_t *)d_id_dist,
                                    width, rows, tile_rows, i * tile_rows, tile_rows * n, 2);
             VRTM_HIP(m, hipGetLastError());
         }
@@ -363,10 +366,7 @@ int vrt_multi_dispatch_frame(vrt_multi *m, int width, int height, int mode, void
     if (width < 1 || height < 1) return mfail(m, VRT_E_INVALID, "vrt_multi_dispatch_frame: bad frame shape");
     constexpr int kHalo = 20;   // quad.frag's largest radius
     const int n = (int)m->ctx.size();
-    if (m->band_pixels.size() != (size_t)n) {
-        m->band_rgba.assign((size_t)n, nullptr); m->band_id.assign((size_t)n, nullptr); m->band_shown.assign((size_t)n, nullptr);
-        m->band_pixels.assign((size_t)n, 0);
-    }
+    if (m->band.size() != (size_t)n) m->band.resize((size_t)n);
     hipStream_t s0 = (hipStream_t)vrt_stream(m->ctx[0]);
     VRTM_HIP(m, hipSetDevice(m->devices[0]));
     VRTM_HIP(m, hipEventRecord(m->frame_free, s0));
@@ -382,18 +382,10 @@ int vrt_multi_dispatch_frame(vrt_multi *m, int width, int height, int mode, void
         if (b1 > b0) {
             const int h0 = b0 - kHalo > 0 ? b0 - kHalo : 0, h1 = b1 + kHalo < height ? b1 + kHalo : height;
             const size_t px = (size_t)(h1 - h0) * (size_t)width;
-            if (px > m->band_pixels[(size_t)i]) {
-                VRTM_HIP(m, hipStreamSynchronize(s));
-                (void)hipFree(m->band_rgba[(size_t)i]); (void)hipFree(m->band_id[(size_t)i]); (void)hipFree(m->band_shown[(size_t)i]);
-                m->band_rgba[(size_t)i] = m->band_id[(size_t)i] = m->band_shown[(size_t)i] = nullptr;
-                m->band_pixels[(size_t)i] = 0;
-                VRTM_HIP(m, hipMalloc(&m->band_rgba[(size_t)i], px * 4));
-                VRTM_HIP(m, hipMalloc(&m->band_id[(size_t)i], px * 8));
-                VRTM_HIP(m, hipMalloc(&m->band_shown[(size_t)i], px * 4));
-                m->band_pixels[(size_t)i] = px;
-            }
+            vrt_multi::Images &bd = m->band[(size_t)i];
+            VRTM_HIP(m, reserve_images(bd, px, true, s));
             // vrt_dispatch_rows addresses its images by frame row: the base is shifted up by h0 rows
-            char *rg = (char *)m->band_rgba[(size_t)i], *id = (char *)m->band_id[(size_t)i], *sh = (char *)m->band_shown[(size_t)i];
+            char *rg = bd.rgba, *id = bd.id, *sh = bd.shown;
             int r = vrt_dispatch_rows(c, width, height, h0, h1, mode, rg - (size_t)h0 * (size_t)width * 4, id - (size_t)h0 * (size_t)width * 8, nullptr);
             if (!r) r = vrt_denoise(c, width, h1 - h0, rg, id, sh, nullptr);
             if (r) return mfail(m, r, std::string("device ") + std::to_string(m->devices[(size_t)i]) + ": " + vrt_last_error(c));

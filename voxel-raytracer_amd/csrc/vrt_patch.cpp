@@ -60,12 +60,8 @@ int patch_device(vrt_ctx *c) {
     DropSceneOnFailure guard{c};
     VRT_HIP(c, hipDeviceSynchronize());
     const size_t rec_bytes = c->host_records.size() * sizeof(vrt::Record);
-    if (rec_bytes > c->nodes_capacity) {
-        uint2 *fresh = nullptr;
-        VRT_HIP(c, hipMalloc((void **)&fresh, rec_bytes * 2));   // before the old array goes
-        if (c->d_nodes) (void)hipFree(c->d_nodes);
-        c->d_nodes = fresh;
-        c->nodes_capacity = rec_bytes * 2;
+    if (rec_bytes > c->d_nodes.bytes()) {
+        VRT_HIP(c, c->d_nodes.reserve(rec_bytes * 2));   // room for the patches to come
         VRT_HIP(c, hipMemcpy(c->d_nodes, c->host_records.data(), rec_bytes, hipMemcpyHostToDevice));
     } else {
         if (c->host_records.size() > bt.records_before)
@@ -201,13 +197,7 @@ int vrt_compact(vrt_ctx *c) {
     ++c->tree_gen;
     struct Guard { vrt_ctx *c; bool armed = true; ~Guard() { if (armed) { c->have_scene = false; c->analysis_valid = false; } } } guard{c};
     const size_t bytes = c->host_records.size() * sizeof(vrt::Record);
-    if (bytes > c->nodes_capacity) {   // cannot grow, but a context whose array was never sized stays correct
-        uint2 *fresh = nullptr;
-        VRT_HIP(c, hipMalloc((void **)&fresh, bytes));
-        if (c->d_nodes) (void)hipFree(c->d_nodes);
-        c->d_nodes = fresh;
-        c->nodes_capacity = bytes;
-    }
+    VRT_HIP(c, c->d_nodes.reserve(bytes));   // cannot grow, but a context whose array was never sized stays correct
     VRT_HIP(c, hipMemcpy(c->d_nodes, c->host_records.data(), bytes, hipMemcpyHostToDevice));
     c->info.n_records = (uint32_t)c->host_records.size();
     c->uploaded_records = c->host_records.size();

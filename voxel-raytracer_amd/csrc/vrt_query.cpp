@@ -64,19 +64,6 @@ int cast(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const 
     return VRT_OK;
 }
 
-// device buffers behind the host-buffer forms, kept by the context and grown, never shrunk
-int ensure_query_scratch(vrt_ctx *c, size_t bytes) {
-    if (bytes <= c->query_bytes) return VRT_OK;
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_query) VRT_HIP(c, hipFree(c->d_query));
-    c->d_query = nullptr;
-    c->query_bytes = 0;
-    const size_t grown = bytes + bytes / 2;
-    VRT_HIP(c, hipMalloc(&c->d_query, grown));
-    c->query_bytes = grown;
-    return VRT_OK;
-}
-
 inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
 }  // namespace
@@ -91,9 +78,9 @@ int vrt_cast_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride,
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
     const size_t out_bytes = n * sizeof(vrt_ray_hit);
-    r = ensure_query_scratch(c, align256(o_bytes) + align256(d_bytes) + out_bytes);
+    r = reserve_staging(c, c->d_query, align256(o_bytes) + align256(d_bytes) + out_bytes);   // kept by the context: grown, never shrunk
     if (r) return r;
-    char *base = static_cast<char *>(c->d_query);
+    char *base = static_cast<char *>(c->d_query.get());
     float *d_o = reinterpret_cast<float *>(base);
     float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
     auto *d_out = reinterpret_cast<vrt::query::RayHit *>(base + align256(o_bytes) + align256(d_bytes));
@@ -126,9 +113,9 @@ int vrt_find_voxels(vrt_ctx *c, size_t n, const int32_t *coords, uint32_t *out) 
     r = scene_args(c, a);
     if (r) return r;
     const size_t bytes = n * 3 * sizeof(uint32_t);
-    r = ensure_query_scratch(c, 2 * align256(bytes));
+    r = reserve_staging(c, c->d_query, 2 * align256(bytes));
     if (r) return r;
-    char *base = static_cast<char *>(c->d_query);
+    char *base = static_cast<char *>(c->d_query.get());
     vrt::query::PointArgs q;
     q.coords = reinterpret_cast<const int32_t *>(base);
     q.out = reinterpret_cast<uint32_t *>(base + align256(bytes));

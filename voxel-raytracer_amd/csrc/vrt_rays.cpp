@@ -108,19 +108,6 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     return VRT_OK;
 }
 
-// device buffers behind the host form, kept by the context and grown, never shrunk
-int ensure_rays_scratch(vrt_ctx *c, size_t bytes) {
-    if (bytes <= c->rays_bytes) return VRT_OK;
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_rays) VRT_HIP(c, hipFree(c->d_rays));
-    c->d_rays = nullptr;
-    c->rays_bytes = 0;
-    const size_t grown = bytes + bytes / 2;
-    VRT_HIP(c, hipMalloc(&c->d_rays, grown));
-    c->rays_bytes = grown;
-    return VRT_OK;
-}
-
 inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
 }  // namespace
@@ -134,9 +121,9 @@ int vrt_shade_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
     const size_t rgba_bytes = out_rgba8 ? n * 4 : 0, id_bytes = out_id_dist ? n * 8 : 0;
-    r = ensure_rays_scratch(c, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + id_bytes);
+    r = reserve_staging(c, c->d_rays, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + id_bytes);   // kept by the context: grown, never shrunk
     if (r) return r;
-    char *base = static_cast<char *>(c->d_rays);
+    char *base = static_cast<char *>(c->d_rays.get());
     float *d_o = reinterpret_cast<float *>(base);
     float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
     uint32_t *d_rgba = out_rgba8 ? reinterpret_cast<uint32_t *>(base + align256(o_bytes) + align256(d_bytes)) : nullptr;
@@ -169,9 +156,9 @@ int vrt_shade_rays_hdr(vrt_ctx *c, size_t n, const float *origins, int origin_st
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
     const size_t rgba_bytes = out_rgba8 ? n * 4 : 0, id_bytes = out_id_dist ? n * 8 : 0, rgb_bytes = out_rgb ? n * 12 : 0;
-    r = ensure_rays_scratch(c, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + align256(id_bytes) + rgb_bytes);
+    r = reserve_staging(c, c->d_rays, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + align256(id_bytes) + rgb_bytes);
     if (r) return r;
-    char *base = static_cast<char *>(c->d_rays);
+    char *base = static_cast<char *>(c->d_rays.get());
     float *d_o = reinterpret_cast<float *>(base);
     float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
     char *out = base + align256(o_bytes) + align256(d_bytes);

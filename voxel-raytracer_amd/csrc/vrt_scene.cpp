@@ -36,10 +36,7 @@ uint32_t dim_of_texels(size_t texels) {
 // kernels read (vrt::to_cell4), behind it in the same allocation. cells_capacity counts CELLS of one form.
 int reserve_cells(vrt_ctx *c, size_t n_cells) {
     if (n_cells <= c->cells_capacity) return VRT_OK;
-    uint2 *fresh = nullptr;
-    VRT_HIP(c, hipMalloc((void **)&fresh, 2 * n_cells * sizeof(uint2)));   // before the old one goes: a failure leaves the context usable
-    if (c->d_cells) (void)hipFree(c->d_cells);
-    c->d_cells = fresh;
+    VRT_HIP(c, c->d_cells.reserve(2 * n_cells * sizeof(uint2)));   // a failure leaves the context usable
     c->cells_capacity = n_cells;
     return VRT_OK;
 }
@@ -62,7 +59,7 @@ int upload_roots(vrt_ctx *c) {
         t[i] = on ? c->wide.roots[(size_t)i].record : 0xffffffffu;
         t[8 + i] = on ? c->wide.roots[(size_t)i].node : 0u;
     }
-    if (!c->d_roots) VRT_HIP(c, hipMalloc((void **)&c->d_roots, sizeof t));
+    VRT_HIP(c, c->d_roots.reserve(sizeof t));
     VRT_HIP(c, hipMemcpy(c->d_roots, t, sizeof t, hipMemcpyHostToDevice));
     return VRT_OK;
 }
@@ -138,20 +135,22 @@ Variant base_variant(const vrt_ctx *c) {
     return v;
 }
 
+int reserve_synced(vrt_ctx *c, std::initializer_list<Want> wants) {
+    VRT_HIP(c, hipStreamSynchronize(c->stream));   // work in flight there still reads or writes the old blocks
+    for (const Want &w : wants) VRT_HIP(c, w.buf->reserve(w.bytes));
+    return VRT_OK;
+}
+
+int reserve_staging(vrt_ctx *c, DevMem &buf, size_t bytes) {
+    return bytes <= buf.bytes() ? VRT_OK : reserve_synced(c, {{&buf, bytes + bytes / 2}});
+}
+
 // device images behind the host-buffer entry points: rgba8, (id, dist) and the displayed rgba8
 int ensure_scratch(vrt_ctx *c, size_t px) {
     if (px <= c->scratch_pixels) return VRT_OK;
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->d_rgba) VRT_HIP(c, hipFree(c->d_rgba));
-    if (c->d_id) VRT_HIP(c, hipFree(c->d_id));
-    if (c->d_shown) VRT_HIP(c, hipFree(c->d_shown));
-    c->d_rgba = c->d_id = c->d_shown = nullptr;
-    c->scratch_pixels = 0;
-    VRT_HIP(c, hipMalloc(&c->d_rgba, px * 4));
-    VRT_HIP(c, hipMalloc(&c->d_id, px * 8));
-    VRT_HIP(c, hipMalloc(&c->d_shown, px * 4));
-    c->scratch_pixels = px;
-    return VRT_OK;
+    const int r = reserve_synced(c, {{&c->d_rgba, px * 4}, {&c->d_id, px * 8}, {&c->d_shown, px * 4}});
+    if (!r) c->scratch_pixels = px;
+    return r;
 }
 
 int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
@@ -244,51 +243,20 @@ void vrt_destroy(vrt_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_nodes) (void)hipFree(c->d_nodes);
-    if (c->d_cells) (void)hipFree(c->d_cells);
-    if (c->d_roots) (void)hipFree(c->d_roots);
-    if (c->d_rgba) (void)hipFree(c->d_rgba);
-    if (c->d_id) (void)hipFree(c->d_id);
-    if (c->d_shown) (void)hipFree(c->d_shown);
-    if (c->d_hdr_in) (void)hipFree(c->d_hdr_in);
-    if (c->d_hdr_out) (void)hipFree(c->d_hdr_out);
-    if (c->d_query) (void)hipFree(c->d_query);
-    if (c->d_rays) (void)hipFree(c->d_rays);
-    (void)hipFree(c->accum.d_sums);
-    (void)hipFree(c->accum.d_pass1);
-    (void)hipFree(c->accum.d_id);
-    (void)hipFree(c->accum.d_seed);
-    (void)hipFree(c->accum.d_sq);
-    (void)hipFree(c->accum.d_tiles);
-    (void)hipFree(c->accum.d_hsum);
-    (void)hipFree(c->accum.d_hframe);
-    (void)hipFree(c->accum.d_hrgb);
-    (void)hipFree(c->accum.d_hmean);
     if (c->accum.added) (void)hipEventDestroy(c->accum.added);
     if (c->accum.read) (void)hipEventDestroy(c->accum.read);
     if (!c->seeds.empty()) (void)hipDeviceSynchronize();   // their launches may be on the caller's streams
-    for (auto &b : c->seeds) (void)hipFree(b.d);
     if (!c->sched.empty()) (void)hipDeviceSynchronize();  // their launches may be on the caller's streams
-    for (SchedState &st : c->sched) {
-        (void)hipFree(st.d_cost);
-        (void)hipFree(st.d_order);
-    }
     for (auto &ln : c->lane) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); }
-        (void)hipFree(ln.d_rgba);
-        (void)hipFree(ln.d_id);
         if (ln.done) (void)hipEventDestroy(ln.done);
     }
     for (auto &e : c->prof_events) (void)hipEventDestroy(e);
     if (!c->ray_tables.empty() || !c->miss_masks.empty() || c->occ.d_boxes) (void)hipDeviceSynchronize();
-    for (auto &t : c->ray_tables) (void)hipFree(t.d_tab);
-    for (auto &m : c->miss_masks) {
-        (void)hipFree(m.d_mask);
+    for (auto &m : c->miss_masks)
         if (m.built) (void)hipEventDestroy(m.built);
-    }
-    (void)hipFree(c->occ.d_boxes);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // every device buffer is a DevBuf member and goes here, after the waits above
 }
 
 const char *vrt_last_error(const vrt_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -319,13 +287,9 @@ int vrt_upload_octree(vrt_ctx *c, const uint8_t *texels, size_t used_bytes, uint
     if (!vrt::build_layout(texels, used_bytes, lay, err)) return vrt_fail(c, VRT_E_MALFORMED, "vrt_upload_octree: " + err);
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t bytes = lay.records.size() * sizeof(vrt::Record);
-    if (bytes > c->nodes_capacity) {
+    if (bytes > c->d_nodes.bytes()) {
         VRT_HIP(c, hipDeviceSynchronize());   // dispatches still reading the old array, on whatever stream
-        uint2 *fresh = nullptr;
-        VRT_HIP(c, hipMalloc((void **)&fresh, bytes));   // before the old array goes: a failure leaves the context as it was
-        if (c->d_nodes) (void)hipFree(c->d_nodes);
-        c->d_nodes = fresh;
-        c->nodes_capacity = bytes;
+        VRT_HIP(c, c->d_nodes.reserve(bytes));   // a failure leaves the context as it was
     }
     // after every dispatch still reading the old tree, on whatever stream the caller enqueued it (uploads are rare:
     // a device-wide wait is cheaper than a contract about foreign streams); synchronous so `lay` may die
@@ -387,13 +351,9 @@ int vrt_upload_records(vrt_ctx *c, const uint32_t *records, size_t n_records, ui
     }
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t bytes = n_records * sizeof(vrt::Record);
-    if (bytes > c->nodes_capacity) {
+    if (bytes > c->d_nodes.bytes()) {
         VRT_HIP(c, hipDeviceSynchronize());   // dispatches still reading the old array, on whatever stream
-        uint2 *fresh = nullptr;
-        VRT_HIP(c, hipMalloc((void **)&fresh, bytes));   // before the old array goes: a failure leaves the context as it was
-        if (c->d_nodes) (void)hipFree(c->d_nodes);
-        c->d_nodes = fresh;
-        c->nodes_capacity = bytes;
+        VRT_HIP(c, c->d_nodes.reserve(bytes));   // a failure leaves the context as it was
     }
     VRT_HIP(c, hipDeviceSynchronize());  // see vrt_upload_octree
     VRT_HIP(c, hipMemcpyAsync(c->d_nodes, recs.data(), bytes, hipMemcpyHostToDevice, c->stream));
