@@ -285,6 +285,35 @@ int vrt_accum_resolve_device(vrt_ctx *ctx, void *d_rgba8, void *d_id_dist, void 
  * Sample 0 is therefore the frame, and aperture 0 reproduces the lens-free accumulations byte for byte. */
 int vrt_set_lens(vrt_ctx *ctx, float aperture, float focus_distance);
 
+/* Path depth: multi-bounce diffuse paths. The shader declares BOUNCES (comp:8) but a ray of depth >= 1 that hits an opaque
+ * surface adds the ambient term and ends (comp:590-594): its light transport is one cosine-weighted bounce whatever the constant
+ * says. vrt_set_path_depth sets the depth D of the samples of VRT_MODE_FULL, an integer in 1..VRT_MAX_PATH_DEPTH, default 1;
+ * VRT_E_INVALID outside that range (the previous depth still holds). It is context state, like the uniforms.
+ *
+ * The rule. Inside pathTrace's loop only the opaque, non-emissive branch (comp:584-616) changes. A ray of depth d at such a hit:
+ *   d == 0       unchanged: the direct term through notInShadow, then the bounce ray of depth 1.
+ *   1 <= d < D   an inner vertex. It takes the depth-0 operations verbatim, in this order:
+ *                  lit = notInShadow(hitPoint + normal * 2e-3, lightDir);
+ *                  finalColor += globalLight.rgb * lit * ndotl * surfaceColor.rgb * transmittedColor.rgb * weight / PI;
+ *                  two rand() draws; cosineSampleHemisphere(normal, r);
+ *                  a new ray from hitPoint + normal * 1e-1 with rayIOF n1, the same weight, tint transmittedColor * surfaceColor,
+ *                  distanceInMedium 0, the last voxel as its medium, depth d + 1.
+ *                It adds no ambient term.
+ *   d == D       the shader's terminal branch: the ambient term max(1 - exp(-distanceInMedium / 512), 0.01), then `continue`.
+ * Nothing else moves: a miss at depth > 0 adds sky * sunIntensity / PI; an emissive hit at depth > 0 adds emission / PI and ends
+ * the path; translucent surfaces are glass only at depth <= 0 and diffuse below it, so a bounce chain is linear and never pushes;
+ * (voxel ID, dist) come from depth 0 only; the random numbers come from the pixel's one initRNG stream, in the order the LIFO
+ * stack pops the rays. At D == 1 the middle case is empty and the rule is the shader.
+ *
+ * Who honours it: the samples of VRT_MODE_FULL in the progressive accumulation (vrt_accum_add in every form: corner, jitter, lens,
+ * adaptive, HDR) and in ray batches (vrt_shade_rays, _device, _hdr, _hdr_device). The depth is one of the inputs of an accumulation
+ * of VRT_MODE_FULL: a change restarts the sums at `first`, the same value set again changes nothing. The primary modes ignore it,
+ * their accumulations included (no restart). vrt_dispatch*
+ * frames (views, shards and vrt_multi included) stay the reference's shader at any setting -- so at D > 1 sample 0 of an
+ * unjittered accumulation is no longer the frame. */
+#define VRT_MAX_PATH_DEPTH 8
+int vrt_set_path_depth(vrt_ctx *ctx, int depth);
+
 /* Adaptive accumulation: stop sampling pixels whose mean has converged. vrt_accum_begin_adaptive is vrt_accum_begin_ex (same
  * modes, VRT_ACCUM_JITTER, the lens as context state) plus a stopping rule, which belongs to the accumulation. VRT_E_INVALID
  * unless 2 <= min_samples <= max_samples <= 2^24 and tolerance <= 65535, or for what vrt_accum_begin_ex refuses.

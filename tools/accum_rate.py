@@ -24,6 +24,15 @@ time of one vrt_accum_resolve_hdr_device beside vrt_accum_resolve_device (resolv
 
     python3 tools/accum_rate.py --hdr --out profiles/accum_hdr_rate.jsonl
     python3 tools/accum_rate.py --hdr --mode primary primary_shadow full --jitter --out profiles/accum_hdr_jitter_rate.jsonl
+
+--path-depth D [D ...] measures every accumulation once per path depth (vrt_set_path_depth; VRT_MODE_FULL only honours it) and
+records the depth and the time per sample (path_depth, per_sample_ms); --scenes and --samples restrict the scenes and the sample
+counts of an add.
+
+    python3 tools/accum_rate.py --path-depth 1 2 4 8 --scenes dragon_1080p room_inside_1080p --out profiles/path_depth_rate.jsonl
+
+--out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
+--adaptive takes none of --path-depth, --scenes and --samples (it measures its own scenes and rounds) and refuses them.
 """
 import argparse
 import json
@@ -58,7 +67,12 @@ def main():
     ap.add_argument("--adaptive-lens", nargs=2, type=float, default=(0.1, 40.0), metavar=("APERTURE", "FOCUS"))
     ap.add_argument("--rounds", type=int, default=32)
     ap.add_argument("--hdr", action="store_true", help="each accumulation again with HDR sums, beside the plain one")
+    ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="once per path depth (vrt_set_path_depth)")
+    ap.add_argument("--scenes", nargs="+", default=sorted(SCENES), choices=sorted(SCENES))
+    ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
+    if args.adaptive and (args.path_depth or args.scenes != sorted(SCENES) or args.samples != list(SAMPLES)):
+        ap.error("--adaptive takes none of --path-depth, --scenes, --samples")
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
@@ -68,7 +82,9 @@ def main():
     d_rgba, d_id = ctx.device_alloc(W * H * 4), ctx.device_alloc(W * H * 8)
     d_rgb = ctx.device_alloc(W * H * 12) if args.hdr else None
     rows = []
-    for name, (m, pos, yaw, pitch) in SCENES.items():
+    last_spread = [0.0, 0.0]   # of the last add_ms(): the fastest and the slowest timed add
+    for name, depth in [(s, d) for s in SCENES if s in args.scenes for d in (args.path_depth or [None])]:
+        m, pos, yaw, pitch = SCENES[name]
         if m == "room":
             w = room_world(V)
         else:
@@ -80,12 +96,14 @@ def main():
         ip, iv, cp, _ = V.camera_block(pos, yaw, pitch, W, H)
         ctx.set_camera(ip, iv, cp)
         ctx.set_params(ctx.default_params())
+        if depth is not None:
+            ctx.set_path_depth(depth)
         opaque = V.tree_is_opaque(tex)
         for mname in args.mode:
             mode = V.MODES[mname]
             ctx.dispatch_timed(W, H, 0, H, mode, d_rgba, d_id, 5)
             frame_ms = float(np.median(ctx.dispatch_timed(W, H, 0, H, mode, d_rgba, d_id, max(args.reps, 5))))
-            for n in SAMPLES:
+            for n in args.samples:
                 base_ms = None
                 for lens in [None] + args.lens:
                     ctx.set_lens(*(lens or (0.0, 1.0)))
@@ -100,6 +118,7 @@ def main():
                             ctx.accum_add(n)
                             ctx.synchronize()
                             ts.append((time.perf_counter() - t0) * 1e3)
+                        last_spread[:] = [min(ts), max(ts)]
                         return float(np.median(ts))
 
                     def resolve_ms(hdr):
@@ -121,6 +140,8 @@ def main():
                            "ratio": round(ms / (n * frame_ms), 3), "reps": args.reps}
                     if args.mode != ["full"] or args.jitter or args.lens:
                         row.update(mode=mname, jitter=bool(args.jitter))
+                    if depth is not None:
+                        row.update(path_depth=depth, per_sample_ms=round(ms / n, 4), add_ms_min_max=[round(v, 4) for v in last_spread])
                     if lens is None:
                         base_ms = ms
                     else:

@@ -13,6 +13,10 @@ Prints one JSON object per line; --out writes them to a file too.
 
     python3 tools/shade_rays_rate.py --out profiles/shade_rays_rate.jsonl
     python3 tools/shade_rays_rate.py --hdr --out profiles/shade_rays_hdr_rate.jsonl
+
+--path-depth D [D ...] measures mode 2 of (a)'s batch and of (c)'s probes once per path depth (vrt_set_path_depth) instead:
+
+    python3 tools/shade_rays_rate.py --path-depth 1 2 4 8 --append --out profiles/path_depth_rate.jsonl   (after tools/accum_rate.py's rows)
 """
 import argparse
 import json
@@ -63,6 +67,8 @@ def main():
     ap.add_argument("--rays", type=int, default=1 << 21)
     ap.add_argument("--out", default=None)
     ap.add_argument("--hdr", action="store_true", help="the HDR calls beside the plain ones (see above)")
+    ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
+    ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="mode 2 once per path depth (see above)")
     args = ap.parse_args()
     V = vrt_import.vrt()
     w = V.World()
@@ -98,7 +104,7 @@ def main():
     def finish():
         ctx.close()
         if args.out:
-            with open(args.out, "w") as f:
+            with open(args.out, "a" if args.append else "w") as f:
                 for r in rows:
                     f.write(json.dumps(r) + "\n")
 
@@ -128,6 +134,39 @@ def main():
                           "hdr_ms_min_max": [round(float(hdr.min()), 4), round(float(hdr.max()), 4)],
                           "hdr_rays_per_s": round(n / (hm * 1e-3)), "reps": reps})
             for p in (d_o, d_d, d_rgb, d_rgba, d_id):
+                ctx.device_free(p)
+        finish()
+        return
+
+    if args.path_depth:
+        W, H = 1920, 1080
+        _, origin, dirs = frame_rays(V, W, H)
+        rng = np.random.default_rng(1)
+        n_probe = args.rays
+        o = rng.uniform((-64, -64, -64), (192, 160, 128), (n_probe, 3)).astype(np.float32)
+        d = rng.normal(0, 1, (n_probe, 3)).astype(np.float32)
+        hit, coord, place, _, _ = ctx.cast_rays(o, d)
+        face = (place - coord)[hit].astype(np.float64)
+        ok = np.abs(face).sum(1) == 1
+        cells, normals = place[hit][ok], face[ok]
+        pick = rng.integers(0, len(cells), n_probe)
+        po = (cells[pick] + rng.random((n_probe, 3))).astype(np.float32)
+        pd = cosine_dirs(rng, normals[pick])
+        for case, ro, rd, stride, width in (("frame_rays_1080p_dragon", origin.reshape(1, 3), dirs, 0, W),
+                                            ("probe_rays_dragon", po, pd, 3, n_probe)):
+            n = len(rd)
+            d_o, d_d = upload(ro, rd)
+            d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
+            for depth in args.path_depth:
+                ctx.set_path_depth(depth)
+                for n_samples in (1, 4):
+                    (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=2, width=width, n_samples=n_samples)],
+                                  max(3, args.reps // 2))
+                    m = float(np.median(ms))
+                    emit({"case": case, "mode": 2, "path_depth": depth, "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
+                          "kernel_ms_min_max": [round(float(ms.min()), 4), round(float(ms.max()), 4)],
+                          "per_sample_ms": round(m / n_samples, 4), "paths_per_s": round(n * n_samples / (m * 1e-3)), "reps": len(ms)})
+            for p in (d_o, d_d, d_rgba, d_id):
                 ctx.device_free(p)
         finish()
         return

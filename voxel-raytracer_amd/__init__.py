@@ -25,6 +25,7 @@ OPT_RAY_TABLES, OPT_EMPTY_OCTANTS, OPT_DISPLAY_KERNEL, OPT_FULL_OPAQUE, OPT_HEAV
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL = 0, 1, 2
 MODES = {"primary": MODE_PRIMARY, "primary_shadow": MODE_PRIMARY_SHADOW, "full": MODE_FULL}
 ACCUM_JITTER = 1   # vrt_accum_begin_ex flags (include/vrt.h VRT_ACCUM_JITTER)
+MAX_PATH_DEPTH = 8   # include/vrt.h VRT_MAX_PATH_DEPTH (Context.set_path_depth)
 TONEMAP_CLAMP, TONEMAP_REINHARD = 0, 1   # include/vrt.h VRT_TONEMAP_*
 TONEMAPS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD}
 
@@ -277,6 +278,8 @@ def hip_lib():
         L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
         L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
         L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        L.vrt_set_path_depth.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_set_path_depth.restype = C.c_int
         L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_uint32, C.c_uint32]
         L.vrt_accum_counts.argtypes = [C.c_void_p, C.c_void_p]
@@ -946,6 +949,22 @@ class Context:
                 raise ValueError(f"{name}: expected a float32 value {want}, got {v!r}")
             vals.append(float(f))
         self._chk(self._L.vrt_set_lens(self._h, vals[0], vals[1]))
+
+    def set_path_depth(self, depth):
+        """Path depth of the samples of MODE_FULL in accumulations and ray batches (vrt_set_path_depth): an integer in
+        1..MAX_PATH_DEPTH, default 1 (the shader's one bounce). An opaque, non-emissive hit of a ray of depth d < depth casts a
+        shadow ray, adds the direct term and bounces again; at d == depth it adds the shader's ambient term. Frames
+        (dispatch*) stay the shader at any setting; the primary modes ignore it."""
+        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)):
+            raise ValueError(f"depth: expected an integer in [1, {MAX_PATH_DEPTH}], got {depth!r}")
+        self._chk(self._L.vrt_set_path_depth(self._h, int(depth)))
+        self._path_depth = int(depth)
+
+    @property
+    def path_depth(self):
+        """The path depth set_path_depth() last set through this object (1 until then). A copy kept in Python: the C-ABI has a
+        setter only, so a vrt_set_path_depth call made past this wrapper is not seen here."""
+        return getattr(self, "_path_depth", 1)
 
     def accum_add(self, n_samples=1):
         """Enqueue n_samples more samples (vrt_accum_add) -> the samples now in the accumulation (n_samples after a restart)."""

@@ -326,8 +326,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 // take adaptive_constant_count() at once.
 // HDR: the three float64 sums wait in LDS too (1.5 KiB more per wave: 98 of the CU's 160 KiB at 28 waves); sky and emissive pixels
 // take their float colour from q.hframe, which hdr_frame_kernel wrote as it ran pass 1.
+// Over DeepPaths<...> (a path depth above 1: full::bounce_chain()) the kernels of the opaque route are built for fewer waves per SIMD
+// than their depth-1 twins, at the budget where the chain's loop-carried state -- origin, direction, tint, colour, RNG, medium, live
+// across every segment's march and shadow ray -- stays in registers: no scratch (profiles/path_depth_resource_usage.txt; at the
+// twins' 72 and 80 registers the compiler parks 16-71 of them in scratch around the marches, inside the depth loop).
+template <class TRAV, bool ADAPT, bool HDR>
+constexpr int bounce_wpe() { return deep_paths<TRAV>::value ? (ADAPT && HDR ? 3 : 4) : 7; }
+constexpr int kDeepOpaqueWpe = 4;   // opaque_accum_kernel over DeepPaths<...> (vrt_launch_accum.hip.h)
 template <class TRAV, bool ADAPT = false, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<TRAV, ADAPT, HDR>()))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q) {
     __shared__ uint32_t s_seed[kSeedPlanes][64];
     __shared__ uint32_t s_sum[3][64];
     __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];   // (HDR = false: never touched, and dropped)

@@ -76,7 +76,10 @@ struct KArgs {
     int row_mode;             // 1: one row tile (y = row0 + j); 2: tile_rows == 8 == tile height (y = row0 + ty * row_stride + ly); 0: divide
     const uint2 *nodes;       // level-ordered records (vrt_layout.h), root = record 0
     uint32_t n_records;
-    uint32_t lds_records;     // always 0 and read by no kernel: the word keeps the kernarg offsets (late_args(), kernarg_probe)
+    // Path depth D (include/vrt.h vrt_set_path_depth), 1..8: read only by the DEEP forms of the full path tracer's kernels, which the
+    // dispatcher launches for accumulation steps and ray batches at D > 1; every other kernel is the shader at depth 1 whatever
+    // this word holds. (It stands where a word no kernel read stood: the kernarg offsets of late_args() are unchanged.)
+    uint32_t path_depth;
     // wide layout (vrt_layout.h): 64 cells per node; roots = octree records where a wide tree starts
     const uint2 *cells;
     const uint2 *cells4;      // the same cells in the form of the v4 kernels (vrt_layout.h to_cell4)

@@ -310,6 +310,14 @@ template <class T> struct host_light<T, decltype((void)T::kHostLight)> { static 
 template <class T, class = void> struct miss_tiles { static constexpr bool value = false; };
 template <class T> struct miss_tiles<T, decltype((void)T::kMissTiles)> { static constexpr bool value = T::kMissTiles; };
 
+// ... and DeepPaths<T>, the traversal T for the kernels of the full path tracer that honour KArgs::path_depth (include/vrt.h
+// vrt_set_path_depth; vrt_full.hip.h): the same march() and shadow(), `static constexpr bool kDeepPaths = true`. A kernel over T
+// itself is the shader at depth 1 and keeps its device code.
+template <class T> struct DeepPaths : T { static constexpr bool kDeepPaths = true; };
+template <class T, class = void> struct deep_paths { static constexpr bool value = false; };
+template <class T> struct deep_paths<T, decltype((void)T::kDeepPaths)> { static constexpr bool value = T::kDeepPaths; };
+constexpr int kMaxPathDepth = 8;   // VRT_MAX_PATH_DEPTH
+
 // A primary ray the miss-tile proof covers ("Miss tiles"): no component of its direction within 2e-8 of (-1e-8, 0], so that after
 // march()'s renormalisation (a factor within a few ulps of 1) none lies in (-1e-8, 0] and every step of the DDA has t >= 0.
 VRT_DEV bool miss_forward(F3 d) {

@@ -464,6 +464,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     }
     hipError_t e;
     if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
+        if (mode == VRT_MODE_FULL) a.path_depth = (uint32_t)c->accum.path_depth;   // frames keep fill_scene_args()'s 1: the shader
         e = launch_accum_step(c->accum, a, vs, v, mode, (int)grid, two_pass, lsel, *acc, s);
     } else if (two_pass && c->two_pass_form >= 5) {
         e = vrt::launch::trace_full_opaque(a, vs, (int)grid, c->two_pass_form, s, prof.ev0, prof.ev1);

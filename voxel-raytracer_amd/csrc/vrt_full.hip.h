@@ -219,6 +219,12 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     // x / PI in its in-range form where the dispatcher vouches for the lights' range (KArgs::shade_fast, div_pi_inrange())
     const bool shade_fast = a.shade_fast != 0;
     const auto over_pi = [&](float x) { return shade_fast ? div_pi_inrange(x) : x / kPI; };
+    // Path depth D (include/vrt.h vrt_set_path_depth), honoured by the kernels over DeepPaths<...>: an opaque, non-emissive hit of a
+    // ray of depth d < D is an inner vertex and takes the depth-0 operations (shadow ray, direct term, two draws, bounce ray of
+    // depth d + 1); at d == D it is the shader's terminal branch. Every other kernel: D = BOUNCES, the shader.
+    constexpr bool DEEP = deep_paths<TRAV>::value;
+    int max_depth = kBounces;
+    if constexpr (DEEP) max_depth = (int)a.path_depth < kMaxPathDepth ? (int)a.path_depth : kMaxPathDepth;
 
 #ifdef VRT_EXP_STATS   // experiment builds only (tools/room_stats.sh): what the wave's time is made of, left in tile_cost
     unsigned long long st_acc = 0;
@@ -347,7 +353,7 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sc[k] * emission * r.weight);
                 continue;
             }
-            if (r.depth == 0) {
+            if (DEEP ? r.depth < max_depth : r.depth == 0) {
                 // (the dispatcher's LightSetup, which the primary + shadow kernel takes, costs this one 135 instructions per wave:
                 // at its register budget the uniform values are re-materialised inside the shadow loop)
                 VRT_ST_MARK(9);
@@ -370,7 +376,7 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(amb * sc[k] * tc[k] * r.weight);
                 continue;
             }
-            for (int i = 0; i < kIndirectSamples && sp < kMaxRays && r.depth <= kBounces; ++i) {
+            for (int i = 0; i < kIndirectSamples && sp < kMaxRays && (DEEP ? r.depth < max_depth : r.depth <= kBounces); ++i) {
                 const float rx = rng_next(rng), ry = rng_next(rng);
                 const F3 bd = cosine_hemisphere(normal, rx, ry);
                 const float nw = r.weight / (float)kIndirectSamples;
@@ -408,6 +414,107 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
 // again without a stack, and writes the pixel's final colour. The accumulation order per pixel is pathTrace's: direct term, then
 // the bounce's term. Everything pass 2 recomputes is computed from the same inputs by the same operations as pass 1 did.
 // Only the bounce depends on initRNG's sampleIndex (`sample`): the sample loop of vrt_accum.hip.h runs this once per sample on one seed.
+//
+// Path depth D > 1 (include/vrt.h vrt_set_path_depth; the kernels over DeepPaths<...>): the one bounce becomes a chain. In an opaque
+// scene no ray of depth >= 1 ever pushes a second ray (glass is glass at depth 0 only), so the chain is linear: bounce_chain() marches
+// one segment after the other in the lane's registers -- no ray stack, no scratch for it -- and each segment is trace_pixel_full's
+// iteration for a ray of depth >= 1, operation for operation: the miss, emissive and terminal exits, else the inner vertex (shadow ray,
+// direct term, two draws, the next direction, tint * surface colour). What a ray of the general loop carries and the one bounce of
+// bounce_pixel() did not need is carried here: the medium it travels in (the voxel before the last surface: one colour word, as on
+// the general kernel's stack) for the absorption of comp:512-516, which a chain that started behind a flipped normal can meet.
+// The loop ends when no lane of the wave is alive, at D at the latest; the marches keep their own step caps.
+template <class TRAV>
+__device__ void bounce_chain(const KArgs &a, const typename TRAV::Ctx &tc_, F3 o, F3 d, float iof, float tint[3], uint32_t &rng, float fc[3]) {
+    const float kPI = 3.14159265359f;
+    const float sky[3] = {0.5f, 0.7f, 1.0f};
+    const float kSun = 3.0f;
+    const bool shade_fast = a.shade_fast != 0;
+    const auto over_pi = [&](float x) { return shade_fast ? div_pi_inrange(x) : x / kPI; };
+    const int max_depth = (int)a.path_depth < kMaxPathDepth ? (int)a.path_depth : kMaxPathDepth;
+    const float *gl = a.global_light;
+    const F3 light{a.light_dir[0], a.light_dir[1], a.light_dir[2]};
+    uint32_t medium = 0u;   // the first bounce leaves a surface seen from empty space: alpha 0, no absorption (as in bounce_pixel())
+    bool alive = true;
+    for (int depth = 1; depth <= max_depth; ++depth) {
+        // per segment, as bounce_pixel(): the one-loop march while every live lane travels in refraction 1.0
+        const uint64_t general = __builtin_amdgcn_ballot_w64(alive && iof != 1.0f);
+        if (__builtin_amdgcn_ballot_w64(alive) == 0ull) break;
+        if (!alive) continue;
+        Hit h;
+        bool hit;
+        if (general == 0ull) hit = TRAV::Eye85::march(a, tc_, o, d, 1.0f, 85u, h);
+        else hit = TRAV::General::march(a, tc_, o, d, iof, iof_to_byte(iof), h);
+        float tc[3] = {tint[0], tint[1], tint[2]};
+        if (!hit) {   // comp:489-495 at depth > 0
+#pragma unroll
+            for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sky[k] * kSun * 1.0f);
+            alive = false;
+            continue;
+        }
+        const F3 hn{h.axis == 0 ? h.n : 0.0f, h.axis == 1 ? h.n : 0.0f, h.axis == 2 ? h.n : 0.0f};
+        F3 normal = hn;
+        if (!(len3(hn) > 0.0f)) normal = F3{0.0f, 1.0f, 0.0f};
+        const F3 hp = h.point;
+        F3 hpw = hp;
+        float dim;
+        if (a.voxel_scale != 1.0f) {
+            hpw = F3{hp.x / a.voxel_scale, hp.y / a.voxel_scale, hp.z / a.voxel_scale};
+            dim = 0.0f + len3(sub3(hpw, o)) / a.voxel_scale;
+        } else {
+            dim = 0.0f + len3(sub3(hpw, o));
+        }
+        Decoded hv = decode_leaf(h.h0, h.h1);
+        Decoded last = decode_leaf(h.p0, h.p1);
+        if (hv.c[3] <= 0.0f) { hv.p[0] = 1.0f; hv.p[1] = 0.0f; hv.p[2] = 0.0f; }
+        if (last.c[3] <= 0.0f) {
+            if (iof > 0.0f) { last.p[0] = 0.0f; last.p[1] = 0.0f; last.p[2] = 0.0f; }
+            else { last.p[0] = 1.0f; last.p[1] = 0.0f; last.p[2] = 0.0f; }
+        }
+        float sc[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sc[k] = hv.c[3] > 0.0f ? hv.c[k] : last.c[k];
+        float n2 = hv.p[0] > 0.0f ? hv.p[0] : 1.0f;
+        float n1 = last.p[0] > 0.0f ? last.p[0] : 1.0f;
+        if ((medium >> 24) != 0u && dim > 1e-6f) {   // mediumDensity = alpha * 5 > 0
+            const float mc[3] = {unorm_of((float)(medium & 0xffu)), unorm_of((float)((medium >> 8) & 0xffu)), unorm_of((float)((medium >> 16) & 0xffu))};
+            absorb(tc, unorm_of((float)(medium >> 24)) * 5.0f, dim, mc);
+        }
+        if (h.map.x == a.highlighted[0] && h.map.y == a.highlighted[1] && h.map.z == a.highlighted[2]) {
+            sc[0] = 1.0f - sc[0]; sc[1] = 1.0f - sc[1]; sc[2] = 1.0f - sc[2];
+        }
+        const float cosi = dot3(d, normal);
+        if (cosi > 0.0f) { normal = F3{-normal.x, -normal.y, -normal.z}; const float t = n1; n1 = n2; n2 = t; }
+        const float ndotl = fmax_c(dot3(normal, light), 0.0f);
+        const float emission = hv.p[1] * 10.0f;
+        if (emission > 0.0f) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sc[k] * emission * 1.0f);
+            alive = false;
+            continue;
+        }
+        if (depth >= max_depth) {   // the shader's terminal branch (comp:590-594)
+            const float amb = fmax_c(1.0f - det_expf(-dim / 512.0f), 0.01f);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(amb * sc[k] * tc[k] * 1.0f);
+            alive = false;
+            continue;
+        }
+        // an inner vertex: the depth-0 operations (comp:584-589, 596-616)
+        const int lit = TRAV::shadow(a, tc_, add3(hp, scale3(normal, 2e-3f)), light, h);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float direct = gl[k] * (float)lit * ndotl;
+            fc[k] = fc[k] + over_pi(direct * sc[k] * tc[k] * 1.0f);
+        }
+        const float rx = rng_next(rng), ry = rng_next(rng);
+        d = cosine_hemisphere(normal, rx, ry);
+        o = add3(hp, scale3(normal, 1e-1f));
+        iof = n1;
+        tint[0] = tc[0] * sc[0]; tint[1] = tc[1] * sc[1]; tint[2] = tc[2] * sc[2];
+        medium = h.p0;
+    }
+}
+
 template <class TRAV, bool HDR>
 __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int px, int py, const Seed seed, uint32_t &rgba, uint32_t sample,
                              float *fc_out) {
@@ -444,6 +551,12 @@ __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int 
     const float rx = rng_next(rng), ry = rng_next(rng);
     const F3 bd = cosine_hemisphere(normal, rx, ry);
     const F3 ro = add3(hp, scale3(normal, 1e-1f));
+    if constexpr (deep_paths<TRAV>::value) {
+        bounce_chain<TRAV>(a, tc_, ro, bd, n1, tint, rng, fc);
+        rgba = unorm8(fc[0]) | (unorm8(fc[1]) << 8) | (unorm8(fc[2]) << 16) | (255u << 24);
+        if constexpr (HDR) { fc_out[0] = fc[0]; fc_out[1] = fc[1]; fc_out[2] = fc[2]; }
+        return true;
+    }
     Hit h;
     // A bounce ray starts in the medium in front of the surface: empty space (n1 = 1.0), which the one-loop march of views from
     // empty space (TRAV::Eye85) takes -- except behind a flipped normal (an axis-aligned ray on a zero direction component, comp:497,

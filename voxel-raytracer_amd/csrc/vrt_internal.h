@@ -89,6 +89,7 @@ struct vrt_ctx {
     vrt_params params{};
     float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
     float lens[2] = {0.0f, 1.0f};   // vrt_set_lens: aperture, focus distance (the progressive accumulation only)
+    int path_depth = 1;             // vrt_set_path_depth: the samples of VRT_MODE_FULL in accumulations and ray batches (frames: always 1)
     int variant = 0;
     int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL = denoise::Args::rows_path: 0 each wave the cheaper walk; 2, 3: one walk forced
     // scratch outputs for the host-buffer dispatch
@@ -216,6 +217,7 @@ struct vrt_ctx {
         // what every sample depends on, as it was at the first sample in the sums
         float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
         float lens[2] = {0.0f, 1.0f};
+        int path_depth = 1;
         vrt_params params{};
         uint64_t tree_gen = 0;
         DevBuf<uint32_t> d_sums;                 // 4 words per pixel

@@ -126,6 +126,31 @@ inline hipError_t accum_bounce(bool hdr, const KArgs &a, const ViewSet &vs, cons
     return hdr ? accum_bounce_hdr(a, vs, q, adaptive, grid, s) : accum_bounce(a, vs, q, adaptive, grid, s);
 }
 
+// vrt_launch_accum_deep.hip, vrt_launch_accum_hdr_deep.hip: the sample launches of VRT_MODE_FULL at a path depth above 1 (include/vrt.h
+// vrt_set_path_depth): the same shapes and arguments, kernels that read a.path_depth. accum_full_deep takes any variant and launches
+// v4 for the wide traversals, v1 for the record-array ones (same workgroup shape, same bytes).
+hipError_t accum_opaque_deep(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
+                             int grid, hipStream_t s);
+hipError_t accum_full_deep(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
+                           const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_bounce_deep(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, int grid, hipStream_t s);
+hipError_t accum_opaque_hdr_deep(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
+                                 int grid, hipStream_t s);
+hipError_t accum_full_hdr_deep(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                               const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_bounce_hdr_deep(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s);
+inline hipError_t accum_opaque_deep(bool hdr, accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                                    const accum::Lens &l, int grid, hipStream_t s) {
+    return hdr ? accum_opaque_hdr_deep(src, a, vs, q, adaptive, l, grid, s) : accum_opaque_deep(src, a, vs, q, adaptive, l, grid, s);
+}
+inline hipError_t accum_full_deep(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                                  bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+    return hdr ? accum_full_hdr_deep(src, v, a, vs, q, adaptive, l, grid, s) : accum_full_deep(src, v, a, vs, q, adaptive, l, grid, s);
+}
+inline hipError_t accum_bounce_deep(bool hdr, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s) {
+    return hdr ? accum_bounce_hdr_deep(a, vs, q, adaptive, grid, s) : accum_bounce_deep(a, vs, q, adaptive, grid, s);
+}
+
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
@@ -135,6 +160,13 @@ hipError_t shade_rays(int mode, const Variant &v, const KArgs &a, const ViewSet 
 // mode, q.out_rgba takes the tone-mapped bytes of the mean
 hipError_t shade_rays_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, uint32_t grid, hipStream_t s,
                           hipEvent_t ev0, hipEvent_t ev1);
+
+// vrt_launch_rays_deep.hip, vrt_launch_rays_hdr_deep.hip: VRT_MODE_FULL of the two above at a path depth above 1 (kernels that read
+// a.path_depth; v4 for the wide variants, v1 for the record-array ones)
+hipError_t shade_rays_deep(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s, hipEvent_t ev0,
+                           hipEvent_t ev1);
+hipError_t shade_rays_hdr_deep(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, uint32_t grid, hipStream_t s,
+                               hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

@@ -34,14 +34,25 @@ template <class TRAV, int BLOCK, int WPE, class F>
 hipError_t shape(bool adaptive, F &&f) {
     return adaptive ? f(Shape<TRAV, BLOCK, WPE, true>{}) : f(Shape<TRAV, BLOCK, WPE, false>{});
 }
-// the general full path tracer: the shapes trace_full() launches trace_kernel<2> in
-template <class F>
+// DEEP (the objects vrt_launch_accum_deep.hip, vrt_launch_accum_hdr_deep.hip): the kernels that honour KArgs::path_depth
+template <bool DEEP, class T>
+using Path = typename std::conditional<DEEP, DeepPaths<T>, T>::type;
+// the general full path tracer: the shapes trace_full() launches trace_kernel<2> in. DEEP: every variant gives the same bytes, so a
+// launch is normalised to one of two instantiated traversals of its workgroup shape -- v4 for the wide ones, v1 (right for any
+// tree) for the record-array ones
+template <bool DEEP = false, class F>
 hipError_t full_shapes(const Variant &v, bool adaptive, F &&f) {
-    if (v.trav == 4) return shape<v4::TravAny, 64, 5>(adaptive, f);
-    if (v.trav == 3) return shape<v3::Trav, 64, 5>(adaptive, f);
-    if (v.trav == 2) return shape<v2::Trav, 256, 1>(adaptive, f);
-    if (v.trav == 1) return shape<v1::Trav, 256, 1>(adaptive, f);
-    return hipErrorInvalidValue;
+    if constexpr (DEEP) {
+        if (v.trav >= 3) return shape<DeepPaths<v4::TravAny>, 64, 5>(adaptive, f);
+        if (v.trav >= 1) return shape<DeepPaths<v1::Trav>, 256, 1>(adaptive, f);
+        return hipErrorInvalidValue;
+    } else {
+        if (v.trav == 4) return shape<v4::TravAny, 64, 5>(adaptive, f);
+        if (v.trav == 3) return shape<v3::Trav, 64, 5>(adaptive, f);
+        if (v.trav == 2) return shape<v2::Trav, 256, 1>(adaptive, f);
+        if (v.trav == 1) return shape<v1::Trav, 256, 1>(adaptive, f);
+        return hipErrorInvalidValue;
+    }
 }
 // the primary modes: the variants the dispatcher normalises an accumulation to
 template <class F>
@@ -87,10 +98,10 @@ hipError_t primary(int mode, accum::Source src, const Variant &v, const KArgs &a
     });
 }
 
-template <bool HDR>
+template <bool HDR, bool DEEP = false>
 hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, const accum::Lens &l, int grid,
                   hipStream_t s) {
-    return shape<v4::Trav, 64, 6>(adaptive, [&](auto sh) {
+    return shape<Path<DEEP, v4::Trav>, 64, DEEP ? accum::kDeepOpaqueWpe : 6>(adaptive, [&](auto sh) {
         using S = decltype(sh);
         const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
         if (src == accum::Source::kJitter) return go(accum::opaque_accum_kernel<accum::JitterSource, typename S::Trav, S::kWpe, S::kAdapt, HDR>, grid, 64, s, a, vs, qs);
@@ -99,10 +110,10 @@ hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const Fi
     });
 }
 
-template <bool HDR>
+template <bool HDR, bool DEEP = false>
 hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
                 const accum::Lens &l, int grid, hipStream_t s) {
-    return full_shapes(v, adaptive, [&](auto sh) {
+    return full_shapes<DEEP>(v, adaptive, [&](auto sh) {
         using S = decltype(sh);
         const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
         if (src == accum::Source::kCorner)
@@ -113,10 +124,10 @@ hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewS
     });
 }
 
-template <bool HDR>
+template <bool HDR, bool DEEP = false>
 hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s) {
-    if (adaptive) return go(accum::bounce_accum_kernel<v4::TravAny, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q));
-    return go(accum::bounce_accum_kernel<v4::TravAny, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q));
+    if (adaptive) return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q));
+    return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q));
 }
 
 }  // namespace accum_impl

@@ -74,6 +74,8 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     // the world is empty outside wide root 0: a property of the tree, applied by find() per ray (never to a first lookup); the
     // tighter root is a property of a view's eye and is not taken
     a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
+    const bool deep = mode == VRT_MODE_FULL && c->path_depth > 1;   // vrt_set_path_depth: the kernels that read a.path_depth
+    if (deep) a.path_depth = (uint32_t)c->path_depth;
 
     vrt::rays::Args q;
     q.origins = d_origins;
@@ -99,9 +101,10 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
         hq.n_total = hdr->n_prior + n_samples;
         hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
         hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
+        e = deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
+                 : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
     } else {
-        e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
+        e = deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
     }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     prof.commit(c);

@@ -99,7 +99,7 @@ void fill_scene_args(const vrt_ctx *c, vrt::KArgs &a) {
     a.tex_dim = (int)c->info.tex_dim;
     a.nodes = c->d_nodes;
     a.n_records = c->info.n_records;
-    a.lds_records = 0u;
+    a.path_depth = 1u;   // frames; accumulation steps and ray batches of VRT_MODE_FULL set the context's
     a.cells = c->d_cells;
     a.cells4 = c->d_cells ? c->d_cells + c->cells_capacity : nullptr;
     a.n_roots = c->wide_ok ? (uint32_t)c->wide.roots.size() : 0u;
@@ -400,6 +400,13 @@ int vrt_set_lens(vrt_ctx *c, float aperture, float focus_distance) {
         return vrt_fail(c, VRT_E_INVALID, "vrt_set_lens: the focus distance must be finite and > 0");
     c->lens[0] = aperture;
     c->lens[1] = focus_distance;
+    return VRT_OK;
+}
+
+int vrt_set_path_depth(vrt_ctx *c, int depth) {
+    if (!c) return VRT_E_INVALID;
+    if (depth < 1 || depth > VRT_MAX_PATH_DEPTH) return vrt_fail(c, VRT_E_INVALID, "vrt_set_path_depth: the depth must be 1 to 8");
+    c->path_depth = depth;
     return VRT_OK;
 }
 
