@@ -314,6 +314,41 @@ int vrt_set_lens(vrt_ctx *ctx, float aperture, float focus_distance);
 #define VRT_MAX_PATH_DEPTH 8
 int vrt_set_path_depth(vrt_ctx *ctx, int depth);
 
+/* Sun disc: soft shadows. The shader's sun is a point at infinity: every shadow ray runs along lightDir, and a shadow edge is the same
+ * hard staircase at any number of samples. vrt_set_sun_disc gives the sun an angular size: tan_radius is the tangent of its angular
+ * radius (the real sun: about 0.00465), default 0. It is context state, like the path depth. VRT_E_INVALID unless tan_radius is finite
+ * and 0 <= tan_radius <= 1 (the previous value still holds).
+ *
+ * Who honours it: whoever honours the path depth, at every depth D in 1..8 -- the samples of VRT_MODE_FULL in the progressive
+ * accumulation (vrt_accum_add in every form: corner, jitter, lens, adaptive, HDR) and in ray batches (vrt_shade_rays, _device, _hdr,
+ * _hdr_device). vrt_dispatch* frames (views, shards and vrt_multi included) stay the reference's shader at any setting;
+ * VRT_MODE_PRIMARY and VRT_MODE_PRIMARY_SHADOW ignore it, their accumulations included: they draw no random number. The value is one
+ * of the inputs of an accumulation of VRT_MODE_FULL: a change restarts the sums at `first`, the same value set again changes
+ * nothing; accumulations of the primary modes do not restart.
+ *
+ * At tan_radius == 0 nothing changes: no extra random number is drawn, the same kernels are launched, every byte is the same.
+ * At tan_radius > 0 (all arithmetic float32, every operation rounded on its own, no contraction):
+ *   1. The basis, once per launch, with the operations of normalize3 / len3 / cross3: with L = vrt_params.light_dir as given,
+ *      ll = len3(L), Ln = normalize3(L), up = fabsf(Ln.z) < 0.999f ? (0,0,1) : (1,0,0) (cosineSampleHemisphere's choice),
+ *      T = normalize3(cross3(up, Ln)), B = cross3(Ln, T). A zero or non-finite light_dir gives unspecified shading for the
+ *      shadowed terms; the call still terminates.
+ *   2. The rule applies inside pathTrace's loop, only at a vertex that casts a shadow ray: the opaque, non-emissive branch
+ *      (comp:584-616) of a ray of depth d < D (at D = 1: d = 0).
+ *   3. That vertex, in this order:
+ *        u1 = rand(), then u2 = rand(), from the pixel's one initRNG stream, immediately before notInShadow -- hence before the
+ *          two draws of the bounce direction;
+ *        (dx, dy) = the concentric map of vrt_set_lens step 3 with lu = u1, lv = u2;
+ *        s = tan_radius; v_i = (Ln_i + (s * dx) * T_i) + (s * dy) * B_i; L' = normalize3(v) * ll -- the length of lightDir keeps
+ *          the meaning it has in the shader;
+ *        lit = notInShadow(hitPoint + normal * 2e-3, L'), the shadow ray's set-up (comp:335-345) computed from L';
+ *        ndotl' = max(dot(normal, L'), 0);
+ *        the shader's direct term with lit and ndotl'; then the two bounce draws and everything after them, unchanged.
+ *   4. What does not move: the translucent branch's unshadowed direct term (comp:547-572) keeps ndotl from L; sky, emission, the
+ *      ambient term, (voxel ID, dist), the glass stack and the order in which the LIFO stack pops rays.
+ *   5. Consequence: a pixel's stream carries four draws per shadowing vertex instead of two, so sample k is not sample k of the
+ *      hard-shadow accumulation with a softened term: it is a different, equally valid sample. */
+int vrt_set_sun_disc(vrt_ctx *ctx, float tan_radius);
+
 /* Adaptive accumulation: stop sampling pixels whose mean has converged. vrt_accum_begin_adaptive is vrt_accum_begin_ex (same
  * modes, VRT_ACCUM_JITTER, the lens as context state) plus a stopping rule, which belongs to the accumulation. VRT_E_INVALID
  * unless 2 <= min_samples <= max_samples <= 2^24 and tolerance <= 65535, or for what vrt_accum_begin_ex refuses.

@@ -31,6 +31,11 @@ counts of an add.
 
     python3 tools/accum_rate.py --path-depth 1 2 4 8 --scenes dragon_1080p room_inside_1080p --out profiles/path_depth_rate.jsonl
 
+--sun R [R ...] (with --path-depth) measures each of them once per sun disc too (vrt_set_sun_disc, tan_radius R; 0 is the point sun)
+and records it (sun_disc):
+
+    python3 tools/accum_rate.py --path-depth 1 4 --sun 0 0.00465 0.05 --scenes dragon_1080p room_inside_1080p --out profiles/sun_disc_rate.jsonl
+
 --out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
 --adaptive takes none of --path-depth, --scenes and --samples (it measures its own scenes and rounds) and refuses them.
 """
@@ -68,11 +73,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=32)
     ap.add_argument("--hdr", action="store_true", help="each accumulation again with HDR sums, beside the plain one")
     ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="once per path depth (vrt_set_path_depth)")
+    ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
     ap.add_argument("--scenes", nargs="+", default=sorted(SCENES), choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
-    if args.adaptive and (args.path_depth or args.scenes != sorted(SCENES) or args.samples != list(SAMPLES)):
-        ap.error("--adaptive takes none of --path-depth, --scenes, --samples")
+    if args.adaptive and (args.path_depth or args.sun or args.scenes != sorted(SCENES) or args.samples != list(SAMPLES)):
+        ap.error("--adaptive takes none of --path-depth, --sun, --scenes, --samples")
+    if args.sun and not args.path_depth:
+        ap.error("--sun goes with --path-depth")
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
@@ -83,7 +91,7 @@ def main():
     d_rgb = ctx.device_alloc(W * H * 12) if args.hdr else None
     rows = []
     last_spread = [0.0, 0.0]   # of the last add_ms(): the fastest and the slowest timed add
-    for name, depth in [(s, d) for s in SCENES if s in args.scenes for d in (args.path_depth or [None])]:
+    for name, depth, sun in [(s, d, r) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])]:
         m, pos, yaw, pitch = SCENES[name]
         if m == "room":
             w = room_world(V)
@@ -98,6 +106,8 @@ def main():
         ctx.set_params(ctx.default_params())
         if depth is not None:
             ctx.set_path_depth(depth)
+        if sun is not None:
+            ctx.set_sun_disc(sun)
         opaque = V.tree_is_opaque(tex)
         for mname in args.mode:
             mode = V.MODES[mname]
@@ -142,6 +152,8 @@ def main():
                         row.update(mode=mname, jitter=bool(args.jitter))
                     if depth is not None:
                         row.update(path_depth=depth, per_sample_ms=round(ms / n, 4), add_ms_min_max=[round(v, 4) for v in last_spread])
+                    if sun is not None:
+                        row.update(sun_disc=sun)
                     if lens is None:
                         base_ms = ms
                     else:

@@ -17,6 +17,10 @@ Prints one JSON object per line; --out writes them to a file too.
 --path-depth D [D ...] measures mode 2 of (a)'s batch and of (c)'s probes once per path depth (vrt_set_path_depth) instead:
 
     python3 tools/shade_rays_rate.py --path-depth 1 2 4 8 --append --out profiles/path_depth_rate.jsonl   (after tools/accum_rate.py's rows)
+
+--sun R [R ...] (with --path-depth) measures each of them once per sun disc too (vrt_set_sun_disc) and records it (sun_disc):
+
+    python3 tools/shade_rays_rate.py --path-depth 1 4 --sun 0 0.00465 0.05 --append --out profiles/sun_disc_rate.jsonl
 """
 import argparse
 import json
@@ -69,7 +73,10 @@ def main():
     ap.add_argument("--hdr", action="store_true", help="the HDR calls beside the plain ones (see above)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="mode 2 once per path depth (see above)")
+    ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
     args = ap.parse_args()
+    if args.sun and not args.path_depth:
+        ap.error("--sun goes with --path-depth")
     V = vrt_import.vrt()
     w = V.World()
     assert w.load_vox(os.path.join(ROOT, "tests", "golden", "maps", "dragon.vox"))
@@ -157,13 +164,15 @@ def main():
             n = len(rd)
             d_o, d_d = upload(ro, rd)
             d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
-            for depth in args.path_depth:
+            for depth, sun in [(dd, r) for dd in args.path_depth for r in (args.sun or [None])]:
                 ctx.set_path_depth(depth)
+                if sun is not None:
+                    ctx.set_sun_disc(sun)
                 for n_samples in (1, 4):
                     (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=2, width=width, n_samples=n_samples)],
                                   max(3, args.reps // 2))
                     m = float(np.median(ms))
-                    emit({"case": case, "mode": 2, "path_depth": depth, "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
+                    emit({"case": case, "mode": 2, "path_depth": depth, **({} if sun is None else {"sun_disc": sun}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
                           "kernel_ms_min_max": [round(float(ms.min()), 4), round(float(ms.max()), 4)],
                           "per_sample_ms": round(m / n_samples, 4), "paths_per_s": round(n * n_samples / (m * 1e-3)), "reps": len(ms)})
             for p in (d_o, d_d, d_rgba, d_id):

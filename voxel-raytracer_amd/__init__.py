@@ -280,6 +280,8 @@ def hip_lib():
         L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
         L.vrt_set_path_depth.argtypes = [C.c_void_p, C.c_int]
         L.vrt_set_path_depth.restype = C.c_int
+        L.vrt_set_sun_disc.argtypes = [C.c_void_p, C.c_float]
+        L.vrt_set_sun_disc.restype = C.c_int
         L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_uint32, C.c_uint32]
         L.vrt_accum_counts.argtypes = [C.c_void_p, C.c_void_p]
@@ -965,6 +967,22 @@ class Context:
         """The path depth set_path_depth() last set through this object (1 until then). A copy kept in Python: the C-ABI has a
         setter only, so a vrt_set_path_depth call made past this wrapper is not seen here."""
         return getattr(self, "_path_depth", 1)
+
+    def set_sun_disc(self, tan_radius):
+        """Sun disc of the samples of MODE_FULL in accumulations and ray batches (vrt_set_sun_disc): the tangent of the sun's
+        angular radius, a finite number in [0, 1], default 0 (the shader's point sun; the real sun is about 0.00465). Above 0 every
+        vertex that casts a shadow ray draws its own light direction on the disc: soft shadows. Frames (dispatch*) and the primary
+        modes ignore it. A value outside the range raises (VRT_E_INVALID) and the previous one holds."""
+        if isinstance(tan_radius, bool) or not isinstance(tan_radius, (int, float, np.integer, np.floating)):
+            raise ValueError(f"tan_radius: expected a number in [0, 1], got {tan_radius!r}")
+        self._chk(self._L.vrt_set_sun_disc(self._h, float(tan_radius)))
+        self._sun_disc = float(np.float32(tan_radius))
+
+    @property
+    def sun_disc(self):
+        """The value set_sun_disc() last set through this object (0.0 until then), as the float32 the library holds. A copy kept
+        in Python: the C-ABI has a setter only."""
+        return getattr(self, "_sun_disc", 0.0)
 
     def accum_add(self, n_samples=1):
         """Enqueue n_samples more samples (vrt_accum_add) -> the samples now in the accumulation (n_samples after a restart)."""

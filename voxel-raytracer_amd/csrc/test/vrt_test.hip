@@ -22,6 +22,7 @@
 #include "../vrt_layout.h"
 #include "../vrt_miss.h"
 #include "../vrt_sched.hip.h"
+#include "../vrt_sun.h"
 
 namespace vrt {
 // the adaptive stopping rule on the device: out[i] = adaptive_active(n[i], s[i], q[i], min, max, tol)
@@ -136,6 +137,14 @@ using vrt_internal::view_matrix_in_range;
     } while (0)
 
 extern "C" {
+
+// host only: the sun disc's block as the dispatcher makes it (vrt_sun.h sun_block()) -> out[11] = tan_radius, ll, Ln, T, B
+void vrt_test_sun_block(const float *light_dir, float tan_radius, float *out) {
+    const vrt::Sun s = sun_block(light_dir, tan_radius);
+    out[0] = s.tan_radius; out[1] = s.ll;
+    for (int i = 0; i < 3; ++i) { out[2 + i] = s.Ln[i]; out[5 + i] = s.T[i]; out[8 + i] = s.B[i]; }
+}
+
 
 // Arithmetic-contract probe (math_probe_kernel / math_probe_full_kernel): out[i] = op(x[i], y[i]) on `device`; host arrays, synchronous.
 int vrt_test_math(int device, int op, const float *x, const float *y, float *out, int n) {

@@ -25,7 +25,8 @@ using Accum = vrt_ctx::Accum;
 bool same_inputs(const vrt_ctx *c, const Accum &ac) {
     return std::memcmp(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj) == 0 && std::memcmp(ac.inv_view, c->inv_view, sizeof ac.inv_view) == 0 &&
            std::memcmp(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos) == 0 && std::memcmp(&ac.params, &c->params, sizeof ac.params) == 0 &&
-           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || ac.path_depth == c->path_depth) && ac.tree_gen == c->tree_gen;   // the primary modes ignore the depth
+           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc)) &&   // the primary modes ignore the depth and the sun disc
+           ac.tree_gen == c->tree_gen;
 }
 
 void take_inputs(const vrt_ctx *c, Accum &ac) {
@@ -34,6 +35,7 @@ void take_inputs(const vrt_ctx *c, Accum &ac) {
     std::memcpy(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos);
     std::memcpy(ac.lens, c->lens, sizeof ac.lens);
     ac.path_depth = c->path_depth;
+    ac.sun_disc = c->sun_disc;
     ac.params = c->params;
     ac.tree_gen = c->tree_gen;
 }
@@ -179,6 +181,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     q.hframe = ac.d_hframe;
     const bool hdr = acc.hdr, adaptive = acc.adaptive;
     const bool deep = mode == VRT_MODE_FULL && a.path_depth > 1u;   // the kernels that honour the path depth (vrt_set_path_depth)
+    const bool sun_on = mode == VRT_MODE_FULL && acc.sun > 0.0f;    // ... and the sun disc (vrt_set_sun_disc), at every depth
+    const vrt::Sun sun = sun_on ? sun_block(a.light_dir, acc.sun) : vrt::Sun{};   // radius 0: nothing is made, nothing is passed
     const vrt::accum::HdrFrame hf{ac.d_pass1, ac.d_id, ac.d_hframe};
     q.sums = ac.d_sums;
     q.pass1_rgba = ac.d_pass1;
@@ -202,7 +206,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     if (mode != VRT_MODE_FULL)   // one launch, the samples looped in the lanes
         return launch::accum_primary(hdr, mode, src, v, a, vs, q, adaptive, l, grid, s);
     if (two_pass && src != Source::kCorner)   // MODE 6's chain per sample, looped in the lanes
-        return deep ? launch::accum_opaque_deep(hdr, src, a, vs, q, adaptive, l, grid, s) : launch::accum_opaque(hdr, src, a, vs, q, adaptive, l, grid, s);
+        return sun_on ? launch::accum_opaque_sun(hdr, src, a, vs, q, adaptive, l, sun, grid, s)
+               : deep ? launch::accum_opaque_deep(hdr, src, a, vs, q, adaptive, l, grid, s) : launch::accum_opaque(hdr, src, a, vs, q, adaptive, l, grid, s);
     hipError_t e = hipSuccess;
     if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
         a.defer_rec = reinterpret_cast<float *>(ac.d_seed.get());
@@ -214,7 +219,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
             if (e != hipSuccess) return e;
             ac.pass1 = true;
         }
-        return deep ? launch::accum_bounce_deep(hdr, a, vs, q, adaptive, grid, s) : launch::accum_bounce(hdr, a, vs, q, adaptive, grid, s);
+        return sun_on ? launch::accum_bounce_sun(hdr, a, vs, q, adaptive, sun, grid, s)
+               : deep ? launch::accum_bounce_deep(hdr, a, vs, q, adaptive, grid, s) : launch::accum_bounce(hdr, a, vs, q, adaptive, grid, s);
     }
     // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
     const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, a.width, a.height, ac.min_samples, ac.max_samples,
@@ -224,7 +230,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         q.n = 1u;
         if (adaptive) e = launch::adaptive_tiles(tl, s);
         if (e == hipSuccess)
-            e = deep ? launch::accum_full_deep(hdr, src, v, a, vs, q, adaptive, l, grid, s) : launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
+            e = sun_on ? launch::accum_full_sun(hdr, src, v, a, vs, q, adaptive, l, sun, grid, s)
+                : deep ? launch::accum_full_deep(hdr, src, v, a, vs, q, adaptive, l, grid, s) : launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
     }
     return e;
 }
@@ -312,7 +319,8 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         }
         if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     } else if (r == VRT_OK) {
-        const AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
+        AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
+        step.sun = ac.mode == VRT_MODE_FULL ? ac.sun_disc : 0.0f;
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again

@@ -9,6 +9,14 @@ namespace vrt {
 struct F3 { float x, y, z; };
 struct I3 { int x, y, z; };
 
+// The sun disc (include/vrt.h vrt_set_sun_disc): its tangent radius and the basis the host makes once per launch from
+// vrt_params.light_dir = L (vrt_sun.h sun_block()): ll = len3(L), Ln = normalize3(L), T and B across it. 11 floats, a by-value
+// kernel argument of its own of the kernels over SunPaths<...> (vrt_common.hip.h) -- KArgs and ViewSet keep their layout.
+struct Sun {
+    float tan_radius, ll;
+    float Ln[3], T[3], B[3];
+};
+
 // One camera and the two images it renders into. A launch carries up to kMaxViews of them (blockIdx.y selects
 // the view): frames of one scene that are known together -- a stereo pair, the next frames of a camera path, the
 // views of a light-field rig -- share one launch, so the drain of one view's last waves is filled by the next

@@ -318,6 +318,17 @@ template <class T, class = void> struct deep_paths { static constexpr bool value
 template <class T> struct deep_paths<T, decltype((void)T::kDeepPaths)> { static constexpr bool value = T::kDeepPaths; };
 constexpr int kMaxPathDepth = 8;   // VRT_MAX_PATH_DEPTH
 
+// ... and SunPaths<T>, DeepPaths<T> for the kernels that also honour the sun disc (include/vrt.h vrt_set_sun_disc; vrt_full.hip.h
+// sun_dir()): `static constexpr bool kSunPaths = true`, and a Ctx that carries the launch's Sun beside T's own -- the kernel copies its
+// Sun argument there once, and march() / shadow() take the Ctx as T's. One family serves every depth 1..8: it reads KArgs::path_depth.
+template <class T> struct SunPaths : DeepPaths<T> {
+    static constexpr bool kSunPaths = true;
+    struct Ctx : T::Ctx { Sun sun; };
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
+};
+template <class T, class = void> struct sun_paths { static constexpr bool value = false; };
+template <class T> struct sun_paths<T, decltype((void)T::kSunPaths)> { static constexpr bool value = T::kSunPaths; };
+
 // A primary ray the miss-tile proof covers ("Miss tiles"): no component of its direction within 2e-8 of (-1e-8, 0], so that after
 // march()'s renormalisation (a factor within a few ulps of 1) none lies in (-1e-8, 0] and every step of the DDA has t >= 0.
 VRT_DEV bool miss_forward(F3 d) {

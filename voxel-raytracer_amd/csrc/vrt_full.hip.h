@@ -101,6 +101,21 @@ VRT_DEV void det_sincos(float xin, float &s_out, float &c_out) {  // Cephes sinf
     c_out = sign_c < 0 ? -cv : cv;
 }
 
+// The concentric map (Shirley-Chiu) of (lu, lv) in [0, 1)^2 to the unit disc, with the conventions' sin / cos (include/vrt.h
+// vrt_set_lens, step 3): the lens point of vrt_lens.hip.h and the point of the sun disc (sun_dir()) are this one function.
+VRT_DEV void concentric_disc(float lu, float lv, float &lx, float &ly) {
+    const float a = 2.0f * lu - 1.0f, b = 2.0f * lv - 1.0f;
+    lx = ly = 0.0f;
+    if (a == 0.0f && b == 0.0f) return;
+    float r, phi;
+    if (__builtin_fabsf(a) > __builtin_fabsf(b)) { r = a; phi = 0.785398163f * (b / a); }
+    else { r = b; phi = 1.57079633f - 0.785398163f * (a / b); }
+    float s, c;
+    det_sincos(phi, s, c);
+    lx = r * c;
+    ly = r * s;
+}
+
 // comp:381-399; `sample` is initRNG's sampleIndex (uint(sampleIndex): the same bits for every int)
 VRT_DEV uint32_t rng_init(int px, int py, uint32_t sample) {
     uint32_t seed = (uint32_t)px + (uint32_t)py * 1920u + 123456u + sample * 78901u;
@@ -130,6 +145,17 @@ VRT_DEV F3 cosine_hemisphere(F3 n, float rx, float ry) {
     F3 bitangent = cross3(n, tangent);
     F3 r = add3(add3(scale3(tangent, x), scale3(bitangent, z)), scale3(n, ct));
     return normalize3(r);
+}
+
+// The sun disc (include/vrt.h vrt_set_sun_disc, step 3): the light direction L' of one shadowing vertex, from the next two draws of
+// the pixel's stream -- drawn immediately before notInShadow, hence before the bounce's two. L' keeps lightDir's length ll.
+VRT_DEV F3 sun_dir(const Sun &s, uint32_t &rng) {
+    const float u1 = rng_next(rng), u2 = rng_next(rng);
+    float dx, dy;
+    concentric_disc(u1, u2, dx, dy);
+    const float sx = s.tan_radius * dx, sy = s.tan_radius * dy;
+    const F3 v{(s.Ln[0] + sx * s.T[0]) + sy * s.B[0], (s.Ln[1] + sx * s.T[1]) + sy * s.B[1], (s.Ln[2] + sx * s.T[2]) + sy * s.B[2]};
+    return scale3(normalize3(v), s.ll);
 }
 
 // GLSL refract / reflect
@@ -225,6 +251,9 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     constexpr bool DEEP = deep_paths<TRAV>::value;
     int max_depth = kBounces;
     if constexpr (DEEP) max_depth = (int)a.path_depth < kMaxPathDepth ? (int)a.path_depth : kMaxPathDepth;
+    // Sun disc (include/vrt.h vrt_set_sun_disc), honoured by the kernels over SunPaths<...>: a vertex that casts a shadow ray draws
+    // its own light direction L' (sun_dir()) and takes lit and n.l from it; the translucent branch keeps L.
+    constexpr bool SUN = sun_paths<TRAV>::value;
 
 #ifdef VRT_EXP_STATS   // experiment builds only (tools/room_stats.sh): what the wave's time is made of, left in tile_cost
     unsigned long long st_acc = 0;
@@ -360,14 +389,20 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
 #ifdef VRT_EXP_STATS
                 const unsigned long long st_t1 = __builtin_readcyclecounter();
 #endif
-                const int lit = TRAV::shadow(a, tc_, add3(hp, scale3(normal, 2e-3f)), light, h);
+                F3 ld = light;
+                float nl = ndotl;
+                if constexpr (SUN) {
+                    ld = sun_dir(tc_.sun, rng);
+                    nl = fmax_c(dot3(normal, ld), 0.0f);
+                }
+                const int lit = TRAV::shadow(a, tc_, add3(hp, scale3(normal, 2e-3f)), ld, h);
 #ifdef VRT_EXP_STATS
                 if (VRT_EXP_STATS == 3) st_acc += __builtin_readcyclecounter() - st_t1;
                 st_t3 = __builtin_readcyclecounter();
 #endif
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const float direct = gl[k] * (float)lit * ndotl;
+                    const float direct = gl[k] * (float)lit * nl;
                     fc[k] = fc[k] + over_pi(direct * sc[k] * tc[k] * r.weight);
                 }
             } else {
@@ -500,10 +535,16 @@ __device__ void bounce_chain(const KArgs &a, const typename TRAV::Ctx &tc_, F3 o
             continue;
         }
         // an inner vertex: the depth-0 operations (comp:584-589, 596-616)
-        const int lit = TRAV::shadow(a, tc_, add3(hp, scale3(normal, 2e-3f)), light, h);
+        F3 ld = light;
+        float nl = ndotl;
+        if constexpr (sun_paths<TRAV>::value) {   // the sun disc: this vertex's own light direction, two draws before the bounce's
+            ld = sun_dir(tc_.sun, rng);
+            nl = fmax_c(dot3(normal, ld), 0.0f);
+        }
+        const int lit = TRAV::shadow(a, tc_, add3(hp, scale3(normal, 2e-3f)), ld, h);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float direct = gl[k] * (float)lit * ndotl;
+            const float direct = gl[k] * (float)lit * nl;
             fc[k] = fc[k] + over_pi(direct * sc[k] * tc[k] * 1.0f);
         }
         const float rx = rng_next(rng), ry = rng_next(rng);
@@ -537,8 +578,21 @@ __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int 
     const F3 normal{naxis == 0 ? nval : 0.0f, naxis == 1 ? nval : 0.0f, naxis == 2 ? nval : 0.0f};
     const float *gl = a.global_light;
     const F3 light{a.light_dir[0], a.light_dir[1], a.light_dir[2]};
-    const float ndotl = fmax_c(nval * comp(light, naxis), 0.0f);
-    const float lit = (word & (1u << 28)) ? 1.0f : 0.0f;
+    float ndotl = fmax_c(nval * comp(light, naxis), 0.0f);
+    float lit = (word & (1u << 28)) ? 1.0f : 0.0f;
+    // The sun disc (kernels over SunPaths<...>): the depth-0 shadow ray belongs to the sample. The seed's lit bit is pass 1's, for
+    // lightDir itself, and is ignored: the vertex draws its L' first (the sample's first two numbers) and casts its own shadow ray
+    // from the seed's hit point. No primary Hit is at hand to resume from, so the walk starts as march()'s does (TRAV::fresh()): the
+    // resume state only saves the first descent.
+    uint32_t sun_rng = 0u;
+    if constexpr (sun_paths<TRAV>::value) {
+        sun_rng = rng_init(px, py, sample);
+        const F3 ld = sun_dir(tc_.sun, sun_rng);
+        Hit h0;
+        TRAV::fresh(h0);
+        lit = (float)TRAV::shadow(a, tc_, add3(hp, scale3(normal, 2e-3f)), ld, h0);
+        ndotl = fmax_c(dot3(normal, ld), 0.0f);
+    }
     float fc[3], tint[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {   // comp:587-589 as trace_pixel<1> evaluates it (the throughput of a primary ray from empty space is the light)
@@ -546,8 +600,8 @@ __device__ bool bounce_pixel(const KArgs &a, const typename TRAV::Ctx &tc_, int 
         fc[k] = 0.0f + over_pi(direct * sc[k] * gl[k] * 1.0f);
         tint[k] = gl[k] * sc[k];
     }
-    // comp:596-616: the first two random numbers of the pixel
-    uint32_t rng = rng_init(px, py, sample);
+    // comp:596-616: the first two random numbers of the pixel (with a sun disc: the next two)
+    uint32_t rng = sun_paths<TRAV>::value ? sun_rng : rng_init(px, py, sample);
     const float rx = rng_next(rng), ry = rng_next(rng);
     const F3 bd = cosine_hemisphere(normal, rx, ry);
     const F3 ro = add3(hp, scale3(normal, 1e-1f));

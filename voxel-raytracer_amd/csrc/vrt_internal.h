@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "vrt_args.h"
+#include "vrt_sun.h"
 #include "vrt_devbuf.h"
 #include "vrt_layout.h"
 #include "vrt_miss.h"
@@ -90,6 +91,7 @@ struct vrt_ctx {
     float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
     float lens[2] = {0.0f, 1.0f};   // vrt_set_lens: aperture, focus distance (the progressive accumulation only)
     int path_depth = 1;             // vrt_set_path_depth: the samples of VRT_MODE_FULL in accumulations and ray batches (frames: always 1)
+    float sun_disc = 0.0f;          // vrt_set_sun_disc: the tangent of the sun's angular radius, honoured where the path depth is
     int variant = 0;
     int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL = denoise::Args::rows_path: 0 each wave the cheaper walk; 2, 3: one walk forced
     // scratch outputs for the host-buffer dispatch
@@ -218,6 +220,7 @@ struct vrt_ctx {
         float inv_proj[16]{}, inv_view[16]{}, cam_pos[4]{};
         float lens[2] = {0.0f, 1.0f};
         int path_depth = 1;
+        float sun_disc = 0.0f;
         vrt_params params{};
         uint64_t tree_gen = 0;
         DevBuf<uint32_t> d_sums;                 // 4 words per pixel
@@ -282,6 +285,7 @@ int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm);
 // itself. The light block: the uniforms of the shading and the shadow ray's set-up.
 void fill_scene_args(const vrt_ctx *c, vrt::KArgs &a);
 void fill_light_args(const vrt_ctx *c, vrt::KArgs &a);
+// sun_block(light_dir, tan_radius), the sun disc's block for a launch whose light direction is light_dir: vrt_sun.h
 // The context's variant (vrt_set_variant) as this scene allows it: the record-array kernels without a wide layout, the
 // explicit-AABB ones where a unit-size node is internal. Frames and ray batches start from it.
 Variant base_variant(const vrt_ctx *c);
@@ -307,11 +311,13 @@ struct ProfSlot {
 // (adaptive: n rounds of the context's adaptive accumulation, vrt_accum_begin_adaptive; the kernels' adaptive forms)
 // (hdr: an HDR accumulation, vrt_accum_keep_hdr; the kernels' HDR forms. frame_only, with hdr, modes 0 / 1 from the corner: no
 // sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
+// (sun > 0: VRT_MODE_FULL with a sun disc of that tangent radius, vrt_set_sun_disc; the kernels over SunPaths<...>)
 struct AccumStep {
     uint32_t first, n;
     bool jitter;
     float aperture = 0.0f, focus = 1.0f;
     bool adaptive = false, hdr = false, frame_only = false;
+    float sun = 0.0f;
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);

@@ -85,6 +85,14 @@ struct TravT {
         w.last = I3{0x55555555, 0x2aaaaaaa, 0x55555555};
     }
 
+    // A Hit to hand shadow() where no march came before it (the sun disc's depth-0 shadow ray over pass 1's seeds, vrt_full.hip.h
+    // bounce_pixel()): its walk starts as reset() leaves it, so the first lookup descends from the root as march()'s does.
+    static VRT_DEV void fresh(Hit &h) {
+        Walk w;
+        reset(w);
+        h.r_node = w.node; h.r_s = (int)w.cs; h.r_anode = w.anode; h.r_as = (int)w.acs; h.r_last = w.last;
+    }
+
     static VRT_DEV uint2 load_cell(const KArgs &a, uint32_t node, uint32_t cs, I3 p) {
         const uint32_t bx = __builtin_amdgcn_ubfe((uint32_t)p.x, cs, 2u), by = __builtin_amdgcn_ubfe((uint32_t)p.y, cs, 2u),
                        bz = __builtin_amdgcn_ubfe((uint32_t)p.z, cs, 2u);

@@ -151,6 +151,31 @@ inline hipError_t accum_bounce_deep(bool hdr, const KArgs &a, const ViewSet &vs,
     return hdr ? accum_bounce_hdr_deep(a, vs, q, adaptive, grid, s) : accum_bounce_deep(a, vs, q, adaptive, grid, s);
 }
 
+// vrt_launch_accum_sun.hip, vrt_launch_accum_hdr_sun.hip: the same launches with a sun disc (include/vrt.h vrt_set_sun_disc), at any
+// path depth: kernels over SunPaths<...>, which take `sun` (vrt_sun.h sun_block()) as their last argument
+hipError_t accum_opaque_sun(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
+                            const Sun &sun, int grid, hipStream_t s);
+hipError_t accum_full_sun(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
+                          const accum::Lens &l, const Sun &sun, int grid, hipStream_t s);
+hipError_t accum_bounce_sun(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const Sun &sun, int grid, hipStream_t s);
+hipError_t accum_opaque_hdr_sun(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
+                                const Sun &sun, int grid, hipStream_t s);
+hipError_t accum_full_hdr_sun(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                              const accum::Lens &l, const Sun &sun, int grid, hipStream_t s);
+hipError_t accum_bounce_hdr_sun(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const Sun &sun, int grid, hipStream_t s);
+inline hipError_t accum_opaque_sun(bool hdr, accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                                   const accum::Lens &l, const Sun &sun, int grid, hipStream_t s) {
+    return hdr ? accum_opaque_hdr_sun(src, a, vs, q, adaptive, l, sun, grid, s) : accum_opaque_sun(src, a, vs, q, adaptive, l, sun, grid, s);
+}
+inline hipError_t accum_full_sun(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                                 bool adaptive, const accum::Lens &l, const Sun &sun, int grid, hipStream_t s) {
+    return hdr ? accum_full_hdr_sun(src, v, a, vs, q, adaptive, l, sun, grid, s) : accum_full_sun(src, v, a, vs, q, adaptive, l, sun, grid, s);
+}
+inline hipError_t accum_bounce_sun(bool hdr, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const Sun &sun, int grid,
+                                   hipStream_t s) {
+    return hdr ? accum_bounce_hdr_sun(a, vs, q, adaptive, sun, grid, s) : accum_bounce_sun(a, vs, q, adaptive, sun, grid, s);
+}
+
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
@@ -167,6 +192,12 @@ hipError_t shade_rays_deep(const Variant &v, const KArgs &a, const ViewSet &vs, 
                            hipEvent_t ev1);
 hipError_t shade_rays_hdr_deep(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, uint32_t grid, hipStream_t s,
                                hipEvent_t ev0, hipEvent_t ev1);
+
+// vrt_launch_rays_sun.hip, vrt_launch_rays_hdr_sun.hip: VRT_MODE_FULL of the same with a sun disc, at any path depth
+hipError_t shade_rays_sun(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const Sun &sun, uint32_t grid, hipStream_t s,
+                          hipEvent_t ev0, hipEvent_t ev1);
+hipError_t shade_rays_hdr_sun(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Sun &sun, uint32_t grid,
+                              hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

@@ -35,16 +35,20 @@ hipError_t shape(bool adaptive, F &&f) {
     return adaptive ? f(Shape<TRAV, BLOCK, WPE, true>{}) : f(Shape<TRAV, BLOCK, WPE, false>{});
 }
 // DEEP (the objects vrt_launch_accum_deep.hip, vrt_launch_accum_hdr_deep.hip): the kernels that honour KArgs::path_depth
-template <bool DEEP, class T>
-using Path = typename std::conditional<DEEP, DeepPaths<T>, T>::type;
+// SUN (vrt_launch_accum_sun.hip, vrt_launch_accum_hdr_sun.hip): those that also honour the sun disc, at every depth; their last
+// argument is the Sun (`sun...`, one or none)
+template <bool DEEP, class T, bool SUN = false>
+using Path = typename std::conditional<SUN, SunPaths<T>, typename std::conditional<DEEP, DeepPaths<T>, T>::type>::type;
+template <bool SUN, class PLAIN, class WITH_SUN>
+using Src = typename std::conditional<SUN, WITH_SUN, PLAIN>::type;
 // the general full path tracer: the shapes trace_full() launches trace_kernel<2> in. DEEP: every variant gives the same bytes, so a
 // launch is normalised to one of two instantiated traversals of its workgroup shape -- v4 for the wide ones, v1 (right for any
 // tree) for the record-array ones
-template <bool DEEP = false, class F>
+template <bool DEEP = false, bool SUN = false, class F>
 hipError_t full_shapes(const Variant &v, bool adaptive, F &&f) {
     if constexpr (DEEP) {
-        if (v.trav >= 3) return shape<DeepPaths<v4::TravAny>, 64, 5>(adaptive, f);
-        if (v.trav >= 1) return shape<DeepPaths<v1::Trav>, 256, 1>(adaptive, f);
+        if (v.trav >= 3) return shape<Path<true, v4::TravAny, SUN>, 64, 5>(adaptive, f);
+        if (v.trav >= 1) return shape<Path<true, v1::Trav, SUN>, 256, 1>(adaptive, f);
         return hipErrorInvalidValue;
     } else {
         if (v.trav == 4) return shape<v4::TravAny, 64, 5>(adaptive, f);
@@ -98,36 +102,43 @@ hipError_t primary(int mode, accum::Source src, const Variant &v, const KArgs &a
     });
 }
 
-template <bool HDR, bool DEEP = false>
+template <bool HDR, bool DEEP = false, class... SUN>
 hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, const accum::Lens &l, int grid,
-                  hipStream_t s) {
-    return shape<Path<DEEP, v4::Trav>, 64, DEEP ? accum::kDeepOpaqueWpe : 6>(adaptive, [&](auto sh) {
+                  hipStream_t s, const SUN &...sun) {
+    constexpr bool kSun = sizeof...(SUN) != 0;
+    return shape<Path<DEEP, v4::Trav, kSun>, 64, DEEP ? accum::kDeepOpaqueWpe : 6>(adaptive, [&](auto sh) {
         using S = decltype(sh);
         const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
-        if (src == accum::Source::kJitter) return go(accum::opaque_accum_kernel<accum::JitterSource, typename S::Trav, S::kWpe, S::kAdapt, HDR>, grid, 64, s, a, vs, qs);
-        if (src == accum::Source::kLens) return go(accum::opaque_accum_kernel<accum::LensSource, typename S::Trav, S::kWpe, S::kAdapt, HDR, accum::Lens>, grid, 64, s, a, vs, qs, l);
+        if (src == accum::Source::kJitter) return go(accum::opaque_accum_kernel<Src<kSun, accum::JitterSource, accum::SunJitterSource>, typename S::Trav, S::kWpe, S::kAdapt, HDR, SUN...>, grid, 64, s, a, vs, qs, sun...);
+        if (src == accum::Source::kLens) return go(accum::opaque_accum_kernel<Src<kSun, accum::LensSource, accum::SunLensSource>, typename S::Trav, S::kWpe, S::kAdapt, HDR, accum::Lens, SUN...>, grid, 64, s, a, vs, qs, l, sun...);
         return hipErrorInvalidValue;   // the corner's: pass 1 once, then accum_bounce
     });
 }
 
-template <bool HDR, bool DEEP = false>
+template <bool HDR, bool DEEP = false, class... SUN>
 hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
-                const accum::Lens &l, int grid, hipStream_t s) {
-    return full_shapes<DEEP>(v, adaptive, [&](auto sh) {
+                const accum::Lens &l, int grid, hipStream_t s, const SUN &...sun) {
+    constexpr bool kSun = sizeof...(SUN) != 0;
+    return full_shapes<DEEP, kSun>(v, adaptive, [&](auto sh) {
         using S = decltype(sh);
         const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
         if (src == accum::Source::kCorner)
-            return go(accum::full_accum_kernel<accum::CornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR>, grid, S::kBlock, s, a, vs, qs);
+            return go(accum::full_accum_kernel<Src<kSun, accum::CornerSource, accum::SunCornerSource>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, SUN...>, grid, S::kBlock, s, a, vs, qs, sun...);
         if (src == accum::Source::kJitter)
-            return go(accum::full_accum_kernel<accum::JitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR>, grid, S::kBlock, s, a, vs, qs);
-        return go(accum::full_accum_kernel<accum::LensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens>, grid, S::kBlock, s, a, vs, qs, l);
+            return go(accum::full_accum_kernel<Src<kSun, accum::JitterSource, accum::SunJitterSource>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, SUN...>, grid, S::kBlock, s, a, vs, qs, sun...);
+        return go(accum::full_accum_kernel<Src<kSun, accum::LensSource, accum::SunLensSource>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, SUN...>, grid, S::kBlock, s, a, vs, qs, l, sun...);
     });
 }
 
-template <bool HDR, bool DEEP = false>
-hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s) {
-    if (adaptive) return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q));
-    return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q));
+template <bool HDR, bool DEEP = false, class... SUN>
+hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s, const SUN &...sun) {
+    if constexpr (sizeof...(SUN) != 0) {
+        if (adaptive) return go(accum::bounce_accum_sun_kernel<SunPaths<v4::TravAny>, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q), sun...);
+        return go(accum::bounce_accum_sun_kernel<SunPaths<v4::TravAny>, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q), sun...);
+    } else {
+        if (adaptive) return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q));
+        return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q));
+    }
 }
 
 }  // namespace accum_impl

@@ -42,16 +42,7 @@ VRT_DEV void lens_point(uint32_t k, float &lx, float &ly) {
     for (uint32_t i = 0, b = k; b; ++i, b >>= 1)
         if (b & 1u) { gu ^= kLensDirs.u[i]; gv ^= kLensDirs.v[i]; }
     const float lu = (float)((gu >> 8) ^ 0x800000u) * 0x1p-24f, lv = (float)((gv >> 8) ^ 0x800000u) * 0x1p-24f;
-    const float a = 2.0f * lu - 1.0f, b = 2.0f * lv - 1.0f;
-    lx = ly = 0.0f;
-    if (a == 0.0f && b == 0.0f) return;
-    float r, phi;
-    if (__builtin_fabsf(a) > __builtin_fabsf(b)) { r = a; phi = 0.785398163f * (b / a); }
-    else { r = b; phi = 1.57079633f - 0.785398163f * (a / b); }
-    float s, c;
-    full::det_sincos(phi, s, c);
-    lx = r * c;
-    ly = r * s;
+    full::concentric_disc(lu, lv, lx, ly);
 }
 
 // sample's lens ray of pixel (px, py), the medium at its origin included

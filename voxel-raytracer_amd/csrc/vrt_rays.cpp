@@ -76,6 +76,9 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
     const bool deep = mode == VRT_MODE_FULL && c->path_depth > 1;   // vrt_set_path_depth: the kernels that read a.path_depth
     if (deep) a.path_depth = (uint32_t)c->path_depth;
+    const bool sun_on = mode == VRT_MODE_FULL && c->sun_disc > 0.0f;   // vrt_set_sun_disc: the kernels over SunPaths<...>, at every depth
+    if (sun_on) a.path_depth = (uint32_t)c->path_depth;
+    const vrt::Sun sun = sun_on ? sun_block(a.light_dir, c->sun_disc) : vrt::Sun{};
 
     vrt::rays::Args q;
     q.origins = d_origins;
@@ -101,10 +104,12 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
         hq.n_total = hdr->n_prior + n_samples;
         hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
         hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
-                 : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
+        e = sun_on ? vrt::launch::shade_rays_hdr_sun(v, a, vs, hq, sun, grid, s, prof.ev0, prof.ev1)
+            : deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
+                   : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
     } else {
-        e = deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
+        e = sun_on ? vrt::launch::shade_rays_sun(v, a, vs, q, sun, grid, s, prof.ev0, prof.ev1)
+            : deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
     }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     prof.commit(c);

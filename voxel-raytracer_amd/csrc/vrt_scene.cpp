@@ -410,6 +410,14 @@ int vrt_set_path_depth(vrt_ctx *c, int depth) {
     return VRT_OK;
 }
 
+int vrt_set_sun_disc(vrt_ctx *c, float tan_radius) {
+    if (!c) return VRT_E_INVALID;
+    if (!(tan_radius >= 0.0f && tan_radius <= 1.0f))   // NaN fails both
+        return vrt_fail(c, VRT_E_INVALID, "vrt_set_sun_disc: the tangent of the radius must be finite and in [0, 1]");
+    c->sun_disc = tan_radius;
+    return VRT_OK;
+}
+
 int vrt_variant_available(int variant) {
     return find_variant(variant) ? 1 : 0;
 }
