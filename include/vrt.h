@@ -349,6 +349,64 @@ int vrt_set_path_depth(vrt_ctx *ctx, int depth);
  *      hard-shadow accumulation with a softened term: it is a different, equally valid sample. */
 int vrt_set_sun_disc(vrt_ctx *ctx, float tan_radius);
 
+/* Emitter sampling: next-event estimation towards emissive voxels. A voxel with a non-zero illumination byte lights a surface only
+ * when a cosine-distributed bounce ray happens to hit it (the shader's `emission > 0 && depth > 0` branch, comp:575-581): indoors the
+ * slowest-converging term of the image. vrt_set_emitter_sampling(ctx, 1) makes every vertex that casts a shadow ray also connect to a
+ * random point on a random emitter, and in exchange drops what bounce rays find by accident. enable is 0 (default) or 1; anything
+ * else is VRT_E_INVALID (the previous value still holds). It is context state, like the path depth and the sun disc.
+ *
+ * The emitter list. An emitter is a leaf of the current tree whose record has alpha byte > 0 and illumination byte > 0: exactly the
+ * leaves for which the shader's `emission` is positive. An entry is the leaf's cube in tree (grid) coordinates, four int32
+ * {lo.x, lo.y, lo.z, size}: its minimum corner and its edge length under the world bounds of vrt_params, split as the shader splits
+ * them; a merged volume is one entry with size > 1. (A merged leaf whose box is no cube -- possible only where the bounds are no power
+ * of two -- is listed as its unit cells; a box that holds no cell is not listed.) The order is ascending by (lo.x, lo.y, lo.z) and
+ * does not depend on record order: a patched or compacted tree gives the list of a fresh upload of the same world. The list is made
+ * lazily, by the first vrt_emitters call and by the first add or batch that honours sampling, after any change of the tree (upload,
+ * patch, batch end, compaction) or of the bounds.
+ *   vrt_emitters returns N and writes the first min(N, cap) entries to out (out may be NULL where cap is 0), whether or not sampling
+ * is enabled; for N > VRT_MAX_EMITTERS it writes none. VRT_E_STATE before any upload and while a patch batch is open.
+ *   With sampling on and N > VRT_MAX_EMITTERS every call that would honour sampling returns VRT_E_STATE with a message.
+ *
+ * Who honours it: exactly who honours the path depth and the sun disc -- the samples of VRT_MODE_FULL in vrt_accum_add in every form
+ * (corner, jitter, lens, adaptive, HDR) and vrt_shade_rays, _device, _hdr, _hdr_device, at every D in 1..8, with any sun radius.
+ * vrt_dispatch* frames, views, shards, vrt_multi and the two primary modes ignore it. The flag is one of the inputs of an accumulation
+ * of VRT_MODE_FULL: a change restarts the sums at `first`, the same value set again changes nothing; accumulations of the primary
+ * modes do not restart.
+ *
+ * Off, or N == 0: nothing changes -- no extra random number is drawn, the same kernels are launched, every byte is the same.
+ * On with N > 0 (all arithmetic float32, every operation rounded on its own, no contraction). At every vertex that casts a shadow
+ * ray -- the opaque, non-emissive branch (comp:584-616) of a ray of depth d < D -- after the sun's direct term (which follows the
+ * sun's own two draws, if any) and before the two draws of the bounce direction:
+ *   1. Four draws from the pixel's stream, in this order: u0 = rand(), uf = rand(), ua = rand(), ub = rand().
+ *   2. The emitter: j = min((int)(u0 * (float)N), N - 1), with corner lo and sz = (float)size.
+ *      The face: f = min((int)(uf * 6.0f), 5), ax = f >> 1, side = f & 1, a1 = (ax + 1) % 3, a2 = (ax + 2) % 3.
+ *      The point q on it: q[ax] = (float)lo[ax] + (side ? sz : 0.0f), q[a1] = (float)lo[a1] + ua * sz, q[a2] = (float)lo[a2] + ub * sz.
+ *   3. The connection: x = hitPoint + normal * 1e-1 (the bounce ray's origin, in grid units); w = q - x; r2 = dot3(w, w); if
+ *      !(r2 > 0) nothing more happens; dir = w * (1 / sqrt(r2)); cs = dot3(normal, dir); cl = side ? -dir[ax] : dir[ax]; if
+ *      !(cs > 0 && cl > 0) nothing is marched or added -- the four draws stay spent.
+ *   4. The connection ray is the ray the bounce would make (make_ray, comp:604-615) with dir in place of the hemisphere direction:
+ *      origin x, rayIOF n1, the same weight, tint = transmittedColor * surfaceColor, distanceInMedium 0, the last voxel as its
+ *      medium, depth d + 1.
+ *   5. It is marched with the shader's own hitMarching (the first hit). It contributes only if it hits and the hit cell lies in
+ *      emitter j's cube: per axis lo <= hitMapPos < lo + size.
+ *   6. Then the hit is evaluated as the shader evaluates any hit of a ray of depth >= 1, up to the emissive test: the distance in the
+ *      medium (comp:499-501), the absorption (comp:512-516), the highlighted-voxel inversion, emission = props[1] * 10. If
+ *      emission > 0:
+ *        E_k  = tc'[k] * sc'[k] * emission * weight / PI    (the shader's own depth > 0 emissive term, comp:579)
+ *        area = ((float)N * 6.0f) * (sz * sz)
+ *        g    = ((cs * cl) * area) / (PI * r2)
+ *        fc[k] = fc[k] + E_k * g
+ *   7. In exchange a ray of depth >= 1 that hits an emissive voxel adds nothing and ends: the light would be counted twice.
+ * What does not move: the depth-0 emissive term, the sky and ambient terms, the translucent branch, (voxel ID, dist), the order in
+ * which the LIFO stack pops rays.
+ * Consequences: the expectation of a sample equals that of the same sample with sampling off -- the two estimators integrate the same
+ * quantity, one over direction, one over emitter area (the choice is uniform over emitters and over the six faces: unbiased, but
+ * wasteful where emitter sizes differ much). Sample k itself is a different, equally valid sample: the stream carries four more draws
+ * per shadowing vertex. */
+#define VRT_MAX_EMITTERS (1u << 20)
+int vrt_set_emitter_sampling(vrt_ctx *ctx, int enable);
+long vrt_emitters(vrt_ctx *ctx, int32_t *out, size_t cap);
+
 /* Adaptive accumulation: stop sampling pixels whose mean has converged. vrt_accum_begin_adaptive is vrt_accum_begin_ex (same
  * modes, VRT_ACCUM_JITTER, the lens as context state) plus a stopping rule, which belongs to the accumulation. VRT_E_INVALID
  * unless 2 <= min_samples <= max_samples <= 2^24 and tolerance <= 65535, or for what vrt_accum_begin_ex refuses.

@@ -36,6 +36,13 @@ and records it (sun_disc):
 
     python3 tools/accum_rate.py --path-depth 1 4 --sun 0 0.00465 0.05 --scenes dragon_1080p room_inside_1080p --out profiles/sun_disc_rate.jsonl
 
+--emit E [E ...] (with --path-depth) measures each of them once per setting of emitter sampling too (vrt_set_emitter_sampling, 0 or
+1) and records it (emitter_sampling, and the length of the list: emitters). The scene lamp_room_1080p is tests/emit_worlds.py's
+lamp room seen from inside, which has emitters; the room fixture and the maps have none, so their two settings launch the same
+kernels:
+
+    python3 tools/accum_rate.py --path-depth 1 4 --emit 0 1 --scenes lamp_room_1080p room_inside_1080p --samples 16 --out profiles/emit_rate.jsonl
+
 --out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
 --adaptive takes none of --path-depth, --scenes and --samples (it measures its own scenes and rounds) and refuses them.
 """
@@ -57,7 +64,9 @@ SCENES = {   # name -> (map, pose): the golden 1080p / 4K frames' poses
     "dragon_1080p": ("dragon", (63.5, 60.5, 140.5), -90.0, -10.0),
     "nature_1080p": ("nature", (60.5, 80.5, 200.5), -90.0, -20.0),
     "room_inside_1080p": ("room", (14.5, 30.5, 16.5), 32.0, -10.0),
+    "lamp_room_1080p": ("lamp", (36.5, 44.5, 50.5), -38.0, 8.0),   # tests/emit_worlds.py: POSE
 }
+DEFAULT_SCENES = sorted(s for s in SCENES if SCENES[s][0] != "lamp")   # the lamp room: on request (--scenes), for --emit
 
 
 def main():
@@ -74,13 +83,17 @@ def main():
     ap.add_argument("--hdr", action="store_true", help="each accumulation again with HDR sums, beside the plain one")
     ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="once per path depth (vrt_set_path_depth)")
     ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
-    ap.add_argument("--scenes", nargs="+", default=sorted(SCENES), choices=sorted(SCENES))
+    ap.add_argument("--emit", nargs="+", type=int, default=None, choices=(0, 1), metavar="E",
+                    help="with --path-depth: once per setting of emitter sampling (vrt_set_emitter_sampling)")
+    ap.add_argument("--scenes", nargs="+", default=DEFAULT_SCENES, choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
-    if args.adaptive and (args.path_depth or args.sun or args.scenes != sorted(SCENES) or args.samples != list(SAMPLES)):
-        ap.error("--adaptive takes none of --path-depth, --sun, --scenes, --samples")
+    if args.adaptive and (args.path_depth or args.sun or args.emit or args.scenes != DEFAULT_SCENES or args.samples != list(SAMPLES)):
+        ap.error("--adaptive takes none of --path-depth, --sun, --emit, --scenes, --samples")
     if args.sun and not args.path_depth:
         ap.error("--sun goes with --path-depth")
+    if args.emit and not args.path_depth:
+        ap.error("--emit goes with --path-depth")
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
@@ -91,10 +104,14 @@ def main():
     d_rgb = ctx.device_alloc(W * H * 12) if args.hdr else None
     rows = []
     last_spread = [0.0, 0.0]   # of the last add_ms(): the fastest and the slowest timed add
-    for name, depth, sun in [(s, d, r) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])]:
+    for name, depth, sun, emit in [(s, d, r, e) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])
+                                   for e in (args.emit or [None])]:
         m, pos, yaw, pitch = SCENES[name]
         if m == "room":
             w = room_world(V)
+        elif m == "lamp":
+            import emit_worlds
+            w = emit_worlds.lamp_room(V)
         else:
             w = V.World()
             assert w.load_vox(os.path.join(MAPS, m + ".vox"))
@@ -108,6 +125,8 @@ def main():
             ctx.set_path_depth(depth)
         if sun is not None:
             ctx.set_sun_disc(sun)
+        if emit is not None:
+            ctx.set_emitter_sampling(emit)
         opaque = V.tree_is_opaque(tex)
         for mname in args.mode:
             mode = V.MODES[mname]
@@ -154,6 +173,10 @@ def main():
                         row.update(path_depth=depth, per_sample_ms=round(ms / n, 4), add_ms_min_max=[round(v, 4) for v in last_spread])
                     if sun is not None:
                         row.update(sun_disc=sun)
+                    if emit is not None:
+                        row.update(emitter_sampling=emit, emitters=len(ctx.emitters()))
+                        if emit and row["emitters"]:
+                            row["path"] = "general"   # the opaque routes are not taken
                     if lens is None:
                         base_ms = ms
                     else:
@@ -181,6 +204,8 @@ def main():
 def _scenes(V, ctx, W, H):
     from conftest import MAPS, room_world
     for name, (m, pos, yaw, pitch) in SCENES.items():
+        if name not in DEFAULT_SCENES:
+            continue
         if m == "room":
             w = room_world(V)
         else:

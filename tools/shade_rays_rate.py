@@ -21,6 +21,11 @@ Prints one JSON object per line; --out writes them to a file too.
 --sun R [R ...] (with --path-depth) measures each of them once per sun disc too (vrt_set_sun_disc) and records it (sun_disc):
 
     python3 tools/shade_rays_rate.py --path-depth 1 4 --sun 0 0.00465 0.05 --append --out profiles/sun_disc_rate.jsonl
+
+--emit E [E ...] (with --path-depth) measures them in tests/emit_worlds.py's lamp room instead of the dragon (which has no emitter),
+once per setting of emitter sampling (vrt_set_emitter_sampling, 0 or 1), and records it (emitter_sampling):
+
+    python3 tools/shade_rays_rate.py --path-depth 1 4 --emit 0 1 --append --out profiles/emit_rate.jsonl
 """
 import argparse
 import json
@@ -37,9 +42,9 @@ import vrt_import  # noqa: E402
 POSE = ((63.5, 60.5, 140.5), -90.0, -10.0)   # the golden 1080p dragon frame
 
 
-def frame_rays(V, W, H):
+def frame_rays(V, W, H, pose=POSE):
     """comp:624-641 in float64, rounded to float32 at the end"""
-    ip, iv, cp, _ = V.camera_block(POSE[0], POSE[1], POSE[2], W, H)
+    ip, iv, cp, _ = V.camera_block(pose[0], pose[1], pose[2], W, H)
     ipm = np.asarray(ip, np.float64).reshape(4, 4).T
     ivm = np.asarray(iv, np.float64).reshape(4, 4).T
     u = np.arange(W) / W * 2 - 1
@@ -74,12 +79,20 @@ def main():
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="mode 2 once per path depth (see above)")
     ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
+    ap.add_argument("--emit", nargs="+", type=int, default=None, choices=(0, 1), metavar="E",
+                    help="with --path-depth: in the lamp room, once per setting of emitter sampling (vrt_set_emitter_sampling)")
     args = ap.parse_args()
     if args.sun and not args.path_depth:
         ap.error("--sun goes with --path-depth")
+    if args.emit and not args.path_depth:
+        ap.error("--emit goes with --path-depth")
     V = vrt_import.vrt()
-    w = V.World()
-    assert w.load_vox(os.path.join(ROOT, "tests", "golden", "maps", "dragon.vox"))
+    if args.emit:
+        import emit_worlds
+        w = emit_worlds.lamp_room(V)
+    else:
+        w = V.World()
+        assert w.load_vox(os.path.join(ROOT, "tests", "golden", "maps", "dragon.vox"))
     ctx = V.Context(0)
     ctx.upload_octree(*w.flatten())
     rows = []
@@ -147,10 +160,17 @@ def main():
 
     if args.path_depth:
         W, H = 1920, 1080
-        _, origin, dirs = frame_rays(V, W, H)
+        world = "dragon"
+        box = ((-64, -64, -64), (192, 160, 128))
+        pose = POSE
+        if args.emit:   # the probes start inside the room
+            world = "lamp_room"
+            box = ((emit_worlds.LO + 1,) * 3, (emit_worlds.HI,) * 3)
+            pose = (emit_worlds.POSE[:3], emit_worlds.POSE[3], emit_worlds.POSE[4])
+        _, origin, dirs = frame_rays(V, W, H, pose)
         rng = np.random.default_rng(1)
         n_probe = args.rays
-        o = rng.uniform((-64, -64, -64), (192, 160, 128), (n_probe, 3)).astype(np.float32)
+        o = rng.uniform(box[0], box[1], (n_probe, 3)).astype(np.float32)
         d = rng.normal(0, 1, (n_probe, 3)).astype(np.float32)
         hit, coord, place, _, _ = ctx.cast_rays(o, d)
         face = (place - coord)[hit].astype(np.float64)
@@ -159,20 +179,23 @@ def main():
         pick = rng.integers(0, len(cells), n_probe)
         po = (cells[pick] + rng.random((n_probe, 3))).astype(np.float32)
         pd = cosine_dirs(rng, normals[pick])
-        for case, ro, rd, stride, width in (("frame_rays_1080p_dragon", origin.reshape(1, 3), dirs, 0, W),
-                                            ("probe_rays_dragon", po, pd, 3, n_probe)):
+        for case, ro, rd, stride, width in ((f"frame_rays_1080p_{world}", origin.reshape(1, 3), dirs, 0, W),
+                                            (f"probe_rays_{world}", po, pd, 3, n_probe)):
             n = len(rd)
             d_o, d_d = upload(ro, rd)
             d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
-            for depth, sun in [(dd, r) for dd in args.path_depth for r in (args.sun or [None])]:
+            for depth, sun, em in [(dd, r, e) for dd in args.path_depth for r in (args.sun or [None]) for e in (args.emit or [None])]:
                 ctx.set_path_depth(depth)
                 if sun is not None:
                     ctx.set_sun_disc(sun)
+                if em is not None:
+                    ctx.set_emitter_sampling(em)
                 for n_samples in (1, 4):
                     (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=2, width=width, n_samples=n_samples)],
                                   max(3, args.reps // 2))
                     m = float(np.median(ms))
-                    emit({"case": case, "mode": 2, "path_depth": depth, **({} if sun is None else {"sun_disc": sun}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
+                    emit({"case": case, "mode": 2, "path_depth": depth, **({} if sun is None else {"sun_disc": sun}),
+                          **({} if em is None else {"emitter_sampling": em}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
                           "kernel_ms_min_max": [round(float(ms.min()), 4), round(float(ms.max()), 4)],
                           "per_sample_ms": round(m / n_samples, 4), "paths_per_s": round(n * n_samples / (m * 1e-3)), "reps": len(ms)})
             for p in (d_o, d_d, d_rgba, d_id):

@@ -26,6 +26,7 @@ MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL = 0, 1, 2
 MODES = {"primary": MODE_PRIMARY, "primary_shadow": MODE_PRIMARY_SHADOW, "full": MODE_FULL}
 ACCUM_JITTER = 1   # vrt_accum_begin_ex flags (include/vrt.h VRT_ACCUM_JITTER)
 MAX_PATH_DEPTH = 8   # include/vrt.h VRT_MAX_PATH_DEPTH (Context.set_path_depth)
+MAX_EMITTERS = 1 << 20   # include/vrt.h VRT_MAX_EMITTERS (Context.emitters, Context.set_emitter_sampling)
 TONEMAP_CLAMP, TONEMAP_REINHARD = 0, 1   # include/vrt.h VRT_TONEMAP_*
 TONEMAPS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD}
 
@@ -282,6 +283,10 @@ def hip_lib():
         L.vrt_set_path_depth.restype = C.c_int
         L.vrt_set_sun_disc.argtypes = [C.c_void_p, C.c_float]
         L.vrt_set_sun_disc.restype = C.c_int
+        L.vrt_set_emitter_sampling.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_set_emitter_sampling.restype = C.c_int
+        L.vrt_emitters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.vrt_emitters.restype = C.c_long
         L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_uint32, C.c_uint32]
         L.vrt_accum_counts.argtypes = [C.c_void_p, C.c_void_p]
@@ -983,6 +988,38 @@ class Context:
         """The value set_sun_disc() last set through this object (0.0 until then), as the float32 the library holds. A copy kept
         in Python: the C-ABI has a setter only."""
         return getattr(self, "_sun_disc", 0.0)
+
+    def set_emitter_sampling(self, on):
+        """Emitter sampling of the samples of MODE_FULL in accumulations and ray batches (vrt_set_emitter_sampling): 0 / False
+        (default) or 1 / True. On, every vertex that casts a shadow ray also connects to a random point of the emitter list
+        (emitters()) and bounce rays that hit an emissive voxel add nothing: the same expectation, far less variance indoors. Frames
+        (dispatch*) and the primary modes ignore it. Any other value raises (VRT_E_INVALID) and the previous one holds."""
+        if not isinstance(on, (bool, int, np.integer)) or int(on) not in (0, 1):
+            raise ValueError(f"emitter sampling: expected 0 or 1, got {on!r}")
+        self._chk(self._L.vrt_set_emitter_sampling(self._h, int(on)))
+        self._emitter_sampling = bool(on)
+
+    @property
+    def emitter_sampling(self):
+        """The value set_emitter_sampling() last set through this object (False until then). A copy kept in Python: the C-ABI has
+        a setter only."""
+        return getattr(self, "_emitter_sampling", False)
+
+    def emitters(self):
+        """The emitter list of the current tree (vrt_emitters) -> int32[N, 4]: lo.x, lo.y, lo.z, size of every leaf with alpha and
+        illumination above 0, ascending by (lo.x, lo.y, lo.z). Above MAX_EMITTERS entries the library holds none: that raises."""
+        n = self._L.vrt_emitters(self._h, None, 0)
+        if n < 0:
+            self._chk(n)
+        if n > MAX_EMITTERS:
+            raise VrtError(f"emitters: the tree has {n} emitters, more than MAX_EMITTERS")
+        out = np.zeros((n, 4), np.int32)
+        if n:
+            got = self._L.vrt_emitters(self._h, out.ctypes.data, n)
+            if got < 0:
+                self._chk(got)
+            assert got == n
+        return out
 
     def accum_add(self, n_samples=1):
         """Enqueue n_samples more samples (vrt_accum_add) -> the samples now in the accumulation (n_samples after a restart)."""

@@ -23,6 +23,7 @@
 #include "../vrt_miss.h"
 #include "../vrt_sched.hip.h"
 #include "../vrt_sun.h"
+#include "../vrt_emitters.h"
 
 namespace vrt {
 // the adaptive stopping rule on the device: out[i] = adaptive_active(n[i], s[i], q[i], min, max, tol)
@@ -145,6 +146,19 @@ void vrt_test_sun_block(const float *light_dir, float tan_radius, float *out) {
     for (int i = 0; i < 3; ++i) { out[2 + i] = s.Ln[i]; out[5 + i] = s.T[i]; out[8 + i] = s.B[i]; }
 }
 
+
+// host only: the emitter list as the context makes it (vrt_emitters.h emitter_list()) of a caller's record array (n_records x 2
+// words) and world bounds -> N, and the first min(N, cap) entries of four int32 in out (none where N exceeds max_entries)
+long vrt_test_emitter_list(const uint32_t *records, size_t n_records, const int *wmin, const int *wmax, uint64_t max_entries, int32_t *out, size_t cap) {
+    if (!records || !wmin || !wmax || (cap && !out)) return VRT_E_INVALID;
+    std::vector<vrt::Record> recs(n_records);
+    for (size_t i = 0; i < n_records; ++i) recs[i] = vrt::Record{records[2 * i], records[2 * i + 1]};
+    std::vector<int32_t> list;
+    const uint64_t n = emitter_list(recs, wmin, wmax, max_entries, list);
+    const size_t take = list.size() / 4 < cap ? list.size() / 4 : cap;
+    for (size_t i = 0; i < take * 4; ++i) out[i] = list[i];
+    return (long)n;
+}
 
 // Arithmetic-contract probe (math_probe_kernel / math_probe_full_kernel): out[i] = op(x[i], y[i]) on `device`; host arrays, synchronous.
 int vrt_test_math(int device, int op, const float *x, const float *y, float *out, int n) {

@@ -25,7 +25,7 @@ using Accum = vrt_ctx::Accum;
 bool same_inputs(const vrt_ctx *c, const Accum &ac) {
     return std::memcmp(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj) == 0 && std::memcmp(ac.inv_view, c->inv_view, sizeof ac.inv_view) == 0 &&
            std::memcmp(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos) == 0 && std::memcmp(&ac.params, &c->params, sizeof ac.params) == 0 &&
-           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc)) &&   // the primary modes ignore the depth and the sun disc
+           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc && ac.emitter_sampling == c->emitter_sampling)) &&   // the primary modes ignore the depth, the sun disc and emitter sampling
            ac.tree_gen == c->tree_gen;
 }
 
@@ -36,6 +36,7 @@ void take_inputs(const vrt_ctx *c, Accum &ac) {
     std::memcpy(ac.lens, c->lens, sizeof ac.lens);
     ac.path_depth = c->path_depth;
     ac.sun_disc = c->sun_disc;
+    ac.emitter_sampling = c->emitter_sampling;
     ac.params = c->params;
     ac.tree_gen = c->tree_gen;
 }
@@ -183,6 +184,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     const bool deep = mode == VRT_MODE_FULL && a.path_depth > 1u;   // the kernels that honour the path depth (vrt_set_path_depth)
     const bool sun_on = mode == VRT_MODE_FULL && acc.sun > 0.0f;    // ... and the sun disc (vrt_set_sun_disc), at every depth
     const vrt::Sun sun = sun_on ? sun_block(a.light_dir, acc.sun) : vrt::Sun{};   // radius 0: nothing is made, nothing is passed
+    const bool emit_on = mode == VRT_MODE_FULL && acc.emit;         // ... and emitter sampling (vrt_set_emitter_sampling): the general path tracer only
+    if (emit_on && two_pass) return hipErrorInvalidValue;           // the dispatcher does not choose the opaque routes for it
     const vrt::accum::HdrFrame hf{ac.d_pass1, ac.d_id, ac.d_hframe};
     q.sums = ac.d_sums;
     q.pass1_rgba = ac.d_pass1;
@@ -230,7 +233,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         q.n = 1u;
         if (adaptive) e = launch::adaptive_tiles(tl, s);
         if (e == hipSuccess)
-            e = sun_on ? launch::accum_full_sun(hdr, src, v, a, vs, q, adaptive, l, sun, grid, s)
+            e = emit_on ? launch::accum_full_emit(hdr, src, v, a, vs, q, adaptive, l, vrt::Emit{sun, ac.emit_list, ac.emit_n}, grid, s)
+                : sun_on ? launch::accum_full_sun(hdr, src, v, a, vs, q, adaptive, l, sun, grid, s)
                 : deep ? launch::accum_full_deep(hdr, src, v, a, vs, q, adaptive, l, grid, s) : launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
     }
     return e;
@@ -265,6 +269,14 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
     if (!c->have_camera) return vrt_fail(c, VRT_E_STATE, "vrt_accum_add: no camera set (call vrt_set_camera first)");
     if (n_samples == 0) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_add: n_samples must be at least 1");
     // the restart rule: anything a sample depends on changed since the first sample in the sums -> the sums start again at `first`
+    // emitter sampling (vrt_set_emitter_sampling): the list of the current tree, before anything is queued
+    const bool sampling = ac.mode == VRT_MODE_FULL && c->emitter_sampling;
+    if (sampling) {
+        const int re = ensure_emitters(c, "vrt_accum_add", true);
+        if (re) return re;
+        ac.emit_list = c->emitters.d_list;
+        ac.emit_n = (uint32_t)c->emitters.n;
+    }
     const bool restart = ac.total == 0 || !same_inputs(c, ac);
     const uint32_t base = restart ? 0u : ac.total;
     if (n_samples > vrt::accum::kMaxSamples - base)   // an adaptive accumulation: rounds
@@ -321,6 +333,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
     } else if (r == VRT_OK) {
         AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
         step.sun = ac.mode == VRT_MODE_FULL ? ac.sun_disc : 0.0f;
+        step.emit = sampling && c->emitters.n > 0;   // an empty list: the launches of sampling off
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again

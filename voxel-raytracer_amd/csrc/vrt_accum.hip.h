@@ -188,6 +188,14 @@ struct SunLensSource {
     const Lens &L;
     const Sun &S;
 };
+// ... and for the kernels over EmitPaths<...> (include/vrt.h vrt_set_emitter_sampling): the last argument is the Emit, Sun included
+struct EmitCornerSource { static constexpr bool kJitter = false, kLens = false; const Emit &S; };
+struct EmitJitterSource { static constexpr bool kJitter = true, kLens = false; const Emit &S; };
+struct EmitLensSource {
+    static constexpr bool kJitter = false, kLens = true;
+    const Lens &L;
+    const Emit &S;
+};
 
 // ---- the kernels of the three shapes ----
 // L...: the lens kernels' fourth argument, the Lens. Each body is its kernel's own and writes out its trace call per source and its
@@ -289,7 +297,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
-    if constexpr (sun_paths<TRAV>::value) tc_.sun = src.S;
+    if constexpr (emit_paths<TRAV>::value) TRAV::take(tc_, src.S);
+    else if constexpr (sun_paths<TRAV>::value) tc_.sun = src.S;
     int px, py;
     if constexpr (ADAPT) {
         if (!listed_pixel<BLOCK>(a, q, px, py)) return;

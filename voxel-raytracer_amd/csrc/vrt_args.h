@@ -17,6 +17,16 @@ struct Sun {
     float Ln[3], T[3], B[3];
 };
 
+// Emitter sampling (include/vrt.h vrt_set_emitter_sampling): the context's emitter list on the device -- n entries of four int32
+// {lo.x, lo.y, lo.z, size}, ascending by (lo.x, lo.y, lo.z) (vrt_emitters.h emitter_list()) -- and the launch's Sun beside it (all zero
+// without a sun disc: nothing is drawn for it). A by-value kernel argument of its own of the kernels over EmitPaths<...>, in the
+// Sun's place.
+struct Emit {
+    Sun sun;
+    const int32_t *list;
+    uint32_t n;
+};
+
 // One camera and the two images it renders into. A launch carries up to kMaxViews of them (blockIdx.y selects
 // the view): frames of one scene that are known together -- a stereo pair, the next frames of a camera path, the
 // views of a light-field rig -- share one launch, so the drain of one view's last waves is filled by the next

@@ -329,6 +329,19 @@ template <class T> struct SunPaths : DeepPaths<T> {
 template <class T, class = void> struct sun_paths { static constexpr bool value = false; };
 template <class T> struct sun_paths<T, decltype((void)T::kSunPaths)> { static constexpr bool value = T::kSunPaths; };
 
+// ... and EmitPaths<T>, SunPaths<T> for the kernels that also sample the emitter list (include/vrt.h vrt_set_emitter_sampling;
+// vrt_full.hip.h emit_connect()): `static constexpr bool kEmitPaths = true`, and a Ctx that carries the list (pointer, N) beside the
+// Sun. The Sun is honoured only where its tan_radius > 0, a wave-uniform branch: at radius 0 the family draws nothing for it. One
+// family serves every depth 1..8 and every radius.
+template <class T> struct EmitPaths : SunPaths<T> {
+    static constexpr bool kEmitPaths = true;
+    struct Ctx : SunPaths<T>::Ctx { const int32_t *emit; uint32_t n_emit; };
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
+    static VRT_DEV void take(Ctx &c, const Emit &e) { c.sun = e.sun; c.emit = e.list; c.n_emit = e.n; }
+};
+template <class T, class = void> struct emit_paths { static constexpr bool value = false; };
+template <class T> struct emit_paths<T, decltype((void)T::kEmitPaths)> { static constexpr bool value = T::kEmitPaths; };
+
 // A primary ray the miss-tile proof covers ("Miss tiles"): no component of its direction within 2e-8 of (-1e-8, 0], so that after
 // march()'s renormalisation (a factor within a few ulps of 1) none lies in (-1e-8, 0] and every step of the DDA has t >= 0.
 VRT_DEV bool miss_forward(F3 d) {

@@ -188,6 +188,68 @@ VRT_DEV RayS make_ray(F3 o, F3 d, float iof, float w, const float tint[3], float
     return r;
 }
 
+// Emitter sampling (include/vrt.h vrt_set_emitter_sampling, steps 1-6), for the kernels over EmitPaths<...>: the next-event estimate
+// of one shadowing vertex. Four draws pick an emitter, one of its six faces and a point q on it; the connection ray is the bounce
+// ray with the direction towards q (origin x = hitPoint + normal * 1e-1, rayIOF n1, the vertex's weight, tint = transmittedColor *
+// surfaceColor, the last voxel -- mc, md -- as its medium); it contributes where its first hit lies in the emitter's cube: the
+// shader's own depth > 0 emissive term E times g = cs * cl * area / (PI * r2), area = N * 6 * size^2.
+template <class TRAV, class OVER_PI>
+VRT_DEV void emit_connect(const KArgs &a, const typename TRAV::Ctx &tc_, F3 hp, F3 normal, float n1, const float tint[3], float weight,
+                          const float mc[3], float md, uint32_t &rng, const OVER_PI &over_pi, float fc[3]) {
+    const float kPI = 3.14159265359f;
+    const float u0 = rng_next(rng), uf = rng_next(rng), ua = rng_next(rng), ub = rng_next(rng);
+    const int n = (int)tc_.n_emit;
+    int j = (int)(u0 * (float)n);
+    j = j < n - 1 ? j : n - 1;
+    const int4 e = *reinterpret_cast<const int4 *>(tc_.emit + (size_t)j * 4u);
+    int f = (int)(uf * 6.0f);
+    f = f < 5 ? f : 5;
+    const int ax = f >> 1, side = f & 1;
+    const float sz = (float)e.w;
+    const float fixed = side ? sz : 0.0f;
+    // q[ax] = lo[ax] + (side ? sz : 0), q[a1] = lo[a1] + ua * sz, q[a2] = lo[a2] + ub * sz with a1 = (ax + 1) % 3, a2 = (ax + 2) % 3
+    const F3 q{(float)e.x + (ax == 0 ? fixed : (ax == 2 ? ua * sz : ub * sz)), (float)e.y + (ax == 1 ? fixed : (ax == 0 ? ua * sz : ub * sz)),
+               (float)e.z + (ax == 2 ? fixed : (ax == 1 ? ua * sz : ub * sz))};
+    const F3 x = add3(hp, scale3(normal, 1e-1f));
+    const F3 w = sub3(q, x);
+    const float r2 = dot3(w, w);
+    if (!(r2 > 0.0f)) return;
+    const F3 dir = scale3(w, 1.0f / __builtin_sqrtf(r2));
+    const float cs = dot3(normal, dir);
+    const float cl = side ? -comp(dir, ax) : comp(dir, ax);
+    if (!(cs > 0.0f && cl > 0.0f)) return;   // the four draws stay spent
+    Hit h;
+    if (!TRAV::march(a, tc_, x, dir, n1, iof_to_byte(n1), h)) return;
+    if (h.map.x < e.x || h.map.x >= e.x + e.w || h.map.y < e.y || h.map.y >= e.y + e.w || h.map.z < e.z || h.map.z >= e.z + e.w) return;
+    // the hit as the loop evaluates a hit of a ray of depth >= 1, up to the emissive test
+    float dim;
+    if (a.voxel_scale != 1.0f) {
+        const F3 hpw{h.point.x / a.voxel_scale, h.point.y / a.voxel_scale, h.point.z / a.voxel_scale};
+        dim = 0.0f + len3(sub3(hpw, x)) / a.voxel_scale;
+    } else {
+        dim = 0.0f + len3(sub3(h.point, x));
+    }
+    Decoded hv = decode_leaf(h.h0, h.h1);
+    const Decoded last = decode_leaf(h.p0, h.p1);
+    if (hv.c[3] <= 0.0f) hv.p[1] = 0.0f;
+    float sc[3], tc[3] = {tint[0], tint[1], tint[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sc[k] = hv.c[3] > 0.0f ? hv.c[k] : last.c[k];
+    if (dim > 1e-6f && md > 0.0f) absorb(tc, md, dim, mc);
+    if (h.map.x == a.highlighted[0] && h.map.y == a.highlighted[1] && h.map.z == a.highlighted[2]) {
+        sc[0] = 1.0f - sc[0]; sc[1] = 1.0f - sc[1]; sc[2] = 1.0f - sc[2];
+    }
+    const float emission = hv.p[1] * 10.0f;
+    if (!(emission > 0.0f)) return;
+    const float area = ((float)n * 6.0f) * (sz * sz);
+    const float g = ((cs * cl) * area) / (kPI * r2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float ek = over_pi(tc[k] * sc[k] * emission * weight);
+        fc[k] = fc[k] + ek * g;
+    }
+}
+
 // sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
 // with JIT also the jittered sample whose ray is traced; LENS: the ray `lens` instead, origin and medium included (pixel_ray())
 // HDR: fc_out[3] takes the float colour unorm8() receives
@@ -254,6 +316,10 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     // Sun disc (include/vrt.h vrt_set_sun_disc), honoured by the kernels over SunPaths<...>: a vertex that casts a shadow ray draws
     // its own light direction L' (sun_dir()) and takes lit and n.l from it; the translucent branch keeps L.
     constexpr bool SUN = sun_paths<TRAV>::value;
+    // Emitter sampling (include/vrt.h vrt_set_emitter_sampling), honoured by the kernels over EmitPaths<...>: that vertex then connects
+    // to a point of the emitter list (emit_connect()), and in exchange a ray of depth >= 1 that hits an emissive voxel adds nothing.
+    // These kernels take the Sun only where it has a radius.
+    constexpr bool EMIT = emit_paths<TRAV>::value;
 
 #ifdef VRT_EXP_STATS   // experiment builds only (tools/room_stats.sh): what the wave's time is made of, left in tile_cost
     unsigned long long st_acc = 0;
@@ -378,8 +444,10 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 for (int k = 0; k < 3; ++k) fc[k] = fc[k] + tc[k] * sc[k] * emission * r.weight;
                 continue;
             } else if (emission > 0.0f) {
+                if constexpr (!EMIT) {   // (EMIT: the vertex before has sampled the emitters itself)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sc[k] * emission * r.weight);
+                    for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sc[k] * emission * r.weight);
+                }
                 continue;
             }
             if (DEEP ? r.depth < max_depth : r.depth == 0) {
@@ -391,7 +459,12 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
 #endif
                 F3 ld = light;
                 float nl = ndotl;
-                if constexpr (SUN) {
+                if constexpr (EMIT) {
+                    if (tc_.sun.tan_radius > 0.0f) {
+                        ld = sun_dir(tc_.sun, rng);
+                        nl = fmax_c(dot3(normal, ld), 0.0f);
+                    }
+                } else if constexpr (SUN) {
                     ld = sun_dir(tc_.sun, rng);
                     nl = fmax_c(dot3(normal, ld), 0.0f);
                 }
@@ -404,6 +477,10 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 for (int k = 0; k < 3; ++k) {
                     const float direct = gl[k] * (float)lit * nl;
                     fc[k] = fc[k] + over_pi(direct * sc[k] * tc[k] * r.weight);
+                }
+                if constexpr (EMIT) {   // four draws, after the sun's and before the bounce's
+                    const float tint[3] = {tc[0] * sc[0], tc[1] * sc[1], tc[2] * sc[2]};
+                    emit_connect<TRAV>(a, tc_, hp, normal, n1, tint, r.weight / (float)kIndirectSamples, last.c, last.c[3] * 5.0f, rng, over_pi, fc);
                 }
             } else {
                 const float amb = fmax_c(1.0f - det_expf(-r.dim / 512.0f), 0.01f);

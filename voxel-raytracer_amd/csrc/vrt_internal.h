@@ -32,6 +32,7 @@
 
 #include "vrt_args.h"
 #include "vrt_sun.h"
+#include "vrt_emitters.h"
 #include "vrt_devbuf.h"
 #include "vrt_layout.h"
 #include "vrt_miss.h"
@@ -92,6 +93,17 @@ struct vrt_ctx {
     float lens[2] = {0.0f, 1.0f};   // vrt_set_lens: aperture, focus distance (the progressive accumulation only)
     int path_depth = 1;             // vrt_set_path_depth: the samples of VRT_MODE_FULL in accumulations and ray batches (frames: always 1)
     float sun_disc = 0.0f;          // vrt_set_sun_disc: the tangent of the sun's angular radius, honoured where the path depth is
+    bool emitter_sampling = false;  // vrt_set_emitter_sampling: next-event estimation towards the emitter list, honoured where the path depth is
+    // the emitter list (vrt_emitters.cpp ensure_emitters()) of the tree generation and world bounds it was made for
+    struct Emitters {
+        bool built = false;
+        uint64_t tree_gen = 0;
+        int wmin[3] = {0, 0, 0}, wmax[3] = {0, 0, 0};
+        uint64_t n = 0;                  // N; above VRT_MAX_EMITTERS nothing is held
+        std::vector<int32_t> list;       // 4 per entry: lo.x, lo.y, lo.z, size
+        DevBuf<int32_t> d_list;          // the same on the device
+    };
+    Emitters emitters;
     int variant = 0;
     int denoise_variant = 0;  // VRT_OPT_DISPLAY_KERNEL = denoise::Args::rows_path: 0 each wave the cheaper walk; 2, 3: one walk forced
     // scratch outputs for the host-buffer dispatch
@@ -221,6 +233,9 @@ struct vrt_ctx {
         float lens[2] = {0.0f, 1.0f};
         int path_depth = 1;
         float sun_disc = 0.0f;
+        bool emitter_sampling = false;
+        const int32_t *emit_list = nullptr;      // the context's emitter list as the add that queues a step found it (emitters.d_list, N)
+        uint32_t emit_n = 0;
         vrt_params params{};
         uint64_t tree_gen = 0;
         DevBuf<uint32_t> d_sums;                 // 4 words per pixel
@@ -285,6 +300,9 @@ int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm);
 // itself. The light block: the uniforms of the shading and the shadow ray's set-up.
 void fill_scene_args(const vrt_ctx *c, vrt::KArgs &a);
 void fill_light_args(const vrt_ctx *c, vrt::KArgs &a);
+// The context's emitter list for the current tree and bounds (vrt_emitters.cpp), made if it is not: c->emitters. VRT_E_STATE before an
+// upload and while a patch batch is open; with `sampling` also where the list exceeds VRT_MAX_EMITTERS.
+int ensure_emitters(vrt_ctx *c, const char *what, bool sampling);
 // sun_block(light_dir, tan_radius), the sun disc's block for a launch whose light direction is light_dir: vrt_sun.h
 // The context's variant (vrt_set_variant) as this scene allows it: the record-array kernels without a wide layout, the
 // explicit-AABB ones where a unit-size node is internal. Frames and ray batches start from it.
@@ -312,12 +330,15 @@ struct ProfSlot {
 // (hdr: an HDR accumulation, vrt_accum_keep_hdr; the kernels' HDR forms. frame_only, with hdr, modes 0 / 1 from the corner: no
 // sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
 // (sun > 0: VRT_MODE_FULL with a sun disc of that tangent radius, vrt_set_sun_disc; the kernels over SunPaths<...>)
+// (emit: VRT_MODE_FULL with emitter sampling on and a list that is not empty, vrt_set_emitter_sampling; the general path tracer over
+// EmitPaths<...>, never the opaque routes)
 struct AccumStep {
     uint32_t first, n;
     bool jitter;
     float aperture = 0.0f, focus = 1.0f;
     bool adaptive = false, hdr = false, frame_only = false;
     float sun = 0.0f;
+    bool emit = false;
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);

@@ -176,6 +176,18 @@ inline hipError_t accum_bounce_sun(bool hdr, const KArgs &a, const ViewSet &vs, 
     return hdr ? accum_bounce_hdr_sun(a, vs, q, adaptive, sun, grid, s) : accum_bounce_sun(a, vs, q, adaptive, sun, grid, s);
 }
 
+// vrt_launch_accum_emit.hip, vrt_launch_accum_hdr_emit.hip: one sample of the general full path tracer with emitter sampling
+// (include/vrt.h vrt_set_emitter_sampling), at any path depth and sun radius: kernels over EmitPaths<...>, which take `em` -- the
+// context's emitter list and the launch's Sun -- as their last argument. The opaque routes have no such form.
+hipError_t accum_full_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
+                           const accum::Lens &l, const Emit &em, int grid, hipStream_t s);
+hipError_t accum_full_hdr_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                               const accum::Lens &l, const Emit &em, int grid, hipStream_t s);
+inline hipError_t accum_full_emit(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                                  bool adaptive, const accum::Lens &l, const Emit &em, int grid, hipStream_t s) {
+    return hdr ? accum_full_hdr_emit(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emit(src, v, a, vs, q, adaptive, l, em, grid, s);
+}
+
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
@@ -198,6 +210,12 @@ hipError_t shade_rays_sun(const Variant &v, const KArgs &a, const ViewSet &vs, c
                           hipEvent_t ev0, hipEvent_t ev1);
 hipError_t shade_rays_hdr_sun(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Sun &sun, uint32_t grid,
                               hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
+// vrt_launch_rays_emit.hip, vrt_launch_rays_hdr_emit.hip: VRT_MODE_FULL of the same with emitter sampling, at any path depth and sun radius
+hipError_t shade_rays_emit(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const Emit &em, uint32_t grid, hipStream_t s,
+                           hipEvent_t ev0, hipEvent_t ev1);
+hipError_t shade_rays_hdr_emit(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Emit &em, uint32_t grid,
+                               hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

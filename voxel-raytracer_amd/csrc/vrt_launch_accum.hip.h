@@ -130,6 +130,25 @@ hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewS
     });
 }
 
+// EMIT (vrt_launch_accum_emit.hip, vrt_launch_accum_hdr_emit.hip): the general full path tracer over EmitPaths<...>, in the two
+// normalised traversals of the DEEP forms; the kernels' last argument is the Emit
+template <bool HDR>
+hipError_t full_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
+                     const accum::Lens &l, const Emit &em, int grid, hipStream_t s) {
+    const auto f = [&](auto sh) {
+        using S = decltype(sh);
+        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
+        if (src == accum::Source::kCorner)
+            return go(accum::full_accum_kernel<accum::EmitCornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, Emit>, grid, S::kBlock, s, a, vs, qs, em);
+        if (src == accum::Source::kJitter)
+            return go(accum::full_accum_kernel<accum::EmitJitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, Emit>, grid, S::kBlock, s, a, vs, qs, em);
+        return go(accum::full_accum_kernel<accum::EmitLensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, Emit>, grid, S::kBlock, s, a, vs, qs, l, em);
+    };
+    if (v.trav >= 3) return shape<EmitPaths<v4::TravAny>, 64, 5>(adaptive, f);
+    if (v.trav >= 1) return shape<EmitPaths<v1::Trav>, 256, 1>(adaptive, f);
+    return hipErrorInvalidValue;
+}
+
 template <bool HDR, bool DEEP = false, class... SUN>
 hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s, const SUN &...sun) {
     if constexpr (sizeof...(SUN) != 0) {

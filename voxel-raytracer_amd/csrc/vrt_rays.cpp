@@ -79,6 +79,16 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     const bool sun_on = mode == VRT_MODE_FULL && c->sun_disc > 0.0f;   // vrt_set_sun_disc: the kernels over SunPaths<...>, at every depth
     if (sun_on) a.path_depth = (uint32_t)c->path_depth;
     const vrt::Sun sun = sun_on ? sun_block(a.light_dir, c->sun_disc) : vrt::Sun{};
+    // vrt_set_emitter_sampling: the kernels over EmitPaths<...>, at every depth and sun radius; an empty list: the launches of sampling off
+    bool emit_on = false;
+    if (mode == VRT_MODE_FULL && c->emitter_sampling) {
+        const int re = ensure_emitters(c, "vrt_shade_rays", true);
+        if (re) return re;
+        emit_on = c->emitters.n > 0;
+    }
+    if (emit_on) a.path_depth = (uint32_t)c->path_depth;
+    vrt::Emit em{};
+    if (emit_on) em = vrt::Emit{sun, c->emitters.d_list.get(), (uint32_t)c->emitters.n};
 
     vrt::rays::Args q;
     q.origins = d_origins;
@@ -104,11 +114,13 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
         hq.n_total = hdr->n_prior + n_samples;
         hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
         hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = sun_on ? vrt::launch::shade_rays_hdr_sun(v, a, vs, hq, sun, grid, s, prof.ev0, prof.ev1)
+        e = emit_on ? vrt::launch::shade_rays_hdr_emit(v, a, vs, hq, em, grid, s, prof.ev0, prof.ev1)
+            : sun_on ? vrt::launch::shade_rays_hdr_sun(v, a, vs, hq, sun, grid, s, prof.ev0, prof.ev1)
             : deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
                    : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
     } else {
-        e = sun_on ? vrt::launch::shade_rays_sun(v, a, vs, q, sun, grid, s, prof.ev0, prof.ev1)
+        e = emit_on ? vrt::launch::shade_rays_emit(v, a, vs, q, em, grid, s, prof.ev0, prof.ev1)
+            : sun_on ? vrt::launch::shade_rays_sun(v, a, vs, q, sun, grid, s, prof.ev0, prof.ev1)
             : deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
     }
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
