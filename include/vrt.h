@@ -401,11 +401,57 @@ int vrt_set_sun_disc(vrt_ctx *ctx, float tan_radius);
  * which the LIFO stack pops rays.
  * Consequences: the expectation of a sample equals that of the same sample with sampling off -- the two estimators integrate the same
  * quantity, one over direction, one over emitter area (the choice is uniform over emitters and over the six faces: unbiased, but
- * wasteful where emitter sizes differ much). Sample k itself is a different, equally valid sample: the stream carries four more draws
+ * wasteful where emitter sizes differ much -- vrt_set_emitter_importance below). Sample k itself is a different, equally valid sample: the stream carries four more draws
  * per shadowing vertex. */
 #define VRT_MAX_EMITTERS (1u << 20)
 int vrt_set_emitter_sampling(vrt_ctx *ctx, int enable);
 long vrt_emitters(vrt_ctx *ctx, int32_t *out, size_t cap);
+
+/* Emitter importance: how a vertex picks from the emitter list. vrt_set_emitter_importance(ctx, VRT_EMIT_POWER) replaces the uniform
+ * choice of steps 1-2 above -- one of N emitters, one of six faces -- by one that picks the emitter in proportion to its power and the
+ * face among those turned towards the vertex. mode is VRT_EMIT_UNIFORM (default) or VRT_EMIT_POWER; anything else is VRT_E_INVALID
+ * (the previous value still holds). It is context state, like the flag, and vrt_set_emitter_sampling keeps its 0 / 1 contract. The
+ * mode is read only where sampling is on and the list is not empty: otherwise the same kernels run and the same bytes come out at
+ * either mode. Exactly the callers that honour the flag honour the mode (see "Who honours it" above, at every D and any sun radius),
+ * and it is one of the inputs of an accumulation of VRT_MODE_FULL exactly as the flag is: a change restarts the sums at `first`, the
+ * same value set again changes nothing; accumulations of the primary modes do not restart. With VRT_EMIT_UNIFORM every launch and
+ * every byte is that of the rule above.
+ *
+ * Weights. Entry j of the list with the record words (w0, w1) of its leaf, as the shader's decoder reads them, has the integer weight
+ *     W_j = size^2 * illum * (R + G + B),   illum = (w1 >> 8) & 0xff,   R, G, B the low three bytes of w0;
+ * a unit cell of a merged leaf that is no cube takes that leaf's record. With C_j the inclusive prefix sum and Wtot = C_{N-1} the
+ * thresholds are, in exact integers,
+ *     Wtot > 0:   T_j = (j + 1) + floor(C_j * (2^24 - N) / Wtot)
+ *     Wtot == 0:  T_j = floor((j + 1) * 2^24 / N)
+ * so that T is strictly increasing, T_{N-1} = 2^24 and every emitter holds at least one of the 2^24 ticks: a black or highlighted
+ * emitter is never given probability zero, and the estimator stays unbiased. The table is made and uploaded with the list, by the same
+ * lazy rule.
+ *   vrt_emitter_cdf behaves as vrt_emitters does: it returns N and writes the first min(N, cap) thresholds T_j to out, in the list's
+ * order (out may be NULL where cap is 0), whatever the flag and the mode; for N > VRT_MAX_EMITTERS it writes none. VRT_E_STATE before
+ * any upload and while a patch batch is open. With sampling on, VRT_EMIT_POWER set and N > VRT_MAX_EMITTERS the calls that honour
+ * sampling return the same VRT_E_STATE as with VRT_EMIT_UNIFORM.
+ *
+ * Per vertex (all arithmetic float32, every operation rounded on its own, no contraction), at every vertex that casts a shadow ray, at
+ * the position the uniform rule occupies; the four draws u0, uf, ua, ub are taken in the same order:
+ *   1. The emitter: t = min((uint32)(u0 * 16777216.0f), 16777215) (rand() can return exactly 1.0f: the clamp is for that case);
+ *      j = the smallest index with T_j > t; ticks = T_j - T_{j-1} with T_{-1} = 0; p = (float)ticks * 0x1p-24f. Corner lo and
+ *      sz = (float)size as before.
+ *   2. The faces: x = hitPoint + normal * 1e-1. Per axis k in the order 0, 1, 2 the low face is visible if x[k] < (float)lo[k], the
+ *      high face if x[k] > (float)lo[k] + sz, otherwise neither. m = the number of visible faces, 0 to 3. m == 0 (x inside the cube's
+ *      slab on every axis): nothing more happens, the four draws stay spent. Otherwise i = min((int)(uf * (float)m), m - 1), and the
+ *      i-th visible face in axis order gives ax and side; a1, a2 and the point q on the face are those of step 2 above.
+ *   3. Steps 3 to 6 above, word for word: w, r2, dir, cs, cl, the !(cs > 0 && cl > 0) test, the connection ray, the march, the in-cube
+ *      test, the hit's evaluation, E_k -- with the weight
+ *        g = ((cs * cl) * ((float)m * (sz * sz))) / ((PI * r2) * p)
+ *   4. Step 7 above is unchanged: a ray of depth >= 1 that hits an emissive voxel adds nothing and ends.
+ * Consequences: the same expectation as VRT_EMIT_UNIFORM and as sampling off; a bright emitter is reached in proportion to its
+ * share of the list's power instead of once in N vertices, and no connection is drawn towards a face turned away. The threshold
+ * search is a lower bound of ceil(log2 N) steps on a global table of at most 4 MB. Not done: multiple importance sampling with the
+ * bounce, faces by projected solid angle, the stack-free opaque routes, vrt_multi. */
+#define VRT_EMIT_UNIFORM 0
+#define VRT_EMIT_POWER   1
+int vrt_set_emitter_importance(vrt_ctx *ctx, int mode);
+long vrt_emitter_cdf(vrt_ctx *ctx, uint32_t *out, size_t cap);
 
 /* Adaptive accumulation: stop sampling pixels whose mean has converged. vrt_accum_begin_adaptive is vrt_accum_begin_ex (same
  * modes, VRT_ACCUM_JITTER, the lens as context state) plus a stopping rule, which belongs to the accumulation. VRT_E_INVALID

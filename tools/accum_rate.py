@@ -43,6 +43,14 @@ kernels:
 
     python3 tools/accum_rate.py --path-depth 1 4 --emit 0 1 --scenes lamp_room_1080p room_inside_1080p --samples 16 --out profiles/emit_rate.jsonl
 
+--emit-power M [M ...] (with --emit) measures each setting with sampling on once per importance mode too (vrt_set_emitter_importance, 0
+uniform or 1 power) and records it (emitter_importance); with sampling off the mode is not read and the row is measured once. The
+scene power_room_1080p is tests/emit_power_worlds.py's room seen from inside: a merged lamp of size 4 and 256 dim singles:
+
+    python3 tools/accum_rate.py --path-depth 1 4 --emit 0 1 --emit-power 0 1 --scenes power_room_1080p lamp_room_1080p --samples 16 --out profiles/emit_power_rate.jsonl
+
+--variant V (with --path-depth) measures with vrt_set_variant(V) and records it (variant); 1 takes the record-array kernels.
+
 --out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
 --adaptive takes none of --path-depth, --scenes and --samples (it measures its own scenes and rounds) and refuses them.
 """
@@ -65,8 +73,9 @@ SCENES = {   # name -> (map, pose): the golden 1080p / 4K frames' poses
     "nature_1080p": ("nature", (60.5, 80.5, 200.5), -90.0, -20.0),
     "room_inside_1080p": ("room", (14.5, 30.5, 16.5), 32.0, -10.0),
     "lamp_room_1080p": ("lamp", (36.5, 44.5, 50.5), -38.0, 8.0),   # tests/emit_worlds.py: POSE
+    "power_room_1080p": ("power", (36.5, 44.5, 50.5), -38.0, 8.0),   # tests/emit_power_worlds.py: POSE
 }
-DEFAULT_SCENES = sorted(s for s in SCENES if SCENES[s][0] != "lamp")   # the lamp room: on request (--scenes), for --emit
+DEFAULT_SCENES = sorted(s for s in SCENES if SCENES[s][0] not in ("lamp", "power"))   # the two lamp rooms: on request (--scenes), for --emit
 
 
 def main():
@@ -85,15 +94,21 @@ def main():
     ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
     ap.add_argument("--emit", nargs="+", type=int, default=None, choices=(0, 1), metavar="E",
                     help="with --path-depth: once per setting of emitter sampling (vrt_set_emitter_sampling)")
+    ap.add_argument("--emit-power", nargs="+", type=int, default=None, choices=(0, 1), metavar="M",
+                    help="with --emit: sampling on once per importance mode (vrt_set_emitter_importance)")
+    ap.add_argument("--variant", type=int, default=None, metavar="V",
+                    help="with --path-depth: the traversal variant (vrt_set_variant; 1: the record-array kernels), recorded as variant")
     ap.add_argument("--scenes", nargs="+", default=DEFAULT_SCENES, choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
-    if args.adaptive and (args.path_depth or args.sun or args.emit or args.scenes != DEFAULT_SCENES or args.samples != list(SAMPLES)):
-        ap.error("--adaptive takes none of --path-depth, --sun, --emit, --scenes, --samples")
+    if args.adaptive and (args.path_depth or args.sun or args.emit or args.emit_power or args.scenes != DEFAULT_SCENES or args.samples != list(SAMPLES)):
+        ap.error("--adaptive takes none of --path-depth, --sun, --emit, --emit-power, --scenes, --samples")
     if args.sun and not args.path_depth:
         ap.error("--sun goes with --path-depth")
     if args.emit and not args.path_depth:
         ap.error("--emit goes with --path-depth")
+    if args.emit_power and not args.emit:
+        ap.error("--emit-power goes with --emit")
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
@@ -104,14 +119,17 @@ def main():
     d_rgb = ctx.device_alloc(W * H * 12) if args.hdr else None
     rows = []
     last_spread = [0.0, 0.0]   # of the last add_ms(): the fastest and the slowest timed add
-    for name, depth, sun, emit in [(s, d, r, e) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])
-                                   for e in (args.emit or [None])]:
+    for name, depth, sun, emit, imp in [(s, d, r, e, m) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])
+                                        for e in (args.emit or [None]) for m in ((args.emit_power if e else args.emit_power[:1]) if args.emit_power else [None])]:
         m, pos, yaw, pitch = SCENES[name]
         if m == "room":
             w = room_world(V)
         elif m == "lamp":
             import emit_worlds
             w = emit_worlds.lamp_room(V)
+        elif m == "power":
+            import emit_power_worlds
+            w = emit_power_worlds.room(V)
         else:
             w = V.World()
             assert w.load_vox(os.path.join(MAPS, m + ".vox"))
@@ -121,12 +139,16 @@ def main():
         ip, iv, cp, _ = V.camera_block(pos, yaw, pitch, W, H)
         ctx.set_camera(ip, iv, cp)
         ctx.set_params(ctx.default_params())
+        if args.variant is not None:
+            ctx.set_variant(args.variant)
         if depth is not None:
             ctx.set_path_depth(depth)
         if sun is not None:
             ctx.set_sun_disc(sun)
         if emit is not None:
             ctx.set_emitter_sampling(emit)
+        if imp is not None:
+            ctx.set_emitter_importance(imp if emit else 0)
         opaque = V.tree_is_opaque(tex)
         for mname in args.mode:
             mode = V.MODES[mname]
@@ -171,12 +193,16 @@ def main():
                         row.update(mode=mname, jitter=bool(args.jitter))
                     if depth is not None:
                         row.update(path_depth=depth, per_sample_ms=round(ms / n, 4), add_ms_min_max=[round(v, 4) for v in last_spread])
+                        if args.variant is not None:
+                            row.update(variant=args.variant)
                     if sun is not None:
                         row.update(sun_disc=sun)
                     if emit is not None:
                         row.update(emitter_sampling=emit, emitters=len(ctx.emitters()))
                         if emit and row["emitters"]:
                             row["path"] = "general"   # the opaque routes are not taken
+                        if imp is not None and emit:
+                            row.update(emitter_importance=imp)
                     if lens is None:
                         base_ms = ms
                     else:

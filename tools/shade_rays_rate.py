@@ -26,6 +26,12 @@ Prints one JSON object per line; --out writes them to a file too.
 once per setting of emitter sampling (vrt_set_emitter_sampling, 0 or 1), and records it (emitter_sampling):
 
     python3 tools/shade_rays_rate.py --path-depth 1 4 --emit 0 1 --append --out profiles/emit_rate.jsonl
+
+--emit-power M [M ...] (with --emit) measures sampling on once per importance mode too (vrt_set_emitter_importance, 0 uniform or 1
+power) and records it (emitter_importance); --emit-world power_room takes tests/emit_power_worlds.py's room (a merged lamp of size 4
+and 256 dim singles) instead of the lamp room:
+
+    python3 tools/shade_rays_rate.py --path-depth 1 4 --emit 0 1 --emit-power 0 1 --emit-world power_room --append --out profiles/emit_power_rate.jsonl
 """
 import argparse
 import json
@@ -81,7 +87,12 @@ def main():
     ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
     ap.add_argument("--emit", nargs="+", type=int, default=None, choices=(0, 1), metavar="E",
                     help="with --path-depth: in the lamp room, once per setting of emitter sampling (vrt_set_emitter_sampling)")
+    ap.add_argument("--emit-power", nargs="+", type=int, default=None, choices=(0, 1), metavar="M",
+                    help="with --emit: sampling on once per importance mode (vrt_set_emitter_importance)")
+    ap.add_argument("--emit-world", default="lamp_room", choices=("lamp_room", "power_room"), help="with --emit: the world")
     args = ap.parse_args()
+    if args.emit_power and not args.emit:
+        ap.error("--emit-power goes with --emit")
     if args.sun and not args.path_depth:
         ap.error("--sun goes with --path-depth")
     if args.emit and not args.path_depth:
@@ -89,7 +100,11 @@ def main():
     V = vrt_import.vrt()
     if args.emit:
         import emit_worlds
-        w = emit_worlds.lamp_room(V)
+        if args.emit_world == "power_room":
+            import emit_power_worlds
+            w = emit_power_worlds.room(V)
+        else:
+            w = emit_worlds.lamp_room(V)
     else:
         w = V.World()
         assert w.load_vox(os.path.join(ROOT, "tests", "golden", "maps", "dragon.vox"))
@@ -164,7 +179,7 @@ def main():
         box = ((-64, -64, -64), (192, 160, 128))
         pose = POSE
         if args.emit:   # the probes start inside the room
-            world = "lamp_room"
+            world = args.emit_world
             box = ((emit_worlds.LO + 1,) * 3, (emit_worlds.HI,) * 3)
             pose = (emit_worlds.POSE[:3], emit_worlds.POSE[3], emit_worlds.POSE[4])
         _, origin, dirs = frame_rays(V, W, H, pose)
@@ -184,18 +199,22 @@ def main():
             n = len(rd)
             d_o, d_d = upload(ro, rd)
             d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
-            for depth, sun, em in [(dd, r, e) for dd in args.path_depth for r in (args.sun or [None]) for e in (args.emit or [None])]:
+            for depth, sun, em, imp in [(dd, r, e, m) for dd in args.path_depth for r in (args.sun or [None]) for e in (args.emit or [None])
+                                        for m in ((args.emit_power if e else args.emit_power[:1]) if args.emit_power else [None])]:
                 ctx.set_path_depth(depth)
                 if sun is not None:
                     ctx.set_sun_disc(sun)
                 if em is not None:
                     ctx.set_emitter_sampling(em)
+                if imp is not None:
+                    ctx.set_emitter_importance(imp if em else 0)
                 for n_samples in (1, 4):
                     (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=2, width=width, n_samples=n_samples)],
                                   max(3, args.reps // 2))
                     m = float(np.median(ms))
                     emit({"case": case, "mode": 2, "path_depth": depth, **({} if sun is None else {"sun_disc": sun}),
-                          **({} if em is None else {"emitter_sampling": em}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
+                          **({} if em is None else {"emitter_sampling": em}),
+                          **({"emitter_importance": imp} if imp is not None and em else {}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
                           "kernel_ms_min_max": [round(float(ms.min()), 4), round(float(ms.max()), 4)],
                           "per_sample_ms": round(m / n_samples, 4), "paths_per_s": round(n * n_samples / (m * 1e-3)), "reps": len(ms)})
             for p in (d_o, d_d, d_rgba, d_id):

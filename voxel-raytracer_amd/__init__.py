@@ -27,6 +27,7 @@ MODES = {"primary": MODE_PRIMARY, "primary_shadow": MODE_PRIMARY_SHADOW, "full":
 ACCUM_JITTER = 1   # vrt_accum_begin_ex flags (include/vrt.h VRT_ACCUM_JITTER)
 MAX_PATH_DEPTH = 8   # include/vrt.h VRT_MAX_PATH_DEPTH (Context.set_path_depth)
 MAX_EMITTERS = 1 << 20   # include/vrt.h VRT_MAX_EMITTERS (Context.emitters, Context.set_emitter_sampling)
+EMIT_UNIFORM, EMIT_POWER = 0, 1   # include/vrt.h VRT_EMIT_* (Context.set_emitter_importance)
 TONEMAP_CLAMP, TONEMAP_REINHARD = 0, 1   # include/vrt.h VRT_TONEMAP_*
 TONEMAPS = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD}
 
@@ -287,6 +288,10 @@ def hip_lib():
         L.vrt_set_emitter_sampling.restype = C.c_int
         L.vrt_emitters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.vrt_emitters.restype = C.c_long
+        L.vrt_set_emitter_importance.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_set_emitter_importance.restype = C.c_int
+        L.vrt_emitter_cdf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.vrt_emitter_cdf.restype = C.c_long
         L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_uint32, C.c_uint32]
         L.vrt_accum_counts.argtypes = [C.c_void_p, C.c_void_p]
@@ -1016,6 +1021,39 @@ class Context:
         out = np.zeros((n, 4), np.int32)
         if n:
             got = self._L.vrt_emitters(self._h, out.ctypes.data, n)
+            if got < 0:
+                self._chk(got)
+            assert got == n
+        return out
+
+    def set_emitter_importance(self, mode):
+        """How a vertex picks from the emitter list where emitter sampling is on (vrt_set_emitter_importance): EMIT_UNIFORM (0,
+        default), one of N emitters and one of six faces, or EMIT_POWER (1), the emitter in proportion to its power (emitter_cdf())
+        and the face among those turned towards the vertex: the same expectation, less variance where emitters differ much. Read
+        only where sampling is on and the list is not empty. Any other value raises (VRT_E_INVALID) and the previous one holds."""
+        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or int(mode) not in (EMIT_UNIFORM, EMIT_POWER):
+            raise ValueError(f"emitter importance: expected EMIT_UNIFORM (0) or EMIT_POWER (1), got {mode!r}")
+        self._chk(self._L.vrt_set_emitter_importance(self._h, int(mode)))
+        self._emitter_importance = int(mode)
+
+    @property
+    def emitter_importance(self):
+        """The value set_emitter_importance() last set through this object (EMIT_UNIFORM until then). A copy kept in Python: the
+        C-ABI has a setter only."""
+        return getattr(self, "_emitter_importance", EMIT_UNIFORM)
+
+    def emitter_cdf(self):
+        """The thresholds by which EMIT_POWER picks from the emitter list (vrt_emitter_cdf) -> uint32[N], in the order of
+        emitters(): strictly increasing, the last one 2^24; entry j is picked with probability (T[j] - T[j - 1]) / 2^24. Above
+        MAX_EMITTERS entries the library holds none: that raises."""
+        n = self._L.vrt_emitter_cdf(self._h, None, 0)
+        if n < 0:
+            self._chk(n)
+        if n > MAX_EMITTERS:
+            raise VrtError(f"emitter_cdf: the tree has {n} emitters, more than MAX_EMITTERS")
+        out = np.zeros(n, np.uint32)
+        if n:
+            got = self._L.vrt_emitter_cdf(self._h, out.ctypes.data, n)
             if got < 0:
                 self._chk(got)
             assert got == n

@@ -121,6 +121,18 @@ __global__ void march_step_probe_kernel(const float *in, const int *dpos, uint32
         o[19] = __float_as_uint((__builtin_floorf(pf.z * inv_side) + dposf.z) * side);
     }
 }
+
+// the selection of VRT_EMIT_POWER on the device: the kernels' own emit_pick() (vrt_common.hip.h) on a caller's table, with the rule's
+// conversion of the draw: out[2 * i] = j, out[2 * i + 1] = ticks for u0[i]
+__global__ void emit_pick_probe_kernel(const uint32_t *cdf, uint32_t n, const float *u0, uint32_t *out, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uint32_t t = (uint32_t)(u0[i] * 16777216.0f);
+    t = t < 16777215u ? t : 16777215u;
+    uint32_t ticks;
+    out[2 * i] = emit_pick(cdf, n, t, ticks);
+    out[2 * i + 1] = ticks;
+}
 }  // namespace vrt
 
 namespace vrt_internal {
@@ -158,6 +170,58 @@ long vrt_test_emitter_list(const uint32_t *records, size_t n_records, const int 
     const size_t take = list.size() / 4 < cap ? list.size() / 4 : cap;
     for (size_t i = 0; i < take * 4; ++i) out[i] = list[i];
     return (long)n;
+}
+
+// host only: the weights and thresholds of VRT_EMIT_POWER as the context makes them (vrt_emitters.h emitter_walk(), emitter_weights(),
+// emitter_cdf()) of a caller's record array and world bounds -> N, and the first min(N, cap) weights and thresholds (none where N
+// exceeds max_entries)
+long vrt_test_emitter_cdf(const uint32_t *records, size_t n_records, const int *wmin, const int *wmax, uint64_t max_entries, uint64_t *weights_out,
+                          uint32_t *cdf_out, size_t cap) {
+    if (!records || !wmin || !wmax || (cap && (!weights_out || !cdf_out))) return VRT_E_INVALID;
+    std::vector<vrt::Record> recs(n_records);
+    for (size_t i = 0; i < n_records; ++i) recs[i] = vrt::Record{records[2 * i], records[2 * i + 1]};
+    std::vector<int32_t> list;
+    std::vector<uint32_t> words, cdf;
+    std::vector<uint64_t> weights;
+    const uint64_t n = emitter_walk(recs, wmin, wmax, max_entries, list, &words);
+    emitter_weights(list, words, weights);
+    emitter_cdf(weights, cdf);
+    const size_t take = cdf.size() < cap ? cdf.size() : cap;
+    for (size_t i = 0; i < take; ++i) { weights_out[i] = weights[i]; cdf_out[i] = cdf[i]; }
+    return (long)n;
+}
+
+// ... and of a caller's list (n entries of four int32) with its record words (two per entry), for lists no tree of a test's size gives
+long vrt_test_emitter_cdf_list(const int32_t *list, const uint32_t *words, size_t n, uint64_t *weights_out, uint32_t *cdf_out) {
+    if (n && (!list || !words || !weights_out || !cdf_out)) return VRT_E_INVALID;
+    const std::vector<int32_t> l(list, list + 4 * n);
+    const std::vector<uint32_t> w(words, words + 2 * n);
+    std::vector<uint32_t> cdf;
+    std::vector<uint64_t> weights;
+    emitter_weights(l, w, weights);
+    emitter_cdf(weights, cdf);
+    for (size_t i = 0; i < n; ++i) { weights_out[i] = weights[i]; cdf_out[i] = cdf[i]; }
+    return (long)n;
+}
+
+// Device probe of the selection (emit_pick_probe_kernel): a table of n thresholds and `count` draws, host arrays, synchronous.
+// out: 2 * count words = j, ticks. The table must be strictly increasing and end at 2^24, as emitter_cdf() makes it.
+int vrt_test_emit_pick(int device, const uint32_t *cdf, uint32_t n, const float *u0, uint32_t *out, int count) {
+    if (!cdf || !u0 || !out || n < 1 || n > VRT_MAX_EMITTERS || count < 1 || cdf[n - 1] != (1u << 24)) return VRT_E_INVALID;
+    VRT_HIP(c, hipSetDevice(device));
+    uint32_t *d_cdf = nullptr, *d_out = nullptr;
+    float *d_u = nullptr;
+    struct Free { uint32_t *&a, *&o; float *&u; ~Free() { (void)hipFree(a); (void)hipFree(o); (void)hipFree(u); } } free_on_exit{d_cdf, d_out, d_u};
+    VRT_HIP(c, hipMalloc((void **)&d_cdf, (size_t)n * sizeof(uint32_t)));
+    VRT_HIP(c, hipMalloc((void **)&d_u, (size_t)count * sizeof(float)));
+    VRT_HIP(c, hipMalloc((void **)&d_out, (size_t)count * 2 * sizeof(uint32_t)));
+    VRT_HIP(c, hipMemcpy(d_cdf, cdf, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    VRT_HIP(c, hipMemcpy(d_u, u0, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(vrt::emit_pick_probe_kernel, dim3((count + 255) / 256), dim3(256), 0, nullptr, d_cdf, n, d_u, d_out, count);
+    VRT_HIP(c, hipGetLastError());
+    VRT_HIP(c, hipDeviceSynchronize());
+    VRT_HIP(c, hipMemcpy(out, d_out, (size_t)count * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VRT_OK;
 }
 
 // Arithmetic-contract probe (math_probe_kernel / math_probe_full_kernel): out[i] = op(x[i], y[i]) on `device`; host arrays, synchronous.

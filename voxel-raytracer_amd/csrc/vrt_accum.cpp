@@ -25,7 +25,7 @@ using Accum = vrt_ctx::Accum;
 bool same_inputs(const vrt_ctx *c, const Accum &ac) {
     return std::memcmp(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj) == 0 && std::memcmp(ac.inv_view, c->inv_view, sizeof ac.inv_view) == 0 &&
            std::memcmp(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos) == 0 && std::memcmp(&ac.params, &c->params, sizeof ac.params) == 0 &&
-           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc && ac.emitter_sampling == c->emitter_sampling)) &&   // the primary modes ignore the depth, the sun disc and emitter sampling
+           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc && ac.emitter_sampling == c->emitter_sampling && ac.emitter_importance == c->emitter_importance)) &&   // the primary modes ignore the depth, the sun disc, emitter sampling and its mode
            ac.tree_gen == c->tree_gen;
 }
 
@@ -37,6 +37,7 @@ void take_inputs(const vrt_ctx *c, Accum &ac) {
     ac.path_depth = c->path_depth;
     ac.sun_disc = c->sun_disc;
     ac.emitter_sampling = c->emitter_sampling;
+    ac.emitter_importance = c->emitter_importance;
     ac.params = c->params;
     ac.tree_gen = c->tree_gen;
 }
@@ -233,7 +234,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         q.n = 1u;
         if (adaptive) e = launch::adaptive_tiles(tl, s);
         if (e == hipSuccess)
-            e = emit_on ? launch::accum_full_emit(hdr, src, v, a, vs, q, adaptive, l, vrt::Emit{sun, ac.emit_list, ac.emit_n}, grid, s)
+            e = emit_on && acc.emit_power ? launch::accum_full_emitp(hdr, src, v, a, vs, q, adaptive, l, vrt::EmitPower{vrt::Emit{sun, ac.emit_list, ac.emit_n}, ac.emit_cdf}, grid, s)
+                : emit_on ? launch::accum_full_emit(hdr, src, v, a, vs, q, adaptive, l, vrt::Emit{sun, ac.emit_list, ac.emit_n}, grid, s)
                 : sun_on ? launch::accum_full_sun(hdr, src, v, a, vs, q, adaptive, l, sun, grid, s)
                 : deep ? launch::accum_full_deep(hdr, src, v, a, vs, q, adaptive, l, grid, s) : launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
     }
@@ -276,6 +278,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         if (re) return re;
         ac.emit_list = c->emitters.d_list;
         ac.emit_n = (uint32_t)c->emitters.n;
+        ac.emit_cdf = c->emitters.d_cdf;
     }
     const bool restart = ac.total == 0 || !same_inputs(c, ac);
     const uint32_t base = restart ? 0u : ac.total;
@@ -334,6 +337,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
         step.sun = ac.mode == VRT_MODE_FULL ? ac.sun_disc : 0.0f;
         step.emit = sampling && c->emitters.n > 0;   // an empty list: the launches of sampling off
+        step.emit_power = step.emit && c->emitter_importance == VRT_EMIT_POWER;   // vrt_set_emitter_importance
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again

@@ -196,6 +196,14 @@ struct EmitLensSource {
     const Lens &L;
     const Emit &S;
 };
+// ... and for the kernels over EmitPowerPaths<...> (include/vrt.h vrt_set_emitter_importance): the EmitPower, which holds the Emit
+struct EmitPowerCornerSource { static constexpr bool kJitter = false, kLens = false; const EmitPower &S; };
+struct EmitPowerJitterSource { static constexpr bool kJitter = true, kLens = false; const EmitPower &S; };
+struct EmitPowerLensSource {
+    static constexpr bool kJitter = false, kLens = true;
+    const Lens &L;
+    const EmitPower &S;
+};
 
 // ---- the kernels of the three shapes ----
 // L...: the lens kernels' fourth argument, the Lens. Each body is its kernel's own and writes out its trace call per source and its

@@ -27,6 +27,14 @@ struct Emit {
     uint32_t n;
 };
 
+// ... and with VRT_EMIT_POWER (include/vrt.h vrt_set_emitter_importance): the same, and the list's table of thresholds -- one uint32
+// per entry, strictly increasing, the last one 2^24 (vrt_emitters.h emitter_cdf()). A by-value kernel argument of its own of the
+// kernels over EmitPowerPaths<...>, in the Emit's place; the Emit keeps its layout.
+struct EmitPower {
+    Emit emit;
+    const uint32_t *cdf;
+};
+
 // One camera and the two images it renders into. A launch carries up to kMaxViews of them (blockIdx.y selects
 // the view): frames of one scene that are known together -- a stereo pair, the next frames of a camera path, the
 // views of a light-field rig -- share one launch, so the drain of one view's last waves is filled by the next

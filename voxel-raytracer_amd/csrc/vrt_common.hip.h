@@ -342,6 +342,33 @@ template <class T> struct EmitPaths : SunPaths<T> {
 template <class T, class = void> struct emit_paths { static constexpr bool value = false; };
 template <class T> struct emit_paths<T, decltype((void)T::kEmitPaths)> { static constexpr bool value = T::kEmitPaths; };
 
+// ... and EmitPowerPaths<T>, EmitPaths<T> for the kernels that pick the emitter in proportion to its power and the face among those
+// the vertex can see (include/vrt.h vrt_set_emitter_importance, VRT_EMIT_POWER; vrt_full.hip.h emit_connect_power()): `static
+// constexpr bool kEmitPowerPaths = true`, and a Ctx that carries the table of thresholds beside the list.
+template <class T> struct EmitPowerPaths : EmitPaths<T> {
+    static constexpr bool kEmitPowerPaths = true;
+    struct Ctx : EmitPaths<T>::Ctx { const uint32_t *cdf; };
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
+    static VRT_DEV void take(Ctx &c, const EmitPower &e) { EmitPaths<T>::take(c, e.emit); c.cdf = e.cdf; }
+};
+template <class T, class = void> struct emit_power_paths { static constexpr bool value = false; };
+template <class T> struct emit_power_paths<T, decltype((void)T::kEmitPowerPaths)> { static constexpr bool value = T::kEmitPowerPaths; };
+
+// The threshold search of VRT_EMIT_POWER: the smallest index j with cdf[j] > t, for a strictly increasing table of n >= 1 thresholds
+// whose last one exceeds t, and ticks = cdf[j] - cdf[j - 1] (cdf[-1] = 0). A branch-free lower bound: ceil(log2 n) steps, each one load
+// and one select, the same count in every lane; the table is a global array of at most 4 MB.
+VRT_DEV uint32_t emit_pick(const uint32_t *cdf, uint32_t n, uint32_t t, uint32_t &ticks) {
+    uint32_t base = 0u, len = n;
+    while (len > 1u) {
+        const uint32_t half = len >> 1;
+        base = cdf[base + half - 1u] <= t ? base + half : base;
+        len -= half;
+    }
+    const uint32_t below = base ? cdf[base - 1u] : 0u;
+    ticks = cdf[base] - below;
+    return base;
+}
+
 // A primary ray the miss-tile proof covers ("Miss tiles"): no component of its direction within 2e-8 of (-1e-8, 0], so that after
 // march()'s renormalisation (a factor within a few ulps of 1) none lies in (-1e-8, 0] and every step of the DDA has t >= 0.
 VRT_DEV bool miss_forward(F3 d) {

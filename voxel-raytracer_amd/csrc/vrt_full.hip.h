@@ -250,6 +250,76 @@ VRT_DEV void emit_connect(const KArgs &a, const typename TRAV::Ctx &tc_, F3 hp, 
     }
 }
 
+// The same with VRT_EMIT_POWER (include/vrt.h vrt_set_emitter_importance, "Per vertex"), for the kernels over EmitPowerPaths<...>: u0
+// picks the emitter by the table of thresholds (emit_pick(): probability p = ticks * 2^-24, in proportion to its power), uf one of the
+// m <= 3 faces the vertex can see -- none: nothing more happens -- and from q on the steps are emit_connect()'s, word for word; the
+// weight is g = cs * cl * (m * size^2) / (PI * r2 * p). (emit_connect()'s body from `const F3 w` on, once more: a change there is a
+// change here.)
+template <class TRAV, class OVER_PI>
+VRT_DEV void emit_connect_power(const KArgs &a, const typename TRAV::Ctx &tc_, F3 hp, F3 normal, float n1, const float tint[3], float weight,
+                                const float mc[3], float md, uint32_t &rng, const OVER_PI &over_pi, float fc[3]) {
+    const float kPI = 3.14159265359f;
+    const float u0 = rng_next(rng), uf = rng_next(rng), ua = rng_next(rng), ub = rng_next(rng);
+    uint32_t t = (uint32_t)(u0 * 16777216.0f);   // rand() can return exactly 1.0f
+    t = t < 16777215u ? t : 16777215u;
+    uint32_t ticks;
+    const uint32_t j = emit_pick(tc_.cdf, tc_.n_emit, t, ticks);
+    const float p = (float)ticks * 0x1p-24f;
+    const int4 e = *reinterpret_cast<const int4 *>(tc_.emit + (size_t)j * 4u);
+    const float sz = (float)e.w;
+    const F3 x = add3(hp, scale3(normal, 1e-1f));
+    // per axis at most one face is turned towards x: the low one where x lies below the cube, the high one where it lies above
+    const float lox = (float)e.x, loy = (float)e.y, loz = (float)e.z;
+    const bool hx = x.x > lox + sz, hy = x.y > loy + sz, hz = x.z > loz + sz;
+    const int vx = (x.x < lox || hx) ? 1 : 0, vy = (x.y < loy || hy) ? 1 : 0, vz = (x.z < loz || hz) ? 1 : 0;
+    const int m = vx + vy + vz;
+    if (m == 0) return;   // x inside the cube's slab on every axis: the four draws stay spent
+    int i = (int)(uf * (float)m);
+    i = i < m - 1 ? i : m - 1;
+    const int ax = (vx && i == 0) ? 0 : ((vy && i == vx) ? 1 : 2);
+    const int side = (ax == 0 ? hx : (ax == 1 ? hy : hz)) ? 1 : 0;
+    const float fixed = side ? sz : 0.0f;
+    // q[ax] = lo[ax] + (side ? sz : 0), q[a1] = lo[a1] + ua * sz, q[a2] = lo[a2] + ub * sz with a1 = (ax + 1) % 3, a2 = (ax + 2) % 3
+    const F3 q{lox + (ax == 0 ? fixed : (ax == 2 ? ua * sz : ub * sz)), loy + (ax == 1 ? fixed : (ax == 0 ? ua * sz : ub * sz)),
+               loz + (ax == 2 ? fixed : (ax == 1 ? ua * sz : ub * sz))};
+    const F3 w = sub3(q, x);
+    const float r2 = dot3(w, w);
+    if (!(r2 > 0.0f)) return;
+    const F3 dir = scale3(w, 1.0f / __builtin_sqrtf(r2));
+    const float cs = dot3(normal, dir);
+    const float cl = side ? -comp(dir, ax) : comp(dir, ax);
+    if (!(cs > 0.0f && cl > 0.0f)) return;   // the four draws stay spent
+    Hit h;
+    if (!TRAV::march(a, tc_, x, dir, n1, iof_to_byte(n1), h)) return;
+    if (h.map.x < e.x || h.map.x >= e.x + e.w || h.map.y < e.y || h.map.y >= e.y + e.w || h.map.z < e.z || h.map.z >= e.z + e.w) return;
+    // the hit as the loop evaluates a hit of a ray of depth >= 1, up to the emissive test
+    float dim;
+    if (a.voxel_scale != 1.0f) {
+        const F3 hpw{h.point.x / a.voxel_scale, h.point.y / a.voxel_scale, h.point.z / a.voxel_scale};
+        dim = 0.0f + len3(sub3(hpw, x)) / a.voxel_scale;
+    } else {
+        dim = 0.0f + len3(sub3(h.point, x));
+    }
+    Decoded hv = decode_leaf(h.h0, h.h1);
+    const Decoded last = decode_leaf(h.p0, h.p1);
+    if (hv.c[3] <= 0.0f) hv.p[1] = 0.0f;
+    float sc[3], tc[3] = {tint[0], tint[1], tint[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sc[k] = hv.c[3] > 0.0f ? hv.c[k] : last.c[k];
+    if (dim > 1e-6f && md > 0.0f) absorb(tc, md, dim, mc);
+    if (h.map.x == a.highlighted[0] && h.map.y == a.highlighted[1] && h.map.z == a.highlighted[2]) {
+        sc[0] = 1.0f - sc[0]; sc[1] = 1.0f - sc[1]; sc[2] = 1.0f - sc[2];
+    }
+    const float emission = hv.p[1] * 10.0f;
+    if (!(emission > 0.0f)) return;
+    const float g = ((cs * cl) * ((float)m * (sz * sz))) / ((kPI * r2) * p);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float ek = over_pi(tc[k] * sc[k] * emission * weight);
+        fc[k] = fc[k] + ek * g;
+    }
+}
+
 // sample: initRNG's sampleIndex (comp:629 passes 0; the progressive accumulation of vrt_accum.hip.h passes 0, 1, 2, ...), and
 // with JIT also the jittered sample whose ray is traced; LENS: the ray `lens` instead, origin and medium included (pixel_ray())
 // HDR: fc_out[3] takes the float colour unorm8() receives
@@ -480,7 +550,10 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 }
                 if constexpr (EMIT) {   // four draws, after the sun's and before the bounce's
                     const float tint[3] = {tc[0] * sc[0], tc[1] * sc[1], tc[2] * sc[2]};
-                    emit_connect<TRAV>(a, tc_, hp, normal, n1, tint, r.weight / (float)kIndirectSamples, last.c, last.c[3] * 5.0f, rng, over_pi, fc);
+                    if constexpr (emit_power_paths<TRAV>::value)   // VRT_EMIT_POWER (vrt_set_emitter_importance)
+                        emit_connect_power<TRAV>(a, tc_, hp, normal, n1, tint, r.weight / (float)kIndirectSamples, last.c, last.c[3] * 5.0f, rng, over_pi, fc);
+                    else
+                        emit_connect<TRAV>(a, tc_, hp, normal, n1, tint, r.weight / (float)kIndirectSamples, last.c, last.c[3] * 5.0f, rng, over_pi, fc);
                 }
             } else {
                 const float amb = fmax_c(1.0f - det_expf(-r.dim / 512.0f), 0.01f);

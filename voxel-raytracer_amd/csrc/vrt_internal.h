@@ -94,6 +94,7 @@ struct vrt_ctx {
     int path_depth = 1;             // vrt_set_path_depth: the samples of VRT_MODE_FULL in accumulations and ray batches (frames: always 1)
     float sun_disc = 0.0f;          // vrt_set_sun_disc: the tangent of the sun's angular radius, honoured where the path depth is
     bool emitter_sampling = false;  // vrt_set_emitter_sampling: next-event estimation towards the emitter list, honoured where the path depth is
+    int emitter_importance = VRT_EMIT_UNIFORM;   // vrt_set_emitter_importance: how a vertex picks from the list; read only where sampling is on and the list is not empty
     // the emitter list (vrt_emitters.cpp ensure_emitters()) of the tree generation and world bounds it was made for
     struct Emitters {
         bool built = false;
@@ -102,6 +103,8 @@ struct vrt_ctx {
         uint64_t n = 0;                  // N; above VRT_MAX_EMITTERS nothing is held
         std::vector<int32_t> list;       // 4 per entry: lo.x, lo.y, lo.z, size
         DevBuf<int32_t> d_list;          // the same on the device
+        std::vector<uint32_t> cdf;       // one threshold per entry (vrt_emitters.h emitter_cdf()), made and uploaded with the list
+        DevBuf<uint32_t> d_cdf;
     };
     Emitters emitters;
     int variant = 0;
@@ -236,6 +239,8 @@ struct vrt_ctx {
         bool emitter_sampling = false;
         const int32_t *emit_list = nullptr;      // the context's emitter list as the add that queues a step found it (emitters.d_list, N)
         uint32_t emit_n = 0;
+        int emitter_importance = VRT_EMIT_UNIFORM;
+        const uint32_t *emit_cdf = nullptr;      // ... and its thresholds (emitters.d_cdf)
         vrt_params params{};
         uint64_t tree_gen = 0;
         DevBuf<uint32_t> d_sums;                 // 4 words per pixel
@@ -339,6 +344,7 @@ struct AccumStep {
     bool adaptive = false, hdr = false, frame_only = false;
     float sun = 0.0f;
     bool emit = false;
+    bool emit_power = false;   // with emit: VRT_EMIT_POWER (vrt_set_emitter_importance), the kernels over EmitPowerPaths<...>
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);

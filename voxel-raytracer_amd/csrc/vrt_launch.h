@@ -188,6 +188,17 @@ inline hipError_t accum_full_emit(bool hdr, accum::Source src, const Variant &v,
     return hdr ? accum_full_hdr_emit(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emit(src, v, a, vs, q, adaptive, l, em, grid, s);
 }
 
+// vrt_launch_accum_emitp.hip, vrt_launch_accum_hdr_emitp.hip: the same with VRT_EMIT_POWER (include/vrt.h vrt_set_emitter_importance):
+// kernels over EmitPowerPaths<...>, which take `em` -- the Emit and the list's table of thresholds -- as their last argument
+hipError_t accum_full_emitp(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
+                            const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s);
+hipError_t accum_full_hdr_emitp(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                                const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s);
+inline hipError_t accum_full_emitp(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                                   bool adaptive, const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s) {
+    return hdr ? accum_full_hdr_emitp(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emitp(src, v, a, vs, q, adaptive, l, em, grid, s);
+}
+
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
@@ -216,6 +227,12 @@ hipError_t shade_rays_emit(const Variant &v, const KArgs &a, const ViewSet &vs, 
                            hipEvent_t ev0, hipEvent_t ev1);
 hipError_t shade_rays_hdr_emit(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Emit &em, uint32_t grid,
                                hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
+// vrt_launch_rays_emitp.hip, vrt_launch_rays_hdr_emitp.hip: ... and with VRT_EMIT_POWER (vrt_set_emitter_importance)
+hipError_t shade_rays_emitp(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const EmitPower &em, uint32_t grid, hipStream_t s,
+                            hipEvent_t ev0, hipEvent_t ev1);
+hipError_t shade_rays_hdr_emitp(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const EmitPower &em, uint32_t grid,
+                                hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

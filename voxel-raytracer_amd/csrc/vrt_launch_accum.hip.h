@@ -149,6 +149,25 @@ hipError_t full_emit(accum::Source src, const Variant &v, const KArgs &a, const 
     return hipErrorInvalidValue;
 }
 
+// EMIT POWER (vrt_launch_accum_emitp.hip, vrt_launch_accum_hdr_emitp.hip): the same over EmitPowerPaths<...> (include/vrt.h
+// vrt_set_emitter_importance, VRT_EMIT_POWER); the kernels' last argument is the EmitPower
+template <bool HDR>
+hipError_t full_emit_power(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
+                           const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s) {
+    const auto f = [&](auto sh) {
+        using S = decltype(sh);
+        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
+        if (src == accum::Source::kCorner)
+            return go(accum::full_accum_kernel<accum::EmitPowerCornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitPower>, grid, S::kBlock, s, a, vs, qs, em);
+        if (src == accum::Source::kJitter)
+            return go(accum::full_accum_kernel<accum::EmitPowerJitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitPower>, grid, S::kBlock, s, a, vs, qs, em);
+        return go(accum::full_accum_kernel<accum::EmitPowerLensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, EmitPower>, grid, S::kBlock, s, a, vs, qs, l, em);
+    };
+    if (v.trav >= 3) return shape<EmitPowerPaths<v4::TravAny>, 64, 5>(adaptive, f);
+    if (v.trav >= 1) return shape<EmitPowerPaths<v1::Trav>, 256, 1>(adaptive, f);
+    return hipErrorInvalidValue;
+}
+
 template <bool HDR, bool DEEP = false, class... SUN>
 hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s, const SUN &...sun) {
     if constexpr (sizeof...(SUN) != 0) {

@@ -89,6 +89,8 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     if (emit_on) a.path_depth = (uint32_t)c->path_depth;
     vrt::Emit em{};
     if (emit_on) em = vrt::Emit{sun, c->emitters.d_list.get(), (uint32_t)c->emitters.n};
+    const bool power = emit_on && c->emitter_importance == VRT_EMIT_POWER;   // vrt_set_emitter_importance: the kernels over EmitPowerPaths<...>
+    const vrt::EmitPower emp{em, power ? c->emitters.d_cdf.get() : nullptr};
 
     vrt::rays::Args q;
     q.origins = d_origins;
@@ -114,12 +116,14 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
         hq.n_total = hdr->n_prior + n_samples;
         hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
         hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = emit_on ? vrt::launch::shade_rays_hdr_emit(v, a, vs, hq, em, grid, s, prof.ev0, prof.ev1)
+        e = power ? vrt::launch::shade_rays_hdr_emitp(v, a, vs, hq, emp, grid, s, prof.ev0, prof.ev1)
+            : emit_on ? vrt::launch::shade_rays_hdr_emit(v, a, vs, hq, em, grid, s, prof.ev0, prof.ev1)
             : sun_on ? vrt::launch::shade_rays_hdr_sun(v, a, vs, hq, sun, grid, s, prof.ev0, prof.ev1)
             : deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
                    : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
     } else {
-        e = emit_on ? vrt::launch::shade_rays_emit(v, a, vs, q, em, grid, s, prof.ev0, prof.ev1)
+        e = power ? vrt::launch::shade_rays_emitp(v, a, vs, q, emp, grid, s, prof.ev0, prof.ev1)
+            : emit_on ? vrt::launch::shade_rays_emit(v, a, vs, q, em, grid, s, prof.ev0, prof.ev1)
             : sun_on ? vrt::launch::shade_rays_sun(v, a, vs, q, sun, grid, s, prof.ev0, prof.ev1)
             : deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
     }
