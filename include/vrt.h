@@ -446,12 +446,58 @@ long vrt_emitters(vrt_ctx *ctx, int32_t *out, size_t cap);
  *   4. Step 7 above is unchanged: a ray of depth >= 1 that hits an emissive voxel adds nothing and ends.
  * Consequences: the same expectation as VRT_EMIT_UNIFORM and as sampling off; a bright emitter is reached in proportion to its
  * share of the list's power instead of once in N vertices, and no connection is drawn towards a face turned away. The threshold
- * search is a lower bound of ceil(log2 N) steps on a global table of at most 4 MB. Not done: multiple importance sampling with the
- * bounce, faces by projected solid angle, the stack-free opaque routes, vrt_multi. */
+ * search is a lower bound of ceil(log2 N) steps on a global table of at most 4 MB. Multiple importance sampling with the bounce:
+ * vrt_set_emitter_mis below. Not done: faces by projected solid angle, the stack-free opaque routes, vrt_multi. */
 #define VRT_EMIT_UNIFORM 0
 #define VRT_EMIT_POWER   1
 int vrt_set_emitter_importance(vrt_ctx *ctx, int mode);
 long vrt_emitter_cdf(vrt_ctx *ctx, uint32_t *out, size_t cap);
+
+/* Emitter MIS: weigh the emitter connection against the bounce ray. With VRT_EMIT_POWER alone a bounce ray that finds an emitter adds
+ * nothing and all emitted light arrives through the connection, whose weight g = cs * cl * (m * size^2) / (PI * r2 * p) nothing bounds:
+ * at a vertex 0.1 off a surface that an emitter touches r2 is a few hundredths and g runs into the tens -- fireflies that never average
+ * out, just where the dropped bounce ray was the good estimator. vrt_set_emitter_mis(ctx, 1) keeps both samples and weighs each by the
+ * balance heuristic, the same function of (vertex, direction) on both sides; the two weights sum to one. enable is 0 (default) or 1;
+ * anything else is VRT_E_INVALID (the previous value still holds). It is context state, and vrt_set_emitter_importance keeps its 0 / 1
+ * contract. The flag is read only where vrt_set_emitter_sampling is on, the emitter list is not empty and the mode is VRT_EMIT_POWER:
+ * in every other case the same kernels launch and the same bytes come out at either value. Exactly the callers that honour the emitter
+ * flag and the mode honour this flag (vrt_accum_add of VRT_MODE_FULL in every form, vrt_shade_rays and its three siblings, at every D
+ * and any sun radius); frames, views, shards and vrt_multi ignore it. Where it is read it is one of the inputs of an accumulation of
+ * VRT_MODE_FULL: a change restarts the sums at `first`, the same value set again changes nothing. Where it is not read a change does
+ * not restart, and accumulations of the primary modes never do.
+ *
+ * Per launch: inv_power = Wtot > 0 ? (float)(1.0 / (double)Wtot) : 0.0f, with Wtot the sum of the list's integer weights W_j, kept when
+ * the table of thresholds is made.
+ *
+ * The densities (all arithmetic float32, every operation rounded on its own, no contraction). emit_mis_density(x, dir, cs, hit), for a
+ * ray from x in the direction dir whose march ended in `hit` (point, axis, cell `map`, leaf words w0, w1), cs the cosine at x:
+ *     v = hit.point - x;  r2 = dot3(v, v);  cl = fabsf(dir[hit.axis])
+ *     axis k is visible if x[k] < (float)map[k] || x[k] > (float)map[k] + 1.0f;  m = the number of visible axes
+ *     w = illum * (R + G + B), of the hit voxel's words exactly as W_j reads them
+ *     pl = (m == 0 || !(cl > 0)) ? 0 : ((((float)w * inv_power) * r2) / ((float)m * cl))
+ *     pb = (cs > 0 ? cs : 0) / PI
+ * pl is the power rule's solid-angle density computed from the hit alone -- the bounce side knows its hit, not the list entry -- with
+ * two stated simplifications. The emitter's probability is w / Wtot (the size^2 of W_j cancels against the face's area) and ignores
+ * the table's one-tick floor: by the formula for T_j the true p is at least (W_j / Wtot) * (1 - N * 2^-24). And m is that of the hit
+ * cell, not of the list's cube; it can only be larger. So the function is exact for single voxels and under-trusts connections to a
+ * merged emitter by at most m_cell / m_cube <= 3. The weights need only be the same function on both sides and sum to one.
+ *
+ * The connection: VRT_EMIT_POWER's steps 1 to 3, word for word, up to and including emission > 0 and g. Then pl and pb of the
+ * connection's own hit, its x, its dir and its cs. !(pl > 0): nothing is added. Otherwise wn = pl / (pl + pb) and
+ *     fc[k] = fc[k] + (E_k * g) * wn.
+ * The four draws and their order are unchanged.
+ * The bounce: when the bounce ray is made, cb = dot3(normal, bd) is kept. Where that ray (depth >= 1) hits a voxel with emission > 0:
+ * pl and pb of x = the ray's origin, dir = its direction, cs = cb and this hit; wb = !(pl > 0) ? 1 : pb / (pl + pb);
+ *     fc[k] = fc[k] + (tc[k] * sc[k] * emission * weight / PI) * wb
+ * and the path ends there, as it does with the flag off.
+ * Consequences: the expectation is that of VRT_EMIT_POWER, VRT_EMIT_UNIFORM and sampling off. With g = pb / pl the connection's term is
+ * E * pb / (pl + pb), at most E (up to the two simplifications: at most 1 / (1 - N * 2^-24) times that, and the float32 difference
+ * between the sampled point and the marched hit). A black emitter (w == 0) is carried by the bounce alone, at weight 1. Sample k at
+ * flag 1 draws the same numbers as at flag 0. One case is not exactly unbiased: a vertex whose x lies inside an emitter's own list cube
+ * but outside the hit cell -- the connection cannot be drawn there (m of the cube is 0), yet the bounce is weighted below 1; it arises
+ * only for rays started inside solids. Not done: MIS under VRT_EMIT_UNIFORM (its density needs the cube's size at the hit), a
+ * hit-to-list lookup that would make m and the ticks exact, the power heuristic, the stack-free opaque routes, vrt_multi. */
+int vrt_set_emitter_mis(vrt_ctx *ctx, int enable);
 
 /* Adaptive accumulation: stop sampling pixels whose mean has converged. vrt_accum_begin_adaptive is vrt_accum_begin_ex (same
  * modes, VRT_ACCUM_JITTER, the lens as context state) plus a stopping rule, which belongs to the accumulation. VRT_E_INVALID

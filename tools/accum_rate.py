@@ -49,6 +49,12 @@ scene power_room_1080p is tests/emit_power_worlds.py's room seen from inside: a 
 
     python3 tools/accum_rate.py --path-depth 1 4 --emit 0 1 --emit-power 0 1 --scenes power_room_1080p lamp_room_1080p --samples 16 --out profiles/emit_power_rate.jsonl
 
+--emit-mis F [F ...] (with --emit-power) measures each setting with sampling on and mode 1 once per value of the MIS flag too
+(vrt_set_emitter_mis, 0 or 1) and records it (emitter_mis); elsewhere the flag is not read and the row is measured once. The scene
+mis_room_1080p is tests/emit_mis_worlds.py's room seen from inside, looking at the foot of the lamp on the floor:
+
+    python3 tools/accum_rate.py --path-depth 1 4 --emit 0 1 --emit-power 1 --emit-mis 0 1 --scenes mis_room_1080p power_room_1080p --samples 16 --out profiles/emit_mis_rate.jsonl
+
 --variant V (with --path-depth) measures with vrt_set_variant(V) and records it (variant); 1 takes the record-array kernels.
 
 --out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
@@ -74,8 +80,9 @@ SCENES = {   # name -> (map, pose): the golden 1080p / 4K frames' poses
     "room_inside_1080p": ("room", (14.5, 30.5, 16.5), 32.0, -10.0),
     "lamp_room_1080p": ("lamp", (36.5, 44.5, 50.5), -38.0, 8.0),   # tests/emit_worlds.py: POSE
     "power_room_1080p": ("power", (36.5, 44.5, 50.5), -38.0, 8.0),   # tests/emit_power_worlds.py: POSE
+    "mis_room_1080p": ("mis", (36.5, 44.5, 50.5), -20.0, -35.0),   # tests/emit_mis_worlds.py: INSIDE_POSE
 }
-DEFAULT_SCENES = sorted(s for s in SCENES if SCENES[s][0] not in ("lamp", "power"))   # the two lamp rooms: on request (--scenes), for --emit
+DEFAULT_SCENES = sorted(s for s in SCENES if SCENES[s][0] not in ("lamp", "power", "mis"))   # the lamp rooms: on request (--scenes), for --emit
 
 
 def main():
@@ -96,19 +103,23 @@ def main():
                     help="with --path-depth: once per setting of emitter sampling (vrt_set_emitter_sampling)")
     ap.add_argument("--emit-power", nargs="+", type=int, default=None, choices=(0, 1), metavar="M",
                     help="with --emit: sampling on once per importance mode (vrt_set_emitter_importance)")
+    ap.add_argument("--emit-mis", nargs="+", type=int, default=None, choices=(0, 1), metavar="F",
+                    help="with --emit-power: sampling on at mode 1 once per MIS flag (vrt_set_emitter_mis)")
     ap.add_argument("--variant", type=int, default=None, metavar="V",
                     help="with --path-depth: the traversal variant (vrt_set_variant; 1: the record-array kernels), recorded as variant")
     ap.add_argument("--scenes", nargs="+", default=DEFAULT_SCENES, choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
-    if args.adaptive and (args.path_depth or args.sun or args.emit or args.emit_power or args.scenes != DEFAULT_SCENES or args.samples != list(SAMPLES)):
-        ap.error("--adaptive takes none of --path-depth, --sun, --emit, --emit-power, --scenes, --samples")
+    if args.adaptive and (args.path_depth or args.sun or args.emit or args.emit_power or args.emit_mis or args.scenes != DEFAULT_SCENES or args.samples != list(SAMPLES)):
+        ap.error("--adaptive takes none of --path-depth, --sun, --emit, --emit-power, --emit-mis, --scenes, --samples")
     if args.sun and not args.path_depth:
         ap.error("--sun goes with --path-depth")
     if args.emit and not args.path_depth:
         ap.error("--emit goes with --path-depth")
     if args.emit_power and not args.emit:
         ap.error("--emit-power goes with --emit")
+    if args.emit_mis and not args.emit_power:
+        ap.error("--emit-mis goes with --emit-power")
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
@@ -119,8 +130,9 @@ def main():
     d_rgb = ctx.device_alloc(W * H * 12) if args.hdr else None
     rows = []
     last_spread = [0.0, 0.0]   # of the last add_ms(): the fastest and the slowest timed add
-    for name, depth, sun, emit, imp in [(s, d, r, e, m) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])
-                                        for e in (args.emit or [None]) for m in ((args.emit_power if e else args.emit_power[:1]) if args.emit_power else [None])]:
+    for name, depth, sun, emit, imp, mis in [(s, d, r, e, m, f) for s in SCENES if s in args.scenes for d in (args.path_depth or [None]) for r in (args.sun or [None])
+                                             for e in (args.emit or [None]) for m in ((args.emit_power if e else args.emit_power[:1]) if args.emit_power else [None])
+                                             for f in ((args.emit_mis if e and m == 1 else args.emit_mis[:1]) if args.emit_mis else [None])]:
         m, pos, yaw, pitch = SCENES[name]
         if m == "room":
             w = room_world(V)
@@ -130,6 +142,9 @@ def main():
         elif m == "power":
             import emit_power_worlds
             w = emit_power_worlds.room(V)
+        elif m == "mis":
+            import emit_mis_worlds
+            w = emit_mis_worlds.room(V)
         else:
             w = V.World()
             assert w.load_vox(os.path.join(MAPS, m + ".vox"))
@@ -149,6 +164,8 @@ def main():
             ctx.set_emitter_sampling(emit)
         if imp is not None:
             ctx.set_emitter_importance(imp if emit else 0)
+        if mis is not None:
+            ctx.set_emitter_mis(mis if emit and imp == 1 else 0)
         opaque = V.tree_is_opaque(tex)
         for mname in args.mode:
             mode = V.MODES[mname]
@@ -203,6 +220,8 @@ def main():
                             row["path"] = "general"   # the opaque routes are not taken
                         if imp is not None and emit:
                             row.update(emitter_importance=imp)
+                        if mis is not None and emit and imp == 1:
+                            row.update(emitter_mis=mis)
                     if lens is None:
                         base_ms = ms
                     else:

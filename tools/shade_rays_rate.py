@@ -32,6 +32,11 @@ power) and records it (emitter_importance); --emit-world power_room takes tests/
 and 256 dim singles) instead of the lamp room:
 
     python3 tools/shade_rays_rate.py --path-depth 1 4 --emit 0 1 --emit-power 0 1 --emit-world power_room --append --out profiles/emit_power_rate.jsonl
+
+--emit-mis F [F ...] (with --emit-power) measures sampling on at mode 1 once per value of the MIS flag too (vrt_set_emitter_mis, 0 or
+1) and records it (emitter_mis); --emit-world mis_room takes tests/emit_mis_worlds.py's room, the frame's rays from its INSIDE_POSE:
+
+    python3 tools/shade_rays_rate.py --path-depth 1 4 --emit 0 1 --emit-power 1 --emit-mis 0 1 --emit-world mis_room --append --out profiles/emit_mis_rate.jsonl
 """
 import argparse
 import json
@@ -89,8 +94,12 @@ def main():
                     help="with --path-depth: in the lamp room, once per setting of emitter sampling (vrt_set_emitter_sampling)")
     ap.add_argument("--emit-power", nargs="+", type=int, default=None, choices=(0, 1), metavar="M",
                     help="with --emit: sampling on once per importance mode (vrt_set_emitter_importance)")
-    ap.add_argument("--emit-world", default="lamp_room", choices=("lamp_room", "power_room"), help="with --emit: the world")
+    ap.add_argument("--emit-mis", nargs="+", type=int, default=None, choices=(0, 1), metavar="F",
+                    help="with --emit-power: sampling on at mode 1 once per MIS flag (vrt_set_emitter_mis)")
+    ap.add_argument("--emit-world", default="lamp_room", choices=("lamp_room", "power_room", "mis_room"), help="with --emit: the world")
     args = ap.parse_args()
+    if args.emit_mis and not args.emit_power:
+        ap.error("--emit-mis goes with --emit-power")
     if args.emit_power and not args.emit:
         ap.error("--emit-power goes with --emit")
     if args.sun and not args.path_depth:
@@ -103,6 +112,9 @@ def main():
         if args.emit_world == "power_room":
             import emit_power_worlds
             w = emit_power_worlds.room(V)
+        elif args.emit_world == "mis_room":
+            import emit_mis_worlds
+            w = emit_mis_worlds.room(V)
         else:
             w = emit_worlds.lamp_room(V)
     else:
@@ -182,6 +194,8 @@ def main():
             world = args.emit_world
             box = ((emit_worlds.LO + 1,) * 3, (emit_worlds.HI,) * 3)
             pose = (emit_worlds.POSE[:3], emit_worlds.POSE[3], emit_worlds.POSE[4])
+            if args.emit_world == "mis_room":
+                pose = (emit_mis_worlds.INSIDE_POSE[:3], emit_mis_worlds.INSIDE_POSE[3], emit_mis_worlds.INSIDE_POSE[4])
         _, origin, dirs = frame_rays(V, W, H, pose)
         rng = np.random.default_rng(1)
         n_probe = args.rays
@@ -199,8 +213,9 @@ def main():
             n = len(rd)
             d_o, d_d = upload(ro, rd)
             d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
-            for depth, sun, em, imp in [(dd, r, e, m) for dd in args.path_depth for r in (args.sun or [None]) for e in (args.emit or [None])
-                                        for m in ((args.emit_power if e else args.emit_power[:1]) if args.emit_power else [None])]:
+            for depth, sun, em, imp, mis in [(dd, r, e, m, f) for dd in args.path_depth for r in (args.sun or [None]) for e in (args.emit or [None])
+                                             for m in ((args.emit_power if e else args.emit_power[:1]) if args.emit_power else [None])
+                                             for f in ((args.emit_mis if e and m == 1 else args.emit_mis[:1]) if args.emit_mis else [None])]:
                 ctx.set_path_depth(depth)
                 if sun is not None:
                     ctx.set_sun_disc(sun)
@@ -208,13 +223,16 @@ def main():
                     ctx.set_emitter_sampling(em)
                 if imp is not None:
                     ctx.set_emitter_importance(imp if em else 0)
+                if mis is not None:
+                    ctx.set_emitter_mis(mis if em and imp == 1 else 0)
                 for n_samples in (1, 4):
                     (ms,) = timed([lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=2, width=width, n_samples=n_samples)],
                                   max(3, args.reps // 2))
                     m = float(np.median(ms))
                     emit({"case": case, "mode": 2, "path_depth": depth, **({} if sun is None else {"sun_disc": sun}),
                           **({} if em is None else {"emitter_sampling": em}),
-                          **({"emitter_importance": imp} if imp is not None and em else {}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
+                          **({"emitter_importance": imp} if imp is not None and em else {}),
+                          **({"emitter_mis": mis} if mis is not None and em and imp == 1 else {}), "rays": n, "n_samples": n_samples, "batch_kernel_ms": round(m, 4),
                           "kernel_ms_min_max": [round(float(ms.min()), 4), round(float(ms.max()), 4)],
                           "per_sample_ms": round(m / n_samples, 4), "paths_per_s": round(n * n_samples / (m * 1e-3)), "reps": len(ms)})
             for p in (d_o, d_d, d_rgba, d_id):

@@ -290,6 +290,8 @@ def hip_lib():
         L.vrt_emitters.restype = C.c_long
         L.vrt_set_emitter_importance.argtypes = [C.c_void_p, C.c_int]
         L.vrt_set_emitter_importance.restype = C.c_int
+        L.vrt_set_emitter_mis.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_set_emitter_mis.restype = C.c_int
         L.vrt_emitter_cdf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.vrt_emitter_cdf.restype = C.c_long
         L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -1041,6 +1043,22 @@ class Context:
         """The value set_emitter_importance() last set through this object (EMIT_UNIFORM until then). A copy kept in Python: the
         C-ABI has a setter only."""
         return getattr(self, "_emitter_importance", EMIT_UNIFORM)
+
+    def set_emitter_mis(self, enable):
+        """Weigh the emitter connection against the bounce ray by the balance heuristic (vrt_set_emitter_mis): 0 / False (default) or
+        1 / True. Both keep their sample, so a vertex next to an emitter no longer carries an unbounded connection weight: the same
+        expectation, no fireflies where emitters touch surfaces. Read only where sampling is on, the list is not empty and the mode
+        is EMIT_POWER. Any other value raises before the library is touched and the previous one holds."""
+        if not isinstance(enable, (bool, int, np.integer)) or int(enable) not in (0, 1):
+            raise ValueError(f"emitter MIS: expected 0, 1 or a bool, got {enable!r}")
+        self._chk(self._L.vrt_set_emitter_mis(self._h, int(enable)))
+        self._emitter_mis = int(enable)
+
+    @property
+    def emitter_mis(self):
+        """The value set_emitter_mis() last set through this object (0 until then). A copy kept in Python: the C-ABI has a setter
+        only."""
+        return getattr(self, "_emitter_mis", 0)
 
     def emitter_cdf(self):
         """The thresholds by which EMIT_POWER picks from the emitter list (vrt_emitter_cdf) -> uint32[N], in the order of

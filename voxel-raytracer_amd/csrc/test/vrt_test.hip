@@ -133,6 +133,25 @@ __global__ void emit_pick_probe_kernel(const uint32_t *cdf, uint32_t n, const fl
     out[2 * i] = emit_pick(cdf, n, t, ticks);
     out[2 * i + 1] = ticks;
 }
+
+// the densities of vrt_set_emitter_mis on the device: the kernels' own emit_mis_density() (vrt_common.hip.h) on a caller's cases. Per
+// case fin[8] = x, dir, cs, inv_power and fin[8..10] = the hit point, iin[6] = axis, cell, w0, w1; out[2 * i] = pl, out[2 * i + 1] = pb
+__global__ void emit_mis_probe_kernel(const float *fin, const int32_t *iin, float *out, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const float *f = fin + (size_t)i * 11u;
+    const int32_t *q = iin + (size_t)i * 6u;
+    Hit h{};
+    h.point = F3{f[8], f[9], f[10]};
+    h.axis = q[0];
+    h.map = I3{q[1], q[2], q[3]};
+    h.h0 = (uint32_t)q[4];
+    h.h1 = (uint32_t)q[5];
+    float pl, pb;
+    emit_mis_density(F3{f[0], f[1], f[2]}, F3{f[3], f[4], f[5]}, f[6], h, f[7], pl, pb);
+    out[2 * i] = pl;
+    out[2 * i + 1] = pb;
+}
 }  // namespace vrt
 
 namespace vrt_internal {
@@ -222,6 +241,42 @@ int vrt_test_emit_pick(int device, const uint32_t *cdf, uint32_t n, const float 
     VRT_HIP(c, hipDeviceSynchronize());
     VRT_HIP(c, hipMemcpy(out, d_out, (size_t)count * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VRT_OK;
+}
+
+// Device probe of vrt_set_emitter_mis's densities (emit_mis_probe_kernel): `count` cases of 11 floats and 6 int32 each, host arrays,
+// synchronous. out: 2 * count floats = pl, pb. The axis must be 0, 1 or 2.
+int vrt_test_emit_mis_density(int device, const float *fin, const int32_t *iin, float *out, int count) {
+    if (!fin || !iin || !out || count < 1) return VRT_E_INVALID;
+    for (int i = 0; i < count; ++i)
+        if (iin[6 * (size_t)i] < 0 || iin[6 * (size_t)i] > 2) return VRT_E_INVALID;
+    VRT_HIP(c, hipSetDevice(device));
+    float *d_f = nullptr, *d_out = nullptr;
+    int32_t *d_i = nullptr;
+    struct Free { float *&f, *&o; int32_t *&i; ~Free() { (void)hipFree(f); (void)hipFree(o); (void)hipFree(i); } } free_on_exit{d_f, d_out, d_i};
+    VRT_HIP(c, hipMalloc((void **)&d_f, (size_t)count * 11 * sizeof(float)));
+    VRT_HIP(c, hipMalloc((void **)&d_i, (size_t)count * 6 * sizeof(int32_t)));
+    VRT_HIP(c, hipMalloc((void **)&d_out, (size_t)count * 2 * sizeof(float)));
+    VRT_HIP(c, hipMemcpy(d_f, fin, (size_t)count * 11 * sizeof(float), hipMemcpyHostToDevice));
+    VRT_HIP(c, hipMemcpy(d_i, iin, (size_t)count * 6 * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(vrt::emit_mis_probe_kernel, dim3((count + 255) / 256), dim3(256), 0, nullptr, d_f, d_i, d_out, count);
+    VRT_HIP(c, hipGetLastError());
+    VRT_HIP(c, hipDeviceSynchronize());
+    VRT_HIP(c, hipMemcpy(out, d_out, (size_t)count * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return VRT_OK;
+}
+
+// host only: Wtot and inv_power of vrt_set_emitter_mis as the context makes them (vrt_emitters.h emitter_cdf(), emitter_inv_power()) of a
+// caller's list with its record words
+long vrt_test_emitter_inv_power(const int32_t *list, const uint32_t *words, size_t n, uint64_t *wtot_out, float *inv_out) {
+    if ((n && (!list || !words)) || !wtot_out || !inv_out) return VRT_E_INVALID;
+    const std::vector<int32_t> l(list, list + 4 * n);
+    const std::vector<uint32_t> w(words, words + 2 * n);
+    std::vector<uint32_t> cdf;
+    std::vector<uint64_t> weights;
+    emitter_weights(l, w, weights);
+    emitter_cdf(weights, cdf, wtot_out);
+    *inv_out = emitter_inv_power(*wtot_out);
+    return (long)n;
 }
 
 // Arithmetic-contract probe (math_probe_kernel / math_probe_full_kernel): out[i] = op(x[i], y[i]) on `device`; host arrays, synchronous.

@@ -22,10 +22,16 @@ namespace {
 using Accum = vrt_ctx::Accum;
 
 // does the next sample still belong to the samples in the sums? (camera block, uniforms and tree as at the first of them)
+// vrt_set_emitter_mis where a full-mode add reads it: sampling on, a list that is not empty (ensure_emitters() has run by then) and
+// VRT_EMIT_POWER. Elsewhere the flag is no input: a change there does not restart.
+bool mis_read(const vrt_ctx *c) {
+    return c->emitter_mis && c->emitter_sampling && c->emitters.n > 0 && c->emitter_importance == VRT_EMIT_POWER;
+}
+
 bool same_inputs(const vrt_ctx *c, const Accum &ac) {
     return std::memcmp(ac.inv_proj, c->inv_proj, sizeof ac.inv_proj) == 0 && std::memcmp(ac.inv_view, c->inv_view, sizeof ac.inv_view) == 0 &&
            std::memcmp(ac.cam_pos, c->cam_pos, sizeof ac.cam_pos) == 0 && std::memcmp(&ac.params, &c->params, sizeof ac.params) == 0 &&
-           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc && ac.emitter_sampling == c->emitter_sampling && ac.emitter_importance == c->emitter_importance)) &&   // the primary modes ignore the depth, the sun disc, emitter sampling and its mode
+           std::memcmp(ac.lens, c->lens, sizeof ac.lens) == 0 && (ac.mode != VRT_MODE_FULL || (ac.path_depth == c->path_depth && ac.sun_disc == c->sun_disc && ac.emitter_sampling == c->emitter_sampling && ac.emitter_importance == c->emitter_importance && ac.emitter_mis == mis_read(c))) &&   // the primary modes ignore the depth, the sun disc, emitter sampling, its mode and its MIS
            ac.tree_gen == c->tree_gen;
 }
 
@@ -38,6 +44,7 @@ void take_inputs(const vrt_ctx *c, Accum &ac) {
     ac.sun_disc = c->sun_disc;
     ac.emitter_sampling = c->emitter_sampling;
     ac.emitter_importance = c->emitter_importance;
+    ac.emitter_mis = mis_read(c);
     ac.params = c->params;
     ac.tree_gen = c->tree_gen;
 }
@@ -234,7 +241,8 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         q.n = 1u;
         if (adaptive) e = launch::adaptive_tiles(tl, s);
         if (e == hipSuccess)
-            e = emit_on && acc.emit_power ? launch::accum_full_emitp(hdr, src, v, a, vs, q, adaptive, l, vrt::EmitPower{vrt::Emit{sun, ac.emit_list, ac.emit_n}, ac.emit_cdf}, grid, s)
+            e = emit_on && acc.emit_power && acc.emit_mis ? launch::accum_full_emitm(hdr, src, v, a, vs, q, adaptive, l, vrt::EmitMis{vrt::EmitPower{vrt::Emit{sun, ac.emit_list, ac.emit_n}, ac.emit_cdf}, ac.emit_inv_power}, grid, s)
+                : emit_on && acc.emit_power ? launch::accum_full_emitp(hdr, src, v, a, vs, q, adaptive, l, vrt::EmitPower{vrt::Emit{sun, ac.emit_list, ac.emit_n}, ac.emit_cdf}, grid, s)
                 : emit_on ? launch::accum_full_emit(hdr, src, v, a, vs, q, adaptive, l, vrt::Emit{sun, ac.emit_list, ac.emit_n}, grid, s)
                 : sun_on ? launch::accum_full_sun(hdr, src, v, a, vs, q, adaptive, l, sun, grid, s)
                 : deep ? launch::accum_full_deep(hdr, src, v, a, vs, q, adaptive, l, grid, s) : launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
@@ -279,6 +287,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         ac.emit_list = c->emitters.d_list;
         ac.emit_n = (uint32_t)c->emitters.n;
         ac.emit_cdf = c->emitters.d_cdf;
+        ac.emit_inv_power = emitter_inv_power(c->emitters.wtot);
     }
     const bool restart = ac.total == 0 || !same_inputs(c, ac);
     const uint32_t base = restart ? 0u : ac.total;
@@ -338,6 +347,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         step.sun = ac.mode == VRT_MODE_FULL ? ac.sun_disc : 0.0f;
         step.emit = sampling && c->emitters.n > 0;   // an empty list: the launches of sampling off
         step.emit_power = step.emit && c->emitter_importance == VRT_EMIT_POWER;   // vrt_set_emitter_importance
+        step.emit_mis = step.emit_power && c->emitter_mis;   // vrt_set_emitter_mis
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again

@@ -204,6 +204,14 @@ struct EmitPowerLensSource {
     const Lens &L;
     const EmitPower &S;
 };
+// ... and for the kernels over EmitMisPaths<...> (include/vrt.h vrt_set_emitter_mis): the EmitMis, which holds the EmitPower
+struct EmitMisCornerSource { static constexpr bool kJitter = false, kLens = false; const EmitMis &S; };
+struct EmitMisJitterSource { static constexpr bool kJitter = true, kLens = false; const EmitMis &S; };
+struct EmitMisLensSource {
+    static constexpr bool kJitter = false, kLens = true;
+    const Lens &L;
+    const EmitMis &S;
+};
 
 // ---- the kernels of the three shapes ----
 // L...: the lens kernels' fourth argument, the Lens. Each body is its kernel's own and writes out its trace call per source and its

@@ -35,6 +35,14 @@ struct EmitPower {
     const uint32_t *cdf;
 };
 
+// ... and with vrt_set_emitter_mis(ctx, 1) on top of VRT_EMIT_POWER (include/vrt.h vrt_set_emitter_mis): the same, and
+// inv_power = (float)(1.0 / (double)Wtot) of the list's summed integer weights, 0 where Wtot is 0 (vrt_emitters.h emitter_cdf()). A
+// by-value kernel argument of its own of the kernels over EmitMisPaths<...>, in the EmitPower's place; Emit and EmitPower keep their layout.
+struct EmitMis {
+    EmitPower power;
+    float inv_power;
+};
+
 // One camera and the two images it renders into. A launch carries up to kMaxViews of them (blockIdx.y selects
 // the view): frames of one scene that are known together -- a stereo pair, the next frames of a camera path, the
 // views of a light-field rig -- share one launch, so the drain of one view's last waves is filled by the next

@@ -369,6 +369,34 @@ VRT_DEV uint32_t emit_pick(const uint32_t *cdf, uint32_t n, uint32_t t, uint32_t
     return base;
 }
 
+// ... and EmitMisPaths<T>, EmitPowerPaths<T> for the kernels that weigh the connection against the bounce ray by the balance
+// heuristic (include/vrt.h vrt_set_emitter_mis; vrt_full.hip.h emit_connect_power(), trace_pixel_full()): `static constexpr bool
+// kEmitMisPaths = true`, and a Ctx that carries inv_power = 1 / Wtot beside the table.
+template <class T> struct EmitMisPaths : EmitPowerPaths<T> {
+    static constexpr bool kEmitMisPaths = true;
+    struct Ctx : EmitPowerPaths<T>::Ctx { float inv_power; };
+    static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
+    static VRT_DEV void take(Ctx &c, const EmitMis &e) { EmitPowerPaths<T>::take(c, e.power); c.inv_power = e.inv_power; }
+};
+template <class T, class = void> struct emit_mis_paths { static constexpr bool value = false; };
+template <class T> struct emit_mis_paths<T, decltype((void)T::kEmitMisPaths)> { static constexpr bool value = T::kEmitMisPaths; };
+
+// The two solid-angle densities of vrt_set_emitter_mis at the vertex x for the direction dir that ended in the hit h, a function of the
+// hit alone so that the connection and the bounce ray evaluate the same one: pl, the power rule's density of drawing this direction
+// -- the hit voxel's share w / Wtot of the list's power over the m faces of the hit cell that x sees, r2 / cl from area to solid
+// angle -- and pb = max(cs, 0) / PI, the cosine-weighted bounce's. pl is 0 where x sees no face of the cell or cl is not positive.
+VRT_DEV void emit_mis_density(F3 x, F3 dir, float cs, const Hit &h, float inv_power, float &pl, float &pb) {
+    const float kPI = 3.14159265359f;
+    const F3 v = sub3(h.point, x);
+    const float r2 = dot3(v, v);
+    const float cl = __builtin_fabsf(comp(dir, h.axis));
+    const float mx = (float)h.map.x, my = (float)h.map.y, mz = (float)h.map.z;
+    const int m = ((x.x < mx || x.x > mx + 1.0f) ? 1 : 0) + ((x.y < my || x.y > my + 1.0f) ? 1 : 0) + ((x.z < mz || x.z > mz + 1.0f) ? 1 : 0);
+    const uint32_t w = ((h.h1 >> 8) & 0xffu) * ((h.h0 & 0xffu) + ((h.h0 >> 8) & 0xffu) + ((h.h0 >> 16) & 0xffu));
+    pl = (m == 0 || !(cl > 0.0f)) ? 0.0f : ((((float)w * inv_power) * r2) / ((float)m * cl));
+    pb = (cs > 0.0f ? cs : 0.0f) / kPI;   // fmaxf(cs, 0) with the zero's sign settled
+}
+
 // A primary ray the miss-tile proof covers ("Miss tiles"): no component of its direction within 2e-8 of (-1e-8, 0], so that after
 // march()'s renormalisation (a factor within a few ulps of 1) none lies in (-1e-8, 0] and every step of the DDA has t >= 0.
 VRT_DEV bool miss_forward(F3 d) {

@@ -1,5 +1,5 @@
-// vrt_emitters.cpp -- emitter sampling's host side (include/vrt.h vrt_set_emitter_sampling, vrt_set_emitter_importance): the flag, the
-// mode, and the context's emitter list with its table of thresholds.
+// vrt_emitters.cpp -- emitter sampling's host side (include/vrt.h vrt_set_emitter_sampling, vrt_set_emitter_importance,
+// vrt_set_emitter_mis): the flag, the mode, the MIS flag, and the context's emitter list with its table of thresholds and their Wtot.
 // The list is a function of the tree and the world bounds (vrt_emitters.h emitter_list()); it is made lazily -- by vrt_emitters, and by
 // the first VRT_MODE_FULL add or ray batch with sampling on -- and made again when vrt_ctx::tree_gen (uploads, patches, batch ends,
 // compactions) or the bounds (vrt_set_params) have moved since. No device code.
@@ -21,7 +21,7 @@ int ensure_emitters(vrt_ctx *c, const char *what, bool sampling) {
         std::vector<uint64_t> weights;
         em.n = emitter_walk(c->host_records, c->params.world_min, c->params.world_max, VRT_MAX_EMITTERS, em.list, &words);
         emitter_weights(em.list, words, weights);
-        emitter_cdf(weights, em.cdf);
+        emitter_cdf(weights, em.cdf, &em.wtot);
         if (!em.list.empty()) {
             VRT_HIP(c, hipSetDevice(c->device));
             // launches of any stream (ray batches take the caller's) may still read the list
@@ -57,6 +57,13 @@ int vrt_set_emitter_importance(vrt_ctx *c, int mode) {
     if (mode != VRT_EMIT_UNIFORM && mode != VRT_EMIT_POWER)
         return vrt_fail(c, VRT_E_INVALID, "vrt_set_emitter_importance: mode must be VRT_EMIT_UNIFORM or VRT_EMIT_POWER");
     c->emitter_importance = mode;
+    return VRT_OK;
+}
+
+int vrt_set_emitter_mis(vrt_ctx *c, int enable) {
+    if (!c) return VRT_E_INVALID;
+    if (enable != 0 && enable != 1) return vrt_fail(c, VRT_E_INVALID, "vrt_set_emitter_mis: enable must be 0 or 1");
+    c->emitter_mis = enable != 0;
     return VRT_OK;
 }
 

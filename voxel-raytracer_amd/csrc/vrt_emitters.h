@@ -102,11 +102,13 @@ inline void emitter_weights(const std::vector<int32_t> &list, const std::vector<
 //   Wtot > 0:  T_j = (j + 1) + floor(C_j * (2^24 - N) / Wtot)       Wtot == 0:  T_j = floor((j + 1) * 2^24 / N)
 // so that T is strictly increasing, every emitter holds at least one of the 2^24 ticks and T_{N-1} = 2^24. N is at most 2^20
 // (VRT_MAX_EMITTERS) and Wtot below 2^63: the product passes 64 bits.
-inline void emitter_cdf(const std::vector<uint64_t> &weights, std::vector<uint32_t> &out) {
+// With `wtot` it also hands out Wtot, which vrt_set_emitter_mis turns into the launch's inv_power (emitter_inv_power()).
+inline void emitter_cdf(const std::vector<uint64_t> &weights, std::vector<uint32_t> &out, uint64_t *wtot = nullptr) {
     const uint64_t n = weights.size();
     out.resize(n);
     uint64_t total = 0;
     for (uint64_t w : weights) total += w;
+    if (wtot) *wtot = total;
     uint64_t c = 0;
     for (uint64_t j = 0; j < n; ++j) {
         c += weights[j];
@@ -114,3 +116,7 @@ inline void emitter_cdf(const std::vector<uint64_t> &weights, std::vector<uint32
         else out[j] = (uint32_t)(((j + 1) << 24) / n);
     }
 }
+
+// inv_power of include/vrt.h vrt_set_emitter_mis, "Per launch": 1 / Wtot in float32, rounded once from the float64 quotient; 0 for a
+// list without power.
+inline float emitter_inv_power(uint64_t wtot) { return wtot > 0 ? (float)(1.0 / (double)wtot) : 0.0f; }

@@ -254,7 +254,8 @@ VRT_DEV void emit_connect(const KArgs &a, const typename TRAV::Ctx &tc_, F3 hp, 
 // picks the emitter by the table of thresholds (emit_pick(): probability p = ticks * 2^-24, in proportion to its power), uf one of the
 // m <= 3 faces the vertex can see -- none: nothing more happens -- and from q on the steps are emit_connect()'s, word for word; the
 // weight is g = cs * cl * (m * size^2) / (PI * r2 * p). (emit_connect()'s body from `const F3 w` on, once more: a change there is a
-// change here.)
+// change here.) The kernels over EmitMisPaths<...> (vrt_set_emitter_mis) scale the term by wn = pl / (pl + pb) of the connection's
+// own hit and add nothing where pl is not positive.
 template <class TRAV, class OVER_PI>
 VRT_DEV void emit_connect_power(const KArgs &a, const typename TRAV::Ctx &tc_, F3 hp, F3 normal, float n1, const float tint[3], float weight,
                                 const float mc[3], float md, uint32_t &rng, const OVER_PI &over_pi, float fc[3]) {
@@ -313,10 +314,22 @@ VRT_DEV void emit_connect_power(const KArgs &a, const typename TRAV::Ctx &tc_, F
     const float emission = hv.p[1] * 10.0f;
     if (!(emission > 0.0f)) return;
     const float g = ((cs * cl) * ((float)m * (sz * sz))) / ((kPI * r2) * p);
+    if constexpr (emit_mis_paths<TRAV>::value) {   // vrt_set_emitter_mis: the balance heuristic's share of the connection
+        float pl, pb;
+        emit_mis_density(x, dir, cs, h, tc_.inv_power, pl, pb);
+        if (!(pl > 0.0f)) return;
+        const float wn = pl / (pl + pb);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float ek = over_pi(tc[k] * sc[k] * emission * weight);
-        fc[k] = fc[k] + ek * g;
+        for (int k = 0; k < 3; ++k) {
+            const float ek = over_pi(tc[k] * sc[k] * emission * weight);
+            fc[k] = fc[k] + (ek * g) * wn;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float ek = over_pi(tc[k] * sc[k] * emission * weight);
+            fc[k] = fc[k] + ek * g;
+        }
     }
 }
 
@@ -390,6 +403,11 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
     // to a point of the emitter list (emit_connect()), and in exchange a ray of depth >= 1 that hits an emissive voxel adds nothing.
     // These kernels take the Sun only where it has a radius.
     constexpr bool EMIT = emit_paths<TRAV>::value;
+    // Emitter MIS (include/vrt.h vrt_set_emitter_mis), honoured by the kernels over EmitMisPaths<...>: the connection and the bounce
+    // ray that finds an emitter both keep their sample, each weighted by the balance heuristic over emit_mis_density(). cb: the
+    // cosine of the bounce ray in flight at its vertex -- a ray of depth >= 1 is marched as soon as it is made, never pushed.
+    constexpr bool MIS = emit_mis_paths<TRAV>::value;
+    [[maybe_unused]] float cb = 0.0f;
 
 #ifdef VRT_EXP_STATS   // experiment builds only (tools/room_stats.sh): what the wave's time is made of, left in tile_cost
     unsigned long long st_acc = 0;
@@ -517,6 +535,12 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 if constexpr (!EMIT) {   // (EMIT: the vertex before has sampled the emitters itself)
 #pragma unroll
                     for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sc[k] * emission * r.weight);
+                } else if constexpr (MIS) {   // ... and with vrt_set_emitter_mis the bounce ray keeps the complementary share
+                    float pl, pb;
+                    emit_mis_density(r.o, r.d, cb, h, tc_.inv_power, pl, pb);
+                    const float wb = !(pl > 0.0f) ? 1.0f : pb / (pl + pb);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) fc[k] = fc[k] + over_pi(tc[k] * sc[k] * emission * r.weight) * wb;
                 }
                 continue;
             }
@@ -571,6 +595,7 @@ __device__ void trace_pixel_full(const KArgs &a, const View &vw, const typename 
                 // the primary ray came through): it takes r's registers instead of a round trip through scratch, 17 words each
                 // way per lane with the march waiting on the reload. (Round 2 did this for an empty stack only.)
                 r = make_ray(add3(hp, scale3(normal, 1e-1f)), bd, n1, nw, tint, 0.0f, last.c, last.c[3] * 5.0f, r.depth + 1);
+                if constexpr (MIS) cb = dot3(normal, bd);
                 in_regs = true;
             }
             VRT_ST_MARK(9);

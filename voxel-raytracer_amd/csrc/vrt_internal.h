@@ -95,6 +95,7 @@ struct vrt_ctx {
     float sun_disc = 0.0f;          // vrt_set_sun_disc: the tangent of the sun's angular radius, honoured where the path depth is
     bool emitter_sampling = false;  // vrt_set_emitter_sampling: next-event estimation towards the emitter list, honoured where the path depth is
     int emitter_importance = VRT_EMIT_UNIFORM;   // vrt_set_emitter_importance: how a vertex picks from the list; read only where sampling is on and the list is not empty
+    bool emitter_mis = false;       // vrt_set_emitter_mis: read only where sampling is on, the list is not empty and the mode is VRT_EMIT_POWER
     // the emitter list (vrt_emitters.cpp ensure_emitters()) of the tree generation and world bounds it was made for
     struct Emitters {
         bool built = false;
@@ -105,6 +106,7 @@ struct vrt_ctx {
         DevBuf<int32_t> d_list;          // the same on the device
         std::vector<uint32_t> cdf;       // one threshold per entry (vrt_emitters.h emitter_cdf()), made and uploaded with the list
         DevBuf<uint32_t> d_cdf;
+        uint64_t wtot = 0;               // the sum of the list's integer weights W_j, kept when the table is made (vrt_set_emitter_mis)
     };
     Emitters emitters;
     int variant = 0;
@@ -241,6 +243,8 @@ struct vrt_ctx {
         uint32_t emit_n = 0;
         int emitter_importance = VRT_EMIT_UNIFORM;
         const uint32_t *emit_cdf = nullptr;      // ... and its thresholds (emitters.d_cdf)
+        bool emitter_mis = false;                // vrt_set_emitter_mis as the sums took it: the flag where it is read, false elsewhere
+        float emit_inv_power = 0.0f;             // ... and 1 / Wtot of the list (emitter_inv_power())
         vrt_params params{};
         uint64_t tree_gen = 0;
         DevBuf<uint32_t> d_sums;                 // 4 words per pixel
@@ -345,6 +349,7 @@ struct AccumStep {
     float sun = 0.0f;
     bool emit = false;
     bool emit_power = false;   // with emit: VRT_EMIT_POWER (vrt_set_emitter_importance), the kernels over EmitPowerPaths<...>
+    bool emit_mis = false;     // with emit_power: vrt_set_emitter_mis, the kernels over EmitMisPaths<...>
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);

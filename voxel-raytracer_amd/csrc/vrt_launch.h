@@ -199,6 +199,17 @@ inline hipError_t accum_full_emitp(bool hdr, accum::Source src, const Variant &v
     return hdr ? accum_full_hdr_emitp(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emitp(src, v, a, vs, q, adaptive, l, em, grid, s);
 }
 
+// vrt_launch_accum_emitm.hip, vrt_launch_accum_hdr_emitm.hip: the same with vrt_set_emitter_mis on top of VRT_EMIT_POWER (include/vrt.h):
+// kernels over EmitMisPaths<...>, which take `em` -- the EmitPower and 1 / Wtot -- as their last argument
+hipError_t accum_full_emitm(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
+                            const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s);
+hipError_t accum_full_hdr_emitm(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                                const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s);
+inline hipError_t accum_full_emitm(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                                   bool adaptive, const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s) {
+    return hdr ? accum_full_hdr_emitm(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emitm(src, v, a, vs, q, adaptive, l, em, grid, s);
+}
+
 // vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
 // rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
 // starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
@@ -232,6 +243,12 @@ hipError_t shade_rays_hdr_emit(const Variant &v, const KArgs &a, const ViewSet &
 hipError_t shade_rays_emitp(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const EmitPower &em, uint32_t grid, hipStream_t s,
                             hipEvent_t ev0, hipEvent_t ev1);
 hipError_t shade_rays_hdr_emitp(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const EmitPower &em, uint32_t grid,
+                                hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
+// vrt_launch_rays_emitm.hip, vrt_launch_rays_hdr_emitm.hip: ... and with vrt_set_emitter_mis on top of VRT_EMIT_POWER
+hipError_t shade_rays_emitm(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const EmitMis &em, uint32_t grid, hipStream_t s,
+                            hipEvent_t ev0, hipEvent_t ev1);
+hipError_t shade_rays_hdr_emitm(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const EmitMis &em, uint32_t grid,
                                 hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch

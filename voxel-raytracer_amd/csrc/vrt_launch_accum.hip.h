@@ -168,6 +168,25 @@ hipError_t full_emit_power(accum::Source src, const Variant &v, const KArgs &a, 
     return hipErrorInvalidValue;
 }
 
+// EMIT MIS (vrt_launch_accum_emitm.hip, vrt_launch_accum_hdr_emitm.hip): the same over EmitMisPaths<...> (include/vrt.h
+// vrt_set_emitter_mis); the kernels' last argument is the EmitMis
+template <bool HDR>
+hipError_t full_emit_mis(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
+                         const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s) {
+    const auto f = [&](auto sh) {
+        using S = decltype(sh);
+        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
+        if (src == accum::Source::kCorner)
+            return go(accum::full_accum_kernel<accum::EmitMisCornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitMis>, grid, S::kBlock, s, a, vs, qs, em);
+        if (src == accum::Source::kJitter)
+            return go(accum::full_accum_kernel<accum::EmitMisJitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitMis>, grid, S::kBlock, s, a, vs, qs, em);
+        return go(accum::full_accum_kernel<accum::EmitMisLensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, EmitMis>, grid, S::kBlock, s, a, vs, qs, l, em);
+    };
+    if (v.trav >= 3) return shape<EmitMisPaths<v4::TravAny>, 64, 5>(adaptive, f);
+    if (v.trav >= 1) return shape<EmitMisPaths<v1::Trav>, 256, 1>(adaptive, f);
+    return hipErrorInvalidValue;
+}
+
 template <bool HDR, bool DEEP = false, class... SUN>
 hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s, const SUN &...sun) {
     if constexpr (sizeof...(SUN) != 0) {

@@ -91,6 +91,8 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     if (emit_on) em = vrt::Emit{sun, c->emitters.d_list.get(), (uint32_t)c->emitters.n};
     const bool power = emit_on && c->emitter_importance == VRT_EMIT_POWER;   // vrt_set_emitter_importance: the kernels over EmitPowerPaths<...>
     const vrt::EmitPower emp{em, power ? c->emitters.d_cdf.get() : nullptr};
+    const bool mis = power && c->emitter_mis;   // vrt_set_emitter_mis: the kernels over EmitMisPaths<...>
+    const vrt::EmitMis emm{emp, mis ? emitter_inv_power(c->emitters.wtot) : 0.0f};
 
     vrt::rays::Args q;
     q.origins = d_origins;
@@ -116,13 +118,15 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
         hq.n_total = hdr->n_prior + n_samples;
         hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
         hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = power ? vrt::launch::shade_rays_hdr_emitp(v, a, vs, hq, emp, grid, s, prof.ev0, prof.ev1)
+        e = mis ? vrt::launch::shade_rays_hdr_emitm(v, a, vs, hq, emm, grid, s, prof.ev0, prof.ev1)
+            : power ? vrt::launch::shade_rays_hdr_emitp(v, a, vs, hq, emp, grid, s, prof.ev0, prof.ev1)
             : emit_on ? vrt::launch::shade_rays_hdr_emit(v, a, vs, hq, em, grid, s, prof.ev0, prof.ev1)
             : sun_on ? vrt::launch::shade_rays_hdr_sun(v, a, vs, hq, sun, grid, s, prof.ev0, prof.ev1)
             : deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
                    : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
     } else {
-        e = power ? vrt::launch::shade_rays_emitp(v, a, vs, q, emp, grid, s, prof.ev0, prof.ev1)
+        e = mis ? vrt::launch::shade_rays_emitm(v, a, vs, q, emm, grid, s, prof.ev0, prof.ev1)
+            : power ? vrt::launch::shade_rays_emitp(v, a, vs, q, emp, grid, s, prof.ev0, prof.ev1)
             : emit_on ? vrt::launch::shade_rays_emit(v, a, vs, q, em, grid, s, prof.ev0, prof.ev1)
             : sun_on ? vrt::launch::shade_rays_sun(v, a, vs, q, sun, grid, s, prof.ev0, prof.ev1)
             : deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
