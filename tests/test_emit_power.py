@@ -346,7 +346,7 @@ def test_hip_code_object_holds_the_power_kernels(V):
     blob = open(V.HIP_LIB, "rb").read()
     assert b"gfx950" in blob
     names = set(re.findall(rb"_ZN3vrt[0-9A-Za-z_]*EmitPowerPaths[0-9A-Za-z_]*", blob))
-    for kernel in (b"full_accum_kernel", b"shade_rays_full_emitp_kernel"):
+    for kernel in (b"full_accum_kernel", b"shade_rays_full_kernel"):
         for trav in (b"v4", b"v1"):
             assert any(kernel in n and b"EmitPowerPathsINS_2" + trav in n for n in names), f"no {kernel.decode()} over EmitPowerPaths<{trav.decode()}::...>"
 

@@ -248,7 +248,7 @@ def test_hip_code_object_holds_the_emit_kernels(V):
     blob = open(V.HIP_LIB, "rb").read()
     assert b"gfx950" in blob
     names = set(re.findall(rb"_ZN3vrt[0-9A-Za-z_]*EmitPaths[0-9A-Za-z_]*", blob))
-    for kernel in (b"full_accum_kernel", b"shade_rays_full_emit_kernel"):
+    for kernel in (b"full_accum_kernel", b"shade_rays_full_kernel"):
         assert any(kernel in n for n in names), f"no {kernel.decode()} over EmitPaths in libvrt_hip.so"
     for trav in (b"v4", b"v1"):
         assert any(trav in n for n in names), f"no kernel over EmitPaths<{trav.decode()}::...>"

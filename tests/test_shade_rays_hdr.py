@@ -111,15 +111,16 @@ def test_header_declares_and_library_exports_the_hdr_calls(V):
 
 
 def test_hip_code_object_holds_the_hdr_forms(V):
-    """shade_rays_kernel<MODE, TRAV, WPE, HDR> and shade_rays_full_kernel<TRAV, WPE, LOOP, HDR> over rays::HdrArgs: the mangled
-    names end their template arguments in Lb1E (HDR = true), in both modes' kernels and both LOOP forms"""
+    """shade_rays_kernel<MODE, TRAV, WPE, HDR> and shade_rays_full_kernel<TRAV, WPE, LOOP, HDR, X...> over rays::HdrArgs: the mangled
+    names end their template arguments in Lb1E (HDR = true) -- and, the full kernel's, in the empty pack JE of a family that takes no
+    argument -- in both modes' kernels and both LOOP forms"""
     blob = open(V.HIP_LIB, "rb").read()
     assert b"gfx950" in blob
     names = set(re.findall(rb"_ZN3vrt4rays\d+shade_rays_(?:full_)?kernelI[A-Za-z0-9_]+", blob))
-    hdr = {n for n in names if re.search(rb"Lb1EEEv", n)}
+    hdr = {n for n in names if re.search(rb"Lb1E(?:JE)?EEv", n)}
     assert any(b"shade_rays_kernelILi0E" in n for n in hdr) and any(b"shade_rays_kernelILi1E" in n for n in hdr), sorted(names)
-    assert any(b"full_kernel" in n and b"Lb1ELb1EEEv" in n for n in hdr), sorted(names)
-    assert any(b"full_kernel" in n and b"Lb0ELb1EEEv" in n for n in hdr), sorted(names)
+    assert any(b"full_kernel" in n and b"Lb1ELb1EJEEEv" in n for n in hdr), sorted(names)
+    assert any(b"full_kernel" in n and b"Lb0ELb1EJEEEv" in n for n in hdr), sorted(names)
 
 
 def test_wrappers_refuse_bad_values_before_the_device(V):

@@ -244,7 +244,7 @@ def test_hip_code_object_holds_the_sun_kernels(V):
     blob = open(V.HIP_LIB, "rb").read()
     assert b"gfx950" in blob
     names = set(re.findall(rb"_ZN3vrt[0-9A-Za-z_]*SunPaths[0-9A-Za-z_]*", blob))
-    for kernel in (b"full_accum_kernel", b"opaque_accum_kernel", b"bounce_accum_sun_kernel", b"shade_rays_full_sun_kernel"):
+    for kernel in (b"full_accum_kernel", b"opaque_accum_kernel", b"bounce_accum_kernel", b"shade_rays_full_kernel"):
         assert any(kernel in n for n in names), f"no {kernel.decode()} over SunPaths in libvrt_hip.so"
 
 

@@ -189,11 +189,10 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     q.hsum = ac.d_hsum;
     q.hframe = ac.d_hframe;
     const bool hdr = acc.hdr, adaptive = acc.adaptive;
-    const bool deep = mode == VRT_MODE_FULL && a.path_depth > 1u;   // the kernels that honour the path depth (vrt_set_path_depth)
-    const bool sun_on = mode == VRT_MODE_FULL && acc.sun > 0.0f;    // ... and the sun disc (vrt_set_sun_disc), at every depth
-    const vrt::Sun sun = sun_on ? sun_block(a.light_dir, acc.sun) : vrt::Sun{};   // radius 0: nothing is made, nothing is passed
-    const bool emit_on = mode == VRT_MODE_FULL && acc.emit;         // ... and emitter sampling (vrt_set_emitter_sampling): the general path tracer only
-    if (emit_on && two_pass) return hipErrorInvalidValue;           // the dispatcher does not choose the opaque routes for it
+    // the kernels of VRT_MODE_FULL by the step's own snapshot (acc.paths: what the add that queued it read), not the context
+    launch::PathFamily fam;
+    launch::PathArgs pa;
+    if (!launch::select_paths(mode, acc.paths, a.light_dir, two_pass, fam, pa)) return hipErrorInvalidValue;
     const vrt::accum::HdrFrame hf{ac.d_pass1, ac.d_id, ac.d_hframe};
     q.sums = ac.d_sums;
     q.pass1_rgba = ac.d_pass1;
@@ -217,8 +216,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     if (mode != VRT_MODE_FULL)   // one launch, the samples looped in the lanes
         return launch::accum_primary(hdr, mode, src, v, a, vs, q, adaptive, l, grid, s);
     if (two_pass && src != Source::kCorner)   // MODE 6's chain per sample, looped in the lanes
-        return sun_on ? launch::accum_opaque_sun(hdr, src, a, vs, q, adaptive, l, sun, grid, s)
-               : deep ? launch::accum_opaque_deep(hdr, src, a, vs, q, adaptive, l, grid, s) : launch::accum_opaque(hdr, src, a, vs, q, adaptive, l, grid, s);
+        return launch::accum_opaque(hdr, fam, pa, src, a, vs, q, adaptive, l, grid, s);
     hipError_t e = hipSuccess;
     if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
         a.defer_rec = reinterpret_cast<float *>(ac.d_seed.get());
@@ -230,8 +228,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
             if (e != hipSuccess) return e;
             ac.pass1 = true;
         }
-        return sun_on ? launch::accum_bounce_sun(hdr, a, vs, q, adaptive, sun, grid, s)
-               : deep ? launch::accum_bounce_deep(hdr, a, vs, q, adaptive, grid, s) : launch::accum_bounce(hdr, a, vs, q, adaptive, grid, s);
+        return launch::accum_bounce(hdr, fam, pa, a, vs, q, adaptive, grid, s);
     }
     // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
     const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, a.width, a.height, ac.min_samples, ac.max_samples,
@@ -240,12 +237,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         q.first = acc.first + k;
         q.n = 1u;
         if (adaptive) e = launch::adaptive_tiles(tl, s);
-        if (e == hipSuccess)
-            e = emit_on && acc.emit_power && acc.emit_mis ? launch::accum_full_emitm(hdr, src, v, a, vs, q, adaptive, l, vrt::EmitMis{vrt::EmitPower{vrt::Emit{sun, ac.emit_list, ac.emit_n}, ac.emit_cdf}, ac.emit_inv_power}, grid, s)
-                : emit_on && acc.emit_power ? launch::accum_full_emitp(hdr, src, v, a, vs, q, adaptive, l, vrt::EmitPower{vrt::Emit{sun, ac.emit_list, ac.emit_n}, ac.emit_cdf}, grid, s)
-                : emit_on ? launch::accum_full_emit(hdr, src, v, a, vs, q, adaptive, l, vrt::Emit{sun, ac.emit_list, ac.emit_n}, grid, s)
-                : sun_on ? launch::accum_full_sun(hdr, src, v, a, vs, q, adaptive, l, sun, grid, s)
-                : deep ? launch::accum_full_deep(hdr, src, v, a, vs, q, adaptive, l, grid, s) : launch::accum_full(hdr, src, v, a, vs, q, adaptive, l, grid, s);
+        if (e == hipSuccess) e = launch::accum_full(hdr, fam, pa, src, v, a, vs, q, adaptive, l, grid, s);
     }
     return e;
 }
@@ -344,10 +336,10 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     } else if (r == VRT_OK) {
         AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
-        step.sun = ac.mode == VRT_MODE_FULL ? ac.sun_disc : 0.0f;
-        step.emit = sampling && c->emitters.n > 0;   // an empty list: the launches of sampling off
-        step.emit_power = step.emit && c->emitter_importance == VRT_EMIT_POWER;   // vrt_set_emitter_importance
-        step.emit_mis = step.emit_power && c->emitter_mis;   // vrt_set_emitter_mis
+        // the snapshot launch_accum_step() selects the kernels by: the depth and the sun as the sums took them, the emitter switches
+        // (same_inputs() has found them unchanged) and the list as this add found it
+        step.paths = PathSetup{ac.path_depth, ac.sun_disc, sampling, c->emitter_importance, c->emitter_mis,
+                               ac.emit_list, ac.emit_n, ac.emit_cdf, ac.emit_inv_power};
         r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, ac.mode, ac.d_pass1, ac.d_id, c->stream, nullptr, 1, &step);
     }
     if (r) {   // what this add left in the sums is unknown: the next add starts again

@@ -180,37 +180,14 @@ struct LensSource {
     static constexpr bool kJitter = false, kLens = true;
     const Lens &L;   // the kernel's Lens argument, read where it is used
 };
-// ... and the same three for the kernels over SunPaths<...> (include/vrt.h vrt_set_sun_disc): the kernel's last argument is the Sun
-struct SunCornerSource { static constexpr bool kJitter = false, kLens = false; const Sun &S; };
-struct SunJitterSource { static constexpr bool kJitter = true, kLens = false; const Sun &S; };
-struct SunLensSource {
+// ... and the same three for the kernels over a family that takes an argument (vrt_common.hip.h: SunPaths<...> and the emitter
+// families; A = TRAV::Arg): the kernel's last argument, handed to the traversal's context by TRAV::take()
+template <class A> struct ArgCornerSource { static constexpr bool kJitter = false, kLens = false; const A &S; };
+template <class A> struct ArgJitterSource { static constexpr bool kJitter = true, kLens = false; const A &S; };
+template <class A> struct ArgLensSource {
     static constexpr bool kJitter = false, kLens = true;
     const Lens &L;
-    const Sun &S;
-};
-// ... and for the kernels over EmitPaths<...> (include/vrt.h vrt_set_emitter_sampling): the last argument is the Emit, Sun included
-struct EmitCornerSource { static constexpr bool kJitter = false, kLens = false; const Emit &S; };
-struct EmitJitterSource { static constexpr bool kJitter = true, kLens = false; const Emit &S; };
-struct EmitLensSource {
-    static constexpr bool kJitter = false, kLens = true;
-    const Lens &L;
-    const Emit &S;
-};
-// ... and for the kernels over EmitPowerPaths<...> (include/vrt.h vrt_set_emitter_importance): the EmitPower, which holds the Emit
-struct EmitPowerCornerSource { static constexpr bool kJitter = false, kLens = false; const EmitPower &S; };
-struct EmitPowerJitterSource { static constexpr bool kJitter = true, kLens = false; const EmitPower &S; };
-struct EmitPowerLensSource {
-    static constexpr bool kJitter = false, kLens = true;
-    const Lens &L;
-    const EmitPower &S;
-};
-// ... and for the kernels over EmitMisPaths<...> (include/vrt.h vrt_set_emitter_mis): the EmitMis, which holds the EmitPower
-struct EmitMisCornerSource { static constexpr bool kJitter = false, kLens = false; const EmitMis &S; };
-struct EmitMisJitterSource { static constexpr bool kJitter = true, kLens = false; const EmitMis &S; };
-struct EmitMisLensSource {
-    static constexpr bool kJitter = false, kLens = true;
-    const Lens &L;
-    const EmitMis &S;
+    const A &S;
 };
 
 // ---- the kernels of the three shapes ----
@@ -265,7 +242,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
-    if constexpr (sun_paths<TRAV>::value) tc_.sun = src.S;
+    if constexpr (sun_paths<TRAV>::value) TRAV::take(tc_, src.S);
     int px, py;
     if (!frame_pixel<64>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
@@ -313,6 +290,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
+    // (SunPaths<...>: the Sun assigned here, not through its take() -- with the call seven of this kernel's forms compile to the same
+    // instructions in another order and other registers, profiles/path_family_fold_codegen.txt)
     if constexpr (emit_paths<TRAV>::value) TRAV::take(tc_, src.S);
     else if constexpr (sun_paths<TRAV>::value) tc_.sun = src.S;
     int px, py;
@@ -365,101 +344,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 // than their depth-1 twins, at the budget where the chain's loop-carried state -- origin, direction, tint, colour, RNG, medium, live
 // across every segment's march and shadow ray -- stays in registers: no scratch (profiles/path_depth_resource_usage.txt; at the
 // twins' 72 and 80 registers the compiler parks 16-71 of them in scratch around the marches, inside the depth loop).
-// (bounce_accum_sun_kernel below is this kernel's body once more, for the sun disc: a change here is a change there.)
+// X...: the Sun of SunPaths<...> (include/vrt.h vrt_set_sun_disc) as a fourth argument of its own, none for the other traversals:
+// full::bounce_pixel() then ignores the seed's lit bit and casts the depth-0 shadow ray per sample.
 template <class TRAV, bool ADAPT, bool HDR>
 constexpr int bounce_wpe() { return deep_paths<TRAV>::value ? (ADAPT && HDR ? 3 : 4) : 7; }
 constexpr int kDeepOpaqueWpe = 4;   // opaque_accum_kernel over DeepPaths<...> (vrt_launch_accum.hip.h)
-template <class TRAV, bool ADAPT = false, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<TRAV, ADAPT, HDR>()))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q) {
+template <class TRAV, bool ADAPT = false, bool HDR = false, class... X>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<TRAV, ADAPT, HDR>()))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const X... arg) {
     __shared__ uint32_t s_seed[kSeedPlanes][64];
     __shared__ uint32_t s_sum[3][64];
     __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];   // (HDR = false: never touched, and dropped)
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
-    const int lane = threadIdx.x & 63;
-    const int tile = blockIdx.x;
-    int px, py;
-    tile_pixel(a, tile, px, py);
-    if (px >= a.width || py >= a.height) return;
-    const uint32_t *sp = reinterpret_cast<const uint32_t *>(a.defer_rec) + ((size_t)tile * kSeedPlanes) * 64 + lane;
-    const uint32_t word = sp[3 * 64];
-    uint32_t r = 0u, g = 0u, b = 0u;
-    PixelState st{};
-    HdrSum hs{};
-    if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
-    if constexpr (HDR) hs = load_hdr(q.hsum, (size_t)py * (size_t)a.width + (size_t)px);
-    if (word & kSeedValid) {
-#pragma unroll
-        for (uint32_t p = 0; p < kSeedPlanes; ++p) s_seed[p][lane] = sp[p * 64];
-        if constexpr (ADAPT) {
-            s_sum[0][lane] = st.r; s_sum[1][lane] = st.g; s_sum[2][lane] = st.b;
-        } else {
-            s_sum[0][lane] = 0u; s_sum[1][lane] = 0u; s_sum[2][lane] = 0u;
-        }
-        // volatile: the seed is read back for every sample, not hoisted into registers across the loop
-        volatile uint32_t *vs_seed = &s_seed[0][0];
-        volatile uint32_t *vs_sum = &s_sum[0][0];
-        volatile double *vs_hsum = &s_hsum[0][0];
-        if constexpr (HDR) { vs_hsum[0 * 64 + lane] = hs.r; vs_hsum[1 * 64 + lane] = hs.g; vs_hsum[2 * 64 + lane] = hs.b; }
-        // every sample is bounce_pixel's own arithmetic on the same seed: direct term, then the bounce's term, then unorm8
-        for (uint32_t k = 0; k < q.n; ++k) {
-            if constexpr (ADAPT) {
-                st.r = vs_sum[0 * 64 + lane]; st.g = vs_sum[1 * 64 + lane]; st.b = vs_sum[2 * 64 + lane];
-                if (!state_active(q.min, q.max, q.tol, st)) break;
-            }
-            Seed seed;
-            seed.hp = F3{__uint_as_float(vs_seed[0 * 64 + lane]), __uint_as_float(vs_seed[1 * 64 + lane]), __uint_as_float(vs_seed[2 * 64 + lane])};
-            seed.word = vs_seed[3 * 64 + lane];
-            seed.iof = __uint_as_float(vs_seed[4 * 64 + lane]);
-            const KArgs ak = loop_args(a);
-            uint32_t rgba = 0u;
-            if constexpr (HDR) {
-                float fc[3] = {0.0f, 0.0f, 0.0f};
-                full::bounce_pixel<TRAV, true>(ak, tc_, px, py, seed, rgba, q.first + k, fc);
-                vs_hsum[0 * 64 + lane] = vs_hsum[0 * 64 + lane] + (double)hdr_value(fc[0]);
-                vs_hsum[1 * 64 + lane] = vs_hsum[1 * 64 + lane] + (double)hdr_value(fc[1]);
-                vs_hsum[2 * 64 + lane] = vs_hsum[2 * 64 + lane] + (double)hdr_value(fc[2]);
-            } else full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, rgba, q.first + k);
-            vs_sum[0 * 64 + lane] = vs_sum[0 * 64 + lane] + (rgba & 0xffu);
-            vs_sum[1 * 64 + lane] = vs_sum[1 * 64 + lane] + ((rgba >> 8) & 0xffu);
-            vs_sum[2 * 64 + lane] = vs_sum[2 * 64 + lane] + ((rgba >> 16) & 0xffu);
-            if constexpr (ADAPT) {
-                const uint32_t l = (rgba & 0xffu) + ((rgba >> 8) & 0xffu) + ((rgba >> 16) & 0xffu);
-                st.n += 1u;
-                st.q += (uint64_t)(l * l);
-            }
-        }
-        r = vs_sum[0 * 64 + lane]; g = vs_sum[1 * 64 + lane]; b = vs_sum[2 * 64 + lane];
-        if constexpr (HDR) { hs.r = vs_hsum[0 * 64 + lane]; hs.g = vs_hsum[1 * 64 + lane]; hs.b = vs_hsum[2 * 64 + lane]; }
-    } else if constexpr (ADAPT) {
-        const uint32_t more = adaptive_constant_count(st.n, q.n, q.min) - st.n;
-        add_repeat(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], more, st);
-        r = st.r; g = st.g; b = st.b;
-        if constexpr (HDR) add_hdr_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, more, hs);
-    } else {   // sky, emissive surfaces: pass 1's bytes are every sample's
-        add_bytes(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], r, g, b);
-        r *= q.n; g *= q.n; b *= q.n;
-        if constexpr (HDR) add_hdr_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, q.n, hs);
-    }
-    if constexpr (HDR) store_hdr(q.hsum, (size_t)py * (size_t)a.width + (size_t)px, hs);
-    if constexpr (ADAPT) {
-        st.r = r; st.g = g; st.b = b;
-        store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);
-    } else {
-        store_sums(q.sums, (size_t)py * (size_t)a.width + (size_t)px, r, g, b);
-    }
-}
-
-// The same over SunPaths<...> (include/vrt.h vrt_set_sun_disc), with the Sun as a fourth argument of its own: full::bounce_pixel() then
-// ignores the seed's lit bit and casts the depth-0 shadow ray per sample. The body is written out again, as every body here is.
-template <class TRAV, bool ADAPT = false, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<TRAV, ADAPT, HDR>()))) void bounce_accum_sun_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const Sun sun) {
-    __shared__ uint32_t s_seed[kSeedPlanes][64];
-    __shared__ uint32_t s_sum[3][64];
-    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];   // (HDR = false: never touched, and dropped)
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    tc_.sun = sun;
+    if constexpr (sizeof...(X) != 0) ((tc_.sun = arg), ...);   // the one Sun, assigned as full_accum_kernel assigns it and for its reason
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x;
     int px, py;

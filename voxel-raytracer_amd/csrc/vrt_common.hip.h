@@ -324,7 +324,9 @@ constexpr int kMaxPathDepth = 8;   // VRT_MAX_PATH_DEPTH
 template <class T> struct SunPaths : DeepPaths<T> {
     static constexpr bool kSunPaths = true;
     struct Ctx : T::Ctx { Sun sun; };
+    using Arg = Sun;
     static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
+    static VRT_DEV void take(Ctx &c, const Arg &s) { c.sun = s; }
 };
 template <class T, class = void> struct sun_paths { static constexpr bool value = false; };
 template <class T> struct sun_paths<T, decltype((void)T::kSunPaths)> { static constexpr bool value = T::kSunPaths; };
@@ -337,7 +339,8 @@ template <class T> struct EmitPaths : SunPaths<T> {
     static constexpr bool kEmitPaths = true;
     struct Ctx : SunPaths<T>::Ctx { const int32_t *emit; uint32_t n_emit; };
     static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
-    static VRT_DEV void take(Ctx &c, const Emit &e) { c.sun = e.sun; c.emit = e.list; c.n_emit = e.n; }
+    using Arg = Emit;
+    static VRT_DEV void take(Ctx &c, const Arg &e) { c.sun = e.sun; c.emit = e.list; c.n_emit = e.n; }
 };
 template <class T, class = void> struct emit_paths { static constexpr bool value = false; };
 template <class T> struct emit_paths<T, decltype((void)T::kEmitPaths)> { static constexpr bool value = T::kEmitPaths; };
@@ -349,7 +352,8 @@ template <class T> struct EmitPowerPaths : EmitPaths<T> {
     static constexpr bool kEmitPowerPaths = true;
     struct Ctx : EmitPaths<T>::Ctx { const uint32_t *cdf; };
     static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
-    static VRT_DEV void take(Ctx &c, const EmitPower &e) { EmitPaths<T>::take(c, e.emit); c.cdf = e.cdf; }
+    using Arg = EmitPower;
+    static VRT_DEV void take(Ctx &c, const Arg &e) { EmitPaths<T>::take(c, e.emit); c.cdf = e.cdf; }
 };
 template <class T, class = void> struct emit_power_paths { static constexpr bool value = false; };
 template <class T> struct emit_power_paths<T, decltype((void)T::kEmitPowerPaths)> { static constexpr bool value = T::kEmitPowerPaths; };
@@ -376,7 +380,8 @@ template <class T> struct EmitMisPaths : EmitPowerPaths<T> {
     static constexpr bool kEmitMisPaths = true;
     struct Ctx : EmitPowerPaths<T>::Ctx { float inv_power; };
     static VRT_DEV void block_init(const KArgs &a, Ctx &c) { T::block_init(a, c); }
-    static VRT_DEV void take(Ctx &c, const EmitMis &e) { EmitPowerPaths<T>::take(c, e.power); c.inv_power = e.inv_power; }
+    using Arg = EmitMis;
+    static VRT_DEV void take(Ctx &c, const Arg &e) { EmitPowerPaths<T>::take(c, e.power); c.inv_power = e.inv_power; }
 };
 template <class T, class = void> struct emit_mis_paths { static constexpr bool value = false; };
 template <class T> struct emit_mis_paths<T, decltype((void)T::kEmitMisPaths)> { static constexpr bool value = T::kEmitMisPaths; };

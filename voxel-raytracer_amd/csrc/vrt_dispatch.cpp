@@ -454,7 +454,7 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     bool measure = false;
     long grid = schedule(c, s, v, acc != nullptr, mode, tiles, vs, a, st, measure);
     const ProfSlot prof = acc ? ProfSlot{} : ProfSlot::take(c);
-    const bool two_pass = !(acc && acc->emit) && opaque_two_pass(c, mode, v, vs, n_views, lens, lsel);   // emitter sampling: the general path tracer
+    const bool two_pass = !(acc && acc->paths.emit()) && opaque_two_pass(c, mode, v, vs, n_views, lens, lsel);   // emitter sampling: the general path tracer
     // the general full path tracer starts the heaviest groups of an ordered launch, measuring or not, as part-tile waves (KArgs::split_count)
     if (mode == VRT_MODE_FULL && !two_pass && st && a.group_order && c->heavy_split_on) {
         a.split_count = st->d_order + st->n_groups;

@@ -338,18 +338,29 @@ struct ProfSlot {
 // (adaptive: n rounds of the context's adaptive accumulation, vrt_accum_begin_adaptive; the kernels' adaptive forms)
 // (hdr: an HDR accumulation, vrt_accum_keep_hdr; the kernels' HDR forms. frame_only, with hdr, modes 0 / 1 from the corner: no
 // sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
-// (sun > 0: VRT_MODE_FULL with a sun disc of that tangent radius, vrt_set_sun_disc; the kernels over SunPaths<...>)
-// (emit: VRT_MODE_FULL with emitter sampling on and a list that is not empty, vrt_set_emitter_sampling; the general path tracer over
-// EmitPaths<...>, never the opaque routes)
+// (paths: what selects the kernels of VRT_MODE_FULL, as the add that queues the step read it)
+// PathSetup: the settings that select the family of path tracer kernels of a VRT_MODE_FULL launch and fill its argument block
+// (vrt_launch.h select_paths()), as an accumulation step or a ray batch read them
+struct PathSetup {
+    int path_depth = 1;             // vrt_set_path_depth
+    float sun_radius = 0.0f;        // vrt_set_sun_disc: the tangent of the radius, 0: no disc
+    bool sampling = false;          // vrt_set_emitter_sampling
+    int importance = VRT_EMIT_UNIFORM;   // vrt_set_emitter_importance
+    bool mis = false;               // vrt_set_emitter_mis
+    const int32_t *list = nullptr;  // the context's emitter list, its length, its thresholds and 1 / Wtot (vrt_emitters.cpp)
+    uint32_t n = 0;
+    const uint32_t *cdf = nullptr;
+    float inv_power = 0.0f;
+    // emitter sampling as a launch sees it -- an empty list gives the launches of sampling off: the general path tracer over
+    // EmitPaths<...>, never the opaque routes
+    bool emit() const { return sampling && n > 0; }
+};
 struct AccumStep {
     uint32_t first, n;
     bool jitter;
     float aperture = 0.0f, focus = 1.0f;
     bool adaptive = false, hdr = false, frame_only = false;
-    float sun = 0.0f;
-    bool emit = false;
-    bool emit_power = false;   // with emit: VRT_EMIT_POWER (vrt_set_emitter_importance), the kernels over EmitPowerPaths<...>
-    bool emit_mis = false;     // with emit_power: vrt_set_emitter_mis, the kernels over EmitMisPaths<...>
+    PathSetup paths{};
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);

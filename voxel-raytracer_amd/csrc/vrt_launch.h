@@ -70,22 +70,26 @@ hipError_t denoise_hdr(const DenoiseHdr &d, bool whole_groups, hipStream_t s);
 hipError_t cast_rays(const KArgs &a, const query::RayArgs &q, hipStream_t s);
 hipError_t find_voxels(const KArgs &a, const query::PointArgs &q, hipStream_t s);
 
+// The family of path tracer kernels a VRT_MODE_FULL sample launch takes (vrt_common.hip.h: the traversal itself, or its DeepPaths,
+// SunPaths, EmitPaths, EmitPowerPaths or EmitMisPaths wrapper; each family honours what the ones before it do), and the argument
+// block of the last one, which holds every other family's: EmitMis{EmitPower{Emit{Sun, list, n}, cdf}, inv_power}. A kernel is handed
+// its own family's slice. select_paths() (vrt_scene.cpp) derives both from the settings a caller read (vrt_internal.h PathSetup).
+enum class PathFamily { kPlain, kDeep, kSun, kEmit, kEmitPower, kEmitMis };
+using PathArgs = EmitMis;
+// `fam` and `pa` for a launch of `mode` whose light direction is light_dir. An empty list gives the launches of sampling off, the
+// mode VRT_EMIT_POWER counts only with sampling, MIS only with that mode, a sun of radius 0 makes no block, the primary modes read
+// none of it. false: emitter sampling on an opaque route (`opaque`), which has no such kernels.
+bool select_paths(int mode, const vrt_internal::PathSetup &p, const float light_dir[3], bool opaque, PathFamily &fam, PathArgs &pa);
+
 // vrt_launch_accum.hip: the progressive accumulation (vrt_accum.hip.h), whole frames, one 8 x 8 tile per wave. One launch per
 // shape, for the ray source `src` (l: the lens of Source::kLens, read for that source only) and, with `adaptive`, the kernels'
-// adaptive forms, which read all of q; the others read its Args part. hipErrorInvalidValue: no kernel of that shape.
+// adaptive forms, which read all of q; the others read its Args part. `q` is filled for either object, `hdr` picks it (the plain
+// functions take q's AdaptArgs part). hipErrorInvalidValue: no kernel of that shape.
 // accum_primary: q.n samples of `mode` (0 or 1) from the jitter or lens source, `v` as the dispatcher normalises it for an
-// accumulation (v4 64/7, v3 64/6, v2 or v1 256/1). accum_opaque: q.n samples of the opaque full path tracer from the jitter or
-// lens source (v4, 64 lanes). accum_full: one sample (q.first) of the general full path tracer in the traversal and workgroup
-// shape of `v` (grid = tiles / waves per workgroup); adaptive, it traces the tiles adaptive_tiles listed before it.
-// accum_bounce: q.n samples of the diffuse bounce over pass 1's seeds in a.defer_rec (grid = tiles). accum_repeat: n frames'
-// bytes. adaptive_resolve: by each pixel's own count. adaptive_counts: vrt_accum_counts.
+// accumulation (v4 64/7, v3 64/6, v2 or v1 256/1). accum_repeat: n frames' bytes. adaptive_resolve: by each pixel's own count.
+// adaptive_counts: vrt_accum_counts.
 hipError_t accum_primary(int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q,
                          bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
-                        int grid, hipStream_t s);
-hipError_t accum_full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                      const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, int grid, hipStream_t s);
 hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s);
 hipError_t accum_repeat(const accum::RepeatAdapt &q, hipStream_t s);
 hipError_t accum_resolve(const accum::Resolve &q, hipStream_t s);
@@ -99,157 +103,58 @@ hipError_t adaptive_counts(const accum::Counts &c, hipStream_t s);
 // float mean and its tone-mapped bytes.
 hipError_t accum_primary_hdr(int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
                              bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_opaque_hdr(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
-                            int grid, hipStream_t s);
-hipError_t accum_full_hdr(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                          const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_bounce_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s);
 hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::Repeat> &q, hipStream_t s);
 hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::RepeatAdapt> &q, hipStream_t s);
 hipError_t accum_frame_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
 hipError_t accum_pass1_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
 hipError_t accum_resolve_hdr(const accum::HdrResolve &q, hipStream_t s);
-// One call per shape of a sample launch: `q` filled for either object, `hdr` picks it (the plain functions take q's AdaptArgs part)
 inline hipError_t accum_primary(bool hdr, int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
                                 const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
     return hdr ? accum_primary_hdr(mode, src, v, a, vs, q, adaptive, l, grid, s) : accum_primary(mode, src, v, a, vs, q, adaptive, l, grid, s);
 }
-inline hipError_t accum_opaque(bool hdr, accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                               const accum::Lens &l, int grid, hipStream_t s) {
-    return hdr ? accum_opaque_hdr(src, a, vs, q, adaptive, l, grid, s) : accum_opaque(src, a, vs, q, adaptive, l, grid, s);
-}
-inline hipError_t accum_full(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
-                             bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
-    return hdr ? accum_full_hdr(src, v, a, vs, q, adaptive, l, grid, s) : accum_full(src, v, a, vs, q, adaptive, l, grid, s);
-}
-inline hipError_t accum_bounce(bool hdr, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s) {
-    return hdr ? accum_bounce_hdr(a, vs, q, adaptive, grid, s) : accum_bounce(a, vs, q, adaptive, grid, s);
-}
 
-// vrt_launch_accum_deep.hip, vrt_launch_accum_hdr_deep.hip: the sample launches of VRT_MODE_FULL at a path depth above 1 (include/vrt.h
-// vrt_set_path_depth): the same shapes and arguments, kernels that read a.path_depth. accum_full_deep takes any variant and launches
-// v4 for the wide traversals, v1 for the record-array ones (same workgroup shape, same bytes).
-hipError_t accum_opaque_deep(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
-                             int grid, hipStream_t s);
-hipError_t accum_full_deep(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                           const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_bounce_deep(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, int grid, hipStream_t s);
-hipError_t accum_opaque_hdr_deep(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
-                                 int grid, hipStream_t s);
-hipError_t accum_full_hdr_deep(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                               const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_bounce_hdr_deep(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s);
-inline hipError_t accum_opaque_deep(bool hdr, accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                                    const accum::Lens &l, int grid, hipStream_t s) {
-    return hdr ? accum_opaque_hdr_deep(src, a, vs, q, adaptive, l, grid, s) : accum_opaque_deep(src, a, vs, q, adaptive, l, grid, s);
-}
-inline hipError_t accum_full_deep(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
-                                  bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
-    return hdr ? accum_full_hdr_deep(src, v, a, vs, q, adaptive, l, grid, s) : accum_full_deep(src, v, a, vs, q, adaptive, l, grid, s);
-}
-inline hipError_t accum_bounce_deep(bool hdr, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s) {
-    return hdr ? accum_bounce_hdr_deep(a, vs, q, adaptive, grid, s) : accum_bounce_deep(a, vs, q, adaptive, grid, s);
-}
+// The sample launches of VRT_MODE_FULL over the family F (vrt_launch_accum.hip.h), one explicit instantiation per object:
+// vrt_launch_accum.hip and vrt_launch_accum_hdr.hip hold the plain family's, vrt_launch_accum{,_hdr}_{deep,sun,emit,emitp,emitm}.hip
+// one other family's each. opaque: q.n samples of the opaque full path tracer from the jitter or lens source (v4, 64 lanes). full:
+// one sample (q.first) of the general full path tracer in the traversal and workgroup shape of `v` (grid = tiles / waves per
+// workgroup) -- every family but the plain one takes any variant and launches v4 for the wide traversals, v1 for the record-array
+// ones (same workgroup shape, same bytes); adaptive, it traces the tiles adaptive_tiles listed before it. bounce: q.n samples of the
+// diffuse bounce over pass 1's seeds in a.defer_rec (grid = tiles). The emitter families have `full` only.
+template <bool HDR, PathFamily F>
+struct AccumPaths {
+    static hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
+                             const PathArgs &pa, int grid, hipStream_t s);
+    static hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                           const accum::Lens &l, const PathArgs &pa, int grid, hipStream_t s);
+    static hipError_t bounce(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const PathArgs &pa, int grid, hipStream_t s);
+};
+// ... and the one switch from the family as a value to those instantiations (vrt_scene.cpp, which sees none of the kernels): `q`
+// filled for either object, `hdr` picks it
+hipError_t accum_opaque(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const KArgs &a, const ViewSet &vs,
+                        const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_full(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
+                      const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_bounce(bool hdr, PathFamily fam, const PathArgs &pa, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                        bool adaptive, int grid, hipStream_t s);
 
-// vrt_launch_accum_sun.hip, vrt_launch_accum_hdr_sun.hip: the same launches with a sun disc (include/vrt.h vrt_set_sun_disc), at any
-// path depth: kernels over SunPaths<...>, which take `sun` (vrt_sun.h sun_block()) as their last argument
-hipError_t accum_opaque_sun(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
-                            const Sun &sun, int grid, hipStream_t s);
-hipError_t accum_full_sun(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                          const accum::Lens &l, const Sun &sun, int grid, hipStream_t s);
-hipError_t accum_bounce_sun(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const Sun &sun, int grid, hipStream_t s);
-hipError_t accum_opaque_hdr_sun(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
-                                const Sun &sun, int grid, hipStream_t s);
-hipError_t accum_full_hdr_sun(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                              const accum::Lens &l, const Sun &sun, int grid, hipStream_t s);
-hipError_t accum_bounce_hdr_sun(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const Sun &sun, int grid, hipStream_t s);
-inline hipError_t accum_opaque_sun(bool hdr, accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                                   const accum::Lens &l, const Sun &sun, int grid, hipStream_t s) {
-    return hdr ? accum_opaque_hdr_sun(src, a, vs, q, adaptive, l, sun, grid, s) : accum_opaque_sun(src, a, vs, q, adaptive, l, sun, grid, s);
-}
-inline hipError_t accum_full_sun(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
-                                 bool adaptive, const accum::Lens &l, const Sun &sun, int grid, hipStream_t s) {
-    return hdr ? accum_full_hdr_sun(src, v, a, vs, q, adaptive, l, sun, grid, s) : accum_full_sun(src, v, a, vs, q, adaptive, l, sun, grid, s);
-}
-inline hipError_t accum_bounce_sun(bool hdr, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const Sun &sun, int grid,
-                                   hipStream_t s) {
-    return hdr ? accum_bounce_hdr_sun(a, vs, q, adaptive, sun, grid, s) : accum_bounce_sun(a, vs, q, adaptive, sun, grid, s);
-}
-
-// vrt_launch_accum_emit.hip, vrt_launch_accum_hdr_emit.hip: one sample of the general full path tracer with emitter sampling
-// (include/vrt.h vrt_set_emitter_sampling), at any path depth and sun radius: kernels over EmitPaths<...>, which take `em` -- the
-// context's emitter list and the launch's Sun -- as their last argument. The opaque routes have no such form.
-hipError_t accum_full_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                           const accum::Lens &l, const Emit &em, int grid, hipStream_t s);
-hipError_t accum_full_hdr_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                               const accum::Lens &l, const Emit &em, int grid, hipStream_t s);
-inline hipError_t accum_full_emit(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
-                                  bool adaptive, const accum::Lens &l, const Emit &em, int grid, hipStream_t s) {
-    return hdr ? accum_full_hdr_emit(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emit(src, v, a, vs, q, adaptive, l, em, grid, s);
-}
-
-// vrt_launch_accum_emitp.hip, vrt_launch_accum_hdr_emitp.hip: the same with VRT_EMIT_POWER (include/vrt.h vrt_set_emitter_importance):
-// kernels over EmitPowerPaths<...>, which take `em` -- the Emit and the list's table of thresholds -- as their last argument
-hipError_t accum_full_emitp(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                            const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s);
-hipError_t accum_full_hdr_emitp(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                                const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s);
-inline hipError_t accum_full_emitp(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
-                                   bool adaptive, const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s) {
-    return hdr ? accum_full_hdr_emitp(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emitp(src, v, a, vs, q, adaptive, l, em, grid, s);
-}
-
-// vrt_launch_accum_emitm.hip, vrt_launch_accum_hdr_emitm.hip: the same with vrt_set_emitter_mis on top of VRT_EMIT_POWER (include/vrt.h):
-// kernels over EmitMisPaths<...>, which take `em` -- the EmitPower and 1 / Wtot -- as their last argument
-hipError_t accum_full_emitm(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                            const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s);
-hipError_t accum_full_hdr_emitm(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                                const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s);
-inline hipError_t accum_full_emitm(bool hdr, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
-                                   bool adaptive, const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s) {
-    return hdr ? accum_full_hdr_emitm(src, v, a, vs, q, adaptive, l, em, grid, s) : accum_full_emitm(src, v, a, vs, q, adaptive, l, em, grid, s);
-}
-
-// vrt_launch_rays.hip: pathTrace of `mode` for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the mapping
-// rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel here
-// starts a ray in any medium. VRT_MODE_FULL loops q.n_samples samples in the lane. ev0 / ev1 as for trace_primary.
+// vrt_launch_rays.hip: pathTrace of `mode` (0 or 1) for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the
+// mapping rays::plan() chose (grid = its waves); `v`: the dispatcher's variant, of which only the traversal is taken -- every kernel
+// here starts a ray in any medium. ev0 / ev1 as for trace_primary.
 hipError_t shade_rays(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s,
                       hipEvent_t ev0, hipEvent_t ev1);
-// vrt_launch_rays_hdr.hip: the same kernels' HDR forms (include/vrt.h vrt_shade_rays_hdr): q.n_samples is the call's own in every
-// mode, q.out_rgba takes the tone-mapped bytes of the mean
+// vrt_launch_rays_hdr.hip: the same kernels' HDR forms (include/vrt.h vrt_shade_rays_hdr): q.n_samples is the call's own,
+// q.out_rgba takes the tone-mapped bytes of the mean
 hipError_t shade_rays_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, uint32_t grid, hipStream_t s,
                           hipEvent_t ev0, hipEvent_t ev1);
-
-// vrt_launch_rays_deep.hip, vrt_launch_rays_hdr_deep.hip: VRT_MODE_FULL of the two above at a path depth above 1 (kernels that read
-// a.path_depth; v4 for the wide variants, v1 for the record-array ones)
-hipError_t shade_rays_deep(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s, hipEvent_t ev0,
-                           hipEvent_t ev1);
-hipError_t shade_rays_hdr_deep(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, uint32_t grid, hipStream_t s,
-                               hipEvent_t ev0, hipEvent_t ev1);
-
-// vrt_launch_rays_sun.hip, vrt_launch_rays_hdr_sun.hip: VRT_MODE_FULL of the same with a sun disc, at any path depth
-hipError_t shade_rays_sun(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const Sun &sun, uint32_t grid, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1);
-hipError_t shade_rays_hdr_sun(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Sun &sun, uint32_t grid,
-                              hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-
-// vrt_launch_rays_emit.hip, vrt_launch_rays_hdr_emit.hip: VRT_MODE_FULL of the same with emitter sampling, at any path depth and sun radius
-hipError_t shade_rays_emit(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const Emit &em, uint32_t grid, hipStream_t s,
-                           hipEvent_t ev0, hipEvent_t ev1);
-hipError_t shade_rays_hdr_emit(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Emit &em, uint32_t grid,
-                               hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-
-// vrt_launch_rays_emitp.hip, vrt_launch_rays_hdr_emitp.hip: ... and with VRT_EMIT_POWER (vrt_set_emitter_importance)
-hipError_t shade_rays_emitp(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const EmitPower &em, uint32_t grid, hipStream_t s,
-                            hipEvent_t ev0, hipEvent_t ev1);
-hipError_t shade_rays_hdr_emitp(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const EmitPower &em, uint32_t grid,
-                                hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-
-// vrt_launch_rays_emitm.hip, vrt_launch_rays_hdr_emitm.hip: ... and with vrt_set_emitter_mis on top of VRT_EMIT_POWER
-hipError_t shade_rays_emitm(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, const EmitMis &em, uint32_t grid, hipStream_t s,
-                            hipEvent_t ev0, hipEvent_t ev1);
-hipError_t shade_rays_hdr_emitm(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const EmitMis &em, uint32_t grid,
-                                hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// VRT_MODE_FULL of the two over the family F (vrt_launch_rays_paths.hip.h), q.n_samples samples looped in the lane; one explicit
+// instantiation per object, vrt_launch_rays{,_hdr}{,_deep,_sun,_emit,_emitp,_emitm}.hip. The plain forms take q's Args part.
+template <bool HDR, PathFamily F>
+struct RayPaths {
+    static hipError_t full(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const PathArgs &pa, uint32_t grid,
+                           hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+};
+hipError_t shade_rays_full(bool hdr, PathFamily fam, const PathArgs &pa, const Variant &v, const KArgs &a, const ViewSet &vs,
+                           const rays::HdrArgs &q, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 
 }  // namespace launch
 }  // namespace vrt

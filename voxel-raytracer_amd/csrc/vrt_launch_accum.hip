@@ -13,19 +13,8 @@ hipError_t accum_primary(int mode, accum::Source src, const Variant &v, const KA
     return accum_impl::primary<false>(mode, src, v, a, vs, q, adaptive, l, grid, s);
 }
 
-hipError_t accum_opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, const accum::Lens &l,
-                        int grid, hipStream_t s) {
-    return accum_impl::opaque<false>(src, a, vs, q, adaptive, l, grid, s);
-}
-
-hipError_t accum_full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive,
-                      const accum::Lens &l, int grid, hipStream_t s) {
-    return accum_impl::full<false>(src, v, a, vs, q, adaptive, l, grid, s);
-}
-
-hipError_t accum_bounce(const KArgs &a, const ViewSet &vs, const accum::AdaptArgs &q, bool adaptive, int grid, hipStream_t s) {
-    return accum_impl::bounce<false>(a, vs, q, adaptive, grid, s);
-}
+// the sample launches of VRT_MODE_FULL, the plain family's (the other families: objects of their own)
+template struct AccumPaths<false, PathFamily::kPlain>;
 
 hipError_t accum_repeat(const accum::Repeat &q, hipStream_t s) {
     if (q.pixels == 0u) return hipSuccess;

@@ -1,8 +1,9 @@
 // vrt_launch_accum.hip.h -- the launch functions of the progressive accumulation's sample kernels (vrt_accum.hip.h), templated on
-// HDR: vrt_launch_accum.hip instantiates the plain forms, vrt_launch_accum_hdr.hip those of HDR accumulations (two objects, so
-// that `make -j` compiles them side by side). One function per shape -- the primary modes and the opaque chain looped in the
-// lanes, one sample of the general full path tracer, the bounce over pass 1's seeds, the repeat of a frame -- each for the ray
-// source and the adaptive form asked for.
+// HDR and, for VRT_MODE_FULL, on the family of path tracer kernels (vrt_launch.h PathFamily): vrt_launch_accum.hip instantiates the
+// plain forms, vrt_launch_accum_hdr.hip those of HDR accumulations, vrt_launch_accum{,_hdr}_{deep,sun,emit,emitp,emitm}.hip one
+// family's each (objects of their own, so that `make -j` compiles them side by side). One function per shape -- the primary modes
+// and the opaque chain looped in the lanes, one sample of the general full path tracer, the bounce over pass 1's seeds, the repeat
+// of a frame -- each for the ray source and the adaptive form asked for.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,24 @@
 
 namespace vrt {
 namespace launch {
+// A family's wrapper of the traversal T (vrt_common.hip.h): the plain family launches the kernels over T itself
+template <PathFamily F, class T> struct PathsOf { using type = T; };
+template <class T> struct PathsOf<PathFamily::kDeep, T> { using type = DeepPaths<T>; };
+template <class T> struct PathsOf<PathFamily::kSun, T> { using type = SunPaths<T>; };
+template <class T> struct PathsOf<PathFamily::kEmit, T> { using type = EmitPaths<T>; };
+template <class T> struct PathsOf<PathFamily::kEmitPower, T> { using type = EmitPowerPaths<T>; };
+template <class T> struct PathsOf<PathFamily::kEmitMis, T> { using type = EmitMisPaths<T>; };
+template <PathFamily F, class T> using Paths = typename PathsOf<F, T>::type;
+// ... and its slice of the PathArgs, the kernels' last argument (Paths<F, T>::Arg): f(slice), or f() for the families that take none
+template <PathFamily F, class FN>
+hipError_t with_arg(const PathArgs &pa, FN &&f) {
+    if constexpr (F == PathFamily::kEmitMis) return f(pa);
+    else if constexpr (F == PathFamily::kEmitPower) return f(pa.power);
+    else if constexpr (F == PathFamily::kEmit) return f(pa.power.emit);
+    else if constexpr (F == PathFamily::kSun) return f(pa.power.emit.sun);
+    else return f();
+}
+
 namespace accum_impl {
 
 template <class K, class... P>
@@ -34,21 +53,20 @@ template <class TRAV, int BLOCK, int WPE, class F>
 hipError_t shape(bool adaptive, F &&f) {
     return adaptive ? f(Shape<TRAV, BLOCK, WPE, true>{}) : f(Shape<TRAV, BLOCK, WPE, false>{});
 }
-// DEEP (the objects vrt_launch_accum_deep.hip, vrt_launch_accum_hdr_deep.hip): the kernels that honour KArgs::path_depth
-// SUN (vrt_launch_accum_sun.hip, vrt_launch_accum_hdr_sun.hip): those that also honour the sun disc, at every depth; their last
-// argument is the Sun (`sun...`, one or none)
-template <bool DEEP, class T, bool SUN = false>
-using Path = typename std::conditional<SUN, SunPaths<T>, typename std::conditional<DEEP, DeepPaths<T>, T>::type>::type;
-template <bool SUN, class PLAIN, class WITH_SUN>
-using Src = typename std::conditional<SUN, WITH_SUN, PLAIN>::type;
-// the general full path tracer: the shapes trace_full() launches trace_kernel<2> in. DEEP: every variant gives the same bytes, so a
-// launch is normalised to one of two instantiated traversals of its workgroup shape -- v4 for the wide ones, v1 (right for any
-// tree) for the record-array ones
-template <bool DEEP = false, bool SUN = false, class F>
-hipError_t full_shapes(const Variant &v, bool adaptive, F &&f) {
-    if constexpr (DEEP) {
-        if (v.trav >= 3) return shape<Path<true, v4::TravAny, SUN>, 64, 5>(adaptive, f);
-        if (v.trav >= 1) return shape<Path<true, v1::Trav, SUN>, 256, 1>(adaptive, f);
+// ... and a kernel's ray source: the plain one, or with an argument A the one that carries it too
+template <class PLAIN, template <class> class WITH, class... A> struct SrcOf { using type = PLAIN; };
+template <class PLAIN, template <class> class WITH, class A> struct SrcOf<PLAIN, WITH, A> { using type = WITH<A>; };
+template <class... A> using CornerSrc = typename SrcOf<accum::CornerSource, accum::ArgCornerSource, A...>::type;
+template <class... A> using JitterSrc = typename SrcOf<accum::JitterSource, accum::ArgJitterSource, A...>::type;
+template <class... A> using LensSrc = typename SrcOf<accum::LensSource, accum::ArgLensSource, A...>::type;
+// the general full path tracer: the shapes trace_full() launches trace_kernel<2> in. Every family but the plain one gives the same
+// bytes in every variant, so a launch is normalised to one of two instantiated traversals of its workgroup shape -- v4 for the wide
+// ones, v1 (right for any tree) for the record-array ones
+template <PathFamily F, class FN>
+hipError_t full_shapes(const Variant &v, bool adaptive, FN &&f) {
+    if constexpr (F != PathFamily::kPlain) {
+        if (v.trav >= 3) return shape<Paths<F, v4::TravAny>, 64, 5>(adaptive, f);
+        if (v.trav >= 1) return shape<Paths<F, v1::Trav>, 256, 1>(adaptive, f);
         return hipErrorInvalidValue;
     } else {
         if (v.trav == 4) return shape<v4::TravAny, 64, 5>(adaptive, f);
@@ -102,102 +120,59 @@ hipError_t primary(int mode, accum::Source src, const Variant &v, const KArgs &a
     });
 }
 
-template <bool HDR, bool DEEP = false, class... SUN>
+// The three sample launches of VRT_MODE_FULL over the family F, `arg` its argument (one, or none). The emitter families exist for
+// the general path tracer only: the opaque routes have no such kernels.
+template <bool HDR, PathFamily F, class... ARG>
 hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, const accum::Lens &l, int grid,
-                  hipStream_t s, const SUN &...sun) {
-    constexpr bool kSun = sizeof...(SUN) != 0;
-    return shape<Path<DEEP, v4::Trav, kSun>, 64, DEEP ? accum::kDeepOpaqueWpe : 6>(adaptive, [&](auto sh) {
+                  hipStream_t s, const ARG &...arg) {
+    if constexpr (F >= PathFamily::kEmit) return hipErrorInvalidValue;
+    else return shape<Paths<F, v4::Trav>, 64, F == PathFamily::kPlain ? 6 : accum::kDeepOpaqueWpe>(adaptive, [&](auto sh) {
         using S = decltype(sh);
         const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
-        if (src == accum::Source::kJitter) return go(accum::opaque_accum_kernel<Src<kSun, accum::JitterSource, accum::SunJitterSource>, typename S::Trav, S::kWpe, S::kAdapt, HDR, SUN...>, grid, 64, s, a, vs, qs, sun...);
-        if (src == accum::Source::kLens) return go(accum::opaque_accum_kernel<Src<kSun, accum::LensSource, accum::SunLensSource>, typename S::Trav, S::kWpe, S::kAdapt, HDR, accum::Lens, SUN...>, grid, 64, s, a, vs, qs, l, sun...);
+        if (src == accum::Source::kJitter) return go(accum::opaque_accum_kernel<JitterSrc<ARG...>, typename S::Trav, S::kWpe, S::kAdapt, HDR, ARG...>, grid, 64, s, a, vs, qs, arg...);
+        if (src == accum::Source::kLens) return go(accum::opaque_accum_kernel<LensSrc<ARG...>, typename S::Trav, S::kWpe, S::kAdapt, HDR, accum::Lens, ARG...>, grid, 64, s, a, vs, qs, l, arg...);
         return hipErrorInvalidValue;   // the corner's: pass 1 once, then accum_bounce
     });
 }
 
-template <bool HDR, bool DEEP = false, class... SUN>
+template <bool HDR, PathFamily F, class... ARG>
 hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
-                const accum::Lens &l, int grid, hipStream_t s, const SUN &...sun) {
-    constexpr bool kSun = sizeof...(SUN) != 0;
-    return full_shapes<DEEP, kSun>(v, adaptive, [&](auto sh) {
+                const accum::Lens &l, int grid, hipStream_t s, const ARG &...arg) {
+    return full_shapes<F>(v, adaptive, [&](auto sh) {
         using S = decltype(sh);
         const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
         if (src == accum::Source::kCorner)
-            return go(accum::full_accum_kernel<Src<kSun, accum::CornerSource, accum::SunCornerSource>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, SUN...>, grid, S::kBlock, s, a, vs, qs, sun...);
+            return go(accum::full_accum_kernel<CornerSrc<ARG...>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, ARG...>, grid, S::kBlock, s, a, vs, qs, arg...);
         if (src == accum::Source::kJitter)
-            return go(accum::full_accum_kernel<Src<kSun, accum::JitterSource, accum::SunJitterSource>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, SUN...>, grid, S::kBlock, s, a, vs, qs, sun...);
-        return go(accum::full_accum_kernel<Src<kSun, accum::LensSource, accum::SunLensSource>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, SUN...>, grid, S::kBlock, s, a, vs, qs, l, sun...);
+            return go(accum::full_accum_kernel<JitterSrc<ARG...>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, ARG...>, grid, S::kBlock, s, a, vs, qs, arg...);
+        return go(accum::full_accum_kernel<LensSrc<ARG...>, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, ARG...>, grid, S::kBlock, s, a, vs, qs, l, arg...);
     });
 }
 
-// EMIT (vrt_launch_accum_emit.hip, vrt_launch_accum_hdr_emit.hip): the general full path tracer over EmitPaths<...>, in the two
-// normalised traversals of the DEEP forms; the kernels' last argument is the Emit
-template <bool HDR>
-hipError_t full_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
-                     const accum::Lens &l, const Emit &em, int grid, hipStream_t s) {
-    const auto f = [&](auto sh) {
-        using S = decltype(sh);
-        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
-        if (src == accum::Source::kCorner)
-            return go(accum::full_accum_kernel<accum::EmitCornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, Emit>, grid, S::kBlock, s, a, vs, qs, em);
-        if (src == accum::Source::kJitter)
-            return go(accum::full_accum_kernel<accum::EmitJitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, Emit>, grid, S::kBlock, s, a, vs, qs, em);
-        return go(accum::full_accum_kernel<accum::EmitLensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, Emit>, grid, S::kBlock, s, a, vs, qs, l, em);
-    };
-    if (v.trav >= 3) return shape<EmitPaths<v4::TravAny>, 64, 5>(adaptive, f);
-    if (v.trav >= 1) return shape<EmitPaths<v1::Trav>, 256, 1>(adaptive, f);
-    return hipErrorInvalidValue;
-}
-
-// EMIT POWER (vrt_launch_accum_emitp.hip, vrt_launch_accum_hdr_emitp.hip): the same over EmitPowerPaths<...> (include/vrt.h
-// vrt_set_emitter_importance, VRT_EMIT_POWER); the kernels' last argument is the EmitPower
-template <bool HDR>
-hipError_t full_emit_power(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
-                           const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s) {
-    const auto f = [&](auto sh) {
-        using S = decltype(sh);
-        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
-        if (src == accum::Source::kCorner)
-            return go(accum::full_accum_kernel<accum::EmitPowerCornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitPower>, grid, S::kBlock, s, a, vs, qs, em);
-        if (src == accum::Source::kJitter)
-            return go(accum::full_accum_kernel<accum::EmitPowerJitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitPower>, grid, S::kBlock, s, a, vs, qs, em);
-        return go(accum::full_accum_kernel<accum::EmitPowerLensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, EmitPower>, grid, S::kBlock, s, a, vs, qs, l, em);
-    };
-    if (v.trav >= 3) return shape<EmitPowerPaths<v4::TravAny>, 64, 5>(adaptive, f);
-    if (v.trav >= 1) return shape<EmitPowerPaths<v1::Trav>, 256, 1>(adaptive, f);
-    return hipErrorInvalidValue;
-}
-
-// EMIT MIS (vrt_launch_accum_emitm.hip, vrt_launch_accum_hdr_emitm.hip): the same over EmitMisPaths<...> (include/vrt.h
-// vrt_set_emitter_mis); the kernels' last argument is the EmitMis
-template <bool HDR>
-hipError_t full_emit_mis(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive,
-                         const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s) {
-    const auto f = [&](auto sh) {
-        using S = decltype(sh);
-        const accum::ArgsOf<S::kAdapt, HDR> qs = slice<S::kAdapt, HDR>(q);
-        if (src == accum::Source::kCorner)
-            return go(accum::full_accum_kernel<accum::EmitMisCornerSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitMis>, grid, S::kBlock, s, a, vs, qs, em);
-        if (src == accum::Source::kJitter)
-            return go(accum::full_accum_kernel<accum::EmitMisJitterSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, EmitMis>, grid, S::kBlock, s, a, vs, qs, em);
-        return go(accum::full_accum_kernel<accum::EmitMisLensSource, typename S::Trav, S::kBlock, S::kWpe, S::kAdapt, HDR, accum::Lens, EmitMis>, grid, S::kBlock, s, a, vs, qs, l, em);
-    };
-    if (v.trav >= 3) return shape<EmitMisPaths<v4::TravAny>, 64, 5>(adaptive, f);
-    if (v.trav >= 1) return shape<EmitMisPaths<v1::Trav>, 256, 1>(adaptive, f);
-    return hipErrorInvalidValue;
-}
-
-template <bool HDR, bool DEEP = false, class... SUN>
-hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s, const SUN &...sun) {
-    if constexpr (sizeof...(SUN) != 0) {
-        if (adaptive) return go(accum::bounce_accum_sun_kernel<SunPaths<v4::TravAny>, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q), sun...);
-        return go(accum::bounce_accum_sun_kernel<SunPaths<v4::TravAny>, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q), sun...);
-    } else {
-        if (adaptive) return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, true, HDR>, grid, 64, s, a, vs, slice<true, HDR>(q));
-        return go(accum::bounce_accum_kernel<Path<DEEP, v4::TravAny>, false, HDR>, grid, 64, s, a, vs, slice<false, HDR>(q));
-    }
+template <bool HDR, PathFamily F, class... ARG>
+hipError_t bounce(const KArgs &a, const ViewSet &vs, const Filled<HDR> &q, bool adaptive, int grid, hipStream_t s, const ARG &...arg) {
+    if constexpr (F >= PathFamily::kEmit) return hipErrorInvalidValue;
+    else if (adaptive) return go(accum::bounce_accum_kernel<Paths<F, v4::TravAny>, true, HDR, ARG...>, grid, 64, s, a, vs, slice<true, HDR>(q), arg...);
+    else return go(accum::bounce_accum_kernel<Paths<F, v4::TravAny>, false, HDR, ARG...>, grid, 64, s, a, vs, slice<false, HDR>(q), arg...);
 }
 
 }  // namespace accum_impl
+
+// vrt_launch.h AccumPaths: each object instantiates its own (`template struct AccumPaths<HDR, F>;`) and so holds that family's kernels
+template <bool HDR, PathFamily F>
+hipError_t AccumPaths<HDR, F>::opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                                      const accum::Lens &l, const PathArgs &pa, int grid, hipStream_t s) {
+    return with_arg<F>(pa, [&](const auto &...arg) { return accum_impl::opaque<HDR, F>(src, a, vs, q, adaptive, l, grid, s, arg...); });
+}
+template <bool HDR, PathFamily F>
+hipError_t AccumPaths<HDR, F>::full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+                                    const accum::Lens &l, const PathArgs &pa, int grid, hipStream_t s) {
+    return with_arg<F>(pa, [&](const auto &...arg) { return accum_impl::full<HDR, F>(src, v, a, vs, q, adaptive, l, grid, s, arg...); });
+}
+template <bool HDR, PathFamily F>
+hipError_t AccumPaths<HDR, F>::bounce(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const PathArgs &pa, int grid,
+                                      hipStream_t s) {
+    return with_arg<F>(pa, [&](const auto &...arg) { return accum_impl::bounce<HDR, F>(a, vs, q, adaptive, grid, s, arg...); });
+}
 }  // namespace launch
 }  // namespace vrt

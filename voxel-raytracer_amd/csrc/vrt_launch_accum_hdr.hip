@@ -12,19 +12,8 @@ hipError_t accum_primary_hdr(int mode, accum::Source src, const Variant &v, cons
     return accum_impl::primary<true>(mode, src, v, a, vs, q, adaptive, l, grid, s);
 }
 
-hipError_t accum_opaque_hdr(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
-                            int grid, hipStream_t s) {
-    return accum_impl::opaque<true>(src, a, vs, q, adaptive, l, grid, s);
-}
-
-hipError_t accum_full_hdr(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                          const accum::Lens &l, int grid, hipStream_t s) {
-    return accum_impl::full<true>(src, v, a, vs, q, adaptive, l, grid, s);
-}
-
-hipError_t accum_bounce_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s) {
-    return accum_impl::bounce<true>(a, vs, q, adaptive, grid, s);
-}
+// the sample launches of VRT_MODE_FULL, the plain family's (the other families: objects of their own)
+template struct AccumPaths<true, PathFamily::kPlain>;
 
 hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::Repeat> &q, hipStream_t s) {
     if (q.pixels == 0u) return hipSuccess;

@@ -1,23 +1,5 @@
-// vrt_launch_accum_hdr_deep.hip -- vrt_launch_accum_deep.hip's kernels for HDR accumulations (include/vrt.h vrt_accum_keep_hdr):
-// the sample kernels over DeepPaths<...> with HDR = true, an object of their own.
+// vrt_launch_accum_hdr_deep.hip -- the accumulation's VRT_MODE_FULL kernels over DeepPaths<...> (include/vrt.h vrt_set_path_depth),
+// HDR forms, in an object of their own: vrt_launch_accum.hip.h
 #include "vrt_launch_accum.hip.h"
 
-namespace vrt {
-namespace launch {
-
-hipError_t accum_opaque_hdr_deep(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
-                                 int grid, hipStream_t s) {
-    return accum_impl::opaque<true, true>(src, a, vs, q, adaptive, l, grid, s);
-}
-
-hipError_t accum_full_hdr_deep(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                               const accum::Lens &l, int grid, hipStream_t s) {
-    return accum_impl::full<true, true>(src, v, a, vs, q, adaptive, l, grid, s);
-}
-
-hipError_t accum_bounce_hdr_deep(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, int grid, hipStream_t s) {
-    return accum_impl::bounce<true, true>(a, vs, q, adaptive, grid, s);
-}
-
-}  // namespace launch
-}  // namespace vrt
+template struct vrt::launch::AccumPaths<true, vrt::launch::PathFamily::kDeep>;

@@ -1,14 +1,5 @@
-// vrt_launch_accum_hdr_emit.hip -- vrt_launch_accum_emit.hip's kernels for HDR accumulations (include/vrt.h vrt_accum_keep_hdr):
-// full_accum_kernel over EmitPaths<...> with HDR = true, an object of their own.
+// vrt_launch_accum_hdr_emit.hip -- the accumulation's VRT_MODE_FULL kernels over EmitPaths<...> (include/vrt.h vrt_set_emitter_sampling),
+// HDR forms, in an object of their own: vrt_launch_accum.hip.h
 #include "vrt_launch_accum.hip.h"
 
-namespace vrt {
-namespace launch {
-
-hipError_t accum_full_hdr_emit(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                               const accum::Lens &l, const Emit &em, int grid, hipStream_t s) {
-    return accum_impl::full_emit<true>(src, v, a, vs, q, adaptive, l, em, grid, s);
-}
-
-}  // namespace launch
-}  // namespace vrt
+template struct vrt::launch::AccumPaths<true, vrt::launch::PathFamily::kEmit>;

@@ -1,14 +1,5 @@
-// vrt_launch_accum_hdr_emitm.hip -- vrt_launch_accum_emitm.hip's kernels for HDR accumulations (include/vrt.h vrt_accum_keep_hdr):
-// full_accum_kernel over EmitMisPaths<...> with HDR = true, an object of their own.
+// vrt_launch_accum_hdr_emitm.hip -- the accumulation's VRT_MODE_FULL kernels over EmitMisPaths<...> (include/vrt.h vrt_set_emitter_mis),
+// HDR forms, in an object of their own: vrt_launch_accum.hip.h
 #include "vrt_launch_accum.hip.h"
 
-namespace vrt {
-namespace launch {
-
-hipError_t accum_full_hdr_emitm(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                                const accum::Lens &l, const EmitMis &em, int grid, hipStream_t s) {
-    return accum_impl::full_emit_mis<true>(src, v, a, vs, q, adaptive, l, em, grid, s);
-}
-
-}  // namespace launch
-}  // namespace vrt
+template struct vrt::launch::AccumPaths<true, vrt::launch::PathFamily::kEmitMis>;

@@ -1,14 +1,5 @@
-// vrt_launch_accum_hdr_emitp.hip -- vrt_launch_accum_emitp.hip's kernels for HDR accumulations (include/vrt.h vrt_accum_keep_hdr):
-// full_accum_kernel over EmitPowerPaths<...> with HDR = true, an object of their own.
+// vrt_launch_accum_hdr_emitp.hip -- the accumulation's VRT_MODE_FULL kernels over EmitPowerPaths<...> (include/vrt.h vrt_set_emitter_importance),
+// HDR forms, in an object of their own: vrt_launch_accum.hip.h
 #include "vrt_launch_accum.hip.h"
 
-namespace vrt {
-namespace launch {
-
-hipError_t accum_full_hdr_emitp(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
-                                const accum::Lens &l, const EmitPower &em, int grid, hipStream_t s) {
-    return accum_impl::full_emit_power<true>(src, v, a, vs, q, adaptive, l, em, grid, s);
-}
-
-}  // namespace launch
-}  // namespace vrt
+template struct vrt::launch::AccumPaths<true, vrt::launch::PathFamily::kEmitPower>;

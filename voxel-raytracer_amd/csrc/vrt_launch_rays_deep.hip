@@ -1,41 +1,5 @@
-// vrt_launch_rays_deep.hip -- vrt_launch_rays.hip's VRT_MODE_FULL kernels at a path depth above 1 (include/vrt.h vrt_set_path_depth):
-// shade_rays_full_kernel over DeepPaths<...>, which reads KArgs::path_depth, in an object of its own. Every traversal gives the same
-// bytes, so a launch is normalised to one of two: v4's general loop for the wide variants, v1 (right for any tree) for the others.
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
+// vrt_launch_rays_deep.hip -- the ray batches' VRT_MODE_FULL kernel over DeepPaths<...> (include/vrt.h vrt_set_path_depth),
+// plain forms, in an object of its own: vrt_launch_rays_paths.hip.h
+#include "vrt_launch_rays_paths.hip.h"
 
-#include "vrt_launch.h"
-#include "vrt_kernels.hip.h"
-#include "vrt_kernels_v1.hip.h"
-#include "vrt_kernels_wide.hip.h"
-#include "vrt_kernels_v4.hip.h"
-#include "vrt_rays.hip.h"
-
-namespace vrt {
-namespace launch {
-
-namespace {
-hipError_t go(void (*kernel)(const KArgs, const ViewSet, const rays::Args), const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid,
-              hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (ev0 || ev1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, s, ev0, ev1, 0, a, vs, q);
-    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, s, a, vs, q);
-    return hipGetLastError();
-}
-
-template <bool LOOP>
-hipError_t full(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s, hipEvent_t ev0,
-                hipEvent_t ev1) {
-    if (v.trav >= 3) return go(rays::shade_rays_full_kernel<DeepPaths<v4::TravAny>, 5, LOOP>, a, vs, q, grid, s, ev0, ev1);
-    if (v.trav >= 1) return go(rays::shade_rays_full_kernel<DeepPaths<v1::Trav>, 1, LOOP>, a, vs, q, grid, s, ev0, ev1);
-    return hipErrorInvalidValue;
-}
-}  // namespace
-
-hipError_t shade_rays_deep(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::Args &q, uint32_t grid, hipStream_t s, hipEvent_t ev0,
-                hipEvent_t ev1) {
-    if (q.n == 0u) return hipSuccess;
-    return q.n_samples > 1u ? full<true>(v, a, vs, q, grid, s, ev0, ev1) : full<false>(v, a, vs, q, grid, s, ev0, ev1);
-}
-
-}  // namespace launch
-}  // namespace vrt
+template struct vrt::launch::RayPaths<false, vrt::launch::PathFamily::kDeep>;

@@ -1,42 +1,5 @@
-// vrt_launch_rays_hdr_emit.hip -- vrt_launch_rays_hdr.hip's VRT_MODE_FULL kernels with emitter sampling (include/vrt.h
-// vrt_set_emitter_sampling): shade_rays_full_emit_kernel over EmitPaths<...>, which takes the Emit (the emitter list and the Sun) as
-// its fourth argument and reads KArgs::path_depth (every depth 1..8, any sun radius), in an object of its own. v4's general loop
-// for the wide variants, v1 (right for any tree) for the others.
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
+// vrt_launch_rays_hdr_emit.hip -- the ray batches' VRT_MODE_FULL kernel over EmitPaths<...> (include/vrt.h vrt_set_emitter_sampling),
+// HDR forms, in an object of its own: vrt_launch_rays_paths.hip.h
+#include "vrt_launch_rays_paths.hip.h"
 
-#include "vrt_launch.h"
-#include "vrt_kernels.hip.h"
-#include "vrt_kernels_v1.hip.h"
-#include "vrt_kernels_wide.hip.h"
-#include "vrt_kernels_v4.hip.h"
-#include "vrt_rays.hip.h"
-
-namespace vrt {
-namespace launch {
-
-namespace {
-hipError_t go(void (*kernel)(const KArgs, const ViewSet, const rays::HdrArgs, const Emit), const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q,
-              const Emit &em, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    if (ev0 || ev1) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, s, ev0, ev1, 0, a, vs, q, em);
-    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, s, a, vs, q, em);
-    return hipGetLastError();
-}
-
-template <bool LOOP>
-hipError_t full(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Emit &em, uint32_t grid, hipStream_t s,
-                hipEvent_t ev0, hipEvent_t ev1) {
-    if (v.trav >= 3) return go(rays::shade_rays_full_emit_kernel<EmitPaths<v4::TravAny>, 5, LOOP, true>, a, vs, q, em, grid, s, ev0, ev1);
-    if (v.trav >= 1) return go(rays::shade_rays_full_emit_kernel<EmitPaths<v1::Trav>, 1, LOOP, true>, a, vs, q, em, grid, s, ev0, ev1);
-    return hipErrorInvalidValue;
-}
-}  // namespace
-
-hipError_t shade_rays_hdr_emit(const Variant &v, const KArgs &a, const ViewSet &vs, const rays::HdrArgs &q, const Emit &em, uint32_t grid, hipStream_t s,
-                          hipEvent_t ev0, hipEvent_t ev1) {
-    if (q.n == 0u) return hipSuccess;
-    return q.n_samples > 1u ? full<true>(v, a, vs, q, em, grid, s, ev0, ev1) : full<false>(v, a, vs, q, em, grid, s, ev0, ev1);
-}
-
-}  // namespace launch
-}  // namespace vrt
+template struct vrt::launch::RayPaths<true, vrt::launch::PathFamily::kEmit>;

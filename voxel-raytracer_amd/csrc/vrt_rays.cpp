@@ -74,27 +74,22 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     // the world is empty outside wide root 0: a property of the tree, applied by find() per ray (never to a first lookup); the
     // tighter root is a property of a view's eye and is not taken
     a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
-    const bool deep = mode == VRT_MODE_FULL && c->path_depth > 1;   // vrt_set_path_depth: the kernels that read a.path_depth
-    if (deep) a.path_depth = (uint32_t)c->path_depth;
-    const bool sun_on = mode == VRT_MODE_FULL && c->sun_disc > 0.0f;   // vrt_set_sun_disc: the kernels over SunPaths<...>, at every depth
-    if (sun_on) a.path_depth = (uint32_t)c->path_depth;
-    const vrt::Sun sun = sun_on ? sun_block(a.light_dir, c->sun_disc) : vrt::Sun{};
-    // vrt_set_emitter_sampling: the kernels over EmitPaths<...>, at every depth and sun radius; an empty list: the launches of sampling off
-    bool emit_on = false;
-    if (mode == VRT_MODE_FULL && c->emitter_sampling) {
+    // the kernels of VRT_MODE_FULL by the context's settings as this call finds them, the emitter list made for the current tree
+    PathSetup ps{c->path_depth, c->sun_disc, mode == VRT_MODE_FULL && c->emitter_sampling, c->emitter_importance, c->emitter_mis};
+    if (ps.sampling) {
         const int re = ensure_emitters(c, "vrt_shade_rays", true);
         if (re) return re;
-        emit_on = c->emitters.n > 0;
+        ps.list = c->emitters.d_list.get();
+        ps.n = (uint32_t)c->emitters.n;
+        ps.cdf = c->emitters.d_cdf.get();
+        ps.inv_power = emitter_inv_power(c->emitters.wtot);
     }
-    if (emit_on) a.path_depth = (uint32_t)c->path_depth;
-    vrt::Emit em{};
-    if (emit_on) em = vrt::Emit{sun, c->emitters.d_list.get(), (uint32_t)c->emitters.n};
-    const bool power = emit_on && c->emitter_importance == VRT_EMIT_POWER;   // vrt_set_emitter_importance: the kernels over EmitPowerPaths<...>
-    const vrt::EmitPower emp{em, power ? c->emitters.d_cdf.get() : nullptr};
-    const bool mis = power && c->emitter_mis;   // vrt_set_emitter_mis: the kernels over EmitMisPaths<...>
-    const vrt::EmitMis emm{emp, mis ? emitter_inv_power(c->emitters.wtot) : 0.0f};
+    vrt::launch::PathFamily fam;
+    vrt::launch::PathArgs pa;
+    vrt::launch::select_paths(mode, ps, a.light_dir, false, fam, pa);   // no opaque route here: nothing is refused
+    if (mode == VRT_MODE_FULL) a.path_depth = (uint32_t)c->path_depth;   // vrt_set_path_depth: every family but the plain one reads it
 
-    vrt::rays::Args q;
+    vrt::rays::HdrArgs q{};   // Args first in the layout (what late_rays(), vrt_rays.hip.h, relies on), then what the HDR forms add
     q.origins = d_origins;
     q.dirs = d_dirs;
     q.out_rgba = d_rgba;
@@ -103,34 +98,21 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     q.origin_stride = origin_stride;
     q.width = (uint32_t)width;
     q.first = first_sample;
-    q.n_samples = mode == VRT_MODE_FULL ? n_samples : 1u;   // the other modes draw no random number: every sample is the same
+    // the primary modes draw no random number, every sample is the same: the plain forms trace one, the HDR forms add it n_samples times over
+    q.n_samples = (mode == VRT_MODE_FULL || hdr) ? n_samples : 1u;
+    if (hdr) {
+        q.sums = hdr->d_sums;
+        q.out_rgb = hdr->d_rgb;
+        q.n_total = hdr->n_prior + n_samples;
+        q.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
+        q.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
+    }
     const uint32_t grid = vrt::rays::plan(q.n, q.width, q.tiles_x);
     const ProfSlot prof = ProfSlot::take(c);
     hipError_t e;
-    if (hdr) {
-        vrt::rays::HdrArgs hq;
-        // HdrArgs derives from Args: the plain arguments are its base, first in the layout -- what late_rays() (vrt_rays.hip.h) relies
-        // on when it reads the kernel's third argument at Args' place in either form
-        static_cast<vrt::rays::Args &>(hq) = q;
-        hq.n_samples = n_samples;   // every mode: the primary modes add their one sample n_samples times over
-        hq.sums = hdr->d_sums;
-        hq.out_rgb = hdr->d_rgb;
-        hq.n_total = hdr->n_prior + n_samples;
-        hq.op = hdr->tm ? hdr->tm->op : VRT_TONEMAP_CLAMP;
-        hq.exposure = hdr->tm ? hdr->tm->exposure : 1.0f;
-        e = mis ? vrt::launch::shade_rays_hdr_emitm(v, a, vs, hq, emm, grid, s, prof.ev0, prof.ev1)
-            : power ? vrt::launch::shade_rays_hdr_emitp(v, a, vs, hq, emp, grid, s, prof.ev0, prof.ev1)
-            : emit_on ? vrt::launch::shade_rays_hdr_emit(v, a, vs, hq, em, grid, s, prof.ev0, prof.ev1)
-            : sun_on ? vrt::launch::shade_rays_hdr_sun(v, a, vs, hq, sun, grid, s, prof.ev0, prof.ev1)
-            : deep ? vrt::launch::shade_rays_hdr_deep(v, a, vs, hq, grid, s, prof.ev0, prof.ev1)
-                   : vrt::launch::shade_rays_hdr(mode, v, a, vs, hq, grid, s, prof.ev0, prof.ev1);
-    } else {
-        e = mis ? vrt::launch::shade_rays_emitm(v, a, vs, q, emm, grid, s, prof.ev0, prof.ev1)
-            : power ? vrt::launch::shade_rays_emitp(v, a, vs, q, emp, grid, s, prof.ev0, prof.ev1)
-            : emit_on ? vrt::launch::shade_rays_emit(v, a, vs, q, em, grid, s, prof.ev0, prof.ev1)
-            : sun_on ? vrt::launch::shade_rays_sun(v, a, vs, q, sun, grid, s, prof.ev0, prof.ev1)
-            : deep ? vrt::launch::shade_rays_deep(v, a, vs, q, grid, s, prof.ev0, prof.ev1) : vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
-    }
+    if (mode == VRT_MODE_FULL) e = vrt::launch::shade_rays_full(hdr != nullptr, fam, pa, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
+    else if (hdr) e = vrt::launch::shade_rays_hdr(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
+    else e = vrt::launch::shade_rays(mode, v, a, vs, q, grid, s, prof.ev0, prof.ev1);
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     prof.commit(c);
     return VRT_OK;

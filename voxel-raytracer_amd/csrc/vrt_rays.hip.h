@@ -140,282 +140,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 // loop_args()); the medium's two words stay in registers. The mean is accum_resolve_kernel's: (sum + n / 2) / n per channel of the
 // bytes each sample would store, alpha 255; the (voxel ID, dist) pair is the same for every sample.
 // HDR: one add_hdr() per sample in sample order; LOOP carries the three float64 sums (six registers) across the back edge.
-// (shade_rays_full_sun_kernel, shade_rays_full_emit_kernel, shade_rays_full_emitp_kernel and shade_rays_full_emitm_kernel below are this
-// kernel's body once more, for the sun disc, emitter sampling's two modes and its MIS: a change here is a change there.)
-template <class TRAV, int WPE, bool LOOP, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q) {
+// X...: the argument of TRAV's family (vrt_common.hip.h: TRAV::Arg -- the Sun of SunPaths<...>, the Emit, EmitPower or EmitMis of the
+// emitter families), a fourth argument of its own after the three that late_args(), late_view() and late_rays() re-read, which rides
+// in the traversal's context; none for the plain traversals and DeepPaths<...>. One body for every family, as the accumulation's
+// kernels take their Lens: under a shared __device__ body the kernel compiles to other code (profiles/sun_disc_codegen.txt), with
+// the argument as a template parameter to the same (profiles/path_family_fold_codegen.txt).
+template <class TRAV, int WPE, bool LOOP, bool HDR = false, class... X>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q, const X... arg) {
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
-    uint32_t i;
-    int px, py;
-    if (!ray_of_lane(q, i, px, py)) return;
-    LensRay lr = RaySource::load(a, q, i);
-    uint32_t rgba;
-    int2 idd;
-    LateOut lo;
-    if constexpr (!LOOP && HDR) {
-        float fc[3];
-        full::trace_pixel_full<TRAV, false, true, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr, fc);
-        const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
-        accum::HdrSum hs = first_hdr(lq->sums, i);
-        accum::add_hdr(fc, hs);
-        finish_hdr(i, hs, idd);
-    } else if constexpr (!LOOP) {
-        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    } else {
-        const uint32_t eye0 = lr.eye0, eye1 = lr.eye1;
-        uint32_t r = 0u, g = 0u, b = 0u;
-        accum::HdrSum hs{};
-        if constexpr (HDR) hs = first_hdr(q.sums, i);
-        const uint32_t n = q.n_samples;
-        for (uint32_t k = 0; k < n; ++k) {
-#ifdef __HIP_DEVICE_COMPILE__
-            const KArgs ak = *late_args();
-            const View vk = *late_view();
-            const Args qk = *late_rays();
-#else
-            const KArgs ak = a;
-            const View vk = vs.v[0];
-            const Args qk = q;
-#endif
-            const float *o = qk.origins + (qk.origin_stride ? (size_t)i * 3u : (size_t)0);
-            const float *d = qk.dirs + (size_t)i * 3u;
-            const F3 dir{d[0], d[1], d[2]};
-            LensRay lk;
-            lk.o = F3{o[0], o[1], o[2]};
-            lk.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));
-            lk.eye0 = eye0; lk.eye1 = eye1;
-            if constexpr (HDR) {
-                float fc[3];
-                full::trace_pixel_full<TRAV, false, true, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk, fc);
-                accum::add_hdr(fc, hs);
-            } else {
-                full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
-                r += rgba & 0xffu;
-                g += (rgba >> 8) & 0xffu;
-                b += (rgba >> 16) & 0xffu;
-            }
-        }
-        if constexpr (HDR) {
-            finish_hdr(i, hs, idd);
-        } else {
-            const uint32_t h = n >> 1;
-            rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
-        }
-    }
-    if constexpr (!HDR) store(i, rgba, idd);
-}
-
-// The same over SunPaths<...> (include/vrt.h vrt_set_sun_disc): the Sun is a fourth argument of its own, after the three that
-// late_args(), late_view() and late_rays() re-read, and rides in the traversal's context. The body is written out again, as the
-// accumulation's kernels write theirs: under a shared __device__ body shade_rays_full_kernel compiles to other code
-// (profiles/sun_disc_codegen.txt), and its mangled name is part of what tests/test_shade_rays_hdr.py pins.
-template <class TRAV, int WPE, bool LOOP, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_sun_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q, const Sun sun) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    tc_.sun = sun;
-    uint32_t i;
-    int px, py;
-    if (!ray_of_lane(q, i, px, py)) return;
-    LensRay lr = RaySource::load(a, q, i);
-    uint32_t rgba;
-    int2 idd;
-    LateOut lo;
-    if constexpr (!LOOP && HDR) {
-        float fc[3];
-        full::trace_pixel_full<TRAV, false, true, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr, fc);
-        const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
-        accum::HdrSum hs = first_hdr(lq->sums, i);
-        accum::add_hdr(fc, hs);
-        finish_hdr(i, hs, idd);
-    } else if constexpr (!LOOP) {
-        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    } else {
-        const uint32_t eye0 = lr.eye0, eye1 = lr.eye1;
-        uint32_t r = 0u, g = 0u, b = 0u;
-        accum::HdrSum hs{};
-        if constexpr (HDR) hs = first_hdr(q.sums, i);
-        const uint32_t n = q.n_samples;
-        for (uint32_t k = 0; k < n; ++k) {
-#ifdef __HIP_DEVICE_COMPILE__
-            const KArgs ak = *late_args();
-            const View vk = *late_view();
-            const Args qk = *late_rays();
-#else
-            const KArgs ak = a;
-            const View vk = vs.v[0];
-            const Args qk = q;
-#endif
-            const float *o = qk.origins + (qk.origin_stride ? (size_t)i * 3u : (size_t)0);
-            const float *d = qk.dirs + (size_t)i * 3u;
-            const F3 dir{d[0], d[1], d[2]};
-            LensRay lk;
-            lk.o = F3{o[0], o[1], o[2]};
-            lk.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));
-            lk.eye0 = eye0; lk.eye1 = eye1;
-            if constexpr (HDR) {
-                float fc[3];
-                full::trace_pixel_full<TRAV, false, true, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk, fc);
-                accum::add_hdr(fc, hs);
-            } else {
-                full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
-                r += rgba & 0xffu;
-                g += (rgba >> 8) & 0xffu;
-                b += (rgba >> 16) & 0xffu;
-            }
-        }
-        if constexpr (HDR) {
-            finish_hdr(i, hs, idd);
-        } else {
-            const uint32_t h = n >> 1;
-            rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
-        }
-    }
-    if constexpr (!HDR) store(i, rgba, idd);
-}
-
-// ... and over EmitPaths<...> (include/vrt.h vrt_set_emitter_sampling): the fourth argument is the Emit -- the emitter list and the
-// Sun -- and rides in the traversal's context. The body once more, for the reasons above.
-template <class TRAV, int WPE, bool LOOP, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_emit_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q, const Emit em) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    TRAV::take(tc_, em);
-    uint32_t i;
-    int px, py;
-    if (!ray_of_lane(q, i, px, py)) return;
-    LensRay lr = RaySource::load(a, q, i);
-    uint32_t rgba;
-    int2 idd;
-    LateOut lo;
-    if constexpr (!LOOP && HDR) {
-        float fc[3];
-        full::trace_pixel_full<TRAV, false, true, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr, fc);
-        const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
-        accum::HdrSum hs = first_hdr(lq->sums, i);
-        accum::add_hdr(fc, hs);
-        finish_hdr(i, hs, idd);
-    } else if constexpr (!LOOP) {
-        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    } else {
-        const uint32_t eye0 = lr.eye0, eye1 = lr.eye1;
-        uint32_t r = 0u, g = 0u, b = 0u;
-        accum::HdrSum hs{};
-        if constexpr (HDR) hs = first_hdr(q.sums, i);
-        const uint32_t n = q.n_samples;
-        for (uint32_t k = 0; k < n; ++k) {
-#ifdef __HIP_DEVICE_COMPILE__
-            const KArgs ak = *late_args();
-            const View vk = *late_view();
-            const Args qk = *late_rays();
-#else
-            const KArgs ak = a;
-            const View vk = vs.v[0];
-            const Args qk = q;
-#endif
-            const float *o = qk.origins + (qk.origin_stride ? (size_t)i * 3u : (size_t)0);
-            const float *d = qk.dirs + (size_t)i * 3u;
-            const F3 dir{d[0], d[1], d[2]};
-            LensRay lk;
-            lk.o = F3{o[0], o[1], o[2]};
-            lk.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));
-            lk.eye0 = eye0; lk.eye1 = eye1;
-            if constexpr (HDR) {
-                float fc[3];
-                full::trace_pixel_full<TRAV, false, true, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk, fc);
-                accum::add_hdr(fc, hs);
-            } else {
-                full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
-                r += rgba & 0xffu;
-                g += (rgba >> 8) & 0xffu;
-                b += (rgba >> 16) & 0xffu;
-            }
-        }
-        if constexpr (HDR) {
-            finish_hdr(i, hs, idd);
-        } else {
-            const uint32_t h = n >> 1;
-            rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
-        }
-    }
-    if constexpr (!HDR) store(i, rgba, idd);
-}
-
-// ... and over EmitPowerPaths<...> (include/vrt.h vrt_set_emitter_importance, VRT_EMIT_POWER): the fourth argument is the EmitPower --
-// the Emit and the table of thresholds. The body once more.
-template <class TRAV, int WPE, bool LOOP, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_emitp_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q, const EmitPower em) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    TRAV::take(tc_, em);
-    uint32_t i;
-    int px, py;
-    if (!ray_of_lane(q, i, px, py)) return;
-    LensRay lr = RaySource::load(a, q, i);
-    uint32_t rgba;
-    int2 idd;
-    LateOut lo;
-    if constexpr (!LOOP && HDR) {
-        float fc[3];
-        full::trace_pixel_full<TRAV, false, true, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr, fc);
-        const HdrArgs __attribute__((address_space(4))) *lq = (const HdrArgs __attribute__((address_space(4))) *)late_rays();
-        accum::HdrSum hs = first_hdr(lq->sums, i);
-        accum::add_hdr(fc, hs);
-        finish_hdr(i, hs, idd);
-    } else if constexpr (!LOOP) {
-        full::trace_pixel_full<TRAV, false, true>(a, vs.v[0], tc_, px, py, rgba, idd, lo, q.first, &lr);
-    } else {
-        const uint32_t eye0 = lr.eye0, eye1 = lr.eye1;
-        uint32_t r = 0u, g = 0u, b = 0u;
-        accum::HdrSum hs{};
-        if constexpr (HDR) hs = first_hdr(q.sums, i);
-        const uint32_t n = q.n_samples;
-        for (uint32_t k = 0; k < n; ++k) {
-#ifdef __HIP_DEVICE_COMPILE__
-            const KArgs ak = *late_args();
-            const View vk = *late_view();
-            const Args qk = *late_rays();
-#else
-            const KArgs ak = a;
-            const View vk = vs.v[0];
-            const Args qk = q;
-#endif
-            const float *o = qk.origins + (qk.origin_stride ? (size_t)i * 3u : (size_t)0);
-            const float *d = qk.dirs + (size_t)i * 3u;
-            const F3 dir{d[0], d[1], d[2]};
-            LensRay lk;
-            lk.o = F3{o[0], o[1], o[2]};
-            lk.dir = scale3(dir, 1.0f / __builtin_sqrtf(dot3(dir, dir)));
-            lk.eye0 = eye0; lk.eye1 = eye1;
-            if constexpr (HDR) {
-                float fc[3];
-                full::trace_pixel_full<TRAV, false, true, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk, fc);
-                accum::add_hdr(fc, hs);
-            } else {
-                full::trace_pixel_full<TRAV, false, true>(ak, vk, tc_, px, py, rgba, idd, lo, qk.first + k, &lk);
-                r += rgba & 0xffu;
-                g += (rgba >> 8) & 0xffu;
-                b += (rgba >> 16) & 0xffu;
-            }
-        }
-        if constexpr (HDR) {
-            finish_hdr(i, hs, idd);
-        } else {
-            const uint32_t h = n >> 1;
-            rgba = ((r + h) / n) | (((g + h) / n) << 8) | (((b + h) / n) << 16) | (255u << 24);
-        }
-    }
-    if constexpr (!HDR) store(i, rgba, idd);
-}
-
-// ... and over EmitMisPaths<...> (include/vrt.h vrt_set_emitter_mis): the fourth argument is the EmitMis -- the EmitPower and
-// 1 / Wtot. The body once more.
-template <class TRAV, int WPE, bool LOOP, bool HDR = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void shade_rays_full_emitm_kernel(const KArgs a, const ViewSet vs, const ArgsOf<HDR> q, const EmitMis em) {
-    typename TRAV::Ctx tc_;
-    TRAV::block_init(a, tc_);
-    TRAV::take(tc_, em);
+    if constexpr (sizeof...(X) != 0) TRAV::take(tc_, arg...);
     uint32_t i;
     int px, py;
     if (!ray_of_lane(q, i, px, py)) return;

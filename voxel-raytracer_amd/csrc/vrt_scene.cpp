@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <new>
+#include <type_traits>
 
 using namespace vrt_internal;
 #include "vrt_launch.h"
@@ -162,6 +163,26 @@ int check_tonemap(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
 }
 
 }  // namespace vrt_internal
+
+// The one place that says which kernels a VRT_MODE_FULL launch takes. The families nest -- each honours what the ones before it do --
+// so the last setting that is on names the family, and the block is filled up to that family's slice.
+bool vrt::launch::select_paths(int mode, const PathSetup &p, const float light_dir[3], bool opaque, PathFamily &fam, PathArgs &pa) {
+    fam = PathFamily::kPlain;
+    pa = PathArgs{};
+    if (mode != VRT_MODE_FULL) return true;
+    const bool sun = p.sun_radius > 0.0f;                             // vrt_set_sun_disc, at every depth; radius 0: no block is made
+    const bool emit = p.emit();                                       // vrt_set_emitter_sampling, at every depth and sun radius
+    const bool power = emit && p.importance == VRT_EMIT_POWER;        // vrt_set_emitter_importance
+    const bool mis = power && p.mis;                                  // vrt_set_emitter_mis
+    if (emit && opaque) return false;                                 // the dispatcher does not choose the opaque routes for it
+    if (sun) pa.power.emit.sun = sun_block(light_dir, p.sun_radius);
+    if (emit) { pa.power.emit.list = p.list; pa.power.emit.n = p.n; }
+    if (power) pa.power.cdf = p.cdf;
+    if (mis) pa.inv_power = p.inv_power;
+    fam = mis ? PathFamily::kEmitMis : power ? PathFamily::kEmitPower : emit ? PathFamily::kEmit : sun ? PathFamily::kSun
+          : p.path_depth > 1 ? PathFamily::kDeep : PathFamily::kPlain;   // vrt_set_path_depth: the kernels that read KArgs::path_depth
+    return true;
+}
 
 extern "C" {
 
@@ -440,3 +461,55 @@ void *vrt_stream(vrt_ctx *c) { return c ? (void *)c->stream : nullptr; }
 int vrt_device(const vrt_ctx *c) { return c ? c->device : VRT_E_INVALID; }
 
 }  // extern "C"
+
+// ... and the one switch from the family as a value to the per-object instantiations of vrt_launch.h AccumPaths / RayPaths. Here, in a
+// translation unit that sees their declarations only: where the launch headers are included a use would instantiate the kernels.
+namespace vrt {
+namespace launch {
+
+// f(std::integral_constant<PathFamily, F>{}) for F == fam
+template <class FN>
+static hipError_t with_family(PathFamily fam, FN &&f) {
+    switch (fam) {
+        case PathFamily::kPlain: return f(std::integral_constant<PathFamily, PathFamily::kPlain>{});
+        case PathFamily::kDeep: return f(std::integral_constant<PathFamily, PathFamily::kDeep>{});
+        case PathFamily::kSun: return f(std::integral_constant<PathFamily, PathFamily::kSun>{});
+        case PathFamily::kEmit: return f(std::integral_constant<PathFamily, PathFamily::kEmit>{});
+        case PathFamily::kEmitPower: return f(std::integral_constant<PathFamily, PathFamily::kEmitPower>{});
+        case PathFamily::kEmitMis: return f(std::integral_constant<PathFamily, PathFamily::kEmitMis>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t accum_opaque(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const KArgs &a, const ViewSet &vs,
+                        const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+    return with_family(fam, [&](auto f) {
+        return hdr ? AccumPaths<true, decltype(f)::value>::opaque(src, a, vs, q, adaptive, l, pa, grid, s)
+                   : AccumPaths<false, decltype(f)::value>::opaque(src, a, vs, q, adaptive, l, pa, grid, s);
+    });
+}
+hipError_t accum_full(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
+                      const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+    return with_family(fam, [&](auto f) {
+        return hdr ? AccumPaths<true, decltype(f)::value>::full(src, v, a, vs, q, adaptive, l, pa, grid, s)
+                   : AccumPaths<false, decltype(f)::value>::full(src, v, a, vs, q, adaptive, l, pa, grid, s);
+    });
+}
+hipError_t accum_bounce(bool hdr, PathFamily fam, const PathArgs &pa, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+                        bool adaptive, int grid, hipStream_t s) {
+    return with_family(fam, [&](auto f) {
+        return hdr ? AccumPaths<true, decltype(f)::value>::bounce(a, vs, q, adaptive, pa, grid, s)
+                   : AccumPaths<false, decltype(f)::value>::bounce(a, vs, q, adaptive, pa, grid, s);
+    });
+}
+
+hipError_t shade_rays_full(bool hdr, PathFamily fam, const PathArgs &pa, const Variant &v, const KArgs &a, const ViewSet &vs,
+                           const rays::HdrArgs &q, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    return with_family(fam, [&](auto f) {
+        return hdr ? RayPaths<true, decltype(f)::value>::full(v, a, vs, q, pa, grid, s, ev0, ev1)
+                   : RayPaths<false, decltype(f)::value>::full(v, a, vs, q, pa, grid, s, ev0, ev1);
+    });
+}
+
+}  // namespace launch
+}  // namespace vrt
