@@ -784,6 +784,65 @@ int vrt_denoise_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, 
                          float *out_rgb, uint8_t *out_rgba8);
 int vrt_accum_resolve_hdr_shown(vrt_ctx *ctx, const vrt_tonemap *tm, float *out_shown_rgb, uint8_t *out_shown_rgba8);
 int vrt_accum_resolve_hdr_shown_device(vrt_ctx *ctx, const vrt_tonemap *tm, void *d_shown_rgb, void *d_shown_rgba8, void *stream);
+
+/* EXTENSION: guide planes -- per pixel of an accumulation (or per ray of a batch) the first hit's normal, albedo, depth and coverage,
+ * averaged over the samples: the feature buffers a denoiser or a compositor asks for beside the colour. Features, not radiance: no
+ * shading, no shadow ray, no random number.
+ *
+ * The guide of one sample of one pixel is taken from the depth-0 march of that sample's own ray: the ray sample k of the
+ * accumulation starts from -- the pixel's corner, the jittered ray of VRT_ACCUM_JITTER or the thin-lens ray of vrt_set_lens, origin
+ * and medium at the origin included -- marched as every frame marches it. The guide hit is therefore the hit the sample's
+ * (voxel ID, dist) describes.
+ *   hit      the march returned a hit. A miss adds nothing to any sum below.
+ *   normal   +1 or -1 on one axis: hitNormal, or (0, 1, 0) where its length is not above 0 (comp:497), before the flip towards the
+ *            ray of comp:524. Three signed integer sums.
+ *   albedo   the four bytes of surfaceColor (comp:505-507): the hit leaf's R, G, B, A, or the previous voxel's where the hit leaf's
+ *            alpha is 0; where the hit cell is the highlighted voxel (vrt_params) R, G, B become 255 - byte and A 255. Four
+ *            unsigned integer sums. Alpha below 1 shows glass: through glass the guide is the glass surface, no refraction is
+ *            followed.
+ *   depth    the float32 distance from the sample's ray origin to the hit point in world units: with p = hitPoint, each component
+ *            divided by u_voxelScale only when the scale is not 1, and o the ray's origin, d = sqrtf((dx*dx + dy*dy) + dz*dz) of
+ *            p - o, every operation rounded on its own; then h(d) = min(max(0, d), 65504.0f) as in vrt_accum_keep_hdr point 1,
+ *            added as a double, one add per sample in sample order, to one float64 sum.
+ *   hits     one unsigned count.
+ * The state is 40 bytes per pixel (uint32[4], int32[3], uint32, double), the accumulation's own, allocated by the first guide call:
+ * an accumulation that never asks takes what it took. The planes of n samples, every division in float64 and one rounding to
+ * float32:
+ *   normal[3] = (float)(nsum / n)    albedo[4] = (float)(asum / (255.0 * n))    coverage = (float)(hits / n)
+ *   depth = hits ? (float)(dsum / hits) : 0
+ * Integer sums do not depend on how the samples were split over calls, and the depth sum is sequential per pixel: the planes are
+ * the same bits after any sequence of vrt_accum_add and guide calls that leads to the same samples.
+ *
+ * vrt_accum_guides         HOST buffers [H][W][3], [H][W][4], [H][W], [H][W] (any may be NULL), synchronous. Needs an accumulation of
+ *                          any mode and form (corner, jitter, lens, adaptive, plain or HDR) that holds samples: VRT_E_STATE before
+ *                          vrt_accum_begin* and before the first vrt_accum_add. The first call adds the guides of samples
+ *                          first_sample .. first_sample + total - 1, a later call those of the samples added since the last one,
+ *                          then the planes are resolved over `total`. Whatever restarts the accumulation's sums -- a begin, or a
+ *                          vrt_accum_add after a change of camera, uniforms, tree or lens -- clears the guide state with them. The
+ *                          missing samples are marched with the context's current inputs: where those changed since the last
+ *                          vrt_accum_add (which would restart) and samples are missing, the call returns VRT_E_STATE; add first.
+ *                          Path depth, sun disc and the emitter settings are no inputs of a guide.
+ * vrt_accum_guides_device  the same into DEVICE buffers; the resolve is enqueued on `stream` (NULL: the context's), ordered against
+ *                          the adds as vrt_accum_resolve_device is.
+ * Adaptive accumulations: `total` is the number of rounds, and every pixel's guide takes every round's sample index whatever its
+ * active mask says -- a pixel that stopped early still has n = total guide samples, so its planes stay comparable with its
+ * neighbours'. These calls read and write no byte of the accumulation's own sums: vrt_accum_resolve* return the same bytes with and
+ * without them. They take no profiling slot.
+ *
+ * Ray batches, stateless, beside vrt_shade_rays: one march per ray, no sample index (a caller's ray has no jitter); the planes are
+ * those of n = 1 -- normal [n][3] (zeros on a miss), albedo [n][4] = (float)(byte / 255.0), depth [n] = h(d) (0 on a miss) -- and
+ * out_hit one byte per ray, 1 or 0. Rays, origin_stride and width as in vrt_shade_rays (width >= 1 only chooses how rays map to
+ * lanes: a batch at least 8 wide and two rows high is traced in 8 x 8 tiles); origins in glass, in a solid or outside the world and
+ * un-normalised or axis-parallel directions behave as there. Any output may be NULL, not all. Errors: those of vrt_shade_rays.
+ * vrt_guide_rays: HOST buffers, synchronous; vrt_guide_rays_device: DEVICE buffers, enqueued on `stream` (NULL: the context's).
+ * Unlike vrt_shade_rays they take no profiling slot (vrt_set_profiling) and do not count towards its stride.
+ * Not provided: guides past glass (the first opaque hit along the refracted ray), motion vectors, frames, views, shards, vrt_multi. */
+int vrt_accum_guides(vrt_ctx *ctx, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage);
+int vrt_accum_guides_device(vrt_ctx *ctx, void *d_normal, void *d_albedo, void *d_depth, void *d_coverage, void *stream);
+int vrt_guide_rays(vrt_ctx *ctx, size_t n, const float *origins, int origin_stride, const float *dirs, int width, float *out_normal,
+                   float *out_albedo, float *out_depth, uint8_t *out_hit);
+int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, void *d_normal,
+                          void *d_albedo, void *d_depth, void *d_hit, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

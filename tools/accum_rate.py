@@ -57,6 +57,14 @@ mis_room_1080p is tests/emit_mis_worlds.py's room seen from inside, looking at t
 
 --variant V (with --path-depth) measures with vrt_set_variant(V) and records it (variant); 1 takes the record-array kernels.
 
+--guides measures the guide planes (vrt_accum_guides_device) instead: on each scene of --scenes, from the corner, jittered and through a
+thin lens (the first --lens, default 0.1 40), the wall time of one guide call that catches up --samples new samples (guide_ms: the
+guide kernel over them plus the resolve), of a call with nothing new (resolve_ms: the resolve alone), the guide time per sample
+between them (guide_per_sample_ms), and beside it one vrt_accum_add of as many samples of VRT_MODE_PRIMARY from the same source
+(primary_add_ms, primary_per_sample_ms: the same march with its shading; the corner's is the repeat path, which marches nothing):
+
+    python3 tools/accum_rate.py --guides --scenes dragon_1080p room_inside_1080p --samples 16 --out profiles/guides_rate.jsonl
+
 --out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
 --adaptive takes none of --path-depth, --scenes and --samples (it measures its own scenes and rounds) and refuses them.
 """
@@ -107,6 +115,7 @@ def main():
                     help="with --emit-power: sampling on at mode 1 once per MIS flag (vrt_set_emitter_mis)")
     ap.add_argument("--variant", type=int, default=None, metavar="V",
                     help="with --path-depth: the traversal variant (vrt_set_variant; 1: the record-array kernels), recorded as variant")
+    ap.add_argument("--guides", action="store_true", help="the guide planes beside primary-mode adds (see above)")
     ap.add_argument("--scenes", nargs="+", default=DEFAULT_SCENES, choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
@@ -123,6 +132,8 @@ def main():
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
+    if args.guides:
+        return guides_main(V, args)
     from conftest import MAPS, room_world
     W, H = 1920, 1080
     ctx = V.Context(0)
@@ -246,10 +257,10 @@ def main():
                 f.write(json.dumps(r) + "\n")
 
 
-def _scenes(V, ctx, W, H):
+def _scenes(V, ctx, W, H, names=DEFAULT_SCENES):
     from conftest import MAPS, room_world
     for name, (m, pos, yaw, pitch) in SCENES.items():
-        if name not in DEFAULT_SCENES:
+        if name not in names or name not in DEFAULT_SCENES:
             continue
         if m == "room":
             w = room_world(V)
@@ -305,6 +316,58 @@ def adaptive_main(V, args):
                 print(json.dumps(row), flush=True)
                 rows.append(row)
             ctx.set_lens(0.0, 1.0)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+def guides_main(V, args):
+    W, H = 1920, 1080
+    ctx = V.Context(0)
+    d_planes = [ctx.device_alloc(W * H * 4 * k) for k in (3, 4, 1, 1)]
+    lens = tuple(args.lens[0]) if args.lens else (0.1, 40.0)
+    rows = []
+
+    def timed(body, before=None):
+        ts = []
+        for _ in range(args.reps + 1):
+            if before:
+                before()
+                ctx.synchronize()
+            t0 = time.perf_counter()
+            body()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts[1:])), min(ts[1:]), max(ts[1:])   # the first: code object load, buffers
+
+    for name, tex in _scenes(V, ctx, W, H, args.scenes):
+        for source, jitter, ln in (("corner", False, None), ("jitter", True, None), ("lens", False, lens)):
+            ctx.set_lens(*(ln or (0.0, 1.0)))
+            for n in args.samples:
+                ctx.accum_begin(W, H, 0, mode=V.MODES["primary"], jitter=jitter)
+                ctx.accum_add(n)
+                ctx.accum_guides_device(*d_planes)
+                ctx.synchronize()
+                guide = timed(lambda: ctx.accum_guides_device(*d_planes), before=lambda: ctx.accum_add(n))
+                resolve = timed(lambda: ctx.accum_guides_device(*d_planes))
+                ctx.accum_begin(W, H, 0, mode=V.MODES["primary"], jitter=jitter)
+                ctx.accum_add(n)
+                ctx.synchronize()
+                add = timed(lambda: ctx.accum_add(n))
+                row = {"scene": name, "width": W, "height": H, "source": source, "n": n, "guide_ms": round(guide[0], 4),
+                       "guide_ms_min_max": [round(guide[1], 4), round(guide[2], 4)], "resolve_ms": round(resolve[0], 4),
+                       "guide_per_sample_ms": round((guide[0] - resolve[0]) / n, 4), "primary_add_ms": round(add[0], 4),
+                       "primary_add_ms_min_max": [round(add[1], 4), round(add[2], 4)], "primary_per_sample_ms": round(add[0] / n, 4),
+                       "guide_vs_primary": round((guide[0] - resolve[0]) / add[0], 3), "reps": args.reps}
+                if ln:
+                    row.update(aperture=ln[0], focus=ln[1])
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+        ctx.set_lens(0.0, 1.0)
+    for d in d_planes:
+        ctx.device_free(d)
     ctx.close()
     if args.out:
         with open(args.out, "w") as f:

@@ -37,6 +37,12 @@ and 256 dim singles) instead of the lamp room:
 1) and records it (emitter_mis); --emit-world mis_room takes tests/emit_mis_worlds.py's room, the frame's rays from its INSIDE_POSE:
 
     python3 tools/shade_rays_rate.py --path-depth 1 4 --emit 0 1 --emit-power 1 --emit-mis 0 1 --emit-world mis_room --append --out profiles/emit_mis_rate.jsonl
+
+--guides measures vrt_guide_rays_device (all four outputs written) alternated call by call with vrt_shade_rays_device in
+VRT_MODE_PRIMARY on the same rays -- the same march with its shading on top -- on the 1080p dragon frame's rays and on a list of
+1 M random rays; wall time around each call and a synchronise (the guide launches take no profiling slot):
+
+    python3 tools/shade_rays_rate.py --guides --append --out profiles/guides_rate.jsonl   (after tools/accum_rate.py --guides)
 """
 import argparse
 import json
@@ -88,6 +94,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--hdr", action="store_true", help="the HDR calls beside the plain ones (see above)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
+    ap.add_argument("--guides", action="store_true", help="vrt_guide_rays_device beside mode-0 vrt_shade_rays_device (see above)")
     ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="mode 2 once per path depth (see above)")
     ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
     ap.add_argument("--emit", nargs="+", type=int, default=None, choices=(0, 1), metavar="E",
@@ -154,6 +161,40 @@ def main():
             with open(args.out, "a" if args.append else "w") as f:
                 for r in rows:
                     f.write(json.dumps(r) + "\n")
+
+    if args.guides:
+        import time
+        W, H = 1920, 1080
+        _, origin, dirs = frame_rays(V, W, H)
+        rng = np.random.default_rng(1)
+        n_list = 1 << 20
+        lo = rng.uniform((-64, -64, -64), (192, 160, 128), (n_list, 3)).astype(np.float32)
+        ld = rng.normal(0, 1, (n_list, 3)).astype(np.float32)
+        for case, o, d, stride, width in (("frame_rays_1080p_dragon", origin.reshape(1, 3), dirs, 0, W),
+                                          ("random_rays_1m_dragon", lo, ld, 3, n_list)):
+            n = len(d)
+            d_o, d_d = upload(o, d)
+            d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
+            d_n, d_a, d_z, d_h = ctx.device_alloc(n * 12), ctx.device_alloc(n * 16), ctx.device_alloc(n * 4), ctx.device_alloc(n)
+            calls = [lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=0, width=width),
+                     lambda: ctx.guide_rays_device(n, d_o, stride, d_d, d_n, d_a, d_z, d_h, width=width)]
+            ms = [[], []]
+            for rep in range(args.reps + 2):   # the first two rounds: code objects
+                for i, f in enumerate(calls):
+                    ctx.synchronize()
+                    t0 = time.perf_counter()
+                    f()
+                    ctx.synchronize()
+                    if rep >= 2:
+                        ms[i].append((time.perf_counter() - t0) * 1e3)
+            pm, gm = float(np.median(ms[0])), float(np.median(ms[1]))
+            emit({"case": case, "rays": n, "primary_call_ms": round(pm, 4), "guide_call_ms": round(gm, 4), "guide_over_primary": round(gm / pm, 3),
+                  "primary_ms_min_max": [round(min(ms[0]), 4), round(max(ms[0]), 4)], "guide_ms_min_max": [round(min(ms[1]), 4), round(max(ms[1]), 4)],
+                  "guide_rays_per_s": round(n / (gm * 1e-3)), "reps": args.reps})
+            for p in (d_o, d_d, d_rgba, d_id, d_n, d_a, d_z, d_h):
+                ctx.device_free(p)
+        finish()
+        return
 
     if args.hdr:
         W, H = 1920, 1080

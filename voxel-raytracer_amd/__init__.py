@@ -308,6 +308,12 @@ def hip_lib():
         L.vrt_denoise_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr_shown.argtypes = [C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr_shown_device.argtypes = [C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_accum_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_accum_guides_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_guide_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
+        L.vrt_guide_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
         _hip = L
     return _hip
 
@@ -1173,6 +1179,43 @@ class Context:
         """vrt_accum_resolve_hdr_device: DEVICE buffers (any may be None; d_shown needs d_rgba), enqueued on `stream`"""
         tm = self._tonemap(tonemap, exposure)
         self._chk(self._L.vrt_accum_resolve_hdr_device(self._h, d_rgb, C.byref(tm), d_rgba, d_shown, stream))
+
+    def accum_guides(self):
+        """The accumulation's guide planes (vrt_accum_guides): first-hit features averaged over the samples in the sums ->
+        {"normal": float32[H,W,3], "albedo": float32[H,W,4], "depth": float32[H,W], "coverage": float32[H,W]}."""
+        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
+        out = {"normal": np.zeros((h, w, 3), np.float32), "albedo": np.zeros((h, w, 4), np.float32),
+               "depth": np.zeros((h, w), np.float32), "coverage": np.zeros((h, w), np.float32)}
+        self._chk(self._L.vrt_accum_guides(self._h, out["normal"].ctypes.data, out["albedo"].ctypes.data, out["depth"].ctypes.data,
+                                           out["coverage"].ctypes.data))
+        return out
+
+    def accum_guides_device(self, d_normal, d_albedo, d_depth, d_coverage, stream=None):
+        """vrt_accum_guides_device: DEVICE buffers (H*W x 3, x 4, x 1, x 1 floats; any may be None), the resolve enqueued on `stream`"""
+        self._chk(self._L.vrt_accum_guides_device(self._h, d_normal, d_albedo, d_depth, d_coverage, stream))
+
+    def guide_rays(self, origins, dirs, width=None):
+        """First-hit guides of the caller's own rays (vrt_guide_rays), one march each. origins, dirs as in shade_rays; width: the
+        batch as an image of that width for the lane mapping (None: a list) -> {"normal": float32[n,3], "albedo": float32[n,4],
+        "depth": float32[n], "hit": bool[n]}."""
+        o, stride, d = shade_ray_args(origins, dirs)
+        n = d.shape[0]
+        normal = np.zeros((n, 3), np.float32)
+        albedo = np.zeros((n, 4), np.float32)
+        depth = np.zeros(n, np.float32)
+        hit = np.zeros(n, np.uint8)
+        w = max(n, 1) if width is None else int(width)
+        self._chk(self._L.vrt_guide_rays(self._h, n, o.ctypes.data if n else None, stride, d.ctypes.data if n else None, w,
+                                         normal.ctypes.data, albedo.ctypes.data, depth.ctypes.data, hit.ctypes.data))
+        return {"normal": normal, "albedo": albedo, "depth": depth, "hit": hit != 0}
+
+    def guide_rays_device(self, n, d_origins, origin_stride, d_dirs, d_normal, d_albedo, d_depth, d_hit, width=None, stream=None):
+        """vrt_guide_rays_device: DEVICE buffers (n x 3, n x 4, n floats, n bytes; any may be None, not all), enqueued on `stream`"""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 30:
+            raise ValueError(f"n: expected an integer in [0, 2^30], got {n!r}")
+        w = max(int(n), 1) if width is None else int(width)
+        self._chk(self._L.vrt_guide_rays_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, d_normal, d_albedo,
+                                                d_depth, d_hit, stream))
 
     def accum_resolve_hdr_shown(self, tonemap="clamp", exposure=1.0):
         """The HDR display pass on an HDR accumulation (vrt_accum_resolve_hdr_shown): the ID-aware blur on the float mean, then the

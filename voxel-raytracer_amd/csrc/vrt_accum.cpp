@@ -98,24 +98,6 @@ int ensure_float_image(vrt_ctx *c, DevBuf<float> &buf, size_t px) {
     return px * 12 <= buf.bytes() ? VRT_OK : reserve_synced(c, {{&buf, px * 12}});
 }
 
-// A resolve on stream s, ordered against the context's: the samples were added on the context's stream, and later adds must not
-// overtake this read (nor, through `read`, the last call's use of the float mean). Nothing to do when s is the context's stream.
-template <class BODY>
-int joined(vrt_ctx *c, hipStream_t s, const BODY &body) {
-    Accum &ac = c->accum;
-    if (s != c->stream) {
-        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
-        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
-    }
-    const int r = body();
-    if (r) return r;
-    if (s != c->stream) {
-        VRT_HIP(c, hipEventRecord(ac.read, s));
-        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
-    }
-    return VRT_OK;
-}
-
 // The HDR display pass on the accumulation: the existing resolve launch writes the float mean (exactly vrt_accum_resolve_hdr's
 // out_rgb) into the scratch, vrt_denoise_hdr filters it with the accumulation's id_dist image. Two launches on purpose: the display
 // pass stages every pixel about eight times across its tiles' halos, and 28 bytes of sums and count per staged tap against 12 of
@@ -162,6 +144,7 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
     if (!ac.added) VRT_HIP(c, hipEventCreateWithFlags(&ac.added, hipEventDisableTiming));
     if (!ac.read) VRT_HIP(c, hipEventCreateWithFlags(&ac.read, hipEventDisableTiming));
     ac.begun = true;
+    ++ac.epoch;   // the sums start: a guide state of earlier samples (vrt_guides.cpp) is void
     ac.width = width;
     ac.height = height;
     ac.first = first_sample;
@@ -179,6 +162,8 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
 }
 
 }  // namespace
+
+bool vrt_internal::accum_inputs_current(const vrt_ctx *c) { return same_inputs(c, c->accum); }
 
 // the step's samples go into the context's sums; an adaptive accumulation (acc.adaptive) passes its rule and state too, to the
 // kernels' adaptive forms, an HDR one (acc.hdr) its float64 sums, to the HDR object's
@@ -211,6 +196,9 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         vs.v[0].gen_z = 0.0f;
         vs.v[0].gen_fast = 0u;
     }
+    if (acc.guides)   // vrt_accum_guides: the samples' first hits into the guide state, none of the sums touched
+        return launch::accum_guides(src, v, a, vs, vrt::guides::Args{vrt::guides::state_of(ac.d_guides.get(), (size_t)ac.width * (size_t)ac.height), acc.first, acc.n},
+                                    l, grid, s);
     if (acc.frame_only)   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
         return (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? launch::accum_frame_hdr(mode, v, a, vs, hf, grid, s) : hipErrorInvalidValue;
     if (mode != VRT_MODE_FULL)   // one launch, the samples looped in the lanes
@@ -291,6 +279,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         if (ac.adaptive) VRT_HIP(c, hipMemsetAsync(ac.d_sq, 0, (size_t)ac.width * (size_t)ac.height * 8, c->stream));
         if (ac.hdr) VRT_HIP(c, hipMemsetAsync(ac.d_hsum, 0, (size_t)ac.width * (size_t)ac.height * 24, c->stream));   // +0.0
         take_inputs(c, ac);
+        ++ac.epoch;
         ac.total = 0;
         ac.pass1 = false;
         ac.frame = false;
@@ -375,7 +364,7 @@ int vrt_accum_resolve_device(vrt_ctx *c, void *d_rgba8, void *d_id_dist, void *d
     if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_device: the display pass needs d_rgba8");
     VRT_HIP(c, hipSetDevice(c->device));
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return joined(c, s, [&] { return resolve_into(c, d_rgba8, d_id_dist, d_shown_rgba8, s); });
+    return accum_joined(c, s, [&] { return resolve_into(c, d_rgba8, d_id_dist, d_shown_rgba8, s); });
 }
 
 int vrt_accum_keep_hdr(vrt_ctx *c, int enable) {
@@ -410,7 +399,7 @@ int vrt_accum_resolve_hdr_device(vrt_ctx *c, void *d_rgb, const vrt_tonemap *tm,
     if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_hdr_device: the display pass needs d_rgba8");
     VRT_HIP(c, hipSetDevice(c->device));
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return joined(c, s, [&] { return resolve_hdr_into(c, static_cast<float *>(d_rgb), tm, d_rgba8, d_shown_rgba8, s); });
+    return accum_joined(c, s, [&] { return resolve_hdr_into(c, static_cast<float *>(d_rgb), tm, d_rgba8, d_shown_rgba8, s); });
 }
 
 int vrt_accum_resolve_hdr_shown(vrt_ctx *c, const vrt_tonemap *tm, float *out_shown_rgb, uint8_t *out_shown_rgba8) {
@@ -438,7 +427,7 @@ int vrt_accum_resolve_hdr_shown_device(vrt_ctx *c, const vrt_tonemap *tm, void *
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     Accum &ac = c->accum;
     if ((r = ensure_float_image(c, ac.d_hmean, (size_t)ac.width * (size_t)ac.height))) return r;
-    return joined(c, s, [&] { return resolve_hdr_shown_into(c, tm, d_shown_rgb, d_shown_rgba8, s); });
+    return accum_joined(c, s, [&] { return resolve_hdr_shown_into(c, tm, d_shown_rgb, d_shown_rgba8, s); });
 }
 
 int vrt_accum_counts(vrt_ctx *c, uint32_t *out_counts) {

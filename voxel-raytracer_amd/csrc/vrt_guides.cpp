@@ -1,0 +1,172 @@
+// vrt_guides.cpp -- the guide planes (include/vrt.h vrt_accum_guides, vrt_guide_rays and their device forms): first-hit normal,
+// albedo, depth and coverage. For an accumulation: the call-order checks, the guide state (made at the first call, 40 bytes per
+// pixel), which samples it still lacks, their launch through the dispatcher -- enqueue() with an AccumStep whose `guides` is set, in
+// VRT_MODE_PRIMARY, so the views, the lens selection, the variant and the frame block are those of the accumulation's own primary
+// launches -- and the resolve. For ray batches: vrt_shade_rays's arguments and staging, one launch, no state. Neither touches the
+// accumulation's sums.
+#include "vrt_internal.h"
+#include "vrt_launch.h"
+
+using namespace vrt_internal;
+
+namespace {
+
+using Accum = vrt_ctx::Accum;
+
+int guide_state(vrt_ctx *c, const char *what) {
+    if (!c) return VRT_E_INVALID;
+    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
+    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
+    return VRT_OK;
+}
+
+// The guides of the samples the state does not hold yet, on the context's stream (which orders every use of the state)
+int catch_up(vrt_ctx *c, const char *what) {
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if (px > ac.guide_pixels) {
+        const int r = reserve_synced(c, {{&ac.d_guides, px * vrt::guides::kStateBytes}});
+        if (r) return r;
+        ac.guide_pixels = px;
+        ac.guide_total = 0;
+        ac.guide_epoch = 0;   // no epoch: cleared below
+    }
+    if (ac.guide_epoch != ac.epoch) {   // the sums started again since (or this is the first call): so does the state
+        VRT_HIP(c, hipMemsetAsync(ac.d_guides, 0, px * vrt::guides::kStateBytes, c->stream));   // +0.0, no hits
+        ac.guide_epoch = ac.epoch;
+        ac.guide_total = 0;
+    }
+    if (ac.guide_total >= ac.total) return VRT_OK;
+    // the missing samples are marched with the context's inputs, which must still be those of the samples in the sums (the next
+    // vrt_accum_add would restart): a camera, uniforms, tree or lens changed since the last add leaves nothing to march them with
+    if (!accum_inputs_current(c))
+        return vrt_fail(c, VRT_E_STATE, std::string(what) + ": camera, uniforms, tree or lens changed since the last vrt_accum_add");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
+    AccumStep step{ac.first + ac.guide_total, ac.total - ac.guide_total, (ac.flags & VRT_ACCUM_JITTER) != 0u, ac.lens[0], ac.lens[1]};
+    step.guides = true;
+    const int r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, VRT_MODE_PRIMARY, nullptr, nullptr, c->stream, nullptr, 1, &step);
+    if (r) {   // what the launch left in the state is unknown
+        ac.guide_epoch = 0;
+        return r;
+    }
+    ac.guide_total = ac.total;
+    return VRT_OK;
+}
+
+int resolve_into(vrt_ctx *c, float *d_normal, float *d_albedo, float *d_depth, float *d_coverage, hipStream_t s) {
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if (!d_normal && !d_albedo && !d_depth && !d_coverage) return VRT_OK;
+    const vrt::guides::Resolve q{vrt::guides::state_of(ac.d_guides.get(), px), d_normal, d_albedo, d_depth, d_coverage, ac.total, (uint32_t)px};
+    VRT_HIP(c, vrt::launch::guides_resolve(q, s));
+    return VRT_OK;
+}
+
+int check_rays(vrt_ctx *c, size_t n, const void *origins, int origin_stride, const void *dirs, bool any_out, const char *what) {
+    if (!c) return VRT_E_INVALID;
+    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no octree uploaded (call vrt_upload_octree first)");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
+    if (origin_stride != 0 && origin_stride != 3) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": origin_stride must be 0 or 3");
+    if (n > ((size_t)1 << 30)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": at most 2^30 rays per call");
+    if (!any_out) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": every output is null");
+    if (n > 0 && (!origins || !dirs)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null buffer");
+    return VRT_OK;
+}
+
+int guide_batch(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const float *d_dirs, int width, float *d_normal, float *d_albedo,
+                float *d_depth, uint8_t *d_hit, hipStream_t s) {
+    const int ra = ensure_analysis(c);
+    if (ra) return ra;
+    const Variant v = base_variant(c);   // the launch reads its traversal only
+    vrt::KArgs a;
+    vrt::ViewSet vs;
+    fill_ray_batch_args(c, n, width, a, vs);
+    vrt::guides::RayArgs q{d_origins, d_dirs, d_normal, d_albedo, d_depth, d_hit, (uint32_t)n, origin_stride, (uint32_t)width, 0u};
+    const uint32_t grid = vrt::rays::plan(q.n, q.width, q.tiles_x);
+    const hipError_t e = vrt::launch::guide_rays(v, a, vs, q, grid, s);
+    if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return VRT_OK;
+}
+
+inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+}  // namespace
+
+extern "C" {
+
+int vrt_accum_guides(vrt_ctx *c, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage) {
+    int r = guide_state(c, "vrt_accum_guides");
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if ((r = catch_up(c, "vrt_accum_guides"))) return r;
+    if (px * 9 * sizeof(float) > ac.d_gout.bytes() && (r = reserve_synced(c, {{&ac.d_gout, px * 9 * sizeof(float)}}))) return r;
+    float *g = ac.d_gout;
+    float *d_normal = out_normal ? g : nullptr, *d_albedo = out_albedo ? g + px * 3 : nullptr;
+    float *d_depth = out_depth ? g + px * 7 : nullptr, *d_coverage = out_coverage ? g + px * 8 : nullptr;
+    if ((r = resolve_into(c, d_normal, d_albedo, d_depth, d_coverage, c->stream))) return r;
+    if (out_normal) VRT_HIP(c, hipMemcpyAsync(out_normal, d_normal, px * 12, hipMemcpyDeviceToHost, c->stream));
+    if (out_albedo) VRT_HIP(c, hipMemcpyAsync(out_albedo, d_albedo, px * 16, hipMemcpyDeviceToHost, c->stream));
+    if (out_depth) VRT_HIP(c, hipMemcpyAsync(out_depth, d_depth, px * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_coverage) VRT_HIP(c, hipMemcpyAsync(out_coverage, d_coverage, px * 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_accum_guides_device(vrt_ctx *c, void *d_normal, void *d_albedo, void *d_depth, void *d_coverage, void *stream) {
+    int r = guide_state(c, "vrt_accum_guides_device");
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    if ((r = catch_up(c, "vrt_accum_guides_device"))) return r;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return accum_joined(c, s, [&] {
+        return resolve_into(c, static_cast<float *>(d_normal), static_cast<float *>(d_albedo), static_cast<float *>(d_depth),
+                            static_cast<float *>(d_coverage), s);
+    });
+}
+
+int vrt_guide_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride, const float *dirs, int width, float *out_normal,
+                   float *out_albedo, float *out_depth, uint8_t *out_hit) {
+    int r = check_rays(c, n, origins, origin_stride, dirs, out_normal || out_albedo || out_depth || out_hit, "vrt_guide_rays");
+    if (r) return r;
+    if (width < 1) return vrt_fail(c, VRT_E_INVALID, "vrt_guide_rays: width must be at least 1");
+    if (n == 0) return VRT_OK;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
+    const size_t nb = out_normal ? n * 12 : 0, ab = out_albedo ? n * 16 : 0, db = out_depth ? n * 4 : 0, hb = out_hit ? n : 0;
+    r = reserve_staging(c, c->d_rays, align256(o_bytes) + align256(d_bytes) + align256(nb) + align256(ab) + align256(db) + hb);
+    if (r) return r;
+    char *base = static_cast<char *>(c->d_rays.get());
+    float *d_o = reinterpret_cast<float *>(base);
+    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
+    char *out = base + align256(o_bytes) + align256(d_bytes);
+    float *d_n = out_normal ? reinterpret_cast<float *>(out) : nullptr;
+    float *d_a = out_albedo ? reinterpret_cast<float *>(out + align256(nb)) : nullptr;
+    float *d_z = out_depth ? reinterpret_cast<float *>(out + align256(nb) + align256(ab)) : nullptr;
+    uint8_t *d_h = out_hit ? reinterpret_cast<uint8_t *>(out + align256(nb) + align256(ab) + align256(db)) : nullptr;
+    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
+    r = guide_batch(c, n, d_o, origin_stride, d_d, width, d_n, d_a, d_z, d_h, c->stream);
+    if (r) return r;
+    if (d_n) VRT_HIP(c, hipMemcpyAsync(out_normal, d_n, nb, hipMemcpyDeviceToHost, c->stream));
+    if (d_a) VRT_HIP(c, hipMemcpyAsync(out_albedo, d_a, ab, hipMemcpyDeviceToHost, c->stream));
+    if (d_z) VRT_HIP(c, hipMemcpyAsync(out_depth, d_z, db, hipMemcpyDeviceToHost, c->stream));
+    if (d_h) VRT_HIP(c, hipMemcpyAsync(out_hit, d_h, hb, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_guide_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, void *d_normal,
+                          void *d_albedo, void *d_depth, void *d_hit, void *stream) {
+    const int r = check_rays(c, n, d_origins, origin_stride, d_dirs, d_normal || d_albedo || d_depth || d_hit, "vrt_guide_rays_device");
+    if (r) return r;
+    if (width < 1) return vrt_fail(c, VRT_E_INVALID, "vrt_guide_rays_device: width must be at least 1");
+    if (n == 0) return VRT_OK;
+    VRT_HIP(c, hipSetDevice(c->device));
+    return guide_batch(c, n, static_cast<const float *>(d_origins), origin_stride, static_cast<const float *>(d_dirs), width,
+                       static_cast<float *>(d_normal), static_cast<float *>(d_albedo), static_cast<float *>(d_depth),
+                       static_cast<uint8_t *>(d_hit), stream ? (hipStream_t)stream : c->stream);
+}
+
+}  // extern "C"

@@ -16,6 +16,8 @@
 //   vrt_rays.cpp       pathTrace for ray batches of the caller's (vrt_shade_rays): arguments without a camera, the staging buffers
 //   vrt_accum.cpp      progressive multi-sample accumulation (any mode, sub-pixel jitter): begin / add / resolve, the restart rule,
 //                      and the launches of one step of it (launch_accum_step, called by enqueue())
+//   vrt_guides.cpp     guide planes (vrt_accum_guides, vrt_guide_rays): the accumulation's guide state, the samples it still lacks,
+//                      their launch through enqueue() (an AccumStep with `guides`), the resolve; the stateless ray-batch form
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts; its shard and band
@@ -266,6 +268,13 @@ struct vrt_ctx {
         size_t hdr_pixels = 0;                   // what the two above were last sized for
         DevBuf<float> d_hrgb;                    // vrt_accum_resolve_hdr's float image on its way to the host
         DevBuf<float> d_hmean;                   // vrt_accum_resolve_hdr_shown*: the float mean the display pass reads, made at the first such call
+        // vrt_accum_guides (vrt_guides.cpp): the guide state, made at the first such call. `epoch` counts the starts of the sums (every
+        // begin and every restart of vrt_accum_add); the state holds the guides of the first guide_total samples of epoch guide_epoch
+        uint64_t epoch = 0, guide_epoch = 0;
+        uint32_t guide_total = 0;
+        DevBuf<void> d_guides;                   // vrt_guides.h State: 40 bytes per pixel
+        size_t guide_pixels = 0;                 // what it was last sized for
+        DevBuf<float> d_gout;                    // vrt_accum_guides' four planes on their way to the host (9 floats per pixel)
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
@@ -339,6 +348,8 @@ struct ProfSlot {
 // (hdr: an HDR accumulation, vrt_accum_keep_hdr; the kernels' HDR forms. frame_only, with hdr, modes 0 / 1 from the corner: no
 // sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
 // (paths: what selects the kernels of VRT_MODE_FULL, as the add that queues the step read it)
+// (guides, in VRT_MODE_PRIMARY: not the samples' colour into the sums but their first-hit guides into the accumulation's guide
+// state, vrt_guides.cpp; jitter, aperture and focus as above, nothing else of the step is read)
 // PathSetup: the settings that select the family of path tracer kernels of a VRT_MODE_FULL launch and fill its argument block
 // (vrt_launch.h select_paths()), as an accumulation step or a ray batch read them
 struct PathSetup {
@@ -361,6 +372,7 @@ struct AccumStep {
     float aperture = 0.0f, focus = 1.0f;
     bool adaptive = false, hdr = false, frame_only = false;
     PathSetup paths{};
+    bool guides = false;
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
@@ -381,6 +393,30 @@ constexpr long kSchedMaxDenoiseGroups = 2048;   // beyond ~8,000 tiles (16 round
 // the lens selection (as constructed when there is no lens). Points a.defer_rec, and pass 1's outputs, at the accumulation's buffers.
 hipError_t launch_accum_step(vrt_ctx::Accum &ac, vrt::KArgs &a, vrt::ViewSet &vs, const Variant &v, int mode, int grid, bool two_pass,
                              const vrt::LensSel &lsel, const AccumStep &acc, hipStream_t s);
+// does the next sample still belong to the samples in the sums? (what vrt_accum_add's restart rule compares)
+bool accum_inputs_current(const vrt_ctx *c);
+// A read of the accumulation on stream s, ordered against the context's: the samples were added on the context's stream, and later adds must not
+// overtake this read (nor, through `read`, the last call's use of the float mean). Nothing to do when s is the context's stream.
+template <class BODY>
+int accum_joined(vrt_ctx *c, hipStream_t s, const BODY &body) {
+    vrt_ctx::Accum &ac = c->accum;
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.added, c->stream));
+        VRT_HIP(c, hipStreamWaitEvent(s, ac.added, 0));
+    }
+    const int r = body();
+    if (r) return r;
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(ac.read, s));
+        VRT_HIP(c, hipStreamWaitEvent(c->stream, ac.read, 0));
+    }
+    return VRT_OK;
+}
+
+// vrt_rays.cpp
+// The kernel arguments of a caller's ray batch of n rays as an image of `width` (after ensure_analysis): the scene and light blocks
+// as a frame carries them, and nothing derived from an eye -- no first lookup, ray table, miss mask or tightened root
+void fill_ray_batch_args(const vrt_ctx *c, size_t n, int width, vrt::KArgs &a, vrt::ViewSet &vs);
 
 // vrt_raygen.cpp
 bool build_ray_table(const float *m, int W, int H, std::vector<float> &tab, float &z_out);

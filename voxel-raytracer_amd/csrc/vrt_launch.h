@@ -5,6 +5,7 @@
 #include "vrt_query.h"
 #include "vrt_accum.h"
 #include "vrt_rays.h"
+#include "vrt_guides.h"
 
 namespace vrt {
 namespace launch {
@@ -155,6 +156,15 @@ struct RayPaths {
 };
 hipError_t shade_rays_full(bool hdr, PathFamily fam, const PathArgs &pa, const Variant &v, const KArgs &a, const ViewSet &vs,
                            const rays::HdrArgs &q, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+
+// vrt_launch_guides.hip: the guide planes (vrt_guides.hip.h). accum_guides: samples q.first .. q.first + q.n - 1 of every pixel of a
+// whole frame into the guide state, for the ray source `src` (l: the lens of Source::kLens), `v`, `a`, `vs` and `grid` as the
+// dispatcher makes them for an accumulation's launch of VRT_MODE_PRIMARY. guides_resolve: the state -> the four float planes.
+// guide_rays: one march per ray of a caller's batch, its planes stored at once (grid = rays::plan()'s waves; `v`: the traversal only).
+hipError_t accum_guides(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const guides::Args &q, const accum::Lens &l,
+                        int grid, hipStream_t s);
+hipError_t guides_resolve(const guides::Resolve &q, hipStream_t s);
+hipError_t guide_rays(const Variant &v, const KArgs &a, const ViewSet &vs, const guides::RayArgs &q, uint32_t grid, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt

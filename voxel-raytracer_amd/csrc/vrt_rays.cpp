@@ -58,22 +58,10 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     const Variant v = base_variant(c);   // the launch reads its traversal only
     vrt::KArgs a;
     vrt::ViewSet vs;
-    std::memset(&a, 0, sizeof a);
-    std::memset(&vs, 0, sizeof vs);   // no first lookup (first_valid 0), no ray tables (gen_fast 0), no miss mask
-    a.n_views = 1;
-    fill_scene_args(c, a);
-    fill_light_args(c, a);
+    fill_ray_batch_args(c, n, width, a, vs);
     // the HDR forms hand the float itself out: below 2^-103 div_pi_inrange() may differ from x / PI in the last bit -- a colour term
     // that stores byte 0 either way, but a different float
     if (hdr) a.shade_fast = 0;
-    a.width = width;
-    a.height = (int)((n + (size_t)width - 1) / (size_t)width);
-    a.n_rows = a.height;
-    a.tile_rows = a.height;
-    a.row_mode = 1;
-    // the world is empty outside wide root 0: a property of the tree, applied by find() per ray (never to a first lookup); the
-    // tighter root is a property of a view's eye and is not taken
-    a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
     // the kernels of VRT_MODE_FULL by the context's settings as this call finds them, the emitter list made for the current tree
     PathSetup ps{c->path_depth, c->sun_disc, mode == VRT_MODE_FULL && c->emitter_sampling, c->emitter_importance, c->emitter_mis};
     if (ps.sampling) {
@@ -121,6 +109,22 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
 inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
 }  // namespace
+
+void vrt_internal::fill_ray_batch_args(const vrt_ctx *c, size_t n, int width, vrt::KArgs &a, vrt::ViewSet &vs) {
+    std::memset(&a, 0, sizeof a);
+    std::memset(&vs, 0, sizeof vs);   // no first lookup (first_valid 0), no ray tables (gen_fast 0), no miss mask
+    a.n_views = 1;
+    fill_scene_args(c, a);
+    fill_light_args(c, a);
+    a.width = width;
+    a.height = (int)((n + (size_t)width - 1) / (size_t)width);
+    a.n_rows = a.height;
+    a.tile_rows = a.height;
+    a.row_mode = 1;
+    // the world is empty outside wide root 0: a property of the tree, applied by find() per ray (never to a first lookup); the
+    // tighter root is a property of a view's eye and is not taken
+    a.root0_only = (a.n_roots == 1u && c->root0_only_on && vrt::content_only_in_root0(c->host_records, c->wide)) ? 1 : 0;
+}
 
 extern "C" {
 
