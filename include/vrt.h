@@ -843,6 +843,78 @@ int vrt_guide_rays(vrt_ctx *ctx, size_t n, const float *origins, int origin_stri
                    float *out_albedo, float *out_depth, uint8_t *out_hit);
 int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, void *d_normal,
                           void *d_albedo, void *d_depth, void *d_hit, void *stream);
+
+/* EXTENSION: the guided filter -- an edge-avoiding a-trous wavelet filter on FLOAT radiance whose edge weights come from the guide
+ * planes above. vrt_denoise_hdr averages inside one voxel ID, so where a voxel is a pixel wide it filters nothing; this filter
+ * averages across voxels that lie on one surface (same normal, same albedo, depth on the centre's own slope) and stops at the edges
+ * the planes show. Input: any [H][W][3] float image -- an HDR accumulation's mean, a ray batch's -- and the four planes in the shapes
+ * vrt_accum_guides_device writes: normal [H][W][3], albedo [H][W][4], depth [H][W], coverage [H][W].
+ *
+ * All arithmetic below is float32: every operation rounded on its own, no contraction. h(c) = min(max(0, c), 65504.0f) with the
+ * min / max conventions of vrt_accum_keep_hdr point 1 (NaN -> +0). p is a pixel, q a tap, s a level's step.
+ *  1. Inputs. Every colour float goes through h. Every guide float goes through g(v): NaN -> 0, anything else clamped to
+ *     [-65504, 65504]. A pixel is LIVE when g(coverage) > 0. A pixel that is not live yields h(c) per channel, at every `levels`, and
+ *     is never a tap: sky is never mixed into surfaces, nor surfaces into sky.
+ *  2. Modulation. With VRT_FILTER_DEMODULATE m_ch = max(albedo_ch + (1.0f - coverage), 1.0f / 255.0f) for ch in R, G, B (the albedo
+ *     plane is coverage-weighted, so the part of the pixel that saw sky counts as albedo 1); otherwise m_ch = 1. Level 0 reads
+ *     u = h(c) / m.
+ *  3. Depth slopes of the centre. gx = the smaller of |Z(x-1, y) - Z(x, y)| and |Z(x+1, y) - Z(x, y)| over those of the two
+ *     neighbours that are inside the image and live, 0 if there is none; gy likewise over (x, y-1) and (x, y+1). The one-sided
+ *     minimum keeps the slope of the surface the pixel lies on at a depth edge.
+ *  4. Level i = 0 .. levels-1, s = 1 << i. For a live p: sumw = 0, sum_ch = 0; then over oy = -2..2 (outer), ox = -2..2 (inner),
+ *     q = p + s * (ox, oy), skipped when outside the image or not live:
+ *       dn2 = (dx*dx + dy*dy) + dz*dz                   of the three normal differences q - p
+ *       da2 = (a0*a0 + a1*a1) + (a2*a2 + a3*a3)         of the four albedo differences (alpha separates glass from the opaque)
+ *       dzq = |Z_q - Z_p|
+ *       den = sigma_depth * ((gx * (float)(|ox|*s) + gy * (float)(|oy|*s)) + Z_p * (1.0f / 256.0f)) + 0x1p-20f
+ *       e   = (dn2 * kn + da2 * ka) + dzq / den
+ *       w   = (B[|oy|] * B[|ox|]) * det_expf(-e)        B = {3/8, 1/4, 1/16}; det_expf: the kernels' exp (Cephes-style, plain mul/add)
+ *       sumw = sumw + w;  sum_ch = sum_ch + w * u_q[ch]
+ *     and u'_p[ch] = sum_ch / sumw. kn = 1.0f / (sigma_normal * sigma_normal), ka = 1.0f / (sigma_albedo * sigma_albedo), computed
+ *     once on the host. The centre tap has e = +0 and w = 9/64 exactly, so sumw > 0. Levels ping-pong between two images: a level
+ *     never reads what it writes, and the sum order is the loop order above, whatever the launch shape.
+ *  5. Output. f = h(u * m); with levels == 0 that is h(h(c) / m * m), h(c) bit for bit without demodulation. out_rgb [H][W][3]
+ *     receives f, out_rgba8 [H][W][4] unorm8(tonemap(f)), alpha 255, with vrt_accum_resolve_hdr's two operators (tm == NULL:
+ *     VRT_TONEMAP_CLAMP, exposure 1). Either output may be NULL, not both.
+ * There is no colour or luminance term: without a per-pixel variance its width would be a guess. Depth is meant to be >= 0 (the guide
+ * planes' is); a negative depth is taken as it is and may make den <= 0, whose outcome the rules above still define (h ends it).
+ *
+ * vrt_filter_default    levels 1, VRT_FILTER_DEMODULATE, sigma_normal 1.0, sigma_albedo 0.05, sigma_depth 2.0: the best row
+ *                       of the quality sweep in profiles/filter_quality.txt (DESIGN.md section 3 "Guided filter").
+ * vrt_filter_hdr        DEVICE pointers, stream-ordered, stateless. f == NULL: vrt_filter_default. VRT_E_INVALID: a NULL input, both
+ *                       outputs NULL, d_out_rgb equal to any input, levels outside 0..VRT_FILTER_MAX_LEVELS, unknown flag bits, a
+ *                       sigma that is not finite or not > 0 (or so small that 1 / sigma^2 is not finite), a tone map
+ *                       vrt_accum_resolve_hdr refuses, a frame size vrt_denoise refuses. Scratch is the context's: 48 bytes per pixel
+ *                       of packed guides (levels >= 1) and 16 per pixel for each of the two level images (levels >= 2, >= 3),
+ *                       allocated by the first call that needs them, grown and never shrunk; a call that grows them waits for the
+ *                       device. Calls on different streams are ordered against each other, since they share the scratch.
+ * vrt_filter_hdr_host   the same through HOST buffers, synchronous, staged through 64 more bytes per pixel the context keeps.
+ * vrt_accum_resolve_hdr_filtered  the filter on an HDR accumulation: the input is its float mean -- exactly vrt_accum_resolve_hdr's
+ *                       out_rgb -- with the accumulation's own guide planes, which the call first brings up to date exactly as a
+ *                       vrt_accum_guides call would. HOST buffers (either may be NULL, not both), synchronous. Errors: VRT_E_STATE
+ *                       where vrt_accum_guides or vrt_accum_resolve_hdr return it (no begin, no sample, begun without HDR, inputs
+ *                       changed since the last add while guide samples are missing); VRT_E_INVALID as above. Mean, planes and outputs
+ *                       pass through 64 bytes per pixel that belong to the accumulation, allocated by the first such call.
+ * vrt_accum_resolve_hdr_filtered_device  the same into DEVICE buffers, enqueued on `stream` (NULL: the context's), ordered against the
+ *                       adds as vrt_accum_resolve_hdr_device is.
+ * The accumulation forms read and write no byte of the accumulation's sums: vrt_accum_resolve*, vrt_accum_resolve_hdr* and
+ * vrt_accum_guides* return the same bits with and without them. None of these calls takes a profiling slot or counts towards the
+ * stride. Not provided: variance- or luminance-guided weights (SVGF; they need per-pixel second moments of the HDR sums), temporal
+ * reprojection and motion vectors, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
+ * (an image-shaped batch can call vrt_filter_hdr with vrt_guide_rays_device's planes and a coverage plane made of its hit bytes). */
+#define VRT_FILTER_MAX_LEVELS 8
+#define VRT_FILTER_DEMODULATE 1u
+typedef struct vrt_filter { int32_t levels; uint32_t flags; float sigma_normal, sigma_albedo, sigma_depth; } vrt_filter;
+void vrt_filter_default(vrt_filter *f);
+int vrt_filter_hdr(vrt_ctx *ctx, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo,
+                   const void *d_depth, const void *d_coverage, const vrt_filter *f, const vrt_tonemap *tm, void *d_out_rgb,
+                   void *d_out_rgba8, void *stream);
+int vrt_filter_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, const float *normal, const float *albedo,
+                        const float *depth, const float *coverage, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb,
+                        uint8_t *out_rgba8);
+int vrt_accum_resolve_hdr_filtered(vrt_ctx *ctx, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8);
+int vrt_accum_resolve_hdr_filtered_device(vrt_ctx *ctx, const vrt_filter *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
+                                          void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

@@ -37,8 +37,27 @@ class Tonemap(C.Structure):
     _fields_ = [("op", C.c_int32), ("exposure", C.c_float)]
 
 
+class Filter(C.Structure):
+    """include/vrt.h vrt_filter"""
+    _fields_ = [("levels", C.c_int32), ("flags", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
+FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
+FILTER_DEMODULATE = 1    # include/vrt.h VRT_FILTER_DEMODULATE
+
+
 class VrtError(RuntimeError):
     pass
+
+
+def default_filter():
+    """vrt_filter_default as a dict: {"levels", "demodulate", "sigma_normal", "sigma_albedo", "sigma_depth"} -- the keyword
+    arguments Context.filter_hdr and Context.accum_resolve_hdr_filtered take. Needs no device."""
+    f = Filter()
+    hip_lib().vrt_filter_default(C.byref(f))
+    return {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE), "sigma_normal": float(f.sigma_normal),
+            "sigma_albedo": float(f.sigma_albedo), "sigma_depth": float(f.sigma_depth)}
 
 
 def build(targets=("../libvrt_hip.so", "../libvrt_hip_test.so", "../libvrt_host.so")):
@@ -314,6 +333,15 @@ def hip_lib():
                                      C.c_void_p, C.c_void_p]
         L.vrt_guide_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_filter_default.argtypes = [C.POINTER(Filter)]
+        L.vrt_filter_default.restype = None
+        L.vrt_filter_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p,
+                                                                                         C.c_void_p, C.c_void_p]
+        L.vrt_filter_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(Filter), C.POINTER(Tonemap),
+                                                                                              C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_hdr_filtered.argtypes = [C.c_void_p, C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_hdr_filtered_device.argtypes = [C.c_void_p, C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
+                                                            C.c_void_p]
         _hip = L
     return _hip
 
@@ -1256,6 +1284,80 @@ class Context:
         on `stream`"""
         tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
         self._chk(self._L.vrt_denoise_hdr(self._h, width, height, d_rgb, d_id, C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, stream))
+
+    @staticmethod
+    def _filter(filt):
+        """None (the NULL vrt_filter: vrt_filter_default) or a dict with any of default_filter()'s keys -> Filter or None"""
+        if filt is None:
+            return None
+        d = default_filter()
+        unknown = set(filt) - set(d)
+        if unknown:
+            raise ValueError(f"filter: unknown keys {sorted(unknown)}")
+        d.update(filt)
+        lv = d["levels"]
+        if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)) or not 0 <= lv <= FILTER_MAX_LEVELS:
+            raise ValueError(f"levels: expected an integer in [0, {FILTER_MAX_LEVELS}], got {lv!r}")
+        sig = []
+        for name in ("sigma_normal", "sigma_albedo", "sigma_depth"):
+            v = d[name]
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{name}: expected a number, got {v!r}")
+            x = float(v)
+            e = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
+            if not (np.isfinite(e) and e > 0.0):
+                raise ValueError(f"{name}: expected a float32 value finite and > 0, got {v!r}")
+            sig.append(float(e))
+        return Filter(int(lv), FILTER_DEMODULATE if d["demodulate"] else 0, *sig)
+
+    def filter_hdr(self, rgb, guides, filter=None, tonemap="clamp", exposure=1.0):
+        """The guided filter through host arrays (vrt_filter_hdr_host): an edge-avoiding a-trous filter on a float image rgb[H,W,3]
+        whose edge weights come from `guides` = {"normal": [H,W,3], "albedo": [H,W,4], "depth": [H,W], "coverage": [H,W]}, the
+        planes accum_guides returns. filter: None (vrt_filter_default) or a dict with any of default_filter()'s keys
+        -> (rgb float32[H,W,3]: the filtered floats; rgba8 uint8[H,W,4]: their tone-mapped bytes)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter(filter)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        n, a = np.ascontiguousarray(guides["normal"], np.float32), np.ascontiguousarray(guides["albedo"], np.float32)
+        z, cov = np.ascontiguousarray(guides["depth"], np.float32), np.ascontiguousarray(guides["coverage"], np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+        h, w = rgb.shape[:2]
+        if n.shape != (h, w, 3) or a.shape != (h, w, 4) or z.shape != (h, w) or cov.shape != (h, w):
+            raise ValueError(f"expected guides [H,W,3], [H,W,4], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {a.shape}, {z.shape}, {cov.shape}")
+        out = np.zeros_like(rgb)
+        out8 = np.zeros((h, w, 4), np.uint8)
+        self._chk(self._L.vrt_filter_hdr_host(self._h, w, h, rgb.ctypes.data, n.ctypes.data, a.ctypes.data, z.ctypes.data, cov.ctypes.data,
+                                              C.byref(f) if f else None, C.byref(tm) if tm else None, out.ctypes.data, out8.ctypes.data))
+        return out, out8
+
+    def filter_hdr_device(self, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_out_rgb, d_out_rgba, filter=None,
+                          tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_filter_hdr: DEVICE buffers (d_rgb: W*H x 3 floats; the planes as accum_guides_device writes them; d_out_rgb,
+        d_out_rgba: either may be None, not both), enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter(filter)
+        self._chk(self._L.vrt_filter_hdr(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, C.byref(f) if f else None,
+                                         C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, stream))
+
+    def accum_resolve_hdr_filtered(self, filter=None, tonemap="clamp", exposure=1.0):
+        """The guided filter on an HDR accumulation (vrt_accum_resolve_hdr_filtered): its float mean filtered with its own guide
+        planes -> (rgb float32[H,W,3]: the filtered mean; rgba8[H,W,4]: its tone-mapped bytes)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter(filter)
+        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
+        rgb = np.zeros((h, w, 3), np.float32)
+        rgba = np.zeros((h, w, 4), np.uint8)
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, rgb.ctypes.data,
+                                                         rgba.ctypes.data))
+        return rgb, rgba
+
+    def accum_resolve_hdr_filtered_device(self, d_rgb, d_rgba, filter=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_filtered_device: DEVICE buffers (either may be None, not both), enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter(filter)
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered_device(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, d_rgb, d_rgba,
+                                                                stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

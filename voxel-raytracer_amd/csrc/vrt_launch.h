@@ -6,6 +6,7 @@
 #include "vrt_accum.h"
 #include "vrt_rays.h"
 #include "vrt_guides.h"
+#include "vrt_filter.h"
 
 namespace vrt {
 namespace launch {
@@ -165,6 +166,13 @@ hipError_t accum_guides(accum::Source src, const Variant &v, const KArgs &a, con
                         int grid, hipStream_t s);
 hipError_t guides_resolve(const guides::Resolve &q, hipStream_t s);
 hipError_t guide_rays(const Variant &v, const KArgs &a, const ViewSet &vs, const guides::RayArgs &q, uint32_t grid, hipStream_t s);
+
+// vrt_launch_filter.hip: the guided filter (vrt_filter.hip.h), whole frames, one lane per pixel. filter_prepass: the caller's guide
+// planes -> the packed planes; filter_level: one level's taps at q.step (first: reads the caller's image; last: writes the outputs);
+// filter_through: levels == 0.
+hipError_t filter_prepass(const filter::Prepass &q, hipStream_t s);
+hipError_t filter_level(const filter::Level &q, bool first, bool last, hipStream_t s);
+hipError_t filter_through(const filter::Through &q, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt
