@@ -876,7 +876,8 @@ int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int ori
  *  5. Output. f = h(u * m); with levels == 0 that is h(h(c) / m * m), h(c) bit for bit without demodulation. out_rgb [H][W][3]
  *     receives f, out_rgba8 [H][W][4] unorm8(tonemap(f)), alpha 255, with vrt_accum_resolve_hdr's two operators (tm == NULL:
  *     VRT_TONEMAP_CLAMP, exposure 1). Either output may be NULL, not both.
- * There is no colour or luminance term: without a per-pixel variance its width would be a guess. Depth is meant to be >= 0 (the guide
+ * There is no colour or luminance term here: without a per-pixel variance its width would be a guess (vrt_filter_hdr_var below has
+ * both). Depth is meant to be >= 0 (the guide
  * planes' is); a negative depth is taken as it is and may make den <= 0, whose outcome the rules above still define (h ends it).
  *
  * vrt_filter_default    levels 1, VRT_FILTER_DEMODULATE, sigma_normal 1.0, sigma_albedo 0.05, sigma_depth 2.0: the best row
@@ -899,8 +900,8 @@ int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int ori
  *                       adds as vrt_accum_resolve_hdr_device is.
  * The accumulation forms read and write no byte of the accumulation's sums: vrt_accum_resolve*, vrt_accum_resolve_hdr* and
  * vrt_accum_guides* return the same bits with and without them. None of these calls takes a profiling slot or counts towards the
- * stride. Not provided: variance- or luminance-guided weights (SVGF; they need per-pixel second moments of the HDR sums), temporal
- * reprojection and motion vectors, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
+ * stride. Not provided: per-sample second moments of the HDR sums (vrt_filter_hdr_var's variance input is where they would arrive;
+ * until then the accumulation forms estimate the variance spatially), temporal reprojection and motion vectors, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
  * (an image-shaped batch can call vrt_filter_hdr with vrt_guide_rays_device's planes and a coverage plane made of its hit bytes). */
 #define VRT_FILTER_MAX_LEVELS 8
 #define VRT_FILTER_DEMODULATE 1u
@@ -915,6 +916,71 @@ int vrt_filter_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, c
 int vrt_accum_resolve_hdr_filtered(vrt_ctx *ctx, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8);
 int vrt_accum_resolve_hdr_filtered_device(vrt_ctx *ctx, const vrt_filter *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
                                           void *stream);
+/* EXTENSION: the variance-guided filter -- the guided filter above with an edge-stopping LUMINANCE term whose width is the pixel's own
+ * variance, and that variance carried through the levels (SVGF's rule). Shadow edges, penumbrae and the falloff around emitters lie on
+ * one surface -- one normal, one albedo, a smooth depth -- so no guide sees them and every level of vrt_filter_hdr past the first
+ * blurs them; here a tap whose luminance differs from the centre's by many standard deviations counts for little. The variance is
+ * the caller's plane d_variance [H][W] -- the variance of Y (V1) of the INPUT image at that pixel: of the mean, not of one sample --
+ * or, with d_variance == NULL, a spatial estimate from the image itself (SVGF's rule for pixels with a short history).
+ *
+ * All arithmetic is float32, every operation rounded on its own, nothing contracted. Points 1-3 of vrt_filter_hdr (inputs,
+ * modulation, depth slopes) hold unchanged; u is level 0's h(c) / m.
+ *  V1. Luminance. Y(u) = (0.2126f * u.x + 0.7152f * u.y) + 0.0722f * u.z.
+ *  V2. Initial variance v0_p of a live pixel. hv(x): NaN, -0 and everything negative -> +0, otherwise at most 65504.0f * 65504.0f.
+ *      Ym = Y(m) with point 2's m; without VRT_FILTER_DEMODULATE Ym is 1.0f and is not computed.
+ *      With a caller's plane: v0 = hv(var_p) / (Ym * Ym).
+ *      With d_variance == NULL: sw = s1 = s2 = 0, then over oy = -3..3 (outer), ox = -3..3 (inner), q = p + (ox, oy), skipped when
+ *      outside the image or not live:
+ *        e  = point 4's e with s = 1, that is den = sigma_depth * ((gx * (float)|ox| + gy * (float)|oy|) + Z_p * (1.0f / 256.0f)) + 0x1p-20f
+ *        w  = det_expf(-e)                               no B factor
+ *        l  = Y(u_q)
+ *        sw = sw + w;  s1 = s1 + w * l;  s2 = s2 + w * (l * l)
+ *      and m1 = s1 / sw, m2 = s2 / sw, v0 = max(0, m2 - m1 * m1) (NaN -> +0). The centre has w = 1, so sw > 0.
+ *  V3. Level i = 0 .. levels-1, s = 1 << i, live p. First the centre's smoothed variance: gs = gv = 0, then over oy = -1..1 (outer),
+ *      ox = -1..1 (inner), q = p + s * (ox, oy), skipped when outside the image or not live: G = 1/4 for the centre, 1/8 for the four
+ *      edges, 1/16 for the four corners; gs = gs + G; gv = gv + G * v_q. vbar = gv / gs and
+ *        sl = sigma_lum * sqrtf(vbar) + 0x1p-20f         the IEEE correctly rounded square root
+ *      The 3 x 3 runs on the level's own lattice, spacing s (SVGF's has spacing 1): that is what a level has at hand.
+ *      Then point 4's 25 taps in point 4's order, with
+ *        dl   = |Y(u_q) - Y(u_p)|
+ *        e    = ((dn2 * kn + da2 * ka) + dzq / den) + dl / sl
+ *        w    = (B[|oy|] * B[|ox|]) * det_expf(-e)
+ *        sumw = sumw + w;  sum_ch = sum_ch + w * u_q[ch];  sumv = sumv + (w * w) * v_q
+ *      and u'_p[ch] = sum_ch / sumw, v'_p = sumv / (sumw * sumw). The centre tap has e = +0 and w = 9/64.
+ *  V4. Output. The colours as in point 5. out_variance [H][W] receives hv(v * (Ym * Ym)) for a live pixel, v the variance after the last
+ *      level (v0 with levels == 0), and +0 for a pixel that is not live: it is the variance of Y of the OUTPUT image, a plane a
+ *      further call can take. (hv ends what a negative depth may make of v, as h ends the colours.)
+ * Two identities follow. On an image whose live pixels all carry one colour, without demodulation, dl = 0 at every tap of level 0,
+ * and of a later level where the levels before returned that colour exactly -- they do where every channel is 0 or a power of two
+ * (each w * c is exact, sum_ch is c times sumw, the quotient c). The colour outputs are then vrt_filter_hdr's bit for bit: up to one
+ * level for any colour, at every level count for such a colour. With levels == 0 the colour outputs are vrt_filter_hdr's at levels == 0.
+ *
+ * vrt_filter_var_default  levels 3, VRT_FILTER_DEMODULATE, sigma_normal 0.5, sigma_albedo 0.05, sigma_depth 2.0, sigma_lum 4.0: the best
+ *                       row of the quality sweep with the spatial estimate (profiles/filter_var_quality.txt, DESIGN.md section 3
+ *                       "Variance-guided filter").
+ * vrt_filter_hdr_var    DEVICE pointers, stream-ordered, stateless. f == NULL: vrt_filter_var_default. levels, flags, the guide sigmas,
+ *                       the tone map, the frame size, the stream ordering, and the scratch with its ownership and growth are
+ *                       vrt_filter_hdr's (levels == 0 with d_out_variance takes the packed guides too); sigma_lum must be finite
+ *                       and > 0. d_variance may be NULL (the spatial estimate). d_out_variance is an output only and may be NULL;
+ *                       one of the two colour outputs must not be. VRT_E_INVALID also where d_out_rgb or d_out_variance equals
+ *                       any input, d_variance included.
+ * vrt_filter_hdr_var_host  the same through HOST buffers, synchronous, staged through 72 bytes per pixel the context keeps.
+ * vrt_accum_resolve_hdr_filtered_var, _device  vrt_accum_resolve_hdr_filtered{,_device} with this filter: the same input, the same
+ *                       VRT_E_STATE rule, the guide state brought up to date as a vrt_accum_guides call would, 72 bytes per pixel
+ *                       that belong to the accumulation. The accumulation keeps no second moments yet: always the spatial estimate.
+ * These calls read and write no byte of the accumulation's sums, take no profiling slot and do not count towards the stride. */
+typedef struct vrt_filter_var { int32_t levels; uint32_t flags; float sigma_normal, sigma_albedo, sigma_depth, sigma_lum; } vrt_filter_var;
+void vrt_filter_var_default(vrt_filter_var *f);
+int vrt_filter_hdr_var(vrt_ctx *ctx, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo,
+                       const void *d_depth, const void *d_coverage, const void *d_variance, const vrt_filter_var *f, const vrt_tonemap *tm,
+                       void *d_out_rgb, void *d_out_rgba8, void *d_out_variance, void *stream);
+int vrt_filter_hdr_var_host(vrt_ctx *ctx, int width, int height, const float *rgb, const float *normal, const float *albedo,
+                            const float *depth, const float *coverage, const float *variance, const vrt_filter_var *f,
+                            const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8, float *out_variance);
+int vrt_accum_resolve_hdr_filtered_var(vrt_ctx *ctx, const vrt_filter_var *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8,
+                                       float *out_variance);
+int vrt_accum_resolve_hdr_filtered_var_device(vrt_ctx *ctx, const vrt_filter_var *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
+                                              void *d_variance_out, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

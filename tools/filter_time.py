@@ -8,6 +8,10 @@ as many warm-up calls (the windows' min and max are the run-to-run figure):
     to the row with one level fewer: what the level with step 1 << (levels - 1) adds to the call (for levels 1: prepass + first level).
   * the accumulation route, vrt_accum_resolve_hdr_filtered_device at the defaults and at 5 levels, against
     vrt_accum_resolve_hdr_shown_device (the ID-aware blur on the same mean) and vrt_accum_resolve_hdr_device (no filter).
+--var times the variance-guided filter instead (vrt_filter_hdr_var, all three outputs, sigmas: its defaults) for the same levels, with
+the spatial estimate and with a supplied plane (the input's own spatial estimate, taken from a levels-0 call), beside vrt_filter_hdr
+at the same level counts and the guide sigmas of the same defaults in the same session; and, at levels 0, the call with and without
+the variance output: the difference is the prepass and the variance kernel (what profiles/filter_var_rate.jsonl holds).
 --json appends one line per timing (what profiles/filter_rate.jsonl holds); --label NAME is recorded with each line (A/B builds)."""
 import argparse
 import json
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--scene", default="room", choices=sorted(SCENES))
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--levels", nargs="+", type=int, default=[0, 1, 2, 3, 4, 5])
+    ap.add_argument("--var", action="store_true", help="the variance-guided filter beside the guide-only one (see above)")
     args = ap.parse_args()
     V = vrt_import.vrt()
     import torch
@@ -83,6 +88,41 @@ def main():
             with open(args.json, "a") as f:
                 f.write(json.dumps(row) + "\n")
 
+    if args.var:
+        dv = V.default_filter_var()
+        guide = {k: v for k, v in dv.items() if k != "sigma_lum"}
+        outv = torch.zeros((H, W), dtype=torch.float32, device=dev)
+        plane = torch.zeros((H, W), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        ins = [mean.data_ptr()] + [p.data_ptr() for p in planes]
+        ctx.filter_hdr_var_device(W, H, *ins, None, out.data_ptr(), None, plane.data_ptr(), dict(dv, levels=0))
+        ctx.synchronize()
+        prev = {}
+        for levels in args.levels:
+            rows = (("vrt_filter_hdr", None, lambda: ctx.filter_hdr_device(W, H, *ins, out.data_ptr(), out8.data_ptr(), dict(guide, levels=levels),
+                                                                           "reinhard", 1.0, stream=side.cuda_stream)),
+                    ("vrt_filter_hdr_var", "spatial", lambda: ctx.filter_hdr_var_device(W, H, *ins, None, out.data_ptr(), out8.data_ptr(), outv.data_ptr(),
+                                                                                        dict(dv, levels=levels), "reinhard", 1.0, stream=side.cuda_stream)),
+                    ("vrt_filter_hdr_var", "plane", lambda: ctx.filter_hdr_var_device(W, H, *ins, plane.data_ptr(), out.data_ptr(), out8.data_ptr(),
+                                                                                      outv.data_ptr(), dict(dv, levels=levels), "reinhard", 1.0,
+                                                                                      stream=side.cuda_stream)))
+            if levels == 0:
+                rows += (("vrt_filter_hdr_var", "no variance output", lambda: ctx.filter_hdr_var_device(
+                    W, H, *ins, None, out.data_ptr(), out8.data_ptr(), None, dict(dv, levels=0), "reinhard", 1.0, stream=side.cuda_stream)),)
+            for name, source, call in rows:
+                med, ms = timed(call)
+                key = (name, source)
+                note(call=name, variance=source, levels=levels, demodulate=dv["demodulate"], ms_median=round(med, 5),
+                     ms_windows=[round(m, 5) for m in ms], level_ms=None if key not in prev else round(med - prev[key], 5))
+                prev[key] = med
+        for name, levels, call in (("vrt_accum_resolve_hdr_filtered_device", None, lambda: ctx.accum_resolve_hdr_filtered_device(
+                                        out.data_ptr(), out8.data_ptr(), guide, "reinhard", 1.0, stream=side.cuda_stream)),
+                                   ("vrt_accum_resolve_hdr_filtered_var_device", None, lambda: ctx.accum_resolve_hdr_filtered_var_device(
+                                        out.data_ptr(), out8.data_ptr(), outv.data_ptr(), None, "reinhard", 1.0, stream=side.cuda_stream))):
+            med, ms = timed(call)
+            note(call=name, levels=dv["levels"], demodulate=dv["demodulate"], ms_median=round(med, 5), ms_windows=[round(m, 5) for m in ms])
+        ctx.close()
+        return
     d = V.default_filter()
     for demod in (True, False):
         prev = None

@@ -43,6 +43,11 @@ class Filter(C.Structure):
                 ("sigma_depth", C.c_float)]
 
 
+class FilterVar(C.Structure):
+    """include/vrt.h vrt_filter_var"""
+    _fields_ = Filter._fields_ + [("sigma_lum", C.c_float)]
+
+
 FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
 FILTER_DEMODULATE = 1    # include/vrt.h VRT_FILTER_DEMODULATE
 
@@ -58,6 +63,15 @@ def default_filter():
     hip_lib().vrt_filter_default(C.byref(f))
     return {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE), "sigma_normal": float(f.sigma_normal),
             "sigma_albedo": float(f.sigma_albedo), "sigma_depth": float(f.sigma_depth)}
+
+
+def default_filter_var():
+    """vrt_filter_var_default as a dict: default_filter()'s keys and "sigma_lum" -- the keyword arguments Context.filter_hdr_var and
+    Context.accum_resolve_hdr_filtered_var take. Needs no device."""
+    f = FilterVar()
+    hip_lib().vrt_filter_var_default(C.byref(f))
+    return {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE), "sigma_normal": float(f.sigma_normal),
+            "sigma_albedo": float(f.sigma_albedo), "sigma_depth": float(f.sigma_depth), "sigma_lum": float(f.sigma_lum)}
 
 
 def build(targets=("../libvrt_hip.so", "../libvrt_hip_test.so", "../libvrt_host.so")):
@@ -342,6 +356,13 @@ def hip_lib():
         L.vrt_accum_resolve_hdr_filtered.argtypes = [C.c_void_p, C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr_filtered_device.argtypes = [C.c_void_p, C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
                                                             C.c_void_p]
+        L.vrt_filter_var_default.argtypes = [C.POINTER(FilterVar)]
+        L.vrt_filter_var_default.restype = None
+        L.vrt_filter_hdr_var.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 4
+        L.vrt_filter_hdr_var_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 3
+        L.vrt_accum_resolve_hdr_filtered_var.argtypes = [C.c_void_p, C.POINTER(FilterVar), C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vrt_accum_resolve_hdr_filtered_var_device.argtypes = [C.c_void_p, C.POINTER(FilterVar), C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p]
         _hip = L
     return _hip
 
@@ -1358,6 +1379,83 @@ class Context:
         f = self._filter(filter)
         self._chk(self._L.vrt_accum_resolve_hdr_filtered_device(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, d_rgb, d_rgba,
                                                                 stream))
+
+    @staticmethod
+    def _filter_var(filt):
+        """None (the NULL vrt_filter_var: vrt_filter_var_default) or a dict with any of default_filter_var()'s keys -> FilterVar or
+        None; the rules of _filter, for sigma_lum too"""
+        if filt is None:
+            return None
+        d = default_filter_var()
+        unknown = set(filt) - set(d)
+        if unknown:
+            raise ValueError(f"filter: unknown keys {sorted(unknown)}")
+        d.update(filt)
+        lum = d.pop("sigma_lum")
+        g = Context._filter(d)
+        try:
+            lum = Context._filter({"sigma_depth": lum}).sigma_depth   # the same rule as any sigma
+        except ValueError as e:
+            raise ValueError(str(e).replace("sigma_depth", "sigma_lum")) from None
+        return FilterVar(g.levels, g.flags, g.sigma_normal, g.sigma_albedo, g.sigma_depth, lum)
+
+    def filter_hdr_var(self, rgb, guides, variance=None, filter=None, tonemap="clamp", exposure=1.0):
+        """The variance-guided filter through host arrays (vrt_filter_hdr_var_host): filter_hdr with an edge-stopping luminance term
+        whose width is each pixel's variance. variance: [H,W], the variance of the luminance of rgb at each pixel, or None: the
+        filter estimates it spatially. filter: None (vrt_filter_var_default) or a dict with any of default_filter_var()'s keys
+        -> (rgb float32[H,W,3], rgba8 uint8[H,W,4], variance float32[H,W]: the filtered image's)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        n, a = np.ascontiguousarray(guides["normal"], np.float32), np.ascontiguousarray(guides["albedo"], np.float32)
+        z, cov = np.ascontiguousarray(guides["depth"], np.float32), np.ascontiguousarray(guides["coverage"], np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+        h, w = rgb.shape[:2]
+        if n.shape != (h, w, 3) or a.shape != (h, w, 4) or z.shape != (h, w) or cov.shape != (h, w):
+            raise ValueError(f"expected guides [H,W,3], [H,W,4], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {a.shape}, {z.shape}, {cov.shape}")
+        if variance is not None:
+            variance = np.ascontiguousarray(variance, np.float32)
+            if variance.shape != (h, w):
+                raise ValueError(f"expected variance[H,W] for H, W = {h}, {w}; got {variance.shape}")
+        out = np.zeros_like(rgb)
+        out8 = np.zeros((h, w, 4), np.uint8)
+        outv = np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_filter_hdr_var_host(self._h, w, h, rgb.ctypes.data, n.ctypes.data, a.ctypes.data, z.ctypes.data, cov.ctypes.data,
+                                                  variance.ctypes.data if variance is not None else None, C.byref(f) if f else None,
+                                                  C.byref(tm) if tm else None, out.ctypes.data, out8.ctypes.data, outv.ctypes.data))
+        return out, out8, outv
+
+    def filter_hdr_var_device(self, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance, d_out_rgb, d_out_rgba,
+                              d_out_variance, filter=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_filter_hdr_var: DEVICE buffers (filter_hdr_device's; d_variance: W*H floats or None; d_out_variance: W*H floats or
+        None; d_out_rgb, d_out_rgba: either may be None, not both), enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        self._chk(self._L.vrt_filter_hdr_var(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance,
+                                             C.byref(f) if f else None, C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, d_out_variance,
+                                             stream))
+
+    def accum_resolve_hdr_filtered_var(self, filter=None, tonemap="clamp", exposure=1.0):
+        """The variance-guided filter on an HDR accumulation (vrt_accum_resolve_hdr_filtered_var): its float mean filtered with its
+        own guide planes and a spatially estimated variance -> (rgb float32[H,W,3], rgba8[H,W,4], variance float32[H,W])."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
+        rgb = np.zeros((h, w, 3), np.float32)
+        rgba = np.zeros((h, w, 4), np.uint8)
+        var = np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered_var(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, rgb.ctypes.data,
+                                                             rgba.ctypes.data, var.ctypes.data))
+        return rgb, rgba, var
+
+    def accum_resolve_hdr_filtered_var_device(self, d_rgb, d_rgba, d_variance, filter=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_filtered_var_device: DEVICE buffers (d_rgb, d_rgba: either may be None, not both; d_variance may be
+        None), enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered_var_device(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, d_rgb,
+                                                                    d_rgba, d_variance, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

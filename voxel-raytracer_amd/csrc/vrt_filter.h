@@ -60,5 +60,23 @@ struct Through {
     float exposure;
 };
 
+// ---- the variance-guided filter (vrt_filter_var.hip.h, include/vrt.h vrt_filter_hdr_var) ----
+// The variance of a pixel's luminance rides in the words the guide-only filter leaves unused: the initial one (V2) in plane 2's .w,
+// a level's in its image's .w. No kernel loads or stages a word more than its guide-only form.
+
+// V2: the initial variance of every live pixel into plane 2's .w, after the prepass
+struct Variance {
+    Level l;                  // rgb, pack, width, height, kn, ka, sigma_depth, demodulate; the rest unused
+    float *pack_w;            // l.pack again, as floats: the kernel stores the one float, never the word
+    const float *variance;    // the caller's plane, or null: the spatial estimate
+    float *out_variance;      // levels == 0 only: the output plane (V4)
+};
+
+struct LevelVar {
+    Level l;                  // src / dst carry the variance in .w
+    float sigma_lum;
+    float *out_variance;      // the last level's; may be null
+};
+
 }  // namespace filter
 }  // namespace vrt

@@ -49,6 +49,9 @@ VRT_DEV float depth_slope(const Guides &g, size_t p, size_t stride, bool lo, boo
     return s;
 }
 
+// The two kernels that are no templates live in one object, vrt_launch_filter.o: vrt_launch_filter_var.hip, which shares the device
+// functions and launches these through vrt_launch.h, defines VRT_FILTER_NO_PLAIN_KERNELS
+#ifndef VRT_FILTER_NO_PLAIN_KERNELS
 __global__ __launch_bounds__(kBlockX *kBlockY) void filter_prepass_kernel(const Prepass q) {
     const int x = (int)(blockIdx.x * kBlockX + threadIdx.x), y = (int)(blockIdx.y * kBlockY + threadIdx.y);
     if (x >= q.width || y >= q.height) return;
@@ -67,19 +70,25 @@ __global__ __launch_bounds__(kBlockX *kBlockY) void filter_prepass_kernel(const 
                                  guide_value(q.g.albedo[p * 4 + 3]));
     q.pack[2 * px + p] = make_float4(gx, gy, cov, 0.0f);
 }
+#endif
 
-// w of one tap (point 4): n_* = normal and depth, a_* = albedo of the centre p and the tap q, slope = gx * |ox| s + gy * |oy| s,
-// zfloor = Z_p / 256, b = B[|oy|] * B[|ox|]
-VRT_DEV float tap_weight(const Level &q, const float4 &n_p, const float4 &a_p, const float4 &n_q, const float4 &a_q, float slope, float zfloor,
-                         float b) {
+// e of one tap from the guides (point 4): n_* = normal and depth, a_* = albedo of the centre p and the tap q,
+// slope = gx * |ox| s + gy * |oy| s, zfloor = Z_p / 256. The variance-guided kernels (vrt_filter_var.hip.h) add their term to it.
+VRT_DEV float tap_exponent(float kn, float ka, float sigma_depth, const float4 &n_p, const float4 &a_p, const float4 &n_q, const float4 &a_q,
+                           float slope, float zfloor) {
     const float dx = n_q.x - n_p.x, dy = n_q.y - n_p.y, dz = n_q.z - n_p.z;
     const float dn2 = (dx * dx + dy * dy) + dz * dz;
     const float a0 = a_q.x - a_p.x, a1 = a_q.y - a_p.y, a2 = a_q.z - a_p.z, a3 = a_q.w - a_p.w;
     const float da2 = (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
     const float dzq = __builtin_fabsf(n_q.w - n_p.w);
-    const float den = q.sigma_depth * (slope + zfloor) + 0x1p-20f;
-    const float e = (dn2 * q.kn + da2 * q.ka) + dzq / den;
-    return b * det_expf(-e);
+    const float den = sigma_depth * (slope + zfloor) + 0x1p-20f;
+    return (dn2 * kn + da2 * ka) + dzq / den;
+}
+
+// w of one tap (point 4): b = B[|oy|] * B[|ox|]
+VRT_DEV float tap_weight(const Level &q, const float4 &n_p, const float4 &a_p, const float4 &n_q, const float4 &a_q, float slope, float zfloor,
+                         float b) {
+    return b * det_expf(-tap_exponent(q.kn, q.ka, q.sigma_depth, n_p, a_p, n_q, a_q, slope, zfloor));
 }
 
 VRT_DEV float b3(int a) { return a == 0 ? 0.375f : (a == 1 ? 0.25f : 0.0625f); }
@@ -223,6 +232,7 @@ __global__ __launch_bounds__(kLatX *kLatY) void filter_level_lattice_kernel(cons
     finish_pixel<LAST>(q, p, sum, sumw, a_p, c_p.z);
 }
 
+#ifndef VRT_FILTER_NO_PLAIN_KERNELS
 __global__ __launch_bounds__(256) void filter_through_kernel(const Through q) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= q.pixels) return;
@@ -238,6 +248,7 @@ __global__ __launch_bounds__(256) void filter_through_kernel(const Through q) {
     }
     store_pixel(q.out_rgb, q.out_rgba, p, f, q.op, q.exposure);
 }
+#endif
 
 }  // namespace filter
 }  // namespace vrt

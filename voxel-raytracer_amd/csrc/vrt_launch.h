@@ -174,5 +174,10 @@ hipError_t filter_prepass(const filter::Prepass &q, hipStream_t s);
 hipError_t filter_level(const filter::Level &q, bool first, bool last, hipStream_t s);
 hipError_t filter_through(const filter::Through &q, hipStream_t s);
 
+// vrt_launch_filter_var.hip: the variance-guided filter (vrt_filter_var.hip.h) behind the same prepass. filter_variance: the initial
+// variance into the packed planes (q.variance null: the spatial estimate); filter_var_level: one level, as filter_level.
+hipError_t filter_variance(const filter::Variance &q, hipStream_t s);
+hipError_t filter_var_level(const filter::LevelVar &q, bool first, bool last, hipStream_t s);
+
 }  // namespace launch
 }  // namespace vrt
