@@ -1307,11 +1307,12 @@ class Context:
         self._chk(self._L.vrt_denoise_hdr(self._h, width, height, d_rgb, d_id, C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, stream))
 
     @staticmethod
-    def _filter(filt):
-        """None (the NULL vrt_filter: vrt_filter_default) or a dict with any of default_filter()'s keys -> Filter or None"""
+    def _filter_struct(filt, struct, defaults, sigmas):
+        """None (the NULL filter: the library's default) or a dict with any of the keys of defaults() -> struct(levels, flags,
+        *sigmas), every sigma named in `sigmas` a float32 value finite and > 0; ValueError otherwise"""
         if filt is None:
             return None
-        d = default_filter()
+        d = defaults()
         unknown = set(filt) - set(d)
         if unknown:
             raise ValueError(f"filter: unknown keys {sorted(unknown)}")
@@ -1320,7 +1321,7 @@ class Context:
         if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)) or not 0 <= lv <= FILTER_MAX_LEVELS:
             raise ValueError(f"levels: expected an integer in [0, {FILTER_MAX_LEVELS}], got {lv!r}")
         sig = []
-        for name in ("sigma_normal", "sigma_albedo", "sigma_depth"):
+        for name in sigmas:
             v = d[name]
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
                 raise ValueError(f"{name}: expected a number, got {v!r}")
@@ -1329,15 +1330,17 @@ class Context:
             if not (np.isfinite(e) and e > 0.0):
                 raise ValueError(f"{name}: expected a float32 value finite and > 0, got {v!r}")
             sig.append(float(e))
-        return Filter(int(lv), FILTER_DEMODULATE if d["demodulate"] else 0, *sig)
+        return struct(int(lv), FILTER_DEMODULATE if d["demodulate"] else 0, *sig)
 
-    def filter_hdr(self, rgb, guides, filter=None, tonemap="clamp", exposure=1.0):
-        """The guided filter through host arrays (vrt_filter_hdr_host): an edge-avoiding a-trous filter on a float image rgb[H,W,3]
-        whose edge weights come from `guides` = {"normal": [H,W,3], "albedo": [H,W,4], "depth": [H,W], "coverage": [H,W]}, the
-        planes accum_guides returns. filter: None (vrt_filter_default) or a dict with any of default_filter()'s keys
-        -> (rgb float32[H,W,3]: the filtered floats; rgba8 uint8[H,W,4]: their tone-mapped bytes)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter(filter)
+    @staticmethod
+    def _filter(filt):
+        """None (the NULL vrt_filter: vrt_filter_default) or a dict with any of default_filter()'s keys -> Filter or None"""
+        return Context._filter_struct(filt, Filter, default_filter, ("sigma_normal", "sigma_albedo", "sigma_depth"))
+
+    @staticmethod
+    def _filter_planes(rgb, guides):
+        """rgb[H,W,3] and the four guide planes as contiguous float32 arrays of matching shapes -> (rgb, normal, albedo, depth,
+        coverage, H, W); ValueError otherwise"""
         rgb = np.ascontiguousarray(rgb, np.float32)
         n, a = np.ascontiguousarray(guides["normal"], np.float32), np.ascontiguousarray(guides["albedo"], np.float32)
         z, cov = np.ascontiguousarray(guides["depth"], np.float32), np.ascontiguousarray(guides["coverage"], np.float32)
@@ -1346,6 +1349,16 @@ class Context:
         h, w = rgb.shape[:2]
         if n.shape != (h, w, 3) or a.shape != (h, w, 4) or z.shape != (h, w) or cov.shape != (h, w):
             raise ValueError(f"expected guides [H,W,3], [H,W,4], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {a.shape}, {z.shape}, {cov.shape}")
+        return rgb, n, a, z, cov, h, w
+
+    def filter_hdr(self, rgb, guides, filter=None, tonemap="clamp", exposure=1.0):
+        """The guided filter through host arrays (vrt_filter_hdr_host): an edge-avoiding a-trous filter on a float image rgb[H,W,3]
+        whose edge weights come from `guides` = {"normal": [H,W,3], "albedo": [H,W,4], "depth": [H,W], "coverage": [H,W]}, the
+        planes accum_guides returns. filter: None (vrt_filter_default) or a dict with any of default_filter()'s keys
+        -> (rgb float32[H,W,3]: the filtered floats; rgba8 uint8[H,W,4]: their tone-mapped bytes)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter(filter)
+        rgb, n, a, z, cov, h, w = self._filter_planes(rgb, guides)
         out = np.zeros_like(rgb)
         out8 = np.zeros((h, w, 4), np.uint8)
         self._chk(self._L.vrt_filter_hdr_host(self._h, w, h, rgb.ctypes.data, n.ctypes.data, a.ctypes.data, z.ctypes.data, cov.ctypes.data,
@@ -1384,20 +1397,7 @@ class Context:
     def _filter_var(filt):
         """None (the NULL vrt_filter_var: vrt_filter_var_default) or a dict with any of default_filter_var()'s keys -> FilterVar or
         None; the rules of _filter, for sigma_lum too"""
-        if filt is None:
-            return None
-        d = default_filter_var()
-        unknown = set(filt) - set(d)
-        if unknown:
-            raise ValueError(f"filter: unknown keys {sorted(unknown)}")
-        d.update(filt)
-        lum = d.pop("sigma_lum")
-        g = Context._filter(d)
-        try:
-            lum = Context._filter({"sigma_depth": lum}).sigma_depth   # the same rule as any sigma
-        except ValueError as e:
-            raise ValueError(str(e).replace("sigma_depth", "sigma_lum")) from None
-        return FilterVar(g.levels, g.flags, g.sigma_normal, g.sigma_albedo, g.sigma_depth, lum)
+        return Context._filter_struct(filt, FilterVar, default_filter_var, ("sigma_normal", "sigma_albedo", "sigma_depth", "sigma_lum"))
 
     def filter_hdr_var(self, rgb, guides, variance=None, filter=None, tonemap="clamp", exposure=1.0):
         """The variance-guided filter through host arrays (vrt_filter_hdr_var_host): filter_hdr with an edge-stopping luminance term
@@ -1406,14 +1406,7 @@ class Context:
         -> (rgb float32[H,W,3], rgba8 uint8[H,W,4], variance float32[H,W]: the filtered image's)."""
         tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
         f = self._filter_var(filter)
-        rgb = np.ascontiguousarray(rgb, np.float32)
-        n, a = np.ascontiguousarray(guides["normal"], np.float32), np.ascontiguousarray(guides["albedo"], np.float32)
-        z, cov = np.ascontiguousarray(guides["depth"], np.float32), np.ascontiguousarray(guides["coverage"], np.float32)
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
-        h, w = rgb.shape[:2]
-        if n.shape != (h, w, 3) or a.shape != (h, w, 4) or z.shape != (h, w) or cov.shape != (h, w):
-            raise ValueError(f"expected guides [H,W,3], [H,W,4], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {a.shape}, {z.shape}, {cov.shape}")
+        rgb, n, a, z, cov, h, w = self._filter_planes(rgb, guides)
         if variance is not None:
             variance = np.ascontiguousarray(variance, np.float32)
             if variance.shape != (h, w):

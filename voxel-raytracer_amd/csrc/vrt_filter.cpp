@@ -1,9 +1,10 @@
-// vrt_filter.cpp -- the guided filter (include/vrt.h vrt_filter_hdr and its host and accumulation forms): validation, the context's
-// scratch, the prepass and the level loop, and the route from an HDR accumulation -- its float mean (vrt_accum_resolve_hdr_device)
-// and its own guide planes (vrt_accum_guides_device, which brings the guide state up to date) into the accumulation's scratch, then
-// the stateless filter on them. The variance-guided forms (vrt_filter_hdr_var and its host and accumulation forms) follow the same
-// routes with the same scratch: the prepass, then the variance kernel, then their own level kernels. Host code; the kernels are
-// behind vrt_launch.h. Nothing here touches the accumulation's sums.
+// vrt_filter.cpp -- the guided filter and its variance-guided form (include/vrt.h vrt_filter_hdr, vrt_filter_hdr_var and their host
+// and accumulation forms). One route serves both (filter_frame): validation, the context's scratch, the prepass, the variance kernel
+// of the variance-guided form, the level loop. One helper stages host planes around it (filter_host), one brings an HDR
+// accumulation's float mean (vrt_accum_resolve_hdr_device) and its own guide planes (vrt_accum_guides_device, which brings the guide
+// state up to date) into the accumulation's scratch and runs it on them (filter_accum). The entry points are thin callers: the
+// guide-only ones pass no variance input, no variance output and no luminance width. Host code; the kernels are behind
+// vrt_launch.h. Nothing here touches the accumulation's sums.
 #include "vrt_internal.h"
 #include "vrt_launch.h"
 
@@ -14,7 +15,7 @@ using namespace vrt_internal;
 namespace {
 
 // Mean or caller's image, the four planes, the float output and the bytes: 3 + 3 + 4 + 1 + 1 + 3 + 1 words per pixel, the layout
-// of both staging blocks (the context's for vrt_filter_hdr_host, the accumulation's for its filtered resolve)
+// of both staging blocks (the context's for the host forms, the accumulation's for its filtered resolves)
 constexpr size_t kStageBytes = 64;
 // ... and, for the variance-guided forms, the variance plane in and out behind them: 2 more words
 constexpr size_t kStageVarBytes = 72;
@@ -28,42 +29,39 @@ Stage stage_of(float *base, size_t px) {
                  base + px * 16, base + px * 17};
 }
 
-struct Checked {
-    vrt_filter f;
+// The filter a call runs with, in one shape for both forms: the guide-only one has no sigma_lum (var false). kn, ka: check_filter's.
+struct Params {
+    vrt_filter_var f;
+    bool var;
     float kn, ka;
 };
+Params params_of(const vrt_filter *f) {   // NULL: vrt_filter_default
+    vrt_filter d;
+    vrt_filter_default(&d);
+    if (f) d = *f;
+    return Params{{d.levels, d.flags, d.sigma_normal, d.sigma_albedo, d.sigma_depth, 0.0f}, false, 0.0f, 0.0f};
+}
+Params params_of(const vrt_filter_var *f) {   // NULL: vrt_filter_var_default
+    Params k{{}, true, 0.0f, 0.0f};
+    if (f) k.f = *f;
+    else vrt_filter_var_default(&k.f);
+    return k;
+}
 
-// the filter a call runs with (NULL: the defaults), or VRT_E_INVALID in the name of `what`; needs no device
-int check_filter(vrt_ctx *c, const char *what, const vrt_filter *f, Checked &out) {
-    if (f) out.f = *f;
-    else vrt_filter_default(&out.f);
-    const vrt_filter &g = out.f;
+// VRT_E_INVALID in the name of `what` unless the call's filter is one the header allows; fills kn and ka. Needs no device.
+int check_filter(vrt_ctx *c, const char *what, Params &k) {
+    const vrt_filter_var &g = k.f;
     if (g.levels < 0 || g.levels > VRT_FILTER_MAX_LEVELS)
         return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": levels must be in 0..VRT_FILTER_MAX_LEVELS");
     if (g.flags & ~(uint32_t)VRT_FILTER_DEMODULATE) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown flags");
     for (const float sg : {g.sigma_normal, g.sigma_albedo, g.sigma_depth})
         if (!(sg > 0.0f) || !(sg <= 3.402823466e38f)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": every sigma must be finite and > 0");
-    out.kn = 1.0f / (g.sigma_normal * g.sigma_normal);
-    out.ka = 1.0f / (g.sigma_albedo * g.sigma_albedo);
-    if (!(out.kn <= 3.402823466e38f) || !(out.ka <= 3.402823466e38f))   // sigma * sigma went to 0: 0 * kn at the centre tap would be NaN
+    k.kn = 1.0f / (g.sigma_normal * g.sigma_normal);
+    k.ka = 1.0f / (g.sigma_albedo * g.sigma_albedo);
+    if (!(k.kn <= 3.402823466e38f) || !(k.ka <= 3.402823466e38f))   // sigma * sigma went to 0: 0 * kn at the centre tap would be NaN
         return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": sigma_normal or sigma_albedo too small (1 / sigma^2 is not finite)");
-    return VRT_OK;
-}
-
-struct CheckedVar {
-    vrt_filter_var f;
-    Checked k;
-};
-
-// the same for a vrt_filter_var (NULL: vrt_filter_var_default)
-int check_filter_var(vrt_ctx *c, const char *what, const vrt_filter_var *f, CheckedVar &out) {
-    if (f) out.f = *f;
-    else vrt_filter_var_default(&out.f);
-    const vrt_filter_var &g = out.f;
-    const vrt_filter guide{g.levels, g.flags, g.sigma_normal, g.sigma_albedo, g.sigma_depth};
-    const int r = check_filter(c, what, &guide, out.k);
-    if (r) return r;
-    if (!(g.sigma_lum > 0.0f) || !(g.sigma_lum <= 3.402823466e38f)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": every sigma must be finite and > 0");
+    if (k.var && (!(g.sigma_lum > 0.0f) || !(g.sigma_lum <= 3.402823466e38f)))
+        return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": every sigma must be finite and > 0");
     return VRT_OK;
 }
 
@@ -82,8 +80,9 @@ int ensure_level_scratch(vrt_ctx *c, size_t px, int levels) {
     return VRT_OK;
 }
 
-int ensure_stage(vrt_ctx *c, DevBuf<float> &buf, size_t px, size_t bytes_per_pixel = kStageBytes) {
-    return px * bytes_per_pixel <= buf.bytes() ? VRT_OK : reserve_synced(c, {{&buf, px * bytes_per_pixel}});
+int ensure_stage(vrt_ctx *c, DevBuf<float> &buf, size_t px, bool var) {
+    const size_t bytes = px * (var ? kStageVarBytes : kStageBytes);
+    return bytes <= buf.bytes() ? VRT_OK : reserve_synced(c, {{&buf, bytes}});
 }
 
 int check_outputs(vrt_ctx *c, const char *what, const void *out_rgb, const void *out_rgba8) {
@@ -91,37 +90,141 @@ int check_outputs(vrt_ctx *c, const char *what, const void *out_rgb, const void 
     return VRT_OK;
 }
 
-// the call-order checks of the accumulation forms: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
-int filtered_state(vrt_ctx *c, const char *what) {
-    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
-    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
-    if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
+// a frame's planes, in device memory or (filter_host) the caller's; variance and out_variance: the variance-guided form's, may be null
+struct Planes {
+    const void *rgb, *normal, *albedo, *depth, *coverage, *variance;
+    void *out_rgb, *out_rgba8, *out_variance;
+};
+
+// what every form checks of its arguments before anything else, in this order; k: filled by check_filter
+int check_call(vrt_ctx *c, const char *what, const Planes *io, void *out_rgb, void *out_rgba8, Params &k, const vrt_tonemap *tm, bool device) {
+    if (io && (!io->rgb || !io->normal || !io->albedo || !io->depth || !io->coverage)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null input");
+    int r = check_outputs(c, what, out_rgb, out_rgba8);
+    if (r) return r;
+    if (io && device)
+        for (const void *out : {static_cast<const void *>(io->out_rgb), static_cast<const void *>(io->out_variance)})
+            if (out && (out == io->rgb || out == io->normal || out == io->albedo || out == io->depth || out == io->coverage || out == io->variance))
+                return vrt_fail(c, VRT_E_INVALID,
+                                std::string(what) + (k.var ? ": d_out_rgb and d_out_variance must not alias an input" : ": d_out_rgb must not alias an input"));
+    if ((r = check_filter(c, what, k))) return r;
+    return check_tonemap(c, what, tm);
+}
+
+// The stateless filter on device planes, stream-ordered, in the name of `what`: vrt_filter_hdr with k.var false (d.variance and
+// d.out_variance null), else vrt_filter_hdr_var
+int filter_frame(vrt_ctx *c, const char *what, int width, int height, const Planes &d, Params k, const vrt_tonemap *tm, void *stream) {
+    int r = check_frame(c, width, height);
+    if (r) return r;
+    if ((r = check_call(c, what, &d, d.out_rgb, d.out_rgba8, k, tm, true))) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * (size_t)height;
+    const int levels = k.f.levels;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    float *const out_rgb = static_cast<float *>(d.out_rgb), *const out_variance = static_cast<float *>(d.out_variance);
+    uint32_t *const out_rgba = static_cast<uint32_t *>(d.out_rgba8);
+    const vrt::filter::Guides g{static_cast<const float *>(d.normal), static_cast<const float *>(d.albedo), static_cast<const float *>(d.depth),
+                                static_cast<const float *>(d.coverage)};
+    vrt::filter::LevelVar q{};
+    q.l.rgb = static_cast<const float *>(d.rgb);
+    q.l.width = width;
+    q.l.height = height;
+    q.l.kn = k.kn;
+    q.l.ka = k.ka;
+    q.l.sigma_depth = k.f.sigma_depth;
+    q.l.demodulate = (k.f.flags & VRT_FILTER_DEMODULATE) ? 1u : 0u;
+    q.l.op = tm ? tm->op : VRT_TONEMAP_CLAMP;
+    q.l.exposure = tm ? tm->exposure : 1.0f;
+    q.sigma_lum = k.f.sigma_lum;
+    if (levels == 0) {   // the colours are the same in both forms
+        const vrt::filter::Through t{q.l.rgb, g, out_rgb, out_rgba, (uint32_t)px, q.l.demodulate, q.l.op, q.l.exposure};
+        VRT_HIP(c, vrt::launch::filter_through(t, s));
+        if (!out_variance) return VRT_OK;   // else V2's variance is the output: scratch for one level, the prepass, the variance kernel
+    }
+    if ((r = ensure_level_scratch(c, px, levels ? levels : 1))) return r;
+    vrt_ctx::FilterScratch &fs = c->filter;
+    if (fs.used && fs.last != s) VRT_HIP(c, hipStreamWaitEvent(s, fs.done, 0));   // the scratch is still the last call's
+    VRT_HIP(c, vrt::launch::filter_prepass(vrt::filter::Prepass{g, fs.d_pack, width, height}, s));
+    q.l.pack = fs.d_pack;
+    if (k.var)
+        VRT_HIP(c, vrt::launch::filter_variance(vrt::filter::Variance{q.l, reinterpret_cast<float *>(fs.d_pack.get()),
+                                                                      static_cast<const float *>(d.variance), levels == 0 ? out_variance : nullptr},
+                                                s));
+    for (int i = 0; i < levels; ++i) {
+        const bool first = i == 0, last = i == levels - 1;
+        q.l.step = 1 << i;
+        q.l.src = first ? nullptr : ((i & 1) ? fs.d_ping.get() : fs.d_pong.get());   // level 0 writes ping, level 1 pong, ...
+        q.l.dst = last ? nullptr : ((i & 1) ? fs.d_pong.get() : fs.d_ping.get());
+        q.l.out_rgb = last ? out_rgb : nullptr;
+        q.l.out_rgba = last ? out_rgba : nullptr;
+        q.out_variance = last ? out_variance : nullptr;
+        if (k.var) VRT_HIP(c, vrt::launch::filter_level(q, first, last, s));
+        else VRT_HIP(c, vrt::launch::filter_level(q.l, first, last, s));
+    }
+    VRT_HIP(c, hipEventRecord(fs.done, s));
+    fs.last = s;
+    fs.used = true;
     return VRT_OK;
 }
 
-// mean and planes into the accumulation's stage and the filter on them, all on stream s; d_rgb / d_rgba: where the outputs go
-int filtered_into(vrt_ctx *c, const vrt_filter *f, const vrt_tonemap *tm, const Stage &st, void *d_rgb, void *d_rgba, hipStream_t s) {
-    vrt_ctx::Accum &ac = c->accum;
-    int r = vrt_accum_guides_device(c, st.normal, st.albedo, st.depth, st.coverage, s);   // brings the guide state up to date first
-    if (r) return r;
-    if ((r = vrt_accum_resolve_hdr_device(c, st.rgb, tm, nullptr, nullptr, s))) return r;
-    // the stage belongs to the accumulation, whose every use the context's stream orders: a caller's stream is joined back
-    return accum_joined(c, s, [&] {
-        return vrt_filter_hdr(c, ac.width, ac.height, st.rgb, st.normal, st.albedo, st.depth, st.coverage, f, tm, d_rgb, d_rgba, s);
-    });
+// the outputs the caller asked for, from a stage to the host on the context's stream, and the wait for them
+int download(vrt_ctx *c, const Stage &st, size_t px, void *out_rgb, void *out_rgba8, void *out_variance) {
+    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st.out_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
+    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st.out_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_variance) VRT_HIP(c, hipMemcpyAsync(out_variance, st.out_variance, px * 4, hipMemcpyDeviceToHost, c->stream));
+    VRT_HIP(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
 }
 
-// the same for the variance-guided filter; the accumulation has no variance of its own: the spatial estimate
-int filtered_into_var(vrt_ctx *c, const vrt_filter_var *f, const vrt_tonemap *tm, const Stage &st, void *d_rgb, void *d_rgba, void *d_variance,
-                      hipStream_t s) {
-    vrt_ctx::Accum &ac = c->accum;
-    int r = vrt_accum_guides_device(c, st.normal, st.albedo, st.depth, st.coverage, s);
+// the host forms: the caller's planes h through the context's staging block, on the context's stream
+int filter_host(vrt_ctx *c, const char *what, int width, int height, const Planes &h, Params k, const vrt_tonemap *tm) {
+    int r = check_frame(c, width, height);
     if (r) return r;
+    if ((r = check_call(c, what, &h, h.out_rgb, h.out_rgba8, k, tm, false))) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * (size_t)height;
+    if ((r = ensure_stage(c, c->filter.d_host, px, k.var))) return r;
+    const Stage st = stage_of(c->filter.d_host, px);
+    VRT_HIP(c, hipMemcpyAsync(st.rgb, h.rgb, px * 12, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(st.normal, h.normal, px * 12, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(st.albedo, h.albedo, px * 16, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(st.depth, h.depth, px * 4, hipMemcpyHostToDevice, c->stream));
+    VRT_HIP(c, hipMemcpyAsync(st.coverage, h.coverage, px * 4, hipMemcpyHostToDevice, c->stream));
+    if (h.variance) VRT_HIP(c, hipMemcpyAsync(st.variance, h.variance, px * 4, hipMemcpyHostToDevice, c->stream));
+    const Planes d{st.rgb, st.normal, st.albedo, st.depth, st.coverage, h.variance ? st.variance : nullptr, h.out_rgb ? st.out_rgb : nullptr,
+                   h.out_rgba8 ? st.out_rgba : nullptr, h.out_variance ? st.out_variance : nullptr};
+    if ((r = filter_frame(c, what, width, height, d, k, tm, nullptr))) return r;
+    return download(c, st, px, h.out_rgb, h.out_rgba8, h.out_variance);
+}
+
+// The accumulation forms: mean and planes into the accumulation's stage and the filter on them. to_host: the outputs are the caller's
+// host buffers, filled on the context's stream before the return; else device memory, written in the order of `stream`. The
+// accumulation has no variance of its own: the variance-guided form estimates it spatially.
+int filter_accum(vrt_ctx *c, const char *what, Params k, const vrt_tonemap *tm, bool to_host, void *out_rgb, void *out_rgba8, void *out_variance,
+                 void *stream) {
+    if (!c) return VRT_E_INVALID;
+    // the call-order checks: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
+    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
+    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
+    if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
+    int r = check_call(c, what, nullptr, out_rgb, out_rgba8, k, tm, false);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    vrt_ctx::Accum &ac = c->accum;
+    const size_t px = (size_t)ac.width * (size_t)ac.height;
+    if ((r = ensure_stage(c, ac.d_filter, px, k.var))) return r;
+    const Stage st = stage_of(ac.d_filter, px);
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if ((r = vrt_accum_guides_device(c, st.normal, st.albedo, st.depth, st.coverage, s))) return r;   // brings the guide state up to date first
     if ((r = vrt_accum_resolve_hdr_device(c, st.rgb, tm, nullptr, nullptr, s))) return r;
-    return accum_joined(c, s, [&] {
-        return vrt_filter_hdr_var(c, ac.width, ac.height, st.rgb, st.normal, st.albedo, st.depth, st.coverage, nullptr, f, tm, d_rgb, d_rgba,
-                                  d_variance, s);
-    });
+    Planes d{st.rgb, st.normal, st.albedo, st.depth, st.coverage, nullptr, out_rgb, out_rgba8, out_variance};
+    if (to_host) {
+        d.out_rgb = out_rgb ? st.out_rgb : nullptr;
+        d.out_rgba8 = out_rgba8 ? st.out_rgba : nullptr;
+        d.out_variance = out_variance ? st.out_variance : nullptr;
+    }
+    // the stage belongs to the accumulation, whose every use the context's stream orders: a caller's stream is joined back
+    if ((r = accum_joined(c, s, [&] { return filter_frame(c, what, ac.width, ac.height, d, k, tm, s); }))) return r;
+    return to_host ? download(c, st, px, out_rgb, out_rgba8, out_variance) : VRT_OK;
 }
 
 }  // namespace
@@ -137,125 +240,6 @@ void vrt_filter_default(vrt_filter *f) {
     f->sigma_depth = 2.0f;
 }
 
-int vrt_filter_hdr(vrt_ctx *c, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo, const void *d_depth,
-                   const void *d_coverage, const vrt_filter *f, const vrt_tonemap *tm, void *d_out_rgb, void *d_out_rgba8, void *stream) {
-    int r = check_frame(c, width, height);
-    if (r) return r;
-    if (!d_rgb || !d_normal || !d_albedo || !d_depth || !d_coverage) return vrt_fail(c, VRT_E_INVALID, "vrt_filter_hdr: null input");
-    if ((r = check_outputs(c, "vrt_filter_hdr", d_out_rgb, d_out_rgba8))) return r;
-    if (d_out_rgb && (d_out_rgb == d_rgb || d_out_rgb == d_normal || d_out_rgb == d_albedo || d_out_rgb == d_depth || d_out_rgb == d_coverage))
-        return vrt_fail(c, VRT_E_INVALID, "vrt_filter_hdr: d_out_rgb must not alias an input");
-    Checked k;
-    if ((r = check_filter(c, "vrt_filter_hdr", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_filter_hdr", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)width * (size_t)height;
-    const int levels = k.f.levels;
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint32_t demod = (k.f.flags & VRT_FILTER_DEMODULATE) ? 1u : 0u;
-    const int op = tm ? tm->op : VRT_TONEMAP_CLAMP;
-    const float exposure = tm ? tm->exposure : 1.0f;
-    const vrt::filter::Guides g{static_cast<const float *>(d_normal), static_cast<const float *>(d_albedo), static_cast<const float *>(d_depth),
-                                static_cast<const float *>(d_coverage)};
-    if (levels == 0) {
-        const vrt::filter::Through q{static_cast<const float *>(d_rgb), g, static_cast<float *>(d_out_rgb), static_cast<uint32_t *>(d_out_rgba8),
-                                     (uint32_t)px, demod, op, exposure};
-        VRT_HIP(c, vrt::launch::filter_through(q, s));
-        return VRT_OK;
-    }
-    if ((r = ensure_level_scratch(c, px, levels))) return r;
-    vrt_ctx::FilterScratch &fs = c->filter;
-    if (fs.used && fs.last != s) VRT_HIP(c, hipStreamWaitEvent(s, fs.done, 0));   // the scratch is still the last call's
-    VRT_HIP(c, vrt::launch::filter_prepass(vrt::filter::Prepass{g, fs.d_pack, width, height}, s));
-    vrt::filter::Level q{};
-    q.rgb = static_cast<const float *>(d_rgb);
-    q.pack = fs.d_pack;
-    q.width = width;
-    q.height = height;
-    q.kn = k.kn;
-    q.ka = k.ka;
-    q.sigma_depth = k.f.sigma_depth;
-    q.demodulate = demod;
-    q.op = op;
-    q.exposure = exposure;
-    for (int i = 0; i < levels; ++i) {
-        const bool first = i == 0, last = i == levels - 1;
-        q.step = 1 << i;
-        q.src = first ? nullptr : ((i & 1) ? fs.d_ping.get() : fs.d_pong.get());   // level 0 writes ping, level 1 pong, ...
-        q.dst = last ? nullptr : ((i & 1) ? fs.d_pong.get() : fs.d_ping.get());
-        q.out_rgb = last ? static_cast<float *>(d_out_rgb) : nullptr;
-        q.out_rgba = last ? static_cast<uint32_t *>(d_out_rgba8) : nullptr;
-        VRT_HIP(c, vrt::launch::filter_level(q, first, last, s));
-    }
-    VRT_HIP(c, hipEventRecord(fs.done, s));
-    fs.last = s;
-    fs.used = true;
-    return VRT_OK;
-}
-
-int vrt_filter_hdr_host(vrt_ctx *c, int width, int height, const float *rgb, const float *normal, const float *albedo, const float *depth,
-                        const float *coverage, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8) {
-    int r = check_frame(c, width, height);
-    if (r) return r;
-    if (!rgb || !normal || !albedo || !depth || !coverage) return vrt_fail(c, VRT_E_INVALID, "vrt_filter_hdr_host: null input");
-    if ((r = check_outputs(c, "vrt_filter_hdr_host", out_rgb, out_rgba8))) return r;
-    Checked k;
-    if ((r = check_filter(c, "vrt_filter_hdr_host", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_filter_hdr_host", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)width * (size_t)height;
-    if ((r = ensure_stage(c, c->filter.d_host, px))) return r;
-    const Stage st = stage_of(c->filter.d_host, px);
-    VRT_HIP(c, hipMemcpyAsync(st.rgb, rgb, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.normal, normal, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.albedo, albedo, px * 16, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.depth, depth, px * 4, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.coverage, coverage, px * 4, hipMemcpyHostToDevice, c->stream));
-    r = vrt_filter_hdr(c, width, height, st.rgb, st.normal, st.albedo, st.depth, st.coverage, &k.f, tm, out_rgb ? st.out_rgb : nullptr,
-                       out_rgba8 ? st.out_rgba : nullptr, nullptr);
-    if (r) return r;
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st.out_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st.out_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
-}
-
-int vrt_accum_resolve_hdr_filtered(vrt_ctx *c, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8) {
-    if (!c) return VRT_E_INVALID;
-    int r = filtered_state(c, "vrt_accum_resolve_hdr_filtered");
-    if (r) return r;
-    if ((r = check_outputs(c, "vrt_accum_resolve_hdr_filtered", out_rgb, out_rgba8))) return r;
-    Checked k;
-    if ((r = check_filter(c, "vrt_accum_resolve_hdr_filtered", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_accum_resolve_hdr_filtered", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    vrt_ctx::Accum &ac = c->accum;
-    const size_t px = (size_t)ac.width * (size_t)ac.height;
-    if ((r = ensure_stage(c, ac.d_filter, px))) return r;
-    const Stage st = stage_of(ac.d_filter, px);
-    if ((r = filtered_into(c, &k.f, tm, st, out_rgb ? st.out_rgb : nullptr, out_rgba8 ? st.out_rgba : nullptr, c->stream))) return r;
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st.out_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st.out_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
-}
-
-int vrt_accum_resolve_hdr_filtered_device(vrt_ctx *c, const vrt_filter *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8, void *stream) {
-    if (!c) return VRT_E_INVALID;
-    int r = filtered_state(c, "vrt_accum_resolve_hdr_filtered_device");
-    if (r) return r;
-    if ((r = check_outputs(c, "vrt_accum_resolve_hdr_filtered_device", d_rgb, d_rgba8))) return r;
-    Checked k;
-    if ((r = check_filter(c, "vrt_accum_resolve_hdr_filtered_device", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_accum_resolve_hdr_filtered_device", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    vrt_ctx::Accum &ac = c->accum;
-    const size_t px = (size_t)ac.width * (size_t)ac.height;
-    if ((r = ensure_stage(c, ac.d_filter, px))) return r;
-    return filtered_into(c, &k.f, tm, stage_of(ac.d_filter, px), d_rgb, d_rgba8, stream ? (hipStream_t)stream : c->stream);
-}
-
-// ---- the variance-guided forms (include/vrt.h vrt_filter_hdr_var, V1-V4) ----
 void vrt_filter_var_default(vrt_filter_var *f) {
     if (!f) return;
     f->levels = 3;
@@ -266,137 +250,48 @@ void vrt_filter_var_default(vrt_filter_var *f) {
     f->sigma_lum = 4.0f;
 }
 
+int vrt_filter_hdr(vrt_ctx *c, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo, const void *d_depth,
+                   const void *d_coverage, const vrt_filter *f, const vrt_tonemap *tm, void *d_out_rgb, void *d_out_rgba8, void *stream) {
+    const Planes d{d_rgb, d_normal, d_albedo, d_depth, d_coverage, nullptr, d_out_rgb, d_out_rgba8, nullptr};
+    return filter_frame(c, "vrt_filter_hdr", width, height, d, params_of(f), tm, stream);
+}
+
 int vrt_filter_hdr_var(vrt_ctx *c, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo, const void *d_depth,
                        const void *d_coverage, const void *d_variance, const vrt_filter_var *f, const vrt_tonemap *tm, void *d_out_rgb,
                        void *d_out_rgba8, void *d_out_variance, void *stream) {
-    int r = check_frame(c, width, height);
-    if (r) return r;
-    if (!d_rgb || !d_normal || !d_albedo || !d_depth || !d_coverage) return vrt_fail(c, VRT_E_INVALID, "vrt_filter_hdr_var: null input");
-    if ((r = check_outputs(c, "vrt_filter_hdr_var", d_out_rgb, d_out_rgba8))) return r;
-    for (const void *out : {static_cast<const void *>(d_out_rgb), static_cast<const void *>(d_out_variance)})
-        if (out && (out == d_rgb || out == d_normal || out == d_albedo || out == d_depth || out == d_coverage || out == d_variance))
-            return vrt_fail(c, VRT_E_INVALID, "vrt_filter_hdr_var: d_out_rgb and d_out_variance must not alias an input");
-    CheckedVar k;
-    if ((r = check_filter_var(c, "vrt_filter_hdr_var", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_filter_hdr_var", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)width * (size_t)height;
-    const int levels = k.f.levels;
-    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint32_t demod = (k.f.flags & VRT_FILTER_DEMODULATE) ? 1u : 0u;
-    const int op = tm ? tm->op : VRT_TONEMAP_CLAMP;
-    const float exposure = tm ? tm->exposure : 1.0f;
-    const vrt::filter::Guides g{static_cast<const float *>(d_normal), static_cast<const float *>(d_albedo), static_cast<const float *>(d_depth),
-                                static_cast<const float *>(d_coverage)};
-    if (levels == 0) {   // the colours are vrt_filter_hdr's (the second identity)
-        const vrt::filter::Through q{static_cast<const float *>(d_rgb), g, static_cast<float *>(d_out_rgb), static_cast<uint32_t *>(d_out_rgba8),
-                                     (uint32_t)px, demod, op, exposure};
-        VRT_HIP(c, vrt::launch::filter_through(q, s));
-        if (!d_out_variance) return VRT_OK;
-    }
-    if ((r = ensure_level_scratch(c, px, levels ? levels : 1))) return r;
-    vrt_ctx::FilterScratch &fs = c->filter;
-    if (fs.used && fs.last != s) VRT_HIP(c, hipStreamWaitEvent(s, fs.done, 0));   // the scratch is still the last call's
-    VRT_HIP(c, vrt::launch::filter_prepass(vrt::filter::Prepass{g, fs.d_pack, width, height}, s));
-    vrt::filter::LevelVar q{};
-    q.l.rgb = static_cast<const float *>(d_rgb);
-    q.l.pack = fs.d_pack;
-    q.l.width = width;
-    q.l.height = height;
-    q.l.kn = k.k.kn;
-    q.l.ka = k.k.ka;
-    q.l.sigma_depth = k.f.sigma_depth;
-    q.l.demodulate = demod;
-    q.l.op = op;
-    q.l.exposure = exposure;
-    q.sigma_lum = k.f.sigma_lum;
-    VRT_HIP(c, vrt::launch::filter_variance(vrt::filter::Variance{q.l, reinterpret_cast<float *>(fs.d_pack.get()), static_cast<const float *>(d_variance),
-                                                                  levels == 0 ? static_cast<float *>(d_out_variance) : nullptr},
-                                            s));
-    for (int i = 0; i < levels; ++i) {
-        const bool first = i == 0, last = i == levels - 1;
-        q.l.step = 1 << i;
-        q.l.src = first ? nullptr : ((i & 1) ? fs.d_ping.get() : fs.d_pong.get());   // level 0 writes ping, level 1 pong, ...
-        q.l.dst = last ? nullptr : ((i & 1) ? fs.d_pong.get() : fs.d_ping.get());
-        q.l.out_rgb = last ? static_cast<float *>(d_out_rgb) : nullptr;
-        q.l.out_rgba = last ? static_cast<uint32_t *>(d_out_rgba8) : nullptr;
-        q.out_variance = last ? static_cast<float *>(d_out_variance) : nullptr;
-        VRT_HIP(c, vrt::launch::filter_var_level(q, first, last, s));
-    }
-    VRT_HIP(c, hipEventRecord(fs.done, s));
-    fs.last = s;
-    fs.used = true;
-    return VRT_OK;
+    const Planes d{d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance, d_out_rgb, d_out_rgba8, d_out_variance};
+    return filter_frame(c, "vrt_filter_hdr_var", width, height, d, params_of(f), tm, stream);
+}
+
+int vrt_filter_hdr_host(vrt_ctx *c, int width, int height, const float *rgb, const float *normal, const float *albedo, const float *depth,
+                        const float *coverage, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8) {
+    const Planes h{rgb, normal, albedo, depth, coverage, nullptr, out_rgb, out_rgba8, nullptr};
+    return filter_host(c, "vrt_filter_hdr_host", width, height, h, params_of(f), tm);
 }
 
 int vrt_filter_hdr_var_host(vrt_ctx *c, int width, int height, const float *rgb, const float *normal, const float *albedo, const float *depth,
                             const float *coverage, const float *variance, const vrt_filter_var *f, const vrt_tonemap *tm, float *out_rgb,
                             uint8_t *out_rgba8, float *out_variance) {
-    int r = check_frame(c, width, height);
-    if (r) return r;
-    if (!rgb || !normal || !albedo || !depth || !coverage) return vrt_fail(c, VRT_E_INVALID, "vrt_filter_hdr_var_host: null input");
-    if ((r = check_outputs(c, "vrt_filter_hdr_var_host", out_rgb, out_rgba8))) return r;
-    CheckedVar k;
-    if ((r = check_filter_var(c, "vrt_filter_hdr_var_host", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_filter_hdr_var_host", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    const size_t px = (size_t)width * (size_t)height;
-    if ((r = ensure_stage(c, c->filter.d_host, px, kStageVarBytes))) return r;
-    const Stage st = stage_of(c->filter.d_host, px);
-    VRT_HIP(c, hipMemcpyAsync(st.rgb, rgb, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.normal, normal, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.albedo, albedo, px * 16, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.depth, depth, px * 4, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.coverage, coverage, px * 4, hipMemcpyHostToDevice, c->stream));
-    if (variance) VRT_HIP(c, hipMemcpyAsync(st.variance, variance, px * 4, hipMemcpyHostToDevice, c->stream));
-    r = vrt_filter_hdr_var(c, width, height, st.rgb, st.normal, st.albedo, st.depth, st.coverage, variance ? st.variance : nullptr, &k.f, tm,
-                           out_rgb ? st.out_rgb : nullptr, out_rgba8 ? st.out_rgba : nullptr, out_variance ? st.out_variance : nullptr, nullptr);
-    if (r) return r;
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st.out_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st.out_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) VRT_HIP(c, hipMemcpyAsync(out_variance, st.out_variance, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    const Planes h{rgb, normal, albedo, depth, coverage, variance, out_rgb, out_rgba8, out_variance};
+    return filter_host(c, "vrt_filter_hdr_var_host", width, height, h, params_of(f), tm);
+}
+
+int vrt_accum_resolve_hdr_filtered(vrt_ctx *c, const vrt_filter *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8) {
+    return filter_accum(c, "vrt_accum_resolve_hdr_filtered", params_of(f), tm, true, out_rgb, out_rgba8, nullptr, nullptr);
+}
+
+int vrt_accum_resolve_hdr_filtered_device(vrt_ctx *c, const vrt_filter *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8, void *stream) {
+    return filter_accum(c, "vrt_accum_resolve_hdr_filtered_device", params_of(f), tm, false, d_rgb, d_rgba8, nullptr, stream);
 }
 
 int vrt_accum_resolve_hdr_filtered_var(vrt_ctx *c, const vrt_filter_var *f, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8,
                                        float *out_variance) {
-    if (!c) return VRT_E_INVALID;
-    int r = filtered_state(c, "vrt_accum_resolve_hdr_filtered_var");
-    if (r) return r;
-    if ((r = check_outputs(c, "vrt_accum_resolve_hdr_filtered_var", out_rgb, out_rgba8))) return r;
-    CheckedVar k;
-    if ((r = check_filter_var(c, "vrt_accum_resolve_hdr_filtered_var", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_accum_resolve_hdr_filtered_var", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    vrt_ctx::Accum &ac = c->accum;
-    const size_t px = (size_t)ac.width * (size_t)ac.height;
-    if ((r = ensure_stage(c, ac.d_filter, px, kStageVarBytes))) return r;
-    const Stage st = stage_of(ac.d_filter, px);
-    if ((r = filtered_into_var(c, &k.f, tm, st, out_rgb ? st.out_rgb : nullptr, out_rgba8 ? st.out_rgba : nullptr,
-                               out_variance ? st.out_variance : nullptr, c->stream)))
-        return r;
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st.out_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st.out_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) VRT_HIP(c, hipMemcpyAsync(out_variance, st.out_variance, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    return filter_accum(c, "vrt_accum_resolve_hdr_filtered_var", params_of(f), tm, true, out_rgb, out_rgba8, out_variance, nullptr);
 }
 
 int vrt_accum_resolve_hdr_filtered_var_device(vrt_ctx *c, const vrt_filter_var *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
                                               void *d_variance_out, void *stream) {
-    if (!c) return VRT_E_INVALID;
-    int r = filtered_state(c, "vrt_accum_resolve_hdr_filtered_var_device");
-    if (r) return r;
-    if ((r = check_outputs(c, "vrt_accum_resolve_hdr_filtered_var_device", d_rgb, d_rgba8))) return r;
-    CheckedVar k;
-    if ((r = check_filter_var(c, "vrt_accum_resolve_hdr_filtered_var_device", f, k))) return r;
-    if ((r = check_tonemap(c, "vrt_accum_resolve_hdr_filtered_var_device", tm))) return r;
-    VRT_HIP(c, hipSetDevice(c->device));
-    vrt_ctx::Accum &ac = c->accum;
-    const size_t px = (size_t)ac.width * (size_t)ac.height;
-    if ((r = ensure_stage(c, ac.d_filter, px, kStageVarBytes))) return r;
-    return filtered_into_var(c, &k.f, tm, stage_of(ac.d_filter, px), d_rgb, d_rgba8, d_variance_out, stream ? (hipStream_t)stream : c->stream);
+    return filter_accum(c, "vrt_accum_resolve_hdr_filtered_var_device", params_of(f), tm, false, d_rgb, d_rgba8, d_variance_out, stream);
 }
 
 }  // extern "C"

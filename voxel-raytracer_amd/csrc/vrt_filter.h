@@ -1,5 +1,5 @@
-// vrt_filter.h -- the arguments of the guided filter's kernels (vrt_filter.hip.h, include/vrt.h vrt_filter_hdr), shared by the host
-// side (vrt_filter.cpp) and the launch file (vrt_launch_filter.hip).
+// vrt_filter.h -- the arguments of the guided filter's kernels (vrt_filter.hip.h, include/vrt.h vrt_filter_hdr and
+// vrt_filter_hdr_var), shared by the host side (vrt_filter.cpp) and the launch file (vrt_launch_filter.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -60,7 +60,7 @@ struct Through {
     float exposure;
 };
 
-// ---- the variance-guided filter (vrt_filter_var.hip.h, include/vrt.h vrt_filter_hdr_var) ----
+// ---- the variance-guided form (include/vrt.h vrt_filter_hdr_var) ----
 // The variance of a pixel's luminance rides in the words the guide-only filter leaves unused: the initial one (V2) in plane 2's .w,
 // a level's in its image's .w. No kernel loads or stages a word more than its guide-only form.
 
@@ -77,6 +77,10 @@ struct LevelVar {
     float sigma_lum;
     float *out_variance;      // the last level's; may be null
 };
+
+// the guide-only arguments of either level struct
+__host__ __device__ inline const Level &level_of(const Level &q) { return q; }
+__host__ __device__ inline const Level &level_of(const LevelVar &q) { return q.l; }
 
 }  // namespace filter
 }  // namespace vrt

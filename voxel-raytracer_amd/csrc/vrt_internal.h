@@ -119,9 +119,9 @@ struct vrt_ctx {
     // ... and the two float images of vrt_denoise_hdr_host (vrt_display.cpp)
     DevBuf<void> d_hdr_in, d_hdr_out;
     size_t hdr_scratch_pixels = 0;
-    // the guided filter's scratch (vrt_filter.cpp): the packed guides and the two level images of vrt_filter_hdr, shared by its calls
-    // on any stream -- `done` is recorded after each call's launches and awaited by a call on another stream -- and the staging of
-    // vrt_filter_hdr_host (inputs and outputs, 64 bytes per pixel)
+    // the guided filter's scratch (vrt_filter.cpp): the packed guides and the two level images of vrt_filter_hdr and vrt_filter_hdr_var,
+    // shared by their calls on any stream -- `done` is recorded after each call's launches and awaited by a call on another stream --
+    // and the staging of their host forms (inputs and outputs, 64 bytes per pixel, 72 with the variance planes)
     struct FilterScratch {
         DevBuf<float4> d_pack, d_ping, d_pong;
         hipEvent_t done = nullptr;
@@ -290,7 +290,7 @@ struct vrt_ctx {
         DevBuf<void> d_guides;                   // vrt_guides.h State: 40 bytes per pixel
         size_t guide_pixels = 0;                 // what it was last sized for
         DevBuf<float> d_gout;                    // vrt_accum_guides' four planes on their way to the host (9 floats per pixel)
-        DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp, 64 bytes per pixel)
+        DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp, 64 or 72 bytes per pixel)
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*

@@ -167,17 +167,15 @@ hipError_t accum_guides(accum::Source src, const Variant &v, const KArgs &a, con
 hipError_t guides_resolve(const guides::Resolve &q, hipStream_t s);
 hipError_t guide_rays(const Variant &v, const KArgs &a, const ViewSet &vs, const guides::RayArgs &q, uint32_t grid, hipStream_t s);
 
-// vrt_launch_filter.hip: the guided filter (vrt_filter.hip.h), whole frames, one lane per pixel. filter_prepass: the caller's guide
-// planes -> the packed planes; filter_level: one level's taps at q.step (first: reads the caller's image; last: writes the outputs);
-// filter_through: levels == 0.
+// vrt_launch_filter.hip: the guided filter and its variance-guided form (vrt_filter.hip.h), whole frames, one lane per pixel.
+// filter_prepass: the caller's guide planes -> the packed planes; filter_variance: after it, the initial variance into the packed
+// planes (q.variance null: the spatial estimate); filter_level: one level's taps at the step of q (first: reads the caller's image;
+// last: writes the outputs), guide-only or variance-guided by the argument's type; filter_through: levels == 0.
 hipError_t filter_prepass(const filter::Prepass &q, hipStream_t s);
-hipError_t filter_level(const filter::Level &q, bool first, bool last, hipStream_t s);
-hipError_t filter_through(const filter::Through &q, hipStream_t s);
-
-// vrt_launch_filter_var.hip: the variance-guided filter (vrt_filter_var.hip.h) behind the same prepass. filter_variance: the initial
-// variance into the packed planes (q.variance null: the spatial estimate); filter_var_level: one level, as filter_level.
 hipError_t filter_variance(const filter::Variance &q, hipStream_t s);
-hipError_t filter_var_level(const filter::LevelVar &q, bool first, bool last, hipStream_t s);
+hipError_t filter_level(const filter::Level &q, bool first, bool last, hipStream_t s);
+hipError_t filter_level(const filter::LevelVar &q, bool first, bool last, hipStream_t s);
+hipError_t filter_through(const filter::Through &q, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt
