@@ -901,7 +901,8 @@ int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int ori
  * The accumulation forms read and write no byte of the accumulation's sums: vrt_accum_resolve*, vrt_accum_resolve_hdr* and
  * vrt_accum_guides* return the same bits with and without them. None of these calls takes a profiling slot or counts towards the
  * stride. Not provided: per-sample second moments of the HDR sums (vrt_filter_hdr_var's variance input is where they would arrive;
- * until then the accumulation forms estimate the variance spatially), temporal reprojection and motion vectors, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
+ * until then the accumulation forms estimate the variance spatially, or take the temporal one of vrt_accum_resolve_hdr_temporal below),
+ * motion vectors of moving geometry, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
  * (an image-shaped batch can call vrt_filter_hdr with vrt_guide_rays_device's planes and a coverage plane made of its hit bytes). */
 #define VRT_FILTER_MAX_LEVELS 8
 #define VRT_FILTER_DEMODULATE 1u
@@ -981,6 +982,99 @@ int vrt_accum_resolve_hdr_filtered_var(vrt_ctx *ctx, const vrt_filter_var *f, co
                                        float *out_variance);
 int vrt_accum_resolve_hdr_filtered_var_device(vrt_ctx *ctx, const vrt_filter_var *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
                                               void *d_variance_out, void *stream);
+/* EXTENSION: temporal accumulation -- last frame's integrated colour and luminance moments reprojected into this frame through the
+ * guide planes, each tap tested against them, blended with this frame's image, and a TEMPORAL variance handed to the filter above
+ * (SVGF's rules). An accumulation restarts on every change of the camera block, so a moving camera never holds more than one frame's
+ * samples per pixel; this pass carries them across the move, and gives vrt_filter_hdr_var the variance input the accumulation forms
+ * above estimate spatially. Input: a float image [H][W][3] and the normal [H][W][3], depth [H][W] and coverage [H][W] planes that
+ * vrt_accum_guides_device writes, with the camera block they were made with, in vrt_set_camera's shapes; no albedo.
+ *
+ * The history is the caller's memory, as d_sums is for vrt_shade_rays_hdr_device: 48 bytes per pixel as three row-major planes of
+ * 16-byte words, plane k at byte k * W * H * 16, 16-byte aligned:
+ *   plane 0  {r, g, b, N}           the integrated colour and the history length, a float
+ *   plane 1  {m1, m2, Z, coverage}  the first and second moment of luminance, the depth and coverage of the frame that wrote it
+ *   plane 2  {nx, ny, nz, +0}       the normal of the frame that wrote it
+ * history_in == NULL marks the first frame: no pixel has a history and the previous camera is not read. history_out must differ from
+ * history_in and from every input, since a pass reads its neighbours; a caller ping-pongs two histories.
+ *
+ * All arithmetic is float32, every operation rounded on its own, nothing contracted; h, g and hv as in vrt_filter_hdr_var, min and
+ * max with vrt_accum_keep_hdr's conventions. The inputs go through h (colour) and g (normal, depth, coverage); every value read from
+ * the history goes through h (colour, m1), hv (m2) or g (the rest), and N then into [0, (float)max_history]. A pixel is LIVE when
+ * g(coverage) > 0. A pixel that is not live writes {h(c), 0}, {0, 0, 0, 0}, {0, 0, 0, 0} to the history, h(c) to out_rgb and +0 to
+ * out_variance, and is never a tap. For a live pixel p = (px, py) with depth Z_p and normal n_p:
+ *  T1. World point. d = shader_ray_dir() (the ray generation of comp:624-641, one operation at a time) at
+ *      ((float)px + offset_x, (float)py + offset_y), scaled by 1.0f / sqrtf(dot(d, d)) as primary_ray_dir()'s general form does;
+ *      P_i = e_i + Z_p * d_i with e = camera_pos. The planes' depth is the distance from the RAY'S origin: with a thin lens
+ *      (vrt_set_lens) that origin is not e and P is approximate.
+ *  T2. Previous position. clip = mat_vec(prev_view_proj, P, 1) in mat_vec's order, (m0*x + m1*y) + (m2*z + m3*w). No history unless
+ *      clip.w > 1e-6f. fx = (((clip.x / clip.w) + 1.0f) * 0.5f) * (float)W - offset_x, the inverse of the shader's u; fy likewise with
+ *      clip.y, H and offset_y. No history unless fx > -1 && fx < W && fy > -1 && fy < H (NaN: false). x0 = floorf(fx), tx = fx - x0,
+ *      the same in y. Zexp = sqrtf((dx*dx + dy*dy) + dz*dz) of P - prev_camera_pos: the depth the previous frame saw P at.
+ *  T3. Taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), in that order, with the weights (1.0f - tx) * (1.0f - ty),
+ *      tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty. A tap q COUNTS when it is inside the image, its stored coverage is > 0 and its
+ *      N >= 1, (nq.x*np.x + nq.y*np.y) + nq.z*np.z >= normal_min, and |Zq - Zexp| <= depth_tol * Zexp + 0x1p-20f. sw = the sum of
+ *      the counted taps' weights, from 0 in tap order; there is a history iff sw > 0, and every previous quantity X -- the colour,
+ *      N, m1, m2 -- is (the sum of w * Xq, from 0 in tap order) / sw. Without a history every previous quantity is +0.
+ *  T4. N' = min(Nprev + 1.0f, (float)max_history), a = max(1.0f / N', alpha_min), am = max(1.0f / N', alpha_moments_min).
+ *  T5. c' = cp + a * (h(c) - cp) per channel; Y = V1's luminance of h(c); m1' = m1p + am * (Y - m1p); m2' = m2p + am * (Y * Y - m2p).
+ *      A pixel without a history therefore returns h(c), Y and Y * Y exactly, with N' = 1.
+ *  T6. The history receives {c', N'}, {m1', m2', Z_p, coverage_p}, {n_p, +0}; out_rgb [H][W][3] receives c'; out_variance [H][W]
+ *      receives hv(max(0, m2' - m1' * m1') / (N' - 1.0f)) where N' >= 2 -- the variance of the MEAN, exact while a = 1 / N' and an
+ *      approximation once alpha_min or max_history binds -- and 65504.0f * 65504.0f where N' < 2: the luminance term of
+ *      vrt_filter_hdr_var vanishes there and the guides alone filter a pixel that has no history.
+ *
+ * vrt_temporal_default  max_history 8, alpha_min 0.4, alpha_moments_min 0.6, normal_min 0.0, depth_tol 0.4, offsets 0: the best row of
+ *                       the quality sweep in profiles/temporal_quality.txt (DESIGN.md section 3 "Temporal accumulation"); the two
+ *                       previous-camera fields zeroed, the caller fills them.
+ *                       prev_view_proj is the previous frame's FORWARD projection * view, column-major: what main.cpp:808-809
+ *                       multiplies, the inverse of that frame's inv_view * inv_projection.
+ * vrt_temporal_hdr      DEVICE pointers, stream-ordered (NULL: the context's), stateless: it reads no context state, keeps no scratch
+ *                       and takes no profiling slot. d_out_rgb and d_out_variance may be NULL. VRT_E_INVALID: a NULL input, t or
+ *                       d_history_out; d_history_out equal to d_history_in or to an input, or an output equal to an input or to
+ *                       another output; a history that is not 16-byte aligned; max_history outside 1..32768, an alpha outside
+ *                       [0, 1], normal_min outside [-1, 1], depth_tol not finite or not > 0, an offset outside [0, 1]; a matrix or
+ *                       camera position entry that is not finite (the previous camera's only where d_history_in is given); a
+ *                       frame size vrt_denoise refuses.
+ * vrt_temporal_hdr_host the same through HOST buffers, synchronous, staged through 144 bytes per pixel the context keeps.
+ * vrt_accum_resolve_hdr_temporal  the pass on an HDR accumulation, chained with vrt_filter_hdr_var: the input is its float mean
+ *                       (vrt_accum_resolve_hdr's out_rgb) with its own planes, brought up to date as a vrt_accum_guides call would,
+ *                       and the context's CURRENT camera block; offset_x / offset_y of t are replaced by 0.5 for VRT_ACCUM_JITTER
+ *                       and 0 otherwise. T1-T6, then vrt_filter_hdr_var on the integrated colour with T6's variance as its
+ *                       plane (f == NULL: vrt_filter_var_default). out_integrated [H][W][3] (may be NULL) is the UNFILTERED
+ *                       integrated colour, which is also what the history stores; out_rgb, out_rgba8, out_variance are the
+ *                       filter's (one of the first two must not be NULL). HOST buffers, the histories too (history_in may be
+ *                       NULL), synchronous. Errors: VRT_E_STATE as vrt_accum_resolve_hdr_filtered_var, VRT_E_INVALID as the two
+ *                       stateless calls. The accumulation's filter stage serves it, grown to 84 bytes per pixel (12 for the
+ *                       integrated image), and by 96 more for the two histories of this host form.
+ * vrt_accum_resolve_hdr_temporal_device  the same with DEVICE histories and outputs, enqueued on `stream` (NULL: the context's),
+ *                       ordered against the adds as vrt_accum_resolve_hdr_device is.
+ * These calls read and write no byte of the accumulation's sums: every resolve and guide call returns the same bits with and without
+ * them. None takes a profiling slot or counts towards the stride. Not provided: a 3 x 3 search where all four bilinear taps fail,
+ * the filter's first level fed back into the history, an albedo or voxel-ID test, moving geometry (a voxel edit between frames is
+ * seen only through the depth and normal tests), lens-exact reprojection, frames, views, shards and vrt_multi. */
+typedef struct vrt_temporal {
+    float prev_view_proj[16];   /* previous frame's FORWARD projection * view, column-major */
+    float prev_camera_pos[4];   /* previous frame's camera_pos */
+    float offset_x, offset_y;   /* where in the pixel the planes' ray passes: 0 corner, 0.5 jittered; finite, in [0, 1] */
+    int32_t max_history;        /* 1 .. 32768 */
+    float alpha_min, alpha_moments_min;   /* in [0, 1] */
+    float normal_min;           /* finite, in [-1, 1] */
+    float depth_tol;            /* finite, > 0 */
+} vrt_temporal;
+void vrt_temporal_default(vrt_temporal *t);
+int vrt_temporal_hdr(vrt_ctx *ctx, int width, int height, const float inv_projection[16], const float inv_view[16],
+                     const float camera_pos[4], const void *d_rgb, const void *d_normal, const void *d_depth, const void *d_coverage,
+                     const void *d_history_in, const vrt_temporal *t, void *d_history_out, void *d_out_rgb, void *d_out_variance,
+                     void *stream);
+int vrt_temporal_hdr_host(vrt_ctx *ctx, int width, int height, const float inv_projection[16], const float inv_view[16],
+                          const float camera_pos[4], const float *rgb, const float *normal, const float *depth, const float *coverage,
+                          const void *history_in, const vrt_temporal *t, void *history_out, float *out_rgb, float *out_variance);
+int vrt_accum_resolve_hdr_temporal(vrt_ctx *ctx, const vrt_temporal *t, const vrt_filter_var *f, const vrt_tonemap *tm,
+                                   const void *history_in, void *history_out, float *out_integrated, float *out_rgb, uint8_t *out_rgba8,
+                                   float *out_variance);
+int vrt_accum_resolve_hdr_temporal_device(vrt_ctx *ctx, const vrt_temporal *t, const vrt_filter_var *f, const vrt_tonemap *tm,
+                                          const void *d_history_in, void *d_history_out, void *d_integrated, void *d_rgb, void *d_rgba8,
+                                          void *d_variance_out, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

@@ -48,6 +48,16 @@ class FilterVar(C.Structure):
     _fields_ = Filter._fields_ + [("sigma_lum", C.c_float)]
 
 
+class Temporal(C.Structure):
+    """include/vrt.h vrt_temporal"""
+    _fields_ = [("prev_view_proj", C.c_float * 16), ("prev_camera_pos", C.c_float * 4), ("offset_x", C.c_float), ("offset_y", C.c_float),
+                ("max_history", C.c_int32), ("alpha_min", C.c_float), ("alpha_moments_min", C.c_float), ("normal_min", C.c_float),
+                ("depth_tol", C.c_float)]
+
+
+TEMPORAL_KEYS = ("offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min", "depth_tol")
+HISTORY_BYTES = 48       # include/vrt.h vrt_temporal_hdr: a history's bytes per pixel, three planes of 16-byte words
+
 FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
 FILTER_DEMODULATE = 1    # include/vrt.h VRT_FILTER_DEMODULATE
 
@@ -72,6 +82,15 @@ def default_filter_var():
     hip_lib().vrt_filter_var_default(C.byref(f))
     return {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE), "sigma_normal": float(f.sigma_normal),
             "sigma_albedo": float(f.sigma_albedo), "sigma_depth": float(f.sigma_depth), "sigma_lum": float(f.sigma_lum)}
+
+
+def default_temporal():
+    """vrt_temporal_default as a dict: {"offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min",
+    "depth_tol"} -- the keys the `temporal` argument of Context.temporal_hdr and Context.accum_resolve_hdr_temporal takes. The
+    previous camera is an argument of its own there. Needs no device."""
+    t = Temporal()
+    hip_lib().vrt_temporal_default(C.byref(t))
+    return {k: (int if k == "max_history" else float)(getattr(t, k)) for k in TEMPORAL_KEYS}
 
 
 def build(targets=("../libvrt_hip.so", "../libvrt_hip_test.so", "../libvrt_host.so")):
@@ -363,6 +382,12 @@ def hip_lib():
         L.vrt_accum_resolve_hdr_filtered_var.argtypes = [C.c_void_p, C.POINTER(FilterVar), C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr_filtered_var_device.argtypes = [C.c_void_p, C.POINTER(FilterVar), C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
                                                                 C.c_void_p, C.c_void_p]
+        L.vrt_temporal_default.argtypes = [C.POINTER(Temporal)]
+        L.vrt_temporal_default.restype = None
+        L.vrt_temporal_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(Temporal)] + [C.c_void_p] * 4
+        L.vrt_temporal_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(Temporal)] + [C.c_void_p] * 3
+        L.vrt_accum_resolve_hdr_temporal.argtypes = [C.c_void_p, C.POINTER(Temporal), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 6
+        L.vrt_accum_resolve_hdr_temporal_device.argtypes = [C.c_void_p, C.POINTER(Temporal), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 7
         _hip = L
     return _hip
 
@@ -1449,6 +1474,103 @@ class Context:
         f = self._filter_var(filter)
         self._chk(self._L.vrt_accum_resolve_hdr_filtered_var_device(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, d_rgb,
                                                                     d_rgba, d_variance, stream))
+
+    @staticmethod
+    def _temporal(temporal, prev_camera):
+        """a dict with any of default_temporal()'s keys (None: the defaults) and the previous frame's camera (prev_view_proj[16],
+        prev_camera_pos[3 or 4]), or None where no history comes in -> Temporal; ValueError for an unknown key"""
+        t = Temporal()
+        hip_lib().vrt_temporal_default(C.byref(t))
+        for k, v in (temporal or {}).items():
+            if k not in TEMPORAL_KEYS:
+                raise ValueError(f"unknown temporal key {k!r}; expected any of {TEMPORAL_KEYS}")
+            setattr(t, k, int(v) if k == "max_history" else float(v))
+        if prev_camera is not None:
+            vp = np.ascontiguousarray(prev_camera[0], np.float32).reshape(-1)
+            cp = np.ascontiguousarray(prev_camera[1], np.float32).reshape(-1)
+            if vp.size != 16 or cp.size not in (3, 4):
+                raise ValueError("expected prev_camera = (prev_view_proj[16], prev_camera_pos[3 or 4])")
+            t.prev_view_proj[:] = [float(v) for v in vp]
+            t.prev_camera_pos[:cp.size] = [float(v) for v in cp]
+        return t
+
+    @staticmethod
+    def _camera_block(camera):
+        ip, iv, cp = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in camera[:3])
+        if ip.size != 16 or iv.size != 16 or cp.size != 4:
+            raise ValueError("expected camera = (inv_projection[16], inv_view[16], camera_pos[4])")
+        return ip, iv, cp
+
+    def temporal_hdr(self, camera, rgb, guides, history=None, prev_camera=None, temporal=None):
+        """The temporal pass through host arrays (vrt_temporal_hdr_host): last frame's `history` float32[3,H,W,4] (None: the first
+        frame) reprojected into this frame -- rgb[H,W,3] with the "normal", "depth" and "coverage" planes of `guides` and the
+        camera block they were made with, camera = (inv_projection, inv_view, camera_pos) as set_camera takes them -- tested
+        against the planes and blended. prev_camera = (prev_view_proj[16], prev_camera_pos): the previous frame's forward
+        projection * view and eye, needed with a history. temporal: None (vrt_temporal_default) or a dict with any of
+        default_temporal()'s keys -> (history float32[3,H,W,4]: the next call's; rgb float32[H,W,3]: the integrated colour;
+        variance float32[H,W]: of its luminance, the plane filter_hdr_var takes)."""
+        ip, iv, cp = self._camera_block(camera)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        n, z, cov = (np.ascontiguousarray(guides[k], np.float32) for k in ("normal", "depth", "coverage"))
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+        h, w = rgb.shape[:2]
+        if n.shape != (h, w, 3) or z.shape != (h, w) or cov.shape != (h, w):
+            raise ValueError(f"expected guides [H,W,3], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {z.shape}, {cov.shape}")
+        if history is not None:
+            history = np.ascontiguousarray(history, np.float32)
+            if history.shape != (3, h, w, 4):
+                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
+            if prev_camera is None:
+                raise ValueError("a history needs prev_camera")
+        t = self._temporal(temporal, prev_camera if history is not None else None)
+        out_h, out, outv = np.zeros((3, h, w, 4), np.float32), np.zeros_like(rgb), np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_temporal_hdr_host(self._h, w, h, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, rgb.ctypes.data, n.ctypes.data,
+                                                z.ctypes.data, cov.ctypes.data, history.ctypes.data if history is not None else None,
+                                                C.byref(t), out_h.ctypes.data, out.ctypes.data, outv.ctypes.data))
+        return out_h, out, outv
+
+    def temporal_hdr_device(self, width, height, camera, d_rgb, d_normal, d_depth, d_coverage, d_history_in, d_history_out, d_out_rgb,
+                            d_out_variance, prev_camera=None, temporal=None, stream=None):
+        """vrt_temporal_hdr: DEVICE buffers (d_rgb: W*H x 3 floats; the planes as accum_guides_device writes them; the histories
+        W*H x HISTORY_BYTES bytes each, d_history_in None on the first frame; d_out_rgb, d_out_variance: either may be None),
+        enqueued on `stream`"""
+        ip, iv, cp = self._camera_block(camera)
+        t = self._temporal(temporal, prev_camera if d_history_in is not None else None)
+        self._chk(self._L.vrt_temporal_hdr(self._h, width, height, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_depth,
+                                           d_coverage, d_history_in, C.byref(t), d_history_out, d_out_rgb, d_out_variance, stream))
+
+    def accum_resolve_hdr_temporal(self, history=None, prev_camera=None, temporal=None, filter=None, tonemap="clamp", exposure=1.0):
+        """The temporal pass and the variance-guided filter on an HDR accumulation (vrt_accum_resolve_hdr_temporal): its float mean
+        with its own guide planes and the context's current camera, integrated with `history` (None: the first frame), then
+        filtered with the temporal variance -> (history float32[3,H,W,4], integrated float32[H,W,3]: unfiltered, what the
+        history holds; rgb float32[H,W,3], rgba8[H,W,4], variance float32[H,W]: the filter's)."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
+        if history is not None:
+            history = np.ascontiguousarray(history, np.float32)
+            if history.shape != (3, h, w, 4):
+                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
+            if prev_camera is None:
+                raise ValueError("a history needs prev_camera")
+        t = self._temporal(temporal, prev_camera if history is not None else None)
+        out_h, integ = np.zeros((3, h, w, 4), np.float32), np.zeros((h, w, 3), np.float32)
+        rgb, rgba, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 4), np.uint8), np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_accum_resolve_hdr_temporal(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
+                                                         history.ctypes.data if history is not None else None, out_h.ctypes.data,
+                                                         integ.ctypes.data, rgb.ctypes.data, rgba.ctypes.data, var.ctypes.data))
+        return out_h, integ, rgb, rgba, var
+
+    def accum_resolve_hdr_temporal_device(self, d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, prev_camera=None,
+                                          temporal=None, filter=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_temporal_device: DEVICE buffers (d_history_in None on the first frame; d_integrated and d_variance
+        may be None; d_rgb, d_rgba: either may be None, not both), enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        t = self._temporal(temporal, prev_camera if d_history_in is not None else None)
+        self._chk(self._L.vrt_accum_resolve_hdr_temporal_device(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
+                                                                d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -229,6 +229,22 @@ int filter_accum(vrt_ctx *c, const char *what, Params k, const vrt_tonemap *tm, 
 
 }  // namespace
 
+namespace vrt_internal {
+
+int filter_var_check(vrt_ctx *c, const char *what, const vrt_filter_var *f, const vrt_tonemap *tm, const void *out_rgb, const void *out_rgba8) {
+    Params k = params_of(f);
+    return check_call(c, what, nullptr, const_cast<void *>(out_rgb), const_cast<void *>(out_rgba8), k, tm, false);
+}
+
+int filter_var_frame(vrt_ctx *c, const char *what, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo,
+                     const void *d_depth, const void *d_coverage, const void *d_variance, const vrt_filter_var *f, const vrt_tonemap *tm,
+                     void *d_out_rgb, void *d_out_rgba8, void *d_out_variance, void *stream) {
+    const Planes d{d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance, d_out_rgb, d_out_rgba8, d_out_variance};
+    return filter_frame(c, what, width, height, d, params_of(f), tm, stream);
+}
+
+}  // namespace vrt_internal
+
 extern "C" {
 
 void vrt_filter_default(vrt_filter *f) {

@@ -134,6 +134,8 @@ struct vrt_ctx {
         ~FilterScratch() { if (done) (void)hipEventDestroy(done); }
     };
     FilterScratch filter;
+    // the staging of vrt_temporal_hdr_host (vrt_temporal.cpp): both histories, the inputs and the outputs, 144 bytes per pixel
+    DevBuf<float4> d_temporal;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     DevBuf<void> d_query;
     // device buffers behind vrt_shade_rays (vrt_rays.cpp)
@@ -290,7 +292,8 @@ struct vrt_ctx {
         DevBuf<void> d_guides;                   // vrt_guides.h State: 40 bytes per pixel
         size_t guide_pixels = 0;                 // what it was last sized for
         DevBuf<float> d_gout;                    // vrt_accum_guides' four planes on their way to the host (9 floats per pixel)
-        DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp, 64 or 72 bytes per pixel)
+        DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp, 64 or 72 bytes per pixel);
+                                                 // vrt_accum_resolve_hdr_temporal*: the same and the integrated image (vrt_temporal.cpp, 84, or 180 with the host form's histories)
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
@@ -428,6 +431,14 @@ int accum_joined(vrt_ctx *c, hipStream_t s, const BODY &body) {
     }
     return VRT_OK;
 }
+
+// vrt_filter.cpp
+// What vrt_filter_hdr_var checks of its filter, tone map and colour outputs (one of which must not be null), in the name of `what`,
+// before anything is enqueued; and the call itself in that name: the chain of vrt_accum_resolve_hdr_temporal (vrt_temporal.cpp)
+int filter_var_check(vrt_ctx *c, const char *what, const vrt_filter_var *f, const vrt_tonemap *tm, const void *out_rgb, const void *out_rgba8);
+int filter_var_frame(vrt_ctx *c, const char *what, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo,
+                     const void *d_depth, const void *d_coverage, const void *d_variance, const vrt_filter_var *f, const vrt_tonemap *tm,
+                     void *d_out_rgb, void *d_out_rgba8, void *d_out_variance, void *stream);
 
 // vrt_rays.cpp
 // The kernel arguments of a caller's ray batch of n rays as an image of `width` (after ensure_analysis): the scene and light blocks

@@ -7,6 +7,7 @@
 #include "vrt_rays.h"
 #include "vrt_guides.h"
 #include "vrt_filter.h"
+#include "vrt_temporal.h"
 
 namespace vrt {
 namespace launch {
@@ -176,6 +177,10 @@ hipError_t filter_variance(const filter::Variance &q, hipStream_t s);
 hipError_t filter_level(const filter::Level &q, bool first, bool last, hipStream_t s);
 hipError_t filter_level(const filter::LevelVar &q, bool first, bool last, hipStream_t s);
 hipError_t filter_through(const filter::Through &q, hipStream_t s);
+
+// vrt_launch_temporal.hip: the temporal pass (vrt_temporal.hip.h), a whole frame, one lane per pixel, one 8 x 8 tile per wave:
+// T1-T6 of include/vrt.h vrt_temporal_hdr from q's planes and (where given) its previous history into the new one.
+hipError_t temporal_pass(const temporal::Args &q, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt
