@@ -12,6 +12,8 @@ The world is test_gpu_dispatch_interleaved's corner world: a floor, a wall and a
 import numpy as np
 import pytest
 
+import temporal_worlds as TW
+
 pytestmark = pytest.mark.gpu
 
 F = np.float32
@@ -20,6 +22,7 @@ POSE = (50.5, 40.5, 50.5, -135.0, -43.0)
 # and in the display pass's tiles), small again
 STEPS = ((16, 8, 1), (72, 40, 1000), (16, 8, 3))
 TOLERANCE = 8
+GUIDES = ("normal", "albedo", "depth", "coverage")
 
 
 def _world(V, extra=0):
@@ -76,7 +79,8 @@ def _adaptive(ctx):
 
 def run_all(V, ctx, w, h, n):
     """every host-buffer entry point once, at frame shape w x h and n rays / points -> {call: tuple of arrays}"""
-    ctx.set_camera(*V.camera_block(POSE[:3], POSE[3], POSE[4], w, h)[:3])
+    cam = V.camera_block(POSE[:3], POSE[3], POSE[4], w, h)[:3]
+    ctx.set_camera(*cam)
     o, d, pts = _inputs(n)
     out = {}
     for mode in (0, 1, 2):
@@ -90,10 +94,26 @@ def run_all(V, ctx, w, h, n):
     out["find_voxels"] = ctx.find_voxels(pts)
     out["shade_rays"] = ctx.shade_rays(o, d, 2, width=8, first_sample=5, n_samples=2)
     out["shade_rays_hdr"] = ctx.shade_rays_hdr(o, d, 2, width=8, first_sample=5, n_samples=2, tonemap="reinhard", exposure=1.5)
+    rays = ctx.guide_rays(o, d, width=8)
+    out["guide_rays"] = tuple(rays[k] for k in ("normal", "albedo", "depth", "hit"))
     out["accum plain"] = _accum(ctx, w, h, ctx.accum_resolve)
     out["accum jitter"] = _accum(ctx, w, h, ctx.accum_resolve, jitter=True)
     out["accum adaptive"] = _accum(ctx, w, h, lambda: _adaptive(ctx), jitter=True, adaptive=(2, 4, TOLERANCE))
     out["accum hdr"] = _accum(ctx, w, h, lambda: _hdr(ctx), jitter=True, hdr=True)
+    # what reads that HDR accumulation through the accumulation's own staging: its guide planes, the filtered resolves, the temporal
+    # resolve without and with a history
+    g = ctx.accum_guides()
+    out["accum_guides"] = tuple(g[k] for k in GUIDES)
+    out["accum filtered"] = ctx.accum_resolve_hdr_filtered(None, "reinhard", 1.5)
+    out["accum filtered var"] = ctx.accum_resolve_hdr_filtered_var(None, "reinhard", 1.5)
+    first = ctx.accum_resolve_hdr_temporal(None, None, None, None, "reinhard", 1.5)
+    out["accum temporal"] = first
+    out["accum temporal, history"] = ctx.accum_resolve_hdr_temporal(first[0], TW.prev_camera(cam), None, None, "reinhard", 1.5)
+    # ... and the stateless host forms on the planes and the mean just resolved, through the context's
+    mean = out["accum hdr"][0]
+    out["filter_hdr"] = ctx.filter_hdr(mean, g, None, "reinhard", 1.5)
+    out["filter_hdr_var"] = ctx.filter_hdr_var(mean, g, None, None, "reinhard", 1.5)
+    out["temporal_hdr"] = ctx.temporal_hdr(cam, mean, g, first[0], TW.prev_camera(cam))
     return out
 
 

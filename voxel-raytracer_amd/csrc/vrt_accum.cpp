@@ -10,7 +10,7 @@
 // An HDR accumulation (vrt_accum_keep_hdr before the begin) keeps three float64 sums per pixel of the samples' float colours too:
 // the kernels' HDR forms, 24 + 12 bytes per pixel allocated only then, and vrt_accum_resolve_hdr's mean and tone map. Where the
 // samples are all one frame, that frame comes from the HDR frame kernel, which hands out its float colour.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 #include "vrt_launch.h"
 
 #include <cstring>
@@ -49,13 +49,6 @@ void take_inputs(const vrt_ctx *c, Accum &ac) {
     ac.tree_gen = c->tree_gen;
 }
 
-int resolve_state(vrt_ctx *c, const char *what) {
-    if (!c) return VRT_E_INVALID;
-    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
-    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
-    return VRT_OK;
-}
-
 // sums -> rgba8 into d_rgba, the frame's id_dist into d_id (either may be null), the display pass into d_shown (needs d_rgba)
 int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_t s) {
     Accum &ac = c->accum;
@@ -71,10 +64,8 @@ int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_
 
 // vrt_accum_resolve_hdr*: the call-order checks of a resolve, an HDR accumulation, a tone map the header defines
 int resolve_hdr_state(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
-    int r = resolve_state(c, what);
-    if (r) return r;
-    if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
-    return check_tonemap(c, what, tm);
+    const int r = accum_state(c, what, true);
+    return r ? r : check_tonemap(c, what, tm);
 }
 
 // float64 sums -> float mean into d_rgb, its tone-mapped rgba8 into d_rgba (either may be null), the display pass into d_shown
@@ -164,6 +155,15 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
 }  // namespace
 
 bool vrt_internal::accum_inputs_current(const vrt_ctx *c) { return same_inputs(c, c->accum); }
+
+int vrt_internal::accum_state(vrt_ctx *c, const char *what, bool need_hdr) {
+    if (!c) return VRT_E_INVALID;
+    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
+    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
+    if (need_hdr && !c->accum.hdr)
+        return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
+    return VRT_OK;
+}
 
 // the step's samples go into the context's sums; an adaptive accumulation (acc.adaptive) passes its rule and state too, to the
 // kernels' adaptive forms, an HDR one (acc.hdr) its float64 sums, to the HDR object's
@@ -341,7 +341,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
 }
 
 int vrt_accum_resolve(vrt_ctx *c, uint8_t *out_rgba8, int32_t *out_id_dist, uint8_t *out_shown_rgba8) {
-    int r = resolve_state(c, "vrt_accum_resolve");
+    int r = accum_state(c, "vrt_accum_resolve", false);
     if (r) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     const Accum &ac = c->accum;
@@ -351,15 +351,15 @@ int vrt_accum_resolve(vrt_ctx *c, uint8_t *out_rgba8, int32_t *out_id_dist, uint
     const bool want_rgba = out_rgba8 || out_shown_rgba8;
     r = resolve_into(c, want_rgba ? c->d_rgba : nullptr, nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
     if (r) return r;
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_id_dist) VRT_HIP(c, hipMemcpyAsync(out_id_dist, ac.d_id, px * 8, hipMemcpyDeviceToHost, c->stream));
-    if (out_shown_rgba8) VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    st.out(px * 4, out_rgba8, c->d_rgba);
+    st.out(px * 8, out_id_dist, ac.d_id);
+    st.out(px * 4, out_shown_rgba8, c->d_shown);
+    return st.download(c, c->stream);
 }
 
 int vrt_accum_resolve_device(vrt_ctx *c, void *d_rgba8, void *d_id_dist, void *d_shown_rgba8, void *stream) {
-    int r = resolve_state(c, "vrt_accum_resolve_device");
+    int r = accum_state(c, "vrt_accum_resolve_device", false);
     if (r) return r;
     if (d_shown_rgba8 && !d_rgba8) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_resolve_device: the display pass needs d_rgba8");
     VRT_HIP(c, hipSetDevice(c->device));
@@ -386,11 +386,11 @@ int vrt_accum_resolve_hdr(vrt_ctx *c, float *out_rgb, const vrt_tonemap *tm, uin
     const bool want_rgba = out_rgba8 || out_shown_rgba8;
     r = resolve_hdr_into(c, out_rgb ? ac.d_hrgb : nullptr, tm, want_rgba ? c->d_rgba : nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
     if (r) return r;
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, ac.d_hrgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_shown_rgba8) VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    st.out(px * 12, out_rgb, ac.d_hrgb);
+    st.out(px * 4, out_rgba8, c->d_rgba);
+    st.out(px * 4, out_shown_rgba8, c->d_shown);
+    return st.download(c, c->stream);
 }
 
 int vrt_accum_resolve_hdr_device(vrt_ctx *c, void *d_rgb, const vrt_tonemap *tm, void *d_rgba8, void *d_shown_rgba8, void *stream) {
@@ -413,10 +413,10 @@ int vrt_accum_resolve_hdr_shown(vrt_ctx *c, const vrt_tonemap *tm, float *out_sh
     if (out_shown_rgb && (r = ensure_float_image(c, ac.d_hrgb, px))) return r;
     r = resolve_hdr_shown_into(c, tm, out_shown_rgb ? ac.d_hrgb : nullptr, out_shown_rgba8 ? c->d_shown : nullptr, c->stream);
     if (r) return r;
-    if (out_shown_rgb) VRT_HIP(c, hipMemcpyAsync(out_shown_rgb, ac.d_hrgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_shown_rgba8) VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    st.out(px * 12, out_shown_rgb, ac.d_hrgb);
+    st.out(px * 4, out_shown_rgba8, c->d_shown);
+    return st.download(c, c->stream);
 }
 
 int vrt_accum_resolve_hdr_shown_device(vrt_ctx *c, const vrt_tonemap *tm, void *d_shown_rgb, void *d_shown_rgba8, void *stream) {
@@ -448,10 +448,10 @@ int vrt_accum_counts(vrt_ctx *c, uint32_t *out_counts) {
                                ac.max_samples, ac.tolerance};
     VRT_HIP(c, vrt::launch::adaptive_counts(q, c->stream));
     uint32_t active = 0;
-    if (out_counts) VRT_HIP(c, hipMemcpyAsync(out_counts, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(&active, d_active, 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return (int)active;
+    vrt_stage::Stage st(4);
+    st.out(px * 4, out_counts, c->d_rgba);
+    st.out(4, &active, d_active);
+    return (r = st.download(c, c->stream)) ? r : (int)active;
 }
 
 }  // extern "C"

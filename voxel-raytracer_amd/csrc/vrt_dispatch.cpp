@@ -2,7 +2,7 @@
 // views, the kernel variant the scene and the views allow, the frame block of the kernel arguments (the scene and light blocks are
 // vrt_scene.cpp's), the feedback tile scheduler, the form of the full path tracer -- over the caches above it (scheduling states, ray
 // tables, miss masks), and carries the vrt_dispatch* entry points of include/vrt.h. Host code; the kernels are behind vrt_launch.h.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 
 #include <algorithm>
 #include <cmath>
@@ -555,13 +555,10 @@ int vrt_dispatch(vrt_ctx *c, int width, int height, int mode, uint8_t *out_rgba8
     const size_t px = (size_t)width * (size_t)height;
     r = ensure_scratch(c, px);
     if (r) return r;
-    r = enqueue(c, width, height, 0, height, height, 0, 0, mode, out_rgba8 ? c->d_rgba : nullptr,
-                out_id_dist ? c->d_id : nullptr, c->stream);
-    if (r) return r;
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_id_dist) VRT_HIP(c, hipMemcpyAsync(out_id_dist, c->d_id, px * 8, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    const int rgba = st.out(px * 4, out_rgba8, c->d_rgba), id = st.out(px * 8, out_id_dist, c->d_id);
+    r = enqueue(c, width, height, 0, height, height, 0, 0, mode, st.at(rgba), st.at(id), c->stream);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_dispatch_wait(vrt_ctx *c, int ticket) {

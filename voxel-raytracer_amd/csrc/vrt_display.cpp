@@ -1,6 +1,6 @@
 // vrt_display.cpp -- the display pass that consumes the two images in the reference's frame loop (the fullscreen quad drawn by
 // src/main.cpp:951-967 with shaders/quad.frag:22-83) and the fused frame call. Host code; the kernel is behind vrt_launch.h.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 
 #include <cmath>
 #include <cstdio>
@@ -95,14 +95,12 @@ int vrt_denoise_hdr_host(vrt_ctx *c, int width, int height, const float *rgb, co
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)width * (size_t)height;
     if ((r = ensure_scratch(c, px)) || (r = ensure_hdr_scratch(c, px))) return r;
-    VRT_HIP(c, hipMemcpyAsync(c->d_hdr_in, rgb, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(c->d_id, id_dist, px * 8, hipMemcpyHostToDevice, c->stream));
-    r = vrt_denoise_hdr(c, width, height, c->d_hdr_in, c->d_id, tm, out_rgb ? c->d_hdr_out : nullptr, out_rgba8 ? c->d_shown : nullptr, nullptr);
-    if (r) return r;
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, c->d_hdr_out, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);   // the pass's staging depends on its pointers' alignment: the images keep their own buffers
+    const int in = st.in(px * 12, rgb, c->d_hdr_in), id = st.in(px * 8, id_dist, c->d_id);
+    const int o_rgb = st.out(px * 12, out_rgb, c->d_hdr_out), o_rgba = st.out(px * 4, out_rgba8, c->d_shown);
+    if ((r = st.upload(c, c->stream))) return r;
+    r = vrt_denoise_hdr(c, width, height, st.at(in), st.at(id), tm, st.at(o_rgb), st.at(o_rgba), nullptr);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_denoise_host(vrt_ctx *c, int width, int height, const uint8_t *rgba8, const int32_t *id_dist, uint8_t *out_rgba8) {
@@ -113,13 +111,11 @@ int vrt_denoise_host(vrt_ctx *c, int width, int height, const uint8_t *rgba8, co
     const size_t px = (size_t)width * (size_t)height;
     r = ensure_scratch(c, px);
     if (r) return r;
-    VRT_HIP(c, hipMemcpyAsync(c->d_rgba, rgba8, px * 4, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(c->d_id, id_dist, px * 8, hipMemcpyHostToDevice, c->stream));
-    r = vrt_denoise(c, width, height, c->d_rgba, c->d_id, c->d_shown, nullptr);
-    if (r) return r;
-    VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    const int in = st.in(px * 4, rgba8, c->d_rgba), id = st.in(px * 8, id_dist, c->d_id), shown = st.out(px * 4, out_rgba8, c->d_shown);
+    if ((r = st.upload(c, c->stream))) return r;
+    r = vrt_denoise(c, width, height, st.at(in), st.at(id), st.at(shown), nullptr);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_dispatch_frame(vrt_ctx *c, int width, int height, int mode, uint8_t *out_shown_rgba8, uint8_t *out_rgba8,
@@ -135,11 +131,11 @@ int vrt_dispatch_frame(vrt_ctx *c, int width, int height, int mode, uint8_t *out
     if (r) return r;
     r = vrt_denoise(c, width, height, c->d_rgba, c->d_id, c->d_shown, nullptr);
     if (r) return r;
-    VRT_HIP(c, hipMemcpyAsync(out_shown_rgba8, c->d_shown, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, c->d_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_id_dist) VRT_HIP(c, hipMemcpyAsync(out_id_dist, c->d_id, px * 8, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    st.out(px * 4, out_shown_rgba8, c->d_shown);
+    st.out(px * 4, out_rgba8, c->d_rgba);
+    st.out(px * 8, out_id_dist, c->d_id);
+    return st.download(c, c->stream);
 }
 
 }  // extern "C"

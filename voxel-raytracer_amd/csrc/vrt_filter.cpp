@@ -5,7 +5,7 @@
 // state up to date) into the accumulation's scratch and runs it on them (filter_accum). The entry points are thin callers: the
 // guide-only ones pass no variance input, no variance output and no luminance width. Host code; the kernels are behind
 // vrt_launch.h. Nothing here touches the accumulation's sums.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 #include "vrt_launch.h"
 
 #include <cmath>
@@ -13,21 +13,6 @@
 using namespace vrt_internal;
 
 namespace {
-
-// Mean or caller's image, the four planes, the float output and the bytes: 3 + 3 + 4 + 1 + 1 + 3 + 1 words per pixel, the layout
-// of both staging blocks (the context's for the host forms, the accumulation's for its filtered resolves)
-constexpr size_t kStageBytes = 64;
-// ... and, for the variance-guided forms, the variance plane in and out behind them: 2 more words
-constexpr size_t kStageVarBytes = 72;
-struct Stage {
-    float *rgb, *normal, *albedo, *depth, *coverage, *out_rgb;
-    uint32_t *out_rgba;
-    float *variance, *out_variance;   // inside the block only where it was sized with kStageVarBytes
-};
-Stage stage_of(float *base, size_t px) {
-    return Stage{base, base + px * 3, base + px * 6, base + px * 10, base + px * 11, base + px * 12, reinterpret_cast<uint32_t *>(base + px * 15),
-                 base + px * 16, base + px * 17};
-}
 
 // The filter a call runs with, in one shape for both forms: the guide-only one has no sigma_lum (var false). kn, ka: check_filter's.
 struct Params {
@@ -78,11 +63,6 @@ int ensure_level_scratch(vrt_ctx *c, size_t px, int levels) {
     VRT_HIP(c, fs.d_ping.reserve(ping));
     VRT_HIP(c, fs.d_pong.reserve(pong));
     return VRT_OK;
-}
-
-int ensure_stage(vrt_ctx *c, DevBuf<float> &buf, size_t px, bool var) {
-    const size_t bytes = px * (var ? kStageVarBytes : kStageBytes);
-    return bytes <= buf.bytes() ? VRT_OK : reserve_synced(c, {{&buf, bytes}});
 }
 
 int check_outputs(vrt_ctx *c, const char *what, const void *out_rgb, const void *out_rgba8) {
@@ -166,13 +146,25 @@ int filter_frame(vrt_ctx *c, const char *what, int width, int height, const Plan
     return VRT_OK;
 }
 
-// the outputs the caller asked for, from a stage to the host on the context's stream, and the wait for them
-int download(vrt_ctx *c, const Stage &st, size_t px, void *out_rgb, void *out_rgba8, void *out_variance) {
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st.out_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st.out_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) VRT_HIP(c, hipMemcpyAsync(out_variance, st.out_variance, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+// The layout of both staging blocks (the context's for the host forms, the accumulation's for its filtered resolves): mean or caller's
+// image, the four planes, the float output and the bytes; for the variance-guided forms (var) the variance plane in and out behind
+// them. u: the caller's planes; `in`: what the first five are -- the caller's, or (kKept) made on the device. The variance input is
+// the caller's or none.
+enum { kRgb, kNormal, kAlbedo, kDepth, kCoverage, kOutRgb, kOutRgba, kVariance, kOutVariance };
+void declare(vrt_stage::Stage &st, size_t px, bool var, vrt_stage::Dir in, const Planes &u) {
+    st.add(in, px * 12, u.rgb);
+    st.add(in, px * 12, u.normal);
+    st.add(in, px * 16, u.albedo);
+    st.add(in, px * 4, u.depth);
+    st.add(in, px * 4, u.coverage);
+    st.out(px * 12, u.out_rgb);
+    st.out(px * 4, u.out_rgba8);
+    st.in(var ? px * 4 : 0, u.variance);
+    st.out(var ? px * 4 : 0, u.out_variance);
+}
+Planes planes_of(const vrt_stage::Stage &st) {   // ... as a launch gets them
+    return Planes{st.at(kRgb), st.at(kNormal), st.at(kAlbedo), st.at(kDepth), st.at(kCoverage), st.at(kVariance), st.at(kOutRgb), st.at(kOutRgba),
+                  st.at(kOutVariance)};
 }
 
 // the host forms: the caller's planes h through the context's staging block, on the context's stream
@@ -182,18 +174,11 @@ int filter_host(vrt_ctx *c, const char *what, int width, int height, const Plane
     if ((r = check_call(c, what, &h, h.out_rgb, h.out_rgba8, k, tm, false))) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)width * (size_t)height;
-    if ((r = ensure_stage(c, c->filter.d_host, px, k.var))) return r;
-    const Stage st = stage_of(c->filter.d_host, px);
-    VRT_HIP(c, hipMemcpyAsync(st.rgb, h.rgb, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.normal, h.normal, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.albedo, h.albedo, px * 16, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.depth, h.depth, px * 4, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st.coverage, h.coverage, px * 4, hipMemcpyHostToDevice, c->stream));
-    if (h.variance) VRT_HIP(c, hipMemcpyAsync(st.variance, h.variance, px * 4, hipMemcpyHostToDevice, c->stream));
-    const Planes d{st.rgb, st.normal, st.albedo, st.depth, st.coverage, h.variance ? st.variance : nullptr, h.out_rgb ? st.out_rgb : nullptr,
-                   h.out_rgba8 ? st.out_rgba : nullptr, h.out_variance ? st.out_variance : nullptr};
-    if ((r = filter_frame(c, what, width, height, d, k, tm, nullptr))) return r;
-    return download(c, st, px, h.out_rgb, h.out_rgba8, h.out_variance);
+    vrt_stage::Stage st(4);
+    declare(st, px, k.var, vrt_stage::kIn, h);
+    if ((r = st.reserve_synced(c, c->filter.d_host)) || (r = st.upload(c, c->stream))) return r;
+    r = filter_frame(c, what, width, height, planes_of(st), k, tm, nullptr);
+    return r ? r : st.download(c, c->stream);
 }
 
 // The accumulation forms: mean and planes into the accumulation's stage and the filter on them. to_host: the outputs are the caller's
@@ -201,30 +186,20 @@ int filter_host(vrt_ctx *c, const char *what, int width, int height, const Plane
 // accumulation has no variance of its own: the variance-guided form estimates it spatially.
 int filter_accum(vrt_ctx *c, const char *what, Params k, const vrt_tonemap *tm, bool to_host, void *out_rgb, void *out_rgba8, void *out_variance,
                  void *stream) {
-    if (!c) return VRT_E_INVALID;
-    // the call-order checks: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
-    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
-    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
-    if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
-    int r = check_call(c, what, nullptr, out_rgb, out_rgba8, k, tm, false);
-    if (r) return r;
+    int r = accum_state(c, what, true);   // the call-order checks: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
+    if (r || (r = check_call(c, what, nullptr, out_rgb, out_rgba8, k, tm, false))) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     vrt_ctx::Accum &ac = c->accum;
     const size_t px = (size_t)ac.width * (size_t)ac.height;
-    if ((r = ensure_stage(c, ac.d_filter, px, k.var))) return r;
-    const Stage st = stage_of(ac.d_filter, px);
+    vrt_stage::Stage st(4, to_host);
+    declare(st, px, k.var, vrt_stage::kKept, Planes{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out_rgb, out_rgba8, out_variance});
+    if ((r = st.reserve_synced(c, ac.d_filter))) return r;
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((r = vrt_accum_guides_device(c, st.normal, st.albedo, st.depth, st.coverage, s))) return r;   // brings the guide state up to date first
-    if ((r = vrt_accum_resolve_hdr_device(c, st.rgb, tm, nullptr, nullptr, s))) return r;
-    Planes d{st.rgb, st.normal, st.albedo, st.depth, st.coverage, nullptr, out_rgb, out_rgba8, out_variance};
-    if (to_host) {
-        d.out_rgb = out_rgb ? st.out_rgb : nullptr;
-        d.out_rgba8 = out_rgba8 ? st.out_rgba : nullptr;
-        d.out_variance = out_variance ? st.out_variance : nullptr;
-    }
+    if ((r = vrt_accum_guides_device(c, st.at(kNormal), st.at(kAlbedo), st.at(kDepth), st.at(kCoverage), s))) return r;   // brings the guide state up to date first
+    if ((r = vrt_accum_resolve_hdr_device(c, st.at(kRgb), tm, nullptr, nullptr, s))) return r;
     // the stage belongs to the accumulation, whose every use the context's stream orders: a caller's stream is joined back
-    if ((r = accum_joined(c, s, [&] { return filter_frame(c, what, ac.width, ac.height, d, k, tm, s); }))) return r;
-    return to_host ? download(c, st, px, out_rgb, out_rgba8, out_variance) : VRT_OK;
+    r = accum_joined(c, s, [&] { return filter_frame(c, what, ac.width, ac.height, planes_of(st), k, tm, s); });
+    return r ? r : st.download(c, c->stream);
 }
 
 }  // namespace

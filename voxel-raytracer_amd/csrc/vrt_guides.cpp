@@ -4,7 +4,7 @@
 // VRT_MODE_PRIMARY, so the views, the lens selection, the variant and the frame block are those of the accumulation's own primary
 // launches -- and the resolve. For ray batches: vrt_shade_rays's arguments and staging, one launch, no state. Neither touches the
 // accumulation's sums.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 #include "vrt_launch.h"
 
 using namespace vrt_internal;
@@ -12,13 +12,6 @@ using namespace vrt_internal;
 namespace {
 
 using Accum = vrt_ctx::Accum;
-
-int guide_state(vrt_ctx *c, const char *what) {
-    if (!c) return VRT_E_INVALID;
-    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
-    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
-    return VRT_OK;
-}
 
 // The guides of the samples the state does not hold yet, on the context's stream (which orders every use of the state)
 int catch_up(vrt_ctx *c, const char *what) {
@@ -88,34 +81,27 @@ int guide_batch(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride,
     return VRT_OK;
 }
 
-inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
-
 }  // namespace
 
 extern "C" {
 
 int vrt_accum_guides(vrt_ctx *c, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage) {
-    int r = guide_state(c, "vrt_accum_guides");
+    int r = accum_state(c, "vrt_accum_guides", false);
     if (r) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     Accum &ac = c->accum;
     const size_t px = (size_t)ac.width * (size_t)ac.height;
     if ((r = catch_up(c, "vrt_accum_guides"))) return r;
-    if (px * 9 * sizeof(float) > ac.d_gout.bytes() && (r = reserve_synced(c, {{&ac.d_gout, px * 9 * sizeof(float)}}))) return r;
-    float *g = ac.d_gout;
-    float *d_normal = out_normal ? g : nullptr, *d_albedo = out_albedo ? g + px * 3 : nullptr;
-    float *d_depth = out_depth ? g + px * 7 : nullptr, *d_coverage = out_coverage ? g + px * 8 : nullptr;
-    if ((r = resolve_into(c, d_normal, d_albedo, d_depth, d_coverage, c->stream))) return r;
-    if (out_normal) VRT_HIP(c, hipMemcpyAsync(out_normal, d_normal, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_albedo) VRT_HIP(c, hipMemcpyAsync(out_albedo, d_albedo, px * 16, hipMemcpyDeviceToHost, c->stream));
-    if (out_depth) VRT_HIP(c, hipMemcpyAsync(out_depth, d_depth, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_coverage) VRT_HIP(c, hipMemcpyAsync(out_coverage, d_coverage, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);
+    const int normal = st.out(px * 12, out_normal), albedo = st.out(px * 16, out_albedo), depth = st.out(px * 4, out_depth);
+    const int coverage = st.out(px * 4, out_coverage);
+    if ((r = st.reserve_synced(c, ac.d_gout))) return r;
+    r = resolve_into(c, st.at<float>(normal), st.at<float>(albedo), st.at<float>(depth), st.at<float>(coverage), c->stream);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_accum_guides_device(vrt_ctx *c, void *d_normal, void *d_albedo, void *d_depth, void *d_coverage, void *stream) {
-    int r = guide_state(c, "vrt_accum_guides_device");
+    int r = accum_state(c, "vrt_accum_guides_device", false);
     if (r) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     if ((r = catch_up(c, "vrt_accum_guides_device"))) return r;
@@ -133,28 +119,14 @@ int vrt_guide_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride
     if (width < 1) return vrt_fail(c, VRT_E_INVALID, "vrt_guide_rays: width must be at least 1");
     if (n == 0) return VRT_OK;
     VRT_HIP(c, hipSetDevice(c->device));
-    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
-    const size_t nb = out_normal ? n * 12 : 0, ab = out_albedo ? n * 16 : 0, db = out_depth ? n * 4 : 0, hb = out_hit ? n : 0;
-    r = reserve_staging(c, c->d_rays, align256(o_bytes) + align256(d_bytes) + align256(nb) + align256(ab) + align256(db) + hb);
-    if (r) return r;
-    char *base = static_cast<char *>(c->d_rays.get());
-    float *d_o = reinterpret_cast<float *>(base);
-    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
-    char *out = base + align256(o_bytes) + align256(d_bytes);
-    float *d_n = out_normal ? reinterpret_cast<float *>(out) : nullptr;
-    float *d_a = out_albedo ? reinterpret_cast<float *>(out + align256(nb)) : nullptr;
-    float *d_z = out_depth ? reinterpret_cast<float *>(out + align256(nb) + align256(ab)) : nullptr;
-    uint8_t *d_h = out_hit ? reinterpret_cast<uint8_t *>(out + align256(nb) + align256(ab) + align256(db)) : nullptr;
-    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
-    r = guide_batch(c, n, d_o, origin_stride, d_d, width, d_n, d_a, d_z, d_h, c->stream);
-    if (r) return r;
-    if (d_n) VRT_HIP(c, hipMemcpyAsync(out_normal, d_n, nb, hipMemcpyDeviceToHost, c->stream));
-    if (d_a) VRT_HIP(c, hipMemcpyAsync(out_albedo, d_a, ab, hipMemcpyDeviceToHost, c->stream));
-    if (d_z) VRT_HIP(c, hipMemcpyAsync(out_depth, d_z, db, hipMemcpyDeviceToHost, c->stream));
-    if (d_h) VRT_HIP(c, hipMemcpyAsync(out_hit, d_h, hb, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(256);
+    const int o = st.in((origin_stride ? n : 1) * 3 * sizeof(float), origins), d = st.in(n * 3 * sizeof(float), dirs);
+    const int normal = st.out(out_normal ? n * 12 : 0, out_normal), albedo = st.out(out_albedo ? n * 16 : 0, out_albedo);
+    const int depth = st.out(out_depth ? n * 4 : 0, out_depth), hit = st.out(out_hit ? n : 0, out_hit);
+    if ((r = st.reserve_staging(c, c->d_rays)) || (r = st.upload(c, c->stream))) return r;
+    r = guide_batch(c, n, st.at<float>(o), origin_stride, st.at<float>(d), width, st.at<float>(normal), st.at<float>(albedo), st.at<float>(depth),
+                    st.at<uint8_t>(hit), c->stream);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_guide_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, void *d_normal,

@@ -5,6 +5,8 @@
 //   vrt_devbuf.h       DevBuf<T>, the owner of every device buffer below: reserve() is the one way to grow, the destructor the one
 //                      free. A new buffer is a DevBuf member, its owner waits for what may still use the old block in front of
 //                      reserve(), and vrt_destroy gets no line for it
+//   vrt_stage.h        Stage, the staging of every entry point that takes host buffers: the planes a call declares give the size of
+//                      its block, each plane's device pointer, the copies up, the copies down and the final wait
 //   vrt_scene.cpp      create / destroy, uniforms, camera, uploads, the layouts on the device (ensure_analysis); what every launch
 //                      takes from them: the scene and light blocks of KArgs, the base variant, the profiling slot; growth of the
 //                      buffers the context's stream orders (reserve_synced: scratch images, staging, the accumulation's groups)
@@ -121,7 +123,7 @@ struct vrt_ctx {
     size_t hdr_scratch_pixels = 0;
     // the guided filter's scratch (vrt_filter.cpp): the packed guides and the two level images of vrt_filter_hdr and vrt_filter_hdr_var,
     // shared by their calls on any stream -- `done` is recorded after each call's launches and awaited by a call on another stream --
-    // and the staging of their host forms (inputs and outputs, 64 bytes per pixel, 72 with the variance planes)
+    // and the staging of their host forms (inputs and outputs: vrt_filter.cpp declare())
     struct FilterScratch {
         DevBuf<float4> d_pack, d_ping, d_pong;
         hipEvent_t done = nullptr;
@@ -134,7 +136,7 @@ struct vrt_ctx {
         ~FilterScratch() { if (done) (void)hipEventDestroy(done); }
     };
     FilterScratch filter;
-    // the staging of vrt_temporal_hdr_host (vrt_temporal.cpp): both histories, the inputs and the outputs, 144 bytes per pixel
+    // the staging of vrt_temporal_hdr_host (vrt_temporal.cpp, where its planes are declared): both histories, the inputs and the outputs
     DevBuf<float4> d_temporal;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     DevBuf<void> d_query;
@@ -291,9 +293,9 @@ struct vrt_ctx {
         uint32_t guide_total = 0;
         DevBuf<void> d_guides;                   // vrt_guides.h State: 40 bytes per pixel
         size_t guide_pixels = 0;                 // what it was last sized for
-        DevBuf<float> d_gout;                    // vrt_accum_guides' four planes on their way to the host (9 floats per pixel)
-        DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp, 64 or 72 bytes per pixel);
-                                                 // vrt_accum_resolve_hdr_temporal*: the same and the integrated image (vrt_temporal.cpp, 84, or 180 with the host form's histories)
+        DevBuf<float> d_gout;                    // vrt_accum_guides' four planes on their way to the host
+        DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp declare());
+                                                 // vrt_accum_resolve_hdr_temporal*: those, the integrated image and the host form's histories (vrt_temporal.cpp temporal_accum())
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
@@ -414,6 +416,8 @@ hipError_t launch_accum_step(vrt_ctx::Accum &ac, vrt::KArgs &a, vrt::ViewSet &vs
                              const vrt::LensSel &lsel, const AccumStep &acc, hipStream_t s);
 // does the next sample still belong to the samples in the sums? (what vrt_accum_add's restart rule compares)
 bool accum_inputs_current(const vrt_ctx *c);
+// the call-order checks of everything that reads the accumulation, in the name of `what`: begun, holds samples, and with need_hdr keeps HDR sums
+int accum_state(vrt_ctx *c, const char *what, bool need_hdr);
 // A read of the accumulation on stream s, ordered against the context's: the samples were added on the context's stream, and later adds must not
 // overtake this read (nor, through `read`, the last call's use of the float mean). Nothing to do when s is the context's stream.
 template <class BODY>

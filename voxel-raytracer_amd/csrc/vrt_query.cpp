@@ -1,6 +1,6 @@
 // vrt_query.cpp -- the world queries of include/vrt.h (vrt_cast_rays, vrt_cast_rays_device, vrt_find_voxels): call-order
 // checks, the scene block of the kernel arguments (fill_scene_args), and the device buffers the host-buffer forms stage through.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 #include "vrt_launch.h"
 
 #include <cstring>
@@ -64,8 +64,6 @@ int cast(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const 
     return VRT_OK;
 }
 
-inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
-
 }  // namespace
 
 extern "C" {
@@ -76,21 +74,12 @@ int vrt_cast_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride,
     if (r || n == 0) return r;
     static_assert(sizeof(vrt_ray_hit) == sizeof(vrt::query::RayHit), "vrt_ray_hit and the kernel's record differ");
     VRT_HIP(c, hipSetDevice(c->device));
-    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
-    const size_t out_bytes = n * sizeof(vrt_ray_hit);
-    r = reserve_staging(c, c->d_query, align256(o_bytes) + align256(d_bytes) + out_bytes);   // kept by the context: grown, never shrunk
-    if (r) return r;
-    char *base = static_cast<char *>(c->d_query.get());
-    float *d_o = reinterpret_cast<float *>(base);
-    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
-    auto *d_out = reinterpret_cast<vrt::query::RayHit *>(base + align256(o_bytes) + align256(d_bytes));
-    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
-    r = cast(c, n, d_o, origin_stride, d_d, box_min, box_max, d_out, c->stream);
-    if (r) return r;
-    VRT_HIP(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(256);
+    const int o = st.in((origin_stride ? n : 1) * 3 * sizeof(float), origins), d = st.in(n * 3 * sizeof(float), dirs);
+    const int hits = st.out(n * sizeof(vrt_ray_hit), out);
+    if ((r = st.reserve_staging(c, c->d_query)) || (r = st.upload(c, c->stream))) return r;   // kept by the context: grown, never shrunk
+    r = cast(c, n, st.at<float>(o), origin_stride, st.at<float>(d), box_min, box_max, st.at<vrt::query::RayHit>(hits), c->stream);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_cast_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs,
@@ -112,19 +101,13 @@ int vrt_find_voxels(vrt_ctx *c, size_t n, const int32_t *coords, uint32_t *out) 
     vrt::KArgs a;
     r = scene_args(c, a);
     if (r) return r;
-    const size_t bytes = n * 3 * sizeof(uint32_t);
-    r = reserve_staging(c, c->d_query, 2 * align256(bytes));
-    if (r) return r;
-    char *base = static_cast<char *>(c->d_query.get());
-    vrt::query::PointArgs q;
-    q.coords = reinterpret_cast<const int32_t *>(base);
-    q.out = reinterpret_cast<uint32_t *>(base + align256(bytes));
-    q.n = (uint32_t)n;
-    VRT_HIP(c, hipMemcpyAsync(base, coords, bytes, hipMemcpyHostToDevice, c->stream));
+    vrt_stage::Stage st(256);
+    const int pts = st.in(n * 3 * sizeof(int32_t), coords), found = st.out(n * 3 * sizeof(uint32_t), out);
+    st.kept(0);   // the block ends on the alignment, as it always has
+    if ((r = st.reserve_staging(c, c->d_query)) || (r = st.upload(c, c->stream))) return r;
+    const vrt::query::PointArgs q{st.at<const int32_t>(pts), st.at<uint32_t>(found), (uint32_t)n};
     VRT_HIP(c, vrt::launch::find_voxels(a, q, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(out, q.out, bytes, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    return st.download(c, c->stream);
 }
 
 }  // extern "C"

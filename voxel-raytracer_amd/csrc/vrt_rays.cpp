@@ -2,7 +2,7 @@
 // argument checks, the kernel arguments -- the scene and the uniforms as a frame launch carries them, and nothing of a camera: no
 // eye lookup, first lookup, ray table, miss mask, tightened root or tile order -- and the device buffers the host form stages
 // through. Reads no camera, lens or accumulation state and writes none.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 #include "vrt_launch.h"
 
 #include <cstring>
@@ -42,12 +42,7 @@ int check_hdr(vrt_ctx *c, size_t n, const void *origins, int origin_stride, cons
     if (r) return r;
     if (n_prior != 0u && !sums) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": n_prior without sums");
     if ((uint64_t)n_prior + n_samples > ((uint64_t)1 << 24)) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": more than 2^24 samples in all");
-    if (tm) {
-        if (tm->op != VRT_TONEMAP_CLAMP && tm->op != VRT_TONEMAP_REINHARD) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": unknown tone-map operator");
-        if (!(tm->exposure > 0.0f) || !(tm->exposure <= 3.402823466e38f))
-            return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": exposure must be finite and > 0");
-    }
-    return VRT_OK;
+    return check_tonemap(c, what, tm);
 }
 
 // The launch: the scene and light blocks of KArgs as a frame carries them (vrt_scene.cpp), and nothing derived from an eye
@@ -106,8 +101,6 @@ int shade(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride, const
     return VRT_OK;
 }
 
-inline size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
-
 }  // namespace
 
 void vrt_internal::fill_ray_batch_args(const vrt_ctx *c, size_t n, int width, vrt::KArgs &a, vrt::ViewSet &vs) {
@@ -133,23 +126,13 @@ int vrt_shade_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride
     int r = check(c, n, origins, origin_stride, dirs, width, mode, n_samples, out_rgba8 || out_id_dist, "vrt_shade_rays");
     if (r || n == 0) return r;
     VRT_HIP(c, hipSetDevice(c->device));
-    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
-    const size_t rgba_bytes = out_rgba8 ? n * 4 : 0, id_bytes = out_id_dist ? n * 8 : 0;
-    r = reserve_staging(c, c->d_rays, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + id_bytes);   // kept by the context: grown, never shrunk
-    if (r) return r;
-    char *base = static_cast<char *>(c->d_rays.get());
-    float *d_o = reinterpret_cast<float *>(base);
-    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
-    uint32_t *d_rgba = out_rgba8 ? reinterpret_cast<uint32_t *>(base + align256(o_bytes) + align256(d_bytes)) : nullptr;
-    int2 *d_id = out_id_dist ? reinterpret_cast<int2 *>(base + align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes)) : nullptr;
-    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
-    r = shade(c, n, d_o, origin_stride, d_d, width, mode, first_sample, n_samples, d_rgba, d_id, c->stream);
-    if (r) return r;
-    if (d_rgba) VRT_HIP(c, hipMemcpyAsync(out_rgba8, d_rgba, rgba_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (d_id) VRT_HIP(c, hipMemcpyAsync(out_id_dist, d_id, id_bytes, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(256);
+    const int o = st.in((origin_stride ? n : 1) * 3 * sizeof(float), origins), d = st.in(n * 3 * sizeof(float), dirs);
+    const int rgba = st.out(out_rgba8 ? n * 4 : 0, out_rgba8), id = st.out(out_id_dist ? n * 8 : 0, out_id_dist);
+    if ((r = st.reserve_staging(c, c->d_rays)) || (r = st.upload(c, c->stream))) return r;   // kept by the context: grown, never shrunk
+    r = shade(c, n, st.at<float>(o), origin_stride, st.at<float>(d), width, mode, first_sample, n_samples, st.at<uint32_t>(rgba), st.at<int2>(id),
+              c->stream);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_shade_rays_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, int mode,
@@ -168,27 +151,15 @@ int vrt_shade_rays_hdr(vrt_ctx *c, size_t n, const float *origins, int origin_st
                       "vrt_shade_rays_hdr");
     if (r || n == 0) return r;
     VRT_HIP(c, hipSetDevice(c->device));
-    const size_t o_bytes = (origin_stride ? n : 1) * 3 * sizeof(float), d_bytes = n * 3 * sizeof(float);
-    const size_t rgba_bytes = out_rgba8 ? n * 4 : 0, id_bytes = out_id_dist ? n * 8 : 0, rgb_bytes = out_rgb ? n * 12 : 0;
-    r = reserve_staging(c, c->d_rays, align256(o_bytes) + align256(d_bytes) + align256(rgba_bytes) + align256(id_bytes) + rgb_bytes);
-    if (r) return r;
-    char *base = static_cast<char *>(c->d_rays.get());
-    float *d_o = reinterpret_cast<float *>(base);
-    float *d_d = reinterpret_cast<float *>(base + align256(o_bytes));
-    char *out = base + align256(o_bytes) + align256(d_bytes);
-    uint32_t *d_rgba = out_rgba8 ? reinterpret_cast<uint32_t *>(out) : nullptr;
-    int2 *d_id = out_id_dist ? reinterpret_cast<int2 *>(out + align256(rgba_bytes)) : nullptr;
-    float *d_rgb = out_rgb ? reinterpret_cast<float *>(out + align256(rgba_bytes) + align256(id_bytes)) : nullptr;
-    VRT_HIP(c, hipMemcpyAsync(d_o, origins, o_bytes, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(d_d, dirs, d_bytes, hipMemcpyHostToDevice, c->stream));
-    const Hdr hdr{nullptr, d_rgb, 0u, tm};
-    r = shade(c, n, d_o, origin_stride, d_d, width, mode, first_sample, n_samples, d_rgba, d_id, c->stream, &hdr);
-    if (r) return r;
-    if (d_rgba) VRT_HIP(c, hipMemcpyAsync(out_rgba8, d_rgba, rgba_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (d_id) VRT_HIP(c, hipMemcpyAsync(out_id_dist, d_id, id_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (d_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(256);
+    const int o = st.in((origin_stride ? n : 1) * 3 * sizeof(float), origins), d = st.in(n * 3 * sizeof(float), dirs);
+    const int rgba = st.out(out_rgba8 ? n * 4 : 0, out_rgba8), id = st.out(out_id_dist ? n * 8 : 0, out_id_dist);
+    const int rgb = st.out(out_rgb ? n * 12 : 0, out_rgb);
+    if ((r = st.reserve_staging(c, c->d_rays)) || (r = st.upload(c, c->stream))) return r;
+    const Hdr hdr{nullptr, st.at<float>(rgb), 0u, tm};
+    r = shade(c, n, st.at<float>(o), origin_stride, st.at<float>(d), width, mode, first_sample, n_samples, st.at<uint32_t>(rgba), st.at<int2>(id),
+              c->stream, &hdr);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_shade_rays_hdr_device(vrt_ctx *c, size_t n, const void *d_origins, int origin_stride, const void *d_dirs, int width, int mode,

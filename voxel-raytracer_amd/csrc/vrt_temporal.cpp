@@ -4,7 +4,7 @@
 // float mean and its own guide planes into the accumulation's filter stage, runs the pass on them with the context's current camera
 // block and the variance-guided filter on what it returns (temporal_accum). Host code; the kernel is behind vrt_launch.h. Nothing
 // here touches the accumulation's sums.
-#include "vrt_internal.h"
+#include "vrt_stage.h"
 #include "vrt_launch.h"
 
 #include <cmath>
@@ -15,10 +15,6 @@ using namespace vrt_internal;
 namespace {
 
 constexpr size_t kHistory = vrt::temporal::kHistoryBytes;
-// the staging of the host form: both histories, rgb, normal, depth, coverage, the integrated image and the variance
-constexpr size_t kHostStageBytes = 2 * kHistory + 12 + 12 + 4 + 4 + 12 + 4;
-// the accumulation's stage: mean 3, normal 3, albedo 4, depth, coverage, integrated 3, variance, out_rgb 3, out_rgba8, out_variance
-constexpr size_t kAccumStageFloats = 21;
 
 bool all_finite(const float *v, int n) {
     for (int i = 0; i < n; ++i)
@@ -113,66 +109,46 @@ int temporal_frame(vrt_ctx *c, const char *what, int width, int height, const fl
     return VRT_OK;
 }
 
-inline size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
-
 // The accumulation forms: mean and planes into the accumulation's stage, the pass on them, the filter on its outputs. to_host: the
 // histories and the outputs are the caller's host buffers, staged behind the stage's planes and filled on the context's stream
 // before the return; else device memory, read and written in the order of `stream`.
 int temporal_accum(vrt_ctx *c, const char *what, const vrt_temporal *t, const vrt_filter_var *f, const vrt_tonemap *tm, bool to_host,
                    const void *history_in, void *history_out, void *out_integrated, void *out_rgb, void *out_rgba8, void *out_variance,
                    void *stream) {
-    if (!c) return VRT_E_INVALID;
-    // the call-order checks: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
-    if (!c->accum.begun) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no accumulation (call vrt_accum_begin first)");
-    if (c->accum.total == 0) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation holds no samples (call vrt_accum_add first)");
-    if (!c->accum.hdr) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no HDR sums (vrt_accum_keep_hdr before the begin)");
+    int r = accum_state(c, what, true);   // the call-order checks: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
+    if (r) return r;
     if (!history_out) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null history_out");
     if (history_out == history_in) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": history_out must differ from history_in");
-    int r = check_params(c, what, t, history_in != nullptr);
-    if (r) return r;
+    if ((r = check_params(c, what, t, history_in != nullptr))) return r;
     if ((r = filter_var_check(c, what, f, tm, out_rgb, out_rgba8))) return r;
     if ((r = check_camera(c, what, c->inv_proj, c->inv_view, c->cam_pos))) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     vrt_ctx::Accum &ac = c->accum;
     const size_t px = (size_t)ac.width * (size_t)ac.height;
-    const size_t plane_bytes = px * kAccumStageFloats * sizeof(float);
-    const size_t bytes = to_host ? align16(plane_bytes) + 2 * px * kHistory : plane_bytes;
-    if (bytes > ac.d_filter.bytes() && (r = reserve_synced(c, {{&ac.d_filter, bytes}}))) return r;
-    float *const base = ac.d_filter;
-    float *const mean = base, *const normal = base + px * 3, *const albedo = base + px * 6, *const depth = base + px * 10,
-                 *const coverage = base + px * 11, *const st_integ = base + px * 12, *const variance = base + px * 15,
-                 *const st_rgb = base + px * 16, *const st_rgba = base + px * 19, *const st_var = base + px * 20;
-    char *const st_hin = reinterpret_cast<char *>(base) + align16(plane_bytes), *const st_hout = st_hin + px * kHistory;
+    // the accumulation's stage: the mean, its planes, the pass's integrated image and variance, the filter's outputs; the host form's
+    // histories behind them, as the 16-byte words the pass reads -- device histories are the caller's and take no room
+    vrt_stage::Stage st(4, to_host);
+    const int mean = st.kept(px * 12), normal = st.kept(px * 12), albedo = st.kept(px * 16), depth = st.kept(px * 4), coverage = st.kept(px * 4);
+    const int integrated = st.kept(px * 12, out_integrated), variance = st.kept(px * 4);
+    const int f_rgb = st.out(px * 12, out_rgb), f_rgba = st.out(px * 4, out_rgba8), f_var = st.out(px * 4, out_variance);
+    if (to_host) st.align = 16;
+    const int hin = st.in(to_host ? px * kHistory : 0, history_in), hout = st.out(to_host ? px * kHistory : 0, history_out);
+    if ((r = st.reserve_synced(c, ac.d_filter))) return r;
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((r = vrt_accum_guides_device(c, normal, albedo, depth, coverage, s))) return r;   // brings the guide state up to date first
-    if ((r = vrt_accum_resolve_hdr_device(c, mean, tm, nullptr, nullptr, s))) return r;
+    if ((r = vrt_accum_guides_device(c, st.at(normal), st.at(albedo), st.at(depth), st.at(coverage), s))) return r;   // brings the guide state up to date first
+    if ((r = vrt_accum_resolve_hdr_device(c, st.at(mean), tm, nullptr, nullptr, s))) return r;
     vrt_temporal tt = *t;
     tt.offset_x = tt.offset_y = (ac.flags & VRT_ACCUM_JITTER) ? 0.5f : 0.0f;
-    Io d{mean, normal, depth, coverage, history_in, history_out, out_integrated ? out_integrated : st_integ, variance};
-    void *f_rgb = out_rgb, *f_rgba = out_rgba8, *f_var = out_variance;
-    if (to_host) {
-        if (history_in) VRT_HIP(c, hipMemcpyAsync(st_hin, history_in, px * kHistory, hipMemcpyHostToDevice, s));
-        d.history_in = history_in ? st_hin : nullptr;
-        d.history_out = st_hout;
-        d.out_rgb = st_integ;
-        f_rgb = out_rgb ? st_rgb : nullptr;
-        f_rgba = out_rgba8 ? st_rgba : nullptr;
-        f_var = out_variance ? st_var : nullptr;
-    }
+    if ((r = st.upload(c, s))) return r;
+    const Io d{st.at(mean), st.at(normal), st.at(depth), st.at(coverage), st.at(hin), st.at(hout), st.at(integrated), st.at(variance)};
     // the stage belongs to the accumulation, whose every use the context's stream orders: a caller's stream is joined back
     r = accum_joined(c, s, [&] {
         const int rt = temporal_frame(c, what, ac.width, ac.height, c->inv_proj, c->inv_view, c->cam_pos, d, &tt, s);
         if (rt) return rt;
-        return filter_var_frame(c, what, ac.width, ac.height, d.out_rgb, normal, albedo, depth, coverage, variance, f, tm, f_rgb, f_rgba, f_var, s);
+        return filter_var_frame(c, what, ac.width, ac.height, d.out_rgb, d.normal, st.at(albedo), d.depth, d.coverage, d.out_variance, f, tm,
+                                st.at(f_rgb), st.at(f_rgba), st.at(f_var), s);
     });
-    if (r || !to_host) return r;
-    VRT_HIP(c, hipMemcpyAsync(history_out, st_hout, px * kHistory, hipMemcpyDeviceToHost, c->stream));
-    if (out_integrated) VRT_HIP(c, hipMemcpyAsync(out_integrated, st_integ, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st_rgb, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgba8) VRT_HIP(c, hipMemcpyAsync(out_rgba8, st_rgba, px * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) VRT_HIP(c, hipMemcpyAsync(out_variance, st_var, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    return r ? r : st.download(c, c->stream);
 }
 
 }  // namespace
@@ -210,23 +186,14 @@ int vrt_temporal_hdr_host(vrt_ctx *c, int width, int height, const float inv_pro
     if ((r = check_camera(c, what, inv_projection, inv_view, camera_pos))) return r;
     VRT_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)width * (size_t)height;
-    if (px * kHostStageBytes > c->d_temporal.bytes() && (r = reserve_synced(c, {{&c->d_temporal, px * kHostStageBytes}}))) return r;
-    char *const base = reinterpret_cast<char *>(c->d_temporal.get());
-    char *const st_hin = base, *const st_hout = base + px * kHistory;
-    float *const st_rgb = reinterpret_cast<float *>(base + 2 * px * kHistory), *const st_normal = st_rgb + px * 3, *const st_depth = st_rgb + px * 6,
-                 *const st_cov = st_rgb + px * 7, *const st_out = st_rgb + px * 8, *const st_var = st_rgb + px * 11;
-    if (history_in) VRT_HIP(c, hipMemcpyAsync(st_hin, history_in, px * kHistory, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st_rgb, rgb, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st_normal, normal, px * 12, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st_depth, depth, px * 4, hipMemcpyHostToDevice, c->stream));
-    VRT_HIP(c, hipMemcpyAsync(st_cov, coverage, px * 4, hipMemcpyHostToDevice, c->stream));
-    const Io d{st_rgb, st_normal, st_depth, st_cov, history_in ? st_hin : nullptr, st_hout, out_rgb ? st_out : nullptr, out_variance ? st_var : nullptr};
-    if ((r = temporal_frame(c, what, width, height, inv_projection, inv_view, camera_pos, d, t, c->stream))) return r;
-    VRT_HIP(c, hipMemcpyAsync(history_out, st_hout, px * kHistory, hipMemcpyDeviceToHost, c->stream));
-    if (out_rgb) VRT_HIP(c, hipMemcpyAsync(out_rgb, st_out, px * 12, hipMemcpyDeviceToHost, c->stream));
-    if (out_variance) VRT_HIP(c, hipMemcpyAsync(out_variance, st_var, px * 4, hipMemcpyDeviceToHost, c->stream));
-    VRT_HIP(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
+    vrt_stage::Stage st(4);   // both histories, the inputs, the integrated image and the variance
+    const int hin = st.in(px * kHistory, history_in), hout = st.out(px * kHistory, history_out);
+    const int s_rgb = st.in(px * 12, rgb), s_normal = st.in(px * 12, normal), s_depth = st.in(px * 4, depth), s_cov = st.in(px * 4, coverage);
+    const int s_out = st.out(px * 12, out_rgb), s_var = st.out(px * 4, out_variance);
+    if ((r = st.reserve_synced(c, c->d_temporal)) || (r = st.upload(c, c->stream))) return r;
+    const Io d{st.at(s_rgb), st.at(s_normal), st.at(s_depth), st.at(s_cov), st.at(hin), st.at(hout), st.at(s_out), st.at(s_var)};
+    r = temporal_frame(c, what, width, height, inv_projection, inv_view, camera_pos, d, t, c->stream);
+    return r ? r : st.download(c, c->stream);
 }
 
 int vrt_accum_resolve_hdr_temporal(vrt_ctx *c, const vrt_temporal *t, const vrt_filter_var *f, const vrt_tonemap *tm, const void *history_in,
