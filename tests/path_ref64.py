@@ -100,12 +100,76 @@ Jittered and thin-lens samples of the accumulation enter through PathTrace.lens:
 in float64 with a per-ray origin bound (err3 / lo3) and direction bound (dir_err), and _run carries both as it does a
 batch's.
 
+Path depth, sun disc, emitter sampling, emitter importance and emitter MIS (include/vrt.h under those titles; depth=,
+tan_radius=, emit= and mis= of the three constructors; the defaults give the shader, bit for bit what this module gave
+before it took them). Restated from the header's text alone -- not from the kernels, not from the C checkers; tests/deep_ref64.py
+holds the sun's basis and direction, the emitter list, weights and thresholds, and the discrete choices.
+  * Path depth. The opaque, non-emissive branch of a ray of depth d: d < D casts the shadow ray, adds the direct term, takes
+    its draws and pushes the bounce of depth d + 1 with distanceInMedium 0; it adds no ambient term. d >= D (d >= 1 at D = 1)
+    takes the terminal ambient branch. Translucent surfaces below depth 0 are diffuse (they were already), so a chain is
+    linear: a pop precedes every push. err3, lo3, edim and the relative colour error pass from vertex to vertex as they did
+    from depth 0 to depth 1.
+  * The order of a vertex's draws: u1, u2 of the sun (if its radius is > 0), then u0, uf, ua, ub of the connection (if
+    sampling is on and the list is not empty), then the bounce's two.
+  * Sun disc. L' from deep_ref64.sun_dirs; notInShadow from hitPoint + normal * 2e-3 along L' with the per-ray direction bound
+    deep_ref64.sun_dir_err (derived there; R.not_in_shadow adds dir_err * t per step and leaves a ray with a component within
+    the direction margin of 0 undecided); ndotl' = max(dot(normal, L'), 0) is continuous: its absolute error, the same bound,
+    goes into the colour bound (cerr += the term at ndotl' = 1 times the bound). The translucent branch keeps ndotl from L.
+  * Emitter connections (_connect). x = hitPoint + normal * 1e-1 with the bounce origin's per-axis bound ex3. j, f, t, i, p in
+    exact float32 (deep_ref64). q: the face coordinate is an exact integer, the other two lo + u * sz round twice (u * sz and
+    the sum): u (u sz) + u |q|. w = q - x has e3 = ex3 + xe3 (below) + eq + u |w| per axis; r2 and dir = w / |w| in float64;
+    dir's bound is R.GIVEN_DIR_ERR (the float32 normalisation, relative, <= absolute for a unit vector) + |e3|_2 / r: the
+    projection (I - n n^T) dw / r does not lengthen dw. cs > 0, cl > 0 and r2 > 0 are undecided within that bound of 0; the
+    visible-face tests x[k] < lo[k], x[k] > lo[k] + sz within ex3[k] + xe3[k] of the plane. The connection is marched with march() from
+    x with ex3 + xe3 and that direction bound, rayIOF n1; the in-cube test is undecided where a coordinate of the hit other
+    than the crossed one lies within the floor margin of a face of the cube. The hit is evaluated as a deeper ray's
+    (distanceInMedium from x, the absorption in the last voxel's medium, the highlight inversion, emission = props[1] * 10).
+    g's relative error, dir_err / cs + dir_err / cl + 2 |e3|_2 / r + 14u (its products, quotients and E_k's), joins the ray's
+    colour bound. Rule 7 is a branch: with sampling on a deeper ray that finds an emitter adds nothing.
+  * MIS (_mis_density). pl and pb in float64 from x, dir, cs and the hit: m of the hit CELL, w of the hit voxel's words,
+    inv_power the float32 of 1.0 / Wtot. The visible-axis tests are undecided within ex3 + xe3 of their planes, !(pl > 0) where cl
+    lies within dir's bound of 0 (m and w are integers), and pb's bound is relative, so cs within it of 0 is undecided too.
+    rel(pl) = 2 |e_v|_2 / r + dir_err / cl + 8u with e_v the bound of hit.point - x, rel(pb) = dir_err / cs + 2u;
+    wn = pl / (pl + pb) and wb = pb / (pl + pb) move by (1 - w) (rel(pl) + rel(pb)) relative. A contributing connection ends
+    on the face it aimed at (a face turned towards x is its cube's first along the line), so its hit is q within the march's
+    own roundings wherever the float32 x lies. The bounce keeps cb = dot(normal, bd) (bound: BOUNCE_DIR_ERR) in the ray.
+  * What the float comparison found missing, again: a VERTEX's error across its ray. m.line (above) entered only the distance
+    in a medium. A connection reads the vertex itself -- cl = w[ax] / r at a grazing face is w[ax] over a coordinate of x --
+    and after two bounces the float32 vertex lay 3.6e-4 from this module's, 40 times its per-axis bound. Every ray now carries
+    xerr[3], what its origin may be off by beyond err3: at a hit on a plane of axis b the point moves by e_a + e_b |d_a / d_b|
+    in coordinate a and not at all in b (so floor-ceiling-floor chains do not amplify it), plus the march's own m.line3. It
+    enters everything continuous of a connection and of an MIS density, and the connection's march. And corners: where a step
+    lands within the margin of a plane of another axis, the float32 run may cross that plane first and be in the cell on
+    the near side of the crossed axis, which R._floor_undecided's alternatives do not hold; a connection aimed at the rim
+    of an emitter's face met exactly that (hit there, missed here). march(corners=True), for connections, tries that cell
+    too. And the distance in a medium: a ray of depth >= 2 starts from a vertex its chain has moved and ends on one it
+    moves on, so its length carries |xerr|_2 of both ends in edim (a connection's, |xe3|_2 of its vertex). Rays aimed into
+    the dragon's penumbrae found it: a last segment 0.15 voxels long after five bounces, whose terminal ambient term
+    1 - exp(-dim / 512) is relative to that length, lay 2.3e-3 off at D = 6 and D = 8 under a bound of 4e-4.
+  * Known unsound: the floor margins of the shadow and bounce marches at inner vertices (depth >= 1) still take the per-axis
+    bound err3 without xerr. The float32 vertex may lie xerr further (3.6e-4 seen, 40 times err3), so a step of such a march
+    that passes a cell boundary closer than xerr is decided here although the float32 run may take the other cell. This
+    cannot hide a wrong kernel (a decided ray is compared exactly); it can fail a right one on a batch other than the
+    tests'. No decided ray of any batch at any setting disagrees. With xerr in those margins every comparison still holds,
+    but the undecided share of the lamp room at (8, 0.05, mis) rises from 23 % to 36 %, over the ceiling of 0.30 that the
+    tests keep, and the other shares by a tenth to a half; the margins wait for a bound on xerr that does not grow with
+    every change of the hit axis.
+  * STATS per pixel: shadowing, inner and terminal vertices, vertices whose lit differs from the point sun's, connections
+    drawn, marched and contributing, bounce hits on emitters weighted by MIS; self.why counts which rule of a connection
+    left a pixel undecided.
+
 Not restated: origins outside the world, the display pass of a mode-2 frame (shader_ref64.display covers quad.frag), the
-adaptive rule of the accumulation (tied to its own restatement), INDIRECT_SAMPLES / BOUNCES other than 1.
+adaptive rule of the accumulation (tied to its own restatement), INDIRECT_SAMPLES other than 1.
+
+DEEP_FLAWS plants the misreadings of these rules that a kernel and its checker could share. One replaces the name first
+thought of: "wb applied where !(pl > 0)" cannot be told from the rule by construction -- pl = 0 there, so pb / (pl + pb) is
+1, the value the rule states -- and mis_wb_cosine_at_hit (the bounce's pb from the cosine at the hit, not from cb) stands
+in for it as the misreading of the bounce's weight.
 
 flaws= plants one plausible misreading at a time, so the tests can show that the comparison catches it."""
 import numpy as np
 
+import deep_ref64 as DR
 import shader_ref64 as R
 
 U = R.U
@@ -121,6 +185,10 @@ _F1E4 = np.float32(1e-4)
 
 FLAWS = ("fifo", "exit_swap", "dim_no_scale", "bounce_offset", "no_pi_deep", "rng_row", "no_miss_absorption",
          "id_reflect_first", "id_zero_locks")
+# misreadings of the path depth, the sun disc and the emitter rules (tests/test_deep_reference64.py)
+DEEP_FLAWS = ("inner_ambient", "inner_keeps_dim", "depth_off_by_one", "sun_draws_after_bounce", "sun_unit_length", "sun_glass_ndotl",
+              "emit_origin_2e3", "emit_draw_order", "emit_keeps_bounce_emission", "emit_any_emitter", "power_six_faces", "power_no_p",
+              "mis_m_of_cube", "mis_wb_cosine_at_hit")
 
 
 def _pcg(st):
@@ -194,7 +262,36 @@ class _March:
     pass
 
 
-def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=None):
+def _corner_undecided(w, new, mp, ax, sgn, cur, nxt, near):
+    """a step that lands within the margin of a plane of another axis j (`near`) may, in float32, cross that plane first: the run
+    is then in the cell on the far side of j and the near side of the crossed axis, which the alternatives of R._floor_undecided
+    (all on the far side of the crossed axis) do not hold. True where that cell belongs to neither the node left nor the node
+    entered (a connection aimed at the rim of an emitter's face clips such corners)"""
+    und = np.zeros(new.shape[0], bool)
+    rows = np.nonzero(near.any(1))[0]
+    if not rows.size:
+        return und
+    other = np.array([[1, 2], [0, 2], [0, 1]])[ax[rows]]
+    for pick in ((0,), (1,), (0, 1)):
+        js = other[:, list(pick)]
+        ok = np.all(near[rows[:, None], js], 1)
+        q, jq = rows[ok], js[ok]
+        if not q.size:
+            continue
+        alt = mp[q].copy()
+        alt[np.arange(q.size), ax[q]] -= sgn[q].astype(np.int64)
+        for c in range(jq.shape[1]):
+            j = jq[:, c]
+            v = new[q, j]
+            alt[np.arange(q.size), j] += np.where(v >= np.rint(v), -1, 1)
+        inw = w.in_world(alt)
+        node = np.full(q.size, -2, np.int64)
+        node[inw] = w.find(alt[inw])
+        und[q[(node != cur[q]) & (node != nxt[q])]] = True
+    return und
+
+
+def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=None, corners=False):
     """hitMarching (comp:248-330) for rays from grid-space origins org[n, 3] (per-axis error err3) with rayIOF iof.
     oax: an axis whose start floor is already decided (-1: none); lock_ax / lock_p: a coordinate that moves away from
     the plane lock_p and cannot cross it again (-1: none); lo3: per-axis error the ray's line keeps however often a
@@ -213,6 +310,7 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=N
     m.snap = np.zeros(n, bool)
     m.P = np.zeros(n)
     m.line = np.zeros(n)
+    m.line3 = np.zeros((n, 3))
     if not n:
         return m
     small = np.any((d != 0) & (np.abs(d) < np.maximum(R.DIR_MARGIN, 2.0 * dir_err)[:, None]), 1)
@@ -256,6 +354,8 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=N
         nxt[go] = w.find(mp[go])
         near = (ax_in & ~stuck)[:, None] & (fr < R.DELTA_FLOOR + R.DELTA_SAFETY * e)
         m.amb[act] |= R._floor_undecided(w, new, mp, nxt, near)
+        if corners:
+            m.amb[act] |= _corner_undecided(w, new, mp, ax, np.sign(dax), cur, nxt, near)
         sn = (8.0 * U * (span + e[r, ax]) < _spacing_below(P) / 2) & ~near.any(1)
         s32 = np.sign(dax).astype(np.float32)
         new[sn, ax[sn]] = (P[sn].astype(np.float32) + s32[sn] * _F1E4).astype(np.float32)
@@ -283,6 +383,7 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=N
         m.mp[h], m.pt[h], m.ax[h] = mp[hit], new[hit], ax[hit]
         m.hv[h], m.lv[h], m.snap[h], m.P[h] = nxt[hit], prev[hit], sn[hit], P[hit]
         m.line[h] = line[hit].max(1)
+        m.line3[h] = line[hit]
         node[act] = nxt
         act = act[go & ~hit]
     m.amb[act] = True                                                          # capped while still moving
@@ -291,19 +392,22 @@ def march(w, org, err3, d, dir_err, iof, oax, lock_ax, lock_p, lo3=None, given=N
 
 
 _FIELDS = {"org": 3, "err3": 3, "lo3": 3, "d": 3, "dir_err": 0, "iof": 0, "w": 0, "tint": 3, "dim": 0, "edim": 0, "mc": 3, "md": 0,
-           "depth": 0, "rel": 0, "oax": 0, "lock_ax": 0, "lock_p": 0, "given": 0}
+           "depth": 0, "rel": 0, "oax": 0, "lock_ax": 0, "lock_p": 0, "given": 0, "cb": 0, "xerr": 3}
 _INT = ("depth", "oax", "lock_ax", "given")
 STATS = ("rays", "peak_stack", "dropped_refract", "tir", "exit_glass", "deep_emission", "deep_sky", "miss_absorbed",
-         "hit_absorbed", "glass_hits", "deep_ambient", "id_zero_hit", "id_reentry")
+         "hit_absorbed", "glass_hits", "deep_ambient", "id_zero_hit", "id_reentry",
+         # per ray, for the path depth, the sun disc and the emitter rules
+         "shadowing", "inner", "terminal", "sun_differs", "conn_drawn", "conn_marched", "conn_contributing", "mis_bounce_hits")
 
 
 class PathTrace:
     """pathTrace in VRT_MODE_FULL for every requested pixel at initRNG sample `sample`; frame() assembles the outputs."""
 
     def __init__(self, world, inv_proj, inv_view, cam_pos, width, height, xs=None, ys=None, sample=0, voxel_scale=1.0,
-                 global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1), flaws=()):
+                 global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1), flaws=(), depth=1, tan_radius=0.0,
+                 emit=None, mis=False):
         """a frame: one origin (cameraPos), ray_dirs' directions, the frame's width"""
-        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws, depth, tan_radius, emit, mis)
         self.W, self.H = int(width), int(height)
         if xs is None:
             ys, xs = np.mgrid[0:self.H, 0:self.W]
@@ -319,11 +423,11 @@ class PathTrace:
 
     @classmethod
     def rays(cls, world, origins, dirs, width, sample=0, voxel_scale=1.0, global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None,
-             highlighted=(-1, -1, -1), flaws=()):
+             highlighted=(-1, -1, -1), flaws=(), depth=1, tan_radius=0.0, emit=None, mis=False):
         """a ray batch (include/vrt.h, "Rays", "Direction", "width"): origins float32 (n, 3) or (3,) shared, in world units;
         dirs float32 (n, 3) as given, any length; ray i of sample `sample` seeds initRNG((i % width, i // width), sample)"""
         self = cls.__new__(cls)
-        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws, depth, tan_radius, emit, mis)
         d, length = R.given_dirs(dirs)
         self.W = int(width)
         self.xs, self.ys = R.batch_pixels(d.shape[0], self.W, self.flaws)
@@ -332,9 +436,17 @@ class PathTrace:
         self._run(np.array(origins, np.float32).astype(np.float64), d, length, given=True)
         return self
 
-    def _uniforms(self, world, voxel_scale, global_light, light_dir, highlighted, flaws):
+    def _uniforms(self, world, voxel_scale, global_light, light_dir, highlighted, flaws, depth=1, tan_radius=0.0, emit=None, mis=False):
+        """the shader's uniforms and the context state of include/vrt.h: depth (the path depth D), tan_radius (the sun disc),
+        emit (None: sampling off; the importance by name) and mis (read only under the power rule with a list that is not empty)"""
         assert light_dir is not None, "lightDir is a uniform: pass the host's float32 value"
-        unknown = set(flaws) - set(FLAWS) - set(R.FLAWS) - set(R.RAY_FLAWS)
+        assert 1 <= int(depth) <= 8 and 0.0 <= float(tan_radius) <= 1.0 and emit in (None, "uniform", "power"), (depth, tan_radius, emit)
+        self.D, self.sun_s = int(depth), float(np.float32(tan_radius))
+        self.em = DR.Emitters(world) if emit is not None else None
+        self.emit = emit if self.em is not None and self.em.N > 0 else None
+        self.mis = bool(mis) and self.emit == "power"
+        self.sun = DR.sun_basis(light_dir) if self.sun_s > 0 else None
+        unknown = set(flaws) - set(FLAWS) - set(R.FLAWS) - set(R.RAY_FLAWS) - set(DEEP_FLAWS)
         assert not unknown, unknown
         self.w, self.flaws = world, frozenset(flaws)
         self.scale = float(np.float32(voxel_scale))
@@ -344,12 +456,12 @@ class PathTrace:
 
     @classmethod
     def lens(cls, world, rays, voxel_scale=1.0, global_light=(1.0, 1.0, 1.0, 1.0), light_dir=None, highlighted=(-1, -1, -1),
-             flaws=()):
+             flaws=(), depth=1, tan_radius=0.0, emit=None, mis=False):
         """a jittered and / or thin-lens sample of the accumulation (include/vrt.h VRT_ACCUM_JITTER, vrt_set_lens): `rays` is
         tests/lens_ref64.py's lens_rays(camera block, W, H, xs, ys, sample, jitter, aperture, focus) -- per-ray float64
         origins and unit directions with the bounds of their float32 counterparts; initRNG(pixel, sample)"""
         self = cls.__new__(cls)
-        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws)
+        self._uniforms(world, voxel_scale, global_light, light_dir, highlighted, flaws, depth, tan_radius, emit, mis)
         self.W, self.H, self.xs, self.ys = rays.W, rays.H, rays.xs, rays.ys
         self.rng = init_rng(self.xs, self.ys, rays.rng_sample, 1920)
         self._run(rays.o, rays.d, np.ones(rays.d.shape[0]), given=False, err3=rays.err_o * abs(self.scale) + U * np.abs(rays.o * self.scale),
@@ -402,6 +514,7 @@ class PathTrace:
         self.first_hit = np.zeros(n, bool)
         self.stats = {k: np.zeros(n, np.int64) for k in STATS}
         self.id_written = np.zeros(n, bool)
+        self.why = {}
         for _ in range(1024):
             act = np.nonzero((self.sp > 0) & ~self.amb)[0]
             if not act.size:
@@ -430,6 +543,11 @@ class PathTrace:
             self.S[k][idx, sl] = v
         self.sp[idx] += 1
         self.stats["peak_stack"][idx] = np.maximum(self.stats["peak_stack"][idx], self.sp[idx])
+
+    def _undecide(self, idx, mask, why):
+        """pixels idx[mask] are undecided; self.why counts the pixels each rule of the emitter connections was first to leave out"""
+        self.why[why] = self.why.get(why, 0) + int((mask & ~self.amb[idx]).sum())
+        self.amb[idx] |= mask
 
     def _add(self, idx, c, rel):
         self.fc[idx] += c
@@ -490,7 +608,23 @@ class PathTrace:
         ln = np.linalg.norm(hpw - org, axis=1) * np.where(r["given"][hi] == 1, self.tlen[idx], 1.0)
         dim = r["dim"][hi] + (ln if "dim_no_scale" in fl else ln / self.scale)  # comp:501
         lerr = m.line[hi] / self.scale                                           # the hit point's deviation across the ray
+        # the same per axis in grid units, with what the ray's origin was off by across its own parent: an origin moved by e moves
+        # the point where the line meets the plane of axis b by e_a + e_b |d_a / d_b| in coordinate a, and not at all in b
+        # (connections and MIS densities read it; two hits in a row on planes of one axis do not amplify it)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            xo = r["xerr"][hi]
+            xe = xo + xo[kr, ax][:, None] * np.abs(d / d[kr, ax][:, None]) + m.line3[hi]
+        xe = np.where(np.isfinite(xe), xe, np.inf)
+        xe[kr, ax] = 0.0
         edim = r["edim"][hi] + lerr + (perr.max(1) + r["err3"][hi].max(1) + 4 * U * (np.abs(hpw).max(1) + np.abs(org).max(1) + ln)) / self.scale
+        # a ray of depth >= 2 starts from a vertex that its chain has moved (xo) and ends on one that it moves on (xe): its length,
+        # and so its distance in the medium, changes by no more than both displacements. A ray of depth 1 starts from the primary
+        # hit, whose deviation it already carries in edim, as at D = 1.
+        chain = dep >= 2
+        if chain.any():
+            xn = np.where(chain, (np.linalg.norm(xo, axis=1) + np.linalg.norm(xe, axis=1)) / self.scale, 0.0)
+            self.amb[idx] |= ~np.isfinite(xn)
+            edim = edim + np.where(np.isfinite(xn), xn, 0.0)
         hva, lva = w.a[hv] > 0, w.a[lv] > 0
         n2 = np.where(w.refractive[hv], w.refr[hv], 1.0)                         # comp:503, 507
         n1 = np.where(w.refractive[lv], w.refr[lv], 1.0)                         # comp:504, 508
@@ -572,7 +706,12 @@ class PathTrace:
             fall = (sp == MAX_RAYS) | (refl_i[g] <= 0.001) | (refr_i[g] <= 0.001)
             fb = g[fall]
             if fb.size:
-                c = tc[fb] * (sc[fb] * (self.gl[:3] * ndotl[fb, None])) * r["w"][hi][fb, None]
+                nd_fb = ndotl[fb]                                                # point 4 of the sun disc: ndotl from L
+                if self.sun is not None and "sun_glass_ndotl" in fl:
+                    st, u1 = rand(self.rng[idx[fb]])
+                    self.rng[idx[fb]], u2 = rand(st)
+                    nd_fb = np.maximum((normal[fb] * DR.sun_dirs(self.sun, self.sun_s, u1, u2, fl)).sum(1), 0.0)
+                c = tc[fb] * (sc[fb] * (self.gl[:3] * nd_fb[:, None])) * r["w"][hi][fb, None]
                 self._add(idx[fb], c, rel[fb] + 5 * U)
             sp_g = g[~fall]
             if sp_g.size:
@@ -581,7 +720,7 @@ class PathTrace:
                                   rel=rel[sp_g], tc=tc[sp_g], fres=fres[sp_g], e_f=e_f[sp_g], n1=n1[sp_g], n2=n2[sp_g],
                                   dep=dep[sp_g], tir=tir[sp_g], refr=refr[sp_g], eta=eta[sp_g], dd=dd[sp_g], kk=kk[sp_g],
                                   dir_err=r["dir_err"][hi[sp_g]], dim=dim[sp_g], edim=edim[sp_g], lerr=lerr[sp_g], lv_rgb=lv_rgb[sp_g],
-                                  lv_md=lv_md[sp_g], hv_rgb=hv_rgb[sp_g], hv_md=hv_md[sp_g])
+                                  lv_md=lv_md[sp_g], hv_rgb=hv_rgb[sp_g], hv_md=hv_md[sp_g], xerr=xe[sp_g])
         # ---- opaque, and glass deeper (comp:573-618) ----
         o = np.nonzero(~glass)[0]
         if not o.size:
@@ -595,9 +734,13 @@ class PathTrace:
         if e0.any():
             self._add(idx[o[e0]], base[e0] * em0[e0, None], rel[o[e0]] + 5 * U)
         if e1.any():
-            self._add(idx[o[e1]], base[e1] * em[e1, None] / deep_pi, rel[o[e1]] + 6 * U)
-            self.stats["deep_emission"][idx[o[e1]]] += 1
-        deep = (em <= 0) & (dep[o] != 0)
+            self._deep_emission(idx[o[e1]], base[e1] * em[e1, None] / deep_pi, rel[o[e1]] + 6 * U, r, hi[o[e1]], m, xe[o[e1]])
+        Dt = max(self.D - 1, 1) if "depth_off_by_one" in fl else self.D
+        dull = em <= 0
+        inner = dull & (dep[o] >= 1) & (dep[o] < Dt)
+        deep = dull & (dep[o] >= Dt)                                              # the terminal branch (comp:590-594)
+        if "inner_ambient" in fl:
+            deep = deep | inner
         if deep.any():
             q = o[deep]
             ex = np.exp(-dim[q] / 512.0)
@@ -605,29 +748,234 @@ class PathTrace:
             e_amb = E_EXP * ex + ex * (edim[q] + 2 * U * dim[q]) / 512.0 + 2 * U
             self._add(idx[q], base[deep] * amb_c[:, None] / deep_pi, rel[q] + e_amb / amb_c + 6 * U)
             self.stats["deep_ambient"][idx[q]] += 1
-        top = (em <= 0) & (dep[o] == 0)
+            self.stats["terminal"][idx[q]] += dep[q] >= self.D
+        top = dull & (dep[o] < Dt)                                                # a vertex that casts a shadow ray
         if top.any():
             q = o[top]
-            lit, samb = R.not_in_shadow(w, pt[q], normal[q], perr[q].max(1), self.L, self.flaws)
-            self.amb[idx[q]] |= samb
-            c = (self.gl[:3] * (lit * ndotl[q])[:, None]) * sc[q] * tc[q] * r["w"][hi][q, None] / R.PI
-            self._add(idx[q], c, rel[q] + 6 * U)
-            b = q[(self.sp[idx[q]] < MAX_RAYS) & (dep[q] <= 1)]                 # comp:597
-            if b.size:
-                bi = idx[b]
-                st = self.rng[bi]
-                st, rx = rand(st)
-                st, ry = rand(st)
-                self.rng[bi] = st
-                bd = cosine_hemisphere(normal[b], rx, ry)
-                off = 1e-4 if "bounce_offset" in fl else 1e-1
-                o_ = pt[b] + normal[b] * off
-                self._push(bi, org=o_, err3=perr[b] + U * np.abs(o_), lo3=perr[b] + U * np.abs(o_), d=bd, dir_err=np.full(b.size, BOUNCE_DIR_ERR),
-                           iof=n1[b], w=r["w"][hi][b], tint=tc[b] * sc[b], dim=0.0, edim=lerr[b], mc=lv_rgb[b], md=lv_md[b],
-                           depth=dep[b] + 1, rel=rel[b] + 2 * U, oax=-1, lock_ax=-1, lock_p=0.0, given=0)
+            iq = idx[q]
+            self.stats["shadowing"][iq] += 1
+            self.stats["inner"][iq] += dep[q] >= 1
+            assert np.all(self.sp[iq] < MAX_RAYS)                                 # comp:597: a pop came first
+            # the vertex's draws, in the stream's order: the sun's two, the connection's four, the bounce's two
+            st = self.rng[iq]
+            draws = {}
+            late_sun = "sun_draws_after_bounce" in fl
+            names = (("u1", "u2") if self.sun is not None and not late_sun else ()) \
+                + ((("ua", "ub", "u0", "uf") if "emit_draw_order" in fl else ("u0", "uf", "ua", "ub")) if self.emit else ()) \
+                + ("rx", "ry") + (("u1", "u2") if self.sun is not None and late_sun else ())
+            for name in names:
+                st, draws[name] = rand(st)
+            self.rng[iq] = st
+            wq = r["w"][hi][q]
+            # the floor margins of the shadow and bounce marches keep the per-axis bounds from vertex to vertex: a known gap
+            # (module docstring, "Known unsound")
+            pq = perr[q]
+            if self.sun is None:
+                lit, samb = R.not_in_shadow(w, pt[q], normal[q], pq.max(1), self.L, self.flaws)
+                self.amb[iq] |= samb
+                c = (self.gl[:3] * (lit * ndotl[q])[:, None]) * sc[q] * tc[q] * wq[:, None] / R.PI
+                self._add(iq, c, rel[q] + 6 * U)
+            else:
+                Lp = DR.sun_dirs(self.sun, self.sun_s, draws["u1"], draws["u2"], fl)
+                de = DR.sun_dir_err(self.sun_s, self.sun[0])
+                lit, samb = R.not_in_shadow(w, pt[q], normal[q], pq.max(1), Lp, self.flaws, dir_err=de)
+                self.amb[iq] |= samb
+                lit0, _ = R.not_in_shadow(w, pt[q], normal[q], perr[q].max(1), self.L, self.flaws)
+                self.stats["sun_differs"][iq] += lit != lit0
+                nd = np.maximum((normal[q] * Lp).sum(1), 0.0)                        # ndotl', within de of the float32 value
+                full = self.gl[:3] * sc[q] * tc[q] * wq[:, None] / R.PI
+                self._add(iq, full * (lit * nd)[:, None], rel[q] + 6 * U)
+                self.cerr[iq] += full * (lit * de)[:, None]
+            off = 1e-4 if "bounce_offset" in fl else 1e-1
+            o_ = pt[q] + normal[q] * off
+            eo = pq + U * np.abs(o_)
+            if self.emit:
+                x = pt[q] + normal[q] * 2e-3 if "emit_origin_2e3" in fl else pt[q] + normal[q] * 1e-1
+                self._connect(iq, x, perr[q] + U * np.abs(x), xe[q], normal[q], n1[q], wq, tc[q] * sc[q], rel[q] + 2 * U, lv_rgb[q], lv_md[q],
+                              lerr[q], draws["u0"], draws["uf"], draws["ua"], draws["ub"])
+            bd = cosine_hemisphere(normal[q], draws["rx"], draws["ry"])
+            keep = (dep[q] >= 1) & ("inner_keeps_dim" in fl)
+            self._push(iq, org=o_, err3=eo, lo3=eo, d=bd, dir_err=np.full(q.size, BOUNCE_DIR_ERR),
+                       iof=n1[q], w=wq, tint=tc[q] * sc[q], dim=np.where(keep, dim[q], 0.0), edim=np.where(keep, edim[q], lerr[q]),
+                       mc=lv_rgb[q], md=lv_md[q], depth=dep[q] + 1, rel=rel[q] + 2 * U, oax=-1, lock_ax=-1, lock_p=0.0, given=0,
+                       cb=(normal[q] * bd).sum(1), xerr=xe[q])
+
+    # ---- emitter rules (include/vrt.h "Emitter sampling", "Emitter importance", "Emitter MIS") -----------------------------
+    def _deep_emission(self, iq, c, rel, r, hq, m, xe):
+        """a ray of depth >= 1 on an emissive voxel (comp:575-581): the shader's term with sampling off; nothing with sampling on
+        (rule 7); the term times wb under MIS. c[k, 3]: the shader's term; hq: the rays' rows in the popped arrays and the march"""
+        fl = self.flaws
+        if self.emit is None or "emit_keeps_bounce_emission" in fl:
+            self._add(iq, c, rel)
+            self.stats["deep_emission"][iq] += 1
+            return
+        if not self.mis:
+            return
+        cs = r["cb"][hq]
+        derr = r["dir_err"][hq]
+        if "mis_wb_cosine_at_hit" in fl:
+            cs = np.abs(r["d"][hq][np.arange(hq.size), m.ax[hq]])
+        ev3 = r["err3"][hq] + r["xerr"][hq] + m.err3[hq] + xe
+        pl, pb, rel_pl, rel_pb, und = self._mis_density(r["org"][hq], r["err3"][hq] + r["xerr"][hq], ev3, r["d"][hq], derr, cs, m.pt[hq], m.ax[hq], m.mp[hq],
+                                                        m.hv[hq])
+        self._undecide(iq, und, "MIS density of a bounce hit")
+        pos = pl > 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            wb = np.where(pos, pb / (pl + pb), 1.0)
+        self._add(iq, c * wb[:, None], rel + np.where(pos, (1.0 - wb) * (rel_pl + rel_pb), 0.0) + 3 * U)
+        self.stats["deep_emission"][iq] += 1
+        self.stats["mis_bounce_hits"][iq] += pos
+
+    def _mis_density(self, x, ex3, ev3, dirv, derr, cs, pt, ax, mp, hv, m_cube=None):
+        """emit_mis_density(x, dir, cs, hit) -> (pl, pb, relative bound of pl, of pb, undecided). x within ex3 per axis as the floor
+        margins take it, v = hit.point - x within ev3, dir within derr per component, cs within derr. Undecided: a visible-axis test within ex3 of its plane,
+        cl or cs within derr of 0 (the !(pl > 0) test, and pb's relative bound)"""
+        w = self.w
+        kr = np.arange(x.shape[0])
+        v = pt - x
+        r2 = (v * v).sum(1)
+        cl = np.abs(dirv[kr, ax])
+        lo = mp.astype(np.float64)
+        und = np.any((np.abs(x - lo) <= ex3) | (np.abs(x - (lo + 1.0)) <= ex3), 1)
+        mm = ((x < lo) | (x > lo + 1.0)).sum(1)
+        if m_cube is not None:
+            mm = m_cube
+        wv = (w.p[hv, 1] * w.rgb[hv].sum(1)).astype(np.float64)
+        und |= (cl <= derr) | (np.abs(cs) <= derr)
+        ok = (mm > 0) & (cl > 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pl = np.where(ok, ((wv * self.em.inv_power) * r2) / (np.maximum(mm, 1) * np.where(ok, cl, 1.0)), 0.0)
+            pb = np.maximum(cs, 0.0) / R.PI
+            e_v = np.linalg.norm(ev3 + U * np.abs(v), axis=1)
+            rel_pl = 2.0 * e_v / np.sqrt(np.maximum(r2, 1e-300)) + derr / np.where(ok, cl, 1.0) + 8 * U
+            rel_pb = derr / np.maximum(np.abs(cs), 1e-300) + 2 * U
+        return pl, pb, rel_pl, rel_pb, und
+
+    def _connect(self, iq, x, ex3, xe3, normal, n1, wt, tint, rel, mc, md, edim0, u0, uf, ua, ub):
+        """steps 1-6 of "Emitter sampling" (the uniform rule) or of "Emitter importance" (the power rule), then "Emitter MIS",
+        at the shadowing vertices of pixels iq. x[k, 3]: hitPoint + normal * 1e-1 within ex3 per axis as the floor margins take it, and
+        within ex3 + xe3 for the continuous quantities (xe3: the chain's deviation across its rays, 0 along the normal); n1, wt, tint, rel, mc, md: what the
+        bounce ray would carry (make_ray, comp:604-615); edim0: the hit's deviation across its ray, as the bounce takes it"""
+        w, fl, E = self.w, self.flaws, self.em
+        k = iq.size
+        kr = np.arange(k)
+        self.stats["conn_drawn"][iq] += 1
+        power = self.emit == "power"
+        if power:
+            j, p = DR.pick_power(u0, E.T)
+        else:
+            j, p = DR.pick_uniform(u0, E.N), np.ones(k)
+        lo, sz = E.lo[j].astype(np.float64), E.size[j].astype(np.float64)
+        hi_ = lo + sz[:, None]
+        if power:
+            low, high = x < lo, x > hi_
+            self._undecide(iq, np.any((np.abs(x - lo) <= ex3 + xe3) | (np.abs(x - hi_) <= ex3 + xe3), 1), "visible face")
+            vis = low | high
+            mf = vis.sum(1)
+            go = mf > 0
+            i = DR.pick_index(uf, np.maximum(mf, 1))
+            axf = np.argmax(vis & ((np.cumsum(vis, 1) - 1) == i[:, None]), 1)
+            side = high[kr, axf]
+        else:
+            f = DR.pick_index(uf, 6)
+            axf, side = f >> 1, (f & 1) == 1
+            mf = np.full(k, 6)
+            go = np.ones(k, bool)
+        a1, a2 = (axf + 1) % 3, (axf + 2) % 3
+        q = np.zeros((k, 3))
+        eq = np.zeros((k, 3))
+        q[kr, axf] = lo[kr, axf] + np.where(side, sz, 0.0)
+        for a, u in ((a1, ua), (a2, ub)):
+            q[kr, a] = lo[kr, a] + u * sz
+            eq[kr, a] = U * (u * sz) + U * np.abs(q[kr, a])
+        wv = q - x
+        r2 = (wv * wv).sum(1)
+        e3 = ex3 + xe3 + eq + U * np.abs(wv)
+        e_w = np.linalg.norm(e3, axis=1)
+        self._undecide(iq, go & (np.sqrt(r2) <= 2.0 * e_w), "r2 > 0")
+        go &= r2 > 0
+        rr = np.sqrt(np.where(r2 > 0, r2, 1.0))
+        dirv = wv / rr[:, None]
+        derr = R.GIVEN_DIR_ERR + e_w / rr
+        cs = (normal * dirv).sum(1)
+        cl = np.where(side, -dirv[kr, axf], dirv[kr, axf])
+        self._undecide(iq, go & ((np.abs(cs) <= derr) | (np.abs(cl) <= derr)), "cs > 0 and cl > 0")
+        go &= (cs > 0) & (cl > 0)
+        g_ = np.nonzero(go & ~self.amb[iq])[0]
+        if not g_.size:
+            return
+        gi = iq[g_]
+        self.stats["conn_marched"][gi] += 1
+        none = np.full(g_.size, -1, np.int64)
+        ef = (ex3 + xe3)[g_]
+        m = march(w, x[g_], ef, dirv[g_], derr[g_], n1[g_], none, none, np.zeros(g_.size), ef, np.zeros(g_.size, np.int64), corners=True)
+        self._undecide(gi, m.amb, "the connection's march")
+        h = np.nonzero(m.hit & ~m.amb)[0]
+        if not h.size:
+            return
+        g_, gi = g_[h], gi[h]
+        hr = np.arange(h.size)
+        pt, mp, hv, axh = m.pt[h], m.mp[h], m.hv[h], m.ax[h]
+        inside = np.all((mp >= lo[g_]) & (mp < hi_[g_]), 1)                      # step 5
+        margin = R.DELTA_FLOOR + R.DELTA_SAFETY * m.err3[h]
+        # for the continuous quantities: a connection that contributes ends on the face it aimed at (a face turned towards x is
+        # the cube's first along the line), so wherever the float32 x lies its line runs through the float32 q, and the hit is q
+        # within the march's own roundings: the per-axis bound and the deviation across the line by the rounded direction
+        perr = m.err3[h] + m.line3[h] + eq[g_]
+        nearp = (np.abs(pt - lo[g_]) <= margin) | (np.abs(pt - hi_[g_]) <= margin)
+        nearp[hr, axh] = False
+        if "emit_any_emitter" in fl:
+            inside[:] = True
+        else:
+            self._undecide(gi, nearp.any(1), "in-cube test")
+        hva = w.a[hv] > 0
+        emission = np.where(hva, w.p[hv, 1] / 255.0, 0.0) * 10.0
+        c_ = np.nonzero(inside & (emission > 0))[0]
+        if not c_.size:
+            return
+        g_, gi = g_[c_], gi[c_]
+        pt, mp, hv, axh, perr, emission = pt[c_], mp[c_], hv[c_], axh[c_], perr[c_], emission[c_]
+        xg, exg, dg, deg = x[g_], ex3[g_], dirv[g_], derr[g_]
+        # step 6: the hit of a ray of depth >= 1 up to the emissive test (comp:499-520)
+        hpw = pt / self.scale
+        ln = np.linalg.norm(hpw - xg, axis=1)
+        dim = ln / self.scale
+        edim = edim0[g_] + m.line[h][c_] / self.scale + (perr.max(1) + exg.max(1) + 4 * U * (np.abs(hpw).max(1) + np.abs(xg).max(1) + ln)) / self.scale
+        edim = edim + np.linalg.norm(xe3[g_], axis=1) / self.scale             # the connection's length moves with its vertex
+        tc = tint[g_].copy()
+        rl = rel[g_].copy()
+        self._undecide(gi, (md[g_] > 0) & (np.abs(dim - 1e-6) <= edim), "distanceInMedium > 1e-6")
+        ab = (dim > 1e-6) & (md[g_] > 0.0)
+        if ab.any():
+            f, e = self._absorb(md[g_][ab], dim[ab], edim[ab], mc[g_][ab])
+            tc[ab] *= f
+            rl[ab] += e
+        sc = w.rgb[hv] / 255.0
+        hl = np.all(mp == self.hl, 1)
+        sc[hl] = 1.0 - sc[hl]
+        E_k = tc * sc * (emission * wt[g_])[:, None] / R.PI
+        szg, mg, pg = sz[g_], mf[g_].astype(np.float64), p[g_]
+        if power:
+            if "power_six_faces" in fl:
+                mg = np.full(g_.size, 6.0)
+            gg = ((cs[g_] * cl[g_]) * (mg * (szg * szg))) / ((R.PI * r2[g_]) * (1.0 if "power_no_p" in fl else pg))
+        else:
+            gg = ((cs[g_] * cl[g_]) * ((E.N * 6.0) * (szg * szg))) / (R.PI * r2[g_])
+        rl += deg / cs[g_] + deg / cl[g_] + 2.0 * e_w[g_] / rr[g_] + 14 * U
+        c = E_k * gg[:, None]
+        if self.mis:
+            pl, pb, rel_pl, rel_pb, und = self._mis_density(xg, exg + xe3[g_], exg + xe3[g_] + perr, dg, deg, cs[g_], pt, axh, mp, hv,
+                                                            mf[g_] if "mis_m_of_cube" in fl else None)
+            self._undecide(gi, und, "MIS density of a connection")
+            pos = pl > 0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                wn = np.where(pos, pl / (pl + pb), 0.0)
+            c, rl, gi = (c * wn[:, None])[pos], (rl + (1.0 - wn) * (rel_pl + rel_pb) + 3 * U)[pos], gi[pos]
+        self._add(gi, c, rl)
+        self.stats["conn_contributing"][gi] += 1
 
     def _spawn_glass(self, gi, d, normal, pt, perr, ax, P, hv, lv, iof, w, rel, tc, fres, e_f, n1, n2, dep, tir, refr, eta,
-                     dd, kk, dir_err, dim, edim, lerr, lv_rgb, lv_md, hv_rgb, hv_md):
+                     dd, kk, dir_err, dim, edim, lerr, lv_rgb, lv_md, hv_rgb, hv_md, xerr):
         """push the reflected and the refracted ray of the glass hits of pixels gi (comp:555-571); every array has one
         row per pixel: the hit (point, normal after the flip, error, axis, plane P, hit and last voxel), the popped ray
         (rayIOF, weight, direction error, distanceInMedium) and what comp:497-537 made of them"""
@@ -669,7 +1017,7 @@ class PathTrace:
             self._push(gi[q], org=o, err3=e3, lo3=e3, d=rd, dir_err=dir_err[q], iof=n1[q], w=rw, tint=tc[q], dim=dim[q],
                        edim=edim[q] + lerr[q], mc=lv_rgb[q], md=lv_md[q], depth=dep[q],
                        rel=rel[q] + e_f[q] / np.maximum(fres[q], 1e-30) + 2 * U, oax=aq,
-                       lock_ax=np.where(away, aq, -1), lock_p=P[q], given=0)
+                       lock_ax=np.where(away, aq, -1), lock_p=P[q], given=0, cb=0.0, xerr=xerr[q])
 
         def refract(sel):
             q = np.nonzero(sel & (self.sp[gi] < MAX_RAYS) & ~tir)[0]
@@ -682,7 +1030,7 @@ class PathTrace:
             self._push(gi[q], org=o, err3=perr[q] + U * np.abs(o), lo3=perr[q] + U * np.abs(o), d=refr[q] / np.linalg.norm(refr[q], axis=1, keepdims=True),
                        dir_err=de, iof=n2[q], w=w[q] * (1.0 - fres[q]), tint=tc[q], dim=0.0, edim=lerr[q], mc=hv_rgb[q],
                        md=hv_md[q], depth=dep[q], rel=rel[q] + e_f[q] / np.maximum(1.0 - fres[q], 1e-30) + 2 * U, oax=-1,
-                       lock_ax=-1, lock_p=0.0, given=0)
+                       lock_ax=-1, lock_p=0.0, given=0, cb=0.0, xerr=xerr[q])
 
         first = np.ones(gi.size, bool)
         if "id_reflect_first" in self.flaws:

@@ -69,7 +69,8 @@ Jittered and thin-lens samples (Trace.lens; include/vrt.h VRT_ACCUM_JITTER, vrt_
 the sample's rays in float64 with a per-axis origin bound and a per-ray direction bound; _trace takes them as optional
 inputs: the origin bound joins ray_start's rounding (the floor of the origin, the position error, the distances), the
 direction bound adds dir_err * t to every step's position error and makes a component within 2 * dir_err of 0 undecided.
-Still not restated: origins outside the world, the adaptive rule, INDIRECT_SAMPLES / BOUNCES other than 1.
+Still not restated: origins outside the world, the adaptive rule, INDIRECT_SAMPLES other than 1 (path depth, the sun disc
+and the emitter rules: tests/path_ref64.py; notInShadow takes the disc's per-ray direction with its bound).
 
 Radiance. colour_bound is the one bound on a colour: rel * |c| + EPS_COLOR / 255, rel = 7u for the products (+ the
 absorption's terms), 0 for a sky whose float32 products are exact. frame()'s tie test and radiance() both call it.
@@ -315,9 +316,13 @@ def ray_dirs(P, Vw, xs, ys, W, H, pixel_center=False):
     return wd[:, :3] / np.linalg.norm(wd[:, :3], axis=1, keepdims=True)
 
 
-def not_in_shadow(w, pt, normal, err, L, flaws=()):
+def not_in_shadow(w, pt, normal, err, L, flaws=(), dir_err=None):
     """notInShadow (comp:333-377) from hit points pt[n, 3] with axis normals normal[n, 3] (origin pt + normal*2e-3) and
-    float32 position error bounds err[n] -> (lit bool[n], undecided bool[n])"""
+    float32 position error bounds err[n] -> (lit bool[n], undecided bool[n]). L is the uniform lightDir (3,) or one
+    direction per ray (n, 3) as the sun disc makes them (include/vrt.h, "Sun disc": the set-up of comp:335-345 computed
+    from L'); then dir_err[n] bounds the absolute float32 error of each of its components: every step adds dir_err * t to
+    the position error as path_ref64.march() does (and scales the step's own relative terms by |L'| where that exceeds
+    1), and a ray with a non-zero component within max(DIR_MARGIN, 2 * dir_err) of 0 is undecided"""
     n = pt.shape[0]
     lit = np.ones(n, bool)
     amb = np.zeros(n, bool)
@@ -331,6 +336,10 @@ def not_in_shadow(w, pt, normal, err, L, flaws=()):
     assert np.all(w.in_world(mp))
     near = np.abs(pos - np.rint(pos))[np.abs(normal) > 0] < 2.5e-4            # the offset origin, along the normal
     amb[near] = True
+    if dir_err is not None:
+        dir_err = np.broadcast_to(np.asarray(dir_err, np.float64), (n,))
+        amb |= np.any((d != 0) & (np.abs(d) < np.maximum(DIR_MARGIN, 2.0 * dir_err)[:, None]), 1)
+        dlen = np.maximum(1.0, np.sqrt((d * d).sum(1)))
     occluder = (w.a > 25) if "emissive_shadows" in flaws else ((w.a > 25) & (w.p[:, 1] == 0))   # comp:355
     cap = 1 << 16 if "no_shadow_cap" in flaws else SHADOW_CAP
     act = np.arange(n)
@@ -344,7 +353,11 @@ def not_in_shadow(w, pt, normal, err, L, flaws=()):
         amb[o] |= abs(k - (cap + 0.5)) < SHADOW_CAP_MARGIN
         act, node = act[~occ], node[~occ]
         new, ax, stuck, fr, t = _step(w, pos[act], d[act], inv[act], node, 1e-3)
-        err[act] += _step_error(new, t)
+        if dir_err is None:
+            err[act] += _step_error(new, t)
+        else:
+            with np.errstate(invalid="ignore", over="ignore"):
+                err[act] += _step_error(new, t * dlen[act]) + dir_err[act] * np.abs(t)
         margin = DELTA_FLOOR + DELTA_SAFETY * err[act]
         with np.errstate(invalid="ignore"):
             m = np.floor(np.clip(new, -2.0 ** 40, 2.0 ** 40)).astype(np.int64)
