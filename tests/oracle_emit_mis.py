@@ -1,73 +1,28 @@
 """pathTrace with emitter sampling, either mode of vrt_set_emitter_importance and the balance heuristic of vrt_set_emitter_mis
-(tests/oracle_emit_mis.c; include/vrt.h) -- TEST INFRASTRUCTURE ONLY.
+(tests/oracle_paths.c; include/vrt.h) -- TEST INFRASTRUCTURE ONLY.
 
-build(tmp_dir) compiles oracle_emit_mis.c the way oracle_emit_power.py builds its own. shade() traces a batch at one sample, depth,
-radius, emitter list, weights, mode and MIS flag (debug plants a misreading of the rule) -> bytes, (voxel ID, dist), the unclamped
-float colour and, on request, the vertex log. density() and weights_of() restate the header's emit_mis_density and the two weights in
-numpy float32, one rounding per operation; inv_power() restates the launch's 1 / Wtot. The checker computes its thresholds and its
-inv_power from the weights itself."""
-import ctypes as C
-import os
-import subprocess
-
+shade() is oracle_paths' with every rule: a batch at one sample, depth, radius, emitter list, weights, mode and MIS flag (debug plants
+a misreading of the rule) -> bytes, (voxel ID, dist), the unclamped float colour and, on request, the vertex log, whose VERTEX is the
+whole record. density() and weights_of() restate the header's emit_mis_density and the two weights in numpy float32, one rounding per
+operation; inv_power() restates the launch's 1 / Wtot. The checker computes its thresholds and its inv_power from the weights itself."""
 import numpy as np
 
-import oracle_emit as oe
 import oracle_emit_power as oep
-import oracle_path_depth as opd
+import oracle_paths as core
 
-ROOT = oe.ROOT
-UNIFORM, POWER = oep.UNIFORM, oep.POWER
-SKY0, SKY, GLASS, EMIT0, EMIT, DIRECT, AMBIENT = range(7)
-VERTEX = np.dtype(oep.VERTEX.descr + [("has_mis", np.int32), ("mx", np.float32, 3), ("mdir", np.float32, 3), ("mcs", np.float32),
-                                      ("mpoint", np.float32, 3), ("maxis", np.int32), ("mcell", np.int32, 3), ("mrgb", np.int32),
-                                      ("millum", np.int32), ("mm", np.int32), ("mw", np.int32), ("pl", np.float32),
-                                      ("pb", np.float32), ("wt", np.float32)])
-assert VERTEX.itemsize == oep.VERTEX.itemsize + 88
+UNIFORM, POWER = core.UNIFORM, core.POWER
+SKY0, SKY, GLASS, EMIT0, EMIT, DIRECT, AMBIENT = range(7)   # o_path_vertex.kind
+VERTEX = core.prefix("wt")
+assert VERTEX == core.VERTEX and VERTEX.itemsize == oep.VERTEX.itemsize + 88
 PI = np.float32(3.14159265359)
-
-
-def build(tmp_dir):
-    out = os.path.join(str(tmp_dir), "liboracle_emit_mis.so")
-    srcs = [os.path.join(ROOT, "tests", "oracle_emit_mis.c")] + [os.path.join(oe.ORACLE, f) for f in
-                                                                 ("octree_oracle.c", "vox_oracle.c", "camera_oracle.c")]
-    subprocess.run(["gcc", *oe.CFLAGS, "-shared", "-o", out, *srcs, "-lm"], check=True)
-    L = C.CDLL(out)
-    L.o_shade_rays_emitm.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_size_t]
-    L.o_shade_rays_emitm.restype = C.c_size_t
-    return L
+FLAWS = {0: core.FLAW_NONE, 1: core.FLAW_MIS_BOUNCE_FULL, 2: core.FLAW_MIS_BOUNCE_NONE}   # debug: the bounce keeps weight 1, adds nothing
+build = core.build
 
 
 def shade(L, scene, origins, dirs, depth, tan_radius, emitters, weights, mode, mis, width=None, sample=0, log=False, debug=0):
-    """-> (rgba8[n,4], id_dist[n,2], rgb float32[n,3]) of the batch at sample `sample`, path depth `depth`, sun disc `tan_radius`, the
-    emitter list `emitters` (int32[N, 4]; None or N == 0: sampling off) with its weights (uint64[N]), the mode and the MIS flag; with
-    log=True also the vertex log (a VERTEX array). origins (n, 3) or (3,) shared"""
-    assert 1 <= depth <= oe.MAX_DEPTH and 0.0 <= tan_radius <= 1.0 and mode in (UNIFORM, POWER) and mis in (0, 1) and debug in (0, 1, 2)
-    o, stride, d = opd._rays(origins, dirs)
-    e, ep = oe._list(emitters)
-    wt = np.zeros(0, np.uint64) if weights is None else np.ascontiguousarray(weights, np.uint64)
-    assert len(wt) == len(e) or (mode == UNIFORM and len(wt) == 0)
-    wp = wt.ctypes.data if len(wt) else None
-    n = d.shape[0]
-    rgba = np.zeros((n, 4), np.uint8)
-    idd = np.zeros((n, 2), np.int32)
-    rgb = np.zeros((n, 3), np.float32)
-    s = int(sample) & 0xFFFFFFFF
-    s = s - (1 << 32) if s >= 1 << 31 else s
-    w = int(n if width is None else width)
-    head = (C.addressof(scene), n, o.ctypes.data, stride, d.ctypes.data, w, int(depth), float(tan_radius), ep, wp, len(e), int(mode), int(mis),
-            int(debug), s)
-    if log:
-        dummy = np.zeros(1, VERTEX)
-        cap = L.o_shade_rays_emitm(*head, None, None, None, dummy.ctypes.data, 0)
-    vlog = np.zeros(max(cap, 1) if log else 1, VERTEX)
-    got = L.o_shade_rays_emitm(*head, rgba.ctypes.data, idd.ctypes.data, rgb.ctypes.data, vlog.ctypes.data if log else None, cap if log else 0)
-    if log:
-        assert got == cap, "vertex log cut"
-        return rgba, idd, rgb, vlog[:got]
-    return rgba, idd, rgb
+    """oracle_paths.shade() of the depth, the radius, the list, its weights, the mode and the MIS flag; the log as a VERTEX array"""
+    return core.cut(core.shade(L, scene, origins, dirs, depth, tan_radius, emitters, weights, mode, mis, width=width, sample=sample, log=log,
+                               flaw=FLAWS[debug]), VERTEX)
 
 
 def inv_power(wts):

@@ -1,20 +1,44 @@
-/* tests/oracle_emit_power.c -- TEST INFRASTRUCTURE ONLY: pathTrace with a path depth, a sun disc and emitter sampling in either mode of
- * include/vrt.h vrt_set_emitter_importance.
+/* tests/oracle_paths.c -- TEST INFRASTRUCTURE ONLY: the one checker of the five path rules of VRT_MODE_FULL (include/vrt.h).
  *
- * oracle/rt_oracle.c is included unchanged. path_trace_emitp() is tests/oracle_emit.c's path_trace_emit(), loop for loop, with the
- * list's weights (uint64[n], W_j of the header) and a mode beside the list. At mode 0 (VRT_EMIT_UNIFORM) it is that function bit for
- * bit; with n == 0 it is path_trace_sun (tests/test_emit_power.py checks both). At mode 1 (VRT_EMIT_POWER) the shadowing vertex picks
- * emitter j by the thresholds T -- which o_shade_rays_emitp computes from the weights itself, in exact integers; it never sees the
- * product's table -- and the face among the m faces turned towards x = hitPoint + normal * 1e-1; m == 0 ends the vertex's sampling
- * with the four draws spent. From q on the steps are the uniform rule's; the weight is g = cs * cl * (m * size^2) / (PI * r2 * p).
+ * oracle/rt_oracle.c is included unchanged. path_trace_paths() is its path_trace loop with each rule at its one place, and
+ * o_shade_rays_paths is the one entry point. The rules, and the arguments that switch each one off:
  *
- * `debug` plants a misreading of the rule, for the test that shows the expectation test can tell: 1 puts 6 in m's place in g, 2
- * leaves p out of g. 0 is the rule.
+ * 1. Path depth (vrt_set_path_depth), `depth` D in 1 .. 8: depth 0 and the inner vertices 1 <= d < D take the depth-0 operations,
+ *    d == D the shader's terminal branch. Off at D = 1: the oracle's own loop.
+ * 2. Sun disc (vrt_set_sun_disc), `tan_radius` > 0: a shadowing vertex first draws its own light direction (two draws, the
+ *    concentric map, the basis). Off at tan_radius 0: nothing is drawn and the shadow ray goes towards lightDir.
+ * 3. Emitter sampling (vrt_set_emitter_sampling), `n_emit` > 0: after the sun's direct term a shadowing vertex spends four draws on
+ *    a connection to the list -- emitter, face, point -- and adds E * g with g = cs * cl * (n * 6 * size^2) / (PI * r2); a ray of
+ *    depth >= 1 that hits an emissive voxel adds nothing. Off at n_emit 0: nothing is drawn, and neither rule below is read.
+ * 4. Emitter importance (vrt_set_emitter_importance), `mode` 1 (VRT_EMIT_POWER): the vertex picks emitter j by the thresholds T --
+ *    which o_shade_rays_paths computes from the weights itself, in exact integers; it never sees the product's table -- and the face
+ *    among the m faces turned towards x = hitPoint + normal * 1e-1; m == 0 ends the vertex's sampling with the four draws spent. From
+ *    q on the steps are rule 3's; the weight is g = cs * cl * (m * size^2) / (PI * r2 * p). Off at mode 0 (VRT_EMIT_UNIFORM): the
+ *    weights are not read.
+ * 5. Emitter MIS (vrt_set_emitter_mis), `mis` 1 at mode 1: the connection that would add E * g adds (E * g) * wn with wn = pl /
+ *    (pl + pb), nothing where !(pl > 0), and a ray of depth >= 1 that hits an emissive voxel adds its emissive term times wb = pb /
+ *    (pl + pb), 1 where !(pl > 0). mis_density() is the header's emit_mis_density: it is given the hit alone -- point, axis, cell and
+ *    the voxel's colour and illumination bytes -- and inv_power, which o_shade_rays_paths computes from the weights itself. Off at
+ *    mis 0, and at mode 0.
  *
- * The log record is oracle_emit.c's o_emit_vertex followed by t, ticks and m (zero at mode 0 and outside DIRECT vertices) and by x. Built by
- * tests/oracle_emit_power.py with the oracle's own flags together with the other three oracle sources. */
+ * `flaw` plants one misreading of a rule, for the tests that show that an expectation test can tell. O_FLAW_NONE is the rule; every
+ * other value names one flaw, of rule 4's g or of rule 5's bounce side (the enum below).
+ *
+ * The log has one record type, o_path_vertex: the loop's fields, then those each rule added, in the order of the rules. What a rule
+ * draws and computes is zero where the rule is off; the fields that describe the loop itself (lp, rx, ry, normal, shadow_steps; x
+ * with a list) are filled at every setting. For a DIRECT vertex the density's fields are those of its connection (zero where no
+ * connection reached `g`), for an EMIT record those of the bounce ray's hit. Built by tests/oracle_paths.py with the oracle's own
+ * flags together with the other three oracle sources. */
 #include "../oracle/rt_oracle.c"
 #include <stdlib.h>
+
+enum {
+    O_FLAW_NONE = 0,
+    O_FLAW_POWER_SIX_FACES = 1,   /* importance: 6 in m's place in g                                  */
+    O_FLAW_POWER_NO_P = 2,        /* importance: g without p                                          */
+    O_FLAW_MIS_BOUNCE_FULL = 3,   /* MIS: the bounce side keeps weight 1 (light is counted twice)     */
+    O_FLAW_MIS_BOUNCE_NONE = 4    /* MIS: the bounce side adds nothing                                */
+};
 
 enum {
     O_PD_SKY0 = 0,      /* miss at depth 0:        gl * sky * tc * w                         */
@@ -46,7 +70,39 @@ typedef struct {
     /* mode 1 only: the tick t = min((uint32)(u0 * 2^24), 2^24 - 1), the ticks emitter j holds, the number of faces x sees */
     int32_t t, ticks, m;
     float x[3];   /* both modes: the connection's origin, hitPoint + normal * 1e-1 */
-} o_emitp_vertex;
+    /* mis 1 only (zero elsewhere), DIRECT vertices whose connection reached g and EMIT records: the inputs of the density -- x, dir, cs,
+     * the hit's point, axis (-1: the hit has no normal), cell, colour word (R | G << 8 | B << 16) and illumination byte -- then m, w,
+     * pl, pb and the weight applied (wn or wb); has_mis says that these fields are filled */
+    int32_t has_mis;
+    float mx[3], mdir[3], mcs, mpoint[3];
+    int32_t maxis, mcell[3], mrgb, millum, mm, mw;
+    float pl, pb, wt;
+} o_path_vertex;
+
+/* include/vrt.h vrt_set_emitter_mis, emit_mis_density: every operation float32, rounded on its own */
+typedef struct { int32_t axis, cell[3], rgb, illum, m, w; float point[3], pl, pb; } mis_t;
+static int byte_of(float unorm) { return (int)rintf(unorm * 255.0f); }
+static mis_t mis_density(v3 x, v3 dir, float cs, v3 point, v3 hn, i3 cell, const vox_t *hv, float inv_power) {
+    mis_t d;
+    d.axis = hn.x != 0.0f ? 0 : (hn.y != 0.0f ? 1 : (hn.z != 0.0f ? 2 : -1));   /* no normal: the direction is 0 on the hit's axis */
+    d.cell[0] = cell.x; d.cell[1] = cell.y; d.cell[2] = cell.z;
+    d.point[0] = point.x; d.point[1] = point.y; d.point[2] = point.z;
+    const int R = byte_of(hv->color[0]), G = byte_of(hv->color[1]), B = byte_of(hv->color[2]);
+    d.rgb = R | (G << 8) | (B << 16);
+    d.illum = byte_of(hv->props[1]);
+    const v3 v = sub3(point, x);
+    const float r2 = dot3(v, v);
+    const float cl = d.axis < 0 ? 0.0f : fabsf(vget(dir, d.axis));
+    d.m = 0;
+    for (int k = 0; k < 3; k++) {
+        const float xk = vget(x, k);
+        if (xk < (float)d.cell[k] || xk > (float)d.cell[k] + 1.0f) d.m++;
+    }
+    d.w = d.illum * (R + G + B);
+    d.pl = (d.m == 0 || !(cl > 0.0f)) ? 0.0f : ((((float)d.w * inv_power) * r2) / ((float)d.m * cl));
+    d.pb = (cs > 0.0f ? cs : 0.0f) / kPI;
+    return d;
+}
 
 /* the basis of include/vrt.h vrt_set_sun_disc, step 1, with the oracle's own normalize3 / len3 / cross3 */
 typedef struct { float s, ll; v3 Ln, T, B; } sun_t;
@@ -87,18 +143,29 @@ void o_sun_basis(const float *light_dir, float tan_radius, float *out) {
 }
 
 typedef struct {
-    o_emitp_vertex *buf;
+    o_path_vertex *buf;
     size_t cap, n;
     uint32_t ray;
 } pd_log;
 
 /* the record pd_put() wrote last, or NULL where it was not kept */
-static o_emitp_vertex *pd_last(pd_log *lg) { return (lg && lg->n >= 1 && lg->n <= lg->cap) ? &lg->buf[lg->n - 1] : NULL; }
+static o_path_vertex *pd_last(pd_log *lg) { return (lg && lg->n >= 1 && lg->n <= lg->cap) ? &lg->buf[lg->n - 1] : NULL; }
+
+static void pd_mis(o_path_vertex *v, v3 x, v3 dir, float cs, const mis_t *d, float wt) {
+    if (!v) return;
+    v->has_mis = 1;
+    v->mx[0] = x.x; v->mx[1] = x.y; v->mx[2] = x.z;
+    v->mdir[0] = dir.x; v->mdir[1] = dir.y; v->mdir[2] = dir.z;
+    v->mcs = cs;
+    for (int k = 0; k < 3; k++) { v->mpoint[k] = d->point[k]; v->mcell[k] = d->cell[k]; }
+    v->maxis = d->axis; v->mrgb = d->rgb; v->millum = d->illum; v->mm = d->m; v->mw = d->w;
+    v->pl = d->pl; v->pb = d->pb; v->wt = wt;
+}
 
 static void pd_put(pd_log *lg, int kind, int depth, int chain, int lit, float ndotl, const float *sc, const float *tc, float w, float extra) {
     if (!lg) return;
     if (lg->n < lg->cap) {
-        o_emitp_vertex *v = &lg->buf[lg->n];
+        o_path_vertex *v = &lg->buf[lg->n];
         v->ray = lg->ray; v->kind = kind; v->depth = depth; v->chain = chain; v->lit = lit;
         v->ndotl = ndotl;
         for (int k = 0; k < 3; k++) { v->sc[k] = sc ? sc[k] : 0.0f; v->tc[k] = tc[k]; }
@@ -111,13 +178,17 @@ static void pd_put(pd_log *lg, int kind, int depth, int chain, int lit, float nd
         for (int k = 0; k < 3; k++) v->q[k] = v->E[k] = 0.0f;
         v->t = v->ticks = v->m = 0;
         v->x[0] = v->x[1] = v->x[2] = 0.0f;
+        v->has_mis = 0;
+        for (int k = 0; k < 3; k++) { v->mx[k] = v->mdir[k] = v->mpoint[k] = 0.0f; v->mcell[k] = 0; }
+        v->mcs = v->pl = v->pb = v->wt = 0.0f;
+        v->maxis = v->mrgb = v->millum = v->mm = v->mw = 0;
     }
     lg->n++;   /* counts past the capacity: the caller sees that the log was cut */
 }
 
 /* comp:435-622 pathTrace in O_MODE_FULL with the path depth `D` (1 .. 8), the sun disc `sun`, the emitter list (n_emit entries), its
- * thresholds and the mode */
-static void path_trace_emitp(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const sun_t *sun, const int32_t *emit, int n_emit, const uint32_t *cdf, int mode, int debug, float out_rgb[3], int32_t *voxel_id, int32_t *pixel_dist, pd_log *lg) {
+ * thresholds, the mode and -- read at mode 1 with n_emit > 0 only -- the MIS flag with inv_power = 1 / Wtot */
+static void path_trace_paths(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const sun_t *sun, const int32_t *emit, int n_emit, const uint32_t *cdf, int mode, int mis, float inv_power, int flaw, float out_rgb[3], int32_t *voxel_id, int32_t *pixel_dist, pd_log *lg) {
     const o_scene *s = c->s;
     int32_t cur = 0;
     i3 nmin = {s->bounds_min[0], s->bounds_min[1], s->bounds_min[2]};
@@ -143,6 +214,8 @@ static void path_trace_emitp(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const s
     const float *gl = s->global_light;
     v3 light = {s->light_dir[0], s->light_dir[1], s->light_dir[2]};
 
+    const int use_mis = mis && mode == 1 && n_emit > 0;
+    float cb = 0.0f;   /* the cosine of the bounce ray in flight at its vertex: a ray of depth >= 1 is popped right after its push */
     while (sp > 0) {
         ray_t r = stack[--sp];
         const int chain = chain_of[sp];
@@ -230,12 +303,22 @@ static void path_trace_emitp(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const s
                 pd_put(lg, O_PD_EMIT0, r.depth, chain, 0, ndotl, sc, tc, r.weight, emission);
                 continue;
             } else if (emission > 0.0f) {
+                if (use_mis) {   /* EMITTER MIS, the bounce: the complementary share of the balance heuristic */
+                    const mis_t d = mis_density(r.origin, r.dir, cb, hp, hn, mp, &hv, inv_power);
+                    float wb = !(d.pl > 0.0f) ? 1.0f : d.pb / (d.pl + d.pb);
+                    if (flaw == O_FLAW_MIS_BOUNCE_FULL) wb = 1.0f;
+                    if (flaw != O_FLAW_MIS_BOUNCE_NONE)
+                        for (int k = 0; k < 3; k++) fc[k] = fc[k] + (tc[k] * sc[k] * emission * r.weight / kPI) * wb;
+                    pd_put(lg, O_PD_EMIT, r.depth, chain, 0, ndotl, sc, tc, r.weight, emission);
+                    pd_mis(pd_last(lg), r.origin, r.dir, cb, &d, flaw == O_FLAW_MIS_BOUNCE_NONE ? 0.0f : wb);
+                    continue;
+                }
                 if (n_emit > 0) continue;   /* EMITTER SAMPLING (7): the vertex before has sampled the emitters itself */
                 for (int k = 0; k < 3; k++) fc[k] = fc[k] + tc[k] * sc[k] * emission * r.weight / kPI;
                 pd_put(lg, O_PD_EMIT, r.depth, chain, 0, ndotl, sc, tc, r.weight, emission);
                 continue;
             }
-            o_emitp_vertex *direct_rec = NULL;
+            o_path_vertex *direct_rec = NULL;
             if (r.depth < D) {   /* THE RULE: depth 0, and the inner vertices 1 <= d < D, take the depth-0 operations */
                 /* THE SUN DISC: at tan_radius > 0 this vertex draws its own light direction first */
                 float u1 = 0.0f, u2 = 0.0f, dx = 0.0f, dy = 0.0f;
@@ -350,16 +433,26 @@ static void path_trace_emitp(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const s
                                 const float emission2 = hv2.props[1] * 10.0f;
                                 if (emission2 > 0.0f) {
                                     if (mode == 1) {
-                                        const float mg = debug == 1 ? 6.0f : (float)m;
-                                        if (debug == 2) g = ((cs * cl) * (mg * (sz * sz))) / (kPI * r2);
+                                        const float mg = flaw == O_FLAW_POWER_SIX_FACES ? 6.0f : (float)m;
+                                        if (flaw == O_FLAW_POWER_NO_P) g = ((cs * cl) * (mg * (sz * sz))) / (kPI * r2);
                                         else g = ((cs * cl) * (mg * (sz * sz))) / ((kPI * r2) * p);
                                     } else {
                                         const float area = ((float)n_emit * 6.0f) * (sz * sz);
                                         g = ((cs * cl) * area) / (kPI * r2);
                                     }
-                                    for (int k = 0; k < 3; k++) {
-                                        E[k] = tc2[k] * sc2[k] * emission2 * cr.weight / kPI;
-                                        fc[k] = fc[k] + E[k] * g;
+                                    if (use_mis) {   /* EMITTER MIS, the connection: its share of the balance heuristic */
+                                        const mis_t d = mis_density(x, dir, cs, hp2, hn2, mp2, &hv2, inv_power);
+                                        const float wn = d.pl > 0.0f ? d.pl / (d.pl + d.pb) : 0.0f;
+                                        for (int k = 0; k < 3; k++) {
+                                            E[k] = tc2[k] * sc2[k] * emission2 * cr.weight / kPI;
+                                            if (d.pl > 0.0f) fc[k] = fc[k] + (E[k] * g) * wn;
+                                        }
+                                        pd_mis(direct_rec, x, dir, cs, &d, wn);
+                                    } else {
+                                        for (int k = 0; k < 3; k++) {
+                                            E[k] = tc2[k] * sc2[k] * emission2 * cr.weight / kPI;
+                                            fc[k] = fc[k] + E[k] * g;
+                                        }
                                     }
                                 }
                             }
@@ -386,6 +479,7 @@ static void path_trace_emitp(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const s
                 float rx = rand_f(c), ry = rand_f(c);
                 if (direct_rec) { direct_rec->rx = rx; direct_rec->ry = ry; }
                 v3 bd = cosine_hemisphere(normal, rx, ry);
+                cb = dot3(normal, bd);
                 float nw = r.weight / (float)INDIRECT_SAMPLES;
                 float tint[4] = {tc[0] * sc[0], tc[1] * sc[1], tc[2] * sc[2], tc[3] * sc[3]};
                 chain_of[sp] = r.depth == 0 ? ++chains : chain;
@@ -397,8 +491,6 @@ static void path_trace_emitp(ctx_t *c, v3 ray_origin, v3 ray_dir, int D, const s
     out_rgb[0] = fc[0]; out_rgb[1] = fc[1]; out_rgb[2] = fc[2];
 }
 
-/* Every output but the scene and the rays may be NULL. Returns the number of log records the batch produced (more than log_cap:
- * the log holds the first log_cap of them). */
 /* The thresholds of the header, in exact integers: out[n] from the weights[n] */
 void o_emit_thresholds(const uint64_t *weights, int n, uint32_t *out) {
     uint64_t total = 0, cum = 0;
@@ -410,8 +502,10 @@ void o_emit_thresholds(const uint64_t *weights, int n, uint32_t *out) {
     }
 }
 
-size_t o_shade_rays_emitp(const o_scene *s, size_t n, const float *origins, int stride, const float *dirs, int width, int depth, float tan_radius,
-                         const int32_t *emit, const uint64_t *weights, int n_emit, int mode, int debug, int sample, uint8_t *rgba8, int32_t *id_dist, float *rgb_out, o_emitp_vertex *log, size_t log_cap) {
+/* Every output but the scene and the rays may be NULL. Returns the number of log records the batch produced (more than log_cap:
+ * the log holds the first log_cap of them). */
+size_t o_shade_rays_paths(const o_scene *s, size_t n, const float *origins, int stride, const float *dirs, int width, int depth, float tan_radius,
+                          const int32_t *emit, const uint64_t *weights, int n_emit, int mode, int mis, int flaw, int sample, uint8_t *rgba8, int32_t *id_dist, float *rgb_out, o_path_vertex *log, size_t log_cap) {
     ctx_t c;
     memset(&c, 0, sizeof c);
     c.s = s;
@@ -423,6 +517,11 @@ size_t o_shade_rays_emitp(const o_scene *s, size_t n, const float *origins, int 
         if (!cdf) return 0;
         o_emit_thresholds(weights, n_emit, cdf);
     }
+    /* per launch: inv_power = 1 / Wtot, rounded once from the float64 quotient; 0 for a list without power */
+    uint64_t wtot = 0;
+    if (n_emit > 0 && mode == 1)
+        for (int j = 0; j < n_emit; j++) wtot += weights[j];
+    const float inv_power = wtot > 0 ? (float)(1.0 / (double)wtot) : 0.0f;
     for (size_t i = 0; i < n; i++) {
         c.px_fetches = 0;
         c.px_index = (uint32_t)i;
@@ -432,7 +531,7 @@ size_t o_shade_rays_emitp(const o_scene *s, size_t n, const float *origins, int 
         float rgb[3];
         int32_t vid, dist;
         lg.ray = (uint32_t)i;
-        path_trace_emitp(&c, ro, wd, depth, &sun, emit, n_emit, cdf, mode, debug, rgb, &vid, &dist, log ? &lg : NULL);
+        path_trace_paths(&c, ro, wd, depth, &sun, emit, n_emit, cdf, mode, mis, inv_power, flaw, rgb, &vid, &dist, log ? &lg : NULL);
         if (rgba8) { rgba8[i * 4 + 0] = unorm8(rgb[0]); rgba8[i * 4 + 1] = unorm8(rgb[1]); rgba8[i * 4 + 2] = unorm8(rgb[2]); rgba8[i * 4 + 3] = 255; }
         if (id_dist) { id_dist[i * 2 + 0] = vid; id_dist[i * 2 + 1] = dist; }
         if (rgb_out) { rgb_out[i * 3 + 0] = rgb[0]; rgb_out[i * 3 + 1] = rgb[1]; rgb_out[i * 3 + 2] = rgb[2]; }

@@ -1,6 +1,6 @@
-"""The checkers of the path depth, the sun disc and the emitter rules (tests/oracle_path_depth.c, oracle_sun.c, oracle_emit.c,
-oracle_emit_power.c, oracle_emit_mis.c) against the independent float64 restatement (tests/path_ref64.py with depth=, tan_radius=,
-emit= and mis=, written from the text of include/vrt.h alone).
+"""The checker of the path depth, the sun disc and the emitter rules (tests/oracle_paths.c, through each of its five wrappers:
+oracle_path_depth, oracle_sun, oracle_emit, oracle_emit_power, oracle_emit_mis) against the independent float64 restatement
+(tests/path_ref64.py with depth=, tan_radius=, emit= and mis=, written from the text of include/vrt.h alone).
 
 Per batch and setting (D, tan_radius, rule) every decided ray must agree exactly in bytes, voxel ID and dist, and the checker's
 unclamped float colour must lie within the reference's float32 bound. The reference's per-ray stats prove that a batch exercises the
@@ -138,13 +138,13 @@ class DeepBatch(Batch):
 
 @pytest.fixture(scope="module")
 def CK(tmp_path_factory):
-    """the five checkers"""
-    t = tmp_path_factory.mktemp("oracle_deep_ref64")
-    return {"depth": opd.build(t), "sun": osun.build(t), "emit": oe.build(t), "power": oep.build(t), "mis": om.build(t)}
+    """the checker, under the name of each of its five wrappers"""
+    L = om.build(tmp_path_factory.mktemp("oracle_deep_ref64"))
+    return dict.fromkeys(("depth", "sun", "emit", "power", "mis"), L)
 
 
 def checker_shade(CK, b, s, setting, k, o=None, d=None):
-    """the checker that was written for the setting's last rule -> (rgba8, id_dist, rgb float32)"""
+    """the checker through the wrapper of the setting's last rule -> (rgba8, id_dist, rgb float32)"""
     D, rad, rule = setting
     o, d = (b.o if o is None else o), (b.d if d is None else d)
     if rule == OFF and rad == 0.0:

@@ -1,5 +1,5 @@
-"""Emitter MIS (include/vrt.h vrt_set_emitter_mis): what holds without a GPU. The checker (tests/oracle_emit_mis.c) is
-oracle_emit_power.c at flag 0, bit for bit; at flag 1 its log shows the density and the two weights of the balance heuristic, which a
+"""Emitter MIS (include/vrt.h vrt_set_emitter_mis): what holds without a GPU. The checker (tests/oracle_paths.c through oracle_emit_mis) is
+oracle_emit_power at flag 0, bit for bit; at flag 1 its log shows the density and the two weights of the balance heuristic, which a
 numpy float32 restatement reproduces bit for bit and which sum to one; the estimator has the expectation of the power rule and of
 sampling off, both planted misreadings of the bounce side fail that test, every connection weight g * wn is bounded where the power
 rule's g runs past 10, and next to emitters the variance falls. The kernels are held to the checker on the MI355X

@@ -1,6 +1,6 @@
 """Emitter importance (include/vrt.h vrt_set_emitter_importance, VRT_EMIT_POWER): what holds without a GPU. The host's weights and
-thresholds are a Python big-integer restatement's, up to weights in the 2^57 range; the checker (tests/oracle_emit_power.c) is
-oracle_emit.c at mode 0 and oracle_sun with an empty list, bit for bit; at mode 1 its log shows the rule's tick, emitter, visible
+thresholds are a Python big-integer restatement's, up to weights in the 2^57 range; the checker (tests/oracle_paths.c through oracle_emit_power) is
+oracle_emit at mode 0 and oracle_sun with an empty list, bit for bit; at mode 1 its log shows the rule's tick, emitter, visible
 faces, point and weight; the estimator has the expectation of the uniform one and of sampling off at less variance than the uniform
 one, and a planted misreading of the weight fails that test; the host's table code runs clean under the host sanitizers as a program
 of its own. The kernels are held to the checker on the MI355X (test_gpu_emit_power.py)."""

@@ -1,4 +1,4 @@
-"""Emitter sampling (include/vrt.h vrt_set_emitter_sampling): what holds without a GPU. The checker (tests/oracle_emit.c: oracle_sun's
+"""Emitter sampling (include/vrt.h vrt_set_emitter_sampling): what holds without a GPU. The checker (tests/oracle_paths.c through oracle_emit: oracle_sun's
 loop with the rule applied at the shadowing vertices and at the emissive hits of depth >= 1) is oracle_sun with an empty list; its log
 shows the rule's draws, emitter, face, point and cosines; its float colour is the sum of the contributions it logs; the estimator with
 sampling on has the expectation of the one with sampling off, at a fraction of its variance; and the host's list builder gives the

@@ -1,6 +1,6 @@
 """Emitter MIS (include/vrt.h vrt_set_emitter_mis) on the MI355X: the kernels' own emit_mis_density() against the numpy restatement;
 the samples of VRT_MODE_FULL in accumulations and ray batches with sampling on, VRT_EMIT_POWER and the flag set, at D in {1, 3} and
-sun radius in {0, 0.05}, byte for byte (HDR: bit for bit) against the checker (tests/oracle_emit_mis.c) in emit_mis_worlds.py's room
+sun radius in {0, 0.05}, byte for byte (HDR: bit for bit) against the checker (tests/oracle_paths.c through oracle_emit_mis) in emit_mis_worlds.py's room
 at 72 x 44: a merged lamp on the floor, singles against walls and ceiling, a black emitter, glass in front of the camera. Where the
 flag is not read -- sampling off, VRT_EMIT_UNIFORM, a world without emitters -- flag 1 gives flag 0's bytes and does not restart.
 Every reference sample is computed once per (mode, ray source, D, radius, sample) and shared."""

@@ -1,6 +1,6 @@
 """Emitter importance (include/vrt.h vrt_set_emitter_importance) on the MI355X: the kernels' own threshold search against the Python
 rule on tables of 1 to 2^20 entries; the samples of VRT_MODE_FULL in accumulations and ray batches with sampling on and VRT_EMIT_POWER,
-at D in {1, 3} and sun radius in {0, 0.05}, byte for byte (HDR: bit for bit) against the checker (tests/oracle_emit_power.c) in
+at D in {1, 3} and sun radius in {0, 0.05}, byte for byte (HDR: bit for bit) against the checker (tests/oracle_paths.c through oracle_emit_power) in
 emit_power_worlds.py's room at 72 x 44: a merged lamp of size 4 and a panel of 256 dim singles, glass in front of the camera. Mode 1
 without sampling or without emitters is mode 0; mode 0 with sampling is oracle_emit; the table after an upload, patches and a
 compaction is the Python table of a fresh world. Every reference sample is computed once per (mode, ray source, D, radius, sample) and
@@ -339,7 +339,7 @@ def test_mode_1_without_emitters_is_mode_0_on_every_route(ctx, V, dragon):
 
 
 def test_mode_0_with_sampling_on_is_oracle_emit(ctx, refs, batches, libs):
-    """VRT_EMIT_UNIFORM, set explicitly after VRT_EMIT_POWER: the uniform rule's bytes, by oracle_emit.c itself"""
+    """VRT_EMIT_UNIFORM, set explicitly after VRT_EMIT_POWER: the uniform rule's bytes, by oracle_emit itself"""
     _load(ctx, refs, 3, 0.05, mode=1)
     try:
         ctx.set_emitter_importance(0)

@@ -1,6 +1,6 @@
 """Emitter sampling (include/vrt.h vrt_set_emitter_sampling) on the MI355X: the samples of VRT_MODE_FULL in accumulations and ray
 batches with sampling on, at D in {1, 3} and sun radius in {0, 0.05}, byte for byte (HDR: bit for bit) against the checker
-(tests/oracle_emit.c) in the lamp room with its pane at 72 x 44: a merged lamp and three single emitters, glass in front of the
+(tests/oracle_paths.c through oracle_emit) in the lamp room with its pane at 72 x 44: a merged lamp and three single emitters, glass in front of the
 camera. The list itself against a Python walk after an upload, a patch and a compaction; sampling off, and sampling on in a world
 without emitters (the dragon), against oracle_sun's checker and against sampling off. Every reference sample is computed once per
 (list, ray source, D, radius, sample) and shared."""

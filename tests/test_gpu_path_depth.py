@@ -1,5 +1,5 @@
 """Path depth (include/vrt.h vrt_set_path_depth) on the MI355X: the samples of VRT_MODE_FULL in accumulations and ray batches at
-D in {1, 2, 3, 8}, byte for byte (HDR: bit for bit) against the checker (tests/oracle_path_depth.c). Three worlds at 72 x 44 --
+D in {1, 2, 3, 8}, byte for byte (HDR: bit for bit) against the checker (tests/oracle_paths.c through oracle_path_depth). Three worlds at 72 x 44 --
 nine tiles across and a half tile at the bottom edge: the dragon (opaque: the two-pass routes), the room seen from inside (glass:
 the general kernel) and the unit-internal stream (no wide layout: the record-array kernels). Every reference sample is computed
 once per (world, ray source, D, sample) and shared."""

@@ -1,6 +1,6 @@
 """Sun disc (include/vrt.h vrt_set_sun_disc) on the MI355X: the samples of VRT_MODE_FULL in accumulations and ray batches with a
 sun of tan_radius 0.05 (and 1.0 once per world) at D in {1, 3}, byte for byte (HDR: bit for bit) against the checker
-(tests/oracle_sun.c), on test_gpu_path_depth.py's worlds at 72 x 44: the dragon (opaque: the two-pass and one-kernel routes), the
+(tests/oracle_paths.c through oracle_sun), on test_gpu_path_depth.py's worlds at 72 x 44: the dragon (opaque: the two-pass and one-kernel routes), the
 room seen from inside (glass: the general kernel) and the unit-internal stream (the record-array kernels). Every reference sample
 is computed once per (world, ray source, D, radius, sample) and shared. Radius 0 is the parent: oracle_path_depth's bytes."""
 import numpy as np

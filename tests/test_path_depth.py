@@ -1,4 +1,4 @@
-"""Path depth (include/vrt.h vrt_set_path_depth): what holds without a GPU. The checker (tests/oracle_path_depth.c: the oracle's
+"""Path depth (include/vrt.h vrt_set_path_depth): what holds without a GPU. The checker (tests/oracle_paths.c through oracle_path_depth: the oracle's
 path_trace loop with the rule applied to its one branch) is the oracle at depth 1, its float colour is the sum of the
 contributions it logs by the rule's formulas, its paths have the structure the rule gives them, the feature is not vacuous
 and (voxel ID, dist) do not depend on the depth; the library declares and exports the call and holds the new kernels. The

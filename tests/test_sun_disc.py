@@ -1,5 +1,5 @@
-"""Sun disc (include/vrt.h vrt_set_sun_disc): what holds without a GPU. The checker (tests/oracle_sun.c: oracle_path_depth's loop
-with the rule applied at the shadowing vertices) is oracle_path_depth at radius 0; its log shows the rule's draws, map, direction
+"""Sun disc (include/vrt.h vrt_set_sun_disc): what holds without a GPU. The checker (tests/oracle_paths.c through oracle_sun: the depth
+loop with the rule applied at the shadowing vertices) is oracle_path_depth at radius 0; its log shows the rule's draws, map, direction
 and n.l; its float colour is the sum of the contributions it logs; and the penumbra of a straight edge has the area of the
 visible part of the disc. The kernels are held to the checker on the MI355X (test_gpu_sun_disc.py)."""
 import ctypes as C
