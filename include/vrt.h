@@ -900,9 +900,8 @@ int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int ori
  *                       adds as vrt_accum_resolve_hdr_device is.
  * The accumulation forms read and write no byte of the accumulation's sums: vrt_accum_resolve*, vrt_accum_resolve_hdr* and
  * vrt_accum_guides* return the same bits with and without them. None of these calls takes a profiling slot or counts towards the
- * stride. Not provided: per-sample second moments of the HDR sums (vrt_filter_hdr_var's variance input is where they would arrive;
- * until then the accumulation forms estimate the variance spatially, or take the temporal one of vrt_accum_resolve_hdr_temporal below),
- * motion vectors of moving geometry, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
+ * stride. Per-sample second moments of the HDR sums: vrt_accum_keep_moments below, whose plane vrt_filter_hdr_var's variance input
+ * takes. Not provided: motion vectors of moving geometry, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
  * (an image-shaped batch can call vrt_filter_hdr with vrt_guide_rays_device's planes and a coverage plane made of its hit bytes). */
 #define VRT_FILTER_MAX_LEVELS 8
 #define VRT_FILTER_DEMODULATE 1u
@@ -968,7 +967,11 @@ int vrt_accum_resolve_hdr_filtered_device(vrt_ctx *ctx, const vrt_filter *f, con
  * vrt_filter_hdr_var_host  the same through HOST buffers, synchronous, staged through 72 bytes per pixel the context keeps.
  * vrt_accum_resolve_hdr_filtered_var, _device  vrt_accum_resolve_hdr_filtered{,_device} with this filter: the same input, the same
  *                       VRT_E_STATE rule, the guide state brought up to date as a vrt_accum_guides call would, 72 bytes per pixel
- *                       that belong to the accumulation. The accumulation keeps no second moments yet: always the spatial estimate.
+ *                       that belong to the accumulation. The variance: on an accumulation that keeps moments
+ *                       (vrt_accum_keep_moments below) and holds two samples or more, vrt_accum_variance_device's plane (M3) as
+ *                       d_variance, through four more bytes per pixel that belong to the accumulation, made at the first such call
+ *                       (an adaptive accumulation has min_samples >= 2, so every pixel then holds two samples); on every other
+ *                       accumulation, and with one sample, the spatial estimate (d_variance == NULL).
  * These calls read and write no byte of the accumulation's sums, take no profiling slot and do not count towards the stride. */
 typedef struct vrt_filter_var { int32_t levels; uint32_t flags; float sigma_normal, sigma_albedo, sigma_depth, sigma_lum; } vrt_filter_var;
 void vrt_filter_var_default(vrt_filter_var *f);
@@ -982,6 +985,46 @@ int vrt_accum_resolve_hdr_filtered_var(vrt_ctx *ctx, const vrt_filter_var *f, co
                                        float *out_variance);
 int vrt_accum_resolve_hdr_filtered_var_device(vrt_ctx *ctx, const vrt_filter_var *f, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
                                               void *d_variance_out, void *stream);
+/* EXTENSION: luminance moments of an HDR accumulation -- a MEASURED variance for the filter above. A sample's luminance exists only
+ * inside the sample kernels, so the sums are kept there.
+ *
+ * vrt_accum_keep_moments(ctx, 1) makes the HDR accumulations begun after it keep two more float64 sums per pixel. It is context state,
+ * read by the next vrt_accum_begin / _begin_ex / _begin_adaptive exactly as vrt_accum_keep_hdr is; it is not part of the restart
+ * rule, and changing it leaves a running accumulation as it was begun. It takes effect only in an accumulation begun with HDR on and
+ * is ignored otherwise. Default 0. VRT_E_INVALID unless enable is 0 or 1.
+ *
+ * All float32 operations below are rounded on their own; nothing is contracted.
+ *  M1. A sample's luminance and its square. y = Y(h(c)) with V1's Y (float32, V1's association) on the sample's three h(c) values of
+ *      vrt_accum_keep_hdr point 1; q = y * y, a FLOAT32 product (q <= 65504^2: no overflow).
+ *  M2. The sums. Two float64 sums per pixel start at +0.0: S1 = S1 + (double)y and S2 = S2 + (double)q, one add each per sample the
+ *      pixel takes, in sample-index order, exactly where and when the three colour sums take theirs. They continue across
+ *      vrt_accum_add calls (3 + 5 samples equal 8 bit for bit); whatever zeroes the colour sums zeroes them. A pixel whose every
+ *      sample is one float colour adds (double)y * k and (double)q * k for k samples at once: both exact for k <= 2^24, y and q being
+ *      floats, so the result is the k sequential adds'.
+ *  M3. The resolve, n the pixel's own count (the accumulation's when not adaptive). n < 2: the variance is 65504.0f * 65504.0f,
+ *      "unknown", the value the temporal pass gives a pixel without history. Otherwise
+ *        m1 = S1 / (double)n;  m2 = S2 / (double)n;  m1f = (float)m1;  sq = m1f * m1f (float32);  d = m2 - (double)sq
+ *        var = hv((float)(max(0, d) / (double)(n - 1)))      max with the zero first: NaN -> +0; hv of V2
+ *      the variance of the MEAN's luminance, what vrt_filter_hdr_var's d_variance asks for. The square of the mean is a float32
+ *      product on purpose, as q is: a pixel whose samples are all equal has m1 = y, sq = q, m2 = q and a variance of exactly +0 at
+ *      any count -- sky, the primary modes from the corner and pixels without a bounce are not handed rounding noise as a width. The
+ *      price: on a nearly constant pixel the rounding of m1 to float32 leaves a floor of about 2^-22 * m1^2 / (n - 1) (|d| below that
+ *      is not resolved, and may come out as +0 or as the floor).
+ *
+ * vrt_accum_variance    the M3 plane [H][W] into a HOST buffer, synchronous.
+ * vrt_accum_variance_device  the same into a DEVICE buffer, enqueued on `stream` (NULL: the context's), ordered against the adds as
+ *                       vrt_accum_resolve_hdr_device is.
+ * Both: VRT_E_STATE with no begin, no sample yet, an accumulation begun without HDR or begun without moments; VRT_E_INVALID for a NULL
+ * output. Neither takes a profiling slot or counts towards the stride.
+ * With moments off nothing changes: the same kernels, the same bytes, the same footprint. With moments on the accumulation takes 16
+ * bytes per pixel more, allocated at the begin; every resolve, vrt_accum_counts and the guide calls return the bits they return
+ * without -- the colour sums are the same bits -- and only vrt_accum_resolve_hdr_filtered_var{,_device} change, as said there.
+ * Not provided: moments of ray batches (vrt_shade_rays_hdr_device's d_sums are the caller's), moments as an input of
+ * vrt_accum_resolve_hdr_temporal, per-channel variance, a per-pixel mix of the spatial and the measured variance, frames, views,
+ * shards and vrt_multi. */
+int vrt_accum_keep_moments(vrt_ctx *ctx, int enable);
+int vrt_accum_variance(vrt_ctx *ctx, float *out_variance);
+int vrt_accum_variance_device(vrt_ctx *ctx, void *d_variance, void *stream);
 /* EXTENSION: temporal accumulation -- last frame's integrated colour and luminance moments reprojected into this frame through the
  * guide planes, each tap tested against them, blended with this frame's image, and a TEMPORAL variance handed to the filter above
  * (SVGF's rules). An accumulation restarts on every change of the camera block, so a moving camera never holds more than one frame's

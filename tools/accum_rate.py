@@ -65,6 +65,14 @@ between them (guide_per_sample_ms), and beside it one vrt_accum_add of as many s
 
     python3 tools/accum_rate.py --guides --scenes dragon_1080p room_inside_1080p --samples 16 --out profiles/guides_rate.jsonl
 
+--moments measures accumulations that keep luminance moments (vrt_accum_keep_moments) beside the same HDR accumulations without, in
+the same process: on each scene of --scenes, VRT_MODE_FULL at each --path-depth (default 1), from the corner and jittered, the wall time
+of one add of --samples samples each way, alternated (hdr_add_ms, moments_add_ms, their per-sample times and ratio), of one
+vrt_accum_variance_device (variance_ms), and of one vrt_accum_resolve_hdr_filtered_var_device at the defaults on the accumulation
+without moments (the spatial estimate) and with (the measured plane): filtered_var_spatial_ms, filtered_var_moments_ms.
+
+    python3 tools/accum_rate.py --moments --path-depth 1 4 --scenes dragon_1080p room_inside_1080p --samples 16 --out profiles/moments_rate.jsonl
+
 --out replaces the file: tools/shade_rays_rate.py --path-depth ... --append adds the ray batches' rows to it, so it runs second.
 --adaptive takes none of --path-depth, --scenes and --samples (it measures its own scenes and rounds) and refuses them.
 """
@@ -116,6 +124,7 @@ def main():
     ap.add_argument("--variant", type=int, default=None, metavar="V",
                     help="with --path-depth: the traversal variant (vrt_set_variant; 1: the record-array kernels), recorded as variant")
     ap.add_argument("--guides", action="store_true", help="the guide planes beside primary-mode adds (see above)")
+    ap.add_argument("--moments", action="store_true", help="HDR accumulations with luminance moments beside those without (see above)")
     ap.add_argument("--scenes", nargs="+", default=DEFAULT_SCENES, choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
     args = ap.parse_args()
@@ -134,6 +143,8 @@ def main():
         return adaptive_main(V, args)
     if args.guides:
         return guides_main(V, args)
+    if args.moments:
+        return moments_main(V, args)
     from conftest import MAPS, room_world
     W, H = 1920, 1080
     ctx = V.Context(0)
@@ -367,6 +378,65 @@ def guides_main(V, args):
                 rows.append(row)
         ctx.set_lens(0.0, 1.0)
     for d in d_planes:
+        ctx.device_free(d)
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+def moments_main(V, args):
+    W, H = 1920, 1080
+    ctx = V.Context(0)
+    d_rgb, d_rgba, d_var, d_plane = (ctx.device_alloc(W * H * k) for k in (12, 4, 4, 4))
+    rows = []
+
+    def timed(body):
+        ts = []
+        for _ in range(args.reps + 1):
+            t0 = time.perf_counter()
+            body()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts[1:])), min(ts[1:]), max(ts[1:])   # the first: code object load, buffers
+
+    for name, tex in _scenes(V, ctx, W, H, args.scenes):
+        opaque = V.tree_is_opaque(tex)
+        for depth in args.path_depth or [1]:
+            ctx.set_path_depth(depth)
+            for source, jitter in (("corner", False), ("jitter", True)):
+                for n in args.samples:
+                    ts = {False: [], True: []}
+                    for r in range(2 * max(args.reps, 1) + 2):          # alternated, the first of each untimed
+                        moments = bool(r & 1)
+                        ctx.accum_begin(W, H, 0, mode=V.MODES["full"], jitter=jitter, hdr=True, moments=moments)
+                        ctx.accum_add(n)          # the first add: pass 1 once per accumulation, code object load
+                        ctx.synchronize()
+                        t0 = time.perf_counter()
+                        ctx.accum_add(n)
+                        ctx.synchronize()
+                        if r >= 2:
+                            ts[moments].append((time.perf_counter() - t0) * 1e3)
+                    hdr_ms, mom_ms = float(np.median(ts[False])), float(np.median(ts[True]))
+                    # the accumulation begun last keeps moments: its plane, then the filtered resolve on it and on one without
+                    var = timed(lambda: ctx.accum_variance_device(d_plane))
+                    with_plane = timed(lambda: ctx.accum_resolve_hdr_filtered_var_device(d_rgb, d_rgba, d_var))
+                    ctx.accum_begin(W, H, 0, mode=V.MODES["full"], jitter=jitter, hdr=True)
+                    ctx.accum_add(2 * n)
+                    spatial = timed(lambda: ctx.accum_resolve_hdr_filtered_var_device(d_rgb, d_rgba, d_var))
+                    row = {"scene": name, "width": W, "height": H, "path": "opaque" if opaque else "general", "source": source,
+                           "path_depth": depth, "n": n, "hdr_add_ms": round(hdr_ms, 4), "moments_add_ms": round(mom_ms, 4),
+                           "hdr_add_ms_min_max": [round(min(ts[False]), 4), round(max(ts[False]), 4)],
+                           "moments_add_ms_min_max": [round(min(ts[True]), 4), round(max(ts[True]), 4)],
+                           "hdr_per_sample_ms": round(hdr_ms / n, 4), "moments_per_sample_ms": round(mom_ms / n, 4),
+                           "moments_vs_hdr": round(mom_ms / hdr_ms, 4), "variance_ms": round(var[0], 4),
+                           "filtered_var_spatial_ms": round(spatial[0], 4), "filtered_var_moments_ms": round(with_plane[0], 4),
+                           "filtered_var_moments_ms_min_max": [round(with_plane[1], 4), round(with_plane[2], 4)], "reps": args.reps}
+                    print(json.dumps(row), flush=True)
+                    rows.append(row)
+        ctx.set_path_depth(1)
+    for d in (d_rgb, d_rgba, d_var, d_plane):
         ctx.device_free(d)
     ctx.close()
     if args.out:

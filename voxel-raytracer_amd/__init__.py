@@ -353,6 +353,9 @@ def hip_lib():
         L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_keep_hdr.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_accum_keep_moments.argtypes = [C.c_void_p, C.c_int]
+        L.vrt_accum_variance.argtypes = [C.c_void_p, C.c_void_p]
+        L.vrt_accum_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
         L.vrt_accum_resolve_hdr_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
         L.vrt_denoise_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
@@ -979,14 +982,20 @@ class Context:
         self._chk(self._L.vrt_shade_rays_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, int(mode),
                                                 int(first_sample) & 0xFFFFFFFF, int(n_samples), d_rgba, d_id, stream))
 
-    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False, adaptive=None, hdr=False):
+    def accum_begin(self, width, height, first_sample=0, mode=MODE_FULL, jitter=False, adaptive=None, hdr=False, moments=False):
         """(Re)start the progressive accumulation of `mode` at sample index `first_sample` (vrt_accum_begin_ex); jitter=True
         moves each sample's ray inside the pixel (VRT_ACCUM_JITTER: anti-aliased frames). adaptive=(min_samples, max_samples,
         tolerance) makes it adaptive (vrt_accum_begin_adaptive): accum_add then adds rounds, in which only the pixels the
         stopping rule keeps active take a sample; accum_counts() reports them. hdr=True keeps float64 sums of the samples'
-        unclamped colours too (vrt_accum_keep_hdr, set for this begin): accum_resolve_hdr() resolves them."""
+        unclamped colours too (vrt_accum_keep_hdr, set for this begin): accum_resolve_hdr() resolves them. moments=True (needs
+        hdr=True) keeps two more float64 sums per pixel, of the samples' luminance and its square (vrt_accum_keep_moments, set for
+        this begin): accum_variance() resolves them, and accum_resolve_hdr_filtered_var() takes that plane."""
         if not isinstance(hdr, (bool, np.bool_)) and not (isinstance(hdr, (int, np.integer)) and hdr in (0, 1)):
             raise ValueError(f"hdr: expected a bool, got {hdr!r}")
+        if not isinstance(moments, (bool, np.bool_)) and not (isinstance(moments, (int, np.integer)) and moments in (0, 1)):
+            raise ValueError(f"moments: expected a bool, got {moments!r}")
+        if moments and not hdr:
+            raise ValueError("moments: the luminance moments ride with the HDR sums (hdr=True)")
         if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or mode not in (MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL):
             raise ValueError(f"mode: expected MODE_PRIMARY, MODE_PRIMARY_SHADOW or MODE_FULL, got {mode!r}")
         if not isinstance(jitter, (bool, np.bool_)) and not (isinstance(jitter, (int, np.integer)) and jitter in (0, 1)):
@@ -1010,10 +1019,12 @@ class Context:
             if not 0 <= tol <= 65535:
                 raise ValueError(f"adaptive tolerance: expected an integer in [0, 65535], got {tol!r}")
             self._chk(self._L.vrt_accum_keep_hdr(self._h, 1 if hdr else 0))
+            self._chk(self._L.vrt_accum_keep_moments(self._h, 1 if moments else 0))
             self._chk(self._L.vrt_accum_begin_adaptive(self._h, int(width), int(height), int(mode), int(first_sample),
                                                        ACCUM_JITTER if jitter else 0, lo, hi, tol))
         else:
             self._chk(self._L.vrt_accum_keep_hdr(self._h, 1 if hdr else 0))
+            self._chk(self._L.vrt_accum_keep_moments(self._h, 1 if moments else 0))
             self._chk(self._L.vrt_accum_begin_ex(self._h, int(width), int(height), int(mode), int(first_sample),
                                                  ACCUM_JITTER if jitter else 0))
         self._accum_shape = (int(height), int(width))
@@ -1254,6 +1265,18 @@ class Context:
         tm = self._tonemap(tonemap, exposure)
         self._chk(self._L.vrt_accum_resolve_hdr_device(self._h, d_rgb, C.byref(tm), d_rgba, d_shown, stream))
 
+    def accum_variance(self):
+        """The variance of the mean's luminance of an accumulation begun with moments=True (vrt_accum_variance, M1-M3 of
+        include/vrt.h) -> float32[H, W]; 65504^2 ("unknown") where a pixel holds fewer than two samples."""
+        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
+        var = np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_accum_variance(self._h, var.ctypes.data))
+        return var
+
+    def accum_variance_device(self, ptr, stream=None):
+        """vrt_accum_variance_device: a DEVICE buffer of H*W floats, enqueued on `stream`"""
+        self._chk(self._L.vrt_accum_variance_device(self._h, ptr, stream))
+
     def accum_guides(self):
         """The accumulation's guide planes (vrt_accum_guides): first-hit features averaged over the samples in the sums ->
         {"normal": float32[H,W,3], "albedo": float32[H,W,4], "depth": float32[H,W], "coverage": float32[H,W]}."""
@@ -1456,7 +1479,9 @@ class Context:
 
     def accum_resolve_hdr_filtered_var(self, filter=None, tonemap="clamp", exposure=1.0):
         """The variance-guided filter on an HDR accumulation (vrt_accum_resolve_hdr_filtered_var): its float mean filtered with its
-        own guide planes and a spatially estimated variance -> (rgb float32[H,W,3], rgba8[H,W,4], variance float32[H,W])."""
+        own guide planes and its variance -> (rgb float32[H,W,3], rgba8[H,W,4], variance float32[H,W]). The variance is the
+        measured one (accum_variance()'s plane) on an accumulation begun with moments=True that holds two samples or more, and a
+        spatial estimate from the mean itself on every other."""
         tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
         f = self._filter_var(filter)
         h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so

@@ -10,6 +10,8 @@
 // An HDR accumulation (vrt_accum_keep_hdr before the begin) keeps three float64 sums per pixel of the samples' float colours too:
 // the kernels' HDR forms, 24 + 12 bytes per pixel allocated only then, and vrt_accum_resolve_hdr's mean and tone map. Where the
 // samples are all one frame, that frame comes from the HDR frame kernel, which hands out its float colour.
+// One that keeps moments too (vrt_accum_keep_moments): 16 bytes per pixel more for the two float64 sums of the samples' luminance and
+// its square, the kernels' MOM forms, and vrt_accum_variance's plane (M3).
 #include "vrt_stage.h"
 #include "vrt_launch.h"
 
@@ -66,6 +68,15 @@ int resolve_into(vrt_ctx *c, void *d_rgba, void *d_id, void *d_shown, hipStream_
 int resolve_hdr_state(vrt_ctx *c, const char *what, const vrt_tonemap *tm) {
     const int r = accum_state(c, what, true);
     return r ? r : check_tonemap(c, what, tm);
+}
+
+// vrt_accum_variance*: the call-order checks of an HDR resolve, an accumulation that keeps moments, an output
+int variance_state(vrt_ctx *c, const char *what, const void *out) {
+    const int r = accum_state(c, what, true);
+    if (r) return r;
+    if (!c->accum.moments)
+        return vrt_fail(c, VRT_E_STATE, std::string(what) + ": the accumulation keeps no moments (vrt_accum_keep_moments before the begin)");
+    return out ? VRT_OK : vrt_fail(c, VRT_E_INVALID, std::string(what) + ": null output");
 }
 
 // float64 sums -> float mean into d_rgb, its tone-mapped rgba8 into d_rgba (either may be null), the display pass into d_shown
@@ -132,6 +143,11 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
         if ((r = reserve_synced(c, {{&ac.d_hsum, px * 24}, {&ac.d_hframe, px * 12}}))) return r;
         ac.hdr_pixels = px;
     }
+    if (c->accum_keep_hdr && c->accum_keep_moments && px > ac.mom_pixels) {   // the moments: S1 and S2
+        ac.begun = false;
+        if ((r = reserve_synced(c, {{&ac.d_msum, px * 16}}))) return r;
+        ac.mom_pixels = px;
+    }
     if (!ac.added) VRT_HIP(c, hipEventCreateWithFlags(&ac.added, hipEventDisableTiming));
     if (!ac.read) VRT_HIP(c, hipEventCreateWithFlags(&ac.read, hipEventDisableTiming));
     ac.begun = true;
@@ -149,10 +165,24 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
     ac.max_samples = rule ? rule[1] : 0u;
     ac.tolerance = rule ? rule[2] : 0u;
     ac.hdr = c->accum_keep_hdr;
+    ac.moments = ac.hdr && c->accum_keep_moments;
     return VRT_OK;
 }
 
 }  // namespace
+
+int vrt_internal::accum_variance_into(vrt_ctx *c, float *d_variance, hipStream_t s) {
+    Accum &ac = c->accum;
+    const vrt::accum::MomVariance q{ac.d_msum, ac.d_sums, d_variance, ac.total, ac.adaptive ? 1u : 0u, (uint32_t)((size_t)ac.width * (size_t)ac.height)};
+    VRT_HIP(c, vrt::launch::accum_variance(q, s));
+    return VRT_OK;
+}
+
+int vrt_internal::ensure_variance_plane(vrt_ctx *c) {
+    Accum &ac = c->accum;
+    const size_t bytes = (size_t)ac.width * (size_t)ac.height * 4;
+    return bytes <= ac.d_mvar.bytes() ? VRT_OK : reserve_synced(c, {{&ac.d_mvar, bytes}});
+}
 
 bool vrt_internal::accum_inputs_current(const vrt_ctx *c) { return same_inputs(c, c->accum); }
 
@@ -170,10 +200,12 @@ int vrt_internal::accum_state(vrt_ctx *c, const char *what, bool need_hdr) {
 hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSet &vs, const Variant &v, int mode, int grid, bool two_pass,
                                            const vrt::LensSel &lsel, const AccumStep &acc, hipStream_t s) {
     namespace launch = vrt::launch;
-    vrt::accum::HdrArgs q{};
+    vrt::accum::MomArgs q{};
     q.hsum = ac.d_hsum;
     q.hframe = ac.d_hframe;
+    q.msum = ac.d_msum;
     const bool hdr = acc.hdr, adaptive = acc.adaptive;
+    const launch::AccumForm form = launch::accum_form(hdr, acc.moments);
     // the kernels of VRT_MODE_FULL by the step's own snapshot (acc.paths: what the add that queued it read), not the context
     launch::PathFamily fam;
     launch::PathArgs pa;
@@ -202,9 +234,9 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     if (acc.frame_only)   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
         return (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? launch::accum_frame_hdr(mode, v, a, vs, hf, grid, s) : hipErrorInvalidValue;
     if (mode != VRT_MODE_FULL)   // one launch, the samples looped in the lanes
-        return launch::accum_primary(hdr, mode, src, v, a, vs, q, adaptive, l, grid, s);
+        return launch::accum_primary(hdr, acc.moments, mode, src, v, a, vs, q, adaptive, l, grid, s);
     if (two_pass && src != Source::kCorner)   // MODE 6's chain per sample, looped in the lanes
-        return launch::accum_opaque(hdr, fam, pa, src, a, vs, q, adaptive, l, grid, s);
+        return launch::accum_opaque(form, fam, pa, src, a, vs, q, adaptive, l, grid, s);
     hipError_t e = hipSuccess;
     if (two_pass) {   // pass 1 once per accumulation, then one launch of the sample-looped bounce
         a.defer_rec = reinterpret_cast<float *>(ac.d_seed.get());
@@ -216,7 +248,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
             if (e != hipSuccess) return e;
             ac.pass1 = true;
         }
-        return launch::accum_bounce(hdr, fam, pa, a, vs, q, adaptive, grid, s);
+        return launch::accum_bounce(form, fam, pa, a, vs, q, adaptive, grid, s);
     }
     // the general path tracer, one launch per sample; an adaptive round first lists the tiles with an active pixel
     const vrt::accum::Tiles tl{ac.d_sums, ac.d_sq, ac.d_tiles, ac.d_tiles + ac.tile_cap, a.width, a.height, ac.min_samples, ac.max_samples,
@@ -225,7 +257,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         q.first = acc.first + k;
         q.n = 1u;
         if (adaptive) e = launch::adaptive_tiles(tl, s);
-        if (e == hipSuccess) e = launch::accum_full(hdr, fam, pa, src, v, a, vs, q, adaptive, l, grid, s);
+        if (e == hipSuccess) e = launch::accum_full(form, fam, pa, src, v, a, vs, q, adaptive, l, grid, s);
     }
     return e;
 }
@@ -278,6 +310,7 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         VRT_HIP(c, hipMemsetAsync(ac.d_sums, 0, (size_t)ac.width * (size_t)ac.height * 16, c->stream));
         if (ac.adaptive) VRT_HIP(c, hipMemsetAsync(ac.d_sq, 0, (size_t)ac.width * (size_t)ac.height * 8, c->stream));
         if (ac.hdr) VRT_HIP(c, hipMemsetAsync(ac.d_hsum, 0, (size_t)ac.width * (size_t)ac.height * 24, c->stream));   // +0.0
+        if (ac.moments) VRT_HIP(c, hipMemsetAsync(ac.d_msum, 0, (size_t)ac.width * (size_t)ac.height * 16, c->stream));
         take_inputs(c, ac);
         ++ac.epoch;
         ac.total = 0;
@@ -306,25 +339,29 @@ int vrt_accum_add(vrt_ctx *c, uint32_t n_samples, uint32_t *total_out) {
         const vrt::accum::Repeat q{ac.d_pass1, ac.d_sums, n_samples, (uint32_t)((size_t)ac.width * (size_t)ac.height)};
         hipError_t e;
         if (ac.adaptive) {   // each pixel's count goes to min(rounds, min_samples): no trace
-            vrt::accum::RepeatHdrOf<vrt::accum::RepeatAdapt> qa{};
+            vrt::accum::RepeatMomOf<vrt::accum::RepeatAdapt> qa{};
             static_cast<vrt::accum::Repeat &>(qa) = q;
             qa.sq = ac.d_sq;
             qa.min = ac.min_samples;
             qa.hsum = ac.d_hsum;
             qa.hframe = ac.d_hframe;
-            e = ac.hdr ? vrt::launch::accum_repeat_hdr(qa, c->stream) : vrt::launch::accum_repeat(qa, c->stream);
+            qa.msum = ac.d_msum;
+            e = ac.moments ? vrt::launch::accum_repeat_mom(qa, c->stream)
+                           : (ac.hdr ? vrt::launch::accum_repeat_hdr(qa, c->stream) : vrt::launch::accum_repeat(qa, c->stream));
         } else if (ac.hdr) {
-            vrt::accum::RepeatHdrOf<vrt::accum::Repeat> qh{};
+            vrt::accum::RepeatMomOf<vrt::accum::Repeat> qh{};
             static_cast<vrt::accum::Repeat &>(qh) = q;
             qh.hsum = ac.d_hsum;
             qh.hframe = ac.d_hframe;
-            e = vrt::launch::accum_repeat_hdr(qh, c->stream);
+            qh.msum = ac.d_msum;
+            e = ac.moments ? vrt::launch::accum_repeat_mom(qh, c->stream) : vrt::launch::accum_repeat_hdr(qh, c->stream);
         } else {
             e = vrt::launch::accum_repeat(q, c->stream);
         }
         if (e != hipSuccess) r = vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     } else if (r == VRT_OK) {
         AccumStep step{ac.first + base, n_samples, jitter, ac.lens[0], ac.lens[1], ac.adaptive, ac.hdr};
+        step.moments = ac.moments;
         // the snapshot launch_accum_step() selects the kernels by: the depth and the sun as the sums took them, the emitter switches
         // (same_inputs() has found them unchanged) and the list as this add found it
         step.paths = PathSetup{ac.path_depth, ac.sun_disc, sampling, c->emitter_importance, c->emitter_mis,
@@ -372,6 +409,32 @@ int vrt_accum_keep_hdr(vrt_ctx *c, int enable) {
     if (enable != 0 && enable != 1) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_keep_hdr: enable must be 0 or 1");
     c->accum_keep_hdr = enable == 1;
     return VRT_OK;
+}
+
+int vrt_accum_keep_moments(vrt_ctx *c, int enable) {
+    if (!c) return VRT_E_INVALID;
+    if (enable != 0 && enable != 1) return vrt_fail(c, VRT_E_INVALID, "vrt_accum_keep_moments: enable must be 0 or 1");
+    c->accum_keep_moments = enable == 1;
+    return VRT_OK;
+}
+
+int vrt_accum_variance(vrt_ctx *c, float *out_variance) {
+    int r = variance_state(c, "vrt_accum_variance", out_variance);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    Accum &ac = c->accum;
+    if ((r = ensure_variance_plane(c)) || (r = accum_variance_into(c, ac.d_mvar, c->stream))) return r;
+    vrt_stage::Stage st(4);
+    st.out((size_t)ac.width * (size_t)ac.height * 4, out_variance, ac.d_mvar);
+    return st.download(c, c->stream);
+}
+
+int vrt_accum_variance_device(vrt_ctx *c, void *d_variance, void *stream) {
+    const int r = variance_state(c, "vrt_accum_variance_device", d_variance);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return accum_joined(c, s, [&] { return accum_variance_into(c, static_cast<float *>(d_variance), s); });
 }
 
 int vrt_accum_resolve_hdr(vrt_ctx *c, float *out_rgb, const vrt_tonemap *tm, uint8_t *out_rgba8, uint8_t *out_shown_rgba8) {

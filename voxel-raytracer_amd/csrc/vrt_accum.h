@@ -1,5 +1,5 @@
 // vrt_accum.h -- the arguments of the progressive-accumulation kernels (vrt_accum.hip.h), shared by the host side (vrt_accum.cpp)
-// and the launch files (vrt_launch_accum.hip, vrt_launch_accum_hdr.hip).
+// and the launch files (vrt_launch_accum.hip, vrt_launch_accum_hdr.hip, vrt_launch_accum_mom.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -79,10 +79,21 @@ struct HdrOf : BASE {
     double *hsum;                // 3 doubles per pixel, row-major: the R, G, B sums of h(c)
     const float *hframe;         // 3 floats per pixel: the corner frame's float colour (bounce kernel: pass 1's), where one was made
 };
-template <bool ADAPT, bool HDR = false>
-using ArgsOf = typename std::conditional<HDR, HdrOf<typename std::conditional<ADAPT, AdaptArgs, Args>::type>,
-                                         typename std::conditional<ADAPT, AdaptArgs, Args>::type>::type;
-using HdrArgs = HdrOf<AdaptArgs>;   // what the dispatcher fills; the launch functions pass the kernel its own slice
+// ---- luminance moments (include/vrt.h vrt_accum_keep_moments) ----
+// Beside the HDR sums, two float64 sums per pixel of the samples' luminance y = Y(h(c)) and its float32 square q = y * y (M1, M2),
+// added where and when the colour sums are. The kernels' template parameter MOM (with HDR) picks the argument type that carries them,
+// as HDR picks HdrOf<>: the HDR-only kernels keep their arguments and their code.
+template <class BASE>
+struct MomOf : BASE {
+    double *msum;                // 2 doubles per pixel, row-major: S1 = sum of y, S2 = sum of q
+};
+template <bool ADAPT>
+using PlainArgsOf = typename std::conditional<ADAPT, AdaptArgs, Args>::type;
+template <bool ADAPT, bool HDR = false, bool MOM = false>
+using ArgsOf = typename std::conditional<MOM, MomOf<HdrOf<PlainArgsOf<ADAPT>>>,
+                                         typename std::conditional<HDR, HdrOf<PlainArgsOf<ADAPT>>, PlainArgsOf<ADAPT>>::type>::type;
+using HdrArgs = HdrOf<AdaptArgs>;
+using MomArgs = MomOf<HdrArgs>;     // what the dispatcher fills; the launch functions pass the kernel its own slice
 
 // hdr_frame_kernel: where the corner frame's bytes, id_dist and float colour go
 struct HdrFrame {
@@ -102,6 +113,16 @@ struct HdrResolve {
     uint32_t pixels;
     int32_t op;                  // VRT_TONEMAP_*
     float exposure;
+};
+
+// M3: the two moment sums -> the variance of the mean's luminance, one float per pixel
+struct MomVariance {
+    const double *msum;
+    const uint32_t *sums;        // adaptive: the pixel's own count is its fourth word
+    float *out;
+    uint32_t n;                  // samples in the sums (not adaptive)
+    uint32_t adaptive;
+    uint32_t pixels;
 };
 
 // Before each round of a one-sample kernel: the 8 x 8 tiles of the frame that hold an active pixel -> tiles[0 .. *n_tiles)
@@ -134,6 +155,11 @@ template <class BASE>
 struct RepeatHdrOf : BASE {
     double *hsum;
     const float *hframe;
+};
+// ... and of those that keep moments (repeat_mom_kernel, a sibling of the HDR repeat kernels)
+template <class BASE>
+struct RepeatMomOf : RepeatHdrOf<BASE> {
+    double *msum;
 };
 
 // Where a sample's ray comes from (vrt_accum.hip.h CornerSource, JitterSource, LensSource): the pixel's corner, the jittered ray

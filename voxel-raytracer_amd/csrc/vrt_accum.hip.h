@@ -33,6 +33,11 @@
 // Where every sample of a pixel is the same float c (repeat_kernel, the bounce kernel's sky and emissive pixels), k samples add
 // (double)c * k: m * c is exact in a double for m <= 2^24, so the product equals the k adds. Those routes read the float from
 // hdr_frame_kernel's image, which replaces the frame (or pass 1) they otherwise take the bytes from. Both, and hdr_resolve_kernel: vrt_accum_hdr.hip.h.
+//
+// Accumulations that keep moments (include/vrt.h vrt_accum_keep_moments, points M1-M3) take the HDR kernels with the template
+// parameter MOM = true as well: each sample's luminance y = Y(h(c)) and its float32 square go into two more float64 sums per pixel,
+// one add each where the colour sums take theirs, and k equal samples add (double)y * k and (double)q * k -- exact as above, y and
+// q being floats. The repeat kernels' forms and the M3 resolve: vrt_accum_mom.hip.h.
 #pragma once
 #include "vrt_accum.h"
 #include "vrt_hdr.hip.h"
@@ -122,6 +127,39 @@ VRT_DEV void lds_add_hdr(volatile double *p, int n, const float *fc) {
     p[2 * n] = p[2 * n] + (double)hdr_value(fc[2]);
 }
 
+// ---- luminance moments (MOM = true): M1 and M2 of include/vrt.h vrt_accum_keep_moments ----
+struct MomSum { double s1, s2; };
+
+// y = Y(h(c)) with V1's Y and its association
+VRT_DEV float mom_luminance(const float *fc) { return (0.2126f * hdr_value(fc[0]) + 0.7152f * hdr_value(fc[1])) + 0.0722f * hdr_value(fc[2]); }
+
+VRT_DEV MomSum load_mom(const double *msum, size_t o) {
+    const double *p = msum + o * 2;
+    return MomSum{p[0], p[1]};
+}
+VRT_DEV void store_mom(double *msum, size_t o, const MomSum &m) {
+    double *p = msum + o * 2;
+    p[0] = m.s1; p[1] = m.s2;
+}
+VRT_DEV void add_mom(const float *fc, MomSum &m) {
+    const float y = mom_luminance(fc), q = y * y;
+    m.s1 = m.s1 + (double)y;
+    m.s2 = m.s2 + (double)q;
+}
+VRT_DEV void add_mom_repeat(const float *fc, uint32_t k, MomSum &m) {
+    const float y = mom_luminance(fc), q = y * y;
+    m.s1 = m.s1 + (double)y * (double)k;
+    m.s2 = m.s2 + (double)q * (double)k;
+}
+// ... in the LDS slots of the sample-looped kernels, planes 3 and 4 behind the three colour sums' (16 bytes more per lane)
+VRT_DEV void lds_put_mom(volatile double *p, int n, const MomSum &m) { p[3 * n] = m.s1; p[4 * n] = m.s2; }
+VRT_DEV MomSum lds_get_mom(volatile double *p, int n) { return MomSum{p[3 * n], p[4 * n]}; }
+VRT_DEV void lds_add_mom(volatile double *p, int n, const float *fc) {
+    const float y = mom_luminance(fc), q = y * y;
+    p[3 * n] = p[3 * n] + (double)y;
+    p[4 * n] = p[4 * n] + (double)q;
+}
+
 VRT_DEV size_t pixel_offset(const KArgs &a, int px, int py) { return (size_t)py * (size_t)a.width + (size_t)px; }
 
 // This lane's pixel of 8 x 8 tile `tile` of a whole frame (KArgs: row0 = 0, n_rows = height, compact = 0)
@@ -197,8 +235,9 @@ template <class A> struct ArgLensSource {
 
 // q.n samples q.first, q.first + 1, ... of MODE 0 or 1, looped in the lanes: the traversal the frame kernel would take
 // (trace_kernel's 8 x 8 tiles, its eye lookup and empty-octant proofs: the eye does not move), the shadow ray in MODE 1
-template <class SRC, int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT, bool HDR, class... L>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const L... lens) {
+template <class SRC, int MODE, class TRAV, int BLOCK, int WPE, bool ADAPT, bool HDR, bool MOM, class... L>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void primary_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR, MOM> q, const L... lens) {
+    static_assert(HDR || !MOM, "the moments ride with the HDR sums");
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
@@ -206,10 +245,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     if (!frame_pixel<BLOCK>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
     PixelState st{};
-    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? BLOCK : 1];   // (HDR = false: never touched, and dropped)
+    __shared__ double s_hsum[HDR ? (MOM ? 5 : 3) : 1][HDR ? BLOCK : 1];   // (HDR = false: never touched, and dropped)
     volatile double *vs_hsum = &s_hsum[0][HDR ? threadIdx.x : 0];
     if constexpr (ADAPT) st = load_state(q, pixel_offset(a, px, py));
     if constexpr (HDR) lds_put_hdr(vs_hsum, BLOCK, load_hdr(q.hsum, pixel_offset(a, px, py)));
+    if constexpr (MOM) lds_put_mom(vs_hsum, BLOCK, load_mom(q.msum, pixel_offset(a, px, py)));
     for (uint32_t k = 0; k < q.n; ++k) {
         if constexpr (ADAPT)
             if (!state_active(q.min, q.max, q.tol, st)) break;
@@ -228,17 +268,20 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         if constexpr (ADAPT) add_sample(rgba, st);
         else add_bytes(rgba, r, g, b);
         if constexpr (HDR) lds_add_hdr(vs_hsum, BLOCK, fc);
+        if constexpr (MOM) lds_add_mom(vs_hsum, BLOCK, fc);
     }
     if constexpr (ADAPT) store_state(q, pixel_offset(a, px, py), st);
     else store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
     if constexpr (HDR) store_hdr(q.hsum, pixel_offset(a, px, py), lds_get_hdr(vs_hsum, BLOCK));
+    if constexpr (MOM) store_mom(q.msum, pixel_offset(a, px, py), lds_get_mom(vs_hsum, BLOCK));
 }
 
 // q.n samples of MODE 6's two stages, looped in the lanes: pass 1 from the sample's ray, its seed in registers, then bounce_pixel
 // with initRNG's sample index; 64 lanes, one 8 x 8 tile per wave. Pass 1 depends on the sample, so it cannot be shared as
 // bounce_accum_kernel shares it.
-template <class SRC, class TRAV, int WPE, bool ADAPT, bool HDR, class... L>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const L... lens) {
+template <class SRC, class TRAV, int WPE, bool ADAPT, bool HDR, bool MOM, class... L>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void opaque_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR, MOM> q, const L... lens) {
+    static_assert(HDR || !MOM, "the moments ride with the HDR sums");
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
@@ -247,10 +290,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     if (!frame_pixel<64>(a, px, py)) return;
     uint32_t r = 0u, g = 0u, b = 0u;
     PixelState st{};
-    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];
+    __shared__ double s_hsum[HDR ? (MOM ? 5 : 3) : 1][HDR ? 64 : 1];
     volatile double *vs_hsum = &s_hsum[0][HDR ? threadIdx.x : 0];
     if constexpr (ADAPT) st = load_state(q, pixel_offset(a, px, py));
     if constexpr (HDR) lds_put_hdr(vs_hsum, 64, load_hdr(q.hsum, pixel_offset(a, px, py)));
+    if constexpr (MOM) lds_put_mom(vs_hsum, 64, load_mom(q.msum, pixel_offset(a, px, py)));
     for (uint32_t k = 0; k < q.n; ++k) {
         if constexpr (ADAPT)
             if (!state_active(q.min, q.max, q.tol, st)) break;
@@ -277,16 +321,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
         if constexpr (ADAPT) add_sample(rgba, st);
         else add_bytes(rgba, r, g, b);
         if constexpr (HDR) lds_add_hdr(vs_hsum, 64, fc);
+        if constexpr (MOM) lds_add_mom(vs_hsum, 64, fc);
     }
     if constexpr (ADAPT) store_state(q, pixel_offset(a, px, py), st);
     else store_sums(q.sums, pixel_offset(a, px, py), r, g, b);
     if constexpr (HDR) store_hdr(q.hsum, pixel_offset(a, px, py), lds_get_hdr(vs_hsum, 64));
+    if constexpr (MOM) store_mom(q.msum, pixel_offset(a, px, py), lds_get_mom(vs_hsum, 64));
 }
 
 // Sample q.first (q.n == 1) of the general full path tracer: trace_kernel<2>'s tiles, one pixel per lane.
 // ADAPT: the waves take the round's listed tiles (listed_pixel()), and only active lanes trace.
-template <class SRC, class TRAV, int BLOCK, int WPE, bool ADAPT, bool HDR, class... L>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const L... lens) {
+template <class SRC, class TRAV, int BLOCK, int WPE, bool ADAPT, bool HDR, bool MOM, class... L>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) void full_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR, MOM> q, const L... lens) {
+    static_assert(HDR || !MOM, "the moments ride with the HDR sums");
     const SRC src{lens...};
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
@@ -320,6 +367,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         add_hdr(fc, hs);
         store_hdr(q.hsum, pixel_offset(a, px, py), hs);
     }
+    if constexpr (MOM) {
+        MomSum ms = load_mom(q.msum, pixel_offset(a, px, py));
+        add_mom(fc, ms);
+        store_mom(q.msum, pixel_offset(a, px, py), ms);
+    }
     if constexpr (ADAPT) {
         add_sample(rgba, st);
         store_state(q, pixel_offset(a, px, py), st);
@@ -349,11 +401,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 template <class TRAV, bool ADAPT, bool HDR>
 constexpr int bounce_wpe() { return deep_paths<TRAV>::value ? (ADAPT && HDR ? 3 : 4) : 7; }
 constexpr int kDeepOpaqueWpe = 4;   // opaque_accum_kernel over DeepPaths<...> (vrt_launch_accum.hip.h)
-template <class TRAV, bool ADAPT = false, bool HDR = false, class... X>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<TRAV, ADAPT, HDR>()))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR> q, const X... arg) {
+// MOM: the two moment sums wait there as well (1 KiB more per wave: 126 KiB at 28 waves); sky and emissive pixels take y and q from the
+// same float colour.
+template <class TRAV, bool ADAPT = false, bool HDR = false, bool MOM = false, class... X>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<TRAV, ADAPT, HDR>()))) void bounce_accum_kernel(const KArgs a, const ViewSet vs, const ArgsOf<ADAPT, HDR, MOM> q, const X... arg) {
+    static_assert(HDR || !MOM, "the moments ride with the HDR sums");
     __shared__ uint32_t s_seed[kSeedPlanes][64];
     __shared__ uint32_t s_sum[3][64];
-    __shared__ double s_hsum[HDR ? 3 : 1][HDR ? 64 : 1];   // (HDR = false: never touched, and dropped)
+    __shared__ double s_hsum[HDR ? (MOM ? 5 : 3) : 1][HDR ? 64 : 1];   // (HDR = false: never touched, and dropped)
     typename TRAV::Ctx tc_;
     TRAV::block_init(a, tc_);
     if constexpr (sizeof...(X) != 0) ((tc_.sun = arg), ...);   // the one Sun, assigned as full_accum_kernel assigns it and for its reason
@@ -369,6 +424,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<T
     HdrSum hs{};
     if constexpr (ADAPT) st = load_state(q, (size_t)py * (size_t)a.width + (size_t)px);
     if constexpr (HDR) hs = load_hdr(q.hsum, (size_t)py * (size_t)a.width + (size_t)px);
+    MomSum ms{};
+    if constexpr (MOM) ms = load_mom(q.msum, (size_t)py * (size_t)a.width + (size_t)px);
     if (word & kSeedValid) {
 #pragma unroll
         for (uint32_t p = 0; p < kSeedPlanes; ++p) s_seed[p][lane] = sp[p * 64];
@@ -382,6 +439,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<T
         volatile uint32_t *vs_sum = &s_sum[0][0];
         volatile double *vs_hsum = &s_hsum[0][0];
         if constexpr (HDR) { vs_hsum[0 * 64 + lane] = hs.r; vs_hsum[1 * 64 + lane] = hs.g; vs_hsum[2 * 64 + lane] = hs.b; }
+        if constexpr (MOM) lds_put_mom(vs_hsum + lane, 64, ms);
         // every sample is bounce_pixel's own arithmetic on the same seed: direct term, then the bounce's term, then unorm8
         for (uint32_t k = 0; k < q.n; ++k) {
             if constexpr (ADAPT) {
@@ -400,6 +458,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<T
                 vs_hsum[0 * 64 + lane] = vs_hsum[0 * 64 + lane] + (double)hdr_value(fc[0]);
                 vs_hsum[1 * 64 + lane] = vs_hsum[1 * 64 + lane] + (double)hdr_value(fc[1]);
                 vs_hsum[2 * 64 + lane] = vs_hsum[2 * 64 + lane] + (double)hdr_value(fc[2]);
+                if constexpr (MOM) lds_add_mom(vs_hsum + lane, 64, fc);
             } else full::bounce_pixel<TRAV>(ak, tc_, px, py, seed, rgba, q.first + k);
             vs_sum[0 * 64 + lane] = vs_sum[0 * 64 + lane] + (rgba & 0xffu);
             vs_sum[1 * 64 + lane] = vs_sum[1 * 64 + lane] + ((rgba >> 8) & 0xffu);
@@ -412,17 +471,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(bounce_wpe<T
         }
         r = vs_sum[0 * 64 + lane]; g = vs_sum[1 * 64 + lane]; b = vs_sum[2 * 64 + lane];
         if constexpr (HDR) { hs.r = vs_hsum[0 * 64 + lane]; hs.g = vs_hsum[1 * 64 + lane]; hs.b = vs_hsum[2 * 64 + lane]; }
+        if constexpr (MOM) ms = lds_get_mom(vs_hsum + lane, 64);
     } else if constexpr (ADAPT) {
         const uint32_t more = adaptive_constant_count(st.n, q.n, q.min) - st.n;
         add_repeat(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], more, st);
         r = st.r; g = st.g; b = st.b;
         if constexpr (HDR) add_hdr_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, more, hs);
+        if constexpr (MOM) add_mom_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, more, ms);
     } else {   // sky, emissive surfaces: pass 1's bytes are every sample's
         add_bytes(q.pass1_rgba[(size_t)py * (size_t)a.width + (size_t)px], r, g, b);
         r *= q.n; g *= q.n; b *= q.n;
         if constexpr (HDR) add_hdr_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, q.n, hs);
+        if constexpr (MOM) add_mom_repeat(q.hframe + ((size_t)py * (size_t)a.width + (size_t)px) * 3, q.n, ms);
     }
     if constexpr (HDR) store_hdr(q.hsum, (size_t)py * (size_t)a.width + (size_t)px, hs);
+    if constexpr (MOM) store_mom(q.msum, (size_t)py * (size_t)a.width + (size_t)px, ms);
     if constexpr (ADAPT) {
         st.r = r; st.g = g; st.b = b;
         store_state(q, (size_t)py * (size_t)a.width + (size_t)px, st);

@@ -183,7 +183,9 @@ int filter_host(vrt_ctx *c, const char *what, int width, int height, const Plane
 
 // The accumulation forms: mean and planes into the accumulation's stage and the filter on them. to_host: the outputs are the caller's
 // host buffers, filled on the context's stream before the return; else device memory, written in the order of `stream`. The
-// accumulation has no variance of its own: the variance-guided form estimates it spatially.
+// variance-guided form takes the variance an accumulation that keeps moments has measured (vrt_accum_variance_device's plane, M3,
+// through the accumulation's own four bytes per pixel) once every pixel holds two samples; any other accumulation has none of its
+// own, and the form estimates it spatially.
 int filter_accum(vrt_ctx *c, const char *what, Params k, const vrt_tonemap *tm, bool to_host, void *out_rgb, void *out_rgba8, void *out_variance,
                  void *stream) {
     int r = accum_state(c, what, true);   // the call-order checks: those of vrt_accum_guides, then vrt_accum_resolve_hdr's
@@ -197,8 +199,13 @@ int filter_accum(vrt_ctx *c, const char *what, Params k, const vrt_tonemap *tm, 
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if ((r = vrt_accum_guides_device(c, st.at(kNormal), st.at(kAlbedo), st.at(kDepth), st.at(kCoverage), s))) return r;   // brings the guide state up to date first
     if ((r = vrt_accum_resolve_hdr_device(c, st.at(kRgb), tm, nullptr, nullptr, s))) return r;
+    Planes p = planes_of(st);
+    if (k.var && ac.moments && ac.total >= 2u) {   // (adaptive: min_samples >= 2, so every pixel holds two samples)
+        if ((r = ensure_variance_plane(c)) || (r = vrt_accum_variance_device(c, ac.d_mvar, s))) return r;
+        p.variance = ac.d_mvar;
+    }
     // the stage belongs to the accumulation, whose every use the context's stream orders: a caller's stream is joined back
-    r = accum_joined(c, s, [&] { return filter_frame(c, what, ac.width, ac.height, planes_of(st), k, tm, s); });
+    r = accum_joined(c, s, [&] { return filter_frame(c, what, ac.width, ac.height, p, k, tm, s); });
     return r ? r : st.download(c, c->stream);
 }
 

@@ -287,6 +287,11 @@ struct vrt_ctx {
         size_t hdr_pixels = 0;                   // what the two above were last sized for
         DevBuf<float> d_hrgb;                    // vrt_accum_resolve_hdr's float image on its way to the host
         DevBuf<float> d_hmean;                   // vrt_accum_resolve_hdr_shown*: the float mean the display pass reads, made at the first such call
+        // vrt_accum_keep_moments as it stood at the begin of an HDR accumulation: the two float64 sums of the samples' luminance and its square
+        bool moments = false;
+        DevBuf<double> d_msum;                   // 2 doubles per pixel
+        size_t mom_pixels = 0;                   // what it was last sized for
+        DevBuf<float> d_mvar;                    // M3's plane: vrt_accum_variance's way to the host, the variance-guided resolve's input; made at the first such call
         // vrt_accum_guides (vrt_guides.cpp): the guide state, made at the first such call. `epoch` counts the starts of the sums (every
         // begin and every restart of vrt_accum_add); the state holds the guides of the first guide_total samples of epoch guide_epoch
         uint64_t epoch = 0, guide_epoch = 0;
@@ -299,6 +304,7 @@ struct vrt_ctx {
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
+    bool accum_keep_moments = false;             // vrt_accum_keep_moments: likewise, and only where that begin keeps HDR sums
     const uint32_t *dbg_group_order = nullptr;  // vrt_set_tile_order: caller-owned buffers instead of the scheduler's
     uint32_t *dbg_tile_cost = nullptr;
     bool dbg_sched = false;
@@ -366,6 +372,7 @@ struct ProfSlot {
 // (jitter: the jittered samples of VRT_ACCUM_JITTER, in `mode`; vrt_accum.hip.h JitterSource)
 // (aperture > 0: the samples of a thin lens, vrt_set_lens; vrt_accum.hip.h LensSource, vrt_lens.hip.h)
 // (adaptive: n rounds of the context's adaptive accumulation, vrt_accum_begin_adaptive; the kernels' adaptive forms)
+// (moments, with hdr: the accumulation keeps luminance moments, vrt_accum_keep_moments; the kernels' MOM forms)
 // (hdr: an HDR accumulation, vrt_accum_keep_hdr; the kernels' HDR forms. frame_only, with hdr, modes 0 / 1 from the corner: no
 // sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
 // (paths: what selects the kernels of VRT_MODE_FULL, as the add that queues the step read it)
@@ -394,6 +401,7 @@ struct AccumStep {
     bool adaptive = false, hdr = false, frame_only = false;
     PathSetup paths{};
     bool guides = false;
+    bool moments = false;
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
@@ -418,6 +426,10 @@ hipError_t launch_accum_step(vrt_ctx::Accum &ac, vrt::KArgs &a, vrt::ViewSet &vs
 bool accum_inputs_current(const vrt_ctx *c);
 // the call-order checks of everything that reads the accumulation, in the name of `what`: begun, holds samples, and with need_hdr keeps HDR sums
 int accum_state(vrt_ctx *c, const char *what, bool need_hdr);
+// M3's plane of an accumulation that keeps moments (the caller has checked), enqueued on s into d_variance
+int accum_variance_into(vrt_ctx *c, float *d_variance, hipStream_t s);
+// ... and room for it in the accumulation's own scratch (Accum::d_mvar, 4 bytes per pixel)
+int ensure_variance_plane(vrt_ctx *c);
 // A read of the accumulation on stream s, ordered against the context's: the samples were added on the context's stream, and later adds must not
 // overtake this read (nor, through `read`, the last call's use of the float mean). Nothing to do when s is the context's stream.
 template <class BODY>

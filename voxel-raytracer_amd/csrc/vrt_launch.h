@@ -111,8 +111,17 @@ hipError_t accum_repeat_hdr(const accum::RepeatHdrOf<accum::RepeatAdapt> &q, hip
 hipError_t accum_frame_hdr(int mode, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
 hipError_t accum_pass1_hdr(const KArgs &a, const ViewSet &vs, const accum::HdrFrame &q, int grid, hipStream_t s);
 hipError_t accum_resolve_hdr(const accum::HdrResolve &q, hipStream_t s);
-inline hipError_t accum_primary(bool hdr, int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
-                                const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+// vrt_launch_accum_mom.hip: the same for HDR accumulations that keep moments (include/vrt.h vrt_accum_keep_moments), `q` with the two
+// moment sums too. accum_repeat_mom: the HDR repeat with (double)y * k and (double)q * k of the frame's float colour.
+// accum_variance: M3, the sums -> the variance plane.
+hipError_t accum_primary_mom(int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::MomArgs &q,
+                             bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_repeat_mom(const accum::RepeatMomOf<accum::Repeat> &q, hipStream_t s);
+hipError_t accum_repeat_mom(const accum::RepeatMomOf<accum::RepeatAdapt> &q, hipStream_t s);
+hipError_t accum_variance(const accum::MomVariance &q, hipStream_t s);
+inline hipError_t accum_primary(bool hdr, bool moments, int mode, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
+                                const accum::MomArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+    if (hdr && moments) return accum_primary_mom(mode, src, v, a, vs, q, adaptive, l, grid, s);
     return hdr ? accum_primary_hdr(mode, src, v, a, vs, q, adaptive, l, grid, s) : accum_primary(mode, src, v, a, vs, q, adaptive, l, grid, s);
 }
 
@@ -123,21 +132,24 @@ inline hipError_t accum_primary(bool hdr, int mode, accum::Source src, const Var
 // workgroup) -- every family but the plain one takes any variant and launches v4 for the wide traversals, v1 for the record-array
 // ones (same workgroup shape, same bytes); adaptive, it traces the tiles adaptive_tiles listed before it. bounce: q.n samples of the
 // diffuse bounce over pass 1's seeds in a.defer_rec (grid = tiles). The emitter families have `full` only.
-template <bool HDR, PathFamily F>
+// MOM (with HDR): the forms that keep moments, vrt_launch_accum_mom{,_deep,_sun,_emit,_emitp,_emitm}.hip.
+template <bool HDR, PathFamily F, bool MOM = false>
 struct AccumPaths {
-    static hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const accum::Lens &l,
+    static hipError_t opaque(accum::Source src, const KArgs &a, const ViewSet &vs, const accum::MomArgs &q, bool adaptive, const accum::Lens &l,
                              const PathArgs &pa, int grid, hipStream_t s);
-    static hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive,
+    static hipError_t full(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const accum::MomArgs &q, bool adaptive,
                            const accum::Lens &l, const PathArgs &pa, int grid, hipStream_t s);
-    static hipError_t bounce(const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q, bool adaptive, const PathArgs &pa, int grid, hipStream_t s);
+    static hipError_t bounce(const KArgs &a, const ViewSet &vs, const accum::MomArgs &q, bool adaptive, const PathArgs &pa, int grid, hipStream_t s);
 };
 // ... and the one switch from the family as a value to those instantiations (vrt_scene.cpp, which sees none of the kernels): `q`
-// filled for either object, `hdr` picks it
-hipError_t accum_opaque(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const KArgs &a, const ViewSet &vs,
-                        const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_full(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
-                      const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
-hipError_t accum_bounce(bool hdr, PathFamily fam, const PathArgs &pa, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+// filled for every object, `form` picks it
+enum class AccumForm { kPlain, kHdr, kMoments };
+inline AccumForm accum_form(bool hdr, bool moments) { return hdr ? (moments ? AccumForm::kMoments : AccumForm::kHdr) : AccumForm::kPlain; }
+hipError_t accum_opaque(AccumForm form, PathFamily fam, const PathArgs &pa, accum::Source src, const KArgs &a, const ViewSet &vs,
+                        const accum::MomArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_full(AccumForm form, PathFamily fam, const PathArgs &pa, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
+                      const accum::MomArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s);
+hipError_t accum_bounce(AccumForm form, PathFamily fam, const PathArgs &pa, const KArgs &a, const ViewSet &vs, const accum::MomArgs &q,
                         bool adaptive, int grid, hipStream_t s);
 
 // vrt_launch_rays.hip: pathTrace of `mode` (0 or 1) for the q.n rays of a caller's batch (vrt_rays.hip.h), one lane per ray in the

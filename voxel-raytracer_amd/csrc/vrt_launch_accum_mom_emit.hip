@@ -1,0 +1,5 @@
+// vrt_launch_accum_mom_emit.hip -- the accumulation's VRT_MODE_FULL kernels over EmitPaths<...> (include/vrt.h vrt_set_emitter_sampling),
+// the forms that keep moments (vrt_accum_keep_moments), in an object of their own: vrt_launch_accum.hip.h
+#include "vrt_launch_accum.hip.h"
+
+template struct vrt::launch::AccumPaths<true, vrt::launch::PathFamily::kEmit, true>;

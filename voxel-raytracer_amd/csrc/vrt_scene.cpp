@@ -481,25 +481,33 @@ static hipError_t with_family(PathFamily fam, FN &&f) {
     return hipErrorInvalidValue;
 }
 
-hipError_t accum_opaque(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const KArgs &a, const ViewSet &vs,
-                        const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+// f(AccumPaths<HDR, F, MOM>'s tag) for the form: HDR and MOM as constants
+template <PathFamily F, class FN>
+static hipError_t with_form(AccumForm form, FN &&f) {
+    switch (form) {
+        case AccumForm::kPlain: return f(AccumPaths<false, F>{});
+        case AccumForm::kHdr: return f(AccumPaths<true, F>{});
+        case AccumForm::kMoments: return f(AccumPaths<true, F, true>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t accum_opaque(AccumForm form, PathFamily fam, const PathArgs &pa, accum::Source src, const KArgs &a, const ViewSet &vs,
+                        const accum::MomArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
     return with_family(fam, [&](auto f) {
-        return hdr ? AccumPaths<true, decltype(f)::value>::opaque(src, a, vs, q, adaptive, l, pa, grid, s)
-                   : AccumPaths<false, decltype(f)::value>::opaque(src, a, vs, q, adaptive, l, pa, grid, s);
+        return with_form<decltype(f)::value>(form, [&](auto p) { return decltype(p)::opaque(src, a, vs, q, adaptive, l, pa, grid, s); });
     });
 }
-hipError_t accum_full(bool hdr, PathFamily fam, const PathArgs &pa, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
-                      const accum::HdrArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
+hipError_t accum_full(AccumForm form, PathFamily fam, const PathArgs &pa, accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs,
+                      const accum::MomArgs &q, bool adaptive, const accum::Lens &l, int grid, hipStream_t s) {
     return with_family(fam, [&](auto f) {
-        return hdr ? AccumPaths<true, decltype(f)::value>::full(src, v, a, vs, q, adaptive, l, pa, grid, s)
-                   : AccumPaths<false, decltype(f)::value>::full(src, v, a, vs, q, adaptive, l, pa, grid, s);
+        return with_form<decltype(f)::value>(form, [&](auto p) { return decltype(p)::full(src, v, a, vs, q, adaptive, l, pa, grid, s); });
     });
 }
-hipError_t accum_bounce(bool hdr, PathFamily fam, const PathArgs &pa, const KArgs &a, const ViewSet &vs, const accum::HdrArgs &q,
+hipError_t accum_bounce(AccumForm form, PathFamily fam, const PathArgs &pa, const KArgs &a, const ViewSet &vs, const accum::MomArgs &q,
                         bool adaptive, int grid, hipStream_t s) {
     return with_family(fam, [&](auto f) {
-        return hdr ? AccumPaths<true, decltype(f)::value>::bounce(a, vs, q, adaptive, pa, grid, s)
-                   : AccumPaths<false, decltype(f)::value>::bounce(a, vs, q, adaptive, pa, grid, s);
+        return with_form<decltype(f)::value>(form, [&](auto p) { return decltype(p)::bounce(a, vs, q, adaptive, pa, grid, s); });
     });
 }
 
