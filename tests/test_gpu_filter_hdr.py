@@ -58,8 +58,11 @@ def _same_both(got, want, what):
 # ---- the stateless form on random planes -------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def planes70():
-    """70 x 37: two workgroups across with a ragged right edge, ten down with a ragged last one; NaN, Inf, negative values (depth
-    included), dead pixels singly, a dead block and a live pixel alone inside it"""
+    """70 x 37: the lattice levels' 32 x 8 tile gives three tiles across (the last 6 wide) and five down at step 1, 2 x 3 per residue
+    class at step 2 and 1 x 2 at step 4, every class with class 0's count; the gather levels' 64 x 4 workgroups two across with a
+    ragged right edge, ten down with a ragged last one. Frames that cross the lattice tiles' seams at steps 2 and 4:
+    tests/test_gpu_filter_seams.py. NaN, Inf, negative values (depth included), dead pixels singly, a dead block and a live pixel alone
+    inside it"""
     return random_case(np.random.default_rng(70), 37, 70, negative_depth=True)
 
 

@@ -7,6 +7,7 @@
 //     ray tables and of the dispatcher's "world is empty outside wide root 0" analysis: the same sources (vrt_layout.cpp,
 //     vrt_raygen.cpp) linked a second time.
 //   * the adaptive accumulation's stopping rule (vrt_accum.h adaptive_active), on the host and on the device.
+//   * the guided filter's launch geometry (vrt_filter.hip.h): the tile constants the coverage model of tests/filter_geometry.py needs.
 // libvrt_hip.so exports none of this (tests/test_abi.py checks that).
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include "../vrt_sched.hip.h"
 #include "../vrt_sun.h"
 #include "../vrt_emitters.h"
+#include "../vrt_filter.hip.h"
 
 namespace vrt {
 // the adaptive stopping rule on the device: out[i] = adaptive_active(n[i], s[i], q[i], min, max, tol)
@@ -169,6 +171,14 @@ using vrt_internal::view_matrix_in_range;
     } while (0)
 
 extern "C" {
+
+// host only: the guided filter's launch geometry as this build has it (vrt_filter.hip.h) -> out[7] = kBlockX, kBlockY, kVarX, kVarY,
+// kLatX, kLatY, kLatticeMaxStep
+void vrt_test_filter_geometry(int32_t *out) {
+    namespace f = vrt::filter;
+    const int32_t g[7] = {f::kBlockX, f::kBlockY, f::kVarX, f::kVarY, f::kLatX, f::kLatY, f::kLatticeMaxStep};
+    for (int i = 0; i < 7; ++i) out[i] = g[i];
+}
 
 // host only: the sun disc's block as the dispatcher makes it (vrt_sun.h sun_block()) -> out[11] = tan_radius, ll, Ln, T, B
 void vrt_test_sun_block(const float *light_dir, float tan_radius, float *out) {

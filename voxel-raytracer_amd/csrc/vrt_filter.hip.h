@@ -333,6 +333,7 @@ __global__ __launch_bounds__(kBlockX *kBlockY) void filter_level_kernel(const Q 
 // A word outside the image is staged as not live. The sums run in the same order over the same values: the same bits. A lane's
 // loads and stores lie s words apart, which is what the form pays: it wins up to step 4 and loses from step 8 on.
 constexpr int kLatX = 32, kLatY = 8, kWinX = kLatX + 4, kWinY = kLatY + 4;
+constexpr int kLatticeMaxStep = 4;   // the lattice form up to this step, the gather form above it (vrt_launch_filter.hip)
 
 template <class Q, bool FIRST, bool LAST>
 __global__ __launch_bounds__(kLatX *kLatY) void filter_level_lattice_kernel(const Q q) {

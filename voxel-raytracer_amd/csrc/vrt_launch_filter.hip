@@ -18,8 +18,8 @@ const dim3 kFrameBlock(filter::kBlockX, filter::kBlockY);
 // The lattice form up to this step, the gather form above it, for both argument types. Guide-only, per level at 1080p: the lattice
 // form takes 0.11 / 0.09 / 0.13 ms at steps 1 / 2 / 4 against 0.17-0.27 / 0.17 / 0.19 ms, and 0.22 / 0.24 / 0.23 ms at steps
 // 8 / 16 / 32 against 0.16 / 0.15 / 0.17 ms (profiles/filter_levels_ab.txt). The variance-guided levels cross over at the same step
-// (profiles/filter_var_levels_ab.txt).
-constexpr int kLatticeMaxStep = 4;
+// (profiles/filter_var_levels_ab.txt). The constant stands beside the tile's in vrt_filter.hip.h, where the test library reads it.
+using filter::kLatticeMaxStep;
 
 template <class Q>
 hipError_t level(const Q &q, bool first, bool last, hipStream_t s) {
