@@ -1019,8 +1019,7 @@ int vrt_accum_resolve_hdr_filtered_var_device(vrt_ctx *ctx, const vrt_filter_var
  * With moments off nothing changes: the same kernels, the same bytes, the same footprint. With moments on the accumulation takes 16
  * bytes per pixel more, allocated at the begin; every resolve, vrt_accum_counts and the guide calls return the bits they return
  * without -- the colour sums are the same bits -- and only vrt_accum_resolve_hdr_filtered_var{,_device} change, as said there.
- * Not provided: moments of ray batches (vrt_shade_rays_hdr_device's d_sums are the caller's), moments as an input of
- * vrt_accum_resolve_hdr_temporal, per-channel variance, a per-pixel mix of the spatial and the measured variance, frames, views,
+ * Not provided: moments of ray batches (vrt_shade_rays_hdr_device's d_sums are the caller's), per-channel variance, a per-pixel mix of the spatial and the measured variance, frames, views,
  * shards and vrt_multi. */
 int vrt_accum_keep_moments(vrt_ctx *ctx, int enable);
 int vrt_accum_variance(vrt_ctx *ctx, float *out_variance);
@@ -1092,8 +1091,9 @@ int vrt_accum_variance_device(vrt_ctx *ctx, void *d_variance, void *stream);
  * vrt_accum_resolve_hdr_temporal_device  the same with DEVICE histories and outputs, enqueued on `stream` (NULL: the context's),
  *                       ordered against the adds as vrt_accum_resolve_hdr_device is.
  * These calls read and write no byte of the accumulation's sums: every resolve and guide call returns the same bits with and without
- * them. None takes a profiling slot or counts towards the stride. Not provided: a 3 x 3 search where all four bilinear taps fail,
- * the filter's first level fed back into the history, an albedo or voxel-ID test, moving geometry (a voxel edit between frames is
+ * them. None takes a profiling slot or counts towards the stride. The measured variance of an accumulation that keeps moments as
+ * an input, and a 3 x 3 search where all four bilinear taps fail, are vrt_temporal_hdr_mom's, below. Not provided: the filter's
+ * first level fed back into the history, an albedo or voxel-ID test, moving geometry (a voxel edit between frames is
  * seen only through the depth and normal tests), lens-exact reprojection, frames, views, shards and vrt_multi. */
 typedef struct vrt_temporal {
     float prev_view_proj[16];   /* previous frame's FORWARD projection * view, column-major */
@@ -1118,6 +1118,78 @@ int vrt_accum_resolve_hdr_temporal(vrt_ctx *ctx, const vrt_temporal *t, const vr
 int vrt_accum_resolve_hdr_temporal_device(vrt_ctx *ctx, const vrt_temporal *t, const vrt_filter_var *f, const vrt_tonemap *tm,
                                           const void *d_history_in, void *d_history_out, void *d_integrated, void *d_rgb, void *d_rgba8,
                                           void *d_variance_out, void *stream);
+/* EXTENSION: the temporal pass with MEASURED frame variances and a 3 x 3 search -- vrt_temporal_hdr above hands a pixel without a
+ * history 65504^2, which the variance-guided filter then carries to its neighbours level by level; and a pixel loses its history
+ * whenever all four bilinear taps fail. These calls take this frame's measured variance of the mean (vrt_accum_variance_device's
+ * plane, M3) as one more input, integrate it as the colour is integrated, and hand it out while the history is short; and they can
+ * look for a history in the 3 x 3 neighbourhood of the reprojected position where the bilinear taps found none (SVGF's fallback).
+ * New entry points beside the old ones: every existing call keeps its bits.
+ *
+ * All arithmetic is float32, every operation rounded on its own, nothing contracted; h, g, hv as in vrt_temporal_hdr. The history
+ * has vrt_temporal_hdr's layout except plane 2, which is {nx, ny, nz, V}: V the variance of the integrated mean's luminance by T7.
+ * Inputs, liveness, the pixel that is not live (it stores +0 in V's place too) and T1, T2, T4, T5 are vrt_temporal_hdr's, unchanged.
+ * T3 is unchanged, and V is one more previous quantity: Vq = hv(plane 2's fourth float of tap q), weighted as every other.
+ *  T3s. The search. Only where search == 1, a history is given, T2 produced a position (clip.w > 1e-6f and fx, fy inside T2's
+ *      window), and T3 ended with sw == 0. xc = (int)floorf(fx + 0.5f), yc = (int)floorf(fy + 0.5f). The nine taps (xc + dx, yc + dy),
+ *      dy outer from -1 to 1, dx inner from -1 to 1. A tap COUNTS by T3's own tests, unchanged: inside the image, stored coverage > 0,
+ *      N >= 1, the normal test, the depth test against the same Zexp and tolerance. Every counted tap has weight 1.0f; sw is their
+ *      sum, from 0 in that order; there is a history iff sw > 0, and every previous quantity X -- the colour, N, m1, m2, V -- is
+ *      (the sum of Xq, from 0 in that order) / sw. With search == 0 the step does not exist.
+ *  T7. The variance of the integrated mean, from measured frame variances. v = hv(variance_in[p]), or 65504.0f * 65504.0f where
+ *      d_variance_in is NULL. Vp is the previous quantity V (+0 without a history). om = 1.0f - a with T4's a;
+ *      V' = hv((om * om) * Vp + (a * a) * v). The integrated colour is a weighted sum of independent frame means, so this is its
+ *      variance with whatever weights T4 chose, exponential ones included; T6's estimate is exact only while a = 1 / N'. Without a
+ *      history a = 1 and V' = v exactly.
+ *  T6m. Outputs. The history is T6's with plane 2 = {n_p, V'}. out_rgb is T6's. out_variance = N' < (float)measured_below ? V' :
+ *      T6's value (which is 65504.0f * 65504.0f at N' < 2).
+ * A history written by vrt_temporal_hdr carries +0 in V's place: handed to these calls it reads as "exactly known" and is
+ * under-trusted only until the (1 - a)^2 decay has worn that off; vrt_temporal_hdr ignores the slot, so a history of these calls can
+ * go back to it. measured_below = 1, search = 0 is vrt_temporal_hdr on every output, and on the history except that one float. A
+ * frame of one sample has v = "unknown" (M3 at n < 2) and behaves as today at a disocclusion.
+ *
+ * vrt_temporal_mom_default  vrt_temporal_default's fields, then measured_below and search: the best row of the quality sweep in
+ *                       profiles/temporal_mom_quality.txt at vrt_temporal_default's tap tests (DESIGN.md section 3 "Temporal
+ *                       pass with measured variances").
+ * vrt_temporal_hdr_mom  DEVICE pointers, stream-ordered, stateless, no profiling slot: every rule of vrt_temporal_hdr. d_variance_in
+ *                       [H][W] may be NULL; it counts among the inputs for the aliasing rules. VRT_E_INVALID also for
+ *                       measured_below outside 1..32769 (32769: always the measured variance, max_history being at most 32768)
+ *                       and search other than 0 or 1.
+ * vrt_temporal_hdr_mom_host  the same through HOST buffers, synchronous, staged through 148 bytes per pixel the context keeps.
+ * vrt_accum_resolve_hdr_temporal_mom, _device  the chain of vrt_accum_resolve_hdr_temporal{,_device} with this pass: the same
+ *                       input, camera, offsets, filter, outputs, staging and VRT_E_STATE rule. d_variance_in is the accumulation's
+ *                       own M3 plane where it was begun with moments (vrt_accum_keep_moments) -- exactly what
+ *                       vrt_accum_variance_device returns, through the accumulation's own four bytes per pixel -- and NULL where
+ *                       it was not.
+ * These calls read and write no byte of the accumulation's sums: every resolve, vrt_accum_counts, vrt_accum_variance and the guide
+ * calls return the same bits with and without them. None takes a profiling slot or counts towards the stride. Not provided (out of
+ * scope here): the filter's first level fed back into the history, an albedo or voxel-ID test, moving geometry, lens-exact
+ * reprojection, per-channel variance, frames, views, shards and vrt_multi; vrt_temporal_default is what it was. */
+typedef struct vrt_temporal_mom {
+    float prev_view_proj[16];   /* vrt_temporal's fields in their order ... */
+    float prev_camera_pos[4];
+    float offset_x, offset_y;
+    int32_t max_history;
+    float alpha_min, alpha_moments_min;
+    float normal_min;
+    float depth_tol;
+    int32_t measured_below;     /* ... then: out_variance is T7's V' while N' < measured_below; 1 .. 32769 */
+    int32_t search;             /* T3s: 0 or 1 */
+} vrt_temporal_mom;
+void vrt_temporal_mom_default(vrt_temporal_mom *t);
+int vrt_temporal_hdr_mom(vrt_ctx *ctx, int width, int height, const float inv_projection[16], const float inv_view[16],
+                         const float camera_pos[4], const void *d_rgb, const void *d_normal, const void *d_depth, const void *d_coverage,
+                         const void *d_variance_in, const void *d_history_in, const vrt_temporal_mom *t, void *d_history_out,
+                         void *d_out_rgb, void *d_out_variance, void *stream);
+int vrt_temporal_hdr_mom_host(vrt_ctx *ctx, int width, int height, const float inv_projection[16], const float inv_view[16],
+                              const float camera_pos[4], const float *rgb, const float *normal, const float *depth, const float *coverage,
+                              const float *variance_in, const void *history_in, const vrt_temporal_mom *t, void *history_out,
+                              float *out_rgb, float *out_variance);
+int vrt_accum_resolve_hdr_temporal_mom(vrt_ctx *ctx, const vrt_temporal_mom *t, const vrt_filter_var *f, const vrt_tonemap *tm,
+                                       const void *history_in, void *history_out, float *out_integrated, float *out_rgb,
+                                       uint8_t *out_rgba8, float *out_variance);
+int vrt_accum_resolve_hdr_temporal_mom_device(vrt_ctx *ctx, const vrt_temporal_mom *t, const vrt_filter_var *f, const vrt_tonemap *tm,
+                                              const void *d_history_in, void *d_history_out, void *d_integrated, void *d_rgb,
+                                              void *d_rgba8, void *d_variance_out, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

@@ -55,7 +55,13 @@ class Temporal(C.Structure):
                 ("depth_tol", C.c_float)]
 
 
+class TemporalMom(C.Structure):
+    """include/vrt.h vrt_temporal_mom"""
+    _fields_ = Temporal._fields_ + [("measured_below", C.c_int32), ("search", C.c_int32)]
+
+
 TEMPORAL_KEYS = ("offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min", "depth_tol")
+TEMPORAL_MOM_KEYS = TEMPORAL_KEYS + ("measured_below", "search")
 HISTORY_BYTES = 48       # include/vrt.h vrt_temporal_hdr: a history's bytes per pixel, three planes of 16-byte words
 
 FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
@@ -91,6 +97,14 @@ def default_temporal():
     t = Temporal()
     hip_lib().vrt_temporal_default(C.byref(t))
     return {k: (int if k == "max_history" else float)(getattr(t, k)) for k in TEMPORAL_KEYS}
+
+
+def default_temporal_mom():
+    """vrt_temporal_mom_default as a dict: default_temporal()'s keys, "measured_below" and "search" -- the keys the `temporal`
+    argument of Context.temporal_hdr_mom and Context.accum_resolve_hdr_temporal_mom takes. Needs no device."""
+    t = TemporalMom()
+    hip_lib().vrt_temporal_mom_default(C.byref(t))
+    return {k: (float if k in TEMPORAL_KEYS and k != "max_history" else int)(getattr(t, k)) for k in TEMPORAL_MOM_KEYS}
 
 
 def build(targets=("../libvrt_hip.so", "../libvrt_hip_test.so", "../libvrt_host.so")):
@@ -391,6 +405,12 @@ def hip_lib():
         L.vrt_temporal_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(Temporal)] + [C.c_void_p] * 3
         L.vrt_accum_resolve_hdr_temporal.argtypes = [C.c_void_p, C.POINTER(Temporal), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 6
         L.vrt_accum_resolve_hdr_temporal_device.argtypes = [C.c_void_p, C.POINTER(Temporal), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 7
+        L.vrt_temporal_mom_default.argtypes = [C.POINTER(TemporalMom)]
+        L.vrt_temporal_mom_default.restype = None
+        L.vrt_temporal_hdr_mom.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(TemporalMom)] + [C.c_void_p] * 4
+        L.vrt_temporal_hdr_mom_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(TemporalMom)] + [C.c_void_p] * 3
+        L.vrt_accum_resolve_hdr_temporal_mom.argtypes = [C.c_void_p, C.POINTER(TemporalMom), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 6
+        L.vrt_accum_resolve_hdr_temporal_mom_device.argtypes = [C.c_void_p, C.POINTER(TemporalMom), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 7
         _hip = L
     return _hip
 
@@ -1596,6 +1616,94 @@ class Context:
         t = self._temporal(temporal, prev_camera if d_history_in is not None else None)
         self._chk(self._L.vrt_accum_resolve_hdr_temporal_device(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
                                                                 d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, stream))
+
+    @staticmethod
+    def _temporal_mom(temporal, prev_camera):
+        """_temporal() for the calls that take a vrt_temporal_mom: a dict with any of default_temporal_mom()'s keys -> TemporalMom"""
+        t = TemporalMom()
+        hip_lib().vrt_temporal_mom_default(C.byref(t))
+        for k, v in (temporal or {}).items():
+            if k not in TEMPORAL_MOM_KEYS:
+                raise ValueError(f"unknown temporal key {k!r}; expected any of {TEMPORAL_MOM_KEYS}")
+            setattr(t, k, int(v) if k in ("max_history", "measured_below", "search") else float(v))
+        if prev_camera is not None:
+            b = Context._temporal(None, prev_camera)
+            t.prev_view_proj[:] = list(b.prev_view_proj)
+            t.prev_camera_pos[:] = list(b.prev_camera_pos)
+        return t
+
+    def temporal_hdr_mom(self, camera, rgb, guides, variance=None, history=None, prev_camera=None, temporal=None):
+        """The temporal pass with measured variances and a 3 x 3 search through host arrays (vrt_temporal_hdr_mom_host):
+        temporal_hdr's arguments, `variance` float32[H,W] -- this frame's measured variance of the mean, what accum_variance returns;
+        None: unknown -- and temporal a dict with any of default_temporal_mom()'s keys -> (history float32[3,H,W,4], rgb
+        float32[H,W,3], variance float32[H,W]): temporal_hdr's, the history with the integrated variance in plane 2's fourth float."""
+        ip, iv, cp = self._camera_block(camera)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        n, z, cov = (np.ascontiguousarray(guides[k], np.float32) for k in ("normal", "depth", "coverage"))
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+        h, w = rgb.shape[:2]
+        if n.shape != (h, w, 3) or z.shape != (h, w) or cov.shape != (h, w):
+            raise ValueError(f"expected guides [H,W,3], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {z.shape}, {cov.shape}")
+        if variance is not None:
+            variance = np.ascontiguousarray(variance, np.float32)
+            if variance.shape != (h, w):
+                raise ValueError(f"expected variance[H,W] for H, W = {h}, {w}; got {variance.shape}")
+        if history is not None:
+            history = np.ascontiguousarray(history, np.float32)
+            if history.shape != (3, h, w, 4):
+                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
+            if prev_camera is None:
+                raise ValueError("a history needs prev_camera")
+        t = self._temporal_mom(temporal, prev_camera if history is not None else None)
+        out_h, out, outv = np.zeros((3, h, w, 4), np.float32), np.zeros_like(rgb), np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_temporal_hdr_mom_host(self._h, w, h, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, rgb.ctypes.data,
+                                                    n.ctypes.data, z.ctypes.data, cov.ctypes.data,
+                                                    variance.ctypes.data if variance is not None else None,
+                                                    history.ctypes.data if history is not None else None, C.byref(t), out_h.ctypes.data,
+                                                    out.ctypes.data, outv.ctypes.data))
+        return out_h, out, outv
+
+    def temporal_hdr_mom_device(self, width, height, camera, d_rgb, d_normal, d_depth, d_coverage, d_variance_in, d_history_in,
+                                d_history_out, d_out_rgb, d_out_variance, prev_camera=None, temporal=None, stream=None):
+        """vrt_temporal_hdr_mom: temporal_hdr_device's DEVICE buffers and d_variance_in (W*H floats, may be None), enqueued on
+        `stream`"""
+        ip, iv, cp = self._camera_block(camera)
+        t = self._temporal_mom(temporal, prev_camera if d_history_in is not None else None)
+        self._chk(self._L.vrt_temporal_hdr_mom(self._h, width, height, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, d_rgb, d_normal,
+                                               d_depth, d_coverage, d_variance_in, d_history_in, C.byref(t), d_history_out, d_out_rgb,
+                                               d_out_variance, stream))
+
+    def accum_resolve_hdr_temporal_mom(self, history=None, prev_camera=None, temporal=None, filter=None, tonemap="clamp", exposure=1.0):
+        """accum_resolve_hdr_temporal with the measured-variance pass (vrt_accum_resolve_hdr_temporal_mom): the variance input is the
+        accumulation's own measured variance where it keeps moments (accum_keep_moments), unknown where it does not; temporal a dict
+        with any of default_temporal_mom()'s keys -> the same five arrays."""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
+        if history is not None:
+            history = np.ascontiguousarray(history, np.float32)
+            if history.shape != (3, h, w, 4):
+                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
+            if prev_camera is None:
+                raise ValueError("a history needs prev_camera")
+        t = self._temporal_mom(temporal, prev_camera if history is not None else None)
+        out_h, integ = np.zeros((3, h, w, 4), np.float32), np.zeros((h, w, 3), np.float32)
+        rgb, rgba, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 4), np.uint8), np.zeros((h, w), np.float32)
+        self._chk(self._L.vrt_accum_resolve_hdr_temporal_mom(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
+                                                             history.ctypes.data if history is not None else None, out_h.ctypes.data,
+                                                             integ.ctypes.data, rgb.ctypes.data, rgba.ctypes.data, var.ctypes.data))
+        return out_h, integ, rgb, rgba, var
+
+    def accum_resolve_hdr_temporal_mom_device(self, d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, prev_camera=None,
+                                              temporal=None, filter=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_temporal_mom_device: accum_resolve_hdr_temporal_device's DEVICE buffers, enqueued on `stream`"""
+        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        f = self._filter_var(filter)
+        t = self._temporal_mom(temporal, prev_camera if d_history_in is not None else None)
+        self._chk(self._L.vrt_accum_resolve_hdr_temporal_mom_device(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
+                                                                    d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance,
+                                                                    stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -193,6 +193,8 @@ hipError_t filter_through(const filter::Through &q, hipStream_t s);
 // vrt_launch_temporal.hip: the temporal pass (vrt_temporal.hip.h), a whole frame, one lane per pixel, one 8 x 8 tile per wave:
 // T1-T6 of include/vrt.h vrt_temporal_hdr from q's planes and (where given) its previous history into the new one.
 hipError_t temporal_pass(const temporal::Args &q, hipStream_t s);
+// ... and the kernel's second form: T3s, T7 and T6m of vrt_temporal_hdr_mom
+hipError_t temporal_pass_mom(const temporal::ArgsMom &q, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt

@@ -9,13 +9,21 @@
 namespace vrt {
 namespace launch {
 
-hipError_t temporal_pass(const temporal::Args &q, hipStream_t s) {
+namespace {
+
+template <class A>
+hipError_t launch(const A &q, hipStream_t s) {
     const unsigned tiles_x = (unsigned)((q.width + temporal::kTile - 1) / temporal::kTile);
     const unsigned tiles_y = (unsigned)((q.height + temporal::kTile - 1) / temporal::kTile);
     const dim3 grid((tiles_x + temporal::kWaves - 1) / temporal::kWaves, tiles_y), block(64, temporal::kWaves);
-    hipLaunchKernelGGL(temporal::temporal_kernel, grid, block, 0, s, q);
+    hipLaunchKernelGGL(temporal::temporal_kernel<A>, grid, block, 0, s, q);
     return hipGetLastError();
 }
+
+}  // namespace
+
+hipError_t temporal_pass(const temporal::Args &q, hipStream_t s) { return launch(q, s); }
+hipError_t temporal_pass_mom(const temporal::ArgsMom &q, hipStream_t s) { return launch(q, s); }
 
 }  // namespace launch
 }  // namespace vrt

@@ -12,7 +12,7 @@ namespace temporal {
 // taps and stores move whole words.
 //   plane 0  r, g, b, N
 //   plane 1  m1, m2, Z, coverage
-//   plane 2  nx, ny, nz, +0
+//   plane 2  nx, ny, nz, +0 (vrt_temporal_hdr) or V, the measured variance of the integrated mean (vrt_temporal_hdr_mom, T7)
 constexpr size_t kHistoryBytes = 48;
 
 struct Args {
@@ -30,6 +30,13 @@ struct Args {
     float offset_x, offset_y;
     float max_history;          // (float)vrt_temporal::max_history, exact up to 32768
     float alpha_min, alpha_moments_min, normal_min, depth_tol;
+};
+
+// vrt_temporal_hdr_mom's: the same, then T7's input and T6m's and T3s's switches
+struct ArgsMom : Args {
+    const float *variance_in;   // this frame's measured variance, 1 float per pixel; null: unknown, 65504^2 everywhere
+    float measured_below;       // (float)vrt_temporal_mom::measured_below, exact up to 32769
+    int search;                 // 0 or 1
 };
 
 }  // namespace temporal

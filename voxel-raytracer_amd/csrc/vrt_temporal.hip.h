@@ -7,7 +7,14 @@
 // load; a tap's guide words (planes 1 and 2) come first and its colour word (plane 0) only where the tap counts, so a wave whose
 // taps all fail never loads a colour. No LDS, no barrier, no scratch (profiles/temporal_resource_usage.txt).
 // Every expression is the header's, operation by operation; tests/oracle_temporal.c restates them.
+// The kernel has two compile-time forms, chosen by its argument type. Args is vrt_temporal_hdr's. ArgsMom is vrt_temporal_hdr_mom's
+// (T3s, T7, T6m; tests/oracle_temporal_mom.c): the measured variance V rides in plane 2's fourth float, which every tap's guide load
+// brings anyway, and the 3 x 3 search is one rolled loop behind the sw == 0 branch that keeps running sums and no per-tap values.
+// Everything the second form adds is behind `if constexpr`: the first compiles to the instructions it had
+// (profiles/temporal_mom_codegen.txt).
 #pragma once
+#include <type_traits>
+
 #include "vrt_hdr.hip.h"
 #include "vrt_temporal.h"
 
@@ -47,7 +54,9 @@ VRT_DEV float previous(const bool ok[4], const float w[4], float x0, float x1, f
     return s / sw;
 }
 
-__global__ __launch_bounds__(64 * kWaves) void temporal_kernel(const Args q) {
+template <class A>
+__global__ __launch_bounds__(64 * kWaves) void temporal_kernel(const A q) {
+    constexpr bool kMom = std::is_same<A, ArgsMom>::value;
     const int x = (int)(blockIdx.x * kWaves + threadIdx.y) * kTile + (int)(threadIdx.x & 7u);
     const int y = (int)blockIdx.y * kTile + (int)(threadIdx.x >> 3);
     if (x >= q.width || y >= q.height) return;
@@ -69,6 +78,9 @@ __global__ __launch_bounds__(64 * kWaves) void temporal_kernel(const Args q) {
     float w[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m1q[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m2q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     size_t t[4] = {0, 0, 0, 0};
     float sw = 0.0f;
+    [[maybe_unused]] float vq[4] = {0.0f, 0.0f, 0.0f, 0.0f};                       // T7's V of the taps
+    [[maybe_unused]] float s_fx = 0.0f, s_fy = 0.0f, s_zexp = 0.0f, s_ztol = 0.0f;   // T2's position, for T3s
+    [[maybe_unused]] bool placed = false;
     if (q.history_in) {   // the same in every lane
         // T1
         const F3 d = ray_dir(q, (float)x + q.offset_x, (float)y + q.offset_y);
@@ -89,18 +101,23 @@ __global__ __launch_bounds__(64 * kWaves) void temporal_kernel(const Args q) {
                 w[1] = tx * (1.0f - ty);
                 w[2] = (1.0f - tx) * ty;
                 w[3] = tx * ty;
+                if constexpr (kMom) { s_fx = fx; s_fy = fy; s_zexp = zexp; s_ztol = ztol; placed = true; }
                 // T3: the guide words of every tap, then the verdicts
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
                     if (qx < 0 || qx >= q.width || qy < 0 || qy >= q.height) continue;
                     t[k] = (size_t)qy * (size_t)q.width + (size_t)qx;
-                    const float4 g1 = q.history_in[px + t[k]], g2 = q.history_in[2 * px + t[k]];
+                    float4 g1 = q.history_in[px + t[k]], g2 = q.history_in[2 * px + t[k]];
+                    // keeps plane 2's word one 16-byte load: V is used blocks later, and the compiler otherwise gathers it again as a
+                    // load of its own, four more gathers a pixel
+                    if constexpr (kMom) asm volatile("" : "+v"(g2.x), "+v"(g2.y), "+v"(g2.z), "+v"(g2.w));
                     m1q[k] = accum::hdr_value(g1.x);
                     m2q[k] = var_value(g1.y);
                     const float zq = guide_value(g1.z);
                     const float nd = (guide_value(g2.x) * n_p.x + guide_value(g2.y) * n_p.y) + guide_value(g2.z) * n_p.z;
                     ok[k] = guide_value(g1.w) > 0.0f && nd >= q.normal_min && __builtin_fabsf(zq - zexp) <= ztol;
+                    if constexpr (kMom) vq[k] = var_value(g2.w);
                 }
             }
         }
@@ -127,6 +144,43 @@ __global__ __launch_bounds__(64 * kWaves) void temporal_kernel(const Args q) {
         m1p = previous(ok, w, m1q[0], m1q[1], m1q[2], m1q[3], sw);
         m2p = previous(ok, w, m2q[0], m2q[1], m2q[2], m2q[3], sw);
     }
+    [[maybe_unused]] float vp = 0.0f;
+    if constexpr (kMom) {
+        if (sw > 0.0f) {
+            vp = previous(ok, w, vq[0], vq[1], vq[2], vq[3], sw);
+        } else if (placed && q.search != 0 && sw == 0.0f) {
+            // T3s: rare and divergent, so one rolled loop over the nine taps with running sums -- guide words, then the colour word
+            const int xc = (int)__builtin_floorf(s_fx + 0.5f), yc = (int)__builtin_floorf(s_fy + 0.5f);
+            float sc0 = 0.0f, sc1 = 0.0f, sc2 = 0.0f, sn = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f, ssw = 0.0f;
+#pragma unroll 1
+            for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll 1
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int qx = xc + dx, qy = yc + dy;
+                    if (qx < 0 || qx >= q.width || qy < 0 || qy >= q.height) continue;
+                    const size_t tq = (size_t)qy * (size_t)q.width + (size_t)qx;
+                    const float4 g1 = q.history_in[px + tq], g2 = q.history_in[2 * px + tq];
+                    const float nd = (guide_value(g2.x) * n_p.x + guide_value(g2.y) * n_p.y) + guide_value(g2.z) * n_p.z;
+                    if (!(guide_value(g1.w) > 0.0f && nd >= q.normal_min && __builtin_fabsf(guide_value(g1.z) - s_zexp) <= s_ztol)) continue;
+                    const float4 h0 = q.history_in[tq];
+                    const float nq = fmin_c(fmax_c(0.0f, guide_value(h0.w)), q.max_history);
+                    if (!(nq >= 1.0f)) continue;
+                    ssw = ssw + 1.0f;
+                    sc0 = sc0 + accum::hdr_value(h0.x);
+                    sc1 = sc1 + accum::hdr_value(h0.y);
+                    sc2 = sc2 + accum::hdr_value(h0.z);
+                    sn = sn + nq;
+                    s1 = s1 + accum::hdr_value(g1.x);
+                    s2 = s2 + var_value(g1.y);
+                    sv = sv + var_value(g2.w);
+                }
+            }
+            if (ssw > 0.0f) {
+                cp[0] = sc0 / ssw; cp[1] = sc1 / ssw; cp[2] = sc2 / ssw;
+                n_prev = sn / ssw; m1p = s1 / ssw; m2p = s2 / ssw; vp = sv / ssw;
+            }
+        }
+    }
     // T4
     const float n_new = fmin_c(n_prev + 1.0f, q.max_history);
     const float a = fmax_c(1.0f / n_new, q.alpha_min), am = fmax_c(1.0f / n_new, q.alpha_moments_min);
@@ -134,12 +188,23 @@ __global__ __launch_bounds__(64 * kWaves) void temporal_kernel(const Args q) {
     const float r[3] = {cp[0] + a * (c[0] - cp[0]), cp[1] + a * (c[1] - cp[1]), cp[2] + a * (c[2] - cp[2])};
     const float yl = luminance(c[0], c[1], c[2]);
     const float m1 = m1p + am * (yl - m1p), m2 = m2p + am * (yl * yl - m2p);
-    // T6
+    // T7
+    [[maybe_unused]] float v_new = 0.0f;
+    if constexpr (kMom) {
+        const float v = q.variance_in ? var_value(q.variance_in[p]) : kVarMax;
+        const float om = 1.0f - a;
+        v_new = var_value((om * om) * vp + (a * a) * v);
+    }
+    // T6, T6m
     q.history_out[p] = make_float4(r[0], r[1], r[2], n_new);
     q.history_out[px + p] = make_float4(m1, m2, z_p, cov);
-    q.history_out[2 * px + p] = make_float4(n_p.x, n_p.y, n_p.z, 0.0f);
+    q.history_out[2 * px + p] = make_float4(n_p.x, n_p.y, n_p.z, v_new);
     if (q.out_rgb) { q.out_rgb[p * 3 + 0] = r[0]; q.out_rgb[p * 3 + 1] = r[1]; q.out_rgb[p * 3 + 2] = r[2]; }
-    if (q.out_variance) q.out_variance[p] = n_new >= 2.0f ? var_value(fmax_c(0.0f, m2 - m1 * m1) / (n_new - 1.0f)) : kVarMax;
+    if (q.out_variance) {
+        const float spread = n_new >= 2.0f ? var_value(fmax_c(0.0f, m2 - m1 * m1) / (n_new - 1.0f)) : kVarMax;
+        if constexpr (kMom) q.out_variance[p] = n_new < q.measured_below ? v_new : spread;
+        else q.out_variance[p] = spread;
+    }
 }
 
 }  // namespace temporal
