@@ -538,10 +538,6 @@ def test_error_states(V):
         L = ctx._L
         box = (C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1024, 1024, 1024)
         out = (V.RayHit * 4)()
-        L.vrt_cast_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.vrt_cast_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
         # before any upload
         assert L.vrt_cast_rays(ctx._h, 4, o.ctypes.data, 0, d.ctypes.data, box[0], box[1], out) == -5
         assert L.vrt_find_voxels(ctx._h, 1, np.zeros(3, np.int32).ctypes.data, np.zeros(3, np.uint32).ctypes.data) == -5

@@ -527,8 +527,6 @@ def test_box_records_expand_exactly_the_nodes_that_meet_the_box(V):
         if n == 1:
             H = V.host_lib()
             import ctypes as C
-            H.vrth_world_path_records.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int,
-                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
             p, cnt = C.c_void_p(), C.c_size_t(0)
             assert H.vrth_world_path_records(w._h, (C.c_uint8 * 16)(), 0, lo[0], lo[1], lo[2], C.byref(p), C.byref(cnt)) == 0
             one = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(cnt.value, 2)).copy()

@@ -1,7 +1,6 @@
 """Does the order in which a launch's tiles start matter?  Records the ticks each 8x8 tile took (ORDERED flavour of
 the default kernel), then times the same frame with the tiles started heaviest-first (LPT), lightest-first, and in
 the natural order, next to the plain kernel. Pixels are compared with the plain kernel's."""
-import ctypes as C
 import importlib
 import os
 import sys
@@ -34,7 +33,6 @@ def main():
     buf = plan.local_buffer(dev)
     p = plan.pointers(buf)
     L = ctx._L
-    L.vrt_set_tile_order.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     n_tiles = (W // 8) * (H // 8)
     n_wg = n_tiles // 4
 

@@ -62,6 +62,10 @@ class TemporalMom(C.Structure):
 
 TEMPORAL_KEYS = ("offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min", "depth_tol")
 TEMPORAL_MOM_KEYS = TEMPORAL_KEYS + ("measured_below", "search")
+_TEMPORAL_INTS = ("max_history", "measured_below", "search")   # the keys that are int32 fields; the others are floats
+# the two temporal structs as (mirror, the library's default function, the keys a caller may set)
+_TEMPORAL = (Temporal, "vrt_temporal_default", TEMPORAL_KEYS)
+_TEMPORAL_MOM = (TemporalMom, "vrt_temporal_mom_default", TEMPORAL_MOM_KEYS)
 HISTORY_BYTES = 48       # include/vrt.h vrt_temporal_hdr: a history's bytes per pixel, three planes of 16-byte words
 
 FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
@@ -72,39 +76,62 @@ class VrtError(RuntimeError):
     pass
 
 
+def _filter_defaults(struct, default):
+    f = struct()
+    getattr(hip_lib(), default)(C.byref(f))
+    d = {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE)}
+    d.update((k, float(getattr(f, k))) for k, _ in struct._fields_[2:])   # the sigmas
+    return d
+
+
 def default_filter():
     """vrt_filter_default as a dict: {"levels", "demodulate", "sigma_normal", "sigma_albedo", "sigma_depth"} -- the keyword
     arguments Context.filter_hdr and Context.accum_resolve_hdr_filtered take. Needs no device."""
-    f = Filter()
-    hip_lib().vrt_filter_default(C.byref(f))
-    return {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE), "sigma_normal": float(f.sigma_normal),
-            "sigma_albedo": float(f.sigma_albedo), "sigma_depth": float(f.sigma_depth)}
+    return _filter_defaults(Filter, "vrt_filter_default")
 
 
 def default_filter_var():
     """vrt_filter_var_default as a dict: default_filter()'s keys and "sigma_lum" -- the keyword arguments Context.filter_hdr_var and
     Context.accum_resolve_hdr_filtered_var take. Needs no device."""
-    f = FilterVar()
-    hip_lib().vrt_filter_var_default(C.byref(f))
-    return {"levels": int(f.levels), "demodulate": bool(f.flags & FILTER_DEMODULATE), "sigma_normal": float(f.sigma_normal),
-            "sigma_albedo": float(f.sigma_albedo), "sigma_depth": float(f.sigma_depth), "sigma_lum": float(f.sigma_lum)}
+    return _filter_defaults(FilterVar, "vrt_filter_var_default")
+
+
+def _temporal_struct(kind, temporal=None, prev_camera=None):
+    """kind: _TEMPORAL or _TEMPORAL_MOM. The library's defaults, then the caller's keys (ValueError for one the struct does not
+    have), then the previous frame's camera where a history comes in -> the struct"""
+    struct, default, keys = kind
+    t = struct()
+    getattr(hip_lib(), default)(C.byref(t))
+    for k, v in (temporal or {}).items():
+        if k not in keys:
+            raise ValueError(f"unknown temporal key {k!r}; expected any of {keys}")
+        setattr(t, k, int(v) if k in _TEMPORAL_INTS else float(v))
+    if prev_camera is not None:
+        vp = np.ascontiguousarray(prev_camera[0], np.float32).reshape(-1)
+        cp = np.ascontiguousarray(prev_camera[1], np.float32).reshape(-1)
+        if vp.size != 16 or cp.size not in (3, 4):
+            raise ValueError("expected prev_camera = (prev_view_proj[16], prev_camera_pos[3 or 4])")
+        t.prev_view_proj[:] = [float(v) for v in vp]
+        t.prev_camera_pos[:cp.size] = [float(v) for v in cp]
+    return t
+
+
+def _temporal_defaults(kind):
+    t = _temporal_struct(kind)
+    return {k: (int if k in _TEMPORAL_INTS else float)(getattr(t, k)) for k in kind[2]}
 
 
 def default_temporal():
     """vrt_temporal_default as a dict: {"offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min",
     "depth_tol"} -- the keys the `temporal` argument of Context.temporal_hdr and Context.accum_resolve_hdr_temporal takes. The
     previous camera is an argument of its own there. Needs no device."""
-    t = Temporal()
-    hip_lib().vrt_temporal_default(C.byref(t))
-    return {k: (int if k == "max_history" else float)(getattr(t, k)) for k in TEMPORAL_KEYS}
+    return _temporal_defaults(_TEMPORAL)
 
 
 def default_temporal_mom():
     """vrt_temporal_mom_default as a dict: default_temporal()'s keys, "measured_below" and "search" -- the keys the `temporal`
     argument of Context.temporal_hdr_mom and Context.accum_resolve_hdr_temporal_mom takes. Needs no device."""
-    t = TemporalMom()
-    hip_lib().vrt_temporal_mom_default(C.byref(t))
-    return {k: (float if k in TEMPORAL_KEYS and k != "max_history" else int)(getattr(t, k)) for k in TEMPORAL_MOM_KEYS}
+    return _temporal_defaults(_TEMPORAL_MOM)
 
 
 def build(targets=("../libvrt_hip.so", "../libvrt_hip_test.so", "../libvrt_host.so")):
@@ -153,6 +180,38 @@ def _real_array(a, what):
     return a
 
 
+# ---- The argument checks. Each takes the variable parts of its message: callers and tests read the texts.
+def _check_int(name, v, want, lo=None, hi=None):
+    """v: an int or np.integer, not a bool, in [lo, hi] (None: unbounded) -> int(v); ValueError "{name}: expected {want}, got ..."
+    otherwise"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or (lo is not None and v < lo) or (hi is not None and v > hi):
+        raise ValueError(f"{name}: expected {want}, got {v!r}")
+    return int(v)
+
+
+def _check_f32(name, v, ok, want):
+    """v: a number, not a bool, whose float32 value is finite and satisfies ok() -> that value as a Python float; ValueError
+    otherwise, "expected a float32 value {want}" for a number"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name}: expected a number, got {v!r}")
+    x = float(v)
+    f = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
+    if not (np.isfinite(f) and ok(f)):
+        raise ValueError(f"{name}: expected a float32 value {want}, got {v!r}")
+    return float(f)
+
+
+def _positive(x):
+    return x > 0.0
+
+
+def _check_flag(name, v, want, bools=(bool, np.bool_)):
+    """v: one of `bools`, or an int or np.integer that is 0 or 1 -> 0 or 1; ValueError "{name}: expected {want}, got ..." otherwise"""
+    if not isinstance(v, bools) and not (isinstance(v, (int, np.integer)) and v in (0, 1)):
+        raise ValueError(f"{name}: expected {want}, got {v!r}")
+    return int(v)
+
+
 def query_ray_args(origins, dirs, box=WORLD_BOX):
     """Checks and converts the arguments of Context.cast_rays (no device involved) -> (origins float32[k, 3] with k = 1
     (shared origin) or n, origin_stride 0 or 3, dirs float32[n, 3], box_min float32[3], box_max float32[3])."""
@@ -199,8 +258,202 @@ def query_point_args(coords):
     return np.ascontiguousarray(c, np.int32)
 
 
+# ---- The foreign-function signatures: one table per library, name -> (restype, argtypes), applied once when the library loads.
+# HOST_API and HIP_API hold every function of include/vrt_host.h and include/vrt.h (tests/test_abi.py compares them with the
+# prototypes); TEST_API the probes of libvrt_hip_test.so this module calls. A row reads like its prototype:
+_i, _u32, _u64, _f, _sz, _long = C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_size_t, C.c_long
+_p, _s = C.c_void_p, C.c_char_p   # void *: handles, streams, host and device buffers; const char *: strings and Python bytes
+_pi, _pi32, _pu32, _pu8, _pf, _pl, _psz, _pp = (C.POINTER(t) for t in (C.c_int, C.c_int32, C.c_uint32, C.c_uint8, C.c_float, C.c_long,
+                                                                       C.c_size_t, C.c_void_p))
+_tm, _flt, _fltv, _tmp, _tmpm = (C.POINTER(t) for t in (Tonemap, Filter, FilterVar, Temporal, TemporalMom))
+_RECORDS_OUT = [_pp, _psz]        # uint32_t **records, size_t *n_records
+
+HOST_API = {
+    "vrth_world_create": (_p, [_pi32, _pi32]),
+    "vrth_world_destroy": (None, [_p]),
+    "vrth_world_root": (_p, [_p]),
+    "vrth_world_load_vox": (_i, [_p, _s, _i, _i, _i]),
+    "vrth_world_load_vox_mem": (_i, [_p, _s, _sz, _i, _i, _i, _pl]),
+    "vrth_world_insert": (_i, [_p, _i, _i, _i, _u32, _f, _f, _f]),
+    "vrth_world_insert_many": (_i, [_p, _p, _p, _sz, _f, _f, _f]),
+    "vrth_world_remove": (_i, [_p, _i, _i, _i]),
+    "vrth_world_find": (_i, [_p, _i, _i, _i, _pu32]),
+    "vrth_world_ray_cast": (_i, [_p, _pf, _pf, _pi32, _pi]),
+    "vrth_world_ray_cast_many": (_long, [_p, _pf, _p, _sz, _p, _p]),
+    "vrth_world_texel_count": (_sz, [_p]),
+    "vrth_world_flatten": (_i, [_p, _pp, _psz, _pu32]),
+    "vrth_world_records": (_i, [_p] + _RECORDS_OUT + [_pu32]),
+    "vrth_octree_records": (_i, [_p] + _RECORDS_OUT + [_pu32]),
+    "vrth_octree_node_state": (_i, [_p, _pu8, _i]),
+    "vrth_octree_subtree_records": (_i, [_p, _pu8, _i] + _RECORDS_OUT),
+    "vrth_octree_path_records": (_i, [_p, _pu8, _i, _i, _i, _i] + _RECORDS_OUT),
+    "vrth_world_path_records": (_i, [_p, _pu8, _i, _i, _i, _i] + _RECORDS_OUT),
+    "vrth_octree_box_records": (_i, [_p, _pu8, _i, _pi32, _pi32] + _RECORDS_OUT),
+    "vrth_world_box_records": (_i, [_p, _pu8, _i, _pi32, _pi32] + _RECORDS_OUT),
+    "vrth_world_node_state": (_i, [_p, _pu8, _i]),
+    "vrth_world_subtree_records": (_i, [_p, _pu8, _i] + _RECORDS_OUT),
+    "vrth_free": (None, [_p]),
+    "vrth_camera_block": (_i, [_pf, _f, _f, _i, _i, _pf, _pf, _pf, _pf]),
+    "vrth_write_vox": (_i, [_s, _i, _i, _i, _p, _sz, _p]),
+    "vrth_encode_vox": (_i, [_i, _i, _i, _p, _sz, _p, _pp, _psz]),
+    "vrth_make_custom_vox": (_i, [_pp, _psz]),
+    "vrth_world_fill_heights": (_i, [_p, _p] + [_i] * 8),
+    "vrth_fnv1a64": (_u64, [_p, _sz]),
+    "vrth_version": (_s, []),
+}
+
+_RAYS = [_p, _sz, _p, _i, _p]              # ctx, n, origins, origin_stride, dirs
+_BATCH = _RAYS + [_i, _i, _u32, _u32]      # ... width, mode, first_sample, n_samples
+_FRAME = [_p, _i, _i]                      # ctx, width, height
+_CAMERA = [_p, _p, _p]                     # inv_projection[16], inv_view[16], camera_pos[4] of the temporal calls
+
+HIP_API = {
+    "vrt_create": (_i, [_i, _pp]),
+    "vrt_destroy": (None, [_p]),
+    "vrt_last_error": (_s, [_p]),
+    "vrt_default_params": (None, [C.POINTER(Params)]),
+    "vrt_set_params": (_i, [_p, C.POINTER(Params)]),
+    "vrt_upload_octree": (_i, [_p, _p, _sz, _u32]),
+    "vrt_get_scene_info": (_i, [_p, C.POINTER(SceneInfo)]),
+    "vrt_patch_plan": (_i, [_p, _i, _i, _i, _i, C.POINTER(Patch)]),
+    "vrt_patch_plan_box": (_i, [_p, _pi32, _pi32, _i, C.POINTER(Patch)]),
+    "vrt_patch_apply": (_i, [_p, C.POINTER(Patch), _p, _sz]),
+    "vrt_patch_begin": (_i, [_p]),
+    "vrt_patch_end": (_i, [_p]),
+    "vrt_compact": (_i, [_p]),
+    "vrt_upload_records": (_i, [_p, _p, _sz, _u32]),
+    "vrt_cast_rays": (_i, _RAYS + [_p, _p, _p]),
+    "vrt_cast_rays_device": (_i, _RAYS + [_p, _p, _p, _p]),
+    "vrt_find_voxels": (_i, [_p, _sz, _p, _p]),
+    "vrt_shade_rays": (_i, _BATCH + [_p, _p]),
+    "vrt_shade_rays_device": (_i, _BATCH + [_p, _p, _p]),
+    "vrt_accum_begin": (_i, _FRAME + [_u32]),
+    "vrt_accum_begin_ex": (_i, _FRAME + [_i, _u32, _u32]),
+    "vrt_accum_add": (_i, [_p, _u32, _pu32]),
+    "vrt_accum_resolve": (_i, [_p, _p, _p, _p]),
+    "vrt_accum_resolve_device": (_i, [_p, _p, _p, _p, _p]),
+    "vrt_set_lens": (_i, [_p, _f, _f]),
+    "vrt_set_path_depth": (_i, [_p, _i]),
+    "vrt_set_sun_disc": (_i, [_p, _f]),
+    "vrt_set_emitter_sampling": (_i, [_p, _i]),
+    "vrt_emitters": (_long, [_p, _p, _sz]),
+    "vrt_set_emitter_importance": (_i, [_p, _i]),
+    "vrt_emitter_cdf": (_long, [_p, _p, _sz]),
+    "vrt_set_emitter_mis": (_i, [_p, _i]),
+    "vrt_accum_begin_adaptive": (_i, _FRAME + [_i, _u32, _u32, _u32, _u32, _u32]),
+    "vrt_accum_counts": (_i, [_p, _p]),
+    "vrt_accum_keep_hdr": (_i, [_p, _i]),
+    "vrt_accum_resolve_hdr": (_i, [_p, _p, _tm, _p, _p]),
+    "vrt_accum_resolve_hdr_device": (_i, [_p, _p, _tm, _p, _p, _p]),
+    "vrt_shade_rays_hdr": (_i, _BATCH + [_tm, _p, _p, _p]),
+    "vrt_shade_rays_hdr_device": (_i, _BATCH + [_u32, _p, _tm, _p, _p, _p, _p]),
+    "vrt_set_camera": (_i, [_p, _pf, _pf, _pf]),
+    "vrt_dispatch": (_i, _FRAME + [_i, _p, _p]),
+    "vrt_dispatch_async": (_i, _FRAME + [_i, _p, _p, _pi]),
+    "vrt_dispatch_wait": (_i, [_p, _i]),
+    "vrt_host_alloc": (_i, [_p, _sz, _pp]),
+    "vrt_host_free": (_i, [_p, _p]),
+    "vrt_dispatch_rows": (_i, _FRAME + [_i, _i, _i, _p, _p, _p]),
+    "vrt_dispatch_shard": (_i, _FRAME + [_i, _i, _i, _i, _p, _p, _p]),
+    "vrt_shard_rows": (_i, [_i, _i, _i, _i]),
+    "vrt_dispatch_tiles": (_i, _FRAME + [_i, _i, _i, _i, _p, _p, _p]),
+    "vrt_device_alloc": (_i, [_p, _sz, _pp]),
+    "vrt_device_free": (_i, [_p, _p]),
+    "vrt_device_read": (_i, [_p, _p, _p, _sz, _p]),
+    "vrt_device_write": (_i, [_p, _p, _p, _sz, _p]),
+    "vrt_device_copy": (_i, [_p, _p, _p, _sz, _p]),
+    "vrt_ipc_export": (_i, [_p, _p, _s]),
+    "vrt_ipc_open": (_i, [_p, _s, _pp]),
+    "vrt_ipc_close": (_i, [_p, _p]),
+    "vrt_stream_write_flag": (_i, [_p, _p, _u32, _p]),
+    "vrt_stream_wait_flag": (_i, [_p, _p, _u32, _p]),
+    "vrt_create_multi": (_i, [_i, _pi, _pp]),
+    "vrt_destroy_multi": (None, [_p]),
+    "vrt_multi_last_error": (_s, [_p]),
+    "vrt_multi_devices": (_i, [_p]),
+    "vrt_multi_context": (_p, [_p, _i]),
+    "vrt_multi_upload_octree": (_i, [_p, _p, _sz, _u32]),
+    "vrt_multi_set_camera": (_i, [_p, _pf, _pf, _pf]),
+    "vrt_multi_set_params": (_i, [_p, C.POINTER(Params)]),
+    "vrt_multi_frame_alloc": (_i, _FRAME + [_pp, _pp]),
+    "vrt_multi_frame_free": (_i, [_p, _p, _p]),
+    "vrt_multi_dispatch": (_i, _FRAME + [_i, _i, _i, _p, _p]),
+    "vrt_multi_dispatch_frame": (_i, _FRAME + [_i, _p]),
+    "vrt_multi_synchronize": (_i, [_p]),
+    "vrt_multi_stream": (_p, [_p]),
+    "vrt_dispatch_views": (_i, _FRAME + [_i, _i, _i, _i, C.POINTER(View), _i, _p]),
+    "vrt_dispatch_timed": (_i, _FRAME + [_i, _i, _i, _p, _p, _p, _i, _pf]),
+    "vrt_denoise": (_i, _FRAME + [_p, _p, _p, _p]),
+    "vrt_denoise_host": (_i, _FRAME + [_p, _p, _p]),
+    "vrt_denoise_hdr": (_i, _FRAME + [_p, _p, _tm, _p, _p, _p]),
+    "vrt_denoise_hdr_host": (_i, _FRAME + [_p, _p, _tm, _p, _p]),
+    "vrt_accum_resolve_hdr_shown": (_i, [_p, _tm, _p, _p]),
+    "vrt_accum_resolve_hdr_shown_device": (_i, [_p, _tm, _p, _p, _p]),
+    "vrt_accum_guides": (_i, [_p, _p, _p, _p, _p]),
+    "vrt_accum_guides_device": (_i, [_p, _p, _p, _p, _p, _p]),
+    "vrt_guide_rays": (_i, _RAYS + [_i, _p, _p, _p, _p]),
+    "vrt_guide_rays_device": (_i, _RAYS + [_i, _p, _p, _p, _p, _p]),
+    "vrt_filter_default": (None, [_flt]),
+    "vrt_filter_hdr": (_i, _FRAME + [_p] * 5 + [_flt, _tm, _p, _p, _p]),
+    "vrt_filter_hdr_host": (_i, _FRAME + [_p] * 5 + [_flt, _tm, _p, _p]),
+    "vrt_accum_resolve_hdr_filtered": (_i, [_p, _flt, _tm, _p, _p]),
+    "vrt_accum_resolve_hdr_filtered_device": (_i, [_p, _flt, _tm, _p, _p, _p]),
+    "vrt_filter_var_default": (None, [_fltv]),
+    "vrt_filter_hdr_var": (_i, _FRAME + [_p] * 6 + [_fltv, _tm] + [_p] * 4),
+    "vrt_filter_hdr_var_host": (_i, _FRAME + [_p] * 6 + [_fltv, _tm] + [_p] * 3),
+    "vrt_accum_resolve_hdr_filtered_var": (_i, [_p, _fltv, _tm, _p, _p, _p]),
+    "vrt_accum_resolve_hdr_filtered_var_device": (_i, [_p, _fltv, _tm, _p, _p, _p, _p]),
+    "vrt_accum_keep_moments": (_i, [_p, _i]),
+    "vrt_accum_variance": (_i, [_p, _p]),
+    "vrt_accum_variance_device": (_i, [_p, _p, _p]),
+    "vrt_temporal_default": (None, [_tmp]),
+    "vrt_temporal_hdr": (_i, _FRAME + _CAMERA + [_p] * 5 + [_tmp] + [_p] * 4),
+    "vrt_temporal_hdr_host": (_i, _FRAME + _CAMERA + [_p] * 5 + [_tmp] + [_p] * 3),
+    "vrt_accum_resolve_hdr_temporal": (_i, [_p, _tmp, _fltv, _tm] + [_p] * 6),
+    "vrt_accum_resolve_hdr_temporal_device": (_i, [_p, _tmp, _fltv, _tm] + [_p] * 7),
+    "vrt_temporal_mom_default": (None, [_tmpm]),
+    "vrt_temporal_hdr_mom": (_i, _FRAME + _CAMERA + [_p] * 6 + [_tmpm] + [_p] * 4),
+    "vrt_temporal_hdr_mom_host": (_i, _FRAME + _CAMERA + [_p] * 6 + [_tmpm] + [_p] * 3),
+    "vrt_accum_resolve_hdr_temporal_mom": (_i, [_p, _tmpm, _fltv, _tm] + [_p] * 6),
+    "vrt_accum_resolve_hdr_temporal_mom_device": (_i, [_p, _tmpm, _fltv, _tm] + [_p] * 7),
+    "vrt_dispatch_frame": (_i, _FRAME + [_i, _p, _p, _p]),
+    "vrt_set_profiling": (_i, [_p, _i]),
+    "vrt_set_profiling_stride": (_i, [_p, _i]),
+    "vrt_profile_read": (_i, [_p, _pf, _i]),
+    "vrt_synchronize": (_i, [_p]),
+    "vrt_stream": (_p, [_p]),
+    "vrt_device": (_i, [_p]),
+    "vrt_set_variant": (_i, [_p, _i]),
+    "vrt_variant_available": (_i, [_i]),
+    "vrt_set_tile_scheduling": (_i, [_p, _i]),
+    "vrt_set_option": (_i, [_p, _i, _i]),
+    "vrt_get_tile_order": (_long, [_p, _p, _p, _sz]),
+    "vrt_set_tile_order": (_i, [_p, _i, _p, _p]),
+    "vrt_version": (_s, []),
+}
+
+_TREE = [_p, _sz]                          # texels, used_bytes
+_WORLD = [_pi32, _pi32]                    # wmin[3], wmax[3]
+
+TEST_API = {   # csrc/test/vrt_test.hip has no header: these rows are kept right by review
+    "vrt_test_math": (_i, [_i, _i, _p, _p, _p, _i]),
+    "vrt_test_build_layout": (_long, _TREE + [_p, _sz, C.POINTER(SceneInfo)]),
+    "vrt_test_patch_check": (_long, _TREE + _TREE + _WORLD + [_i, _i, _i, _p, _sz, _p, _i]),
+    "vrt_test_ray_table": (_i, [_p, _i, _i, _p, _p, _p]),
+    "vrt_test_root0": (_i, _TREE + _WORLD + [_pi32, _pi32]),
+    "vrt_test_view_in_range": (_i, [_p]),
+    "vrt_test_wide_find": (_i, _TREE + _WORLD + [_p, _sz, _p, _p]),
+    "vrt_test_adaptive_rule": (_i, [_u32, _u64, _u64, _u32, _u32, _u32]),
+    "vrt_test_adaptive_rule_device": (_i, [_i, _p, _p, _p, _u32, _u32, _u32, _p, _i]),
+    "vrt_test_lens_select": (_i, _TREE + _WORLD + [_f, _pf, _pf, _f, _pi32]),
+    "vrt_test_miss_mask": (_i, _TREE + _WORLD + [_f, _pf, _pf, _pf, _i, _i, _p, _pi32]),
+    "vrt_test_tile_order": (_i, [_i, _p, _u32, _u32, _p, _p]),
+    "vrt_test_tree_is_opaque": (_i, _TREE),
+}
+
 _host = None
 _hip = None
+_test = None
 
 
 def host_lib():
@@ -209,38 +462,9 @@ def host_lib():
         if not os.path.exists(HOST_LIB):
             raise VrtError(f"{HOST_LIB} is missing: run __graft_entry__.build() (make -C {CSRC})")
         L = C.CDLL(HOST_LIB)
-        L.vrth_world_create.restype = C.c_void_p
-        L.vrth_world_create.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.vrth_world_destroy.argtypes = [C.c_void_p]
-        L.vrth_world_load_vox.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
-        L.vrth_world_load_vox_mem.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_long)]
-        L.vrth_world_insert.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_float, C.c_float,
-                                        C.c_float]
-        L.vrth_world_insert_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float,
-                                             C.c_float]
-        L.vrth_world_remove.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.vrth_world_find.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
-        L.vrth_world_ray_cast.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                          C.POINTER(C.c_int32), C.POINTER(C.c_int)]
-        L.vrth_world_ray_cast_many.restype = C.c_long
-        L.vrth_world_ray_cast_many.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.vrth_world_texel_count.restype = C.c_size_t
-        L.vrth_world_texel_count.argtypes = [C.c_void_p]
-        L.vrth_world_flatten.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                         C.POINTER(C.c_uint32)]
-        L.vrth_free.argtypes = [C.c_void_p]
-        L.vrth_camera_block.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int, C.c_int,
-                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                        C.POINTER(C.c_float)]
-        L.vrth_write_vox.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.vrth_encode_vox.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
-                                      C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-        L.vrth_make_custom_vox.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-        L.vrth_world_fill_heights.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8
-        L.vrth_fnv1a64.restype = C.c_uint64
-        L.vrth_fnv1a64.argtypes = [C.c_void_p, C.c_size_t]
-        L.vrth_version.restype = C.c_char_p
+        for name, (res, args) in HOST_API.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
         _host = L
     return _host
 
@@ -259,163 +483,11 @@ def hip_lib():
         except ImportError:
             pass
         L = C.CDLL(HIP_LIB)
-        L.vrt_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.vrt_destroy.argtypes = [C.c_void_p]
-        L.vrt_last_error.restype = C.c_char_p
-        L.vrt_last_error.argtypes = [C.c_void_p]
-        L.vrt_default_params.argtypes = [C.POINTER(Params)]
-        L.vrt_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
-        L.vrt_upload_octree.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]
-        L.vrt_get_scene_info.argtypes = [C.c_void_p, C.POINTER(SceneInfo)]
-        L.vrt_set_camera.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.vrt_dispatch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.vrt_dispatch_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-        L.vrt_dispatch_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_shard_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-        L.vrt_dispatch_timed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float)]
-        L.vrt_synchronize.argtypes = [C.c_void_p]
-        L.vrt_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_denoise_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.vrt_get_tile_order.restype = C.c_long
-        L.vrt_get_tile_order.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        L.vrt_set_tile_order.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.vrt_dispatch_views.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.POINTER(View), C.c_int, C.c_void_p]
-        L.vrt_patch_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Patch)]
-        L.vrt_patch_apply.argtypes = [C.c_void_p, C.POINTER(Patch), C.c_void_p, C.c_size_t]
-        L.vrt_dispatch_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
-        L.vrt_stream.restype = C.c_void_p
-        L.vrt_stream.argtypes = [C.c_void_p]
-        L.vrt_device.argtypes = [C.c_void_p]
-        L.vrt_set_variant.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_variant_available.argtypes = [C.c_int]
-        L.vrt_patch_begin.argtypes = [C.c_void_p]
-        L.vrt_patch_end.argtypes = [C.c_void_p]
-        L.vrt_compact.argtypes = [C.c_void_p]
-        L.vrt_dispatch_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        L.vrt_dispatch_wait.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_host_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
-        L.vrt_host_free.argtypes = [C.c_void_p, C.c_void_p]
-        L.vrt_dispatch_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
-        L.vrt_device_free.argtypes = [C.c_void_p, C.c_void_p]
-        L.vrt_device_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.vrt_device_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.vrt_device_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.vrt_ipc_export.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
-        L.vrt_ipc_open.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
-        L.vrt_ipc_close.argtypes = [C.c_void_p, C.c_void_p]
-        L.vrt_stream_write_flag.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.vrt_stream_wait_flag.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.vrt_create_multi.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]
-        L.vrt_destroy_multi.argtypes = [C.c_void_p]
-        L.vrt_multi_last_error.restype = C.c_char_p
-        L.vrt_multi_last_error.argtypes = [C.c_void_p]
-        L.vrt_multi_devices.argtypes = [C.c_void_p]
-        L.vrt_multi_context.restype = C.c_void_p
-        L.vrt_multi_context.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_multi_upload_octree.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]
-        L.vrt_multi_set_camera.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.vrt_multi_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
-        L.vrt_multi_frame_alloc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-        L.vrt_multi_frame_free.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_multi_dispatch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.vrt_multi_synchronize.argtypes = [C.c_void_p]
-        L.vrt_multi_stream.restype = C.c_void_p
-        L.vrt_multi_stream.argtypes = [C.c_void_p]
-        L.vrt_version.restype = C.c_char_p
-        L.vrt_cast_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_cast_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
-        L.vrt_find_voxels.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        L.vrt_shade_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32,
-                                     C.c_uint32, C.c_void_p, C.c_void_p]
-        L.vrt_shade_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_shade_rays_hdr.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32,
-                                         C.c_uint32, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_shade_rays_hdr_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Tonemap), C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
-        L.vrt_accum_begin_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
-        L.vrt_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float]
-        L.vrt_set_path_depth.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_set_path_depth.restype = C.c_int
-        L.vrt_set_sun_disc.argtypes = [C.c_void_p, C.c_float]
-        L.vrt_set_sun_disc.restype = C.c_int
-        L.vrt_set_emitter_sampling.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_set_emitter_sampling.restype = C.c_int
-        L.vrt_emitters.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.vrt_emitters.restype = C.c_long
-        L.vrt_set_emitter_importance.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_set_emitter_importance.restype = C.c_int
-        L.vrt_set_emitter_mis.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_set_emitter_mis.restype = C.c_int
-        L.vrt_emitter_cdf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.vrt_emitter_cdf.restype = C.c_long
-        L.vrt_accum_begin_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
-                                               C.c_uint32, C.c_uint32]
-        L.vrt_accum_counts.argtypes = [C.c_void_p, C.c_void_p]
-        L.vrt_accum_add.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-        L.vrt_accum_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_keep_hdr.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_accum_keep_moments.argtypes = [C.c_void_p, C.c_int]
-        L.vrt_accum_variance.argtypes = [C.c_void_p, C.c_void_p]
-        L.vrt_accum_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_denoise_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
-                                      C.c_void_p]
-        L.vrt_denoise_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr_shown.argtypes = [C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr_shown_device.argtypes = [C.c_void_p, C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_guides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_guides_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_guide_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_void_p]
-        L.vrt_guide_rays_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_filter_default.argtypes = [C.POINTER(Filter)]
-        L.vrt_filter_default.restype = None
-        L.vrt_filter_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p,
-                                                                                         C.c_void_p, C.c_void_p]
-        L.vrt_filter_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(Filter), C.POINTER(Tonemap),
-                                                                                              C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr_filtered.argtypes = [C.c_void_p, C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr_filtered_device.argtypes = [C.c_void_p, C.POINTER(Filter), C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
-                                                            C.c_void_p]
-        L.vrt_filter_var_default.argtypes = [C.POINTER(FilterVar)]
-        L.vrt_filter_var_default.restype = None
-        L.vrt_filter_hdr_var.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 4
-        L.vrt_filter_hdr_var_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 3
-        L.vrt_accum_resolve_hdr_filtered_var.argtypes = [C.c_void_p, C.POINTER(FilterVar), C.POINTER(Tonemap), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_accum_resolve_hdr_filtered_var_device.argtypes = [C.c_void_p, C.POINTER(FilterVar), C.POINTER(Tonemap), C.c_void_p, C.c_void_p,
-                                                                C.c_void_p, C.c_void_p]
-        L.vrt_temporal_default.argtypes = [C.POINTER(Temporal)]
-        L.vrt_temporal_default.restype = None
-        L.vrt_temporal_hdr.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(Temporal)] + [C.c_void_p] * 4
-        L.vrt_temporal_hdr_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(Temporal)] + [C.c_void_p] * 3
-        L.vrt_accum_resolve_hdr_temporal.argtypes = [C.c_void_p, C.POINTER(Temporal), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 6
-        L.vrt_accum_resolve_hdr_temporal_device.argtypes = [C.c_void_p, C.POINTER(Temporal), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 7
-        L.vrt_temporal_mom_default.argtypes = [C.POINTER(TemporalMom)]
-        L.vrt_temporal_mom_default.restype = None
-        L.vrt_temporal_hdr_mom.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(TemporalMom)] + [C.c_void_p] * 4
-        L.vrt_temporal_hdr_mom_host.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(TemporalMom)] + [C.c_void_p] * 3
-        L.vrt_accum_resolve_hdr_temporal_mom.argtypes = [C.c_void_p, C.POINTER(TemporalMom), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 6
-        L.vrt_accum_resolve_hdr_temporal_mom_device.argtypes = [C.c_void_p, C.POINTER(TemporalMom), C.POINTER(FilterVar), C.POINTER(Tonemap)] + [C.c_void_p] * 7
+        for name, (res, args) in HIP_API.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
         _hip = L
     return _hip
-
-
-_test = None
 
 
 def test_lib():
@@ -430,18 +502,9 @@ def test_lib():
         except ImportError:
             pass
         L = C.CDLL(TEST_LIB)
-        L.vrt_test_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.vrt_test_build_layout.restype = C.c_long
-        L.vrt_test_build_layout.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(SceneInfo)]
-        L.vrt_test_patch_check.restype = C.c_long
-        L.vrt_test_patch_check.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                           C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
-        L.vrt_test_ray_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.vrt_test_root0.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                     C.POINTER(C.c_int32)]
-        L.vrt_test_view_in_range.argtypes = [C.c_void_p]
-        L.vrt_test_wide_find.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
-                                         C.c_size_t, C.c_void_p, C.c_void_p]
+        for name, (res, args) in TEST_API.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
         _test = L
     return _test
 
@@ -543,7 +606,6 @@ class World:
         """EXTENSION: the device record array straight from the tree -> (uint32[n,2], tex_dim), or None when the
         root is itself a leaf (texel path only)."""
         L = host_lib()
-        L.vrth_world_records.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]
         p, n, d = C.c_void_p(), C.c_size_t(0), C.c_uint32(0)
         r = L.vrth_world_records(self._h, C.byref(p), C.byref(n), C.byref(d))
         if r == -2:
@@ -558,8 +620,6 @@ class World:
         """EXTENSION: the sub-tree under the node reached by `path` (child indices from the root) as device records, only the nodes
         that meet the box of voxels [lo, hi] (inclusive) expanded, the rest "keep" records (vrth_world_box_records) -> uint32[n, 2]"""
         L = host_lib()
-        L.vrth_world_box_records.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                             C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         p, n = C.c_void_p(), C.c_size_t(0)
         pa = (C.c_uint8 * 16)(*list(path))
         r = L.vrth_world_box_records(self._h, pa, len(path), (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi]),
@@ -675,15 +735,12 @@ def adaptive_rule(n, s, q, min_samples, max_samples, tolerance):
     """Host probe (vrt_test_adaptive_rule): is a pixel with n samples, S = s and Q = q active under the adaptive accumulation's
     stopping rule (include/vrt.h vrt_accum_begin_adaptive)? The function the kernels evaluate, compiled for the host."""
     L = test_lib()
-    L.vrt_test_adaptive_rule.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
     return L.vrt_test_adaptive_rule(int(n), int(s), int(q), int(min_samples), int(max_samples), int(tolerance)) == 1
 
 
 def adaptive_rule_device(n, s, q, min_samples, max_samples, tolerance, device=0):
     """Device probe (vrt_test_adaptive_rule_device): the same rule on the GPU for arrays of states -> bool array"""
     L = test_lib()
-    L.vrt_test_adaptive_rule_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                C.c_void_p, C.c_int]
     n = np.ascontiguousarray(n, np.uint32)
     s = np.ascontiguousarray(s, np.uint64)
     q = np.ascontiguousarray(q, np.uint64)
@@ -701,8 +758,6 @@ def lens_choice(texels, cam_pos, inv_view, aperture, voxel_scale=1.0, world_min=
     """Host-only (vrt_test_lens_select): which side of each one-eye shortcut an accumulation with a thin lens of this aperture
     takes -> dict(box_valid, eye_shared, first_shared, no_medium, empty, lo, hi, root_shift); root_shift -1: no wide form."""
     L = test_lib()
-    L.vrt_test_lens_select.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float,
-                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int32)]
     t = np.ascontiguousarray(texels, np.uint8)
     cp = np.ascontiguousarray(cam_pos, np.float32)
     iv = np.ascontiguousarray(inv_view, np.float32)
@@ -721,9 +776,6 @@ def miss_mask(texels, inv_proj, inv_view, cam_pos, width, height, voxel_scale=1.
     whole_view) with mask a ((height + 7) // 8, (width + 7) // 8) uint8 array, 1 = traced, 0 = forward-pointing rays miss; or None
     when the view gets no mask."""
     L = test_lib()
-    L.vrt_test_miss_mask.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_float,
-                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
-                                     C.c_void_p, C.POINTER(C.c_int32)]
     t = np.ascontiguousarray(texels, np.uint8)
     ip = np.ascontiguousarray(inv_proj, np.float32).reshape(-1)
     iv = np.ascontiguousarray(inv_view, np.float32).reshape(-1)
@@ -747,7 +799,6 @@ def test_tile_order(tile_ticks, wave_slots, device=0):
     t = np.ascontiguousarray(tile_ticks, np.uint32).reshape(-1)
     assert t.size % 4 == 0
     n = t.size // 4
-    L.vrt_test_tile_order.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     order = np.zeros(n, np.uint32)
     split = np.zeros(1, np.uint32)
     r = L.vrt_test_tile_order(device, t.ctypes.data, n, wave_slots, order.ctypes.data, split.ctypes.data)
@@ -760,7 +811,6 @@ def test_tile_order(tile_ticks, wave_slots, device=0):
 def tree_is_opaque(texels):
     """Host-only (vrt_test_tree_is_opaque): may VRT_MODE_FULL run without a ray stack on this tree (for an eye in empty space)?"""
     L = test_lib()
-    L.vrt_test_tree_is_opaque.argtypes = [C.c_void_p, C.c_size_t]
     t = np.ascontiguousarray(texels, np.uint8)
     r = L.vrt_test_tree_is_opaque(t.ctypes.data if t.size else None, t.size)
     if r < 0:
@@ -789,6 +839,63 @@ def wide_find(texels, points, world_min=(-1023, -1023, -1023), world_max=(1024, 
     if r != 0:
         raise VrtError(f"vrt_test_wide_find failed ({r})")
     return out, (int(stats[0]), int(stats[1]))
+
+
+# ---- The pieces the HDR post chain's methods are made of (Context._tonemap .. accum_resolve_hdr_temporal_mom_device)
+def _ref(struct):
+    """a struct or None -> byref or the NULL pointer (the byref keeps the struct alive)"""
+    return None if struct is None else C.byref(struct)
+
+
+def _addr(a):
+    """an optional host array -> its address or NULL; the caller holds the array while the library reads it"""
+    return None if a is None else a.ctypes.data
+
+
+_GUIDE_PLANES = {"normal": (3,), "albedo": (4,), "depth": (), "coverage": ()}   # accum_guides' planes: the floats per pixel past [H,W]
+
+
+def _planes(rgb, guides, keys):
+    """rgb[H,W,3] and the planes of `guides` named in `keys` as contiguous float32 arrays of matching shapes -> (rgb, [planes], H,
+    W); ValueError otherwise"""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    g = [np.ascontiguousarray(guides[k], np.float32) for k in keys]
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+    h, w = rgb.shape[:2]
+    if any(p.shape != (h, w) + _GUIDE_PLANES[k] for p, k in zip(g, keys)):
+        want = ", ".join("[H,W" + "".join(f",{c}" for c in _GUIDE_PLANES[k]) + "]" for k in keys)
+        raise ValueError(f"expected guides {want} for H, W = {h}, {w}; got {', '.join(str(p.shape) for p in g)}")
+    return rgb, g, h, w
+
+
+def _variance_plane(variance, h, w):
+    """the optional variance[H,W] -> a contiguous float32 array or None; ValueError for another shape"""
+    if variance is None:
+        return None
+    variance = np.ascontiguousarray(variance, np.float32)
+    if variance.shape != (h, w):
+        raise ValueError(f"expected variance[H,W] for H, W = {h}, {w}; got {variance.shape}")
+    return variance
+
+
+def _history_planes(history, prev_camera, h, w):
+    """the optional history[3,H,W,4], which needs prev_camera -> a contiguous float32 array or None; ValueError otherwise"""
+    if history is None:
+        return None
+    history = np.ascontiguousarray(history, np.float32)
+    if history.shape != (3, h, w, 4):
+        raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
+    if prev_camera is None:
+        raise ValueError("a history needs prev_camera")
+    return history
+
+
+def _zeros(h, w, *kinds):
+    """zero-filled output planes by kind"""
+    shapes = {"history": ((3, h, w, 4), np.float32), "rgb": ((h, w, 3), np.float32), "rgba8": ((h, w, 4), np.uint8),
+              "plane": ((h, w), np.float32)}
+    return [np.zeros(*shapes[k]) for k in kinds]
 
 
 class Context:
@@ -821,7 +928,6 @@ class Context:
     def upload_records(self, records, tex_dim):
         """EXTENSION: upload the record array World.records() returns (no texel stream, no 2^23-texel limit)."""
         r = np.ascontiguousarray(records, np.uint32).reshape(-1, 2)
-        self._L.vrt_upload_records.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32]
         self._chk(self._L.vrt_upload_records(self._h, r.ctypes.data, r.shape[0], tex_dim))
 
     def scene_info(self):
@@ -931,7 +1037,6 @@ class Context:
         return np.array(ms, np.float32)
 
     def set_profiling(self, max_launches, every=1):
-        self._L.vrt_set_profiling_stride.argtypes = [C.c_void_p, C.c_int]
         self._chk(self._L.vrt_set_profiling_stride(self._h, every))
         self._chk(self._L.vrt_set_profiling(self._h, max_launches))
 
@@ -960,8 +1065,7 @@ class Context:
         if b.shape != (2, 3):
             raise ValueError(f"box: expected ((x, y, z), (x, y, z)), got shape {b.shape}")
         b = np.ascontiguousarray(b, np.float32)
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n < 2 ** 31:
-            raise ValueError(f"n: expected an integer in [0, 2^31), got {n!r}")
+        _check_int("n", n, "an integer in [0, 2^31)", 0, 2 ** 31 - 1)
         if origin_stride not in (0, 3):
             raise ValueError(f"origin_stride: expected 0 (one shared origin) or 3, got {origin_stride!r}")
         L = self._L
@@ -996,8 +1100,7 @@ class Context:
                           n_samples=1, stream=None):
         """vrt_shade_rays_device: DEVICE buffers (d_rgba: n x 4 bytes, d_id: n x 2 int32, either may be None), enqueued on
         `stream`"""
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 30:
-            raise ValueError(f"n: expected an integer in [0, 2^30], got {n!r}")
+        _check_int("n", n, "an integer in [0, 2^30]", 0, 2 ** 30)
         w = max(int(n), 1) if width is None else int(width)
         self._chk(self._L.vrt_shade_rays_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, int(mode),
                                                 int(first_sample) & 0xFFFFFFFF, int(n_samples), d_rgba, d_id, stream))
@@ -1010,34 +1113,25 @@ class Context:
         unclamped colours too (vrt_accum_keep_hdr, set for this begin): accum_resolve_hdr() resolves them. moments=True (needs
         hdr=True) keeps two more float64 sums per pixel, of the samples' luminance and its square (vrt_accum_keep_moments, set for
         this begin): accum_variance() resolves them, and accum_resolve_hdr_filtered_var() takes that plane."""
-        if not isinstance(hdr, (bool, np.bool_)) and not (isinstance(hdr, (int, np.integer)) and hdr in (0, 1)):
-            raise ValueError(f"hdr: expected a bool, got {hdr!r}")
-        if not isinstance(moments, (bool, np.bool_)) and not (isinstance(moments, (int, np.integer)) and moments in (0, 1)):
-            raise ValueError(f"moments: expected a bool, got {moments!r}")
+        _check_flag("hdr", hdr, "a bool")
+        _check_flag("moments", moments, "a bool")
         if moments and not hdr:
             raise ValueError("moments: the luminance moments ride with the HDR sums (hdr=True)")
-        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or mode not in (MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_FULL):
-            raise ValueError(f"mode: expected MODE_PRIMARY, MODE_PRIMARY_SHADOW or MODE_FULL, got {mode!r}")
-        if not isinstance(jitter, (bool, np.bool_)) and not (isinstance(jitter, (int, np.integer)) and jitter in (0, 1)):
-            raise ValueError(f"jitter: expected a bool, got {jitter!r}")
+        _check_int("mode", mode, "MODE_PRIMARY, MODE_PRIMARY_SHADOW or MODE_FULL", MODE_PRIMARY, MODE_FULL)
+        _check_flag("jitter", jitter, "a bool")
         for name, v in (("width", width), ("height", height)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 1 << 30:
-                raise ValueError(f"{name}: expected a positive integer, got {v!r}")
+            _check_int(name, v, "a positive integer", 1, 1 << 30)
         if width * height > 1 << 30:
             raise ValueError(f"width * height: at most 2^30 pixels, got {width * height}")
-        if isinstance(first_sample, bool) or not isinstance(first_sample, (int, np.integer)) or not 0 <= first_sample < 1 << 32:
-            raise ValueError(f"first_sample: expected an integer in [0, 2^32), got {first_sample!r}")
+        _check_int("first_sample", first_sample, "an integer in [0, 2^32)", 0, (1 << 32) - 1)
         if adaptive is not None:
             if not isinstance(adaptive, (tuple, list)) or len(adaptive) != 3:
                 raise ValueError(f"adaptive: expected None or (min_samples, max_samples, tolerance), got {adaptive!r}")
-            for name, v in zip(("min_samples", "max_samples", "tolerance"), adaptive):
-                if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                    raise ValueError(f"adaptive {name}: expected an integer, got {v!r}")
-            lo, hi, tol = (int(v) for v in adaptive)
+            names = ("min_samples", "max_samples", "tolerance")
+            lo, hi, tol = (_check_int(f"adaptive {name}", v, "an integer") for name, v in zip(names, adaptive))
             if not 2 <= lo <= hi <= 1 << 24:
                 raise ValueError(f"adaptive: need 2 <= min_samples <= max_samples <= 2^24, got {adaptive!r}")
-            if not 0 <= tol <= 65535:
-                raise ValueError(f"adaptive tolerance: expected an integer in [0, 65535], got {tol!r}")
+            _check_int("adaptive tolerance", tol, "an integer in [0, 65535]", 0, 65535)
             self._chk(self._L.vrt_accum_keep_hdr(self._h, 1 if hdr else 0))
             self._chk(self._L.vrt_accum_keep_moments(self._h, 1 if moments else 0))
             self._chk(self._L.vrt_accum_begin_adaptive(self._h, int(width), int(height), int(mode), int(first_sample),
@@ -1052,10 +1146,7 @@ class Context:
     def accum_counts(self):
         """An adaptive accumulation's per-pixel sample counts and how many pixels are still active (vrt_accum_counts)
         -> (counts uint32[H, W], active int)."""
-        shape = getattr(self, "_accum_shape", None)
-        if shape is None:
-            raise VrtError("accum_counts: no accumulation (call accum_begin first)")
-        counts = np.zeros(shape, np.uint32)
+        counts = np.zeros(self._accum_hw("accum_counts"), np.uint32)
         r = self._L.vrt_accum_counts(self._h, counts.ctypes.data)
         self._chk(min(r, 0))
         return counts, int(r)
@@ -1063,25 +1154,16 @@ class Context:
     def set_lens(self, aperture, focus_distance):
         """Thin lens for the progressive accumulation (vrt_set_lens): lens radius `aperture` (0: a pinhole) and the distance of
         the plane of focus along the view axis, both in world units. Frames stay pinhole."""
-        vals = []
-        for name, v, ok, want in (("aperture", aperture, lambda x: x >= 0.0, "finite and >= 0"),
-                                  ("focus_distance", focus_distance, lambda x: x > 0.0, "finite and > 0")):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise ValueError(f"{name}: expected a number, got {v!r}")
-            x = float(v)
-            f = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
-            if not (np.isfinite(f) and ok(f)):
-                raise ValueError(f"{name}: expected a float32 value {want}, got {v!r}")
-            vals.append(float(f))
-        self._chk(self._L.vrt_set_lens(self._h, vals[0], vals[1]))
+        aperture = _check_f32("aperture", aperture, lambda x: x >= 0.0, "finite and >= 0")
+        focus_distance = _check_f32("focus_distance", focus_distance, _positive, "finite and > 0")
+        self._chk(self._L.vrt_set_lens(self._h, aperture, focus_distance))
 
     def set_path_depth(self, depth):
         """Path depth of the samples of MODE_FULL in accumulations and ray batches (vrt_set_path_depth): an integer in
         1..MAX_PATH_DEPTH, default 1 (the shader's one bounce). An opaque, non-emissive hit of a ray of depth d < depth casts a
         shadow ray, adds the direct term and bounces again; at d == depth it adds the shader's ambient term. Frames
         (dispatch*) stay the shader at any setting; the primary modes ignore it."""
-        if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)):
-            raise ValueError(f"depth: expected an integer in [1, {MAX_PATH_DEPTH}], got {depth!r}")
+        _check_int("depth", depth, f"an integer in [1, {MAX_PATH_DEPTH}]")   # the range is the library's to refuse
         self._chk(self._L.vrt_set_path_depth(self._h, int(depth)))
         self._path_depth = int(depth)
 
@@ -1112,8 +1194,7 @@ class Context:
         (default) or 1 / True. On, every vertex that casts a shadow ray also connects to a random point of the emitter list
         (emitters()) and bounce rays that hit an emissive voxel add nothing: the same expectation, far less variance indoors. Frames
         (dispatch*) and the primary modes ignore it. Any other value raises (VRT_E_INVALID) and the previous one holds."""
-        if not isinstance(on, (bool, int, np.integer)) or int(on) not in (0, 1):
-            raise ValueError(f"emitter sampling: expected 0 or 1, got {on!r}")
+        _check_flag("emitter sampling", on, "0 or 1", bools=bool)
         self._chk(self._L.vrt_set_emitter_sampling(self._h, int(on)))
         self._emitter_sampling = bool(on)
 
@@ -1144,8 +1225,7 @@ class Context:
         default), one of N emitters and one of six faces, or EMIT_POWER (1), the emitter in proportion to its power (emitter_cdf())
         and the face among those turned towards the vertex: the same expectation, less variance where emitters differ much. Read
         only where sampling is on and the list is not empty. Any other value raises (VRT_E_INVALID) and the previous one holds."""
-        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or int(mode) not in (EMIT_UNIFORM, EMIT_POWER):
-            raise ValueError(f"emitter importance: expected EMIT_UNIFORM (0) or EMIT_POWER (1), got {mode!r}")
+        _check_int("emitter importance", mode, "EMIT_UNIFORM (0) or EMIT_POWER (1)", EMIT_UNIFORM, EMIT_POWER)
         self._chk(self._L.vrt_set_emitter_importance(self._h, int(mode)))
         self._emitter_importance = int(mode)
 
@@ -1160,8 +1240,7 @@ class Context:
         1 / True. Both keep their sample, so a vertex next to an emitter no longer carries an unbounded connection weight: the same
         expectation, no fireflies where emitters touch surfaces. Read only where sampling is on, the list is not empty and the mode
         is EMIT_POWER. Any other value raises before the library is touched and the previous one holds."""
-        if not isinstance(enable, (bool, int, np.integer)) or int(enable) not in (0, 1):
-            raise ValueError(f"emitter MIS: expected 0, 1 or a bool, got {enable!r}")
+        _check_flag("emitter MIS", enable, "0, 1 or a bool", bools=bool)
         self._chk(self._L.vrt_set_emitter_mis(self._h, int(enable)))
         self._emitter_mis = int(enable)
 
@@ -1190,21 +1269,16 @@ class Context:
 
     def accum_add(self, n_samples=1):
         """Enqueue n_samples more samples (vrt_accum_add) -> the samples now in the accumulation (n_samples after a restart)."""
-        if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or not 1 <= n_samples <= 1 << 24:
-            raise ValueError(f"n_samples: expected an integer in [1, 2^24], got {n_samples!r}")
+        _check_int("n_samples", n_samples, "an integer in [1, 2^24]", 1, 1 << 24)
         total = C.c_uint32(0)
         self._chk(self._L.vrt_accum_add(self._h, int(n_samples), C.byref(total)))
         return int(total.value)
 
     def accum_resolve(self):
         """The resolved accumulation (vrt_accum_resolve) -> (rgba8[H,W,4], id_dist[H,W,2], shown rgba8[H,W,4])."""
-        shape = getattr(self, "_accum_shape", None)
-        if shape is None:
-            raise VrtError("accum_resolve: no accumulation (call accum_begin first)")
-        h, w = shape
-        rgba = np.zeros((h, w, 4), np.uint8)
+        h, w = self._accum_hw("accum_resolve")
+        rgba, shown = _zeros(h, w, "rgba8", "rgba8")
         idd = np.zeros((h, w, 2), np.int32)
-        shown = np.zeros((h, w, 4), np.uint8)
         self._chk(self._L.vrt_accum_resolve(self._h, rgba.ctypes.data, idd.ctypes.data, shown.ctypes.data))
         return rgba, idd, shown
 
@@ -1216,19 +1290,23 @@ class Context:
     def _tonemap(tonemap, exposure):
         if tonemap not in TONEMAPS:
             raise ValueError(f"tonemap: expected 'clamp' or 'reinhard', got {tonemap!r}")
-        if isinstance(exposure, bool) or not isinstance(exposure, (int, float, np.integer, np.floating)):
-            raise ValueError(f"exposure: expected a number, got {exposure!r}")
-        x = float(exposure)
-        e = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
-        if not (np.isfinite(e) and e > 0.0):
-            raise ValueError(f"exposure: expected a float32 value finite and > 0, got {exposure!r}")
-        return Tonemap(TONEMAPS[tonemap], float(e))
+        return Tonemap(TONEMAPS[tonemap], _check_f32("exposure", exposure, _positive, "finite and > 0"))
+
+    def _tonemap_ref(self, tonemap, exposure):
+        """the tonemap / exposure arguments of the post chain -> a vrt_tonemap by reference; tonemap None: the NULL vrt_tonemap"""
+        return None if tonemap is None else C.byref(self._tonemap(tonemap, exposure))
+
+    def _accum_hw(self, who=None):
+        """the current accumulation's (h, w). None begun: VrtError in `who`'s name, or without one (0, 0) and the library says so"""
+        shape = getattr(self, "_accum_shape", None)
+        if shape is None and who:
+            raise VrtError(f"{who}: no accumulation (call accum_begin first)")
+        return shape or (0, 0)
 
     @staticmethod
     def _hdr_samples(n_samples, n_prior):
         for name, v, lo in (("n_samples", n_samples, 1), ("n_prior", n_prior, 0)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= 1 << 24:
-                raise ValueError(f"{name}: expected an integer in [{lo}, 2^24], got {v!r}")
+            _check_int(name, v, f"an integer in [{lo}, 2^24]", lo, 1 << 24)
         if int(n_prior) + int(n_samples) > 1 << 24:
             raise ValueError(f"n_prior + n_samples: at most 2^24 samples in all, got {int(n_prior) + int(n_samples)}")
 
@@ -1258,8 +1336,7 @@ class Context:
         self._hdr_samples(n_samples, n_prior)
         if n_prior != 0 and d_sums is None:
             raise ValueError("n_prior: needs d_sums")
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 30:
-            raise ValueError(f"n: expected an integer in [0, 2^30], got {n!r}")
+        _check_int("n", n, "an integer in [0, 2^30]", 0, 2 ** 30)
         w = max(int(n), 1) if width is None else int(width)
         self._chk(self._L.vrt_shade_rays_hdr_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, int(mode),
                                                     int(first_sample) & 0xFFFFFFFF, int(n_samples), int(n_prior), d_sums,
@@ -1270,13 +1347,7 @@ class Context:
         colours; rgba8[H,W,4]: its tone-mapped bytes, 'clamp' (exposure * x) or 'reinhard' (x' / (1 + x'), x' = exposure * x);
         shown rgba8[H,W,4]: the display pass on those bytes)."""
         tm = self._tonemap(tonemap, exposure)
-        shape = getattr(self, "_accum_shape", None)
-        if shape is None:
-            raise VrtError("accum_resolve_hdr: no accumulation (call accum_begin first)")
-        h, w = shape
-        rgb = np.zeros((h, w, 3), np.float32)
-        rgba = np.zeros((h, w, 4), np.uint8)
-        shown = np.zeros((h, w, 4), np.uint8)
+        rgb, rgba, shown = _zeros(*self._accum_hw("accum_resolve_hdr"), "rgb", "rgba8", "rgba8")
         self._chk(self._L.vrt_accum_resolve_hdr(self._h, rgb.ctypes.data, C.byref(tm), rgba.ctypes.data, shown.ctypes.data))
         return rgb, rgba, shown
 
@@ -1288,8 +1359,7 @@ class Context:
     def accum_variance(self):
         """The variance of the mean's luminance of an accumulation begun with moments=True (vrt_accum_variance, M1-M3 of
         include/vrt.h) -> float32[H, W]; 65504^2 ("unknown") where a pixel holds fewer than two samples."""
-        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
-        var = np.zeros((h, w), np.float32)
+        var, = _zeros(*self._accum_hw(), "plane")
         self._chk(self._L.vrt_accum_variance(self._h, var.ctypes.data))
         return var
 
@@ -1300,11 +1370,9 @@ class Context:
     def accum_guides(self):
         """The accumulation's guide planes (vrt_accum_guides): first-hit features averaged over the samples in the sums ->
         {"normal": float32[H,W,3], "albedo": float32[H,W,4], "depth": float32[H,W], "coverage": float32[H,W]}."""
-        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
-        out = {"normal": np.zeros((h, w, 3), np.float32), "albedo": np.zeros((h, w, 4), np.float32),
-               "depth": np.zeros((h, w), np.float32), "coverage": np.zeros((h, w), np.float32)}
-        self._chk(self._L.vrt_accum_guides(self._h, out["normal"].ctypes.data, out["albedo"].ctypes.data, out["depth"].ctypes.data,
-                                           out["coverage"].ctypes.data))
+        h, w = self._accum_hw()
+        out = {k: np.zeros((h, w) + c, np.float32) for k, c in _GUIDE_PLANES.items()}
+        self._chk(self._L.vrt_accum_guides(self._h, *(p.ctypes.data for p in out.values())))
         return out
 
     def accum_guides_device(self, d_normal, d_albedo, d_depth, d_coverage, stream=None):
@@ -1328,8 +1396,7 @@ class Context:
 
     def guide_rays_device(self, n, d_origins, origin_stride, d_dirs, d_normal, d_albedo, d_depth, d_hit, width=None, stream=None):
         """vrt_guide_rays_device: DEVICE buffers (n x 3, n x 4, n floats, n bytes; any may be None, not all), enqueued on `stream`"""
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= 2 ** 30:
-            raise ValueError(f"n: expected an integer in [0, 2^30], got {n!r}")
+        _check_int("n", n, "an integer in [0, 2^30]", 0, 2 ** 30)
         w = max(int(n), 1) if width is None else int(width)
         self._chk(self._L.vrt_guide_rays_device(self._h, int(n), d_origins, int(origin_stride), d_dirs, w, d_normal, d_albedo,
                                                 d_depth, d_hit, stream))
@@ -1337,42 +1404,35 @@ class Context:
     def accum_resolve_hdr_shown(self, tonemap="clamp", exposure=1.0):
         """The HDR display pass on an HDR accumulation (vrt_accum_resolve_hdr_shown): the ID-aware blur on the float mean, then the
         tone map -> (shown_rgb float32[H,W,3]: the filtered mean; shown_rgba8[H,W,4]: its tone-mapped bytes)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        shape = getattr(self, "_accum_shape", None)
-        if shape is None:
-            raise VrtError("accum_resolve_hdr_shown: no accumulation (call accum_begin first)")
-        h, w = shape
-        rgb = np.zeros((h, w, 3), np.float32)
-        rgba = np.zeros((h, w, 4), np.uint8)
-        self._chk(self._L.vrt_accum_resolve_hdr_shown(self._h, C.byref(tm) if tm else None, rgb.ctypes.data, rgba.ctypes.data))
+        tm = self._tonemap_ref(tonemap, exposure)
+        rgb, rgba = _zeros(*self._accum_hw("accum_resolve_hdr_shown"), "rgb", "rgba8")
+        self._chk(self._L.vrt_accum_resolve_hdr_shown(self._h, tm, rgb.ctypes.data, rgba.ctypes.data))
         return rgb, rgba
 
     def accum_resolve_hdr_shown_device(self, d_shown_rgb, d_shown_rgba, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_accum_resolve_hdr_shown_device: DEVICE buffers (either may be None, not both), enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        self._chk(self._L.vrt_accum_resolve_hdr_shown_device(self._h, C.byref(tm) if tm else None, d_shown_rgb, d_shown_rgba, stream))
+        tm = self._tonemap_ref(tonemap, exposure)
+        self._chk(self._L.vrt_accum_resolve_hdr_shown_device(self._h, tm, d_shown_rgb, d_shown_rgba, stream))
 
     def denoise_hdr(self, rgb, id_dist, tonemap="clamp", exposure=1.0):
         """The display pass in HDR through host arrays (vrt_denoise_hdr_host): quad.frag's ID-aware blur on a float image
         rgb[H,W,3], each float through h(c) = min(max(0, c), 65504), then the tone map of accum_resolve_hdr
         -> (rgb float32[H,W,3]: the filtered floats; rgba8 uint8[H,W,4]: their tone-mapped bytes)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
+        tm = self._tonemap_ref(tonemap, exposure)
         rgb = np.ascontiguousarray(rgb, np.float32)
         idd = np.ascontiguousarray(id_dist, np.int32)
         if rgb.ndim != 3 or rgb.shape[2] != 3 or idd.shape != rgb.shape[:2] + (2,):
             raise ValueError(f"expected rgb[H,W,3] and id_dist[H,W,2], got {rgb.shape} and {idd.shape}")
         h, w = rgb.shape[:2]
-        out = np.zeros_like(rgb)
-        out8 = np.zeros((h, w, 4), np.uint8)
-        self._chk(self._L.vrt_denoise_hdr_host(self._h, w, h, rgb.ctypes.data, idd.ctypes.data, C.byref(tm) if tm else None, out.ctypes.data,
-                                               out8.ctypes.data))
+        out, out8 = _zeros(h, w, "rgb", "rgba8")
+        self._chk(self._L.vrt_denoise_hdr_host(self._h, w, h, rgb.ctypes.data, idd.ctypes.data, tm, out.ctypes.data, out8.ctypes.data))
         return out, out8
 
     def denoise_hdr_device(self, width, height, d_rgb, d_id, d_out_rgb, d_out_rgba, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_denoise_hdr: DEVICE buffers (d_rgb: W*H x 3 floats; d_out_rgb, d_out_rgba: either may be None, not both), enqueued
         on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        self._chk(self._L.vrt_denoise_hdr(self._h, width, height, d_rgb, d_id, C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, stream))
+        tm = self._tonemap_ref(tonemap, exposure)
+        self._chk(self._L.vrt_denoise_hdr(self._h, width, height, d_rgb, d_id, tm, d_out_rgb, d_out_rgba, stream))
 
     @staticmethod
     def _filter_struct(filt, struct, defaults, sigmas):
@@ -1385,20 +1445,9 @@ class Context:
         if unknown:
             raise ValueError(f"filter: unknown keys {sorted(unknown)}")
         d.update(filt)
-        lv = d["levels"]
-        if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)) or not 0 <= lv <= FILTER_MAX_LEVELS:
-            raise ValueError(f"levels: expected an integer in [0, {FILTER_MAX_LEVELS}], got {lv!r}")
-        sig = []
-        for name in sigmas:
-            v = d[name]
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise ValueError(f"{name}: expected a number, got {v!r}")
-            x = float(v)
-            e = np.float32(x) if abs(x) <= float(np.finfo(np.float32).max) else np.float32(np.nan)
-            if not (np.isfinite(e) and e > 0.0):
-                raise ValueError(f"{name}: expected a float32 value finite and > 0, got {v!r}")
-            sig.append(float(e))
-        return struct(int(lv), FILTER_DEMODULATE if d["demodulate"] else 0, *sig)
+        lv = _check_int("levels", d["levels"], f"an integer in [0, {FILTER_MAX_LEVELS}]", 0, FILTER_MAX_LEVELS)
+        sig = [_check_f32(name, d[name], _positive, "finite and > 0") for name in sigmas]
+        return struct(lv, FILTER_DEMODULATE if d["demodulate"] else 0, *sig)
 
     @staticmethod
     def _filter(filt):
@@ -1406,138 +1455,99 @@ class Context:
         return Context._filter_struct(filt, Filter, default_filter, ("sigma_normal", "sigma_albedo", "sigma_depth"))
 
     @staticmethod
-    def _filter_planes(rgb, guides):
-        """rgb[H,W,3] and the four guide planes as contiguous float32 arrays of matching shapes -> (rgb, normal, albedo, depth,
-        coverage, H, W); ValueError otherwise"""
-        rgb = np.ascontiguousarray(rgb, np.float32)
-        n, a = np.ascontiguousarray(guides["normal"], np.float32), np.ascontiguousarray(guides["albedo"], np.float32)
-        z, cov = np.ascontiguousarray(guides["depth"], np.float32), np.ascontiguousarray(guides["coverage"], np.float32)
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
-        h, w = rgb.shape[:2]
-        if n.shape != (h, w, 3) or a.shape != (h, w, 4) or z.shape != (h, w) or cov.shape != (h, w):
-            raise ValueError(f"expected guides [H,W,3], [H,W,4], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {a.shape}, {z.shape}, {cov.shape}")
-        return rgb, n, a, z, cov, h, w
+    def _filter_var(filt):
+        """None (the NULL vrt_filter_var: vrt_filter_var_default) or a dict with any of default_filter_var()'s keys -> FilterVar or
+        None; the rules of _filter, for sigma_lum too"""
+        return Context._filter_struct(filt, FilterVar, default_filter_var, ("sigma_normal", "sigma_albedo", "sigma_depth", "sigma_lum"))
 
     def filter_hdr(self, rgb, guides, filter=None, tonemap="clamp", exposure=1.0):
         """The guided filter through host arrays (vrt_filter_hdr_host): an edge-avoiding a-trous filter on a float image rgb[H,W,3]
         whose edge weights come from `guides` = {"normal": [H,W,3], "albedo": [H,W,4], "depth": [H,W], "coverage": [H,W]}, the
         planes accum_guides returns. filter: None (vrt_filter_default) or a dict with any of default_filter()'s keys
         -> (rgb float32[H,W,3]: the filtered floats; rgba8 uint8[H,W,4]: their tone-mapped bytes)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter(filter)
-        rgb, n, a, z, cov, h, w = self._filter_planes(rgb, guides)
-        out = np.zeros_like(rgb)
-        out8 = np.zeros((h, w, 4), np.uint8)
-        self._chk(self._L.vrt_filter_hdr_host(self._h, w, h, rgb.ctypes.data, n.ctypes.data, a.ctypes.data, z.ctypes.data, cov.ctypes.data,
-                                              C.byref(f) if f else None, C.byref(tm) if tm else None, out.ctypes.data, out8.ctypes.data))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter(filter))
+        rgb, planes, h, w = _planes(rgb, guides, tuple(_GUIDE_PLANES))
+        out, out8 = _zeros(h, w, "rgb", "rgba8")
+        self._chk(self._L.vrt_filter_hdr_host(self._h, w, h, rgb.ctypes.data, *(p.ctypes.data for p in planes), f, tm, out.ctypes.data,
+                                              out8.ctypes.data))
         return out, out8
 
     def filter_hdr_device(self, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_out_rgb, d_out_rgba, filter=None,
                           tonemap="clamp", exposure=1.0, stream=None):
         """vrt_filter_hdr: DEVICE buffers (d_rgb: W*H x 3 floats; the planes as accum_guides_device writes them; d_out_rgb,
         d_out_rgba: either may be None, not both), enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter(filter)
-        self._chk(self._L.vrt_filter_hdr(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, C.byref(f) if f else None,
-                                         C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, stream))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter(filter))
+        self._chk(self._L.vrt_filter_hdr(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, f, tm, d_out_rgb,
+                                         d_out_rgba, stream))
 
     def accum_resolve_hdr_filtered(self, filter=None, tonemap="clamp", exposure=1.0):
         """The guided filter on an HDR accumulation (vrt_accum_resolve_hdr_filtered): its float mean filtered with its own guide
         planes -> (rgb float32[H,W,3]: the filtered mean; rgba8[H,W,4]: its tone-mapped bytes)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter(filter)
-        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
-        rgb = np.zeros((h, w, 3), np.float32)
-        rgba = np.zeros((h, w, 4), np.uint8)
-        self._chk(self._L.vrt_accum_resolve_hdr_filtered(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, rgb.ctypes.data,
-                                                         rgba.ctypes.data))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter(filter))
+        rgb, rgba = _zeros(*self._accum_hw(), "rgb", "rgba8")
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered(self._h, f, tm, rgb.ctypes.data, rgba.ctypes.data))
         return rgb, rgba
 
     def accum_resolve_hdr_filtered_device(self, d_rgb, d_rgba, filter=None, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_accum_resolve_hdr_filtered_device: DEVICE buffers (either may be None, not both), enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter(filter)
-        self._chk(self._L.vrt_accum_resolve_hdr_filtered_device(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, d_rgb, d_rgba,
-                                                                stream))
-
-    @staticmethod
-    def _filter_var(filt):
-        """None (the NULL vrt_filter_var: vrt_filter_var_default) or a dict with any of default_filter_var()'s keys -> FilterVar or
-        None; the rules of _filter, for sigma_lum too"""
-        return Context._filter_struct(filt, FilterVar, default_filter_var, ("sigma_normal", "sigma_albedo", "sigma_depth", "sigma_lum"))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter(filter))
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered_device(self._h, f, tm, d_rgb, d_rgba, stream))
 
     def filter_hdr_var(self, rgb, guides, variance=None, filter=None, tonemap="clamp", exposure=1.0):
         """The variance-guided filter through host arrays (vrt_filter_hdr_var_host): filter_hdr with an edge-stopping luminance term
         whose width is each pixel's variance. variance: [H,W], the variance of the luminance of rgb at each pixel, or None: the
         filter estimates it spatially. filter: None (vrt_filter_var_default) or a dict with any of default_filter_var()'s keys
         -> (rgb float32[H,W,3], rgba8 uint8[H,W,4], variance float32[H,W]: the filtered image's)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        rgb, n, a, z, cov, h, w = self._filter_planes(rgb, guides)
-        if variance is not None:
-            variance = np.ascontiguousarray(variance, np.float32)
-            if variance.shape != (h, w):
-                raise ValueError(f"expected variance[H,W] for H, W = {h}, {w}; got {variance.shape}")
-        out = np.zeros_like(rgb)
-        out8 = np.zeros((h, w, 4), np.uint8)
-        outv = np.zeros((h, w), np.float32)
-        self._chk(self._L.vrt_filter_hdr_var_host(self._h, w, h, rgb.ctypes.data, n.ctypes.data, a.ctypes.data, z.ctypes.data, cov.ctypes.data,
-                                                  variance.ctypes.data if variance is not None else None, C.byref(f) if f else None,
-                                                  C.byref(tm) if tm else None, out.ctypes.data, out8.ctypes.data, outv.ctypes.data))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter_var(filter))
+        rgb, planes, h, w = _planes(rgb, guides, tuple(_GUIDE_PLANES))
+        variance = _variance_plane(variance, h, w)
+        out, out8, outv = _zeros(h, w, "rgb", "rgba8", "plane")
+        self._chk(self._L.vrt_filter_hdr_var_host(self._h, w, h, rgb.ctypes.data, *(p.ctypes.data for p in planes), _addr(variance), f, tm,
+                                                  out.ctypes.data, out8.ctypes.data, outv.ctypes.data))
         return out, out8, outv
 
     def filter_hdr_var_device(self, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance, d_out_rgb, d_out_rgba,
                               d_out_variance, filter=None, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_filter_hdr_var: DEVICE buffers (filter_hdr_device's; d_variance: W*H floats or None; d_out_variance: W*H floats or
         None; d_out_rgb, d_out_rgba: either may be None, not both), enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        self._chk(self._L.vrt_filter_hdr_var(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance,
-                                             C.byref(f) if f else None, C.byref(tm) if tm else None, d_out_rgb, d_out_rgba, d_out_variance,
-                                             stream))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter_var(filter))
+        self._chk(self._L.vrt_filter_hdr_var(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_variance, f, tm,
+                                             d_out_rgb, d_out_rgba, d_out_variance, stream))
 
     def accum_resolve_hdr_filtered_var(self, filter=None, tonemap="clamp", exposure=1.0):
         """The variance-guided filter on an HDR accumulation (vrt_accum_resolve_hdr_filtered_var): its float mean filtered with its
         own guide planes and its variance -> (rgb float32[H,W,3], rgba8[H,W,4], variance float32[H,W]). The variance is the
         measured one (accum_variance()'s plane) on an accumulation begun with moments=True that holds two samples or more, and a
         spatial estimate from the mean itself on every other."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
-        rgb = np.zeros((h, w, 3), np.float32)
-        rgba = np.zeros((h, w, 4), np.uint8)
-        var = np.zeros((h, w), np.float32)
-        self._chk(self._L.vrt_accum_resolve_hdr_filtered_var(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, rgb.ctypes.data,
-                                                             rgba.ctypes.data, var.ctypes.data))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter_var(filter))
+        rgb, rgba, var = _zeros(*self._accum_hw(), "rgb", "rgba8", "plane")
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered_var(self._h, f, tm, rgb.ctypes.data, rgba.ctypes.data, var.ctypes.data))
         return rgb, rgba, var
 
     def accum_resolve_hdr_filtered_var_device(self, d_rgb, d_rgba, d_variance, filter=None, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_accum_resolve_hdr_filtered_var_device: DEVICE buffers (d_rgb, d_rgba: either may be None, not both; d_variance may be
         None), enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        self._chk(self._L.vrt_accum_resolve_hdr_filtered_var_device(self._h, C.byref(f) if f else None, C.byref(tm) if tm else None, d_rgb,
-                                                                    d_rgba, d_variance, stream))
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter_var(filter))
+        self._chk(self._L.vrt_accum_resolve_hdr_filtered_var_device(self._h, f, tm, d_rgb, d_rgba, d_variance, stream))
 
     @staticmethod
     def _temporal(temporal, prev_camera):
         """a dict with any of default_temporal()'s keys (None: the defaults) and the previous frame's camera (prev_view_proj[16],
         prev_camera_pos[3 or 4]), or None where no history comes in -> Temporal; ValueError for an unknown key"""
-        t = Temporal()
-        hip_lib().vrt_temporal_default(C.byref(t))
-        for k, v in (temporal or {}).items():
-            if k not in TEMPORAL_KEYS:
-                raise ValueError(f"unknown temporal key {k!r}; expected any of {TEMPORAL_KEYS}")
-            setattr(t, k, int(v) if k == "max_history" else float(v))
-        if prev_camera is not None:
-            vp = np.ascontiguousarray(prev_camera[0], np.float32).reshape(-1)
-            cp = np.ascontiguousarray(prev_camera[1], np.float32).reshape(-1)
-            if vp.size != 16 or cp.size not in (3, 4):
-                raise ValueError("expected prev_camera = (prev_view_proj[16], prev_camera_pos[3 or 4])")
-            t.prev_view_proj[:] = [float(v) for v in vp]
-            t.prev_camera_pos[:cp.size] = [float(v) for v in cp]
-        return t
+        return _temporal_struct(_TEMPORAL, temporal, prev_camera)
+
+    @staticmethod
+    def _temporal_mom(temporal, prev_camera):
+        """_temporal() for the calls that take a vrt_temporal_mom: a dict with any of default_temporal_mom()'s keys -> TemporalMom"""
+        return _temporal_struct(_TEMPORAL_MOM, temporal, prev_camera)
 
     @staticmethod
     def _camera_block(camera):
@@ -1545,6 +1555,42 @@ class Context:
         if ip.size != 16 or iv.size != 16 or cp.size != 4:
             raise ValueError("expected camera = (inv_projection[16], inv_view[16], camera_pos[4])")
         return ip, iv, cp
+
+    # The four temporal entry points in their two flavours, as temporal_frame / temporal_accum of csrc/vrt_temporal.cpp: one body
+    # each, told the C function by name (looked up when every argument has passed) and the builder of its struct; the _mom
+    # flavour's one more plane comes as a tuple that the other flavour leaves empty.
+    def _temporal_frame(self, fn, build, camera, rgb, guides, variance, history, prev_camera, temporal):
+        ip, iv, cp = self._camera_block(camera)
+        rgb, planes, h, w = _planes(rgb, guides, ("normal", "depth", "coverage"))
+        planes += [_variance_plane(v, h, w) for v in variance]
+        history = _history_planes(history, prev_camera, h, w)
+        t = build(temporal, prev_camera if history is not None else None)
+        outs = _zeros(h, w, "history", "rgb", "plane")
+        self._chk(getattr(self._L, fn)(self._h, w, h, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, rgb.ctypes.data,
+                                       *(_addr(p) for p in planes), _addr(history), C.byref(t), *(o.ctypes.data for o in outs)))
+        return tuple(outs)
+
+    def _temporal_frame_device(self, fn, build, width, height, camera, d_in, d_history_in, d_out, prev_camera, temporal, stream):
+        ip, iv, cp = self._camera_block(camera)
+        t = build(temporal, prev_camera if d_history_in is not None else None)
+        self._chk(getattr(self._L, fn)(self._h, width, height, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, *d_in, d_history_in,
+                                       C.byref(t), *d_out, stream))
+
+    def _temporal_accum(self, fn, build, history, prev_camera, temporal, filter, tonemap, exposure):
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter_var(filter))
+        h, w = self._accum_hw()
+        history = _history_planes(history, prev_camera, h, w)
+        t = build(temporal, prev_camera if history is not None else None)
+        outs = _zeros(h, w, "history", "rgb", "rgb", "rgba8", "plane")
+        self._chk(getattr(self._L, fn)(self._h, C.byref(t), f, tm, _addr(history), *(o.ctypes.data for o in outs)))
+        return tuple(outs)
+
+    def _temporal_accum_device(self, fn, build, d_history_in, d_out, prev_camera, temporal, filter, tonemap, exposure, stream):
+        tm = self._tonemap_ref(tonemap, exposure)
+        f = _ref(self._filter_var(filter))
+        t = build(temporal, prev_camera if d_history_in is not None else None)
+        self._chk(getattr(self._L, fn)(self._h, C.byref(t), f, tm, d_history_in, *d_out, stream))
 
     def temporal_hdr(self, camera, rgb, guides, history=None, prev_camera=None, temporal=None):
         """The temporal pass through host arrays (vrt_temporal_hdr_host): last frame's `history` float32[3,H,W,4] (None: the first
@@ -1554,156 +1600,61 @@ class Context:
         projection * view and eye, needed with a history. temporal: None (vrt_temporal_default) or a dict with any of
         default_temporal()'s keys -> (history float32[3,H,W,4]: the next call's; rgb float32[H,W,3]: the integrated colour;
         variance float32[H,W]: of its luminance, the plane filter_hdr_var takes)."""
-        ip, iv, cp = self._camera_block(camera)
-        rgb = np.ascontiguousarray(rgb, np.float32)
-        n, z, cov = (np.ascontiguousarray(guides[k], np.float32) for k in ("normal", "depth", "coverage"))
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
-        h, w = rgb.shape[:2]
-        if n.shape != (h, w, 3) or z.shape != (h, w) or cov.shape != (h, w):
-            raise ValueError(f"expected guides [H,W,3], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {z.shape}, {cov.shape}")
-        if history is not None:
-            history = np.ascontiguousarray(history, np.float32)
-            if history.shape != (3, h, w, 4):
-                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
-            if prev_camera is None:
-                raise ValueError("a history needs prev_camera")
-        t = self._temporal(temporal, prev_camera if history is not None else None)
-        out_h, out, outv = np.zeros((3, h, w, 4), np.float32), np.zeros_like(rgb), np.zeros((h, w), np.float32)
-        self._chk(self._L.vrt_temporal_hdr_host(self._h, w, h, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, rgb.ctypes.data, n.ctypes.data,
-                                                z.ctypes.data, cov.ctypes.data, history.ctypes.data if history is not None else None,
-                                                C.byref(t), out_h.ctypes.data, out.ctypes.data, outv.ctypes.data))
-        return out_h, out, outv
+        return self._temporal_frame("vrt_temporal_hdr_host", self._temporal, camera, rgb, guides, (), history, prev_camera, temporal)
 
     def temporal_hdr_device(self, width, height, camera, d_rgb, d_normal, d_depth, d_coverage, d_history_in, d_history_out, d_out_rgb,
                             d_out_variance, prev_camera=None, temporal=None, stream=None):
         """vrt_temporal_hdr: DEVICE buffers (d_rgb: W*H x 3 floats; the planes as accum_guides_device writes them; the histories
         W*H x HISTORY_BYTES bytes each, d_history_in None on the first frame; d_out_rgb, d_out_variance: either may be None),
         enqueued on `stream`"""
-        ip, iv, cp = self._camera_block(camera)
-        t = self._temporal(temporal, prev_camera if d_history_in is not None else None)
-        self._chk(self._L.vrt_temporal_hdr(self._h, width, height, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_depth,
-                                           d_coverage, d_history_in, C.byref(t), d_history_out, d_out_rgb, d_out_variance, stream))
+        self._temporal_frame_device("vrt_temporal_hdr", self._temporal, width, height, camera, (d_rgb, d_normal, d_depth, d_coverage),
+                                    d_history_in, (d_history_out, d_out_rgb, d_out_variance), prev_camera, temporal, stream)
 
     def accum_resolve_hdr_temporal(self, history=None, prev_camera=None, temporal=None, filter=None, tonemap="clamp", exposure=1.0):
         """The temporal pass and the variance-guided filter on an HDR accumulation (vrt_accum_resolve_hdr_temporal): its float mean
         with its own guide planes and the context's current camera, integrated with `history` (None: the first frame), then
         filtered with the temporal variance -> (history float32[3,H,W,4], integrated float32[H,W,3]: unfiltered, what the
         history holds; rgb float32[H,W,3], rgba8[H,W,4], variance float32[H,W]: the filter's)."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
-        if history is not None:
-            history = np.ascontiguousarray(history, np.float32)
-            if history.shape != (3, h, w, 4):
-                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
-            if prev_camera is None:
-                raise ValueError("a history needs prev_camera")
-        t = self._temporal(temporal, prev_camera if history is not None else None)
-        out_h, integ = np.zeros((3, h, w, 4), np.float32), np.zeros((h, w, 3), np.float32)
-        rgb, rgba, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 4), np.uint8), np.zeros((h, w), np.float32)
-        self._chk(self._L.vrt_accum_resolve_hdr_temporal(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
-                                                         history.ctypes.data if history is not None else None, out_h.ctypes.data,
-                                                         integ.ctypes.data, rgb.ctypes.data, rgba.ctypes.data, var.ctypes.data))
-        return out_h, integ, rgb, rgba, var
+        return self._temporal_accum("vrt_accum_resolve_hdr_temporal", self._temporal, history, prev_camera, temporal, filter, tonemap,
+                                    exposure)
 
     def accum_resolve_hdr_temporal_device(self, d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, prev_camera=None,
                                           temporal=None, filter=None, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_accum_resolve_hdr_temporal_device: DEVICE buffers (d_history_in None on the first frame; d_integrated and d_variance
         may be None; d_rgb, d_rgba: either may be None, not both), enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        t = self._temporal(temporal, prev_camera if d_history_in is not None else None)
-        self._chk(self._L.vrt_accum_resolve_hdr_temporal_device(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
-                                                                d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, stream))
-
-    @staticmethod
-    def _temporal_mom(temporal, prev_camera):
-        """_temporal() for the calls that take a vrt_temporal_mom: a dict with any of default_temporal_mom()'s keys -> TemporalMom"""
-        t = TemporalMom()
-        hip_lib().vrt_temporal_mom_default(C.byref(t))
-        for k, v in (temporal or {}).items():
-            if k not in TEMPORAL_MOM_KEYS:
-                raise ValueError(f"unknown temporal key {k!r}; expected any of {TEMPORAL_MOM_KEYS}")
-            setattr(t, k, int(v) if k in ("max_history", "measured_below", "search") else float(v))
-        if prev_camera is not None:
-            b = Context._temporal(None, prev_camera)
-            t.prev_view_proj[:] = list(b.prev_view_proj)
-            t.prev_camera_pos[:] = list(b.prev_camera_pos)
-        return t
+        self._temporal_accum_device("vrt_accum_resolve_hdr_temporal_device", self._temporal, d_history_in,
+                                    (d_history_out, d_integrated, d_rgb, d_rgba, d_variance), prev_camera, temporal, filter, tonemap,
+                                    exposure, stream)
 
     def temporal_hdr_mom(self, camera, rgb, guides, variance=None, history=None, prev_camera=None, temporal=None):
         """The temporal pass with measured variances and a 3 x 3 search through host arrays (vrt_temporal_hdr_mom_host):
         temporal_hdr's arguments, `variance` float32[H,W] -- this frame's measured variance of the mean, what accum_variance returns;
         None: unknown -- and temporal a dict with any of default_temporal_mom()'s keys -> (history float32[3,H,W,4], rgb
         float32[H,W,3], variance float32[H,W]): temporal_hdr's, the history with the integrated variance in plane 2's fourth float."""
-        ip, iv, cp = self._camera_block(camera)
-        rgb = np.ascontiguousarray(rgb, np.float32)
-        n, z, cov = (np.ascontiguousarray(guides[k], np.float32) for k in ("normal", "depth", "coverage"))
-        if rgb.ndim != 3 or rgb.shape[2] != 3:
-            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
-        h, w = rgb.shape[:2]
-        if n.shape != (h, w, 3) or z.shape != (h, w) or cov.shape != (h, w):
-            raise ValueError(f"expected guides [H,W,3], [H,W], [H,W] for H, W = {h}, {w}; got {n.shape}, {z.shape}, {cov.shape}")
-        if variance is not None:
-            variance = np.ascontiguousarray(variance, np.float32)
-            if variance.shape != (h, w):
-                raise ValueError(f"expected variance[H,W] for H, W = {h}, {w}; got {variance.shape}")
-        if history is not None:
-            history = np.ascontiguousarray(history, np.float32)
-            if history.shape != (3, h, w, 4):
-                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
-            if prev_camera is None:
-                raise ValueError("a history needs prev_camera")
-        t = self._temporal_mom(temporal, prev_camera if history is not None else None)
-        out_h, out, outv = np.zeros((3, h, w, 4), np.float32), np.zeros_like(rgb), np.zeros((h, w), np.float32)
-        self._chk(self._L.vrt_temporal_hdr_mom_host(self._h, w, h, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, rgb.ctypes.data,
-                                                    n.ctypes.data, z.ctypes.data, cov.ctypes.data,
-                                                    variance.ctypes.data if variance is not None else None,
-                                                    history.ctypes.data if history is not None else None, C.byref(t), out_h.ctypes.data,
-                                                    out.ctypes.data, outv.ctypes.data))
-        return out_h, out, outv
+        return self._temporal_frame("vrt_temporal_hdr_mom_host", self._temporal_mom, camera, rgb, guides, (variance,), history,
+                                    prev_camera, temporal)
 
     def temporal_hdr_mom_device(self, width, height, camera, d_rgb, d_normal, d_depth, d_coverage, d_variance_in, d_history_in,
                                 d_history_out, d_out_rgb, d_out_variance, prev_camera=None, temporal=None, stream=None):
         """vrt_temporal_hdr_mom: temporal_hdr_device's DEVICE buffers and d_variance_in (W*H floats, may be None), enqueued on
         `stream`"""
-        ip, iv, cp = self._camera_block(camera)
-        t = self._temporal_mom(temporal, prev_camera if d_history_in is not None else None)
-        self._chk(self._L.vrt_temporal_hdr_mom(self._h, width, height, ip.ctypes.data, iv.ctypes.data, cp.ctypes.data, d_rgb, d_normal,
-                                               d_depth, d_coverage, d_variance_in, d_history_in, C.byref(t), d_history_out, d_out_rgb,
-                                               d_out_variance, stream))
+        self._temporal_frame_device("vrt_temporal_hdr_mom", self._temporal_mom, width, height, camera,
+                                    (d_rgb, d_normal, d_depth, d_coverage, d_variance_in), d_history_in,
+                                    (d_history_out, d_out_rgb, d_out_variance), prev_camera, temporal, stream)
 
     def accum_resolve_hdr_temporal_mom(self, history=None, prev_camera=None, temporal=None, filter=None, tonemap="clamp", exposure=1.0):
         """accum_resolve_hdr_temporal with the measured-variance pass (vrt_accum_resolve_hdr_temporal_mom): the variance input is the
         accumulation's own measured variance where it keeps moments (accum_keep_moments), unknown where it does not; temporal a dict
         with any of default_temporal_mom()'s keys -> the same five arrays."""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        h, w = getattr(self, "_accum_shape", None) or (0, 0)   # no accumulation: the library says so
-        if history is not None:
-            history = np.ascontiguousarray(history, np.float32)
-            if history.shape != (3, h, w, 4):
-                raise ValueError(f"expected history[3,H,W,4] for H, W = {h}, {w}; got {history.shape}")
-            if prev_camera is None:
-                raise ValueError("a history needs prev_camera")
-        t = self._temporal_mom(temporal, prev_camera if history is not None else None)
-        out_h, integ = np.zeros((3, h, w, 4), np.float32), np.zeros((h, w, 3), np.float32)
-        rgb, rgba, var = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 4), np.uint8), np.zeros((h, w), np.float32)
-        self._chk(self._L.vrt_accum_resolve_hdr_temporal_mom(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
-                                                             history.ctypes.data if history is not None else None, out_h.ctypes.data,
-                                                             integ.ctypes.data, rgb.ctypes.data, rgba.ctypes.data, var.ctypes.data))
-        return out_h, integ, rgb, rgba, var
+        return self._temporal_accum("vrt_accum_resolve_hdr_temporal_mom", self._temporal_mom, history, prev_camera, temporal, filter,
+                                    tonemap, exposure)
 
     def accum_resolve_hdr_temporal_mom_device(self, d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance, prev_camera=None,
                                               temporal=None, filter=None, tonemap="clamp", exposure=1.0, stream=None):
         """vrt_accum_resolve_hdr_temporal_mom_device: accum_resolve_hdr_temporal_device's DEVICE buffers, enqueued on `stream`"""
-        tm = None if tonemap is None else self._tonemap(tonemap, exposure)   # None: the NULL vrt_tonemap
-        f = self._filter_var(filter)
-        t = self._temporal_mom(temporal, prev_camera if d_history_in is not None else None)
-        self._chk(self._L.vrt_accum_resolve_hdr_temporal_mom_device(self._h, C.byref(t), C.byref(f) if f else None, C.byref(tm) if tm else None,
-                                                                    d_history_in, d_history_out, d_integrated, d_rgb, d_rgba, d_variance,
-                                                                    stream))
+        self._temporal_accum_device("vrt_accum_resolve_hdr_temporal_mom_device", self._temporal_mom, d_history_in,
+                                    (d_history_out, d_integrated, d_rgb, d_rgba, d_variance), prev_camera, temporal, filter, tonemap,
+                                    exposure, stream)
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""
@@ -1719,9 +1670,6 @@ class Context:
         (vrt_patch_plan / vrth_world_path_records / vrt_patch_apply). Returns the depth of the node replaced, or None
         when the edit needs a full upload (nothing was changed on the device then)."""
         H = host_lib()
-        H.vrth_world_node_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int]
-        H.vrth_world_path_records.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int,
-                                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         plan = Patch()
         while max_depth >= 1:
             if self._L.vrt_patch_plan(self._h, x, y, z, max_depth, C.byref(plan)) != 0:
@@ -1743,10 +1691,6 @@ class Context:
         (vrt_patch_plan_box / vrth_world_box_records / vrt_patch_apply). Returns the depth of the node replaced, or None when the
         edit needs a full upload."""
         H = host_lib()
-        H.vrth_world_node_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int]
-        H.vrth_world_box_records.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                             C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-        self._L.vrt_patch_plan_box.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(Patch)]
         lo3, hi3 = (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi])
         plan = Patch()
         while max_depth >= 1:
@@ -1795,7 +1739,6 @@ class Context:
 
     def set_tile_scheduling(self, period):
         """Feedback scheduling of the tracing kernel's tiles (vrt_set_tile_scheduling): 0 = off, default 16."""
-        self._L.vrt_set_tile_scheduling.argtypes = [C.c_void_p, C.c_int]
         self._chk(self._L.vrt_set_tile_scheduling(self._h, period))
 
     def sched_order(self, stream=None, cap=1 << 20):
@@ -1899,7 +1842,6 @@ class Multi:
 
     def dispatch_frame(self, width, height, mode, d_shown):
         """vrt_multi_dispatch_frame: the displayed frame (trace + display pass in row bands with a halo) into d_shown on device 0"""
-        self._L.vrt_multi_dispatch_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         r = self._L.vrt_multi_dispatch_frame(self._h, width, height, mode, C.c_void_p(d_shown))
         if r != 0:
             raise VrtError(f"vrt_multi_dispatch_frame failed ({r}): {self._L.vrt_multi_last_error(self._h).decode()}")
