@@ -798,8 +798,8 @@ int vrt_accum_resolve_hdr_shown_device(vrt_ctx *ctx, const vrt_tonemap *tm, void
  *            ray of comp:524. Three signed integer sums.
  *   albedo   the four bytes of surfaceColor (comp:505-507): the hit leaf's R, G, B, A, or the previous voxel's where the hit leaf's
  *            alpha is 0; where the hit cell is the highlighted voxel (vrt_params) R, G, B become 255 - byte and A 255. Four
- *            unsigned integer sums. Alpha below 1 shows glass: through glass the guide is the glass surface, no refraction is
- *            followed.
+ *            unsigned integer sums. Alpha below 1 shows glass: by default the guide through glass is the glass surface and no
+ *            refraction is followed; vrt_set_guide_glass (below) follows it.
  *   depth    the float32 distance from the sample's ray origin to the hit point in world units: with p = hitPoint, each component
  *            divided by u_voxelScale only when the scale is not 1, and o the ray's origin, d = sqrtf((dx*dx + dy*dy) + dz*dz) of
  *            p - o, every operation rounded on its own; then h(d) = min(max(0, d), 65504.0f) as in vrt_accum_keep_hdr point 1,
@@ -836,7 +836,44 @@ int vrt_accum_resolve_hdr_shown_device(vrt_ctx *ctx, const vrt_tonemap *tm, void
  * un-normalised or axis-parallel directions behave as there. Any output may be NULL, not all. Errors: those of vrt_shade_rays.
  * vrt_guide_rays: HOST buffers, synchronous; vrt_guide_rays_device: DEVICE buffers, enqueued on `stream` (NULL: the context's).
  * Unlike vrt_shade_rays they take no profiling slot (vrt_set_profiling) and do not count towards its stride.
- * Not provided: guides past glass (the first opaque hit along the refracted ray), motion vectors, frames, views, shards, vrt_multi. */
+ *
+ * Guides past glass: vrt_set_guide_glass(ctx, 1) makes a guide sample follow the refracted ray through translucent surfaces to the
+ * first opaque one, at most VRT_GUIDE_MAX_SURFACES surfaces in all. `on` is 0 (the default: everything above) or 1, VRT_E_INVALID
+ * otherwise. It is context state: an accumulation reads it at vrt_accum_begin*, as vrt_accum_keep_hdr is read, and every call that
+ * brings that accumulation's guide state up to date -- vrt_accum_guides*, vrt_accum_resolve_hdr_filtered*, ..._filtered_var*,
+ * ..._temporal*, ..._temporal_mom* -- uses the rule as begun, so one guide state never mixes the two rules; a change takes effect at
+ * the next begin and is no part of the restart rule. vrt_guide_rays and vrt_guide_rays_device read it at the call. Frames, views,
+ * shards and vrt_multi ignore it. One sample's guide, every float operation float32 with no contraction:
+ *   G0  Segment 0 is the sample's own ray exactly as above: the origin, the start medium read from the leaf at the origin, the
+ *       normalised direction. S = 0, L = 0.0f.
+ *   G1  March the segment with the frame's own march. A miss on any segment makes the sample a miss: it adds nothing to any sum,
+ *       whatever glass it passed -- sky seen through glass has coverage 0, as sky seen directly has.
+ *   G2  On a hit take the normal (comp:497, before the flip), the four surfaceColor bytes b (comp:505-507) and the highlighted
+ *       voxel's inversion, all exactly as above. d_j = sqrtf((dx*dx + dy*dy) + dz*dz) of p - o in world units: p the hit point, each
+ *       component divided by u_voxelScale only when the scale is not 1; o the segment's origin, the ray's own for segment 0 and for
+ *       later segments the grid-space origin of G5 divided in the same way. L = L + d_j. If S == 0, A0 = the alpha byte of b.
+ *       S = S + 1.
+ *   G3  If the alpha byte of b is 255 the chain ends here, on an opaque surface.
+ *   G4  Otherwise, if S == VRT_GUIDE_MAX_SURFACES, the chain ends here, on glass.
+ *   G5  Otherwise comp:547-572 as VRT_MODE_FULL has it: the alpha-0 rules for the hit and the previous voxel's properties (the
+ *       latter with this segment's medium), n1 and n2, the normal flipped and n1, n2 swapped when dot(inc, normal) > 0, refr_dir =
+ *       refract(inc, normal, n1 / n2), R0 = (n1 - n2) / (n1 + n2) * (n1 - n2) / (n1 + n2), fres = clamp(R0 + (1 - R0) *
+ *       pow(1 - max(0, dot(-inc, normal)), 5), 0, 1) with the shader's deterministic pow, has_tir = length(refr_dir) < 0.001f,
+ *       reflect_i = fres, refract_i = has_tir ? 0 : 1 - fres. Where reflect_i <= 0.001f or refract_i <= 0.001f the shader shades
+ *       this surface and spawns nothing: the chain ends here, on glass. (The shader's full-stack test is no part of the rule: a guide
+ *       has no stack.) Otherwise the next segment starts at hitPoint - normal * 1e-4f (grid units) along refr_dir, as given, in
+ *       medium n2, whose byte is rint(n2 * 85); go to G1.
+ *   G6  The sample is a hit: the normal, R, G and B are the final surface's, A = A0, the first surface's alpha byte, and the depth
+ *       is h(L), the length of the bent path. A is 255 where the pixel sees its surface directly and the glass's alpha where it sees
+ *       it through glass, so an albedo distance still separates "through the pane" from "beside the pane", whose radiance differs
+ *       by the pane's tint, while R, G, B, the normal and the depth separate the objects behind it.
+ * The sums, the 40-byte state, the resolve and the hit count are those above. With the setting off, or where no segment-0 hit is
+ * translucent, G0-G6 give the guide above bit for bit. For vrt_temporal_hdr* the depth plane then places a pixel's point at
+ * origin + dir * L, the unfolded path: exact where nothing refracts, approximate behind a pane.
+ * Not provided: following reflections, a per-surface tint plane, exact reprojection through refraction, motion vectors, frames,
+ * views, shards, vrt_multi. */
+#define VRT_GUIDE_MAX_SURFACES 8
+int vrt_set_guide_glass(vrt_ctx *ctx, int on);
 int vrt_accum_guides(vrt_ctx *ctx, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage);
 int vrt_accum_guides_device(vrt_ctx *ctx, void *d_normal, void *d_albedo, void *d_depth, void *d_coverage, void *stream);
 int vrt_guide_rays(vrt_ctx *ctx, size_t n, const float *origins, int origin_stride, const float *dirs, int width, float *out_normal,
@@ -901,7 +938,7 @@ int vrt_guide_rays_device(vrt_ctx *ctx, size_t n, const void *d_origins, int ori
  * The accumulation forms read and write no byte of the accumulation's sums: vrt_accum_resolve*, vrt_accum_resolve_hdr* and
  * vrt_accum_guides* return the same bits with and without them. None of these calls takes a profiling slot or counts towards the
  * stride. Per-sample second moments of the HDR sums: vrt_accum_keep_moments below, whose plane vrt_filter_hdr_var's variance input
- * takes. Not provided: motion vectors of moving geometry, guides past glass, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
+ * takes. Not provided: motion vectors of moving geometry, frames, views, shards and vrt_multi, and a filtered form of vrt_shade_rays_hdr
  * (an image-shaped batch can call vrt_filter_hdr with vrt_guide_rays_device's planes and a coverage plane made of its hit bytes). */
 #define VRT_FILTER_MAX_LEVELS 8
 #define VRT_FILTER_DEMODULATE 1u

@@ -65,6 +65,11 @@ between them (guide_per_sample_ms), and beside it one vrt_accum_add of as many s
 
     python3 tools/accum_rate.py --guides --scenes dragon_1080p room_inside_1080p --samples 16 --out profiles/guides_rate.jsonl
 
+--glass (with --guides) measures every row twice in the same process, with guides past glass off and on (vrt_set_guide_glass, read by
+the begin; "glass": false / true in the row), the plain form first:
+
+    python3 tools/accum_rate.py --guides --glass --scenes room_inside_1080p lamp_room_1080p --samples 16 --out profiles/guides_glass_rate.jsonl
+
 --moments measures accumulations that keep luminance moments (vrt_accum_keep_moments) beside the same HDR accumulations without, in
 the same process: on each scene of --scenes, VRT_MODE_FULL at each --path-depth (default 1), from the corner and jittered, the wall time
 of one add of --samples samples each way, alternated (hdr_add_ms, moments_add_ms, their per-sample times and ratio), of one
@@ -124,6 +129,7 @@ def main():
     ap.add_argument("--variant", type=int, default=None, metavar="V",
                     help="with --path-depth: the traversal variant (vrt_set_variant; 1: the record-array kernels), recorded as variant")
     ap.add_argument("--guides", action="store_true", help="the guide planes beside primary-mode adds (see above)")
+    ap.add_argument("--glass", action="store_true", help="with --guides: each row with guides past glass off and on (see above)")
     ap.add_argument("--moments", action="store_true", help="HDR accumulations with luminance moments beside those without (see above)")
     ap.add_argument("--scenes", nargs="+", default=DEFAULT_SCENES, choices=sorted(SCENES))
     ap.add_argument("--samples", nargs="+", type=int, default=list(SAMPLES), metavar="N", help="samples per timed add")
@@ -138,6 +144,8 @@ def main():
         ap.error("--emit-power goes with --emit")
     if args.emit_mis and not args.emit_power:
         ap.error("--emit-mis goes with --emit-power")
+    if args.glass and not args.guides:
+        ap.error("--glass goes with --guides")
     V = vrt_import.vrt()
     if args.adaptive:
         return adaptive_main(V, args)
@@ -271,10 +279,13 @@ def main():
 def _scenes(V, ctx, W, H, names=DEFAULT_SCENES):
     from conftest import MAPS, room_world
     for name, (m, pos, yaw, pitch) in SCENES.items():
-        if name not in names or name not in DEFAULT_SCENES:
+        if name not in names or (name not in DEFAULT_SCENES and m != "lamp"):
             continue
         if m == "room":
             w = room_world(V)
+        elif m == "lamp":   # on request: through its pane (--guides --glass)
+            import emit_worlds
+            w = emit_worlds.lamp_room(V)
         else:
             w = V.World()
             assert w.load_vox(os.path.join(MAPS, m + ".vox"))
@@ -356,7 +367,8 @@ def guides_main(V, args):
     for name, tex in _scenes(V, ctx, W, H, args.scenes):
         for source, jitter, ln in (("corner", False, None), ("jitter", True, None), ("lens", False, lens)):
             ctx.set_lens(*(ln or (0.0, 1.0)))
-            for n in args.samples:
+            for n, glass in [(n, g) for n in args.samples for g in ((False, True) if args.glass else (False,))]:
+                ctx.set_guide_glass(glass)
                 ctx.accum_begin(W, H, 0, mode=V.MODES["primary"], jitter=jitter)
                 ctx.accum_add(n)
                 ctx.accum_guides_device(*d_planes)
@@ -374,9 +386,12 @@ def guides_main(V, args):
                        "guide_vs_primary": round((guide[0] - resolve[0]) / add[0], 3), "reps": args.reps}
                 if ln:
                     row.update(aperture=ln[0], focus=ln[1])
+                if args.glass:
+                    row["glass"] = glass
                 print(json.dumps(row), flush=True)
                 rows.append(row)
         ctx.set_lens(0.0, 1.0)
+        ctx.set_guide_glass(False)
     for d in d_planes:
         ctx.device_free(d)
     ctx.close()

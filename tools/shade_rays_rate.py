@@ -43,6 +43,12 @@ VRT_MODE_PRIMARY on the same rays -- the same march with its shading on top -- o
 1 M random rays; wall time around each call and a synchronise (the guide launches take no profiling slot):
 
     python3 tools/shade_rays_rate.py --guides --append --out profiles/guides_rate.jsonl   (after tools/accum_rate.py --guides)
+
+--glass (with --guides) measures in the lamp room of tests/emit_worlds.py instead, on 1 M rays from its eye and on 1 M rays from random
+origins inside it, and alternates a third call with them: vrt_guide_rays_device with guides past glass on (vrt_set_guide_glass, read
+at the call): glass_guide_call_ms, glass_over_plain.
+
+    python3 tools/shade_rays_rate.py --guides --glass --append --out profiles/guides_glass_rate.jsonl
 """
 import argparse
 import json
@@ -95,6 +101,7 @@ def main():
     ap.add_argument("--hdr", action="store_true", help="the HDR calls beside the plain ones (see above)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     ap.add_argument("--guides", action="store_true", help="vrt_guide_rays_device beside mode-0 vrt_shade_rays_device (see above)")
+    ap.add_argument("--glass", action="store_true", help="with --guides: in the lamp room, guides past glass beside the plain ones (see above)")
     ap.add_argument("--path-depth", nargs="+", type=int, default=None, metavar="D", help="mode 2 once per path depth (see above)")
     ap.add_argument("--sun", nargs="+", type=float, default=None, metavar="R", help="with --path-depth: once per sun disc (vrt_set_sun_disc)")
     ap.add_argument("--emit", nargs="+", type=int, default=None, choices=(0, 1), metavar="E",
@@ -113,8 +120,13 @@ def main():
         ap.error("--sun goes with --path-depth")
     if args.emit and not args.path_depth:
         ap.error("--emit goes with --path-depth")
+    if args.glass and not args.guides:
+        ap.error("--glass goes with --guides")
     V = vrt_import.vrt()
-    if args.emit:
+    if args.glass:
+        import emit_worlds
+        w = emit_worlds.lamp_room(V)
+    elif args.emit:
         import emit_worlds
         if args.emit_world == "power_room":
             import emit_power_worlds
@@ -170,15 +182,26 @@ def main():
         n_list = 1 << 20
         lo = rng.uniform((-64, -64, -64), (192, 160, 128), (n_list, 3)).astype(np.float32)
         ld = rng.normal(0, 1, (n_list, 3)).astype(np.float32)
-        for case, o, d, stride, width in (("frame_rays_1080p_dragon", origin.reshape(1, 3), dirs, 0, W),
-                                          ("random_rays_1m_dragon", lo, ld, 3, n_list)):
+        cases = (("frame_rays_1080p_dragon", origin.reshape(1, 3), dirs, 0, W), ("random_rays_1m_dragon", lo, ld, 3, n_list))
+        if args.glass:
+            eye = np.array(emit_worlds.EYE, np.float32).reshape(1, 3)
+            inside = rng.uniform((emit_worlds.LO + 1,) * 3, (emit_worlds.HI,) * 3, (n_list, 3)).astype(np.float32)
+            cases = (("eye_rays_1m_lamp_room", eye, ld, 0, n_list), ("random_rays_1m_lamp_room", inside, ld, 3, n_list))
+
+        def guide_call(glass, n, d_o, stride, d_d, outs, width):
+            ctx.set_guide_glass(glass)
+            ctx.guide_rays_device(n, d_o, stride, d_d, *outs, width=width)
+
+        for case, o, d, stride, width in cases:
             n = len(d)
             d_o, d_d = upload(o, d)
             d_rgba, d_id = ctx.device_alloc(n * 4), ctx.device_alloc(n * 8)
             d_n, d_a, d_z, d_h = ctx.device_alloc(n * 12), ctx.device_alloc(n * 16), ctx.device_alloc(n * 4), ctx.device_alloc(n)
             calls = [lambda: ctx.shade_rays_device(n, d_o, stride, d_d, d_rgba, d_id, mode=0, width=width),
-                     lambda: ctx.guide_rays_device(n, d_o, stride, d_d, d_n, d_a, d_z, d_h, width=width)]
-            ms = [[], []]
+                     lambda: guide_call(False, n, d_o, stride, d_d, (d_n, d_a, d_z, d_h), width)]
+            if args.glass:
+                calls.append(lambda: guide_call(True, n, d_o, stride, d_d, (d_n, d_a, d_z, d_h), width))
+            ms = [[] for _ in calls]
             for rep in range(args.reps + 2):   # the first two rounds: code objects
                 for i, f in enumerate(calls):
                     ctx.synchronize()
@@ -188,9 +211,15 @@ def main():
                     if rep >= 2:
                         ms[i].append((time.perf_counter() - t0) * 1e3)
             pm, gm = float(np.median(ms[0])), float(np.median(ms[1]))
-            emit({"case": case, "rays": n, "primary_call_ms": round(pm, 4), "guide_call_ms": round(gm, 4), "guide_over_primary": round(gm / pm, 3),
-                  "primary_ms_min_max": [round(min(ms[0]), 4), round(max(ms[0]), 4)], "guide_ms_min_max": [round(min(ms[1]), 4), round(max(ms[1]), 4)],
-                  "guide_rays_per_s": round(n / (gm * 1e-3)), "reps": args.reps})
+            row = {"case": case, "rays": n, "primary_call_ms": round(pm, 4), "guide_call_ms": round(gm, 4), "guide_over_primary": round(gm / pm, 3),
+                   "primary_ms_min_max": [round(min(ms[0]), 4), round(max(ms[0]), 4)], "guide_ms_min_max": [round(min(ms[1]), 4), round(max(ms[1]), 4)],
+                   "guide_rays_per_s": round(n / (gm * 1e-3)), "reps": args.reps}
+            if args.glass:
+                xm = float(np.median(ms[2]))
+                row.update(glass_guide_call_ms=round(xm, 4), glass_ms_min_max=[round(min(ms[2]), 4), round(max(ms[2]), 4)],
+                           glass_over_plain=round(xm / gm, 3))
+            emit(row)
+            ctx.set_guide_glass(False)
             for p in (d_o, d_d, d_rgba, d_id, d_n, d_a, d_z, d_h):
                 ctx.device_free(p)
         finish()

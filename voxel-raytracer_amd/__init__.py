@@ -391,6 +391,7 @@ HIP_API = {
     "vrt_accum_resolve_hdr_shown_device": (_i, [_p, _tm, _p, _p, _p]),
     "vrt_accum_guides": (_i, [_p, _p, _p, _p, _p]),
     "vrt_accum_guides_device": (_i, [_p, _p, _p, _p, _p, _p]),
+    "vrt_set_guide_glass": (_i, [_p, _i]),
     "vrt_guide_rays": (_i, _RAYS + [_i, _p, _p, _p, _p]),
     "vrt_guide_rays_device": (_i, _RAYS + [_i, _p, _p, _p, _p, _p]),
     "vrt_filter_default": (None, [_flt]),
@@ -1378,6 +1379,21 @@ class Context:
     def accum_guides_device(self, d_normal, d_albedo, d_depth, d_coverage, stream=None):
         """vrt_accum_guides_device: DEVICE buffers (H*W x 3, x 4, x 1, x 1 floats; any may be None), the resolve enqueued on `stream`"""
         self._chk(self._L.vrt_accum_guides_device(self._h, d_normal, d_albedo, d_depth, d_coverage, stream))
+
+    def set_guide_glass(self, on):
+        """Guides past glass (vrt_set_guide_glass, G0-G6 of include/vrt.h): 0 / False (default) or 1 / True. On, a guide sample
+        follows the refracted ray through translucent surfaces to the first opaque one: its normal, RGB and the bent path's length,
+        with the first surface's alpha. Read by the next accum_begin() (a change leaves an open accumulation's guides alone) and by
+        guide_rays*() at the call. Any other value raises before the library is touched and the previous one holds."""
+        _check_flag("guide glass", on, "0, 1 or a bool")
+        self._chk(self._L.vrt_set_guide_glass(self._h, int(on)))
+        self._guide_glass = bool(on)
+
+    @property
+    def guide_glass(self):
+        """The value set_guide_glass() last set through this object (False until then). A copy kept in Python: the C-ABI has a
+        setter only."""
+        return getattr(self, "_guide_glass", False)
 
     def guide_rays(self, origins, dirs, width=None):
         """First-hit guides of the caller's own rays (vrt_guide_rays), one march each. origins, dirs as in shade_rays; width: the

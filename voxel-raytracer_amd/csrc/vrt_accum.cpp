@@ -166,6 +166,7 @@ int begin(vrt_ctx *c, int width, int height, int mode, uint32_t first_sample, ui
     ac.tolerance = rule ? rule[2] : 0u;
     ac.hdr = c->accum_keep_hdr;
     ac.moments = ac.hdr && c->accum_keep_moments;
+    ac.guide_glass = c->guide_glass;
     return VRT_OK;
 }
 
@@ -230,7 +231,7 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
     }
     if (acc.guides)   // vrt_accum_guides: the samples' first hits into the guide state, none of the sums touched
         return launch::accum_guides(src, v, a, vs, vrt::guides::Args{vrt::guides::state_of(ac.d_guides.get(), (size_t)ac.width * (size_t)ac.height), acc.first, acc.n},
-                                    l, grid, s);
+                                    l, acc.glass, grid, s);
     if (acc.frame_only)   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
         return (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? launch::accum_frame_hdr(mode, v, a, vs, hf, grid, s) : hipErrorInvalidValue;
     if (mode != VRT_MODE_FULL)   // one launch, the samples looped in the lanes

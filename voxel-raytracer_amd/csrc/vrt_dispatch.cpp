@@ -384,10 +384,16 @@ long schedule(vrt_ctx *c, hipStream_t s, const Variant &v, bool accumulating, in
     return grid;
 }
 
+// Does the tree hold no translucent leaf (vrt::tree_is_opaque), derived once per tree
+bool scene_opaque(vrt_ctx *c) {
+    if (!c->scene_opaque_valid) { c->scene_opaque = vrt::tree_is_opaque(c->host_records); c->scene_opaque_valid = true; }
+    return c->scene_opaque;
+}
+
 // The full path tracer as two tile-coherent passes, where the scene and the view allow it
 bool opaque_two_pass(vrt_ctx *c, int mode, const Variant &v, const vrt::ViewSet &vs, int n_views, bool lens, const vrt::LensSel &lsel) {
     if (!(mode == VRT_MODE_FULL && c->two_pass_on && v.trav == 4 && n_views == 1 && c->variant == 0 && vs.v[0].out_rgba)) return false;
-    if (!c->scene_opaque_valid) { c->scene_opaque = vrt::tree_is_opaque(c->host_records); c->scene_opaque_valid = true; }
+    (void)scene_opaque(c);
     if (lens) return c->scene_opaque && lsel.empty;   // every origin of the lens in empty space
     const uint32_t eye_alpha = vs.v[0].eye0 >> 24, eye_b = vs.v[0].eye1 & 0xffu;
     return c->scene_opaque && eye_alpha == 0u && (eye_b == 0u || eye_b == 85u || eye_b == 255u);
@@ -465,7 +471,11 @@ int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_ro
     hipError_t e;
     if (acc) {   // progressive accumulation (vrt_accum.cpp): the frame's samples go into the context's sums
         if (mode == VRT_MODE_FULL) a.path_depth = (uint32_t)c->accum.path_depth;   // frames keep fill_scene_args()'s 1: the shader
-        e = launch_accum_step(c->accum, a, vs, v, mode, (int)grid, two_pass, lsel, *acc, s);
+        AccumStep step = *acc;
+        // guides past glass: a tree without a translucent leaf whose rays all start in empty space (trav 4) has every first hit
+        // opaque, so the chain ends on it and the plain kernels give the same planes
+        if (step.guides && step.glass && v.trav == 4 && scene_opaque(c)) step.glass = false;
+        e = launch_accum_step(c->accum, a, vs, v, mode, (int)grid, two_pass, lsel, step, s);
     } else if (two_pass && c->two_pass_form >= 5) {
         e = vrt::launch::trace_full_opaque(a, vs, (int)grid, c->two_pass_form, s, prof.ev0, prof.ev1);
     } else if (two_pass) {

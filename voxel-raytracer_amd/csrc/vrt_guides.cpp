@@ -3,7 +3,8 @@
 // pixel), which samples it still lacks, their launch through the dispatcher -- enqueue() with an AccumStep whose `guides` is set, in
 // VRT_MODE_PRIMARY, so the views, the lens selection, the variant and the frame block are those of the accumulation's own primary
 // launches -- and the resolve. For ray batches: vrt_shade_rays's arguments and staging, one launch, no state. Neither touches the
-// accumulation's sums.
+// accumulation's sums. Guides past glass (vrt_set_guide_glass): the accumulation's launches take the rule its begin read
+// (Accum::guide_glass), ray batches the context's at the call.
 #include "vrt_stage.h"
 #include "vrt_launch.h"
 
@@ -37,6 +38,7 @@ int catch_up(vrt_ctx *c, const char *what) {
     if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
     AccumStep step{ac.first + ac.guide_total, ac.total - ac.guide_total, (ac.flags & VRT_ACCUM_JITTER) != 0u, ac.lens[0], ac.lens[1]};
     step.guides = true;
+    step.glass = ac.guide_glass;
     const int r = enqueue(c, ac.width, ac.height, 0, ac.height, ac.height, 0, 0, VRT_MODE_PRIMARY, nullptr, nullptr, c->stream, nullptr, 1, &step);
     if (r) {   // what the launch left in the state is unknown
         ac.guide_epoch = 0;
@@ -76,7 +78,7 @@ int guide_batch(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride,
     fill_ray_batch_args(c, n, width, a, vs);
     vrt::guides::RayArgs q{d_origins, d_dirs, d_normal, d_albedo, d_depth, d_hit, (uint32_t)n, origin_stride, (uint32_t)width, 0u};
     const uint32_t grid = vrt::rays::plan(q.n, q.width, q.tiles_x);
-    const hipError_t e = vrt::launch::guide_rays(v, a, vs, q, grid, s);
+    const hipError_t e = vrt::launch::guide_rays(v, a, vs, q, c->guide_glass, grid, s);
     if (e != hipSuccess) return vrt_fail(c, VRT_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return VRT_OK;
 }
@@ -110,6 +112,13 @@ int vrt_accum_guides_device(vrt_ctx *c, void *d_normal, void *d_albedo, void *d_
         return resolve_into(c, static_cast<float *>(d_normal), static_cast<float *>(d_albedo), static_cast<float *>(d_depth),
                             static_cast<float *>(d_coverage), s);
     });
+}
+
+int vrt_set_guide_glass(vrt_ctx *c, int on) {
+    if (!c) return VRT_E_INVALID;
+    if (on != 0 && on != 1) return vrt_fail(c, VRT_E_INVALID, "vrt_set_guide_glass: on must be 0 or 1");
+    c->guide_glass = on == 1;
+    return VRT_OK;
 }
 
 int vrt_guide_rays(vrt_ctx *c, size_t n, const float *origins, int origin_stride, const float *dirs, int width, float *out_normal,

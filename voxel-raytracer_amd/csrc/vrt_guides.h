@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/vrt.h"   // VRT_GUIDE_MAX_SURFACES
 
 namespace vrt {
 namespace guides {

@@ -299,12 +299,14 @@ struct vrt_ctx {
         DevBuf<void> d_guides;                   // vrt_guides.h State: 40 bytes per pixel
         size_t guide_pixels = 0;                 // what it was last sized for
         DevBuf<float> d_gout;                    // vrt_accum_guides' four planes on their way to the host
+        bool guide_glass = false;                // vrt_set_guide_glass as it stood at the begin: the rule of every sample in the guide state
         DevBuf<float> d_filter;                  // vrt_accum_resolve_hdr_filtered*: mean, planes and outputs (vrt_filter.cpp declare());
                                                  // vrt_accum_resolve_hdr_temporal*: those, the integrated image and the host form's histories (vrt_temporal.cpp temporal_accum())
     };
     Accum accum;
     bool accum_keep_hdr = false;                 // vrt_accum_keep_hdr: read by the next vrt_accum_begin*
     bool accum_keep_moments = false;             // vrt_accum_keep_moments: likewise, and only where that begin keeps HDR sums
+    bool guide_glass = false;                    // vrt_set_guide_glass: read by the next vrt_accum_begin*, and by vrt_guide_rays* at the call
     const uint32_t *dbg_group_order = nullptr;  // vrt_set_tile_order: caller-owned buffers instead of the scheduler's
     uint32_t *dbg_tile_cost = nullptr;
     bool dbg_sched = false;
@@ -377,7 +379,8 @@ struct ProfSlot {
 // sample, but the mode's frame -- bytes, id_dist, float colour -- into the accumulation's buffers, for the repeat path)
 // (paths: what selects the kernels of VRT_MODE_FULL, as the add that queues the step read it)
 // (guides, in VRT_MODE_PRIMARY: not the samples' colour into the sums but their first-hit guides into the accumulation's guide
-// state, vrt_guides.cpp; jitter, aperture and focus as above, nothing else of the step is read)
+// state, vrt_guides.cpp; jitter, aperture and focus as above, nothing else of the step is read. glass: by the past-glass rule --
+// enqueue() takes the plain kernels all the same where the tree holds no translucent leaf and every origin is in empty space)
 // PathSetup: the settings that select the family of path tracer kernels of a VRT_MODE_FULL launch and fill its argument block
 // (vrt_launch.h select_paths()), as an accumulation step or a ray batch read them
 struct PathSetup {
@@ -401,6 +404,7 @@ struct AccumStep {
     bool adaptive = false, hdr = false, frame_only = false;
     PathSetup paths{};
     bool guides = false;
+    bool glass = false;             // with guides: the past-glass rule (vrt_set_guide_glass as the accumulation's begin read it)
     bool moments = false;
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,

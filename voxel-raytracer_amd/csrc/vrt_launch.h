@@ -175,10 +175,10 @@ hipError_t shade_rays_full(bool hdr, PathFamily fam, const PathArgs &pa, const V
 // whole frame into the guide state, for the ray source `src` (l: the lens of Source::kLens), `v`, `a`, `vs` and `grid` as the
 // dispatcher makes them for an accumulation's launch of VRT_MODE_PRIMARY. guides_resolve: the state -> the four float planes.
 // guide_rays: one march per ray of a caller's batch, its planes stored at once (grid = rays::plan()'s waves; `v`: the traversal only).
-hipError_t accum_guides(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const guides::Args &q, const accum::Lens &l,
+hipError_t accum_guides(accum::Source src, const Variant &v, const KArgs &a, const ViewSet &vs, const guides::Args &q, const accum::Lens &l, bool glass,
                         int grid, hipStream_t s);
 hipError_t guides_resolve(const guides::Resolve &q, hipStream_t s);
-hipError_t guide_rays(const Variant &v, const KArgs &a, const ViewSet &vs, const guides::RayArgs &q, uint32_t grid, hipStream_t s);
+hipError_t guide_rays(const Variant &v, const KArgs &a, const ViewSet &vs, const guides::RayArgs &q, bool glass, uint32_t grid, hipStream_t s);
 
 // vrt_launch_filter.hip: the guided filter and its variance-guided form (vrt_filter.hip.h), whole frames, one lane per pixel.
 // filter_prepass: the caller's guide planes -> the packed planes; filter_variance: after it, the initial variance into the packed
