@@ -85,11 +85,12 @@ def check(frame, rgba, idd, min_decided_hits, what, cap=UNDECIDED_CAP):
 
 
 def test_reference_never_touches_the_oracle_or_the_product():
-    """shader_ref64.py, path_ref64.py, lens_ref64.py and deep_ref64.py read texels, a camera block, uniforms and the context's
+    """shader_ref64.py, path_ref64.py, lens_ref64.py, deep_ref64.py and guide_ref64.py (on the first, second and third) read texels, a camera block, uniforms and the context's
     settings: they import numpy (path_ref64, lens_ref64 and deep_ref64 the first reference too, path_ref64 also deep_ref64) and
     nothing else, and name no file, library or entry point of oracle/, of the checkers or of the product's tracing."""
     for module, allowed in (("shader_ref64.py", {"numpy"}), ("path_ref64.py", {"numpy", "shader_ref64", "deep_ref64"}),
-                            ("lens_ref64.py", {"numpy", "shader_ref64"}), ("deep_ref64.py", {"numpy", "shader_ref64"})):
+                            ("lens_ref64.py", {"numpy", "shader_ref64"}), ("deep_ref64.py", {"numpy", "shader_ref64"}),
+                            ("guide_ref64.py", {"numpy", "shader_ref64", "path_ref64", "lens_ref64"})):
         _independent(module, allowed)
 
 
