@@ -36,10 +36,11 @@ dragon = tge.dragon
 class Refs(tge.Refs):
     """test_gpu_emitters.Refs whose samples are the MIS checker's: the list with its weights, and `on` naming mode and flag"""
 
-    def __init__(self, libs, O, V, world, highlighted=None):
-        super().__init__(libs[:5], O, V, world, pose=mw.POSE, lens=mw.LENS)
+    def __init__(self, libs, O, V, world, highlighted=None, pose=mw.POSE, lens=mw.LENS, W=W, H=H, bounds=()):
+        """bounds: the (world_min, world_max) of a world that does not have the default ones"""
+        super().__init__(libs[:5], O, V, world, pose=pose, lens=lens, W=W, H=H)
         self.M = libs[5]
-        self.list, self.words = op.walk(world.records()[0])
+        self.list, self.words = op.walk(world.records()[0], *bounds)
         self.weights = np.array(op.weights(self.list, self.words), np.uint64)
         self.highlighted = highlighted
         if highlighted is not None:
@@ -55,7 +56,7 @@ class Refs(tge.Refs):
         key = (source, D, radius, k, on)
         if key not in self._samples:
             o, d = self.rays(source, k)
-            self._samples[key] = self.shade(o, d, D, radius, k, on, W)
+            self._samples[key] = self.shade(o, d, D, radius, k, on, self.W)
         return self._samples[key]
 
     def mean(self, source, D, radius, first, n, on=MIS):

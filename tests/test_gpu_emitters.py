@@ -4,6 +4,8 @@ batches with sampling on, at D in {1, 3} and sun radius in {0, 0.05}, byte for b
 camera. The list itself against a Python walk after an upload, a patch and a compaction; sampling off, and sampling on in a world
 without emitters (the dragon), against oracle_sun's checker and against sampling off. Every reference sample is computed once per
 (list, ray source, D, radius, sample) and shared."""
+from functools import partial
+
 import numpy as np
 import pytest
 
@@ -22,14 +24,16 @@ W, H = ew.W, ew.H
 DEPTHS = (1, 3)
 RADII = (0.0, 0.05)
 SOURCES = {"corner": (False, False), "jitter": (True, False), "lens": (False, True)}   # jitter, lens
+ALL_SOURCES = dict(SOURCES, **{"jitter+lens": (True, True)})   # what Refs and _begin take; the tests here run SOURCES
 RULE = (2, 6, 8)   # adaptive: min, max, tolerance
 
 
 class Refs:
     """The checker's side for one world: its scene, its list, each sample's rays and each sample's result, computed once"""
 
-    def __init__(self, libs, O, V, world, pose=ew.POSE, lens=ew.LENS):
+    def __init__(self, libs, O, V, world, pose=ew.POSE, lens=ew.LENS, W=W, H=H):
         self.E, self.S, self.R, self.LL, self.HH = libs
+        self.W, self.H = W, H
         self.tex, self.dim = world.flatten()
         ip, iv, cp, _ = V.camera_block(pose[:3], pose[3], pose[4], W, H)
         self.cam = (ip, iv, cp)
@@ -40,7 +44,8 @@ class Refs:
         self._samples = {}
 
     def rays(self, source, k):
-        jitter, lens = SOURCES[source]
+        W, H = self.W, self.H
+        jitter, lens = ALL_SOURCES[source]
         key = (source, k if (jitter or lens) else 0)
         if key not in self._rays:
             if not jitter and not lens:
@@ -61,17 +66,17 @@ class Refs:
         key = (source, D, radius, k, on)
         if key not in self._samples:
             o, d = self.rays(source, k)
-            self._samples[key] = oe.shade(self.E, self.scene, o, d, D, radius, self.list if on else None, width=W, sample=k)
+            self._samples[key] = oe.shade(self.E, self.scene, o, d, D, radius, self.list if on else None, width=self.W, sample=k)
         return self._samples[key]
 
     def mean(self, source, D, radius, first, n, on=True):
         total = sum(self.sample(source, D, radius, first + k, on)[0].astype(np.uint64) for k in range(n))
         out = ((total + n // 2) // n).astype(np.uint8)
         out[:, 3] = 255
-        return out.reshape(H, W, 4)
+        return out.reshape(self.H, self.W, 4)
 
     def frame_id(self):
-        return self.sample("corner", 1, 0.0, 0)[1].reshape(H, W, 2)
+        return self.sample("corner", 1, 0.0, 0)[1].reshape(self.H, self.W, 2)
 
 
 @pytest.fixture(scope="module")
@@ -115,7 +120,7 @@ def _reset(c):
     c.set_emitter_sampling(0)
 
 
-def _same(got, ref, what):
+def _same(got, ref, what, W=W):
     got, ref = np.asarray(got), np.asarray(ref)
     assert got.shape == ref.shape, f"{what}: shape {got.shape} against {ref.shape}"
     if not np.array_equal(got, ref):
@@ -129,36 +134,37 @@ def _bits(a):
     return np.ascontiguousarray(a, F).view(np.uint32)
 
 
-def _begin(c, r, source, first=0, **kw):
-    jitter, lens = SOURCES[source]
+def _begin(c, r, source, first=0, W=W, H=H, **kw):
+    jitter, lens = ALL_SOURCES[source]
     c.set_lens(*(r.lens if lens else (0.0, 1.0)))
     c.accum_begin(W, H, first, mode=2, jitter=jitter, **kw)
 
 
-def _forms(c, r, source, D, radius, on=True):
+def _forms(c, r, source, D, radius, on=True, W=W, H=H, what=None):
     """plain, adaptive and HDR accumulations of one (source, D, radius): samples 0 .. 7 added as 3 + 5, an adaptive run of six
-    rounds, an HDR run of 1 + 2"""
-    what = f"{source} D={D} radius {radius}"
-    _begin(c, r, source)
+    rounds, an HDR run of 1 + 2; W, H: the frame r was built for; what: the name the failure messages carry"""
+    what = what or f"{source} D={D} radius {radius}"
+    same, begin = partial(_same, W=W), partial(_begin, W=W, H=H)
+    begin(c, r, source)
     assert c.accum_add(3) == 3
-    _same(c.accum_resolve()[0], r.mean(source, D, radius, 0, 3, on), f"{what} rgba8 after 3")
+    same(c.accum_resolve()[0], r.mean(source, D, radius, 0, 3, on), f"{what} rgba8 after 3")
     assert c.accum_add(5) == 8
     got = c.accum_resolve()
-    _same(got[0], r.mean(source, D, radius, 0, 8, on), f"{what} rgba8 after 3 + 5")
-    _same(got[1], r.frame_id(), f"{what} id_dist")
-    _begin(c, r, source)
+    same(got[0], r.mean(source, D, radius, 0, 8, on), f"{what} rgba8 after 3 + 5")
+    same(got[1], r.frame_id(), f"{what} id_dist")
+    begin(c, r, source)
     assert c.accum_add(8) == 8
-    _same(c.accum_resolve()[0], got[0], f"{what}: 8 in one add against 3 + 5")
-    _begin(c, r, source, adaptive=RULE)
+    same(c.accum_resolve()[0], got[0], f"{what}: 8 in one add against 3 + 5")
+    begin(c, r, source, adaptive=RULE)
     assert c.accum_add(2) == 2 and c.accum_add(4) == 6
     got = c.accum_resolve()
     counts, active = c.accum_counts()
     st = oracle_adaptive.accumulate(lambda k: r.sample(source, D, radius, k, on)[0].reshape(H, W, 4), H, W, 0, 6, RULE, np.int64)
     assert np.array_equal(counts, st.counts()), f"{what}: adaptive counts"
     assert active == int(st.active(RULE).sum())
-    _same(got[0], st.resolve(), f"{what} adaptive rgba8")
-    _same(got[1], r.frame_id(), f"{what} adaptive id_dist")
-    _begin(c, r, source, hdr=True)
+    same(got[0], st.resolve(), f"{what} adaptive rgba8")
+    same(got[1], r.frame_id(), f"{what} adaptive id_dist")
+    begin(c, r, source, hdr=True)
     assert c.accum_add(1) == 1 and c.accum_add(2) == 3
     acc = oracle_hdr.Accum(r.HH, H, W)
     for k in range(3):
@@ -166,9 +172,9 @@ def _forms(c, r, source, D, radius, on=True):
     want = acc.mean()
     for op, e in (("clamp", 1.0), ("reinhard", 1.7)):
         rgb, rgba, _ = c.accum_resolve_hdr(op, e)
-        _same(_bits(rgb), _bits(want), f"{what} float mean ({op})")
-        _same(rgba, oracle_hdr.tonemap(r.HH, want, op, e), f"{what} {op} bytes")
-    _same(c.accum_resolve()[0], r.mean(source, D, radius, 0, 3, on), f"{what} the bytes beside the floats")
+        same(_bits(rgb), _bits(want), f"{what} float mean ({op})")
+        same(rgba, oracle_hdr.tonemap(r.HH, want, op, e), f"{what} {op} bytes")
+    same(c.accum_resolve()[0], r.mean(source, D, radius, 0, 3, on), f"{what} the bytes beside the floats")
 
 
 # ---- the accumulation ----
