@@ -57,9 +57,13 @@ def refs_of(libs, O, V, case, pose=None):
     return r
 
 
-def load(c, case, r):
-    s = case.setting
+def upload(c, case):
     c.upload_octree(case.tex, case.dim)
+
+
+def settings(c, case, r):
+    """the case's camera, uniforms and scheduled setting into a context that holds its tree"""
+    s = case.setting
     c.set_camera(*r.cam)
     c.set_params(case.fill_params(c.default_params()))
     c.set_variant(s["variant"])
@@ -70,6 +74,11 @@ def load(c, case, r):
     c.set_emitter_importance(1 if s["rule"].startswith("power") else 0)
     c.set_emitter_mis(1 if s["rule"] == "power+mis" else 0)
     c.set_guide_glass(False)
+
+
+def load(c, case, r):
+    upload(c, case)
+    settings(c, case, r)
 
 
 def reset(c):
@@ -97,8 +106,10 @@ def _hdr_sums(HH, rgbs):
     return sums, mean
 
 
-def run_case(c, V, O, libs, case, report=lambda route, check: check()):
-    """every route of the sweep on one case; report(route, check) runs one route's comparison (the fuzzer's catches the assertion)"""
+def run_case(c, V, O, libs, case, report=lambda route, check: check(), resident=False):
+    """every route of the sweep on one case; report(route, check) runs one route's comparison (the fuzzer's catches the assertion);
+    resident: the context already holds the case's tree (test_gpu_edit_sessions.py runs these bodies on a tree that patches left
+    behind), only the settings are made"""
     import torch
     s, W, H, name = case.setting, case.W, case.H, case.name()
     source, D, radius, on = s["source"], s["D"], s["radius"], ON[s["rule"]]
@@ -109,7 +120,7 @@ def run_case(c, V, O, libs, case, report=lambda route, check: check()):
     same = lambda got, ref, what: tge._same(got, ref, f"{name}: {what}", W)   # noqa: E731
     device = case.index % 3 == 0
     side = torch.cuda.Stream(device="cuda:0") if device else None
-    load(c, case, r)
+    (settings if resident else load)(c, case, r)
     assert np.array_equal(c.emitters(), case.list), f"{name}: the emitter list"
 
     report("accum forms", lambda: tge._forms(c, r, source, D, radius, on, W, H, what=name))

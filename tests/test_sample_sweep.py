@@ -195,13 +195,16 @@ def _ref_world(case):
 @pytest.mark.parametrize("index", REF_INDICES)
 @pytest.mark.parametrize("family", sw.FAMILIES)
 def test_the_checkers_match_the_float64_references(PL, RL, GL, O, cases, family, index):
-    c = cases[(family, index)]
+    check_against_references(PL, RL, GL, O, cases[(family, index)], MEASURED[(family, index)])
+
+
+def check_against_references(PL, RL, GL, O, c, measured):
+    """the comparison itself, on any Case-shaped world (test_edit_sessions.py runs it on edited ones) with its measured shares"""
     s, u = c.setting, c.uniforms
     o, d = corner_rays(RL, O, c)
     what = c.name()
     world = _ref_world(c)
     scene = c.scene(O)
-    measured = MEASURED[(family, index)]
     # the path rules
     rgba, idd, rgb = checker_sample(PL, RL, O, c)
     t = PR.PathTrace.rays(world, o, d, c.W, sample=0, voxel_scale=u["voxel_scale"], global_light=u["global_light"],

@@ -440,6 +440,16 @@ TEST_API = {   # csrc/test/vrt_test.hip has no header: these rows are kept right
     "vrt_test_math": (_i, [_i, _i, _p, _p, _p, _i]),
     "vrt_test_build_layout": (_long, _TREE + [_p, _sz, C.POINTER(SceneInfo)]),
     "vrt_test_patch_check": (_long, _TREE + _TREE + _WORLD + [_i, _i, _i, _p, _sz, _p, _i]),
+    "vrt_test_extract_subtree": (_long, _TREE + [_p, _i, _p, _sz]),
+    "vrt_test_patch_session_upload": (_p, [_p] + _TREE + [_u32] + _WORLD),
+    "vrt_test_patch_session_close": (None, [_p]),
+    "vrt_test_patch_session_plan": (_i, [_p, _pi32, _pi32, _i, _p, _p]),
+    "vrt_test_patch_session_begin": (_i, [_p]),
+    "vrt_test_patch_session_end": (_i, [_p]),
+    "vrt_test_patch_session_apply": (_i, [_p, _i, _p, _p, _sz, _p]),
+    "vrt_test_patch_session_compact": (_i, [_p]),
+    "vrt_test_patch_session_counts": (None, [_p, _p]),
+    "vrt_test_patch_session_check": (_i, [_p] + _TREE + [_u32, _p, _sz, _pi32, _i, _p, _p, _p, _sz]),
     "vrt_test_ray_table": (_i, [_p, _i, _i, _p, _p, _p]),
     "vrt_test_root0": (_i, _TREE + _WORLD + [_pi32, _pi32]),
     "vrt_test_view_in_range": (_i, [_p]),
@@ -704,6 +714,139 @@ def patch_check(texels_before, texels_after, voxel, points, world_min=(-1023, -1
     if r < 0:
         raise VrtError(f"vrt_test_patch_check failed ({r})")
     return int(r), int(info[0]), int(info[1]), int(info[2]), bool(info[3])
+
+
+def subtree_records(texels, path):
+    """Host-only (vrt_test_extract_subtree): the sub-tree under the node `path` (child indices from the root) reaches in a fresh layout of
+    a texel stream, as vrt_patch_apply takes it -> uint32[n, 2]. For hand-written streams, which hold what World never emits."""
+    L = test_lib()
+    t = np.ascontiguousarray(texels, np.uint8)
+    pa = (C.c_uint8 * 16)(*list(path))
+    n = L.vrt_test_extract_subtree(t.ctypes.data, t.size, pa, len(path), None, 0)
+    if n < 0:
+        raise VrtError(f"vrt_test_extract_subtree failed ({n})")
+    out = np.zeros((n, 2), np.uint32)
+    L.vrt_test_extract_subtree(t.ctypes.data, t.size, pa, len(path), out.ctypes.data, n)
+    return out
+
+
+class PatchSession:
+    """Host-only (vrt_test_patch_session_*): one record array and one wide layout that take a whole chain of patches, batches and
+    compactions by the rules of vrt_patch.cpp, with no device. The editing methods carry Context's names and answers (patch_voxel,
+    patch_box, patch_begin, patch_end, compact, upload_octree), so that one driver serves both; check() holds the patched structures
+    to a fresh layout of a stream."""
+
+    def __init__(self, texels, tex_dim, world_min=(-1023, -1023, -1023), world_max=(1024, 1024, 1024)):
+        self._L = test_lib()
+        self._mn, self._mx = (C.c_int32 * 3)(*world_min), (C.c_int32 * 3)(*world_max)
+        self._h = None
+        self.last = (0, 0, 0)            # of the last patch: it voided the wide layout, re-pointed a cell, changed a root
+        self.upload_octree(texels, tex_dim)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.vrt_test_patch_session_close(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def upload_octree(self, texels, tex_dim):
+        t = np.ascontiguousarray(texels, np.uint8)
+        h = self._L.vrt_test_patch_session_upload(self._h, t.ctypes.data if t.size else None, t.size, int(tex_dim), self._mn, self._mx)
+        if not h:
+            raise VrtError("vrt_test_patch_session_upload failed")
+        self._h = h
+
+    def _patch(self, world, lo, hi, voxel, max_depth):
+        H = host_lib()
+        lo3, hi3 = (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi])
+        depth, path = C.c_int32(0), (C.c_uint8 * 16)()
+        while max_depth >= 1:
+            if self._L.vrt_test_patch_session_plan(self._h, lo3, hi3, max_depth, C.byref(depth), path) != 0:
+                return None
+            if H.vrth_world_node_state(world._h, path, depth.value) == 2:
+                p, n = C.c_void_p(), C.c_size_t(0)
+                if voxel:
+                    r = H.vrth_world_path_records(world._h, path, depth.value, int(lo[0]), int(lo[1]), int(lo[2]), C.byref(p), C.byref(n))
+                else:
+                    r = H.vrth_world_box_records(world._h, path, depth.value, lo3, hi3, C.byref(p), C.byref(n))
+                if r != 0:
+                    return None
+                info = (C.c_uint32 * 3)()
+                try:
+                    r = self._L.vrt_test_patch_session_apply(self._h, depth.value, path, p, n.value, info)
+                finally:
+                    H.vrth_free(p)
+                if r != 0:
+                    raise VrtError(f"vrt_test_patch_session_apply failed ({r})")
+                self.last = tuple(int(v) for v in info)
+                return depth.value
+            max_depth = depth.value - 1
+        return None
+
+    def patch_voxel(self, world, x, y, z, max_depth=15):
+        return self._patch(world, (x, y, z), (x, y, z), True, max_depth)
+
+    def plan(self, x, y, z, max_depth=15):
+        """vrt_patch_plan's answer for a voxel -> the path (a list of child indices), or None"""
+        p3 = (C.c_int32 * 3)(int(x), int(y), int(z))
+        depth, path = C.c_int32(0), (C.c_uint8 * 16)()
+        if self._L.vrt_test_patch_session_plan(self._h, p3, p3, max_depth, C.byref(depth), path) != 0:
+            return None
+        return list(path[:depth.value])
+
+    def apply(self, path, records):
+        """vrt_patch_apply with a caller's sub-tree records -> (it voided the wide layout, re-pointed a cell, changed a root)"""
+        r = np.ascontiguousarray(records, np.uint32).reshape(-1, 2)
+        info = (C.c_uint32 * 3)()
+        self._chk(self._L.vrt_test_patch_session_apply(self._h, len(path), (C.c_uint8 * 16)(*path), r.ctypes.data, r.shape[0], info), "apply")
+        self.last = tuple(int(v) for v in info)
+        return self.last
+
+    def patch_box(self, world, lo, hi, max_depth=15):
+        return self._patch(world, lo, hi, False, max_depth)
+
+    def _chk(self, r, what):
+        if r != 0:
+            raise VrtError(f"vrt_test_patch_session_{what} failed ({r})")
+
+    def patch_begin(self):
+        self._chk(self._L.vrt_test_patch_session_begin(self._h), "begin")
+
+    def patch_end(self):
+        self._chk(self._L.vrt_test_patch_session_end(self._h), "end")
+
+    def compact(self):
+        self._chk(self._L.vrt_test_patch_session_compact(self._h), "compact")
+
+    def counts(self):
+        """-> dict(n_records, compactions, peak_records, n_cells)"""
+        out = np.zeros(4, np.uint64)
+        self._L.vrt_test_patch_session_counts(self._h, out.ctypes.data)
+        return dict(n_records=int(out[0]), compactions=int(out[1]), peak_records=int(out[2]), n_cells=int(out[3]))
+
+    def scene_info(self):
+        return {"n_records": self.counts()["n_records"]}
+
+    def check(self, texels, tex_dim, points, eye, stale=False):
+        """the patched structures against a fresh layout of `texels` -> dict; list, cdf: the patched array's emitter list and thresholds;
+        repointed: the last patch re-pointed a cell or a root and the layout was not rebuilt since; stale: with that cell or root at
+        its old value (what bad_cells is there to notice)"""
+        t = np.ascontiguousarray(texels, np.uint8)
+        pts = np.ascontiguousarray(points, np.int32).reshape(-1, 3)
+        out = np.zeros(28, np.uint32)
+        probe = np.zeros(28, np.uint32)
+        args = (self._h, t.ctypes.data if t.size else None, t.size, int(tex_dim), pts.ctypes.data if len(pts) else None, len(pts),
+                (C.c_int32 * 3)(*[int(v) for v in eye]), 1 if stale else 0)
+        self._chk(self._L.vrt_test_patch_session_check(*args, probe.ctypes.data, None, None, 0), "check")
+        n = int(probe[5])
+        lst, cdf = np.zeros((n, 4), np.int32), np.zeros(n, np.uint32)
+        self._chk(self._L.vrt_test_patch_session_check(*args, out.ctypes.data, lst.ctypes.data if n else None, cdf.ctypes.data if n else None, n),
+                  "check")
+        o = [int(v) for v in out]
+        return dict(bad_cells=o[0], bad_records=o[1], opaque=(bool(o[2]), bool(o[3])), emitters_equal=bool(o[4]), n_emitters=(o[5], o[6]),
+                    wide=bool(o[7]), root0=(tuple(o[8:14]), tuple(o[14:20])), texels=(o[20], o[21]), tex_dim=(o[22], o[23]),
+                    live_records=o[24], n_records=o[25], fresh_records=o[26], repointed=bool(o[27]), list=lst, cdf=cdf)
 
 
 def ray_table(inv_projection, width, height):

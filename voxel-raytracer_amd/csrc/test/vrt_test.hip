@@ -11,6 +11,7 @@
 // libvrt_hip.so exports none of this (tests/test_abi.py checks that).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -514,6 +515,295 @@ long vrt_test_patch_check(const uint8_t *before, size_t before_bytes, const uint
         }
     }
     return bad;
+}
+
+// Host-only check of a CHAIN of edits (no device): vrt_test_patch_check lays both trees out afresh at every step; a session lays the
+// first stream out once and then takes every patch, batch and compaction on the SAME records and wide layout, by the rules of
+// vrt_patch.cpp restated on host structures alone (patch_host(), patch_device()'s bookkeeping, vrt_patch_plan_box() with its own
+// compaction, vrt_compact(), ensure_analysis()). The sub-trees come from the caller (vrth_world_path_records / vrth_world_box_records).
+struct PatchSession {
+    std::vector<vrt::Record> records;
+    vrt::WideTree wide;
+    int wmin[3], wmax[3];
+    bool analysis_valid = false, wide_ok = false;
+    size_t uploaded_records = 0, stream_texels = 0;
+    uint32_t tex_dim = 1;
+    bool dim_from_texels = false;
+    bool open = false, dirty = false, wide_invalid = false;   // the batch
+    long texel_delta = 0;
+    uint32_t compactions = 0;                                 // all of them, vrt_patch_plan_box's own included
+    size_t peak_records = 0;
+    // the one cell (last_cell >= 0) or root table entry (last_root >= 0) the last patch re-pointed, with the value it had before:
+    // what a device copy that was never made would leave (vrt_test_patch_session_check's `stale`); void once the layout is rebuilt
+    long last_cell = -1, last_root = -1;
+    vrt::WideCell old_cell{0u, 0u};
+    uint32_t old_root = 0;
+};
+
+static uint32_t session_dim_of_texels(size_t texels) {   // vrt_scene.cpp dim_of_texels(): ceil(cbrt()), at least 1
+    const size_t d = (size_t)ceil(cbrt((double)texels));
+    return (uint32_t)(d == 0 ? 1 : d);
+}
+
+static void session_ensure(PatchSession *s) {   // ensure_analysis()
+    if (s->analysis_valid) return;
+    std::string why;
+    s->wide_ok = !vrt::has_unit_internal_node(s->records, s->wmin, s->wmax) && vrt::build_wide(s->records, s->wmin, s->wmax, s->wide, why);
+    s->last_cell = s->last_root = -1;
+    s->analysis_valid = true;
+}
+
+static void session_compact(PatchSession *s) {   // vrt_compact()
+    vrt::compact_records(s->records);
+    s->uploaded_records = s->records.size();
+    s->analysis_valid = false;
+    ++s->compactions;
+}
+
+static void session_end(PatchSession *s) {   // patch_device(): what it keeps in the context beside the copies
+    const bool was_dirty = s->dirty, invalid = s->wide_invalid;
+    const long delta = s->texel_delta;
+    s->open = s->dirty = s->wide_invalid = false;
+    s->texel_delta = 0;
+    if (!was_dirty) return;
+    s->stream_texels = (size_t)((long)s->stream_texels + delta);
+    if (s->dim_from_texels) s->tex_dim = session_dim_of_texels(s->stream_texels);
+    if (s->wide_ok && invalid) s->analysis_valid = false;
+}
+
+// Host-only: the sub-tree under the node reached by `depth` child indices in a fresh layout of a stream, as vrt_patch_apply takes it
+// (vrt::extract_subtree): hand-written streams hold what the host library never emits. -> the record count (the first min(count,
+// cap) records in out), or a negative code.
+long vrt_test_extract_subtree(const uint8_t *texels, size_t used_bytes, const uint8_t *path, int depth, uint32_t *out, size_t cap) {
+    if (!path || depth < 1 || depth > 15 || (cap && !out)) return VRT_E_INVALID;
+    vrt::Layout lay;
+    std::string err;
+    if (!vrt::build_layout(texels, used_bytes, lay, err)) return VRT_E_MALFORMED;
+    std::vector<vrt::Record> sub;
+    if (!vrt::extract_subtree(lay.records, path, depth, sub)) return VRT_E_STATE;
+    for (size_t i = 0; i < sub.size() && i < cap; ++i) { out[2 * i] = sub[i].w0; out[2 * i + 1] = sub[i].w1; }
+    return (long)sub.size();
+}
+
+// (re)starts the session from a full upload of this stream (vrt_upload_octree); h = NULL: a new session. NULL when malformed.
+void *vrt_test_patch_session_upload(void *h, const uint8_t *texels, size_t used_bytes, uint32_t tex_dim, const int32_t wmin[3],
+                                    const int32_t wmax[3]) {
+    if (!wmin || !wmax) return nullptr;
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (s && s->open) return nullptr;
+    vrt::Layout lay;
+    std::string err;
+    if (!vrt::build_layout(texels, used_bytes, lay, err)) return nullptr;
+    if (!s) s = new PatchSession();
+    for (int k = 0; k < 3; ++k) { s->wmin[k] = wmin[k]; s->wmax[k] = wmax[k]; }
+    s->records.swap(lay.records);
+    s->uploaded_records = s->records.size();
+    s->stream_texels = used_bytes / 4;
+    s->tex_dim = tex_dim ? tex_dim : 1;
+    s->dim_from_texels = s->tex_dim == session_dim_of_texels(s->stream_texels);
+    s->analysis_valid = false;
+    if (s->records.size() > s->peak_records) s->peak_records = s->records.size();
+    return s;
+}
+
+void vrt_test_patch_session_close(void *h) { delete static_cast<PatchSession *>(h); }
+
+// vrt_patch_plan_box(): 0 and the plan, or VRT_E_STATE when the edit needs a full upload
+int vrt_test_patch_session_plan(void *h, const int32_t lo[3], const int32_t hi[3], int max_depth, int32_t *depth_out, uint8_t path_out[16]) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (!s || !lo || !hi || !depth_out || !path_out || lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2]) return VRT_E_INVALID;
+    session_ensure(s);
+    if (!s->open && s->records.size() > 2 * s->uploaded_records + (1u << 12)) {
+        session_compact(s);
+        session_ensure(s);
+    }
+    const int p[3] = {lo[0], lo[1], lo[2]};
+    int md = max_depth > 15 ? 15 : max_depth;
+    while (md >= 1) {
+        vrt::PatchSite site;
+        if (!vrt::plan_patch(s->records, s->wide, s->wide_ok && !s->wide_invalid, s->wmin, s->wmax, p, md, site)) break;
+        int mn[3], mx[3];
+        for (int k = 0; k < 3; ++k) { mn[k] = s->wmin[k]; mx[k] = s->wmax[k]; }
+        for (int d = 0; d < site.depth; ++d)
+            for (int k = 0; k < 3; ++k) {
+                const int mid = mn[k] + ((mx[k] - mn[k]) >> 1);
+                if ((site.path[d] >> (2 - k)) & 1u) mn[k] = mid; else mx[k] = mid;
+            }
+        if (hi[0] < mx[0] && hi[1] < mx[1] && hi[2] < mx[2] && hi[0] >= mn[0] && hi[1] >= mn[1] && hi[2] >= mn[2]) {
+            *depth_out = site.depth;
+            std::memcpy(path_out, site.path, 16);
+            return VRT_OK;
+        }
+        md = site.depth - 1;
+    }
+    return VRT_E_STATE;
+}
+
+int vrt_test_patch_session_begin(void *h) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (!s || s->open) return VRT_E_STATE;
+    session_ensure(s);
+    s->open = true;
+    s->dirty = s->wide_invalid = false;
+    s->texel_delta = 0;
+    return VRT_OK;
+}
+
+int vrt_test_patch_session_end(void *h) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (!s || !s->open) return VRT_E_STATE;
+    session_end(s);
+    return VRT_OK;
+}
+
+// vrt_patch_apply() with patch_host()'s batch rule. info (optional): [0] the patch voided the wide layout, [1] a cell was re-pointed,
+// [2] a root changed.
+int vrt_test_patch_session_apply(void *h, int depth, const uint8_t path[16], const uint32_t *sub, size_t n_sub, uint32_t info[3]) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (!s || !path || !sub || depth < 1 || depth > 15) return VRT_E_INVALID;
+    const bool single = !s->open;
+    if (single) { const int r = vrt_test_patch_session_begin(h); if (r) return r; }
+    int lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { lo[k] = s->wmin[k]; hi[k] = s->wmax[k]; }
+    for (int d = 0; d < depth; ++d) {
+        if (path[d] > 7) { if (single) s->open = false; return VRT_E_INVALID; }
+        for (int k = 0; k < 3; ++k) {
+            const int mid = lo[k] + ((hi[k] - lo[k]) >> 1);
+            if ((path[d] >> (2 - k)) & 1u) lo[k] = mid; else hi[k] = mid;
+        }
+    }
+    const bool wide_now = s->wide_ok && !s->wide_invalid;
+    vrt::PatchSite site;
+    vrt::PatchRanges rg;
+    std::string why;
+    if (!vrt::plan_patch(s->records, s->wide, wide_now, s->wmin, s->wmax, lo, depth, site) || site.depth != depth ||
+        std::memcmp(site.path, path, (size_t)depth) != 0) { if (single) s->open = false; return VRT_E_STATE; }
+    vrt::WideCell old_cell{0u, 0u};
+    uint32_t old_root = 0;
+    const size_t at = (size_t)site.parent_node * 64 + site.parent_cell;
+    if (wide_now && site.root_index >= 0) old_root = s->wide.roots[(size_t)site.root_index].node;
+    else if (wide_now && at < s->wide.cells.size()) old_cell = s->wide.cells[at];
+    if (!vrt::apply_patch(s->records, s->wide, wide_now, site, reinterpret_cast<const vrt::Record *>(sub), n_sub, rg, why)) {
+        if (single) s->open = false;
+        return VRT_E_MALFORMED;
+    }
+    s->dirty = true;
+    s->texel_delta += rg.texel_delta;
+    if (info) { info[0] = rg.wide_invalid ? 1u : 0u; info[1] = rg.cell_repointed ? 1u : 0u; info[2] = (wide_now && site.root_index >= 0) ? 1u : 0u; }
+    if (wide_now) {
+        s->wide_invalid = s->wide_invalid || rg.wide_invalid;
+        if (!rg.wide_invalid && site.root_index >= 0 && s->wide.roots[(size_t)site.root_index].node != old_root) {
+            s->last_root = site.root_index; s->last_cell = -1; s->old_root = old_root;
+        } else if (!rg.wide_invalid && rg.cell_repointed) {
+            s->last_cell = (long)at; s->last_root = -1; s->old_cell = old_cell;
+        }
+    }
+    if (s->records.size() > s->peak_records) s->peak_records = s->records.size();
+    if (single) session_end(s);
+    return VRT_OK;
+}
+
+int vrt_test_patch_session_compact(void *h) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (!s || s->open) return VRT_E_STATE;
+    session_compact(s);
+    return VRT_OK;
+}
+
+// counters: [0] records now, [1] compactions so far, [2] the largest record count so far, [3] wide cells now
+void vrt_test_patch_session_counts(void *h, uint64_t out[4]) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    out[0] = s->records.size(); out[1] = s->compactions; out[2] = s->peak_records; out[3] = s->wide.cells.size();
+}
+
+// The patched structures, as the next dispatch would find them, against a fresh layout of `after`, on n points and for an eye cell:
+// out[0] points that differ through the cells (0xffffffff: one side has a wide layout and the other none), [1] through the records
+// alone, [2] / [3] tree_is_opaque patched / fresh, [4] 1 when emitter list and thresholds are equal, [5] / [6] their lengths,
+// [7] 1 when both have a wide form, [8..13] / [14..19] vrt_test_root0's six findings patched / fresh, [20] / [21] tracked and actual
+// texel count, [22] / [23] tracked u_texDim and after_dim, [24] live records, [25] all records, [26] the fresh layout's, [27] 1 when
+// the last patch re-pointed a cell or a root and the layout has not been rebuilt since. With list_out / cdf_out (cap entries): the
+// patched array's emitter list and thresholds. stale = 1: the comparison is made with that cell or root at its value from before the
+// patch -- the sensitivity check of out[0].
+int vrt_test_patch_session_check(void *h, const uint8_t *after, size_t after_bytes, uint32_t after_dim, const int32_t *points, size_t n,
+                                 const int32_t eye[3], int stale, uint32_t out[28], int32_t *list_out, uint32_t *cdf_out, size_t cap) {
+    PatchSession *s = static_cast<PatchSession *>(h);
+    if (!s || !eye || !out || (n && !points) || s->open) return VRT_E_INVALID;
+    vrt::Layout la;
+    std::string err;
+    if (!vrt::build_layout(after, after_bytes, la, err)) return VRT_E_MALFORMED;
+    session_ensure(s);
+    out[27] = (s->wide_ok && (s->last_cell >= 0 || s->last_root >= 0)) ? 1u : 0u;
+    struct Swap {   // the stale value in for the length of the check
+        PatchSession *s; bool on;
+        void flip() {
+            if (!on) return;
+            if (s->last_cell >= 0) std::swap(s->wide.cells[(size_t)s->last_cell], s->old_cell);
+            else std::swap(s->wide.roots[(size_t)s->last_root].node, s->old_root);
+        }
+        ~Swap() { flip(); }
+    } swap{s, stale && out[27]};
+    swap.flip();
+    vrt::WideTree wa;
+    const bool wide_a = !vrt::has_unit_internal_node(la.records, s->wmin, s->wmax) && vrt::build_wide(la.records, s->wmin, s->wmax, wa, err);
+    const vrt::WideTree none;
+    uint32_t bad_cells = 0, bad_records = 0;
+    for (size_t i = 0; i < n; ++i)
+        for (int pass = 0; pass < 2; ++pass) {
+            if (pass == 0 && !(s->wide_ok && wide_a)) continue;
+            uint32_t a0, a1, b0, b1;
+            int amn[3], amx[3], bmn[3], bmx[3];
+            const int ka = vrt::wide_find_host(s->records, pass == 0 ? s->wide : none, s->wmin, s->wmax, points + 3 * i, a0, a1, amn, amx);
+            const int kb = vrt::wide_find_host(la.records, pass == 0 ? wa : none, s->wmin, s->wmax, points + 3 * i, b0, b1, bmn, bmx);
+            bool same = ka == kb && a0 == b0 && a1 == b1;
+            for (int k = 0; k < 3; ++k) same = same && amn[k] == bmn[k] && amx[k] == bmx[k];
+            if (!same) ++(pass == 0 ? bad_cells : bad_records);
+        }
+    out[0] = s->wide_ok == wide_a ? bad_cells : 0xffffffffu;
+    out[1] = bad_records;
+    out[2] = vrt::tree_is_opaque(s->records) ? 1u : 0u;
+    out[3] = vrt::tree_is_opaque(la.records) ? 1u : 0u;
+    std::vector<int32_t> lp, lf;
+    std::vector<uint32_t> wp, wf, cp, cf;
+    std::vector<uint64_t> weights;
+    emitter_walk(s->records, s->wmin, s->wmax, 1u << 20, lp, &wp);
+    emitter_weights(lp, wp, weights);
+    emitter_cdf(weights, cp);
+    emitter_walk(la.records, s->wmin, s->wmax, 1u << 20, lf, &wf);
+    emitter_weights(lf, wf, weights);
+    emitter_cdf(weights, cf);
+    out[4] = (lp == lf && cp == cf) ? 1u : 0u;
+    out[5] = (uint32_t)cp.size();
+    out[6] = (uint32_t)cf.size();
+    for (size_t i = 0; i < cp.size() && i < cap; ++i) {
+        if (list_out) std::memcpy(list_out + 4 * i, lp.data() + 4 * i, 4 * sizeof(int32_t));
+        if (cdf_out) cdf_out[i] = cp[i];
+    }
+    const bool both = s->wide_ok && wide_a && !s->wide.roots.empty() && !wa.roots.empty();
+    out[7] = both ? 1u : 0u;
+    for (int side = 0; side < 2; ++side) {
+        uint32_t *o = out + 8 + 6 * side;
+        for (int k = 0; k < 6; ++k) o[k] = 0;
+        if (!both) continue;
+        const vrt::WideTree &wt = side ? wa : s->wide;
+        const std::vector<vrt::Record> &recs = side ? la.records : s->records;
+        uint32_t node = wt.roots[0].node;
+        int shift = wt.roots[0].shift, mn[3] = {wt.roots[0].origin[0], wt.roots[0].origin[1], wt.roots[0].origin[2]};
+        o[5] = (uint32_t)shift;
+        o[0] = vrt::content_only_in_root0(recs, wt) ? 1u : 0u;
+        const int eyes[1][3] = {{eye[0], eye[1], eye[2]}};
+        if (o[0]) vrt::tighten_root0(wt, eyes, 1, vrt::v3::kAnchorShift, node, shift, mn);
+        o[1] = (uint32_t)shift; o[2] = (uint32_t)mn[0]; o[3] = (uint32_t)mn[1]; o[4] = (uint32_t)mn[2];
+    }
+    out[20] = (uint32_t)s->stream_texels;
+    out[21] = (uint32_t)(after_bytes / 4);
+    out[22] = s->tex_dim;
+    out[23] = after_dim;
+    std::vector<vrt::Record> live(s->records);
+    vrt::compact_records(live);
+    out[24] = (uint32_t)live.size();
+    out[25] = (uint32_t)s->records.size();
+    out[26] = (uint32_t)la.records.size();
+    return VRT_OK;
 }
 
 // Host-only: what the dispatcher concludes about a tree before it runs VRT_MODE_FULL without a ray stack (vrt::tree_is_opaque):
