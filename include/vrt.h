@@ -1227,6 +1227,106 @@ int vrt_accum_resolve_hdr_temporal_mom(vrt_ctx *ctx, const vrt_temporal_mom *t, 
 int vrt_accum_resolve_hdr_temporal_mom_device(vrt_ctx *ctx, const vrt_temporal_mom *t, const vrt_filter_var *f, const vrt_tonemap *tm,
                                               const void *d_history_in, void *d_history_out, void *d_integrated, void *d_rgb,
                                               void *d_rgba8, void *d_variance_out, void *stream);
+/* EXTENSION: guided upsampling -- radiance traced at 1 / r of the resolution (r = 1 .. VRT_UPSAMPLE_MAX_FACTOR in each direction)
+ * and rebuilt at full size by a joint bilateral upsample that FULL-resolution guide planes steer. A march is about a hundred times
+ * cheaper than a shaded sample, so the full-size planes cost little; the pass runs on the albedo-divided image, so per-voxel colour
+ * comes back at full sharpness; and the caller gets a mask of the pixels that could not be rebuilt, which vrt_shade_rays_hdr can
+ * shade exactly. Three families of calls: the guide planes of a frame (vrt_guide_frame*), the pass (vrt_upsample_hdr*), and the pass
+ * on an HDR accumulation (vrt_accum_resolve_hdr_upsampled*).
+ *
+ * vrt_guide_frame         the guide planes of ONE sample per pixel through the pixel's corner ray (the frame's own ray, offset 0) of a
+ *                         width x height frame, from the context's current camera, uniforms and tree, in the shapes
+ *                         vrt_accum_guides* writes; vrt_set_guide_glass is read at the call, as vrt_guide_rays reads it. By
+ *                         definition the planes are bit for bit those of vrt_accum_begin_ex(ctx, W, H, VRT_MODE_PRIMARY, 0, 0),
+ *                         vrt_accum_add(ctx, 1, ..), vrt_accum_guides_device(..). HOST buffers, synchronous. Any output may be NULL,
+ *                         not all of them (VRT_E_INVALID); the frame size rule is vrt_denoise's; VRT_E_STATE before an upload or a
+ *                         camera has been set and while a patch batch is open. The call reads and writes no accumulation state: it
+ *                         may be made in the middle of an accumulation of any size, whose resolves, counts, variance and guides
+ *                         return the same bits afterwards. It takes no profiling slot. The march runs on 40 bytes per pixel of
+ *                         guide state that belong to the context, grown and never shrunk; every call is ordered on it.
+ * vrt_guide_frame_device  the same into DEVICE buffers; the resolve is enqueued on `stream` (NULL: the context's), after the march on
+ *                         the context's stream.
+ *
+ * The pass. LOW is the w x h image with its planes, HIGH the W x H = r w x r h planes. All arithmetic is float32, every operation
+ * rounded on its own, nothing contracted; h, g, det_expf and the tone map are vrt_filter_hdr's. p = (x, y) is a high pixel, q a low one.
+ *  U1. Inputs. Colours go through h, guide floats of both sizes through g. A pixel of either size is LIVE when g(coverage) > 0.
+ *  U2. Modulation. With VRT_UPSAMPLE_DEMODULATE m of a live pixel is vrt_filter_hdr's point 2 from its OWN albedo and coverage: low
+ *      pixels use the low planes, high pixels the high planes. m = 1 for a pixel that is not live, and for every pixel without the
+ *      flag. u_q = h(c_q) / m_q for a low pixel q.
+ *  U3. Position of p in the low image. fx = ((float)x + offset_hi_x) / (float)r - offset_lo_x, x0 = floorf(fx), tx = fx - x0; the
+ *      same in y. (The two frames show the same view: the shader's u = px / W * 2 - 1 gives the same bits for X / w and r X / (r w).)
+ *  U4. Taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), in that order, with the bilinear weights b of T3: (1-tx)(1-ty),
+ *      tx(1-ty), (1-tx)ty, tx ty. A tap is skipped when it lies outside the low image or when its liveness differs from p's: sky is
+ *      never mixed into surfaces, nor surfaces into sky. For a live p and the tap q = (X, Y):
+ *        dn2, da2 as in point 4 of the filter, between the tap's LOW guides and p's HIGH guides (q - p)
+ *        dzq = |Z_q - Z_p|
+ *        gx, gy   point 3's one-sided slopes of p on the HIGH depth plane (neighbours inside the high image and live)
+ *        ddx = fabsf((float)X - fx) * (float)r, ddy = fabsf((float)Y - fy) * (float)r      the tap's distance in high pixels
+ *        den = sigma_depth * ((gx * ddx + gy * ddy) + Z_p * (1.0f / 256.0f)) + 0x1p-20f
+ *        e   = (dn2 * kn + da2 * ka) + dzq / den                    kn, ka as in the filter, computed once on the host
+ *        w   = b * det_expf(-e)
+ *      and for a p that is not live w = b. sumw = sumw + w; sum_ch = sum_ch + w * u_q[ch], from 0 in tap order.
+ *  U5. Resolve. Where sumw > min_weight: u_p[ch] = sum_ch / sumw, unresolved = 0. Otherwise (a NaN sumw included) the nearest low
+ *      pixel N = (clamp((int)floorf(fx + 0.5f), 0, w-1), clamp((int)floorf(fy + 0.5f), 0, h-1)) is taken whatever its liveness:
+ *      u_p = u_N, unresolved = 1.
+ *  U6. Output. f = h(u_p * m_p) with the HIGH pixel's m. out_rgb [H][W][3] receives f, out_rgba8 [H][W][4] the tone-mapped bytes as
+ *      in point 5 of the filter, out_unresolved [H][W] one byte per pixel. Any output may be NULL, not both colour outputs.
+ * Identities: with r = 1, equal offsets and the same planes on both sides every pixel has one tap of weight 1 and three of weight 0,
+ * and the colour outputs are vrt_filter_hdr's at levels = 0 bit for bit. Where every guide of a region agrees, e = +0 and the pass
+ * is the float32 bilinear interpolation of u.
+ *
+ * vrt_upsample_default    factor 2, VRT_UPSAMPLE_DEMODULATE, sigma_normal 0.5, sigma_albedo 0.05, sigma_depth 0.5, min_weight 0, offsets 0:
+ *                         the best row of the quality sweep in profiles/upsample_quality.txt (DESIGN.md section 3 "Guided
+ *                         upsampling", which also says where upsampling loses to the full-size image of the same cost).
+ * vrt_upsample_hdr        DEVICE pointers, stream-ordered (NULL: the context's), stateless: it reads no context state, keeps no scratch
+ *                         and takes no profiling slot. width, height: the LOW size. u == NULL: vrt_upsample_default. VRT_E_INVALID: a NULL
+ *                         input, both colour outputs NULL, an output equal to an input or to another output, a factor outside
+ *                         1..VRT_UPSAMPLE_MAX_FACTOR, unknown flag bits, a sigma that is not finite or not > 0 (or so small that
+ *                         1 / sigma^2 is not finite), a min_weight outside [0, 1), an offset outside [0, 1], a tone map
+ *                         vrt_accum_resolve_hdr refuses, a low or a high frame size vrt_denoise refuses.
+ * vrt_upsample_hdr_host   the same through HOST buffers, synchronous, staged through 48 bytes per low and 53 per high pixel the
+ *                         context keeps.
+ * vrt_accum_resolve_hdr_upsampled  the pass on an HDR accumulation, which is the LOW image: the input is its float mean with its own
+ *                         guide planes, brought up to date as a vrt_accum_guides call would; the high planes are vrt_guide_frame's at
+ *                         r w x r h with the context's current inputs and the guide-glass rule AS BEGUN, so the two sides never mix
+ *                         rules. The low offsets are replaced by 0.5 for VRT_ACCUM_JITTER and 0 otherwise, the high offsets by 0.
+ *                         u == NULL: the default. HOST buffers, synchronous. VRT_E_STATE where vrt_accum_resolve_hdr_filtered returns
+ *                         it, and where the context's camera, uniforms, tree or lens changed since the last vrt_accum_add: the high
+ *                         planes would show another view. Mean and planes pass through the accumulation's own stage. The sums are
+ *                         never touched: every resolve, vrt_accum_counts, vrt_accum_variance and the guide calls return the same bits
+ *                         with and without these calls. No profiling slot is taken.
+ * vrt_accum_resolve_hdr_upsampled_device  the same into DEVICE buffers of the HIGH size, enqueued on `stream` (NULL: the context's),
+ *                         ordered against the adds as vrt_accum_resolve_hdr_device is.
+ * Not provided: a built-in repair of unresolved pixels; a luminance or variance term; upsampling of variance or moment planes;
+ * the filters chained inside the accumulation form (chain vrt_filter_hdr* on the outputs with vrt_guide_frame_device's planes); the
+ * lens's origin shift; frames, views, shards and vrt_multi. */
+#define VRT_UPSAMPLE_MAX_FACTOR 4
+#define VRT_UPSAMPLE_DEMODULATE 1u
+struct vrt_upsample {
+    int32_t factor;                      /* r: 1 .. VRT_UPSAMPLE_MAX_FACTOR; W = r * w, H = r * h */
+    uint32_t flags;
+    float sigma_normal, sigma_albedo, sigma_depth;   /* finite, > 0, as vrt_filter's */
+    float min_weight;                    /* finite, in [0, 1) */
+    float offset_lo_x, offset_lo_y;      /* where in the pixel the LOW planes' ray passes: 0 corner, 0.5 jittered; in [0, 1] */
+    float offset_hi_x, offset_hi_y;      /* the same for the HIGH planes */
+};
+typedef struct vrt_upsample vrt_upsample;
+void vrt_upsample_default(vrt_upsample *u);
+int vrt_guide_frame(vrt_ctx *ctx, int width, int height, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage);
+int vrt_guide_frame_device(vrt_ctx *ctx, int width, int height, void *d_normal, void *d_albedo, void *d_depth, void *d_coverage,
+                           void *stream);
+int vrt_upsample_hdr(vrt_ctx *ctx, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo,
+                     const void *d_depth, const void *d_coverage, const void *d_hi_normal, const void *d_hi_albedo,
+                     const void *d_hi_depth, const void *d_hi_coverage, const vrt_upsample *u, const vrt_tonemap *tm, void *d_out_rgb,
+                     void *d_out_rgba8, void *d_out_unresolved, void *stream);
+int vrt_upsample_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, const float *normal, const float *albedo,
+                          const float *depth, const float *coverage, const float *hi_normal, const float *hi_albedo,
+                          const float *hi_depth, const float *hi_coverage, const vrt_upsample *u, const vrt_tonemap *tm,
+                          float *out_rgb, uint8_t *out_rgba8, uint8_t *out_unresolved);
+int vrt_accum_resolve_hdr_upsampled(vrt_ctx *ctx, const vrt_upsample *u, const vrt_tonemap *tm, float *out_rgb, uint8_t *out_rgba8,
+                                    uint8_t *out_unresolved);
+int vrt_accum_resolve_hdr_upsampled_device(vrt_ctx *ctx, const vrt_upsample *u, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
+                                           void *d_unresolved, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

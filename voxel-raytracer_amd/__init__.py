@@ -60,6 +60,13 @@ class TemporalMom(C.Structure):
     _fields_ = Temporal._fields_ + [("measured_below", C.c_int32), ("search", C.c_int32)]
 
 
+class Upsample(C.Structure):
+    """include/vrt.h vrt_upsample"""
+    _fields_ = [("factor", C.c_int32), ("flags", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float), ("min_weight", C.c_float), ("offset_lo_x", C.c_float), ("offset_lo_y", C.c_float),
+                ("offset_hi_x", C.c_float), ("offset_hi_y", C.c_float)]
+
+
 TEMPORAL_KEYS = ("offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min", "depth_tol")
 TEMPORAL_MOM_KEYS = TEMPORAL_KEYS + ("measured_below", "search")
 _TEMPORAL_INTS = ("max_history", "measured_below", "search")   # the keys that are int32 fields; the others are floats
@@ -70,6 +77,8 @@ HISTORY_BYTES = 48       # include/vrt.h vrt_temporal_hdr: a history's bytes per
 
 FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
 FILTER_DEMODULATE = 1    # include/vrt.h VRT_FILTER_DEMODULATE
+UPSAMPLE_MAX_FACTOR = 4  # include/vrt.h VRT_UPSAMPLE_MAX_FACTOR
+UPSAMPLE_DEMODULATE = 1  # include/vrt.h VRT_UPSAMPLE_DEMODULATE
 
 
 class VrtError(RuntimeError):
@@ -94,6 +103,17 @@ def default_filter_var():
     """vrt_filter_var_default as a dict: default_filter()'s keys and "sigma_lum" -- the keyword arguments Context.filter_hdr_var and
     Context.accum_resolve_hdr_filtered_var take. Needs no device."""
     return _filter_defaults(FilterVar, "vrt_filter_var_default")
+
+
+def default_upsample():
+    """vrt_upsample_default as a dict: {"factor", "demodulate", "sigma_normal", "sigma_albedo", "sigma_depth", "min_weight",
+    "offset_lo_x", "offset_lo_y", "offset_hi_x", "offset_hi_y"} -- the keys the `upsample` argument of Context.upsample_hdr and
+    Context.accum_resolve_hdr_upsampled takes. Needs no device."""
+    u = Upsample()
+    hip_lib().vrt_upsample_default(C.byref(u))
+    d = {"factor": int(u.factor), "demodulate": bool(u.flags & UPSAMPLE_DEMODULATE)}
+    d.update((k, float(getattr(u, k))) for k, _ in Upsample._fields_[2:])
+    return d
 
 
 def _temporal_struct(kind, temporal=None, prev_camera=None):
@@ -265,7 +285,7 @@ _i, _u32, _u64, _f, _sz, _long = C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c
 _p, _s = C.c_void_p, C.c_char_p   # void *: handles, streams, host and device buffers; const char *: strings and Python bytes
 _pi, _pi32, _pu32, _pu8, _pf, _pl, _psz, _pp = (C.POINTER(t) for t in (C.c_int, C.c_int32, C.c_uint32, C.c_uint8, C.c_float, C.c_long,
                                                                        C.c_size_t, C.c_void_p))
-_tm, _flt, _fltv, _tmp, _tmpm = (C.POINTER(t) for t in (Tonemap, Filter, FilterVar, Temporal, TemporalMom))
+_tm, _flt, _fltv, _tmp, _tmpm, _ups = (C.POINTER(t) for t in (Tonemap, Filter, FilterVar, Temporal, TemporalMom, Upsample))
 _RECORDS_OUT = [_pp, _psz]        # uint32_t **records, size_t *n_records
 
 HOST_API = {
@@ -417,6 +437,13 @@ HIP_API = {
     "vrt_temporal_hdr_mom_host": (_i, _FRAME + _CAMERA + [_p] * 6 + [_tmpm] + [_p] * 3),
     "vrt_accum_resolve_hdr_temporal_mom": (_i, [_p, _tmpm, _fltv, _tm] + [_p] * 6),
     "vrt_accum_resolve_hdr_temporal_mom_device": (_i, [_p, _tmpm, _fltv, _tm] + [_p] * 7),
+    "vrt_upsample_default": (None, [_ups]),
+    "vrt_guide_frame": (_i, _FRAME + [_p] * 4),
+    "vrt_guide_frame_device": (_i, _FRAME + [_p] * 5),
+    "vrt_upsample_hdr": (_i, _FRAME + [_p] * 9 + [_ups, _tm] + [_p] * 4),
+    "vrt_upsample_hdr_host": (_i, _FRAME + [_p] * 9 + [_ups, _tm] + [_p] * 3),
+    "vrt_accum_resolve_hdr_upsampled": (_i, [_p, _ups, _tm] + [_p] * 3),
+    "vrt_accum_resolve_hdr_upsampled_device": (_i, [_p, _ups, _tm] + [_p] * 4),
     "vrt_dispatch_frame": (_i, _FRAME + [_i, _p, _p, _p]),
     "vrt_set_profiling": (_i, [_p, _i]),
     "vrt_set_profiling_stride": (_i, [_p, _i]),
@@ -1038,7 +1065,7 @@ def _history_planes(history, prev_camera, h, w):
 def _zeros(h, w, *kinds):
     """zero-filled output planes by kind"""
     shapes = {"history": ((3, h, w, 4), np.float32), "rgb": ((h, w, 3), np.float32), "rgba8": ((h, w, 4), np.uint8),
-              "plane": ((h, w), np.float32)}
+              "plane": ((h, w), np.float32), "mask": ((h, w), np.uint8)}
     return [np.zeros(*shapes[k]) for k in kinds]
 
 
@@ -1814,6 +1841,90 @@ class Context:
         self._temporal_accum_device("vrt_accum_resolve_hdr_temporal_mom_device", self._temporal_mom, d_history_in,
                                     (d_history_out, d_integrated, d_rgb, d_rgba, d_variance), prev_camera, temporal, filter, tonemap,
                                     exposure, stream)
+
+    # Guided upsampling (include/vrt.h vrt_guide_frame, vrt_upsample_hdr, vrt_accum_resolve_hdr_upsampled), as upsample_frame /
+    # upsample_host / upsample_accum of csrc/vrt_upsample.cpp: the struct from one builder, the planes through _planes
+    @staticmethod
+    def _frame_size(width, height):
+        return (_check_int("width", width, "an integer >= 1", 1), _check_int("height", height, "an integer >= 1", 1))
+
+    @staticmethod
+    def _upsample(upsample):
+        """None (the NULL vrt_upsample: vrt_upsample_default) or a dict with any of default_upsample()'s keys -> Upsample or None;
+        ValueError for an unknown key, a factor outside 1..UPSAMPLE_MAX_FACTOR, a sigma that is not finite and > 0, a min_weight
+        outside [0, 1) or an offset outside [0, 1]"""
+        if upsample is None:
+            return None
+        d = default_upsample()
+        unknown = set(upsample) - set(d)
+        if unknown:
+            raise ValueError(f"upsample: unknown keys {sorted(unknown)}")
+        d.update(upsample)
+        r = _check_int("factor", d["factor"], f"an integer in [1, {UPSAMPLE_MAX_FACTOR}]", 1, UPSAMPLE_MAX_FACTOR)
+        sig = [_check_f32(k, d[k], _positive, "finite and > 0") for k in ("sigma_normal", "sigma_albedo", "sigma_depth")]
+        mw = _check_f32("min_weight", d["min_weight"], lambda x: 0.0 <= x < 1.0, "in [0, 1)")
+        off = [_check_f32(k, d[k], lambda x: 0.0 <= x <= 1.0, "in [0, 1]") for k in ("offset_lo_x", "offset_lo_y", "offset_hi_x", "offset_hi_y")]
+        return Upsample(r, UPSAMPLE_DEMODULATE if d["demodulate"] else 0, *sig, mw, *off)
+
+    def guide_frame(self, width, height):
+        """The guide planes of a frame (vrt_guide_frame): one sample per pixel through the pixel's corner ray, from the context's
+        current camera, uniforms and tree, with no accumulation involved -> accum_guides()'s dict at [height, width]."""
+        w, h = self._frame_size(width, height)
+        out = {k: np.zeros((h, w) + c, np.float32) for k, c in _GUIDE_PLANES.items()}
+        self._chk(self._L.vrt_guide_frame(self._h, w, h, *(p.ctypes.data for p in out.values())))
+        return out
+
+    def guide_frame_device(self, width, height, d_normal, d_albedo, d_depth, d_coverage, stream=None):
+        """vrt_guide_frame_device: DEVICE buffers (H*W x 3, x 4, x 1, x 1 floats; any may be None, not all), the resolve enqueued on
+        `stream`"""
+        w, h = self._frame_size(width, height)
+        self._chk(self._L.vrt_guide_frame_device(self._h, w, h, d_normal, d_albedo, d_depth, d_coverage, stream))
+
+    def upsample_hdr(self, rgb, guides, hi_guides, upsample=None, tonemap="clamp", exposure=1.0):
+        """Guided upsampling through host arrays (vrt_upsample_hdr_host): the LOW image rgb[h,w,3] with its planes `guides` rebuilt
+        at r times the size from the HIGH planes `hi_guides` ([r h, r w, ..]; both as accum_guides / guide_frame return them).
+        upsample: None (vrt_upsample_default) or a dict with any of default_upsample()'s keys -> (rgb float32[H,W,3], rgba8
+        uint8[H,W,4], unresolved uint8[H,W]: 1 where no tap counted and the nearest low pixel was taken)."""
+        tm = self._tonemap_ref(tonemap, exposure)
+        u = self._upsample(upsample)
+        r = u.factor if u is not None else default_upsample()["factor"]
+        rgb, planes, h, w = _planes(rgb, guides, tuple(_GUIDE_PLANES))
+        hi = [np.ascontiguousarray(hi_guides[k], np.float32) for k in _GUIDE_PLANES]
+        if any(p.shape != (r * h, r * w) + c for p, c in zip(hi, _GUIDE_PLANES.values())):
+            raise ValueError(f"expected hi_guides at [{r * h}, {r * w}] for factor {r}; got {', '.join(str(p.shape) for p in hi)}")
+        out, out8, mask = _zeros(r * h, r * w, "rgb", "rgba8", "mask")
+        self._chk(self._L.vrt_upsample_hdr_host(self._h, w, h, rgb.ctypes.data, *(p.ctypes.data for p in planes), *(p.ctypes.data for p in hi),
+                                                _ref(u), tm, out.ctypes.data, out8.ctypes.data, mask.ctypes.data))
+        return out, out8, mask
+
+    def upsample_hdr_device(self, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_hi_normal, d_hi_albedo, d_hi_depth,
+                            d_hi_coverage, d_out_rgb, d_out_rgba, d_out_unresolved, upsample=None, tonemap="clamp", exposure=1.0,
+                            stream=None):
+        """vrt_upsample_hdr: DEVICE buffers (width, height: the LOW size; the high planes and the outputs at factor times it; d_out_rgb,
+        d_out_rgba: either may be None, not both; d_out_unresolved may be None), enqueued on `stream`"""
+        tm = self._tonemap_ref(tonemap, exposure)
+        u = _ref(self._upsample(upsample))
+        self._chk(self._L.vrt_upsample_hdr(self._h, width, height, d_rgb, d_normal, d_albedo, d_depth, d_coverage, d_hi_normal, d_hi_albedo,
+                                           d_hi_depth, d_hi_coverage, u, tm, d_out_rgb, d_out_rgba, d_out_unresolved, stream))
+
+    def accum_resolve_hdr_upsampled(self, upsample=None, tonemap="clamp", exposure=1.0):
+        """Guided upsampling of an HDR accumulation (vrt_accum_resolve_hdr_upsampled): its float mean and its own planes are the LOW
+        side, the guide planes of the frame `factor` times its size the HIGH side; the offsets are the accumulation's own -> (rgb
+        float32[H,W,3], rgba8[H,W,4], unresolved uint8[H,W]) at the high size."""
+        tm = self._tonemap_ref(tonemap, exposure)
+        u = self._upsample(upsample)
+        r = u.factor if u is not None else default_upsample()["factor"]
+        h, w = self._accum_hw()
+        rgb, rgba, mask = _zeros(r * h, r * w, "rgb", "rgba8", "mask")
+        self._chk(self._L.vrt_accum_resolve_hdr_upsampled(self._h, _ref(u), tm, rgb.ctypes.data, rgba.ctypes.data, mask.ctypes.data))
+        return rgb, rgba, mask
+
+    def accum_resolve_hdr_upsampled_device(self, d_rgb, d_rgba, d_unresolved, upsample=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_upsampled_device: DEVICE buffers of the HIGH size (d_rgb, d_rgba: either may be None, not both;
+        d_unresolved may be None), enqueued on `stream`"""
+        tm = self._tonemap_ref(tonemap, exposure)
+        u = _ref(self._upsample(upsample))
+        self._chk(self._L.vrt_accum_resolve_hdr_upsampled_device(self._h, u, tm, d_rgb, d_rgba, d_unresolved, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -230,7 +230,10 @@ hipError_t vrt_internal::launch_accum_step(Accum &ac, vrt::KArgs &a, vrt::ViewSe
         vs.v[0].gen_fast = 0u;
     }
     if (acc.guides)   // vrt_accum_guides: the samples' first hits into the guide state, none of the sums touched
-        return launch::accum_guides(src, v, a, vs, vrt::guides::Args{vrt::guides::state_of(ac.d_guides.get(), (size_t)ac.width * (size_t)ac.height), acc.first, acc.n},
+        return launch::accum_guides(src, v, a, vs,
+                                    vrt::guides::Args{acc.guide_state ? vrt::guides::state_of(acc.guide_state, (size_t)a.width * (size_t)a.height)
+                                                                      : vrt::guides::state_of(ac.d_guides.get(), (size_t)ac.width * (size_t)ac.height),
+                                                      acc.first, acc.n},
                                     l, acc.glass, grid, s);
     if (acc.frame_only)   // an HDR accumulation's corner frame of a primary mode, every sample of the repeat path
         return (hdr && mode != VRT_MODE_FULL && src == Source::kCorner) ? launch::accum_frame_hdr(mode, v, a, vs, hf, grid, s) : hipErrorInvalidValue;

@@ -83,9 +83,78 @@ int guide_batch(vrt_ctx *c, size_t n, const float *d_origins, int origin_stride,
     return VRT_OK;
 }
 
+// what vrt_guide_frame* check before anything is enqueued
+int check_guide_frame(vrt_ctx *c, const char *what, int width, int height, bool any_out) {
+    if (!c) return VRT_E_INVALID;
+    const int r = check_frame(c, width, height);
+    if (r) return r;
+    if (!any_out) return vrt_fail(c, VRT_E_INVALID, std::string(what) + ": every output is null");
+    return VRT_OK;
+}
+
 }  // namespace
 
+// One sample per pixel -- sample 0 from the corner, the lens as vrt_accum_add would take it -- through the corner form of guide_kernel
+// into the context's own state, then the guide resolve with n = 1: the launches of vrt_accum_begin_ex(PRIMARY, 0, 0), vrt_accum_add(1),
+// vrt_accum_guides_device, with no accumulation involved.
+int vrt_internal::guide_frame_planes(vrt_ctx *c, const char *what, int width, int height, bool glass, float *d_normal, float *d_albedo,
+                                     float *d_depth, float *d_coverage, hipStream_t s) {
+    if (!c->have_scene) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no octree uploaded (call vrt_upload_octree first)");
+    if (c->batch.open) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": a patch batch is open (call vrt_patch_end first)");
+    if (!c->have_camera) return vrt_fail(c, VRT_E_STATE, std::string(what) + ": no camera set (call vrt_set_camera first)");
+    vrt_ctx::GuideFrame &gf = c->guide_frame;
+    const size_t px = (size_t)width * (size_t)height;
+    if (!gf.marched) VRT_HIP(c, hipEventCreateWithFlags(&gf.marched, hipEventDisableTiming));
+    if (!gf.read) VRT_HIP(c, hipEventCreateWithFlags(&gf.read, hipEventDisableTiming));
+    if (px * vrt::guides::kStateBytes > gf.d_state.bytes()) {
+        const int r = reserve_synced(c, {{&gf.d_state, px * vrt::guides::kStateBytes}});
+        if (r) return r;
+    }
+    VRT_HIP(c, hipMemsetAsync(gf.d_state.get(), 0, px * vrt::guides::kStateBytes, c->stream));   // +0.0, no hits
+    AccumStep step{0u, 1u, false, c->lens[0], c->lens[1]};
+    step.guides = true;
+    step.glass = glass;
+    step.guide_state = gf.d_state.get();
+    int r = enqueue(c, width, height, 0, height, height, 0, 0, VRT_MODE_PRIMARY, nullptr, nullptr, c->stream, nullptr, 1, &step);
+    if (r) return r;
+    // the state is the context's, whose every use the context's stream orders: a caller's stream is joined back
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(gf.marched, c->stream));
+        VRT_HIP(c, hipStreamWaitEvent(s, gf.marched, 0));
+    }
+    const vrt::guides::Resolve q{vrt::guides::state_of(gf.d_state.get(), px), d_normal, d_albedo, d_depth, d_coverage, 1u, (uint32_t)px};
+    VRT_HIP(c, vrt::launch::guides_resolve(q, s));
+    if (s != c->stream) {
+        VRT_HIP(c, hipEventRecord(gf.read, s));
+        VRT_HIP(c, hipStreamWaitEvent(c->stream, gf.read, 0));
+    }
+    return VRT_OK;
+}
+
 extern "C" {
+
+int vrt_guide_frame(vrt_ctx *c, int width, int height, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage) {
+    int r = check_guide_frame(c, "vrt_guide_frame", width, height, out_normal || out_albedo || out_depth || out_coverage);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)width * (size_t)height;
+    vrt_stage::Stage st(4);
+    const int normal = st.out(px * 12, out_normal), albedo = st.out(px * 16, out_albedo), depth = st.out(px * 4, out_depth);
+    const int coverage = st.out(px * 4, out_coverage);
+    if ((r = st.reserve_synced(c, c->guide_frame.d_host))) return r;
+    r = guide_frame_planes(c, "vrt_guide_frame", width, height, c->guide_glass, st.at<float>(normal), st.at<float>(albedo), st.at<float>(depth),
+                           st.at<float>(coverage), c->stream);
+    return r ? r : st.download(c, c->stream);
+}
+
+int vrt_guide_frame_device(vrt_ctx *c, int width, int height, void *d_normal, void *d_albedo, void *d_depth, void *d_coverage, void *stream) {
+    const int r = check_guide_frame(c, "vrt_guide_frame_device", width, height, d_normal || d_albedo || d_depth || d_coverage);
+    if (r) return r;
+    VRT_HIP(c, hipSetDevice(c->device));
+    return guide_frame_planes(c, "vrt_guide_frame_device", width, height, c->guide_glass, static_cast<float *>(d_normal),
+                              static_cast<float *>(d_albedo), static_cast<float *>(d_depth), static_cast<float *>(d_coverage),
+                              stream ? (hipStream_t)stream : c->stream);
+}
 
 int vrt_accum_guides(vrt_ctx *c, float *out_normal, float *out_albedo, float *out_depth, float *out_coverage) {
     int r = accum_state(c, "vrt_accum_guides", false);

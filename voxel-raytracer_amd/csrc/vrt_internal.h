@@ -138,6 +138,23 @@ struct vrt_ctx {
     FilterScratch filter;
     // the staging of vrt_temporal_hdr_host (vrt_temporal.cpp, where its planes are declared): both histories, the inputs and the outputs
     DevBuf<float4> d_temporal;
+    // vrt_guide_frame* (vrt_guides.cpp): the guide state of one sample per pixel of a frame, 40 bytes per pixel, grown and never
+    // shrunk; the march and every growth are ordered on the context's stream, a caller's stream that resolves it is joined back
+    struct GuideFrame {
+        DevBuf<void> d_state;
+        DevBuf<float> d_host;                    // vrt_guide_frame's four planes on their way to the host
+        hipEvent_t marched = nullptr, read = nullptr;
+        GuideFrame() = default;
+        GuideFrame(const GuideFrame &) = delete;
+        GuideFrame &operator=(const GuideFrame &) = delete;
+        ~GuideFrame() {
+            if (marched) (void)hipEventDestroy(marched);
+            if (read) (void)hipEventDestroy(read);
+        }
+    };
+    GuideFrame guide_frame;
+    // the staging of vrt_upsample_hdr_host (vrt_upsample.cpp, where its planes are declared)
+    DevBuf<float> d_upsample;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     DevBuf<void> d_query;
     // device buffers behind vrt_shade_rays (vrt_rays.cpp)
@@ -406,6 +423,8 @@ struct AccumStep {
     bool guides = false;
     bool glass = false;             // with guides: the past-glass rule (vrt_set_guide_glass as the accumulation's begin read it)
     bool moments = false;
+    void *guide_state = nullptr;    // with guides: the state to march into instead of the accumulation's (vrt_guide_frame, whose frame
+                                    // size is the launch's own); nothing of the accumulation is read or written then
 };
 int enqueue(vrt_ctx *c, int width, int height, int row0, int n_rows, int tile_rows, int row_stride, int compact, int mode,
             void *d_rgba, void *d_id, hipStream_t s, const vrt_view *views = nullptr, int n_views = 1, const AccumStep *acc = nullptr);
@@ -459,6 +478,13 @@ int filter_var_check(vrt_ctx *c, const char *what, const vrt_filter_var *f, cons
 int filter_var_frame(vrt_ctx *c, const char *what, int width, int height, const void *d_rgb, const void *d_normal, const void *d_albedo,
                      const void *d_depth, const void *d_coverage, const void *d_variance, const vrt_filter_var *f, const vrt_tonemap *tm,
                      void *d_out_rgb, void *d_out_rgba8, void *d_out_variance, void *stream);
+
+// vrt_guides.cpp
+// vrt_guide_frame_device in the name of `what` with the guide-glass rule given (the entry points: the context's at the call; the
+// upsampled resolve: the accumulation's as begun): the planes of one corner sample per pixel of a width x height frame from the
+// context's current inputs, marched on the context's stream into the context's own state, resolved on s
+int guide_frame_planes(vrt_ctx *c, const char *what, int width, int height, bool glass, float *d_normal, float *d_albedo, float *d_depth,
+                       float *d_coverage, hipStream_t s);
 
 // vrt_rays.cpp
 // The kernel arguments of a caller's ray batch of n rays as an image of `width` (after ensure_analysis): the scene and light blocks

@@ -8,6 +8,7 @@
 #include "vrt_guides.h"
 #include "vrt_filter.h"
 #include "vrt_temporal.h"
+#include "vrt_upsample.h"
 
 namespace vrt {
 namespace launch {
@@ -195,6 +196,10 @@ hipError_t filter_through(const filter::Through &q, hipStream_t s);
 hipError_t temporal_pass(const temporal::Args &q, hipStream_t s);
 // ... and the kernel's second form: T3s, T7 and T6m of vrt_temporal_hdr_mom
 hipError_t temporal_pass_mom(const temporal::ArgsMom &q, hipStream_t s);
+
+// vrt_launch_upsample.hip: the guided upsampling pass (vrt_upsample.hip.h), a whole HIGH frame, one lane per high pixel, one 8 x 8
+// tile per wave: U1-U6 of include/vrt.h vrt_upsample_hdr from q's low image and planes and its high planes.
+hipError_t upsample_pass(const upsample::Args &q, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt
