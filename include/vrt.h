@@ -1327,6 +1327,109 @@ int vrt_accum_resolve_hdr_upsampled(vrt_ctx *ctx, const vrt_upsample *u, const v
                                     uint8_t *out_unresolved);
 int vrt_accum_resolve_hdr_upsampled_device(vrt_ctx *ctx, const vrt_upsample *u, const vrt_tonemap *tm, void *d_rgb, void *d_rgba8,
                                            void *d_unresolved, void *stream);
+/* EXTENSION: auto-exposure -- light metering on the device. Every HDR route ends in vrt_tonemap { op, exposure }, and the exposure is
+ * a number the caller has to know: the room seen from inside and the dragon against the sky want different ones. These calls take a
+ * luminance histogram of a float image on the device (vrt_meter_hdr), turn it into an exposure with eye adaptation from frame to frame
+ * (the record, a vrt_exposure that the CALLER carries), and tone map by a record that lies in device memory (vrt_tonemap_hdr), so that
+ * a stream of frames never waits for the host. With the binning rule below everything but two float operations is integer arithmetic,
+ * and the whole rule is the same bits on the device, on the host (vrt_meter_resolve) and in the scalar checker (tests/oracle_meter.c).
+ *
+ * The rule. float32 where it is float, every operation rounded on its own, nothing contracted; h is h(c) of vrt_accum_keep_hdr point
+ * 1, min and max follow the conventions of the unorm8 store stated there (min(a, b) = b < a ? b : a, max(a, b) = a < b ? b : a).
+ *  E1. Luminance. Y = (0.2126f * h(r) + 0.7152f * h(g)) + 0.0722f * h(b): M1's luminance (vrt_accum_keep_moments), V1's Y of the
+ *      clamped channels. Y is finite, at least +0 and below 2^16: a NaN, an infinity or a negative channel has gone through h.
+ *  E2. Bin. k = max((int)(bits(Y) >> 20) - 888, 0), bits the float's 32 bits as an unsigned integer: the exponent and the top three
+ *      mantissa bits, counted from 2^-16 (exponent field 111, 111 * 8 = 888) -- eight bins per octave, 32 octaves. The largest
+ *      possible Y, Y(65504, 65504, 65504) = 65504 in float32, lands in bin 255. Bin 0 holds everything below 2^-16 * 1.125, +0
+ *      included, and counts as BLACK. No logarithm is evaluated anywhere.
+ *  E3. Histogram. VRT_METER_BINS uint32 counts of the pixels of the metered rectangle; N is their number. The frame-size rule is
+ *      vrt_denoise's, so N <= 2^30 and no count can wrap.
+ *  E4. Window. a = (uint64)N * low_permille / 1000, b = (uint64)N * high_permille / 1000, integer divisions. Pixels are ranked by
+ *      bin: bin k holds the ranks [cum_{k-1}, cum_k), cum_k the number of pixels in bins 0..k. n_k is the size of the overlap of
+ *      [cum_{k-1}, cum_k) with [a, b).
+ *  E5. Sums. Over k = 1..255 only: M = sum n_k and S = sum n_k * k, both uint64. Black pixels occupy ranks but never enter the sums.
+ *  E6. Metered luminance. If M = 0, metered = +0.0f. Otherwise t = (S << 20) / M as a uint64 integer division,
+ *      bits = (888u << 20) + (uint32)t + (1u << 19), Ym = float_from_bits(bits). This is the mean of the bins' pseudo-logarithms
+ *      taken at the bins' centres, in exact integer arithmetic; when every windowed pixel lies in one bin, Ym is that bin's centre.
+ *      The pseudo-logarithm is Mitchell's piecewise-linear one -- the float's bits read as a fixed-point number, exact at powers of
+ *      two and linear between them -- so Ym is a geometric mean to within 0.086 octave (the largest gap between log2(1 + f) and f),
+ *      not exactly.
+ *  E7. Target. e* = min(max(key / Ym, min_exposure), max_exposure), one float division. If M = 0, e* = io->exposure when
+ *      io->frames > 0, otherwise min(max(1.0f, min_exposure), max_exposure).
+ *  E8. Adaptation. When adapt == 1.0f, or io->frames == 0, or M = 0: exposure = e*. Otherwise exposure = prev + adapt * (e* - prev)
+ *      with prev = io->exposure. The record then holds exposure, metered (Ym, or +0.0f), window = M, and frames incremented,
+ *      saturating at 2^32 - 1. For adapt < 1 the step never overshoots: adapt * d is not beyond d.
+ *  E9. Tone map by a record. e = min(tm->exposure * E, 3.402823466e38f) with E the record's exposure; with no record e = tm->exposure.
+ *      The bytes are unorm8(tone_map(x, op, e)) per channel with the tone map of vrt_accum_resolve_hdr point 4, alpha 255. With no
+ *      record these are the rgba8 bytes vrt_accum_resolve_hdr gives for the same mean and tm.
+ * Exact scaling: an image scaled by 2^j shifts every bin by 8 j, makes Ym exactly 2^j times larger and e* exactly 2^-j times,
+ * wherever no clamp of h, bin 0 or the exposure range is met (E2 and E6).
+ *
+ * vrt_meter_default       key 0.18, low_permille 500, high_permille 950, min_exposure 2^-10, max_exposure 2^10, adapt 1, rectangle 0
+ *                         (the whole frame).
+ * vrt_meter_resolve       E4-E8 on the HOST from a histogram of VRT_METER_BINS counts: needs no context and no device. m == NULL: the
+ *                         default. io: the record, read and written. Returns VRT_OK, or VRT_E_INVALID for a NULL histogram or io, a
+ *                         parameter outside the ranges below, or counts that sum to more than 2^30. The device's finishing step
+ *                         evaluates the same text (csrc/vrt_meter.h).
+ * vrt_meter_hdr           DEVICE pointers, stream-ordered (NULL: the context's), stateless: it reads no context state, keeps no scratch
+ *                         and takes no profiling slot. d_rgb: width x height pixels of 3 floats. d_histogram: VRT_METER_BINS uint32,
+ *                         required -- the call's workspace and an output; the call zeroes it itself, in stream order. d_exposure: one
+ *                         vrt_exposure, read and written on the device (zero it before the first frame); the host never sees it.
+ *                         m == NULL: the default. VRT_E_INVALID: a NULL pointer; a pointer that is no multiple of 4; outputs that alias
+ *                         the input or each other (equal pointers); a frame size vrt_denoise refuses; a rectangle that is not all
+ *                         zeros and not 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height; key not finite or not > 0; not
+ *                         0 <= low_permille < high_permille <= 1000; min_exposure, max_exposure not finite or not
+ *                         0 < min_exposure <= max_exposure; adapt outside (0, 1].
+ * vrt_meter_hdr_host      the same through HOST buffers, synchronous, on the context's stream: rgb in, the record io read and written,
+ *                         out_histogram (may be NULL) the counts.
+ * vrt_tonemap_hdr         E9 on n pixels (1 <= n <= 2^30): DEVICE pointers, stream-ordered, stateless as above. d_rgb: n x 3 floats;
+ *                         d_out_rgba8: n x 4 bytes; d_exposure: the record, or NULL for none. tm as in vrt_accum_resolve_hdr (NULL:
+ *                         VRT_TONEMAP_CLAMP, exposure 1). VRT_E_INVALID: a NULL d_rgb or d_out_rgba8, a pointer that is no multiple of
+ *                         4, an output equal to an input, n outside its range, a tone map vrt_accum_resolve_hdr refuses.
+ * vrt_tonemap_hdr_host    the same through HOST buffers, synchronous; e: the record, or NULL.
+ * vrt_accum_resolve_hdr_metered  an HDR accumulation resolved as vrt_accum_resolve_hdr_device resolves it, into the accumulation's
+ *                         own stage; the mean metered over E1-E8 (the rectangle is of the accumulation's frame) into the record;
+ *                         tone mapped by the fresh record over E9. HOST buffers, synchronous: io is read and written, out_rgb
+ *                         [H][W][3], out_rgba8 [H][W][4] and out_histogram [VRT_METER_BINS] may each be NULL. State errors and
+ *                         ordering are vrt_accum_resolve_hdr's (VRT_E_STATE: no begin, no sample yet, begun without HDR);
+ *                         VRT_E_INVALID: a NULL io, the parameters as above, a tone map vrt_accum_resolve_hdr refuses. The sums are
+ *                         never touched: every other resolve, vrt_accum_counts, vrt_accum_variance and the guide calls return the same
+ *                         bits with and without these calls. No profiling slot is taken.
+ * vrt_accum_resolve_hdr_metered_device  the same with the record (required), the histogram, the mean and the bytes in the caller's
+ *                         DEVICE memory (the last three may each be NULL; pointers multiples of 4, no two equal), enqueued on
+ *                         `stream` (NULL: the context's), ordered against the adds as vrt_accum_resolve_hdr_device is.
+ * Not provided: a device-side exposure inside the tone maps of the filter, temporal, upsample and display passes (ask them for the
+ * float output and finish with vrt_tonemap_hdr); weighting by coverage, or centre weighting; more tone-map operators; frames, views,
+ * shards and vrt_multi. */
+#define VRT_METER_BINS 256
+struct vrt_meter {
+    float key;                            /* the luminance the metered value is mapped to; finite, > 0; default 0.18 */
+    int32_t low_permille, high_permille;  /* the rank window, 0 <= low < high <= 1000; default 500, 950 */
+    float min_exposure, max_exposure;     /* finite, 0 < min <= max; default 2^-10, 2^10 */
+    float adapt;                          /* in (0, 1]; 1 = no adaptation; default 1 */
+    int32_t x0, y0, x1, y1;               /* metered rectangle [x0,x1) x [y0,y1); all four 0 = the whole frame */
+};
+typedef struct vrt_meter vrt_meter;
+struct vrt_exposure {     /* the caller's, carried from frame to frame; zero it before the first */
+    float exposure;       /* E8 */
+    float metered;        /* Ym of E6, +0.0f when nothing was metered */
+    uint32_t window;      /* M of E5 */
+    uint32_t frames;      /* meterings chained into this record, saturating */
+};
+typedef struct vrt_exposure vrt_exposure;
+void vrt_meter_default(vrt_meter *m);
+int vrt_meter_resolve(const uint32_t *histogram, const vrt_meter *m, vrt_exposure *io);
+int vrt_meter_hdr(vrt_ctx *ctx, int width, int height, const void *d_rgb, const vrt_meter *m, void *d_histogram, void *d_exposure,
+                  void *stream);
+int vrt_meter_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, const vrt_meter *m, uint32_t *out_histogram,
+                       vrt_exposure *io);
+int vrt_tonemap_hdr(vrt_ctx *ctx, size_t n, const void *d_rgb, const vrt_tonemap *tm, const void *d_exposure, void *d_out_rgba8,
+                    void *stream);
+int vrt_tonemap_hdr_host(vrt_ctx *ctx, size_t n, const float *rgb, const vrt_tonemap *tm, const vrt_exposure *e, uint8_t *out_rgba8);
+int vrt_accum_resolve_hdr_metered(vrt_ctx *ctx, const vrt_meter *m, const vrt_tonemap *tm, vrt_exposure *io, float *out_rgb,
+                                  uint8_t *out_rgba8, uint32_t *out_histogram);
+int vrt_accum_resolve_hdr_metered_device(vrt_ctx *ctx, const vrt_meter *m, const vrt_tonemap *tm, void *d_exposure, void *d_histogram,
+                                         void *d_rgb, void *d_rgba8, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

@@ -67,6 +67,17 @@ class Upsample(C.Structure):
                 ("offset_hi_x", C.c_float), ("offset_hi_y", C.c_float)]
 
 
+class Meter(C.Structure):
+    """include/vrt.h vrt_meter"""
+    _fields_ = [("key", C.c_float), ("low_permille", C.c_int32), ("high_permille", C.c_int32), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adapt", C.c_float), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
+class Exposure(C.Structure):
+    """include/vrt.h vrt_exposure: the record a caller carries from frame to frame"""
+    _fields_ = [("exposure", C.c_float), ("metered", C.c_float), ("window", C.c_uint32), ("frames", C.c_uint32)]
+
+
 TEMPORAL_KEYS = ("offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min", "depth_tol")
 TEMPORAL_MOM_KEYS = TEMPORAL_KEYS + ("measured_below", "search")
 _TEMPORAL_INTS = ("max_history", "measured_below", "search")   # the keys that are int32 fields; the others are floats
@@ -79,6 +90,7 @@ FILTER_MAX_LEVELS = 8    # include/vrt.h VRT_FILTER_MAX_LEVELS
 FILTER_DEMODULATE = 1    # include/vrt.h VRT_FILTER_DEMODULATE
 UPSAMPLE_MAX_FACTOR = 4  # include/vrt.h VRT_UPSAMPLE_MAX_FACTOR
 UPSAMPLE_DEMODULATE = 1  # include/vrt.h VRT_UPSAMPLE_DEMODULATE
+METER_BINS = 256         # include/vrt.h VRT_METER_BINS
 
 
 class VrtError(RuntimeError):
@@ -114,6 +126,74 @@ def default_upsample():
     d = {"factor": int(u.factor), "demodulate": bool(u.flags & UPSAMPLE_DEMODULATE)}
     d.update((k, float(getattr(u, k))) for k, _ in Upsample._fields_[2:])
     return d
+
+
+_METER_INTS = ("low_permille", "high_permille", "x0", "y0", "x1", "y1")   # the keys that are int32 fields; the others are floats
+
+
+def default_meter():
+    """vrt_meter_default as a dict: {"key", "low_permille", "high_permille", "min_exposure", "max_exposure", "adapt", "x0", "y0", "x1",
+    "y1"} -- the keys the `meter` argument of meter_resolve, Context.meter_hdr and Context.accum_resolve_hdr_metered takes. Needs no
+    device."""
+    m = Meter()
+    hip_lib().vrt_meter_default(C.byref(m))
+    return {k: (int if k in _METER_INTS else float)(getattr(m, k)) for k, _ in Meter._fields_}
+
+
+def _meter(meter):
+    """None (the NULL vrt_meter: vrt_meter_default) or a dict with any of default_meter()'s keys -> Meter or None; ValueError for an
+    unknown key, a key that is not finite and > 0, a rank window that is not 0 <= low < high <= 1000, exposure bounds that are not
+    finite with 0 < min <= max, an adapt outside (0, 1] or a rectangle with a negative or inverted side (its fit into the frame is the
+    library's to check)"""
+    if meter is None:
+        return None
+    d = default_meter()
+    unknown = set(meter) - set(d)
+    if unknown:
+        raise ValueError(f"meter: unknown keys {sorted(unknown)}")
+    d.update(meter)
+    key = _check_f32("key", d["key"], _positive, "finite and > 0")
+    high = _check_int("high_permille", d["high_permille"], "an integer in [1, 1000]", 1, 1000)
+    low = _check_int("low_permille", d["low_permille"], "an integer in [0, high_permille)", 0, high - 1)
+    lo = _check_f32("min_exposure", d["min_exposure"], _positive, "finite and > 0")
+    hi = _check_f32("max_exposure", d["max_exposure"], lambda x: x >= lo, "finite and >= min_exposure")
+    adapt = _check_f32("adapt", d["adapt"], lambda x: 0.0 < x <= 1.0, "in (0, 1]")
+    rect = [_check_int(k, d[k], "an integer in [0, 2^30]", 0, 1 << 30) for k in ("x0", "y0", "x1", "y1")]
+    if any(rect) and not (rect[0] < rect[2] and rect[1] < rect[3]):
+        raise ValueError(f"rectangle: expected all zeros or x0 < x1 and y0 < y1, got {rect}")
+    return Meter(key, low, high, lo, hi, adapt, *rect)
+
+
+def _exposure(state):
+    """None (a zeroed record: the first frame) or a dict as meter_resolve returns it -> Exposure"""
+    if state is None:
+        return Exposure()
+    unknown = set(state) - {"exposure", "metered", "window", "frames"}
+    if unknown:
+        raise ValueError(f"state: unknown keys {sorted(unknown)}")
+    return Exposure(float(np.float32(state.get("exposure", 0.0))), float(np.float32(state.get("metered", 0.0))),
+                    _check_int("window", state.get("window", 0), "an integer in [0, 2^32)", 0, 0xffffffff),
+                    _check_int("frames", state.get("frames", 0), "an integer in [0, 2^32)", 0, 0xffffffff))
+
+
+def _exposure_dict(e):
+    return {"exposure": float(e.exposure), "metered": float(e.metered), "window": int(e.window), "frames": int(e.frames)}
+
+
+def meter_resolve(hist, meter=None, state=None):
+    """vrt_meter_resolve: E4-E8 of include/vrt.h on the host from a histogram of METER_BINS counts. meter: None (vrt_meter_default) or
+    a dict with any of default_meter()'s keys; state: None (a zeroed record) or the dict an earlier call returned -> the new record
+    {"exposure", "metered", "window", "frames"}. Needs no device."""
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.shape != (METER_BINS,):
+        raise ValueError(f"expected {METER_BINS} counts, got {h.shape}")
+    if np.any(np.asarray(hist) != h):
+        raise ValueError("every count must be an integer in [0, 2^32)")
+    e = _exposure(state)
+    r = hip_lib().vrt_meter_resolve(h.ctypes.data, _ref(_meter(meter)), C.byref(e))
+    if r != 0:
+        raise VrtError(f"vrt_meter_resolve: error {r} (the counts sum to more than 2^30)")
+    return _exposure_dict(e)
 
 
 def _temporal_struct(kind, temporal=None, prev_camera=None):
@@ -286,6 +366,7 @@ _p, _s = C.c_void_p, C.c_char_p   # void *: handles, streams, host and device bu
 _pi, _pi32, _pu32, _pu8, _pf, _pl, _psz, _pp = (C.POINTER(t) for t in (C.c_int, C.c_int32, C.c_uint32, C.c_uint8, C.c_float, C.c_long,
                                                                        C.c_size_t, C.c_void_p))
 _tm, _flt, _fltv, _tmp, _tmpm, _ups = (C.POINTER(t) for t in (Tonemap, Filter, FilterVar, Temporal, TemporalMom, Upsample))
+_mtr, _exp = C.POINTER(Meter), C.POINTER(Exposure)
 _RECORDS_OUT = [_pp, _psz]        # uint32_t **records, size_t *n_records
 
 HOST_API = {
@@ -444,6 +525,14 @@ HIP_API = {
     "vrt_upsample_hdr_host": (_i, _FRAME + [_p] * 9 + [_ups, _tm] + [_p] * 3),
     "vrt_accum_resolve_hdr_upsampled": (_i, [_p, _ups, _tm] + [_p] * 3),
     "vrt_accum_resolve_hdr_upsampled_device": (_i, [_p, _ups, _tm] + [_p] * 4),
+    "vrt_meter_default": (None, [_mtr]),
+    "vrt_meter_resolve": (_i, [_p, _mtr, _exp]),
+    "vrt_meter_hdr": (_i, _FRAME + [_p, _mtr, _p, _p, _p]),
+    "vrt_meter_hdr_host": (_i, _FRAME + [_p, _mtr, _p, _exp]),
+    "vrt_tonemap_hdr": (_i, [_p, _sz, _p, _tm, _p, _p, _p]),
+    "vrt_tonemap_hdr_host": (_i, [_p, _sz, _p, _tm, _exp, _p]),
+    "vrt_accum_resolve_hdr_metered": (_i, [_p, _mtr, _tm, _exp] + [_p] * 3),
+    "vrt_accum_resolve_hdr_metered_device": (_i, [_p, _mtr, _tm] + [_p] * 5),
     "vrt_dispatch_frame": (_i, _FRAME + [_i, _p, _p, _p]),
     "vrt_set_profiling": (_i, [_p, _i]),
     "vrt_set_profiling_stride": (_i, [_p, _i]),
@@ -1925,6 +2014,64 @@ class Context:
         tm = self._tonemap_ref(tonemap, exposure)
         u = _ref(self._upsample(upsample))
         self._chk(self._L.vrt_accum_resolve_hdr_upsampled_device(self._h, u, tm, d_rgb, d_rgba, d_unresolved, stream))
+
+    # Auto-exposure (include/vrt.h vrt_meter_hdr, vrt_tonemap_hdr, vrt_accum_resolve_hdr_metered), as the entry points of
+    # csrc/vrt_meter.cpp: the struct from one builder (_meter), the record as the dict meter_resolve returns
+    def meter_hdr(self, rgb, meter=None, state=None):
+        """Light metering through host arrays (vrt_meter_hdr_host): rgb[H,W,3]; meter: None (vrt_meter_default) or a dict with any of
+        default_meter()'s keys; state: None (the first frame) or the record an earlier call returned -> (the new record as a dict,
+        the histogram uint32[METER_BINS] of the metered rectangle)."""
+        m = _meter(meter)
+        e = _exposure(state)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+        hist = np.zeros(METER_BINS, np.uint32)
+        self._chk(self._L.vrt_meter_hdr_host(self._h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data, _ref(m), hist.ctypes.data, C.byref(e)))
+        return _exposure_dict(e), hist
+
+    def meter_hdr_device(self, width, height, d_rgb, d_histogram, d_exposure, meter=None, stream=None):
+        """vrt_meter_hdr: DEVICE buffers (d_rgb H*W x 3 floats; d_histogram METER_BINS uint32, zeroed by the call; d_exposure one
+        vrt_exposure of 16 bytes, read and written), enqueued on `stream`"""
+        w, h = self._frame_size(width, height)
+        self._chk(self._L.vrt_meter_hdr(self._h, w, h, d_rgb, _ref(_meter(meter)), d_histogram, d_exposure, stream))
+
+    def tonemap_hdr(self, rgb, tonemap="clamp", exposure=1.0, state=None):
+        """The tone map by a record through host arrays (vrt_tonemap_hdr_host, E9): rgb[..., 3] float32; state: None (no record: the
+        bytes of accum_resolve_hdr's tone map) or a record as meter_hdr returns it -> rgba8 uint8[..., 4]."""
+        tm = self._tonemap_ref(tonemap, exposure)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim < 1 or rgb.shape[-1] != 3 or rgb.size == 0:
+            raise ValueError(f"expected rgb[..., 3] with at least one pixel, got {rgb.shape}")
+        out = np.zeros(rgb.shape[:-1] + (4,), np.uint8)
+        e = None if state is None else _exposure(state)
+        self._chk(self._L.vrt_tonemap_hdr_host(self._h, rgb.size // 3, rgb.ctypes.data, tm, _ref(e), out.ctypes.data))
+        return out
+
+    def tonemap_hdr_device(self, n, d_rgb, d_out_rgba, d_exposure=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_tonemap_hdr: DEVICE buffers (d_rgb n x 3 floats, d_out_rgba n x 4 bytes; d_exposure: the record, or None), enqueued on
+        `stream`"""
+        tm = self._tonemap_ref(tonemap, exposure)
+        n = _check_int("n", n, "an integer in [1, 2^30]", 1, 1 << 30)
+        self._chk(self._L.vrt_tonemap_hdr(self._h, n, d_rgb, tm, d_exposure, d_out_rgba, stream))
+
+    def accum_resolve_hdr_metered(self, meter=None, tonemap="clamp", exposure=1.0, state=None):
+        """An HDR accumulation resolved, metered and tone mapped by the fresh record (vrt_accum_resolve_hdr_metered) -> (the new
+        record as a dict, rgb float32[H,W,3], rgba8[H,W,4], the histogram uint32[METER_BINS])."""
+        tm = self._tonemap_ref(tonemap, exposure)
+        m = _meter(meter)
+        e = _exposure(state)
+        h, w = self._accum_hw()
+        rgb, rgba = _zeros(h, w, "rgb", "rgba8")
+        hist = np.zeros(METER_BINS, np.uint32)
+        self._chk(self._L.vrt_accum_resolve_hdr_metered(self._h, _ref(m), tm, C.byref(e), rgb.ctypes.data, rgba.ctypes.data, hist.ctypes.data))
+        return _exposure_dict(e), rgb, rgba, hist
+
+    def accum_resolve_hdr_metered_device(self, d_exposure, d_histogram, d_rgb, d_rgba, meter=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_metered_device: DEVICE buffers (d_exposure: the record, required; d_histogram, d_rgb, d_rgba: each
+        may be None), enqueued on `stream`"""
+        tm = self._tonemap_ref(tonemap, exposure)
+        self._chk(self._L.vrt_accum_resolve_hdr_metered_device(self._h, _ref(_meter(meter)), tm, d_exposure, d_histogram, d_rgb, d_rgba, stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -20,6 +20,8 @@
 //                      and the launches of one step of it (launch_accum_step, called by enqueue())
 //   vrt_guides.cpp     guide planes (vrt_accum_guides, vrt_guide_rays): the accumulation's guide state, the samples it still lacks,
 //                      their launch through enqueue() (an AccumStep with `guides`), the resolve; the stateless ray-batch form
+//   vrt_meter.cpp      light metering (vrt_meter_hdr, vrt_tonemap_hdr, vrt_accum_resolve_hdr_metered): validation, the launches, the
+//                      host forms' staging; the rule itself is vrt_meter.h's, shared with the finishing kernel
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts; its shard and band
@@ -155,6 +157,8 @@ struct vrt_ctx {
     GuideFrame guide_frame;
     // the staging of vrt_upsample_hdr_host (vrt_upsample.cpp, where its planes are declared)
     DevBuf<float> d_upsample;
+    // the staging of vrt_meter_hdr_host and vrt_tonemap_hdr_host (vrt_meter.cpp, where their planes are declared)
+    DevBuf<float> d_meter;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     DevBuf<void> d_query;
     // device buffers behind vrt_shade_rays (vrt_rays.cpp)

@@ -9,6 +9,7 @@
 #include "vrt_filter.h"
 #include "vrt_temporal.h"
 #include "vrt_upsample.h"
+#include "vrt_meter.h"
 
 namespace vrt {
 namespace launch {
@@ -200,6 +201,13 @@ hipError_t temporal_pass_mom(const temporal::ArgsMom &q, hipStream_t s);
 // vrt_launch_upsample.hip: the guided upsampling pass (vrt_upsample.hip.h), a whole HIGH frame, one lane per high pixel, one 8 x 8
 // tile per wave: U1-U6 of include/vrt.h vrt_upsample_hdr from q's low image and planes and its high planes.
 hipError_t upsample_pass(const upsample::Args &q, hipStream_t s);
+
+// vrt_launch_meter.hip: light metering (vrt_meter.hip.h). meter_histogram: E1-E3 of include/vrt.h vrt_meter_hdr, the rows of q into
+// q.histogram, which the caller has zeroed on s, on a capped grid; meter_finish: E4-E8, the histogram -> the record, one workgroup;
+// meter_tonemap: E9, q.n pixels on a capped grid; vec: q.rgb and q.out_rgba are both multiples of 16.
+hipError_t meter_histogram(const meter::HistArgs &q, hipStream_t s);
+hipError_t meter_finish(const meter::FinishArgs &q, hipStream_t s);
+hipError_t meter_tonemap(const meter::ToneArgs &q, bool vec, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt
