@@ -1430,6 +1430,82 @@ int vrt_accum_resolve_hdr_metered(vrt_ctx *ctx, const vrt_meter *m, const vrt_to
                                   uint8_t *out_rgba8, uint32_t *out_histogram);
 int vrt_accum_resolve_hdr_metered_device(vrt_ctx *ctx, const vrt_meter *m, const vrt_tonemap *tm, void *d_exposure, void *d_histogram,
                                          void *d_rgb, void *d_rgba8, void *stream);
+/* EXTENSION: bloom -- the glare of an HDR frame, on the device, between metering and the tone map. Every HDR route ends in
+ * unorm8(tone_map(x, op, e)): a lamp of radiance 40 and one of radiance 4 both store 255 with a razor edge. These calls spread what
+ * lies above a threshold over the neighbours before the tone map clips it: a bright pass, a down-sampled pyramid of L levels, an
+ * up-sampling chain that adds the levels up again, and a composite fused with the tone map, which reads the exposure record
+ * vrt_meter_hdr left on the device. 2 L kernel launches, no host round trip, no context state.
+ *
+ * The rule. float32 wherever a value is a float, every operation rounded on its own, nothing contracted; h(c), min and max are those
+ * of vrt_accum_keep_hdr point 1 and vrt_meter_hdr; / is the correctly rounded division. A pyramid pixel is four floats (r, g, b, w).
+ *  B0. Sizes. Level 0 is the W x H input; level l = 1..L is w_l = (w_{l-1} + 1) >> 1 by h_l = (h_{l-1} + 1) >> 1. A level may be
+ *      1 x 1, and the levels after it stay 1 x 1. 1 <= L <= VRT_BLOOM_MAX_LEVELS.
+ *  B1. Exposure of the bright pass. eb = min(tm->exposure * E, 3.402823466e38f) with E the device record's exposure: E9's e. With no
+ *      record eb = tm->exposure; with a NULL tm, tm->exposure is 1. With a record the threshold is therefore in display units: 1.0 is
+ *      what the tone map is about to clip.
+ *  B2. Bright pass, per input pixel c: x_ch = h(c_ch); Y = E1's luminance of x; Ye = min(Y * eb, 3.402823466e38f);
+ *      d = Ye - threshold. If knee > 0: s = min(max(d + knee, 0), knee + knee) and soft = (s * s) / (4.0f * knee); otherwise soft = 0.
+ *      a = max(max(soft, d), 0); g = min(a / max(Ye, 0x1p-16f), 1.0f); b_ch = x_ch * g; w = 1.
+ *  B3. Firefly weights (VRT_BLOOM_KARIS): w = 1.0f / (1.0f + Y(b)) with E1's luminance of b, then b_ch = b_ch * w. The weight
+ *      travels as the fourth component through level 1 only.
+ *  B4. Down-sample. Destination (X, Y) of level l reads the 4 x 4 block of level l - 1 whose columns are
+ *      clamp(2X + o, 0, w_{l-1} - 1) for o = -1, 0, 1, 2, the rows likewise. The weights are [1 3 3 1] (x) [1 3 3 1] / 64, evaluated
+ *      with additions only: T(a0, a1, a2, a3) is p0 = a0 + a1, p1 = a1 + a2, p2 = a2 + a3, T = (p0 + p1) + (p1 + p2). r_j = T of
+ *      row j's four columns in ascending order, for the four rows in ascending order; v = T(r_0, r_1, r_2, r_3) * 0.015625f, per
+ *      component. Level 1 reads B2 / B3's pixels. Level 1 with KARIS stores D_1.ch = v.ch / v.w and w = 1; every other level stores v.
+ *  B5. Up-sample up(S, w, h) of an image S of w' x h' to w x h. For destination column x: nx = x >> 1 and
+ *      fx = clamp(nx + ((x & 1) ? 1 : -1), 0, w' - 1); rows likewise. lerp(far, near) = ((far + near) + (near + near)) * 0.25f;
+ *      t(row) = lerp(S[row][fx], S[row][nx]); up = lerp(t(fy), t(ny)).
+ *  B6. Chain. U_L = D_L; for l = L-1 .. 1: U_l = D_l + up(U_{l+1}, w_l, h_l).
+ *  B7. Composite. B = up(U_1, W, H) * invL with invL = 1.0f / (float)L; f_ch = h(x_ch + intensity * B_ch).
+ *  B8. Outputs. out_rgb is f; out_rgba8 is unorm8(tone_map(f_ch, op, e)) with E9's e, alpha 255.
+ * What follows from the weights: with threshold = knee = 0, no KARIS and eb = 1 a constant image (k, k, k), k dyadic, gives every D_l
+ * and B exactly k. Scaling the image, the threshold and the knee by 2^j scales B and f exactly wherever no clamp of h and not the
+ * 2^-16 floor is met. One pixel of value v in a black frame, away from the border, gives 4^l * sum(D_l) == v exactly.
+ *
+ * vrt_bloom_default          levels 5, VRT_BLOOM_KARIS, threshold 1, knee 0.5, intensity 0.2.
+ * vrt_bloom_workspace_bytes  the bytes of d_workspace for a width x height frame and `levels`: 16 per pyramid pixel of the levels
+ *                            1..L, each level rounded up to 256 bytes. 0 for arguments vrt_bloom_hdr would refuse. Needs no context.
+ * vrt_bloom_hdr              DEVICE pointers, stream-ordered (NULL: the context's), stateless as vrt_meter_hdr is: it reads no context
+ *                            state, keeps no scratch and takes no profiling slot. d_rgb: width x height pixels of 3 floats.
+ *                            b == NULL: the default. tm as in vrt_tonemap_hdr. d_exposure: the record, or NULL for none; it is only
+ *                            read. d_workspace: vrt_bloom_workspace_bytes bytes of the caller's, a multiple of 16; it needs no
+ *                            initialising, the call never reads a word of it that it has not written, and its contents afterwards
+ *                            mean nothing. d_out_rgb (3 floats per pixel) and d_out_rgba8 (4 bytes per pixel): either may be NULL,
+ *                            not both. VRT_E_INVALID: a NULL d_rgb or d_workspace, or both outputs NULL; a workspace that is no
+ *                            multiple of 16, another pointer that is no multiple of 4; an output equal to d_rgb, d_exposure, the
+ *                            workspace or the other output; a frame size vrt_denoise refuses; levels outside
+ *                            1..VRT_BLOOM_MAX_LEVELS; unknown flags; not 0 <= knee <= threshold <= 65504; intensity not finite or
+ *                            outside [0, 65504]; a tone map vrt_accum_resolve_hdr refuses.
+ * vrt_bloom_hdr_host         the same through HOST buffers, synchronous, on the context's stream; e: the record, or NULL.
+ * vrt_accum_resolve_hdr_bloomed  an HDR accumulation resolved as vrt_accum_resolve_hdr_device resolves it, into the accumulation's own
+ *                            stage; metered as vrt_accum_resolve_hdr_metered meters it into the record io; bloomed and tone mapped by
+ *                            the fresh record. io == NULL skips the metering and there is no record (eb = e = tm->exposure). HOST
+ *                            buffers, synchronous; out_rgb [H][W][3] (f) and out_rgba8 [H][W][4]: either may be NULL, not both. State
+ *                            errors, ordering and the parameter checks of m are vrt_accum_resolve_hdr_metered's; those of b and tm are
+ *                            vrt_bloom_hdr's. The sums are never touched. No profiling slot is taken.
+ * vrt_accum_resolve_hdr_bloomed_device  the same with the record (NULL: no metering), f and the bytes in the caller's DEVICE memory
+ *                            (pointers multiples of 4, no two equal), enqueued on `stream` (NULL: the context's).
+ * Not provided: lens dirt, streaks, anamorphic shapes; bloom inside the filter, temporal, upsample and display passes (take their
+ * float output and call vrt_bloom_hdr); frames, views, shards and vrt_multi. */
+#define VRT_BLOOM_MAX_LEVELS 8
+#define VRT_BLOOM_KARIS 1u
+struct vrt_bloom {
+    int32_t levels;      /* L, 1..VRT_BLOOM_MAX_LEVELS; default 5 */
+    uint32_t flags;      /* VRT_BLOOM_KARIS or 0; default VRT_BLOOM_KARIS */
+    float threshold, knee, intensity;   /* 0 <= knee <= threshold <= 65504, 0 <= intensity <= 65504; default 1, 0.5, 0.2 */
+};
+typedef struct vrt_bloom vrt_bloom;
+void vrt_bloom_default(vrt_bloom *b);
+size_t vrt_bloom_workspace_bytes(int width, int height, int levels);
+int vrt_bloom_hdr(vrt_ctx *ctx, int width, int height, const void *d_rgb, const vrt_bloom *b, const vrt_tonemap *tm,
+                  const void *d_exposure, void *d_workspace, void *d_out_rgb, void *d_out_rgba8, void *stream);
+int vrt_bloom_hdr_host(vrt_ctx *ctx, int width, int height, const float *rgb, const vrt_bloom *b, const vrt_tonemap *tm,
+                       const vrt_exposure *e, float *out_rgb, uint8_t *out_rgba8);
+int vrt_accum_resolve_hdr_bloomed(vrt_ctx *ctx, const vrt_meter *m, const vrt_bloom *b, const vrt_tonemap *tm, vrt_exposure *io,
+                                  float *out_rgb, uint8_t *out_rgba8);
+int vrt_accum_resolve_hdr_bloomed_device(vrt_ctx *ctx, const vrt_meter *m, const vrt_bloom *b, const vrt_tonemap *tm, void *d_exposure,
+                                         void *d_rgb, void *d_rgba8, void *stream);
 /* EXTENSION: one whole frame of the reference's loop -- dispatch (src/main.cpp:946) then the display pass
  * (:951-967) -- with both intermediate images kept on the device; only what the caller asks for comes back.
  * HOST pointers, synchronous. out_shown_rgba8 receives what the reference puts on screen; out_rgba8 and

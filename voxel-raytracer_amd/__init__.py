@@ -78,6 +78,11 @@ class Exposure(C.Structure):
     _fields_ = [("exposure", C.c_float), ("metered", C.c_float), ("window", C.c_uint32), ("frames", C.c_uint32)]
 
 
+class Bloom(C.Structure):
+    """include/vrt.h vrt_bloom"""
+    _fields_ = [("levels", C.c_int32), ("flags", C.c_uint32), ("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float)]
+
+
 TEMPORAL_KEYS = ("offset_x", "offset_y", "max_history", "alpha_min", "alpha_moments_min", "normal_min", "depth_tol")
 TEMPORAL_MOM_KEYS = TEMPORAL_KEYS + ("measured_below", "search")
 _TEMPORAL_INTS = ("max_history", "measured_below", "search")   # the keys that are int32 fields; the others are floats
@@ -91,6 +96,8 @@ FILTER_DEMODULATE = 1    # include/vrt.h VRT_FILTER_DEMODULATE
 UPSAMPLE_MAX_FACTOR = 4  # include/vrt.h VRT_UPSAMPLE_MAX_FACTOR
 UPSAMPLE_DEMODULATE = 1  # include/vrt.h VRT_UPSAMPLE_DEMODULATE
 METER_BINS = 256         # include/vrt.h VRT_METER_BINS
+BLOOM_MAX_LEVELS = 8     # include/vrt.h VRT_BLOOM_MAX_LEVELS
+BLOOM_KARIS = 1          # include/vrt.h VRT_BLOOM_KARIS
 
 
 class VrtError(RuntimeError):
@@ -194,6 +201,42 @@ def meter_resolve(hist, meter=None, state=None):
     if r != 0:
         raise VrtError(f"vrt_meter_resolve: error {r} (the counts sum to more than 2^30)")
     return _exposure_dict(e)
+
+
+def default_bloom():
+    """vrt_bloom_default as a dict: {"levels", "karis", "threshold", "knee", "intensity"} -- the keys the `bloom` argument of
+    Context.bloom_hdr and Context.accum_resolve_hdr_bloomed takes. Needs no device."""
+    b = Bloom()
+    hip_lib().vrt_bloom_default(C.byref(b))
+    return {"levels": int(b.levels), "karis": bool(b.flags & BLOOM_KARIS), "threshold": float(b.threshold), "knee": float(b.knee),
+            "intensity": float(b.intensity)}
+
+
+def _bloom(bloom):
+    """None (the NULL vrt_bloom: vrt_bloom_default) or a dict with any of default_bloom()'s keys -> Bloom or None; ValueError for an
+    unknown key, levels outside 1..BLOOM_MAX_LEVELS, a karis that is no flag, not 0 <= knee <= threshold <= 65504 or an intensity
+    outside [0, 65504]"""
+    if bloom is None:
+        return None
+    d = default_bloom()
+    unknown = set(bloom) - set(d)
+    if unknown:
+        raise ValueError(f"bloom: unknown keys {sorted(unknown)}")
+    d.update(bloom)
+    levels = _check_int("levels", d["levels"], f"an integer in [1, {BLOOM_MAX_LEVELS}]", 1, BLOOM_MAX_LEVELS)
+    karis = _check_flag("karis", d["karis"], "a bool")
+    threshold = _check_f32("threshold", d["threshold"], lambda x: 0.0 <= x <= 65504.0, "in [0, 65504]")
+    knee = _check_f32("knee", d["knee"], lambda x: 0.0 <= x <= threshold, "in [0, threshold]")
+    intensity = _check_f32("intensity", d["intensity"], lambda x: 0.0 <= x <= 65504.0, "in [0, 65504]")
+    return Bloom(levels, BLOOM_KARIS if karis else 0, threshold, knee, intensity)
+
+
+def bloom_workspace_bytes(width, height, levels):
+    """vrt_bloom_workspace_bytes: the bytes of the workspace Context.bloom_hdr_device needs for a width x height frame and `levels`
+    levels; 0 for arguments the call would refuse. Needs no device."""
+    for name, v in (("width", width), ("height", height), ("levels", levels)):
+        _check_int(name, v, "an int32", -(1 << 31), (1 << 31) - 1)
+    return int(hip_lib().vrt_bloom_workspace_bytes(width, height, levels))
 
 
 def _temporal_struct(kind, temporal=None, prev_camera=None):
@@ -366,7 +409,7 @@ _p, _s = C.c_void_p, C.c_char_p   # void *: handles, streams, host and device bu
 _pi, _pi32, _pu32, _pu8, _pf, _pl, _psz, _pp = (C.POINTER(t) for t in (C.c_int, C.c_int32, C.c_uint32, C.c_uint8, C.c_float, C.c_long,
                                                                        C.c_size_t, C.c_void_p))
 _tm, _flt, _fltv, _tmp, _tmpm, _ups = (C.POINTER(t) for t in (Tonemap, Filter, FilterVar, Temporal, TemporalMom, Upsample))
-_mtr, _exp = C.POINTER(Meter), C.POINTER(Exposure)
+_mtr, _exp, _blm = C.POINTER(Meter), C.POINTER(Exposure), C.POINTER(Bloom)
 _RECORDS_OUT = [_pp, _psz]        # uint32_t **records, size_t *n_records
 
 HOST_API = {
@@ -533,6 +576,12 @@ HIP_API = {
     "vrt_tonemap_hdr_host": (_i, [_p, _sz, _p, _tm, _exp, _p]),
     "vrt_accum_resolve_hdr_metered": (_i, [_p, _mtr, _tm, _exp] + [_p] * 3),
     "vrt_accum_resolve_hdr_metered_device": (_i, [_p, _mtr, _tm] + [_p] * 5),
+    "vrt_bloom_default": (None, [_blm]),
+    "vrt_bloom_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vrt_bloom_hdr": (_i, _FRAME + [_p, _blm, _tm] + [_p] * 5),
+    "vrt_bloom_hdr_host": (_i, _FRAME + [_p, _blm, _tm, _exp, _p, _p]),
+    "vrt_accum_resolve_hdr_bloomed": (_i, [_p, _mtr, _blm, _tm, _exp, _p, _p]),
+    "vrt_accum_resolve_hdr_bloomed_device": (_i, [_p, _mtr, _blm, _tm] + [_p] * 4),
     "vrt_dispatch_frame": (_i, _FRAME + [_i, _p, _p, _p]),
     "vrt_set_profiling": (_i, [_p, _i]),
     "vrt_set_profiling_stride": (_i, [_p, _i]),
@@ -2072,6 +2121,50 @@ class Context:
         may be None), enqueued on `stream`"""
         tm = self._tonemap_ref(tonemap, exposure)
         self._chk(self._L.vrt_accum_resolve_hdr_metered_device(self._h, _ref(_meter(meter)), tm, d_exposure, d_histogram, d_rgb, d_rgba, stream))
+
+    # Bloom (include/vrt.h vrt_bloom_hdr, vrt_accum_resolve_hdr_bloomed), as the entry points of csrc/vrt_bloom.cpp: the struct from
+    # one builder (_bloom), the record as the dict meter_resolve returns
+    def bloom_hdr(self, rgb, bloom=None, tonemap="clamp", exposure=1.0, state=None):
+        """Bloom through host arrays (vrt_bloom_hdr_host): rgb[H,W,3]; bloom: None (vrt_bloom_default) or a dict with any of
+        default_bloom()'s keys; state: None (no record) or a record as meter_hdr returns it -> (f float32[H,W,3], rgba8[H,W,4])."""
+        b = _bloom(bloom)
+        tm = self._tonemap_ref(tonemap, exposure)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"expected rgb[H,W,3], got {rgb.shape}")
+        e = None if state is None else _exposure(state)
+        out, rgba = _zeros(rgb.shape[0], rgb.shape[1], "rgb", "rgba8")
+        self._chk(self._L.vrt_bloom_hdr_host(self._h, rgb.shape[1], rgb.shape[0], rgb.ctypes.data, _ref(b), tm, _ref(e), out.ctypes.data,
+                                             rgba.ctypes.data))
+        return out, rgba
+
+    def bloom_hdr_device(self, width, height, d_rgb, d_workspace, d_out_rgb, d_out_rgba, d_exposure=None, bloom=None, tonemap="clamp",
+                         exposure=1.0, stream=None):
+        """vrt_bloom_hdr: DEVICE buffers (d_rgb H*W x 3 floats; d_workspace bloom_workspace_bytes() bytes, a multiple of 16, not
+        initialised; d_out_rgb H*W x 3 floats and d_out_rgba H*W x 4 bytes: either may be None, not both; d_exposure: the record,
+        or None), enqueued on `stream`"""
+        w, h = self._frame_size(width, height)
+        tm = self._tonemap_ref(tonemap, exposure)
+        self._chk(self._L.vrt_bloom_hdr(self._h, w, h, d_rgb, _ref(_bloom(bloom)), tm, d_exposure, d_workspace, d_out_rgb, d_out_rgba, stream))
+
+    def accum_resolve_hdr_bloomed(self, meter=None, bloom=None, tonemap="clamp", exposure=1.0, state=None, metering=True):
+        """An HDR accumulation resolved, metered, bloomed and tone mapped by the fresh record (vrt_accum_resolve_hdr_bloomed) -> (the
+        new record as a dict, f float32[H,W,3], rgba8[H,W,4]). metering False: no metering and no record (io == NULL); the record
+        returned is None."""
+        tm = self._tonemap_ref(tonemap, exposure)
+        m, b = _meter(meter), _bloom(bloom)
+        e = _exposure(state) if metering else None
+        h, w = self._accum_hw()
+        rgb, rgba = _zeros(h, w, "rgb", "rgba8")
+        self._chk(self._L.vrt_accum_resolve_hdr_bloomed(self._h, _ref(m), _ref(b), tm, _ref(e), rgb.ctypes.data, rgba.ctypes.data))
+        return (None if e is None else _exposure_dict(e)), rgb, rgba
+
+    def accum_resolve_hdr_bloomed_device(self, d_exposure, d_rgb, d_rgba, meter=None, bloom=None, tonemap="clamp", exposure=1.0, stream=None):
+        """vrt_accum_resolve_hdr_bloomed_device: DEVICE buffers (d_exposure: the record, None: no metering; d_rgb, d_rgba: either may
+        be None, not both), enqueued on `stream`"""
+        tm = self._tonemap_ref(tonemap, exposure)
+        self._chk(self._L.vrt_accum_resolve_hdr_bloomed_device(self._h, _ref(_meter(meter)), _ref(_bloom(bloom)), tm, d_exposure, d_rgb, d_rgba,
+                                                               stream))
 
     def denoise(self, rgba, id_dist):
         """quad.frag's ID-aware blur through host arrays -> rgba8[H,W,4]."""

@@ -22,6 +22,8 @@
 //                      their launch through enqueue() (an AccumStep with `guides`), the resolve; the stateless ray-batch form
 //   vrt_meter.cpp      light metering (vrt_meter_hdr, vrt_tonemap_hdr, vrt_accum_resolve_hdr_metered): validation, the launches, the
 //                      host forms' staging; the rule itself is vrt_meter.h's, shared with the finishing kernel
+//   vrt_bloom.cpp      bloom (vrt_bloom_hdr, vrt_accum_resolve_hdr_bloomed): validation, the 2 L launches of a call, the host form's
+//                      staging; the pyramid's sizes and the workspace's layout are vrt_bloom.h's
 //   vrt_raygen.cpp     per-projection ray-generation tables (pure host arithmetic)
 //   vrt_launch_*.hip   the ONLY files that hold device code: kernel instantiations behind vrt_launch.h
 //   vrt_multi.hip      several devices behind one handle (uses the public API of the per-device contexts; its shard and band
@@ -159,6 +161,8 @@ struct vrt_ctx {
     DevBuf<float> d_upsample;
     // the staging of vrt_meter_hdr_host and vrt_tonemap_hdr_host (vrt_meter.cpp, where their planes are declared)
     DevBuf<float> d_meter;
+    // the staging of vrt_bloom_hdr_host (vrt_bloom.cpp, where its planes are declared): input, record, pyramid, outputs
+    DevBuf<float4> d_bloom;
     // device buffers behind vrt_cast_rays / vrt_find_voxels (vrt_query.cpp)
     DevBuf<void> d_query;
     // device buffers behind vrt_shade_rays (vrt_rays.cpp)

@@ -10,6 +10,7 @@
 #include "vrt_temporal.h"
 #include "vrt_upsample.h"
 #include "vrt_meter.h"
+#include "vrt_bloom.h"
 
 namespace vrt {
 namespace launch {
@@ -208,6 +209,12 @@ hipError_t upsample_pass(const upsample::Args &q, hipStream_t s);
 hipError_t meter_histogram(const meter::HistArgs &q, hipStream_t s);
 hipError_t meter_finish(const meter::FinishArgs &q, hipStream_t s);
 hipError_t meter_tonemap(const meter::ToneArgs &q, bool vec, hipStream_t s);
+
+// vrt_launch_bloom.hip: bloom (vrt_bloom.hip.h). bloom_down: one level of B4 of include/vrt.h vrt_bloom_hdr, a lane per destination
+// pixel; first: q.rgb through the bright pass (B2, and B3 with karis), else q.src. bloom_up: one step of B6 in place, or with `last`
+// the composite and the tone map (B7, B8).
+hipError_t bloom_down(const bloom::DownArgs &q, bool first, bool karis, hipStream_t s);
+hipError_t bloom_up(const bloom::UpArgs &q, bool last, hipStream_t s);
 
 }  // namespace launch
 }  // namespace vrt
